@@ -6,7 +6,7 @@ query / result buffers already resident in HBM.  The workload is BASELINE.json c
 synthetic index the metric's target is quoted on (k=1500, m=2500, idf_weighting=2).
 
   One process per GPU (launched by torch.distributed.run -- or by this script itself when started bare with --gpus N), and at EVERY N, N = 1 included,
-  BOTH modes of SURVEY.md 8(e) in one line, so that a 1/2/4/8 curve can be read mode by mode:
+  with --full BOTH modes of SURVEY.md 8(e) in one line, so that a 1/2/4/8 curve can be read mode by mode (a plain run: the mode of `value` alone):
     value_replicas      every GPU holds the whole index and serves its own slice of the query stream through srn_predict_batch_device (2^20 evolving sessions
                         per step and GPU), no data-path collective (how the reference scales: replicas + session affinity, src/endpoints/recommend_resource.rs:17-19)
     value_item_sharded  the north star's partitioning: the index ITEM-SHARDED over the N GPUs (owner = hash of the item id), every rank sees the whole
@@ -19,7 +19,18 @@ synthetic index the metric's target is quoted on (k=1500, m=2500, idf_weighting=
   At N > 1 the item-sharded mode is timed twice: first with the exchange of batch i + 1 NOT overlapped with batch i (one communicator busy at a time),
   then overlapped (two communicators in flight) under a watchdog; the line says which run `value_item_sharded` comes from and carries both.
 
-Order of events (no timing counts before parity):
+A plain run (`bench.py --gpus N --steps K --warmup W`) does only what the headline figure needs: it generates the workload, builds the index, warms up, times the K steps,
+writes the last step's outputs if `--dump-outputs DIR` is given, and prints the line (metric, value, unit, higher_is_better, dtype, ms_per_step, ...).  At N = 1 that is
+the replicas mode alone; at N > 1 the item-sharded mode alone (its non-overlapped, overlapped and streaming runs: `value` is the best of them), the unsharded index kept
+resident as its posting lists as in a --full run.  Everything else -- the parity gate, the top-n property check, the roofline and its counter passes, the batch-size
+sweep, the long-session and single-query latencies, the CPU baseline, the replicas mode at N > 1, the group of one shard and the 8-shard block at N = 1 -- runs with
+`--full` only, in the order below.
+
+  --dump-outputs DIR  after the timed steps: the rows the timed path wrote in its last step, as DIR/ids.npy, DIR/scores.npy, DIR/counts.npy (float64; ids are
+                      48-bit and exact; slots past a row's count are 0) and DIR/rows.npy (which rows of the batch: all of them up to 65 536 rows, above that a
+                      fixed seeded sample of 65 536).  Same arguments, same inputs: two builds can be compared output for output.
+
+Order of events with --full (no timing counts before parity):
   1. PARITY GATE  `--parity` queries drawn uniformly over batch 0 (seeded permutation; the launch's first and last 32 always among them) FROM THE ROWS THE FULL-SIZE
                   LAUNCH WROTE, through the product call of every mode that is timed, against the canonical CPU oracle (the closed form of DESIGN.md section 1: a valid
                   refinement of the reference, NOT its literal tie behaviour -- on the reference's own example 13-17 % of the queries differ from the literal loops in which
@@ -131,6 +142,9 @@ def main():
     ap.add_argument("--no-sweep", action="store_true", help="skip the batch-size sweep")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU time of the baseline sample")
     ap.add_argument("--traffic-file", default=None, help="profiles/*_traffic_<config>.json from the PMC passes (default: newest match)")
+    ap.add_argument("--full", action="store_true", help="besides the headline: parity gate, property check, roofline (with its counter passes), sweeps, latencies, CPU baseline "
+                    "and the other mode / shard configurations (the --no-* options above switch parts of it off); a plain run times the headline alone")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write the last timed step's results (ids, scores, counts, rows; float64 .npy) under DIR")
     args = ap.parse_args()
 
     rehearse = args.rehearse > 1 or os.environ.get("SRN_BENCH_REHEARSE") == "1"
@@ -192,8 +206,14 @@ def main():
 
     inter, n_items, k, m, idfw = synth.CONFIGS[args.config]
     how_many, last_items = synth.HOW_MANY, synth.LAST_ITEMS
-    mode = args.mode if args.mode != "auto" else "both"
+    if args.mode != "auto":
+        mode = args.mode
+    elif args.full:
+        mode = "both"
+    else:       # a plain run times the mode of the headline alone
+        mode = "replicas" if world == 1 else "item-sharded"
     do_rep, do_shard = mode in ("replicas", "both"), mode in ("item-sharded", "both")
+    keep_index = do_rep or args.mode == "auto"   # the unsharded index stays resident as the item-sharded phase's posting lists, plain or --full alike
     t0 = time.time()
     off, items, ts = synth.training_sessions(inter, n_items)
     if args.tie_per_second > 1:
@@ -319,6 +339,30 @@ def main():
         elapsed = D.max_over_ranks(time.perf_counter() - t0, ctl_dev)
         return elapsed, np.array([a.elapsed_time(b) for a, b in ev])
 
+    # --dump-outputs: the mode whose line is printed writes what its last timed step computed (rank 0's rows)
+    dump_from = "replicas" if (do_rep and (world == 1 or not do_shard)) else "item-sharded"
+    DUMP_ROWS = 1 << 16           # 65 536 rows of 21 ids + 21 scores in float64: 22 MB, under the 64 MB the dump may take
+
+    def dump_outputs(d_ids, d_sc, d_cnt, B):
+        """The rows of a B-query launch (device tensors: int64 ids, float64 scores, int32 counts) as float64 .npy files under --dump-outputs: every row up to
+        DUMP_ROWS rows, above that a fixed seeded sample of DUMP_ROWS of them (rows.npy says which).  Slots past a row's count are written as 0."""
+        if not args.dump_outputs:
+            return
+        torch.cuda.synchronize()
+        rows = np.arange(B, dtype=np.int64) if B <= DUMP_ROWS else np.sort(np.random.default_rng(synth.SEED).choice(B, DUMP_ROWS, replace=False))
+        sel = torch.from_numpy(rows).to(dev)
+        ids = d_ids.view(B, how_many).index_select(0, sel).cpu().numpy().view(np.uint64)
+        sc = d_sc.view(B, how_many).index_select(0, sel).cpu().numpy()
+        cnt = d_cnt.view(B).index_select(0, sel).cpu().numpy().view(np.uint32)
+        n = np.where(cnt == 0xFFFFFFFF, 0, np.minimum(cnt, how_many)).astype(np.int64)
+        inside = np.arange(how_many)[None, :] < n[:, None]
+        if ids[inside].size and int(ids[inside].max()) >= (1 << 53):
+            raise RuntimeError("--dump-outputs: an item id above 2^53 has no exact float64")
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in (("ids", np.where(inside, ids, 0).astype(np.float64)), ("scores", np.where(inside, sc, 0.0)),
+                        ("counts", cnt.astype(np.float64)), ("rows", rows.astype(np.float64))):
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
+
     # =========================== item-sharded index over the N GPUs (srn_shard_group_*, RCCL inside the library) ===========================
     shard_steps = args.shard_steps or args.steps
     pending = {"line": None}      # what the overlap watchdog prints if the overlapped run never comes back: the line built on the non-overlapped run
@@ -337,7 +381,7 @@ def main():
         postings = None
         bq_mean = None
         resident = {"shard": int(shard.info["device_bytes"]), "unsharded_index_kept_for_the_replicas_phase": int(index.info["device_bytes"]) if (index is not None and do_rep) else 0, "replicated_postings": 0}
-        if rank == 0 and index is not None:           # (the roofline's per-query byte counters come from the unsharded index: taken before it may be let go below)
+        if rank == 0 and index is not None and args.full:   # (the roofline's per-query byte counters come from the unsharded index: taken before it may be let go below)
             nstat = min(Bs, 8192)
             dbg = sa.predict_batch_debug(index, (sbatches[0][2][:sbatches[0][3][nstat]], sbatches[0][3][:nstat + 1]), k, m, how_many, False, neighbours=False)
             bq_mean = float(algorithmic_bytes(dbg["stats"]).mean())
@@ -348,8 +392,10 @@ def main():
             # index leaves HBM, so that a rank holds what an item-sharded deployment holds: its shard + the replicated lists
             if index is None:
                 raise RuntimeError("the neighbours pipeline needs the unsharded index on every rank to cut the postings view from")
-            if do_rep:
+            if keep_index:
                 postings = index
+                if not do_rep:
+                    resident["replicated_postings"] = int(index.info["device_bytes"])
             else:
                 postings = SH.postings_view(index, device=local_rank)
                 resident["replicated_postings"] = int(postings.info["device_bytes"])
@@ -373,7 +419,7 @@ def main():
         # the non-overlapped form first wherever there are peers: one communicator busy at a time, nothing in it that can wait on a peer's other collective
         group.set_overlap(world == 1)
         s_parity = 0
-        if args.parity > 0:                                           # (a collective call: every rank runs it, rank 0 checks)
+        if args.parity > 0 and args.full:                             # (a collective call: every rank runs it, rank 0 checks)
             sstep(0)
             torch.cuda.synchronize()
             if rank == 0:
@@ -397,7 +443,7 @@ def main():
                     "per_q": {kk: (st1[kk] - st0[kk]) / nqs for kk in ("bytes_head", "bytes_counts", "bytes_lists", "bytes_results", "bytes_lists_max_rank", "bytes_neighbours")}}
 
         def shard_line_of(run, probe):
-            ach = bq_mean * Bs / (run["ms_per_step"] * 1e-3) / 1e9
+            ach = bq_mean * Bs / (run["ms_per_step"] * 1e-3) / 1e9 if bq_mean is not None else None
             per_q = run["per_q"]
             line = dict(common)
             line.update({
@@ -418,16 +464,20 @@ def main():
                 "roofline": {"bound": "hbm", "kernel": "item-sharded step: list exchange + unsharded kernels over the rank's row fragments + top-n merge", "achieved": ach,
                              "peak": HBM_PEAK_GBS * world, "unit": "GB/s", "frac": ach / (HBM_PEAK_GBS * world), "traffic": None,
                              "algorithmic_bytes_per_query": bq_mean, "queries_per_launch": Bs,
-                             "note": "the same algorithmic bytes as the unsharded path (every datum is touched once, on the shard that owns it) against the whole step and N x 8 TB/s"},
+                             "note": "the same algorithmic bytes as the unsharded path (every datum is touched once, on the shard that owns it) against the whole step and N x 8 TB/s"} if ach is not None else None,
                 "exchange_bytes_per_query_rank0": {"cuts_all_reduce": per_q["bytes_head"], "kept_counts_all_gather": per_q["bytes_counts"], "list_prefixes_sent": per_q["bytes_lists"],
                                                    "list_prefixes_fullest_rank": per_q["bytes_lists_max_rank"], "neighbour_lists_all_gather": per_q["bytes_neighbours"],
                                                    "topn_all_gather": per_q["bytes_results"]},
                 "latency": {"step_ms_p50": run["step_ms_p50"], "step_ms_p90": run["step_ms_p90"]},
                 "parity_checked": s_parity, "parity_checked_positions": "uniform over batch", "queries_served_last_step": run["queries_served_last_step"], "timed_batches": run["timed_batches"]})
+            if ach is None:          # (a plain run: no per-query byte counters, no roofline)
+                del line["roofline"]
             return line
 
         first = one_run(world == 1)
         if world == 1:
+            if rank == 0 and dump_from == "item-sharded":
+                dump_outputs(s_out[0], s_out[1], s_out[2], Bs)
             return (shard_line_of(first, None) if rank == 0 else None), sbatches
         # N > 1: the overlapped form (two communicators in flight: batch i + 1's exchange beside batch i's kernels and result gather) under a watchdog.  If it never comes
         # back, the line of the non-overlapped run is printed from the watchdog and the process leaves: a SCALE run cannot end without a line.
@@ -477,6 +527,8 @@ def main():
                 probe["streaming_non_overlapped"] = {"error": repr(e)[:300]}
             wd3.cancel()
         pending["line"] = None
+        if rank == 0 and dump_from == "item-sharded":       # (every run's last step served the same batch; the streaming run checks that its rows equal the gather form's)
+            dump_outputs(s_out[0], s_out[1], s_out[2], Bs)
         return (shard_line_of(best, probe) if rank == 0 else None), sbatches
 
     def measure_traffic_now(B):
@@ -540,16 +592,34 @@ def main():
 
         # ---- 1. parity gate (rank 0; the other ranks wait at the barrier below) --------------------------------------------
         parity_checked = 0
-        if rank == 0 and args.parity > 0:
+        if rank == 0 and args.parity > 0 and args.full:
             pos = gate_positions(B, args.parity)
             step(0)                              # the FULL-SIZE launch of batch 0, the one the timed region repeats: the checked rows are rows IT wrote
             torch.cuda.synchronize()
             parity_checked = gate(out_ids.cpu().numpy().view(np.uint64).reshape(B, how_many)[pos], out_sc.cpu().numpy().reshape(B, how_many)[pos],
                                   out_cnt.cpu().numpy().view(np.uint32)[pos], flat0, qo0, pos, "whole index")
         sa.reserve(index, B, last_items, k, m, how_many, False, stream.cuda_stream)   # size the stream's workspace up front (srn_index_reserve): no call of the run allocates
-        index.kernel_timing(True)      # per-kernel HIP events on the launch stream for the timed region (the roofline's launch duration); off again for the sweeps below
+        if args.full:
+            index.kernel_timing(True)  # per-kernel HIP events on the launch stream for the timed region (the roofline's launch duration); off again for the sweeps below
         elapsed, step_ms = timed(step)
+        if rank == 0 and dump_from == "replicas":
+            dump_outputs(out_ids, out_sc, out_cnt, B)
         served = int((out_cnt.cpu().numpy().view(np.uint32) != 0xFFFFFFFF).sum())
+        if not args.full:
+            if rank != 0:
+                return None
+            return dict(common, **{
+                "value": args.gpus * args.steps * B / elapsed, "ms_per_step": elapsed / args.steps * 1e3, "scaling": "weak",
+                "config": {"workload": "BASELINE configs[2]: synthetic %d interactions / %d items, k=%d m=%d idf_weighting=%g "
+                                       "last_items=%d how_many=%d" % (inter, n_items, k, m, idfw, last_items, how_many)
+                                       if args.config == "cfg3" else "synth.CONFIGS[%s]" % args.config,
+                           "name": args.config, "batch_per_gpu": B, "query_pool_batches": args.pool,
+                           "parallelism": "query-sharded replicas x%d (no data-path collective)" % args.gpus,
+                           "setup_s": {"generate": round(t_gen, 2), "index_build_upload": round(t_build, 2), "index_builder": args.builder if avro is None else "avro loader"},
+                           "index": "csr (built by this library)" if avro is None else "avro (pre-built: VMISIndex::new, vmis_index.rs:85-314)"},
+                "latency": {"step_ms_p50": float(np.percentile(step_ms, 50)), "step_ms_p90": float(np.percentile(step_ms, 90))},
+                "queries_served_last_step": served,
+                "_parity_checked": 0, "_props_ok": None, "_B": B})
         # size-independent properties of the WHOLE last batch (the oracle gate above covers 2 048 queries): every row is a valid top-n list --
         # count <= n, scores positive-or-not but non-increasing, equal scores in ascending id order, no item twice
         cnt = out_cnt.to(torch.int64)
@@ -1000,7 +1070,7 @@ def main():
                 line["cpu_baseline"] = result["cpu_baseline"]
             else:
                 cpu = None
-                if world == 1 and not args.no_cpu_baseline and sb is not None:
+                if world == 1 and args.full and not args.no_cpu_baseline and sb is not None:
                     cores = usable_cores()
                     n_cpu = int(min(args.shard_batch, 4096))
                     r = oracle_index().predict_batch("literal", sb[0][2][:sb[0][3][n_cpu]], sb[0][3][:n_cpu + 1], k, m, how_many, False, threads=cores, want_results=False)
@@ -1021,6 +1091,7 @@ def main():
         else:
             line = dict(common, value=None, value_mode=None, item_sharded_error=shard_error)
         line["value_replicas"], line["value_item_sharded"] = v_rep, v_sh
+        line["full"] = bool(args.full)
         return line
 
     shard_line, shard_error, sb = None, None, None
@@ -1044,7 +1115,7 @@ def main():
             shard_error = repr(e)
         wd.cancel()
     g8 = None
-    if rank == 0 and world == 1 and index is not None and not args.no_local_g8 and args.config in ("cfg3", "cfg2", "tiny", "small"):
+    if rank == 0 and world == 1 and index is not None and args.full and not args.no_local_g8 and args.config in ("cfg3", "cfg2", "tiny", "small"):
         try:
             g8 = local_g8_block()
         except Exception as e:

@@ -1,5 +1,5 @@
-"""Generates tests/golden/example_golden.npz from the reference's example data -- run in the build
-container only (needs /root/reference/assets/example/example.zip; the GPU box has no /root/reference).
+"""Generates tests/golden/example_golden.npz from the reference's example data (assets/example of the
+reference repository: its train.txt and test.txt, as shipped, are tests/golden/example_sessions.zip).
 
 What is stored is DATA: the training sessions as parsed by the oracle's restatement of read_from_file
 (src/vmisknn/vmis_index.rs:591-686), the 931 evaluator queries of test.txt (src/bin/evaluator.rs:46-56)

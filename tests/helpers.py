@@ -6,16 +6,12 @@ import zipfile
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REFERENCE_ZIP = "/root/reference/assets/example/example.zip"
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-
-
-def have_reference_assets():
-    return os.path.exists(REFERENCE_ZIP)
+EXAMPLE_ZIP = os.path.join(GOLDEN, "example_sessions.zip")   # the reference's example data set (assets/example): train.txt and test.txt as shipped
 
 
 def extract_example(tmpdir):
-    with zipfile.ZipFile(REFERENCE_ZIP) as z:
+    with zipfile.ZipFile(EXAMPLE_ZIP) as z:
         z.extractall(tmpdir)
     return str(tmpdir)
 

@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -25,7 +26,7 @@ def _run(args, timeout=600):
 
 @pytest.mark.parametrize("world", [2, 3])
 def test_rehearsal_of_the_multi_gpu_line(world):
-    line = _run(["--rehearse", str(world), "--steps", "2", "--warmup", "1", "--config", "tiny", "--batch", "8192", "--shard-batch", "4096", "--no-sweep", "--cpu-seconds", "1"])
+    line = _run(["--full", "--rehearse", str(world), "--steps", "2", "--warmup", "1", "--config", "tiny", "--batch", "8192", "--shard-batch", "4096", "--no-sweep", "--cpu-seconds", "1"])
     for key in CONTRACT:
         assert key in line, key
     assert line["n_gpus"] == world and line["value_mode"] == "item-sharded" and line["scaling"] == "strong"
@@ -49,7 +50,7 @@ def test_rehearsal_of_the_multi_gpu_line(world):
 
 
 def test_single_gpu_line_carries_both_modes():
-    line = _run(["--steps", "2", "--warmup", "1", "--config", "tiny", "--batch", "8192", "--shard-batch", "4096", "--no-sweep", "--cpu-seconds", "1"])
+    line = _run(["--full", "--steps", "2", "--warmup", "1", "--config", "tiny", "--batch", "8192", "--shard-batch", "4096", "--no-sweep", "--cpu-seconds", "1"])
     for key in CONTRACT:
         assert key in line, key
     assert line["n_gpus"] == 1 and line["value_mode"] == "replicas" and line["scaling"] == "weak" and line["value"] == line["value_replicas"] > 0
@@ -68,9 +69,9 @@ def test_single_gpu_line_carries_both_modes():
 
 
 def test_default_bench_line_on_the_tiny_config_carries_every_block():
-    """`python bench.py` as the driver runs it (N = 1, sweeps and CPU baseline on), on the generator's tiny config so that it takes seconds: ONE line, the contract's keys, `roofline`,
+    """`python bench.py --full` (N = 1, sweeps and CPU baseline on), on the generator's tiny config so that it takes seconds: ONE line, the contract's keys, `roofline`,
     `cpu_baseline`, the batch sweep and -- since round 4 -- `latency.long_sessions` (sessions of up to 8 / 10 items through the fast kernel's MID instantiation, oracle-gated inside the run)."""
-    line = _run(["--config", "tiny", "--batch", "16384", "--steps", "2", "--warmup", "1", "--cpu-seconds", "1"])
+    line = _run(["--full", "--config", "tiny", "--batch", "16384", "--steps", "2", "--warmup", "1", "--cpu-seconds", "1"])
     for key in CONTRACT + ("value_replicas", "value_item_sharded", "value_mode"):
         assert key in line, key
     assert line["n_gpus"] == 1 and line["steps"] == 2 and line["value"] > 0
@@ -88,9 +89,58 @@ def test_bench_line_through_the_avro_route():
     """`bench.py --index avro:per-item --tie-per-second 8` (round 6): the same synthetic sessions through the reference's production route -- a stand-in producer writes the
     Avro item / session index with its own order among equal timestamps, srn_index_new_from_avro loads it, the parity gate checks against the oracle's restatement of
     VMISIndex::new -- on the tiny config, so that the path stays alive between rounds."""
-    line = _run(["--config", "tiny", "--batch", "16384", "--steps", "2", "--warmup", "1", "--no-sweep", "--no-cpu-baseline", "--no-measure-traffic", "--mode", "replicas",
+    line = _run(["--full", "--config", "tiny", "--batch", "16384", "--steps", "2", "--warmup", "1", "--no-sweep", "--no-cpu-baseline", "--no-measure-traffic", "--mode", "replicas",
                  "--index", "avro:per-item", "--tie-per-second", "8", "--producer-max-len", "30"])
     cfg = line["config"]
     assert cfg["index"].startswith("avro") and cfg["avro"]["producer_tie_order"] == "per-item" and cfg["avro"]["tie_order_inference"] == "on"
     assert cfg["avro"]["sessions_named_by_some_list"] < cfg["avro"]["sessions_in_the_session_index"]      # sessions beyond the producer's length cut are in no list
     assert line["parity_checked"] > 0 and line["value"] > 0 and cfg["avro"]["share_on_the_fast_kernels"] > 0.95
+
+
+PLAIN = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "dtype", "data", "config", "value_mode")
+
+
+def _dumped(d):
+    out = {}
+    for name in ("ids", "scores", "counts", "rows"):
+        a = np.load(os.path.join(d, name + ".npy"))
+        assert a.dtype == np.float64, (name, a.dtype)
+        out[name] = a
+    assert sum(a.nbytes for a in out.values()) <= 64 << 20
+    return out
+
+
+def test_plain_line_times_the_headline_alone_and_dumps_its_last_step(tmp_path):
+    """A plain run (no --full): the headline's keys, exactly --steps timed steps, none of the --full blocks; --dump-outputs writes the last timed step's rows (a fixed
+    seeded sample of 65 536 of them above that many), the same bytes run after run and the same as a --full run of the same arguments, whose parity gate checks them."""
+    args = ["--config", "tiny", "--batch", "70000", "--steps", "3", "--warmup", "2"]
+    line = _run(args + ["--dump-outputs", str(tmp_path / "a")])
+    for key in PLAIN:
+        assert key in line, key
+    assert line["n_gpus"] == 1 and line["steps"] == 3 and line["warmup"] == 2 and line["value_mode"] == "replicas" and line["full"] is False
+    assert line["value"] > 0 and abs(line["value"] - 70000 / (line["ms_per_step"] * 1e-3)) <= 1e-6 * line["value"]
+    for key in ("roofline", "roofline_secondary", "cpu_baseline", "item_sharded", "parity_checked"):
+        assert key not in line, key
+    a = _dumped(tmp_path / "a")
+    assert a["rows"].shape == (65536,) and np.all(np.diff(a["rows"]) > 0) and a["rows"][-1] < 70000
+    assert a["ids"].shape == (65536, 21) and a["scores"].shape == (65536, 21) and a["counts"].shape == (65536,)
+    assert np.all(a["counts"] <= 21) and a["counts"].sum() > 0
+    _run(args + ["--dump-outputs", str(tmp_path / "b")])
+    full = _run(args + ["--full", "--mode", "replicas", "--no-sweep", "--no-cpu-baseline", "--no-measure-traffic", "--dump-outputs", str(tmp_path / "c")])
+    assert full["full"] is True and full["parity_checked"] > 0 and full["full_batch_properties_ok"] is True
+    for other in (_dumped(tmp_path / "b"), _dumped(tmp_path / "c")):
+        for name in a:
+            assert np.array_equal(a[name], other[name]), name
+
+
+def test_plain_rehearsal_line_is_the_item_sharded_headline(tmp_path):
+    """The plain N > 1 line (here two ranks on device 0 over gloo callbacks): the item-sharded mode alone, its runs and the line, no replicas phase, no parity gate;
+    --dump-outputs writes rank 0's rows of the last timed step."""
+    line = _run(["--rehearse", "2", "--steps", "2", "--warmup", "1", "--config", "tiny", "--shard-batch", "4096", "--dump-outputs", str(tmp_path)])
+    assert "item_sharded_error" not in line, line["item_sharded_error"]
+    for key in PLAIN:
+        assert key in line, key
+    assert line["n_gpus"] == 2 and line["value_mode"] == "item-sharded" and line["value"] == line["value_item_sharded"] > 0 and line["value_replicas"] is None
+    assert "replicas" not in line and "roofline" not in line and line["parity_checked"] == 0 and line["queries_served_last_step"] == 4096
+    d = _dumped(tmp_path)
+    assert d["rows"].shape == (4096,) and d["ids"].shape == (4096, 21) and np.all(d["counts"] <= 21) and d["counts"].sum() > 0

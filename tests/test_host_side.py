@@ -10,7 +10,7 @@ import pytest
 
 import serenade_amd as sa
 from serenade_amd import capi, synth
-from helpers import ROOT, extract_example, have_reference_assets, small_dataset
+from helpers import ROOT, extract_example, small_dataset
 from oracle import oracle as O
 
 
@@ -115,7 +115,6 @@ def test_tsv_loader_matches_read_from_file_quirks(tmp_path):
     assert q995 == int(round(float(np.quantile(lens, 0.995))))
 
 
-@pytest.mark.skipif(not have_reference_assets(), reason="/root/reference assets not present (GPU box)")
 def test_new_from_csv_on_reference_example(tmp_path):
     d = extract_example(tmp_path)
     path = os.path.join(d, "train.txt")
@@ -303,7 +302,6 @@ def test_evaluator_metric_known_answers():
     assert r.stdout.count(" ok") == 8 and "MISMATCH" not in r.stdout
 
 
-@pytest.mark.skipif(not have_reference_assets(), reason="/root/reference assets not present (GPU box)")
 def test_evaluate_file_reproduces_readme_metrics(tmp_path):
     """evaluate_file.rs mirror on the oracle's predictions for the reference example (example.toml parameters, how_many=20):
     README.md:170-172 -> Mrr 0.3277 Ndcg 0.3553 HitRate 0.6402 Popularity 0.0499 Precision 0.0680 Coverage 0.2765

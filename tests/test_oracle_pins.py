@@ -5,7 +5,7 @@ import os
 import numpy as np
 import pytest
 
-from helpers import (GOLDEN, assert_valid_topn, evaluator_queries, extract_example, flatten, have_reference_assets,
+from helpers import (GOLDEN, assert_valid_topn, evaluator_queries, extract_example, flatten,
                      mrr_hitrate, random_queries, read_test_data_evolving, small_dataset)
 from oracle import oracle as O
 
@@ -112,10 +112,6 @@ def test_golden_fixture_is_reproduced_by_the_oracle():
     assert len(g["q_off_a"]) - 1 == 931                              # README.md:172 "Qty test evaluations: 931"
 
 
-needs_ref = pytest.mark.skipif(not have_reference_assets(), reason="/root/reference assets not present (GPU box)")
-
-
-@needs_ref
 def test_reference_example_readme_vectors(tmp_path):
     """GV-1 and AGG-1/2 of SURVEY.md 8c, straight from the reference's example data and README."""
     d = extract_example(tmp_path)
@@ -224,7 +220,7 @@ def test_what_canonical_costs_against_the_literal_reference_on_tied_data(capsys)
     """the canonical closed form replaces the reference's container-order-dependent behaviour at ties and
     the t-digest p99.5 (vmis_index.rs:689-716, Q10) by the exact quantile.  How far can that move the reference's own quality numbers?  Measured here against the
     LITERAL restatement (same loops, heaps and scan orders as vmis_index.rs:325-415 / mod.rs:118-215, with this oracle's map iteration order standing in for
-    hashbrown's) on a tied-timestamp synthetic set, and -- where /root/reference is present -- on assets/example (306 of its sessions share a timestamp).
+    hashbrown's) on a tied-timestamp synthetic set, and on the reference's example data (tests/golden/example_sessions.zip: 306 of its sessions share a timestamp).
     The numbers are copied into DESIGN.md section 2; the asserts are the bounds that table claims."""
     rows = []
     off, items, ts, qs = _tied_workload()
@@ -233,26 +229,25 @@ def test_what_canonical_costs_against_the_literal_reference_on_tied_data(capsys)
         sd, od, dm, base = _divergence(ix, "literal", ix, "canonical", qs, k, m, 21, items)
         rows.append(("synthetic tied, k=%d m=%d" % (k, m), len(qs), sd, od, dm, base))
         assert abs(dm["Mrr"]) < 0.01 and abs(dm["HitRate"]) < 0.01 and abs(dm["Ndcg"]) < 0.01 and abs(dm["Recall"]) < 0.01, dm
-    if have_reference_assets():
-        import tempfile
-        with tempfile.TemporaryDirectory() as tmp:
-            d = extract_example(tmp)
-            eoff, eitems, ets, _ = O.read_tsv(os.path.join(d, "train.txt"))
-            test = read_test_data_evolving(os.path.join(d, "test.txt"))
-            train_col = [int(l.split()[1]) for l in list(open(os.path.join(d, "train.txt")))[1:] if len(l.split()) >= 3]
-        assert len(ets) - len(np.unique(ets)) > 100                                    # (timestamps do tie in the example)
-        for (k, m, last, idfw) in ((50, 500, 2, 1.0), (288, 1502, 4, 2.0)):           # example.toml / BASELINE configs[0] (README TPE optimum)
-            eqs = evaluator_queries(test, last)
-            ix = O.OracleIndex(eoff, eitems, ets, m, 15, idfw, fast=True)
-            sd, od, dm, base = _divergence(ix, "literal", ix, "canonical", eqs, k, m, 21, train_col)
-            rows.append(("assets/example, k=%d m=%d last=%d" % (k, m, last), len(eqs), sd, od, dm, base))
-            assert sd < 0.30 and abs(dm["Mrr"]) < 0.005 and abs(dm["HitRate"]) < 0.005, (sd, dm)
-            # Q10: the reference's t-digest estimate of p99.5 may land one off the exact quantile (15): what a +-1 max_session_len does to canonical results
-            for ml in (14, 16):
-                ix2 = O.OracleIndex(eoff, eitems, ets, m, ml, idfw, fast=True)
-                sd2, od2, dm2, _ = _divergence(ix, "canonical", ix2, "canonical", eqs, k, m, 21, train_col)
-                rows.append(("assets/example, k=%d m=%d last=%d: max_session_len %d vs 15" % (k, m, last, ml), len(eqs), sd2, od2, dm2, None))
-                assert abs(dm2["Mrr"]) < 0.01 and abs(dm2["HitRate"]) < 0.01, (ml, dm2)
+    import tempfile
+    with tempfile.TemporaryDirectory() as tmp:
+        d = extract_example(tmp)
+        eoff, eitems, ets, _ = O.read_tsv(os.path.join(d, "train.txt"))
+        test = read_test_data_evolving(os.path.join(d, "test.txt"))
+        train_col = [int(l.split()[1]) for l in list(open(os.path.join(d, "train.txt")))[1:] if len(l.split()) >= 3]
+    assert len(ets) - len(np.unique(ets)) > 100                                    # (timestamps do tie in the example)
+    for (k, m, last, idfw) in ((50, 500, 2, 1.0), (288, 1502, 4, 2.0)):           # example.toml / BASELINE configs[0] (README TPE optimum)
+        eqs = evaluator_queries(test, last)
+        ix = O.OracleIndex(eoff, eitems, ets, m, 15, idfw, fast=True)
+        sd, od, dm, base = _divergence(ix, "literal", ix, "canonical", eqs, k, m, 21, train_col)
+        rows.append(("assets/example, k=%d m=%d last=%d" % (k, m, last), len(eqs), sd, od, dm, base))
+        assert sd < 0.30 and abs(dm["Mrr"]) < 0.005 and abs(dm["HitRate"]) < 0.005, (sd, dm)
+        # Q10: the reference's t-digest estimate of p99.5 may land one off the exact quantile (15): what a +-1 max_session_len does to canonical results
+        for ml in (14, 16):
+            ix2 = O.OracleIndex(eoff, eitems, ets, m, ml, idfw, fast=True)
+            sd2, od2, dm2, _ = _divergence(ix, "canonical", ix2, "canonical", eqs, k, m, 21, train_col)
+            rows.append(("assets/example, k=%d m=%d last=%d: max_session_len %d vs 15" % (k, m, last, ml), len(eqs), sd2, od2, dm2, None))
+            assert abs(dm2["Mrr"]) < 0.01 and abs(dm2["HitRate"]) < 0.01, (ml, dm2)
     with capsys.disabled():
         for name, nq, sd, od, dm, base in rows:
             print("\n[canonical-vs-literal] %s: %d queries, top-21 set differs %.2f %%, ranked list differs %.2f %%; deltas %s%s" % (

@@ -7,9 +7,9 @@
 set -x
 tag=${1:-rXX}
 R=$PWD; O=$R/gpurun_out/${tag}p; mkdir -p $O
-python bench.py > $O/${tag}_bench_cfg3.json 2> $O/bench_cfg3.err
-python bench.py --config cfg2 --no-cpu-baseline --mode replicas --no-measure-traffic > $O/${tag}_bench_cfg2.json 2>/dev/null
-python bench.py --config cfg4 --no-cpu-baseline --mode replicas --no-measure-traffic > $O/${tag}_bench_cfg4.json 2>/dev/null
+python bench.py --full > $O/${tag}_bench_cfg3.json 2> $O/bench_cfg3.err
+python bench.py --full --config cfg2 --no-cpu-baseline --mode replicas --no-measure-traffic > $O/${tag}_bench_cfg2.json 2>/dev/null
+python bench.py --full --config cfg4 --no-cpu-baseline --mode replicas --no-measure-traffic > $O/${tag}_bench_cfg4.json 2>/dev/null
 python tools/latency_probe.py cfg3 > $O/${tag}_latency_cfg3.txt 2>&1
 SRN_HOST_CHUNKS=1 python tools/phase_profile.py cfg3 131072 > $O/phase_cfg3.log 2>&1
 SRN_HOST_CHUNKS=1 python tools/phase_profile.py cfg3 300 > $O/phase_cfg3_alone.log 2>&1
