@@ -399,6 +399,47 @@ int srn_recommend(srn_batcher_t* b, srn_session_store_t* s, const char* session_
                   int user_consent, size_t max_items_in_session, uint64_t now_secs, uint64_t* out_ids, double* out_scores,
                   size_t* out_n);
 
+/* ---- offline evaluation: test sets and hyper-parameter trials ----------------------------------------------------------
+ * The reference's evaluation loop (src/bin/evaluator.rs:46-76, src/objective.rs:8-52) on the GPU: every prefix of every test session is
+ * predicted and scored against the rest of its session, and the eight metrics of src/metrics/evaluation_reporter.rs come back.  Prefixes,
+ * recommendation rows and per-query terms stay in device memory; one srn_evaluate call runs any number of trials on one index.
+ *
+ * An evaluation set binds test sessions and training-item frequencies to one index (which must have a device: SRN_ENODEV otherwise):
+ *   items_flat / sess_off: test session i = items_flat[sess_off[i] .. sess_off[i+1]), each ordered by time as read_test_data_evolving orders it
+ *                          (src/io.rs:40-59; equal times keep file order).  A session of one event gives no query (the loop starts at state 1).
+ *   train_item_ids / train_item_counts: how often each item occurs in the training data's item column (popularity.rs:20-29).  Repeated ids
+ *                          add up; the number of distinct ids is Coverage's denominator (coverage.rs:17-25).
+ * The set keeps a pointer to the index: free the set first. */
+typedef struct srn_eval_set srn_eval_set_t;
+typedef struct {
+    uint32_t k, m, how_many;          /* predict's arguments (m <= the index's m_index is the normal case: one index answers every smaller m) */
+    uint32_t max_items_in_session;    /* the window: a prefix is its last max_items_in_session items (evaluator.rs:50-55); 1..SRN_MAX_SESSION_LEN */
+    uint32_t length;                  /* @N of the metrics (1..SRN_MAX_HOW_MANY); independent of how_many (hyperparameter_search.rs asks for 21, scores @20) */
+    uint32_t flags;                   /* SRN_FLAG_BUSINESS_LOGIC */
+    uint32_t max_chunk_queries;       /* queries per device round (0 = default); rounded down to a multiple of 256.  Results do not depend on it */
+    uint32_t reserved;                /* 0 */
+} srn_eval_trial_t;
+typedef struct {
+    uint64_t n_evaluations;           /* qty_evaluations: queries of the trial */
+    /* the report line of evaluation_reporter.rs, in its order (F1 of 0 / 0 is 0, f1score.rs:27-36) */
+    double mrr, ndcg, hit_rate, popularity, precision, coverage, recall, f1score;
+    /* raw sums over the queries (averages = sum / n_evaluations) */
+    double sum_mrr, sum_ndcg, sum_hit_rate, sum_popularity, sum_precision, sum_recall;
+    uint64_t covered_items, unique_training_items;   /* Coverage = covered_items / unique_training_items */
+    double ms_predict, ms_eval;       /* device time (HIP events) of the predict launches and of the expansion + metric + reduction kernels */
+} srn_eval_result_t;
+int srn_eval_set_create(const srn_index_t* idx, const uint64_t* items_flat, const uint64_t* sess_off, size_t n_sessions,
+                        const uint64_t* train_item_ids, const uint64_t* train_item_counts, size_t n_train_items, srn_eval_set_t** out);
+/* the same from the reference's TSV files "SessionId ItemId Time" (src/io.rs:13-59): sessions in ascending SessionId, events by rounded time */
+int srn_eval_set_from_tsv(const srn_index_t* idx, const char* test_path, const char* train_path, srn_eval_set_t** out);
+/* Runs n_trials trials and blocks until they are done; out[t] is trial t's result.  Sums are added in a fixed order (partial sums per
+ * group of 256 queries): the same trial gives the same bits from call to call, alone or among others, for any max_chunk_queries.
+ * Every trial is checked before anything is launched: predict's argument checks, length 0 (SRN_EINVAL) or above SRN_MAX_HOW_MANY, and a
+ * window of 0 (SRN_EINVAL) or above SRN_MAX_SESSION_LEN (SRN_ERANGE: a prefix could exceed the kernels' session limit) fail the whole call.
+ * stream: a hipStream_t (NULL = the null stream). */
+int srn_evaluate(srn_eval_set_t* set, const srn_eval_trial_t* trials, size_t n_trials, srn_eval_result_t* out, void* stream);
+void srn_eval_set_free(srn_eval_set_t* set);
+
 int srn_device_count(int* out);
 void srn_limits(srn_limits_t* out);
 const char* srn_last_error(void);

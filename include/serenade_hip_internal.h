@@ -37,6 +37,11 @@ int srn_debug_last_big_count(const srn_index_t* idx, uint32_t* out_listed);
 /* Test aid: batches of this item shard that went through the wave-per-query back end of srn_sback.hip (the shard group's neighbours pipeline), since the shard was attached. */
 int srn_debug_sback_launches(const srn_index_t* idx, uint64_t* out_launches);
 
+/* Test aid: one trial of srn_evaluate with its per-query terms.  out_terms [n * 7] (query order: sessions in set order, states ascending):
+ * mrr, hit, ndcg, intersection size, precision, recall, popularity; *out_n = the trial's query count n (out_terms may be NULL to ask for it;
+ * cap < n: SRN_ERANGE).  *out (may be NULL) = what srn_evaluate returns for the trial. */
+int srn_debug_eval_terms(srn_eval_set_t* set, const srn_eval_trial_t* trial, double* out_terms, size_t cap, size_t* out_n, srn_eval_result_t* out);
+
 /* Test / experiment knobs (environment variables SRN_NO_FAST, SRN_NO_MID, SRN_NO_MASKS, SRN_NO_MERGE, SRN_DENSE, SRN_HOT_SLOTS,
  * SRN_SKETCH_SLOTS, SRN_LDS_BUDGET_KB, SRN_GRID_MULT, SRN_DEBUG) force individual kernel code paths.  They are read ONCE,
  * when the library is first used -- never on the launch path; this call re-reads them (the parity tests switch paths

@@ -2,7 +2,10 @@
 
 The package holds only what that path needs: the HIP kernels + C ABI (csrc/, built into
 libserenade_hip.so), a ctypes binding (capi), the host-side mirror of the reference interface
-(vmisknn) and the synthetic workload generator used by bench.py (synth)."""
+(vmisknn), the offline evaluation loop and hyper-parameter search on the GPU (evaluation, hpo) and the synthetic workload generator
+used by bench.py (synth)."""
 from .vmisknn import CSR, ItemScore, VMISIndex, SerenadeError, predict, predict_batch, predict_batch_debug, predict_batch_device, reserve  # noqa: F401
+from .evaluation import EvalSet, evaluate  # noqa: F401
 
-__all__ = ["CSR", "ItemScore", "VMISIndex", "SerenadeError", "predict", "predict_batch", "predict_batch_debug", "predict_batch_device", "reserve"]
+__all__ = ["CSR", "ItemScore", "VMISIndex", "SerenadeError", "predict", "predict_batch", "predict_batch_debug", "predict_batch_device", "reserve",
+           "EvalSet", "evaluate"]

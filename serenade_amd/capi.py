@@ -52,6 +52,17 @@ SHARD_GROUP_ID_BYTES = 256
 FLAG_INPUTS_RESIDENT = 2
 
 
+class EvalTrial(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("k", "m", "how_many", "max_items_in_session", "length", "flags", "max_chunk_queries", "reserved")]
+
+
+class EvalResult(C.Structure):
+    _fields_ = [("n_evaluations", C.c_uint64)] + \
+               [(n, C.c_double) for n in ("mrr", "ndcg", "hit_rate", "popularity", "precision", "coverage", "recall", "f1score",
+                                          "sum_mrr", "sum_ndcg", "sum_hit_rate", "sum_popularity", "sum_precision", "sum_recall")] + \
+               [("covered_items", C.c_uint64), ("unique_training_items", C.c_uint64), ("ms_predict", C.c_double), ("ms_eval", C.c_double)]
+
+
 class Limits(C.Structure):
     _fields_ = [("max_how_many", C.c_uint32), ("max_session_len", C.c_uint32), ("max_k", C.c_uint32), ("reserved", C.c_uint32)]
 
@@ -126,6 +137,11 @@ SYMBOLS = {
     "srn_debug_last_big_count": (_i, [_vp, C.POINTER(C.c_uint32)]),
     "srn_debug_sback_launches": (_i, [_vp, C.POINTER(_u64)]),
     "srn_last_path_counts": (_i, [_vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "srn_eval_set_create": (_i, [_vp, _vp, _vp, _sz, _vp, _vp, _sz, C.POINTER(_vp)]),
+    "srn_eval_set_from_tsv": (_i, [_vp, C.c_char_p, C.c_char_p, C.POINTER(_vp)]),
+    "srn_evaluate": (_i, [_vp, C.POINTER(EvalTrial), _sz, C.POINTER(EvalResult), _vp]),
+    "srn_eval_set_free": (None, [_vp]),
+    "srn_debug_eval_terms": (_i, [_vp, C.POINTER(EvalTrial), _vp, _sz, C.POINTER(_sz), C.POINTER(EvalResult)]),
     "srn_device_count": (_i, [C.POINTER(_i)]),
     "srn_limits": (None, [C.POINTER(Limits)]),
     "srn_last_error": (C.c_char_p, []),

@@ -485,4 +485,73 @@ int srn_debug_sback_launches(const srn_index_t* idx, uint64_t* out_launches) {
 
 void srn_debug_reload_knobs(void) { reload_knobs(); }
 
+// ---- offline evaluation (srn_eval.hip) ----
+static int check_eval_index(const srn_index_t* idx) {
+    if (!idx) return fail(SRN_EINVAL, "null index");
+    if (!idx->dev) return fail(SRN_ENODEV, "index has no device attached; evaluation runs on the GPU only");
+    if (idx->flat.postings_only) return fail(SRN_EINVAL, "a postings-only view holds no rows");
+    return check_not_a_shard(idx);
+}
+
+// every trial is checked before anything is launched; the checks that need no index come first
+static int check_trials(const srn_eval_set_t* set, const srn_eval_trial_t* trials, size_t n_trials, const srn_eval_result_t* out) {
+    if (n_trials && (!trials || !out)) return fail(SRN_EINVAL, "null argument");
+    for (size_t t = 0; t < n_trials; ++t) {
+        const srn_eval_trial_t& tr = trials[t];
+        if (tr.max_items_in_session == 0) return fail(SRN_EINVAL, "max_items_in_session must be > 0");
+        if (tr.max_items_in_session > SRN_MAX_SESSION_LEN) return fail(SRN_ERANGE, "max_items_in_session above SRN_MAX_SESSION_LEN: a prefix could exceed the kernels' session limit");
+        if (tr.length == 0) return fail(SRN_EINVAL, "length must be > 0");
+        if (tr.length > SRN_MAX_HOW_MANY) return fail(SRN_ERANGE, "length above SRN_MAX_HOW_MANY");
+        if (tr.k == 0 || tr.m == 0 || tr.how_many == 0) return fail(SRN_EINVAL, "k, m and how_many must be > 0");
+        if (tr.how_many > SRN_MAX_HOW_MANY) return fail(SRN_ERANGE, "how_many above SRN_MAX_HOW_MANY");
+        if (tr.k > SRN_MAX_K) return fail(SRN_ERANGE, "k above SRN_MAX_K");
+        if (tr.m > 0x7FFFFFFFu) return fail(SRN_ERANGE, "m too large");
+    }
+    if (!set) return fail(SRN_EINVAL, "null evaluation set");
+    for (size_t t = 0; t < n_trials; ++t) { int rc = check_predict_args(set->idx, trials[t].k, trials[t].m, trials[t].how_many); if (rc) return rc; }
+    return SRN_OK;
+}
+
+int srn_eval_set_create(const srn_index_t* idx, const uint64_t* items_flat, const uint64_t* sess_off, size_t n_sessions,
+                        const uint64_t* train_item_ids, const uint64_t* train_item_counts, size_t n_train_items, srn_eval_set_t** out) {
+    return guarded([&]() -> int {
+        if (!out) return fail(SRN_EINVAL, "null argument");
+        *out = nullptr;
+        int rc = check_eval_index(idx); if (rc) return rc;
+        if (!sess_off || (sess_off[n_sessions] && !items_flat) || (n_train_items && (!train_item_ids || !train_item_counts))) return fail(SRN_EINVAL, "null buffer");
+        if (sess_off[0] != 0) return fail(SRN_EINVAL, "sess_off must start at 0");
+        for (size_t s = 0; s < n_sessions; ++s) if (sess_off[s + 1] < sess_off[s]) return fail(SRN_EINVAL, "sess_off not monotone");
+        if (n_sessions >= 0xFFFFFFFFull) return fail(SRN_ERANGE, "too many test sessions");
+        return eval_set_create(idx, items_flat, sess_off, n_sessions, train_item_ids, train_item_counts, n_train_items, out); });
+}
+
+int srn_eval_set_from_tsv(const srn_index_t* idx, const char* test_path, const char* train_path, srn_eval_set_t** out) {
+    return guarded([&]() -> int {
+        if (!out || !test_path || !train_path) return fail(SRN_EINVAL, "null argument");
+        *out = nullptr;
+        int rc = check_eval_index(idx); if (rc) return rc;
+        return eval_set_from_tsv(idx, test_path, train_path, out); });
+}
+
+int srn_evaluate(srn_eval_set_t* set, const srn_eval_trial_t* trials, size_t n_trials, srn_eval_result_t* out, void* stream) {
+    return guarded([&]() -> int {
+        int rc = check_trials(set, trials, n_trials, out); if (rc) return rc;
+        if (n_trials == 0) return SRN_OK;
+        return eval_run(set, trials, n_trials, out, stream, nullptr, 0); });
+}
+
+int srn_debug_eval_terms(srn_eval_set_t* set, const srn_eval_trial_t* trial, double* out_terms, size_t cap, size_t* out_n, srn_eval_result_t* out) {
+    return guarded([&]() -> int {
+        if (!trial || !out_n) return fail(SRN_EINVAL, "null argument");
+        srn_eval_result_t tmp;
+        int rc = check_trials(set, trial, 1, &tmp); if (rc) return rc;
+        *out_n = (size_t)eval_n_queries(set);
+        if (!out_terms) return SRN_OK;
+        rc = eval_run(set, trial, 1, &tmp, nullptr, out_terms, cap); if (rc) return rc;
+        if (out) *out = tmp;
+        return SRN_OK; });
+}
+
+void srn_eval_set_free(srn_eval_set_t* set) { eval_set_free(set); }
+
 }  // extern "C"

@@ -1,0 +1,397 @@
+// Offline evaluation on the GPU (include/serenade_hip.h, "offline evaluation"): the reference's evaluation loop (src/bin/evaluator.rs:46-76,
+// src/objective.rs:8-52) over a test set resident in HBM.  A trial runs in chunks of queries; per chunk
+//   eval_expand_kernel   the chunk's prefixes (CSR) straight from the resident test sessions, windowed to the trial's max_items_in_session
+//   device_predict       the same launch sequence srn_predict_batch_device takes (the rows are the same bytes)
+//   eval_metrics_kernel  one wave per query: the per-query terms of src/metrics/*.rs, and the recommended items' coverage bits
+//   eval_group_kernel    partial sums per group of 256 GLOBAL query indices (chunks are multiples of 256, so a group never straddles two)
+// The host adds the groups' partial sums in group order: a trial's sums do not depend on the chunk size or on the other trials of the call.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <map>
+#include <unordered_map>
+#include <vector>
+
+#include "srn_internal.h"
+#include "srn_runtime.h"
+#include "srn_device.h"
+#include "srn_hipsync.h"
+
+// the terms must be the bits the host formulas give: no fused multiply-adds
+#pragma clang fp contract(off)
+
+namespace srn {
+
+static constexpr uint32_t kGroup = 256;          // queries per partial sum
+static constexpr uint32_t kTerms = 8;            // per query: mrr, hit, ndcg, intersection, precision, recall, popularity, (unused)
+static constexpr uint32_t kSums = 6;             // per group: mrr, hit, ndcg, precision, recall, popularity
+static constexpr uint32_t kDefaultChunk = 1u << 20;
+static constexpr uint32_t kMaxChunk = 1u << 24;  // chunk items < 2^24 * SRN_MAX_SESSION_LEN < 2^32: q_off stays 32-bit
+static constexpr uint32_t kMetricWaves = 4;
+
+struct EvalDevice {
+    int device = 0;
+    uint64_t* items = nullptr; uint64_t* sess_off = nullptr;   // the test sessions
+    double* freq = nullptr;                                     // [n_items] training count of each dense item of the index
+    double* ndcg_w = nullptr;                                   // [SRN_MAX_HOW_MANY] w_i, then [SRN_MAX_HOW_MANY + 1] prefix sums of w (ndcg.rs:13-27)
+    // grow-only workspace
+    char* scan = nullptr; size_t scan_bytes = 0;               // per-session query / item offsets of one window
+    char* chunk = nullptr; size_t chunk_bytes = 0;             // a chunk's prefixes, q_off, (session, state), rows, terms
+    char* part = nullptr; size_t part_bytes = 0;               // per-group partial sums of every trial of a call
+    char* cover = nullptr; size_t cover_bytes = 0;             // coverage bitmaps + popcounts + the error word
+    std::vector<hipEvent_t> ev;
+};
+
+uint64_t eval_n_queries(const srn_eval_set* set) {
+    uint64_t n = 0;
+    for (size_t s = 0; s + 1 < set->sess_off.size(); ++s) { const uint64_t l = set->sess_off[s + 1] - set->sess_off[s]; if (l > 1) n += l - 1; }
+    return n;
+}
+
+// items of the prefixes of states 1..n at window W: sum_{t=1}^{n} min(t, W)
+__host__ __device__ inline uint64_t prefix_items(uint64_t n, uint64_t W) { return n <= W ? n * (n + 1) / 2 : W * (W + 1) / 2 + (n - W) * W; }
+
+__global__ void __launch_bounds__(256) eval_expand_kernel(const uint64_t* __restrict__ items, const uint64_t* __restrict__ sess_off,
+                                                          const uint64_t* __restrict__ sess_q, const uint64_t* __restrict__ sess_i, uint32_t n_sessions,
+                                                          uint64_t q0, uint32_t nq, uint32_t W, uint64_t item_base,
+                                                          uint64_t* __restrict__ out_items, uint32_t* __restrict__ out_qoff, uint2* __restrict__ out_ss) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nq) return;
+    const uint64_t g = q0 + i;
+    uint32_t lo = 0, hi = n_sessions;   // the session s with sess_q[s] <= g < sess_q[s + 1] (sessions without queries have sess_q[s] == sess_q[s + 1])
+    while (hi - lo > 1) { const uint32_t mid = (lo + hi) / 2; if (sess_q[mid] <= g) lo = mid; else hi = mid; }
+    const uint32_t s = lo;
+    const uint64_t state = g - sess_q[s] + 1;
+    const uint64_t start = state > W ? state - W : 0, len = state - start;
+    const uint64_t at = sess_i[s] + prefix_items(state - 1, W) - item_base;
+    const uint64_t* src = items + sess_off[s] + start;
+    for (uint64_t j = 0; j < len; ++j) out_items[at + j] = src[j];
+    out_qoff[i] = (uint32_t)at;
+    if (i == nq - 1) out_qoff[nq] = (uint32_t)(at + len);
+    out_ss[i] = make_uint2(s, (uint32_t)state);
+}
+
+struct MetricArgs {
+    const uint64_t* items; const uint64_t* sess_off;
+    const uint2* ss; const uint64_t* ids; const uint32_t* counts;
+    const double* freq; const double* w; const double* wsum; double max_freq;
+    IdSlot const* id_table; uint32_t id_mask;
+    uint32_t nq, how_many, length;
+    double* terms; uint32_t* cover; uint32_t* err;
+};
+
+// one wave per query: rank positions across the lanes (64 per round), each lane scans the suffix for its item
+__global__ void __launch_bounds__(64 * kMetricWaves) eval_metrics_kernel(MetricArgs a) {
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t q = blockIdx.x * kMetricWaves + (threadIdx.x >> 6);
+    if (q >= a.nq) return;   // (wave-uniform)
+    const uint32_t cnt = a.counts[q];
+    double* t = a.terms + (size_t)q * kTerms;
+    if (cnt == 0xFFFFFFFFu) {   // a query predict could not serve: the call fails
+        if (lane == 0) { atomicOr(a.err, 1u); for (uint32_t j = 0; j < kTerms; ++j) t[j] = 0.0; }
+        return;
+    }
+    const uint2 ss = a.ss[q];
+    const uint64_t* sfx = a.items + a.sess_off[ss.x] + ss.y;
+    const uint32_t slen = (uint32_t)(a.sess_off[ss.x + 1] - a.sess_off[ss.x] - ss.y);   // >= 1
+    const uint64_t next0 = sfx[0];
+    const uint32_t n_top = min(cnt, a.length);
+    const uint64_t* row = a.ids + (size_t)q * a.how_many;
+    int first = -1; uint32_t inter = 0; double num = 0.0, pop = 0.0;
+    for (uint32_t base = 0; base < n_top; base += 64) {
+        const uint32_t p = base + lane;
+        bool found = false, hit = false; double pv = 0.0;
+        if (p < n_top) {
+            const uint64_t id = row[p];
+            hit = id == next0;
+            for (uint32_t j = 0; j < slen && !found; ++j) found = sfx[j] == id;
+            uint32_t h = (uint32_t)dev_mix64(id) & a.id_mask, dense = kNone;   // the index's dictionary: recommended ids are always index items
+            for (;;) { const IdSlot sl = a.id_table[h]; if (sl.idx == kNone) break; if (sl.key == id) { dense = sl.idx; break; } h = (h + 1) & a.id_mask; }
+            if (dense != kNone) {
+                pv = a.freq[dense] / a.max_freq;
+                // popular items are recommended by most queries: an atomic only while the bit is still clear (one hot word would serialise them all)
+                uint32_t* word = a.cover + (dense >> 5); const uint32_t bit = 1u << (dense & 31);
+                if ((__hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & bit) == 0u) atomicOr(word, bit);
+            }
+        }
+        const uint64_t fm = __ballot(found), hm = __ballot(hit);
+        if (first < 0 && hm) first = (int)(base + __ffsll((long long)hm) - 1);
+        inter += (uint32_t)__popcll(fm);
+        // in rank order, one term at a time (the host restatements add in that order)
+        const uint32_t n_here = min(64u, n_top - base);
+        for (uint32_t l = 0; l < n_here; ++l) {
+            pop += __shfl(pv, (int)l);
+            if ((fm >> l) & 1ull) num += a.w[base + l];
+        }
+    }
+    if (lane == 0) {
+        t[0] = first >= 0 ? 1.0 / (double)(first + 1) : 0.0;                  // mrr.rs:24-33
+        t[1] = first >= 0 ? 1.0 : 0.0;                                          // hitrate.rs:24-33
+        t[2] = num / a.wsum[min(slen, a.length)];                               // ndcg.rs:42-56 (the ideal list: the first min(|suffix|, length) next items, all relevant)
+        t[3] = (double)inter;
+        t[4] = (double)inter / (double)a.length;                                // precision.rs:31-43
+        t[5] = (double)inter / (double)slen;                                    // recall.rs:31-44 (duplicates counted)
+        t[6] = n_top ? pop / (double)n_top : 0.0;                               // popularity.rs:41-58
+        t[7] = 0.0;
+    }
+}
+
+// one wave per group of 256 queries: four queries per lane in order, then a fixed butterfly
+__global__ void __launch_bounds__(64) eval_group_kernel(const double* __restrict__ terms, uint32_t nq, double* __restrict__ part) {
+    const uint32_t lane = threadIdx.x, q0 = blockIdx.x * kGroup;
+    double s[kSums] = {0, 0, 0, 0, 0, 0};
+    for (uint32_t r = 0; r < kGroup / 64; ++r) {
+        const uint32_t q = q0 + lane * (kGroup / 64) + r;
+        if (q < nq) {
+            const double* t = terms + (size_t)q * kTerms;
+            s[0] += t[0]; s[1] += t[1]; s[2] += t[2]; s[3] += t[4]; s[4] += t[5]; s[5] += t[6];
+        }
+    }
+#pragma unroll
+    for (uint32_t j = 0; j < kSums; ++j)
+        for (int off = 32; off >= 1; off >>= 1) s[j] += __shfl_xor(s[j], off);
+    if (lane == 0)
+#pragma unroll
+        for (uint32_t j = 0; j < kSums; ++j) part[(size_t)blockIdx.x * kSums + j] = s[j];
+}
+
+__global__ void __launch_bounds__(256) eval_popcount_kernel(const uint32_t* __restrict__ bits, uint32_t words, unsigned long long* __restrict__ out) {
+    uint32_t c = 0;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < words; i += gridDim.x * blockDim.x) c += __popc(bits[i]);
+    for (int off = 32; off >= 1; off >>= 1) c += __shfl_xor(c, off);
+    if ((threadIdx.x & 63) == 0 && c) atomicAdd(out, (unsigned long long)c);
+}
+
+namespace {
+template <typename T> int upload_new(T** p, const T* src, size_t n) {
+    HIP_TRY(hipMalloc((void**)p, std::max<size_t>(n * sizeof(T), 16)));
+    if (n) HIP_TRY(hipMemcpy(*p, src, n * sizeof(T), hipMemcpyHostToDevice));
+    return SRN_OK;
+}
+size_t align256(size_t b) { return (b + 255) / 256 * 256; }
+}  // namespace
+
+void eval_set_free(srn_eval_set* set) {
+    if (!set) return;
+    if (EvalDevice* e = set->dev) {
+        (void)hipSetDevice(e->device);
+        for (void* p : {(void*)e->items, (void*)e->sess_off, (void*)e->freq, (void*)e->ndcg_w, (void*)e->scan, (void*)e->chunk, (void*)e->part, (void*)e->cover})
+            if (p) (void)hipFree(p);
+        for (hipEvent_t x : e->ev) (void)hipEventDestroy(x);
+        delete e;
+    }
+    delete set;
+}
+
+int eval_set_create(const srn_index* idx, const uint64_t* items_flat, const uint64_t* sess_off, size_t n_sessions,
+                    const uint64_t* train_ids, const uint64_t* train_counts, size_t n_train, srn_eval_set** out) {
+    const FlatIndex& ix = idx->flat;
+    srn_eval_set* set = new srn_eval_set();
+    struct Guard { srn_eval_set*& s; ~Guard() { if (s) eval_set_free(s); } } guard{set};
+    set->idx = idx;
+    set->sess_off.assign(sess_off, sess_off + n_sessions + 1);
+    for (size_t s = 0; s < n_sessions; ++s) set->max_session_len = std::max<uint64_t>(set->max_session_len, sess_off[s + 1] - sess_off[s]);
+    // training counts -> per dense item of the index; Coverage's denominator counts every distinct training item, in the index or not
+    std::unordered_map<uint64_t, uint64_t> merged; merged.reserve(n_train * 2 + 1);
+    for (size_t i = 0; i < n_train; ++i) merged[train_ids[i]] += train_counts[i];
+    std::vector<double> freq(ix.n_items, 0.0); uint64_t max_freq = 0;
+    for (const auto& kv : merged) {
+        max_freq = std::max(max_freq, kv.second);
+        const uint32_t d = ix.lookup(kv.first);
+        if (d != kNone) freq[d] = (double)kv.second;
+    }
+    set->max_freq = max_freq ? (double)max_freq : 1.0;
+    set->unique_training_items = merged.size();
+    // ndcg.rs:13-27 on the host (std::log2), so that the device terms are the host formulas' bits
+    std::vector<double> w(2 * SRN_MAX_HOW_MANY + 1, 0.0);
+    for (uint32_t i = 0; i < SRN_MAX_HOW_MANY; ++i) w[i] = i == 0 ? 1.0 : 1.0 / std::log2((double)i + 1.0);
+    for (uint32_t n = 1; n <= SRN_MAX_HOW_MANY; ++n) w[SRN_MAX_HOW_MANY + n] = w[SRN_MAX_HOW_MANY + n - 1] + w[n - 1];
+    EvalDevice* e = new EvalDevice(); set->dev = e; e->device = idx->device;
+    HIP_TRY(hipSetDevice(e->device));
+    int rc;
+    if ((rc = upload_new(&e->items, items_flat, sess_off[n_sessions]))) return rc;
+    if ((rc = upload_new(&e->sess_off, sess_off, n_sessions + 1))) return rc;
+    if ((rc = upload_new(&e->freq, freq.data(), freq.size()))) return rc;
+    if ((rc = upload_new(&e->ndcg_w, w.data(), w.size()))) return rc;
+    *out = set; set = nullptr;
+    return SRN_OK;
+}
+
+// src/io.rs:13-59: "SessionId ItemId Time" after a header line, time rounded half away from zero; sessions in ascending SessionId, each one's
+// events ordered by time (a stable sort: equal times keep file order)
+static int read_tsv_rows(const char* path, std::vector<std::pair<uint32_t, std::pair<long long, uint64_t>>>& rows) {
+    FILE* f = fopen(path, "r");
+    if (!f) return fail(SRN_EIO, std::string("cannot open ") + path);
+    char line[4096];
+    bool header = true;
+    while (fgets(line, sizeof line, f)) {
+        if (header) { header = false; continue; }
+        char* p = line; char* end = nullptr;
+        const unsigned long long s = strtoull(p, &end, 10); if (end == p) continue; p = end;
+        const unsigned long long it = strtoull(p, &end, 10); if (end == p) continue; p = end;
+        const double t = strtod(p, &end); if (end == p) continue;
+        rows.push_back({(uint32_t)s, {std::llround(t), (uint64_t)it}});
+    }
+    fclose(f);
+    return SRN_OK;
+}
+
+int eval_set_from_tsv(const srn_index* idx, const char* test_path, const char* train_path, srn_eval_set** out) {
+    std::vector<std::pair<uint32_t, std::pair<long long, uint64_t>>> test, train;
+    int rc = read_tsv_rows(test_path, test); if (rc) return rc;
+    rc = read_tsv_rows(train_path, train); if (rc) return rc;
+    std::map<uint32_t, std::vector<std::pair<long long, uint64_t>>> by_session;
+    for (const auto& r : test) by_session[r.first].push_back(r.second);
+    std::vector<uint64_t> items, off{0};
+    for (auto& kv : by_session) {
+        std::stable_sort(kv.second.begin(), kv.second.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
+        for (const auto& e : kv.second) items.push_back(e.second);
+        off.push_back(items.size());
+    }
+    std::unordered_map<uint64_t, uint64_t> counts;
+    for (const auto& r : train) ++counts[r.second.second];
+    std::vector<uint64_t> ids, cnt;
+    for (const auto& kv : counts) { ids.push_back(kv.first); cnt.push_back(kv.second); }
+    return eval_set_create(idx, items.data(), off.data(), off.size() - 1, ids.data(), cnt.data(), ids.size(), out);
+}
+
+static uint32_t chunk_queries(const srn_eval_trial_t& t) {
+    uint32_t c = t.max_chunk_queries ? t.max_chunk_queries : std::min<uint32_t>(kDefaultChunk, (1u << 26) / t.how_many);
+    c = std::min(c, kMaxChunk) / kGroup * kGroup;
+    return std::max(c, kGroup);
+}
+
+int eval_run(srn_eval_set* set, const srn_eval_trial_t* trials, size_t n_trials, srn_eval_result_t* out, void* user_stream, double* terms_out, size_t cap) {
+    EvalDevice* e = set->dev; const srn_index* idx = set->idx; const FlatIndex& ix = idx->flat;
+    HIP_TRY(hipSetDevice(e->device));
+    hipStream_t st = (hipStream_t)user_stream;
+    const size_t n_s = set->sess_off.size() - 1;
+    const uint64_t nq_all = eval_n_queries(set);
+    const uint64_t n_groups = (nq_all + kGroup - 1) / kGroup;
+    const uint32_t bitmap_words = (uint32_t)((ix.n_items + 31) / 32 + 1);
+    if (terms_out && cap < nq_all) return fail(SRN_ERANGE, "per-query terms: no room for every query of the trial");
+    // device buffers for the whole call
+    int rc;
+    const size_t cover_stride = align256((size_t)bitmap_words * 4);
+    if ((rc = ensure(&e->cover, &e->cover_bytes, n_trials * cover_stride + align256(n_trials * 8) + 256))) return rc;
+    uint32_t* err = (uint32_t*)(e->cover + n_trials * cover_stride + align256(n_trials * 8));
+    unsigned long long* covered = (unsigned long long*)(e->cover + n_trials * cover_stride);
+    HIP_TRY(hipMemsetAsync(e->cover, 0, e->cover_bytes, st));
+    if ((rc = ensure(&e->part, &e->part_bytes, std::max<size_t>(n_trials * n_groups * kSums * 8, 256)))) return rc;
+    size_t max_chunk = 0, n_events = 0;
+    for (size_t t = 0; t < n_trials; ++t) { const uint64_t c = std::min<uint64_t>(chunk_queries(trials[t]), nq_all); max_chunk = std::max<size_t>(max_chunk, c);
+                                            n_events += 4 * ((nq_all + chunk_queries(trials[t]) - 1) / chunk_queries(trials[t])); }
+    while (e->ev.size() < n_events) { hipEvent_t x; HIP_TRY(hipEventCreate(&x)); e->ev.push_back(x); }
+    if ((rc = ensure(&e->scan, &e->scan_bytes, 2 * (n_s + 1) * 8))) return rc;
+    std::vector<uint64_t> scan(2 * (n_s + 1));
+    uint32_t scan_W = 0;
+    size_t ev_at = 0;
+    std::vector<std::pair<size_t, size_t>> trial_events(n_trials);
+    for (size_t ti = 0; ti < n_trials; ++ti) {
+        const srn_eval_trial_t& tr = trials[ti];
+        const uint32_t W = tr.max_items_in_session;
+        trial_events[ti].first = ev_at;
+        if (nq_all == 0) { trial_events[ti].second = ev_at; continue; }
+        if (W != scan_W) {   // per-session query and item offsets of this window (one scan per distinct window in a row of trials)
+            uint64_t q = 0, it = 0;
+            for (size_t s = 0; s < n_s; ++s) {
+                scan[s] = q; scan[n_s + 1 + s] = it;
+                const uint64_t l = set->sess_off[s + 1] - set->sess_off[s];
+                if (l > 1) { q += l - 1; it += prefix_items(l - 1, W); }
+            }
+            scan[n_s] = q; scan[2 * n_s + 1] = it;
+            HIP_TRY(hipMemcpyAsync(e->scan, scan.data(), scan.size() * 8, hipMemcpyHostToDevice, st));
+            HIP_TRY(hipStreamSynchronize(st));   // (the host vector is rewritten by the next window)
+            scan_W = W;
+        }
+        const uint64_t* sess_q = (const uint64_t*)e->scan; const uint64_t* sess_i = sess_q + n_s + 1;
+        const uint32_t max_len = (uint32_t)std::min<uint64_t>(W, set->max_session_len - 1);
+        const uint32_t chunk = chunk_queries(tr);
+        const uint32_t cq = (uint32_t)std::min<uint64_t>(chunk, nq_all);
+        // chunk buffers: items | q_off | (session, state) | ids | scores | counts | terms
+        const size_t o_items = 0, o_qoff = align256((size_t)cq * max_len * 8), o_ss = o_qoff + align256(((size_t)cq + 1) * 4),
+                     o_ids = o_ss + align256((size_t)cq * 8), o_sc = o_ids + align256((size_t)cq * tr.how_many * 8),
+                     o_cnt = o_sc + align256((size_t)cq * tr.how_many * 8), o_terms = o_cnt + align256((size_t)cq * 4),
+                     bytes = o_terms + align256((size_t)cq * kTerms * 8);
+        if (bytes > e->chunk_bytes) { HIP_TRY(hipStreamSynchronize(st)); if ((rc = ensure(&e->chunk, &e->chunk_bytes, bytes))) return rc; }
+        char* cb = e->chunk;
+        uint64_t* d_items = (uint64_t*)(cb + o_items); uint32_t* d_qoff = (uint32_t*)(cb + o_qoff); uint2* d_ss = (uint2*)(cb + o_ss);
+        uint64_t* d_ids = (uint64_t*)(cb + o_ids); double* d_sc = (double*)(cb + o_sc); uint32_t* d_cnt = (uint32_t*)(cb + o_cnt); double* d_terms = (double*)(cb + o_terms);
+        double* part = (double*)e->part + ti * n_groups * kSums;
+        uint32_t* bitmap = (uint32_t*)(e->cover + ti * cover_stride);
+        for (uint64_t q0 = 0; q0 < nq_all; q0 += chunk) {
+            const uint32_t nq = (uint32_t)std::min<uint64_t>(chunk, nq_all - q0);
+            hipEvent_t* ev = &e->ev[ev_at]; ev_at += 4;
+            HIP_TRY(hipEventRecord(ev[0], st));
+            // item offset of query q0: its session's start + the prefixes before it
+            uint64_t item_base;
+            { const size_t s = (size_t)(std::upper_bound(scan.begin(), scan.begin() + n_s + 1, q0) - scan.begin()) - 1;
+              item_base = scan[n_s + 1 + s] + prefix_items(q0 - scan[s], W); }
+            eval_expand_kernel<<<(nq + 255) / 256, 256, 0, st>>>(e->items, e->sess_off, sess_q, sess_i, (uint32_t)n_s, q0, nq, W, item_base, d_items, d_qoff, d_ss);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipEventRecord(ev[1], st));
+            LaunchParams p{};
+            p.nq = nq; p.k = tr.k; p.m = tr.m; p.how_many = tr.how_many; p.flags = tr.flags & SRN_FLAG_BUSINESS_LOGIC; p.max_len = max_len;
+            p.items_flat = d_items; p.q_off = d_qoff; p.out_ids = d_ids; p.out_scores = d_sc; p.out_counts = d_cnt;
+            if ((rc = device_predict(idx->dev, ix, p, true, st, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr))) return rc;
+            HIP_TRY(hipSetDevice(e->device));
+            HIP_TRY(hipEventRecord(ev[2], st));
+            MetricArgs a{};
+            a.items = e->items; a.sess_off = e->sess_off; a.ss = d_ss; a.ids = d_ids; a.counts = d_cnt;
+            a.freq = e->freq; a.w = e->ndcg_w; a.wsum = e->ndcg_w + SRN_MAX_HOW_MANY; a.max_freq = set->max_freq;
+            a.id_table = idx->dev->di.id_table; a.id_mask = idx->dev->di.id_mask;
+            a.nq = nq; a.how_many = tr.how_many; a.length = tr.length; a.terms = d_terms; a.cover = bitmap; a.err = err;
+            eval_metrics_kernel<<<(nq + kMetricWaves - 1) / kMetricWaves, 64 * kMetricWaves, 0, st>>>(a);
+            HIP_TRY(hipGetLastError());
+            eval_group_kernel<<<(nq + kGroup - 1) / kGroup, 64, 0, st>>>(d_terms, nq, part + (q0 / kGroup) * kSums);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipEventRecord(ev[3], st));
+            if (terms_out) {   // (test aid) the chunk's terms, 7 per query
+                std::vector<double> h((size_t)nq * kTerms);
+                HIP_TRY(hipMemcpyAsync(h.data(), d_terms, h.size() * 8, hipMemcpyDeviceToHost, st));
+                HIP_TRY(hipStreamSynchronize(st));
+                for (uint32_t q = 0; q < nq; ++q) std::copy(h.begin() + (size_t)q * kTerms, h.begin() + (size_t)q * kTerms + 7, terms_out + (q0 + q) * 7);
+            }
+        }
+        eval_popcount_kernel<<<std::min<uint32_t>((bitmap_words + 255) / 256, 1024), 256, 0, st>>>(bitmap, bitmap_words, covered + ti);
+        HIP_TRY(hipGetLastError());
+        trial_events[ti].second = ev_at;
+    }
+    // results: the groups' partial sums in group order
+    std::vector<double> part(std::max<size_t>(n_trials * n_groups * kSums, 1));
+    std::vector<unsigned long long> cov(std::max<size_t>(n_trials, 1)); uint32_t h_err = 0;
+    if (n_trials * n_groups) HIP_TRY(hipMemcpyAsync(part.data(), e->part, n_trials * n_groups * kSums * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(cov.data(), covered, n_trials * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&h_err, err, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (h_err) return fail(SRN_ERANGE, "a query exceeded the kernel's table limits");
+    for (size_t ti = 0; ti < n_trials; ++ti) {
+        srn_eval_result_t& r = out[ti];
+        r = srn_eval_result_t{};
+        double s[kSums] = {0, 0, 0, 0, 0, 0};
+        for (uint64_t g = 0; g < n_groups; ++g)
+            for (uint32_t j = 0; j < kSums; ++j) s[j] += part[(ti * n_groups + g) * kSums + j];
+        r.n_evaluations = nq_all;
+        r.sum_mrr = s[0]; r.sum_hit_rate = s[1]; r.sum_ndcg = s[2]; r.sum_precision = s[3]; r.sum_recall = s[4]; r.sum_popularity = s[5];
+        const double n = (double)nq_all;
+        auto avg = [&](double v) { return nq_all ? v / n : 0.0; };
+        r.mrr = avg(s[0]); r.hit_rate = avg(s[1]); r.ndcg = avg(s[2]); r.precision = avg(s[3]); r.recall = avg(s[4]); r.popularity = avg(s[5]);
+        const double f = 2.0 * (r.precision * r.recall) / (r.precision + r.recall);
+        r.f1score = std::isnan(f) ? 0.0 : f;                                               // f1score.rs:27-36
+        r.covered_items = cov[ti]; r.unique_training_items = set->unique_training_items;
+        r.coverage = set->unique_training_items ? (double)cov[ti] / (double)set->unique_training_items : 0.0;
+        for (size_t k = trial_events[ti].first; k < trial_events[ti].second; k += 4) {
+            float a = 0, b = 0, c = 0;
+            HIP_TRY(hipEventElapsedTime(&a, e->ev[k], e->ev[k + 1]));
+            HIP_TRY(hipEventElapsedTime(&b, e->ev[k + 1], e->ev[k + 2]));
+            HIP_TRY(hipEventElapsedTime(&c, e->ev[k + 2], e->ev[k + 3]));
+            r.ms_eval += (double)a + (double)c; r.ms_predict += (double)b;
+        }
+    }
+    return SRN_OK;
+}
+
+}  // namespace srn

@@ -217,3 +217,23 @@ struct srn_index {
 struct srn_sessions {
     srn::Sessions s;
 };
+
+// ---- offline evaluation (srn_eval.hip): test sessions + training-item frequencies bound to one index ----
+namespace srn { struct EvalDevice; }
+struct srn_eval_set {
+    const srn_index* idx = nullptr;
+    std::vector<uint64_t> sess_off;      // host copy of the test sessions' offsets (the per-window query / item scans)
+    uint64_t max_session_len = 0;
+    double max_freq = 1.0;               // largest training count (1 without training items, as a 0 / 0 never arises)
+    uint64_t unique_training_items = 0;
+    srn::EvalDevice* dev = nullptr;
+};
+namespace srn {
+int eval_set_create(const srn_index* idx, const uint64_t* items_flat, const uint64_t* sess_off, size_t n_sessions,
+                    const uint64_t* train_ids, const uint64_t* train_counts, size_t n_train, srn_eval_set** out);
+int eval_set_from_tsv(const srn_index* idx, const char* test_path, const char* train_path, srn_eval_set** out);
+// trials already checked (srn_capi.cpp).  terms != nullptr: one trial, its per-query terms [n * 7] (cap entries of room)
+int eval_run(srn_eval_set* set, const srn_eval_trial_t* trials, size_t n_trials, srn_eval_result_t* out, void* stream, double* terms, size_t cap);
+uint64_t eval_n_queries(const srn_eval_set* set);   // queries of any trial: sum over sessions of (len - 1)
+void eval_set_free(srn_eval_set* set);
+}  // namespace srn

@@ -1,0 +1,162 @@
+"""Hyper-parameter search over srn_evaluate: the reference's exhaustive_grid_search.rs and hyperparameter_search.rs on the GPU.
+
+One index serves every m up to its m_index (posting lists are most-recent-first and the m-cut never admits an entry past position m,
+vmis_index.rs:325-390), and only idf_weighting is baked into an index (mod.rs:146-152).  So search() builds one index per distinct
+idf weighting, at the largest m asked for with it, and evaluates all of that weighting's trials in one srn_evaluate call.
+
+    python -m serenade_amd.hpo <config.toml> [--random N --seed S]
+
+reads the [hyperparam] keys of the reference's configuration (training_data_path, test_data_path, save_records, out_path,
+enable_business_logic), writes exhaustive_grid_search.rs's CSV and prints its "Best ..." lines.  TPE (tpe_hyperparameter_optm.rs) is
+not restated: evaluate() takes any list of trials, so an external optimiser can drive it.
+"""
+import argparse
+import ctypes as C
+import itertools
+import random as _random
+import sys
+
+import numpy as np
+
+from . import capi
+from .evaluation import EvalSet, evaluate
+from .vmisknn import VMISIndex
+
+# exhaustive_grid_search.rs:22-25, loop order m > k > window > idf (:48-51)
+EXHAUSTIVE_GRID = {"m": [100, 500, 1000, 2500], "k": [50, 100, 500, 1000, 1500], "max_items_in_session": [1, 2, 3, 5, 7, 10],
+                   "idf_weighting": [1, 2, 3, 5, 7, 10]}
+# hyperparameter_search.rs:12-21 (150 random combinations, kept only where k <= m)
+RANDOM_GRID = {"m": [100, 250, 500, 750, 1000, 2500], "k": [50, 100, 500, 1000, 1500], "max_items_in_session": [1, 2, 3, 5, 7, 15, 100],
+               "idf_weighting": [1, 2, 3]}
+_KEYS = ("m", "k", "max_items_in_session", "idf_weighting")
+GOAL = "MRR@20"
+
+
+def exhaustive(grid=EXHAUSTIVE_GRID):
+    """The Cartesian product in the reference's loop order -> list of trial dicts (m, k, max_items_in_session, idf_weighting)."""
+    return [dict(zip(_KEYS, c)) for c in itertools.product(*(grid[k] for k in _KEYS))]
+
+
+def random(grid=RANDOM_GRID, n=150, seed=0, k_le_m=False):
+    """n distinct combinations drawn with a seeded generator (the reference draws from thread_rng); k_le_m drops those with k > m afterwards,
+    as hyperparameter_search.rs does."""
+    every = exhaustive(grid)
+    picks = [every[i] for i in _random.Random(seed).sample(range(len(every)), min(int(n), len(every)))]
+    return [t for t in picks if t["k"] <= t["m"]] if k_le_m else picks
+
+
+def index_plan(trials):
+    """{idf_weighting: m_index}: one index per distinct idf weighting, at the largest m of its trials."""
+    plan = {}
+    for t in trials:
+        w = float(t["idf_weighting"])
+        plan[w] = max(plan.get(w, 0), int(t["m"]))
+    return plan
+
+
+def _build_index(sessions, m_index, idf_weighting, device):
+    """VMISIndex::new_from_csv's index (p99.5 session-length cut) on sessions read once."""
+    q = C.c_uint64()
+    capi.check(capi.lib().srn_sessions_length_quantile(sessions, 0.995, C.byref(q)))
+    v = capi.SessionsView()
+    capi.check(capi.lib().srn_sessions_view(sessions, C.byref(v)))
+    h = C.c_void_p()
+    capi.check(capi.lib().srn_index_build_gpu(C.byref(v), int(m_index), int(q.value), float(idf_weighting), int(device), C.byref(h)))
+    return VMISIndex(h)
+
+
+def search(train_path, test_path, trials, business_logic=False, device=0, how_many=20, length=20):
+    """objective() (src/objective.rs:8-52) for every trial: Mrr@length of predict(k, m, how_many) over every windowed prefix.
+    -> {"records": [one per trial, in trial order], "best": the first record of the highest Mrr}."""
+    trials = [dict(t) for t in trials]
+    sessions = C.c_void_p()
+    capi.check(capi.lib().srn_sessions_from_tsv(str(train_path).encode(), C.byref(sessions)))
+    records = [None] * len(trials)
+    try:
+        for w, m_index in index_plan(trials).items():
+            index = _build_index(sessions, m_index, w, device)
+            es = EvalSet.from_tsv(index, test_path, train_path)
+            mine = [i for i, t in enumerate(trials) if float(t["idf_weighting"]) == w]
+            reps = evaluate(es, [dict(k=trials[i]["k"], m=trials[i]["m"], max_items_in_session=trials[i]["max_items_in_session"], how_many=how_many,
+                                      length=length, business_logic=business_logic) for i in mine])
+            for i, rep in zip(mine, reps):
+                t = trials[i]
+                records[i] = {"iteration": i, "n_most_recent_sessions": int(t["m"]), "neighborhood_size_k": int(t["k"]),
+                              "last_items_in_session": int(t["max_items_in_session"]), "idf_weighting": t["idf_weighting"],
+                              GOAL: rep["Mrr@%d" % length], "report": rep}
+            es.close()
+            index.close()
+    finally:
+        capi.lib().srn_sessions_free(sessions)
+    best = None
+    for r in records:   # strictly greater: the first of equal values wins, as in the reference
+        if best is None or r[GOAL] > best[GOAL]:
+            best = r
+    return {"records": records, "best": best}
+
+
+def rust_f64(v):
+    """f64's Display in Rust: shortest round-trip digits, no exponent, no trailing ".0"."""
+    v = float(v)
+    if v != v or v in (float("inf"), float("-inf")):
+        return {True: "NaN", False: "inf" if v > 0 else "-inf"}[v != v]
+    return np.format_float_positional(v, unique=True, trim="-")
+
+
+def read_toml(path):
+    """The small TOML subset the evaluator reads (serenade_amd/csrc/host/evaluator.cpp read_toml): [section] headers, key = value, # comments,
+    quoted strings unquoted -> {"section.key": "value"}."""
+    kv, section = {}, ""
+    with open(path) as f:
+        for line in f:
+            line = line.split("#", 1)[0].strip()
+            if not line:
+                continue
+            if line.startswith("["):
+                section = line[1:line.index("]")].strip()
+                continue
+            if "=" not in line:
+                continue
+            k, v = (x.strip() for x in line.split("=", 1))
+            if len(v) >= 2 and v[0] == '"' and v[-1] == '"':
+                v = v[1:-1]
+            kv[section + "." + k] = v
+    return kv
+
+
+def hyperparam_config(path):
+    kv = read_toml(path)
+    return {"training_data_path": kv.get("hyperparam.training_data_path", ""), "test_data_path": kv.get("hyperparam.test_data_path", ""),
+            "save_records": kv.get("hyperparam.save_records", "false") == "true", "out_path": kv.get("hyperparam.out_path", "results.csv"),
+            "enable_business_logic": kv.get("hyperparam.enable_business_logic", "false") == "true"}
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(prog="python -m serenade_amd.hpo", description="exhaustive (or random) hyper-parameter search on the GPU")
+    ap.add_argument("config")
+    ap.add_argument("--random", type=int, default=0, help="N random combinations of the exhaustive grid instead of all of it")
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--device", type=int, default=0)
+    a = ap.parse_args(argv)
+    cfg = hyperparam_config(a.config)
+    trials = random(EXHAUSTIVE_GRID, a.random, a.seed) if a.random else exhaustive()
+    res = search(cfg["training_data_path"], cfg["test_data_path"], trials, cfg["enable_business_logic"], a.device)
+    with open(cfg["out_path"], "w") as f:   # exhaustive_grid_search.rs:34-46 (the file is created either way)
+        if cfg["save_records"]:
+            f.write("iteration,n_most_recent_sessions,neighborhood_size_k,last_items_in_session,idf_weighting,%s\n" % GOAL)
+            for r in res["records"]:
+                f.write("%d,%d,%d,%d,%d,%s\n" % (r["iteration"], r["n_most_recent_sessions"], r["neighborhood_size_k"], r["last_items_in_session"],
+                                                 int(r["idf_weighting"]), rust_f64(r[GOAL])))
+    b = res["best"]
+    none = b is None
+    print("Best n_most_recent_sessions: %d" % (-1 if none else b["n_most_recent_sessions"]))
+    print("Best neighborhood_size_k: %d" % (-1 if none else b["neighborhood_size_k"]))
+    print("Best last_items_in_session: %d" % (-1 if none else b["last_items_in_session"]))
+    print("Best idf_weighting: %d" % (-1 if none else int(b["idf_weighting"])))
+    print("Business logic were %s." % ("enabled" if cfg["enable_business_logic"] else "disabled"))
+    print("Best value for the goal metric: %s" % rust_f64(float("-inf") if none else b[GOAL]))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

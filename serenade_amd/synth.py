@@ -91,6 +91,17 @@ def queries(n_sessions, n_items, seed=SEED, alpha=ZIPF_ALPHA, max_items=LAST_ITE
     return (items, off, nxt) if with_next else (items, off)
 
 
+def test_sessions(n_sessions, n_items, seed=SEED, alpha=ZIPF_ALPHA):
+    """The whole held-out sessions behind queries(): {session number: items in order}.  Sessions of one event give no query and are not listed.
+    Rebuilt from the prefixes at a window of 255: a session starts at its one-item prefix, and every prefix's next item is its next event."""
+    items, off, nxt = queries(n_sessions, n_items, seed=seed, alpha=alpha, max_items=255, with_next=True)
+    lens = np.diff(off.astype(np.int64))
+    starts = np.flatnonzero(lens == 1)
+    ends = np.append(starts[1:], len(lens))
+    first = items[off[starts].astype(np.int64)]
+    return {i: [int(first[i])] + nxt[a:b].tolist() for i, (a, b) in enumerate(zip(starts, ends))}
+
+
 TIE_MODES = {"ours": 0, "reverse": 1, "mixed": 2, "per-item": 3}
 
 

@@ -1,0 +1,142 @@
+"""Evaluation throughput on one GPU: one trial through srn_evaluate (a) against predict's floor on the same prefixes, device-resident
+(srn_predict_batch_device, b) and against the evaluator's path -- host expansion, srn_predict_batch from pageable memory, metrics on one host
+core -- in C++ (tools/eval_host_path.cpp, c); then a 24-trial grid in one srn_evaluate call.  Writes one JSON file.
+
+    python tools/eval_bench.py [--config cfg3] [--queries 1048576] [--reps 3] [--out profiles/eval_bench_cfg3.json]
+"""
+import argparse
+import ctypes as C
+import json
+import os
+import subprocess
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def host_path_lib():
+    from serenade_amd import build
+    src = os.path.join(ROOT, "tools", "eval_host_path.cpp")
+    out = os.path.join(ROOT, "serenade_amd", "bin", "libeval_host_path.so")
+    if build._stale(out, [src, build.LIB]):
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", out, src, "-L" + os.path.dirname(build.LIB), "-lserenade_hip",
+                               "-Wl,-rpath," + os.path.dirname(build.LIB), "-Wl,-rpath,/opt/rocm/lib"])
+    L = C.CDLL(out)
+    L.srn_host_eval_path.restype = C.c_int
+    L.srn_host_eval_path.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t] + [C.c_size_t] * 5 + [C.c_uint, C.c_void_p, C.c_void_p]
+    return L
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--config", default="cfg3")
+    ap.add_argument("--queries", type=int, default=1 << 20)
+    ap.add_argument("--window", type=int, default=4)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--skip-host", action="store_true", help="leave out (c)")
+    ap.add_argument("--grid", type=int, default=1, help="0: leave out the 24-trial call")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "eval_bench_cfg3.json"))
+    a = ap.parse_args()
+    import torch
+    import serenade_amd as sa
+    from serenade_amd import capi, evaluation, synth
+
+    inter, n_items, k, m, idfw = synth.CONFIGS[a.config]
+    how_many, length, W = 21, 20, a.window
+    t0 = time.time()
+    off, items, ts = synth.training_sessions(inter, n_items)
+    index = sa.VMISIndex.from_sessions(off, items, ts, m, 34, idfw, device=0, builder="gpu")
+    t_index = time.time() - t0
+    n_sess = max(1024, int(a.queries / 3.2) + 4096)
+    sessions = synth.test_sessions(n_sess, n_items, seed=synth.SEED + 7919)
+    keep, nq = {}, 0
+    for s, ev in sessions.items():   # whole sessions up to the query budget
+        if nq + len(ev) - 1 > a.queries:
+            break
+        keep[s] = ev
+        nq += len(ev) - 1
+    sessions = keep
+    t0 = time.time()
+    es = evaluation.EvalSet(index, sessions, items)
+    t_set = time.time() - t0
+    trial = dict(k=k, m=m, max_items_in_session=W, how_many=how_many, length=length)
+    res = {"config": a.config, "k": k, "m": m, "window": W, "how_many": how_many, "length": length, "test_sessions": len(sessions), "queries": nq,
+           "index_build_s": round(t_index, 2), "eval_set_create_s": round(t_set, 3)}
+
+    # (a) srn_evaluate, one trial per call
+    evaluation.evaluate(es, [trial])
+    wall, rep = [], None
+    for _ in range(a.reps):
+        t0 = time.perf_counter()
+        rep = evaluation.evaluate(es, [trial])[0]
+        wall.append((time.perf_counter() - t0) * 1e3)
+    res["a_evaluate"] = {"wall_ms": wall, "ms_predict": rep["ms_predict"], "ms_eval": rep["ms_eval"], "Mrr@20": rep["Mrr@20"], "HitRate@20": rep["HitRate@20"]}
+
+    # (b) the same prefixes through srn_predict_batch_device alone
+    prefixes = [ev[max(0, st - W):st] for ev in sessions.values() for st in range(1, len(ev))]   # evaluator.rs:46-56
+    qoff = np.zeros(len(prefixes) + 1, np.uint32)
+    qoff[1:] = np.cumsum([len(p) for p in prefixes])
+    flat = np.fromiter((x for p in prefixes for x in p), dtype=np.uint64, count=int(qoff[-1]))
+    dev = torch.device("cuda:0")
+    d_items = torch.from_numpy(flat.view(np.int64)).to(dev)
+    d_qoff = torch.from_numpy(qoff.view(np.int32)).to(dev)
+    d_ids = torch.empty(nq * how_many, dtype=torch.int64, device=dev)
+    d_sc = torch.empty(nq * how_many, dtype=torch.float64, device=dev)
+    d_cnt = torch.empty(nq, dtype=torch.int32, device=dev)
+    stream = torch.cuda.current_stream().cuda_stream
+    max_len = int(np.diff(qoff.astype(np.int64)).max())
+
+    def run_b():
+        sa.predict_batch_device(index, d_items.data_ptr(), d_qoff.data_ptr(), nq, max_len, k, m, how_many, False, d_ids.data_ptr(), d_sc.data_ptr(),
+                                d_cnt.data_ptr(), stream)
+    run_b()
+    torch.cuda.synchronize()
+    wall_b = []
+    for _ in range(a.reps):
+        t0 = time.perf_counter()
+        run_b()
+        torch.cuda.synchronize()
+        wall_b.append((time.perf_counter() - t0) * 1e3)
+    res["b_predict_device"] = {"wall_ms": wall_b}
+    res["a_over_b"] = round(min(wall) / min(wall_b), 3)
+    res["eval_kernels_share_of_predict"] = round(rep["ms_eval"] / rep["ms_predict"], 4) if rep["ms_predict"] else None
+
+    # (c) the evaluator's path in C++
+    if not a.skip_host:
+        L = host_path_lib()
+        s_items = np.ascontiguousarray(np.concatenate([np.asarray(v, np.uint64) for v in sessions.values()]), np.uint64)
+        s_off = np.zeros(len(sessions) + 1, np.uint64)
+        s_off[1:] = np.cumsum([len(v) for v in sessions.values()])
+        tr = np.ascontiguousarray(items, np.uint64)
+        ms3, mrr = (C.c_double * 3)(), C.c_double()
+        rows = []
+        for _ in range(max(1, a.reps - 1)):
+            capi.check(L.srn_host_eval_path(index._h, capi.ptr(s_items), capi.ptr(s_off), len(sessions), capi.ptr(tr), len(tr), k, m, how_many, W, length, 0,
+                                            ms3, C.byref(mrr)))
+            rows.append(list(ms3))
+        res["c_host_path"] = {"expand_predict_metrics_ms": rows, "total_ms": [sum(r) for r in rows], "Mrr@20": mrr.value}
+        res["c_over_a"] = round(min(sum(r) for r in rows) / min(wall), 2)
+
+    # a 24-trial grid in one call
+    if a.grid:
+        grid = [dict(k=kk, m=mm, max_items_in_session=w, how_many=how_many, length=length) for mm in (1000, m) for kk in (100, 500, 1000) for w in (1, 2, 3, 4)
+                if kk <= mm]
+        grid = grid[:24]
+        t0 = time.perf_counter()
+        reps = evaluation.evaluate(es, grid)
+        res["grid"] = {"trials": len(grid), "wall_ms": (time.perf_counter() - t0) * 1e3, "ms_predict": sum(r["ms_predict"] for r in reps),
+                       "ms_eval": sum(r["ms_eval"] for r in reps), "queries_per_trial": nq,
+                       "best_mrr": max((r["Mrr@20"], i) for i, r in enumerate(reps))[0]}
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
