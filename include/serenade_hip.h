@@ -103,6 +103,21 @@ int srn_sessions_view(const srn_sessions_t* s, srn_sessions_view_t* out);
  * the reference's t-digest estimate qty_events_p99_5 (vmis_index.rs:689-716, used at :67). */
 int srn_sessions_length_quantile(const srn_sessions_t* s, double q, uint64_t* out);
 void srn_sessions_free(srn_sessions_t* s);
+/* read_from_file (vmis_index.rs:591-686) on the GPU: the same sessions as srn_sessions_from_tsv, bit for bit.  The file is read in
+ * chunks and parsed on the device; time fields outside the exact decimal form the device certifies are parsed by the host loader's
+ * own code.  < 2^32 rows (SRN_ERANGE above: the host loader remains for those).  device < 0: SRN_ENODEV; a missing file: SRN_EIO. */
+int srn_sessions_from_tsv_gpu(const char* path, int device, srn_sessions_t** out);
+#define SRN_EVENTS_TIME_I64 1u /* times are int64 seconds (negative -> 0) instead of f64 */
+#define SRN_EVENTS_DEVICE 2u   /* the three arrays are device memory on `device` (read on `stream`, never copied to the host) */
+/* the same semantics over rows already in memory, in file order; times as f64 (rounded like the file's) or,
+ * with SRN_EVENTS_TIME_I64, int64 seconds (negative -> 0); SRN_EVENTS_DEVICE: the three arrays are device memory on `device` */
+int srn_sessions_from_events(const uint64_t* session_ids, const uint64_t* item_ids, const void* times, size_t n,
+                             unsigned flags, int device, void* stream, srn_sessions_t** out);
+typedef struct {
+    uint64_t lines, rows, skipped, host_parsed; /* lines of the file, rows kept, lines skipped (header, empty, unparsable), lines parsed on the host */
+    double ms_read, ms_upload, ms_parse, ms_group, ms_download;
+} srn_load_info_t;
+int srn_sessions_load_info(const srn_sessions_t* s, srn_load_info_t* out); /* zeros for a host-loaded handle */
 
 /* ---- index ------------------------------------------------------------------------------ */
 
@@ -121,6 +136,9 @@ int srn_index_build_gpu(const srn_sessions_view_t* sessions, size_t m_index, siz
  * max_session_len = 0 selects the exact p99.5 of the session lengths. */
 int srn_index_new_from_csv(const char* path, size_t m_most_recent_sessions, double idf_weighting,
                            size_t max_session_len, int device, srn_index_t** out);
+/* VMISIndex::new_from_csv with the GPU loader + GPU builder (falls back to the host builder exactly where srn_index_new_from_csv does) */
+int srn_index_new_from_csv_gpu(const char* path, size_t m_most_recent_sessions, double idf_weighting,
+                               size_t max_session_len, int device, srn_index_t** out);
 /* VMISIndex::new(base_path) (src/vmisknn/vmis_index.rs:85-314): the pre-built production index, two directories of Avro
  * object-container files (codec null or snappy):
  *   <base>/itemindex/[files].avro     {ItemId: long, session_indices_time_ordered: array<int>, idf: double, ForSale, IsAdult: boolean}

@@ -63,6 +63,14 @@ class EvalResult(C.Structure):
                [("covered_items", C.c_uint64), ("unique_training_items", C.c_uint64), ("ms_predict", C.c_double), ("ms_eval", C.c_double)]
 
 
+class LoadInfo(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("lines", "rows", "skipped", "host_parsed")] + \
+               [(n, C.c_double) for n in ("ms_read", "ms_upload", "ms_parse", "ms_group", "ms_download")]
+
+
+EVENTS_TIME_I64, EVENTS_DEVICE = 1, 2
+
+
 class Limits(C.Structure):
     _fields_ = [("max_how_many", C.c_uint32), ("max_session_len", C.c_uint32), ("max_k", C.c_uint32), ("reserved", C.c_uint32)]
 
@@ -74,6 +82,10 @@ SYMBOLS = {
     "srn_sessions_view": (_i, [_vp, C.POINTER(SessionsView)]),
     "srn_sessions_length_quantile": (_i, [_vp, C.c_double, C.POINTER(_u64)]),
     "srn_sessions_free": (None, [_vp]),
+    "srn_sessions_from_tsv_gpu": (_i, [C.c_char_p, _i, C.POINTER(_vp)]),
+    "srn_sessions_from_events": (_i, [_vp, _vp, _vp, _sz, C.c_uint, _i, _vp, C.POINTER(_vp)]),
+    "srn_sessions_load_info": (_i, [_vp, C.POINTER(LoadInfo)]),
+    "srn_index_new_from_csv_gpu": (_i, [C.c_char_p, _sz, C.c_double, _sz, _i, C.POINTER(_vp)]),
     "srn_index_build": (_i, [C.POINTER(SessionsView), _sz, _sz, C.c_double, _i, C.POINTER(_vp)]),
     "srn_index_new_from_avro": (_i, [C.c_char_p, _i, C.POINTER(_vp)]),
     "srn_index_build_gpu": (_i, [C.POINTER(SessionsView), _sz, _sz, C.c_double, _i, C.POINTER(_vp)]),

@@ -96,6 +96,34 @@ int srn_sessions_length_quantile(const srn_sessions_t* s, double q, uint64_t* ou
 }
 void srn_sessions_free(srn_sessions_t* s) { delete s; }
 
+int srn_sessions_from_tsv_gpu(const char* path, int device, srn_sessions_t** out) {
+    return guarded([&]() -> int {
+        if (!path || !out) return fail(SRN_EINVAL, "null argument");
+        *out = nullptr;
+        if (device < 0) return fail(SRN_ENODEV, "the GPU loader needs a device");
+        srn_sessions* s = new srn_sessions();
+        int rc = sessions_from_tsv_gpu(path, device, s->s, &s->info);
+        if (rc) { delete s; return rc; }
+        *out = s; return SRN_OK; });
+}
+int srn_sessions_from_events(const uint64_t* session_ids, const uint64_t* item_ids, const void* times, size_t n, unsigned flags, int device, void* stream,
+                             srn_sessions_t** out) {
+    return guarded([&]() -> int {
+        if (!out || (n && (!session_ids || !item_ids || !times))) return fail(SRN_EINVAL, "null argument");
+        *out = nullptr;
+        if (flags & ~(SRN_EVENTS_TIME_I64 | SRN_EVENTS_DEVICE)) return fail(SRN_EINVAL, "unknown flags");
+        if (device < 0) return fail(SRN_ENODEV, "the GPU loader needs a device");
+        srn_sessions* s = new srn_sessions();
+        int rc = sessions_from_events(session_ids, item_ids, times, n, flags, device, stream, s->s, &s->info);
+        if (rc) { delete s; return rc; }
+        *out = s; return SRN_OK; });
+}
+int srn_sessions_load_info(const srn_sessions_t* s, srn_load_info_t* out) {
+    if (!s || !out) return fail(SRN_EINVAL, "null argument");
+    *out = s->info;
+    return SRN_OK;
+}
+
 int srn_index_build(const srn_sessions_view_t* sessions, size_t m_index, size_t max_session_len, double idf_weighting,
                     int device, srn_index_t** out) {
     return guarded([&]() -> int {
@@ -130,6 +158,21 @@ int srn_index_new_from_csv(const char* path, size_t m_most_recent_sessions, doub
         srn_sessions_view_t v{s.off.data(), s.items.data(), s.ts.data(), s.ts.size()};
         // same bytes either way; the GPU builder covers what fits 32-bit ranks and offsets
         const bool gpu = device >= 0 && s.ts.size() < 0xFFFFFFFFull && s.items.size() < 0xFFFFFFFFull;
+        return gpu ? srn_index_build_gpu(&v, m_most_recent_sessions, max_session_len, idf_weighting, device, out)
+                   : srn_index_build(&v, m_most_recent_sessions, max_session_len, idf_weighting, device, out); });
+}
+
+int srn_index_new_from_csv_gpu(const char* path, size_t m_most_recent_sessions, double idf_weighting, size_t max_session_len,
+                               int device, srn_index_t** out) {
+    return guarded([&]() -> int {
+        if (!path || !out) return fail(SRN_EINVAL, "null argument");
+        *out = nullptr;
+        if (device < 0) return fail(SRN_ENODEV, "the GPU loader needs a device");
+        Sessions s; int rc = sessions_from_tsv_gpu(path, device, s, nullptr); if (rc) return rc;
+        if (max_session_len == 0) max_session_len = sessions_length_quantile_counting(s.off.data(), s.ts.size(), 0.995);
+        srn_sessions_view_t v{s.off.data(), s.items.data(), s.ts.data(), s.ts.size()};
+        // as srn_index_new_from_csv: the GPU builder where 32-bit ranks and offsets suffice
+        const bool gpu = s.ts.size() < 0xFFFFFFFFull && s.items.size() < 0xFFFFFFFFull;
         return gpu ? srn_index_build_gpu(&v, m_most_recent_sessions, max_session_len, idf_weighting, device, out)
                    : srn_index_build(&v, m_most_recent_sessions, max_session_len, idf_weighting, device, out); });
 }

@@ -52,6 +52,13 @@ bool parse_line(const char* p, const char* end, Row& r) {
 }
 }  // namespace
 
+bool parse_tsv_line(const char* p, const char* end, uint64_t& session, uint64_t& item, uint64_t& time) {
+    Row r;
+    if (!parse_line(p, end, r)) return false;
+    session = r.session; item = r.item; time = r.time;
+    return true;
+}
+
 int sessions_from_tsv(const char* path, Sessions& out) {
     FILE* f = fopen(path, "rb");
     if (!f) return fail(SRN_EIO, std::string("cannot open ") + path);

@@ -37,6 +37,13 @@ struct Sessions {
 };
 int sessions_from_tsv(const char* path, Sessions& out);
 uint64_t sessions_length_quantile(const uint64_t* off, size_t n, double q);
+bool parse_tsv_line(const char* p, const char* end, uint64_t& session, uint64_t& item, uint64_t& time);   // one line of sessions_from_tsv (false: skipped)
+// the GPU loader (srn_ingest.hip): the same sessions as sessions_from_tsv; info (may be null) gets the load's counts and stage times
+int sessions_from_tsv_gpu(const char* path, int device, Sessions& out, srn_load_info_t* info);
+int sessions_from_events(const uint64_t* session_ids, const uint64_t* item_ids, const void* times, size_t n, unsigned flags, int device, void* stream,
+                         Sessions& out, srn_load_info_t* info);
+uint64_t sessions_length_quantile_counting(const uint64_t* off, size_t n, double q);   // = sessions_length_quantile, by counting the lengths
+void ingest_reload_knobs();                                                              // SRN_INGEST_CHUNK_BYTES
 
 // ---- the flat index (host copy).  Layout and invariants: DESIGN.md "Data layout in HBM" ----
 struct FlatIndex {
@@ -216,6 +223,7 @@ struct srn_index {
 };
 struct srn_sessions {
     srn::Sessions s;
+    srn_load_info_t info{};   // the GPU loader's counts and stage times (zeros for the host loader)
 };
 
 // ---- offline evaluation (srn_eval.hip): test sessions + training-item frequencies bound to one index ----

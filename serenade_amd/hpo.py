@@ -65,12 +65,18 @@ def _build_index(sessions, m_index, idf_weighting, device):
     return VMISIndex(h)
 
 
-def search(train_path, test_path, trials, business_logic=False, device=0, how_many=20, length=20):
+def search(train_path, test_path, trials, business_logic=False, device=0, how_many=20, length=20, loader="host"):
     """objective() (src/objective.rs:8-52) for every trial: Mrr@length of predict(k, m, how_many) over every windowed prefix.
+    loader="gpu" reads the training sessions with the GPU loader (srn_sessions_from_tsv_gpu: the same sessions).
     -> {"records": [one per trial, in trial order], "best": the first record of the highest Mrr}."""
     trials = [dict(t) for t in trials]
     sessions = C.c_void_p()
-    capi.check(capi.lib().srn_sessions_from_tsv(str(train_path).encode(), C.byref(sessions)))
+    if loader == "gpu":
+        capi.check(capi.lib().srn_sessions_from_tsv_gpu(str(train_path).encode(), int(device), C.byref(sessions)))
+    elif loader == "host":
+        capi.check(capi.lib().srn_sessions_from_tsv(str(train_path).encode(), C.byref(sessions)))
+    else:
+        raise ValueError("loader must be 'host' or 'gpu'")
     records = [None] * len(trials)
     try:
         for w, m_index in index_plan(trials).items():
@@ -137,10 +143,12 @@ def main(argv=None):
     ap.add_argument("--random", type=int, default=0, help="N random combinations of the exhaustive grid instead of all of it")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--gpu-loader", action="store_true", help="read the training file with the GPU loader (the same sessions)")
     a = ap.parse_args(argv)
     cfg = hyperparam_config(a.config)
     trials = random(EXHAUSTIVE_GRID, a.random, a.seed) if a.random else exhaustive()
-    res = search(cfg["training_data_path"], cfg["test_data_path"], trials, cfg["enable_business_logic"], a.device)
+    res = search(cfg["training_data_path"], cfg["test_data_path"], trials, cfg["enable_business_logic"], a.device,
+                 loader="gpu" if a.gpu_loader else "host")
     with open(cfg["out_path"], "w") as f:   # exhaustive_grid_search.rs:34-46 (the file is created either way)
         if cfg["save_records"]:
             f.write("iteration,n_most_recent_sessions,neighborhood_size_k,last_items_in_session,idf_weighting,%s\n" % GOAL)

@@ -127,3 +127,62 @@ def avro_index(base, off, items, ts, m_index, max_len, idf_weighting, tie_mode="
     if rc:
         raise IOError("could not write the Avro index under %s" % base)
     return ids, loff, lsess[:nnz], idf
+
+
+def training_events(off, items, ts, seed=SEED, duplicates=0.01):
+    """The sessions as click-log rows in shuffled order -> (session_ids u64, item_ids u64, times f64): a session's rows end at its timestamp, one
+    second apart, about half of them on a half second (so both roundings occur); a `duplicates` fraction of rows repeats an earlier (session, item)."""
+    rng = np.random.default_rng(seed)
+    off = np.asarray(off, np.int64)
+    lens = np.diff(off)
+    sess = np.repeat(np.arange(len(lens), dtype=np.uint64) * 7 + 3, lens)
+    pos = np.arange(len(items), dtype=np.int64) - np.repeat(off[:-1], lens)
+    times = np.repeat(np.asarray(ts, np.float64), lens) - (np.repeat(lens, lens) - 1 - pos) + 0.5 * rng.integers(0, 2, len(items)) - 0.5
+    it = np.asarray(items, np.uint64)
+    dup = rng.random(len(items)) < duplicates
+    sess, it, times = np.concatenate([sess, sess[dup]]), np.concatenate([it, it[dup]]), np.concatenate([times, times[dup] + 1.0])
+    order = rng.permutation(len(sess))
+    return sess[order], it[order], times[order]
+
+
+def _digits(v, width):
+    """u64 column -> (n x width) ASCII digits right-aligned, and the mask of the significant ones (at least one)."""
+    out = np.empty((len(v), width), np.uint8)
+    x = v.astype(np.uint64).copy()
+    for c in range(width - 1, -1, -1):
+        out[:, c] = (x % 10).astype(np.uint8) + 48
+        x //= 10
+    n = np.maximum(1, np.floor(np.log10(np.maximum(v.astype(np.float64), 1))).astype(np.int64) + 1)
+    return out, np.arange(width)[None, :] >= (width - n)[:, None]
+
+
+def write_training_tsv(path, session_ids, item_ids, times, bad_lines=0, seed=SEED, rows_per_block=1 << 22):
+    """A training TSV ("SessionId\\tItemId\\tTime", header first) of the rows in the given order; times are written with one decimal
+    (x.0 / x.5).  bad_lines unparsable lines go in at seeded positions.  Vectorised: tens of millions of rows take seconds."""
+    rng = np.random.default_rng(seed)
+    n = len(session_ids)
+    bad_at = set(rng.integers(0, max(n, 1), bad_lines).tolist()) if bad_lines else set()
+    tab, nl, dot = np.full((1, 1), 9, np.uint8), np.full((1, 1), 10, np.uint8), np.full((1, 1), 46, np.uint8)
+    with open(path, "wb") as f:
+        f.write(b"SessionId\tItemId\tTime\n")
+        for a in range(0, n, rows_per_block):
+            b = min(n, a + rows_per_block)
+            t10 = np.round(np.asarray(times[a:b], np.float64) * 10).astype(np.int64)
+            s, ms = _digits(np.asarray(session_ids[a:b], np.uint64), 20)
+            i, mi = _digits(np.asarray(item_ids[a:b], np.uint64), 20)
+            t, mt = _digits((t10 // 10).astype(np.uint64), 20)
+            fr = ((t10 % 10).astype(np.uint8) + 48)[:, None]
+            m = b - a
+            rows = np.concatenate([s, np.repeat(tab, m, 0), i, np.repeat(tab, m, 0), t, np.repeat(dot, m, 0), fr, np.repeat(nl, m, 0)], axis=1)
+            ones = np.ones((m, 1), bool)
+            mask = np.concatenate([ms, ones, mi, ones, mt, ones, ones, ones], axis=1)
+            cuts = sorted(x - a for x in bad_at if a <= x < b)
+            if not cuts:
+                f.write(rows[mask].tobytes())
+                continue
+            prev = 0
+            for c in cuts + [m]:
+                f.write(rows[prev:c][mask[prev:c]].tobytes())
+                if c < m:
+                    f.write(b"x%d\tnot-an-item\t1.0\n" % c)
+                prev = c

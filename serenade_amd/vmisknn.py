@@ -32,12 +32,30 @@ class VMISIndex:
 
     # ---- constructors ---------------------------------------------------------------------
     @classmethod
-    def new_from_csv(cls, path_to_training, m_most_recent_sessions, idf_weighting, max_session_len=0, device=0):
+    def new_from_csv(cls, path_to_training, m_most_recent_sessions, idf_weighting, max_session_len=0, device=0, loader="host"):
         """VMISIndex::new_from_csv (vmis_index.rs:38-83).  max_session_len=0: exact p99.5 of session lengths
-        (the reference uses a t-digest estimate of the same quantile, vmis_index.rs:689-716)."""
+        (the reference uses a t-digest estimate of the same quantile, vmis_index.rs:689-716).
+        loader="gpu" parses and groups the file on the device (srn_index_new_from_csv_gpu: the same index; needs device >= 0)."""
+        if loader not in ("host", "gpu"):
+            raise ValueError("loader must be 'host' or 'gpu'")
         h = C.c_void_p()
-        capi.check(capi.lib().srn_index_new_from_csv(str(path_to_training).encode(), int(m_most_recent_sessions),
-                                                     float(idf_weighting), int(max_session_len), int(device), C.byref(h)))
+        load = capi.lib().srn_index_new_from_csv_gpu if loader == "gpu" else capi.lib().srn_index_new_from_csv
+        capi.check(load(str(path_to_training).encode(), int(m_most_recent_sessions), float(idf_weighting), int(max_session_len), int(device), C.byref(h)))
+        return cls(h)
+
+    @classmethod
+    def from_events(cls, session_ids, item_ids, times, m_most_recent_sessions, idf_weighting, max_session_len=0, device=0):
+        """new_from_csv on rows already in memory, in file order: NumPy arrays, torch tensors on the CPU, or torch tensors on this
+        device (read in place).  times: float (rounded like the file's) or integer seconds.  Grouped and built on the GPU."""
+        from .ingest import TrainingSessions
+        ts = TrainingSessions.from_events(session_ids, item_ids, times, device=device)
+        try:
+            max_len = int(max_session_len) or ts.length_quantile(0.995)
+            v = ts.view()
+            h = C.c_void_p()
+            capi.check(capi.lib().srn_index_build_gpu(C.byref(v), int(m_most_recent_sessions), max_len, float(idf_weighting), int(device), C.byref(h)))
+        finally:
+            ts.close()
         return cls(h)
 
     @classmethod
