@@ -14,7 +14,7 @@ SOURCES = ["srn_index.cpp", "srn_capi.cpp", "srn_batcher.cpp", "srn_combine.cpp"
 HEADERS = ["srn_internal.h", "srn_kernels.h", "srn_device.h", "srn_prep.h", "srn_runtime.h", os.path.join("..", "..", "include", "serenade_hip.h")]
 
 
-EXPERIMENT_ONLY_FLAGS = ("SRN_FAST_EXP_", "SRN_FAST_STOP", "SRN_ABLATE")   # "timing only, wrong results" macros of the kernels
+EXPERIMENT_ONLY_FLAGS = ("SRN_FAST_EXP_", "SRN_FAST_STOP", "SRN_FAST_EARLY_CLEAR", "SRN_ABLATE")   # "timing only, wrong results" macros of the kernels
 
 
 def _stale(target, deps):

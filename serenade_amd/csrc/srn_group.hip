@@ -123,8 +123,7 @@ struct srn_shard_group {
     ncclComm_t comm[2] = {nullptr, nullptr};   // [0] exchange stream, [1] caller's stream: operations on one communicator serialise in issue order
     srn_shard_comm_t cb{};
     hipStream_t s_x = nullptr; hipEvent_t e_in = nullptr, e_x = nullptr;
-    int* agree_dev = nullptr;   // three flags of set_postings' agreement
-    char* pres_all = nullptr; size_t pres_all_bytes = 0; uint8_t* nb_pbytes = nullptr;   // the shards' presence bitmaps (all-gathered at set_postings) and the byte per session made of them: bit g = shard g holds an item of the session
+    int* agree_dev = nullptr;   // the two flags of set_postings' agreement
     bool stream_ok = false;   // every shard of this rank holds its fragments in the posting order of g->postings (set_postings): batches of the streaming form's shape exchange positions
     bool overlap = false, no_direct = false;   // overlap: opt-in (srn_shard_group_set_overlap) -- two communicators with collectives in flight at once have never been soaked on more than one GPU
     // A batch that failed after its first collective was issued leaves the peers' collectives without their partner: the group is BROKEN on this rank from then on (every
@@ -306,8 +305,7 @@ int group_predict_neighbours(srn_shard_group* g, const LaunchParams& p_in, bool 
     Slot& s = g->slot[g->calls & 1u];
     const bool overlap = g->overlap && !local;
     hipStream_t sx = overlap ? g->s_x : user;
-    const bool pbytes = g->nb_pbytes != nullptr && device_shard_nb_presence_wanted() && p.max_len <= 8;   // (rank-invariant: the knob, the batch shape, what set_postings built on every rank)
-    const uint32_t rec_stride = device_prep_stride(p.max_len), xstride = p.k + 1u + (pbytes ? (p.k + 3u) / 4u : 0u), per = (nq + G - 1) / G;
+    const uint32_t rec_stride = device_prep_stride(p.max_len), xstride = p.k + 1u, per = (nq + G - 1) / G;
     const size_t block_bytes = ((size_t)nq * n * 16 + (size_t)nq * 4 + 255) / 256 * 256, xblock = (size_t)per * xstride * 4;
     // Streaming form (round 5): the exchange carries, instead of the neighbour slots, WHERE the neighbours sit in the query's posting lists -- a third of the bytes --, and
     // every rank's back end streams its fragments in posting order.  Chosen from rank-invariant inputs (batch shape, knobs) + what set_postings settled for this rank.
@@ -345,7 +343,6 @@ int group_predict_neighbours(srn_shard_group* g, const LaunchParams& p_in, bool 
         int rc = device_shard_nb_prep(g->shards[i]->dev, post, p, s.nrec[i], sx, &s.nord[i], &s.nord_bytes[i], &s.nord_ptr[i]); if (rc) return rc;
         const uint32_t q_lo = std::min<uint64_t>(nq, (uint64_t)gi * per), q_hi = std::min<uint64_t>(nq, (uint64_t)q_lo + per);
         rc = device_shard_nb_front(g->shards[i]->dev, g->shards[i]->flat, post, p, s.nrec[i], (uint32_t*)s.xchg, xstride, q_lo, q_hi, sx); if (rc) return rc;
-        if (pbytes && !positions) { rc = device_shard_nb_presence(g->shards[i]->dev, g->shards[i]->flat, p, s.nrec[i], (uint32_t*)s.xchg, xstride, g->nb_pbytes, q_lo, q_hi, sx); if (rc) return rc; }
         if (positions) { rc = device_shard_nb_positions(g->shards[i]->dev, g->shards[i]->flat, post, p, s.nrec[i], (const uint32_t*)s.xchg, xstride, (uint32_t*)s.xpos, pstride, q_lo, q_hi, sx); if (rc) return rc; }
         if (g->timing && i == 0) HIP_TRY(hipEventRecord(g->e_t[1], sx));
     }
@@ -359,7 +356,7 @@ int group_predict_neighbours(srn_shard_group* g, const LaunchParams& p_in, bool 
         pi.out_ids = direct ? d_out_ids : (uint64_t*)blk; pi.out_scores = direct ? d_out_scores : (double*)(blk + (size_t)nq * n * 8); pi.out_counts = direct ? d_out_counts : (uint32_t*)(blk + (size_t)nq * n * 16);
         if (g->timing && i == 0) HIP_TRY(hipEventRecord(g->e_t[2], user));
         HIP_TRY(hipMemsetAsync(pi.out_ids, 0, (size_t)nq * n * 8, user)); HIP_TRY(hipMemsetAsync(pi.out_scores, 0, (size_t)nq * n * 8, user));
-        int rc = device_shard_nb_back(g->shards[i]->dev, g->shards[i]->flat, post, pi, s.nrec[i], (uint32_t*)(positions ? s.xpos : s.xchg), positions ? pstride : xstride, user, s.nord_ptr[i], positions, pbytes && !positions); if (rc) return rc;
+        int rc = device_shard_nb_back(g->shards[i]->dev, g->shards[i]->flat, post, pi, s.nrec[i], (uint32_t*)(positions ? s.xpos : s.xchg), positions ? pstride : xstride, user, s.nord_ptr[i], positions); if (rc) return rc;
         if (g->timing && i == 0) HIP_TRY(hipEventRecord(g->e_t[3], user));
     }
     if (G > 1) {
@@ -594,7 +591,7 @@ void srn_shard_group_free(srn_shard_group_t* g) {
     if (g->s_x) hipStreamDestroy(g->s_x);
     if (g->e_in) hipEventDestroy(g->e_in); if (g->e_x) hipEventDestroy(g->e_x); if (g->e_last) hipEventDestroy(g->e_last);
     for (auto& e : g->e_t) if (e) hipEventDestroy(e);
-    if (g->pres_all) hipFree(g->pres_all); if (g->nb_pbytes) hipFree(g->nb_pbytes); if (g->agree_dev) hipFree(g->agree_dev);
+    if (g->agree_dev) hipFree(g->agree_dev);
     delete g;
 }
 
@@ -617,8 +614,8 @@ int srn_debug_shard_group_times(const srn_shard_group_t* g, double* out3) {   //
     return SRN_OK;
 }
 // Collective over the group (every rank calls it with the postings of the same index, or every rank with NULL): what is rank-LOCAL and can fail -- packed rows that did
-// not fit at attach time, no room for the streaming form's second copy of the fragments, the presence bytes' buffers -- is attempted first, the outcomes are AGREED on
-// (one all-reduce-min of three flags), and only then is anything committed: either every rank takes the neighbours pipeline in the same exchange format, or none does.
+// not fit at attach time, no room for the streaming form's second copy of the fragments -- is attempted first, the outcomes are AGREED on
+// (one all-reduce-min of two flags), and only then is anything committed: either every rank takes the neighbours pipeline in the same exchange format, or none does.
 // (a rank that failed alone used to keep the lists pipeline while its peers issued the neighbours pipeline's collectives on the same communicator.)
 int srn_shard_group_set_postings(srn_shard_group_t* g, const srn_index_t* postings) {
     if (!g) return fail(SRN_EINVAL, "null group");
@@ -627,7 +624,6 @@ int srn_shard_group_set_postings(srn_shard_group_t* g, const srn_index_t* postin
     HIP_TRY(hipSetDevice(g->device));
     auto detach = [&]() {   // back to the lists pipeline: nothing of an earlier set_postings stays
         for (const srn_index* sh : g->shards) (void)device_sback_attach_postings(sh->dev, nullptr, 0);
-        if (g->nb_pbytes) { (void)hipDeviceSynchronize(); (void)hipFree(g->nb_pbytes); g->nb_pbytes = nullptr; }
         g->postings = nullptr; g->postings_max_row_len = 0; g->stream_ok = false;
     };
     detach();
@@ -661,47 +657,21 @@ int srn_shard_group_set_postings(srn_shard_group_t* g, const srn_index_t* postin
         }
         stream_here = local_rc == SRN_OK && all;
     }
-    // The neighbours' presence bytes (round 5, opt-in knob): every shard's presence bitmap all-gathered once, then a byte per session.  Up to 8 shards; every local shard
-    // must have its bitmap (the wave-per-query back end's rows: from SRN_SBACK_MIN_SHARDS shards on).  Buffers first, the collective only if every rank has them.
-    bool pbytes_here = false; size_t block_words = 0; uint8_t* pb = nullptr;
-    const uint64_t n_sess = postings->flat.n_kept + 1;
-    if (local_rc == SRN_OK && G_of(g) >= 2 && G_of(g) <= 8 && device_shard_nb_presence_wanted()) {
-        bool have = !g->shards.empty(); size_t words = 0;
-        for (const srn_index* sh : g->shards) { size_t w = 0; have = have && device_sback_present(sh->dev, &w) != nullptr; words = std::max(words, w); }
-        if (have) {
-            block_words = (std::max<size_t>(words, (size_t)((n_sess + 31) / 32)) + 63) / 64 * 64;
-            pbytes_here = ensure(&g->pres_all, &g->pres_all_bytes, (size_t)G_of(g) * block_words * 4) == SRN_OK && hipMalloc((void**)&pb, (size_t)n_sess + 64) == hipSuccess;
-            if (!pbytes_here && pb) { (void)hipFree(pb); pb = nullptr; }
-        }
-    }
-    // ---- the agreement: min over the ranks of (this rank can take the postings | ... stream | ... has the presence buffers) ----
-    int flags[3] = {local_rc == SRN_OK ? 1 : 0, stream_here ? 1 : 0, pbytes_here ? 1 : 0};
+    // ---- the agreement: min over the ranks of (this rank can take the postings | ... stream) ----
+    int flags[2] = {local_rc == SRN_OK ? 1 : 0, stream_here ? 1 : 0};
     if (g->kind != srn_shard_group::LOCAL) {
         if (!g->agree_dev) HIP_TRY(hipMalloc((void**)&g->agree_dev, 64));
         HIP_TRY(hipMemcpyAsync(g->agree_dev, flags, sizeof flags, hipMemcpyHostToDevice, g->s_x));
-        { const int rc = all_reduce_min_i32(g, 0, g->agree_dev, 3, g->s_x); g->issued = false; if (rc) { if (pb) (void)hipFree(pb); detach(); return rc; } }
+        { const int rc = all_reduce_min_i32(g, 0, g->agree_dev, 2, g->s_x); g->issued = false; if (rc) { detach(); return rc; } }
         HIP_TRY(hipMemcpyAsync(flags, g->agree_dev, sizeof flags, hipMemcpyDeviceToHost, g->s_x));
         HIP_TRY(hipStreamSynchronize(g->s_x));
     }
     if (!flags[0]) {
-        if (pb) (void)hipFree(pb);
         detach();
         return local_rc != SRN_OK ? fail(local_rc, why) : fail(SRN_ESTATE, "a peer rank could not take the replicated postings (its error says why): no rank of the group took them -- the lists pipeline stays");
     }
     if (!flags[1] && stream_here)   // a peer has no room for the streaming form: every rank runs the gather form
         for (const srn_index* sh : g->shards) (void)device_sback_attach_postings(sh->dev, nullptr, 0);
-    if (flags[2]) {
-        HIP_TRY(hipMemsetAsync(g->pres_all, 0, (size_t)G_of(g) * block_words * 4, nullptr));
-        for (size_t i = 0; i < g->shards.size(); ++i) {
-            const uint32_t gi = g->kind == srn_shard_group::LOCAL ? (uint32_t)i : (uint32_t)g->rank;
-            size_t w = 0; const uint32_t* pr = device_sback_present(g->shards[i]->dev, &w);
-            HIP_TRY(hipMemcpyAsync(g->pres_all + (size_t)gi * block_words * 4, pr, w * 4, hipMemcpyDeviceToDevice, nullptr));
-        }
-        { const int rc = all_gather_blocks(g, 0, g->pres_all, block_words * 4, nullptr); g->issued = false; if (rc) { (void)hipFree(pb); detach(); return rc; } }
-        HIP_TRY(launch_presence_bytes(nullptr, (const uint32_t*)g->pres_all, block_words, G_of(g), n_sess, pb));
-        HIP_TRY(hipDeviceSynchronize());
-        g->nb_pbytes = pb;
-    } else if (pb) (void)hipFree(pb);
     // committed last, and the same on every rank
     g->stream_ok = flags[1] != 0; g->postings_max_row_len = postings->flat.max_row_len; g->postings = postings;
     return SRN_OK;

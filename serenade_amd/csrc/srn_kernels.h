@@ -133,23 +133,18 @@ static constexpr uint32_t SB_H = 1024, SB_S = 1024, SB_DUMP = 64, SB_REP_ITEMS =
 struct SBackParams {
     const uint2* frag8;        // [n_kept + 1] 8-byte fragment slots by recency rank: four 16-bit offsets, or {0xFFFF, len, overflow block index} for a fragment of > 4 items
     const uint4* ext8;         // overflow blocks: 8 offsets per 16 bytes, ALL items of a long fragment
-    const uint32_t* present;   // one bit per session: the fragment is not empty (null: not consulted)
     const ItemMeta* sample;    // meta[] of the shard's 256 most popular items, zero-padded
     double inv_idf_chunk[SB_H / 256];   // 1 / max idf_eff over the dense idx [256 c, 256 c + 256)
     double inv_idf_all;        // 1 / max idf_eff over all items of the shard
     // the streaming form (all three set, or the gather form runs): the fragments in POSTING order of the replicated lists the batch's records were written against
     const uint2* frag_post;    // [number of postings] frag_post[e] = frag8[post_rank[e]]
     const uint32_t* post_rank; // the replicated posting lists (recency ranks)
-    uint32_t pbyte_shift;      // < 8: the exchange records carry a presence byte per neighbour behind the slots (at word 1 + k), this shard's bit is pbyte_shift; 8: they do not
-    uint32_t finish_here;      // the serving wave finishes rows of <= 63 entries itself (score, ranking, public ids) instead of leaving a record for vmis_finish_kernel
+    uint32_t finish_here;      // always 0 (the runtime never sets it): see the streaming form's hand-off in srn_sback.hip
     uint32_t* scr;             // shard_back_scratch_words() words per wave of the grid: the members' slots and fragments between walk A and walk B
 };
-hipError_t launch_rows_to_frag8(hipStream_t st, const uint64_t* row_off, const uint32_t* row_items, uint64_t n_rows, const uint32_t* block_base, uint2* frag8, uint4* ext8, uint32_t* present);   // block_base in 16-byte blocks
+hipError_t launch_rows_to_frag8(hipStream_t st, const uint64_t* row_off, const uint32_t* row_items, uint64_t n_rows, const uint32_t* block_base, uint2* frag8, uint4* ext8);   // block_base in 16-byte blocks
 hipError_t launch_frag_post(hipStream_t st, const uint32_t* post_rank, const uint2* frag8, uint2* out, uint64_t n);
 uint32_t shard_back_scratch_words();
-hipError_t launch_presence_bytes(hipStream_t st, const uint32_t* bitmaps, size_t block_words, uint32_t G, uint64_t n, uint8_t* out);   // bit g of out[r] = bit r of bitmap g
-hipError_t launch_shard_nb_presence(dim3 grid, hipStream_t st, const char* prep, uint32_t prep_stride, uint32_t max_len, uint32_t* xchg, uint32_t stride, uint32_t k, const uint8_t* pbytes, uint32_t n_kept,
-                                    uint32_t q_lo, uint32_t q_hi, bool wide);
 hipError_t launch_shard_nb_positions(dim3 grid, hipStream_t st, const char* prep, uint32_t prep_stride, uint32_t max_len, const uint32_t* xin, uint32_t in_stride, uint32_t* xout, uint32_t out_stride,
                                      const uint32_t* post_rank, uint32_t q_lo, uint32_t q_hi, uint32_t m, bool wide);
 uint32_t shard_nb_positions_stride(uint32_t k, uint32_t m);   // words per query of the streaming form's exchange record; 0: this (k, m) has none
@@ -165,8 +160,7 @@ hipError_t launch_prep(hipStream_t st, const DeviceIndex& di, const uint64_t* it
                        uint32_t max_len, char* out, uint32_t stride, uint32_t* zero_a = nullptr, uint32_t* zero_b = nullptr,
                        const IdSlot* loc_table = nullptr, uint32_t loc_mask = 0, unsigned long long* okeys = nullptr);   // zero_a[0..7], zero_b[0]: counters cleared by the prep kernel; loc_table: the item shard's id table (the record's idx), di = the whole index's dictionary and lists
 hipError_t launch_finish_big(hipStream_t st, const DeviceIndex& di, const FastParams& f, uint64_t* out_ids, double* out_scores, uint32_t* out_counts, uint32_t how_many, uint32_t grid, const uint32_t* cnt_retry = nullptr, const uint32_t* cnt_slow = nullptr, uint32_t* host_words = nullptr);
-hipError_t launch_finish(hipStream_t st, const DeviceIndex& di, const FastParams& f, uint64_t* out_ids, double* out_scores, uint32_t* out_counts, uint32_t nq, uint32_t how_many,
-                         const uint32_t* cnt_slow = nullptr, uint32_t* host_words = nullptr);   // (cnt_slow + host_words: the call's path counters published to pinned words, the latency path)   // scores, ranking, public ids of the rows the fast kernel served
+hipError_t launch_finish(hipStream_t st, const DeviceIndex& di, const FastParams& f, uint64_t* out_ids, double* out_scores, uint32_t* out_counts, uint32_t nq, uint32_t how_many);   // scores, ranking, public ids of the rows the fast kernel served
 hipError_t launch_shard_lists_head(hipStream_t st, const DeviceIndex& di, const uint64_t* items_flat, const uint32_t* q_off, uint32_t nq, uint32_t m, uint32_t max_len,
                                    ShardPos* pos_out, int* head);
 hipError_t launch_shard_lists_count(hipStream_t st, const DeviceIndex& di, const uint32_t* q_off, uint32_t nq, uint32_t max_len, const ShardPos* pos_in, const int* head,

@@ -27,18 +27,14 @@ struct Knobs {
     bool no_masks = false, no_merge = false, dense = false, no_fast = false, no_mid = false, no_big = false, no_long = false, debug = false;   // no_long (SRN_NO_LONG): without the LONG instantiation (sessions of 11..20 items go to the general kernel, as until round 4)   // no_mid (SRN_NO_MID): the launch sequence without the fast kernel's MID instantiation (what it would take goes to the general kernel, as before round 4)
     int hot_slots = -1, sketch_slots = -1, lds_budget_kb = 0, grid_mult = 16, fast_runs = 0;
     bool grid_mult_set = false;
-    int host_first_pct = 0;   // SRN_HOST_FIRST_PCT (experiments): a host-pointer batch of 8 192 .. 65 536 queries in TWO chunks, the first this percentage of it (0: the default policy of srn_hostpipe.hip)
     int host_chunks = 0;      // SRN_HOST_CHUNKS: number of chunks a host-pointer batch is cut into (0 = by size, srn_hostpipe.hip)
     int copy_slices = 0;      // SRN_COPY_SLICES: slices a result block is cut into for the copy threads (0 = one per thread)
-    bool host_nocopy = false; // SRN_HOST_NOCOPY (experiments): the chunked host path leaves the results in its pinned staging
     bool host_trace = false;  // SRN_HOST_TRACE (experiments): per-call timeline of the chunked host path on stderr
     bool timing = false;      // SRN_TIMING: kernel timing on from the start (srn_kernel_timing switches it per index)
-    int d2h_blocks = 0;       // SRN_D2H_BLOCKS: workgroups of the chunked host path's own download kernel (0 = hipMemcpyAsync, the default: measured faster, profiles/r03_host_pipe_probe.txt)
     int tiny_max = 256;       // SRN_TINY_MAX: host-pointer batches of up to this many sessions take the zero-copy latency path
     bool no_tiny_spin = false;    // SRN_TINY_SPIN=0: the fused launch's caller waits for the stream instead of spinning on the kernel's last pinned word
     int tiny_fused_max = 48;      // SRN_TINY_FUSED_MAX: sessions per call up to which the latency path is the fused launch (one workgroup per session).  Measured (config 3, host batches): 48 per call p50 56 / p90 77 us against 78 / 83 for prep + general kernel; 64 per call 57 / 103 against 79 / 85 -- a call's chance of a second phase (a query for the general kernel: 0.3 % each) grows with its size, and the p90 with it
     bool no_tiny_fused = false;   // SRN_TINY_FUSED=0: a single-session call through five launches (prep, fast kernel, general kernel, finish, finish-big) instead of the fast kernel's one-launch TINY form
-    int tiny_phases = 0;      // SRN_TINY_PHASES (experiments): the latency path's launches behind the fast kernel -- 0: all of them with every call; 1: finish + finish-big, then MID / general kernel / a second finish only for a call that listed queries for them (a second wait then); 2: finish alone in the first phase.  Measured (profiles/r05_latency_phases.txt): one query per call p50 46 us against 49 with 2, p99 71 against 63; calls of 4 and 16 queries lose at p90 (a second wait more often): 0 stays
     int tiny_fast = 2;        // SRN_TINY_FAST: the latency path's kernels -- 0: prep + general kernel (rounds 1-3); 1: the fast kernel's launch sequence only where the batch has a session of > 8 items (which puts
                               // the whole batch on the general kernel's non-position-set build: 144 us against 52 us per call on config 3); 2 (default): also for calls of <= 32 sessions (one session per call,
                               // config 3, max_items 4: p50 53.3 -> 47.8 us, p90 63.7 -> 54.1; larger rounds stay on the general kernel -- one workgroup per query runs them all at once: nothing to gain,
@@ -46,12 +42,8 @@ struct Knobs {
     int row_slots16 = -1;     // SRN_ROW_SLOTS = 16 | 64: the device row layout (-1 = by index kind: 64-byte slots unsharded, 16-byte fragment slots for item shards)
     int order_min = 131072;    // SRN_ORDER_MIN: batches of at least this many queries are served in the order of their most popular item, an eighth of the order per XCD (0 = never); the ordering
                               // pass is one radix sort of the batch's keys behind the prep kernel
-    bool no_sback_finish = true;    // SRN_SBACK_FINISH=1 (experiment): the wave-per-query back end finishes rows of <= 63 entries itself instead of leaving a record for vmis_finish_kernel.  Measured: the finish kernels' share falls 0.167 -> 0.122 ms per 131 072 queries, the kernel grows 1.606 -> 1.685 (two more dependent gathers per query on a kernel bound by its requests): off
-    bool no_sback_pbytes = true;    // SRN_SBACK_PBYTES=1 (experiment): presence bytes in the neighbours pipeline's exchange records -- the fronting rank marks, per neighbour, which shards hold a fragment of it (the shards' bitmaps all-gathered at set_postings); a back end asks only for fragments that exist: half the requests at G = 8, no look-up of its own.  Measured in round 5: kernel 1.61 -> 1.95 ms (its 22 byte loads were waited for one by one); round 6, read in one batch and the absent lanes truly silent: 1.149 against 1.149 ms, front 0.30 -> 0.36 -- half the fragment requests buy nothing, the kernel's time does not follow them (profiles/r06_sback_ab.txt)
     bool no_sback_second = false;   // SRN_NO_SBACK_SECOND (experiments): what the wave-per-query back end cannot hold goes straight to the general kernel (no fast-kernel back end over the list)
     bool no_sback = false;    // SRN_NO_SBACK: the shard group's back end through vmis_fast_kernel's FM_BACK instantiation (rounds 4) instead of the wave-per-query kernel of srn_sback.hip
-    bool sback_bitmap = false;     // SRN_SBACK_BITMAP=1 (experiments): that kernel asks its presence bitmap before it fetches a fragment.  Measured on config 3 cut in 8: half the fragment
-                                   // fetches, but one more DEPENDENT round trip per query on a kernel that spends 65 % of its time waiting for memory -- 1.65 ms with, 1.52 ms without
     double xgmi_gbps = 76.8;       // SRN_XGMI_GBPS: what one xGMI link moves per direction (AUTO's input below)
     int sback_stream_mode = -1;    // SRN_SBACK_STREAM: 1 = the streaming form wherever the shards have it, 0 = never, unset = AUTO (round 6): a group with real peers (RCCL / callbacks) takes it
                                    // unless its exchanges overlap the previous batch (srn_shard_group_set_overlap) -- it ships a third of the gather form's bytes and costs 0.4 ms more compute per
@@ -115,8 +107,7 @@ struct DeviceState {
     FastParams fast{};            // packed row slots + idf bounds of the fast kernel (row_packed == nullptr: no fast path for this index)
     std::atomic<uint64_t> sback_launches{0};
     void* sb_frag_post = nullptr; const uint32_t* sb_post_for = nullptr; uint64_t sb_frag_post_bytes = 0;   // the fragments in the posting order of the replicated lists at sb_post_for (device_sback_attach_postings)
-    size_t sback_present_words = 0;
-    SBackParams sback{};          // item shards: frag8 rows + presence bitmap of the wave-per-query back end (frag8 == nullptr: the FM_BACK form of the fast kernel serves)
+    SBackParams sback{};          // item shards: frag8 rows of the wave-per-query back end (frag8 == nullptr: the FM_BACK form of the fast kernel serves)
     uint32_t host_max_row_len = 0;
     int n_cu = 256;
     int lds_per_block_max = 65536;

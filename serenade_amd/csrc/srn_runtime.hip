@@ -8,6 +8,7 @@
 #include <chrono>
 
 #include <algorithm>
+#include <climits>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -22,38 +23,36 @@
 namespace srn {
 
 static Knobs g_knobs; static std::once_flag g_knobs_once; static std::mutex g_knobs_mu;
+// Each variable is read once: a flag is on when the variable is set at all, a switch holds a number (0 = off), an int is clamped to [lo, hi].
+static bool env_flag(const char* name) { return getenv(name) != nullptr; }
+static int env_int(const char* name, int unset, int lo = INT_MIN, int hi = INT_MAX) { const char* e = getenv(name); return e ? std::min(hi, std::max(lo, atoi(e))) : unset; }
 static void knobs_read() {
     Knobs k;
-    if (const char* e = getenv("SRN_FAST_HOW_MANY_MAX")) k.fast_how_many_max = std::max(1, std::min(64, atoi(e)));
-    k.no_masks = getenv("SRN_NO_MASKS") != nullptr; k.no_viol = getenv("SRN_NO_VIOL") != nullptr; k.no_merge = getenv("SRN_NO_MERGE") != nullptr; k.dense = getenv("SRN_DENSE") != nullptr;
-    k.no_fast = getenv("SRN_NO_FAST") != nullptr; k.no_mid = getenv("SRN_NO_MID") != nullptr; k.no_big = getenv("SRN_NO_BIG") != nullptr; k.no_long = getenv("SRN_NO_LONG") != nullptr; k.debug = getenv("SRN_DEBUG") != nullptr;
-    if (const char* e = getenv("SRN_ROW_SLOTS")) k.row_slots16 = atoi(e) == 16 ? 1 : atoi(e) == 64 ? 0 : -1;
-    if (const char* e = getenv("SRN_HOT_SLOTS")) k.hot_slots = std::max(0, atoi(e));
-    if (const char* e = getenv("SRN_SKETCH_SLOTS")) k.sketch_slots = std::max(0, atoi(e));
-    if (const char* e = getenv("SRN_LDS_BUDGET_KB")) k.lds_budget_kb = std::max(0, atoi(e));
-    if (const char* e = getenv("SRN_GRID_MULT")) { k.grid_mult = std::max(1, atoi(e)); k.grid_mult_set = true; }
-    if (const char* e = getenv("SRN_HOST_CHUNKS")) k.host_chunks = std::max(0, atoi(e));
-    if (const char* e = getenv("SRN_HOST_FIRST_PCT")) k.host_first_pct = std::min(99, std::max(0, atoi(e)));
-    if (const char* e = getenv("SRN_COPY_SLICES")) k.copy_slices = std::max(0, atoi(e));
-    k.host_nocopy = getenv("SRN_HOST_NOCOPY") != nullptr; k.host_trace = getenv("SRN_HOST_TRACE") != nullptr; k.timing = getenv("SRN_TIMING") != nullptr && atoi(getenv("SRN_TIMING")) != 0;
-    if (const char* e = getenv("SRN_D2H_BLOCKS")) k.d2h_blocks = std::max(0, atoi(e));
-    if (const char* e = getenv("SRN_TINY_MAX")) k.tiny_max = std::max(0, atoi(e));
-    k.no_tiny_fused = getenv("SRN_TINY_FUSED") != nullptr && atoi(getenv("SRN_TINY_FUSED")) == 0;
-    if (const char* e = getenv("SRN_TINY_FUSED_MAX")) k.tiny_fused_max = std::min(256, std::max(1, atoi(e)));
-    k.no_tiny_spin = getenv("SRN_TINY_SPIN") != nullptr && atoi(getenv("SRN_TINY_SPIN")) == 0;
-    if (const char* e = getenv("SRN_TINY_PHASES")) k.tiny_phases = std::min(2, std::max(0, atoi(e)));
-    if (const char* e = getenv("SRN_TINY_FAST")) k.tiny_fast = std::min(3, std::max(0, atoi(e)));
-    if (const char* e = getenv("SRN_PREDICT_LANES")) k.lanes = std::max(0, atoi(e));
-    if (const char* e = getenv("SRN_ORDER_MIN")) k.order_min = std::max(0, atoi(e));
-    k.no_sback_second = getenv("SRN_NO_SBACK_SECOND") != nullptr;
-    k.no_sback_pbytes = !(getenv("SRN_SBACK_PBYTES") != nullptr && atoi(getenv("SRN_SBACK_PBYTES")) != 0);
-    k.no_sback_finish = !(getenv("SRN_SBACK_FINISH") != nullptr && atoi(getenv("SRN_SBACK_FINISH")) != 0);
-    k.no_sback = getenv("SRN_NO_SBACK") != nullptr; k.sback_bitmap = getenv("SRN_SBACK_BITMAP") != nullptr && atoi(getenv("SRN_SBACK_BITMAP")) != 0;
-    k.sback_stream_mode = getenv("SRN_SBACK_STREAM") == nullptr ? -1 : atoi(getenv("SRN_SBACK_STREAM")) != 0 ? 1 : 0;
+    k.fast_how_many_max = env_int("SRN_FAST_HOW_MANY_MAX", k.fast_how_many_max, 1, 64);
+    k.no_masks = env_flag("SRN_NO_MASKS"); k.no_viol = env_flag("SRN_NO_VIOL"); k.no_merge = env_flag("SRN_NO_MERGE"); k.dense = env_flag("SRN_DENSE");
+    k.no_fast = env_flag("SRN_NO_FAST"); k.no_mid = env_flag("SRN_NO_MID"); k.no_big = env_flag("SRN_NO_BIG"); k.no_long = env_flag("SRN_NO_LONG"); k.debug = env_flag("SRN_DEBUG");
+    const int row_slots = env_int("SRN_ROW_SLOTS", -1); k.row_slots16 = row_slots == 16 ? 1 : row_slots == 64 ? 0 : -1;
+    k.hot_slots = env_int("SRN_HOT_SLOTS", k.hot_slots, 0);
+    k.sketch_slots = env_int("SRN_SKETCH_SLOTS", k.sketch_slots, 0);
+    k.lds_budget_kb = env_int("SRN_LDS_BUDGET_KB", k.lds_budget_kb, 0);
+    const int grid_mult = env_int("SRN_GRID_MULT", 0, 1); k.grid_mult_set = grid_mult != 0; if (grid_mult) k.grid_mult = grid_mult;
+    k.host_chunks = env_int("SRN_HOST_CHUNKS", k.host_chunks, 0);
+    k.copy_slices = env_int("SRN_COPY_SLICES", k.copy_slices, 0);
+    k.host_trace = env_flag("SRN_HOST_TRACE"); k.timing = env_int("SRN_TIMING", 0) != 0;
+    k.tiny_max = env_int("SRN_TINY_MAX", k.tiny_max, 0);
+    k.no_tiny_fused = env_int("SRN_TINY_FUSED", 1) == 0;
+    k.tiny_fused_max = env_int("SRN_TINY_FUSED_MAX", k.tiny_fused_max, 1, 256);
+    k.no_tiny_spin = env_int("SRN_TINY_SPIN", 1) == 0;
+    k.tiny_fast = env_int("SRN_TINY_FAST", k.tiny_fast, 0, 3);
+    k.lanes = env_int("SRN_PREDICT_LANES", k.lanes, 0);
+    k.order_min = env_int("SRN_ORDER_MIN", k.order_min, 0);
+    k.no_sback_second = env_flag("SRN_NO_SBACK_SECOND");
+    k.no_sback = env_flag("SRN_NO_SBACK");
+    const int stream = env_int("SRN_SBACK_STREAM", INT_MIN); k.sback_stream_mode = stream == INT_MIN ? -1 : stream != 0 ? 1 : 0;
     k.no_sback_stream = k.sback_stream_mode == 0;
     if (const char* e = getenv("SRN_XGMI_GBPS")) { const double v = atof(e); if (v > 0.0) k.xgmi_gbps = v; }
-    if (const char* e = getenv("SRN_SBACK_MIN_SHARDS")) k.sback_min_shards = std::max(2, atoi(e));
-    if (const char* e = getenv("SRN_FAST_RUNS")) k.fast_runs = atoi(e) == 3 ? 3 : 0;   // tests: the fast kernel's 29-bit-rank form (3 lists per query) on a small index
+    k.sback_min_shards = env_int("SRN_SBACK_MIN_SHARDS", k.sback_min_shards, 2);
+    k.fast_runs = env_int("SRN_FAST_RUNS", 0) == 3 ? 3 : 0;   // tests: the fast kernel's 29-bit-rank form (3 lists per query) on a small index
     std::lock_guard<std::mutex> lk(g_knobs_mu); g_knobs = k;
 }
 Knobs knobs() { std::call_once(g_knobs_once, knobs_read); std::lock_guard<std::mutex> lk(g_knobs_mu); return g_knobs; }
@@ -139,27 +138,26 @@ DeviceState* device_attach(const FlatIndex& ix, int device) {
                 if (knobs().debug) fprintf(stderr, "[srn] no room for the fast kernel's packed rows (%zu bytes): general kernel only\n", (size_t)((n + 1) * slot_bytes + (blocks + 2) * 16));
             }
         }
-        if (good && frag && ix.n_shards >= (uint32_t)knobs().sback_min_shards) {   // the wave-per-query back end's rows (srn_sback.hip): 8-byte slots + overflow blocks + presence bitmap; optional like the packed rows
+        if (good && frag && ix.n_shards >= (uint32_t)knobs().sback_min_shards) {   // the wave-per-query back end's rows (srn_sback.hip): 8-byte slots + overflow blocks; optional like the packed rows
             std::vector<uint32_t> bb(nblocks); uint64_t blocks = 1, longest = 0;
             for (size_t b0 = 0; b0 < nblocks; ++b0) {
                 bb[b0] = (uint32_t)blocks;
                 const size_t hi = std::min(n, (b0 + 1) * 1024);
                 for (size_t r = b0 * 1024; r < hi; ++r) { const uint64_t len = ix.row_off[r + 1] - ix.row_off[r]; longest = std::max(longest, len); if (len > 4) blocks += (len + 7) / 8; }
             }
-            const size_t pwords = (n + 1 + 31) / 32 + 32;
-            void *d_f8 = nullptr, *d_e8 = nullptr, *d_pr = nullptr, *d_sm = nullptr;
+            void *d_f8 = nullptr, *d_e8 = nullptr, *d_sm = nullptr;
             std::vector<ItemMeta> sm(256, ItemMeta{0.0, 0u, 0u});
             for (size_t i = 0; i < std::min<size_t>(256, ix.n_items); ++i) sm[i] = ItemMeta{ix.idf[i], ix.id_rank[i], ix.attr[i]};
             const bool g3 = blocks < 0xFFFFFFF0ull && longest < (1ull << 11) &&   // (what a long fragment's slot can say: srn_sback.hip, SB_LONG)
-                            hipMalloc(&d_f8, (n + 1) * 8) == hipSuccess && hipMalloc(&d_e8, (blocks + 2) * 16) == hipSuccess && hipMalloc(&d_pr, pwords * 4) == hipSuccess &&
+                            hipMalloc(&d_f8, (n + 1) * 8) == hipSuccess && hipMalloc(&d_e8, (blocks + 2) * 16) == hipSuccess &&
                             hipMalloc(&d_sm, 256 * sizeof(ItemMeta)) == hipSuccess && hipMemcpy(d_sm, sm.data(), 256 * sizeof(ItemMeta), hipMemcpyHostToDevice) == hipSuccess &&
-                            hipMemcpy(d_base, bb.data(), nblocks * 4, hipMemcpyHostToDevice) == hipSuccess && hipMemset(d_e8, 0, (blocks + 2) * 16) == hipSuccess && hipMemset(d_pr, 0, pwords * 4) == hipSuccess &&
-                            launch_rows_to_frag8(nullptr, (const uint64_t*)d_off, (const uint32_t*)d_items, (uint64_t)n, (const uint32_t*)d_base, (uint2*)d_f8, (uint4*)d_e8, (uint32_t*)d_pr) == hipSuccess &&
+                            hipMemcpy(d_base, bb.data(), nblocks * 4, hipMemcpyHostToDevice) == hipSuccess && hipMemset(d_e8, 0, (blocks + 2) * 16) == hipSuccess &&
+                            launch_rows_to_frag8(nullptr, (const uint64_t*)d_off, (const uint32_t*)d_items, (uint64_t)n, (const uint32_t*)d_base, (uint2*)d_f8, (uint4*)d_e8) == hipSuccess &&
                             hipDeviceSynchronize() == hipSuccess;
-            if (g3) { for (void* q : {d_f8, d_e8, d_pr, d_sm}) d->allocs.push_back(q);
-                      d->bytes += (n + 1) * 8 + (blocks + 2) * 16 + pwords * 4 + 256 * sizeof(ItemMeta);
-                      d->sback.frag8 = (const uint2*)d_f8; d->sback.ext8 = (const uint4*)d_e8; d->sback.present = (const uint32_t*)d_pr; d->sback.sample = (const ItemMeta*)d_sm; d->sback_present_words = pwords; }
-            else { (void)hipGetLastError(); for (void* q : {d_f8, d_e8, d_pr, d_sm}) if (q) hipFree(q); d->sback = SBackParams{}; }
+            if (g3) { for (void* q : {d_f8, d_e8, d_sm}) d->allocs.push_back(q);
+                      d->bytes += (n + 1) * 8 + (blocks + 2) * 16 + 256 * sizeof(ItemMeta);
+                      d->sback.frag8 = (const uint2*)d_f8; d->sback.ext8 = (const uint4*)d_e8; d->sback.sample = (const ItemMeta*)d_sm; }
+            else { (void)hipGetLastError(); for (void* q : {d_f8, d_e8, d_sm}) if (q) hipFree(q); d->sback = SBackParams{}; }
         }
         if (d_off) hipFree(d_off); if (d_items) hipFree(d_items); if (d_base) hipFree(d_base);
         if (d_slots) { d->allocs.push_back(d_slots); d->bytes += (n + 1) * slot_bytes; }
@@ -514,11 +512,9 @@ static int device_predict_tiny(DeviceState* d, const FlatIndex& ix, Workspace* w
         }
         else
         HIP_TRY(launch_fast(dim3(p.nq), st, d->di, p, fp, kn.debug, 0));
-        // (round 5, experiment: SRN_TINY_PHASES) A single query's call is five launches -- prep, fast kernel, general kernel, finish, finish-big -- and two of them find nothing to
-        // do in 99 calls of 100.  With the path counters published by the finish kernel the host can launch what is behind it only for a call that listed work for it, and wait a
-        // second time then: 46 us against 49 at p50 for one query per call, but 71 against 63 at p99, and calls of 4 / 16 queries lose at p90.  The default stays one phase.
-        const int phases = fused ? 3 : kn.tiny_phases;   // (3: the fused launch is the whole first phase)   // 0: one phase (round 4); 1: finish-big stays in the first phase (a second wait only for handed-over / MID queries); 2: the first phase ends with the finish kernel
-        const bool two_phase = phases != 0;
+        // The fused launch is a whole first phase: the counters it publishes say whether a second one (the kernels of rest() below, and a second wait) is needed at all.  The
+        // five-launch form (SRN_TINY_FUSED=0) has no second phase: rest() goes behind the fast kernel with every call.  (Splitting the five launches into two phases on counters
+        // published by the finish kernel was measured in round 5 and lost at p90 / p99 -- profiles/r05_latency_phases.txt: removed.)
         auto rest = [&]() -> int {
             if (plan.mid_tier) HIP_TRY(launch_fast(dim3(p.nq), st, d->di, p, fp, kn.debug, 0, true));
             HIP_TRY(launch_predict(geo.masks, geo.slot64, false, 0, dim3(p.nq), geo.lds, st, d->di, p, geo.c, w->slow_list, w->slow_cnt, (uint32_t*)(dp + o_rl), (uint32_t*)(dp + o_rc), nullptr, 0,
@@ -529,12 +525,7 @@ static int device_predict_tiny(DeviceState* d, const FlatIndex& ix, Workspace* w
             HIP_TRY(launch_finish_big(st, d->di, fp, p.out_ids, p.out_scores, p.out_counts, p.how_many, (uint32_t)std::min<uint64_t>(p.nq, (uint64_t)d->n_cu * 16), nullptr, w->slow_cnt, w->h_retry_dev));
             return SRN_OK;
         };
-        if (phases == 2) HIP_TRY(launch_finish(st, d->di, fp, p.out_ids, p.out_scores, p.out_counts, p.nq, p.how_many, w->slow_cnt, w->h_retry_dev));
-        else if (phases == 1) {
-            HIP_TRY(launch_finish(st, d->di, fp, p.out_ids, p.out_scores, p.out_counts, p.nq, p.how_many));
-            HIP_TRY(launch_finish_big(st, d->di, fp, p.out_ids, p.out_scores, p.out_counts, p.how_many, (uint32_t)std::min<uint64_t>(p.nq, (uint64_t)d->n_cu * 16), nullptr, w->slow_cnt, w->h_retry_dev));
-        }
-        else if (phases == 0) { int rc = rest(); if (rc) return rc; }
+        if (!fused) { int rc = rest(); if (rc) return rc; }
         auto wait = [&]() -> int {
             if (blocking_wait) {   // a round several callers share: sleep on an interrupt instead of spinning on the signal (the host's cores belong to the callers)
                 if (!w->ev_block) HIP_TRY(hipEventCreateWithFlags(&w->ev_block, hipEventBlockingSync | hipEventDisableTiming));
@@ -572,10 +563,10 @@ static int device_predict_tiny(DeviceState* d, const FlatIndex& ix, Workspace* w
                                        (unsigned long long)c, (unsigned long long)second.load(), (unsigned long long)why[0].load(), (unsigned long long)why[1].load(), (unsigned long long)why[2].load());
         }
         if (fused && published && (hw[1] | hw[2] | hw[4]) == 0u) w->cnt_dirty = false;   // (a clean end with nothing handed on: the counters and the workgroup ticket are back at 0)
-        if (published && two_phase && (hw[1] | hw[2] | (phases >= 2 ? hw[4] : 0u)) != 0u) {   // (handed to the general kernel | listed for MID | queries with > 63 entries)
+        if (fused && published && (hw[1] | hw[2] | hw[4]) != 0u) {   // the second phase (handed to the general kernel | listed for MID | queries with > 63 entries)
             int rc = SRN_OK;
             w->cnt_dirty = true;
-            if (fused && hw[2] == 0u) {   // (nothing listed for MID: the general kernel over what was handed to it -- it writes its rows itself -- and finish-big for a row the fused launch could not finish, each only if needed)
+            if (hw[2] == 0u) {   // (nothing listed for MID: the general kernel over what was handed to it -- it writes its rows itself -- and finish-big for a row the fused launch could not finish, each only if needed)
                 const uint32_t n_slow = hw[1], n_big = hw[4];
                 if (n_slow) HIP_TRY(launch_predict(geo.masks, geo.slot64, false, 0, dim3(std::min<uint32_t>(p.nq, n_slow)), geo.lds, st, d->di, p, geo.c, w->slow_list, w->slow_cnt, (uint32_t*)(dp + o_rl), (uint32_t*)(dp + o_rc), nullptr, 0,
                                                    w->spill, ShardIO{}));
@@ -1014,10 +1005,7 @@ int device_predict(DeviceState* d, const FlatIndex& ix, const LaunchParams& p_in
         const uint32_t grid_fo = fp.order ? std::max<uint32_t>(8u, grid_f / 8u * 8u) : grid_f;   // (an ordered launch walks an eighth of the order per XCD: the grid is a multiple of 8)
         if (back && d->sback.frag8 && !kn.no_sback && p.max_len <= 8) {
             // the item shard's own back end (srn_sback.hip): one wave per query, 12 per CU; a persistent grid of a few waves per resident slot
-            const bool small = (uint64_t)d->di.n_kept + 1u < (1ull << 29);   // (the kernel's presence forms address the fragments through a 32-bit buffer descriptor)
-            SBackParams sbp = d->sback; if (!kn.sback_bitmap || !small) sbp.present = nullptr;
-            sbp.finish_here = kn.no_sback_finish ? 0u : 1u;
-            sbp.pbyte_shift = ext->pbytes && small ? (uint32_t)ix.shard : 8u;   // (not small: the bytes are in the records, this shard fetches every fragment all the same)
+            SBackParams sbp = d->sback;
             // the streaming form where the shard holds its fragments in the posting order of the very lists the records were written against (9 waves per CU: 16.8 KB each)
             const bool stream = ext->positions;
             if (stream && !(d->sb_frag_post && d->sb_post_for == ext->post_rank)) return fail(SRN_ESTATE, "the batch's neighbours came as posting positions, but this shard does not hold its fragments in posting order");
@@ -1217,22 +1205,9 @@ uint32_t device_shard_nb_positions_stride(const LaunchParams& p) {
     if (kn.no_sback_stream || kn.no_sback || p.max_len > 8) return 0u;
     return shard_nb_positions_stride(p.k, p.m);
 }
-const uint32_t* device_sback_present(const DeviceState* d, size_t* words) {
-    if (!d || !d->sback.present) return nullptr;
-    if (words) *words = d->sback_present_words;
-    return d->sback.present;
-}
-bool device_shard_nb_presence_wanted() { const Knobs kn = knobs(); return !kn.no_sback_pbytes && !kn.no_sback; }
-int device_shard_nb_presence(DeviceState* d, const FlatIndex& ix, const LaunchParams& p, const char* records, uint32_t* xchg, uint32_t stride, const uint8_t* pbytes, uint32_t q_lo, uint32_t q_hi, void* stream) {
-    if (q_lo >= q_hi) return SRN_OK;
-    HIP_TRY(hipSetDevice(d->device));
-    const uint32_t grid = (uint32_t)std::min<uint64_t>(q_hi - q_lo, (uint64_t)d->n_cu * 32 * 4);
-    HIP_TRY(launch_shard_nb_presence(dim3(grid), (hipStream_t)stream, records, device_prep_stride(p.max_len), p.max_len, xchg, stride, p.k, pbytes, (uint32_t)ix.n_kept, q_lo, q_hi, fast_nb(ix, knobs()) == 3u));
-    return SRN_OK;
-}
-int device_shard_nb_back(DeviceState* d, const FlatIndex& ix, DeviceState* post, const LaunchParams& p, const char* records, uint32_t* xchg, uint32_t xchg_stride, void* stream, const unsigned long long* order, bool positions, bool pbytes) {
+int device_shard_nb_back(DeviceState* d, const FlatIndex& ix, DeviceState* post, const LaunchParams& p, const char* records, uint32_t* xchg, uint32_t xchg_stride, void* stream, const unsigned long long* order, bool positions) {
     if (p.nq == 0) return SRN_OK;
-    ExtLists ext{records, device_prep_stride(p.max_len), post->di.post_rank, 2, xchg, xchg_stride, 0u, order, positions, pbytes};
+    ExtLists ext{records, device_prep_stride(p.max_len), post->di.post_rank, 2, xchg, xchg_stride, 0u, order, positions};
     return device_predict(d, ix, p, true, stream, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &ext);
 }
 

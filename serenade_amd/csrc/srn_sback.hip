@@ -10,9 +10,9 @@
 //
 // Rows: a third per-shard row array, `frag8` -- 8-byte slots addressed by recency rank, four 16-bit LDS byte offsets (the accumulator word of each of the <= 4 items of the
 // fragment: direct-mapped for the shard's SB_DIRECT most popular items, a sketch word for the rest, replicated words for the 16 hottest -- the same scheme as srn_fast.hip;
-// unused positions point OUT of the wave's LDS allocation (round 6: dropped by the hardware)); a fragment of > 4 items (rare from G = 8 on) keeps all its items in 16-byte overflow blocks -- and a PRESENCE BITMAP, one bit per
-// session: at G = 8 about half of a query's neighbours hold no item of this shard at all, the bitmap (1.5 MB on config 3: L2-resident) is asked first and only the others
-// cost a fragment fetch (tools/shard_gather_bench.hip: a random fragment fetch is an HBM-granule miss at ~50 G/s chip-wide, a bitmap hit ~15x cheaper).
+// unused positions point OUT of the wave's LDS allocation (round 6: dropped by the hardware)); a fragment of > 4 items (rare from G = 8 on) keeps all its items in 16-byte overflow blocks.
+// At G = 8 about half of a query's neighbours hold no item of this shard at all; their (empty) fragments are fetched all the same.  Asking a per-shard presence bitmap first,
+// or presence bytes carried in the exchange records, halves the fragment requests and was measured slower or equal both times (HISTORY.md, rounds 5 and 6): both forms are removed.
 //
 // Same canonical semantics, same integers: the harvest is the fast kernel's -- threshold from the most popular items' exact sums, integer floors per chunk, the sketch filter
 // (DESIGN.md "Why the sketch filter is exact"), walk B + exact table for what the sketch cannot exclude -- written wave-synchronously; the hand-off record and the finish
@@ -60,7 +60,7 @@ static constexpr uint32_t SB_REC_ROOM = SB_HOT - SB_CAND;   // bytes of bitmaps 
 static constexpr uint32_t SBP_BUCKETS = 256, SBP_CODES = SBP_BUCKETS * 32, SBP_WTAB = SBP_CODES + F_K_MAX / 2 + 32, SBP_LDS = SBP_WTAB + 64;
 
 // -------------------------------------------------------------------------------------
-// Attach time: an item shard's CSR row fragments -> frag8 slots + overflow blocks + presence bitmap
+// Attach time: an item shard's CSR row fragments -> frag8 slots + overflow blocks
 // -------------------------------------------------------------------------------------
 __device__ __forceinline__ uint32_t sb_offset_of(uint32_t idx, uint64_t r) {
     if (idx < SB_REP_ITEMS) return (SB_DIRECT + idx * SB_REP + ((uint32_t)r & (SB_REP - 1u))) * 4u;
@@ -81,7 +81,7 @@ __device__ __forceinline__ uint32_t sb_long_len(uint32_t x) { return (x >> 18) &
 __device__ __forceinline__ uint32_t sb_long_block(uint32_t x, uint32_t y) { return ((y >> 2) & SB_LF_MASK) | (((y >> 18) & SB_LF_MASK) << SB_LF_BITS) | (((x >> 2) & 0x3FFu) << (2u * SB_LF_BITS)); }
 __device__ __forceinline__ uint32_t sb_phantom(uint64_t, uint32_t) { return SB_OOR; }
 __global__ __launch_bounds__(1024) void rows_to_frag8_kernel(const uint64_t* __restrict__ row_off, const uint32_t* __restrict__ row_items, uint64_t n,
-                                                             const uint32_t* __restrict__ block_base, uint2* __restrict__ frag8, uint4* __restrict__ ext8, uint32_t* __restrict__ present) {
+                                                             const uint32_t* __restrict__ block_base, uint2* __restrict__ frag8, uint4* __restrict__ ext8) {
     __shared__ uint32_t wave_tot[16];
     const uint64_t r = (uint64_t)blockIdx.x * 1024 + threadIdx.x;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -94,9 +94,6 @@ __global__ __launch_bounds__(1024) void rows_to_frag8_kernel(const uint64_t* __r
     uint32_t base = block_base[blockIdx.x];
     for (int w = 0; w < wave; ++w) base += wave_tot[w];
     const uint32_t eblk = base + inc - e;
-    // presence: bit (r & 31) of word r >> 5 (a wave covers two words)
-    const unsigned long long pb = __ballot(len > 0);
-    if ((lane & 31) == 0 && r <= n) present[r >> 5] = (uint32_t)(pb >> (lane & 32));
     if (r > n) return;
     uint32_t h[4];
     if (len <= 4) {
@@ -118,8 +115,8 @@ __global__ __launch_bounds__(1024) void rows_to_frag8_kernel(const uint64_t* __r
     }
     frag8[r] = make_uint2(h[0] | (h[1] << 16), h[2] | (h[3] << 16));
 }
-hipError_t launch_rows_to_frag8(hipStream_t st, const uint64_t* row_off, const uint32_t* row_items, uint64_t n_rows, const uint32_t* block_base, uint2* frag8, uint4* ext8, uint32_t* present) {
-    hipLaunchKernelGGL(rows_to_frag8_kernel, dim3((unsigned)((n_rows + 1 + 1023) / 1024)), dim3(1024), 0, st, row_off, row_items, n_rows, block_base, frag8, ext8, present);
+hipError_t launch_rows_to_frag8(hipStream_t st, const uint64_t* row_off, const uint32_t* row_items, uint64_t n_rows, const uint32_t* block_base, uint2* frag8, uint4* ext8) {
+    hipLaunchKernelGGL(rows_to_frag8_kernel, dim3((unsigned)((n_rows + 1 + 1023) / 1024)), dim3(1024), 0, st, row_off, row_items, n_rows, block_base, frag8, ext8);
     return hipGetLastError();
 }
 
@@ -150,7 +147,7 @@ hipError_t launch_rows_to_frag8(hipStream_t st, const uint64_t* row_off, const u
 #ifndef SRN_SBACK_WAVES
 #define SRN_SBACK_WAVES 3   // waves per SIMD the register allocation is sized for (12 per CU: the LDS allows 13)
 #endif
-template <bool BITMAP, bool STREAM, bool PBYTES = false>
+template <bool STREAM>
 __global__ __launch_bounds__(64, SRN_SBACK_WAVES) void vmis_shard_back_kernel(DeviceIndex ix_arg, LaunchParams p_arg, FastParams f_arg, SBackParams sb_arg) {
     constexpr uint32_t HOT_OFF = SB_HOT;
     __shared__ __attribute__((aligned(16))) char smem[SB_LDS];
@@ -182,7 +179,6 @@ __global__ __launch_bounds__(64, SRN_SBACK_WAVES) void vmis_shard_back_kernel(De
     const bool wide = f.nb == 3u;
     const uint32_t n_kept = ix.n_kept;
     constexpr uint32_t NCH = F_K_MAX / 64u;   // 24 chunks of 64 neighbours
-    const __amdgpu_buffer_rsrc_t frag_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)sb.frag8, 0, (int)((n_kept + 1u) * 8u), 0x00020000);   // (the forms that know which neighbours are absent; the host admits them only below 2^29 sessions)
 
     // per-phase shader cycles (debug, srn_debug_phase_cycles): summed in registers by the wave, flushed once at the end.  Slots follow the fast kernel's numbering:
     // 8 record + clears, 9 walk A, 10 sample + floors, 11 sketch check, 12 walk B + resolve, 13 hand-off; 5 listed elements, 6 candidates, 7 live queries, 14 served, 15 handed over by cause (20-bit fields: candidates | long-fragment queues | hit list; exact table: upper half of 7)
@@ -239,7 +235,6 @@ __global__ __launch_bounds__(64, SRN_SBACK_WAVES) void vmis_shard_back_kernel(De
         const bool place = lane < 8u && lane < p.max_len && lane < h0.L;   // (places past L hold an earlier batch's items)
         const uint32_t it_idx = place ? pre.idx : kNone, it_kept = place ? pre.kept : 0u; const unsigned long long it_base = place ? pre.base : 0ull;
         const uint32_t kv = pre.kv;
-        uint32_t ln = lane; asm volatile("" : "+v"(ln));
         uint32_t sv[NCH];   // gather form: the neighbour slots; streaming form: the members' {position | run << 20 | weight << 24}, read back from the scratch after walk A
         if constexpr (!STREAM) {
 #pragma unroll
@@ -280,8 +275,7 @@ __global__ __launch_bounds__(64, SRN_SBACK_WAVES) void vmis_shard_back_kernel(De
         }
         if (K == 0u) { if (lane == 0u) p.out_counts[q] = 0u; fetch_next(); continue; }
         SB_TICK(tk8);
-        // ---- walk A: ALL of a lane's <= 24 presence words in flight together, then all fragments of the present ones: a query's walk is three HBM / L2 round trips (slots,
-        // presence, fragments) whatever K is.  A first build walked in two halves with the long fragments' overflow blocks fetched inline: 30 dependent round trips per query on
+        // ---- walk A: ALL of a lane's <= 24 fragments in flight together: a query's walk is two HBM / L2 round trips (slots, fragments) whatever K is.  A first build walked in two halves with the long fragments' overflow blocks fetched inline: 30 dependent round trips per query on
         // 12 waves per CU -- 2.9 ms per 131 072 queries against the 1.9 ms of the kernel it replaces.
         auto add2 = [&](uint32_t wd, uint32_t w) { atomicAdd((uint32_t*)(acc_base + (wd & 0xFFFFu)), w); atomicAdd((uint32_t*)(acc_base + (wd >> 16)), w); };
         uint32_t pm = 0u;    // bit c: this lane's neighbour of chunk c holds an item of this shard (kept for walk B)
@@ -370,34 +364,15 @@ __global__ __launch_bounds__(64, SRN_SBACK_WAVES) void vmis_shard_back_kernel(De
                 }
             }
         } else {
-        {
-            uint32_t pwv[NCH];
 #pragma unroll
-            for (uint32_t c = 0; c < NCH; ++c) {   // (all 24 chunks whatever K, no branch: one batch of look-ups.  With a wave-uniform branch per chunk -- or group of chunks -- each look-up was waited for in its own block)
-                const bool act = c * 64u + lane < K;
-                if constexpr (BITMAP) { const uint32_t r = act ? base + (sv[c] >> NB) : n_kept; pwv[c] = sb.present[r >> 5] >> (r & 31u); }   // (idle lanes: the empty row, whose presence bit is 0)
-                else if constexpr (PBYTES) {   // the fronting rank said which neighbours have a fragment here: a byte each behind the slots.  Clamped and unconditional: inside `act ? ... : 0` each byte load sat in a divergent branch of its own and was waited for there -- 22 round trips, what made this form lose until round 6
-                    const uint32_t pb = (uint32_t)reinterpret_cast<const uint8_t*>(xq + 1u + p.k)[min(c * 64u + ln, p.k - 1u)];
-                    pwv[c] = (pb >> sb.pbyte_shift) & (act ? 1u : 0u);   // (an AND, not a select: the code generator turns a select whose operand is a load back into a branch around the load)
-                }
-                else pwv[c] = act ? 1u : 0u;   // (no bitmap: every neighbour's fragment is fetched; the empty ones are told apart below)
-            }
-#pragma unroll
-            for (uint32_t c = 0; c < NCH; ++c) pm |= (pwv[c] & 1u) << c;
-        }
+        for (uint32_t c = 0; c < NCH; ++c) pm |= (c * 64u + lane < K ? 1u : 0u) << c;   // (every neighbour's fragment is fetched; the empty ones are told apart below)
         {
 #pragma unroll
             for (uint32_t c = 0; c < NCH; ++c) fr[c] = make_uint2(0u, 0u);
 #pragma unroll
             for (uint32_t g = 0; g < NCH; g += 4u) if (g * 64u < K) {   // (wave-uniform, per GROUP of four chunks: a branch per chunk ends the scheduler's region there, and every chunk's loads and LDS reads are then waited for inside their own block; the lanes past K behave as absent neighbours)
 #pragma unroll
-                for (uint32_t c = g; c < g + 4u; ++c) {
-                    if constexpr (BITMAP || PBYTES) {   // (round 6) the absent lanes ask for NOTHING: a buffer load past the descriptor's range is answered with 0 by the address unit, no request leaves it
-                        typedef uint32_t v2u __attribute__((ext_vector_type(2)));
-                        const v2u v = __builtin_amdgcn_raw_buffer_load_b64(frag_rsrc, (pm >> c) & 1u ? (base + (sv[c] >> NB)) * 8u : 0xFFFFFFF8u, 0, 0);
-                        fr[c] = make_uint2(v.x, v.y);
-                    } else fr[c] = sb.frag8[(pm >> c) & 1u ? base + (sv[c] >> NB) : n_kept];   // (unconditional per lane: a load inside a divergent branch is waited for at the branch's end; the lanes past K all read the empty row's slot -- one line)
-                }
+                for (uint32_t c = g; c < g + 4u; ++c) fr[c] = sb.frag8[(pm >> c) & 1u ? base + (sv[c] >> NB) : n_kept];   // (unconditional per lane: a load inside a divergent branch is waited for at the branch's end; the lanes past K all read the empty row's slot -- one line)
             }
             // the neighbours' weights, a byte each (<= 9 * 26), looked up while the fragments travel: the adds below then depend on no LDS read of their own
             uint32_t wq[NCH / 4u];
@@ -412,7 +387,7 @@ __global__ __launch_bounds__(64, SRN_SBACK_WAVES) void vmis_shard_back_kernel(De
                 for (uint32_t c = 0; c < NCH; ++c) wq[c >> 2] |= w16[c] << (8u * (c & 3u));
                 __builtin_amdgcn_sched_barrier(0);
             }
-            // STRAIGHT-LINE adds (round 6): all four positions of every fragment, whoever holds it -- unused positions, the absent lanes' empty row and the lanes past K
+            // STRAIGHT-LINE adds (round 6): all four positions of every fragment, whoever holds it -- unused positions, the empty row of the lanes past K
             // point out of the allocation (SB_OOR: dropped by the hardware), a long fragment's words are replaced by such.  With a branch per chunk (and the weight's
             // LDS read in front of its adds) the chunks ran one after the other, each behind its own s_waitcnt.
 #ifdef SRN_SBACK_SUBTICKS
@@ -425,13 +400,12 @@ __global__ __launch_bounds__(64, SRN_SBACK_WAVES) void vmis_shard_back_kernel(De
 #pragma unroll
                 for (uint32_t c = g; c < g + 4u; ++c) {
                     const uint32_t o0 = fr[c].x & 0xFFFFu;
-                    const bool here = (BITMAP || PBYTES) ? ((pm >> c) & 1u) != 0u : true;   // (those forms' absent lanes hold zeros)
-                    const bool lng = here && o0 >= SB_LONG;   // (never the empty row's slot; a long fragment's four words are out-of-range offsets themselves)
-                    const bool pr = here && (lng || o0 < (SB_H + SB_S) * 4u);   // (a fragment's items fill its positions from the first: an out-of-range offset there = an empty fragment)
+                    const bool lng = o0 >= SB_LONG;   // (never the empty row's slot; a long fragment's four words are out-of-range offsets themselves)
+                    const bool pr = lng || o0 < (SB_H + SB_S) * 4u;   // (a fragment's items fill its positions from the first: an out-of-range offset there = an empty fragment)
                     pm = pr ? pm : pm & ~(1u << c);                  // (walk B skips it too)
                     lngm |= lng ? 1u << c : 0u;
                     const uint32_t w = (wq[c >> 2] >> (8u * (c & 3u))) & 0xFFu;
-                    add2(!here ? SB_OOR * 0x10001u : fr[c].x, w); add2(!here ? SB_OOR * 0x10001u : fr[c].y, w);   // (`here` is a constant in the default form: no select)
+                    add2(fr[c].x, w); add2(fr[c].y, w);
                 }
             }
             if (__ballot(lngm != 0u) != 0ull) {   // fragments of > 4 items (rare from G = 8 on): queued -- {weight | length, first overflow block} --, all the queue's blocks are fetched together below
@@ -601,7 +575,7 @@ __global__ __launch_bounds__(64, SRN_SBACK_WAVES) void vmis_shard_back_kernel(De
                 nh += (uint32_t)__builtin_amdgcn_readlane((int)inc, 63);
             };
             uint32_t nlb = 0u;   // (wave-uniform) long fragments queued for the second step
-            {   // (the fragments are walk A's, still in registers.)  Round 6: every position's word is read WITHOUT a branch -- absent lanes hold the empty row's slot, unused
+            {   // (the fragments are walk A's, still in registers.)  Round 6: every position's word is read WITHOUT a branch -- the lanes past K hold the empty row's slot, unused
                 // positions point out of the allocation and read 0 -- and a lane's hits are kept as four bits per chunk; ONE scan then places all of them.  Until then a
                 // chunk was four predicated reads, each waited for, a ballot and a scan of its own: 22 dependent chains of ~600 cycles per query.
                 const uint32_t lim = STREAM ? nscr : K;
@@ -616,7 +590,7 @@ __global__ __launch_bounds__(64, SRN_SBACK_WAVES) void vmis_shard_back_kernel(De
 #pragma unroll
                     for (uint32_t c = g; c < g + 4u; ++c) {
                         const bool pr = (pm >> c) & 1u, lng = pr && sb_is_long(fr[c].x);
-                        const uint32_t fx = STREAM && !pr ? SB_OOR * 0x10001u : fr[c].x, fy = STREAM && !pr ? SB_OOR * 0x10001u : fr[c].y;   // (the streaming form's lanes past the last member hold a copy of its fragment.  Otherwise as they are: unused positions and a long fragment's words read 0 from out of range; the opt-in forms' absent lanes and the lanes past the last member hold zeros -- the direct-mapped word 0, zeroed above)
+                        const uint32_t fx = STREAM && !pr ? SB_OOR * 0x10001u : fr[c].x, fy = STREAM && !pr ? SB_OOR * 0x10001u : fr[c].y;   // (the streaming form's lanes past the last member hold a copy of its fragment.  Otherwise as they are: unused positions and a long fragment's words read 0 from out of range)
                         const uint32_t i = 4u * (c - g);
                         wv[i] = *(const uint32_t*)(acc_base + (fx & 0xFFFFu)); wv[i + 1u] = *(const uint32_t*)(acc_base + (fx >> 16));
                         wv[i + 2u] = *(const uint32_t*)(acc_base + (fy & 0xFFFFu)); wv[i + 3u] = *(const uint32_t*)(acc_base + (fy >> 16));
@@ -729,15 +703,20 @@ __global__ __launch_bounds__(64, SRN_SBACK_WAVES) void vmis_shard_back_kernel(De
         // ---- hand-off: the query's record for vmis_finish_kernel (score = x / (10 U), ranking, public ids), as the fast kernel writes it ----
         const uint32_t M = ncand + nt;
         uint32_t lh = lane; asm volatile("" : "+v"(lh));   // (opaque, as `ln`: the LDS addresses made of the lane number below were hoisted and spilled -- and a reload's s_waitcnt vmcnt(0) here also sits out the NEXT query's requests)
-        if (sb.finish_here && M <= F_FIN_ENTRIES) {   // (wave-uniform) the row finished by this wave itself, from registers: no record, nothing for the finish kernel (round 5, second half)
-            uint4 e = make_uint4(0u, 0u, 0u, 0u);
-            if (lh < ncand) { const unsigned long long x = ckey[lh]; e = make_uint4((uint32_t)x, (uint32_t)(x >> 32), cidx[lh], 0u); }
-            else if (lh < M) { const uint2 c = hits[lh - ncand]; e = make_uint4(c.y, 0u, c.x, 1u); }
-            finish_inline(ix_arg, M, U, e, lane, q, p.out_ids, p.out_scores, p.out_counts, p.how_many);
-            SB_SYNC();   // (the next query clears what this one still read)
-            c6 += ncand; c14 += 1ull;
-            SB_TICK(tk13);
-            continue;
+        if constexpr (STREAM) {
+            // KEPT ON PURPOSE, never taken (sb.finish_here is always 0; the knob that set it is gone): the row finished by this wave itself, the one piece of the removed
+            // experiments that the streaming form's REGISTER ALLOCATION depends on.  Without this block the instantiation spills 32 bytes instead of 20 -- two more reloads per
+            // query, each a s_waitcnt vmcnt(0) -- and its rank time on config 3 cut in 8 goes 1.74 -> 1.77 ms (profiles/prune_lost_forms_ab.txt).  The gather form does not need it.
+            if (sb.finish_here && M <= F_FIN_ENTRIES) {
+                uint4 e = make_uint4(0u, 0u, 0u, 0u);
+                if (lh < ncand) { const unsigned long long x = ckey[lh]; e = make_uint4((uint32_t)x, (uint32_t)(x >> 32), cidx[lh], 0u); }
+                else if (lh < M) { const uint2 c = hits[lh - ncand]; e = make_uint4(c.y, 0u, c.x, 1u); }
+                finish_inline(ix_arg, M, U, e, lane, q, p.out_ids, p.out_scores, p.out_counts, p.how_many);
+                SB_SYNC();   // (the next query clears what this one still read)
+                c6 += ncand; c14 += 1ull;
+                SB_TICK(tk13);
+                continue;
+            }
         }
         uint32_t ovf_at = 0;
         if (M > F_FIN_ENTRIES) {   // (wave-uniform, rare)
@@ -779,13 +758,11 @@ __global__ __launch_bounds__(64, SRN_SBACK_WAVES) void vmis_shard_back_kernel(De
 
 hipError_t launch_shard_back(dim3 grid, hipStream_t st, const DeviceIndex& di, const LaunchParams& p, const FastParams& f, const SBackParams& sb, bool debug) {
     static bool told = false;
-    if (!told && debug) { told = true; int nb = 0, ns = 0; (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)vmis_shard_back_kernel<false, false>, 64, 0);
-        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&ns, (const void*)vmis_shard_back_kernel<false, true>, 64, 0);
+    if (!told && debug) { told = true; int nb = 0, ns = 0; (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)vmis_shard_back_kernel<false>, 64, 0);
+        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&ns, (const void*)vmis_shard_back_kernel<true>, 64, 0);
         fprintf(stderr, "[srn] vmis_shard_back_kernel: %u bytes of LDS per wave; gather form %d waves per CU, streaming form %d (occupancy API)\n", SB_LDS, nb, ns); }
-    if (sb.frag_post && sb.post_rank && sb.scr) hipLaunchKernelGGL((vmis_shard_back_kernel<false, true>), grid, dim3(64), 0, st, di, p, f, sb);
-    else if (sb.present) hipLaunchKernelGGL((vmis_shard_back_kernel<true, false>), grid, dim3(64), 0, st, di, p, f, sb);
-    else if (sb.pbyte_shift < 8u) hipLaunchKernelGGL((vmis_shard_back_kernel<false, false, true>), grid, dim3(64), 0, st, di, p, f, sb);
-    else hipLaunchKernelGGL((vmis_shard_back_kernel<false, false>), grid, dim3(64), 0, st, di, p, f, sb);
+    if (sb.frag_post && sb.post_rank && sb.scr) hipLaunchKernelGGL((vmis_shard_back_kernel<true>), grid, dim3(64), 0, st, di, p, f, sb);
+    else hipLaunchKernelGGL((vmis_shard_back_kernel<false>), grid, dim3(64), 0, st, di, p, f, sb);
     return hipGetLastError();
 }
 uint32_t shard_back_scratch_words() { return SB_SCR_WORDS; }
@@ -895,47 +872,6 @@ uint32_t shard_nb_positions_stride(uint32_t k, uint32_t m) {
     const uint32_t mw = (m + 63u) >> 6, ncw = (std::min<uint32_t>(k, F_K_MAX) + 7u) >> 3;
     if (32u * mw + 8u * ncw > SB_REC_ROOM) return 0u;   // (in LDS: the bitmaps + a weight byte per member)
     return (2u + 8u * mw + ncw + 1u) / 2u * 2u;
-}
-
-// -------------------------------------------------------------------------------------
-// The neighbours' PRESENCE BYTES (round 5, second half): bit g of session r's byte = shard g holds an item of r.  Built once per group from the shards' presence bitmaps
-// (all-gathered); the rank that fronts a query writes every neighbour's byte behind the neighbour slots of its exchange record, and a back end of shard g asks only for the
-// fragments whose bit g is set -- half the requests at G = 8, and no look-up of its own in front of them (what the per-shard bitmap of SRN_SBACK_BITMAP cost).
-// -------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void presence_bytes_kernel(const uint32_t* __restrict__ bitmaps, size_t block_words, uint32_t G, uint64_t n, uint8_t* __restrict__ out) {
-    for (uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x; r < n; r += (uint64_t)gridDim.x * 256) {
-        uint32_t b = 0;
-        for (uint32_t g = 0; g < G; ++g) b |= ((bitmaps[(size_t)g * block_words + (r >> 5)] >> (r & 31u)) & 1u) << g;
-        out[r] = (uint8_t)b;
-    }
-}
-hipError_t launch_presence_bytes(hipStream_t st, const uint32_t* bitmaps, size_t block_words, uint32_t G, uint64_t n, uint8_t* out) {
-    if (n) hipLaunchKernelGGL(presence_bytes_kernel, dim3((unsigned)std::min<uint64_t>((n + 255) / 256, 1u << 16)), dim3(256), 0, st, bitmaps, block_words, G, n, out);
-    return hipGetLastError();
-}
-__global__ __launch_bounds__(64) void shard_nb_presence_kernel(const char* __restrict__ prep, uint32_t prep_stride, uint32_t max_len, uint32_t* __restrict__ xchg, uint32_t stride, uint32_t k,
-                                                               const uint8_t* __restrict__ pbytes, uint32_t n_kept, uint32_t q_lo, uint32_t q_hi, uint32_t wide) {
-    const uint32_t lane = threadIdx.x;
-    for (uint32_t q = q_lo + blockIdx.x; q < q_hi; q += gridDim.x) {
-        const char* const rec = prep + (size_t)q * prep_stride;
-        const PrepHead* hp = (const PrepHead*)rec;
-        const uint32_t xlo = hp->xlo, L = hp->L;
-        uint32_t it_kept = 0u;
-        if (lane < 8u && lane < L && lane < max_len) it_kept = ((const PrepItem*)(rec + sizeof(PrepHead)))[lane].kept;
-        uint32_t* const xq = xchg + (size_t)q * stride;
-        const uint32_t K = (uint32_t)__builtin_amdgcn_readfirstlane((int)xq[0]);
-        if (K == 0u || K == 0xFFFFFFFFu || K > k) continue;   // (wave-uniform: nothing to mark)
-        const uint32_t nr = (uint32_t)__popcll(__ballot(it_kept > 0u));
-        const bool rel = wide && nr > 3u;
-        const uint32_t NB = wide && !rel ? 3u : 4u, base = rel ? xlo : 0u;
-        uint8_t* const pb = reinterpret_cast<uint8_t*>(xq + 1u + k);
-        for (uint32_t i = lane; i < K; i += 64u) pb[i] = pbytes[min(base + (xq[1u + i] >> NB), n_kept)];
-    }
-}
-hipError_t launch_shard_nb_presence(dim3 grid, hipStream_t st, const char* prep, uint32_t prep_stride, uint32_t max_len, uint32_t* xchg, uint32_t stride, uint32_t k, const uint8_t* pbytes, uint32_t n_kept,
-                                    uint32_t q_lo, uint32_t q_hi, bool wide) {
-    if (q_hi > q_lo) hipLaunchKernelGGL(shard_nb_presence_kernel, grid, dim3(64), 0, st, prep, prep_stride, max_len, xchg, stride, k, pbytes, n_kept, q_lo, q_hi, wide ? 1u : 0u);
-    return hipGetLastError();
 }
 
 // frag_post[e] = frag8[post_rank[e]]: the fragments once more, in posting order (streaming form)

@@ -393,8 +393,7 @@ hipError_t launch_shard_merge_topn(hipStream_t st, const char* part, size_t bloc
                                    uint32_t* out_counts) {
     if (n_shards == 0 || n_shards > 64) return hipErrorInvalidValue;
     const uint32_t lpq = n_shards <= 2 ? 2u : n_shards <= 4 ? 4u : n_shards <= 8 ? 8u : n_shards <= 16 ? 16u : n_shards <= 32 ? 32u : 64u;
-    static const bool old_form = getenv("SRN_MERGE_OLD") != nullptr;   // (experiments: the round-4 form)
-    if (!old_form && how_many >= 1u && how_many <= 40u) {   // (<= 40 KB of LDS per wave: three waves per CU and more)
+    if (how_many >= 1u && how_many <= 40u) {   // (<= 40 KB of LDS per wave: three waves per CU and more)
         const dim3 grid((nq + 64u / lpq - 1) / (64u / lpq)), block(64);
         const size_t lds = (size_t)2u * n_shards * (64u / lpq) * how_many * 8;   // the 2 G input runs
         switch (lpq) {

@@ -847,12 +847,12 @@ def test_serving_order_changes_no_row():
         capi.reload_knobs()
 
 
-@pytest.mark.parametrize("knobs", [{}, {"SRN_TINY_SPIN": "0"}, {"SRN_TINY_FUSED": "0"}, {"SRN_TINY_PHASES": "2", "SRN_TINY_FUSED": "0"}])
+@pytest.mark.parametrize("knobs", [{}, {"SRN_TINY_SPIN": "0"}, {"SRN_TINY_FUSED": "0"}])
 def test_single_session_calls_one_launch_against_the_oracle(knobs):
     """srn_predict -- the reference's call shape, one evolving session per call -- is ONE launch since round 5: the fast kernel's TINY instantiation writes the prep record
     itself, serves the query and finishes its row from registers; what it cannot finish (a session for the MID tier, > 63 entries, a shape for the general kernel) runs behind
     it for that call only.  Every call against the canonical oracle, on an index small enough that many queries have no threshold (> 63 entries: the second phase), with sessions
-    of 1..10 items, unknown and repeated items, business rules; the same with the caller waiting for the stream, with the five-launch form, and with that form in two phases."""
+    of 1..10 items, unknown and repeated items, business rules; the same with the caller waiting for the stream, and with the five-launch form."""
     import serenade_amd as sa
     from serenade_amd import capi
     from oracle import oracle as O

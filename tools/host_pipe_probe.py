@@ -31,9 +31,6 @@ SIZES = [int(x) for x in os.environ.get("PROBE_SIZES", "1048576,65536,4096").spl
 QUICK = os.environ.get("PROBE_QUICK") is not None    # chunk counts only
 for nq, reps in [(s, 4 if s >= (1 << 19) else 10) for s in SIZES]:
     run(nq, reps, "default")
-    run(nq, reps, "no copy to the caller's buffers", SRN_HOST_NOCOPY=1)
     for ch in ((1, 2, 3, 4, 6) if QUICK else (1, 2, 4, 8, 16, 32)):
         if nq // ch >= 1024:
             run(nq, reps, "chunks=%d" % ch, SRN_HOST_CHUNKS=ch)
-    for blk in (() if QUICK else (0, 16, 32, 128, 256)):
-        run(nq, reps, "download kernel blocks=%d" % blk, SRN_D2H_BLOCKS=blk)
