@@ -417,6 +417,53 @@ int srn_recommend(srn_batcher_t* b, srn_session_store_t* s, const char* session_
                   int user_consent, size_t max_items_in_session, uint64_t now_secs, uint64_t* out_ids, double* out_scores,
                   size_t* out_n);
 
+/* ---- device-resident session store + /v1/recommend for a whole batch ----------------------------------------------------
+ * The same handler body with the evolving sessions in HBM (srn_sessions_dev.hip): one call takes n (session key, clicked item, consent) triples, applies the update
+ * rule above to the store and predicts every request's session, through the launch sequence of srn_predict_batch_device, with no host round trip in between.
+ * The result -- rows AND store -- is what n calls of srn_recommend in request order with the same now_secs and max_items_in_session give: a request sees the session as
+ * the earlier requests of its key in the batch left it (any multiplicity; keys compared by all 128 bits); without consent the session is [item] and the store is not
+ * touched, not even its clock.  A stored session longer than a since-lowered max_items_in_session stays that long (one item is dropped per append), as in the reference.
+ *   capacity   live sessions the table holds: a power-of-two open-addressing table of >= 2 * capacity slots, allocated (twice: a sweep rebuilds into the other half,
+ *              there are no tombstones) at creation.  The host keeps an upper bound of the occupied slots (+ n per call); a call that would pass `capacity` by that bound
+ *              waits for the device, takes the exact count and, if that is what makes room, drops the entries older than ttl_secs; if live sessions + n still exceed
+ *              capacity it fails with SRN_ENOMEM and the store is as it was.  Size capacity >= peak live sessions + largest batch; the normal path reads nothing back.
+ *   items_cap  items a stored session may have (1..SRN_MAX_SESSION_LEN); max_items_in_session above it: SRN_ERANGE.  A slot is 32 + 8 * items_cap bytes rounded up to 128.
+ *   ttl_secs / idle_secs: as srn_session_store_create (0 = 30 / 20 minutes); ttl_secs < idle_secs: SRN_EINVAL (TTL governs reclamation only).
+ * Calls on one store from several threads or streams are serialised by the library (a mutex for the enqueue, an event between consecutive calls); different stores run
+ * side by side.  Errors are raised before anything is changed: max_items_in_session 0 SRN_EINVAL; predict's own checks as ever; a store on another device than the index
+ * SRN_EINVAL; n = 0 SRN_OK. */
+typedef struct srn_device_sessions srn_device_sessions_t;
+typedef struct {
+    uint64_t capacity, slots, items_cap, slot_bytes;
+    uint64_t live_bound;        /* the host's upper bound of the occupied slots */
+    uint64_t sweeps, refused;   /* rebuilds that dropped expired entries (explicit or automatic) | calls refused with SRN_ENOMEM for capacity */
+    uint64_t ttl_secs, idle_secs;
+    uint64_t max_stored_len;    /* upper bound of the stored session lengths = the max_len_hint predict is called with */
+} srn_device_sessions_stats_t;
+int srn_device_sessions_create(int device, size_t capacity, size_t items_cap, uint64_t ttl_secs, uint64_t idle_secs, srn_device_sessions_t** out);
+void srn_device_sessions_free(srn_device_sessions_t* s);
+/* srn_session_store_get / _update / _sweep for the device store, from the host (tests, debugging, seeding a store from another one): they block.
+ * update: n above items_cap is SRN_ERANGE.  sweep: *n_live = entries kept. */
+int srn_device_sessions_get(srn_device_sessions_t* s, uint64_t key_hi, uint64_t key_lo, uint64_t now_secs, uint64_t* out_items, size_t cap, size_t* out_n);
+int srn_device_sessions_update(srn_device_sessions_t* s, uint64_t key_hi, uint64_t key_lo, uint64_t now_secs, const uint64_t* items, size_t n);
+int srn_device_sessions_sweep(srn_device_sessions_t* s, uint64_t now_secs, uint64_t* n_live);
+int srn_device_sessions_stats(srn_device_sessions_t* s, srn_device_sessions_stats_t* out);
+/* HIP events around the store's kernels and predict's launches of every batch (off by default); last_ms blocks until the most recent batch is done */
+int srn_device_sessions_timing(srn_device_sessions_t* s, int enable);
+int srn_device_sessions_last_ms(srn_device_sessions_t* s, double* out_ms_store, double* out_ms_predict);
+/* srn_session_key for n strings: string i = ids_flat[off[i] .. off[i + 1]) */
+int srn_session_keys(const char* ids_flat, const uint64_t* off, size_t n, uint64_t* key_hi, uint64_t* key_lo);
+/* Every buffer in the index's device memory; enqueued on `stream` (a hipStream_t) without host synchronisation.  d_consent: one byte per request, NULL = every request
+ * consents.  out rows / counts as srn_predict_batch_device.  store may be NULL only if no request consents (d_consent == NULL with a NULL store: SRN_EINVAL; otherwise the
+ * flags are read back and checked before anything is launched -- that call blocks).  now_secs = 0: the system clock, read once. */
+int srn_recommend_batch_device(const srn_index_t* idx, srn_device_sessions_t* store, const uint64_t* d_key_hi, const uint64_t* d_key_lo, const uint64_t* d_item_ids,
+                               const uint8_t* d_consent, size_t n, uint64_t now_secs, size_t max_items_in_session, size_t k, size_t m, size_t how_many,
+                               unsigned flags, uint64_t* d_out_ids, double* d_out_scores, uint32_t* d_out_counts, void* stream);
+/* The same with host pointers (pageable allowed); the results are in the caller's buffers on return. */
+int srn_recommend_batch(const srn_index_t* idx, srn_device_sessions_t* store, const uint64_t* key_hi, const uint64_t* key_lo, const uint64_t* item_ids,
+                        const uint8_t* consent, size_t n, uint64_t now_secs, size_t max_items_in_session, size_t k, size_t m, size_t how_many,
+                        unsigned flags, uint64_t* out_ids, double* out_scores, uint32_t* out_counts);
+
 /* ---- offline evaluation: test sets and hyper-parameter trials ----------------------------------------------------------
  * The reference's evaluation loop (src/bin/evaluator.rs:46-76, src/objective.rs:8-52) on the GPU: every prefix of every test session is
  * predicted and scored against the rest of its session, and the eight metrics of src/metrics/evaluation_reporter.rs come back.  Prefixes,

@@ -42,6 +42,12 @@ int srn_debug_sback_launches(const srn_index_t* idx, uint64_t* out_launches);
  * cap < n: SRN_ERANGE).  *out (may be NULL) = what srn_evaluate returns for the trial. */
 int srn_debug_eval_terms(srn_eval_set_t* set, const srn_eval_trial_t* trial, double* out_terms, size_t cap, size_t* out_n, srn_eval_result_t* out);
 
+/* Test / measurement aid: the sessions the store's most recent srn_recommend_batch* call emitted (request q = items[q_off[q] .. q_off[q + 1])), where predict read them:
+ * the device pointers (valid until the next call on the store), the request count and the max_len_hint; with h_q_off ([n + 1]) / h_items (cap entries) also copied to
+ * the host.  Any output may be NULL.  Blocks until that call is done. */
+int srn_debug_device_sessions_last_batch(srn_device_sessions_t* s, const void** d_items, const void** d_q_off, size_t* out_n, size_t* out_max_len,
+                                         uint64_t* h_items, size_t cap, uint32_t* h_q_off);
+
 /* Test / experiment knobs (environment variables SRN_NO_FAST, SRN_NO_MID, SRN_NO_MASKS, SRN_NO_MERGE, SRN_DENSE, SRN_HOT_SLOTS,
  * SRN_SKETCH_SLOTS, SRN_LDS_BUDGET_KB, SRN_GRID_MULT, SRN_DEBUG) force individual kernel code paths.  They are read ONCE,
  * when the library is first used -- never on the launch path; this call re-reads them (the parity tests switch paths

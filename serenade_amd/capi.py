@@ -71,6 +71,10 @@ class LoadInfo(C.Structure):
 EVENTS_TIME_I64, EVENTS_DEVICE = 1, 2
 
 
+class DeviceSessionsStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("capacity", "slots", "items_cap", "slot_bytes", "live_bound", "sweeps", "refused", "ttl_secs", "idle_secs", "max_stored_len")]
+
+
 class Limits(C.Structure):
     _fields_ = [("max_how_many", C.c_uint32), ("max_session_len", C.c_uint32), ("max_k", C.c_uint32), ("reserved", C.c_uint32)]
 
@@ -154,6 +158,18 @@ SYMBOLS = {
     "srn_evaluate": (_i, [_vp, C.POINTER(EvalTrial), _sz, C.POINTER(EvalResult), _vp]),
     "srn_eval_set_free": (None, [_vp]),
     "srn_debug_eval_terms": (_i, [_vp, C.POINTER(EvalTrial), _vp, _sz, C.POINTER(_sz), C.POINTER(EvalResult)]),
+    "srn_device_sessions_create": (_i, [_i, _sz, _sz, _u64, _u64, C.POINTER(_vp)]),
+    "srn_device_sessions_free": (None, [_vp]),
+    "srn_device_sessions_get": (_i, [_vp, _u64, _u64, _u64, _vp, _sz, C.POINTER(_sz)]),
+    "srn_device_sessions_update": (_i, [_vp, _u64, _u64, _u64, _vp, _sz]),
+    "srn_device_sessions_sweep": (_i, [_vp, _u64, C.POINTER(_u64)]),
+    "srn_device_sessions_stats": (_i, [_vp, C.POINTER(DeviceSessionsStats)]),
+    "srn_device_sessions_timing": (_i, [_vp, _i]),
+    "srn_device_sessions_last_ms": (_i, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "srn_session_keys": (_i, [_vp, _vp, _sz, _vp, _vp]),
+    "srn_recommend_batch_device": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _u64, _sz, _sz, _sz, _sz, C.c_uint, _vp, _vp, _vp, _vp]),
+    "srn_recommend_batch": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _u64, _sz, _sz, _sz, _sz, C.c_uint, _vp, _vp, _vp]),
+    "srn_debug_device_sessions_last_batch": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_sz), C.POINTER(_sz), _vp, _sz, _vp]),
     "srn_device_count": (_i, [C.POINTER(_i)]),
     "srn_limits": (None, [C.POINTER(Limits)]),
     "srn_last_error": (C.c_char_p, []),

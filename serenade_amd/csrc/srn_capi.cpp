@@ -597,4 +597,60 @@ int srn_debug_eval_terms(srn_eval_set_t* set, const srn_eval_trial_t* trial, dou
 
 void srn_eval_set_free(srn_eval_set_t* set) { eval_set_free(set); }
 
+// ---- device-resident session store (srn_sessions_dev.hip) ----
+int srn_device_sessions_create(int device, size_t capacity, size_t items_cap, uint64_t ttl_secs, uint64_t idle_secs, srn_device_sessions_t** out) {
+    return guarded([&]() -> int { return dsess_create(device, capacity, items_cap, ttl_secs, idle_secs, out); });
+}
+void srn_device_sessions_free(srn_device_sessions_t* s) { dsess_free(s); }
+int srn_device_sessions_get(srn_device_sessions_t* s, uint64_t key_hi, uint64_t key_lo, uint64_t now_secs, uint64_t* out_items, size_t cap, size_t* out_n) {
+    return guarded([&]() -> int { return dsess_get(s, key_hi, key_lo, now_secs, out_items, cap, out_n); });
+}
+int srn_device_sessions_update(srn_device_sessions_t* s, uint64_t key_hi, uint64_t key_lo, uint64_t now_secs, const uint64_t* items, size_t n) {
+    return guarded([&]() -> int { return dsess_update(s, key_hi, key_lo, now_secs, items, n); });
+}
+int srn_device_sessions_sweep(srn_device_sessions_t* s, uint64_t now_secs, uint64_t* n_live) {
+    return guarded([&]() -> int { return dsess_sweep(s, now_secs, n_live); });
+}
+int srn_device_sessions_stats(srn_device_sessions_t* s, srn_device_sessions_stats_t* out) { return guarded([&]() -> int { return dsess_stats(s, out); }); }
+int srn_device_sessions_timing(srn_device_sessions_t* s, int enable) { return guarded([&]() -> int { return dsess_timing(s, enable); }); }
+int srn_device_sessions_last_ms(srn_device_sessions_t* s, double* out_ms_store, double* out_ms_predict) {
+    return guarded([&]() -> int { return dsess_last_ms(s, out_ms_store, out_ms_predict); });
+}
+int srn_debug_device_sessions_last_batch(srn_device_sessions_t* s, const void** d_items, const void** d_q_off, size_t* out_n, size_t* out_max_len,
+                                         uint64_t* h_items, size_t cap, uint32_t* h_q_off) {
+    return guarded([&]() -> int { return dsess_last_csr(s, d_items, d_q_off, out_n, out_max_len, h_items, cap, h_q_off); });
+}
+
+// the checks both entry points share, in srn_predict_batch_device's order; *done: nothing to do (n == 0)
+static int check_recommend_args(const srn_index_t* idx, size_t n, size_t k, size_t m, size_t how_many, unsigned flags, bool buffers, bool* done) {
+    *done = false;
+    int rc = check_predict_args(idx, k, m, how_many); if (rc) return rc;
+    rc = check_not_a_shard(idx); if (rc) return rc;
+    if (n == 0) { *done = true; return SRN_OK; }
+    if (!buffers) return fail(SRN_EINVAL, "null buffer");
+    if (flags & ~(unsigned)SRN_FLAG_BUSINESS_LOGIC) return fail(SRN_EINVAL, "srn_recommend_batch: unknown flags");
+    return SRN_OK;
+}
+int srn_recommend_batch_device(const srn_index_t* idx, srn_device_sessions_t* store, const uint64_t* d_key_hi, const uint64_t* d_key_lo, const uint64_t* d_item_ids,
+                               const uint8_t* d_consent, size_t n, uint64_t now_secs, size_t max_items_in_session, size_t k, size_t m, size_t how_many,
+                               unsigned flags, uint64_t* d_out_ids, double* d_out_scores, uint32_t* d_out_counts, void* stream) {
+    return guarded([&]() -> int {
+        bool done;
+        int rc = check_recommend_args(idx, n, k, m, how_many, flags, d_key_hi && d_key_lo && d_item_ids && d_out_ids && d_out_scores && d_out_counts, &done);
+        if (rc || done) return rc;
+        return dsess_recommend_device(idx, store, d_key_hi, d_key_lo, d_item_ids, d_consent, n, now_secs, max_items_in_session, k, m, how_many, flags,
+                                      d_out_ids, d_out_scores, d_out_counts, stream); });
+}
+int srn_recommend_batch(const srn_index_t* idx, srn_device_sessions_t* store, const uint64_t* key_hi, const uint64_t* key_lo, const uint64_t* item_ids,
+                        const uint8_t* consent, size_t n, uint64_t now_secs, size_t max_items_in_session, size_t k, size_t m, size_t how_many,
+                        unsigned flags, uint64_t* out_ids, double* out_scores, uint32_t* out_counts) {
+    return guarded([&]() -> int {
+        bool done;
+        int rc = check_recommend_args(idx, n, k, m, how_many, flags, key_hi && key_lo && item_ids && out_ids && out_scores && out_counts, &done);
+        if (rc || done) return rc;
+        if (max_items_in_session == 0) return fail(SRN_EINVAL, "srn_recommend_batch: max_items_in_session must be > 0");
+        return dsess_recommend_host(idx, store, key_hi, key_lo, item_ids, consent, n, now_secs, max_items_in_session, k, m, how_many, flags,
+                                    out_ids, out_scores, out_counts); });
+}
+
 }  // extern "C"

@@ -240,3 +240,22 @@ int eval_run(srn_eval_set* set, const srn_eval_trial_t* trials, size_t n_trials,
 uint64_t eval_n_queries(const srn_eval_set* set);   // queries of any trial: sum over sessions of (len - 1)
 void eval_set_free(srn_eval_set* set);
 }  // namespace srn
+
+// ---- device-resident session store (srn_sessions_dev.hip); arguments of the batch calls already checked by the C ABI glue ----
+namespace srn {
+int dsess_create(int device, size_t capacity, size_t items_cap, uint64_t ttl_secs, uint64_t idle_secs, srn_device_sessions** out);
+void dsess_free(srn_device_sessions* s);
+int dsess_get(srn_device_sessions* s, uint64_t hi, uint64_t lo, uint64_t now_secs, uint64_t* out_items, size_t cap, size_t* out_n);
+int dsess_update(srn_device_sessions* s, uint64_t hi, uint64_t lo, uint64_t now_secs, const uint64_t* items, size_t n);
+int dsess_sweep(srn_device_sessions* s, uint64_t now_secs, uint64_t* n_live);
+int dsess_stats(srn_device_sessions* s, srn_device_sessions_stats_t* out);
+int dsess_timing(srn_device_sessions* s, int enable);
+int dsess_last_ms(srn_device_sessions* s, double* ms_store, double* ms_predict);
+int dsess_last_csr(srn_device_sessions* s, const void** d_items, const void** d_qoff, size_t* n, size_t* max_len, uint64_t* h_items, size_t cap, uint32_t* h_qoff);
+int dsess_recommend_device(const srn_index* idx, srn_device_sessions* s, const uint64_t* d_hi, const uint64_t* d_lo, const uint64_t* d_item, const uint8_t* d_consent,
+                           size_t n, uint64_t now_secs, size_t max_items, size_t k, size_t m, size_t how_many, unsigned flags,
+                           uint64_t* d_ids, double* d_scores, uint32_t* d_counts, void* stream);
+int dsess_recommend_host(const srn_index* idx, srn_device_sessions* s, const uint64_t* hi, const uint64_t* lo, const uint64_t* item, const uint8_t* consent,
+                         size_t n, uint64_t now_secs, size_t max_items, size_t k, size_t m, size_t how_many, unsigned flags,
+                         uint64_t* ids, double* scores, uint32_t* counts);
+}  // namespace srn

@@ -110,6 +110,17 @@ int srn_session_key(const char* session_id, size_t len, uint64_t* key_hi, uint64
     return SRN_OK;
 }
 
+int srn_session_keys(const char* ids_flat, const uint64_t* off, size_t n, uint64_t* key_hi, uint64_t* key_lo) {
+    if (n == 0) return SRN_OK;
+    if (!off || !key_hi || !key_lo || (off[n] && !ids_flat)) return fail(SRN_EINVAL, "srn_session_keys: null argument");
+    for (size_t i = 0; i < n; ++i) {
+        if (off[i + 1] < off[i]) return fail(SRN_EINVAL, "srn_session_keys: offsets not monotone");
+        const int rc = srn_session_key(ids_flat ? ids_flat + off[i] : nullptr, (size_t)(off[i + 1] - off[i]), key_hi + i, key_lo + i);
+        if (rc != SRN_OK) return rc;
+    }
+    return SRN_OK;
+}
+
 int srn_session_store_create(uint64_t ttl_secs, uint64_t idle_secs, srn_session_store_t** out) {
     return guarded([&] {
         if (!out) return fail(SRN_EINVAL, "srn_session_store_create: null output");

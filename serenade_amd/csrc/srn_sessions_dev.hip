@@ -1,0 +1,591 @@
+// Device-resident evolving-session store and the batched /v1/recommend body (include/serenade_hip.h, "device-resident session store").
+//
+// srn_recommend (srn_session_store.cpp) is the handler body for ONE request against a host table.  Here the table lives in HBM and one call applies the
+// handler's update rule (recommend_resource.rs:39-56, sessions/mod.rs:37-72) to a whole batch of (key, clicked item, consent) triples, exactly as if the
+// requests had been served one after the other, and predicts every request's session through device_predict -- the launch sequence of srn_predict_batch_device.
+//
+// The table: power-of-two open addressing, linear probing, load <= 0.5, no tombstones (a sweep rebuilds into the second table).  One slot per visitor:
+//   { key_hi u64 | key_lo u64 | epoch u64 | len u32 | state u32 | items u64[items_cap] }   rounded up to a multiple of 128 bytes, 128-byte aligned
+// so that a request touches one aligned slot (items_cap <= 12: one 128-byte line).  state: 0 empty, 1 occupied, 2 claimed by the find kernel of the running call.
+//
+// A batch, all on the caller's stream, nothing read back:
+//   sort            request indices, stable, by (no consent, key_hi, key_lo): the requests of one visitor become one contiguous RUN in request order
+//   sess_find       one lane per run head: find-or-insert the slot.  Two heads never hold the same key, so a slot in state 2 is never "mine" and the loser
+//                   of a claim probes on: nobody waits for anybody.  Reads the stored length under the idle rule
+//   scans           the update rule needs no walk: request j of a run appends iff its item differs from its predecessor's (the stored last item for the
+//                   head), so "kept" is a flag per request, its prefix count inside the run gives every request's session as a window of
+//                   (stored items ++ kept clicks of the run), and the window's length is min(stored + kept so far, limit) (or the stored length where that
+//                   already exceeds a since-lowered limit: one item is dropped per append)
+//   sess_len        window lengths in ORIGINAL request order + the kept clicks compacted; exclusive scan -> q_off
+//   sess_emit       every request copies its window into items_flat: O(window) per request, whatever the run's length
+//   sess_store      the last request of a run writes its window -- the final session -- and the epoch back, once
+//   device_predict  on (items_flat, q_off)
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cstring>
+#include <mutex>
+#include <vector>
+
+#include <rocprim/rocprim.hpp>
+
+#include "srn_internal.h"
+#include "srn_runtime.h"
+#include "srn_device.h"
+#include "srn_hipsync.h"
+
+namespace srn {
+
+namespace {
+constexpr uint32_t kTPB = 256;
+constexpr uint32_t kSlotHead = 32;             // bytes before the items
+constexpr uint32_t kMaxBatch = 1u << 24;       // q_off is 32-bit: n * SRN_MAX_SESSION_LEN < 2^32
+constexpr uint32_t kEmpty = 0, kFull = 1, kClaimed = 2;
+
+struct SlotHead { uint64_t key_hi, key_lo, epoch; uint32_t len, state; };
+static_assert(sizeof(SlotHead) == kSlotHead, "slot header");
+
+struct Table { char* base; uint32_t mask, stride; };
+__device__ __forceinline__ SlotHead* slot_at(const Table& t, uint32_t s) { return (SlotHead*)(t.base + (size_t)s * t.stride); }
+__device__ __forceinline__ uint64_t* slot_items(SlotHead* h) { return (uint64_t*)((char*)h + kSlotHead); }
+__device__ __forceinline__ uint32_t key_hash(uint64_t hi, uint64_t lo) { return (uint32_t)dev_mix64(lo ^ dev_mix64(hi)); }
+__host__ __device__ __forceinline__ bool idle_or_old(uint64_t now, uint64_t epoch, uint64_t limit) { return now > epoch && now - epoch > limit; }
+
+struct BatchArgs {
+    Table t;
+    const uint64_t* key_hi; const uint64_t* key_lo; const uint64_t* item; const uint8_t* consent;   // the caller's arrays
+    const uint32_t* order;   // [n] request index of each sorted position
+    uint32_t n, max_items;
+    uint64_t now, idle;
+    uint32_t* slot_of;       // [n] by sorted position of a run head: its slot (kNone: table full -- cannot happen under the capacity rule)
+    uint32_t* slen;          // [n] ... and the stored length the run starts from (0 if idle)
+    uint32_t* kept;          // [n + 1] 1 = this request appends
+    uint32_t* headpos;       // [n] p for a run head, 0 otherwise; inclusive max scan -> run_start
+    uint32_t* kex;           // [n + 1] exclusive sum of kept
+    uint32_t* run_start;     // [n]
+    uint64_t* compact;       // [n] the kept clicks in sorted order
+    uint32_t* qlen;          // [n + 1] by REQUEST index
+    uint32_t* q_off;         // [n + 1]
+    uint64_t* items_flat;
+    uint32_t* err;
+};
+__device__ __forceinline__ bool consents(const BatchArgs& a, uint32_t req) { return a.consent == nullptr || a.consent[req] != 0; }
+
+__global__ void __launch_bounds__(kTPB) sess_keys_init(const uint64_t* __restrict__ lo, uint32_t n, uint64_t* __restrict__ key, uint32_t* __restrict__ idx) {
+    const uint32_t i = blockIdx.x * kTPB + threadIdx.x;
+    if (i < n) { key[i] = lo[i]; idx[i] = i; }
+}
+__global__ void __launch_bounds__(kTPB) sess_keys_gather(const uint64_t* __restrict__ src, const uint32_t* __restrict__ idx, uint32_t n, uint64_t* __restrict__ key) {
+    const uint32_t i = blockIdx.x * kTPB + threadIdx.x;
+    if (i < n) key[i] = src[idx[i]];
+}
+__global__ void __launch_bounds__(kTPB) sess_keys_consent(const uint8_t* __restrict__ consent, const uint32_t* __restrict__ idx, uint32_t n, uint64_t* __restrict__ key) {
+    const uint32_t i = blockIdx.x * kTPB + threadIdx.x;
+    if (i < n) key[i] = consent[idx[i]] ? 0ull : 1ull;
+}
+
+__global__ void __launch_bounds__(kTPB) sess_find(BatchArgs a) {
+    const uint32_t p = blockIdx.x * kTPB + threadIdx.x;
+    if (p > a.n) return;
+    if (p == a.n) { a.kept[p] = 0; return; }
+    const uint32_t req = a.order[p];
+    if (!consents(a, req)) { a.kept[p] = 0; a.headpos[p] = 0; return; }
+    const uint64_t hi = a.key_hi[req], lo = a.key_lo[req], item = a.item[req];
+    bool head = p == 0;
+    uint64_t prev_item = 0;
+    if (!head) {
+        const uint32_t pr = a.order[p - 1];
+        head = !consents(a, pr) || a.key_hi[pr] != hi || a.key_lo[pr] != lo;
+        prev_item = a.item[pr];
+    }
+    if (!head) { a.kept[p] = item != prev_item; a.headpos[p] = 0; return; }
+    // find-or-insert: a slot claimed during this kernel belongs to another key
+    uint32_t h = key_hash(hi, lo) & a.t.mask, found = kNone, stored = 0;
+    uint64_t last = 0;
+    for (uint32_t probes = 0; probes <= a.t.mask; ++probes, h = (h + 1) & a.t.mask) {
+        SlotHead* s = slot_at(a.t, h);
+        uint32_t st = __hip_atomic_load(&s->state, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (st == kEmpty) {
+            st = atomicCAS(&s->state, kEmpty, kClaimed);
+            if (st == kEmpty) { s->key_hi = hi; s->key_lo = lo; s->epoch = 0; s->len = 0; found = h; break; }
+        }
+        if (st == kFull && s->key_hi == hi && s->key_lo == lo) {
+            found = h;
+            const uint32_t len = s->len;
+            if (len && !idle_or_old(a.now, s->epoch, a.idle)) { stored = len; last = slot_items(s)[len - 1]; }
+            break;
+        }
+    }
+    if (found == kNone) atomicOr(a.err, 1u);
+    a.slot_of[p] = found; a.slen[p] = stored; a.headpos[p] = p;
+    a.kept[p] = stored == 0 || last != item;
+}
+
+// the window of a consenting request at sorted position p: `len` items ending `a` kept clicks into the run, over (stored items ++ kept clicks)
+__global__ void __launch_bounds__(kTPB) sess_len(BatchArgs a) {
+    const uint32_t p = blockIdx.x * kTPB + threadIdx.x;
+    if (p > a.n) return;
+    if (p == a.n) { a.qlen[a.n] = 0; return; }
+    const uint32_t req = a.order[p];
+    if (!consents(a, req)) { a.qlen[req] = 1; return; }
+    const uint32_t s = a.run_start[p], S = a.slen[s], app = a.kex[p + 1] - a.kex[s];
+    a.qlen[req] = S >= a.max_items ? S : min(S + app, a.max_items);
+    if (a.kept[p]) a.compact[a.kex[p]] = a.item[req];
+}
+
+__global__ void __launch_bounds__(kTPB) sess_emit(BatchArgs a) {
+    const uint32_t p = blockIdx.x * kTPB + threadIdx.x;
+    if (p >= a.n) return;
+    const uint32_t req = a.order[p];
+    uint64_t* dst = a.items_flat + a.q_off[req];
+    if (!consents(a, req)) { dst[0] = a.item[req]; return; }
+    const uint32_t s = a.run_start[p], S = a.slen[s], app = a.kex[p + 1] - a.kex[s], len = a.q_off[req + 1] - a.q_off[req];
+    const uint32_t first = S + app - len;
+    const uint64_t* stored = S ? slot_items(slot_at(a.t, a.slot_of[s])) : nullptr;
+    const uint64_t* clicks = a.compact + a.kex[s];
+    for (uint32_t i = 0; i < len; ++i) { const uint32_t at = first + i; dst[i] = at < S ? stored[at] : clicks[at - S]; }
+}
+
+__global__ void __launch_bounds__(kTPB) sess_store(BatchArgs a) {
+    const uint32_t p = blockIdx.x * kTPB + threadIdx.x;
+    if (p >= a.n) return;
+    const uint32_t req = a.order[p];
+    if (!consents(a, req)) return;
+    if (p + 1 < a.n) {
+        const uint32_t nx = a.order[p + 1];
+        if (consents(a, nx) && a.key_hi[nx] == a.key_hi[req] && a.key_lo[nx] == a.key_lo[req]) return;   // not the run's last request
+    }
+    const uint32_t slot = a.slot_of[a.run_start[p]];
+    if (slot == kNone) return;
+    SlotHead* s = slot_at(a.t, slot);
+    const uint32_t off = a.q_off[req], len = a.q_off[req + 1] - off;
+    uint64_t* it = slot_items(s);
+    for (uint32_t i = 0; i < len; ++i) it[i] = a.items_flat[off + i];
+    s->len = len; s->epoch = a.now; s->state = kFull;
+}
+
+// a NULL store: every request's session is its item
+__global__ void __launch_bounds__(kTPB) sess_iota(uint32_t n, uint32_t* q_off) {
+    const uint32_t i = blockIdx.x * kTPB + threadIdx.x;
+    if (i <= n) q_off[i] = i;
+}
+
+// ---- one key, from the host ----
+// out[0] = stored length (~0: unknown key), out[1] = epoch, out[2..] = items
+__global__ void sess_get_one(Table t, uint64_t hi, uint64_t lo, uint64_t* out) {
+    out[0] = ~0ull;
+    uint32_t h = key_hash(hi, lo) & t.mask;
+    for (uint32_t probes = 0; probes <= t.mask; ++probes, h = (h + 1) & t.mask) {
+        SlotHead* s = slot_at(t, h);
+        if (s->state == kEmpty) return;
+        if (s->key_hi == hi && s->key_lo == lo) {
+            out[0] = s->len; out[1] = s->epoch;
+            for (uint32_t i = 0; i < s->len; ++i) out[2 + i] = slot_items(s)[i];
+            return;
+        }
+    }
+}
+// io[0] = n, io[1..] = items in; io[0] <- 1 if the key is new, 0 if it was there, 2 if the table is full
+__global__ void sess_put_one(Table t, uint64_t hi, uint64_t lo, uint64_t now, uint64_t* io) {
+    const uint32_t n = (uint32_t)io[0];
+    uint32_t h = key_hash(hi, lo) & t.mask;
+    for (uint32_t probes = 0; probes <= t.mask; ++probes, h = (h + 1) & t.mask) {
+        SlotHead* s = slot_at(t, h);
+        const bool empty = s->state == kEmpty;
+        if (empty || (s->key_hi == hi && s->key_lo == lo)) {
+            s->key_hi = hi; s->key_lo = lo; s->epoch = now; s->len = n; s->state = kFull;
+            for (uint32_t i = 0; i < n; ++i) slot_items(s)[i] = io[1 + i];
+            io[0] = empty ? 1 : 0;
+            return;
+        }
+    }
+    io[0] = 2;
+}
+
+// counters[0] = occupied slots, [1] = entries a sweep at `now` keeps
+__global__ void __launch_bounds__(kTPB) sess_count(Table t, uint64_t now, uint64_t ttl, unsigned long long* counters) {
+    const uint32_t i = blockIdx.x * kTPB + threadIdx.x;
+    bool occ = false, live = false;
+    if (i <= t.mask) { const SlotHead* s = slot_at(t, i); occ = s->state != kEmpty; live = occ && !idle_or_old(now, s->epoch, ttl); }
+    const unsigned long long mo = __ballot(occ), ml = __ballot(live);
+    if ((threadIdx.x & 63) == 0) { if (mo) atomicAdd(&counters[0], (unsigned long long)__popcll(mo)); if (ml) atomicAdd(&counters[1], (unsigned long long)__popcll(ml)); }
+}
+// the entries a sweep keeps, into the cleared table `to` (every key once: a claimed slot is another key's)
+__global__ void __launch_bounds__(kTPB) sess_rebuild(Table from, Table to, uint64_t now, uint64_t ttl) {
+    const uint32_t i = blockIdx.x * kTPB + threadIdx.x;
+    if (i > from.mask) return;
+    const SlotHead* s = slot_at(from, i);
+    if (s->state == kEmpty || idle_or_old(now, s->epoch, ttl)) return;
+    uint32_t h = key_hash(s->key_hi, s->key_lo) & to.mask;
+    for (uint32_t probes = 0; probes <= to.mask; ++probes, h = (h + 1) & to.mask) {
+        SlotHead* d = slot_at(to, h);
+        if (atomicCAS(&d->state, kEmpty, kFull) != kEmpty) continue;
+        d->key_hi = s->key_hi; d->key_lo = s->key_lo; d->epoch = s->epoch; d->len = s->len;
+        for (uint32_t j = 0; j < s->len; ++j) slot_items(d)[j] = slot_items(const_cast<SlotHead*>(s))[j];
+        return;
+    }
+}
+
+uint64_t wall_secs() { return (uint64_t)std::chrono::duration_cast<std::chrono::seconds>(std::chrono::system_clock::now().time_since_epoch()).count(); }
+size_t align256(size_t b) { return (b + 255) / 256 * 256; }
+dim3 grid_for(size_t n) { return dim3((unsigned)((n + kTPB - 1) / kTPB)); }
+}  // namespace
+
+}  // namespace srn
+
+using namespace srn;
+
+struct srn_device_sessions {
+    int device = 0;
+    uint64_t capacity = 0, n_slots = 0, items_cap = 0, ttl = 0, idle = 0;
+    uint32_t stride = 0;
+    char* table[2] = {nullptr, nullptr}; int cur = 0;      // a sweep rebuilds into the other one
+    std::mutex mu;                                          // covers the enqueue of a call and everything below
+    hipEvent_t last = nullptr;                              // end of the most recent call, whatever stream it ran on
+    hipStream_t own = nullptr;                              // get / update / sweep and the host-pointer entry point
+    uint64_t bound = 0, sweeps = 0, refused = 0;            // bound: upper bound of the occupied slots
+    uint32_t len_bound = 1;                                 // upper bound of the stored session lengths (predict's max_len_hint)
+    char* ws = nullptr; size_t ws_bytes = 0;                // per-batch scratch, grows with the largest n seen
+    char* stage = nullptr; size_t stage_bytes = 0;          // the host-pointer entry point's device copies
+    std::mutex stage_mu;
+    char* small = nullptr;                                  // err word | counters | one session in / out
+    // the most recent batch (debug accessors, timing)
+    const uint64_t* last_items = nullptr; const uint32_t* last_qoff = nullptr; size_t last_n = 0, last_hint = 0;
+    bool timing = false, last_timed = false; hipEvent_t tev[3] = {nullptr, nullptr, nullptr};
+    Table tab() const { return Table{table[cur], (uint32_t)(n_slots - 1), stride}; }
+    uint32_t* err() const { return (uint32_t*)small; }
+    unsigned long long* counters() const { return (unsigned long long*)(small + 64); }
+    uint64_t* one() const { return (uint64_t*)(small + 128); }
+};
+
+namespace srn {
+
+void dsess_free(srn_device_sessions* s) {
+    if (!s) return;
+    (void)hipSetDevice(s->device);
+    if (s->last) { (void)hipEventSynchronize(s->last); (void)hipEventDestroy(s->last); }
+    for (hipEvent_t e : s->tev) if (e) (void)hipEventDestroy(e);
+    if (s->own) { (void)hipStreamSynchronize(s->own); (void)hipStreamDestroy(s->own); }
+    for (void* p : {(void*)s->table[0], (void*)s->table[1], (void*)s->ws, (void*)s->stage, (void*)s->small}) if (p) (void)hipFree(p);
+    delete s;
+}
+
+int dsess_create(int device, size_t capacity, size_t items_cap, uint64_t ttl_secs, uint64_t idle_secs, srn_device_sessions** out) {
+    if (!out) return fail(SRN_EINVAL, "srn_device_sessions_create: null output");
+    *out = nullptr;
+    if (capacity == 0) return fail(SRN_EINVAL, "srn_device_sessions_create: capacity must be > 0");
+    if (capacity > (1ull << 30)) return fail(SRN_ERANGE, "srn_device_sessions_create: capacity above 2^30 sessions");
+    if (items_cap == 0) return fail(SRN_EINVAL, "srn_device_sessions_create: items_cap must be > 0");
+    if (items_cap > SRN_MAX_SESSION_LEN) return fail(SRN_ERANGE, "srn_device_sessions_create: items_cap above SRN_MAX_SESSION_LEN");
+    const uint64_t ttl = ttl_secs ? ttl_secs : 30 * 60, idle = idle_secs ? idle_secs : 20 * 60;   // srn_session_store_create's defaults
+    if (ttl < idle) return fail(SRN_EINVAL, "srn_device_sessions_create: ttl_secs below idle_secs (a swept session could still have been read)");
+    int n_dev = 0;
+    if (device < 0 || hipGetDeviceCount(&n_dev) != hipSuccess || device >= n_dev) return fail(SRN_ENODEV, "srn_device_sessions_create: no such GPU");
+    HIP_TRY(hipSetDevice(device));
+    srn_device_sessions* s = new srn_device_sessions();
+    struct Guard { srn_device_sessions*& s; ~Guard() { if (s) dsess_free(s); } } guard{s};
+    s->device = device; s->capacity = capacity; s->items_cap = items_cap; s->ttl = ttl; s->idle = idle;
+    s->n_slots = 2; while (s->n_slots < 2 * (uint64_t)capacity) s->n_slots <<= 1;
+    s->stride = (uint32_t)((kSlotHead + 8 * items_cap + 127) / 128 * 128);
+    const size_t bytes = (size_t)s->n_slots * s->stride;
+    for (int i = 0; i < 2; ++i)
+        if (hipMalloc((void**)&s->table[i], bytes) != hipSuccess) { (void)hipGetLastError(); return fail(SRN_ENOMEM, "srn_device_sessions_create: no device memory for the table"); }
+    HIP_TRY(hipMalloc((void**)&s->small, 128 + 8 * (2 + SRN_MAX_SESSION_LEN + 1)));
+    HIP_TRY(hipStreamCreateWithFlags(&s->own, hipStreamNonBlocking));
+    HIP_TRY(hipEventCreateWithFlags(&s->last, hipEventDisableTiming));
+    for (hipEvent_t& e : s->tev) HIP_TRY(hipEventCreate(&e));
+    HIP_TRY(hipMemsetAsync(s->table[0], 0, bytes, s->own));
+    HIP_TRY(hipMemsetAsync(s->small, 0, 128, s->own));
+    HIP_TRY(hipStreamSynchronize(s->own));
+    *out = s; s = nullptr;
+    return SRN_OK;
+}
+
+namespace {
+// behind everything enqueued on the store so far, on its own stream (mu held)
+int own_after_last(srn_device_sessions* s) { HIP_TRY(hipSetDevice(s->device)); HIP_TRY(hipStreamWaitEvent(s->own, s->last, 0)); return SRN_OK; }
+
+int rebuild(srn_device_sessions* s, uint64_t now) {   // (own stream, mu held)
+    const Table from = s->tab(); Table to = from; to.base = s->table[s->cur ^ 1];
+    HIP_TRY(hipMemsetAsync(to.base, 0, (size_t)s->n_slots * s->stride, s->own));
+    sess_rebuild<<<grid_for(s->n_slots), kTPB, 0, s->own>>>(from, to, now, s->ttl);
+    HIP_TRY(hipGetLastError());
+    s->cur ^= 1; ++s->sweeps;
+    return SRN_OK;
+}
+int count(srn_device_sessions* s, uint64_t now, uint64_t* occupied, uint64_t* live) {   // blocks (own stream, mu held)
+    HIP_TRY(hipMemsetAsync(s->counters(), 0, 16, s->own));
+    sess_count<<<grid_for(s->n_slots), kTPB, 0, s->own>>>(s->tab(), now, s->ttl, s->counters());
+    HIP_TRY(hipGetLastError());
+    unsigned long long c[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(c, s->counters(), 16, hipMemcpyDeviceToHost, s->own));
+    HIP_TRY(hipStreamSynchronize(s->own));
+    *occupied = c[0]; *live = c[1];
+    return SRN_OK;
+}
+// The capacity rule (mu held): room for n more keys, or SRN_ENOMEM with the table as it was.  Only when the host's bound does not fit does anything wait for the device:
+// the exact counts replace the bound, and entries older than the TTL are dropped (a rebuild) if that makes the room.
+int make_room(srn_device_sessions* s, uint64_t n, uint64_t now) {
+    if (s->bound + n <= s->capacity) return SRN_OK;
+    int rc = own_after_last(s); if (rc) return rc;
+    uint64_t occupied = 0, live = 0;
+    if ((rc = count(s, now, &occupied, &live))) return rc;
+    s->bound = occupied;
+    if (occupied + n <= s->capacity) return SRN_OK;
+    if (live + n > s->capacity) { ++s->refused; return fail(SRN_ENOMEM, "device session store: the batch does not fit the store's capacity (live sessions + batch > capacity)"); }
+    if ((rc = rebuild(s, now))) return rc;
+    HIP_TRY(hipStreamSynchronize(s->own));
+    s->bound = live;
+    return SRN_OK;
+}
+}  // namespace
+
+int dsess_get(srn_device_sessions* s, uint64_t hi, uint64_t lo, uint64_t now_secs, uint64_t* out_items, size_t cap, size_t* out_n) {
+    if (!s || !out_n || (cap && !out_items)) return fail(SRN_EINVAL, "srn_device_sessions_get: null argument");
+    const uint64_t now = now_secs ? now_secs : wall_secs();
+    std::lock_guard<std::mutex> g(s->mu);
+    int rc = own_after_last(s); if (rc) return rc;
+    *out_n = 0;
+    sess_get_one<<<1, 1, 0, s->own>>>(s->tab(), hi, lo, s->one());
+    HIP_TRY(hipGetLastError());
+    std::vector<uint64_t> h(2 + s->items_cap);
+    HIP_TRY(hipMemcpyAsync(h.data(), s->one(), h.size() * 8, hipMemcpyDeviceToHost, s->own));
+    HIP_TRY(hipStreamSynchronize(s->own));
+    if (h[0] == ~0ull || idle_or_old(now, h[1], s->idle)) return SRN_OK;
+    if (h[0] > cap) return fail(SRN_ERANGE, "srn_device_sessions_get: output buffer too small");
+    std::memcpy(out_items, h.data() + 2, h[0] * 8);
+    *out_n = (size_t)h[0];
+    return SRN_OK;
+}
+
+int dsess_update(srn_device_sessions* s, uint64_t hi, uint64_t lo, uint64_t now_secs, const uint64_t* items, size_t n) {
+    if (!s || (n && !items)) return fail(SRN_EINVAL, "srn_device_sessions_update: null argument");
+    if (n > s->items_cap) return fail(SRN_ERANGE, "srn_device_sessions_update: session longer than the store's items_cap");
+    const uint64_t now = now_secs ? now_secs : wall_secs();
+    std::lock_guard<std::mutex> g(s->mu);
+    int rc = make_room(s, 1, now); if (rc) return rc;
+    if ((rc = own_after_last(s))) return rc;
+    std::vector<uint64_t> h(1 + n); h[0] = n;
+    if (n) std::memcpy(h.data() + 1, items, n * 8);
+    HIP_TRY(hipMemcpyAsync(s->one(), h.data(), h.size() * 8, hipMemcpyHostToDevice, s->own));
+    sess_put_one<<<1, 1, 0, s->own>>>(s->tab(), hi, lo, now, s->one());
+    HIP_TRY(hipGetLastError());
+    uint64_t res = 0;
+    HIP_TRY(hipMemcpyAsync(&res, s->one(), 8, hipMemcpyDeviceToHost, s->own));
+    HIP_TRY(hipStreamSynchronize(s->own));
+    if (res == 2) return fail(SRN_ENOMEM, "srn_device_sessions_update: the table is full");
+    s->bound += res;
+    s->len_bound = std::max<uint32_t>(s->len_bound, (uint32_t)n);
+    return SRN_OK;
+}
+
+int dsess_sweep(srn_device_sessions* s, uint64_t now_secs, uint64_t* n_live) {
+    if (!s) return fail(SRN_EINVAL, "srn_device_sessions_sweep: null store");
+    const uint64_t now = now_secs ? now_secs : wall_secs();
+    std::lock_guard<std::mutex> g(s->mu);
+    int rc = own_after_last(s); if (rc) return rc;
+    if ((rc = rebuild(s, now))) return rc;
+    uint64_t occupied = 0, live = 0;
+    if ((rc = count(s, now, &occupied, &live))) return rc;
+    s->bound = occupied;
+    if (n_live) *n_live = occupied;
+    uint32_t err = 0;
+    HIP_TRY(hipMemcpy(&err, s->err(), 4, hipMemcpyDeviceToHost));
+    if (err) return fail(SRN_ESTATE, "device session store: a batch found the table full (the capacity rule was violated)");
+    return SRN_OK;
+}
+
+int dsess_stats(srn_device_sessions* s, srn_device_sessions_stats_t* out) {
+    if (!s || !out) return fail(SRN_EINVAL, "srn_device_sessions_stats: null argument");
+    std::lock_guard<std::mutex> g(s->mu);
+    *out = srn_device_sessions_stats_t{s->capacity, s->n_slots, s->items_cap, s->stride, s->bound, s->sweeps, s->refused, s->ttl, s->idle, s->len_bound};
+    return SRN_OK;
+}
+
+int dsess_timing(srn_device_sessions* s, int enable) {
+    if (!s) return fail(SRN_EINVAL, "srn_device_sessions_timing: null store");
+    std::lock_guard<std::mutex> g(s->mu);
+    s->timing = enable != 0;
+    return SRN_OK;
+}
+int dsess_last_ms(srn_device_sessions* s, double* ms_store, double* ms_predict) {
+    if (!s) return fail(SRN_EINVAL, "srn_device_sessions_last_ms: null store");
+    std::lock_guard<std::mutex> g(s->mu);
+    if (!s->last_timed) return fail(SRN_EINVAL, "srn_device_sessions_last_ms: the last batch was not timed (srn_device_sessions_timing)");
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipEventSynchronize(s->tev[2]));
+    float a = 0, b = 0;
+    HIP_TRY(hipEventElapsedTime(&a, s->tev[0], s->tev[1]));
+    HIP_TRY(hipEventElapsedTime(&b, s->tev[1], s->tev[2]));
+    if (ms_store) *ms_store = a;
+    if (ms_predict) *ms_predict = b;
+    return SRN_OK;
+}
+
+int dsess_last_csr(srn_device_sessions* s, const void** d_items, const void** d_qoff, size_t* n, size_t* max_len, uint64_t* h_items, size_t cap, uint32_t* h_qoff) {
+    if (!s) return fail(SRN_EINVAL, "null store");
+    std::lock_guard<std::mutex> g(s->mu);
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipEventSynchronize(s->last));
+    if (d_items) *d_items = s->last_items;
+    if (d_qoff) *d_qoff = s->last_qoff;
+    if (n) *n = s->last_n;
+    if (max_len) *max_len = s->last_hint;
+    if (h_qoff && s->last_n) {
+        HIP_TRY(hipMemcpy(h_qoff, s->last_qoff, (s->last_n + 1) * 4, hipMemcpyDeviceToHost));
+        const size_t total = h_qoff[s->last_n];
+        if (h_items) {
+            if (total > cap) return fail(SRN_ERANGE, "no room for the emitted sessions");
+            HIP_TRY(hipMemcpy(h_items, s->last_items, total * 8, hipMemcpyDeviceToHost));
+        }
+    }
+    return SRN_OK;
+}
+
+// a NULL store (no request consents): the sessions are the items themselves.  Not the serving path: it allocates and blocks.
+static int recommend_no_store(const srn_index* idx, const uint64_t* d_item, const uint8_t* d_consent, size_t n, LaunchParams p, hipStream_t st) {
+    if (!d_consent) return fail(SRN_EINVAL, "srn_recommend_batch: user consent needs a session store");
+    HIP_TRY(hipSetDevice(idx->device));
+    std::vector<uint8_t> c(n);
+    HIP_TRY(hipMemcpyAsync(c.data(), d_consent, n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (std::any_of(c.begin(), c.end(), [](uint8_t x) { return x != 0; })) return fail(SRN_EINVAL, "srn_recommend_batch: user consent needs a session store");
+    uint32_t* q_off = nullptr;
+    HIP_TRY(hipMalloc((void**)&q_off, (n + 1) * 4));
+    sess_iota<<<grid_for(n + 1), kTPB, 0, st>>>((uint32_t)n, q_off);
+    p.max_len = 1; p.items_flat = d_item; p.q_off = q_off;
+    int rc = hipGetLastError() == hipSuccess ? device_predict(idx->dev, idx->flat, p, true, st, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr)
+                                             : fail(SRN_EHIP, "sess_iota launch failed");
+    (void)hipStreamSynchronize(st);
+    (void)hipFree(q_off);
+    return rc;
+}
+
+// arguments already checked by the C ABI glue (predict's own checks, null buffers, n > 0)
+int dsess_recommend_device(const srn_index* idx, srn_device_sessions* s, const uint64_t* d_hi, const uint64_t* d_lo, const uint64_t* d_item, const uint8_t* d_consent,
+                           size_t n, uint64_t now_secs, size_t max_items, size_t k, size_t m, size_t how_many, unsigned flags,
+                           uint64_t* d_ids, double* d_scores, uint32_t* d_counts, void* stream) {
+    if (max_items == 0) return fail(SRN_EINVAL, "srn_recommend_batch: max_items_in_session must be > 0");
+    if (n > kMaxBatch) return fail(SRN_ERANGE, "srn_recommend_batch: more than 2^24 requests in one call");
+    hipStream_t st = (hipStream_t)stream;
+    LaunchParams p{};
+    p.nq = (uint32_t)n; p.k = (uint32_t)k; p.m = (uint32_t)m; p.how_many = (uint32_t)how_many; p.flags = flags;
+    p.out_ids = d_ids; p.out_scores = d_scores; p.out_counts = d_counts;
+    if (!s) {
+        if (max_items > SRN_MAX_SESSION_LEN) return fail(SRN_ERANGE, "srn_recommend_batch: max_items_in_session above SRN_MAX_SESSION_LEN");
+        return recommend_no_store(idx, d_item, d_consent, n, p, st);
+    }
+    if (max_items > s->items_cap) return fail(SRN_ERANGE, "srn_recommend_batch: max_items_in_session above the store's items_cap");
+    if (s->device != idx->device) return fail(SRN_EINVAL, "srn_recommend_batch: the store and the index are on different devices");
+    const uint64_t now = now_secs ? now_secs : wall_secs();
+    std::lock_guard<std::mutex> g(s->mu);
+    int rc = make_room(s, n, now); if (rc) return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    const uint32_t hint = std::max<uint32_t>(s->len_bound, (uint32_t)max_items);
+    // scratch: sort keys and indices (double-buffered), the per-position and per-request words, the kept clicks, the CSR batch, rocPRIM's temporary storage
+    size_t tmp = 0, t1 = 0;
+    HIP_TRY(rocprim::radix_sort_pairs(nullptr, t1, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, n, 0, 64, st)); tmp = std::max(tmp, t1);
+    HIP_TRY(rocprim::radix_sort_pairs(nullptr, t1, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, n, 0, 1, st)); tmp = std::max(tmp, t1);
+    HIP_TRY(rocprim::exclusive_scan(nullptr, t1, (uint32_t*)nullptr, (uint32_t*)nullptr, 0u, n + 1, rocprim::plus<uint32_t>(), st)); tmp = std::max(tmp, t1);
+    HIP_TRY(rocprim::inclusive_scan(nullptr, t1, (uint32_t*)nullptr, (uint32_t*)nullptr, n, rocprim::maximum<uint32_t>(), st)); tmp = std::max(tmp, t1);
+    const size_t w = align256((n + 1) * 4);
+    const size_t o_keyA = 0, o_keyB = o_keyA + align256(n * 8), o_idxA = o_keyB + align256(n * 8), o_idxB = o_idxA + w, o_slot = o_idxB + w, o_slen = o_slot + w,
+                 o_kept = o_slen + w, o_head = o_kept + w, o_kex = o_head + w, o_run = o_kex + w, o_qlen = o_run + w, o_qoff = o_qlen + w, o_comp = o_qoff + w,
+                 o_flat = o_comp + align256(n * 8), o_tmp = o_flat + align256(n * (size_t)hint * 8), bytes = o_tmp + align256(tmp);
+    if (bytes > s->ws_bytes) {   // (the previous call may still read the scratch: wait for it before it is freed)
+        HIP_TRY(hipEventSynchronize(s->last));
+        if ((rc = ensure(&s->ws, &s->ws_bytes, bytes))) return rc;
+    }
+    HIP_TRY(hipStreamWaitEvent(st, s->last, 0));
+    const bool timed = s->timing;
+    if (timed) HIP_TRY(hipEventRecord(s->tev[0], st));
+    char* b = s->ws;
+    uint64_t* keyA = (uint64_t*)(b + o_keyA); uint64_t* keyB = (uint64_t*)(b + o_keyB); uint32_t* idxA = (uint32_t*)(b + o_idxA); uint32_t* idxB = (uint32_t*)(b + o_idxB);
+    const dim3 gn = grid_for(n), gn1 = grid_for(n + 1);
+    const uint32_t n32 = (uint32_t)n;
+    // stable LSD passes: key_lo, key_hi, then (where some request may not consent) the consent bit -- consenting requests first, each visitor's in request order
+    sess_keys_init<<<gn, kTPB, 0, st>>>(d_lo, n32, keyA, idxA);
+    t1 = tmp; HIP_TRY(rocprim::radix_sort_pairs(b + o_tmp, t1, keyA, keyB, idxA, idxB, n, 0, 64, st));
+    sess_keys_gather<<<gn, kTPB, 0, st>>>(d_hi, idxB, n32, keyA);
+    t1 = tmp; HIP_TRY(rocprim::radix_sort_pairs(b + o_tmp, t1, keyA, keyB, idxB, idxA, n, 0, 64, st));
+    const uint32_t* order = idxA;
+    if (d_consent) {
+        sess_keys_consent<<<gn, kTPB, 0, st>>>(d_consent, idxA, n32, keyA);
+        t1 = tmp; HIP_TRY(rocprim::radix_sort_pairs(b + o_tmp, t1, keyA, keyB, idxA, idxB, n, 0, 1, st));
+        order = idxB;
+    }
+    BatchArgs a{};
+    a.t = s->tab(); a.key_hi = d_hi; a.key_lo = d_lo; a.item = d_item; a.consent = d_consent; a.order = order; a.n = n32; a.max_items = (uint32_t)max_items;
+    a.now = now; a.idle = s->idle;
+    a.slot_of = (uint32_t*)(b + o_slot); a.slen = (uint32_t*)(b + o_slen); a.kept = (uint32_t*)(b + o_kept); a.headpos = (uint32_t*)(b + o_head);
+    a.kex = (uint32_t*)(b + o_kex); a.run_start = (uint32_t*)(b + o_run); a.qlen = (uint32_t*)(b + o_qlen); a.q_off = (uint32_t*)(b + o_qoff);
+    a.compact = (uint64_t*)(b + o_comp); a.items_flat = (uint64_t*)(b + o_flat); a.err = s->err();
+    sess_find<<<gn1, kTPB, 0, st>>>(a);
+    t1 = tmp; HIP_TRY(rocprim::exclusive_scan(b + o_tmp, t1, a.kept, a.kex, 0u, n + 1, rocprim::plus<uint32_t>(), st));
+    t1 = tmp; HIP_TRY(rocprim::inclusive_scan(b + o_tmp, t1, a.headpos, a.run_start, n, rocprim::maximum<uint32_t>(), st));
+    sess_len<<<gn1, kTPB, 0, st>>>(a);
+    t1 = tmp; HIP_TRY(rocprim::exclusive_scan(b + o_tmp, t1, a.qlen, a.q_off, 0u, n + 1, rocprim::plus<uint32_t>(), st));
+    sess_emit<<<gn, kTPB, 0, st>>>(a);
+    sess_store<<<gn, kTPB, 0, st>>>(a);
+    HIP_TRY(hipGetLastError());
+    // from here on the store has changed: whatever happens below, the next call is ordered behind this one
+    s->bound += n;
+    s->len_bound = hint;
+    s->last_items = a.items_flat; s->last_qoff = a.q_off; s->last_n = n; s->last_hint = hint;
+    if (timed) (void)hipEventRecord(s->tev[1], st);
+    p.max_len = hint; p.items_flat = a.items_flat; p.q_off = a.q_off;
+    rc = device_predict(idx->dev, idx->flat, p, true, st, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+    (void)hipSetDevice(s->device);
+    if (timed) (void)hipEventRecord(s->tev[2], st);
+    s->last_timed = timed;
+    (void)hipEventRecord(s->last, st);
+    return rc;
+}
+
+int dsess_recommend_host(const srn_index* idx, srn_device_sessions* s, const uint64_t* hi, const uint64_t* lo, const uint64_t* item, const uint8_t* consent,
+                         size_t n, uint64_t now_secs, size_t max_items, size_t k, size_t m, size_t how_many, unsigned flags,
+                         uint64_t* ids, double* scores, uint32_t* counts) {
+    if (!s && (!consent || std::any_of(consent, consent + n, [](uint8_t x) { return x != 0; }))) return fail(SRN_EINVAL, "srn_recommend_batch: user consent needs a session store");
+    if (n > kMaxBatch) return fail(SRN_ERANGE, "srn_recommend_batch: more than 2^24 requests in one call");
+    HIP_TRY(hipSetDevice(idx->device));
+    // device copies: the store's staging, or (no store) a buffer of this call's own
+    const size_t rows = n * how_many * 8;
+    const size_t o_hi = 0, o_lo = o_hi + align256(n * 8), o_item = o_lo + align256(n * 8), o_con = o_item + align256(n * 8), o_ids = o_con + align256(n),
+                 o_sc = o_ids + align256(rows), o_cnt = o_sc + align256(rows), bytes = o_cnt + align256(n * 4);
+    char* own_buf = nullptr; hipStream_t st = nullptr;
+    std::unique_lock<std::mutex> sl;
+    if (s) {
+        sl = std::unique_lock<std::mutex>(s->stage_mu);
+        if (s->device != idx->device) return fail(SRN_EINVAL, "srn_recommend_batch: the store and the index are on different devices");
+        int rc = ensure(&s->stage, &s->stage_bytes, bytes); if (rc) return rc;
+        st = s->own;
+    } else {
+        HIP_TRY(hipMalloc((void**)&own_buf, bytes));
+    }
+    char* b = s ? s->stage : own_buf;
+    auto run = [&]() -> int {
+        HIP_TRY(hipMemcpyAsync(b + o_hi, hi, n * 8, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(b + o_lo, lo, n * 8, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(b + o_item, item, n * 8, hipMemcpyHostToDevice, st));
+        if (consent) HIP_TRY(hipMemcpyAsync(b + o_con, consent, n, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemsetAsync(b + o_ids, 0, o_cnt - o_ids, st));   // (entries beyond a row's count read as zero, as in buffers a caller cleared)
+        int rc = dsess_recommend_device(idx, s, (const uint64_t*)(b + o_hi), (const uint64_t*)(b + o_lo), (const uint64_t*)(b + o_item), consent ? (const uint8_t*)(b + o_con) : nullptr,
+                                        n, now_secs, max_items, k, m, how_many, flags, (uint64_t*)(b + o_ids), (double*)(b + o_sc), (uint32_t*)(b + o_cnt), st);
+        if (rc) { (void)hipStreamSynchronize(st); return rc; }
+        HIP_TRY(hipSetDevice(idx->device));
+        HIP_TRY(hipMemcpyAsync(ids, b + o_ids, rows, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(scores, b + o_sc, rows, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(counts, b + o_cnt, n * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        return SRN_OK;
+    };
+    const int rc = run();
+    if (own_buf) (void)hipFree(own_buf);
+    if (rc) return rc;
+    for (size_t q = 0; q < n; ++q)
+        if (counts[q] == 0xFFFFFFFFu) return fail(SRN_ERANGE, "a query exceeded the kernel's table limits");
+    return SRN_OK;
+}
+
+}  // namespace srn
