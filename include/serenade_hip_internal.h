@@ -26,6 +26,9 @@ int srn_debug_shard_group_times(const srn_shard_group_t* g, double* out_ms3);
 /* Measurement aid: how many queries of the last predict call the lean fast kernel listed for its MID instantiation (sessions of <= 10 items with 5..8 posting lists or
  * similarity numerators above 15: DESIGN.md section 4.1); srn_last_path_counts' `general` counts what reached the general kernel after both.  0 when the call had no such tier. */
 int srn_debug_last_mid_count(const srn_index_t* idx, uint32_t* out_listed);
+/* Measurement aid: how many queries of the last predict call were not served themselves but received the row of an earlier query of the SAME call with the same item
+ * sequence (batches of at least SRN_ORDER_MIN queries on the fast path).  0 when the call did not merge (small batch, SRN_NO_DEDUP, other paths). */
+int srn_debug_last_dedup_count(const srn_index_t* idx, uint32_t* out_merged);
 /* the persistent latency path: 100 MHz ticks of the last session the lean form's first resident workgroup served -- [0] waited for the doorbell, [1] doorbell -> prep record
  * written, [2] doorbell -> answer posted */
 int srn_debug_serve_stamps(const srn_index_t* idx, uint32_t* out4);

@@ -148,6 +148,7 @@ SYMBOLS = {
     "srn_debug_phase_cycles": (_i, [_vp, _i, _vp]),
     "srn_debug_reload_knobs": (None, []),
     "srn_debug_last_mid_count": (_i, [_vp, C.POINTER(C.c_uint32)]),
+    "srn_debug_last_dedup_count": (_i, [_vp, C.POINTER(C.c_uint32)]),
     "srn_debug_serve_stamps": (_i, [_vp, _vp]),
     "srn_debug_shard_nb_positions_stride": (C.c_uint32, [_sz, _sz]),
     "srn_debug_last_big_count": (_i, [_vp, C.POINTER(C.c_uint32)]),
@@ -213,7 +214,11 @@ def lib():
         _preload_hip_runtime()
         L = C.CDLL(path)
         for name, (res, args) in SYMBOLS.items():
-            fn = getattr(L, name)
+            fn = getattr(L, name, None)
+            if fn is None:
+                if os.environ.get("SRN_LIB_PATH"):   # (an older build loaded for an A/B run: a call of what it lacks raises AttributeError there)
+                    continue
+                raise ImportError("%s lacks %s: rebuild it (`python -c 'import __graft_entry__ as g; g.build()'`)" % (path, name))
             fn.restype, fn.argtypes = res, args
         _lib = L
     return _lib

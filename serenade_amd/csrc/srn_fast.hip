@@ -481,7 +481,8 @@ __global__ __launch_bounds__(512, TINY ? SRN_TINY_WAVES : BIG ? 4 : SRN_FAST_WAV
     const uint32_t qi_step = serving ? 0u : ordered ? gridDim.x >> 3 : gridDim.x;
     uint32_t serve_seq = 0u; bool serve_have = false; unsigned long long serve_t0 = 0ull, serve_c0 = 0ull;   // (wave 0) the number of the request being served; before the first one: the number the host left in done_seq at the launch
     if constexpr (TINY) { if (serving) serve_seq = __atomic_load_n(&(f.serve + blockIdx.x)->done_seq, __ATOMIC_RELAXED); }   // (the host writes done_seq only while no kernel is resident)
-    const uint32_t qi_end = ordered ? ord_count(p.nq, ox) : q_end;
+    // (the copies of an earlier query of the call sort to the end of the order and are not served: f.order_dups, srn_dedup.hip -- the grid is sized from p.nq, a workgroup with nothing left leaves at once)
+    const uint32_t qi_end = ordered ? ord_count(f.order_dups != nullptr ? p.nq - *f.order_dups : p.nq, ox) : q_end;
     for (uint32_t qi = ordered ? blockIdx.x >> 3 : (MODE == FM_FRONT ? f.q_base : 0u) + blockIdx.x; qi < qi_end; qi += qi_step) {
         if constexpr (TINY) {
             if (serving) {

@@ -122,9 +122,16 @@ struct FastParams {
     uint64_t tiny_items[8]; uint32_t tiny_len, host_seq;   // (the TINY launch) the session's items in the kernel arguments (tiny_len = 0: read p.items_flat), the call's number
     ServeCtl* serve;            // (the TINY launch) non-null: the persistent form -- grid of ONE workgroup that serves the sessions the host posts here until told to leave
     uint32_t* host_words;       // (the TINY launch) pinned words the kernel publishes the sequence's counters in: [1] handed to the general kernel, [2] listed for MID, [3] for MID's BIG form, [4] queries with > 63 entries, and last of all [5] = host_seq: the host may read the row
+    const uint32_t* order_dups; // (with `order`, or null) the number of queries at the END of the order that are copies of an earlier query of the call (srn_dedup.hip): the ordered loop stops in front of them
 };
 // the batch's order keys (written by the prep kernel) -> sorted (srn_build_gpu.hip: rocPRIM radix sort on the key bits); temp == nullptr: only *temp_bytes is set
 hipError_t sort_order_keys(hipStream_t st, const unsigned long long* in, unsigned long long* out, size_t n, void* temp, size_t* temp_bytes);
+// queries of one call with the same item sequence (srn_dedup.hip): groups on the device, the smallest query index of each serves, the others get its row at the end
+uint32_t dedup_slots(uint32_t nq);   // words of the hash table (and of its second array) for a batch of nq queries
+hipError_t launch_dedup_group(hipStream_t st, const uint64_t* items_flat, const uint32_t* q_off, uint32_t nq, uint32_t* slots, uint32_t* slot_min, uint32_t n_slots, uint32_t hash_bits,
+                              uint32_t* rep, unsigned long long* okeys, uint32_t* out_counts, uint32_t* n_dup);
+hipError_t launch_dedup_mark(hipStream_t st, uint32_t nq, const uint32_t* rep, uint32_t* out_counts);
+hipError_t launch_dedup_fill(hipStream_t st, uint32_t nq, const uint32_t* rep, uint64_t* out_ids, double* out_scores, uint32_t* out_counts, uint32_t how_many, const uint32_t* n_dup, uint32_t* host_word);
 
 // ---- the item-sharded index's own back end (srn_sback.hip, round 5): one WAVE per query over a shard's row fragments -------------------------------------------------
 // Geometry of a wave's accumulators (words): SB_H direct-mapped (the shard's most popular items; the top SB_REP_ITEMS * SB_REP of them are the replicated words of the

@@ -42,6 +42,8 @@ struct Knobs {
     int row_slots16 = -1;     // SRN_ROW_SLOTS = 16 | 64: the device row layout (-1 = by index kind: 64-byte slots unsharded, 16-byte fragment slots for item shards)
     int order_min = 131072;    // SRN_ORDER_MIN: batches of at least this many queries are served in the order of their most popular item, an eighth of the order per XCD (0 = never); the ordering
                               // pass is one radix sort of the batch's keys behind the prep kernel
+    bool no_dedup = false;     // SRN_NO_DEDUP: every query of an ordered batch is served, also the copies of an earlier query of the same call (srn_dedup.hip; A/B and the tests' reference)
+    int dedup_hash_bits = 0;   // SRN_DEDUP_HASH_BITS (tests only): the grouping pass's hash cut to this many bits -- unequal queries share hashes and the probe chains get long; 0 = all 32
     bool no_sback_second = false;   // SRN_NO_SBACK_SECOND (experiments): what the wave-per-query back end cannot hold goes straight to the general kernel (no fast-kernel back end over the list)
     bool no_sback = false;    // SRN_NO_SBACK: the shard group's back end through vmis_fast_kernel's FM_BACK instantiation (rounds 4) instead of the wave-per-query kernel of srn_sback.hip
     double xgmi_gbps = 76.8;       // SRN_XGMI_GBPS: what one xGMI link moves per direction (AUTO's input below)
@@ -70,6 +72,7 @@ struct Workspace {
     uint64_t calls = 0, untimed_calls = 0; uint32_t last_retry = 0, last_nq = 0;
     bool last_fast = false;      // the last call went through the fast kernel: h_retry[1] = what it handed to the general kernel (otherwise: all of last_nq)
     bool last_mid = false;       // ... and through its MID instantiation: h_retry[2] = the queries the lean instantiation listed for it
+    bool last_dedup = false;     // ... and merged the queries with equal sequences: h_retry[6] = how many were merged
     bool last_untimed = false;   // the last call took the latency path: no events were recorded for it
     // device scratch
     uint32_t* retry_list = nullptr; size_t retry_cap = 0; uint32_t* retry_cnt = nullptr;
@@ -78,6 +81,7 @@ struct Workspace {
     char* prep = nullptr; size_t prep_bytes = 0;     // per-query records of the prep kernel
     char* order = nullptr; size_t order_bytes = 0;   // the batch's order keys as the prep kernel wrote them | sorted | the sort's scratch
     char* sb_scr = nullptr; size_t sb_scr_bytes = 0; // the streaming back end's per-wave scratch
+    // (behind the sort's scratch in each order set, where the call merges equal queries: the merged count | rep[nq] | the grouping pass's hash table, DedupRoom in srn_runtime.hip)
     char* order2 = nullptr; size_t order2_bytes = 0; // ... of the second record set (SRN_FLAG_INPUTS_RESIDENT: call i + 1's prep kernel and sort run beside call i's kernels, which still read theirs)
     uint32_t* retry_list2 = nullptr; size_t retry_cap2 = 0; uint32_t* retry_cnt2 = nullptr;   // what the second LDS tier could not hold either
     uint32_t* slow_list = nullptr; size_t slow_cap = 0; uint32_t* slow_cnt = nullptr;          // what the fast kernel hands to the general one

@@ -46,6 +46,7 @@ static void knobs_read() {
     k.tiny_fast = env_int("SRN_TINY_FAST", k.tiny_fast, 0, 3);
     k.lanes = env_int("SRN_PREDICT_LANES", k.lanes, 0);
     k.order_min = env_int("SRN_ORDER_MIN", k.order_min, 0);
+    k.no_dedup = env_flag("SRN_NO_DEDUP"); k.dedup_hash_bits = env_int("SRN_DEDUP_HASH_BITS", 0, 0, 32);
     k.no_sback_second = env_flag("SRN_NO_SBACK_SECOND");
     k.no_sback = env_flag("SRN_NO_SBACK");
     const int stream = env_int("SRN_SBACK_STREAM", INT_MIN); k.sback_stream_mode = stream == INT_MIN ? -1 : stream != 0 ? 1 : 0;
@@ -436,12 +437,17 @@ static FastPlan fast_plan(const DeviceState* d, const FlatIndex& ix, const Launc
 
 // The serving order of a batch (FastParams::order): room for the keys the prep kernel writes, their sorted copy and the sort's scratch in ONE grow-only buffer; then the sort
 // itself, enqueued on the stream the prep kernel ran on.
-static int order_room(char** buf, size_t* have, uint32_t nq, unsigned long long** keys_in, unsigned long long** keys_out, void** temp, size_t* temp_bytes) {
+struct DedupRoom { uint32_t* n_dup = nullptr; uint32_t* rep = nullptr; uint32_t* slots = nullptr; uint32_t* slot_min = nullptr; uint32_t n_slots = 0; };
+static int order_room(char** buf, size_t* have, uint32_t nq, unsigned long long** keys_in, unsigned long long** keys_out, void** temp, size_t* temp_bytes, DedupRoom* dd = nullptr) {
     size_t tb = 0;
     if (sort_order_keys(nullptr, nullptr, nullptr, nq, nullptr, &tb) != hipSuccess) return fail(SRN_EHIP, "rocprim::radix_sort_keys (size query) failed");
-    const size_t kb = ((size_t)nq * 8 + 255) / 256 * 256;
-    int rc = ensure(buf, have, 2 * kb + tb + 256); if (rc) return rc;
+    const size_t kb = ((size_t)nq * 8 + 255) / 256 * 256, tbr = (tb + 255) / 256 * 256;
+    // (dd: the call merges its equal queries -- the merged count, rep[nq] and the hash table's two arrays belong to the order set, like the keys: a resident call groups on
+    //  the side stream while the previous call's kernels still read THEIR count and representatives)
+    const size_t rb = ((size_t)nq * 4 + 255) / 256 * 256, n_slots = dd ? dedup_slots(nq) : 0;
+    int rc = ensure(buf, have, 2 * kb + tbr + 256 + (dd ? 256 + rb + 2 * n_slots * 4 : 0)); if (rc) return rc;
     *keys_in = (unsigned long long*)*buf; *keys_out = (unsigned long long*)(*buf + kb); *temp = *buf + 2 * kb; *temp_bytes = tb;
+    if (dd) { char* b = *buf + 2 * kb + tbr + 256; dd->n_dup = (uint32_t*)b; dd->rep = (uint32_t*)(b + 256); dd->slots = (uint32_t*)(b + 256 + rb); dd->slot_min = dd->slots + n_slots; dd->n_slots = (uint32_t)n_slots; }
     return SRN_OK;
 }
 
@@ -588,7 +594,7 @@ static int device_predict_tiny(DeviceState* d, const FlatIndex& ix, Workspace* w
     if (*(volatile uint32_t*)(w->pin + o_rc) != 0) return 1;   // (rare: tables too small for some query)
     // what the timing / path-count APIs report after this call: its query count, how many of them the fast sequence handed to the general kernel (all of them where the
     // two-launch form ran), not timed (the stream is idle here: nothing of an earlier call is still writing the pinned words)
-    ++w->untimed_calls; w->last_nq = p.nq; w->last_retry = 0; w->last_fast = tiny_fast; w->last_mid = tiny_fast && plan.mid_tier; w->last_untimed = true;   // (`calls` indexes the event ring: timed calls only)
+    ++w->untimed_calls; w->last_nq = p.nq; w->last_retry = 0; w->last_fast = tiny_fast; w->last_mid = tiny_fast && plan.mid_tier; w->last_dedup = false; w->last_untimed = true;   // (`calls` indexes the event ring: timed calls only)
     const uint64_t* r_ids = (const uint64_t*)(w->pin + o_ids); const double* r_sc = (const double*)(w->pin + o_sc); const uint32_t* r_cnt = (const uint32_t*)(w->pin + o_cnt);
     for (uint32_t q = 0; q < p.nq; ++q) {
         const uint32_t n = r_cnt[q] == 0xFFFFFFFFu ? 0u : std::min<uint32_t>(r_cnt[q], p.how_many);
@@ -927,7 +933,10 @@ int device_predict(DeviceState* d, const FlatIndex& ix, const LaunchParams& p_in
     unsigned long long *okeys_in = nullptr, *okeys_out = nullptr; void* otemp = nullptr; size_t otemp_bytes = 0;
     // (one order per set of prep records: a resident call's prep kernel and sort run on the side stream while the previous call's kernels still read THEIR order)
     const bool order_set2 = resident && (w->resident_calls & 1u) != 0u;
-    if (ordered) { int rc = order_room(order_set2 ? &w->order2 : &w->order, order_set2 ? &w->order2_bytes : &w->order_bytes, p.nq, &okeys_in, &okeys_out, &otemp, &otemp_bytes); if (rc) return rc; }
+    // ... and, in that order, only the first of the call's queries with one and the same item sequence (srn_dedup.hip); the others get its row at the end
+    const bool dedup = ordered && !kn.no_dedup;
+    DedupRoom dd;
+    if (ordered) { int rc = order_room(order_set2 ? &w->order2 : &w->order, order_set2 ? &w->order2_bytes : &w->order_bytes, p.nq, &okeys_in, &okeys_out, &otemp, &otemp_bytes, dedup ? &dd : nullptr); if (rc) return rc; }
     if (reserve_only) return SRN_OK;   // (srn_index_reserve: the workspace is sized, nothing was enqueued)
     if (ext && ext->mode == 1) {
         // The shard group's neighbours pipeline, FRONT: find_neighbors alone for the queries [q_lo, nq) of the batch this rank fronts -- the fast kernel's front end against
@@ -962,12 +971,21 @@ int device_predict(DeviceState* d, const FlatIndex& ix, const LaunchParams& p_in
         if (!w->rec_used[par] && w->calls > 0) { HIP_TRY(hipEventRecord(w->ev_done[par], st)); w->rec_used[par] = true; }   // (earlier calls of this workspace that left no event: everything enqueued so far)
         if (w->rec_used[par]) HIP_TRY(hipStreamWaitEvent(w->side, w->ev_done[par], 0));
         HIP_TRY(launch_prep(w->side, di, p.items_flat, p.q_off, p.nq, p.m, p.max_len, rec, prep_stride, nullptr, nullptr, nullptr, 0, okeys_in));
+        if (dedup) {   // (the count word of a merged row is written on the caller's stream, below: the previous call's kernels may still be writing these very buffers)
+            HIP_TRY(hipMemsetAsync(dd.slots, 0xFF, (size_t)dd.n_slots * 8, w->side));
+            HIP_TRY(launch_dedup_group(w->side, p.items_flat, p.q_off, p.nq, dd.slots, dd.slot_min, dd.n_slots, (uint32_t)kn.dedup_hash_bits, dd.rep, okeys_in, nullptr, dd.n_dup));
+        }
         if (ordered) HIP_TRY(sort_order_keys(w->side, okeys_in, okeys_out, p.nq, otemp, &otemp_bytes));
         HIP_TRY(hipEventRecord(w->ev_prep[par], w->side));
         HIP_TRY(hipStreamWaitEvent(st, w->ev_prep[par], 0));
+        if (dedup) HIP_TRY(launch_dedup_mark(st, p.nq, dd.rep, p.out_counts));
         p.prep = rec; p.prep_stride = prep_stride;
     }
     else { HIP_TRY(launch_prep(st, di, p.items_flat, p.q_off, p.nq, p.m, p.max_len, w->prep, prep_stride, fast ? w->slow_cnt : nullptr, (may_overflow || dense) ? w->retry_cnt : nullptr, nullptr, 0, okeys_in));
+           if (dedup) {
+               HIP_TRY(hipMemsetAsync(dd.slots, 0xFF, (size_t)dd.n_slots * 8, st));
+               HIP_TRY(launch_dedup_group(st, p.items_flat, p.q_off, p.nq, dd.slots, dd.slot_min, dd.n_slots, (uint32_t)kn.dedup_hash_bits, dd.rep, okeys_in, p.out_counts, dd.n_dup));
+           }
            if (ordered) HIP_TRY(sort_order_keys(st, okeys_in, okeys_out, p.nq, otemp, &otemp_bytes));
            p.prep = w->prep; p.prep_stride = prep_stride; }
     if (timed) HIP_TRY(hipEventRecord(ev[3], st));
@@ -1002,6 +1020,7 @@ int device_predict(DeviceState* d, const FlatIndex& ix, const LaunchParams& p_in
         const bool back = ext && ext->mode == 2;   // neighbour lists from the exchange buffer (any rank's front end), this shard's rows
         if (back) { fp.xchg = ext->xchg; fp.xchg_stride = ext->xchg_stride; }
         fp.order = ordered ? okeys_out : back ? ext->order : nullptr;
+        fp.order_dups = dedup ? dd.n_dup : nullptr;
         const uint32_t grid_fo = fp.order ? std::max<uint32_t>(8u, grid_f / 8u * 8u) : grid_f;   // (an ordered launch walks an eighth of the order per XCD: the grid is a multiple of 8)
         if (back && d->sback.frag8 && !kn.no_sback && p.max_len <= 8) {
             // the item shard's own back end (srn_sback.hip): one wave per query, 12 per CU; a persistent grid of a few waves per resident slot
@@ -1049,6 +1068,9 @@ int device_predict(DeviceState* d, const FlatIndex& ix, const LaunchParams& p_in
     } else
         HIP_TRY(launch_predict(geo.masks, slot64, false, 0, dim3(grid), lds, st, di, p, c, nullptr, nullptr, w->retry_list, w->retry_cnt, nullptr, 0, spill, ShardIO{}));
     if (!fast && timed) HIP_TRY(hipEventRecord(ev[4], st));
+    // the merged queries' rows: behind every kernel that can write a representative's row -- the global-table pass included, where the launch has one
+    const bool fill_late = dedup && (may_overflow || dense);
+    if (dedup && !fill_late) HIP_TRY(launch_dedup_fill(st, p.nq, dd.rep, p.out_ids, p.out_scores, p.out_counts, p.how_many, dd.n_dup, w->h_retry_dev + 6));
     if (timed) HIP_TRY(hipEventRecord(ev[1], st));
     if (fork_retry) HIP_TRY(hipStreamWaitEvent(st, w->ev_join, 0));
     else if (may_overflow || dense) {
@@ -1058,10 +1080,11 @@ int device_predict(DeviceState* d, const FlatIndex& ix, const LaunchParams& p_in
         if (!fast) HIP_TRY(hipMemcpyAsync(w->h_retry, final_cnt, 4, hipMemcpyDeviceToHost, st));   // (fast: vmis_finish_big_kernel wrote both words.  Not fast: last_fast = false says
                                                                                                   //  "all of last_nq" -- no host write into a pinned word that an earlier call may still be writing)
     }
+    if (fill_late) HIP_TRY(launch_dedup_fill(st, p.nq, dd.rep, p.out_ids, p.out_scores, p.out_counts, p.how_many, dd.n_dup, w->h_retry_dev + 6));
     HIP_TRY(hipEventRecord(ev[2], st));
     if (resident) { const int par = (int)(w->resident_calls & 1u); HIP_TRY(hipEventRecord(w->ev_done[par], st)); w->rec_used[par] = true; ++w->resident_calls; }
     else if (!ext && w->side) { HIP_TRY(hipEventRecord(w->ev_done[0], st)); w->rec_used[0] = true; }   // (a workspace that has served resident calls: the next one's side-stream prep must not overwrite w->prep under this call's kernels)
-    ++w->calls; w->last_retry = (may_overflow || dense) ? 1 : 0; w->last_nq = p.nq; w->last_fast = fast; w->last_mid = fast && (mid_tier || sback_second); w->last_untimed = false;
+    ++w->calls; w->last_retry = (may_overflow || dense) ? 1 : 0; w->last_nq = p.nq; w->last_fast = fast; w->last_mid = fast && (mid_tier || sback_second); w->last_dedup = dedup; w->last_untimed = false;
     if (may_overflow || dense) w->h_retry_valid = true;   // (from now on the pinned counter holds a finished call's count -- or is being overwritten by a newer one)
 
     if (!on_device) {
@@ -1262,6 +1285,15 @@ int device_last_mid_count(DeviceState* d, uint32_t* listed, uint32_t* big_listed
     { std::lock_guard<std::mutex> lk(d->mu); w = d->last_ws; }
     if (listed) *listed = w->last_fast && w->last_mid ? w->h_retry[2] : 0u;
     if (big_listed) *big_listed = w->last_fast ? w->h_retry[3] : 0u;   // (the BIG form also takes the lean shape's oversized queries: no MID tier needed)
+    return SRN_OK;
+}
+
+int device_last_dedup_count(DeviceState* d, uint32_t* merged) {   // queries of the last call that were not served but got the row of an equal, earlier query of the call (0: the call did not merge)
+    const int rc = device_last_path_counts(d, nullptr, nullptr, nullptr);   // (waits for the call's end)
+    if (rc != SRN_OK) return rc;
+    Workspace* w;
+    { std::lock_guard<std::mutex> lk(d->mu); w = d->last_ws; }
+    if (merged) *merged = w->last_dedup ? w->h_retry[6] : 0u;
     return SRN_OK;
 }
 

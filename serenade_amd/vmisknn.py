@@ -188,6 +188,12 @@ class VMISIndex:
         capi.check(capi.lib().srn_debug_last_mid_count(self._h, C.byref(a)))
         return a.value
 
+    def last_dedup_count(self):
+        """Queries of the last call that got the row of an earlier query of the same call with the same item sequence instead of being served; measurement aid."""
+        a = C.c_uint32()
+        capi.check(capi.lib().srn_debug_last_dedup_count(self._h, C.byref(a)))
+        return a.value
+
     def last_big_count(self):
         """... and how many of those the MID instantiation listed for its BIG form (merged lists beyond the 53 KB layout's buffers); measurement aid."""
         a = C.c_uint32()
