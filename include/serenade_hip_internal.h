@@ -51,7 +51,7 @@ int srn_debug_eval_terms(srn_eval_set_t* set, const srn_eval_trial_t* trial, dou
 int srn_debug_device_sessions_last_batch(srn_device_sessions_t* s, const void** d_items, const void** d_q_off, size_t* out_n, size_t* out_max_len,
                                          uint64_t* h_items, size_t cap, uint32_t* h_q_off);
 
-/* Test / experiment knobs (environment variables SRN_NO_FAST, SRN_NO_MID, SRN_NO_MASKS, SRN_NO_MERGE, SRN_DENSE, SRN_HOT_SLOTS,
+/* Test / experiment knobs (environment variables SRN_NO_FAST, SRN_NO_MID, SRN_NO_MASKS, SRN_NO_MERGE, SRN_HOT_SLOTS,
  * SRN_SKETCH_SLOTS, SRN_LDS_BUDGET_KB, SRN_GRID_MULT, SRN_DEBUG) force individual kernel code paths.  They are read ONCE,
  * when the library is first used -- never on the launch path; this call re-reads them (the parity tests switch paths
  * between calls).  Not for production use: make sure no predict call is in flight. */

@@ -336,7 +336,7 @@ int srn_predict(const srn_index_t* idx, const uint64_t* evolving, size_t len, si
         return rc; });
 }
 
-// ---- the persistent latency path (srn_runtime.hip, "serve") ----
+// ---- the persistent latency path (srn_latency.hip, "serve") ----
 int srn_index_serve_start(srn_index_t* idx, size_t k, size_t m, size_t how_many, int enable_business_logic, unsigned lanes, unsigned max_items_in_session, unsigned idle_ms) {
     return guarded([&]() -> int {
         if (!idx) return fail(SRN_EINVAL, "null index");

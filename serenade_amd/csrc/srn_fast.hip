@@ -499,7 +499,7 @@ __global__ __launch_bounds__(512, TINY ? SRN_TINY_WAVES : BIG ? 4 : SRN_FAST_WAV
                         // a row is final iff a finishing path wrote its count over the sentinel; what the body handed on (general kernel, MID, > 63 entries) nobody
                         // will launch: the caller takes the launch path for this session.  The hand-over counters are nobody's business here: back to 0
                         const uint32_t cnt = __atomic_load_n(&p.out_counts[blockIdx.x], __ATOMIC_RELAXED);
-                        if (cnt & 0x80000000u) { (void)atomicExch(&f.slow_cnt[0], 0u); (void)atomicExch(&f.slow_cnt[1], 0u); (void)atomicExch(&f.slow_cnt[2], 0u); (void)atomicExch(&f.slow_cnt[3], 0u); }
+                        if (cnt & 0x80000000u) { (void)atomicExch(&f.slow_cnt[SC_GENERAL], 0u); (void)atomicExch(&f.slow_cnt[SC_MID], 0u); (void)atomicExch(&f.slow_cnt[SC_BIG_TICKET_LO], 0u); (void)atomicExch(&f.slow_cnt[SC_BIG_TICKET_HI], 0u); }
                         const unsigned long long t_end = wall_clock64();
                         c->stamp[2] = (uint32_t)(t_end - serve_t0); c->stamp[3] = (uint32_t)((unsigned long long)clock64() - serve_c0);   // ([3]: the same span in shader cycles)
                         __atomic_store_n(&c->count, cnt, __ATOMIC_RELAXED);
@@ -582,7 +582,7 @@ __global__ __launch_bounds__(512, TINY ? SRN_TINY_WAVES : BIG ? 4 : SRN_FAST_WAV
             else if (tid == 0) {
                 // (round 5) a query of the lean shape whose merged lists alone outgrow the 53 KB layout -- the headline batches' 0.3 % -- goes straight to the BIG form (80 KB of
                 // LDS: n <= 9 404), not to the general kernel: 3 209 such queries per 2^20 cost 0.27 ms there
-                if (hd.unsafe != 0u) f.slow_list[atomicAdd(f.slow_cnt, 1u)] = q;
+                if (hd.unsafe != 0u) f.slow_list[atomicAdd(&f.slow_cnt[SC_GENERAL], 1u)] = q;
                 else if (!MID && MODE == FM_FUSED && f.bigq_list != nullptr && L >= 1u && L <= 8u && L <= p.max_len && hd.sumw <= 15u && nr <= 4u && hd.rmax - hd.xlo < (1u << 28) &&
                     2u * n + 8u + 256u <= (F_BIG_TOTAL - (F_TOTAL - F_SIDF) - F_WORK) / 4u) f.bigq_list[atomicAdd(f.bigq_cnt, 1u)] = q;
                 // (the MID instantiation looks at the query next, if this launch sequence has one; it decides for itself)
@@ -591,7 +591,7 @@ __global__ __launch_bounds__(512, TINY ? SRN_TINY_WAVES : BIG ? 4 : SRN_FAST_WAV
                 else if (!MID && MODE == FM_FUSED && f.long_list != nullptr && L > F_MID_LMAX && L <= F_LONG_LMAX && L <= p.max_len) f.long_list[atomicAdd(f.long_cnt, 1u)] = q;
                 else if (MID && !BIG && f.bigq_list != nullptr && L >= 1u && L <= F_MID_LMAX && L <= p.max_len && hd.sumw <= F_MID_CLASSES && nr <= F_MID_LISTS && hd.rmax - hd.xlo < (1u << (32u - NB)) &&
                          2u * n + 8u + 256u <= (F_BIG_TOTAL - (F_TOTAL - F_SIDF) - F_WORK) / 4u) f.bigq_list[atomicAdd(f.bigq_cnt, 1u)] = q;   // (only the merge buffers' room is missing: MID's BIG form has it)
-                else f.slow_list[atomicAdd(f.slow_cnt, 1u)] = q;
+                else f.slow_list[atomicAdd(&f.slow_cnt[SC_GENERAL], 1u)] = q;
             }
             continue;
         }
@@ -678,7 +678,7 @@ __global__ __launch_bounds__(512, TINY ? SRN_TINY_WAVES : BIG ? 4 : SRN_FAST_WAV
             wlut[tid] = (uint8_t)num; w10t[tid] = (uint16_t)((9u - mp) * num);
         }
         if constexpr (MODE == FM_BACK) {
-            if (K == 0xFFFFFFFFu) { if (tid == 0) f.slow_list[atomicAdd(f.slow_cnt, 1u)] = q; continue; }   // (the fronting rank could not take it: block-uniform)
+            if (K == 0xFFFFFFFFu) { if (tid == 0) f.slow_list[atomicAdd(&f.slow_cnt[SC_GENERAL], 1u)] = q; continue; }   // (the fronting rank could not take it: block-uniform)
             if (K == 0u) { if (tid == 0) p.out_counts[q] = 0u; continue; }
         } else
         if (nr == 1u) {
@@ -1325,7 +1325,7 @@ __global__ __launch_bounds__(512, TINY ? SRN_TINY_WAVES : BIG ? 4 : SRN_FAST_WAV
         }
         FAST_TICK(12);
         if (misc[FS_FAIL]) {   // block-uniform
-            if (tid == 0) { f.slow_list[atomicAdd(f.slow_cnt, 1u)] = q; if (ticking) { const uint32_t c = misc[FS_FAIL]; tacc[15] += (c & 1u) + ((unsigned long long)((c >> 1) & 1u) << 16) + ((unsigned long long)((c >> 2) & 1u) << 32) + ((unsigned long long)((c >> 3) & 1u) << 48); } }
+            if (tid == 0) { f.slow_list[atomicAdd(&f.slow_cnt[SC_GENERAL], 1u)] = q; if (ticking) { const uint32_t c = misc[FS_FAIL]; tacc[15] += (c & 1u) + ((unsigned long long)((c >> 1) & 1u) << 16) + ((unsigned long long)((c >> 2) & 1u) << 32) + ((unsigned long long)((c >> 3) & 1u) << 48); } }
             continue;
         }
         // ---- hand-off: wave 0 alone (the others go on to the next query's record and wait at its first barrier) ---------------
@@ -1381,7 +1381,7 @@ __global__ __launch_bounds__(512, TINY ? SRN_TINY_WAVES : BIG ? 4 : SRN_FAST_WAV
         // vmis_finish_big_kernel: one 64-bit atomic hands out the list slot (high word) and the arena space (low word, entries).
         const uint32_t M = cnt + nt;
         if (MID && (LONG || L == 10u) && M < p.how_many) {   // (wave-uniform) neighbours of weight 0 may exist and the positive scores do not fill the top n: an item of score 0 can be returned (mod.rs:143-153 inserts it)
-            if (ln == 0u) f.slow_list[atomicAdd(f.slow_cnt, 1u)] = q;
+            if (ln == 0u) f.slow_list[atomicAdd(&f.slow_cnt[SC_GENERAL], 1u)] = q;
             continue;
         }
         if constexpr (TINY) {
@@ -1447,7 +1447,7 @@ __global__ __launch_bounds__(512, TINY ? SRN_TINY_WAVES : BIG ? 4 : SRN_FAST_WAV
             const uint32_t slot = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(tk >> 32), 0);
             ovf_at = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)tk, 0);
             if (cnt > F_CAND_CAP || (unsigned long long)ovf_at + (M - F_FIN_ENTRIES) > f.big_cap_entries) {   // no room: the general kernel redoes the query
-                if (ln == 0u) { f.big_list[slot] = 0xFFFFFFFFu; f.slow_list[atomicAdd(f.slow_cnt, 1u)] = q; }
+                if (ln == 0u) { f.big_list[slot] = 0xFFFFFFFFu; f.slow_list[atomicAdd(&f.slow_cnt[SC_GENERAL], 1u)] = q; }
                 continue;
             }
             if (ln == 0u) f.big_list[slot] = q;
@@ -1486,12 +1486,12 @@ __global__ __launch_bounds__(512, TINY ? SRN_TINY_WAVES : BIG ? 4 : SRN_FAST_WAV
         // themselves off; the last one publishes the counters and, behind a system-scope fence, the call's number -- the word the caller spins on.
         if (wave == 0u && f.host_words) __threadfence_system();   // (executed by EVERY lane that stored a row: a fence orders the executing thread's accesses -- ADVICE r5)
         if (tid == 0u && f.host_words) {
-            if (atomicAdd(&f.slow_cnt[6], 1u) == gridDim.x - 1u) {
-                f.host_words[1] = atomicAdd(&f.slow_cnt[0], 0u); f.host_words[2] = atomicAdd(&f.slow_cnt[1], 0u); f.host_words[3] = atomicAdd(&f.slow_cnt[4], 0u);
-                f.host_words[4] = atomicAdd(&f.slow_cnt[3], 0u);
-                atomicExch(&f.slow_cnt[6], 0u);   // (ready for the next call: where nothing was handed on, every counter is 0 again)
+            if (atomicAdd(&f.slow_cnt[SC_TINY_TICKET], 1u) == gridDim.x - 1u) {
+                f.host_words[HW_GENERAL] = atomicAdd(&f.slow_cnt[SC_GENERAL], 0u); f.host_words[HW_MID] = atomicAdd(&f.slow_cnt[SC_MID], 0u); f.host_words[HW_BIGQ] = atomicAdd(&f.slow_cnt[SC_BIGQ], 0u);
+                f.host_words[HW_OVER63] = atomicAdd(&f.slow_cnt[SC_BIG_TICKET_HI], 0u);
+                atomicExch(&f.slow_cnt[SC_TINY_TICKET], 0u);   // (ready for the next call: where nothing was handed on, every counter is 0 again)
                 __threadfence_system();
-                __atomic_store_n(&f.host_words[5], f.host_seq, __ATOMIC_RELAXED);
+                __atomic_store_n(&f.host_words[HW_SEQ], f.host_seq, __ATOMIC_RELAXED);
             }
         }
     }
@@ -1583,7 +1583,7 @@ __global__ __launch_bounds__(64) void vmis_finish_big_kernel(DeviceIndex ix, con
     constexpr uint32_t CAP = F_CAND_CAP + F_TABLE_BUCKETS * 4u;
     // the launch sequence's two counters (queries for the global-table pass, queries handed to the general kernel: both final before this kernel starts) straight into
     // the workspace's pinned words -- two 4-byte device-to-host copies cost 9 us of every call
-    if (host_words && blockIdx.x == 0u && threadIdx.x == 0u) { if (cnt_retry) host_words[0] = *cnt_retry; if (cnt_slow) { host_words[1] = cnt_slow[0]; host_words[2] = cnt_slow[1]; host_words[3] = cnt_slow[4]; } }   // (cnt_slow[1]: the MID instantiation's list, [4]: its BIG form's)   // (a null source: that word is someone else's)
+    if (host_words && blockIdx.x == 0u && threadIdx.x == 0u) { if (cnt_retry) host_words[HW_GLOBAL] = *cnt_retry; if (cnt_slow) { host_words[HW_GENERAL] = cnt_slow[SC_GENERAL]; host_words[HW_MID] = cnt_slow[SC_MID]; host_words[HW_BIGQ] = cnt_slow[SC_BIGQ]; } }   // (a null source: that word is someone else's)
     __shared__ unsigned long long key[CAP];
     __shared__ uint32_t tieb[CAP];
     __shared__ uint32_t hist[256];
@@ -1661,8 +1661,10 @@ hipError_t launch_finish(hipStream_t st, const DeviceIndex& di, const FastParams
     return hipGetLastError();
 }
 
-hipError_t launch_fast(dim3 grid, hipStream_t st, const DeviceIndex& di, const LaunchParams& p, const FastParams& f, bool debug, int mode, bool mid, bool big, bool lng, bool tiny) {
+hipError_t launch_fast(FastForm form, dim3 grid, hipStream_t st, const DeviceIndex& di, const LaunchParams& p, const FastParams& f, bool debug) {
     constexpr int W = (int)F_WG_PER_CU;
+    const int mode = form == FastForm::Front ? FM_FRONT : form == FastForm::Back ? FM_BACK : FM_FUSED;
+    const bool tiny = form == FastForm::Tiny || form == FastForm::TinyMid, lng = form == FastForm::Long, big = lng || form == FastForm::Big, mid = big || form == FastForm::Mid || form == FastForm::TinyMid;
     const bool wide = f.nb == 3u, frag = di.row_frag != 0u;
     if (mid && (mode != FM_FUSED || frag || (!big && !tiny && f.mid_list == nullptr))) return hipErrorInvalidValue;
     if (big && (!mid || (!lng && f.bigq_list == nullptr))) return hipErrorInvalidValue;

@@ -1,5 +1,5 @@
 // hipFree / hipHostFree / hipDeviceSynchronize wait for EVERYTHING enqueued on the device -- with a persistent latency-path workgroup resident (srn_index_serve_start,
-// srn_serve.hip) that is "until it leaves".  Every such call of this library therefore goes through these wrappers: the resident workgroups are told to leave first
+// srn_latency.hip) that is "until it leaves".  Every such call of this library therefore goes through these wrappers: the resident workgroups are told to leave first
 // (they come back at the next srn_predict that wants them).  Include this header LAST in a translation unit that frees or synchronises.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -99,6 +99,17 @@ struct ServeCtl {
     uint32_t done_seq, status, count, alive; uint32_t stamp[4]; uint32_t pad4[8];
 };
 static_assert(sizeof(ServeCtl) == 256, "ServeCtl layout");
+// The eight device words of FastParams::slow_cnt, cleared as one block: queries handed to the general kernel | the MID instantiation's list | the 64-bit ticket of
+// vmis_finish_big_kernel's list (arena entries in use, list length) | MID's BIG form's list | the LONG form's | the TINY launch's workgroups that are done (the last one publishes) | spare
+enum SlowCnt : uint32_t { SC_GENERAL = 0, SC_MID = 1, SC_BIG_TICKET_LO = 2, SC_BIG_TICKET_HI = 3, SC_BIGQ = 4, SC_LONG = 5, SC_TINY_TICKET = 6, SC_SPARE = 7, SC_WORDS = 8 };
+using SlowCntBlock = uint32_t[SC_WORDS];
+// ... and the pinned words the kernels publish a call's counters in (Workspace::h_retry, FastParams::host_words): queries of the global-table pass | handed to the general kernel |
+// listed for MID | for MID's BIG form | with more than 63 entries | the fused call's number, written last of all | queries that got the row of an equal, earlier query (srn_dedup.hip)
+enum HostWord : uint32_t { HW_GLOBAL = 0, HW_GENERAL = 1, HW_MID = 2, HW_BIGQ = 3, HW_OVER63 = 4, HW_SEQ = 5, HW_MERGED = 6, HW_WORDS = 8 };
+using HostWordBlock = uint32_t[HW_WORDS];
+// the four lists inside slow_list, each slow_cap + 16 words
+enum SlowPart : uint32_t { SL_GENERAL = 0, SL_MID = 1, SL_BIGQ = 2, SL_LONG = 3 };
+inline uint32_t* slow_part(uint32_t* slow_list, size_t slow_cap, SlowPart part) { return slow_list + (size_t)part * (slow_cap + 16); }
 struct FastParams {
     const RowQuad* row_packed; const uint32_t* row_ext16;   // 64-byte slots of 16-bit LDS offsets + overflow blocks (8 items per 16 bytes)
     const ItemMeta* meta_sample;   // meta[] of the 512 most popular items in the order the threshold sample reads them: entry 64 w + l = item 8 l + w
@@ -121,7 +132,7 @@ struct FastParams {
     const unsigned long long* order;
     uint64_t tiny_items[8]; uint32_t tiny_len, host_seq;   // (the TINY launch) the session's items in the kernel arguments (tiny_len = 0: read p.items_flat), the call's number
     ServeCtl* serve;            // (the TINY launch) non-null: the persistent form -- grid of ONE workgroup that serves the sessions the host posts here until told to leave
-    uint32_t* host_words;       // (the TINY launch) pinned words the kernel publishes the sequence's counters in: [1] handed to the general kernel, [2] listed for MID, [3] for MID's BIG form, [4] queries with > 63 entries, and last of all [5] = host_seq: the host may read the row
+    uint32_t* host_words;       // (the TINY launch) pinned words the kernel publishes the sequence's counters in (HostWord), last of all HW_SEQ = host_seq: the host may read the row
     const uint32_t* order_dups; // (with `order`, or null) the number of queries at the END of the order that are copies of an earlier query of the call (srn_dedup.hip): the ordered loop stops in front of them
 };
 // the batch's order keys (written by the prep kernel) -> sorted (srn_build_gpu.hip: rocPRIM radix sort on the key bits); temp == nullptr: only *temp_bytes is set
@@ -160,9 +171,13 @@ hipError_t launch_shard_back(dim3 grid, hipStream_t st, const DeviceIndex& di, c
 // ---- launchers (srn_kernels.hip) -------------------------------------------------------------
 // the predict kernel: stage 0 = fused, 1..3 = the item-sharded pipeline's stages A..C; global_tables = the retry pass with its
 // tables in a global-memory arena (stage 0 only)
-hipError_t launch_predict(bool masks, bool slot64, bool global_tables, int stage, dim3 grid, size_t lds, hipStream_t st, const DeviceIndex& di,
-                          const LaunchParams& p, const KernelCfg& c, const uint32_t* qlist, const uint32_t* qn, uint32_t* retry_list,
-                          uint32_t* retry_cnt, char* gscratch, unsigned long long gscratch_stride, char* nb_spill, const ShardIO& sh, int wg_per_cu = 2);
+struct PredictLaunch {
+    bool masks = false, slot64 = false, global_tables = false; int stage = 0;
+    const uint32_t* qlist = nullptr; const uint32_t* qn = nullptr;        // the queries to serve and their number (null: all of p.nq)
+    uint32_t* retry_list = nullptr; uint32_t* retry_cnt = nullptr;        // where the queries go whose tables do not fit
+    char* gscratch = nullptr; unsigned long long gstride = 0; char* spill = nullptr; ShardIO sh{};
+};
+hipError_t launch_predict(const PredictLaunch& a, dim3 grid, size_t lds, hipStream_t st, const DeviceIndex& di, const LaunchParams& p, const KernelCfg& c);
 hipError_t launch_prep(hipStream_t st, const DeviceIndex& di, const uint64_t* items_flat, const uint32_t* q_off, uint32_t nq, uint32_t m,
                        uint32_t max_len, char* out, uint32_t stride, uint32_t* zero_a = nullptr, uint32_t* zero_b = nullptr,
                        const IdSlot* loc_table = nullptr, uint32_t loc_mask = 0, unsigned long long* okeys = nullptr);   // zero_a[0..7], zero_b[0]: counters cleared by the prep kernel; loc_table: the item shard's id table (the record's idx), di = the whole index's dictionary and lists
@@ -186,7 +201,11 @@ hipError_t launch_shard_mark(hipStream_t st, const uint32_t* flag, uint32_t nq, 
 hipError_t launch_shard_fill_i32(hipStream_t st, int* dst, int v, size_t n);
 hipError_t launch_shard_merge_topn(hipStream_t st, const char* part, size_t block_bytes, uint32_t n_shards, uint32_t nq, uint32_t how_many, uint64_t* out_ids, double* out_scores,
                                    uint32_t* out_counts);
-hipError_t launch_fast(dim3 grid, hipStream_t st, const DeviceIndex& di, const LaunchParams& p, const FastParams& f, bool debug = false, int mode = 0, bool mid = false, bool big = false, bool lng = false, bool tiny = false);   // tiny: ONE workgroup = one query, prep record and finish inside (the latency path)   // debug: say the occupancy once (the SRN_DEBUG knob, read by the runtime); mode: 0 fused, 1 front end only (neighbour lists -> f.xchg), 2 back end only (neighbour lists <- f.xchg); mid: the MID instantiation over f.mid_list (mode 0 only)
+// the forms of vmis_fast_kernel.  Lean: the fused kernel over the batch; Mid / Big / Long: the MID instantiation over f.mid_list, its BIG form over f.bigq_list, the LONG form over
+// f.long_list; Tiny / TinyMid: ONE workgroup = one query, prep record and finish inside (the latency path; TinyMid: sessions of > 4 items at once in the MID form); Front: front end
+// only (neighbour lists -> f.xchg); Back: back end only (neighbour lists <- f.xchg).  debug: say the occupancy once (the SRN_DEBUG knob, read by the runtime)
+enum class FastForm { Lean, Mid, Big, Long, Tiny, TinyMid, Front, Back };
+hipError_t launch_fast(FastForm form, dim3 grid, hipStream_t st, const DeviceIndex& di, const LaunchParams& p, const FastParams& f, bool debug = false);
 hipError_t launch_rows_to_packed(hipStream_t st, const uint64_t* row_off, const uint32_t* row_items, uint64_t n_rows, const uint32_t* block_base,
                                  uint32_t* packed, uint32_t* ext16, bool frag = false);   // grid = ceil((n_rows + 1) / 1024) blocks of 1024; block_base in 16-byte blocks
 hipError_t launch_rows_to_frags(hipStream_t st, const uint64_t* row_off, const uint32_t* row_items, uint64_t n_rows, const uint32_t* block_base,

@@ -392,10 +392,9 @@ __global__ __launch_bounds__(256) void vmis_prep_kernel(DeviceIndex ix, const ui
     do { if (ticking && tid == 0) { const long long t_ = clock64(); atomicAdd(&p.phase_cycles[ph], (unsigned long long)(t_ - t_prev)); t_prev = t_; } } while (0); \
     if (SRN_STOP_AT == (ph)) continue
 
-// WG_PER_CU = workgroups the build is meant to co-reside with: 2 (4 waves per SIMD, <= 128 VGPRs) or 3 (6 waves, <= 80 VGPRs: more
-// latency hiding for the price of spills; used with the small LDS geometry when the queries are large, see device_predict)
-template <int BLOCK, typename SlotT, bool GLOBAL_TABLES, int STAGE = 0, bool MASKS = false, int WG_PER_CU = 2>
-__global__ __launch_bounds__(BLOCK, (WG_PER_CU * BLOCK) / 256) void vmis_predict_kernel(DeviceIndex ix_arg, LaunchParams p_arg, KernelCfg c_arg, LaunchAux aux_arg, ShardIO sh_arg) {
+// built to co-reside with one other workgroup on a CU: 4 waves per SIMD, <= 128 VGPRs (a build for three -- 6 waves, <= 80 VGPRs -- spilled and lost: HISTORY.md)
+template <int BLOCK, typename SlotT, bool GLOBAL_TABLES, int STAGE = 0, bool MASKS = false>
+__global__ __launch_bounds__(BLOCK, 2 * BLOCK / 256) void vmis_predict_kernel(DeviceIndex ix_arg, LaunchParams p_arg, KernelCfg c_arg, LaunchAux aux_arg, ShardIO sh_arg) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     // The parameter blocks (the arguments, packed in order with their natural alignment) are read where they
     // are needed, straight from the kernel-argument segment -- constant memory, scalar loads.  Used as by-value arguments the
@@ -1502,34 +1501,25 @@ __global__ __launch_bounds__(BLOCK, (WG_PER_CU * BLOCK) / 256) void vmis_predict
 // =====================================================================================
 // launchers
 // =====================================================================================
-template <int BLOCK, bool GLOBAL_TABLES, int STAGE = 0, bool MASKS = false, int WG_PER_CU = 2>
-static hipError_t launch_variant(bool slot64, dim3 grid, size_t lds, hipStream_t st, const DeviceIndex& di,
-                                 const LaunchParams& p, const KernelCfg& c, const uint32_t* qlist, const uint32_t* qn,
-                                 uint32_t* retry_list, uint32_t* retry_cnt, char* gs, unsigned long long gstride, char* spill,
-                                 const ShardIO& sh = ShardIO{}) {
+template <int BLOCK, bool GLOBAL_TABLES, int STAGE = 0, bool MASKS = false>
+static hipError_t launch_variant(const PredictLaunch& a, dim3 grid, size_t lds, hipStream_t st, const DeviceIndex& di, const LaunchParams& p, const KernelCfg& c) {
 #define SRN_LAUNCH(SLOT)                                                                                             \
     do {                                                                                                                  \
-        auto kern = vmis_predict_kernel<BLOCK, SLOT, GLOBAL_TABLES, STAGE, MASKS, WG_PER_CU>;                                           \
+        auto kern = vmis_predict_kernel<BLOCK, SLOT, GLOBAL_TABLES, STAGE, MASKS>;                                           \
         hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);     \
         if (e != hipSuccess) return e;                                                                                    \
-        hipLaunchKernelGGL(kern, grid, dim3(BLOCK), lds, st, di, p, c, LaunchAux{qlist, qn, retry_list, retry_cnt, gs, gstride, spill}, sh); \
+        hipLaunchKernelGGL(kern, grid, dim3(BLOCK), lds, st, di, p, c, LaunchAux{a.qlist, a.qn, a.retry_list, a.retry_cnt, a.gscratch, a.gstride, a.spill}, a.sh); \
         return hipGetLastError();                                                                                         \
     } while (0)
-    if (!slot64) SRN_LAUNCH(uint32_t);
+    if (!a.slot64) SRN_LAUNCH(uint32_t);
     SRN_LAUNCH(unsigned long long);
 #undef SRN_LAUNCH
 }
 
-hipError_t launch_predict(bool masks, bool slot64, bool global_tables, int stage, dim3 grid, size_t lds, hipStream_t st, const DeviceIndex& di,
-                          const LaunchParams& p, const KernelCfg& c, const uint32_t* qlist, const uint32_t* qn, uint32_t* retry_list,
-                          uint32_t* retry_cnt, char* gscratch, unsigned long long gscratch_stride, char* nb_spill, const ShardIO& sh, int wg_per_cu) {
-    if (wg_per_cu == 3) {   // the 80-VGPR build exists for the fused kernel with u32 slots and LDS tables only
-        if (global_tables || stage != 0 || slot64) return hipErrorInvalidValue;
-        return masks ? launch_variant<kBlock, false, 0, true, 3>(false, grid, lds, st, di, p, c, qlist, qn, retry_list, retry_cnt, gscratch, gscratch_stride, nb_spill, sh)
-                     : launch_variant<kBlock, false, 0, false, 3>(false, grid, lds, st, di, p, c, qlist, qn, retry_list, retry_cnt, gscratch, gscratch_stride, nb_spill, sh);
-    }
-#define SRN_V(G, S, M) launch_variant<kBlock, G, S, M>(slot64, grid, lds, st, di, p, c, qlist, qn, retry_list, retry_cnt, gscratch, gscratch_stride, nb_spill, sh)
-    if (global_tables) {   // (the stages' global-table passes exist for numerator slots only: with position sets the shard group takes the lists pipeline)
+hipError_t launch_predict(const PredictLaunch& a, dim3 grid, size_t lds, hipStream_t st, const DeviceIndex& di, const LaunchParams& p, const KernelCfg& c) {
+    const bool masks = a.masks; const int stage = a.stage;
+#define SRN_V(G, S, M) launch_variant<kBlock, G, S, M>(a, grid, lds, st, di, p, c)
+    if (a.global_tables) {   // (the stages' global-table passes exist for numerator slots only: with position sets the shard group takes the lists pipeline)
         if (stage != 0) return masks ? hipErrorInvalidValue : stage == 1 ? SRN_V(true, 1, false) : stage == 2 ? SRN_V(true, 2, false) : stage == 3 ? SRN_V(true, 3, false) : hipErrorInvalidValue;
         return masks ? SRN_V(true, 0, true) : SRN_V(true, 0, false);
     }

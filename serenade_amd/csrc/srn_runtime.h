@@ -1,4 +1,4 @@
-// Private to the device runtime (srn_runtime.hip, srn_hostpipe.hip, srn_group.hip): the per-index device state, per-call workspaces and the
+// Private to the device runtime (srn_runtime.hip, srn_latency.hip, srn_hostpipe.hip, srn_group.hip): the per-index device state, per-call workspaces and the
 // test / experiment knobs.  Not part of the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -24,7 +24,7 @@ namespace srn {
 struct Knobs {
     int fast_how_many_max = 64;   // SRN_FAST_HOW_MANY_MAX: the largest how_many the fast kernels take (round 6: 64 -- the threshold sample takes the ceil(n / 8)-th largest per wave; until round 5: 24)
     bool no_viol = false;   // SRN_NO_VIOL: an index with incomplete lists takes the general kernel for every query, as until round 5 (A/B)
-    bool no_masks = false, no_merge = false, dense = false, no_fast = false, no_mid = false, no_big = false, no_long = false, debug = false;   // no_long (SRN_NO_LONG): without the LONG instantiation (sessions of 11..20 items go to the general kernel, as until round 4)   // no_mid (SRN_NO_MID): the launch sequence without the fast kernel's MID instantiation (what it would take goes to the general kernel, as before round 4)
+    bool no_masks = false, no_merge = false, no_fast = false, no_mid = false, no_big = false, no_long = false, debug = false;   // no_long (SRN_NO_LONG): without the LONG instantiation (sessions of 11..20 items go to the general kernel, as until round 4)   // no_mid (SRN_NO_MID): the launch sequence without the fast kernel's MID instantiation (what it would take goes to the general kernel, as before round 4)
     int hot_slots = -1, sketch_slots = -1, lds_budget_kb = 0, grid_mult = 16, fast_runs = 0;
     bool grid_mult_set = false;
     int host_chunks = 0;      // SRN_HOST_CHUNKS: number of chunks a host-pointer batch is cut into (0 = by size, srn_hostpipe.hip)
@@ -58,7 +58,7 @@ struct Knobs {
     int sback_min_shards = 8; // SRN_SBACK_MIN_SHARDS: shards of an index cut in at least this many get the frag8 rows (below: fragments of > 4 items are common and the 1 024 + 1 024-word
                               // geometry too small -- config 3 cut in 4 handed 117 K of 131 K queries on; the FM_BACK form of the fast kernel serves those groups)
     int lanes = 4;            // SRN_PREDICT_LANES: concurrent rounds of the srn_predict combiner (srn_combine.cpp)
-    bool geometry_default() const { return !no_masks && !no_merge && !dense && hot_slots < 0 && sketch_slots < 0 && lds_budget_kb == 0; }
+    bool geometry_default() const { return !no_masks && !no_merge && hot_slots < 0 && sketch_slots < 0 && lds_budget_kb == 0; }
 };
 Knobs knobs();   // (a copy: the tests re-read the environment between calls)
 
@@ -70,9 +70,9 @@ struct Workspace {
     hipEvent_t ev[RING][5] = {};                  // ... [4] = after the fast kernel (== [3] when the launch did not use it)
     bool ring_timed[RING] = {};                   // the call recorded all five (kernel timing on: srn_kernel_timing); otherwise only [2], the end of the call
     uint64_t calls = 0, untimed_calls = 0; uint32_t last_retry = 0, last_nq = 0;
-    bool last_fast = false;      // the last call went through the fast kernel: h_retry[1] = what it handed to the general kernel (otherwise: all of last_nq)
-    bool last_mid = false;       // ... and through its MID instantiation: h_retry[2] = the queries the lean instantiation listed for it
-    bool last_dedup = false;     // ... and merged the queries with equal sequences: h_retry[6] = how many were merged
+    bool last_fast = false;      // the last call went through the fast kernel: h_retry[HW_GENERAL] = what it handed to the general kernel (otherwise: all of last_nq)
+    bool last_mid = false;       // ... and through its MID instantiation: h_retry[HW_MID] = the queries the lean instantiation listed for it
+    bool last_dedup = false;     // ... and merged the queries with equal sequences: h_retry[HW_MERGED] = how many were merged
     bool last_untimed = false;   // the last call took the latency path: no events were recorded for it
     // device scratch
     uint32_t* retry_list = nullptr; size_t retry_cap = 0; uint32_t* retry_cnt = nullptr;
@@ -83,8 +83,7 @@ struct Workspace {
     char* sb_scr = nullptr; size_t sb_scr_bytes = 0; // the streaming back end's per-wave scratch
     // (behind the sort's scratch in each order set, where the call merges equal queries: the merged count | rep[nq] | the grouping pass's hash table, DedupRoom in srn_runtime.hip)
     char* order2 = nullptr; size_t order2_bytes = 0; // ... of the second record set (SRN_FLAG_INPUTS_RESIDENT: call i + 1's prep kernel and sort run beside call i's kernels, which still read theirs)
-    uint32_t* retry_list2 = nullptr; size_t retry_cap2 = 0; uint32_t* retry_cnt2 = nullptr;   // what the second LDS tier could not hold either
-    uint32_t* slow_list = nullptr; size_t slow_cap = 0; uint32_t* slow_cnt = nullptr;          // what the fast kernel hands to the general one
+    uint32_t* slow_list = nullptr; size_t slow_cap = 0; uint32_t* slow_cnt = nullptr;          // what the fast kernel hands to the general one | to MID | to its BIG form | to LONG (slow_part), and the SlowCnt words
     char* fin = nullptr; size_t fin_bytes = 0;   // records for vmis_finish_kernel
     char* big = nullptr; size_t big_bytes = 0;   // overflow entries + list for vmis_finish_big_kernel
     char* pin = nullptr; size_t pin_bytes = 0;   // pinned, device-mapped staging of the latency path (a handful of queries on host pointers)
@@ -92,8 +91,8 @@ struct Workspace {
     char* stage = nullptr; size_t stage_bytes = 0;
     std::mutex call_mu;            // a stream-bound workspace serves one call at a time: two host threads enqueueing on the SAME stream must not interleave their launch sequences (they share these buffers)
     bool cnt_dirty = true;          // slow_cnt may hold non-zero words (any launch sequence but a fused one that handed nothing on leaves them so)
-    uint32_t tiny_seq = 0;          // number of the latency path's last fused call (the kernel writes it into h_retry[5] when the row is complete)
-    uint32_t* h_retry = nullptr;   // pinned
+    uint32_t tiny_seq = 0;          // number of the latency path's last fused call (the kernel writes it into h_retry[HW_SEQ] when the row is complete)
+    uint32_t* h_retry = nullptr;   // pinned: the HostWord words
     uint32_t* h_retry_dev = nullptr;   // ... as the device sees it (vmis_finish_big_kernel writes the two counters there)
     bool h_retry_valid = false; hipEvent_t ev_fork = nullptr, ev_join = nullptr;   // the global-table pass forked beside the finish kernels (srn_runtime.hip)
     hipEvent_t ev_block = nullptr; // blocking-sync event of the latency path (rounds shared by several callers)
@@ -101,7 +100,7 @@ struct Workspace {
     hipStream_t side = nullptr; hipEvent_t ev_prep[2] = {}, ev_done[2] = {}; char* prep2 = nullptr; size_t prep2_bytes = 0; uint64_t resident_calls = 0; bool rec_used[2] = {false, false};
 };
 
-struct ServeState;   // the persistent latency path's resident workgroups (srn_runtime.hip, "serve")
+struct ServeState;   // the persistent latency path's resident workgroups (srn_latency.hip, "serve")
 struct DeviceState {
     int device = 0;
     std::atomic<ServeState*> serve{nullptr}; std::vector<ServeState*> serve_retired;   // (retired: stopped, kept until device_release -- a concurrent srn_predict may still hold the pointer)
@@ -124,7 +123,31 @@ struct DeviceState {
 };
 
 // ---- shared helpers (srn_runtime.hip) ----
-int ensure(char** p, size_t* have, size_t need);   // grow-only device scratch
+int ensure(char** p, size_t* have, size_t need, bool exact = false);   // grow-only device scratch (exact: no room to spare)
+int ensure_list(uint32_t** p, size_t* cap, size_t nq, size_t bytes);   // ... a list sized for `nq` queries: exactly `bytes`, *cap = nq
+
+// LDS layout + table sizes for one launch (all blocks alike).  min_region_b: extra room the caller needs in region B.
+struct Geometry {
+    KernelCfg c{}; bool slot64 = false, masks = false; uint32_t slot_bytes = 4; size_t lds = 0;
+    uint64_t need_sess = 0, need_item = 0; bool sess_may_overflow = false, item_may_overflow = false, sketch_may_wrap = false;
+};
+int make_geometry(const DeviceState* d, const FlatIndex& ix, const LaunchParams& p, uint32_t min_region_b, Geometry& g);
+// does the fast kernel serve this launch, and which tiers stand behind its lean form (srn_runtime.hip)
+struct FastPlan { bool fast = false, mid_tier = false, long_tier = false; uint32_t nb_fast = 0; };
+FastPlan fast_plan(const DeviceState* d, const FlatIndex& ix, const LaunchParams& p, const Geometry& geo, const Knobs& kn, bool has_ext);
+// The fast sequence's buffers -- a workspace's (reserve_fast sizes them for cap_q queries) or a resident form's own -- and the FastParams wired to them: every tier list
+// is null unless `tiers` asks for it
+struct FastBuffers { uint32_t* slow_list = nullptr; size_t slow_cap = 0; uint32_t* slow_cnt = nullptr; char* fin = nullptr; char* big = nullptr; uint64_t big_entries = 0; };
+enum FastTier : unsigned { TIER_MID = 1u, TIER_BIGQ = 2u, TIER_LONG = 4u };
+int reserve_fast(Workspace* w, size_t cap_q);
+FastBuffers fast_buffers(const Workspace* w, size_t cap_q);
+FastParams fast_params(const DeviceState* d, const FastBuffers& b, const FastPlan& plan, unsigned tiers = 0u);
+inline FastParams fast_params(const DeviceState* d, const Workspace* w, const FastPlan& plan, size_t cap_q, unsigned tiers = 0u) { return fast_params(d, fast_buffers(w, cap_q), plan, tiers); }
+inline uint32_t prep_stride_of(uint32_t max_len) { return (uint32_t)(sizeof(PrepHead) + (size_t)max_len * sizeof(PrepItem)); }
+// srn_latency.hip: the one-launch latency path (1: some query needs the global-table pass -- the caller takes the batch path) and the resident workgroups' state
+int device_predict_tiny(DeviceState* d, const FlatIndex& ix, Workspace* w, const Geometry& geo, LaunchParams p, const uint64_t* h_items, const uint32_t* h_qoff,
+                        uint64_t* h_ids, double* h_scores, uint32_t* h_counts, bool blocking_wait);
+void serve_free_retired(DeviceState* d);
 Workspace* ws_acquire(DeviceState* d, bool bind_to_stream, void* user_stream);
 void ws_release(DeviceState* d, Workspace* w, bool bound);
 void hostpipes_free(DeviceState* d);   // srn_hostpipe.hip

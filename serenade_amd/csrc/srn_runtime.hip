@@ -1,7 +1,7 @@
 // =====================================================================================
 // Device runtime of libserenade_hip.so: index upload (row slots laid out on the device), per-call workspaces (own stream,
-// staging buffers, event ring), LDS geometry of a launch, the predict launches (prep kernel, predict kernel, global-table
-// retry pass), the item-sharded pipeline's stages, timing and debug counters.  The kernels live in srn_kernels.hip.
+// staging buffers, event ring), LDS geometry of a launch, the batch launch sequence (device_predict: plan, reserve, enqueue), the item-sharded pipeline's stages,
+// timing and debug counters.  The latency paths live in srn_latency.hip, the kernels in srn_kernels.hip and srn_fast.hip.
 // =====================================================================================
 #include <hip/hip_runtime.h>
 
@@ -29,7 +29,7 @@ static int env_int(const char* name, int unset, int lo = INT_MIN, int hi = INT_M
 static void knobs_read() {
     Knobs k;
     k.fast_how_many_max = env_int("SRN_FAST_HOW_MANY_MAX", k.fast_how_many_max, 1, 64);
-    k.no_masks = env_flag("SRN_NO_MASKS"); k.no_viol = env_flag("SRN_NO_VIOL"); k.no_merge = env_flag("SRN_NO_MERGE"); k.dense = env_flag("SRN_DENSE");
+    k.no_masks = env_flag("SRN_NO_MASKS"); k.no_viol = env_flag("SRN_NO_VIOL"); k.no_merge = env_flag("SRN_NO_MERGE");
     k.no_fast = env_flag("SRN_NO_FAST"); k.no_mid = env_flag("SRN_NO_MID"); k.no_big = env_flag("SRN_NO_BIG"); k.no_long = env_flag("SRN_NO_LONG"); k.debug = env_flag("SRN_DEBUG");
     const int row_slots = env_int("SRN_ROW_SLOTS", -1); k.row_slots16 = row_slots == 16 ? 1 : row_slots == 64 ? 0 : -1;
     k.hot_slots = env_int("SRN_HOT_SLOTS", k.hot_slots, 0);
@@ -205,8 +205,6 @@ static void ws_free(Workspace* w) {
     if (w->order) hipFree(w->order);
     if (w->order2) hipFree(w->order2);
     if (w->sb_scr) hipFree(w->sb_scr);
-    if (w->retry_list2) hipFree(w->retry_list2);
-    if (w->retry_cnt2) hipFree(w->retry_cnt2);
     if (w->slow_list) hipFree(w->slow_list);
     if (w->slow_cnt) hipFree(w->slow_cnt);
     if (w->fin) hipFree(w->fin);
@@ -224,7 +222,6 @@ static void ws_free(Workspace* w) {
     delete w;
 }
 
-void serve_free_retired(DeviceState* d);
 void device_release(DeviceState* d) {
     if (!d) return;
     (void)device_serve_stop(d); serve_free_retired(d);
@@ -295,8 +292,8 @@ Workspace* ws_acquire(DeviceState* d, bool bind_to_stream, void* user_stream) {
     Workspace* w = new Workspace();
     if (hipStreamCreateWithFlags(&w->stream, hipStreamNonBlocking) != hipSuccess) { delete w; return nullptr; }
     for (auto& t : w->ev) for (auto& e : t) if (hipEventCreate(&e) != hipSuccess) { ws_free(w); return nullptr; }
-    if (hipMalloc((void**)&w->retry_cnt, 16) != hipSuccess || hipMalloc((void**)&w->retry_cnt2, 16) != hipSuccess || hipMalloc((void**)&w->slow_cnt, 32) != hipSuccess || hipHostMalloc((void**)&w->h_retry, 32, hipHostMallocCoherent) != hipSuccess)   /* (coherent whatever HIP_HOST_COHERENT says: the latency path's caller reads these words while the kernel that writes them is still running) */ { ws_free(w); return nullptr; }
-    memset(w->h_retry, 0, 32);
+    if (hipMalloc((void**)&w->retry_cnt, 16) != hipSuccess || hipMalloc((void**)&w->slow_cnt, sizeof(SlowCntBlock)) != hipSuccess || hipHostMalloc((void**)&w->h_retry, sizeof(HostWordBlock), hipHostMallocCoherent) != hipSuccess)   /* (coherent whatever HIP_HOST_COHERENT says: the latency path's caller reads these words while the kernel that writes them is still running) */ { ws_free(w); return nullptr; }
+    memset(w->h_retry, 0, sizeof(HostWordBlock));
     if (hipHostGetDevicePointer((void**)&w->h_retry_dev, w->h_retry, 0) != hipSuccess) { ws_free(w); return nullptr; }
     d->all_ws.push_back(w);
     if (bind_to_stream) { d->stream_ws.emplace_back(user_stream, w); w->call_mu.lock(); }   // (nobody else can have found it yet: d->mu is held)
@@ -309,13 +306,19 @@ void ws_release(DeviceState* d, Workspace* w, bool bound) {
     if (bound) w->call_mu.unlock();
 }
 
-int ensure(char** p, size_t* have, size_t need) {
+int ensure(char** p, size_t* have, size_t need, bool exact) {
     if (*have >= need) return SRN_OK;
     if (*p) HIP_TRY(hipFree(*p));
     *p = nullptr; *have = 0;
-    need = need + need / 4 + 256;
+    if (!exact) need = need + need / 4 + 256;
     HIP_TRY(hipMalloc((void**)p, need));
     *have = need; return SRN_OK;
+}
+int ensure_list(uint32_t** p, size_t* cap, size_t nq, size_t bytes) {
+    if (*cap >= nq) return SRN_OK;
+    size_t have = 0; *cap = 0;
+    const int rc = ensure((char**)p, &have, bytes, true); if (rc) return rc;
+    *cap = nq; return SRN_OK;
 }
 
 static inline uint32_t round_up(uint32_t v, uint32_t a) { return (v + a - 1) / a * a; }
@@ -330,12 +333,8 @@ static inline uint32_t prime_at_least(uint64_t n) { uint32_t v = (uint32_t)std::
 
 // a sketch word sums max(w, 0) * num over ALL elements that share it (<= k rows of <= max_row_len items): can that pass 2^32?
 static inline bool sketch_wraps(uint64_t k, uint64_t max_row_len, uint64_t Lmax) { return k * std::max<uint64_t>(1, max_row_len) * 9ull * (Lmax * (Lmax + 1) / 2) >= (1ull << 32); }
-struct Geometry {
-    KernelCfg c{}; bool slot64 = false, masks = false; uint32_t slot_bytes = 4; size_t lds = 0;
-    uint64_t need_sess = 0, need_item = 0; bool sess_may_overflow = false, item_may_overflow = false, sketch_may_wrap = false;
-};
 // LDS layout + table sizes for one launch (all blocks alike).  min_region_b: extra room the caller needs in region B.
-static int make_geometry(const DeviceState* d, const FlatIndex& ix, const LaunchParams& p, uint32_t min_region_b, Geometry& g, uint32_t budget_bytes = 0) {
+int make_geometry(const DeviceState* d, const FlatIndex& ix, const LaunchParams& p, uint32_t min_region_b, Geometry& g) {
     const Knobs kn = knobs();
     const uint64_t Lmax = p.max_len;
     // position-set slots (no first-match pass over the rows) need <= 8 evolving items and lists complete above x_lo
@@ -358,7 +357,7 @@ static int make_geometry(const DeviceState* d, const FlatIndex& ix, const Launch
     const uint32_t region_b = round_up(std::max<uint32_t>(std::max<uint32_t>(p.k * slot_bytes, CAND_CAP * 12), min_region_b), 16);
     c.off_a = c.off_b + region_b;
     const uint32_t lds_max = (uint32_t)std::min(d->lds_per_block_max, 160 * 1024);
-    uint32_t budget = budget_bytes ? budget_bytes : 80 * 1024;   // default: two 512-thread blocks per CU
+    uint32_t budget = 80 * 1024;   // two 512-thread blocks per CU
     if (kn.lds_budget_kb) budget = (uint32_t)kn.lds_budget_kb * 1024;   // experiment knob (occupancy studies)
     if (c.off_a + 32 * 1024 > budget) budget = lds_max;   // long sessions / large k: one block per CU
     if (c.off_a + 8 * 1024 > budget) return fail(SRN_ERANGE, "k / session length too large for the LDS layout");
@@ -413,12 +412,11 @@ static int make_geometry(const DeviceState* d, const FlatIndex& ix, const Launch
 // What the fast kernel needs of the LAUNCH is the position-set condition (DESIGN.md "Why MASKS is exact": m <= m_index, lists complete) and sketch words that cannot wrap
 // at ITS session lengths (<= 10 items: the admission is per query, on the device); the batch's longest session only decides which kernels serve the hand-overs -- up to
 // round 3 one session of nine items sent the whole batch to the general kernel.
-struct FastPlan { bool fast = false, mid_tier = false, long_tier = false; uint32_t nb_fast = 0; };
 static uint32_t fast_nb(const FlatIndex& ix, const Knobs& kn) {   // bits of a fast-kernel slot's list set (0: the index has too many sessions for any)
     const int rank_bits_f = std::max(1, bits_host(ix.n_kept ? ix.n_kept - 1 : 0));
     return kn.fast_runs == 3 && rank_bits_f <= 29 ? 3u : rank_bits_f <= 28 ? 4u : rank_bits_f <= 29 ? 3u : 0u;
 }
-static FastPlan fast_plan(const DeviceState* d, const FlatIndex& ix, const LaunchParams& p, const Geometry& geo, const Knobs& kn, bool has_ext) {
+FastPlan fast_plan(const DeviceState* d, const FlatIndex& ix, const LaunchParams& p, const Geometry& geo, const Knobs& kn, bool has_ext) {
     FastPlan f;
     // the fast kernel packs (rank, set of <= 4 lists) into 32 bits whatever the general kernel's slots look like: up to 2^28 sessions with 4 lists per query,
     // up to 2^29 with 3 (queries with more go to the MID instantiation / the general kernel)
@@ -438,7 +436,9 @@ static FastPlan fast_plan(const DeviceState* d, const FlatIndex& ix, const Launc
 // The serving order of a batch (FastParams::order): room for the keys the prep kernel writes, their sorted copy and the sort's scratch in ONE grow-only buffer; then the sort
 // itself, enqueued on the stream the prep kernel ran on.
 struct DedupRoom { uint32_t* n_dup = nullptr; uint32_t* rep = nullptr; uint32_t* slots = nullptr; uint32_t* slot_min = nullptr; uint32_t n_slots = 0; };
-static int order_room(char** buf, size_t* have, uint32_t nq, unsigned long long** keys_in, unsigned long long** keys_out, void** temp, size_t* temp_bytes, DedupRoom* dd = nullptr) {
+struct OrderBufs { unsigned long long* keys_in = nullptr; unsigned long long* keys_out = nullptr; void* temp = nullptr; size_t temp_bytes = 0; DedupRoom dd; };
+static int order_room(char** buf, size_t* have, uint32_t nq, OrderBufs* o, bool dedup = false) {
+    DedupRoom* dd = dedup ? &o->dd : nullptr;
     size_t tb = 0;
     if (sort_order_keys(nullptr, nullptr, nullptr, nq, nullptr, &tb) != hipSuccess) return fail(SRN_EHIP, "rocprim::radix_sort_keys (size query) failed");
     const size_t kb = ((size_t)nq * 8 + 255) / 256 * 256, tbr = (tb + 255) / 256 * 256;
@@ -446,367 +446,9 @@ static int order_room(char** buf, size_t* have, uint32_t nq, unsigned long long*
     //  the side stream while the previous call's kernels still read THEIR count and representatives)
     const size_t rb = ((size_t)nq * 4 + 255) / 256 * 256, n_slots = dd ? dedup_slots(nq) : 0;
     int rc = ensure(buf, have, 2 * kb + tbr + 256 + (dd ? 256 + rb + 2 * n_slots * 4 : 0)); if (rc) return rc;
-    *keys_in = (unsigned long long*)*buf; *keys_out = (unsigned long long*)(*buf + kb); *temp = *buf + 2 * kb; *temp_bytes = tb;
+    o->keys_in = (unsigned long long*)*buf; o->keys_out = (unsigned long long*)(*buf + kb); o->temp = *buf + 2 * kb; o->temp_bytes = tb;
     if (dd) { char* b = *buf + 2 * kb + tbr + 256; dd->n_dup = (uint32_t*)b; dd->rep = (uint32_t*)(b + 256); dd->slots = (uint32_t*)(b + 256 + rb); dd->slot_min = dd->slots + n_slots; dd->n_slots = (uint32_t)n_slots; }
     return SRN_OK;
-}
-
-// Latency path: a handful of evolving sessions on host pointers (srn_predict: the reference's call shape, one session per call).
-// No copies, no memsets, no events: the queries are written into pinned, device-mapped memory that the kernels read directly, the
-// results come back the same way; two launches (prep kernel + general kernel, one workgroup per query) and one stream synchronise.
-// Returns 1 if a query needs the global-table pass (the caller then takes the normal path).
-static int device_predict_tiny(DeviceState* d, const FlatIndex& ix, Workspace* w, const Geometry& geo, LaunchParams p, const uint64_t* h_items, const uint32_t* h_qoff,
-                               uint64_t* h_ids, double* h_scores, uint32_t* h_counts, bool blocking_wait) {
-    const size_t nitems = h_qoff[p.nq], n_out = (size_t)p.nq * p.how_many;
-    size_t off = 0; auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 63) / 64 * 64; return o; };
-    const size_t o_items = take(nitems * 8), o_qoff = take(((size_t)p.nq + 1) * 4), o_ids = take(n_out * 8), o_sc = take(n_out * 8), o_cnt = take((size_t)p.nq * 4),
-                 o_rc = take(4), o_rl = take((size_t)p.nq * 4 + 4);
-    if (w->pin_bytes < off) {
-        if (w->pin) HIP_TRY(hipHostFree(w->pin));
-        w->pin = nullptr; w->pin_bytes = 0;
-        const size_t want = std::max<size_t>(off * 2, 256 * 1024);   // (room for a full round of the combiner at once: growing a pinned buffer stalls every lane)
-        HIP_TRY(hipHostMalloc((void**)&w->pin, want, hipHostMallocMapped | hipHostMallocCoherent));   // (coherent: the fused launch's caller reads its rows as soon as the kernel's last pinned word says so)
-        w->pin_bytes = want;
-    }
-    char* dp = nullptr; HIP_TRY(hipHostGetDevicePointer((void**)&dp, w->pin, 0));
-    memcpy(w->pin + o_items, h_items, nitems * 8); memcpy(w->pin + o_qoff, h_qoff, ((size_t)p.nq + 1) * 4);
-    *(volatile uint32_t*)(w->pin + o_rc) = 0;
-    p.items_flat = (const uint64_t*)(dp + o_items); p.q_off = (const uint32_t*)(dp + o_qoff);
-    p.out_ids = (uint64_t*)(dp + o_ids); p.out_scores = (double*)(dp + o_sc); p.out_counts = (uint32_t*)(dp + o_cnt);
-    p.stats = nullptr; p.nb_rank = p.nb_num = p.nb_cnt = nullptr; p.phase_cycles = nullptr;
-    hipStream_t st = w->stream;
-    const size_t cap_q = std::max<size_t>(p.nq, (size_t)std::max(1, knobs().tiny_max));   // (sized once for the largest round: hipFree / hipMalloc synchronise the device)
-    { int rc = ensure(&w->spill, &w->spill_bytes, cap_q * p.k * geo.slot_bytes); if (rc) return rc; }
-    const uint32_t prep_stride = (uint32_t)(sizeof(PrepHead) + (size_t)p.max_len * sizeof(PrepItem));
-    { int rc = ensure(&w->prep, &w->prep_bytes, cap_q * prep_stride); if (rc) return rc; }
-    // The fast kernel's launch sequence on the same zero-copy buffers where it pays (round 4): a batch with a session of > 8 items puts ALL its queries on the general kernel's
-    // non-position-set build -- 143 us per call against 52 us on config 3, and one such session in a combined round of srn_predict calls slows the whole round -- while the
-    // lean / MID instantiations serve sessions of <= 10 items at the short sessions' cost.  Four more launches (~2 us each on an idle stream), no more synchronisation.
-    const Knobs kn = knobs();
-    const FastPlan plan = fast_plan(d, ix, p, geo, kn, false);
-    const bool tiny_fast = plan.fast && (kn.tiny_fast == 3 || (kn.tiny_fast >= 1 && p.max_len > 8) || (kn.tiny_fast == 2 && p.nq <= (kn.no_tiny_fused ? 32u : (uint32_t)kn.tiny_fused_max)));   // (the crossover measured with tools/tiny_crossover.py: profiles/r04_serving_tiny_fast.txt)
-    const uint64_t big_entries = (uint64_t)cap_q * 16 + 4096;
-    if (tiny_fast) {   // (sized once, for the largest round)
-        if (w->slow_cap < cap_q) { if (w->slow_list) HIP_TRY(hipFree(w->slow_list)); w->slow_list = nullptr; w->slow_cap = 0;
-            HIP_TRY(hipMalloc((void**)&w->slow_list, (cap_q * 4 + 64) * 4)); w->slow_cap = cap_q; }
-        { int rc = ensure(&w->fin, &w->fin_bytes, cap_q * F_FIN_BYTES + 1024); if (rc) return rc; }
-        { int rc = ensure(&w->big, &w->big_bytes, big_entries * 16 + cap_q * 4 + 64); if (rc) return rc; }
-    }
-    // (round 5) ONE evolving session per call -- srn_predict, the reference's call shape: one launch.  The fast kernel's TINY instantiation writes the prep record itself,
-    // serves the query and finishes its row from registers; the counters it publishes say whether anything is left for the kernels behind it (SRN_TINY_FUSED=0: five launches).
-    const bool fused = tiny_fast && p.nq <= (uint32_t)kn.tiny_fused_max && !kn.no_tiny_fused;
-    if (!fused) { w->cnt_dirty = true; HIP_TRY(launch_prep(st, d->di, p.items_flat, p.q_off, p.nq, p.m, p.max_len, w->prep, prep_stride, tiny_fast ? w->slow_cnt : nullptr)); }
-    p.prep = w->prep; p.prep_stride = prep_stride;
-    if (tiny_fast) {
-        FastParams fp = d->fast; fp.slow_list = w->slow_list; fp.slow_cnt = w->slow_cnt; fp.nb = plan.nb_fast; fp.max_runs = plan.nb_fast; fp.fin = w->fin;
-        fp.big_arena = w->big; fp.big_list = (uint32_t*)(w->big + big_entries * 16); fp.big_ticket = (unsigned long long*)(w->slow_cnt + 2); fp.big_cap_entries = (uint32_t)big_entries;
-        fp.xchg = nullptr; fp.xchg_stride = 0; fp.q_base = 0; fp.order = nullptr;
-        fp.mid_list = plan.mid_tier ? w->slow_list + (w->slow_cap + 16) : nullptr; fp.mid_cnt = plan.mid_tier ? w->slow_cnt + 1 : nullptr;
-        fp.bigq_list = nullptr; fp.bigq_cnt = nullptr; fp.long_list = nullptr; fp.long_cnt = nullptr;   // (no BIG / LONG tier on the latency path)
-        uint32_t seq = 0;
-        if (fused) {
-            uint32_t L1 = 0; for (uint32_t q = 0; q < p.nq; ++q) L1 = std::max(L1, h_qoff[q + 1] - h_qoff[q]);   // the call's longest session
-            if (w->cnt_dirty) HIP_TRY(hipMemsetAsync(w->slow_cnt, 0, 32, st));   // (only after a call that left the counters non-zero: the fused launch leaves them at 0 unless it hands work on)
-            w->cnt_dirty = true;   // (until this call is known to have ended cleanly with nothing handed on: an error return in between must not leave a stale ticket behind a "clean" flag -- ADVICE r5)
-            fp.tiny_len = p.nq == 1 && L1 >= 1u && L1 <= 8u ? L1 : 0u;   // (a single session's items in the kernel arguments where they fit)
-            for (uint32_t i = 0; i < fp.tiny_len; ++i) fp.tiny_items[i] = h_items[h_qoff[0] + i];
-            seq = ++w->tiny_seq; if (seq == 0u) seq = ++w->tiny_seq;
-            fp.host_seq = seq; fp.host_words = w->h_retry_dev;
-            // (a session of > 4 items goes to the MID form at once -- the lean form would only list it: five lists, numerators beyond 15)
-            HIP_TRY(launch_fast(dim3(p.nq), st, d->di, p, fp, kn.debug, 0, plan.mid_tier && L1 > 4u, false, false, true));
-            fp.host_words = nullptr; fp.tiny_len = 0;
-        }
-        else
-        HIP_TRY(launch_fast(dim3(p.nq), st, d->di, p, fp, kn.debug, 0));
-        // The fused launch is a whole first phase: the counters it publishes say whether a second one (the kernels of rest() below, and a second wait) is needed at all.  The
-        // five-launch form (SRN_TINY_FUSED=0) has no second phase: rest() goes behind the fast kernel with every call.  (Splitting the five launches into two phases on counters
-        // published by the finish kernel was measured in round 5 and lost at p90 / p99 -- profiles/r05_latency_phases.txt: removed.)
-        auto rest = [&]() -> int {
-            if (plan.mid_tier) HIP_TRY(launch_fast(dim3(p.nq), st, d->di, p, fp, kn.debug, 0, true));
-            HIP_TRY(launch_predict(geo.masks, geo.slot64, false, 0, dim3(p.nq), geo.lds, st, d->di, p, geo.c, w->slow_list, w->slow_cnt, (uint32_t*)(dp + o_rl), (uint32_t*)(dp + o_rc), nullptr, 0,
-                                   w->spill, ShardIO{}));
-            HIP_TRY(launch_finish(st, d->di, fp, p.out_ids, p.out_scores, p.out_counts, p.nq, p.how_many));
-            // (it also publishes the call's path counters -- handed over, listed for MID -- in the workspace's pinned words: srn_last_path_counts / srn_debug_last_mid_count after a
-            //  latency-path call used to say "all through the general kernel")
-            HIP_TRY(launch_finish_big(st, d->di, fp, p.out_ids, p.out_scores, p.out_counts, p.how_many, (uint32_t)std::min<uint64_t>(p.nq, (uint64_t)d->n_cu * 16), nullptr, w->slow_cnt, w->h_retry_dev));
-            return SRN_OK;
-        };
-        if (!fused) { int rc = rest(); if (rc) return rc; }
-        auto wait = [&]() -> int {
-            if (blocking_wait) {   // a round several callers share: sleep on an interrupt instead of spinning on the signal (the host's cores belong to the callers)
-                if (!w->ev_block) HIP_TRY(hipEventCreateWithFlags(&w->ev_block, hipEventBlockingSync | hipEventDisableTiming));
-                HIP_TRY(hipEventRecord(w->ev_block, st));
-                HIP_TRY(hipEventSynchronize(w->ev_block));
-            } else HIP_TRY(hipStreamSynchronize(st));
-            return SRN_OK;
-        };
-        const volatile uint32_t* hw = w->h_retry;
-        bool seen = false;
-        if (fused && !blocking_wait && !kn.no_tiny_spin) {
-            // the kernel's last store is the call's number in a pinned word, behind a system-scope fence: the row is readable as soon as the host sees it -- before the
-            // queue's completion signal (end-of-kernel cache write-back, signal, the runtime's poll of it) has made its way.  A bounded spin: a fault shows in the stream's wait
-            const auto t0 = std::chrono::steady_clock::now();
-            for (uint32_t spin = 0; !seen; ++spin) {
-                seen = hw[5] == seq;
-                if (!seen) {
-                    __builtin_ia32_pause();   // (the sibling hyper-thread may be another caller spinning on ITS workspace)
-                    if ((spin & 1023u) == 1023u && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(5)) break;
-                }
-            }
-            std::atomic_thread_fence(std::memory_order_acquire);
-        }
-        if (!seen) { int rc = wait(); if (rc) return rc; }
-        // the counters hw[1..4] are this call's only if the kernel published its number behind them; a fused launch that ended without doing so (it cannot, short of a
-        // fault the wait above would have reported) gets the full second phase rather than a guess from stale words
-        const bool published = !fused || hw[5] == seq;
-        if (fused && !published) { int rc = rest(); if (rc) return rc; rc = wait(); if (rc) return rc; }
-        else
-        if (kn.debug && fused) {   // (SRN_DEBUG: how often a single-session call needs the kernels behind the fused launch, and why)
-            static std::atomic<uint64_t> calls{0}, second{0}, why[3] = {{0}, {0}, {0}};
-            const uint64_t c = calls.fetch_add(1) + 1;
-            if ((hw[1] | hw[2] | hw[4]) != 0u) { second.fetch_add(1); if (hw[1]) why[0].fetch_add(1); if (hw[2]) why[1].fetch_add(1); if (hw[4]) why[2].fetch_add(1); }
-            if (c % 1000 == 0) fprintf(stderr, "[srn] fused single-session calls: %llu, with a second phase %llu (handed to the general kernel %llu, listed for MID %llu, > 63 entries %llu)\n",
-                                       (unsigned long long)c, (unsigned long long)second.load(), (unsigned long long)why[0].load(), (unsigned long long)why[1].load(), (unsigned long long)why[2].load());
-        }
-        if (fused && published && (hw[1] | hw[2] | hw[4]) == 0u) w->cnt_dirty = false;   // (a clean end with nothing handed on: the counters and the workgroup ticket are back at 0)
-        if (fused && published && (hw[1] | hw[2] | hw[4]) != 0u) {   // the second phase (handed to the general kernel | listed for MID | queries with > 63 entries)
-            int rc = SRN_OK;
-            w->cnt_dirty = true;
-            if (hw[2] == 0u) {   // (nothing listed for MID: the general kernel over what was handed to it -- it writes its rows itself -- and finish-big for a row the fused launch could not finish, each only if needed)
-                const uint32_t n_slow = hw[1], n_big = hw[4];
-                if (n_slow) HIP_TRY(launch_predict(geo.masks, geo.slot64, false, 0, dim3(std::min<uint32_t>(p.nq, n_slow)), geo.lds, st, d->di, p, geo.c, w->slow_list, w->slow_cnt, (uint32_t*)(dp + o_rl), (uint32_t*)(dp + o_rc), nullptr, 0,
-                                                   w->spill, ShardIO{}));
-                if (n_big) HIP_TRY(launch_finish_big(st, d->di, fp, p.out_ids, p.out_scores, p.out_counts, p.how_many, (uint32_t)std::min<uint64_t>(p.nq, (uint64_t)d->n_cu * 16), nullptr, w->slow_cnt, w->h_retry_dev));
-            }
-            else rc = rest();
-            if (rc) return rc;
-            rc = wait(); if (rc) return rc;
-        }
-    } else {
-    HIP_TRY(launch_predict(geo.masks, geo.slot64, false, 0, dim3(p.nq), geo.lds, st, d->di, p, geo.c, nullptr, nullptr, (uint32_t*)(dp + o_rl), (uint32_t*)(dp + o_rc), nullptr, 0,
-                           w->spill, ShardIO{}));
-    if (blocking_wait) {   // a round several callers share: sleep on an interrupt instead of spinning on the signal (the host's cores belong to the callers)
-        if (!w->ev_block) HIP_TRY(hipEventCreateWithFlags(&w->ev_block, hipEventBlockingSync | hipEventDisableTiming));
-        HIP_TRY(hipEventRecord(w->ev_block, st));
-        HIP_TRY(hipEventSynchronize(w->ev_block));
-    } else HIP_TRY(hipStreamSynchronize(st));
-    }
-    if (*(volatile uint32_t*)(w->pin + o_rc) != 0) return 1;   // (rare: tables too small for some query)
-    // what the timing / path-count APIs report after this call: its query count, how many of them the fast sequence handed to the general kernel (all of them where the
-    // two-launch form ran), not timed (the stream is idle here: nothing of an earlier call is still writing the pinned words)
-    ++w->untimed_calls; w->last_nq = p.nq; w->last_retry = 0; w->last_fast = tiny_fast; w->last_mid = tiny_fast && plan.mid_tier; w->last_dedup = false; w->last_untimed = true;   // (`calls` indexes the event ring: timed calls only)
-    const uint64_t* r_ids = (const uint64_t*)(w->pin + o_ids); const double* r_sc = (const double*)(w->pin + o_sc); const uint32_t* r_cnt = (const uint32_t*)(w->pin + o_cnt);
-    for (uint32_t q = 0; q < p.nq; ++q) {
-        const uint32_t n = r_cnt[q] == 0xFFFFFFFFu ? 0u : std::min<uint32_t>(r_cnt[q], p.how_many);
-        h_counts[q] = r_cnt[q];
-        memcpy(h_ids + (size_t)q * p.how_many, r_ids + (size_t)q * p.how_many, (size_t)n * 8);
-        memcpy(h_scores + (size_t)q * p.how_many, r_sc + (size_t)q * p.how_many, (size_t)n * 8);
-        std::fill(h_ids + (size_t)q * p.how_many + n, h_ids + (size_t)(q + 1) * p.how_many, 0ull);      // the unused tail of each row reads as 0
-        std::fill(h_scores + (size_t)q * p.how_many + n, h_scores + (size_t)(q + 1) * p.how_many, 0.0);
-    }
-    return SRN_OK;
-}
-
-
-// =====================================================================================================================================================================
-// The PERSISTENT latency path (round 6).  srn_predict on the one-launch form costs 28 us from a C++ host of which ~13 us are the GPU's work: the rest
-// is queue submission and completion signalling.  Here a workgroup of vmis_fast_kernel<TINY> stays RESIDENT (one third of one CU) and polls a pinned control block
-// (ServeCtl, srn_kernels.h): the host writes the session and then its number, the workgroup serves it -- same code, same rows -- and answers with the number; the host
-// spins on its own memory.  Doorbell round trip measured on this platform: 1.6 us (tools/ring_probe.hip).  A session the fused form would hand on (general kernel, MID,
-// > 63 entries: 0.3-3 % of config 3's) comes back with status 1 and takes the launch path, as does any call whose k / m / how_many / flags are not the resident ones.
-// hipFree / hipDeviceSynchronize would wait for a resident workgroup for ever: every such call of the library goes through srn_hipsync.h, which makes them leave first.
-// =====================================================================================================================================================================
-struct ServeForm {   // one resident launch: N workgroups of the lean form (sessions of <= 4 items) or of the form for 5..10 items
-    DeviceState* d = nullptr; bool mid = false; std::atomic<bool> dead{false}; uint32_t n = 0;
-    hipStream_t st = nullptr;
-    ServeCtl* ctl = nullptr; ServeCtl* ctl_dev = nullptr;   // [n], pinned
-    char* rows = nullptr; char* rows_dev = nullptr; size_t row_bytes = 0;   // [n] x (ids | scores), pinned
-    char *prep = nullptr, *fin = nullptr, *big = nullptr; uint32_t *slow_list = nullptr, *slow_cnt = nullptr, *counts = nullptr;
-    LaunchParams p{}; FastParams fp{};
-    std::unique_ptr<std::atomic<int>[]> busy; std::vector<uint32_t> seq;   // per workgroup: taken by a caller; the last number posted
-    std::mutex mu; bool running = false;   // (mu: starting / parking the launch)
-};
-struct ServeState {
-    std::vector<ServeForm*> forms; uint32_t k = 0, m = 0, how_many = 0, flags = 0, max_items = 0; unsigned long long idle_ticks = 0;
-    std::atomic<uint64_t> served{0}, not_served{0}, launches{0};
-};
-static std::mutex g_serve_mu; static std::vector<ServeForm*> g_serve_forms; static std::atomic<int> g_serve_running{0};
-
-static void lane_lock(ServeForm* f, uint32_t i) { int e = 0; while (!f->busy[i].compare_exchange_weak(e, 1, std::memory_order_acquire)) { e = 0; __builtin_ia32_pause(); } }
-static void lane_unlock(ServeForm* f, uint32_t i) { f->busy[i].store(0, std::memory_order_release); }
-// (f->mu held, no lane held by this thread) the resident workgroups leave -- after the sessions they are serving
-static void form_park(ServeForm* f) {
-    if (!f->running) return;
-    for (uint32_t i = 0; i < f->n; ++i) lane_lock(f, i);   // (nobody is posting, nothing is in flight)
-    int cur = 0; (void)hipGetDevice(&cur);
-    if (cur != f->d->device) (void)hipSetDevice(f->d->device);
-    for (uint32_t i = 0; i < f->n; ++i) __atomic_store_n(&f->ctl[i].stop, 1u, __ATOMIC_RELEASE);
-    (void)hipStreamSynchronize(f->st);
-    if (cur != f->d->device) (void)hipSetDevice(cur);
-    f->running = false; g_serve_running.fetch_sub(1);
-    for (uint32_t i = 0; i < f->n; ++i) lane_unlock(f, i);
-}
-static std::atomic<int> g_serve_hold{0};   // > 0: some thread is inside a call that waits for the whole device (hipFree ...): no resident launch may start
-void serve_hold_begin() { g_serve_hold.fetch_add(1, std::memory_order_acq_rel); serve_quiesce_all(); }
-void serve_hold_end() { g_serve_hold.fetch_sub(1, std::memory_order_acq_rel); }
-void serve_quiesce_all() {
-    if (g_serve_running.load(std::memory_order_acquire) == 0) return;
-    std::lock_guard<std::mutex> lk(g_serve_mu);
-    for (ServeForm* f : g_serve_forms) { std::lock_guard<std::mutex> fl(f->mu); form_park(f); }
-}
-// (f->mu held, no lane held by this thread) start the resident launch
-static int form_launch(ServeState* s, ServeForm* f) {
-    // (a launch that starts now would be parked at once, or worse, waited for by the free in progress: the caller takes the launch path this time.  A hold that begins
-    //  right after this look parks what is started here: its quiesce takes f->mu, which the caller of this function holds)
-    if (g_serve_hold.load(std::memory_order_acquire) > 0) return SRN_ESTATE;
-    if (f->running) {   // (workgroups that left by their idle timeout: the launch is over once all have)
-        bool all_gone = true; for (uint32_t i = 0; i < f->n; ++i) all_gone = all_gone && __atomic_load_n(&f->ctl[i].alive, __ATOMIC_ACQUIRE) == 0u;
-        if (!all_gone) { form_park(f); } else { HIP_TRY(hipSetDevice(f->d->device)); HIP_TRY(hipStreamSynchronize(f->st)); f->running = false; g_serve_running.fetch_sub(1); }
-    }
-    for (uint32_t i = 0; i < f->n; ++i) lane_lock(f, i);
-    auto unlock_all = [&]() { for (uint32_t i = 0; i < f->n; ++i) lane_unlock(f, i); };
-    hipError_t e = hipSetDevice(f->d->device);
-    for (uint32_t i = 0; i < f->n && e == hipSuccess; ++i) { ServeCtl& c = f->ctl[i]; c.stop = 0; c.alive = 1; c.idle_ticks = s->idle_ticks; c.seq = f->seq[i]; c.done_seq = f->seq[i]; }   // (a post an earlier launch never answered is not served late)
-    std::atomic_thread_fence(std::memory_order_seq_cst);
-    if (e == hipSuccess) e = hipMemsetAsync(f->slow_cnt, 0, 32, f->st);
-    if (e == hipSuccess) e = launch_fast(dim3(f->n), f->st, f->d->di, f->p, f->fp, false, 0, f->mid, false, false, true);
-    if (e == hipSuccess) { f->running = true; g_serve_running.fetch_add(1); s->launches.fetch_add(1); }
-    unlock_all();
-    return e == hipSuccess ? SRN_OK : fail(SRN_EHIP, std::string("the persistent latency path: ") + hipGetErrorString(e));
-}
-static void form_free(ServeForm* f) {
-    { std::lock_guard<std::mutex> lk(g_serve_mu); g_serve_forms.erase(std::remove(g_serve_forms.begin(), g_serve_forms.end(), f), g_serve_forms.end()); }
-    { std::lock_guard<std::mutex> fl(f->mu); form_park(f); }
-    for (void* q : {(void*)f->prep, (void*)f->fin, (void*)f->big, (void*)f->slow_list, (void*)f->slow_cnt, (void*)f->counts}) if (q) (void)hipFree(q);
-    if (f->ctl) (void)hipHostFree(f->ctl); if (f->rows) (void)hipHostFree(f->rows);
-    if (f->st) (void)hipStreamDestroy(f->st);
-    delete f;
-}
-// srn_index_serve_stop may run while other threads are inside srn_predict: a caller that read the state's pointer a moment ago must still find its memory.  Stop therefore
-// RETIRES the state -- its forms are marked dead (no new session is posted, no launch is started again) and parked (every session in flight is answered first) -- and
-// only device_release (srn_index_free: nobody may be using the index any more) frees it.
-void serve_free_retired(DeviceState* d) {
-    std::vector<ServeState*> old;
-    { std::lock_guard<std::mutex> lk(d->mu); old.swap(d->serve_retired); }
-    for (ServeState* s : old) { for (ServeForm* f : s->forms) form_free(f); delete s; }
-}
-int device_serve_stop(DeviceState* d) {
-    ServeState* s = d->serve.exchange(nullptr);
-    if (!s) return SRN_OK;
-    HIP_TRY(hipSetDevice(d->device));
-    for (ServeForm* f : s->forms) { f->dead.store(true); std::lock_guard<std::mutex> fl(f->mu); form_park(f); }
-    { std::lock_guard<std::mutex> lk(d->mu); d->serve_retired.push_back(s); }
-    return SRN_OK;
-}
-int device_serve_start(DeviceState* d, const FlatIndex& ix, uint32_t k, uint32_t m, uint32_t how_many, uint32_t flags, uint32_t lanes, uint32_t max_items, uint32_t idle_ms) {
-    int rc = device_serve_stop(d); if (rc) return rc;
-    if (lanes == 0) return SRN_OK;
-    if (lanes > 256) return fail(SRN_ERANGE, "at most 256 resident workgroups per form");
-    HIP_TRY(hipSetDevice(d->device));
-    const Knobs kn = knobs();
-    ServeState* s = new ServeState(); s->k = k; s->m = m; s->how_many = how_many; s->flags = flags; s->max_items = std::min<uint32_t>(std::max<uint32_t>(max_items, 1), F_MID_LMAX);
-    s->idle_ticks = (unsigned long long)std::max<uint32_t>(idle_ms, 1) * 100000ull;   // (wall_clock64: 100 MHz)
-    auto undo = [&](int code, const std::string& why) { for (ServeForm* f : s->forms) form_free(f); delete s; return fail(code, why); };   // (never published: nobody else holds it)
-    // A resident launch never ends, and HIP multiplexes its streams onto a few hardware queues per priority level: on a queue shared with another stream everything
-    // behind the resident kernel would wait for ever.  The resident streams take the LOWEST priority level, which nothing else in this library uses.
-    int prio_lo = 0, prio_hi = 0; (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-    for (int form = 0; form < (s->max_items > 4 ? 2 : 1); ++form) {
-        ServeForm* f = new ServeForm(); f->d = d; f->mid = form == 1; f->n = lanes; s->forms.push_back(f);
-        f->busy.reset(new std::atomic<int>[lanes]); for (uint32_t i = 0; i < lanes; ++i) f->busy[i].store(0); f->seq.assign(lanes, 0u);
-        { std::lock_guard<std::mutex> lk(g_serve_mu); g_serve_forms.push_back(f); }
-        LaunchParams& p = f->p;
-        p.nq = lanes; p.k = k; p.m = m; p.how_many = how_many; p.flags = flags; p.max_len = f->mid ? F_MID_LMAX : 8u;
-        Geometry geo; if (make_geometry(d, ix, p, 0, geo) != SRN_OK) return undo(SRN_EINVAL, "the persistent latency path: no LDS geometry for these parameters");
-        const FastPlan plan = fast_plan(d, ix, p, geo, kn, false);
-        if (!plan.fast || (f->mid && !plan.mid_tier)) return undo(SRN_EINVAL, "the persistent latency path serves what the fast kernels serve (k <= 1536, m <= 2560 and <= m_index, how_many <= 64, complete lists)");
-        f->row_bytes = ((size_t)how_many * 16 + 63) / 64 * 64;
-        if (hipStreamCreateWithPriority(&f->st, hipStreamNonBlocking, prio_lo) != hipSuccess ||
-            hipHostMalloc((void**)&f->ctl, sizeof(ServeCtl) * lanes, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
-            hipHostMalloc((void**)&f->rows, f->row_bytes * lanes, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
-            hipHostGetDevicePointer((void**)&f->ctl_dev, f->ctl, 0) != hipSuccess || hipHostGetDevicePointer((void**)&f->rows_dev, f->rows, 0) != hipSuccess)
-            return undo(SRN_ENOMEM, "the persistent latency path: pinned control blocks");
-        memset(f->ctl, 0, sizeof(ServeCtl) * lanes); memset(f->rows, 0, f->row_bytes * lanes);
-        const uint32_t prep_stride = (uint32_t)(sizeof(PrepHead) + (size_t)p.max_len * sizeof(PrepItem));
-        const uint64_t big_entries = (uint64_t)lanes * 1024 + 4096;
-        if (hipMalloc((void**)&f->prep, (size_t)prep_stride * lanes + 256) != hipSuccess || hipMalloc((void**)&f->fin, (size_t)F_FIN_BYTES * lanes + 1024) != hipSuccess ||
-            hipMalloc((void**)&f->big, big_entries * 16 + (size_t)lanes * 4 + 64) != hipSuccess || hipMalloc((void**)&f->slow_list, ((size_t)lanes * 4 + 64) * 4) != hipSuccess ||
-            hipMalloc((void**)&f->slow_cnt, 32) != hipSuccess || hipMalloc((void**)&f->counts, (size_t)lanes * 4 + 64) != hipSuccess)
-            return undo(SRN_ENOMEM, "the persistent latency path: device scratch");
-        p.items_flat = nullptr; p.q_off = nullptr;
-        // a workgroup's row: ids at rows + q * how_many * 8 ... the kernels address rows as out_ids[q * how_many + rank]: ids of all workgroups, then scores of all
-        p.out_ids = (uint64_t*)f->rows_dev; p.out_scores = (double*)(f->rows_dev + (size_t)lanes * how_many * 8); p.out_counts = f->counts;
-        if ((size_t)lanes * how_many * 16 > f->row_bytes * lanes) return undo(SRN_EINVAL, "row buffer");
-        p.stats = nullptr; p.nb_rank = p.nb_num = p.nb_cnt = nullptr; p.phase_cycles = nullptr; p.prep = f->prep; p.prep_stride = prep_stride;
-        FastParams& fp = f->fp; fp = d->fast;
-        fp.slow_list = f->slow_list; fp.slow_cnt = f->slow_cnt; fp.nb = plan.nb_fast; fp.max_runs = plan.nb_fast; fp.fin = f->fin;
-        fp.big_arena = f->big; fp.big_list = (uint32_t*)(f->big + big_entries * 16); fp.big_ticket = (unsigned long long*)(f->slow_cnt + 2); fp.big_cap_entries = (uint32_t)big_entries;
-        fp.xchg = nullptr; fp.xchg_stride = 0; fp.q_base = 0; fp.order = nullptr; fp.mid_list = nullptr; fp.mid_cnt = nullptr; fp.bigq_list = nullptr; fp.bigq_cnt = nullptr; fp.long_list = nullptr; fp.long_cnt = nullptr;
-        fp.tiny_len = 0; fp.host_seq = 0; fp.host_words = nullptr; fp.serve = f->ctl_dev;
-    }
-    for (ServeForm* f : s->forms) { std::lock_guard<std::mutex> fl(f->mu); rc = form_launch(s, f); if (rc && rc != SRN_ESTATE) return undo(rc, last_error_string()); }   // (SRN_ESTATE: another thread is freeing device memory right now -- the first call that wants the form starts it)
-    d->serve.store(s);
-    return SRN_OK;
-}
-int device_serve_stats(DeviceState* d, uint64_t* served, uint64_t* not_served, uint64_t* launches, uint32_t* lanes) {
-    ServeState* s = d->serve.load();
-    if (served) *served = s ? s->served.load() : 0; if (not_served) *not_served = s ? s->not_served.load() : 0; if (launches) *launches = s ? s->launches.load() : 0;
-    uint32_t n = 0; if (s) for (ServeForm* f : s->forms) n += f->n;
-    if (lanes) *lanes = n;
-    return SRN_OK;
-}
-int device_serve_last_stamps(DeviceState* d, uint32_t* out4) {   // (measurement aid) 100 MHz ticks of the lean form's first workgroup's last session: waited | record written | answered
-    ServeState* s = d->serve.load();
-    if (!s || s->forms.empty()) return fail(SRN_ESTATE, "nothing resident");
-    for (int i = 0; i < 4; ++i) out4[i] = s->forms[0]->ctl[0].stamp[i];
-    return SRN_OK;
-}
-int device_serve_predict(DeviceState* d, const uint64_t* items, uint32_t len, uint32_t k, uint32_t m, uint32_t how_many, uint32_t flags, uint64_t* out_ids, double* out_scores, size_t* out_n) {
-    ServeState* s = d->serve.load(std::memory_order_acquire);
-    if (!s || k != s->k || m != s->m || how_many != s->how_many || flags != s->flags || len == 0 || len > s->max_items) return 1;
-    ServeForm* f = s->forms[len > 4 ? 1 : 0];
-    if (f->dead) return 1;
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        uint32_t li = f->n;
-        for (uint32_t i = 0; i < f->n; ++i) { int e = 0; if (f->busy[i].compare_exchange_strong(e, 1, std::memory_order_acquire)) { li = i; break; } }
-        if (li == f->n) { s->not_served.fetch_add(1); return 1; }   // (every resident workgroup of that form is taken: the launch path)
-        ServeCtl* c = &f->ctl[li];
-        if (!f->running || __atomic_load_n(&c->alive, __ATOMIC_ACQUIRE) == 0u) {   // parked (something freed device memory) or gone (idle): start the launch again, then look for a lane again
-            lane_unlock(f, li);
-            std::lock_guard<std::mutex> fl(f->mu);
-            if (f->dead.load()) { s->not_served.fetch_add(1); return 1; }   // (retired by srn_index_serve_stop in the meantime: never started again)
-            bool gone = !f->running; for (uint32_t i = 0; i < f->n && !gone; ++i) gone = __atomic_load_n(&f->ctl[i].alive, __ATOMIC_ACQUIRE) == 0u;
-            if (gone) { const int lrc = form_launch(s, f); if (lrc != SRN_OK) { if (lrc != SRN_ESTATE) f->dead = true; s->not_served.fetch_add(1); return 1; } }
-            continue;
-        }
-        uint32_t chk = 0; for (uint32_t i = 0; i < std::min<uint32_t>(len, 5u); ++i) chk ^= (uint32_t)items[i] ^ (uint32_t)(items[i] >> 32);
-        for (uint32_t i = 5; i < len; ++i) c->more[i - 5] = items[i];
-        for (uint32_t i = 0; i < std::min<uint32_t>(len, 5u); ++i) c->items[i] = items[i];
-        uint32_t seq = ++f->seq[li]; if (seq == 0u) seq = ++f->seq[li];
-        c->len = len; c->check = chk ^ seq ^ len;
-        __atomic_store_n(&c->seq, seq, __ATOMIC_RELEASE);
-        const auto t0 = std::chrono::steady_clock::now();
-        bool seen = false;
-        for (uint32_t spin = 0;; ++spin) {
-            if (__atomic_load_n(&c->done_seq, __ATOMIC_ACQUIRE) == seq) { seen = true; break; }
-            __builtin_ia32_pause();
-            if ((spin & 1023u) == 1023u) {
-                if (__atomic_load_n(&c->alive, __ATOMIC_ACQUIRE) == 0u) break;   // (it left between our look and our post: its idle timeout)
-                if (std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(500)) { f->dead = true; break; }   // (a fault: the form is not used again)
-            }
-        }
-        int ret = 1;
-        if (seen && __atomic_load_n(&c->status, __ATOMIC_RELAXED) == 0u) {
-            const uint32_t n = std::min<uint32_t>(__atomic_load_n(&c->count, __ATOMIC_RELAXED), how_many);
-            memcpy(out_ids, f->rows + ((size_t)li * how_many) * 8, (size_t)n * 8);
-            memcpy(out_scores, f->rows + ((size_t)f->n * how_many + (size_t)li * how_many) * 8, (size_t)n * 8);
-            *out_n = n; ret = 0;
-        }
-        lane_unlock(f, li);
-        (ret == 0 ? s->served : s->not_served).fetch_add(1);
-        return ret;
-    }
-    s->not_served.fetch_add(1);
-    return 1;
 }
 
 // the workspace's side stream (highest priority: a hardware queue of its own, dispatched ahead of the running call's persistent workgroups) and its events
@@ -819,6 +461,313 @@ static int ensure_side(Workspace* w) {
     return SRN_OK;
 }
 
+// ---- the fast sequence's buffers and their wiring (declared in srn_runtime.h: the latency paths use them too) ----
+static uint64_t fast_big_entries(size_t cap_q) { return std::min<uint64_t>(0x7FFFFFF0ull, (uint64_t)cap_q * 16 + 4096); }
+int reserve_fast(Workspace* w, size_t cap_q) {   // (all allocations of a call happen before its first launch)
+    { int rc = ensure_list(&w->slow_list, &w->slow_cap, cap_q, (cap_q * 4 + 64) * 4); if (rc) return rc; }   // (second to fourth part: the MID instantiation's list, its BIG form's, the LONG form's)
+    { int rc = ensure(&w->fin, &w->fin_bytes, cap_q * F_FIN_BYTES + 1024); if (rc) return rc; }   // one record per query for vmis_finish_kernel
+    return ensure(&w->big, &w->big_bytes, fast_big_entries(cap_q) * 16 + cap_q * 4 + 64);
+}
+FastBuffers fast_buffers(const Workspace* w, size_t cap_q) { return FastBuffers{w->slow_list, w->slow_cap, w->slow_cnt, w->fin, w->big, fast_big_entries(cap_q)}; }
+FastParams fast_params(const DeviceState* d, const FastBuffers& b, const FastPlan& plan, unsigned tiers) {
+    FastParams fp = d->fast; fp.slow_list = b.slow_list; fp.slow_cnt = b.slow_cnt; fp.nb = plan.nb_fast; fp.max_runs = plan.nb_fast; fp.fin = b.fin;
+    fp.big_arena = b.big; fp.big_list = b.big ? (uint32_t*)(b.big + b.big_entries * 16) : nullptr; fp.big_cap_entries = (uint32_t)b.big_entries;
+    fp.big_ticket = b.slow_cnt ? (unsigned long long*)(b.slow_cnt + SC_BIG_TICKET_LO) : nullptr;
+    fp.xchg = nullptr; fp.xchg_stride = 0; fp.q_base = 0; fp.order = nullptr;
+    fp.mid_list = (tiers & TIER_MID) ? slow_part(b.slow_list, b.slow_cap, SL_MID) : nullptr; fp.mid_cnt = fp.mid_list ? b.slow_cnt + SC_MID : nullptr;
+    fp.bigq_list = (tiers & TIER_BIGQ) ? slow_part(b.slow_list, b.slow_cap, SL_BIGQ) : nullptr; fp.bigq_cnt = fp.bigq_list ? b.slow_cnt + SC_BIGQ : nullptr;
+    fp.long_list = (tiers & TIER_LONG) ? slow_part(b.slow_list, b.slow_cap, SL_LONG) : nullptr; fp.long_cnt = fp.long_list ? b.slow_cnt + SC_LONG : nullptr;
+    return fp;
+}
+
+// ---- the batch launch sequence: plan -> reserve -> enqueue ----
+// What a call of device_predict will do, computed once from the index, the parameters, the knobs and the call's kind; nothing in it touches the device.
+struct LaunchPlan {
+    Knobs kn; Geometry geo;
+    bool retry = false;                                             // some query's session or item table may not fit LDS: the global-table pass stands behind the launch
+    KernelCfg cg{}; uint64_t g_stride = 0; int retry_blocks = 0;    // ... its geometry, a workgroup's arena, its grid
+    uint32_t grid = 0, grid_fast = 0, prep_stride = 0;              // the general kernel's grid, the fast kernel's
+    FastPlan fast;
+    bool resident = false, order_set2 = false;                      // SRN_FLAG_INPUTS_RESIDENT: the front on the side stream; on the second set of order buffers
+    bool ordered = false, dedup = false, prep_clears = false;
+};
+// the global-table pass: tables at twice the worst case in a global-memory arena per workgroup (cg: geo.c on entry), as many workgroups as 2 GB hold, at most one per CU
+static void global_tables_geometry(const DeviceState* d, const Geometry& geo, KernelCfg& cg, uint64_t& g_stride, int& retry_blocks) {
+    cg.sess_slots = (uint32_t)std::min<uint64_t>(1u << 30, std::max<uint64_t>(256, ceil_pow2(geo.need_sess * 2)));
+    cg.item_buckets = prime_at_least(geo.need_item / 2 + 64); cg.item_slots = cg.item_buckets * 4;
+    g_stride = std::max<uint64_t>((uint64_t)cg.sess_slots * geo.slot_bytes, (uint64_t)cg.hot_slots * 4 + (uint64_t)cg.sketch_slots * 4 + (uint64_t)cg.item_slots * 8);
+    g_stride = (g_stride + 255) / 256 * 256;
+    retry_blocks = (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)d->n_cu, (2ull << 30) / g_stride));
+}
+static LaunchPlan make_plan(const DeviceState* d, const FlatIndex& ix, const LaunchParams& p, const Geometry& geo, const ExtLists* ext, bool resident, const Workspace* w) {
+    LaunchPlan pl; pl.kn = knobs(); pl.geo = geo; pl.resident = resident;
+    const Knobs& kn = pl.kn; const KernelCfg& c = geo.c;
+    pl.retry = geo.sess_may_overflow || geo.item_may_overflow;
+    pl.cg = c;
+    if (pl.retry) global_tables_geometry(d, geo, pl.cg, pl.g_stride, pl.retry_blocks);
+    const uint32_t blocks_per_cu = std::max<uint32_t>(1, (160 * 1024) / (uint32_t)geo.lds);
+    // 16 workgroups per resident slot: the hardware hands out workgroups as slots free up, so smaller chunks of queries shorten the
+    // tail of a launch (measured on config 3: x1 10.62 ms, x4 10.50, x16 10.35, x32 10.32)
+    const uint32_t grid_mult = (uint32_t)kn.grid_mult;
+    pl.grid = (uint32_t)std::min<uint64_t>(p.nq, (uint64_t)d->n_cu * std::min<uint32_t>(blocks_per_cu, 2048 / kBlock) * grid_mult);
+    pl.prep_stride = prep_stride_of(p.max_len);
+    pl.fast = fast_plan(d, ix, p, geo, kn, ext != nullptr);
+    // The fast kernel's workgroups walk their queries in a pipeline (the next record is fetched during the current query), so they want ~12 queries each;
+    // beyond that, more and smaller workgroups shorten the tail of the launch.  Measured on config 3 (ms per launch at 8 / 16 / 32 / 64 resident sets): 2^20 queries
+    // 26.29 / 26.06 / 25.85 / 25.81; 2^18: - / 6.62 / 6.57 / 6.63; 2^16: - / 1.70 / 1.72 / 1.78.
+    const uint64_t res_wg = (uint64_t)d->n_cu * F_WG_PER_CU;
+    pl.grid_fast = kn.grid_mult_set ? (uint32_t)std::min<uint64_t>(p.nq, res_wg * grid_mult)
+                                    : (uint32_t)std::min<uint64_t>(p.nq, std::min<uint64_t>(res_wg * 64, std::max<uint64_t>(res_wg * 16, p.nq / 12)));
+    // the serving order: the batch sorted by each query's most popular item (keys from the prep kernel, one radix sort behind it)
+    pl.ordered = pl.fast.fast && !ext && kn.order_min > 0 && p.nq >= (uint32_t)kn.order_min;
+    // (one order per set of prep records: a resident call's prep kernel and sort run on the side stream while the previous call's kernels still read THEIR order)
+    pl.order_set2 = resident && (w->resident_calls & 1u) != 0u;
+    // ... and, in that order, only the first of the call's queries with one and the same item sequence (srn_dedup.hip, DESIGN.md 4.6); the others get its row at the end
+    pl.dedup = pl.ordered && !kn.no_dedup;
+    // The prep kernel clears the launch sequence's counters where it runs on this stream ahead of everything that uses them (two fill kernels otherwise: 6 us each)
+    pl.prep_clears = !ext && !resident;
+    return pl;
+}
+
+// every buffer of the call (all allocations of a call happen before its first launch; hipMalloc / hipFree synchronise the device)
+static int reserve_batch(Workspace* w, const LaunchPlan& pl, const LaunchParams& p, const ExtLists* ext, OrderBufs& ob) {
+    if (pl.retry) {
+        int rc = ensure_list(&w->retry_list, &w->retry_cap, p.nq, (size_t)p.nq * 4 + 64); if (rc) return rc;
+        rc = ensure(&w->gscratch, &w->gscratch_bytes, pl.g_stride * pl.retry_blocks); if (rc) return rc;
+    }
+    // per-block global copy of the neighbour list (walk B reads it after phase 4a has reused the LDS)
+    { int rc = ensure(&w->spill, &w->spill_bytes, (size_t)std::max<uint32_t>(pl.grid, (uint32_t)pl.retry_blocks) * p.k * pl.geo.slot_bytes); if (rc) return rc; }
+    if (!ext) { int rc = ensure(&w->prep, &w->prep_bytes, (size_t)p.nq * pl.prep_stride); if (rc) return rc; }
+    if (pl.resident) {   // a second set of prep records: call i + 1's prep kernel runs while call i's kernels still read theirs
+        int rc = ensure(&w->prep2, &w->prep2_bytes, (size_t)p.nq * pl.prep_stride); if (rc) return rc;
+        rc = ensure_side(w); if (rc) return rc;
+    }
+    if (pl.fast.fast) { int rc = reserve_fast(w, p.nq); if (rc) return rc; }
+    if (pl.ordered) return order_room(pl.order_set2 ? &w->order2 : &w->order, pl.order_set2 ? &w->order2_bytes : &w->order_bytes, p.nq, &ob, pl.dedup);
+    return SRN_OK;
+}
+
+// one call between its reserve and its last enqueue
+struct BatchCall {
+    DeviceState* d; Workspace* w; const LaunchPlan& pl; const ExtLists* ext; hipStream_t st; DeviceIndex di; LaunchParams p; OrderBufs ob;
+    hipEvent_t* ev = nullptr; bool timed = false, fork_retry = false;
+    bool sback_second = false;   // the item shard's wave-per-query back end ran with the fast kernel's back-end form behind it (its list is the MID tier's: srn_debug_last_mid_count reports it)
+    FastParams fp{};
+};
+
+// host-pointer calls: the staging buffer, p pointed at it, the inputs on their way
+static int stage_host_inputs(Workspace* w, hipStream_t st, LaunchParams& p, const uint64_t* h_items, const uint32_t* h_qoff, bool stats, bool nb) {
+    const size_t n_out = (size_t)p.nq * p.how_many, nitems = h_qoff[p.nq];
+    size_t off = 0; auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
+    const size_t o_items = take(nitems * 8), o_qoff = take(((size_t)p.nq + 1) * 4), o_ids = take(n_out * 8), o_sc = take(n_out * 8),
+                 o_cnt = take((size_t)p.nq * 4), o_st = take(stats ? (size_t)p.nq * 32 : 0),
+                 o_nr = take(nb ? (size_t)p.nq * p.k * 4 : 0), o_nn = take(nb ? (size_t)p.nq * p.k * 4 : 0),
+                 o_nc = take(nb ? (size_t)p.nq * 4 : 0);
+    int rc = ensure(&w->stage, &w->stage_bytes, off); if (rc) return rc;
+    char* s = w->stage;
+    p.items_flat = (const uint64_t*)(s + o_items); p.q_off = (const uint32_t*)(s + o_qoff);
+    p.out_ids = (uint64_t*)(s + o_ids); p.out_scores = (double*)(s + o_sc); p.out_counts = (uint32_t*)(s + o_cnt);
+    p.stats = stats ? (uint32_t*)(s + o_st) : nullptr;
+    p.nb_rank = nb ? (uint32_t*)(s + o_nr) : nullptr; p.nb_num = nb ? (uint32_t*)(s + o_nn) : nullptr;
+    p.nb_cnt = nb ? (uint32_t*)(s + o_nc) : nullptr;
+    HIP_TRY(hipMemsetAsync(p.out_ids, 0, n_out * 8, st));      // unused tail of each row reads as 0
+    HIP_TRY(hipMemsetAsync(p.out_scores, 0, n_out * 8, st));
+    HIP_TRY(hipMemcpyAsync((void*)p.items_flat, h_items, nitems * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync((void*)p.q_off, h_qoff, ((size_t)p.nq + 1) * 4, hipMemcpyHostToDevice, st));
+    return SRN_OK;
+}
+// ... and the results back, then the wait for them
+static int fetch_host_outputs(const BatchCall& c, uint64_t* h_ids, double* h_scores, uint32_t* h_counts, uint32_t* h_stats, uint32_t* h_nb_rank, uint32_t* h_nb_num, uint32_t* h_nb_cnt) {
+    const LaunchParams& p = c.p; hipStream_t st = c.st; const size_t n_out = (size_t)p.nq * p.how_many;
+    HIP_TRY(hipMemcpyAsync(h_ids, p.out_ids, n_out * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(h_scores, p.out_scores, n_out * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(h_counts, p.out_counts, (size_t)p.nq * 4, hipMemcpyDeviceToHost, st));
+    if (h_stats) HIP_TRY(hipMemcpyAsync(h_stats, p.stats, (size_t)p.nq * 32, hipMemcpyDeviceToHost, st));
+    if (h_nb_rank) {
+        HIP_TRY(hipMemcpyAsync(h_nb_rank, p.nb_rank, (size_t)p.nq * p.k * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(h_nb_num, p.nb_num, (size_t)p.nq * p.k * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(h_nb_cnt, p.nb_cnt, (size_t)p.nq * 4, hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    return SRN_OK;
+}
+
+// The front of the sequence on stream `s` -- the prep kernel into the record set `rec`, the grouping of equal queries, the sort of the order keys.  On the caller's own
+// stream (prep_clears) the prep kernel also clears the sequence's counters and the grouping pass writes the merged rows' count words; a resident call runs it on the side stream.
+static int enqueue_front(BatchCall& c, hipStream_t s, char* rec) {
+    const LaunchParams& p = c.p; const LaunchPlan& pl = c.pl; OrderBufs& ob = c.ob; Workspace* w = c.w;
+    HIP_TRY(launch_prep(s, c.di, p.items_flat, p.q_off, p.nq, p.m, p.max_len, rec, pl.prep_stride, pl.prep_clears && pl.fast.fast ? w->slow_cnt : nullptr,
+                        pl.prep_clears && pl.retry ? w->retry_cnt : nullptr, nullptr, 0, ob.keys_in));
+    if (pl.dedup) {   // (a resident call: the count word of a merged row is written on the caller's stream -- the previous call's kernels may still be writing these very buffers)
+        HIP_TRY(hipMemsetAsync(ob.dd.slots, 0xFF, (size_t)ob.dd.n_slots * 8, s));
+        HIP_TRY(launch_dedup_group(s, p.items_flat, p.q_off, p.nq, ob.dd.slots, ob.dd.slot_min, ob.dd.n_slots, (uint32_t)pl.kn.dedup_hash_bits, ob.dd.rep, ob.keys_in, pl.prep_clears ? p.out_counts : nullptr, ob.dd.n_dup));
+    }
+    if (pl.ordered) HIP_TRY(sort_order_keys(s, ob.keys_in, ob.keys_out, p.nq, ob.temp, &ob.temp_bytes));
+    c.p.prep = rec; c.p.prep_stride = pl.prep_stride;
+    return SRN_OK;
+}
+// a resident call's front on the side stream: behind the call that used this set of records two calls ago, beside the previous call's kernels
+static int enqueue_front_resident(BatchCall& c) {
+    Workspace* w = c.w; hipStream_t st = c.st;
+    const int par = (int)(w->resident_calls & 1u);
+    // (ev_done[set] = the end of the LAST call that read record set `set`, resident or not: a non-resident device-pointer call on this stream reads w->prep too)
+    if (!w->rec_used[par] && w->calls > 0) { HIP_TRY(hipEventRecord(w->ev_done[par], st)); w->rec_used[par] = true; }   // (earlier calls of this workspace that left no event: everything enqueued so far)
+    if (w->rec_used[par]) HIP_TRY(hipStreamWaitEvent(w->side, w->ev_done[par], 0));
+    { int rc = enqueue_front(c, w->side, par ? w->prep2 : w->prep); if (rc) return rc; }
+    HIP_TRY(hipEventRecord(w->ev_prep[par], w->side));
+    HIP_TRY(hipStreamWaitEvent(st, w->ev_prep[par], 0));
+    if (c.pl.dedup) HIP_TRY(launch_dedup_mark(st, c.p.nq, c.ob.dd.rep, c.p.out_counts));
+    return SRN_OK;
+}
+// The shard group's neighbours pipeline, FRONT: find_neighbors alone for the queries [q_lo, nq) of the batch this rank fronts -- the fast kernel's front end against
+// the replicated posting lists, neighbour lists into the exchange buffer.  Nothing else of the launch sequence runs (the back end of every rank follows the all-gather).
+static int enqueue_shard_front(BatchCall& c) {
+    const ExtLists* ext = c.ext; LaunchParams& p = c.p;
+    if (ext->q_lo >= p.nq) return SRN_OK;
+    p.prep = ext->prep; p.prep_stride = c.pl.prep_stride;
+    FastParams fp = fast_params(c.d, FastBuffers{}, c.pl.fast);
+    fp.xchg = ext->xchg; fp.xchg_stride = ext->xchg_stride; fp.q_base = ext->q_lo;
+    const uint64_t cnt = p.nq - ext->q_lo, res_wg = (uint64_t)c.d->n_cu * F_WG_PER_CU;
+    const uint32_t grid_front = (uint32_t)std::min<uint64_t>(cnt, std::min<uint64_t>(res_wg * 64, std::max<uint64_t>(res_wg * 16, cnt / 12)));
+    HIP_TRY(launch_fast(FastForm::Front, dim3(grid_front), c.st, c.di, p, fp, c.pl.kn.debug));
+    return SRN_OK;
+}
+// the item shard's own back end (srn_sback.hip): one wave per query, 12 per CU; a persistent grid of a few waves per resident slot
+static int enqueue_shard_back(BatchCall& c) {
+    DeviceState* d = c.d; Workspace* w = c.w; const ExtLists* ext = c.ext; const LaunchParams& p = c.p; const Knobs& kn = c.pl.kn; FastParams& fp = c.fp;
+    SBackParams sbp = d->sback;
+    // the streaming form where the shard holds its fragments in the posting order of the very lists the records were written against (9 waves per CU: 16.8 KB each)
+    const bool stream = ext->positions;
+    if (stream && !(d->sb_frag_post && d->sb_post_for == ext->post_rank)) return fail(SRN_ESTATE, "the batch's neighbours came as posting positions, but this shard does not hold its fragments in posting order");
+    const uint64_t slots = (uint64_t)d->n_cu * (stream ? 9 : 12);
+    uint32_t grid_b = (uint32_t)std::min<uint64_t>(p.nq, slots * (kn.grid_mult_set ? (uint32_t)kn.grid_mult : stream ? 4 : 16));   // (gather form, round 6: 1 / 2 / 4 / 8 / 16 / 32 waves per slot = 1.295 / 1.247 / 1.191 / 1.148 / 1.115 / 1.114 ms -- the tail of a persistent grid costs more than the first query of a wave, which has no prefetched record)
+    if (fp.order) grid_b = std::max<uint32_t>(8u, grid_b / 8u * 8u);
+    if (stream) {
+        int rc = ensure(&w->sb_scr, &w->sb_scr_bytes, (size_t)grid_b * shard_back_scratch_words() * 4); if (rc) return rc;
+        sbp.frag_post = (const uint2*)d->sb_frag_post; sbp.post_rank = ext->post_rank; sbp.scr = (uint32_t*)w->sb_scr;
+    }
+    const bool second = !kn.no_sback_second && !stream; c.sback_second = second;   // (the streaming form's records are not neighbour slots)  // what outgrows the wave's room: the round-4 back end (eight waves per query) over a list, before the general kernel
+    if (second) { fp.mid_list = slow_part(w->slow_list, w->slow_cap, SL_MID); fp.mid_cnt = w->slow_cnt + SC_MID; }
+    HIP_TRY(launch_shard_back(dim3(grid_b), c.st, c.di, p, fp, sbp, kn.debug));
+    d->sback_launches.fetch_add(1, std::memory_order_relaxed);
+    if (second) {
+        FastParams fl = fp; fl.order = nullptr;
+        HIP_TRY(launch_fast(FastForm::Back, dim3((uint32_t)std::min<uint64_t>(p.nq, (uint64_t)d->n_cu * F_WG_PER_CU * 4)), c.st, c.di, p, fl, kn.debug));
+        fp.mid_list = nullptr; fp.mid_cnt = nullptr;
+    }
+    return SRN_OK;
+}
+// The fast kernel (srn_fast.hip) serves the common query shape; what it cannot take -- decided per query, on the device -- is queued on slow_list and served by the
+// general kernel right behind it.  Here: its lean form (or the shard group's back end), then MID, BIG and LONG over what was listed for them.
+static int enqueue_fast_tiers(BatchCall& c) {
+    DeviceState* d = c.d; Workspace* w = c.w; const ExtLists* ext = c.ext; const LaunchParams& p = c.p; const LaunchPlan& pl = c.pl; const Knobs& kn = pl.kn; hipStream_t st = c.st;
+    w->cnt_dirty = true;   // (the latency path's fused launch wants the counters at 0 and clears them itself after a sequence like this one)
+    if (!pl.prep_clears) HIP_TRY(hipMemsetAsync(w->slow_cnt, 0, sizeof(SlowCntBlock), st));
+    // (round 5: the BIG form also without a MID tier -- it takes the lean shape's oversized queries of the headline batches; not over an item shard's fragments)
+    const bool big_tier = !kn.no_big && !ext && d->di.row_frag == 0u;
+    FastParams& fp = c.fp;
+    fp = fast_params(d, w, pl.fast, p.nq, (pl.fast.mid_tier ? TIER_MID : 0u) | (big_tier ? TIER_BIGQ : 0u) | (pl.fast.long_tier ? TIER_LONG : 0u));
+    const bool back = ext && ext->mode == 2;   // neighbour lists from the exchange buffer (any rank's front end), this shard's rows
+    if (back) { fp.xchg = ext->xchg; fp.xchg_stride = ext->xchg_stride; }
+    fp.order = pl.ordered ? c.ob.keys_out : back ? ext->order : nullptr;
+    fp.order_dups = pl.dedup ? c.ob.dd.n_dup : nullptr;
+    const uint32_t grid_fo = fp.order ? std::max<uint32_t>(8u, pl.grid_fast / 8u * 8u) : pl.grid_fast;   // (an ordered launch walks an eighth of the order per XCD: the grid is a multiple of 8)
+    if (back && d->sback.frag8 && !kn.no_sback && p.max_len <= 8) { int rc = enqueue_shard_back(c); if (rc) return rc; }
+    else HIP_TRY(launch_fast(back ? FastForm::Back : FastForm::Lean, dim3(grid_fo), st, c.di, p, fp, kn.debug));
+    if (c.timed) HIP_TRY(hipEventRecord(c.ev[4], st));
+    const uint64_t res_wg = (uint64_t)d->n_cu * F_WG_PER_CU;
+    // The MID instantiation over what the lean one listed for it (sessions of <= 10 items, <= 8 lists); what it cannot take either joins slow_list.  The list's length
+    // is known on the device only: a fixed grid, workgroups beyond the list leave at once.
+    if (pl.fast.mid_tier) HIP_TRY(launch_fast(FastForm::Mid, dim3((uint32_t)std::min<uint64_t>(p.nq, res_wg * 8)), st, c.di, p, fp, kn.debug));
+    // ... and MID's BIG form (80 KB of LDS, two workgroups per CU) over what MID passed on only for want of merge-buffer room
+    if (fp.bigq_list) HIP_TRY(launch_fast(FastForm::Big, dim3((uint32_t)std::min<uint64_t>(p.nq, (uint64_t)d->n_cu * 2 * 4)), st, c.di, p, fp, kn.debug));
+    // ... and the LONG form over the sessions of 11..20 items the lean instantiation listed for it
+    if (fp.long_list) HIP_TRY(launch_fast(FastForm::Long, dim3((uint32_t)std::min<uint64_t>(p.nq, (uint64_t)d->n_cu * 2 * 4)), st, c.di, p, fp, kn.debug));
+    return SRN_OK;
+}
+// the general kernel: over what the fast sequence handed to it, or over the whole batch
+static int enqueue_general(const BatchCall& c) {
+    const LaunchPlan& pl = c.pl; Workspace* w = c.w;
+    PredictLaunch a; a.masks = pl.geo.masks; a.slot64 = pl.geo.slot64; a.spill = w->spill; a.retry_list = w->retry_list; a.retry_cnt = w->retry_cnt;
+    if (pl.fast.fast) { a.qlist = w->slow_list; a.qn = w->slow_cnt; }
+    HIP_TRY(launch_predict(a, dim3(pl.grid), pl.geo.lds, c.st, c.di, c.p, pl.geo.c));
+    return SRN_OK;
+}
+// the global-table pass over what the general kernel listed: one workgroup per arena, tables in global memory
+static int enqueue_global_pass(const BatchCall& c, hipStream_t s) {
+    const LaunchPlan& pl = c.pl; Workspace* w = c.w;
+    PredictLaunch a; a.masks = pl.geo.masks; a.slot64 = pl.geo.slot64; a.global_tables = true; a.qlist = w->retry_list; a.qn = w->retry_cnt;
+    a.gscratch = w->gscratch; a.gstride = pl.g_stride; a.spill = w->spill;
+    HIP_TRY(launch_predict(a, dim3(pl.retry_blocks), pl.geo.c.off_a, s, c.di, c.p, pl.cg));
+    return SRN_OK;
+}
+// the fast sequence behind its tiers: the general kernel, the global-table pass where it is forked, the two finish kernels
+static int enqueue_fast_finish(const BatchCall& c) {
+    Workspace* w = c.w; const LaunchParams& p = c.p; hipStream_t st = c.st;
+    { int rc = enqueue_general(c); if (rc) return rc; }
+    if (c.fork_retry) {   // the global-table pass beside the finish kernels (they touch disjoint rows: a finish kernel only completes rows flagged by the fast kernel)
+        HIP_TRY(hipEventRecord(w->ev_fork, st)); HIP_TRY(hipStreamWaitEvent(w->side, w->ev_fork, 0));
+        { int rc = enqueue_global_pass(c, w->side); if (rc) return rc; }
+        HIP_TRY(hipEventRecord(w->ev_join, w->side));
+    }
+    HIP_TRY(launch_finish(st, c.di, c.fp, p.out_ids, p.out_scores, p.out_counts, p.nq, p.how_many));
+    // (it also writes the call's two counters -- global-table queries, handed-over queries; both final once the general kernel is done -- into the pinned words)
+    HIP_TRY(launch_finish_big(st, c.di, c.fp, p.out_ids, p.out_scores, p.out_counts, p.how_many, (uint32_t)std::min<uint64_t>(p.nq, (uint64_t)c.d->n_cu * 16),
+                              c.pl.retry ? w->retry_cnt : nullptr, w->slow_cnt, w->h_retry_dev));
+    return SRN_OK;
+}
+// behind the kernels that serve: the merged queries' rows, the global-table pass (joined, or in line), the call's events and what the next call and the getters read
+static int enqueue_tail(BatchCall& c) {
+    Workspace* w = c.w; const LaunchParams& p = c.p; const LaunchPlan& pl = c.pl; hipStream_t st = c.st; const OrderBufs& ob = c.ob;
+    const bool fast = pl.fast.fast;
+    // the merged queries' rows: behind every kernel that can write a representative's row -- the global-table pass included, where the launch has one
+    const bool fill_late = pl.dedup && pl.retry;
+    if (pl.dedup && !fill_late) HIP_TRY(launch_dedup_fill(st, p.nq, ob.dd.rep, p.out_ids, p.out_scores, p.out_counts, p.how_many, ob.dd.n_dup, w->h_retry_dev + HW_MERGED));
+    if (c.timed) HIP_TRY(hipEventRecord(c.ev[1], st));
+    if (c.fork_retry) HIP_TRY(hipStreamWaitEvent(st, w->ev_join, 0));
+    else if (pl.retry) {
+        { int rc = enqueue_global_pass(c, st); if (rc) return rc; }
+        if (!fast) HIP_TRY(hipMemcpyAsync(w->h_retry + HW_GLOBAL, w->retry_cnt, 4, hipMemcpyDeviceToHost, st));   // (fast: vmis_finish_big_kernel wrote both words.  Not fast: last_fast = false says
+                                                                                                                //  "all of last_nq" -- no host write into a pinned word that an earlier call may still be writing)
+    }
+    if (fill_late) HIP_TRY(launch_dedup_fill(st, p.nq, ob.dd.rep, p.out_ids, p.out_scores, p.out_counts, p.how_many, ob.dd.n_dup, w->h_retry_dev + HW_MERGED));
+    HIP_TRY(hipEventRecord(c.ev[2], st));
+    if (pl.resident) { const int par = (int)(w->resident_calls & 1u); HIP_TRY(hipEventRecord(w->ev_done[par], st)); w->rec_used[par] = true; ++w->resident_calls; }
+    else if (!c.ext && w->side) { HIP_TRY(hipEventRecord(w->ev_done[0], st)); w->rec_used[0] = true; }   // (a workspace that has served resident calls: the next one's side-stream prep must not overwrite w->prep under this call's kernels)
+    ++w->calls; w->last_retry = pl.retry ? 1 : 0; w->last_nq = p.nq; w->last_fast = fast; w->last_mid = fast && (pl.fast.mid_tier || c.sback_second); w->last_dedup = pl.dedup; w->last_untimed = false;
+    if (pl.retry) w->h_retry_valid = true;   // (from now on the pinned counter holds a finished call's count -- or is being overwritten by a newer one)
+    return SRN_OK;
+}
+// everything a call enqueues between its inputs and its results
+static int enqueue_batch(BatchCall& c, bool on_device) {
+    Workspace* w = c.w; const LaunchPlan& pl = c.pl; hipStream_t st = c.st; const bool fast = pl.fast.fast;
+    if (pl.retry && !pl.prep_clears) HIP_TRY(hipMemsetAsync(w->retry_cnt, 0, 4, st));
+    c.ev = w->ev[w->calls % Workspace::RING];
+    // Per-kernel events only when someone asked for kernel times: an event between two kernels idles the stream for ~6 us (three of them: 18 us of a 4 096-query batch's 250)
+    c.timed = c.d->timing.load(std::memory_order_relaxed);
+    w->ring_timed[w->calls % Workspace::RING] = c.timed;
+    if (c.timed) HIP_TRY(hipEventRecord(c.ev[0], st));
+    if (c.ext) { c.p.prep = c.ext->prep; c.p.prep_stride = pl.prep_stride; }
+    else { int rc = pl.resident ? enqueue_front_resident(c) : enqueue_front(c, st, w->prep); if (rc) return rc; }
+    if (c.timed) HIP_TRY(hipEventRecord(c.ev[3], st));
+    // The global-table retry pass serves a handful of queries with one workgroup each, ~0.3 ms behind everything else on config 5 (VERDICT r2 weak 6).  Where earlier
+    // calls on this workspace did retry queries (the pinned counter of the last finished call says so: a hint, read without synchronising) it is forked onto the side
+    // stream right behind the general kernel and runs beside the finish kernels; where nothing is ever retried (configs 2-4) the two extra events would cost more
+    // than the empty pass.
+    // (Tried in round 3 and dropped: the general kernel over the handed-over queries + the global-table pass on the side stream, beside the two finish kernels -- 38 + 4 us
+    //  against 17 + 10 us at 4 096 queries.  4 096 / 65 536 / 2^20 queries: 0.220 / 1.759 / 25.28 ms forked, 0.215 / 1.759 / 25.25 ms in line.)
+    c.fork_retry = fast && pl.retry && on_device && *(volatile uint32_t*)(w->h_retry + HW_GLOBAL) != 0u && w->h_retry_valid;
+    if (c.fork_retry) { int rc = ensure_side(w); if (rc) return rc; }
+    if (fast) {
+        int rc = enqueue_fast_tiers(c); if (rc) return rc;
+        rc = enqueue_fast_finish(c); if (rc) return rc;
+    } else {
+        int rc = enqueue_general(c); if (rc) return rc;
+        if (c.timed) HIP_TRY(hipEventRecord(c.ev[4], st));
+    }
+    return enqueue_tail(c);
+}
+
 int device_predict(DeviceState* d, const FlatIndex& ix, const LaunchParams& p_in, bool on_device, void* user_stream,
                    const uint64_t* h_items, const uint32_t* h_qoff, uint64_t* h_ids, double* h_scores, uint32_t* h_counts,
                    uint32_t* h_stats, uint32_t* h_nb_rank, uint32_t* h_nb_num, uint32_t* h_nb_cnt, const ExtLists* ext, bool reserve_only, bool blocking_wait) {
@@ -826,7 +775,7 @@ int device_predict(DeviceState* d, const FlatIndex& ix, const LaunchParams& p_in
     LaunchParams p = p_in;
     if (p.nq == 0) return SRN_OK;
     // SRN_FLAG_INPUTS_RESIDENT (device-pointer calls): the query buffers are complete in device memory at call time, so the prep kernel of THIS call may run on a side
-    // stream while the previous call's kernels still occupy the caller's stream (see below); the kernels never see the flag
+    // stream while the previous call's kernels still occupy the caller's stream (enqueue_front_resident); the kernels never see the flag
     const bool resident = on_device && !ext && (p.flags & SRN_FLAG_INPUTS_RESIDENT) != 0u;
     p.flags &= ~(unsigned)SRN_FLAG_INPUTS_RESIDENT;
     // item-sharded index, lists mode (device_shard_lists_*): the posting lists of ALL shards for this batch arrive in one gathered
@@ -838,16 +787,10 @@ int device_predict(DeviceState* d, const FlatIndex& ix, const LaunchParams& p_in
     if (!w) return fail(SRN_EHIP, "cannot create HIP stream / events");
     struct Rel { DeviceState* d; Workspace* w; bool b; ~Rel() { if (w) ws_release(d, w, b); } } rel{d, w, on_device};
     hipStream_t st = on_device ? (hipStream_t)user_stream : w->stream;
-
-    // ---- geometry ----------------------------------------------------------------------
     Geometry geo; { int rc = make_geometry(d, ix, p, 0, geo); if (rc) return rc; }
-    const KernelCfg& c = geo.c; const bool slot64 = geo.slot64; const uint32_t slot_bytes = geo.slot_bytes; const size_t lds = geo.lds;
-    const uint64_t need_sess = geo.need_sess, need_item = geo.need_item;
-    const bool may_overflow = geo.sess_may_overflow || geo.item_may_overflow;
 
     if (!on_device && !reserve_only && !h_stats && !h_nb_rank) {
-        const Knobs kn0 = knobs();
-        if (p.nq <= (uint32_t)kn0.tiny_max && !d->phase_on && !kn0.dense) {
+        if (p.nq <= (uint32_t)knobs().tiny_max && !d->phase_on) {
             const int rc = device_predict_tiny(d, ix, w, geo, p, h_items, h_qoff, h_ids, h_scores, h_counts, blocking_wait);
             if (rc != 1) return rc;   // (1: some query needs the global-table pass -- the paths below have it)
         }
@@ -856,250 +799,17 @@ int device_predict(DeviceState* d, const FlatIndex& ix, const LaunchParams& p_in
         ws_release(d, w, false); rel.w = nullptr;
         return device_predict_host_pipelined(d, ix, p, h_items, h_qoff, h_ids, h_scores, h_counts);
     }
-    // ---- buffers -----------------------------------------------------------------------
-    const size_t n_out = (size_t)p.nq * p.how_many;
-    size_t nitems = 0;
-    if (!on_device) {
-        nitems = h_qoff[p.nq];
-        size_t off = 0; auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
-        const size_t o_items = take(nitems * 8), o_qoff = take(((size_t)p.nq + 1) * 4), o_ids = take(n_out * 8), o_sc = take(n_out * 8),
-                     o_cnt = take((size_t)p.nq * 4), o_st = take(h_stats ? (size_t)p.nq * 32 : 0),
-                     o_nr = take(h_nb_rank ? (size_t)p.nq * p.k * 4 : 0), o_nn = take(h_nb_rank ? (size_t)p.nq * p.k * 4 : 0),
-                     o_nc = take(h_nb_rank ? (size_t)p.nq * 4 : 0);
-        int rc = ensure(&w->stage, &w->stage_bytes, off); if (rc) return rc;
-        char* s = w->stage;
-        p.items_flat = (const uint64_t*)(s + o_items); p.q_off = (const uint32_t*)(s + o_qoff);
-        p.out_ids = (uint64_t*)(s + o_ids); p.out_scores = (double*)(s + o_sc); p.out_counts = (uint32_t*)(s + o_cnt);
-        p.stats = h_stats ? (uint32_t*)(s + o_st) : nullptr;
-        p.nb_rank = h_nb_rank ? (uint32_t*)(s + o_nr) : nullptr; p.nb_num = h_nb_rank ? (uint32_t*)(s + o_nn) : nullptr;
-        p.nb_cnt = h_nb_rank ? (uint32_t*)(s + o_nc) : nullptr;
-        HIP_TRY(hipMemsetAsync(p.out_ids, 0, n_out * 8, st));      // unused tail of each row reads as 0
-        HIP_TRY(hipMemsetAsync(p.out_scores, 0, n_out * 8, st));
-        HIP_TRY(hipMemcpyAsync((void*)p.items_flat, h_items, nitems * 8, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync((void*)p.q_off, h_qoff, ((size_t)p.nq + 1) * 4, hipMemcpyHostToDevice, st));
-    }
-    // Opt-in (SRN_DENSE=1): THREE workgroups per CU -- the 80-VGPR build of the kernel with a 52 KB LDS geometry -- and what that
-    // geometry cannot hold goes through the normal one (second tier) before the global-table pass.  Measured on config 3 / 4:
-    // +8.6 % / +4.7 % queries/s (-1 % / -2 % with the end-of-round kernel), but the 80-VGPR build's register spills double the memory traffic (14.5 -> 31.8 GB per launch), so it
-    // stays off until the build fits without spilling.
-    const Knobs kn = knobs();
-    Geometry g3; bool dense = !slot64 && kn.dense && !kn.lds_budget_kb;
-    if (dense && (make_geometry(d, ix, p, 0, g3, 52 * 1024) != SRN_OK || g3.slot64 || g3.masks != geo.masks)) dense = false;
-    uint64_t g_stride = 0; int retry_blocks = 0;
-    KernelCfg cg = c;
-    if (may_overflow || dense) {
-        if (w->retry_cap < p.nq) { if (w->retry_list) HIP_TRY(hipFree(w->retry_list)); w->retry_list = nullptr; w->retry_cap = 0;
-            HIP_TRY(hipMalloc((void**)&w->retry_list, (size_t)p.nq * 4 + 64)); w->retry_cap = p.nq; }
-        cg.sess_slots = (uint32_t)std::min<uint64_t>(1u << 30, std::max<uint64_t>(256, ceil_pow2(need_sess * 2)));
-        cg.item_buckets = prime_at_least(need_item / 2 + 64); cg.item_slots = cg.item_buckets * 4;
-        g_stride = std::max<uint64_t>((uint64_t)cg.sess_slots * slot_bytes, (uint64_t)cg.hot_slots * 4 + (uint64_t)cg.sketch_slots * 4 + (uint64_t)cg.item_slots * 8);
-        g_stride = (g_stride + 255) / 256 * 256;
-        retry_blocks = (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)d->n_cu, (2ull << 30) / g_stride));
-        int rc = ensure(&w->gscratch, &w->gscratch_bytes, g_stride * retry_blocks); if (rc) return rc;
-        if (dense) {
-            if (w->retry_cap2 < p.nq) { if (w->retry_list2) HIP_TRY(hipFree(w->retry_list2)); w->retry_list2 = nullptr; w->retry_cap2 = 0;
-                HIP_TRY(hipMalloc((void**)&w->retry_list2, (size_t)p.nq * 4 + 64)); w->retry_cap2 = p.nq; }
-        }
-    }
-
-    // ---- launches ----------------------------------------------------------------------
-    const uint32_t blocks_per_cu = std::max<uint32_t>(1, (160 * 1024) / (uint32_t)lds);
-    // 16 workgroups per resident slot: the hardware hands out workgroups as slots free up, so smaller chunks of queries shorten the
-    // tail of a launch (measured on config 3: x1 10.62 ms, x4 10.50, x16 10.35, x32 10.32)
-    const uint32_t grid_mult = (uint32_t)kn.grid_mult;
-    const uint32_t grid = (uint32_t)std::min<uint64_t>(p.nq, (uint64_t)d->n_cu * std::min<uint32_t>(blocks_per_cu, 2048 / kBlock) * grid_mult);
-    // per-block global copy of the neighbour list (walk B reads it after phase 4a has reused the LDS)
-    const uint32_t grid3 = dense ? (uint32_t)std::min<uint64_t>(p.nq, (uint64_t)d->n_cu * std::min<uint32_t>(std::max<uint32_t>(1, (160 * 1024) / (uint32_t)g3.lds), 2048 / kBlock) * grid_mult) : 0u;
-    { int rc = ensure(&w->spill, &w->spill_bytes, (size_t)std::max<uint32_t>(std::max(grid, grid3), (uint32_t)retry_blocks) * p.k * slot_bytes); if (rc) return rc; }
-    char* spill = w->spill;
-    const uint32_t prep_stride = (uint32_t)(sizeof(PrepHead) + (size_t)p.max_len * sizeof(PrepItem));
-    if (!ext) { int rc = ensure(&w->prep, &w->prep_bytes, (size_t)p.nq * prep_stride); if (rc) return rc; }
-    if (resident) {   // a second set of prep records: call i + 1's prep kernel runs while call i's kernels still read theirs
-        int rc = ensure(&w->prep2, &w->prep2_bytes, (size_t)p.nq * prep_stride); if (rc) return rc;
-        rc = ensure_side(w); if (rc) return rc;
-    }
-    const FastPlan plan = fast_plan(d, ix, p, geo, kn, ext != nullptr);
-    const uint32_t nb_fast = plan.nb_fast; const bool mid_tier = plan.mid_tier, fast = plan.fast;
-    bool sback_second = false;   // the item shard's wave-per-query back end ran with the fast kernel's back-end form behind it (its list is the MID tier's: srn_debug_last_mid_count reports it)
-    if (fast) {   // (all allocations of a call happen before its first launch)
-        if (w->slow_cap < p.nq) { if (w->slow_list) HIP_TRY(hipFree(w->slow_list)); w->slow_list = nullptr; w->slow_cap = 0;
-            HIP_TRY(hipMalloc((void**)&w->slow_list, ((size_t)p.nq * 4 + 64) * 4)); w->slow_cap = p.nq; }   // (second to fourth part: the MID instantiation's list, its BIG form's, the LONG form's)
-        { int rc = ensure(&w->fin, &w->fin_bytes, (size_t)p.nq * F_FIN_BYTES + 1024); if (rc) return rc; }   // one record per query for vmis_finish_kernel
-        const uint64_t big_entries = std::min<uint64_t>(0x7FFFFFF0ull, (uint64_t)p.nq * 16 + 4096);
-        { int rc = ensure(&w->big, &w->big_bytes, big_entries * 16 + (size_t)p.nq * 4 + 64); if (rc) return rc; }
-    }
-    // the serving order: the batch sorted by each query's most popular item (keys from the prep kernel, one radix sort behind it)
-    const bool ordered = fast && !ext && kn.order_min > 0 && p.nq >= (uint32_t)kn.order_min;
-    unsigned long long *okeys_in = nullptr, *okeys_out = nullptr; void* otemp = nullptr; size_t otemp_bytes = 0;
-    // (one order per set of prep records: a resident call's prep kernel and sort run on the side stream while the previous call's kernels still read THEIR order)
-    const bool order_set2 = resident && (w->resident_calls & 1u) != 0u;
-    // ... and, in that order, only the first of the call's queries with one and the same item sequence (srn_dedup.hip, DESIGN.md 4.6); the others get its row at the end
-    const bool dedup = ordered && !kn.no_dedup;
-    DedupRoom dd;
-    if (ordered) { int rc = order_room(order_set2 ? &w->order2 : &w->order, order_set2 ? &w->order2_bytes : &w->order_bytes, p.nq, &okeys_in, &okeys_out, &otemp, &otemp_bytes, dedup ? &dd : nullptr); if (rc) return rc; }
+    // ---- plan -> reserve -> enqueue ----
+    if (!on_device) { int rc = stage_host_inputs(w, st, p, h_items, h_qoff, h_stats != nullptr, h_nb_rank != nullptr); if (rc) return rc; }   // (p.stats / p.nb_rank decide the plan)
+    const LaunchPlan pl = make_plan(d, ix, p, geo, ext, resident, w);
+    BatchCall c{d, w, pl, ext, st, di, p};
+    { int rc = reserve_batch(w, pl, c.p, ext, c.ob); if (rc) return rc; }
     if (reserve_only) return SRN_OK;   // (srn_index_reserve: the workspace is sized, nothing was enqueued)
-    if (ext && ext->mode == 1) {
-        // The shard group's neighbours pipeline, FRONT: find_neighbors alone for the queries [q_lo, nq) of the batch this rank fronts -- the fast kernel's front end against
-        // the replicated posting lists, neighbour lists into the exchange buffer.  Nothing else of the launch sequence runs (the back end of every rank follows the all-gather).
-        if (!fast) return fail(SRN_EINVAL, "the neighbours pipeline needs the fast kernel's query shape (device_fast_eligible)");
-        if (ext->prep_stride != prep_stride) return fail(SRN_EINVAL, "prep record stride mismatch");
-        if (ext->q_lo >= p.nq) return SRN_OK;
-        p.prep = ext->prep; p.prep_stride = prep_stride;
-        FastParams fp = d->fast; fp.nb = nb_fast; fp.max_runs = nb_fast; fp.slow_list = nullptr; fp.slow_cnt = nullptr; fp.fin = nullptr; fp.mid_list = nullptr; fp.mid_cnt = nullptr; fp.bigq_list = nullptr; fp.bigq_cnt = nullptr; fp.long_list = nullptr; fp.long_cnt = nullptr;
-        fp.xchg = ext->xchg; fp.xchg_stride = ext->xchg_stride; fp.q_base = ext->q_lo; fp.order = nullptr;
-        const uint64_t cnt = p.nq - ext->q_lo, res_wg = (uint64_t)d->n_cu * F_WG_PER_CU;
-        const uint32_t grid_front = (uint32_t)std::min<uint64_t>(cnt, std::min<uint64_t>(res_wg * 64, std::max<uint64_t>(res_wg * 16, cnt / 12)));
-        HIP_TRY(launch_fast(dim3(grid_front), st, di, p, fp, kn.debug, 1));
-        return SRN_OK;
-    }
-    if (ext && ext->mode == 2 && !fast) return fail(SRN_EINVAL, "the neighbours pipeline needs the fast kernel's query shape (device_fast_eligible)");
-    // The prep kernel clears the launch sequence's counters where it runs on this stream ahead of everything that uses them (two fill kernels otherwise: 6 us each)
-    const bool prep_clears = !ext && !resident;
-    if ((may_overflow || dense) && !prep_clears) HIP_TRY(hipMemsetAsync(w->retry_cnt, 0, 4, st));
-    if (dense) HIP_TRY(hipMemsetAsync(w->retry_cnt2, 0, 4, st));
-    hipEvent_t* ev = w->ev[w->calls % Workspace::RING];
-    // Per-kernel events only when someone asked for kernel times: an event between two kernels idles the stream for ~6 us (three of them: 18 us of a 4 096-query batch's 250)
-    const bool timed = d->timing.load(std::memory_order_relaxed);
-    w->ring_timed[w->calls % Workspace::RING] = timed;
-    if (timed) HIP_TRY(hipEventRecord(ev[0], st));
-    if (ext) { if (ext->prep_stride != prep_stride) return fail(SRN_EINVAL, "prep record stride mismatch"); p.prep = ext->prep; p.prep_stride = prep_stride; }
-    else if (resident) {
-        // prep of this call on the side stream: behind the call that used this set of records two calls ago, beside the previous call's kernels
-        const int par = (int)(w->resident_calls & 1u);
-        char* rec = par ? w->prep2 : w->prep;
-        // (ev_done[set] = the end of the LAST call that read record set `set`, resident or not: a non-resident device-pointer call on this stream reads w->prep too)
-        if (!w->rec_used[par] && w->calls > 0) { HIP_TRY(hipEventRecord(w->ev_done[par], st)); w->rec_used[par] = true; }   // (earlier calls of this workspace that left no event: everything enqueued so far)
-        if (w->rec_used[par]) HIP_TRY(hipStreamWaitEvent(w->side, w->ev_done[par], 0));
-        HIP_TRY(launch_prep(w->side, di, p.items_flat, p.q_off, p.nq, p.m, p.max_len, rec, prep_stride, nullptr, nullptr, nullptr, 0, okeys_in));
-        if (dedup) {   // (the count word of a merged row is written on the caller's stream, below: the previous call's kernels may still be writing these very buffers)
-            HIP_TRY(hipMemsetAsync(dd.slots, 0xFF, (size_t)dd.n_slots * 8, w->side));
-            HIP_TRY(launch_dedup_group(w->side, p.items_flat, p.q_off, p.nq, dd.slots, dd.slot_min, dd.n_slots, (uint32_t)kn.dedup_hash_bits, dd.rep, okeys_in, nullptr, dd.n_dup));
-        }
-        if (ordered) HIP_TRY(sort_order_keys(w->side, okeys_in, okeys_out, p.nq, otemp, &otemp_bytes));
-        HIP_TRY(hipEventRecord(w->ev_prep[par], w->side));
-        HIP_TRY(hipStreamWaitEvent(st, w->ev_prep[par], 0));
-        if (dedup) HIP_TRY(launch_dedup_mark(st, p.nq, dd.rep, p.out_counts));
-        p.prep = rec; p.prep_stride = prep_stride;
-    }
-    else { HIP_TRY(launch_prep(st, di, p.items_flat, p.q_off, p.nq, p.m, p.max_len, w->prep, prep_stride, fast ? w->slow_cnt : nullptr, (may_overflow || dense) ? w->retry_cnt : nullptr, nullptr, 0, okeys_in));
-           if (dedup) {
-               HIP_TRY(hipMemsetAsync(dd.slots, 0xFF, (size_t)dd.n_slots * 8, st));
-               HIP_TRY(launch_dedup_group(st, p.items_flat, p.q_off, p.nq, dd.slots, dd.slot_min, dd.n_slots, (uint32_t)kn.dedup_hash_bits, dd.rep, okeys_in, p.out_counts, dd.n_dup));
-           }
-           if (ordered) HIP_TRY(sort_order_keys(st, okeys_in, okeys_out, p.nq, otemp, &otemp_bytes));
-           p.prep = w->prep; p.prep_stride = prep_stride; }
-    if (timed) HIP_TRY(hipEventRecord(ev[3], st));
-    const uint32_t* final_list = w->retry_list; uint32_t* final_cnt = w->retry_cnt;
-    // The global-table retry pass serves a handful of queries with one workgroup each, ~0.3 ms behind everything else on config 5 (VERDICT r2 weak 6).  Where earlier
-    // calls on this workspace did retry queries (the pinned counter of the last finished call says so: a hint, read without synchronising) it is forked onto the side
-    // stream right behind the general kernel and runs beside the finish kernels; where nothing is ever retried (configs 2-4) the two extra events would cost more
-    // than the empty pass.
-    // (Tried in round 3 and dropped: the general kernel over the handed-over queries + the global-table pass on the side stream, beside the two finish kernels -- 38 + 4 us
-    //  against 17 + 10 us at 4 096 queries.  4 096 / 65 536 / 2^20 queries: 0.220 / 1.759 / 25.28 ms forked, 0.215 / 1.759 / 25.25 ms in line.)
-    const bool fork_retry = fast && may_overflow && !dense && on_device && *(volatile uint32_t*)w->h_retry != 0u && w->h_retry_valid;
-    if (fork_retry) { int rc = ensure_side(w); if (rc) return rc; }
-    // The fast kernel (srn_fast.hip) serves the common query shape; what it cannot take -- decided per query, on the device -- is
-    // queued on slow_list and served by the general kernel right behind it.
-    if (fast) {
-        w->cnt_dirty = true;   // (the latency path's fused launch wants the counters at 0 and clears them itself after a sequence like this one)
-        if (!prep_clears) HIP_TRY(hipMemsetAsync(w->slow_cnt, 0, 32, st));   // (slow_cnt[0] = handed-over queries, [1] = the MID instantiation's list, [2..3] = the 64-bit ticket of vmis_finish_big_kernel's list, [4] = MID-BIG's list)
-        // The fast kernel's workgroups walk their queries in a pipeline (the next record is fetched during the current query), so they want ~12 queries each;
-        // beyond that, more and smaller workgroups shorten the tail of the launch.  Measured on config 3 (ms per launch at 8 / 16 / 32 / 64 resident sets): 2^20 queries
-        // 26.29 / 26.06 / 25.85 / 25.81; 2^18: - / 6.62 / 6.57 / 6.63; 2^16: - / 1.70 / 1.72 / 1.78.
-        const uint64_t resident = (uint64_t)d->n_cu * F_WG_PER_CU;
-        const uint32_t grid_f = kn.grid_mult_set ? (uint32_t)std::min<uint64_t>(p.nq, resident * grid_mult)
-                                                 : (uint32_t)std::min<uint64_t>(p.nq, std::min<uint64_t>(resident * 64, std::max<uint64_t>(resident * 16, p.nq / 12)));
-        const uint64_t big_entries = std::min<uint64_t>(0x7FFFFFF0ull, (uint64_t)p.nq * 16 + 4096);
-        FastParams fp = d->fast; fp.slow_list = w->slow_list; fp.slow_cnt = w->slow_cnt; fp.nb = nb_fast; fp.max_runs = nb_fast; fp.fin = w->fin;
-        fp.big_arena = w->big; fp.big_list = (uint32_t*)(w->big + big_entries * 16); fp.big_ticket = (unsigned long long*)(w->slow_cnt + 2); fp.big_cap_entries = (uint32_t)big_entries;
-        fp.xchg = nullptr; fp.xchg_stride = 0; fp.q_base = 0;
-        fp.mid_list = mid_tier ? w->slow_list + (w->slow_cap + 16) : nullptr; fp.mid_cnt = mid_tier ? w->slow_cnt + 1 : nullptr;
-        // (round 5: the BIG form also without a MID tier -- it takes the lean shape's oversized queries of the headline batches; not over an item shard's fragments)
-        fp.bigq_list = !kn.no_big && !ext && d->di.row_frag == 0u ? w->slow_list + 2 * (w->slow_cap + 16) : nullptr; fp.bigq_cnt = fp.bigq_list ? w->slow_cnt + 4 : nullptr;
-        fp.long_list = plan.long_tier ? w->slow_list + 3 * (w->slow_cap + 16) : nullptr; fp.long_cnt = fp.long_list ? w->slow_cnt + 5 : nullptr;
-        const bool back = ext && ext->mode == 2;   // neighbour lists from the exchange buffer (any rank's front end), this shard's rows
-        if (back) { fp.xchg = ext->xchg; fp.xchg_stride = ext->xchg_stride; }
-        fp.order = ordered ? okeys_out : back ? ext->order : nullptr;
-        fp.order_dups = dedup ? dd.n_dup : nullptr;
-        const uint32_t grid_fo = fp.order ? std::max<uint32_t>(8u, grid_f / 8u * 8u) : grid_f;   // (an ordered launch walks an eighth of the order per XCD: the grid is a multiple of 8)
-        if (back && d->sback.frag8 && !kn.no_sback && p.max_len <= 8) {
-            // the item shard's own back end (srn_sback.hip): one wave per query, 12 per CU; a persistent grid of a few waves per resident slot
-            SBackParams sbp = d->sback;
-            // the streaming form where the shard holds its fragments in the posting order of the very lists the records were written against (9 waves per CU: 16.8 KB each)
-            const bool stream = ext->positions;
-            if (stream && !(d->sb_frag_post && d->sb_post_for == ext->post_rank)) return fail(SRN_ESTATE, "the batch's neighbours came as posting positions, but this shard does not hold its fragments in posting order");
-            const uint64_t slots = (uint64_t)d->n_cu * (stream ? 9 : 12);
-            uint32_t grid_b = (uint32_t)std::min<uint64_t>(p.nq, slots * (kn.grid_mult_set ? grid_mult : stream ? 4 : 16));   // (gather form, round 6: 1 / 2 / 4 / 8 / 16 / 32 waves per slot = 1.295 / 1.247 / 1.191 / 1.148 / 1.115 / 1.114 ms -- the tail of a persistent grid costs more than the first query of a wave, which has no prefetched record)
-            if (fp.order) grid_b = std::max<uint32_t>(8u, grid_b / 8u * 8u);
-            if (stream) {
-                int rc = ensure(&w->sb_scr, &w->sb_scr_bytes, (size_t)grid_b * shard_back_scratch_words() * 4); if (rc) return rc;
-                sbp.frag_post = (const uint2*)d->sb_frag_post; sbp.post_rank = ext->post_rank; sbp.scr = (uint32_t*)w->sb_scr;
-            }
-            const bool second = !kn.no_sback_second && !stream; sback_second = second;   // (the streaming form's records are not neighbour slots)  // what outgrows the wave's room: the round-4 back end (eight waves per query) over a list, before the general kernel
-            if (second) { fp.mid_list = w->slow_list + (w->slow_cap + 16); fp.mid_cnt = w->slow_cnt + 1; }
-            HIP_TRY(launch_shard_back(dim3(grid_b), st, di, p, fp, sbp, kn.debug));
-            d->sback_launches.fetch_add(1, std::memory_order_relaxed);
-            if (second) { FastParams fl = fp; fl.order = nullptr; HIP_TRY(launch_fast(dim3((uint32_t)std::min<uint64_t>(p.nq, resident * 4)), st, di, p, fl, kn.debug, 2)); fp.mid_list = nullptr; fp.mid_cnt = nullptr; }
-        } else
-        HIP_TRY(launch_fast(dim3(grid_fo), st, di, p, fp, kn.debug, back ? 2 : 0));
-        if (timed) HIP_TRY(hipEventRecord(ev[4], st));
-        // The MID instantiation over what the lean one listed for it (sessions of <= 10 items, <= 8 lists); what it cannot take either joins slow_list.  The list's length
-        // is known on the device only: a fixed grid, workgroups beyond the list leave at once.
-        if (mid_tier) HIP_TRY(launch_fast(dim3((uint32_t)std::min<uint64_t>(p.nq, resident * 8)), st, di, p, fp, kn.debug, 0, true));
-        // ... and MID's BIG form (80 KB of LDS, two workgroups per CU) over what MID passed on only for want of merge-buffer room
-        if (fp.bigq_list) HIP_TRY(launch_fast(dim3((uint32_t)std::min<uint64_t>(p.nq, (uint64_t)d->n_cu * 2 * 4)), st, di, p, fp, kn.debug, 0, true, true));
-        // ... and the LONG form over the sessions of 11..20 items the lean instantiation listed for it
-        if (fp.long_list) HIP_TRY(launch_fast(dim3((uint32_t)std::min<uint64_t>(p.nq, (uint64_t)d->n_cu * 2 * 4)), st, di, p, fp, kn.debug, 0, true, true, true));
-        HIP_TRY(launch_predict(geo.masks, slot64, false, 0, dim3(grid), lds, st, di, p, c, w->slow_list, w->slow_cnt, w->retry_list, w->retry_cnt, nullptr, 0, spill, ShardIO{}));
-        if (fork_retry) {   // the global-table pass beside the finish kernels (they touch disjoint rows: a finish kernel only completes rows flagged by the fast kernel)
-            HIP_TRY(hipEventRecord(w->ev_fork, st)); HIP_TRY(hipStreamWaitEvent(w->side, w->ev_fork, 0));
-            HIP_TRY(launch_predict(geo.masks, slot64, true, 0, dim3(retry_blocks), c.off_a, w->side, di, p, cg, final_list, final_cnt, nullptr, nullptr, w->gscratch, g_stride, spill, ShardIO{}));
-            HIP_TRY(hipEventRecord(w->ev_join, w->side));
-        }
-        HIP_TRY(launch_finish(st, di, fp, p.out_ids, p.out_scores, p.out_counts, p.nq, p.how_many));
-        // (it also writes the call's two counters -- global-table queries, handed-over queries; both final once the general kernel is done -- into the pinned words)
-        HIP_TRY(launch_finish_big(st, di, fp, p.out_ids, p.out_scores, p.out_counts, p.how_many, (uint32_t)std::min<uint64_t>(p.nq, (uint64_t)d->n_cu * 16),
-                                  (may_overflow || dense) ? final_cnt : nullptr, w->slow_cnt, w->h_retry_dev));
-    } else
-    if (dense) {
-        HIP_TRY(launch_predict(geo.masks, false, false, 0, dim3(grid3), g3.lds, st, di, p, g3.c, nullptr, nullptr, w->retry_list, w->retry_cnt, nullptr, 0, spill, ShardIO{}, 3));
-        HIP_TRY(launch_predict(geo.masks, false, false, 0, dim3(grid), lds, st, di, p, c, w->retry_list, w->retry_cnt, w->retry_list2, w->retry_cnt2, nullptr, 0, spill, ShardIO{}));
-        final_list = w->retry_list2; final_cnt = w->retry_cnt2;
-    } else
-        HIP_TRY(launch_predict(geo.masks, slot64, false, 0, dim3(grid), lds, st, di, p, c, nullptr, nullptr, w->retry_list, w->retry_cnt, nullptr, 0, spill, ShardIO{}));
-    if (!fast && timed) HIP_TRY(hipEventRecord(ev[4], st));
-    // the merged queries' rows: behind every kernel that can write a representative's row -- the global-table pass included, where the launch has one
-    const bool fill_late = dedup && (may_overflow || dense);
-    if (dedup && !fill_late) HIP_TRY(launch_dedup_fill(st, p.nq, dd.rep, p.out_ids, p.out_scores, p.out_counts, p.how_many, dd.n_dup, w->h_retry_dev + 6));
-    if (timed) HIP_TRY(hipEventRecord(ev[1], st));
-    if (fork_retry) HIP_TRY(hipStreamWaitEvent(st, w->ev_join, 0));
-    else if (may_overflow || dense) {
-        const size_t lds_g = c.off_a;
-        HIP_TRY(launch_predict(geo.masks, slot64, true, 0, dim3(retry_blocks), lds_g, st, di, p, cg, final_list, final_cnt, nullptr, nullptr,
-                               w->gscratch, g_stride, spill, ShardIO{}));
-        if (!fast) HIP_TRY(hipMemcpyAsync(w->h_retry, final_cnt, 4, hipMemcpyDeviceToHost, st));   // (fast: vmis_finish_big_kernel wrote both words.  Not fast: last_fast = false says
-                                                                                                  //  "all of last_nq" -- no host write into a pinned word that an earlier call may still be writing)
-    }
-    if (fill_late) HIP_TRY(launch_dedup_fill(st, p.nq, dd.rep, p.out_ids, p.out_scores, p.out_counts, p.how_many, dd.n_dup, w->h_retry_dev + 6));
-    HIP_TRY(hipEventRecord(ev[2], st));
-    if (resident) { const int par = (int)(w->resident_calls & 1u); HIP_TRY(hipEventRecord(w->ev_done[par], st)); w->rec_used[par] = true; ++w->resident_calls; }
-    else if (!ext && w->side) { HIP_TRY(hipEventRecord(w->ev_done[0], st)); w->rec_used[0] = true; }   // (a workspace that has served resident calls: the next one's side-stream prep must not overwrite w->prep under this call's kernels)
-    ++w->calls; w->last_retry = (may_overflow || dense) ? 1 : 0; w->last_nq = p.nq; w->last_fast = fast; w->last_mid = fast && (mid_tier || sback_second); w->last_dedup = dedup; w->last_untimed = false;
-    if (may_overflow || dense) w->h_retry_valid = true;   // (from now on the pinned counter holds a finished call's count -- or is being overwritten by a newer one)
-
-    if (!on_device) {
-        HIP_TRY(hipMemcpyAsync(h_ids, p.out_ids, n_out * 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(h_scores, p.out_scores, n_out * 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(h_counts, p.out_counts, (size_t)p.nq * 4, hipMemcpyDeviceToHost, st));
-        if (h_stats) HIP_TRY(hipMemcpyAsync(h_stats, p.stats, (size_t)p.nq * 32, hipMemcpyDeviceToHost, st));
-        if (h_nb_rank) {
-            HIP_TRY(hipMemcpyAsync(h_nb_rank, p.nb_rank, (size_t)p.nq * p.k * 4, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipMemcpyAsync(h_nb_num, p.nb_num, (size_t)p.nq * p.k * 4, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipMemcpyAsync(h_nb_cnt, p.nb_cnt, (size_t)p.nq * 4, hipMemcpyDeviceToHost, st));
-        }
-        HIP_TRY(hipStreamSynchronize(st));
-    }
-    return SRN_OK;
+    if (ext && ext->mode != 0 && !pl.fast.fast) return fail(SRN_EINVAL, "the neighbours pipeline needs the fast kernel's query shape (device_fast_eligible)");
+    if (ext && ext->prep_stride != pl.prep_stride) return fail(SRN_EINVAL, "prep record stride mismatch");
+    if (ext && ext->mode == 1) return enqueue_shard_front(c);
+    { int rc = enqueue_batch(c, on_device); if (rc) return rc; }
+    return on_device ? SRN_OK : fetch_host_outputs(c, h_ids, h_scores, h_counts, h_stats, h_nb_rank, h_nb_num, h_nb_cnt);
 }
 
 // One stage of the item-sharded pipeline (device buffers, asynchronous on `stream`); see ShardIO.  Like the unsharded launch sequence, a stage has a second pass
@@ -1125,20 +835,18 @@ int device_shard_stage(DeviceState* d, const FlatIndex& ix, int stage, const Lau
     if (retry) {
         w = ws_acquire(d, true, stream); rel.w = w;
         if (!w) return fail(SRN_EHIP, "cannot create HIP stream / events");
-        if (w->retry_cap < p.nq) { if (w->retry_list) HIP_TRY(hipFree(w->retry_list)); w->retry_list = nullptr; w->retry_cap = 0;
-            HIP_TRY(hipMalloc((void**)&w->retry_list, (size_t)p.nq * 4 + 64)); w->retry_cap = p.nq; }
-        cg.sess_slots = (uint32_t)std::min<uint64_t>(1u << 30, std::max<uint64_t>(256, ceil_pow2(geo.need_sess * 2)));
-        cg.item_buckets = prime_at_least(geo.need_item / 2 + 64); cg.item_slots = cg.item_buckets * 4;
-        g_stride = std::max<uint64_t>((uint64_t)cg.sess_slots * geo.slot_bytes, (uint64_t)cg.hot_slots * 4 + (uint64_t)cg.sketch_slots * 4 + (uint64_t)cg.item_slots * 8);
-        g_stride = (g_stride + 255) / 256 * 256;
-        retry_blocks = (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)d->n_cu, (2ull << 30) / g_stride));
+        rc = ensure_list(&w->retry_list, &w->retry_cap, p.nq, (size_t)p.nq * 4 + 64); if (rc) return rc;
+        global_tables_geometry(d, geo, cg, g_stride, retry_blocks);
         rc = ensure(&w->gscratch, &w->gscratch_bytes, g_stride * retry_blocks); if (rc) return rc;
         HIP_TRY(hipMemsetAsync(w->retry_cnt, 0, 4, st));
     }
-    e = launch_predict(geo.masks, geo.slot64, false, stage, dim3(grid), geo.lds, st, d->di, p, geo.c, nullptr, nullptr, w ? w->retry_list : nullptr, w ? w->retry_cnt : nullptr, nullptr, 0, nullptr, sh);
+    PredictLaunch a; a.masks = geo.masks; a.slot64 = geo.slot64; a.stage = stage; a.sh = sh;
+    if (w) { a.retry_list = w->retry_list; a.retry_cnt = w->retry_cnt; }
+    e = launch_predict(a, dim3(grid), geo.lds, st, d->di, p, geo.c);
     if (e != hipSuccess) return fail(SRN_EHIP, std::string("shard stage launch: ") + hipGetErrorString(e));
     if (retry) {
-        e = launch_predict(false, geo.slot64, true, stage, dim3(retry_blocks), geo.c.off_a, st, d->di, p, cg, w->retry_list, w->retry_cnt, nullptr, nullptr, w->gscratch, g_stride, nullptr, sh);
+        PredictLaunch g; g.slot64 = geo.slot64; g.global_tables = true; g.stage = stage; g.sh = sh; g.qlist = w->retry_list; g.qn = w->retry_cnt; g.gscratch = w->gscratch; g.gstride = g_stride;
+        e = launch_predict(g, dim3(retry_blocks), geo.c.off_a, st, d->di, p, cg);
         if (e != hipSuccess) return fail(SRN_EHIP, std::string("shard stage launch (global tables): ") + hipGetErrorString(e));
     }
     return SRN_OK;
@@ -1160,7 +868,7 @@ bool device_fast_eligible(DeviceState* d, const FlatIndex& ix, const LaunchParam
     return (max_row_len_all != 0 || d->fast.row_packed != nullptr) && geo.masks && !wraps && rank_bits_f <= 29 && kn.geometry_default() && !kn.no_fast && p.k <= F_K_MAX && p.m <= F_M_MAX &&
            p.how_many <= 24 && (p.flags & ~(unsigned)SRN_FLAG_BUSINESS_LOGIC) == 0 && p.stats == nullptr && p.nb_rank == nullptr && p.max_len <= 8;
 }
-uint32_t device_prep_stride(uint32_t max_len) { return (uint32_t)(sizeof(PrepHead) + (size_t)max_len * sizeof(PrepItem)); }
+uint32_t device_prep_stride(uint32_t max_len) { return prep_stride_of(max_len); }
 int device_shard_lists_head(DeviceState* d, const LaunchParams& p, void* pos, int* head, void* stream) {
     HIP_TRY(hipSetDevice(d->device));
     if (p.nq == 0) return SRN_OK;
@@ -1200,10 +908,10 @@ int device_shard_nb_prep(DeviceState* d, DeviceState* post, const LaunchParams& 
     if (p.nq == 0) return SRN_OK;
     const Knobs kn = knobs();
     const bool ordered = order_buf && kn.order_min > 0 && p.nq >= (uint32_t)kn.order_min;
-    unsigned long long *kin = nullptr, *kout = nullptr; void* temp = nullptr; size_t tb = 0;
-    if (ordered) { int rc = order_room(order_buf, order_bytes, p.nq, &kin, &kout, &temp, &tb); if (rc) return rc; }
-    HIP_TRY(launch_prep((hipStream_t)stream, post->di, p.items_flat, p.q_off, p.nq, p.m, p.max_len, records, device_prep_stride(p.max_len), nullptr, nullptr, d->di.id_table, d->di.id_mask, kin));
-    if (ordered) { HIP_TRY(sort_order_keys((hipStream_t)stream, kin, kout, p.nq, temp, &tb)); *order_out = kout; }
+    OrderBufs ob;
+    if (ordered) { int rc = order_room(order_buf, order_bytes, p.nq, &ob); if (rc) return rc; }
+    HIP_TRY(launch_prep((hipStream_t)stream, post->di, p.items_flat, p.q_off, p.nq, p.m, p.max_len, records, device_prep_stride(p.max_len), nullptr, nullptr, d->di.id_table, d->di.id_mask, ob.keys_in));
+    if (ordered) { HIP_TRY(sort_order_keys((hipStream_t)stream, ob.keys_in, ob.keys_out, p.nq, ob.temp, &ob.temp_bytes)); *order_out = ob.keys_out; }
     return SRN_OK;
 }
 int device_shard_nb_front(DeviceState* d, const FlatIndex& ix, DeviceState* post, const LaunchParams& p_in, const char* records, uint32_t* xchg, uint32_t xchg_stride, uint32_t q_lo, uint32_t q_hi, void* stream) {
@@ -1255,7 +963,7 @@ int device_last_kernel_ms(DeviceState* d, double* ms_main, double* ms_retry, uin
     HIP_TRY(hipEventElapsedTime(&b, ev[1], ev[2]));
     if (ms_main) *ms_main = a;
     if (ms_retry) *ms_retry = b;
-    if (retried) *retried = w->last_retry ? *w->h_retry : 0;
+    if (retried) *retried = w->last_retry ? w->h_retry[HW_GLOBAL] : 0;
     return SRN_OK;
 }
 
@@ -1273,8 +981,8 @@ int device_last_path_counts(DeviceState* d, uint32_t* nq, uint32_t* general, uin
     if (!w || !(w->calls + w->untimed_calls)) return fail(SRN_EINVAL, "no predict call yet");
     if (!w->last_untimed) HIP_TRY(hipEventSynchronize(w->ev[(w->calls - 1) % Workspace::RING][2]));   // (the latency path returns with its stream idle)
     if (nq) *nq = w->last_nq;
-    if (general) *general = w->last_fast ? w->h_retry[1] : w->last_nq;
-    if (global_pass) *global_pass = w->last_retry ? w->h_retry[0] : 0;
+    if (general) *general = w->last_fast ? w->h_retry[HW_GENERAL] : w->last_nq;
+    if (global_pass) *global_pass = w->last_retry ? w->h_retry[HW_GLOBAL] : 0;
     return SRN_OK;
 }
 int device_last_mid_count(DeviceState* d, uint32_t* listed, uint32_t* big_listed) {   // queries the last call's lean fast kernel listed for the MID instantiation (0: no such tier in that call)
@@ -1283,8 +991,8 @@ int device_last_mid_count(DeviceState* d, uint32_t* listed, uint32_t* big_listed
     if (rc != SRN_OK) return rc;
     Workspace* w;
     { std::lock_guard<std::mutex> lk(d->mu); w = d->last_ws; }
-    if (listed) *listed = w->last_fast && w->last_mid ? w->h_retry[2] : 0u;
-    if (big_listed) *big_listed = w->last_fast ? w->h_retry[3] : 0u;   // (the BIG form also takes the lean shape's oversized queries: no MID tier needed)
+    if (listed) *listed = w->last_fast && w->last_mid ? w->h_retry[HW_MID] : 0u;
+    if (big_listed) *big_listed = w->last_fast ? w->h_retry[HW_BIGQ] : 0u;   // (the BIG form also takes the lean shape's oversized queries: no MID tier needed)
     return SRN_OK;
 }
 
@@ -1293,7 +1001,7 @@ int device_last_dedup_count(DeviceState* d, uint32_t* merged) {   // queries of 
     if (rc != SRN_OK) return rc;
     Workspace* w;
     { std::lock_guard<std::mutex> lk(d->mu); w = d->last_ws; }
-    if (merged) *merged = w->last_dedup ? w->h_retry[6] : 0u;
+    if (merged) *merged = w->last_dedup ? w->h_retry[HW_MERGED] : 0u;
     return SRN_OK;
 }
 

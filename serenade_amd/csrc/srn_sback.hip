@@ -269,7 +269,7 @@ __global__ __launch_bounds__(64, SRN_SBACK_WAVES) void vmis_shard_back_kernel(De
         // early exits, i.e. issues them when K has arrived -- a second dependent round trip per query)
         const uint32_t K = (uint32_t)__builtin_amdgcn_readfirstlane((int)kv);
         if (K == 0xFFFFFFFFu || L < 1u || L > 8u || L > p.max_len || K > F_K_MAX) {   // (wave-uniform) no front end took it, or not this kernel's shape: the general kernel does its candidate work itself
-            if (lane == 0u) f.slow_list[atomicAdd(f.slow_cnt, 1u)] = q;
+            if (lane == 0u) f.slow_list[atomicAdd(&f.slow_cnt[SC_GENERAL], 1u)] = q;
             fetch_next();
             continue;
         }
@@ -697,7 +697,7 @@ __global__ __launch_bounds__(64, SRN_SBACK_WAVES) void vmis_shard_back_kernel(De
         fetch_next();   // (a query without a walk B)
         SB_TICK(tk12);
         if (fail) {   // (beyond this kernel's room: the fast kernel's back-end form takes the query if the launch sequence has one behind this kernel, else the general kernel)
-            if (lane == 0u) { if (f.mid_list) f.mid_list[atomicAdd(f.mid_cnt, 1u)] = q; else f.slow_list[atomicAdd(f.slow_cnt, 1u)] = q; }
+            if (lane == 0u) { if (f.mid_list) f.mid_list[atomicAdd(f.mid_cnt, 1u)] = q; else f.slow_list[atomicAdd(&f.slow_cnt[SC_GENERAL], 1u)] = q; }
             continue;
         }
         // ---- hand-off: the query's record for vmis_finish_kernel (score = x / (10 U), ranking, public ids), as the fast kernel writes it ----
@@ -725,7 +725,7 @@ __global__ __launch_bounds__(64, SRN_SBACK_WAVES) void vmis_shard_back_kernel(De
             const uint32_t slot = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(tk >> 32), 0);
             ovf_at = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)tk, 0);
             if ((unsigned long long)ovf_at + (M - F_FIN_ENTRIES) > f.big_cap_entries) {   // no room: the general kernel redoes the query
-                if (lane == 0u) { f.big_list[slot] = 0xFFFFFFFFu; f.slow_list[atomicAdd(f.slow_cnt, 1u)] = q; }
+                if (lane == 0u) { f.big_list[slot] = 0xFFFFFFFFu; f.slow_list[atomicAdd(&f.slow_cnt[SC_GENERAL], 1u)] = q; }
                 continue;
             }
             if (lane == 0u) f.big_list[slot] = q;
