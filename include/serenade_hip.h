@@ -393,7 +393,8 @@ void srn_batcher_free(srn_batcher_t* b);   /* serves what is still queued, then 
 /* ---- evolving-session store + the /v1/recommend handler body --------------------------------------------------------
  * Replaces RocksDBSessionStore (src/sessions/mod.rs:7-77) and the body of v1_recommend
  * (src/endpoints/recommend_resource.rs:20-65) between the web framework and predict.  The store is in memory (a visitor
- * is pinned to one pod by session_id affinity; nothing has to survive the process).  Keys are the reference's: the MD5
+ * is pinned to one pod by session_id affinity).  This host store does not survive the process; the device-resident store below can
+ * be saved to a file and loaded again (srn_device_sessions_save / _load), as the reference's RocksDB survives a restart.  Keys are the reference's: the MD5
  * digest of the session_id string read as a big-endian u128 (recommend_resource.rs:27-28), here as (hi, lo).
  * A session idle for more than idle_secs reads as empty (mod.rs:46-52; 0 = the reference's 20 minutes); entries older than
  * ttl_secs are dropped (RocksDB TTL, src/bin/serving.rs:55-56; 0 = the reference's 30 minutes).  now_secs = 0 means the
@@ -442,7 +443,7 @@ typedef struct {
 } srn_device_sessions_stats_t;
 int srn_device_sessions_create(int device, size_t capacity, size_t items_cap, uint64_t ttl_secs, uint64_t idle_secs, srn_device_sessions_t** out);
 void srn_device_sessions_free(srn_device_sessions_t* s);
-/* srn_session_store_get / _update / _sweep for the device store, from the host (tests, debugging, seeding a store from another one): they block.
+/* srn_session_store_get / _update / _sweep for the device store, from the host (tests, debugging; one key per call -- whole stores move with srn_device_sessions_export / _import below): they block.
  * update: n above items_cap is SRN_ERANGE.  sweep: *n_live = entries kept. */
 int srn_device_sessions_get(srn_device_sessions_t* s, uint64_t key_hi, uint64_t key_lo, uint64_t now_secs, uint64_t* out_items, size_t cap, size_t* out_n);
 int srn_device_sessions_update(srn_device_sessions_t* s, uint64_t key_hi, uint64_t key_lo, uint64_t now_secs, const uint64_t* items, size_t n);
@@ -451,6 +452,52 @@ int srn_device_sessions_stats(srn_device_sessions_t* s, srn_device_sessions_stat
 /* HIP events around the store's kernels and predict's launches of every batch (off by default); last_ms blocks until the most recent batch is done */
 int srn_device_sessions_timing(srn_device_sessions_t* s, int enable);
 int srn_device_sessions_last_ms(srn_device_sessions_t* s, double* out_ms_store, double* out_ms_predict);
+/* ---- snapshot, restore, merge and grow the device store (bulk, on the device) ----
+ * Every call takes the store's mutex and is ordered behind the store's previous call, like the calls above.  now_secs = 0: the system clock.
+ * The LIVE entries at now_secs are those a sweep at now_secs keeps: occupied and not older than ttl_secs.  The idle rule is a read rule: an entry that is idle but
+ * younger than the TTL is live and is exported with its epoch.  now_secs = 1 therefore means "everything". */
+/* exact counts, from the device: *occupied slots and *live entries (either may be NULL); blocks */
+int srn_device_sessions_count(srn_device_sessions_t* s, uint64_t now_secs, uint64_t* occupied, uint64_t* live);
+/* The live entries as dense arrays, in ascending slot order (two exports of an unchanged store give identical bytes):
+ *   key_hi[i] | key_lo[i] | epoch[i] (seconds, as stored) | len[i] | items[i * items_stride .. + len[i]), the rest of the row zero
+ * items_stride below the store's max_stored_len (srn_device_sessions_stats): SRN_ERANGE.  An empty store and cap = 0 (the arrays may then be NULL) are SRN_OK.
+ * _export_device: device buffers on the store's GPU, enqueued on `stream` with no host synchronisation; writes the first min(live, cap) entries and *d_n = live --
+ *                 the caller compares.  NULL store or d_n: SRN_EINVAL.
+ * _export:        host arrays; blocks.  live > cap: SRN_ERANGE with *n = live and the arrays untouched.  NULL store or n: SRN_EINVAL. */
+int srn_device_sessions_export_device(srn_device_sessions_t* s, uint64_t now_secs, size_t cap, uint64_t* d_key_hi, uint64_t* d_key_lo, uint64_t* d_epoch, uint32_t* d_len,
+                                      uint64_t* d_items, size_t items_stride, uint64_t* d_n, void* stream);
+int srn_device_sessions_export(srn_device_sessions_t* s, uint64_t now_secs, size_t cap, uint64_t* key_hi, uint64_t* key_lo, uint64_t* epoch, uint32_t* len, uint64_t* items,
+                               size_t items_stride, size_t* n);
+/* Inserts n entries in the arrays' form above, each with its own epoch.  The merge rule: among entries with the same 128-bit key in one call the largest epoch wins
+ * (ties: the later index); an entry whose key is stored replaces it iff its epoch is >= the stored one; any other key is inserted.  Both forms block (the checks read
+ * a device reduction back) and nothing is changed unless every check passes: a len[i] above the store's items_cap or above items_stride is SRN_ERANGE; the capacity
+ * rule of a batch applies with every entry counted as a new key and nothing reclaimed (occupied + n > capacity: SRN_ENOMEM, or growth).  n = 0: SRN_OK. */
+int srn_device_sessions_import_device(srn_device_sessions_t* s, const uint64_t* d_key_hi, const uint64_t* d_key_lo, const uint64_t* d_epoch, const uint32_t* d_len,
+                                      const uint64_t* d_items, size_t items_stride, size_t n, void* stream);
+int srn_device_sessions_import(srn_device_sessions_t* s, const uint64_t* key_hi, const uint64_t* key_lo, const uint64_t* epoch, const uint32_t* len, const uint64_t* items,
+                               size_t items_stride, size_t n);
+/* Rebuilds the live entries at now_secs into tables of another capacity and / or items_cap (0 = keep); what a sweep at now_secs drops is dropped.  More live entries
+ * than capacity: SRN_ENOMEM; a live session longer than items_cap (the exact maximum, counted on the device): SRN_ERANGE; no device memory: SRN_ENOMEM -- the
+ * store is unchanged and usable in every case.  Both new tables are allocated before the old ones are freed: peak device memory is the old pair + the new pair.  Blocks. */
+int srn_device_sessions_resize(srn_device_sessions_t* s, size_t capacity, size_t items_cap, uint64_t now_secs);
+/* Opt-in growth.  max_capacity 0 (the default): off.  Otherwise a call that the capacity rule would refuse after its exact count resizes the store to the smallest
+ * capacity * 2^j that holds live sessions + n, if that is <= max_capacity, and goes on; beyond it the call is refused with SRN_ENOMEM and counted as ever. */
+int srn_device_sessions_set_max_capacity(srn_device_sessions_t* s, size_t max_capacity);
+/* *grows: automatic resizes; *resizes: all successful resizes, explicit and automatic (any pointer may be NULL) */
+int srn_device_sessions_growth(srn_device_sessions_t* s, uint64_t* max_capacity, uint64_t* grows, uint64_t* resizes);
+/* The file form (little-endian; byte by byte in DESIGN.md section 11): a 96-byte header, then the export's arrays.  save writes the live entries at now_secs to a
+ * temporary name next to `path` and renames it, so a crash leaves the previous snapshot.  load creates a store on `device` and imports the file: capacity 0 =
+ * max(saved capacity, n), items_cap / ttl_secs / idle_secs 0 = the saved values; n above capacity SRN_ENOMEM, the longest session above items_cap SRN_ERANGE.
+ * A file that is short, has another magic or version, sizes that do not add up, a length above its stride or a checksum mismatch is SRN_EIO (as srn_index_load).
+ * file_info reads and verifies the whole file on the host; it needs no GPU. */
+typedef struct {
+    uint64_t version, n, longest_session, items_stride;
+    uint64_t capacity, items_cap, ttl_secs, idle_secs;   /* of the store that was saved */
+    uint64_t saved_at_secs, payload_bytes;
+} srn_device_sessions_file_info_t;
+int srn_device_sessions_save(srn_device_sessions_t* s, const char* path, uint64_t now_secs);
+int srn_device_sessions_load(const char* path, int device, size_t capacity, size_t items_cap, uint64_t ttl_secs, uint64_t idle_secs, srn_device_sessions_t** out);
+int srn_device_sessions_file_info(const char* path, srn_device_sessions_file_info_t* out);
 /* srn_session_key for n strings: string i = ids_flat[off[i] .. off[i + 1]) */
 int srn_session_keys(const char* ids_flat, const uint64_t* off, size_t n, uint64_t* key_hi, uint64_t* key_lo);
 /* Every buffer in the index's device memory; enqueued on `stream` (a hipStream_t) without host synchronisation.  d_consent: one byte per request, NULL = every request

@@ -75,6 +75,10 @@ class DeviceSessionsStats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("capacity", "slots", "items_cap", "slot_bytes", "live_bound", "sweeps", "refused", "ttl_secs", "idle_secs", "max_stored_len")]
 
 
+class DeviceSessionsFileInfo(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("version", "n", "longest_session", "items_stride", "capacity", "items_cap", "ttl_secs", "idle_secs", "saved_at_secs", "payload_bytes")]
+
+
 class Limits(C.Structure):
     _fields_ = [("max_how_many", C.c_uint32), ("max_session_len", C.c_uint32), ("max_k", C.c_uint32), ("reserved", C.c_uint32)]
 
@@ -167,6 +171,17 @@ SYMBOLS = {
     "srn_device_sessions_stats": (_i, [_vp, C.POINTER(DeviceSessionsStats)]),
     "srn_device_sessions_timing": (_i, [_vp, _i]),
     "srn_device_sessions_last_ms": (_i, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "srn_device_sessions_count": (_i, [_vp, _u64, C.POINTER(_u64), C.POINTER(_u64)]),
+    "srn_device_sessions_export_device": (_i, [_vp, _u64, _sz, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+    "srn_device_sessions_export": (_i, [_vp, _u64, _sz, _vp, _vp, _vp, _vp, _vp, _sz, C.POINTER(_sz)]),
+    "srn_device_sessions_import_device": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _vp]),
+    "srn_device_sessions_import": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _sz]),
+    "srn_device_sessions_resize": (_i, [_vp, _sz, _sz, _u64]),
+    "srn_device_sessions_set_max_capacity": (_i, [_vp, _sz]),
+    "srn_device_sessions_growth": (_i, [_vp, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64)]),
+    "srn_device_sessions_save": (_i, [_vp, C.c_char_p, _u64]),
+    "srn_device_sessions_load": (_i, [C.c_char_p, _i, _sz, _sz, _u64, _u64, C.POINTER(_vp)]),
+    "srn_device_sessions_file_info": (_i, [C.c_char_p, C.POINTER(DeviceSessionsFileInfo)]),
     "srn_session_keys": (_i, [_vp, _vp, _sz, _vp, _vp]),
     "srn_recommend_batch_device": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _u64, _sz, _sz, _sz, _sz, C.c_uint, _vp, _vp, _vp, _vp]),
     "srn_recommend_batch": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _u64, _sz, _sz, _sz, _sz, C.c_uint, _vp, _vp, _vp]),

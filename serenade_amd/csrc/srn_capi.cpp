@@ -625,6 +625,38 @@ int srn_debug_device_sessions_last_batch(srn_device_sessions_t* s, const void** 
     return guarded([&]() -> int { return dsess_last_csr(s, d_items, d_q_off, out_n, out_max_len, h_items, cap, h_q_off); });
 }
 
+int srn_device_sessions_count(srn_device_sessions_t* s, uint64_t now_secs, uint64_t* occupied, uint64_t* live) {
+    return guarded([&]() -> int { return dsess_count(s, now_secs, occupied, live); });
+}
+int srn_device_sessions_export_device(srn_device_sessions_t* s, uint64_t now_secs, size_t cap, uint64_t* d_key_hi, uint64_t* d_key_lo, uint64_t* d_epoch, uint32_t* d_len,
+                                      uint64_t* d_items, size_t items_stride, uint64_t* d_n, void* stream) {
+    return guarded([&]() -> int { return dsess_export_device(s, now_secs, cap, d_key_hi, d_key_lo, d_epoch, d_len, d_items, items_stride, d_n, stream); });
+}
+int srn_device_sessions_export(srn_device_sessions_t* s, uint64_t now_secs, size_t cap, uint64_t* key_hi, uint64_t* key_lo, uint64_t* epoch, uint32_t* len, uint64_t* items,
+                               size_t items_stride, size_t* n) {
+    return guarded([&]() -> int { return dsess_export_host(s, now_secs, cap, key_hi, key_lo, epoch, len, items, items_stride, n); });
+}
+int srn_device_sessions_import_device(srn_device_sessions_t* s, const uint64_t* d_key_hi, const uint64_t* d_key_lo, const uint64_t* d_epoch, const uint32_t* d_len,
+                                      const uint64_t* d_items, size_t items_stride, size_t n, void* stream) {
+    return guarded([&]() -> int { return dsess_import_device(s, d_key_hi, d_key_lo, d_epoch, d_len, d_items, items_stride, n, stream); });
+}
+int srn_device_sessions_import(srn_device_sessions_t* s, const uint64_t* key_hi, const uint64_t* key_lo, const uint64_t* epoch, const uint32_t* len, const uint64_t* items,
+                               size_t items_stride, size_t n) {
+    return guarded([&]() -> int { return dsess_import_host(s, key_hi, key_lo, epoch, len, items, items_stride, n); });
+}
+int srn_device_sessions_resize(srn_device_sessions_t* s, size_t capacity, size_t items_cap, uint64_t now_secs) {
+    return guarded([&]() -> int { return dsess_resize(s, capacity, items_cap, now_secs); });
+}
+int srn_device_sessions_set_max_capacity(srn_device_sessions_t* s, size_t max_capacity) { return guarded([&]() -> int { return dsess_set_max_capacity(s, max_capacity); }); }
+int srn_device_sessions_growth(srn_device_sessions_t* s, uint64_t* max_capacity, uint64_t* grows, uint64_t* resizes) {
+    return guarded([&]() -> int { return dsess_growth(s, max_capacity, grows, resizes); });
+}
+int srn_device_sessions_save(srn_device_sessions_t* s, const char* path, uint64_t now_secs) { return guarded([&]() -> int { return dsess_save(s, path, now_secs); }); }
+int srn_device_sessions_load(const char* path, int device, size_t capacity, size_t items_cap, uint64_t ttl_secs, uint64_t idle_secs, srn_device_sessions_t** out) {
+    return guarded([&]() -> int { return dsess_load(path, device, capacity, items_cap, ttl_secs, idle_secs, out); });
+}
+int srn_device_sessions_file_info(const char* path, srn_device_sessions_file_info_t* out) { return guarded([&]() -> int { return dsess_file_info(path, out); }); }
+
 // the checks both entry points share, in srn_predict_batch_device's order; *done: nothing to do (n == 0)
 static int check_recommend_args(const srn_index_t* idx, size_t n, size_t k, size_t m, size_t how_many, unsigned flags, bool buffers, bool* done) {
     *done = false;

@@ -253,6 +253,21 @@ int dsess_stats(srn_device_sessions* s, srn_device_sessions_stats_t* out);
 int dsess_timing(srn_device_sessions* s, int enable);
 int dsess_last_ms(srn_device_sessions* s, double* ms_store, double* ms_predict);
 int dsess_last_csr(srn_device_sessions* s, const void** d_items, const void** d_qoff, size_t* n, size_t* max_len, uint64_t* h_items, size_t cap, uint32_t* h_qoff);
+int dsess_count(srn_device_sessions* s, uint64_t now_secs, uint64_t* occupied, uint64_t* live);
+int dsess_export_device(srn_device_sessions* s, uint64_t now_secs, size_t cap, uint64_t* d_hi, uint64_t* d_lo, uint64_t* d_epoch, uint32_t* d_len, uint64_t* d_items,
+                        size_t items_stride, uint64_t* d_n, void* stream);
+int dsess_export_host(srn_device_sessions* s, uint64_t now_secs, size_t cap, uint64_t* hi, uint64_t* lo, uint64_t* epoch, uint32_t* len, uint64_t* items,
+                      size_t items_stride, size_t* n);
+int dsess_import_device(srn_device_sessions* s, const uint64_t* d_hi, const uint64_t* d_lo, const uint64_t* d_epoch, const uint32_t* d_len, const uint64_t* d_items,
+                        size_t items_stride, size_t n, void* stream);
+int dsess_import_host(srn_device_sessions* s, const uint64_t* hi, const uint64_t* lo, const uint64_t* epoch, const uint32_t* len, const uint64_t* items,
+                      size_t items_stride, size_t n);
+int dsess_resize(srn_device_sessions* s, size_t capacity, size_t items_cap, uint64_t now_secs);
+int dsess_set_max_capacity(srn_device_sessions* s, size_t max_capacity);
+int dsess_growth(srn_device_sessions* s, uint64_t* max_capacity, uint64_t* grows, uint64_t* resizes);
+int dsess_save(srn_device_sessions* s, const char* path, uint64_t now_secs);
+int dsess_load(const char* path, int device, size_t capacity, size_t items_cap, uint64_t ttl_secs, uint64_t idle_secs, srn_device_sessions** out);
+int dsess_file_info(const char* path, srn_device_sessions_file_info_t* out);
 int dsess_recommend_device(const srn_index* idx, srn_device_sessions* s, const uint64_t* d_hi, const uint64_t* d_lo, const uint64_t* d_item, const uint8_t* d_consent,
                            size_t n, uint64_t now_secs, size_t max_items, size_t k, size_t m, size_t how_many, unsigned flags,
                            uint64_t* d_ids, double* d_scores, uint32_t* d_counts, void* stream);

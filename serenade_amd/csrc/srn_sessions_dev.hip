@@ -20,13 +20,24 @@
 //   sess_emit       every request copies its window into items_flat: O(window) per request, whatever the run's length
 //   sess_store      the last request of a run writes its window -- the final session -- and the epoch back, once
 //   device_predict  on (items_flat, q_off)
+//
+// The store is the one state of the library that training data cannot rebuild, so whole stores move in bulk, each pass behind `last`:
+//   export          live flag per slot, exclusive scan, scatter in slot order into dense arrays (no atomic cursor: an unchanged store exports the same bytes)
+//   import          the batch's sort over the entries' keys; one lane per distinct key picks the run's winner (largest epoch, later index on a tie) and claims or
+//                   finds its slot; a second kernel writes the winners.  Checked before anything is changed
+//   resize / growth sess_rebuild into a freshly allocated pair of tables of another capacity or items_cap
+//   save / load     the export's arrays behind a 96-byte header with a checksum, written through a rename
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <chrono>
+#include <cstdio>
 #include <cstring>
 #include <mutex>
+#include <string>
 #include <vector>
+
+#include <unistd.h>
 
 #include <rocprim/rocprim.hpp>
 
@@ -227,6 +238,127 @@ __global__ void __launch_bounds__(kTPB) sess_rebuild(Table from, Table to, uint6
     }
 }
 
+// ---- bulk export / import / resize ----
+// counters[0] = occupied slots, [1] = entries a sweep at `now` keeps, [2] = the longest session among those
+__global__ void __launch_bounds__(kTPB) sess_count_max(Table t, uint64_t now, uint64_t ttl, unsigned long long* counters) {
+    const uint32_t i = blockIdx.x * kTPB + threadIdx.x;
+    bool occ = false, live = false; uint32_t len = 0;
+    if (i <= t.mask) { const SlotHead* s = slot_at(t, i); occ = s->state != kEmpty; live = occ && !idle_or_old(now, s->epoch, ttl); if (live) len = s->len; }
+    const unsigned long long mo = __ballot(occ), ml = __ballot(live);
+    for (int off = 32; off; off >>= 1) len = max(len, (uint32_t)__shfl_xor((int)len, off));
+    if ((threadIdx.x & 63) == 0) {
+        if (mo) atomicAdd(&counters[0], (unsigned long long)__popcll(mo));
+        if (ml) { atomicAdd(&counters[1], (unsigned long long)__popcll(ml)); atomicMax(&counters[2], (unsigned long long)len); }
+    }
+}
+// flag[i] = 1 for an entry a sweep at `now` keeps; flag[n_slots] = 0, so that the exclusive scan's last word is the number of live entries
+__global__ void __launch_bounds__(kTPB) sess_live_flag(Table t, uint64_t now, uint64_t ttl, uint32_t* __restrict__ flag) {
+    const uint32_t i = blockIdx.x * kTPB + threadIdx.x;
+    if (i > t.mask + 1u) return;
+    uint32_t f = 0;
+    if (i <= t.mask) { const SlotHead* s = slot_at(t, i); f = s->state != kEmpty && !idle_or_old(now, s->epoch, ttl); }
+    flag[i] = f;
+}
+struct ExportArgs {
+    Table t; const uint32_t* pos;      // [n_slots + 1] exclusive scan of the live flags: a live slot's place among the exported entries
+    uint64_t now, ttl, cap, items_stride;
+    uint64_t* key_hi; uint64_t* key_lo; uint64_t* epoch; uint32_t* len; uint64_t* items; uint64_t* d_n;
+    uint32_t lanes_shift;              // 2^lanes_shift adjacent lanes read one slot, 16 bytes each per round
+};
+// Slot -> dense arrays.  A slot is 16-byte elements: 0 = the key, 1 = epoch | len | state, 2.. = item pairs; lane e of a slot's group reads element e, e + lanes, ...
+// so a wave reads whole slots with adjacent lanes and writes each dense array in runs of adjacent words.  Items from `len` on are written as zero.
+__global__ void __launch_bounds__(kTPB) sess_export_scatter(ExportArgs a) {
+    const uint64_t tid = (uint64_t)blockIdx.x * kTPB + threadIdx.x;
+    if (tid == 0) *a.d_n = a.pos[a.t.mask + 1u];
+    const uint64_t slot = tid >> a.lanes_shift;
+    const uint32_t lanes = 1u << a.lanes_shift, lane = (uint32_t)tid & (lanes - 1);
+    if (slot > a.t.mask) return;
+    const SlotHead* s = slot_at(a.t, (uint32_t)slot);
+    const uint64_t ep = s->epoch;
+    if (s->state == kEmpty || idle_or_old(a.now, ep, a.ttl)) return;
+    const uint64_t d = a.pos[slot];
+    if (d >= a.cap) return;
+    const uint32_t len = s->len;
+    const ulonglong2* el = (const ulonglong2*)s;
+    const uint64_t n_el = 2 + (a.items_stride + 1) / 2;
+    for (uint64_t e = lane; e < n_el; e += lanes) {
+        if (e == 0) { const ulonglong2 v = el[0]; a.key_hi[d] = v.x; a.key_lo[d] = v.y; }
+        else if (e == 1) { a.epoch[d] = ep; a.len[d] = len; }
+        else {
+            const uint64_t j = 2 * (e - 2);
+            ulonglong2 v = make_ulonglong2(0, 0);
+            if (j < len) { v = el[e]; if (j + 1 >= len) v.y = 0; }   // (j < len <= items_cap: the pair lies inside the slot, whose size is a multiple of 128)
+            uint64_t* dst = a.items + d * a.items_stride + j;
+            dst[0] = v.x; if (j + 1 < a.items_stride) dst[1] = v.y;
+        }
+    }
+}
+
+struct ImportArgs {
+    Table t;
+    const uint64_t* key_hi; const uint64_t* key_lo; const uint64_t* epoch; const uint32_t* len; const uint64_t* items; uint64_t items_stride;   // the caller's arrays
+    const uint32_t* order;   // [n] entry index of each sorted position
+    uint32_t n;
+    uint32_t* slot_of;       // [n] by sorted position of a run head: its slot
+    uint32_t* win;           // [n] ... and the entry that is written there (kNone: the stored entry is newer, or not a head)
+    uint32_t* err;
+};
+__global__ void __launch_bounds__(kTPB) sess_import_maxlen(const uint32_t* __restrict__ len, uint32_t n, uint32_t* __restrict__ out) {
+    const uint32_t i = blockIdx.x * kTPB + threadIdx.x;
+    uint32_t v = i < n ? len[i] : 0;
+    for (int off = 32; off; off >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, off));
+    if ((threadIdx.x & 63) == 0 && v) atomicMax(out, v);
+}
+// one lane per distinct key (the head of its run): the run's winner -- largest epoch, the later entry on a tie -- and find-or-insert as sess_find does it.  A slot
+// claimed here stays in state 2 until sess_import_write, so every slot in state 1 was complete before this kernel began and its key can be compared
+__global__ void __launch_bounds__(kTPB) sess_import_find(ImportArgs a) {
+    const uint32_t p = blockIdx.x * kTPB + threadIdx.x;
+    if (p >= a.n) return;
+    const uint32_t e0 = a.order[p];
+    const uint64_t hi = a.key_hi[e0], lo = a.key_lo[e0];
+    if (p) { const uint32_t pr = a.order[p - 1]; if (a.key_hi[pr] == hi && a.key_lo[pr] == lo) { a.slot_of[p] = kNone; a.win[p] = kNone; return; } }
+    uint32_t w = e0; uint64_t we = a.epoch[e0];
+    for (uint32_t q = p + 1; q < a.n; ++q) {   // (the sort is stable: a later position of the run is a later entry)
+        const uint32_t r = a.order[q];
+        if (a.key_hi[r] != hi || a.key_lo[r] != lo) break;
+        const uint64_t re = a.epoch[r];
+        if (re >= we) { w = r; we = re; }
+    }
+    uint32_t h = key_hash(hi, lo) & a.t.mask, found = kNone;
+    for (uint32_t probes = 0; probes <= a.t.mask; ++probes, h = (h + 1) & a.t.mask) {
+        SlotHead* s = slot_at(a.t, h);
+        uint32_t st = __hip_atomic_load(&s->state, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (st == kEmpty) {
+            st = atomicCAS(&s->state, kEmpty, kClaimed);
+            if (st == kEmpty) { found = h; break; }
+        }
+        if (st == kFull && s->key_hi == hi && s->key_lo == lo) {
+            found = h;
+            if (we < s->epoch) w = kNone;   // the stored entry is newer: it stays
+            break;
+        }
+    }
+    if (found == kNone) { atomicOr(a.err, 1u); w = kNone; }
+    a.slot_of[p] = found; a.win[p] = w;
+}
+// 16 adjacent lanes write one winner into its slot, a 16-byte element each per round (the layout of sess_export_scatter)
+__global__ void __launch_bounds__(kTPB) sess_import_write(ImportArgs a) {
+    const uint64_t tid = (uint64_t)blockIdx.x * kTPB + threadIdx.x;
+    const uint64_t p = tid >> 4; const uint32_t lane = (uint32_t)tid & 15u;
+    if (p >= a.n) return;
+    const uint32_t w = a.win[p];
+    if (w == kNone) return;
+    SlotHead* s = slot_at(a.t, a.slot_of[p]);
+    const uint32_t len = a.len[w];
+    const uint64_t* src = a.items + (uint64_t)w * a.items_stride;
+    uint64_t* it = slot_items(s);
+    for (uint32_t e = lane; e < 2 + (len + 1) / 2; e += 16) {
+        if (e == 0) { s->key_hi = a.key_hi[w]; s->key_lo = a.key_lo[w]; }
+        else if (e == 1) { s->epoch = a.epoch[w]; s->len = len; s->state = kFull; }
+        else { const uint32_t j = 2 * (e - 2); it[j] = src[j]; if (j + 1 < len) it[j + 1] = src[j + 1]; }
+    }
+}
+
 uint64_t wall_secs() { return (uint64_t)std::chrono::duration_cast<std::chrono::seconds>(std::chrono::system_clock::now().time_since_epoch()).count(); }
 size_t align256(size_t b) { return (b + 255) / 256 * 256; }
 dim3 grid_for(size_t n) { return dim3((unsigned)((n + kTPB - 1) / kTPB)); }
@@ -250,6 +382,8 @@ struct srn_device_sessions {
     char* stage = nullptr; size_t stage_bytes = 0;          // the host-pointer entry point's device copies
     std::mutex stage_mu;
     char* small = nullptr;                                  // err word | counters | one session in / out
+    char* xs = nullptr; size_t xs_bytes = 0;                // export / import scratch (flags and places per slot; sort buffers per entry)
+    uint64_t max_capacity = 0, grows = 0, resizes = 0;      // opt-in growth (0 = off) | automatic resizes | all resizes
     // the most recent batch (debug accessors, timing)
     const uint64_t* last_items = nullptr; const uint32_t* last_qoff = nullptr; size_t last_n = 0, last_hint = 0;
     bool timing = false, last_timed = false; hipEvent_t tev[3] = {nullptr, nullptr, nullptr};
@@ -267,7 +401,7 @@ void dsess_free(srn_device_sessions* s) {
     if (s->last) { (void)hipEventSynchronize(s->last); (void)hipEventDestroy(s->last); }
     for (hipEvent_t e : s->tev) if (e) (void)hipEventDestroy(e);
     if (s->own) { (void)hipStreamSynchronize(s->own); (void)hipStreamDestroy(s->own); }
-    for (void* p : {(void*)s->table[0], (void*)s->table[1], (void*)s->ws, (void*)s->stage, (void*)s->small}) if (p) (void)hipFree(p);
+    for (void* p : {(void*)s->table[0], (void*)s->table[1], (void*)s->ws, (void*)s->stage, (void*)s->small, (void*)s->xs}) if (p) (void)hipFree(p);
     delete s;
 }
 
@@ -324,6 +458,46 @@ int count(srn_device_sessions* s, uint64_t now, uint64_t* occupied, uint64_t* li
     *occupied = c[0]; *live = c[1];
     return SRN_OK;
 }
+int count_max(srn_device_sessions* s, uint64_t now, uint64_t* occupied, uint64_t* live, uint64_t* longest) {   // blocks (own stream, mu held)
+    HIP_TRY(hipMemsetAsync(s->counters(), 0, 24, s->own));
+    sess_count_max<<<grid_for(s->n_slots), kTPB, 0, s->own>>>(s->tab(), now, s->ttl, s->counters());
+    HIP_TRY(hipGetLastError());
+    unsigned long long c[3] = {0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(c, s->counters(), 24, hipMemcpyDeviceToHost, s->own));
+    HIP_TRY(hipStreamSynchronize(s->own));
+    *occupied = c[0]; *live = c[1]; *longest = c[2];
+    return SRN_OK;
+}
+uint64_t slots_for(uint64_t capacity) { uint64_t n = 2; while (n < 2 * capacity) n <<= 1; return n; }
+uint32_t stride_for(uint64_t items_cap) { return (uint32_t)((kSlotHead + 8 * items_cap + 127) / 128 * 128); }
+// Rebuilds the entries a sweep at `now` keeps into tables of another shape (own stream, mu held, behind `last`; blocks).  Both new tables are allocated before the
+// old ones are touched -- peak device memory is the old pair + the new pair -- and every failure leaves the store as it was.
+int resize_locked(srn_device_sessions* s, uint64_t capacity, uint64_t items_cap, uint64_t now, const char* who) {
+    uint64_t occupied = 0, live = 0, longest = 0;
+    int rc = count_max(s, now, &occupied, &live, &longest); if (rc) return rc;
+    if (live > capacity) return fail(SRN_ENOMEM, std::string(who) + ": more live sessions than the new capacity");
+    if (longest > items_cap) return fail(SRN_ERANGE, std::string(who) + ": a stored session is longer than the new items_cap");
+    const uint64_t n_slots = slots_for(capacity); const uint32_t stride = stride_for(items_cap);
+    const size_t bytes = (size_t)n_slots * stride;
+    char* nt[2] = {nullptr, nullptr};
+    for (int i = 0; i < 2; ++i)
+        if (hipMalloc((void**)&nt[i], bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            if (nt[0]) (void)hipFree(nt[0]);
+            return fail(SRN_ENOMEM, std::string(who) + ": no device memory for the new tables");
+        }
+    const Table from = s->tab(), to{nt[0], (uint32_t)(n_slots - 1), stride};
+    hipError_t e = hipMemsetAsync(nt[0], 0, bytes, s->own);
+    if (e == hipSuccess) { sess_rebuild<<<grid_for(s->n_slots), kTPB, 0, s->own>>>(from, to, now, s->ttl); e = hipGetLastError(); }
+    if (e == hipSuccess) e = hipStreamSynchronize(s->own);
+    if (e != hipSuccess) { (void)hipFree(nt[0]); (void)hipFree(nt[1]); return fail(SRN_EHIP, std::string(who) + ": " + hipGetErrorString(e)); }
+    (void)hipFree(s->table[0]); (void)hipFree(s->table[1]);
+    s->table[0] = nt[0]; s->table[1] = nt[1]; s->cur = 0;
+    s->capacity = capacity; s->items_cap = items_cap; s->n_slots = n_slots; s->stride = stride;
+    s->bound = live; s->len_bound = std::max<uint32_t>(1u, std::min<uint32_t>(s->len_bound, (uint32_t)items_cap));
+    ++s->resizes;
+    return SRN_OK;
+}
 // The capacity rule (mu held): room for n more keys, or SRN_ENOMEM with the table as it was.  Only when the host's bound does not fit does anything wait for the device:
 // the exact counts replace the bound, and entries older than the TTL are dropped (a rebuild) if that makes the room.
 int make_room(srn_device_sessions* s, uint64_t n, uint64_t now) {
@@ -333,7 +507,18 @@ int make_room(srn_device_sessions* s, uint64_t n, uint64_t now) {
     if ((rc = count(s, now, &occupied, &live))) return rc;
     s->bound = occupied;
     if (occupied + n <= s->capacity) return SRN_OK;
-    if (live + n > s->capacity) { ++s->refused; return fail(SRN_ENOMEM, "device session store: the batch does not fit the store's capacity (live sessions + batch > capacity)"); }
+    if (live + n > s->capacity) {
+        // opt-in growth: the smallest power-of-two multiple of the capacity that holds live + n, if max_capacity allows it (this path already waits for the device)
+        uint64_t grown = s->capacity;
+        while (grown < live + n && grown < s->max_capacity) grown *= 2;
+        if (grown >= live + n && grown <= s->max_capacity) {
+            rc = resize_locked(s, grown, s->items_cap, now, "device session store (growth)");
+            if (rc == SRN_OK) { ++s->grows; return SRN_OK; }
+            if (rc != SRN_ENOMEM) return rc;
+        }
+        ++s->refused;
+        return fail(SRN_ENOMEM, "device session store: the batch does not fit the store's capacity (live sessions + batch > capacity)");
+    }
     if ((rc = rebuild(s, now))) return rc;
     HIP_TRY(hipStreamSynchronize(s->own));
     s->bound = live;
@@ -585,6 +770,314 @@ int dsess_recommend_host(const srn_index* idx, srn_device_sessions* s, const uin
     if (rc) return rc;
     for (size_t q = 0; q < n; ++q)
         if (counts[q] == 0xFFFFFFFFu) return fail(SRN_ERANGE, "a query exceeded the kernel's table limits");
+    return SRN_OK;
+}
+
+// ---- snapshot: count, bulk export / import, resize, growth, the file form ----
+namespace {
+int xs_ensure(srn_device_sessions* s, size_t bytes) {   // (the previous call may still use the scratch: wait for it before it is freed)
+    if (bytes <= s->xs_bytes) return SRN_OK;
+    HIP_TRY(hipEventSynchronize(s->last));
+    return ensure(&s->xs, &s->xs_bytes, bytes);
+}
+struct DevBuf {   // a blocking call's own device copies
+    char* p = nullptr;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+    int alloc(size_t bytes, const char* who) {
+        if (hipMalloc((void**)&p, bytes ? bytes : 256) != hipSuccess) { (void)hipGetLastError(); p = nullptr; return fail(SRN_ENOMEM, std::string(who) + ": no device memory for the staging copies"); }
+        return SRN_OK;
+    }
+};
+// offsets of the dense arrays of n entries in one buffer: key_hi | key_lo | epoch | len | items | (a u64 word)
+struct Dense { size_t hi, lo, ep, len, items, word, bytes; };
+Dense dense_layout(size_t n, size_t items_stride) {
+    Dense d{};
+    d.hi = 0; d.lo = d.hi + align256(n * 8); d.ep = d.lo + align256(n * 8); d.len = d.ep + align256(n * 8); d.items = d.len + align256(n * 4);
+    d.word = d.items + align256(n * items_stride * 8); d.bytes = d.word + 256;
+    return d;
+}
+
+// flags, scan, scatter on `st`, which already waits for `last` (mu held)
+int export_enqueue(srn_device_sessions* s, uint64_t now, size_t cap, uint64_t* d_hi, uint64_t* d_lo, uint64_t* d_epoch, uint32_t* d_len, uint64_t* d_items,
+                   size_t items_stride, uint64_t* d_n, hipStream_t st) {
+    const size_t n1 = (size_t)s->n_slots + 1;
+    size_t tmp = 0;
+    HIP_TRY(rocprim::exclusive_scan(nullptr, tmp, (uint32_t*)nullptr, (uint32_t*)nullptr, 0u, n1, rocprim::plus<uint32_t>(), st));
+    const size_t w = align256(n1 * 4);
+    int rc = xs_ensure(s, 2 * w + align256(tmp)); if (rc) return rc;
+    uint32_t* flag = (uint32_t*)s->xs; uint32_t* pos = (uint32_t*)(s->xs + w);
+    sess_live_flag<<<grid_for(n1), kTPB, 0, st>>>(s->tab(), now, s->ttl, flag);
+    HIP_TRY(rocprim::exclusive_scan(s->xs + 2 * w, tmp, flag, pos, 0u, n1, rocprim::plus<uint32_t>(), st));
+    ExportArgs a{};
+    a.t = s->tab(); a.pos = pos; a.now = now; a.ttl = s->ttl; a.cap = cap; a.items_stride = items_stride;
+    a.key_hi = d_hi; a.key_lo = d_lo; a.epoch = d_epoch; a.len = d_len; a.items = d_items; a.d_n = d_n;
+    a.lanes_shift = s->stride == 128 ? 3 : 4;
+    sess_export_scatter<<<grid_for((size_t)s->n_slots << a.lanes_shift), kTPB, 0, st>>>(a);
+    HIP_TRY(hipGetLastError());
+    return SRN_OK;
+}
+
+// the blocking export into host arrays (own stream, mu held, behind `last`).  exact_stride: items_stride need only hold the longest live session (save)
+int export_host_locked(srn_device_sessions* s, uint64_t now, size_t cap, uint64_t* hi, uint64_t* lo, uint64_t* epoch, uint32_t* len, uint64_t* items,
+                       size_t items_stride, size_t* n, bool exact_stride, const char* who) {
+    uint64_t occupied = 0, live = 0, longest = 0;
+    int rc = count_max(s, now, &occupied, &live, &longest); if (rc) return rc;
+    *n = (size_t)live;
+    if (items_stride < (exact_stride ? longest : (uint64_t)s->len_bound)) return fail(SRN_ERANGE, std::string(who) + ": items_stride below the longest session the store may hold");
+    if (live > cap) return fail(SRN_ERANGE, std::string(who) + ": more live sessions than the arrays hold (*n is their number)");
+    if (live == 0) return SRN_OK;
+    const Dense d = dense_layout(live, items_stride);
+    DevBuf b; if ((rc = b.alloc(d.bytes, who))) return rc;
+    rc = export_enqueue(s, now, live, (uint64_t*)(b.p + d.hi), (uint64_t*)(b.p + d.lo), (uint64_t*)(b.p + d.ep), (uint32_t*)(b.p + d.len), (uint64_t*)(b.p + d.items),
+                        items_stride, (uint64_t*)(b.p + d.word), s->own);
+    if (rc) { (void)hipStreamSynchronize(s->own); return rc; }
+    hipError_t e = hipMemcpyAsync(hi, b.p + d.hi, live * 8, hipMemcpyDeviceToHost, s->own);
+    if (e == hipSuccess) e = hipMemcpyAsync(lo, b.p + d.lo, live * 8, hipMemcpyDeviceToHost, s->own);
+    if (e == hipSuccess) e = hipMemcpyAsync(epoch, b.p + d.ep, live * 8, hipMemcpyDeviceToHost, s->own);
+    if (e == hipSuccess) e = hipMemcpyAsync(len, b.p + d.len, live * 4, hipMemcpyDeviceToHost, s->own);
+    if (e == hipSuccess && items_stride) e = hipMemcpyAsync(items, b.p + d.items, live * items_stride * 8, hipMemcpyDeviceToHost, s->own);
+    const hipError_t e2 = hipStreamSynchronize(s->own);
+    if (e != hipSuccess || e2 != hipSuccess) return fail(SRN_EHIP, std::string(who) + ": " + hipGetErrorString(e != hipSuccess ? e : e2));
+    return SRN_OK;
+}
+
+// validate (blocks), apply the capacity rule, then sort / find / write on `st` (mu held).  Nothing is changed before every check has passed.
+int import_locked(srn_device_sessions* s, const uint64_t* d_hi, const uint64_t* d_lo, const uint64_t* d_epoch, const uint32_t* d_len, const uint64_t* d_items,
+                  size_t items_stride, size_t n, hipStream_t st, const char* who) {
+    if (n == 0) return SRN_OK;
+    if (n > (1ull << 30)) return fail(SRN_ERANGE, std::string(who) + ": more than 2^30 entries in one call");
+    size_t tmp = 0;
+    HIP_TRY(rocprim::radix_sort_pairs(nullptr, tmp, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, n, 0, 64, st));
+    const size_t w = align256(n * 4), k8 = align256(n * 8);
+    const size_t o_word = 0, o_keyA = 256, o_keyB = o_keyA + k8, o_idxA = o_keyB + k8, o_idxB = o_idxA + w, o_slot = o_idxB + w, o_win = o_slot + w, o_tmp = o_win + w;
+    int rc = xs_ensure(s, o_tmp + align256(tmp)); if (rc) return rc;
+    char* b = s->xs;
+    const uint32_t n32 = (uint32_t)n; const dim3 gn = grid_for(n);
+    HIP_TRY(hipStreamWaitEvent(st, s->last, 0));
+    HIP_TRY(hipMemsetAsync(b + o_word, 0, 4, st));
+    sess_import_maxlen<<<gn, kTPB, 0, st>>>(d_len, n32, (uint32_t*)(b + o_word));
+    HIP_TRY(hipGetLastError());
+    uint32_t longest = 0;
+    HIP_TRY(hipMemcpyAsync(&longest, b + o_word, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (longest > s->items_cap) return fail(SRN_ERANGE, std::string(who) + ": a session is longer than the store's items_cap");
+    if (longest > items_stride) return fail(SRN_ERANGE, std::string(who) + ": a session is longer than items_stride");
+    // every entry counts as a new key; an import reclaims nothing (now = 1: no entry is older than the TTL), so a refused import leaves every slot where it was
+    if ((rc = make_room(s, n, 1))) return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    uint64_t* keyA = (uint64_t*)(b + o_keyA); uint64_t* keyB = (uint64_t*)(b + o_keyB); uint32_t* idxA = (uint32_t*)(b + o_idxA); uint32_t* idxB = (uint32_t*)(b + o_idxB);
+    size_t t1 = tmp;
+    sess_keys_init<<<gn, kTPB, 0, st>>>(d_lo, n32, keyA, idxA);
+    HIP_TRY(rocprim::radix_sort_pairs(b + o_tmp, t1, keyA, keyB, idxA, idxB, n, 0, 64, st));
+    sess_keys_gather<<<gn, kTPB, 0, st>>>(d_hi, idxB, n32, keyA);
+    t1 = tmp; HIP_TRY(rocprim::radix_sort_pairs(b + o_tmp, t1, keyA, keyB, idxB, idxA, n, 0, 64, st));
+    ImportArgs a{};
+    a.t = s->tab(); a.key_hi = d_hi; a.key_lo = d_lo; a.epoch = d_epoch; a.len = d_len; a.items = d_items; a.items_stride = items_stride;
+    a.order = idxA; a.n = n32; a.slot_of = (uint32_t*)(b + o_slot); a.win = (uint32_t*)(b + o_win); a.err = s->err();
+    sess_import_find<<<gn, kTPB, 0, st>>>(a);
+    sess_import_write<<<grid_for(n * 16), kTPB, 0, st>>>(a);
+    HIP_TRY(hipGetLastError());
+    s->bound += n;
+    s->len_bound = std::max<uint32_t>(s->len_bound, longest);
+    (void)hipEventRecord(s->last, st);
+    HIP_TRY(hipStreamSynchronize(st));
+    return SRN_OK;
+}
+
+// ---- the file form: a 96-byte little-endian header, then the arrays of the export ----
+constexpr char kSnapMagic[8] = {'S', 'R', 'N', 'S', 'E', 'S', 'S', '\0'};
+constexpr uint32_t kSnapVersion = 1, kSnapHeader = 96;
+struct SnapHeader {
+    char magic[8]; uint32_t version, header_bytes;
+    uint64_t n, longest, items_stride, capacity, items_cap, ttl, idle, saved_at, payload_bytes, checksum;
+};
+static_assert(sizeof(SnapHeader) == kSnapHeader, "snapshot header");
+struct SnapOffsets { uint64_t hi, lo, ep, len, items, bytes; };
+// false: the sizes overflow
+bool snap_offsets(uint64_t n, uint64_t stride, SnapOffsets* o) {
+    if (n > (1ull << 30) || stride > SRN_MAX_SESSION_LEN) return false;
+    o->hi = 0; o->lo = n * 8; o->ep = n * 16; o->len = n * 24; o->items = n * 24 + (n * 4 + 7) / 8 * 8; o->bytes = o->items + n * stride * 8;
+    return true;
+}
+// sum over the payload's 8-byte words w[i] of mix64(w[i] + (i + 1) * 0x9E3779B97F4A7C15), mod 2^64
+uint64_t snap_checksum(const char* p, uint64_t bytes) {
+    uint64_t sum = 0;
+    for (uint64_t i = 0; i < bytes / 8; ++i) { uint64_t w; std::memcpy(&w, p + i * 8, 8); sum += mix64(w + (i + 1) * 0x9E3779B97F4A7C15ull); }
+    return sum;
+}
+// reads and verifies the whole file: anything that is not a complete, consistent snapshot is SRN_EIO, and no offset is used before it has been checked against the size
+int snap_read(const char* path, std::vector<char>* buf, SnapHeader* h, SnapOffsets* o) {
+    FILE* f = std::fopen(path, "rb");
+    if (!f) return fail(SRN_EIO, std::string("cannot open ") + path);
+    struct Close { FILE* f; ~Close() { std::fclose(f); } } closer{f};
+    if (std::fread(h, 1, kSnapHeader, f) != kSnapHeader) return fail(SRN_EIO, std::string(path) + ": shorter than a session snapshot's header");
+    if (std::memcmp(h->magic, kSnapMagic, 8) != 0) return fail(SRN_EIO, std::string(path) + ": not a session snapshot (magic)");
+    if (h->version != kSnapVersion) return fail(SRN_EIO, std::string(path) + ": unknown session snapshot version");
+    if (h->header_bytes != kSnapHeader || !snap_offsets(h->n, h->items_stride, o) || o->bytes != h->payload_bytes || h->longest > h->items_stride)
+        return fail(SRN_EIO, std::string(path) + ": the header's sizes do not add up");
+    if (std::fseek(f, 0, SEEK_END) != 0) return fail(SRN_EIO, std::string(path) + ": cannot seek");
+    const long size = std::ftell(f);
+    if (size < 0 || (uint64_t)size != kSnapHeader + h->payload_bytes) return fail(SRN_EIO, std::string(path) + ": the file's size is not what its header says");
+    buf->resize(h->payload_bytes);
+    if (std::fseek(f, kSnapHeader, SEEK_SET) != 0 || (h->payload_bytes && std::fread(buf->data(), 1, h->payload_bytes, f) != h->payload_bytes))
+        return fail(SRN_EIO, std::string(path) + ": short read");
+    if (snap_checksum(buf->data(), h->payload_bytes) != h->checksum) return fail(SRN_EIO, std::string(path) + ": checksum mismatch");
+    uint64_t longest = 0;
+    for (uint64_t i = 0; i < h->n; ++i) { uint32_t l; std::memcpy(&l, buf->data() + o->len + i * 4, 4); longest = std::max<uint64_t>(longest, l); }
+    if (longest != h->longest) return fail(SRN_EIO, std::string(path) + ": a session's length disagrees with the header's longest session");
+    return SRN_OK;
+}
+}  // namespace
+
+int dsess_count(srn_device_sessions* s, uint64_t now_secs, uint64_t* occupied, uint64_t* live) {
+    if (!s) return fail(SRN_EINVAL, "srn_device_sessions_count: null store");
+    const uint64_t now = now_secs ? now_secs : wall_secs();
+    std::lock_guard<std::mutex> g(s->mu);
+    int rc = own_after_last(s); if (rc) return rc;
+    uint64_t o = 0, l = 0;
+    if ((rc = count(s, now, &o, &l))) return rc;
+    if (occupied) *occupied = o;
+    if (live) *live = l;
+    return SRN_OK;
+}
+
+int dsess_export_device(srn_device_sessions* s, uint64_t now_secs, size_t cap, uint64_t* d_hi, uint64_t* d_lo, uint64_t* d_epoch, uint32_t* d_len, uint64_t* d_items,
+                        size_t items_stride, uint64_t* d_n, void* stream) {
+    if (!s || !d_n || (cap && (!d_hi || !d_lo || !d_epoch || !d_len || (items_stride && !d_items)))) return fail(SRN_EINVAL, "srn_device_sessions_export_device: null argument");
+    const uint64_t now = now_secs ? now_secs : wall_secs();
+    hipStream_t st = (hipStream_t)stream;
+    std::lock_guard<std::mutex> g(s->mu);
+    if (items_stride < s->len_bound) return fail(SRN_ERANGE, "srn_device_sessions_export_device: items_stride below the longest session the store may hold");
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipStreamWaitEvent(st, s->last, 0));
+    const int rc = export_enqueue(s, now, cap, d_hi, d_lo, d_epoch, d_len, d_items, items_stride, d_n, st);
+    (void)hipEventRecord(s->last, st);
+    return rc;
+}
+
+int dsess_export_host(srn_device_sessions* s, uint64_t now_secs, size_t cap, uint64_t* hi, uint64_t* lo, uint64_t* epoch, uint32_t* len, uint64_t* items,
+                      size_t items_stride, size_t* n) {
+    if (!s || !n || (cap && (!hi || !lo || !epoch || !len || (items_stride && !items)))) return fail(SRN_EINVAL, "srn_device_sessions_export: null argument");
+    const uint64_t now = now_secs ? now_secs : wall_secs();
+    std::lock_guard<std::mutex> g(s->mu);
+    int rc = own_after_last(s); if (rc) return rc;
+    return export_host_locked(s, now, cap, hi, lo, epoch, len, items, items_stride, n, false, "srn_device_sessions_export");
+}
+
+int dsess_import_device(srn_device_sessions* s, const uint64_t* d_hi, const uint64_t* d_lo, const uint64_t* d_epoch, const uint32_t* d_len, const uint64_t* d_items,
+                        size_t items_stride, size_t n, void* stream) {
+    if (!s || (n && (!d_hi || !d_lo || !d_epoch || !d_len || (items_stride && !d_items)))) return fail(SRN_EINVAL, "srn_device_sessions_import_device: null argument");
+    std::lock_guard<std::mutex> g(s->mu);
+    HIP_TRY(hipSetDevice(s->device));
+    return import_locked(s, d_hi, d_lo, d_epoch, d_len, d_items, items_stride, n, (hipStream_t)stream, "srn_device_sessions_import_device");
+}
+
+int dsess_import_host(srn_device_sessions* s, const uint64_t* hi, const uint64_t* lo, const uint64_t* epoch, const uint32_t* len, const uint64_t* items,
+                      size_t items_stride, size_t n) {
+    const char* who = "srn_device_sessions_import";
+    if (!s || (n && (!hi || !lo || !epoch || !len || (items_stride && !items)))) return fail(SRN_EINVAL, std::string(who) + ": null argument");
+    if (n == 0) return SRN_OK;
+    if (n > (1ull << 30)) return fail(SRN_ERANGE, std::string(who) + ": more than 2^30 entries in one call");
+    if (items_stride > SRN_MAX_SESSION_LEN) return fail(SRN_ERANGE, std::string(who) + ": items_stride above SRN_MAX_SESSION_LEN");
+    std::lock_guard<std::mutex> g(s->mu);
+    int rc = own_after_last(s); if (rc) return rc;
+    const Dense d = dense_layout(n, items_stride);
+    DevBuf b; if ((rc = b.alloc(d.bytes, who))) return rc;
+    hipError_t e = hipMemcpyAsync(b.p + d.hi, hi, n * 8, hipMemcpyHostToDevice, s->own);
+    if (e == hipSuccess) e = hipMemcpyAsync(b.p + d.lo, lo, n * 8, hipMemcpyHostToDevice, s->own);
+    if (e == hipSuccess) e = hipMemcpyAsync(b.p + d.ep, epoch, n * 8, hipMemcpyHostToDevice, s->own);
+    if (e == hipSuccess) e = hipMemcpyAsync(b.p + d.len, len, n * 4, hipMemcpyHostToDevice, s->own);
+    if (e == hipSuccess && items_stride) e = hipMemcpyAsync(b.p + d.items, items, n * items_stride * 8, hipMemcpyHostToDevice, s->own);
+    if (e != hipSuccess) { (void)hipStreamSynchronize(s->own); return fail(SRN_EHIP, std::string(who) + ": " + hipGetErrorString(e)); }
+    rc = import_locked(s, (const uint64_t*)(b.p + d.hi), (const uint64_t*)(b.p + d.lo), (const uint64_t*)(b.p + d.ep), (const uint32_t*)(b.p + d.len),
+                       (const uint64_t*)(b.p + d.items), items_stride, n, s->own, who);
+    (void)hipStreamSynchronize(s->own);
+    return rc;
+}
+
+int dsess_resize(srn_device_sessions* s, size_t capacity, size_t items_cap, uint64_t now_secs) {
+    if (!s) return fail(SRN_EINVAL, "srn_device_sessions_resize: null store");
+    if (capacity == 0) return fail(SRN_EINVAL, "srn_device_sessions_resize: capacity must be > 0");
+    if (capacity > (1ull << 30)) return fail(SRN_ERANGE, "srn_device_sessions_resize: capacity above 2^30 sessions");
+    if (items_cap > SRN_MAX_SESSION_LEN) return fail(SRN_ERANGE, "srn_device_sessions_resize: items_cap above SRN_MAX_SESSION_LEN");
+    const uint64_t now = now_secs ? now_secs : wall_secs();
+    std::lock_guard<std::mutex> g(s->mu);
+    int rc = own_after_last(s); if (rc) return rc;
+    return resize_locked(s, capacity, items_cap ? items_cap : s->items_cap, now, "srn_device_sessions_resize");
+}
+
+int dsess_set_max_capacity(srn_device_sessions* s, size_t max_capacity) {
+    if (!s) return fail(SRN_EINVAL, "srn_device_sessions_set_max_capacity: null store");
+    if (max_capacity > (1ull << 30)) return fail(SRN_ERANGE, "srn_device_sessions_set_max_capacity: above 2^30 sessions");
+    std::lock_guard<std::mutex> g(s->mu);
+    s->max_capacity = max_capacity;
+    return SRN_OK;
+}
+
+int dsess_growth(srn_device_sessions* s, uint64_t* max_capacity, uint64_t* grows, uint64_t* resizes) {
+    if (!s) return fail(SRN_EINVAL, "srn_device_sessions_growth: null store");
+    std::lock_guard<std::mutex> g(s->mu);
+    if (max_capacity) *max_capacity = s->max_capacity;
+    if (grows) *grows = s->grows;
+    if (resizes) *resizes = s->resizes;
+    return SRN_OK;
+}
+
+int dsess_file_info(const char* path, srn_device_sessions_file_info_t* out) {
+    if (!path || !out) return fail(SRN_EINVAL, "srn_device_sessions_file_info: null argument");
+    std::vector<char> buf; SnapHeader h; SnapOffsets o;
+    const int rc = snap_read(path, &buf, &h, &o); if (rc) return rc;
+    *out = srn_device_sessions_file_info_t{h.version, h.n, h.longest, h.items_stride, h.capacity, h.items_cap, h.ttl, h.idle, h.saved_at, h.payload_bytes};
+    return SRN_OK;
+}
+
+int dsess_save(srn_device_sessions* s, const char* path, uint64_t now_secs) {
+    if (!s || !path) return fail(SRN_EINVAL, "srn_device_sessions_save: null argument");
+    const uint64_t now = now_secs ? now_secs : wall_secs();
+    SnapHeader h{}; SnapOffsets o{}; std::vector<char> buf;
+    {
+        std::lock_guard<std::mutex> g(s->mu);
+        int rc = own_after_last(s); if (rc) return rc;
+        uint64_t occupied = 0, live = 0, longest = 0;
+        if ((rc = count_max(s, now, &occupied, &live, &longest))) return rc;
+        std::memcpy(h.magic, kSnapMagic, 8);
+        h.version = kSnapVersion; h.header_bytes = kSnapHeader; h.n = live; h.longest = longest; h.items_stride = longest;
+        h.capacity = s->capacity; h.items_cap = s->items_cap; h.ttl = s->ttl; h.idle = s->idle; h.saved_at = now;
+        if (!snap_offsets(h.n, h.items_stride, &o)) return fail(SRN_ERANGE, "srn_device_sessions_save: the store is too large for the file form");
+        buf.assign(o.bytes, 0);
+        size_t n = 0;
+        char* p = buf.data();
+        rc = export_host_locked(s, now, live, (uint64_t*)(p + o.hi), (uint64_t*)(p + o.lo), (uint64_t*)(p + o.ep), (uint32_t*)(p + o.len), (uint64_t*)(p + o.items),
+                                h.items_stride, &n, true, "srn_device_sessions_save");
+        if (rc) return rc;
+    }
+    h.payload_bytes = o.bytes; h.checksum = snap_checksum(buf.data(), o.bytes);
+    // a temporary name in the same directory, then a rename: a crash leaves the previous snapshot
+    const std::string tmp = std::string(path) + ".tmp." + std::to_string((unsigned long long)::getpid());
+    FILE* f = std::fopen(tmp.c_str(), "wb");
+    if (!f) return fail(SRN_EIO, "srn_device_sessions_save: cannot create " + tmp);
+    bool ok = std::fwrite(&h, 1, kSnapHeader, f) == kSnapHeader && (o.bytes == 0 || std::fwrite(buf.data(), 1, o.bytes, f) == o.bytes);
+    ok = ok && std::fflush(f) == 0 && ::fsync(::fileno(f)) == 0;
+    ok = (std::fclose(f) == 0) && ok;
+    if (!ok || std::rename(tmp.c_str(), path) != 0) { std::remove(tmp.c_str()); return fail(SRN_EIO, std::string("srn_device_sessions_save: cannot write ") + path); }
+    return SRN_OK;
+}
+
+int dsess_load(const char* path, int device, size_t capacity, size_t items_cap, uint64_t ttl_secs, uint64_t idle_secs, srn_device_sessions** out) {
+    if (!path || !out) return fail(SRN_EINVAL, "srn_device_sessions_load: null argument");
+    *out = nullptr;
+    std::vector<char> buf; SnapHeader h; SnapOffsets o;
+    int rc = snap_read(path, &buf, &h, &o); if (rc) return rc;
+    const uint64_t cap = capacity ? capacity : std::max<uint64_t>(std::max<uint64_t>(h.capacity, h.n), 1), ic = items_cap ? items_cap : h.items_cap;
+    if (h.n > cap) return fail(SRN_ENOMEM, "srn_device_sessions_load: the snapshot holds more sessions than the capacity");
+    if (h.longest > ic) return fail(SRN_ERANGE, "srn_device_sessions_load: the snapshot's longest session exceeds items_cap");
+    srn_device_sessions* s = nullptr;
+    if ((rc = dsess_create(device, cap, ic, ttl_secs ? ttl_secs : h.ttl, idle_secs ? idle_secs : h.idle, &s))) return rc;
+    const char* p = buf.data();
+    rc = dsess_import_host(s, (const uint64_t*)(p + o.hi), (const uint64_t*)(p + o.lo), (const uint64_t*)(p + o.ep), (const uint32_t*)(p + o.len), (const uint64_t*)(p + o.items),
+                           h.items_stride, h.n);
+    if (rc) { dsess_free(s); return rc; }
+    *out = s;
     return SRN_OK;
 }
 

@@ -3,7 +3,10 @@
 The reference answers each /v1/recommend call with its own vmisknn::predict on an actix worker thread
 (src/endpoints/recommend_resource.rs:56-62).  `Batcher.predict` has that call's shape and may be called from many threads
 at once; the library folds the waiting calls into one kernel launch.  No HTTP and no session store here."""
+import collections
 import ctypes as C
+import os
+import struct
 
 import numpy as np
 
@@ -106,14 +109,180 @@ def session_keys(session_ids):
     return hi, lo
 
 
+SessionCount = collections.namedtuple("SessionCount", "occupied live")
+
+# ---- the snapshot file of a device store, in pure NumPy: no GPU, no library ----
+_SNAP_MAGIC, _SNAP_VERSION, _SNAP_HEADER = b"SRNSESS\0", 1, 96
+_SNAP_FIELDS = ("n", "longest_session", "items_stride", "capacity", "items_cap", "ttl_secs", "idle_secs", "saved_at_secs", "payload_bytes", "checksum")
+
+
+def _snap_checksum(payload):
+    """sum of mix64(w[i] + (i + 1) * 0x9E3779B97F4A7C15) over the payload's little-endian 8-byte words, mod 2^64"""
+    w = np.frombuffer(payload, "<u8").astype(np.uint64)
+    x = w + np.arange(1, w.size + 1, dtype=np.uint64) * np.uint64(0x9E3779B97F4A7C15)
+    x ^= x >> np.uint64(33)
+    x *= np.uint64(0xff51afd7ed558ccd)
+    x ^= x >> np.uint64(33)
+    x *= np.uint64(0xc4ceb9fe1a85ec53)
+    x ^= x >> np.uint64(33)
+    return int(x.sum(dtype=np.uint64))
+
+
+def write_session_snapshot(path, keys, epochs, sessions, capacity=None, items_cap=None, ttl_secs=30 * 60, idle_secs=20 * 60, saved_at=0, items_stride=None):
+    """Writes sessions[i] (a list of item ids) under keys[i] with epochs[i] as a snapshot file DeviceSessionStore.load reads: how a store is seeded from another
+    system's dump.  keys: (hi, lo) uint64 arrays, or a list of 128-bit integers.  capacity / items_cap: what load uses by default (None: n / the longest session)."""
+    if isinstance(keys, tuple):
+        hi, lo = (capi.as_u64(a) for a in keys)
+    else:
+        hi = np.array([int(k) >> 64 for k in keys], np.uint64)
+        lo = np.array([int(k) & (2**64 - 1) for k in keys], np.uint64)
+    n = len(sessions)
+    ep = capi.as_u64(epochs)
+    if not (len(hi) == len(lo) == len(ep) == n):
+        raise ValueError("keys, epochs and sessions differ in length")
+    ln = np.array([len(s) for s in sessions], np.uint32)
+    longest = int(ln.max()) if n else 0
+    stride = longest if items_stride is None else int(items_stride)
+    if stride < longest or stride > capi.MAX_SESSION_LEN:
+        raise ValueError("items_stride must hold the longest session and be at most %d" % capi.MAX_SESSION_LEN)
+    items = np.zeros((n, stride), np.uint64)
+    for i, s in enumerate(sessions):
+        items[i, :len(s)] = np.asarray(s, np.uint64)
+    payload = b"".join([hi.astype("<u8").tobytes(), lo.astype("<u8").tobytes(), ep.astype("<u8").tobytes(), ln.astype("<u4").tobytes(), b"\0" * (-4 * n % 8),
+                        items.astype("<u8").tobytes()])
+    values = (n, longest, stride, max(int(capacity or n), 1), max(int(items_cap or longest), 1), int(ttl_secs), int(idle_secs), int(saved_at), len(payload),
+              _snap_checksum(payload))
+    header = _SNAP_MAGIC + struct.pack("<II10Q", _SNAP_VERSION, _SNAP_HEADER, *values)
+    tmp = "%s.tmp.%d" % (os.fspath(path), os.getpid())
+    with open(tmp, "wb") as f:
+        f.write(header + payload)
+    os.replace(tmp, path)
+
+
+def read_session_snapshot(path):
+    """-> {"key_hi", "key_lo", "epoch", "len", "items"[n, items_stride], "sessions" (lists), and the header's fields}; ValueError for anything but a whole snapshot."""
+    raw = open(path, "rb").read()
+    if len(raw) < _SNAP_HEADER or raw[:8] != _SNAP_MAGIC:
+        raise ValueError("%s: not a session snapshot" % path)
+    version, header_bytes, *values = struct.unpack("<II10Q", raw[8:_SNAP_HEADER])
+    h = dict(zip(_SNAP_FIELDS, values))
+    n, stride = h["n"], h["items_stride"]
+    o_len = 24 * n
+    o_items = o_len + (4 * n + 7) // 8 * 8
+    if version != _SNAP_VERSION or header_bytes != _SNAP_HEADER or n > 2**30 or stride > capi.MAX_SESSION_LEN or h["longest_session"] > stride or \
+            h["payload_bytes"] != o_items + 8 * n * stride or len(raw) != _SNAP_HEADER + h["payload_bytes"]:
+        raise ValueError("%s: unknown version, or sizes that do not add up" % path)
+    payload = raw[_SNAP_HEADER:]
+    if _snap_checksum(payload) != h["checksum"]:
+        raise ValueError("%s: checksum mismatch" % path)
+    out = dict(h, version=version)
+    out["key_hi"], out["key_lo"], out["epoch"] = (np.frombuffer(payload, "<u8", n, 8 * n * j).astype(np.uint64) for j in range(3))
+    out["len"] = np.frombuffer(payload, "<u4", n, o_len).astype(np.uint32)
+    out["items"] = np.frombuffer(payload, "<u8", n * stride, o_items).astype(np.uint64).reshape(n, stride)
+    if n and int(out["len"].max()) != h["longest_session"]:
+        raise ValueError("%s: a session's length disagrees with the header" % path)
+    out["sessions"] = [[int(x) for x in row[:l]] for row, l in zip(out["items"], out["len"])]
+    return out
+
+
 class DeviceSessionStore:
     """The evolving sessions in the GPU's memory: what recommend_batch reads and updates.  get / update / sweep mirror SessionStore's, for one key, from the host."""
 
-    def __init__(self, device_or_index, capacity, items_cap=16, ttl_secs=30 * 60, idle_secs=20 * 60):
+    def __init__(self, device_or_index, capacity, items_cap=16, ttl_secs=30 * 60, idle_secs=20 * 60, max_capacity=None):
+        """max_capacity: opt-in growth -- a batch the capacity rule would refuse doubles the capacity (up to max_capacity) instead; None = a fixed capacity."""
         device = device_or_index if isinstance(device_or_index, int) else device_or_index.info["device"]
         h = C.c_void_p()
         capi.check(capi.lib().srn_device_sessions_create(int(device), int(capacity), int(items_cap), int(ttl_secs), int(idle_secs), C.byref(h)))
         self._h, self.device, self.items_cap = h, int(device), int(items_cap)
+        if max_capacity:
+            capi.check(capi.lib().srn_device_sessions_set_max_capacity(self._h, int(max_capacity)))
+
+    @classmethod
+    def load(cls, device_or_index, path, capacity=None, items_cap=None, ttl_secs=None, idle_secs=None):
+        """A store on that GPU with the sessions of a snapshot file (save, write_session_snapshot); None = the value the file records."""
+        device = device_or_index if isinstance(device_or_index, int) else device_or_index.info["device"]
+        h = C.c_void_p()
+        capi.check(capi.lib().srn_device_sessions_load(os.fsencode(path), int(device), int(capacity or 0), int(items_cap or 0), int(ttl_secs or 0), int(idle_secs or 0),
+                                                       C.byref(h)))
+        self = cls.__new__(cls)
+        self._h, self.device = h, int(device)
+        self.items_cap = int(self.stats["items_cap"])
+        return self
+
+    def save(self, path, now=0):
+        """The live sessions at `now` as a snapshot file, written under a temporary name and renamed."""
+        capi.check(capi.lib().srn_device_sessions_save(self._h, os.fsencode(path), int(now)))
+
+    def count(self, now=0):
+        """-> SessionCount(occupied, live): exact, from the device; live = what a sweep at `now` would keep."""
+        o, l = C.c_uint64(), C.c_uint64()
+        capi.check(capi.lib().srn_device_sessions_count(self._h, int(now), C.byref(o), C.byref(l)))
+        return SessionCount(o.value, l.value)
+
+    def export(self, now=0, device=False):
+        """The live sessions at `now`, in slot order -> (hi, lo), epoch, len, items[n, items_cap] (zero beyond len).  NumPy arrays, or with device=True tensors
+        on the store's GPU, written on the current stream."""
+        L = capi.lib()
+        cap = self.count(now).live
+        while True:
+            stride = int(self.stats["items_cap"])
+            if device:
+                import torch
+                dev = torch.device("cuda", self.device)
+                hi, lo, ep = (torch.zeros(cap, dtype=torch.int64, device=dev) for _ in range(3))
+                ln = torch.zeros(cap, dtype=torch.int32, device=dev)
+                it = torch.zeros((cap, stride), dtype=torch.int64, device=dev)
+                d_n = torch.zeros(1, dtype=torch.int64, device=dev)
+                stream = torch.cuda.current_stream(self.device).cuda_stream
+                capi.check(L.srn_device_sessions_export_device(self._h, int(now), cap, *(C.c_void_p(t.data_ptr()) for t in (hi, lo, ep, ln, it)), stride,
+                                                               C.c_void_p(d_n.data_ptr()), C.c_void_p(stream)))
+                n = int(d_n.item())
+            else:
+                hi, lo, ep = (np.zeros(cap, np.uint64) for _ in range(3))
+                ln, it, got = np.zeros(cap, np.uint32), np.zeros((cap, stride), np.uint64), C.c_size_t()
+                rc = L.srn_device_sessions_export(self._h, int(now), cap, capi.ptr(hi), capi.ptr(lo), capi.ptr(ep), capi.ptr(ln), capi.ptr(it), stride, C.byref(got))
+                n = got.value
+                if rc != 0 and not (rc == capi.SRN_ERANGE and n > cap):
+                    capi.check(rc)
+            if n <= cap:                                    # (more: the store grew between the count and the export)
+                return (hi[:n], lo[:n]), ep[:n], ln[:n], it[:n]
+            cap = n
+
+    def import_entries(self, keys, epoch, len, items):
+        """Inserts the entries (keys[i], epoch[i], items[i, :len[i]]) under the merge rule: the larger epoch wins, a tie replaces.  NumPy arrays, or tensors on the
+        store's GPU (read on the current stream)."""
+        hi, lo = keys
+        arrs = [hi, lo, epoch, len, items]
+        n = arrs[0].shape[0]
+        if any(a.shape[0] != n for a in arrs) or items.ndim != 2:
+            raise ValueError("keys, epoch and len must have one entry per row of items[n, stride]")
+        stride = int(items.shape[1])
+        on_gpu = [_is_torch(a) and a.device.type == "cuda" for a in arrs]
+        if any(on_gpu):
+            import torch
+            if not all(on_gpu) or any(a.device.index != self.device for a in arrs):
+                raise ValueError("keys, epoch, len and items must all be tensors on the store's GPU (device %d), or none of them" % self.device)
+            if any(a.dtype not in (torch.int64, getattr(torch, "uint64", torch.int64)) for a in (hi, lo, epoch, items)) or \
+                    len.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)):
+                raise TypeError("keys, epoch and items must be 64-bit and len 32-bit integer tensors")
+            t = [a.contiguous() for a in arrs]
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            capi.check(capi.lib().srn_device_sessions_import_device(self._h, *(C.c_void_p(a.data_ptr()) for a in t), stride, n, C.c_void_p(stream)))
+            return
+        hi, lo, epoch, items = (capi.as_u64(a.numpy() if _is_torch(a) else a) for a in (hi, lo, epoch, items))
+        ln = capi.as_u32(len.numpy() if _is_torch(len) else len)
+        capi.check(capi.lib().srn_device_sessions_import(self._h, capi.ptr(hi), capi.ptr(lo), capi.ptr(epoch), capi.ptr(ln), capi.ptr(items), stride, n))
+
+    def resize(self, capacity, items_cap=None, now=0):
+        """Rebuilds the live sessions at `now` into tables of another capacity and / or items_cap; on an error the store is unchanged."""
+        capi.check(capi.lib().srn_device_sessions_resize(self._h, int(capacity), int(items_cap or 0), int(now)))
+        self.items_cap = int(self.stats["items_cap"])
+
+    def growth(self):
+        """-> {"max_capacity", "grows" (automatic resizes), "resizes" (all resizes)}."""
+        m, g, r = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        capi.check(capi.lib().srn_device_sessions_growth(self._h, C.byref(m), C.byref(g), C.byref(r)))
+        return {"max_capacity": m.value, "grows": g.value, "resizes": r.value}
 
     def get_session_items(self, key, now=0, cap=256):
         out, n = np.zeros(max(cap, 1), np.uint64), C.c_size_t()
