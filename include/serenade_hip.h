@@ -202,6 +202,37 @@ int srn_index_serve_start(srn_index_t* idx, size_t k, size_t m, size_t how_many,
 int srn_index_serve_stop(srn_index_t* idx);
 int srn_index_serve_stats(const srn_index_t* idx, uint64_t* out_served, uint64_t* out_not_served, uint64_t* out_launches, uint32_t* out_lanes);
 
+/* ---- the device result cache ----------------------------------------------------------------------------------------------------------
+ * predict_next is a pure function of the index, the call's parameters and the query's item sequence.  srn_index_result_cache_enable keeps served rows in device memory
+ * ACROSS calls: a later query with the same sequence gets the cached row -- the very bytes the kernels wrote -- instead of being computed.  Opt-in; without it nothing
+ * changes (same plan, same kernels, same buffers).
+ *   rows      entries of the table (rounded up to whole buckets of `ways` entries; 12 + 8 * max_len + 16 * how_many bytes each).  ALL device memory of the cache is
+ *             allocated here (hipMalloc synchronises the device: enable before serving); calls allocate nothing for it afterwards.
+ *   max_len   1..8: sequences of 1..max_len items are cacheable.  The key is (length, the raw 64-bit ids in order), compared in full on every probe.
+ *   k, m, how_many, enable_business_logic   fixed here: the parameters the cached rows are computed with.  They are not part of the key.
+ * The cache is used by every call of the batch launch sequence that has these parameters and is on the fast path (m and how_many within the fast kernels, no SRN_NO_FAST):
+ * srn_predict_batch_device, srn_predict_batch's chunked path, srn_recommend_batch / _device, the batcher's batches.  Every other call on the index BYPASSES it, computes
+ * as without a cache and counts one bypassed_calls: other parameters, host batches of <= SRN_TINY_MAX sessions and srn_predict (the latency paths), the resident serve
+ * path, srn_predict_batch_debug, srn_find_neighbors, srn_evaluate.  An item shard has no cache (SRN_EINVAL).
+ * A call that uses the cache is served in the sorted order at every batch size, and SRN_FLAG_INPUTS_RESIDENT is ignored for it: the flag is a permission, and the hit
+ * rows are written into the caller's output buffers early in the call, which a previous call may still own on the library's side stream.
+ * Replacement: an empty entry of the bucket, else the least recently used one (stored or hit by the oldest call); never one stored or hit by the call itself.
+ * Returns SRN_EINVAL (rows == 0, a shard), SRN_ERANGE (max_len outside 1..8, the limits of srn_predict's arguments), SRN_ENODEV (no device), SRN_ENOMEM, and SRN_ESTATE
+ * when a cache is already enabled.  srn_index_result_cache_disable frees it (SRN_OK without one); _clear empties it; srn_index_set_attributes clears it (rows under the
+ * business rules depend on the flags); srn_index_free disables it.  _clear and _stats without a cache: SRN_ESTATE.
+ * srn_index_result_cache_stats waits for the cache's kernels enqueued so far.  lookups / hits / inserts / evictions are counted on the device since enable: cacheable
+ * queries looked up (one per group of equal queries where the call merges them) | of those, served from the cache | rows stored | of those, over a live entry. */
+typedef struct srn_result_cache_stats {
+    uint64_t rows, ways, bytes;                       /* entries, entries per bucket, device bytes */
+    uint32_t max_len, k, m, how_many, flags, reserved;
+    uint64_t lookups, hits, inserts, evictions;
+    uint64_t bypassed_calls, clears;                  /* calls on the index that did not use the cache | srn_index_result_cache_clear + srn_index_set_attributes */
+} srn_result_cache_stats_t;
+int srn_index_result_cache_enable(srn_index_t* idx, size_t rows, size_t max_len, size_t k, size_t m, size_t how_many, unsigned flags);
+int srn_index_result_cache_disable(srn_index_t* idx);
+int srn_index_result_cache_clear(srn_index_t* idx);
+int srn_index_result_cache_stats(const srn_index_t* idx, srn_result_cache_stats_t* out);
+
 /* srn_predict is re-entrant on one handle from any number of host threads, like predict() on the Arc<VMISIndex> the actix workers
  * share (src/bin/serving.rs:62-94).  Concurrent calls with the same (k, m, how_many, business flag) COMBINE into rounds: one batch
  * launch serves every call that arrived while the previous rounds ran (a lone caller runs alone, at once; environment

@@ -79,6 +79,11 @@ class DeviceSessionsFileInfo(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("version", "n", "longest_session", "items_stride", "capacity", "items_cap", "ttl_secs", "idle_secs", "saved_at_secs", "payload_bytes")]
 
 
+class ResultCacheStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("rows", "ways", "bytes")] + [(n, C.c_uint32) for n in ("max_len", "k", "m", "how_many", "flags", "reserved")] + \
+               [(n, C.c_uint64) for n in ("lookups", "hits", "inserts", "evictions", "bypassed_calls", "clears")]
+
+
 class Limits(C.Structure):
     _fields_ = [("max_how_many", C.c_uint32), ("max_session_len", C.c_uint32), ("max_k", C.c_uint32), ("reserved", C.c_uint32)]
 
@@ -109,6 +114,10 @@ SYMBOLS = {
     "srn_index_serve_start": (_i, [_vp, _sz, _sz, _sz, C.c_int, C.c_uint, C.c_uint, C.c_uint]),
     "srn_index_serve_stop": (_i, [_vp]),
     "srn_index_serve_stats": (_i, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
+    "srn_index_result_cache_enable": (_i, [_vp, _sz, _sz, _sz, _sz, _sz, C.c_uint]),
+    "srn_index_result_cache_disable": (_i, [_vp]),
+    "srn_index_result_cache_clear": (_i, [_vp]),
+    "srn_index_result_cache_stats": (_i, [_vp, C.POINTER(ResultCacheStats)]),
     "srn_find_neighbors": (_i, [_vp, _vp, _sz, _sz, _sz, _vp, _vp, C.POINTER(_sz)]),
     "srn_index_free": (None, [_vp]),
     "srn_predict": (_i, [_vp, _vp, _sz, _sz, _sz, _sz, _i, _vp, _vp, C.POINTER(_sz)]),

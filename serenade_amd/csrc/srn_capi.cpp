@@ -210,7 +210,10 @@ int srn_index_set_attributes(srn_index_t* idx, const uint64_t* item_ids, const u
             if (j == kNone) continue;   // attributes of items outside the index can never be consulted
             idx->flat.attr[j] = flags[i] == SRN_ATTR_NONE ? (uint8_t)SRN_ATTR_NONE : (uint8_t)(flags[i] & 3u);
         }
-        return idx->dev ? device_update_attr(idx->dev, idx->flat) : SRN_OK; });
+        if (!idx->dev) return SRN_OK;
+        const int rc = device_update_attr(idx->dev, idx->flat);
+        if (rc == SRN_OK) (void)device_result_cache_clear_if_enabled(idx->dev);   // (rows under the business rules depend on the flags)
+        return rc; });
 }
 int srn_index_info(const srn_index_t* idx, srn_index_info_t* out) {
     if (!idx || !out) return fail(SRN_EINVAL, "null argument");
@@ -304,6 +307,7 @@ int srn_find_neighbors(const srn_index_t* idx, const uint64_t* evolving, size_t 
 
 void srn_index_free(srn_index_t* idx) {
     if (!idx) return;
+    if (idx->dev) (void)device_result_cache_disable(idx->dev);
     device_release(idx->dev);
     if (idx->comb) combiner_free(idx->comb);
     delete idx;
@@ -318,8 +322,10 @@ int srn_predict(const srn_index_t* idx, const uint64_t* evolving, size_t len, si
         if (len > SRN_MAX_SESSION_LEN) return fail(SRN_ERANGE, "evolving session longer than SRN_MAX_SESSION_LEN");
         // (round 6) a resident workgroup of the persistent latency path, if the handle has them and this call is what they serve: no launch at all
         if (idx && idx->dev && out_ids && out_scores && len <= 16 && k <= 0xFFFFFFFFull && m <= 0xFFFFFFFFull && how_many <= 0xFFFFFFFFull &&
-            device_serve_predict(idx->dev, evolving, (uint32_t)len, (uint32_t)k, (uint32_t)m, (uint32_t)how_many, enable_business_logic ? SRN_FLAG_BUSINESS_LOGIC : 0u, out_ids, out_scores, out_n) == 0)
+            device_serve_predict(idx->dev, evolving, (uint32_t)len, (uint32_t)k, (uint32_t)m, (uint32_t)how_many, enable_business_logic ? SRN_FLAG_BUSINESS_LOGIC : 0u, out_ids, out_scores, out_n) == 0) {
+            device_result_cache_bypassed(idx->dev);
             return SRN_OK;
+        }
         // concurrent calls on one handle share launches (srn_combine.cpp); a lone caller runs its own round of one at once
         const int lanes = knob_predict_lanes();
         if (lanes > 0 && idx && idx->comb) {
@@ -353,6 +359,35 @@ int srn_index_serve_stop(srn_index_t* idx) {
 int srn_index_serve_stats(const srn_index_t* idx, uint64_t* out_served, uint64_t* out_not_served, uint64_t* out_launches, uint32_t* out_lanes) {
     if (!idx || !idx->dev) return fail(SRN_ENODEV, "index has no device attached");
     return device_serve_stats(idx->dev, out_served, out_not_served, out_launches, out_lanes);
+}
+
+// ---- the device result cache (srn_result_cache.hip) ----
+int srn_index_result_cache_enable(srn_index_t* idx, size_t rows, size_t max_len, size_t k, size_t m, size_t how_many, unsigned flags) {
+    return guarded([&]() -> int {
+        if (!idx) return fail(SRN_EINVAL, "null index");
+        if (flags & ~(unsigned)SRN_FLAG_BUSINESS_LOGIC) return fail(SRN_EINVAL, "srn_index_result_cache_enable: unknown flags");
+        if (rows == 0) return fail(SRN_EINVAL, "srn_index_result_cache_enable: rows must be > 0");
+        if (max_len < 1 || max_len > 8) return fail(SRN_ERANGE, "srn_index_result_cache_enable: max_len must be 1..8");
+        int rc = check_predict_args(idx, k, m, how_many); if (rc) return rc;
+        rc = check_not_a_shard(idx); if (rc) return rc;
+        return device_result_cache_enable(idx->dev, rows, (uint32_t)max_len, (uint32_t)k, (uint32_t)m, (uint32_t)how_many, flags); });
+}
+int srn_index_result_cache_disable(srn_index_t* idx) {
+    return guarded([&]() -> int {
+        if (!idx) return fail(SRN_EINVAL, "null index");
+        return idx->dev ? device_result_cache_disable(idx->dev) : SRN_OK; });
+}
+int srn_index_result_cache_clear(srn_index_t* idx) {
+    return guarded([&]() -> int {
+        if (!idx) return fail(SRN_EINVAL, "null index");
+        if (!idx->dev) return fail(SRN_ENODEV, "index has no device attached");
+        return device_result_cache_clear(idx->dev); });
+}
+int srn_index_result_cache_stats(const srn_index_t* idx, srn_result_cache_stats_t* out) {
+    return guarded([&]() -> int {
+        if (!idx || !out) return fail(SRN_EINVAL, "null argument");
+        if (!idx->dev) return fail(SRN_ENODEV, "index has no device attached");
+        return device_result_cache_stats(idx->dev, out); });
 }
 
 int srn_predict_stats(const srn_index_t* idx, uint64_t* out_rounds, uint64_t* out_requests, uint64_t* out_max_round) {

@@ -193,6 +193,14 @@ int device_reserve(DeviceState* d, const FlatIndex& ix, const LaunchParams& p, v
 int device_last_path_counts(DeviceState* d, uint32_t* nq, uint32_t* general, uint32_t* global_pass);   // debug profiling aid
 int device_last_mid_count(DeviceState* d, uint32_t* listed, uint32_t* big_listed = nullptr);   // queries the last call's lean fast kernel listed for its MID instantiation
 int device_last_dedup_count(DeviceState* d, uint32_t* merged);   // queries of the last call merged into an equal, earlier query of the same call (srn_dedup.hip)
+// ---- the device result cache (srn_result_cache.hip): served rows kept across calls, used by the batch launch sequence where its fast path is ----
+static constexpr unsigned kFlagNoResultCache = 0x80000000u;   // LaunchParams::flags, internal (device_predict strips it): this call bypasses an enabled cache (srn_evaluate)
+int device_result_cache_enable(DeviceState* d, uint64_t rows, uint32_t max_len, uint32_t k, uint32_t m, uint32_t how_many, uint32_t flags);
+int device_result_cache_disable(DeviceState* d);
+int device_result_cache_clear(DeviceState* d);            // SRN_ESTATE: none enabled
+int device_result_cache_clear_if_enabled(DeviceState* d);
+int device_result_cache_stats(DeviceState* d, srn_result_cache_stats_t* out);
+void device_result_cache_bypassed(DeviceState* d);        // a call that did not use the enabled cache (nothing happens without one)
 int device_kernel_times(DeviceState* d, uint32_t max_n, double* ms_main, double* ms_retry, uint32_t* out_n, double* ms_prep = nullptr, double* ms_fast = nullptr);
 
 }  // namespace srn

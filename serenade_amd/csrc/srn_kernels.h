@@ -144,6 +144,16 @@ hipError_t launch_dedup_group(hipStream_t st, const uint64_t* items_flat, const 
 hipError_t launch_dedup_mark(hipStream_t st, uint32_t nq, const uint32_t* rep, uint32_t* out_counts);
 hipError_t launch_dedup_fill(hipStream_t st, uint32_t nq, const uint32_t* rep, uint64_t* out_ids, double* out_scores, uint32_t* out_counts, uint32_t how_many, const uint32_t* n_dup, uint32_t* host_word);
 
+// ---- the device result cache (srn_result_cache.hip): the table as its two kernels see it ----
+static constexpr uint32_t RC_WAYS = 8, RC_MAX_LEN = 8;   // entries per bucket; longest cacheable sequence (RC_WAYS * RC_MAX_LEN lanes compare a bucket's keys at once)
+enum ResultCacheCounter : uint32_t { RC_LOOKUPS = 0, RC_HITS = 1, RC_INSERTS = 2, RC_EVICTIONS = 3, RC_COUNTERS = 4 };
+struct ResultCacheView {
+    uint32_t* stamp; uint32_t* len; uint32_t* count;   // per entry: number of the last call that stored or hit it (0: empty) | sequence length | the row's count
+    uint64_t* keys; uint64_t* ids; double* scores;     // per entry: max_len raw ids | how_many ids | how_many scores
+    unsigned long long* counters;                       // ResultCacheCounter
+    uint32_t n_buckets, max_len, how_many, hash_mask;   // hash_mask: SRN_CACHE_HASH_BITS (tests)
+};
+
 // ---- the item-sharded index's own back end (srn_sback.hip, round 5): one WAVE per query over a shard's row fragments -------------------------------------------------
 // Geometry of a wave's accumulators (words): SB_H direct-mapped (the shard's most popular items; the top SB_REP_ITEMS * SB_REP of them are the replicated words of the
 // SB_REP_ITEMS hottest), SB_S sketch words, SB_DUMP dump words -- baked into the frag8 slots' 16-bit LDS byte offsets at attach time.

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <atomic>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <utility>
@@ -44,6 +45,7 @@ struct Knobs {
                               // pass is one radix sort of the batch's keys behind the prep kernel
     bool no_dedup = false;     // SRN_NO_DEDUP: every query of an ordered batch is served, also the copies of an earlier query of the same call (srn_dedup.hip; A/B and the tests' reference)
     int dedup_hash_bits = 0;   // SRN_DEDUP_HASH_BITS (tests only): the grouping pass's hash cut to this many bits -- unequal queries share hashes and the probe chains get long; 0 = all 32
+    int cache_hash_bits = 0;   // SRN_CACHE_HASH_BITS (tests only): the result cache's hash cut to this many bits -- unequal sequences share buckets, and only the comparison of the keys keeps them apart; 0 = all 32
     bool no_sback_second = false;   // SRN_NO_SBACK_SECOND (experiments): what the wave-per-query back end cannot hold goes straight to the general kernel (no fast-kernel back end over the list)
     bool no_sback = false;    // SRN_NO_SBACK: the shard group's back end through vmis_fast_kernel's FM_BACK instantiation (rounds 4) instead of the wave-per-query kernel of srn_sback.hip
     double xgmi_gbps = 76.8;       // SRN_XGMI_GBPS: what one xGMI link moves per direction (AUTO's input below)
@@ -100,6 +102,19 @@ struct Workspace {
     hipStream_t side = nullptr; hipEvent_t ev_prep[2] = {}, ev_done[2] = {}; char* prep2 = nullptr; size_t prep2_bytes = 0; uint64_t resident_calls = 0; bool rec_used[2] = {false, false};
 };
 
+// An index's device result cache (srn_result_cache.hip): the table, the parameters its rows were computed with, and what orders its kernels across streams
+struct ResultCache {
+    ResultCacheView view{}; char* mem = nullptr; size_t bytes = 0, stamp_bytes = 0; int device = 0;
+    uint32_t k = 0, m = 0, how_many = 0, flags = 0;   // a call with other parameters bypasses the cache
+    std::mutex mu;                  // around "wait on ev, enqueue a cache kernel, record ev": the cache's kernels run in enqueue order whatever their streams
+    hipEvent_t ev = nullptr; hipStream_t own = nullptr;   // own: the clear's and the getter's stream
+    uint32_t seq = 0;               // number of the last call that used the cache: the entries' use stamps (under mu)
+    std::atomic<uint64_t> bypassed{0}, clears{0};
+    ~ResultCache();
+};
+int rcache_enqueue_lookup(ResultCache* rc, hipStream_t st, const LaunchParams& p, const uint32_t* rep, unsigned long long* okeys, const uint32_t* n_dup, uint32_t* n_skip, int hash_bits, uint32_t* now_out);
+int rcache_enqueue_insert(ResultCache* rc, hipStream_t st, const LaunchParams& p, const uint32_t* rep, const unsigned long long* okeys, int hash_bits, uint32_t now);
+
 struct ServeState;   // the persistent latency path's resident workgroups (srn_latency.hip, "serve")
 struct DeviceState {
     int device = 0;
@@ -119,6 +134,7 @@ struct DeviceState {
     Workspace* last_ws = nullptr;   // for srn_last_kernel_ms (single-threaded measurement use)
     std::vector<HostPipe*> free_pipes, all_pipes;   // chunked host-pointer batches (srn_hostpipe.hip), pooled like the workspaces
     unsigned long long* d_phase = nullptr; bool phase_on = false;   // debug per-phase cycle counters
+    std::shared_ptr<ResultCache> rcache;   // srn_index_result_cache_enable (under mu; a call holds its own reference)
     std::atomic<bool> timing{false};   // record the per-kernel events of every call (srn_kernel_timing; SRN_TIMING=1): each event costs ~6 us of idle stream
 };
 
@@ -154,5 +170,6 @@ void hostpipes_free(DeviceState* d);   // srn_hostpipe.hip
 int device_predict_host_pipelined(DeviceState* d, const FlatIndex& ix, const LaunchParams& p, const uint64_t* h_items, const uint32_t* h_qoff,
                                   uint64_t* h_ids, double* h_scores, uint32_t* h_counts);
 uint32_t hostpipe_chunks(uint32_t nq, uint32_t how_many);
+std::shared_ptr<ResultCache> device_result_cache(DeviceState* d);   // the enabled cache, or null
 
 }  // namespace srn

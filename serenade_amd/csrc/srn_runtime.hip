@@ -47,6 +47,7 @@ static void knobs_read() {
     k.lanes = env_int("SRN_PREDICT_LANES", k.lanes, 0);
     k.order_min = env_int("SRN_ORDER_MIN", k.order_min, 0);
     k.no_dedup = env_flag("SRN_NO_DEDUP"); k.dedup_hash_bits = env_int("SRN_DEDUP_HASH_BITS", 0, 0, 32);
+    k.cache_hash_bits = env_int("SRN_CACHE_HASH_BITS", 0, 0, 32);
     k.no_sback_second = env_flag("SRN_NO_SBACK_SECOND");
     k.no_sback = env_flag("SRN_NO_SBACK");
     const int stream = env_int("SRN_SBACK_STREAM", INT_MIN); k.sback_stream_mode = stream == INT_MIN ? -1 : stream != 0 ? 1 : 0;
@@ -226,6 +227,7 @@ void device_release(DeviceState* d) {
     if (!d) return;
     (void)device_serve_stop(d); serve_free_retired(d);
     hipSetDevice(d->device);
+    d->rcache.reset();   // (waits for the device)
     hostpipes_free(d);
     for (Workspace* w : d->all_ws) ws_free(w);
     for (void* p : d->allocs) hipFree(p);
@@ -436,8 +438,9 @@ FastPlan fast_plan(const DeviceState* d, const FlatIndex& ix, const LaunchParams
 // The serving order of a batch (FastParams::order): room for the keys the prep kernel writes, their sorted copy and the sort's scratch in ONE grow-only buffer; then the sort
 // itself, enqueued on the stream the prep kernel ran on.
 struct DedupRoom { uint32_t* n_dup = nullptr; uint32_t* rep = nullptr; uint32_t* slots = nullptr; uint32_t* slot_min = nullptr; uint32_t n_slots = 0; };
-struct OrderBufs { unsigned long long* keys_in = nullptr; unsigned long long* keys_out = nullptr; void* temp = nullptr; size_t temp_bytes = 0; DedupRoom dd; };
-static int order_room(char** buf, size_t* have, uint32_t nq, OrderBufs* o, bool dedup = false) {
+struct OrderBufs { unsigned long long* keys_in = nullptr; unsigned long long* keys_out = nullptr; void* temp = nullptr; size_t temp_bytes = 0; DedupRoom dd;
+                   uint32_t* n_skip = nullptr; };   // (a call that uses the result cache) queries at the end of the order that nobody serves: the merged ones + the cache's hits
+static int order_room(char** buf, size_t* have, uint32_t nq, OrderBufs* o, bool dedup = false, bool cache = false) {
     DedupRoom* dd = dedup ? &o->dd : nullptr;
     size_t tb = 0;
     if (sort_order_keys(nullptr, nullptr, nullptr, nq, nullptr, &tb) != hipSuccess) return fail(SRN_EHIP, "rocprim::radix_sort_keys (size query) failed");
@@ -445,9 +448,11 @@ static int order_room(char** buf, size_t* have, uint32_t nq, OrderBufs* o, bool 
     // (dd: the call merges its equal queries -- the merged count, rep[nq] and the hash table's two arrays belong to the order set, like the keys: a resident call groups on
     //  the side stream while the previous call's kernels still read THEIR count and representatives)
     const size_t rb = ((size_t)nq * 4 + 255) / 256 * 256, n_slots = dd ? dedup_slots(nq) : 0;
-    int rc = ensure(buf, have, 2 * kb + tbr + 256 + (dd ? 256 + rb + 2 * n_slots * 4 : 0)); if (rc) return rc;
+    const size_t dd_bytes = dd ? 256 + rb + 2 * n_slots * 4 : 0;
+    int rc = ensure(buf, have, 2 * kb + tbr + 256 + dd_bytes + (cache ? 256 + 256 : 0)); if (rc) return rc;
     o->keys_in = (unsigned long long*)*buf; o->keys_out = (unsigned long long*)(*buf + kb); o->temp = *buf + 2 * kb; o->temp_bytes = tb;
     if (dd) { char* b = *buf + 2 * kb + tbr + 256; dd->n_dup = (uint32_t*)b; dd->rep = (uint32_t*)(b + 256); dd->slots = (uint32_t*)(b + 256 + rb); dd->slot_min = dd->slots + n_slots; dd->n_slots = (uint32_t)n_slots; }
+    if (cache) o->n_skip = (uint32_t*)(*buf + (2 * kb + tbr + 256 + dd_bytes + 255) / 256 * 256);
     return SRN_OK;
 }
 
@@ -490,6 +495,7 @@ struct LaunchPlan {
     FastPlan fast;
     bool resident = false, order_set2 = false;                      // SRN_FLAG_INPUTS_RESIDENT: the front on the side stream; on the second set of order buffers
     bool ordered = false, dedup = false, prep_clears = false;
+    bool cache = false;                                             // the call looks its queries up in the index's result cache and stores what it served (srn_result_cache.hip)
 };
 // the global-table pass: tables at twice the worst case in a global-memory arena per workgroup (cg: geo.c on entry), as many workgroups as 2 GB hold, at most one per CU
 static void global_tables_geometry(const DeviceState* d, const Geometry& geo, KernelCfg& cg, uint64_t& g_stride, int& retry_blocks) {
@@ -499,7 +505,7 @@ static void global_tables_geometry(const DeviceState* d, const Geometry& geo, Ke
     g_stride = (g_stride + 255) / 256 * 256;
     retry_blocks = (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)d->n_cu, (2ull << 30) / g_stride));
 }
-static LaunchPlan make_plan(const DeviceState* d, const FlatIndex& ix, const LaunchParams& p, const Geometry& geo, const ExtLists* ext, bool resident, const Workspace* w) {
+static LaunchPlan make_plan(const DeviceState* d, const FlatIndex& ix, const LaunchParams& p, const Geometry& geo, const ExtLists* ext, bool resident, const Workspace* w, const ResultCache* rcache) {
     LaunchPlan pl; pl.kn = knobs(); pl.geo = geo; pl.resident = resident;
     const Knobs& kn = pl.kn; const KernelCfg& c = geo.c;
     pl.retry = geo.sess_may_overflow || geo.item_may_overflow;
@@ -520,10 +526,15 @@ static LaunchPlan make_plan(const DeviceState* d, const FlatIndex& ix, const Lau
                                     : (uint32_t)std::min<uint64_t>(p.nq, std::min<uint64_t>(res_wg * 64, std::max<uint64_t>(res_wg * 16, p.nq / 12)));
     // the serving order: the batch sorted by each query's most popular item (keys from the prep kernel, one radix sort behind it)
     pl.ordered = pl.fast.fast && !ext && kn.order_min > 0 && p.nq >= (uint32_t)kn.order_min;
-    // (one order per set of prep records: a resident call's prep kernel and sort run on the side stream while the previous call's kernels still read THEIR order)
-    pl.order_set2 = resident && (w->resident_calls & 1u) != 0u;
     // ... and, in that order, only the first of the call's queries with one and the same item sequence (srn_dedup.hip); the others get its row at the end
     pl.dedup = pl.ordered && !kn.no_dedup;
+    // The result cache is on exactly where the fast path is, for calls with the parameters its rows were computed with.  Such a call is ordered at every
+    // batch size -- the order is what keeps queries away from the serving kernels: a hit sorts behind everything that is served, like a merged query -- and never resident:
+    // the hits' rows are written into the caller's buffers at the front of the call, which on the side stream could overtake a previous call that still owns them.
+    pl.cache = rcache != nullptr && pl.fast.fast && !ext && p.k == rcache->k && p.m == rcache->m && p.how_many == rcache->how_many && (p.flags & SRN_FLAG_BUSINESS_LOGIC) == rcache->flags;
+    if (pl.cache) { pl.ordered = true; pl.resident = false; resident = false; }
+    // (one order per set of prep records: a resident call's prep kernel and sort run on the side stream while the previous call's kernels still read THEIR order)
+    pl.order_set2 = resident && (w->resident_calls & 1u) != 0u;
     // The prep kernel clears the launch sequence's counters where it runs on this stream ahead of everything that uses them (two fill kernels otherwise: 6 us each)
     pl.prep_clears = !ext && !resident;
     return pl;
@@ -543,7 +554,7 @@ static int reserve_batch(Workspace* w, const LaunchPlan& pl, const LaunchParams&
         rc = ensure_side(w); if (rc) return rc;
     }
     if (pl.fast.fast) { int rc = reserve_fast(w, p.nq); if (rc) return rc; }
-    if (pl.ordered) return order_room(pl.order_set2 ? &w->order2 : &w->order, pl.order_set2 ? &w->order2_bytes : &w->order_bytes, p.nq, &ob, pl.dedup);
+    if (pl.ordered) return order_room(pl.order_set2 ? &w->order2 : &w->order, pl.order_set2 ? &w->order2_bytes : &w->order_bytes, p.nq, &ob, pl.dedup, pl.cache);
     return SRN_OK;
 }
 
@@ -553,6 +564,7 @@ struct BatchCall {
     hipEvent_t* ev = nullptr; bool timed = false, fork_retry = false;
     bool sback_second = false;   // the item shard's wave-per-query back end ran with the fast kernel's back-end form behind it (its list is the MID tier's: srn_debug_last_mid_count reports it)
     FastParams fp{};
+    ResultCache* rcache = nullptr; uint32_t cache_now = 0;   // (pl.cache) the index's result cache, held by device_predict for the length of the call; the call's number in it
 };
 
 // host-pointer calls: the staging buffer, p pointed at it, the inputs on their way
@@ -602,6 +614,8 @@ static int enqueue_front(BatchCall& c, hipStream_t s, char* rec) {
         HIP_TRY(hipMemsetAsync(ob.dd.slots, 0xFF, (size_t)ob.dd.n_slots * 8, s));
         HIP_TRY(launch_dedup_group(s, p.items_flat, p.q_off, p.nq, ob.dd.slots, ob.dd.slot_min, ob.dd.n_slots, (uint32_t)pl.kn.dedup_hash_bits, ob.dd.rep, ob.keys_in, pl.prep_clears ? p.out_counts : nullptr, ob.dd.n_dup));
     }
+    // the result cache's lookup: over the representatives, behind their grouping and ahead of the sort -- a hit's row is written here, its key moves behind the served queries
+    if (pl.cache) { int rc = rcache_enqueue_lookup(c.rcache, s, p, pl.dedup ? ob.dd.rep : nullptr, ob.keys_in, pl.dedup ? ob.dd.n_dup : nullptr, ob.n_skip, pl.kn.cache_hash_bits, &c.cache_now); if (rc) return rc; }
     if (pl.ordered) HIP_TRY(sort_order_keys(s, ob.keys_in, ob.keys_out, p.nq, ob.temp, &ob.temp_bytes));
     c.p.prep = rec; c.p.prep_stride = pl.prep_stride;
     return SRN_OK;
@@ -670,7 +684,7 @@ static int enqueue_fast_tiers(BatchCall& c) {
     const bool back = ext && ext->mode == 2;   // neighbour lists from the exchange buffer (any rank's front end), this shard's rows
     if (back) { fp.xchg = ext->xchg; fp.xchg_stride = ext->xchg_stride; }
     fp.order = pl.ordered ? c.ob.keys_out : back ? ext->order : nullptr;
-    fp.order_dups = pl.dedup ? c.ob.dd.n_dup : nullptr;
+    fp.order_dups = pl.cache ? c.ob.n_skip : pl.dedup ? c.ob.dd.n_dup : nullptr;   // (the cache's count: its hits + the merged queries)
     const uint32_t grid_fo = fp.order ? std::max<uint32_t>(8u, pl.grid_fast / 8u * 8u) : pl.grid_fast;   // (an ordered launch walks an eighth of the order per XCD: the grid is a multiple of 8)
     if (back && d->sback.frag8 && !kn.no_sback && p.max_len <= 8) { int rc = enqueue_shard_back(c); if (rc) return rc; }
     else HIP_TRY(launch_fast(back ? FastForm::Back : FastForm::Lean, dim3(grid_fo), st, c.di, p, fp, kn.debug));
@@ -731,6 +745,8 @@ static int enqueue_tail(BatchCall& c) {
                                                                                                                 //  "all of last_nq" -- no host write into a pinned word that an earlier call may still be writing)
     }
     if (fill_late) HIP_TRY(launch_dedup_fill(st, p.nq, ob.dd.rep, p.out_ids, p.out_scores, p.out_counts, p.how_many, ob.dd.n_dup, w->h_retry_dev + HW_MERGED));
+    // the result cache's insert: behind everything that can write a row (the global-table pass included, like fill_late) -- the keys the sort read are still in place
+    if (pl.cache) { int rc = rcache_enqueue_insert(c.rcache, st, p, pl.dedup ? ob.dd.rep : nullptr, ob.keys_in, pl.kn.cache_hash_bits, c.cache_now); if (rc) return rc; }
     HIP_TRY(hipEventRecord(c.ev[2], st));
     if (pl.resident) { const int par = (int)(w->resident_calls & 1u); HIP_TRY(hipEventRecord(w->ev_done[par], st)); w->rec_used[par] = true; ++w->resident_calls; }
     else if (!c.ext && w->side) { HIP_TRY(hipEventRecord(w->ev_done[0], st)); w->rec_used[0] = true; }   // (a workspace that has served resident calls: the next one's side-stream prep must not overwrite w->prep under this call's kernels)
@@ -778,6 +794,9 @@ int device_predict(DeviceState* d, const FlatIndex& ix, const LaunchParams& p_in
     // stream while the previous call's kernels still occupy the caller's stream (enqueue_front_resident); the kernels never see the flag
     const bool resident = on_device && !ext && (p.flags & SRN_FLAG_INPUTS_RESIDENT) != 0u;
     p.flags &= ~(unsigned)SRN_FLAG_INPUTS_RESIDENT;
+    // the index's result cache, if one is enabled and the caller does not rule it out: this call's own reference (srn_index_result_cache_disable may run beside it)
+    const bool no_cache = (p.flags & kFlagNoResultCache) != 0u; p.flags &= ~kFlagNoResultCache;
+    const std::shared_ptr<ResultCache> rcache = device_result_cache(d);
     // item-sharded index, lists mode (device_shard_lists_*): the posting lists of ALL shards for this batch arrive in one gathered
     // buffer with the prep records already written against it; everything below runs unchanged on "an index whose postings live there"
     DeviceIndex di = d->di;
@@ -792,7 +811,7 @@ int device_predict(DeviceState* d, const FlatIndex& ix, const LaunchParams& p_in
     if (!on_device && !reserve_only && !h_stats && !h_nb_rank) {
         if (p.nq <= (uint32_t)knobs().tiny_max && !d->phase_on) {
             const int rc = device_predict_tiny(d, ix, w, geo, p, h_items, h_qoff, h_ids, h_scores, h_counts, blocking_wait);
-            if (rc != 1) return rc;   // (1: some query needs the global-table pass -- the paths below have it)
+            if (rc != 1) { if (rcache) rcache->bypassed.fetch_add(1, std::memory_order_relaxed); return rc; }   // (1: some query needs the global-table pass -- the paths below have it)
         }
         // everything larger: chunks through pinned staging, uploads / kernels / downloads overlapped (srn_hostpipe.hip); each chunk comes back here as a
         // device-pointer call on one of the pipeline's kernel streams.  (This call's own workspace goes back to the pool first.)
@@ -801,8 +820,9 @@ int device_predict(DeviceState* d, const FlatIndex& ix, const LaunchParams& p_in
     }
     // ---- plan -> reserve -> enqueue ----
     if (!on_device) { int rc = stage_host_inputs(w, st, p, h_items, h_qoff, h_stats != nullptr, h_nb_rank != nullptr); if (rc) return rc; }   // (p.stats / p.nb_rank decide the plan)
-    const LaunchPlan pl = make_plan(d, ix, p, geo, ext, resident, w);
-    BatchCall c{d, w, pl, ext, st, di, p};
+    const LaunchPlan pl = make_plan(d, ix, p, geo, ext, resident, w, no_cache ? nullptr : rcache.get());
+    BatchCall c{d, w, pl, ext, st, di, p}; c.rcache = rcache.get();
+    if (rcache && !pl.cache && !reserve_only) rcache->bypassed.fetch_add(1, std::memory_order_relaxed);
     { int rc = reserve_batch(w, pl, c.p, ext, c.ob); if (rc) return rc; }
     if (reserve_only) return SRN_OK;   // (srn_index_reserve: the workspace is sized, nothing was enqueued)
     if (ext && ext->mode != 0 && !pl.fast.fast) return fail(SRN_EINVAL, "the neighbours pipeline needs the fast kernel's query shape (device_fast_eligible)");

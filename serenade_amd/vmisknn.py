@@ -145,6 +145,31 @@ class VMISIndex:
         capi.check(capi.lib().srn_index_serve_stats(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(n)))
         return a.value, b.value, c.value, n.value
 
+    def enable_result_cache(self, rows, max_len, k, m, how_many, business_logic=False):
+        """srn_index_result_cache_enable: keep served rows of sequences of 1..max_len (<= 8) items in a device table of `rows` entries; batch calls with exactly these
+        parameters on the fast path then answer repeated sequences from it (the same bytes), every other call bypasses it."""
+        rows, max_len, k, m, how_many = int(rows), int(max_len), int(k), int(m), int(how_many)
+        if rows <= 0:
+            raise ValueError("rows must be > 0")
+        if not 1 <= max_len <= 8:
+            raise ValueError("max_len must be 1..8")
+        if k <= 0 or m <= 0 or how_many <= 0:
+            raise ValueError("k, m and how_many must be > 0")
+        capi.check(capi.lib().srn_index_result_cache_enable(self._h, rows, max_len, k, m, how_many, capi.FLAG_BUSINESS_LOGIC if business_logic else 0))
+
+    def disable_result_cache(self):
+        capi.check(capi.lib().srn_index_result_cache_disable(self._h))
+
+    def clear_result_cache(self):
+        capi.check(capi.lib().srn_index_result_cache_clear(self._h))
+
+    def result_cache_stats(self):
+        """srn_index_result_cache_stats as a dict (waits for the cache's kernels): rows, ways, bytes, the parameters, and since enable lookups, hits, inserts, evictions,
+        bypassed_calls, clears."""
+        st = capi.ResultCacheStats()
+        capi.check(capi.lib().srn_index_result_cache_stats(self._h, C.byref(st)))
+        return {n: int(getattr(st, n)) for n, _ in capi.ResultCacheStats._fields_ if n != "reserved"}
+
     def session_recency(self):
         """Recency rank of every reference session (0 = oldest; 0xFFFFFFFF: not kept): the total order behind "most recent", ties among equal timestamps included."""
         n = int(self.info["n_sessions_total"])
