@@ -262,6 +262,31 @@ int srn_predict_batch_device(const srn_index_t* idx, const uint64_t* d_items_fla
                              unsigned flags, uint64_t* d_out_ids, double* d_out_scores,
                              uint32_t* d_out_counts, void* stream);
 
+/* ---- exclusion lists -------------------------------------------------------------------------------------------------------------------
+ * predict removes ONE item from a row: the session's most recent one (mod.rs:156-160).  srn_predict_batch_device_excl also removes, per query, a caller-given list of ids
+ * ("already in the basket", "already on the page") and, with SRN_FLAG_EXCLUDE_SESSION, every item of the query's own session -- and still returns how_many entries where
+ * the candidates allow: the rows are those of "remove the ids from ALL candidates, then cut to how_many", bit for bit.  The launch sequence runs unchanged at the INTERNAL
+ *     how_many + max_excl + (SRN_FLAG_EXCLUDE_SESSION ? max_len_hint - 1 : 0)        (above SRN_MAX_HOW_MANY: SRN_ERANGE)
+ * into wide rows, and one kernel (srn_exclude.hip) drops the listed ids and compacts each row.  The wide rows are scratch of the workspace bound to `stream`:
+ * 16 * nq * internal how_many + 4 * nq bytes, grown on first use and kept (2^20 queries, how_many 21, max_excl 16: 620 MB); equal-shaped calls allocate nothing.
+ *   d_excl_flat / d_excl_off   the lists as a CSR of u64 ids and nq + 1 u32 offsets; NULL with max_excl = 0 (NULL with max_excl > 0: SRN_EINVAL)
+ *   max_excl                   the capacity of one list -- an argument, not read from the data, so that the call never waits for the device.  A query whose list is longer
+ *                              gets out_counts[q] = 0xFFFFFFFF, like a query with an empty or over-long session.  Duplicates in a list count toward max_excl and are
+ *                              otherwise harmless, as are ids the index does not know.
+ * Enqueued on `stream` without host synchronisation, like srn_predict_batch_device; SRN_FLAG_BUSINESS_LOGIC and SRN_FLAG_INPUTS_RESIDENT as there.  With max_excl = 0 and
+ * no SRN_FLAG_EXCLUDE_SESSION the call IS srn_predict_batch_device: no scratch, no extra kernel.  Item shards and postings-only views are refused, as for predict.
+ * The internal how_many is what the launch sequence sees: it stays on the fast kernels up to SRN_FAST_HOW_MANY_MAX (64), and an enabled result cache is used exactly when
+ * its parameters equal the INTERNAL ones -- a server that excludes up to E ids enables it with how_many + E -- and is bypassed (and counted so) otherwise.  Cached and
+ * merged rows are the wide, unfiltered ones; the filter runs per query behind them: two equal sessions with different lists get different rows.
+ * srn_predict_batch_excl: the same with host pointers (pageable allowed) -- upload, the device form, download; it blocks.  A convenience form: the chunked host pipeline and
+ * the latency path of srn_predict_batch are NOT extended to it; a serving host uses the device form. */
+#define SRN_FLAG_EXCLUDE_SESSION 4u /* srn_predict_batch*_excl: every item of the query's own session is excluded, not only the most recent one */
+int srn_predict_batch_device_excl(const srn_index_t* idx, const uint64_t* d_items_flat, const uint32_t* d_q_off, size_t nq, size_t max_len_hint,
+                                  const uint64_t* d_excl_flat, const uint32_t* d_excl_off, size_t max_excl, size_t k, size_t m, size_t how_many, unsigned flags,
+                                  uint64_t* d_out_ids, double* d_out_scores, uint32_t* d_out_counts, void* stream);
+int srn_predict_batch_excl(const srn_index_t* idx, const uint64_t* items_flat, const uint32_t* q_off, size_t nq, const uint64_t* excl_flat, const uint32_t* excl_off, size_t max_excl,
+                           size_t k, size_t m, size_t how_many, unsigned flags, uint64_t* out_ids, double* out_scores, uint32_t* out_counts);
+
 /* Debug / measurement variant of srn_predict_batch (host pointers; any of the three extra outputs
  * may be NULL):
  *   out_stats  [nq * 8]  P, C, K, I, D, H, L, status per query -- the per-query terms of the
@@ -480,6 +505,14 @@ int srn_device_sessions_get(srn_device_sessions_t* s, uint64_t key_hi, uint64_t 
 int srn_device_sessions_update(srn_device_sessions_t* s, uint64_t key_hi, uint64_t key_lo, uint64_t now_secs, const uint64_t* items, size_t n);
 int srn_device_sessions_sweep(srn_device_sessions_t* s, uint64_t now_secs, uint64_t* n_live);
 int srn_device_sessions_stats(srn_device_sessions_t* s, srn_device_sessions_stats_t* out);
+/* The store remembers more than it predicts on.  history = 0 (the default): the store keeps max_items_in_session items, as the reference does -- nothing
+ * changes.  history = H in 1..items_cap (above: SRN_ERANGE): a srn_recommend_batch* call on this store keeps a window of the last H clicks -- the same append rule, idle
+ * rule and one-item-dropped-per-append rule, with H in the limit's place -- and predicts on the LAST min(window, max_items_in_session) items of it; it needs
+ * max_items_in_session <= H (else SRN_ERANGE, before anything changes).  The rows are those of a plain store driven with the same constant max_items_in_session.
+ * srn_device_sessions_get / _export / _save see the whole window; the file format does not change and H, a runtime setting, is not saved: a store that was filled with a
+ * history window should be given its H again after srn_device_sessions_load (until then the next call would cut the windows to max_items_in_session, an item per append). */
+int srn_device_sessions_set_history(srn_device_sessions_t* s, size_t history);
+int srn_device_sessions_history(srn_device_sessions_t* s, size_t* out_history);
 /* HIP events around the store's kernels and predict's launches of every batch (off by default); last_ms blocks until the most recent batch is done */
 int srn_device_sessions_timing(srn_device_sessions_t* s, int enable);
 int srn_device_sessions_last_ms(srn_device_sessions_t* s, double* out_ms_store, double* out_ms_predict);
@@ -531,6 +564,12 @@ int srn_device_sessions_load(const char* path, int device, size_t capacity, size
 int srn_device_sessions_file_info(const char* path, srn_device_sessions_file_info_t* out);
 /* srn_session_key for n strings: string i = ids_flat[off[i] .. off[i + 1]) */
 int srn_session_keys(const char* ids_flat, const uint64_t* off, size_t n, uint64_t* key_hi, uint64_t* key_lo);
+/* flags: SRN_FLAG_BUSINESS_LOGIC, and SRN_FLAG_EXCLUDE_SEEN -- a request's recommendations leave out what its visitor has seen: the request's window as the request
+ * sees it (the store's history window, or the session window on a store without one), the earlier requests of its key in the batch included; without consent nothing beyond
+ * the item itself.  The windows are the exclusion lists of srn_predict_batch_device_excl, their capacity the store's max_stored_len bound (srn_device_sessions_stats):
+ * the launch sequence runs at the internal how_many + max_stored_len (above SRN_MAX_HOW_MANY: SRN_ERANGE, before anything changes), which is also what a result cache must
+ * be enabled with to serve such calls. */
+#define SRN_FLAG_EXCLUDE_SEEN 8u
 /* Every buffer in the index's device memory; enqueued on `stream` (a hipStream_t) without host synchronisation.  d_consent: one byte per request, NULL = every request
  * consents.  out rows / counts as srn_predict_batch_device.  store may be NULL only if no request consents (d_consent == NULL with a NULL store: SRN_EINVAL; otherwise the
  * flags are read back and checked before anything is launched -- that call blocks).  now_secs = 0: the system clock, read once. */

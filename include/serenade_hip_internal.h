@@ -51,6 +51,13 @@ int srn_debug_eval_terms(srn_eval_set_t* set, const srn_eval_trial_t* trial, dou
 int srn_debug_device_sessions_last_batch(srn_device_sessions_t* s, const void** d_items, const void** d_q_off, size_t* out_n, size_t* out_max_len,
                                          uint64_t* h_items, size_t cap, uint32_t* h_q_off);
 
+/* Measurement aid (tools/exclude_bench.py): the exclusion filter kernel of srn_predict_batch_device_excl ALONE, over wide rows the caller holds --
+ * d_wide_ids / d_wide_scores [nq * wide], d_wide_counts [nq] -> d_out_* [nq * how_many], [nq]; the exclusion CSR and the session CSR (d_items_flat, d_q_off) may each be
+ * NULL.  Enqueued on `stream`. */
+int srn_debug_exclude_filter(const srn_index_t* idx, size_t nq, const uint64_t* d_wide_ids, const double* d_wide_scores, const uint32_t* d_wide_counts, size_t wide, const uint64_t* d_excl_flat,
+                             const uint32_t* d_excl_off, size_t max_excl, const uint64_t* d_items_flat, const uint32_t* d_q_off, size_t how_many, uint64_t* d_out_ids, double* d_out_scores,
+                             uint32_t* d_out_counts, void* stream);
+
 /* Test / experiment knobs (environment variables SRN_NO_FAST, SRN_NO_MID, SRN_NO_MASKS, SRN_NO_MERGE, SRN_HOT_SLOTS,
  * SRN_SKETCH_SLOTS, SRN_LDS_BUDGET_KB, SRN_GRID_MULT, SRN_DEBUG) force individual kernel code paths.  They are read ONCE,
  * when the library is first used -- never on the launch path; this call re-reads them (the parity tests switch paths

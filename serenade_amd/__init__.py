@@ -4,9 +4,9 @@ The package holds only what that path needs: the HIP kernels + C ABI (csrc/, bui
 libserenade_hip.so), a ctypes binding (capi), the host-side mirror of the reference interface
 (vmisknn), training data from TSV files or in-memory events on the GPU (ingest), the offline evaluation loop and hyper-parameter search on the GPU (evaluation, hpo) and the synthetic workload generator
 used by bench.py (synth)."""
-from .vmisknn import CSR, ItemScore, VMISIndex, SerenadeError, predict, predict_batch, predict_batch_debug, predict_batch_device, reserve  # noqa: F401
+from .vmisknn import CSR, ItemScore, VMISIndex, SerenadeError, predict, predict_batch, predict_batch_debug, predict_batch_device, predict_batch_device_excl, reserve  # noqa: F401
 from .evaluation import EvalSet, evaluate  # noqa: F401
 from .ingest import TrainingSessions  # noqa: F401
 
-__all__ = ["CSR", "ItemScore", "VMISIndex", "SerenadeError", "predict", "predict_batch", "predict_batch_debug", "predict_batch_device", "reserve",
+__all__ = ["CSR", "ItemScore", "VMISIndex", "SerenadeError", "predict", "predict_batch", "predict_batch_debug", "predict_batch_device", "predict_batch_device_excl", "reserve",
            "EvalSet", "evaluate", "TrainingSessions"]

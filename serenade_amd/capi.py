@@ -50,6 +50,8 @@ class ShardComm(C.Structure):
 
 SHARD_GROUP_ID_BYTES = 256
 FLAG_INPUTS_RESIDENT = 2
+FLAG_EXCLUDE_SESSION = 4
+FLAG_EXCLUDE_SEEN = 8
 
 
 class EvalTrial(C.Structure):
@@ -136,6 +138,9 @@ SYMBOLS = {
     "srn_session_store_sweep": (_i, [_vp, _u64, C.POINTER(_u64)]),
     "srn_recommend": (_i, [_vp, _vp, C.c_char_p, _sz, _u64, _i, _sz, _u64, _vp, _vp, C.POINTER(_sz)]),
     "srn_predict_batch_device": (_i, [_vp, _vp, _vp, _sz, _sz, _sz, _sz, _sz, C.c_uint, _vp, _vp, _vp, _vp]),
+    "srn_predict_batch_device_excl": (_i, [_vp, _vp, _vp, _sz, _sz, _vp, _vp, _sz, _sz, _sz, _sz, C.c_uint, _vp, _vp, _vp, _vp]),
+    "srn_predict_batch_excl": (_i, [_vp, _vp, _vp, _sz, _vp, _vp, _sz, _sz, _sz, _sz, C.c_uint, _vp, _vp, _vp]),
+    "srn_debug_exclude_filter": (_i, [_vp, _sz, _vp, _vp, _vp, _sz, _vp, _vp, _sz, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
     "srn_predict_batch_debug": (_i, [_vp, _vp, _vp, _sz, _sz, _sz, _sz, C.c_uint, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "srn_index_reserve": (_i, [_vp, _sz, _sz, _sz, _sz, _sz, C.c_uint, _vp]),
     "srn_last_kernel_ms": (_i, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint32)]),
@@ -192,6 +197,8 @@ SYMBOLS = {
     "srn_device_sessions_load": (_i, [C.c_char_p, _i, _sz, _sz, _u64, _u64, C.POINTER(_vp)]),
     "srn_device_sessions_file_info": (_i, [C.c_char_p, C.POINTER(DeviceSessionsFileInfo)]),
     "srn_session_keys": (_i, [_vp, _vp, _sz, _vp, _vp]),
+    "srn_device_sessions_set_history": (_i, [_vp, _sz]),
+    "srn_device_sessions_history": (_i, [_vp, C.POINTER(_sz)]),
     "srn_recommend_batch_device": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _u64, _sz, _sz, _sz, _sz, C.c_uint, _vp, _vp, _vp, _vp]),
     "srn_recommend_batch": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _u64, _sz, _sz, _sz, _sz, C.c_uint, _vp, _vp, _vp]),
     "srn_debug_device_sessions_last_batch": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_sz), C.POINTER(_sz), _vp, _sz, _vp]),

@@ -427,6 +427,73 @@ int srn_predict_batch_device(const srn_index_t* idx, const uint64_t* d_items_fla
                               nullptr, nullptr); });
 }
 
+// ---- exclusion lists (srn_exclude.hip) ----
+// the checks both forms share; *wide = the internal how_many
+static int check_excl_args(const srn_index_t* idx, size_t nq, size_t max_len_hint, const void* excl_flat, const void* excl_off, size_t max_excl, size_t k, size_t m, size_t how_many,
+                           unsigned flags, size_t* wide) {
+    int rc = check_predict_args(idx, k, m, how_many); if (rc) return rc;
+    rc = check_not_a_shard(idx); if (rc) return rc;
+    if (flags & ~(unsigned)(SRN_FLAG_BUSINESS_LOGIC | SRN_FLAG_INPUTS_RESIDENT | SRN_FLAG_EXCLUDE_SESSION)) return fail(SRN_EINVAL, "srn_predict_batch_excl: unknown flags");
+    if (nq > 0x7FFFFFFFull) return fail(SRN_ERANGE, "too many queries in one batch");
+    if (max_len_hint == 0 || max_len_hint > SRN_MAX_SESSION_LEN) return fail(SRN_ERANGE, "max_len_hint out of range");
+    if (max_excl > SRN_MAX_HOW_MANY) return fail(SRN_ERANGE, "how_many + max_excl above SRN_MAX_HOW_MANY");
+    *wide = how_many + max_excl + ((flags & SRN_FLAG_EXCLUDE_SESSION) ? max_len_hint - 1 : 0);
+    if (*wide > SRN_MAX_HOW_MANY) return fail(SRN_ERANGE, "how_many + max_excl (+ max_len_hint - 1 with SRN_FLAG_EXCLUDE_SESSION) above SRN_MAX_HOW_MANY");
+    if (max_excl > 0 && (!excl_flat || !excl_off)) return fail(SRN_EINVAL, "null exclusion list with max_excl > 0");
+    return SRN_OK;
+}
+int srn_predict_batch_device_excl(const srn_index_t* idx, const uint64_t* d_items_flat, const uint32_t* d_q_off, size_t nq, size_t max_len_hint,
+                                  const uint64_t* d_excl_flat, const uint32_t* d_excl_off, size_t max_excl, size_t k, size_t m, size_t how_many, unsigned flags,
+                                  uint64_t* d_out_ids, double* d_out_scores, uint32_t* d_out_counts, void* stream) {
+    return guarded([&]() -> int {
+        size_t wide = 0;
+        int rc = check_excl_args(idx, nq, max_len_hint, d_excl_flat, d_excl_off, max_excl, k, m, how_many, flags, &wide); if (rc) return rc;
+        if (nq == 0) return SRN_OK;
+        if (!d_items_flat || !d_q_off || !d_out_ids || !d_out_scores || !d_out_counts) return fail(SRN_EINVAL, "null buffer");
+        LaunchParams p{};
+        p.nq = (uint32_t)nq; p.k = (uint32_t)k; p.m = (uint32_t)m; p.how_many = (uint32_t)wide; p.flags = flags & ~(unsigned)SRN_FLAG_EXCLUDE_SESSION; p.max_len = (uint32_t)max_len_hint;
+        p.items_flat = d_items_flat; p.q_off = d_q_off; p.out_ids = d_out_ids; p.out_scores = d_out_scores; p.out_counts = d_out_counts;
+        if (wide == how_many)   // nothing can be excluded (one-item sessions at most, whose item is never in its row): the plain call -- no scratch, no extra kernel
+            return device_predict(idx->dev, idx->flat, p, true, stream, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+        const ExclSpec x{max_excl ? d_excl_flat : nullptr, max_excl ? d_excl_off : nullptr, (uint32_t)max_excl, (flags & SRN_FLAG_EXCLUDE_SESSION) != 0u, (uint32_t)how_many, d_out_ids, d_out_scores, d_out_counts};
+        p.out_ids = nullptr; p.out_scores = nullptr; p.out_counts = nullptr;
+        return device_predict(idx->dev, idx->flat, p, true, stream, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, false, false, &x); });
+}
+int srn_predict_batch_excl(const srn_index_t* idx, const uint64_t* items_flat, const uint32_t* q_off, size_t nq, const uint64_t* excl_flat, const uint32_t* excl_off, size_t max_excl,
+                           size_t k, size_t m, size_t how_many, unsigned flags, uint64_t* out_ids, double* out_scores, uint32_t* out_counts) {
+    return guarded([&]() -> int {
+        if (nq == 0) { size_t wide = 0; return check_excl_args(idx, 0, 1, excl_flat, excl_off, max_excl, k, m, how_many, flags, &wide); }
+        if (!items_flat || !q_off || !out_ids || !out_scores || !out_counts) return fail(SRN_EINVAL, "null buffer");
+        if (nq > 0x7FFFFFFFull) return fail(SRN_ERANGE, "too many queries in one batch");
+        uint32_t max_len = 0;
+        for (size_t q = 0; q < nq; ++q) {
+            if (q_off[q + 1] < q_off[q]) return fail(SRN_EINVAL, "q_off not monotone");
+            if (q_off[q + 1] == q_off[q]) return fail(SRN_EINVAL, "empty evolving session (the reference panics: src/vmisknn/mod.rs:157)");
+            max_len = std::max(max_len, q_off[q + 1] - q_off[q]);
+        }
+        if (max_len > SRN_MAX_SESSION_LEN) return fail(SRN_ERANGE, "evolving session longer than SRN_MAX_SESSION_LEN");
+        size_t wide = 0;
+        int rc = check_excl_args(idx, nq, max_len, excl_flat, excl_off, max_excl, k, m, how_many, flags & ~(unsigned)SRN_FLAG_INPUTS_RESIDENT, &wide); if (rc) return rc;
+        if (max_excl) for (size_t q = 0; q < nq; ++q) if (excl_off[q + 1] < excl_off[q]) return fail(SRN_EINVAL, "excl_off not monotone");
+        if (wide == how_many) return predict_host(idx, items_flat, q_off, nq, k, m, how_many, flags & (unsigned)SRN_FLAG_BUSINESS_LOGIC, out_ids, out_scores, out_counts, nullptr, nullptr, nullptr, nullptr);   // nothing can be excluded: the plain call
+        LaunchParams p{};
+        p.nq = (uint32_t)nq; p.k = (uint32_t)k; p.m = (uint32_t)m; p.how_many = (uint32_t)wide; p.flags = flags & (unsigned)SRN_FLAG_BUSINESS_LOGIC; p.max_len = max_len;
+        const ExclSpec x{max_excl ? excl_flat : nullptr, max_excl ? excl_off : nullptr, (uint32_t)max_excl, (flags & SRN_FLAG_EXCLUDE_SESSION) != 0u, (uint32_t)how_many, nullptr, nullptr, nullptr};
+        return device_predict(idx->dev, idx->flat, p, false, nullptr, items_flat, q_off, out_ids, out_scores, out_counts, nullptr, nullptr, nullptr, nullptr, nullptr, false, false, &x); });
+}
+
+int srn_debug_exclude_filter(const srn_index_t* idx, size_t nq, const uint64_t* d_wide_ids, const double* d_wide_scores, const uint32_t* d_wide_counts, size_t wide, const uint64_t* d_excl_flat,
+                             const uint32_t* d_excl_off, size_t max_excl, const uint64_t* d_items_flat, const uint32_t* d_q_off, size_t how_many, uint64_t* d_out_ids, double* d_out_scores,
+                             uint32_t* d_out_counts, void* stream) {
+    return guarded([&]() -> int {
+        if (!idx || !idx->dev) return fail(SRN_ENODEV, "index has no device attached");
+        if (!d_wide_ids || !d_wide_scores || !d_wide_counts || !d_out_ids || !d_out_scores || !d_out_counts || (d_excl_flat != nullptr) != (d_excl_off != nullptr) || (d_items_flat && !d_q_off))
+            return fail(SRN_EINVAL, "null buffer");
+        if (nq > 0x7FFFFFFFull || how_many == 0 || wide < how_many || wide > SRN_MAX_HOW_MANY || max_excl > SRN_MAX_HOW_MANY) return fail(SRN_ERANGE, "srn_debug_exclude_filter: sizes out of range");
+        return device_exclude_filter(idx->dev, (uint32_t)nq, d_wide_ids, d_wide_scores, d_wide_counts, (uint32_t)wide, d_excl_flat, d_excl_off, (uint32_t)max_excl, d_items_flat, d_q_off,
+                                     d_out_ids, d_out_scores, d_out_counts, (uint32_t)how_many, stream); });
+}
+
 int srn_index_reserve(const srn_index_t* idx, size_t nq, size_t max_len_hint, size_t k, size_t m, size_t how_many, unsigned flags, void* stream) {
     return guarded([&]() -> int {
         int rc = check_predict_args(idx, k, m, how_many); if (rc) return rc;
@@ -651,6 +718,8 @@ int srn_device_sessions_sweep(srn_device_sessions_t* s, uint64_t now_secs, uint6
     return guarded([&]() -> int { return dsess_sweep(s, now_secs, n_live); });
 }
 int srn_device_sessions_stats(srn_device_sessions_t* s, srn_device_sessions_stats_t* out) { return guarded([&]() -> int { return dsess_stats(s, out); }); }
+int srn_device_sessions_set_history(srn_device_sessions_t* s, size_t history) { return guarded([&]() -> int { return dsess_set_history(s, history); }); }
+int srn_device_sessions_history(srn_device_sessions_t* s, size_t* out_history) { return guarded([&]() -> int { return dsess_history(s, out_history); }); }
 int srn_device_sessions_timing(srn_device_sessions_t* s, int enable) { return guarded([&]() -> int { return dsess_timing(s, enable); }); }
 int srn_device_sessions_last_ms(srn_device_sessions_t* s, double* out_ms_store, double* out_ms_predict) {
     return guarded([&]() -> int { return dsess_last_ms(s, out_ms_store, out_ms_predict); });
@@ -699,7 +768,7 @@ static int check_recommend_args(const srn_index_t* idx, size_t n, size_t k, size
     rc = check_not_a_shard(idx); if (rc) return rc;
     if (n == 0) { *done = true; return SRN_OK; }
     if (!buffers) return fail(SRN_EINVAL, "null buffer");
-    if (flags & ~(unsigned)SRN_FLAG_BUSINESS_LOGIC) return fail(SRN_EINVAL, "srn_recommend_batch: unknown flags");
+    if (flags & ~(unsigned)(SRN_FLAG_BUSINESS_LOGIC | SRN_FLAG_EXCLUDE_SEEN)) return fail(SRN_EINVAL, "srn_recommend_batch: unknown flags");
     return SRN_OK;
 }
 int srn_recommend_batch_device(const srn_index_t* idx, srn_device_sessions_t* store, const uint64_t* d_key_hi, const uint64_t* d_key_lo, const uint64_t* d_item_ids,

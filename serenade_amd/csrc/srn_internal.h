@@ -137,11 +137,19 @@ struct ExtLists { const char* prep; uint32_t prep_stride; const uint32_t* post_r
                   int mode = 0; uint32_t* xchg = nullptr; uint32_t xchg_stride = 0; uint32_t q_lo = 0;
                   const unsigned long long* order = nullptr;     // mode 2: the batch's serving order (device_shard_nb_prep sorted it), or null
                   bool positions = false; };                     // mode 2: xchg holds position records (device_shard_nb_positions), not neighbour slots: the streaming back end
+// Exclusion lists (srn_exclude.hip).  The call's LaunchParams carry the INTERNAL how_many W = how_many + the lists' capacity and no output buffers: the
+// launch sequence writes wide rows into the workspace's scratch, and the filter kernel behind it writes the caller's rows.  Device pointers; x_flat / x_off may be null
+// (max_excl 0); session: the items of the query's own session are excluded too (SRN_FLAG_EXCLUDE_SESSION).  A host-pointer call (srn_predict_batch_excl) hands x_flat / x_off
+// as host pointers and leaves out_* null: the rows come back through device_predict's h_ids / h_scores / h_counts
+struct ExclSpec { const uint64_t* x_flat; const uint32_t* x_off; uint32_t max_excl; bool session; uint32_t how_many; uint64_t* out_ids; double* out_scores; uint32_t* out_counts; };
 int device_predict(DeviceState* d, const FlatIndex& ix, const LaunchParams& p, bool buffers_on_device, void* stream,
                    // host-pointer mode: these are host buffers copied in/out by the call
                    const uint64_t* h_items, const uint32_t* h_qoff, uint64_t* h_ids, double* h_scores,
                    uint32_t* h_counts, uint32_t* h_stats, uint32_t* h_nb_rank, uint32_t* h_nb_num, uint32_t* h_nb_cnt, const ExtLists* ext = nullptr,
-                   bool reserve_only = false, bool blocking_wait = false);   // reserve_only (srn_index_reserve): size the call's workspace, enqueue nothing; blocking_wait: the latency path sleeps on an interrupt instead of spinning
+                   bool reserve_only = false, bool blocking_wait = false, const ExclSpec* excl = nullptr);   // reserve_only (srn_index_reserve): size the call's workspace, enqueue nothing; blocking_wait: the latency path sleeps on an interrupt instead of spinning
+// measurement aid (srn_debug_exclude_filter): the filter kernel alone over the caller's wide rows, enqueued on `stream`
+int device_exclude_filter(DeviceState* d, uint32_t nq, const uint64_t* w_ids, const double* w_scores, const uint32_t* w_counts, uint32_t wide, const uint64_t* x_flat, const uint32_t* x_off,
+                          uint32_t max_excl, const uint64_t* items_flat, const uint32_t* q_off, uint64_t* out_ids, double* out_scores, uint32_t* out_counts, uint32_t how_many, void* stream);
 struct ShardIO {
     void* cand; uint32_t* cand_cnt;                                       // A out: [nq * m] packed slots, [nq]
     const void* gathered; const uint32_t* gathered_cnt; uint32_t n_shards;   // B in: [G][nq * gathered_stride], [G][nq]
@@ -259,6 +267,8 @@ int dsess_update(srn_device_sessions* s, uint64_t hi, uint64_t lo, uint64_t now_
 int dsess_sweep(srn_device_sessions* s, uint64_t now_secs, uint64_t* n_live);
 int dsess_stats(srn_device_sessions* s, srn_device_sessions_stats_t* out);
 int dsess_timing(srn_device_sessions* s, int enable);
+int dsess_set_history(srn_device_sessions* s, size_t history);
+int dsess_history(srn_device_sessions* s, size_t* out);
 int dsess_last_ms(srn_device_sessions* s, double* ms_store, double* ms_predict);
 int dsess_last_csr(srn_device_sessions* s, const void** d_items, const void** d_qoff, size_t* n, size_t* max_len, uint64_t* h_items, size_t cap, uint32_t* h_qoff);
 int dsess_count(srn_device_sessions* s, uint64_t now_secs, uint64_t* occupied, uint64_t* live);

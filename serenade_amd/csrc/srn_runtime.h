@@ -91,6 +91,7 @@ struct Workspace {
     char* pin = nullptr; size_t pin_bytes = 0;   // pinned, device-mapped staging of the latency path (a handful of queries on host pointers)
     // staging for host-pointer calls
     char* stage = nullptr; size_t stage_bytes = 0;
+    char* wide = nullptr; size_t wide_bytes = 0;   // calls with exclusion lists (srn_exclude.hip): the wide rows, ids | scores | counts at the internal how_many (host-pointer calls: the lists and the caller-sized rows)
     std::mutex call_mu;            // a stream-bound workspace serves one call at a time: two host threads enqueueing on the SAME stream must not interleave their launch sequences (they share these buffers)
     bool cnt_dirty = true;          // slow_cnt may hold non-zero words (any launch sequence but a fused one that handed nothing on leaves them so)
     uint32_t tiny_seq = 0;          // number of the latency path's last fused call (the kernel writes it into h_retry[HW_SEQ] when the row is complete)
@@ -171,5 +172,11 @@ int device_predict_host_pipelined(DeviceState* d, const FlatIndex& ix, const Lau
                                   uint64_t* h_ids, double* h_scores, uint32_t* h_counts);
 uint32_t hostpipe_chunks(uint32_t nq, uint32_t how_many);
 std::shared_ptr<ResultCache> device_result_cache(DeviceState* d);   // the enabled cache, or null
+// srn_exclude.hip: the wide rows' room in the workspace, and the filter kernel over them (x_flat / items_flat may be null)
+int exclude_wide_room(Workspace* w, uint32_t nq, uint32_t W, uint64_t** ids, double** scores, uint32_t** counts);
+int exclude_host_room(Workspace* w, hipStream_t st, uint32_t nq, ExclSpec& x);   // host-pointer calls: the lists' device copies and the caller-sized rows (the staged output rows are the wide ones)
+int exclude_fetch_host(hipStream_t st, uint32_t nq, const ExclSpec& x, uint64_t* h_ids, double* h_scores, uint32_t* h_counts);
+hipError_t launch_exclude(hipStream_t st, uint32_t nq, const uint64_t* w_ids, const double* w_scores, const uint32_t* w_counts, uint32_t W, const uint64_t* x_flat, const uint32_t* x_off,
+                          uint32_t max_excl, const uint64_t* items_flat, const uint32_t* q_off, uint64_t* out_ids, double* out_scores, uint32_t* out_counts, uint32_t how_many);
 
 }  // namespace srn

@@ -212,6 +212,7 @@ static void ws_free(Workspace* w) {
     if (w->big) hipFree(w->big);
     if (w->pin) hipHostFree(w->pin);
     if (w->stage) hipFree(w->stage);
+    if (w->wide) hipFree(w->wide);
     if (w->h_retry) hipHostFree(w->h_retry);
     if (w->ev_block) hipEventDestroy(w->ev_block);
     if (w->prep2) hipFree(w->prep2);
@@ -786,10 +787,12 @@ static int enqueue_batch(BatchCall& c, bool on_device) {
 
 int device_predict(DeviceState* d, const FlatIndex& ix, const LaunchParams& p_in, bool on_device, void* user_stream,
                    const uint64_t* h_items, const uint32_t* h_qoff, uint64_t* h_ids, double* h_scores, uint32_t* h_counts,
-                   uint32_t* h_stats, uint32_t* h_nb_rank, uint32_t* h_nb_num, uint32_t* h_nb_cnt, const ExtLists* ext, bool reserve_only, bool blocking_wait) {
+                   uint32_t* h_stats, uint32_t* h_nb_rank, uint32_t* h_nb_num, uint32_t* h_nb_cnt, const ExtLists* ext, bool reserve_only, bool blocking_wait, const ExclSpec* excl) {
     HIP_TRY(hipSetDevice(d->device));
     LaunchParams p = p_in;
     if (p.nq == 0) return SRN_OK;
+    if (excl && (ext || h_stats || h_nb_rank)) return fail(SRN_EINVAL, "exclusion lists: batch calls on an unsharded index only");
+    ExclSpec xs{}; if (excl) xs = *excl;
     // SRN_FLAG_INPUTS_RESIDENT (device-pointer calls): the query buffers are complete in device memory at call time, so the prep kernel of THIS call may run on a side
     // stream while the previous call's kernels still occupy the caller's stream (enqueue_front_resident); the kernels never see the flag
     const bool resident = on_device && !ext && (p.flags & SRN_FLAG_INPUTS_RESIDENT) != 0u;
@@ -808,7 +811,7 @@ int device_predict(DeviceState* d, const FlatIndex& ix, const LaunchParams& p_in
     hipStream_t st = on_device ? (hipStream_t)user_stream : w->stream;
     Geometry geo; { int rc = make_geometry(d, ix, p, 0, geo); if (rc) return rc; }
 
-    if (!on_device && !reserve_only && !h_stats && !h_nb_rank) {
+    if (!on_device && !reserve_only && !h_stats && !h_nb_rank && !excl) {
         if (p.nq <= (uint32_t)knobs().tiny_max && !d->phase_on) {
             const int rc = device_predict_tiny(d, ix, w, geo, p, h_items, h_qoff, h_ids, h_scores, h_counts, blocking_wait);
             if (rc != 1) { if (rcache) rcache->bypassed.fetch_add(1, std::memory_order_relaxed); return rc; }   // (1: some query needs the global-table pass -- the paths below have it)
@@ -820,6 +823,9 @@ int device_predict(DeviceState* d, const FlatIndex& ix, const LaunchParams& p_in
     }
     // ---- plan -> reserve -> enqueue ----
     if (!on_device) { int rc = stage_host_inputs(w, st, p, h_items, h_qoff, h_stats != nullptr, h_nb_rank != nullptr); if (rc) return rc; }   // (p.stats / p.nb_rank decide the plan)
+    // exclusion lists (srn_exclude.hip): p.how_many is the internal, wide one -- the launch sequence writes wide rows (the workspace's scratch; a host-pointer call's staged
+    // rows), the filter behind it the caller's
+    if (excl) { int rc = on_device ? exclude_wide_room(w, p.nq, p.how_many, &p.out_ids, &p.out_scores, &p.out_counts) : exclude_host_room(w, st, p.nq, xs); if (rc) return rc; }
     const LaunchPlan pl = make_plan(d, ix, p, geo, ext, resident, w, no_cache ? nullptr : rcache.get());
     BatchCall c{d, w, pl, ext, st, di, p}; c.rcache = rcache.get();
     if (rcache && !pl.cache && !reserve_only) rcache->bypassed.fetch_add(1, std::memory_order_relaxed);
@@ -829,6 +835,9 @@ int device_predict(DeviceState* d, const FlatIndex& ix, const LaunchParams& p_in
     if (ext && ext->prep_stride != pl.prep_stride) return fail(SRN_EINVAL, "prep record stride mismatch");
     if (ext && ext->mode == 1) return enqueue_shard_front(c);
     { int rc = enqueue_batch(c, on_device); if (rc) return rc; }
+    if (excl) HIP_TRY(launch_exclude(st, p.nq, p.out_ids, p.out_scores, p.out_counts, p.how_many, xs.x_flat, xs.x_off, xs.max_excl, xs.session ? p.items_flat : nullptr, p.q_off,
+                                     xs.out_ids, xs.out_scores, xs.out_counts, xs.how_many));
+    if (excl && !on_device) return exclude_fetch_host(st, p.nq, xs, h_ids, h_scores, h_counts);
     return on_device ? SRN_OK : fetch_host_outputs(c, h_ids, h_scores, h_counts, h_stats, h_nb_rank, h_nb_num, h_nb_cnt);
 }
 

@@ -20,6 +20,10 @@
 //   sess_emit       every request copies its window into items_flat: O(window) per request, whatever the run's length
 //   sess_store      the last request of a run writes its window -- the final session -- and the epoch back, once
 //   device_predict  on (items_flat, q_off)
+// With a history window (srn_device_sessions_set_history) the store keeps the last H clicks under the same rules -- H takes the limit's place in sess_len and
+// sess_store -- and predict reads the last min(window, max_items_in_session) items of each window: sess_len writes that length too, a second scan gives p_off, and
+// sess_emit copies the window's suffix into a second buffer.  SRN_FLAG_EXCLUDE_SEEN hands the windows (items_flat, q_off) to the exclusion filter (srn_exclude.hip) as the
+// call's exclusion CSR.
 //
 // The store is the one state of the library that training data cannot rebuild, so whole stores move in bulk, each pass behind `last`:
 //   export          live flag per slot, exclusive scan, scatter in slot order into dense arrays (no atomic cursor: an unchanged store exports the same bytes)
@@ -67,7 +71,8 @@ struct BatchArgs {
     Table t;
     const uint64_t* key_hi; const uint64_t* key_lo; const uint64_t* item; const uint8_t* consent;   // the caller's arrays
     const uint32_t* order;   // [n] request index of each sorted position
-    uint32_t n, max_items;
+    uint32_t n, max_items;   // max_items: what predict reads of a window
+    uint32_t limit;          // what the store keeps: max_items, or the history window H
     uint64_t now, idle;
     uint32_t* slot_of;       // [n] by sorted position of a run head: its slot (kNone: table full -- cannot happen under the capacity rule)
     uint32_t* slen;          // [n] ... and the stored length the run starts from (0 if idle)
@@ -79,6 +84,9 @@ struct BatchArgs {
     uint32_t* qlen;          // [n + 1] by REQUEST index
     uint32_t* q_off;         // [n + 1]
     uint64_t* items_flat;
+    uint32_t* plen;          // history window only (null otherwise): [n + 1] by REQUEST index, the length predict reads; p_off its exclusive scan; pflat those suffixes
+    uint32_t* p_off;
+    uint64_t* pflat;
     uint32_t* err;
 };
 __device__ __forceinline__ bool consents(const BatchArgs& a, uint32_t req) { return a.consent == nullptr || a.consent[req] != 0; }
@@ -137,11 +145,13 @@ __global__ void __launch_bounds__(kTPB) sess_find(BatchArgs a) {
 __global__ void __launch_bounds__(kTPB) sess_len(BatchArgs a) {
     const uint32_t p = blockIdx.x * kTPB + threadIdx.x;
     if (p > a.n) return;
-    if (p == a.n) { a.qlen[a.n] = 0; return; }
+    if (p == a.n) { a.qlen[a.n] = 0; if (a.plen) a.plen[a.n] = 0; return; }
     const uint32_t req = a.order[p];
-    if (!consents(a, req)) { a.qlen[req] = 1; return; }
+    if (!consents(a, req)) { a.qlen[req] = 1; if (a.plen) a.plen[req] = 1; return; }
     const uint32_t s = a.run_start[p], S = a.slen[s], app = a.kex[p + 1] - a.kex[s];
-    a.qlen[req] = S >= a.max_items ? S : min(S + app, a.max_items);
+    const uint32_t wlen = S >= a.limit ? S : min(S + app, a.limit);
+    a.qlen[req] = wlen;
+    if (a.plen) a.plen[req] = min(wlen, a.max_items);
     if (a.kept[p]) a.compact[a.kex[p]] = a.item[req];
 }
 
@@ -150,12 +160,17 @@ __global__ void __launch_bounds__(kTPB) sess_emit(BatchArgs a) {
     if (p >= a.n) return;
     const uint32_t req = a.order[p];
     uint64_t* dst = a.items_flat + a.q_off[req];
-    if (!consents(a, req)) { dst[0] = a.item[req]; return; }
+    uint64_t* pdst = a.pflat ? a.pflat + a.p_off[req] : nullptr;
+    if (!consents(a, req)) { dst[0] = a.item[req]; if (pdst) pdst[0] = a.item[req]; return; }
     const uint32_t s = a.run_start[p], S = a.slen[s], app = a.kex[p + 1] - a.kex[s], len = a.q_off[req + 1] - a.q_off[req];
     const uint32_t first = S + app - len;
     const uint64_t* stored = S ? slot_items(slot_at(a.t, a.slot_of[s])) : nullptr;
     const uint64_t* clicks = a.compact + a.kex[s];
     for (uint32_t i = 0; i < len; ++i) { const uint32_t at = first + i; dst[i] = at < S ? stored[at] : clicks[at - S]; }
+    if (pdst) {   // the window's suffix predict reads
+        const uint32_t pl = a.p_off[req + 1] - a.p_off[req], pfirst = S + app - pl;
+        for (uint32_t i = 0; i < pl; ++i) { const uint32_t at = pfirst + i; pdst[i] = at < S ? stored[at] : clicks[at - S]; }
+    }
 }
 
 __global__ void __launch_bounds__(kTPB) sess_store(BatchArgs a) {
@@ -378,6 +393,7 @@ struct srn_device_sessions {
     hipStream_t own = nullptr;                              // get / update / sweep and the host-pointer entry point
     uint64_t bound = 0, sweeps = 0, refused = 0;            // bound: upper bound of the occupied slots
     uint32_t len_bound = 1;                                 // upper bound of the stored session lengths (predict's max_len_hint)
+    uint32_t history = 0;                                   // srn_device_sessions_set_history: the window the store keeps (0: max_items_in_session, as the reference)
     char* ws = nullptr; size_t ws_bytes = 0;                // per-batch scratch, grows with the largest n seen
     char* stage = nullptr; size_t stage_bytes = 0;          // the host-pointer entry point's device copies
     std::mutex stage_mu;
@@ -588,6 +604,20 @@ int dsess_stats(srn_device_sessions* s, srn_device_sessions_stats_t* out) {
     return SRN_OK;
 }
 
+int dsess_set_history(srn_device_sessions* s, size_t history) {
+    if (!s) return fail(SRN_EINVAL, "srn_device_sessions_set_history: null store");
+    std::lock_guard<std::mutex> g(s->mu);
+    if (history > s->items_cap) return fail(SRN_ERANGE, "srn_device_sessions_set_history: history above the store's items_cap");
+    s->history = (uint32_t)history;
+    return SRN_OK;
+}
+int dsess_history(srn_device_sessions* s, size_t* out) {
+    if (!s || !out) return fail(SRN_EINVAL, "srn_device_sessions_history: null argument");
+    std::lock_guard<std::mutex> g(s->mu);
+    *out = s->history;
+    return SRN_OK;
+}
+
 int dsess_timing(srn_device_sessions* s, int enable) {
     if (!s) return fail(SRN_EINVAL, "srn_device_sessions_timing: null store");
     std::lock_guard<std::mutex> g(s->mu);
@@ -655,9 +685,10 @@ int dsess_recommend_device(const srn_index* idx, srn_device_sessions* s, const u
     if (n > kMaxBatch) return fail(SRN_ERANGE, "srn_recommend_batch: more than 2^24 requests in one call");
     hipStream_t st = (hipStream_t)stream;
     LaunchParams p{};
-    p.nq = (uint32_t)n; p.k = (uint32_t)k; p.m = (uint32_t)m; p.how_many = (uint32_t)how_many; p.flags = flags;
+    const bool excl_seen = (flags & SRN_FLAG_EXCLUDE_SEEN) != 0u;
+    p.nq = (uint32_t)n; p.k = (uint32_t)k; p.m = (uint32_t)m; p.how_many = (uint32_t)how_many; p.flags = flags & ~(unsigned)SRN_FLAG_EXCLUDE_SEEN;
     p.out_ids = d_ids; p.out_scores = d_scores; p.out_counts = d_counts;
-    if (!s) {
+    if (!s) {   // (every session is its item, which is never in its own row: SRN_FLAG_EXCLUDE_SEEN has nothing to exclude)
         if (max_items > SRN_MAX_SESSION_LEN) return fail(SRN_ERANGE, "srn_recommend_batch: max_items_in_session above SRN_MAX_SESSION_LEN");
         return recommend_no_store(idx, d_item, d_consent, n, p, st);
     }
@@ -665,9 +696,14 @@ int dsess_recommend_device(const srn_index* idx, srn_device_sessions* s, const u
     if (s->device != idx->device) return fail(SRN_EINVAL, "srn_recommend_batch: the store and the index are on different devices");
     const uint64_t now = now_secs ? now_secs : wall_secs();
     std::lock_guard<std::mutex> g(s->mu);
+    const uint32_t H = s->history, limit = H ? H : (uint32_t)max_items;
+    if (H > s->items_cap) return fail(SRN_ERANGE, "srn_recommend_batch: the store's history window is above its items_cap (lowered by a resize): set a smaller history or resize again");
+    if (H && max_items > H) return fail(SRN_ERANGE, "srn_recommend_batch: max_items_in_session above the store's history window");
+    const uint32_t hint = std::max<uint32_t>(s->len_bound, limit);          // the longest window the store may hold behind this call
+    const uint32_t phint = H ? (uint32_t)max_items : hint;                  // ... and the longest session predict reads
+    if (excl_seen && how_many + hint > SRN_MAX_HOW_MANY) return fail(SRN_ERANGE, "srn_recommend_batch: how_many + the store's longest window above SRN_MAX_HOW_MANY (SRN_FLAG_EXCLUDE_SEEN)");
     int rc = make_room(s, n, now); if (rc) return rc;
     HIP_TRY(hipSetDevice(s->device));
-    const uint32_t hint = std::max<uint32_t>(s->len_bound, (uint32_t)max_items);
     // scratch: sort keys and indices (double-buffered), the per-position and per-request words, the kept clicks, the CSR batch, rocPRIM's temporary storage
     size_t tmp = 0, t1 = 0;
     HIP_TRY(rocprim::radix_sort_pairs(nullptr, t1, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, n, 0, 64, st)); tmp = std::max(tmp, t1);
@@ -677,7 +713,8 @@ int dsess_recommend_device(const srn_index* idx, srn_device_sessions* s, const u
     const size_t w = align256((n + 1) * 4);
     const size_t o_keyA = 0, o_keyB = o_keyA + align256(n * 8), o_idxA = o_keyB + align256(n * 8), o_idxB = o_idxA + w, o_slot = o_idxB + w, o_slen = o_slot + w,
                  o_kept = o_slen + w, o_head = o_kept + w, o_kex = o_head + w, o_run = o_kex + w, o_qlen = o_run + w, o_qoff = o_qlen + w, o_comp = o_qoff + w,
-                 o_flat = o_comp + align256(n * 8), o_tmp = o_flat + align256(n * (size_t)hint * 8), bytes = o_tmp + align256(tmp);
+                 o_flat = o_comp + align256(n * 8), o_tmp = o_flat + align256(n * (size_t)hint * 8),
+                 o_plen = o_tmp + align256(tmp), o_poff = o_plen + (H ? w : 0), o_pflat = o_poff + (H ? w : 0), bytes = o_pflat + (H ? align256(n * (size_t)phint * 8) : 0);
     if (bytes > s->ws_bytes) {   // (the previous call may still read the scratch: wait for it before it is freed)
         HIP_TRY(hipEventSynchronize(s->last));
         if ((rc = ensure(&s->ws, &s->ws_bytes, bytes))) return rc;
@@ -701,7 +738,8 @@ int dsess_recommend_device(const srn_index* idx, srn_device_sessions* s, const u
         order = idxB;
     }
     BatchArgs a{};
-    a.t = s->tab(); a.key_hi = d_hi; a.key_lo = d_lo; a.item = d_item; a.consent = d_consent; a.order = order; a.n = n32; a.max_items = (uint32_t)max_items;
+    a.t = s->tab(); a.key_hi = d_hi; a.key_lo = d_lo; a.item = d_item; a.consent = d_consent; a.order = order; a.n = n32; a.max_items = (uint32_t)max_items; a.limit = limit;
+    if (H) { a.plen = (uint32_t*)(b + o_plen); a.p_off = (uint32_t*)(b + o_poff); a.pflat = (uint64_t*)(b + o_pflat); }
     a.now = now; a.idle = s->idle;
     a.slot_of = (uint32_t*)(b + o_slot); a.slen = (uint32_t*)(b + o_slen); a.kept = (uint32_t*)(b + o_kept); a.headpos = (uint32_t*)(b + o_head);
     a.kex = (uint32_t*)(b + o_kex); a.run_start = (uint32_t*)(b + o_run); a.qlen = (uint32_t*)(b + o_qlen); a.q_off = (uint32_t*)(b + o_qoff);
@@ -711,16 +749,22 @@ int dsess_recommend_device(const srn_index* idx, srn_device_sessions* s, const u
     t1 = tmp; HIP_TRY(rocprim::inclusive_scan(b + o_tmp, t1, a.headpos, a.run_start, n, rocprim::maximum<uint32_t>(), st));
     sess_len<<<gn1, kTPB, 0, st>>>(a);
     t1 = tmp; HIP_TRY(rocprim::exclusive_scan(b + o_tmp, t1, a.qlen, a.q_off, 0u, n + 1, rocprim::plus<uint32_t>(), st));
+    if (H) { t1 = tmp; HIP_TRY(rocprim::exclusive_scan(b + o_tmp, t1, a.plen, a.p_off, 0u, n + 1, rocprim::plus<uint32_t>(), st)); }
     sess_emit<<<gn, kTPB, 0, st>>>(a);
     sess_store<<<gn, kTPB, 0, st>>>(a);
     HIP_TRY(hipGetLastError());
     // from here on the store has changed: whatever happens below, the next call is ordered behind this one
     s->bound += n;
     s->len_bound = hint;
-    s->last_items = a.items_flat; s->last_qoff = a.q_off; s->last_n = n; s->last_hint = hint;
+    p.max_len = phint; p.items_flat = H ? a.pflat : a.items_flat; p.q_off = H ? a.p_off : a.q_off;
+    s->last_items = p.items_flat; s->last_qoff = p.q_off; s->last_n = n; s->last_hint = phint;
     if (timed) (void)hipEventRecord(s->tev[1], st);
-    p.max_len = hint; p.items_flat = a.items_flat; p.q_off = a.q_off;
-    rc = device_predict(idx->dev, idx->flat, p, true, st, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+    if (excl_seen) {   // the windows are the exclusion CSR, the bound of their lengths its capacity: the launch sequence runs at how_many + hint (srn_exclude.hip)
+        const ExclSpec x{a.items_flat, a.q_off, hint, false, (uint32_t)how_many, d_ids, d_scores, d_counts};
+        p.how_many = (uint32_t)how_many + hint; p.out_ids = nullptr; p.out_scores = nullptr; p.out_counts = nullptr;
+        rc = device_predict(idx->dev, idx->flat, p, true, st, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, false, false, &x);
+    } else
+        rc = device_predict(idx->dev, idx->flat, p, true, st, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
     (void)hipSetDevice(s->device);
     if (timed) (void)hipEventRecord(s->tev[2], st);
     s->last_timed = timed;

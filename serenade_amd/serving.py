@@ -93,6 +93,25 @@ def recommend(batcher, store, session_id, item_id, user_consent=True, max_items_
 
 # ---- the device-resident store and /v1/recommend for a whole batch (srn_device_sessions_*, srn_recommend_batch*) ----
 
+def filter_rows(ids, scores, counts, excl, how_many):
+    """NumPy mirror of the exclusion filter (srn_exclude.hip): rows [nq, W] with `counts` valid entries each -> rows [nq, how_many] without the ids of
+    excl[q] (a list of nq sequences of ids), order kept, counts = min(kept, how_many).  A count of 0xFFFFFFFF is passed on; the entries beyond a count are 0.  It needs no GPU:
+    what the device path computes from the wide rows, and what the tests compare it with."""
+    ids, scores, counts = np.asarray(ids, np.uint64), np.asarray(scores, np.float64), np.asarray(counts, np.uint32)
+    nq, wide = ids.shape
+    if len(excl) != nq:
+        raise ValueError("excl must hold one list per row")
+    out_ids, out_sc, out_cnt = np.zeros((nq, how_many), np.uint64), np.zeros((nq, how_many)), np.zeros(nq, np.uint32)
+    for q in range(nq):
+        if counts[q] == 0xFFFFFFFF:
+            out_cnt[q] = 0xFFFFFFFF
+            continue
+        n = min(int(counts[q]), wide)
+        keep = np.flatnonzero(~np.isin(ids[q, :n], np.asarray(list(excl[q]), np.uint64)))[:how_many]
+        out_ids[q, :len(keep)], out_sc[q, :len(keep)], out_cnt[q] = ids[q, keep], scores[q, keep], len(keep)
+    return out_ids, out_sc, out_cnt
+
+
 def _is_torch(x):
     return type(x).__module__.split(".")[0] == "torch"
 
@@ -188,14 +207,28 @@ def read_session_snapshot(path):
 class DeviceSessionStore:
     """The evolving sessions in the GPU's memory: what recommend_batch reads and updates.  get / update / sweep mirror SessionStore's, for one key, from the host."""
 
-    def __init__(self, device_or_index, capacity, items_cap=16, ttl_secs=30 * 60, idle_secs=20 * 60, max_capacity=None):
-        """max_capacity: opt-in growth -- a batch the capacity rule would refuse doubles the capacity (up to max_capacity) instead; None = a fixed capacity."""
+    def __init__(self, device_or_index, capacity, items_cap=16, ttl_secs=30 * 60, idle_secs=20 * 60, max_capacity=None, history=0):
+        """max_capacity: opt-in growth -- a batch the capacity rule would refuse doubles the capacity (up to max_capacity) instead; None = a fixed capacity.
+        history: the store keeps a window of the last `history` clicks (<= items_cap) and recommend_batch predicts on its last max_items_in_session items; 0 = the
+        store keeps max_items_in_session items, as the reference does."""
         device = device_or_index if isinstance(device_or_index, int) else device_or_index.info["device"]
         h = C.c_void_p()
         capi.check(capi.lib().srn_device_sessions_create(int(device), int(capacity), int(items_cap), int(ttl_secs), int(idle_secs), C.byref(h)))
         self._h, self.device, self.items_cap = h, int(device), int(items_cap)
         if max_capacity:
             capi.check(capi.lib().srn_device_sessions_set_max_capacity(self._h, int(max_capacity)))
+        if history:
+            self.set_history(history)
+
+    def set_history(self, history):
+        """srn_device_sessions_set_history: the window of clicks the store keeps (0 = max_items_in_session).  A runtime setting, not saved: set it again after load."""
+        capi.check(capi.lib().srn_device_sessions_set_history(self._h, int(history)))
+
+    @property
+    def history(self):
+        h = C.c_size_t()
+        capi.check(capi.lib().srn_device_sessions_history(self._h, C.byref(h)))
+        return h.value
 
     @classmethod
     def load(cls, device_or_index, path, capacity=None, items_cap=None, ttl_secs=None, idle_secs=None):
@@ -334,11 +367,13 @@ class DeviceSessionStore:
 
 
 def recommend_batch(index, store, keys, item_ids, consent=None, *, k, m, how_many, max_items_in_session=2, enable_business_logic=False, now=0,
-                    scores=False):
+                    scores=False, exclude_seen=False):
     """/v1/recommend for a batch: request i = (keys[i], item_ids[i], consent[i]); the result is what the requests served one after the other give.
     keys: (hi, lo) uint64 arrays / tensors, or a list of session-id strings.  -> (ids[n, how_many], counts[n]) and scores[n, how_many] with scores=True.
     NumPy arrays (or CPU tensors) in, NumPy arrays out; tensors on the index's GPU are read in place (on the current stream, without synchronising) and the
-    outputs are tensors on it.  store may be None only if no request consents."""
+    outputs are tensors on it.  store may be None only if no request consents.
+    exclude_seen (SRN_FLAG_EXCLUDE_SEEN): a request's rows leave out its visitor's window as the request sees it -- the store's history window, or the session window on a
+    store without one; without consent nothing beyond the item itself."""
     n = len(item_ids)
     if isinstance(keys, list) and (not keys or isinstance(keys[0], (str, bytes))):
         if len(keys) != n:
@@ -348,7 +383,7 @@ def recommend_batch(index, store, keys, item_ids, consent=None, *, k, m, how_man
     arrs = [hi, lo, item_ids] + ([consent] if consent is not None else [])
     if any(len(a) != n for a in arrs):
         raise ValueError("keys, item_ids and consent differ in length")
-    flags = capi.FLAG_BUSINESS_LOGIC if enable_business_logic else 0
+    flags = (capi.FLAG_BUSINESS_LOGIC if enable_business_logic else 0) | (capi.FLAG_EXCLUDE_SEEN if exclude_seen else 0)
     sh = store._h if store is not None else None
     on_gpu = [_is_torch(a) and a.device.type == "cuda" for a in arrs]
     if any(on_gpu):

@@ -298,12 +298,40 @@ def predict(index, evolving_session, k, m, how_many, enable_business_logic):
     return [ItemScore(int(i), float(s)) for i, s in zip(ids[:n.value], sc[:n.value])]
 
 
-def predict_batch(index, sessions, k, m, how_many, enable_business_logic=False, out=None):
+def _flatten_exclude(exclude, nq):
+    """The exclusion lists of a batch -- a list of nq sequences of item ids, or CSR(ids_flat, off) -> (ids u64, off u32, the longest list)."""
+    if isinstance(exclude, CSR):
+        _is_csr_pair(exclude)
+        xf, xo = capi.as_u64(exclude[0]), capi.as_u32(exclude[1])
+    else:
+        xo = np.zeros(len(exclude) + 1, np.uint32)
+        xo[1:] = np.cumsum([len(x) for x in exclude])
+        xf = np.fromiter((i for x in exclude for i in x), dtype=np.uint64, count=int(xo[-1]))
+    if len(xo) - 1 != nq:
+        raise ValueError("exclude must hold one list per query (%d lists for %d queries)" % (len(xo) - 1, nq))
+    return xf, xo, int(np.diff(xo.astype(np.int64)).max()) if nq else 0
+
+
+def predict_batch(index, sessions, k, m, how_many, enable_business_logic=False, out=None, exclude=None, exclude_session=False, max_excl=None):
     """Many evolving sessions in one call (list of sequences, or (items_flat, q_off)).
     -> (ids u64[nq, how_many], scores f64[nq, how_many], counts u32[nq]).  out = (ids, scores, counts) of an earlier call of the same
-    shape: the result buffers are reused (what a serving / evaluator host does) instead of freshly allocated."""
+    shape: the result buffers are reused (what a serving / evaluator host does) instead of freshly allocated.
+    exclude: per query a list of item ids that must not be recommended (a list of nq lists, or CSR(ids_flat, off)); exclude_session: neither may any item of the query's own
+    session.  The rows are those of "remove the ids from all candidates, then cut to how_many" (srn_predict_batch_excl).  max_excl: the capacity of one list (default: the
+    longest list given); how_many + max_excl (+ the longest session - 1 with exclude_session) may not exceed SRN_MAX_HOW_MANY."""
     flat, off = _flatten(sessions)
     nq = len(off) - 1
+    if exclude is not None or exclude_session:
+        if out is not None:
+            raise ValueError("out is not supported together with exclude / exclude_session")
+        xf, xo, longest = _flatten_exclude(exclude, nq) if exclude is not None else (None, None, 0)
+        cap = longest if max_excl is None else int(max_excl)
+        ids, sc, cnt = np.zeros((nq, how_many), np.uint64), np.zeros((nq, how_many)), np.zeros(nq, np.uint32)
+        capi.check(capi.lib().srn_predict_batch_excl(index._h, capi.ptr(flat), capi.ptr(off), nq, capi.ptr(xf) if cap else None, capi.ptr(xo) if cap else None, cap,
+                                                     int(k), int(m), int(how_many),
+                                                     (capi.FLAG_BUSINESS_LOGIC if enable_business_logic else 0) | (capi.FLAG_EXCLUDE_SESSION if exclude_session else 0),
+                                                     capi.ptr(ids), capi.ptr(sc), capi.ptr(cnt)))
+        return ids, sc, cnt
     if out is not None:
         ids, sc, cnt = out
         if ids.shape != (nq, how_many) or sc.shape != (nq, how_many) or cnt.shape != (nq,) or ids.dtype != np.uint64 or sc.dtype != np.float64 or cnt.dtype != np.uint32 \
@@ -350,3 +378,15 @@ def predict_batch_device(index, d_items_flat, d_q_off, nq, max_len, k, m, how_ma
                                                    (capi.FLAG_BUSINESS_LOGIC if enable_business_logic else 0) | (capi.FLAG_INPUTS_RESIDENT if resident else 0),
                                                    C.c_void_p(d_out_ids), C.c_void_p(d_out_scores),
                                                    C.c_void_p(d_out_counts), C.c_void_p(stream)))
+
+
+def predict_batch_device_excl(index, d_items_flat, d_q_off, nq, max_len, d_excl_flat, d_excl_off, max_excl, k, m, how_many, enable_business_logic,
+                              d_out_ids, d_out_scores, d_out_counts, stream=0, resident=False, exclude_session=False):
+    """predict_batch_device with exclusion lists (srn_predict_batch_device_excl): d_excl_flat / d_excl_off are the device addresses of a CSR of u64 ids and nq + 1 u32
+    offsets (0 with max_excl = 0), max_excl the capacity of one list -- a query with a longer list gets the count 0xFFFFFFFF; exclude_session (SRN_FLAG_EXCLUDE_SESSION):
+    the items of the query's own session are excluded too.  Asynchronous on `stream`."""
+    capi.check(capi.lib().srn_predict_batch_device_excl(index._h, C.c_void_p(d_items_flat), C.c_void_p(d_q_off), int(nq), int(max_len),
+                                                        C.c_void_p(d_excl_flat or None), C.c_void_p(d_excl_off or None), int(max_excl), int(k), int(m), int(how_many),
+                                                        (capi.FLAG_BUSINESS_LOGIC if enable_business_logic else 0) | (capi.FLAG_INPUTS_RESIDENT if resident else 0)
+                                                        | (capi.FLAG_EXCLUDE_SESSION if exclude_session else 0),
+                                                        C.c_void_p(d_out_ids), C.c_void_p(d_out_scores), C.c_void_p(d_out_counts), C.c_void_p(stream)))
