@@ -287,6 +287,39 @@ int srn_predict_batch_device_excl(const srn_index_t* idx, const uint64_t* d_item
 int srn_predict_batch_excl(const srn_index_t* idx, const uint64_t* items_flat, const uint32_t* q_off, size_t nq, const uint64_t* excl_flat, const uint32_t* excl_off, size_t max_excl,
                            size_t k, size_t m, size_t how_many, unsigned flags, uint64_t* out_ids, double* out_scores, uint32_t* out_counts);
 
+/* ---- short rows filled from a fallback ranking -------------------------------------------------------------------------------------------
+ * A row is short (count < how_many) whenever the neighbours do not yield enough candidates, and empty whenever the clicked item is unknown to the index -- every product
+ * listed since the index was built.  An index may carry a FALLBACK RANKING: up to SRN_MAX_FALLBACK distinct public item ids, best first; ids the index does not know are
+ * allowed (a list of new products is a legitimate ranking).  With SRN_FLAG_FILL a batch call appends, on the device, on the caller's stream and in place, to every row of
+ * c < how_many entries the first how_many - c entries f of the ranking, in ranking order, that
+ *   - are none of the row's c ids and not the session's most recent item r,
+ *   - are in nothing the call removes from the model's candidates: the query's exclusion list, with SRN_FLAG_EXCLUDE_SESSION every item of the session, with
+ *     SRN_FLAG_EXCLUDE_SEEN the request's window,
+ *   - and, with SRN_FLAG_BUSINESS_LOGIC, pass passes_business_rules(attr(r), attr(f)) (mod.rs:162-182): f needs attributes (an id unknown to the index is dropped) and must
+ *     be for sale; an adult f passes only when r has attributes and is adult.  The attributes are read at call time: a later srn_index_set_attributes is honoured.
+ * The c model entries are untouched; filled entries carry the score -infinity (model scores are finite, but zero and negative ones exist: no finite value can say "no model
+ * score", and -inf keeps the row score-descending); out_counts[q] = c + filled.  A row with c >= how_many is not touched, a count of 0xFFFFFFFF stays, and where the
+ * ranking runs out the row stays short.  Without the flag every call enqueues the same kernels and writes the same bytes as before, ranking or not.
+ * SRN_FLAG_FILL is accepted by srn_predict_batch_device_excl, srn_predict_batch_excl, srn_recommend_batch_device, srn_recommend_batch and srn_eval_trial_t.flags; with the
+ * flag and no ranking they fail with SRN_ESTATE before anything is enqueued.  srn_predict_batch_device_excl with max_excl = 0, no SRN_FLAG_EXCLUDE_SESSION and
+ * SRN_FLAG_FILL is srn_predict_batch_device plus the fill kernel on the caller's buffers: no scratch.  Merged rows and the result cache's rows stay the unfilled ones (the
+ * fill runs per query behind them, like the exclusion filter); the cache's parameters and statistics are unaffected, and a new ranking does not clear it.
+ *   srn_index_set_fallback          replaces an earlier ranking.  n == 0 or an id that occurs twice: SRN_EINVAL; n > SRN_MAX_FALLBACK: SRN_ERANGE.
+ *   srn_index_set_fallback_popular  the first min(n, n_items) items of the index's popularity order: count of kept sessions that hold the item descending, id ascending.
+ *   srn_index_fallback              *out_n = the ranking's length (0: none); up to cap ids into out (may be NULL).
+ *   srn_index_clear_fallback        no ranking (SRN_OK without one).
+ * Item shards and postings-only views are refused, as for predict.  Setting a ranking allocates device memory and waits for the device: set it before serving.  The
+ * concurrency rule is that of srn_index_set_attributes, which overwrites the item records with a blocking copy that no stream orders against a kernel in flight: the
+ * caller makes sure that NO call on the index is running or enqueued-and-unfinished while the ranking (or the attributes) change -- a call that overlaps one may see the
+ * old entries, the new ones, or some of each.  srn_index_free releases the ranking; srn_index_save / srn_index_load do not carry it (the file format is unchanged): set
+ * it again after a load. */
+#define SRN_FLAG_FILL 16u
+#define SRN_MAX_FALLBACK 4096
+int srn_index_set_fallback(srn_index_t* idx, const uint64_t* item_ids, size_t n);
+int srn_index_set_fallback_popular(srn_index_t* idx, size_t n);
+int srn_index_fallback(const srn_index_t* idx, uint64_t* out, size_t cap, size_t* out_n);
+int srn_index_clear_fallback(srn_index_t* idx);
+
 /* Debug / measurement variant of srn_predict_batch (host pointers; any of the three extra outputs
  * may be NULL):
  *   out_stats  [nq * 8]  P, C, K, I, D, H, L, status per query -- the per-query terms of the
@@ -564,7 +597,7 @@ int srn_device_sessions_load(const char* path, int device, size_t capacity, size
 int srn_device_sessions_file_info(const char* path, srn_device_sessions_file_info_t* out);
 /* srn_session_key for n strings: string i = ids_flat[off[i] .. off[i + 1]) */
 int srn_session_keys(const char* ids_flat, const uint64_t* off, size_t n, uint64_t* key_hi, uint64_t* key_lo);
-/* flags: SRN_FLAG_BUSINESS_LOGIC, and SRN_FLAG_EXCLUDE_SEEN -- a request's recommendations leave out what its visitor has seen: the request's window as the request
+/* flags: SRN_FLAG_BUSINESS_LOGIC, SRN_FLAG_FILL (short rows filled from the index's fallback ranking, above), and SRN_FLAG_EXCLUDE_SEEN -- a request's recommendations leave out what its visitor has seen: the request's window as the request
  * sees it (the store's history window, or the session window on a store without one), the earlier requests of its key in the batch included; without consent nothing beyond
  * the item itself.  The windows are the exclusion lists of srn_predict_batch_device_excl, their capacity the store's max_stored_len bound (srn_device_sessions_stats):
  * the launch sequence runs at the internal how_many + max_stored_len (above SRN_MAX_HOW_MANY: SRN_ERANGE, before anything changes), which is also what a result cache must
@@ -597,7 +630,7 @@ typedef struct {
     uint32_t k, m, how_many;          /* predict's arguments (m <= the index's m_index is the normal case: one index answers every smaller m) */
     uint32_t max_items_in_session;    /* the window: a prefix is its last max_items_in_session items (evaluator.rs:50-55); 1..SRN_MAX_SESSION_LEN */
     uint32_t length;                  /* @N of the metrics (1..SRN_MAX_HOW_MANY); independent of how_many (hyperparameter_search.rs asks for 21, scores @20) */
-    uint32_t flags;                   /* SRN_FLAG_BUSINESS_LOGIC */
+    uint32_t flags;                   /* SRN_FLAG_BUSINESS_LOGIC, SRN_FLAG_FILL (the filled rows are scored; SRN_ESTATE without a ranking) */
     uint32_t max_chunk_queries;       /* queries per device round (0 = default); rounded down to a multiple of 256.  Results do not depend on it */
     uint32_t reserved;                /* 0 */
 } srn_eval_trial_t;

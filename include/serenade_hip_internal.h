@@ -58,6 +58,12 @@ int srn_debug_exclude_filter(const srn_index_t* idx, size_t nq, const uint64_t* 
                              const uint32_t* d_excl_off, size_t max_excl, const uint64_t* d_items_flat, const uint32_t* d_q_off, size_t how_many, uint64_t* d_out_ids, double* d_out_scores,
                              uint32_t* d_out_counts, void* stream);
 
+/* Measurement aid (tools/fill_bench.py): the fill kernel of SRN_FLAG_FILL ALONE, in place over rows the caller holds -- d_ids / d_scores
+ * [nq * how_many], d_counts [nq]; the sessions' CSR is needed (the most recent item), the exclusion CSR may be NULL.  flags: SRN_FLAG_BUSINESS_LOGIC,
+ * SRN_FLAG_EXCLUDE_SESSION.  SRN_ESTATE without a ranking.  Enqueued on `stream`. */
+int srn_debug_fill(const srn_index_t* idx, size_t nq, uint64_t* d_ids, double* d_scores, uint32_t* d_counts, size_t how_many, const uint64_t* d_excl_flat, const uint32_t* d_excl_off,
+                   const uint64_t* d_items_flat, const uint32_t* d_q_off, unsigned flags, void* stream);
+
 /* Test / experiment knobs (environment variables SRN_NO_FAST, SRN_NO_MID, SRN_NO_MASKS, SRN_NO_MERGE, SRN_HOT_SLOTS,
  * SRN_SKETCH_SLOTS, SRN_LDS_BUDGET_KB, SRN_GRID_MULT, SRN_DEBUG) force individual kernel code paths.  They are read ONCE,
  * when the library is first used -- never on the launch path; this call re-reads them (the parity tests switch paths

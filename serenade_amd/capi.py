@@ -52,6 +52,8 @@ SHARD_GROUP_ID_BYTES = 256
 FLAG_INPUTS_RESIDENT = 2
 FLAG_EXCLUDE_SESSION = 4
 FLAG_EXCLUDE_SEEN = 8
+FLAG_FILL = 16
+MAX_FALLBACK = 4096
 
 
 class EvalTrial(C.Structure):
@@ -108,6 +110,10 @@ SYMBOLS = {
     "srn_index_save": (_i, [_vp, C.c_char_p]),
     "srn_index_load": (_i, [C.c_char_p, _i, C.POINTER(_vp)]),
     "srn_index_set_attributes": (_i, [_vp, _vp, _vp, _sz]),
+    "srn_index_set_fallback": (_i, [_vp, _vp, _sz]),
+    "srn_index_set_fallback_popular": (_i, [_vp, _sz]),
+    "srn_index_fallback": (_i, [_vp, _vp, _sz, C.POINTER(_sz)]),
+    "srn_index_clear_fallback": (_i, [_vp]),
     "srn_index_info": (_i, [_vp, C.POINTER(IndexInfo)]),
     "srn_index_postings": (_i, [_vp, _u64, _vp, _sz, C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
     "srn_index_items_for_session": (_i, [_vp, C.c_uint32, _vp, _sz, C.POINTER(_sz)]),
@@ -141,6 +147,7 @@ SYMBOLS = {
     "srn_predict_batch_device_excl": (_i, [_vp, _vp, _vp, _sz, _sz, _vp, _vp, _sz, _sz, _sz, _sz, C.c_uint, _vp, _vp, _vp, _vp]),
     "srn_predict_batch_excl": (_i, [_vp, _vp, _vp, _sz, _vp, _vp, _sz, _sz, _sz, _sz, C.c_uint, _vp, _vp, _vp]),
     "srn_debug_exclude_filter": (_i, [_vp, _sz, _vp, _vp, _vp, _sz, _vp, _vp, _sz, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
+    "srn_debug_fill": (_i, [_vp, _sz, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, C.c_uint, _vp]),
     "srn_predict_batch_debug": (_i, [_vp, _vp, _vp, _sz, _sz, _sz, _sz, C.c_uint, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "srn_index_reserve": (_i, [_vp, _sz, _sz, _sz, _sz, _sz, C.c_uint, _vp]),
     "srn_last_kernel_ms": (_i, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint32)]),

@@ -215,6 +215,45 @@ int srn_index_set_attributes(srn_index_t* idx, const uint64_t* item_ids, const u
         if (rc == SRN_OK) (void)device_result_cache_clear_if_enabled(idx->dev);   // (rows under the business rules depend on the flags)
         return rc; });
 }
+// ---- the fallback ranking (srn_fill.hip) ----
+static int check_fallback_index(const srn_index_t* idx) {
+    if (!idx) return fail(SRN_EINVAL, "null index");
+    if (idx->flat.postings_only) return fail(SRN_EINVAL, "a postings-only view serves a shard group, not predict calls: it takes no fallback ranking");
+    return check_not_a_shard(idx);
+}
+int srn_index_set_fallback(srn_index_t* idx, const uint64_t* item_ids, size_t n) {
+    return guarded([&]() -> int {
+        int rc = check_fallback_index(idx); if (rc) return rc;
+        if (n == 0 || !item_ids) return fail(SRN_EINVAL, "srn_index_set_fallback: an empty ranking (srn_index_clear_fallback removes one)");
+        if (n > SRN_MAX_FALLBACK) return fail(SRN_ERANGE, "srn_index_set_fallback: more than SRN_MAX_FALLBACK ids");
+        std::vector<uint64_t> sorted(item_ids, item_ids + n);
+        std::sort(sorted.begin(), sorted.end());
+        if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return fail(SRN_EINVAL, "srn_index_set_fallback: an id occurs twice");
+        if (idx->dev) { rc = device_set_fallback(idx->dev, idx->flat, item_ids, (uint32_t)n); if (rc) { idx->fallback.clear(); return rc; } }
+        idx->fallback.assign(item_ids, item_ids + n);
+        return SRN_OK; });
+}
+int srn_index_set_fallback_popular(srn_index_t* idx, size_t n) {
+    return guarded([&]() -> int {
+        int rc = check_fallback_index(idx); if (rc) return rc;
+        const size_t take = std::min<size_t>(n, idx->flat.n_items);   // (the dense item index IS the popularity order: count of kept sessions descending, id ascending)
+        if (take == 0) return fail(SRN_EINVAL, "srn_index_set_fallback_popular: an empty ranking");
+        if (take > SRN_MAX_FALLBACK) return fail(SRN_ERANGE, "srn_index_set_fallback_popular: more than SRN_MAX_FALLBACK ids");
+        const std::vector<uint64_t> ids(idx->flat.item_id.begin(), idx->flat.item_id.begin() + take);
+        return srn_index_set_fallback(idx, ids.data(), take); });
+}
+int srn_index_fallback(const srn_index_t* idx, uint64_t* out, size_t cap, size_t* out_n) {
+    if (!idx || !out_n) return fail(SRN_EINVAL, "null argument");
+    *out_n = idx->fallback.size();
+    if (out) std::copy(idx->fallback.begin(), idx->fallback.begin() + std::min(cap, idx->fallback.size()), out);
+    return SRN_OK;
+}
+int srn_index_clear_fallback(srn_index_t* idx) {
+    if (!idx) return fail(SRN_EINVAL, "null index");
+    device_clear_fallback(idx->dev);
+    idx->fallback.clear();
+    return SRN_OK;
+}
 int srn_index_info(const srn_index_t* idx, srn_index_info_t* out) {
     if (!idx || !out) return fail(SRN_EINVAL, "null argument");
     const FlatIndex& f = idx->flat;
@@ -427,19 +466,24 @@ int srn_predict_batch_device(const srn_index_t* idx, const uint64_t* d_items_fla
                               nullptr, nullptr); });
 }
 
+// SRN_FLAG_FILL without a ranking: refused before anything is enqueued
+static int check_has_fallback(const srn_index_t* idx) {
+    return device_has_fallback(idx->dev) ? SRN_OK : fail(SRN_ESTATE, "SRN_FLAG_FILL: the index has no fallback ranking (srn_index_set_fallback)");
+}
 // ---- exclusion lists (srn_exclude.hip) ----
 // the checks both forms share; *wide = the internal how_many
 static int check_excl_args(const srn_index_t* idx, size_t nq, size_t max_len_hint, const void* excl_flat, const void* excl_off, size_t max_excl, size_t k, size_t m, size_t how_many,
                            unsigned flags, size_t* wide) {
     int rc = check_predict_args(idx, k, m, how_many); if (rc) return rc;
     rc = check_not_a_shard(idx); if (rc) return rc;
-    if (flags & ~(unsigned)(SRN_FLAG_BUSINESS_LOGIC | SRN_FLAG_INPUTS_RESIDENT | SRN_FLAG_EXCLUDE_SESSION)) return fail(SRN_EINVAL, "srn_predict_batch_excl: unknown flags");
+    if (flags & ~(unsigned)(SRN_FLAG_BUSINESS_LOGIC | SRN_FLAG_INPUTS_RESIDENT | SRN_FLAG_EXCLUDE_SESSION | SRN_FLAG_FILL)) return fail(SRN_EINVAL, "srn_predict_batch_excl: unknown flags");
     if (nq > 0x7FFFFFFFull) return fail(SRN_ERANGE, "too many queries in one batch");
     if (max_len_hint == 0 || max_len_hint > SRN_MAX_SESSION_LEN) return fail(SRN_ERANGE, "max_len_hint out of range");
     if (max_excl > SRN_MAX_HOW_MANY) return fail(SRN_ERANGE, "how_many + max_excl above SRN_MAX_HOW_MANY");
     *wide = how_many + max_excl + ((flags & SRN_FLAG_EXCLUDE_SESSION) ? max_len_hint - 1 : 0);
     if (*wide > SRN_MAX_HOW_MANY) return fail(SRN_ERANGE, "how_many + max_excl (+ max_len_hint - 1 with SRN_FLAG_EXCLUDE_SESSION) above SRN_MAX_HOW_MANY");
     if (max_excl > 0 && (!excl_flat || !excl_off)) return fail(SRN_EINVAL, "null exclusion list with max_excl > 0");
+    if (flags & SRN_FLAG_FILL) return check_has_fallback(idx);
     return SRN_OK;
 }
 int srn_predict_batch_device_excl(const srn_index_t* idx, const uint64_t* d_items_flat, const uint32_t* d_q_off, size_t nq, size_t max_len_hint,
@@ -451,13 +495,14 @@ int srn_predict_batch_device_excl(const srn_index_t* idx, const uint64_t* d_item
         if (nq == 0) return SRN_OK;
         if (!d_items_flat || !d_q_off || !d_out_ids || !d_out_scores || !d_out_counts) return fail(SRN_EINVAL, "null buffer");
         LaunchParams p{};
-        p.nq = (uint32_t)nq; p.k = (uint32_t)k; p.m = (uint32_t)m; p.how_many = (uint32_t)wide; p.flags = flags & ~(unsigned)SRN_FLAG_EXCLUDE_SESSION; p.max_len = (uint32_t)max_len_hint;
+        const bool fill = (flags & SRN_FLAG_FILL) != 0u;   // (the launch sequence never sees the flag: device_fast_eligible sends any flag but the business rules to the general kernel)
+        p.nq = (uint32_t)nq; p.k = (uint32_t)k; p.m = (uint32_t)m; p.how_many = (uint32_t)wide; p.flags = flags & ~(unsigned)(SRN_FLAG_EXCLUDE_SESSION | SRN_FLAG_FILL); p.max_len = (uint32_t)max_len_hint;
         p.items_flat = d_items_flat; p.q_off = d_q_off; p.out_ids = d_out_ids; p.out_scores = d_out_scores; p.out_counts = d_out_counts;
-        if (wide == how_many)   // nothing can be excluded (one-item sessions at most, whose item is never in its row): the plain call -- no scratch, no extra kernel
-            return device_predict(idx->dev, idx->flat, p, true, stream, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+        if (wide == how_many)   // nothing can be excluded (one-item sessions at most, whose item is never in its row): the plain call -- no scratch, no extra kernel (SRN_FLAG_FILL: the fill kernel, in place on the caller's rows)
+            return device_predict(idx->dev, idx->flat, p, true, stream, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, false, false, nullptr, fill);
         const ExclSpec x{max_excl ? d_excl_flat : nullptr, max_excl ? d_excl_off : nullptr, (uint32_t)max_excl, (flags & SRN_FLAG_EXCLUDE_SESSION) != 0u, (uint32_t)how_many, d_out_ids, d_out_scores, d_out_counts};
         p.out_ids = nullptr; p.out_scores = nullptr; p.out_counts = nullptr;
-        return device_predict(idx->dev, idx->flat, p, true, stream, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, false, false, &x); });
+        return device_predict(idx->dev, idx->flat, p, true, stream, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, false, false, &x, fill); });
 }
 int srn_predict_batch_excl(const srn_index_t* idx, const uint64_t* items_flat, const uint32_t* q_off, size_t nq, const uint64_t* excl_flat, const uint32_t* excl_off, size_t max_excl,
                            size_t k, size_t m, size_t how_many, unsigned flags, uint64_t* out_ids, double* out_scores, uint32_t* out_counts) {
@@ -475,11 +520,16 @@ int srn_predict_batch_excl(const srn_index_t* idx, const uint64_t* items_flat, c
         size_t wide = 0;
         int rc = check_excl_args(idx, nq, max_len, excl_flat, excl_off, max_excl, k, m, how_many, flags & ~(unsigned)SRN_FLAG_INPUTS_RESIDENT, &wide); if (rc) return rc;
         if (max_excl) for (size_t q = 0; q < nq; ++q) if (excl_off[q + 1] < excl_off[q]) return fail(SRN_EINVAL, "excl_off not monotone");
-        if (wide == how_many) return predict_host(idx, items_flat, q_off, nq, k, m, how_many, flags & (unsigned)SRN_FLAG_BUSINESS_LOGIC, out_ids, out_scores, out_counts, nullptr, nullptr, nullptr, nullptr);   // nothing can be excluded: the plain call
+        const bool fill = (flags & SRN_FLAG_FILL) != 0u;   // (with the flag the rows always pass through the filter's buffers: the fill kernel works on device rows)
+        if (wide == how_many && !fill) return predict_host(idx, items_flat, q_off, nq, k, m, how_many, flags & (unsigned)SRN_FLAG_BUSINESS_LOGIC, out_ids, out_scores, out_counts, nullptr, nullptr, nullptr, nullptr);   // nothing can be excluded: the plain call
         LaunchParams p{};
         p.nq = (uint32_t)nq; p.k = (uint32_t)k; p.m = (uint32_t)m; p.how_many = (uint32_t)wide; p.flags = flags & (unsigned)SRN_FLAG_BUSINESS_LOGIC; p.max_len = max_len;
         const ExclSpec x{max_excl ? excl_flat : nullptr, max_excl ? excl_off : nullptr, (uint32_t)max_excl, (flags & SRN_FLAG_EXCLUDE_SESSION) != 0u, (uint32_t)how_many, nullptr, nullptr, nullptr};
-        return device_predict(idx->dev, idx->flat, p, false, nullptr, items_flat, q_off, out_ids, out_scores, out_counts, nullptr, nullptr, nullptr, nullptr, nullptr, false, false, &x); });
+        rc = device_predict(idx->dev, idx->flat, p, false, nullptr, items_flat, q_off, out_ids, out_scores, out_counts, nullptr, nullptr, nullptr, nullptr, nullptr, false, false, &x, fill);
+        if (rc) return rc;
+        if (wide == how_many)   // (the plain call's contract, which this one replaces under SRN_FLAG_FILL)
+            for (size_t q = 0; q < nq; ++q) if (out_counts[q] == 0xFFFFFFFFu) return fail(SRN_ERANGE, "a query exceeded the kernel's table limits");
+        return SRN_OK; });
 }
 
 int srn_debug_exclude_filter(const srn_index_t* idx, size_t nq, const uint64_t* d_wide_ids, const double* d_wide_scores, const uint32_t* d_wide_counts, size_t wide, const uint64_t* d_excl_flat,
@@ -492,6 +542,17 @@ int srn_debug_exclude_filter(const srn_index_t* idx, size_t nq, const uint64_t* 
         if (nq > 0x7FFFFFFFull || how_many == 0 || wide < how_many || wide > SRN_MAX_HOW_MANY || max_excl > SRN_MAX_HOW_MANY) return fail(SRN_ERANGE, "srn_debug_exclude_filter: sizes out of range");
         return device_exclude_filter(idx->dev, (uint32_t)nq, d_wide_ids, d_wide_scores, d_wide_counts, (uint32_t)wide, d_excl_flat, d_excl_off, (uint32_t)max_excl, d_items_flat, d_q_off,
                                      d_out_ids, d_out_scores, d_out_counts, (uint32_t)how_many, stream); });
+}
+
+int srn_debug_fill(const srn_index_t* idx, size_t nq, uint64_t* d_ids, double* d_scores, uint32_t* d_counts, size_t how_many, const uint64_t* d_excl_flat, const uint32_t* d_excl_off,
+                   const uint64_t* d_items_flat, const uint32_t* d_q_off, unsigned flags, void* stream) {
+    return guarded([&]() -> int {
+        if (!idx || !idx->dev) return fail(SRN_ENODEV, "index has no device attached");
+        if (!d_ids || !d_scores || !d_counts || !d_items_flat || !d_q_off || (d_excl_flat != nullptr) != (d_excl_off != nullptr)) return fail(SRN_EINVAL, "null buffer");
+        if (nq > 0x7FFFFFFFull || how_many == 0 || how_many > SRN_MAX_HOW_MANY) return fail(SRN_ERANGE, "srn_debug_fill: sizes out of range");
+        int rc = check_has_fallback(idx); if (rc) return rc;
+        return device_fill(idx->dev, (uint32_t)nq, d_ids, d_scores, d_counts, (uint32_t)how_many, d_excl_flat, d_excl_off, d_items_flat, d_q_off, (flags & SRN_FLAG_EXCLUDE_SESSION) != 0u,
+                           (flags & SRN_FLAG_BUSINESS_LOGIC) != 0u, stream); });
 }
 
 int srn_index_reserve(const srn_index_t* idx, size_t nq, size_t max_len_hint, size_t k, size_t m, size_t how_many, unsigned flags, void* stream) {
@@ -657,7 +718,8 @@ static int check_trials(const srn_eval_set_t* set, const srn_eval_trial_t* trial
         if (tr.m > 0x7FFFFFFFu) return fail(SRN_ERANGE, "m too large");
     }
     if (!set) return fail(SRN_EINVAL, "null evaluation set");
-    for (size_t t = 0; t < n_trials; ++t) { int rc = check_predict_args(set->idx, trials[t].k, trials[t].m, trials[t].how_many); if (rc) return rc; }
+    for (size_t t = 0; t < n_trials; ++t) { int rc = check_predict_args(set->idx, trials[t].k, trials[t].m, trials[t].how_many); if (rc) return rc;
+                                            if (trials[t].flags & SRN_FLAG_FILL) { rc = check_has_fallback(set->idx); if (rc) return rc; } }
     return SRN_OK;
 }
 
@@ -768,7 +830,8 @@ static int check_recommend_args(const srn_index_t* idx, size_t n, size_t k, size
     rc = check_not_a_shard(idx); if (rc) return rc;
     if (n == 0) { *done = true; return SRN_OK; }
     if (!buffers) return fail(SRN_EINVAL, "null buffer");
-    if (flags & ~(unsigned)(SRN_FLAG_BUSINESS_LOGIC | SRN_FLAG_EXCLUDE_SEEN)) return fail(SRN_EINVAL, "srn_recommend_batch: unknown flags");
+    if (flags & ~(unsigned)(SRN_FLAG_BUSINESS_LOGIC | SRN_FLAG_EXCLUDE_SEEN | SRN_FLAG_FILL)) return fail(SRN_EINVAL, "srn_recommend_batch: unknown flags");
+    if (flags & SRN_FLAG_FILL) return check_has_fallback(idx);   // (before the store changes)
     return SRN_OK;
 }
 int srn_recommend_batch_device(const srn_index_t* idx, srn_device_sessions_t* store, const uint64_t* d_key_hi, const uint64_t* d_key_lo, const uint64_t* d_item_ids,

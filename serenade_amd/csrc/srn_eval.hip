@@ -336,7 +336,8 @@ int eval_run(srn_eval_set* set, const srn_eval_trial_t* trials, size_t n_trials,
             LaunchParams p{};
             p.nq = nq; p.k = tr.k; p.m = tr.m; p.how_many = tr.how_many; p.flags = (tr.flags & SRN_FLAG_BUSINESS_LOGIC) | kFlagNoResultCache; p.max_len = max_len;   // (a grid of trials is no serving traffic: the index's result cache is bypassed)
             p.items_flat = d_items; p.q_off = d_qoff; p.out_ids = d_ids; p.out_scores = d_sc; p.out_counts = d_cnt;
-            if ((rc = device_predict(idx->dev, ix, p, true, st, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr))) return rc;
+            // (SRN_FLAG_FILL: the metric kernel scores the filled rows -- the fill kernel runs behind the launch sequence, inside the call)
+            if ((rc = device_predict(idx->dev, ix, p, true, st, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, false, false, nullptr, (tr.flags & SRN_FLAG_FILL) != 0u))) return rc;
             HIP_TRY(hipSetDevice(e->device));
             HIP_TRY(hipEventRecord(ev[2], st));
             MetricArgs a{};

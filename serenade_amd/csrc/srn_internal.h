@@ -146,10 +146,18 @@ int device_predict(DeviceState* d, const FlatIndex& ix, const LaunchParams& p, b
                    // host-pointer mode: these are host buffers copied in/out by the call
                    const uint64_t* h_items, const uint32_t* h_qoff, uint64_t* h_ids, double* h_scores,
                    uint32_t* h_counts, uint32_t* h_stats, uint32_t* h_nb_rank, uint32_t* h_nb_num, uint32_t* h_nb_cnt, const ExtLists* ext = nullptr,
-                   bool reserve_only = false, bool blocking_wait = false, const ExclSpec* excl = nullptr);   // reserve_only (srn_index_reserve): size the call's workspace, enqueue nothing; blocking_wait: the latency path sleeps on an interrupt instead of spinning
+                   bool reserve_only = false, bool blocking_wait = false, const ExclSpec* excl = nullptr, bool fill = false);   // reserve_only (srn_index_reserve): size the call's workspace, enqueue nothing; blocking_wait: the latency path sleeps on an interrupt instead of spinning
 // measurement aid (srn_debug_exclude_filter): the filter kernel alone over the caller's wide rows, enqueued on `stream`
 int device_exclude_filter(DeviceState* d, uint32_t nq, const uint64_t* w_ids, const double* w_scores, const uint32_t* w_counts, uint32_t wide, const uint64_t* x_flat, const uint32_t* x_off,
                           uint32_t max_excl, const uint64_t* items_flat, const uint32_t* q_off, uint64_t* out_ids, double* out_scores, uint32_t* out_counts, uint32_t how_many, void* stream);
+// The fallback ranking (srn_fill.hip).  device_predict's `fill` (SRN_FLAG_FILL, stripped from LaunchParams::flags by the caller): behind the launch sequence
+// and the exclusion filter, short rows of the call's final rows are filled in place from the ranking; buffers_on_device calls and host-pointer calls with an ExclSpec only
+bool device_has_fallback(const DeviceState* d);
+int device_set_fallback(DeviceState* d, const FlatIndex& ix, const uint64_t* item_ids, uint32_t n);   // replaces an earlier ranking; synchronises the device
+void device_clear_fallback(DeviceState* d);
+// measurement aid (srn_debug_fill): the fill kernel alone over the caller's rows, enqueued on `stream`
+int device_fill(DeviceState* d, uint32_t nq, uint64_t* ids, double* scores, uint32_t* counts, uint32_t how_many, const uint64_t* x_flat, const uint32_t* x_off,
+                const uint64_t* items_flat, const uint32_t* q_off, bool whole_session, bool business, void* stream);
 struct ShardIO {
     void* cand; uint32_t* cand_cnt;                                       // A out: [nq * m] packed slots, [nq]
     const void* gathered; const uint32_t* gathered_cnt; uint32_t n_shards;   // B in: [G][nq * gathered_stride], [G][nq]
@@ -230,6 +238,7 @@ struct srn_index {
     srn::DeviceState* dev = nullptr;
     int device = -1;
     srn::Combiner* comb = nullptr;   // created with the device state
+    std::vector<uint64_t> fallback;  // the fallback ranking as set (srn_index_set_fallback*; empty: none)
     // reference session index -> recency rank (kNone: not a kept session), built at the first srn_index_items_for_session call (the index is immutable: call_once)
     mutable std::vector<uint32_t> session_to_rank; mutable std::once_flag s2r_once;
 };

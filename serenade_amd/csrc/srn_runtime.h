@@ -135,6 +135,7 @@ struct DeviceState {
     Workspace* last_ws = nullptr;   // for srn_last_kernel_ms (single-threaded measurement use)
     std::vector<HostPipe*> free_pipes, all_pipes;   // chunked host-pointer batches (srn_hostpipe.hip), pooled like the workspaces
     unsigned long long* d_phase = nullptr; bool phase_on = false;   // debug per-phase cycle counters
+    uint64_t* fb_ids = nullptr; uint32_t* fb_idx = nullptr; std::atomic<uint32_t> fb_n{0};   // the fallback ranking (srn_fill.hip): public ids | dense indices (kNone: unknown id), fb_n entries (0: none set)
     std::shared_ptr<ResultCache> rcache;   // srn_index_result_cache_enable (under mu; a call holds its own reference)
     std::atomic<bool> timing{false};   // record the per-kernel events of every call (srn_kernel_timing; SRN_TIMING=1): each event costs ~6 us of idle stream
 };
@@ -178,5 +179,8 @@ int exclude_host_room(Workspace* w, hipStream_t st, uint32_t nq, ExclSpec& x);  
 int exclude_fetch_host(hipStream_t st, uint32_t nq, const ExclSpec& x, uint64_t* h_ids, double* h_scores, uint32_t* h_counts);
 hipError_t launch_exclude(hipStream_t st, uint32_t nq, const uint64_t* w_ids, const double* w_scores, const uint32_t* w_counts, uint32_t W, const uint64_t* x_flat, const uint32_t* x_off,
                           uint32_t max_excl, const uint64_t* items_flat, const uint32_t* q_off, uint64_t* out_ids, double* out_scores, uint32_t* out_counts, uint32_t how_many);
+// srn_fill.hip: the fill kernel over rows [nq][how_many] in place (x_flat may be null; whole_session: SRN_FLAG_EXCLUDE_SESSION)
+hipError_t launch_fill(hipStream_t st, const DeviceState* d, uint32_t nq, uint64_t* ids, double* scores, uint32_t* counts, uint32_t how_many, const uint64_t* x_flat, const uint32_t* x_off,
+                       const uint64_t* items_flat, const uint32_t* q_off, bool whole_session, bool business);
 
 }  // namespace srn

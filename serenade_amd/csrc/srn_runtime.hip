@@ -787,11 +787,13 @@ static int enqueue_batch(BatchCall& c, bool on_device) {
 
 int device_predict(DeviceState* d, const FlatIndex& ix, const LaunchParams& p_in, bool on_device, void* user_stream,
                    const uint64_t* h_items, const uint32_t* h_qoff, uint64_t* h_ids, double* h_scores, uint32_t* h_counts,
-                   uint32_t* h_stats, uint32_t* h_nb_rank, uint32_t* h_nb_num, uint32_t* h_nb_cnt, const ExtLists* ext, bool reserve_only, bool blocking_wait, const ExclSpec* excl) {
+                   uint32_t* h_stats, uint32_t* h_nb_rank, uint32_t* h_nb_num, uint32_t* h_nb_cnt, const ExtLists* ext, bool reserve_only, bool blocking_wait, const ExclSpec* excl, bool fill) {
     HIP_TRY(hipSetDevice(d->device));
     LaunchParams p = p_in;
     if (p.nq == 0) return SRN_OK;
     if (excl && (ext || h_stats || h_nb_rank)) return fail(SRN_EINVAL, "exclusion lists: batch calls on an unsharded index only");
+    if (fill && (ext || h_stats || h_nb_rank || reserve_only || (!on_device && !excl))) return fail(SRN_EINVAL, "SRN_FLAG_FILL: batch calls on an unsharded index only");
+    if (fill && !device_has_fallback(d)) return fail(SRN_ESTATE, "SRN_FLAG_FILL: the index has no fallback ranking (srn_index_set_fallback)");
     ExclSpec xs{}; if (excl) xs = *excl;
     // SRN_FLAG_INPUTS_RESIDENT (device-pointer calls): the query buffers are complete in device memory at call time, so the prep kernel of THIS call may run on a side
     // stream while the previous call's kernels still occupy the caller's stream (enqueue_front_resident); the kernels never see the flag
@@ -837,6 +839,10 @@ int device_predict(DeviceState* d, const FlatIndex& ix, const LaunchParams& p_in
     { int rc = enqueue_batch(c, on_device); if (rc) return rc; }
     if (excl) HIP_TRY(launch_exclude(st, p.nq, p.out_ids, p.out_scores, p.out_counts, p.how_many, xs.x_flat, xs.x_off, xs.max_excl, xs.session ? p.items_flat : nullptr, p.q_off,
                                      xs.out_ids, xs.out_scores, xs.out_counts, xs.how_many));
+    // the fallback ranking (srn_fill.hip): short rows of the call's final rows -- the filter's, or the launch sequence's own -- are filled in place; what the launch sequence
+    // merged or cached above are the unfilled rows
+    if (fill) HIP_TRY(excl ? launch_fill(st, d, p.nq, xs.out_ids, xs.out_scores, xs.out_counts, xs.how_many, xs.x_flat, xs.x_off, p.items_flat, p.q_off, xs.session, (p.flags & SRN_FLAG_BUSINESS_LOGIC) != 0u)
+                           : launch_fill(st, d, p.nq, p.out_ids, p.out_scores, p.out_counts, p.how_many, nullptr, nullptr, p.items_flat, p.q_off, false, (p.flags & SRN_FLAG_BUSINESS_LOGIC) != 0u));
     if (excl && !on_device) return exclude_fetch_host(st, p.nq, xs, h_ids, h_scores, h_counts);
     return on_device ? SRN_OK : fetch_host_outputs(c, h_ids, h_scores, h_counts, h_stats, h_nb_rank, h_nb_num, h_nb_cnt);
 }

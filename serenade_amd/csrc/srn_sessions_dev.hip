@@ -659,7 +659,7 @@ int dsess_last_csr(srn_device_sessions* s, const void** d_items, const void** d_
 }
 
 // a NULL store (no request consents): the sessions are the items themselves.  Not the serving path: it allocates and blocks.
-static int recommend_no_store(const srn_index* idx, const uint64_t* d_item, const uint8_t* d_consent, size_t n, LaunchParams p, hipStream_t st) {
+static int recommend_no_store(const srn_index* idx, const uint64_t* d_item, const uint8_t* d_consent, size_t n, LaunchParams p, hipStream_t st, bool fill) {
     if (!d_consent) return fail(SRN_EINVAL, "srn_recommend_batch: user consent needs a session store");
     HIP_TRY(hipSetDevice(idx->device));
     std::vector<uint8_t> c(n);
@@ -670,7 +670,7 @@ static int recommend_no_store(const srn_index* idx, const uint64_t* d_item, cons
     HIP_TRY(hipMalloc((void**)&q_off, (n + 1) * 4));
     sess_iota<<<grid_for(n + 1), kTPB, 0, st>>>((uint32_t)n, q_off);
     p.max_len = 1; p.items_flat = d_item; p.q_off = q_off;
-    int rc = hipGetLastError() == hipSuccess ? device_predict(idx->dev, idx->flat, p, true, st, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr)
+    int rc = hipGetLastError() == hipSuccess ? device_predict(idx->dev, idx->flat, p, true, st, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, false, false, nullptr, fill)
                                              : fail(SRN_EHIP, "sess_iota launch failed");
     (void)hipStreamSynchronize(st);
     (void)hipFree(q_off);
@@ -685,12 +685,12 @@ int dsess_recommend_device(const srn_index* idx, srn_device_sessions* s, const u
     if (n > kMaxBatch) return fail(SRN_ERANGE, "srn_recommend_batch: more than 2^24 requests in one call");
     hipStream_t st = (hipStream_t)stream;
     LaunchParams p{};
-    const bool excl_seen = (flags & SRN_FLAG_EXCLUDE_SEEN) != 0u;
-    p.nq = (uint32_t)n; p.k = (uint32_t)k; p.m = (uint32_t)m; p.how_many = (uint32_t)how_many; p.flags = flags & ~(unsigned)SRN_FLAG_EXCLUDE_SEEN;
+    const bool excl_seen = (flags & SRN_FLAG_EXCLUDE_SEEN) != 0u, fill = (flags & SRN_FLAG_FILL) != 0u;   // (SRN_FLAG_FILL: srn_fill.hip, behind the call's launch sequence and filter)
+    p.nq = (uint32_t)n; p.k = (uint32_t)k; p.m = (uint32_t)m; p.how_many = (uint32_t)how_many; p.flags = flags & ~(unsigned)(SRN_FLAG_EXCLUDE_SEEN | SRN_FLAG_FILL);
     p.out_ids = d_ids; p.out_scores = d_scores; p.out_counts = d_counts;
     if (!s) {   // (every session is its item, which is never in its own row: SRN_FLAG_EXCLUDE_SEEN has nothing to exclude)
         if (max_items > SRN_MAX_SESSION_LEN) return fail(SRN_ERANGE, "srn_recommend_batch: max_items_in_session above SRN_MAX_SESSION_LEN");
-        return recommend_no_store(idx, d_item, d_consent, n, p, st);
+        return recommend_no_store(idx, d_item, d_consent, n, p, st, fill);
     }
     if (max_items > s->items_cap) return fail(SRN_ERANGE, "srn_recommend_batch: max_items_in_session above the store's items_cap");
     if (s->device != idx->device) return fail(SRN_EINVAL, "srn_recommend_batch: the store and the index are on different devices");
@@ -762,9 +762,9 @@ int dsess_recommend_device(const srn_index* idx, srn_device_sessions* s, const u
     if (excl_seen) {   // the windows are the exclusion CSR, the bound of their lengths its capacity: the launch sequence runs at how_many + hint (srn_exclude.hip)
         const ExclSpec x{a.items_flat, a.q_off, hint, false, (uint32_t)how_many, d_ids, d_scores, d_counts};
         p.how_many = (uint32_t)how_many + hint; p.out_ids = nullptr; p.out_scores = nullptr; p.out_counts = nullptr;
-        rc = device_predict(idx->dev, idx->flat, p, true, st, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, false, false, &x);
+        rc = device_predict(idx->dev, idx->flat, p, true, st, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, false, false, &x, fill);
     } else
-        rc = device_predict(idx->dev, idx->flat, p, true, st, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+        rc = device_predict(idx->dev, idx->flat, p, true, st, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, false, false, nullptr, fill);
     (void)hipSetDevice(s->device);
     if (timed) (void)hipEventRecord(s->tev[2], st);
     s->last_timed = timed;

@@ -5,7 +5,7 @@ srn_eval_set_* / srn_evaluate.
     evaluate(es, [dict(k=50, m=500, max_items_in_session=2), ...])   # -> one report per trial
 
 A trial is a dict: k, m, max_items_in_session (the window), how_many (default 20), length (the metrics' @N, default 20),
-business_logic (default False), max_chunk_queries (default 0: the library's chunk size; results do not depend on it).
+business_logic (default False), fill (default False: with it short rows are filled from the index's fallback ranking before they are scored), max_chunk_queries (default 0: the library's chunk size; results do not depend on it).
 A report holds the evaluator's report line under its own names (qty_evaluations, Mrr@20, ..., F1score@20), the raw sums and the
 device milliseconds of predict and of the evaluation kernels.
 """
@@ -27,7 +27,7 @@ def _trial(t):
     out.how_many = int(t.get("how_many", 20))
     out.max_items_in_session = int(t["max_items_in_session"])
     out.length = int(t.get("length", 20))
-    out.flags = capi.FLAG_BUSINESS_LOGIC if t.get("business_logic", False) else 0
+    out.flags = (capi.FLAG_BUSINESS_LOGIC if t.get("business_logic", False) else 0) | (capi.FLAG_FILL if t.get("fill", False) else 0)
     out.max_chunk_queries = int(t.get("max_chunk_queries", 0))
     out.reserved = 0
     return out

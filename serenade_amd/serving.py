@@ -112,6 +112,44 @@ def filter_rows(ids, scores, counts, excl, how_many):
     return out_ids, out_sc, out_cnt
 
 
+def passes_business_rules(cur, reco):
+    """passes_business_rules of the reference (src/vmisknn/mod.rs:162-182) on attribute bytes (capi.ATTR_*; ATTR_NONE = no attributes)."""
+    if reco == capi.ATTR_NONE or not reco & capi.ATTR_FOR_SALE:
+        return False
+    return not reco & capi.ATTR_ADULT or (cur != capi.ATTR_NONE and bool(cur & capi.ATTR_ADULT))
+
+
+def fill_rows(ids, scores, counts, sessions, ranking, how_many, excl=None, exclude_session=False, attrs=None, business=False):
+    """NumPy mirror of the fill kernel (srn_fill.hip): rows [nq, how_many] with `counts` valid entries each, as a call without SRN_FLAG_FILL returns them
+    (filter_rows' output where the call excludes) -> the rows the same call returns with the flag.  A row of c < how_many entries keeps them and takes the first
+    how_many - c ids f of `ranking`, in its order, that are none of the row's c ids, not sessions[q][-1], not in excl[q] (the query's list; for recommend_batch with
+    exclude_seen the request's window), not in sessions[q] with exclude_session, and -- with business -- pass passes_business_rules(attr(sessions[q][-1]), attr(f)),
+    where attrs maps an item id to its attribute byte and an id it does not hold has none (capi.ATTR_NONE: every item the index does not know).  Filled entries score
+    -inf; counts = c + filled.  Rows with c >= how_many and counts of 0xFFFFFFFF are passed on unchanged.  It needs no GPU."""
+    ids, scores, counts = np.array(ids, np.uint64), np.array(scores, np.float64), np.array(counts, np.uint32)
+    nq = ids.shape[0]
+    if ids.shape != (nq, how_many) or scores.shape != ids.shape or counts.shape != (nq,) or len(sessions) != nq or (excl is not None and len(excl) != nq):
+        raise ValueError("rows must be [nq, how_many] with one count, one session and (if given) one list per row")
+    ranking = [int(f) for f in ranking]
+    attrs = attrs if attrs is not None else {}
+    for q in range(nq):
+        c = int(counts[q])
+        if c >= how_many:   # (0xFFFFFFFF included)
+            continue
+        s = [int(x) for x in sessions[q]]
+        gone = set(int(x) for x in ids[q, :c]) | {s[-1]} | (set(s) if exclude_session else set()) | (set(int(x) for x in excl[q]) if excl is not None else set())
+        cur = attrs.get(s[-1], capi.ATTR_NONE)
+        for f in ranking:
+            if c == how_many:
+                break
+            if f in gone or (business and not passes_business_rules(cur, attrs.get(f, capi.ATTR_NONE))):
+                continue
+            ids[q, c], scores[q, c] = f, -np.inf
+            c += 1
+        counts[q] = c
+    return ids, scores, counts
+
+
 def _is_torch(x):
     return type(x).__module__.split(".")[0] == "torch"
 
@@ -367,13 +405,14 @@ class DeviceSessionStore:
 
 
 def recommend_batch(index, store, keys, item_ids, consent=None, *, k, m, how_many, max_items_in_session=2, enable_business_logic=False, now=0,
-                    scores=False, exclude_seen=False):
+                    scores=False, exclude_seen=False, fill=False):
     """/v1/recommend for a batch: request i = (keys[i], item_ids[i], consent[i]); the result is what the requests served one after the other give.
     keys: (hi, lo) uint64 arrays / tensors, or a list of session-id strings.  -> (ids[n, how_many], counts[n]) and scores[n, how_many] with scores=True.
     NumPy arrays (or CPU tensors) in, NumPy arrays out; tensors on the index's GPU are read in place (on the current stream, without synchronising) and the
     outputs are tensors on it.  store may be None only if no request consents.
     exclude_seen (SRN_FLAG_EXCLUDE_SEEN): a request's rows leave out its visitor's window as the request sees it -- the store's history window, or the session window on a
-    store without one; without consent nothing beyond the item itself."""
+    store without one; without consent nothing beyond the item itself.
+    fill (SRN_FLAG_FILL): rows of fewer than how_many entries are filled from the index's fallback ranking (score -inf), leaving out what the request excludes."""
     n = len(item_ids)
     if isinstance(keys, list) and (not keys or isinstance(keys[0], (str, bytes))):
         if len(keys) != n:
@@ -383,7 +422,7 @@ def recommend_batch(index, store, keys, item_ids, consent=None, *, k, m, how_man
     arrs = [hi, lo, item_ids] + ([consent] if consent is not None else [])
     if any(len(a) != n for a in arrs):
         raise ValueError("keys, item_ids and consent differ in length")
-    flags = (capi.FLAG_BUSINESS_LOGIC if enable_business_logic else 0) | (capi.FLAG_EXCLUDE_SEEN if exclude_seen else 0)
+    flags = (capi.FLAG_BUSINESS_LOGIC if enable_business_logic else 0) | (capi.FLAG_EXCLUDE_SEEN if exclude_seen else 0) | (capi.FLAG_FILL if fill else 0)
     sh = store._h if store is not None else None
     on_gpu = [_is_torch(a) and a.device.type == "cuda" for a in arrs]
     if any(on_gpu):

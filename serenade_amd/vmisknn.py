@@ -105,6 +105,28 @@ class VMISIndex:
         ids, fl = capi.as_u64(item_ids), np.ascontiguousarray(flags, np.uint8)
         capi.check(capi.lib().srn_index_set_attributes(self._h, capi.ptr(ids), capi.ptr(fl), len(ids)))
 
+    # ---- the fallback ranking (srn_index_set_fallback*): what short rows are filled from with fill=True ----
+    def set_fallback(self, ids):
+        """Up to capi.MAX_FALLBACK distinct public item ids, best first (ids the index does not know are allowed); replaces an earlier ranking.  Waits for the device:
+        set it before serving, and with no call on the index in flight."""
+        a = capi.as_u64(ids)
+        capi.check(capi.lib().srn_index_set_fallback(self._h, capi.ptr(a), len(a)))
+
+    def set_fallback_popular(self, n):
+        """The first min(n, n_items) items of the index's popularity order (count of kept sessions that hold the item descending, id ascending)."""
+        capi.check(capi.lib().srn_index_set_fallback_popular(self._h, int(n)))
+
+    def fallback(self):
+        """The ranking as set: uint64[R] (R = 0: none)."""
+        n = C.c_size_t()
+        capi.check(capi.lib().srn_index_fallback(self._h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, np.uint64)
+        capi.check(capi.lib().srn_index_fallback(self._h, capi.ptr(out) if n.value else None, n.value, C.byref(n)))
+        return out
+
+    def clear_fallback(self):
+        capi.check(capi.lib().srn_index_clear_fallback(self._h))
+
     def postings(self, item_id):
         """(reference session indices most-recent-first, idf) of one item, or (None, None) if unknown."""
         n, idf = C.c_int64(), C.c_double()
@@ -312,24 +334,27 @@ def _flatten_exclude(exclude, nq):
     return xf, xo, int(np.diff(xo.astype(np.int64)).max()) if nq else 0
 
 
-def predict_batch(index, sessions, k, m, how_many, enable_business_logic=False, out=None, exclude=None, exclude_session=False, max_excl=None):
+def predict_batch(index, sessions, k, m, how_many, enable_business_logic=False, out=None, exclude=None, exclude_session=False, max_excl=None, fill=False):
     """Many evolving sessions in one call (list of sequences, or (items_flat, q_off)).
     -> (ids u64[nq, how_many], scores f64[nq, how_many], counts u32[nq]).  out = (ids, scores, counts) of an earlier call of the same
     shape: the result buffers are reused (what a serving / evaluator host does) instead of freshly allocated.
     exclude: per query a list of item ids that must not be recommended (a list of nq lists, or CSR(ids_flat, off)); exclude_session: neither may any item of the query's own
     session.  The rows are those of "remove the ids from all candidates, then cut to how_many" (srn_predict_batch_excl).  max_excl: the capacity of one list (default: the
-    longest list given); how_many + max_excl (+ the longest session - 1 with exclude_session) may not exceed SRN_MAX_HOW_MANY."""
+    longest list given); how_many + max_excl (+ the longest session - 1 with exclude_session) may not exceed SRN_MAX_HOW_MANY.
+    fill (SRN_FLAG_FILL): rows of fewer than how_many entries are filled from the index's fallback ranking (VMISIndex.set_fallback*), score -inf, leaving out what the call
+    excludes (serving.fill_rows is the rule in NumPy); it takes the same entry point as exclude."""
     flat, off = _flatten(sessions)
     nq = len(off) - 1
-    if exclude is not None or exclude_session:
+    if exclude is not None or exclude_session or fill:
         if out is not None:
-            raise ValueError("out is not supported together with exclude / exclude_session")
+            raise ValueError("out is not supported together with exclude / exclude_session / fill")
         xf, xo, longest = _flatten_exclude(exclude, nq) if exclude is not None else (None, None, 0)
         cap = longest if max_excl is None else int(max_excl)
         ids, sc, cnt = np.zeros((nq, how_many), np.uint64), np.zeros((nq, how_many)), np.zeros(nq, np.uint32)
         capi.check(capi.lib().srn_predict_batch_excl(index._h, capi.ptr(flat), capi.ptr(off), nq, capi.ptr(xf) if cap else None, capi.ptr(xo) if cap else None, cap,
                                                      int(k), int(m), int(how_many),
-                                                     (capi.FLAG_BUSINESS_LOGIC if enable_business_logic else 0) | (capi.FLAG_EXCLUDE_SESSION if exclude_session else 0),
+                                                     (capi.FLAG_BUSINESS_LOGIC if enable_business_logic else 0) | (capi.FLAG_EXCLUDE_SESSION if exclude_session else 0)
+                                                     | (capi.FLAG_FILL if fill else 0),
                                                      capi.ptr(ids), capi.ptr(sc), capi.ptr(cnt)))
         return ids, sc, cnt
     if out is not None:
@@ -381,12 +406,12 @@ def predict_batch_device(index, d_items_flat, d_q_off, nq, max_len, k, m, how_ma
 
 
 def predict_batch_device_excl(index, d_items_flat, d_q_off, nq, max_len, d_excl_flat, d_excl_off, max_excl, k, m, how_many, enable_business_logic,
-                              d_out_ids, d_out_scores, d_out_counts, stream=0, resident=False, exclude_session=False):
+                              d_out_ids, d_out_scores, d_out_counts, stream=0, resident=False, exclude_session=False, fill=False):
     """predict_batch_device with exclusion lists (srn_predict_batch_device_excl): d_excl_flat / d_excl_off are the device addresses of a CSR of u64 ids and nq + 1 u32
     offsets (0 with max_excl = 0), max_excl the capacity of one list -- a query with a longer list gets the count 0xFFFFFFFF; exclude_session (SRN_FLAG_EXCLUDE_SESSION):
-    the items of the query's own session are excluded too.  Asynchronous on `stream`."""
+    the items of the query's own session are excluded too; fill (SRN_FLAG_FILL): short rows are filled in place from the index's fallback ranking.  Asynchronous on `stream`."""
     capi.check(capi.lib().srn_predict_batch_device_excl(index._h, C.c_void_p(d_items_flat), C.c_void_p(d_q_off), int(nq), int(max_len),
                                                         C.c_void_p(d_excl_flat or None), C.c_void_p(d_excl_off or None), int(max_excl), int(k), int(m), int(how_many),
                                                         (capi.FLAG_BUSINESS_LOGIC if enable_business_logic else 0) | (capi.FLAG_INPUTS_RESIDENT if resident else 0)
-                                                        | (capi.FLAG_EXCLUDE_SESSION if exclude_session else 0),
+                                                        | (capi.FLAG_EXCLUDE_SESSION if exclude_session else 0) | (capi.FLAG_FILL if fill else 0),
                                                         C.c_void_p(d_out_ids), C.c_void_p(d_out_scores), C.c_void_p(d_out_counts), C.c_void_p(stream)))
