@@ -64,6 +64,11 @@ int srn_debug_exclude_filter(const srn_index_t* idx, size_t nq, const uint64_t* 
 int srn_debug_fill(const srn_index_t* idx, size_t nq, uint64_t* d_ids, double* d_scores, uint32_t* d_counts, size_t how_many, const uint64_t* d_excl_flat, const uint32_t* d_excl_off,
                    const uint64_t* d_items_flat, const uint32_t* d_q_off, unsigned flags, void* stream);
 
+/* Test aid (tests/test_gpu_class_counts.py): the k-cut's wave-wide class counts alone.  acc [n_waves * 64]: per lane sixteen 4-bit fields, field c = the lane's count of
+ * class c (<= 15); out16 [n_waves * 16]: per wave the sum over its 64 lanes of every field, as the predict kernels compute it on the matrix unit.
+ * HOST pointers; blocks until the result is back. */
+int srn_debug_class_counts(const uint64_t* acc, size_t n_waves, uint32_t* out16, int device);
+
 /* Test / experiment knobs (environment variables SRN_NO_FAST, SRN_NO_MID, SRN_NO_MASKS, SRN_NO_MERGE, SRN_HOT_SLOTS,
  * SRN_SKETCH_SLOTS, SRN_LDS_BUDGET_KB, SRN_GRID_MULT, SRN_DEBUG) force individual kernel code paths.  They are read ONCE,
  * when the library is first used -- never on the launch path; this call re-reads them (the parity tests switch paths

@@ -49,6 +49,31 @@ __device__ __forceinline__ uint32_t wave_max(uint32_t v) {   // (uniform result)
     v = max(v, SRN_DPP(v, 0x143, 0xc, false));
     return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
 }
+// The k-cut's class counts on the matrix unit, which is otherwise idle in the predict kernels.  acc = sixteen 4-bit counts per lane (field c = class c, each <= 15);
+// returns, in EVERY lane l, the sum over the wave's 64 lanes of field l & 15.  All 64 lanes must be active: call it from block-uniform code only.
+// Three v_mfma_i32_16x16x32_i8 (operand k index of lane (g, i), byte t: 8 g + t; a result column's 16 rows live in the four lanes with equal lane & 15):
+//   stage 1, two MFMAs into one accumulator: A = the lane's counts as bytes (even classes in bytes 0..3, odd ones in 4..7; low word, then high word of acc),
+//            B = a 0/1 selector, byte t of lane (g, j) = 1 iff byte t of A carries class j -> D[i][j] = class j summed over lanes {i, 16 + i, 32 + i, 48 + i}, <= 60;
+//   stage 2: B = the four result registers as bytes 0..3 (4..7 = 0), A = all ones -> every row of column j = the wave's total of class j.
+// Which row sits in which register does not matter.  The DPP form this replaces (8 wave_sum + a select chain) was 96 VALU instructions, 48 of them dependent DPP adds.
+typedef int srn_v4i __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ uint32_t wave_class_counts(unsigned long long acc, uint32_t lane) {
+    uint32_t lq = lane; asm volatile("" : "+v"(lq));   // (opaque: the selectors depend on the lane alone and would be hoisted out of the query loop and spilled)
+    const uint32_t j = lq & 15u, one = 1u << (8u * ((j >> 1) & 3u));
+    const uint32_t s_even = (j & 1u) ? 0u : one, s_odd = (j & 1u) ? one : 0u;
+    const unsigned long long sel = ((unsigned long long)s_odd << 32) | s_even;
+    const unsigned long long b0 = j < 8u ? sel : 0ull, b1 = j < 8u ? 0ull : sel;
+    const uint32_t lo = (uint32_t)acc, hi = (uint32_t)(acc >> 32);
+    const unsigned long long a0 = ((unsigned long long)((lo >> 4) & 0x0F0F0F0Fu) << 32) | (lo & 0x0F0F0F0Fu);
+    const unsigned long long a1 = ((unsigned long long)((hi >> 4) & 0x0F0F0F0Fu) << 32) | (hi & 0x0F0F0F0Fu);
+    srn_v4i d = {0, 0, 0, 0};
+    d = __builtin_amdgcn_mfma_i32_16x16x32_i8((long)a0, (long)b0, d, 0, 0, 0);
+    d = __builtin_amdgcn_mfma_i32_16x16x32_i8((long)a1, (long)b1, d, 0, 0, 0);
+    const uint32_t part = (uint32_t)d.x | ((uint32_t)d.y << 8) | ((uint32_t)d.z << 16) | ((uint32_t)d.w << 24);
+    const srn_v4i zero = {0, 0, 0, 0};
+    const srn_v4i t = __builtin_amdgcn_mfma_i32_16x16x32_i8((long)0x0101010101010101ll, (long)(unsigned long long)part, zero, 0, 0, 0);
+    return (uint32_t)t.x;
+}
 // one LDS atomic per wave: returns this lane's slot in a shared append buffer (only meaningful if pred)
 __device__ __forceinline__ uint32_t wave_append(bool pred, uint32_t* counter) {
     const unsigned long long mask = __ballot(pred);

@@ -256,7 +256,7 @@ __device__ __forceinline__ void merge_pair(const uint32_t* in, uint32_t* out, ui
 // a compacted list D with LDS atomics, then a k-cut pass that read D back).  F = n packed slots (rank << NB | list bit), descending: the <= 4 copies of a session
 // are adjacent.  A thread takes g = ceil(n / 512) <= G consecutive entries plus three beyond them into registers, ORs every group onto its first copy (backwards carry),
 // flags the firsts; block scan #1 -> index among the distinct sessions (the m most recent are kept).  No more than k of them: they ARE the neighbours, written in place.
-// Otherwise the k-cut on the registers: numerator classes (<= 15) counted in packed 4-bit fields + DPP sums, the boundary class n* and its share r*, block scan #2 over
+// Otherwise the k-cut on the registers: numerator classes (<= 15) counted in packed 4-bit fields and summed per wave on the matrix unit (wave_class_counts), the boundary class n* and its share r*, block scan #2 over
 // that class, one atomic per wave for the output slots.  Returns K; the caller's barrier publishes nbl.
 // -------------------------------------------------------------------------------------
 #ifndef SRN_FAST_FUSED_CUT
@@ -308,18 +308,9 @@ __device__ __forceinline__ uint32_t fast_cut(const uint32_t* F, uint32_t* nbl, u
         }
     }
     uint32_t* cls = misc + FS_CLS;
-    {   // class counts: 16 fields of 4 bits per thread, spread over 4 x 64 bits with 16-bit fields, 8 DPP wave sums
-        uint32_t tot[8];
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj) {
-            const unsigned long long t = (acc >> (4 * jj)) & 0x000F000F000F000Full;
-            tot[2 * jj] = wave_sum((uint32_t)t); tot[2 * jj + 1] = wave_sum((uint32_t)(t >> 32));
-        }
-        const uint32_t dw = (lane & 3u) * 2u + (lane >> 3);   // class = lane: word lane & 3, field lane >> 2
-        uint32_t pick = tot[0];
-#pragma unroll
-        for (int x = 1; x < 8; ++x) pick = dw == (uint32_t)x ? tot[x] : pick;
-        const uint32_t mycnt = lane < 16u ? (pick >> (16u * ((lane >> 2) & 1u))) & 0xFFFFu : 0u;
+    {   // class counts: 16 fields of 4 bits per thread (<= G each), summed over the wave on the matrix unit (block-uniform branch: all lanes active); lane c < 16 = class c
+        const uint32_t wc = wave_class_counts(acc, lane);
+        const uint32_t mycnt = lane < 16u ? wc : 0u;
         if (mycnt) atomicAdd(&cls[lane], mycnt);
     }
     __syncthreads();
@@ -864,21 +855,12 @@ __global__ __launch_bounds__(512, TINY ? SRN_TINY_WAVES : BIG ? 4 : SRN_FAST_WAV
 #pragma unroll
                 for (int x = 0; x < 5; ++x) if (o0 + x < o1) atomicAdd(&cls[nmv[x]], 1u);
             } else
-            {   // class counts: 16 fields of 4 bits per thread, spread over 4 x 64 bits with 16-bit fields, 8 DPP wave sums
+            {   // class counts: 16 fields of 4 bits per thread (<= 5 each), summed over the wave on the matrix unit (block-uniform branch: all lanes active); lane c < 16 = class c
                 unsigned long long acc = 0;
 #pragma unroll
                 for (int x = 0; x < 5; ++x) acc += o0 + x < o1 ? 1ull << (4u * nmv[x]) : 0ull;
-                uint32_t tot[8];
-#pragma unroll
-                for (int jj = 0; jj < 4; ++jj) {
-                    const unsigned long long t = (acc >> (4 * jj)) & 0x000F000F000F000Full;
-                    tot[2 * jj] = wave_sum((uint32_t)t); tot[2 * jj + 1] = wave_sum((uint32_t)(t >> 32));
-                }
-                const uint32_t dw = (lane & 3u) * 2u + (lane >> 3);   // class = lane: word lane & 3, field lane >> 2
-                uint32_t pick = tot[0];
-#pragma unroll
-                for (int x = 1; x < 8; ++x) pick = dw == (uint32_t)x ? tot[x] : pick;
-                const uint32_t mycnt = lane < 16u ? (pick >> (16u * ((lane >> 2) & 1u))) & 0xFFFFu : 0u;
+                const uint32_t wc = wave_class_counts(acc, lane);
+                const uint32_t mycnt = lane < 16u ? wc : 0u;
                 if (mycnt) atomicAdd(&cls[lane], mycnt);
             }
             __syncthreads();

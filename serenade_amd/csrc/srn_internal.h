@@ -158,6 +158,8 @@ void device_clear_fallback(DeviceState* d);
 // measurement aid (srn_debug_fill): the fill kernel alone over the caller's rows, enqueued on `stream`
 int device_fill(DeviceState* d, uint32_t nq, uint64_t* ids, double* scores, uint32_t* counts, uint32_t how_many, const uint64_t* x_flat, const uint32_t* x_off,
                 const uint64_t* items_flat, const uint32_t* q_off, bool whole_session, bool business, void* stream);
+// test aid (srn_debug_class_counts): the k-cut's wave-wide class counts (wave_class_counts, srn_device.h) alone; host pointers, acc [n_waves * 64], out16 [n_waves * 16]
+int device_debug_class_counts(const uint64_t* acc, size_t n_waves, uint32_t* out16, int device);
 struct ShardIO {
     void* cand; uint32_t* cand_cnt;                                       // A out: [nq * m] packed slots, [nq]
     const void* gathered; const uint32_t* gathered_cnt; uint32_t n_shards;   // B in: [G][nq * gathered_stride], [G][nq]

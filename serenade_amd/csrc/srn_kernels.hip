@@ -669,22 +669,13 @@ __global__ __launch_bounds__(BLOCK, 2 * BLOCK / 256) void vmis_predict_kernel(De
                 uint32_t* cls = wb + (wwords - 64);
                 if (sumw <= 15 && Cm <= 15 * BLOCK) {
                     // <= 16 classes, <= 15 candidates per thread: count in packed fields.  A thread adds 1 << 4 class into a 64-bit
-                    // word (16 fields of 4 bits), the word is spread over 4 x 64 bits with 16-bit fields (class c -> word c & 3, field
-                    // c >> 2; a wave's sum is <= 64 * 15 per field), 8 DPP wave sums, lane c picks its class.  ~100 VALU
-                    // instructions per wave where a compare + ballot per class and batch costs 4 * (sumw + 1) per batch.
+                    // word (16 fields of 4 bits); the wave's sum per field comes from the matrix unit (wave_class_counts: three MFMAs,
+                    // this branch is block-uniform so all lanes are active), lane c < 16 holds class c.  A compare + ballot per class
+                    // and batch costs 4 * (sumw + 1) VALU instructions per batch.
                     unsigned long long acc = 0;
                     for (uint32_t e = tid; e < Cm; e += BLOCK) acc += 1ull << (4u * num_of(D[e]));
-                    uint32_t tot[8];
-#pragma unroll
-                    for (int jj = 0; jj < 4; ++jj) {
-                        const unsigned long long t = (acc >> (4 * jj)) & 0x000F000F000F000Full;
-                        tot[2 * jj] = wave_sum((uint32_t)t); tot[2 * jj + 1] = wave_sum((uint32_t)(t >> 32));
-                    }
-                    const uint32_t dw = ((uint32_t)lane & 3u) * 2u + ((uint32_t)lane >> 3);   // class = lane: word lane & 3, field lane >> 2
-                    uint32_t pick = tot[0];
-#pragma unroll
-                    for (int x = 1; x < 8; ++x) pick = dw == (uint32_t)x ? tot[x] : pick;
-                    const uint32_t mycnt = lane < 16 ? (pick >> (16u * (((uint32_t)lane >> 2) & 1u))) & 0xFFFFu : 0u;
+                    const uint32_t wc = wave_class_counts(acc, (uint32_t)lane);
+                    const uint32_t mycnt = lane < 16 ? wc : 0u;
                     if (mycnt) atomicAdd(&cls[lane], mycnt);
                 } else {   // lane v counts class v (ballots), one scattered atomic per lane at the end: no same-address pile-up
                     uint32_t mycnt = 0;
@@ -1551,6 +1542,38 @@ hipError_t launch_rows_to_slots(hipStream_t st, const uint64_t* row_off, const u
                                 uint32_t* slots, uint32_t* ext) {
     hipLaunchKernelGGL(rows_to_slots_kernel, dim3((unsigned)((n_rows + 1 + 1023) / 1024)), dim3(1024), 0, st, row_off, row_items, n_rows, block_base, slots, ext);
     return hipGetLastError();
+}
+
+// test aid (srn_debug_class_counts): wave_class_counts alone, one acc word per thread, 512-thread workgroups; lanes 0..15 of wave w write out16[16 w ..].  The grid is
+// rounded up to whole workgroups and a wave beyond n_waves runs on acc = 0, so every wave has all 64 lanes active when it reaches the MFMAs
+__global__ __launch_bounds__(512) void class_counts_debug_kernel(const unsigned long long* __restrict__ acc, uint32_t n_waves, uint32_t* __restrict__ out16) {
+    const uint32_t gt = blockIdx.x * 512u + threadIdx.x, w = gt >> 6, lane = threadIdx.x & 63u;
+    const unsigned long long a = w < n_waves ? acc[gt] : 0ull;
+    const uint32_t c = wave_class_counts(a, lane);
+    if (w < n_waves && lane < 16u) out16[(size_t)w * 16u + lane] = c;
+}
+
+int device_debug_class_counts(const uint64_t* acc, size_t n_waves, uint32_t* out16, int device) {
+    if (!acc || !out16) return fail(SRN_EINVAL, "null buffer");
+    if (n_waves == 0) return SRN_OK;
+    if (n_waves > (1u << 20)) return fail(SRN_ERANGE, "srn_debug_class_counts: at most 2^20 waves");
+    int prev_device = 0;
+    HIP_TRY(hipGetDevice(&prev_device));
+    HIP_TRY(hipSetDevice(device));
+    struct Restore { int d; ~Restore() { (void)hipSetDevice(d); } } restore{prev_device};   // (the caller's current device is left as it was, on every return below)
+    void* mem = nullptr;
+    const size_t in_bytes = n_waves * 64 * 8, out_bytes = n_waves * 16 * 4;
+    if (hipMalloc(&mem, in_bytes + out_bytes) != hipSuccess) { (void)hipGetLastError(); return fail(SRN_ENOMEM, "srn_debug_class_counts: hipMalloc failed"); }
+    unsigned long long* d_acc = (unsigned long long*)mem; uint32_t* d_out = (uint32_t*)((char*)mem + in_bytes);
+    hipError_t e = hipMemcpy(d_acc, acc, in_bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(class_counts_debug_kernel, dim3((unsigned)((n_waves + 7) / 8)), dim3(512), 0, 0, d_acc, (uint32_t)n_waves, d_out);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpy(out16, d_out, out_bytes, hipMemcpyDeviceToHost);   // (the null stream: the copy waits for the kernel)
+    (void)hipFree(mem);
+    if (e != hipSuccess) return fail(SRN_EHIP, std::string("srn_debug_class_counts: ") + hipGetErrorString(e));
+    return SRN_OK;
 }
 
 }  // namespace srn
