@@ -595,6 +595,29 @@ typedef struct {
 int srn_device_sessions_save(srn_device_sessions_t* s, const char* path, uint64_t now_secs);
 int srn_device_sessions_load(const char* path, int device, size_t capacity, size_t items_cap, uint64_t ttl_secs, uint64_t idle_secs, srn_device_sessions_t** out);
 int srn_device_sessions_file_info(const char* path, srn_device_sessions_file_info_t* out);
+/* ---- trending items: what the live sessions hold, counted and ranked on the device (srn_trending.hip) ----
+ * The items the live sessions hold most often.  An entry is IN RANGE when it is live at now_secs (occupied and not older than ttl_secs: what a sweep at now_secs keeps;
+ * now_secs = 0 the system clock, 1 = everything, as for srn_device_sessions_export) and its epoch >= since_secs (0 = no lower bound).
+ * count(id) = the number of in-range entries whose stored window items[0 .. len) contains id AT LEAST once (a window A,B,A counts A once; positions >= len are never read,
+ * so the id 0 is an id like any other).  The ranking is count descending, id ascending; ids with count < min_count (0 is read as 1) are left out.
+ * Writes the first min(cap, ranked) ids and counts (either array may be NULL) and *out_n = ranked, the number of ids with count >= min_count -- the caller compares.
+ * Blocks; takes the store's mutex and is ordered behind the store's previous call like every other store call; changes nothing in the store.
+ * Counts are exact integers and the order is total: two calls on an unchanged store return the same bytes.
+ * NULL store or out_n: SRN_EINVAL; cap > 0 with both arrays NULL: SRN_EINVAL; an empty store or nothing in range: SRN_OK with *out_n = 0.
+ * Scratch is sized from the exact number T of (entry, distinct id) pairs in range, allocated for the call and released: 12 bytes per slot, then 20 T bytes + 4 bytes per
+ * distinct id + rocPRIM's temporaries -- a store of 4 M sessions of 16 items needs about 1.3 GB for a moment.  No device memory for it: SRN_ENOMEM, with the store
+ * untouched and usable.  T above 2^31: SRN_ERANGE. */
+int srn_device_sessions_top_items(srn_device_sessions_t* s, uint64_t now_secs, uint64_t since_secs, uint32_t min_count, size_t cap,
+                                  uint64_t* out_ids, uint32_t* out_counts, size_t* out_n);
+#define SRN_TRENDING_POPULAR_TAIL 1u
+/* Sets the index's fallback ranking from a store's live sessions: the first n entries of srn_device_sessions_top_items(store, now_secs, since_secs,
+ * min_count); with SRN_TRENDING_POPULAR_TAIL, when those are fewer than n, followed by the index's popularity order (srn_index_set_fallback_popular's) without the ids
+ * already in the list, up to n in all.  *out_trending (may be NULL) = how many entries came from the store.  Ids the index does not know stay in the list.
+ * NULL index or store: SRN_EINVAL; n == 0: SRN_EINVAL; n > SRN_MAX_FALLBACK: SRN_ERANGE; item shards and postings-only views refused as for srn_index_set_fallback; an
+ * index without a device: SRN_ENODEV; store on another device than the index: SRN_EINVAL (checked in this order, before any device work).  A resulting list of 0 entries
+ * leaves the ranking as it was (SRN_OK, *out_trending = 0).  The concurrency rule is srn_index_set_fallback's, unchanged: no call on the index may be in flight. */
+int srn_index_set_fallback_trending(srn_index_t* idx, srn_device_sessions_t* store, uint64_t now_secs, uint64_t since_secs, uint32_t min_count, size_t n,
+                                    unsigned flags, size_t* out_trending);
 /* srn_session_key for n strings: string i = ids_flat[off[i] .. off[i + 1]) */
 int srn_session_keys(const char* ids_flat, const uint64_t* off, size_t n, uint64_t* key_hi, uint64_t* key_lo);
 /* flags: SRN_FLAG_BUSINESS_LOGIC, SRN_FLAG_FILL (short rows filled from the index's fallback ranking, above), and SRN_FLAG_EXCLUDE_SEEN -- a request's recommendations leave out what its visitor has seen: the request's window as the request

@@ -54,6 +54,7 @@ FLAG_EXCLUDE_SESSION = 4
 FLAG_EXCLUDE_SEEN = 8
 FLAG_FILL = 16
 MAX_FALLBACK = 4096
+TRENDING_POPULAR_TAIL = 1
 
 
 class EvalTrial(C.Structure):
@@ -204,6 +205,8 @@ SYMBOLS = {
     "srn_device_sessions_save": (_i, [_vp, C.c_char_p, _u64]),
     "srn_device_sessions_load": (_i, [C.c_char_p, _i, _sz, _sz, _u64, _u64, C.POINTER(_vp)]),
     "srn_device_sessions_file_info": (_i, [C.c_char_p, C.POINTER(DeviceSessionsFileInfo)]),
+    "srn_device_sessions_top_items": (_i, [_vp, _u64, _u64, C.c_uint32, _sz, _vp, _vp, C.POINTER(_sz)]),
+    "srn_index_set_fallback_trending": (_i, [_vp, _vp, _u64, _u64, C.c_uint32, _sz, C.c_uint, C.POINTER(_sz)]),
     "srn_session_keys": (_i, [_vp, _vp, _sz, _vp, _vp]),
     "srn_device_sessions_set_history": (_i, [_vp, _sz]),
     "srn_device_sessions_history": (_i, [_vp, C.POINTER(_sz)]),

@@ -826,6 +826,40 @@ int srn_device_sessions_load(const char* path, int device, size_t capacity, size
     return guarded([&]() -> int { return dsess_load(path, device, capacity, items_cap, ttl_secs, idle_secs, out); });
 }
 int srn_device_sessions_file_info(const char* path, srn_device_sessions_file_info_t* out) { return guarded([&]() -> int { return dsess_file_info(path, out); }); }
+// ---- trending items (srn_trending.hip) ----
+int srn_device_sessions_top_items(srn_device_sessions_t* s, uint64_t now_secs, uint64_t since_secs, uint32_t min_count, size_t cap, uint64_t* out_ids, uint32_t* out_counts,
+                                  size_t* out_n) {
+    return guarded([&]() -> int { return dsess_top_items(s, now_secs, since_secs, min_count, cap, out_ids, out_counts, out_n); });
+}
+int srn_index_set_fallback_trending(srn_index_t* idx, srn_device_sessions_t* store, uint64_t now_secs, uint64_t since_secs, uint32_t min_count, size_t n, unsigned flags,
+                                    size_t* out_trending) {
+    return guarded([&]() -> int {
+        const std::string who = "srn_index_set_fallback_trending: ";
+        if (!idx || !store) return fail(SRN_EINVAL, who + "null argument");
+        if (n == 0) return fail(SRN_EINVAL, who + "an empty ranking");
+        if (n > SRN_MAX_FALLBACK) return fail(SRN_ERANGE, who + "more than SRN_MAX_FALLBACK ids");
+        if (check_fallback_index(idx)) return fail(SRN_EINVAL, who + last_error_string());
+        if (!idx->dev) return fail(SRN_ENODEV, who + "the index has no device attached");
+        if (dsess_device_of(store) != idx->device) return fail(SRN_EINVAL, who + "the store and the index are on different devices");
+        if (out_trending) *out_trending = 0;
+        std::vector<uint64_t> list(n);
+        size_t ranked = 0;
+        int rc = dsess_top_items(store, now_secs, since_secs, min_count, n, list.data(), nullptr, &ranked); if (rc) return rc;
+        const size_t trending = std::min(n, ranked);
+        list.resize(trending);
+        if ((flags & SRN_TRENDING_POPULAR_TAIL) && trending < n) {   // the popularity order (the dense item index) without what the list already holds
+            std::vector<uint64_t> have(list);
+            std::sort(have.begin(), have.end());
+            for (size_t i = 0; i < idx->flat.n_items && list.size() < n; ++i) {
+                const uint64_t id = idx->flat.item_id[i];
+                if (!std::binary_search(have.begin(), have.end(), id)) list.push_back(id);
+            }
+        }
+        if (list.empty()) return SRN_OK;   // (the ranking stays as it was)
+        rc = srn_index_set_fallback(idx, list.data(), list.size()); if (rc) return rc;
+        if (out_trending) *out_trending = trending;
+        return SRN_OK; });
+}
 
 // the checks both entry points share, in srn_predict_batch_device's order; *done: nothing to do (n == 0)
 static int check_recommend_args(const srn_index_t* idx, size_t n, size_t k, size_t m, size_t how_many, unsigned flags, bool buffers, bool* done) {

@@ -303,4 +303,7 @@ int dsess_recommend_device(const srn_index* idx, srn_device_sessions* s, const u
 int dsess_recommend_host(const srn_index* idx, srn_device_sessions* s, const uint64_t* hi, const uint64_t* lo, const uint64_t* item, const uint8_t* consent,
                          size_t n, uint64_t now_secs, size_t max_items, size_t k, size_t m, size_t how_many, unsigned flags,
                          uint64_t* ids, double* scores, uint32_t* counts);
+// trending items (srn_trending.hip): the items the store's live sessions hold most often
+int dsess_top_items(srn_device_sessions* s, uint64_t now_secs, uint64_t since_secs, uint32_t min_count, size_t cap, uint64_t* out_ids, uint32_t* out_counts, size_t* out_n);
+int dsess_device_of(const srn_device_sessions* s);
 }  // namespace srn

@@ -48,24 +48,16 @@
 #include "srn_internal.h"
 #include "srn_runtime.h"
 #include "srn_device.h"
+#include "srn_sessions_dev.h"   // the slot, the table and the handle (shared with srn_trending.hip)
 #include "srn_hipsync.h"
 
 namespace srn {
 
 namespace {
 constexpr uint32_t kTPB = 256;
-constexpr uint32_t kSlotHead = 32;             // bytes before the items
 constexpr uint32_t kMaxBatch = 1u << 24;       // q_off is 32-bit: n * SRN_MAX_SESSION_LEN < 2^32
-constexpr uint32_t kEmpty = 0, kFull = 1, kClaimed = 2;
 
-struct SlotHead { uint64_t key_hi, key_lo, epoch; uint32_t len, state; };
-static_assert(sizeof(SlotHead) == kSlotHead, "slot header");
-
-struct Table { char* base; uint32_t mask, stride; };
-__device__ __forceinline__ SlotHead* slot_at(const Table& t, uint32_t s) { return (SlotHead*)(t.base + (size_t)s * t.stride); }
-__device__ __forceinline__ uint64_t* slot_items(SlotHead* h) { return (uint64_t*)((char*)h + kSlotHead); }
 __device__ __forceinline__ uint32_t key_hash(uint64_t hi, uint64_t lo) { return (uint32_t)dev_mix64(lo ^ dev_mix64(hi)); }
-__host__ __device__ __forceinline__ bool idle_or_old(uint64_t now, uint64_t epoch, uint64_t limit) { return now > epoch && now - epoch > limit; }
 
 struct BatchArgs {
     Table t;
@@ -374,7 +366,6 @@ __global__ void __launch_bounds__(kTPB) sess_import_write(ImportArgs a) {
     }
 }
 
-uint64_t wall_secs() { return (uint64_t)std::chrono::duration_cast<std::chrono::seconds>(std::chrono::system_clock::now().time_since_epoch()).count(); }
 size_t align256(size_t b) { return (b + 255) / 256 * 256; }
 dim3 grid_for(size_t n) { return dim3((unsigned)((n + kTPB - 1) / kTPB)); }
 }  // namespace
@@ -382,32 +373,6 @@ dim3 grid_for(size_t n) { return dim3((unsigned)((n + kTPB - 1) / kTPB)); }
 }  // namespace srn
 
 using namespace srn;
-
-struct srn_device_sessions {
-    int device = 0;
-    uint64_t capacity = 0, n_slots = 0, items_cap = 0, ttl = 0, idle = 0;
-    uint32_t stride = 0;
-    char* table[2] = {nullptr, nullptr}; int cur = 0;      // a sweep rebuilds into the other one
-    std::mutex mu;                                          // covers the enqueue of a call and everything below
-    hipEvent_t last = nullptr;                              // end of the most recent call, whatever stream it ran on
-    hipStream_t own = nullptr;                              // get / update / sweep and the host-pointer entry point
-    uint64_t bound = 0, sweeps = 0, refused = 0;            // bound: upper bound of the occupied slots
-    uint32_t len_bound = 1;                                 // upper bound of the stored session lengths (predict's max_len_hint)
-    uint32_t history = 0;                                   // srn_device_sessions_set_history: the window the store keeps (0: max_items_in_session, as the reference)
-    char* ws = nullptr; size_t ws_bytes = 0;                // per-batch scratch, grows with the largest n seen
-    char* stage = nullptr; size_t stage_bytes = 0;          // the host-pointer entry point's device copies
-    std::mutex stage_mu;
-    char* small = nullptr;                                  // err word | counters | one session in / out
-    char* xs = nullptr; size_t xs_bytes = 0;                // export / import scratch (flags and places per slot; sort buffers per entry)
-    uint64_t max_capacity = 0, grows = 0, resizes = 0;      // opt-in growth (0 = off) | automatic resizes | all resizes
-    // the most recent batch (debug accessors, timing)
-    const uint64_t* last_items = nullptr; const uint32_t* last_qoff = nullptr; size_t last_n = 0, last_hint = 0;
-    bool timing = false, last_timed = false; hipEvent_t tev[3] = {nullptr, nullptr, nullptr};
-    Table tab() const { return Table{table[cur], (uint32_t)(n_slots - 1), stride}; }
-    uint32_t* err() const { return (uint32_t*)small; }
-    unsigned long long* counters() const { return (unsigned long long*)(small + 64); }
-    uint64_t* one() const { return (uint64_t*)(small + 128); }
-};
 
 namespace srn {
 

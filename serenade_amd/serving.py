@@ -150,6 +150,32 @@ def fill_rows(ids, scores, counts, sessions, ranking, how_many, excl=None, exclu
     return ids, scores, counts
 
 
+def top_items_model(len, items, epoch, n, now, ttl_secs, since=0, min_count=1):
+    """NumPy statement of DeviceSessionStore.top_items (srn_trending.hip) over the arrays export() returns: len[e], items[e, stride], epoch[e] ->
+    (ids uint64[], counts uint32[]), the first n entries of the ranking (n = None: all of it, so its length is `ranked`).  An entry is in range when a sweep at `now` keeps
+    it -- not (now > epoch and now - epoch > ttl_secs), so now = 1 keeps everything -- and epoch >= since.  count(id) = the in-range entries whose window items[e, :len[e]]
+    holds id at least once; positions from len[e] on are never read.  Count descending, id ascending; counts below min_count (0 is read as 1) are left out.  It needs
+    no GPU and no library."""
+    ln, ep = np.asarray(len, np.int64), np.asarray(epoch, np.uint64)
+    items = np.asarray(items, np.uint64)
+    items = items.reshape(ln.shape[0], items.size // max(ln.shape[0], 1))
+    now, ttl, since = np.uint64(now), np.uint64(ttl_secs), np.uint64(since)
+    old = (now > ep) & ((now - np.minimum(ep, now)) > ttl)
+    in_range = ~old & (ep >= since)
+    e, j = np.nonzero((np.arange(items.shape[1])[None, :] < ln[:, None]) & in_range[:, None])
+    v = items[e, j]
+    order = np.lexsort((v, e))                                   # by entry, then id: the repeats of an id inside a window become neighbours
+    e, v = e[order], v[order]
+    first = np.ones(v.shape[0], bool)
+    first[1:] = (e[1:] != e[:-1]) | (v[1:] != v[:-1])
+    ids, counts = np.unique(v[first], return_counts=True)        # (ids ascending)
+    keep = counts >= max(int(min_count), 1)
+    ids, counts = ids[keep], counts[keep]
+    order = np.argsort(-counts, kind="stable")                   # count descending; stable: id ascending among equal counts
+    ids, counts = ids[order].astype(np.uint64), counts[order].astype(np.uint32)
+    return (ids, counts) if n is None else (ids[:int(n)], counts[:int(n)])
+
+
 def _is_torch(x):
     return type(x).__module__.split(".")[0] == "torch"
 
@@ -343,6 +369,16 @@ class DeviceSessionStore:
         hi, lo, epoch, items = (capi.as_u64(a.numpy() if _is_torch(a) else a) for a in (hi, lo, epoch, items))
         ln = capi.as_u32(len.numpy() if _is_torch(len) else len)
         capi.check(capi.lib().srn_device_sessions_import(self._h, capi.ptr(hi), capi.ptr(lo), capi.ptr(epoch), capi.ptr(ln), capi.ptr(items), stride, n))
+
+    def top_items(self, n, since=0, min_count=1, now=0):
+        """srn_device_sessions_top_items: the n items the live sessions at `now` hold most often -> (ids uint64[], counts uint32[]), count descending, id ascending (fewer
+        than n when fewer are ranked).  count = the sessions, with an epoch >= since, whose stored window holds the item at least once; counts below min_count are left
+        out.  Counted and ranked on the GPU (top_items_model is the rule in NumPy); blocks, and changes nothing in the store."""
+        ids, counts, ranked = np.zeros(int(n), np.uint64), np.zeros(int(n), np.uint32), C.c_size_t()
+        capi.check(capi.lib().srn_device_sessions_top_items(self._h, int(now), int(since), int(min_count), int(n), capi.ptr(ids) if n else None,
+                                                            capi.ptr(counts) if n else None, C.byref(ranked)))
+        got = min(int(n), ranked.value)
+        return ids[:got], counts[:got]
 
     def resize(self, capacity, items_cap=None, now=0):
         """Rebuilds the live sessions at `now` into tables of another capacity and / or items_cap; on an error the store is unchanged."""

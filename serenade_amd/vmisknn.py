@@ -116,6 +116,16 @@ class VMISIndex:
         """The first min(n, n_items) items of the index's popularity order (count of kept sessions that hold the item descending, id ascending)."""
         capi.check(capi.lib().srn_index_set_fallback_popular(self._h, int(n)))
 
+    def set_fallback_trending(self, store, n, since=0, min_count=1, popular_tail=True, now=0):
+        """srn_index_set_fallback_trending: the ranking becomes the first n entries of store.top_items(n, since, min_count, now) -- what the live sessions of a
+        serving.DeviceSessionStore hold most often, products listed since the index was built included -- and, with popular_tail, when those are fewer than n, the index's
+        popularity order without repeats behind them, n in all.  -> the number of entries taken from the store (0 with no tail: the ranking is left as it was).  The
+        rule of set_fallback holds: no call on the index in flight."""
+        got = C.c_size_t()
+        capi.check(capi.lib().srn_index_set_fallback_trending(self._h, store._h, int(now), int(since), int(min_count), int(n),
+                                                              capi.TRENDING_POPULAR_TAIL if popular_tail else 0, C.byref(got)))
+        return got.value
+
     def fallback(self):
         """The ranking as set: uint64[R] (R = 0: none)."""
         n = C.c_size_t()
