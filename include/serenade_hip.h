@@ -649,13 +649,26 @@ int srn_recommend_batch(const srn_index_t* idx, srn_device_sessions_t* store, co
  *                          add up; the number of distinct ids is Coverage's denominator (coverage.rs:17-25).
  * The set keeps a pointer to the index: free the set first. */
 typedef struct srn_eval_set srn_eval_set_t;
+/* Trials under the serving rules.  A test session e_1..e_n gives one query per state t = 1..n-1, scored against the raw e_{t+1}..e_n, with or without
+ * these flags.  W = max_items_in_session, H' = history if history > 0, else W.
+ *   c(t)      with SRN_FLAG_EVAL_HANDLER e_1..e_t without every e_j (j >= 2) equal to e_{j-1} -- what the /v1/recommend handler's rule "append unless the click repeats
+ *             the stored last item, drop the oldest beyond the limit" leaves of the clicks (recommend_resource.rs:39-54); without the flag e_1..e_t
+ *   query(t)  the last min(|c(t)|, W) items of c(t); seen(t) the last min(|c(t)|, H') -- the window a device session store with history H holds behind click t
+ *   list      SRN_FLAG_EXCLUDE_SESSION: query(t)'s items; SRN_FLAG_EXCLUDE_SEEN (alone or with the former): seen(t); neither: none
+ * The scored rows are srn_predict_batch_device_excl's for (query(t), list) -- "remove the ids from all candidates, then cut to how_many" -- filled under that call's rule
+ * with SRN_FLAG_FILL.  SRN_FLAG_EVAL_HANDLER | SRN_FLAG_EXCLUDE_SEEN scores the rows srn_recommend_batch serves with SRN_FLAG_EXCLUDE_SEEN to one visitor per test
+ * session, clicks in order, on a store with history H at a constant clock.  The launch sequence runs at the internal how_many + capacity (H' with
+ * SRN_FLAG_EXCLUDE_SEEN, W with SRN_FLAG_EXCLUDE_SESSION alone); above SRN_MAX_HOW_MANY: SRN_ERANGE.  A trial with none of the three flags is the reference evaluator's. */
+#define SRN_FLAG_EVAL_HANDLER 32u
 typedef struct {
     uint32_t k, m, how_many;          /* predict's arguments (m <= the index's m_index is the normal case: one index answers every smaller m) */
     uint32_t max_items_in_session;    /* the window: a prefix is its last max_items_in_session items (evaluator.rs:50-55); 1..SRN_MAX_SESSION_LEN */
     uint32_t length;                  /* @N of the metrics (1..SRN_MAX_HOW_MANY); independent of how_many (hyperparameter_search.rs asks for 21, scores @20) */
-    uint32_t flags;                   /* SRN_FLAG_BUSINESS_LOGIC, SRN_FLAG_FILL (the filled rows are scored; SRN_ESTATE without a ranking) */
+    uint32_t flags;                   /* SRN_FLAG_BUSINESS_LOGIC, SRN_FLAG_FILL (the filled rows are scored; SRN_ESTATE without a ranking), and the serving rules below:
+                                       * SRN_FLAG_EXCLUDE_SESSION, SRN_FLAG_EXCLUDE_SEEN, SRN_FLAG_EVAL_HANDLER */
     uint32_t max_chunk_queries;       /* queries per device round (0 = default); rounded down to a multiple of 256.  Results do not depend on it */
-    uint32_t reserved;                /* 0 */
+    uint32_t history;                 /* the seen-items window H of SRN_FLAG_EXCLUDE_SEEN (below): 0 = none, or max_items_in_session..SRN_MAX_SESSION_LEN (else SRN_ERANGE).
+                                       * Without SRN_FLAG_EXCLUDE_SEEN it changes no row.  (The field was `reserved`, 0: same offset, same meaning of 0) */
 } srn_eval_trial_t;
 typedef struct {
     uint64_t n_evaluations;           /* qty_evaluations: queries of the trial */
@@ -673,7 +686,8 @@ int srn_eval_set_from_tsv(const srn_index_t* idx, const char* test_path, const c
 /* Runs n_trials trials and blocks until they are done; out[t] is trial t's result.  Sums are added in a fixed order (partial sums per
  * group of 256 queries): the same trial gives the same bits from call to call, alone or among others, for any max_chunk_queries.
  * Every trial is checked before anything is launched: predict's argument checks, length 0 (SRN_EINVAL) or above SRN_MAX_HOW_MANY, and a
- * window of 0 (SRN_EINVAL) or above SRN_MAX_SESSION_LEN (SRN_ERANGE: a prefix could exceed the kernels' session limit) fail the whole call.
+ * window of 0 (SRN_EINVAL) or above SRN_MAX_SESSION_LEN (SRN_ERANGE: a prefix could exceed the kernels' session limit), a history outside its range and an
+ * internal how_many above SRN_MAX_HOW_MANY (both SRN_ERANGE) fail the whole call.
  * stream: a hipStream_t (NULL = the null stream). */
 int srn_evaluate(srn_eval_set_t* set, const srn_eval_trial_t* trials, size_t n_trials, srn_eval_result_t* out, void* stream);
 void srn_eval_set_free(srn_eval_set_t* set);

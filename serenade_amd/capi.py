@@ -53,12 +53,13 @@ FLAG_INPUTS_RESIDENT = 2
 FLAG_EXCLUDE_SESSION = 4
 FLAG_EXCLUDE_SEEN = 8
 FLAG_FILL = 16
+FLAG_EVAL_HANDLER = 32
 MAX_FALLBACK = 4096
 TRENDING_POPULAR_TAIL = 1
 
 
 class EvalTrial(C.Structure):
-    _fields_ = [(n, C.c_uint32) for n in ("k", "m", "how_many", "max_items_in_session", "length", "flags", "max_chunk_queries", "reserved")]
+    _fields_ = [(n, C.c_uint32) for n in ("k", "m", "how_many", "max_items_in_session", "length", "flags", "max_chunk_queries", "history")]
 
 
 class EvalResult(C.Structure):

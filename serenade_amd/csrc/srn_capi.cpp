@@ -720,6 +720,12 @@ static int check_trials(const srn_eval_set_t* set, const srn_eval_trial_t* trial
         if (tr.how_many > SRN_MAX_HOW_MANY) return fail(SRN_ERANGE, "how_many above SRN_MAX_HOW_MANY");
         if (tr.k > SRN_MAX_K) return fail(SRN_ERANGE, "k above SRN_MAX_K");
         if (tr.m > 0x7FFFFFFFu) return fail(SRN_ERANGE, "m too large");
+        // the serving rules (srn_eval.hip): the history window mirrors srn_device_sessions_set_history and max_items_in_session <= H; the launch sequence runs at
+        // how_many + the exclusion lists' capacity
+        if (tr.history != 0 && (tr.history < tr.max_items_in_session || tr.history > SRN_MAX_SESSION_LEN))
+            return fail(SRN_ERANGE, "history must be 0 or in max_items_in_session..SRN_MAX_SESSION_LEN");
+        if (tr.how_many + eval_excl_capacity(tr) > SRN_MAX_HOW_MANY)
+            return fail(SRN_ERANGE, "how_many + the exclusion lists' capacity (history, or max_items_in_session) above SRN_MAX_HOW_MANY");
     }
     if (!set) return fail(SRN_EINVAL, "null evaluation set");
     for (size_t t = 0; t < n_trials; ++t) { int rc = check_predict_args(set->idx, trials[t].k, trials[t].m, trials[t].how_many); if (rc) return rc;

@@ -5,7 +5,18 @@
 //   eval_metrics_kernel  one wave per query: the per-query terms of src/metrics/*.rs, and the recommended items' coverage bits
 //   eval_group_kernel    partial sums per group of 256 GLOBAL query indices (chunks are multiples of 256, so a group never straddles two)
 // The host adds the groups' partial sums in group order: a trial's sums do not depend on the chunk size or on the other trials of the call.
+//
+// Trials under the serving rules (SRN_FLAG_EVAL_HANDLER, SRN_FLAG_EXCLUDE_SESSION, SRN_FLAG_EXCLUDE_SEEN) expand a chunk in three steps instead:
+// once repeated clicks collapse, a query's place in the CSR is no closed form of its state.
+//   eval_serve_count_kernel   per query: |query(t)| and |list| packed into one 64-bit word, from a walk back from e_t under the handler's rule
+//   rocprim::exclusive_scan   both offsets in one scan (the halves cannot carry into each other: a chunk's items and list ids are both below 2^32)
+//   eval_serve_write_kernel   the same walk: items_flat / q_off, the exclusion CSR x_flat / x_off, (session, state)
+// and predict with an ExclSpec over the lists, as srn_predict_batch_device_excl does: wide rows in the workspace's scratch, the filter and the fill kernel behind the
+// launch sequence.  Nothing waits on the host between chunks: the buffers are sized from the capacities.  The metric, group and popcount kernels are the same.
 #include <hip/hip_runtime.h>
+
+#include <cstring>   // rocprim's texture iterator calls the host memset
+#include <rocprim/rocprim.hpp>
 
 #include <algorithm>
 #include <cmath>
@@ -72,6 +83,70 @@ __global__ void __launch_bounds__(256) eval_expand_kernel(const uint64_t* __rest
     out_qoff[i] = (uint32_t)at;
     if (i == nq - 1) out_qoff[nq] = (uint32_t)(at + len);
     out_ss[i] = make_uint2(s, (uint32_t)state);
+}
+
+// ---- expansion under the serving rules ----
+struct ServeArgs {
+    const uint64_t* items; const uint64_t* sess_off; const uint64_t* sess_q; uint32_t n_sessions;
+    uint64_t q0; uint32_t nq;
+    uint32_t W, cap;          // the session window; the exclusion lists' capacity (eval_excl_capacity: H' with SRN_FLAG_EXCLUDE_SEEN, W with SRN_FLAG_EXCLUDE_SESSION alone, else 0)
+    uint32_t handler;         // SRN_FLAG_EVAL_HANDLER: a click equal to the one before it is no click
+    uint64_t* packed;         // [nq + 1] count kernel: list length << 32 | query length; then, scanned in `offs`, the two offsets
+    const uint64_t* offs;
+    uint64_t* out_items; uint32_t* out_qoff; uint64_t* x_flat; uint32_t* x_off; uint2* out_ss;
+};
+
+// global query g -> its session and state (sessions without queries have sess_q[s] == sess_q[s + 1])
+__device__ __forceinline__ void serve_locate(const ServeArgs& a, uint64_t g, uint32_t& s, uint32_t& state) {
+    uint32_t lo = 0, hi = a.n_sessions;
+    while (hi - lo > 1) { const uint32_t mid = (lo + hi) / 2; if (a.sess_q[mid] <= g) lo = mid; else hi = mid; }
+    s = lo; state = (uint32_t)(g - a.sess_q[lo] + 1);
+}
+
+// c(t) from its most recent item backwards, at most `want` items: f(r, id) for the r-th of them; returns how many there were.  ev = the session's events, t >= 1.
+// One thread per query: neighbouring lanes hold neighbouring states of one session, so step r of the walk reads neighbouring addresses across the wave.
+template <typename F> __device__ __forceinline__ uint32_t serve_walk(const uint64_t* __restrict__ ev, uint32_t t, bool handler, uint32_t want, F&& f) {
+    uint32_t r = 0;
+    if (!handler) {
+        const uint32_t n = min(t, want);
+        for (; r < n; ++r) f(r, ev[t - 1 - r]);
+        return n;
+    }
+    uint64_t cur = ev[t - 1];
+    for (uint32_t j = t; j >= 1 && r < want; --j) {   // e_j = ev[j - 1] stays unless it repeats e_{j-1}
+        const uint64_t prev = j >= 2 ? ev[j - 2] : 0ull;
+        if (j == 1 || cur != prev) { f(r, cur); ++r; }
+        cur = prev;
+    }
+    return r;
+}
+
+__global__ void __launch_bounds__(256) eval_serve_count_kernel(ServeArgs a) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i > a.nq) return;
+    if (i == a.nq) { a.packed[i] = 0ull; return; }
+    uint32_t s, t; serve_locate(a, a.q0 + i, s, t);
+    const uint32_t want = max(a.W, a.cap);
+    const uint32_t c = a.handler ? serve_walk(a.items + a.sess_off[s], t, true, want, [](uint32_t, uint64_t) {}) : min(t, want);
+    a.packed[i] = ((uint64_t)min(c, a.cap) << 32) | min(c, a.W);
+}
+
+__global__ void __launch_bounds__(256) eval_serve_write_kernel(ServeArgs a) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i > a.nq) return;
+    const uint64_t o = a.offs[i];
+    const uint32_t qo = (uint32_t)o, xo = (uint32_t)(o >> 32);
+    a.out_qoff[i] = qo; a.x_off[i] = xo;
+    if (i == a.nq) return;
+    const uint64_t o1 = a.offs[i + 1];
+    const uint32_t len = (uint32_t)o1 - qo, xlen = (uint32_t)(o1 >> 32) - xo;
+    uint32_t s, t; serve_locate(a, a.q0 + i, s, t);
+    uint64_t* __restrict__ qi = a.out_items + qo; uint64_t* __restrict__ xi = a.x_flat + xo;
+    serve_walk(a.items + a.sess_off[s], t, a.handler != 0u, max(len, xlen), [&](uint32_t r, uint64_t id) {   // oldest first, as the handler's session is
+        if (r < len) qi[len - 1u - r] = id;
+        if (r < xlen) xi[xlen - 1u - r] = id;
+    });
+    a.out_ss[i] = make_uint2(s, t);
 }
 
 struct MetricArgs {
@@ -259,8 +334,11 @@ int eval_set_from_tsv(const srn_index* idx, const char* test_path, const char* t
 }
 
 static uint32_t chunk_queries(const srn_eval_trial_t& t) {
-    uint32_t c = t.max_chunk_queries ? t.max_chunk_queries : std::min<uint32_t>(kDefaultChunk, (1u << 26) / t.how_many);
-    c = std::min(c, kMaxChunk) / kGroup * kGroup;
+    // (the rows predict writes are how_many + the lists' capacity wide; a trial that excludes nothing has capacity 0)
+    uint32_t c = t.max_chunk_queries ? t.max_chunk_queries : std::min<uint32_t>(kDefaultChunk, (1u << 26) / (t.how_many + eval_excl_capacity(t)));
+    // 32-bit offsets: a chunk's items (<= W per query) and list ids (<= the capacity) both stay below 2^32 (kMaxChunk alone keeps them there while SRN_MAX_SESSION_LEN < 256)
+    const uint32_t per_query = std::max(t.max_items_in_session, eval_excl_capacity(t));
+    c = std::min<uint64_t>(std::min(c, kMaxChunk), 0xFFFFFFFFull / per_query) / kGroup * kGroup;
     return std::max(c, kGroup);
 }
 
@@ -311,15 +389,29 @@ int eval_run(srn_eval_set* set, const srn_eval_trial_t* trials, size_t n_trials,
         const uint32_t max_len = (uint32_t)std::min<uint64_t>(W, set->max_session_len - 1);
         const uint32_t chunk = chunk_queries(tr);
         const uint32_t cq = (uint32_t)std::min<uint64_t>(chunk, nq_all);
-        // chunk buffers: items | q_off | (session, state) | ids | scores | counts | terms
+        // the serving rules: the trial's chunks take the count / scan / write expansion and predict with the lists (a trial without these flags enqueues what it always did)
+        const bool serving = (tr.flags & (SRN_FLAG_EVAL_HANDLER | SRN_FLAG_EXCLUDE_SESSION | SRN_FLAG_EXCLUDE_SEEN)) != 0u;
+        const uint32_t cap = eval_excl_capacity(tr);
+        const uint32_t max_x = (uint32_t)std::min<uint64_t>(cap, set->max_session_len - 1);   // a list is never longer than its query's state
+        size_t scan_tmp = 0;
+        if (serving)   // rocPRIM's temporary storage, for a full chunk and for the last one
+            for (const uint64_t n : {(uint64_t)cq + 1, nq_all % chunk + 1}) {
+                size_t t1 = 0;
+                HIP_TRY(rocprim::exclusive_scan(nullptr, t1, (uint64_t*)nullptr, (uint64_t*)nullptr, 0ull, (size_t)n, rocprim::plus<uint64_t>(), st));
+                scan_tmp = std::max(scan_tmp, t1);
+            }
+        // chunk buffers: items | q_off | (session, state) | ids | scores | counts | terms, and under the serving rules | list ids | x_off | packed lengths | packed offsets | scan storage
         const size_t o_items = 0, o_qoff = align256((size_t)cq * max_len * 8), o_ss = o_qoff + align256(((size_t)cq + 1) * 4),
                      o_ids = o_ss + align256((size_t)cq * 8), o_sc = o_ids + align256((size_t)cq * tr.how_many * 8),
                      o_cnt = o_sc + align256((size_t)cq * tr.how_many * 8), o_terms = o_cnt + align256((size_t)cq * 4),
-                     bytes = o_terms + align256((size_t)cq * kTerms * 8);
+                     o_x = o_terms + align256((size_t)cq * kTerms * 8), o_xoff = o_x + (serving ? align256((size_t)cq * max_x * 8) : 0),
+                     o_pk = o_xoff + (serving ? align256(((size_t)cq + 1) * 4) : 0), o_po = o_pk + (serving ? align256(((size_t)cq + 1) * 8) : 0),
+                     o_tmp = o_po + (serving ? align256(((size_t)cq + 1) * 8) : 0), bytes = o_tmp + align256(scan_tmp);
         if (bytes > e->chunk_bytes) { HIP_TRY(hipStreamSynchronize(st)); if ((rc = ensure(&e->chunk, &e->chunk_bytes, bytes))) return rc; }
         char* cb = e->chunk;
         uint64_t* d_items = (uint64_t*)(cb + o_items); uint32_t* d_qoff = (uint32_t*)(cb + o_qoff); uint2* d_ss = (uint2*)(cb + o_ss);
         uint64_t* d_ids = (uint64_t*)(cb + o_ids); double* d_sc = (double*)(cb + o_sc); uint32_t* d_cnt = (uint32_t*)(cb + o_cnt); double* d_terms = (double*)(cb + o_terms);
+        uint64_t* d_x = (uint64_t*)(cb + o_x); uint32_t* d_xoff = (uint32_t*)(cb + o_xoff);
         double* part = (double*)e->part + ti * n_groups * kSums;
         uint32_t* bitmap = (uint32_t*)(e->cover + ti * cover_stride);
         for (uint64_t q0 = 0; q0 < nq_all; q0 += chunk) {
@@ -327,17 +419,38 @@ int eval_run(srn_eval_set* set, const srn_eval_trial_t* trials, size_t n_trials,
             hipEvent_t* ev = &e->ev[ev_at]; ev_at += 4;
             HIP_TRY(hipEventRecord(ev[0], st));
             // item offset of query q0: its session's start + the prefixes before it
-            uint64_t item_base;
-            { const size_t s = (size_t)(std::upper_bound(scan.begin(), scan.begin() + n_s + 1, q0) - scan.begin()) - 1;
-              item_base = scan[n_s + 1 + s] + prefix_items(q0 - scan[s], W); }
-            eval_expand_kernel<<<(nq + 255) / 256, 256, 0, st>>>(e->items, e->sess_off, sess_q, sess_i, (uint32_t)n_s, q0, nq, W, item_base, d_items, d_qoff, d_ss);
-            HIP_TRY(hipGetLastError());
+            if (serving) {
+                ServeArgs sa{};
+                sa.items = e->items; sa.sess_off = e->sess_off; sa.sess_q = sess_q; sa.n_sessions = (uint32_t)n_s; sa.q0 = q0; sa.nq = nq;
+                sa.W = W; sa.cap = cap; sa.handler = (tr.flags & SRN_FLAG_EVAL_HANDLER) ? 1u : 0u;
+                sa.packed = (uint64_t*)(cb + o_pk); sa.offs = (const uint64_t*)(cb + o_po);
+                sa.out_items = d_items; sa.out_qoff = d_qoff; sa.x_flat = d_x; sa.x_off = d_xoff; sa.out_ss = d_ss;
+                eval_serve_count_kernel<<<(nq + 1 + 255) / 256, 256, 0, st>>>(sa);
+                HIP_TRY(hipGetLastError());
+                size_t t1 = scan_tmp;
+                HIP_TRY(rocprim::exclusive_scan(cb + o_tmp, t1, sa.packed, (uint64_t*)(cb + o_po), 0ull, (size_t)nq + 1, rocprim::plus<uint64_t>(), st));
+                eval_serve_write_kernel<<<(nq + 1 + 255) / 256, 256, 0, st>>>(sa);
+                HIP_TRY(hipGetLastError());
+            } else {
+                uint64_t item_base;
+                { const size_t s = (size_t)(std::upper_bound(scan.begin(), scan.begin() + n_s + 1, q0) - scan.begin()) - 1;
+                  item_base = scan[n_s + 1 + s] + prefix_items(q0 - scan[s], W); }
+                eval_expand_kernel<<<(nq + 255) / 256, 256, 0, st>>>(e->items, e->sess_off, sess_q, sess_i, (uint32_t)n_s, q0, nq, W, item_base, d_items, d_qoff, d_ss);
+                HIP_TRY(hipGetLastError());
+            }
             HIP_TRY(hipEventRecord(ev[1], st));
             LaunchParams p{};
             p.nq = nq; p.k = tr.k; p.m = tr.m; p.how_many = tr.how_many; p.flags = (tr.flags & SRN_FLAG_BUSINESS_LOGIC) | kFlagNoResultCache; p.max_len = max_len;   // (a grid of trials is no serving traffic: the index's result cache is bypassed)
             p.items_flat = d_items; p.q_off = d_qoff; p.out_ids = d_ids; p.out_scores = d_sc; p.out_counts = d_cnt;
             // (SRN_FLAG_FILL: the metric kernel scores the filled rows -- the fill kernel runs behind the launch sequence, inside the call)
-            if ((rc = device_predict(idx->dev, ix, p, true, st, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, false, false, nullptr, (tr.flags & SRN_FLAG_FILL) != 0u))) return rc;
+            const bool fill = (tr.flags & SRN_FLAG_FILL) != 0u;
+            if (cap) {   // the lists are the exclusion CSR of srn_predict_batch_device_excl: the launch sequence writes rows of how_many + cap into the workspace's scratch, the filter the chunk's
+                const ExclSpec x{d_x, d_xoff, cap, false, tr.how_many, d_ids, d_sc, d_cnt};
+                p.how_many = tr.how_many + cap; p.out_ids = nullptr; p.out_scores = nullptr; p.out_counts = nullptr;
+                rc = device_predict(idx->dev, ix, p, true, st, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, false, false, &x, fill);
+            } else
+                rc = device_predict(idx->dev, ix, p, true, st, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, false, false, nullptr, fill);
+            if (rc) return rc;
             HIP_TRY(hipSetDevice(e->device));
             HIP_TRY(hipEventRecord(ev[2], st));
             MetricArgs a{};

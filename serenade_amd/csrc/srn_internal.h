@@ -266,6 +266,12 @@ int eval_set_from_tsv(const srn_index* idx, const char* test_path, const char* t
 // trials already checked (srn_capi.cpp).  terms != nullptr: one trial, its per-query terms [n * 7] (cap entries of room)
 int eval_run(srn_eval_set* set, const srn_eval_trial_t* trials, size_t n_trials, srn_eval_result_t* out, void* stream, double* terms, size_t cap);
 uint64_t eval_n_queries(const srn_eval_set* set);   // queries of any trial: sum over sessions of (len - 1)
+// a trial's exclusion lists hold at most this many ids (0: the trial excludes nothing): the history window -- the session window without one -- with
+// SRN_FLAG_EXCLUDE_SEEN, the session window with SRN_FLAG_EXCLUDE_SESSION alone.  The launch sequence runs at how_many + this
+inline uint32_t eval_excl_capacity(const srn_eval_trial_t& t) {
+    if (t.flags & SRN_FLAG_EXCLUDE_SEEN) return t.history ? t.history : t.max_items_in_session;
+    return (t.flags & SRN_FLAG_EXCLUDE_SESSION) ? t.max_items_in_session : 0u;
+}
 void eval_set_free(srn_eval_set* set);
 }  // namespace srn
 

@@ -5,7 +5,11 @@ srn_eval_set_* / srn_evaluate.
     evaluate(es, [dict(k=50, m=500, max_items_in_session=2), ...])   # -> one report per trial
 
 A trial is a dict: k, m, max_items_in_session (the window), how_many (default 20), length (the metrics' @N, default 20),
-business_logic (default False), fill (default False: with it short rows are filled from the index's fallback ranking before they are scored), max_chunk_queries (default 0: the library's chunk size; results do not depend on it).
+business_logic (default False), fill (default False: with it short rows are filled from the index's fallback ranking before they are scored), max_chunk_queries (default 0: the library's chunk size; results do not depend on it),
+and the serving rules, all off by default: handler_sessions (the sessions /v1/recommend builds: a click that repeats the one before it is dropped),
+exclude_session (a query's own items are left out of its row), exclude_seen with history (the row leaves out the last `history` items the visitor has seen -- the
+session window with history=0; history without exclude_seen changes no row).  handler_sessions + exclude_seen scores the rows recommend_batch(..., exclude_seen=True)
+serves; serving_queries() states the queries and lists of such a trial in Python.
 A report holds the evaluator's report line under its own names (qty_evaluations, Mrr@20, ..., F1score@20), the raw sums and the
 device milliseconds of predict and of the evaluation kernels.
 """
@@ -27,9 +31,32 @@ def _trial(t):
     out.how_many = int(t.get("how_many", 20))
     out.max_items_in_session = int(t["max_items_in_session"])
     out.length = int(t.get("length", 20))
-    out.flags = (capi.FLAG_BUSINESS_LOGIC if t.get("business_logic", False) else 0) | (capi.FLAG_FILL if t.get("fill", False) else 0)
+    out.flags = (capi.FLAG_BUSINESS_LOGIC if t.get("business_logic", False) else 0) | (capi.FLAG_FILL if t.get("fill", False) else 0) | \
+                (capi.FLAG_EXCLUDE_SESSION if t.get("exclude_session", False) else 0) | (capi.FLAG_EXCLUDE_SEEN if t.get("exclude_seen", False) else 0) | \
+                (capi.FLAG_EVAL_HANDLER if t.get("handler_sessions", False) else 0)
     out.max_chunk_queries = int(t.get("max_chunk_queries", 0))
-    out.reserved = 0
+    out.history = int(t.get("history", 0))
+    return out
+
+
+def serving_queries(test_sessions, max_items_in_session, history=0, handler_sessions=False, exclude_session=False, exclude_seen=False):
+    """The queries of a trial under the serving rules, in set order (sessions in order, states ascending) -> [(query, exclusion_list, next_items)]; the closed form of
+    DESIGN.md 10, the counterpart of serving.filter_rows / fill_rows.  For state t of a session e_1..e_n: c = e_1..e_t, with handler_sessions without every click
+    equal to the one before it; query = the last max_items_in_session items of c; the list is empty without exclude_session / exclude_seen, the query's items with
+    exclude_session alone, and with exclude_seen the last `history` items of c (the last max_items_in_session with history=0); next_items = e_{t+1}..e_n, raw.
+    It needs no GPU."""
+    W, H = int(max_items_in_session), int(history)
+    if W < 1 or (H and H < W):
+        raise ValueError("max_items_in_session must be > 0 and history 0 or >= max_items_in_session")
+    seqs = test_sessions.values() if isinstance(test_sessions, dict) else test_sessions
+    out = []
+    for ev in seqs:
+        ev = list(ev)
+        for t in range(1, len(ev)):
+            c = [x for j, x in enumerate(ev[:t]) if not (handler_sessions and j and x == ev[j - 1])]
+            query = c[-W:]
+            lst = c[-(H or W):] if exclude_seen else (list(query) if exclude_session else [])
+            out.append((query, lst, ev[t:]))
     return out
 
 

@@ -4,11 +4,12 @@ One index serves every m up to its m_index (posting lists are most-recent-first 
 vmis_index.rs:325-390), and only idf_weighting is baked into an index (mod.rs:146-152).  So search() builds one index per distinct
 idf weighting, at the largest m asked for with it, and evaluates all of that weighting's trials in one srn_evaluate call.
 
-    python -m serenade_amd.hpo <config.toml> [--random N --seed S]
+    python -m serenade_amd.hpo <config.toml> [--random N --seed S] [--exclude-seen] [--exclude-session] [--history H] [--handler-sessions] [--fill]
 
 reads the [hyperparam] keys of the reference's configuration (training_data_path, test_data_path, save_records, out_path,
 enable_business_logic), writes exhaustive_grid_search.rs's CSV and prints its "Best ..." lines.  TPE (tpe_hyperparameter_optm.rs) is
-not restated: evaluate() takes any list of trials, so an external optimiser can drive it.
+not restated: evaluate() takes any list of trials, so an external optimiser can drive it.  The serving rules (evaluation.py: exclude_seen, exclude_session,
+history, handler_sessions, fill) are options of the whole search, not grid axes: every trial runs under them, and the CSV keeps the reference's columns.
 """
 import argparse
 import ctypes as C
@@ -30,6 +31,7 @@ RANDOM_GRID = {"m": [100, 250, 500, 750, 1000, 2500], "k": [50, 100, 500, 1000, 
                "idf_weighting": [1, 2, 3]}
 _KEYS = ("m", "k", "max_items_in_session", "idf_weighting")
 GOAL = "MRR@20"
+FILL_RANKING = 64   # search(fill=True): the fallback ranking is this many of the most popular training items
 
 
 def exhaustive(grid=EXHAUSTIVE_GRID):
@@ -65,11 +67,18 @@ def _build_index(sessions, m_index, idf_weighting, device):
     return VMISIndex(h)
 
 
-def search(train_path, test_path, trials, business_logic=False, device=0, how_many=20, length=20, loader="host"):
+def search(train_path, test_path, trials, business_logic=False, device=0, how_many=20, length=20, loader="host", exclude_seen=False, exclude_session=False, history=0,
+           handler_sessions=False, fill=False):
     """objective() (src/objective.rs:8-52) for every trial: Mrr@length of predict(k, m, how_many) over every windowed prefix.
     loader="gpu" reads the training sessions with the GPU loader (srn_sessions_from_tsv_gpu: the same sessions).
+    exclude_seen, exclude_session, history, handler_sessions, fill: the serving rules of evaluation.py, applied to every trial (fill: from the most popular
+    training items, set on each index the search builds).
     -> {"records": [one per trial, in trial order], "best": the first record of the highest Mrr}."""
     trials = [dict(t) for t in trials]
+    for i, t in enumerate(trials):   # what srn_evaluate refuses with SRN_ERANGE, said before any index is built: a store's history window is never below the session window
+        if history and int(t["max_items_in_session"]) > int(history):
+            raise ValueError("history=%d is below max_items_in_session=%d of trial %d: the seen-items window holds at least the session window" %
+                             (history, int(t["max_items_in_session"]), i))
     sessions = C.c_void_p()
     if loader == "gpu":
         capi.check(capi.lib().srn_sessions_from_tsv_gpu(str(train_path).encode(), int(device), C.byref(sessions)))
@@ -81,10 +90,13 @@ def search(train_path, test_path, trials, business_logic=False, device=0, how_ma
     try:
         for w, m_index in index_plan(trials).items():
             index = _build_index(sessions, m_index, w, device)
+            if fill:
+                index.set_fallback_popular(FILL_RANKING)
             es = EvalSet.from_tsv(index, test_path, train_path)
             mine = [i for i, t in enumerate(trials) if float(t["idf_weighting"]) == w]
             reps = evaluate(es, [dict(k=trials[i]["k"], m=trials[i]["m"], max_items_in_session=trials[i]["max_items_in_session"], how_many=how_many,
-                                      length=length, business_logic=business_logic) for i in mine])
+                                      length=length, business_logic=business_logic, exclude_seen=exclude_seen, exclude_session=exclude_session, history=history,
+                                      handler_sessions=handler_sessions, fill=fill) for i in mine])
             for i, rep in zip(mine, reps):
                 t = trials[i]
                 records[i] = {"iteration": i, "n_most_recent_sessions": int(t["m"]), "neighborhood_size_k": int(t["k"]),
@@ -144,11 +156,17 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--gpu-loader", action="store_true", help="read the training file with the GPU loader (the same sessions)")
+    ap.add_argument("--exclude-seen", action="store_true", help="every trial leaves out what the visitor has seen (the last --history items, or the session window)")
+    ap.add_argument("--exclude-session", action="store_true", help="every trial leaves out the items of the query's own session")
+    ap.add_argument("--history", type=int, default=0, metavar="H", help="the seen-items window of --exclude-seen (0: the session window); at least the largest last_items_in_session of the grid (10)")
+    ap.add_argument("--handler-sessions", action="store_true", help="queries are the sessions /v1/recommend builds: repeated clicks dropped")
+    ap.add_argument("--fill", action="store_true", help="short rows are filled from the most popular training items before they are scored")
     a = ap.parse_args(argv)
     cfg = hyperparam_config(a.config)
     trials = random(EXHAUSTIVE_GRID, a.random, a.seed) if a.random else exhaustive()
+    rules = dict(exclude_seen=a.exclude_seen, exclude_session=a.exclude_session, history=a.history, handler_sessions=a.handler_sessions, fill=a.fill)
     res = search(cfg["training_data_path"], cfg["test_data_path"], trials, cfg["enable_business_logic"], a.device,
-                 loader="gpu" if a.gpu_loader else "host")
+                 loader="gpu" if a.gpu_loader else "host", **rules)
     with open(cfg["out_path"], "w") as f:   # exhaustive_grid_search.rs:34-46 (the file is created either way)
         if cfg["save_records"]:
             f.write("iteration,n_most_recent_sessions,neighborhood_size_k,last_items_in_session,idf_weighting,%s\n" % GOAL)
@@ -157,6 +175,8 @@ def main(argv=None):
                                                  int(r["idf_weighting"]), rust_f64(r[GOAL])))
     b = res["best"]
     none = b is None
+    if any(rules.values()):
+        print("Serving rules: %s" % ", ".join("%s=%d" % (n, v) if n == "history" else n for n, v in rules.items() if v))
     print("Best n_most_recent_sessions: %d" % (-1 if none else b["n_most_recent_sessions"]))
     print("Best neighborhood_size_k: %d" % (-1 if none else b["neighborhood_size_k"]))
     print("Best last_items_in_session: %d" % (-1 if none else b["last_items_in_session"]))

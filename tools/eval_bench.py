@@ -3,6 +3,12 @@
 core -- in C++ (tools/eval_host_path.cpp, c); then a 24-trial grid in one srn_evaluate call.  Writes one JSON file.
 
     python tools/eval_bench.py [--config cfg3] [--queries 1048576] [--reps 3] [--out profiles/eval_bench_cfg3.json]
+
+--serving: what the serving rules cost.  Four trials alternate in one process, --reps rounds: the plain trial at how_many 21, the plain trial at
+how_many 21 + H' (the launch sequence of an excluding trial without its filter and expansion), exclude_seen at 21 with history H', and the same with handler_sessions.
+A library without the serving rules runs the two plain arms only, so the same file measures the commit before them.  Writes profiles/eval_serving_<config>.json.
+
+    python tools/eval_bench.py --serving [--history 8] [--reps 5]
 """
 import argparse
 import ctypes as C
@@ -32,6 +38,38 @@ def host_path_lib():
     return L
 
 
+def serving_arms(a, es, trial, res):
+    from serenade_amd import capi, evaluation
+    H = a.history
+    arms = {"plain_21": dict(trial), "plain_21_plus_H": dict(trial, how_many=trial["how_many"] + H)}
+    if hasattr(capi, "FLAG_EVAL_HANDLER"):
+        arms["exclude_seen"] = dict(trial, exclude_seen=True, history=H)
+        arms["exclude_seen_handler"] = dict(trial, exclude_seen=True, history=H, handler_sessions=True)
+    out = {n: {"wall_ms": [], "ms_predict": [], "ms_eval": []} for n in arms}
+    for n, t in arms.items():   # first calls size the workspaces
+        evaluation.evaluate(es, [t])
+    for _ in range(a.reps):
+        for n, t in arms.items():
+            t0 = time.perf_counter()
+            rep = evaluation.evaluate(es, [t])[0]
+            out[n]["wall_ms"].append((time.perf_counter() - t0) * 1e3)
+            out[n]["ms_predict"].append(rep["ms_predict"])
+            out[n]["ms_eval"].append(rep["ms_eval"])
+            out[n]["Mrr@20"], out[n]["HitRate@20"] = rep["Mrr@20"], rep["HitRate@20"]
+    for n in arms:
+        w = out[n]["wall_ms"]
+        out[n]["wall_ms_min"], out[n]["wall_ms_max"] = min(w), max(w)
+    res.update({"history": H, "reps": a.reps, "serving_rules": hasattr(capi, "FLAG_EVAL_HANDLER"), "arms": out})
+    if "exclude_seen" in out:
+        base = out["plain_21_plus_H"]["wall_ms_min"]
+        res["exclude_seen_over_plain_21_plus_H"] = round(out["exclude_seen"]["wall_ms_min"] / base, 4)
+        res["exclude_seen_handler_over_plain_21_plus_H"] = round(out["exclude_seen_handler"]["wall_ms_min"] / base, 4)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="cfg3")
@@ -40,8 +78,12 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--skip-host", action="store_true", help="leave out (c)")
     ap.add_argument("--grid", type=int, default=1, help="0: leave out the 24-trial call")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "eval_bench_cfg3.json"))
+    ap.add_argument("--out", default=None, help="default: profiles/eval_bench_cfg3.json, with --serving profiles/eval_serving_<config>.json")
+    ap.add_argument("--serving", action="store_true", help="the serving-rule arms instead of (a), (b), (c) and the grid")
+    ap.add_argument("--history", type=int, default=8, help="--serving: H' (>= --window)")
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "eval_serving_%s.json" % a.config if a.serving else "eval_bench_cfg3.json")
     import torch
     import serenade_amd as sa
     from serenade_amd import capi, evaluation, synth
@@ -67,6 +109,10 @@ def main():
     trial = dict(k=k, m=m, max_items_in_session=W, how_many=how_many, length=length)
     res = {"config": a.config, "k": k, "m": m, "window": W, "how_many": how_many, "length": length, "test_sessions": len(sessions), "queries": nq,
            "index_build_s": round(t_index, 2), "eval_set_create_s": round(t_set, 3)}
+
+    if a.serving:
+        serving_arms(a, es, trial, res)
+        return
 
     # (a) srn_evaluate, one trial per call
     evaluation.evaluate(es, [trial])
