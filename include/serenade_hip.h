@@ -637,6 +637,70 @@ int srn_recommend_batch(const srn_index_t* idx, srn_device_sessions_t* store, co
                         const uint8_t* consent, size_t n, uint64_t now_secs, size_t max_items_in_session, size_t k, size_t m, size_t how_many,
                         unsigned flags, uint64_t* out_ids, double* out_scores, uint32_t* out_counts);
 
+/* ---- click feedback: served rows scored against the visitor's next click, on the device (srn_feedback.hip) ----
+ * A click feedback log keeps, per visitor, the last row served to it: key (128 bit) -> (ids[0 .. c), n_model, epoch).  It is an object of its own, beside the session
+ * store.  srn_feedback_observe* takes a batch of requests and the rows just served to them (the arrays of a srn_recommend_batch* call and its outputs) and gives what
+ * handling the requests one after the other, j = 0 .. n-1, with one `now` gives:
+ *   no consent                           rank[j] = SRN_FEEDBACK_NONE; nothing is read or stored               (counted as no_consent)
+ *   consent, no entry for the key        rank[j] = SRN_FEEDBACK_NONE                                          (first_seen)
+ *   consent, the entry fails the idle rule (now > epoch and now - epoch > idle_secs, the session store's test): rank[j] = SRN_FEEDBACK_NONE   (idle_expired)
+ *   otherwise the request is OBSERVED:   r = the 1-based position of item_ids[j] among the entry's c ids, 0 if it is not there; rank[j] = r, with SRN_FEEDBACK_FILLED
+ *                                        or-ed in when r > n_model; observed += 1 and, for r > 0, hits_model[r] += 1 (r <= n_model) or hits_filled[r] += 1
+ *   then, for every consenting request, the row is stored: c = counts[j] (0xFFFFFFFF -- not served -- is stored as 0; a count above how_many is read as how_many),
+ *                                        ids = ids[j * how_many .. + c), n_model = the number of those c entries whose score is finite (filled entries score -inf,
+ *                                        DESIGN.md 4.9; c without scores), epoch = now                      (stored)
+ * An empty stored row makes the next click an observed miss (the evaluator counts an empty row: qty += 1).  Positions >= c of a row are never read, the id 0 is an id
+ * like any other, and keys are compared by all 128 bits.  Replaying a test set through srn_recommend_batch* and this call reproduces the Mrr and HitRate terms of
+ * srn_evaluate (SRN_FLAG_EVAL_HANDLER, length = how_many) request by request: 1 / r and 1, or 0 and 0.
+ * Everything is integer work on the caller's stream with no host round trip; ranks and counters are the same from run to run and for any cut of the requests into calls.
+ *   capacity   visitors the log can hold; the table has at least 2 * capacity slots (a power of two, linear probing, no tombstones).  The capacity rule is the session
+ *              store's: the host adds n to an upper bound per call; only a call that would pass `capacity` waits for the device, counts, and -- if dropping the
+ *              entries older than ttl_secs makes the room -- sweeps; otherwise SRN_ENOMEM with the log as it was.  No growth.
+ *   row_cap    ids a stored row may have (1..SRN_MAX_HOW_MANY).  A slot is 40 + 8 * row_cap bytes rounded up to 128.  One table is allocated; a sweep allocates the
+ *              second one, rebuilds into it and frees the first.
+ *   ttl_secs / idle_secs: as srn_device_sessions_create (0 = 30 / 20 minutes; ttl_secs < idle_secs: SRN_EINVAL).
+ * Calls on one log are serialised by the library (a mutex for the enqueue, an event between consecutive calls); the caller puts observe on the stream that produced
+ * the rows.  Errors are raised before anything changes: NULL log or arrays SRN_EINVAL; n = 0 SRN_OK; n > 2^24 SRN_ERANGE; how_many 0 SRN_EINVAL, above row_cap SRN_ERANGE;
+ * no such GPU SRN_ENODEV. */
+#define SRN_FEEDBACK_NONE 0xFFFFFFFFu
+#define SRN_FEEDBACK_FILLED 0x80000000u
+typedef struct srn_feedback srn_feedback_t;
+typedef struct {
+    uint64_t capacity, slots, row_cap, slot_bytes;
+    uint64_t live_bound;        /* the host's upper bound of the occupied slots */
+    uint64_t sweeps, refused;   /* rebuilds that dropped old entries (explicit or automatic) | calls refused with SRN_ENOMEM for capacity */
+    uint64_t ttl_secs, idle_secs;
+    /* since creation or srn_feedback_reset_counters: requests = no_consent + first_seen + idle_expired + observed; hits_* = the sum of the histogram's bins */
+    uint64_t requests, no_consent, first_seen, idle_expired, observed, hits_model, hits_filled;
+    uint64_t stored;            /* rows stored: the consenting requests */
+} srn_feedback_stats_t;
+int srn_feedback_create(int device, size_t capacity, size_t row_cap, uint64_t ttl_secs, uint64_t idle_secs, srn_feedback_t** out);
+void srn_feedback_free(srn_feedback_t* f);
+/* Device buffers on the log's GPU, enqueued on `stream` (a hipStream_t) without host synchronisation.  d_consent: one byte per request, NULL = every request consents.
+ * d_ids[n * how_many] / d_scores (may be NULL) / d_counts[n]: the rows served to the requests, how_many the row stride.  d_out_rank[n] (may be NULL: counters only).
+ * now_secs = 0: the system clock, read once. */
+int srn_feedback_observe_device(srn_feedback_t* f, const uint64_t* d_key_hi, const uint64_t* d_key_lo, const uint64_t* d_item_ids, const uint8_t* d_consent, size_t n,
+                                uint64_t now_secs, const uint64_t* d_ids, const double* d_scores, const uint32_t* d_counts, size_t how_many, uint32_t* d_out_rank,
+                                void* stream);
+/* The same with host pointers (pageable allowed); blocks. */
+int srn_feedback_observe(srn_feedback_t* f, const uint64_t* key_hi, const uint64_t* key_lo, const uint64_t* item_ids, const uint8_t* consent, size_t n,
+                         uint64_t now_secs, const uint64_t* ids, const double* scores, const uint32_t* counts, size_t how_many, uint32_t* out_rank);
+/* geometry and counters; waits for the log's kernels.  SRN_ESTATE, with *out filled in, if a batch ever found the table full -- rows were dropped; the capacity
+ * rule excludes it (srn_feedback_sweep reports the same) */
+int srn_feedback_stats(srn_feedback_t* f, srn_feedback_stats_t* out);
+/* hits by rank: hits_model[r] / hits_filled[r] for r = 1 .. row_cap ([0] is unused and 0; either array may be NULL).  cap = entries per array, at least row_cap + 1
+ * (below: SRN_ERANGE); entries beyond row_cap are written as 0.  Blocks. */
+int srn_feedback_histogram(srn_feedback_t* f, uint64_t* hits_model, uint64_t* hits_filled, size_t cap);
+/* every counter and both histograms back to 0, behind the log's previous call; the table is untouched */
+int srn_feedback_reset_counters(srn_feedback_t* f);
+/* drops the entries older than ttl_secs at now_secs (a rebuild); *n_live (may be NULL) = entries kept.  No device memory for the second table: SRN_ENOMEM, the log as it
+ * was.  Blocks. */
+int srn_feedback_sweep(srn_feedback_t* f, uint64_t now_secs, uint64_t* n_live);
+/* (test aid, blocks) one key's entry as a request at now_secs would read it: *out_count = c and the first c of out_ids (cap < c: SRN_ERANGE), *out_n_model, *out_epoch;
+ * *out_count = SRN_FEEDBACK_NONE for a key the log does not hold or whose entry fails the idle rule at now_secs (now_secs = 1: whatever is stored; 0: the clock). */
+int srn_feedback_get(srn_feedback_t* f, uint64_t key_hi, uint64_t key_lo, uint64_t now_secs, uint64_t* out_ids, size_t cap, uint32_t* out_count, uint32_t* out_n_model,
+                     uint64_t* out_epoch);
+
 /* ---- offline evaluation: test sets and hyper-parameter trials ----------------------------------------------------------
  * The reference's evaluation loop (src/bin/evaluator.rs:46-76, src/objective.rs:8-52) on the GPU: every prefix of every test session is
  * predicted and scored against the rest of its session, and the eight metrics of src/metrics/evaluation_reporter.rs come back.  Prefixes,

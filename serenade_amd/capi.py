@@ -85,6 +85,14 @@ class DeviceSessionsFileInfo(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("version", "n", "longest_session", "items_stride", "capacity", "items_cap", "ttl_secs", "idle_secs", "saved_at_secs", "payload_bytes")]
 
 
+FEEDBACK_NONE, FEEDBACK_FILLED = 0xFFFFFFFF, 0x80000000
+
+
+class FeedbackStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("capacity", "slots", "row_cap", "slot_bytes", "live_bound", "sweeps", "refused", "ttl_secs", "idle_secs",
+                                          "requests", "no_consent", "first_seen", "idle_expired", "observed", "hits_model", "hits_filled", "stored")]
+
+
 class ResultCacheStats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("rows", "ways", "bytes")] + [(n, C.c_uint32) for n in ("max_len", "k", "m", "how_many", "flags", "reserved")] + \
                [(n, C.c_uint64) for n in ("lookups", "hits", "inserts", "evictions", "bypassed_calls", "clears")]
@@ -214,6 +222,15 @@ SYMBOLS = {
     "srn_recommend_batch_device": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _u64, _sz, _sz, _sz, _sz, C.c_uint, _vp, _vp, _vp, _vp]),
     "srn_recommend_batch": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _u64, _sz, _sz, _sz, _sz, C.c_uint, _vp, _vp, _vp]),
     "srn_debug_device_sessions_last_batch": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_sz), C.POINTER(_sz), _vp, _sz, _vp]),
+    "srn_feedback_create": (_i, [_i, _sz, _sz, _u64, _u64, C.POINTER(_vp)]),
+    "srn_feedback_free": (None, [_vp]),
+    "srn_feedback_observe_device": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _u64, _vp, _vp, _vp, _sz, _vp, _vp]),
+    "srn_feedback_observe": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _u64, _vp, _vp, _vp, _sz, _vp]),
+    "srn_feedback_stats": (_i, [_vp, C.POINTER(FeedbackStats)]),
+    "srn_feedback_histogram": (_i, [_vp, _vp, _vp, _sz]),
+    "srn_feedback_reset_counters": (_i, [_vp]),
+    "srn_feedback_sweep": (_i, [_vp, _u64, C.POINTER(_u64)]),
+    "srn_feedback_get": (_i, [_vp, _u64, _u64, _u64, _vp, _sz, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(_u64)]),
     "srn_device_count": (_i, [C.POINTER(_i)]),
     "srn_limits": (None, [C.POINTER(Limits)]),
     "srn_last_error": (C.c_char_p, []),

@@ -900,4 +900,29 @@ int srn_recommend_batch(const srn_index_t* idx, srn_device_sessions_t* store, co
                                     out_ids, out_scores, out_counts); });
 }
 
+// ---- click feedback log (srn_feedback.hip) ----
+int srn_feedback_create(int device, size_t capacity, size_t row_cap, uint64_t ttl_secs, uint64_t idle_secs, srn_feedback_t** out) {
+    return guarded([&]() -> int { return fb_create(device, capacity, row_cap, ttl_secs, idle_secs, out); });
+}
+void srn_feedback_free(srn_feedback_t* f) { fb_free(f); }
+int srn_feedback_observe_device(srn_feedback_t* f, const uint64_t* d_key_hi, const uint64_t* d_key_lo, const uint64_t* d_item_ids, const uint8_t* d_consent, size_t n,
+                                uint64_t now_secs, const uint64_t* d_ids, const double* d_scores, const uint32_t* d_counts, size_t how_many, uint32_t* d_out_rank,
+                                void* stream) {
+    return guarded([&]() -> int { return fb_observe_device(f, d_key_hi, d_key_lo, d_item_ids, d_consent, n, now_secs, d_ids, d_scores, d_counts, how_many, d_out_rank, stream); });
+}
+int srn_feedback_observe(srn_feedback_t* f, const uint64_t* key_hi, const uint64_t* key_lo, const uint64_t* item_ids, const uint8_t* consent, size_t n,
+                         uint64_t now_secs, const uint64_t* ids, const double* scores, const uint32_t* counts, size_t how_many, uint32_t* out_rank) {
+    return guarded([&]() -> int { return fb_observe_host(f, key_hi, key_lo, item_ids, consent, n, now_secs, ids, scores, counts, how_many, out_rank); });
+}
+int srn_feedback_stats(srn_feedback_t* f, srn_feedback_stats_t* out) { return guarded([&]() -> int { return fb_stats(f, out); }); }
+int srn_feedback_histogram(srn_feedback_t* f, uint64_t* hits_model, uint64_t* hits_filled, size_t cap) {
+    return guarded([&]() -> int { return fb_histogram(f, hits_model, hits_filled, cap); });
+}
+int srn_feedback_reset_counters(srn_feedback_t* f) { return guarded([&]() -> int { return fb_reset_counters(f); }); }
+int srn_feedback_sweep(srn_feedback_t* f, uint64_t now_secs, uint64_t* n_live) { return guarded([&]() -> int { return fb_sweep(f, now_secs, n_live); }); }
+int srn_feedback_get(srn_feedback_t* f, uint64_t key_hi, uint64_t key_lo, uint64_t now_secs, uint64_t* out_ids, size_t cap, uint32_t* out_count, uint32_t* out_n_model,
+                     uint64_t* out_epoch) {
+    return guarded([&]() -> int { return fb_get(f, key_hi, key_lo, now_secs, out_ids, cap, out_count, out_n_model, out_epoch); });
+}
+
 }  // extern "C"

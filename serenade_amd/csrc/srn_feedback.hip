@@ -1,0 +1,558 @@
+// Click feedback log: the last row served to every visitor, scored against the visitor's next click (include/serenade_hip.h, "click feedback").
+//
+// The rule, request by request, is serving.feedback_model's; the device gives the same ranks and counters for a whole batch, on the caller's stream, nothing read back.
+//
+// The table: power-of-two open addressing, linear probing, load <= 0.5, no tombstones, an object of its own beside the session store.  One slot per visitor:
+//   { key_hi u64 | key_lo u64 | epoch u64 | count u32 | state u32 | n_model u32 | pad u32 | ids u64[row_cap] }   rounded up to a multiple of 128 bytes, 128-byte aligned
+// (row_cap <= 11: one 128-byte line).  state: 0 empty, 1 occupied, 2 claimed by the find kernel of the running call.  One table stands; a sweep allocates the second
+// one, rebuilds the entries not older than the TTL into it and frees the first.
+//
+// A batch:
+//   sort       request indices, stable LSD passes by key_lo, key_hi, then the consent bit (the session store's order): the consenting requests of one visitor become
+//              one contiguous RUN in request order
+//   fb_find    one lane per run head: find-or-insert the slot by the store's claim protocol -- CAS empty -> claimed; two heads never hold the same key, so a claimed slot
+//              is never "mine" and the loser of a claim probes on: nobody waits for anybody.  Records the slot and whether the stored entry is new, idle or live
+//   max scan   of the heads' positions: every position's run start
+//   fb_rank    one lane group (8 lanes for rows of up to 8 ids, else 16) per request.  The prior row of a run head is its slot's, if live; of any other request the row
+//              served to the previous request of the run, n_model counted from that row's scores.  Lane l of the group takes positions l, l + lanes, ...; a ballot per
+//              round finds the match and counts the finite scores.  No lane leaves before the last ballot and the round count is the same across the wave.  The group's
+//              first lane writes out_rank and adds to a histogram in LDS; the workgroup then issues one 64-bit global atomic per non-zero bin.  The grid is capped at
+//              2048 workgroups, each taking every 2048th block of positions, so that a call of 2^20 requests ends in at most 2048 atomics per counter word, not 65536
+//   fb_store   behind fb_rank: the run's last request writes its row, count, n_model, epoch and state full, once (the same lane groups)
+// Integer work throughout: ranks, counters and the table's entries do not depend on the run or on how the requests are cut into calls.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include <rocprim/rocprim.hpp>
+
+#include "srn_internal.h"
+#include "srn_runtime.h"
+#include "srn_device.h"
+#include "srn_sessions_dev.h"   // Table, the slot states, idle_or_old, wall_secs
+#include "srn_hipsync.h"
+
+struct srn_feedback {
+    int device = 0;
+    uint64_t capacity = 0, n_slots = 0, row_cap = 0, ttl = 0, idle = 0;
+    uint32_t stride = 0;
+    char* table = nullptr;                                  // a sweep rebuilds into a second one, allocated for it
+    std::mutex mu;                                          // covers the enqueue of a call and everything below
+    hipEvent_t last = nullptr;                              // end of the most recent call, whatever stream it ran on
+    hipStream_t own = nullptr;                              // stats / get / sweep / reset and the host-pointer entry point
+    uint64_t bound = 0, sweeps = 0, refused = 0;            // bound: upper bound of the occupied slots
+    char* ws = nullptr; size_t ws_bytes = 0;                // per-batch scratch, grows with the largest n seen
+    char* small = nullptr;                                  // err word | occupied, live | one entry out
+    unsigned long long* ctr = nullptr;                      // the counters: 8 words, hits_model[row_cap + 1], hits_filled[row_cap + 1]
+    srn::Table tab() const { return srn::Table{table, (uint32_t)(n_slots - 1), stride}; }
+    uint32_t n_bins() const { return 8u + 2u * ((uint32_t)row_cap + 1u); }
+    uint32_t* err() const { return (uint32_t*)small; }
+    unsigned long long* counts() const { return (unsigned long long*)(small + 64); }
+    uint64_t* one() const { return (uint64_t*)(small + 128); }
+};
+
+namespace srn {
+
+namespace {
+constexpr uint32_t kTPB = 256;
+constexpr uint32_t kMaxBatch = 1u << 24;
+constexpr uint32_t kRankBlocks = 2048;          // fb_rank's grid at the most (256 CUs x 8 workgroups): each workgroup pays one global atomic per non-zero bin
+constexpr uint32_t kFbHead = 40;                // bytes before the ids
+struct FbSlot { uint64_t key_hi, key_lo, epoch; uint32_t count, state, n_model, pad; };
+static_assert(sizeof(FbSlot) == kFbHead, "slot header");
+// bins of the counters: the words of srn_feedback_stats_t in its order, then the two histograms
+enum : uint32_t { kRequests = 0, kNoConsent = 1, kFirstSeen = 2, kIdleExpired = 3, kObserved = 4, kHitsModel = 5, kHitsFilled = 6, kStored = 7, kHist = 8 };
+enum : uint32_t { kNew = 0, kIdle = 1, kLive = 2 };   // what fb_find saw in a head's slot
+
+__device__ __forceinline__ FbSlot* fb_slot(const Table& t, uint32_t s) { return (FbSlot*)(t.base + (size_t)s * t.stride); }
+__device__ __forceinline__ uint64_t* fb_ids(FbSlot* h) { return (uint64_t*)((char*)h + kFbHead); }
+__device__ __forceinline__ uint32_t key_hash(uint64_t hi, uint64_t lo) { return (uint32_t)dev_mix64(lo ^ dev_mix64(hi)); }
+__device__ __forceinline__ bool finite_bits(uint64_t b) { return ((b >> 52) & 0x7FFull) != 0x7FFull; }
+
+struct ObsArgs {
+    Table t;
+    const uint64_t* key_hi; const uint64_t* key_lo; const uint64_t* item; const uint8_t* consent;   // the caller's requests
+    const uint64_t* ids; const uint64_t* scores; const uint32_t* counts; uint32_t how_many;         // ... and rows (scores as bit patterns; may be null)
+    const uint32_t* order;   // [n] request index of each sorted position
+    uint32_t n, row_cap;
+    uint32_t lanes_shift;    // 2^lanes_shift adjacent lanes take one request
+    uint32_t rounds;         // ceil(row_cap / lanes): the same for every group
+    uint64_t now, idle;
+    uint32_t* slot_of;       // [n] by sorted position of a run head: its slot (kNone: table full -- cannot happen under the capacity rule)
+    uint32_t* status;        // [n] ... and kNew / kIdle / kLive
+    uint32_t* headpos;       // [n] p for a run head, 0 otherwise; inclusive max scan -> run_start
+    uint32_t* run_start;     // [n]
+    uint32_t* out_rank;      // [n] by REQUEST index (may be null)
+    unsigned long long* ctr;
+    uint32_t* err;
+};
+__device__ __forceinline__ bool consents(const ObsArgs& a, uint32_t req) { return a.consent == nullptr || a.consent[req] != 0; }
+// the row served to request req: its length as it is stored
+__device__ __forceinline__ uint32_t served_count(const ObsArgs& a, uint32_t req) { const uint32_t c = a.counts[req]; return c == SRN_FEEDBACK_NONE ? 0u : min(c, a.how_many); }
+
+__global__ void __launch_bounds__(kTPB) fb_keys_init(const uint64_t* __restrict__ lo, uint32_t n, uint64_t* __restrict__ key, uint32_t* __restrict__ idx) {
+    const uint32_t i = blockIdx.x * kTPB + threadIdx.x;
+    if (i < n) { key[i] = lo[i]; idx[i] = i; }
+}
+__global__ void __launch_bounds__(kTPB) fb_keys_gather(const uint64_t* __restrict__ src, const uint32_t* __restrict__ idx, uint32_t n, uint64_t* __restrict__ key) {
+    const uint32_t i = blockIdx.x * kTPB + threadIdx.x;
+    if (i < n) key[i] = src[idx[i]];
+}
+__global__ void __launch_bounds__(kTPB) fb_keys_consent(const uint8_t* __restrict__ consent, const uint32_t* __restrict__ idx, uint32_t n, uint64_t* __restrict__ key) {
+    const uint32_t i = blockIdx.x * kTPB + threadIdx.x;
+    if (i < n) key[i] = consent[idx[i]] ? 0ull : 1ull;
+}
+
+__global__ void __launch_bounds__(kTPB) fb_find(ObsArgs a) {
+    const uint32_t p = blockIdx.x * kTPB + threadIdx.x;
+    if (p >= a.n) return;
+    const uint32_t req = a.order[p];
+    a.headpos[p] = 0;
+    if (!consents(a, req)) return;
+    const uint64_t hi = a.key_hi[req], lo = a.key_lo[req];
+    if (p) {
+        const uint32_t pr = a.order[p - 1];
+        if (consents(a, pr) && a.key_hi[pr] == hi && a.key_lo[pr] == lo) return;   // not a head
+    }
+    // find-or-insert: a slot claimed during this kernel belongs to another key
+    uint32_t h = key_hash(hi, lo) & a.t.mask, found = kNone, status = kNew;
+    for (uint32_t probes = 0; probes <= a.t.mask; ++probes, h = (h + 1) & a.t.mask) {
+        FbSlot* s = fb_slot(a.t, h);
+        uint32_t st = __hip_atomic_load(&s->state, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (st == kEmpty) {
+            st = atomicCAS(&s->state, kEmpty, kClaimed);
+            if (st == kEmpty) { s->key_hi = hi; s->key_lo = lo; s->epoch = 0; s->count = 0; s->n_model = 0; found = h; break; }
+        }
+        if (st == kFull && s->key_hi == hi && s->key_lo == lo) {
+            found = h;
+            status = idle_or_old(a.now, s->epoch, a.idle) ? kIdle : kLive;
+            break;
+        }
+    }
+    if (found == kNone) atomicOr(a.err, 1u);
+    a.slot_of[p] = found; a.status[p] = status; a.headpos[p] = p;
+}
+
+// No lane leaves early and the round count is the same across the wave: the ballots need all 64 lanes.  Dynamic LDS: one u32 per bin.
+__global__ void __launch_bounds__(kTPB) fb_rank(ObsArgs a) {
+    extern __shared__ uint32_t bins[];
+    const uint32_t n_bins = kHist + 2u * (a.row_cap + 1u);
+    for (uint32_t i = threadIdx.x; i < n_bins; i += kTPB) bins[i] = 0;
+    __syncthreads();
+    const uint32_t lanes = 1u << a.lanes_shift, lane = threadIdx.x & (lanes - 1);
+    const uint32_t gbase = (threadIdx.x & 63u) & ~(lanes - 1);   // the group's first lane in the wave
+    const uint32_t gmask = (1u << lanes) - 1u;                   // lanes <= 16
+    // the grid is capped (kRankBlocks): a workgroup takes the positions g, g + groups, ... and flushes its histogram once.  Every group makes the same number of trips
+    const uint64_t groups = (uint64_t)gridDim.x * (kTPB >> a.lanes_shift);
+    const uint32_t trips = (uint32_t)((a.n + groups - 1) / groups);
+    for (uint32_t trip = 0; trip < trips; ++trip) {
+        const uint64_t p = trip * groups + (uint64_t)blockIdx.x * (kTPB >> a.lanes_shift) + (threadIdx.x >> a.lanes_shift);
+        uint32_t kind = kRequests;                                   // (no request: nothing is counted)
+        uint32_t req = 0, c = 0, n_model = 0;                        // c = 0: no position is ever read
+        const uint64_t* row = nullptr; const uint64_t* sc = nullptr;
+        uint64_t item = 0;
+        if (p < a.n) {
+            req = a.order[p];
+            if (!consents(a, req)) kind = kNoConsent;
+            else {
+                const uint64_t hi = a.key_hi[req], lo = a.key_lo[req];
+                item = a.item[req];
+                bool head = p == 0;
+                uint32_t pr = 0;
+                if (!head) { pr = a.order[p - 1]; head = !consents(a, pr) || a.key_hi[pr] != hi || a.key_lo[pr] != lo; }
+                if (head) {
+                    const uint32_t st = a.status[p], slot = a.slot_of[p];
+                    kind = st == kLive ? kObserved : st == kIdle ? kIdleExpired : kFirstSeen;
+                    if (st == kLive && slot != kNone) { FbSlot* s = fb_slot(a.t, slot); c = min(s->count, a.row_cap); n_model = s->n_model; row = fb_ids(s); }
+                } else {   // the row served to the previous request of the run
+                    kind = kObserved;
+                    c = served_count(a, pr); n_model = c;
+                    row = a.ids + (size_t)pr * a.how_many;
+                    if (a.scores) sc = a.scores + (size_t)pr * a.how_many;
+                }
+            }
+        }
+        uint32_t found = 0, fin = 0;                                 // the same in every lane of the group
+        for (uint32_t r = 0; r < a.rounds; ++r) {
+            const uint32_t i = (r << a.lanes_shift) + lane;
+            const bool in = i < c;
+            const bool match = in && row[i] == item;
+            const bool finite = in && sc && finite_bits(sc[i]);
+            const uint32_t mm = (uint32_t)(__ballot(match) >> gbase) & gmask, mf = (uint32_t)(__ballot(finite) >> gbase) & gmask;
+            if (!found && mm) found = (r << a.lanes_shift) + (uint32_t)__ffs((int)mm);
+            fin += __popc(mf);
+        }
+        if (sc) n_model = fin;
+        if (kind != kRequests && lane == 0) {
+            uint32_t rank = SRN_FEEDBACK_NONE;
+            atomicAdd(&bins[kRequests], 1u);
+            atomicAdd(&bins[kind], 1u);
+            if (kind != kNoConsent) atomicAdd(&bins[kStored], 1u);
+            if (kind == kObserved) {
+                const bool filled = found > n_model;
+                rank = found | (filled ? SRN_FEEDBACK_FILLED : 0u);
+                if (found) { atomicAdd(&bins[filled ? kHitsFilled : kHitsModel], 1u); atomicAdd(&bins[kHist + (filled ? a.row_cap + 1u : 0u) + found], 1u); }   // found <= c <= row_cap
+            }
+            if (a.out_rank) a.out_rank[req] = rank;
+        }
+    }
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < n_bins; i += kTPB) { const uint32_t v = bins[i]; if (v) atomicAdd(&a.ctr[i], (unsigned long long)v); }
+}
+
+// the run's last request writes the row it was served: the same lane groups, lane l the positions l, l + lanes, ...
+__global__ void __launch_bounds__(kTPB) fb_store(ObsArgs a) {
+    const uint64_t tid = (uint64_t)blockIdx.x * kTPB + threadIdx.x;
+    const uint64_t p = tid >> a.lanes_shift;
+    const uint32_t lanes = 1u << a.lanes_shift, lane = (uint32_t)tid & (lanes - 1);
+    const uint32_t gbase = (threadIdx.x & 63u) & ~(lanes - 1), gmask = (1u << lanes) - 1u;
+    FbSlot* s = nullptr;
+    uint32_t c = 0;
+    const uint64_t* row = nullptr; const uint64_t* sc = nullptr;
+    if (p < a.n) {
+        const uint32_t req = a.order[p];
+        bool last = consents(a, req);
+        if (last && p + 1 < a.n) {
+            const uint32_t nx = a.order[p + 1];
+            last = !(consents(a, nx) && a.key_hi[nx] == a.key_hi[req] && a.key_lo[nx] == a.key_lo[req]);
+        }
+        const uint32_t slot = last ? a.slot_of[a.run_start[p]] : kNone;
+        if (slot != kNone) {
+            s = fb_slot(a.t, slot);
+            c = served_count(a, req);                            // <= how_many <= row_cap
+            row = a.ids + (size_t)req * a.how_many;
+            if (a.scores) sc = a.scores + (size_t)req * a.how_many;
+        }
+    }
+    uint64_t* dst = s ? fb_ids(s) : nullptr;
+    uint32_t fin = 0;
+    for (uint32_t r = 0; r < a.rounds; ++r) {
+        const uint32_t i = (r << a.lanes_shift) + lane;
+        const bool in = i < c;
+        if (in) dst[i] = row[i];
+        const bool finite = in && sc && finite_bits(sc[i]);
+        fin += __popc((uint32_t)(__ballot(finite) >> gbase) & gmask);
+    }
+    if (s && lane == 0) { s->count = c; s->n_model = sc ? fin : c; s->epoch = a.now; s->state = kFull; }
+}
+
+// ---- one key, from the host: out[0] = count (~0: unknown key), out[1] = epoch, out[2] = n_model, out[3..] = ids ----
+__global__ void fb_get_one(Table t, uint64_t hi, uint64_t lo, uint32_t row_cap, uint64_t* out) {
+    out[0] = ~0ull;
+    uint32_t h = key_hash(hi, lo) & t.mask;
+    for (uint32_t probes = 0; probes <= t.mask; ++probes, h = (h + 1) & t.mask) {
+        FbSlot* s = fb_slot(t, h);
+        if (s->state == kEmpty) return;
+        if (s->key_hi == hi && s->key_lo == lo) {
+            const uint32_t c = min(s->count, row_cap);
+            out[0] = c; out[1] = s->epoch; out[2] = s->n_model;
+            for (uint32_t i = 0; i < c; ++i) out[3 + i] = fb_ids(s)[i];
+            return;
+        }
+    }
+}
+// counters[0] = occupied slots, [1] = entries a sweep at `now` keeps
+__global__ void __launch_bounds__(kTPB) fb_count(Table t, uint64_t now, uint64_t ttl, unsigned long long* counters) {
+    const uint32_t i = blockIdx.x * kTPB + threadIdx.x;
+    bool occ = false, live = false;
+    if (i <= t.mask) { const FbSlot* s = fb_slot(t, i); occ = s->state != kEmpty; live = occ && !idle_or_old(now, s->epoch, ttl); }
+    const unsigned long long mo = __ballot(occ), ml = __ballot(live);
+    if ((threadIdx.x & 63) == 0) { if (mo) atomicAdd(&counters[0], (unsigned long long)__popcll(mo)); if (ml) atomicAdd(&counters[1], (unsigned long long)__popcll(ml)); }
+}
+// the entries a sweep keeps, into the cleared table `to` (every key once: a taken slot is another key's)
+__global__ void __launch_bounds__(kTPB) fb_rebuild(Table from, Table to, uint64_t now, uint64_t ttl, uint32_t row_cap) {
+    const uint32_t i = blockIdx.x * kTPB + threadIdx.x;
+    if (i > from.mask) return;
+    FbSlot* s = fb_slot(from, i);
+    if (s->state == kEmpty || idle_or_old(now, s->epoch, ttl)) return;
+    uint32_t h = key_hash(s->key_hi, s->key_lo) & to.mask;
+    for (uint32_t probes = 0; probes <= to.mask; ++probes, h = (h + 1) & to.mask) {
+        FbSlot* d = fb_slot(to, h);
+        if (atomicCAS(&d->state, kEmpty, kFull) != kEmpty) continue;
+        const uint32_t c = min(s->count, row_cap);
+        d->key_hi = s->key_hi; d->key_lo = s->key_lo; d->epoch = s->epoch; d->count = c; d->n_model = s->n_model;
+        for (uint32_t j = 0; j < c; ++j) fb_ids(d)[j] = fb_ids(s)[j];
+        return;
+    }
+}
+
+size_t align256(size_t b) { return (b + 255) / 256 * 256; }
+dim3 grid_for(size_t n) { return dim3((unsigned)((n + kTPB - 1) / kTPB)); }
+
+// behind everything enqueued on the log so far, on its own stream (mu held)
+int own_after_last(srn_feedback* f) { HIP_TRY(hipSetDevice(f->device)); HIP_TRY(hipStreamWaitEvent(f->own, f->last, 0)); return SRN_OK; }
+
+int count(srn_feedback* f, uint64_t now, uint64_t* occupied, uint64_t* live) {   // blocks (own stream, mu held)
+    HIP_TRY(hipMemsetAsync(f->counts(), 0, 16, f->own));
+    fb_count<<<grid_for(f->n_slots), kTPB, 0, f->own>>>(f->tab(), now, f->ttl, f->counts());
+    HIP_TRY(hipGetLastError());
+    unsigned long long c[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(c, f->counts(), 16, hipMemcpyDeviceToHost, f->own));
+    HIP_TRY(hipStreamSynchronize(f->own));
+    *occupied = c[0]; *live = c[1];
+    return SRN_OK;
+}
+// The entries not older than the TTL into a second table, allocated here; the first one is freed (own stream, mu held, behind `last`; blocks).  A failure leaves the log as it was.
+int rebuild(srn_feedback* f, uint64_t now) {
+    const size_t bytes = (size_t)f->n_slots * f->stride;
+    char* nt = nullptr;
+    if (hipMalloc((void**)&nt, bytes) != hipSuccess) { (void)hipGetLastError(); return fail(SRN_ENOMEM, "click feedback log: no device memory for the sweep's second table"); }
+    const Table from = f->tab(); Table to = from; to.base = nt;
+    hipError_t e = hipMemsetAsync(nt, 0, bytes, f->own);
+    if (e == hipSuccess) { fb_rebuild<<<grid_for(f->n_slots), kTPB, 0, f->own>>>(from, to, now, f->ttl, (uint32_t)f->row_cap); e = hipGetLastError(); }
+    if (e == hipSuccess) e = hipStreamSynchronize(f->own);
+    if (e != hipSuccess) { (void)hipFree(nt); return fail(SRN_EHIP, std::string("click feedback log (sweep): ") + hipGetErrorString(e)); }
+    (void)hipFree(f->table);
+    f->table = nt; ++f->sweeps;
+    return SRN_OK;
+}
+// The capacity rule (mu held): room for n more keys, or SRN_ENOMEM with the table as it was.  Only when the host's bound does not fit does anything wait for the device:
+// the exact counts replace the bound, and entries older than the TTL are dropped (a rebuild) if that makes the room.
+int make_room(srn_feedback* f, uint64_t n, uint64_t now) {
+    if (f->bound + n <= f->capacity) return SRN_OK;
+    int rc = own_after_last(f); if (rc) return rc;
+    uint64_t occupied = 0, live = 0;
+    if ((rc = count(f, now, &occupied, &live))) return rc;
+    f->bound = occupied;
+    if (occupied + n <= f->capacity) return SRN_OK;
+    if (live + n > f->capacity) {
+        ++f->refused;
+        return fail(SRN_ENOMEM, "click feedback log: the batch does not fit the log's capacity (live entries + batch > capacity)");
+    }
+    if ((rc = rebuild(f, now))) return rc;
+    f->bound = live;
+    return SRN_OK;
+}
+struct DevBuf {   // a blocking call's own device copies
+    char* p = nullptr;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+    int alloc(size_t bytes, const char* who) {
+        if (hipMalloc((void**)&p, bytes ? bytes : 256) != hipSuccess) { (void)hipGetLastError(); p = nullptr; return fail(SRN_ENOMEM, std::string(who) + ": no device memory for the staging copies"); }
+        return SRN_OK;
+    }
+};
+}  // namespace
+
+void fb_free(srn_feedback* f) {
+    if (!f) return;
+    (void)hipSetDevice(f->device);
+    if (f->last) { (void)hipEventSynchronize(f->last); (void)hipEventDestroy(f->last); }
+    if (f->own) { (void)hipStreamSynchronize(f->own); (void)hipStreamDestroy(f->own); }
+    for (void* p : {(void*)f->table, (void*)f->ws, (void*)f->small, (void*)f->ctr}) if (p) (void)hipFree(p);
+    delete f;
+}
+
+int fb_create(int device, size_t capacity, size_t row_cap, uint64_t ttl_secs, uint64_t idle_secs, srn_feedback** out) {
+    if (!out) return fail(SRN_EINVAL, "srn_feedback_create: null output");
+    *out = nullptr;
+    if (capacity == 0) return fail(SRN_EINVAL, "srn_feedback_create: capacity must be > 0");
+    if (capacity > (1ull << 30)) return fail(SRN_ERANGE, "srn_feedback_create: capacity above 2^30 visitors");
+    if (row_cap == 0) return fail(SRN_EINVAL, "srn_feedback_create: row_cap must be > 0");
+    if (row_cap > SRN_MAX_HOW_MANY) return fail(SRN_ERANGE, "srn_feedback_create: row_cap above SRN_MAX_HOW_MANY");
+    const uint64_t ttl = ttl_secs ? ttl_secs : 30 * 60, idle = idle_secs ? idle_secs : 20 * 60;   // srn_device_sessions_create's defaults
+    if (ttl < idle) return fail(SRN_EINVAL, "srn_feedback_create: ttl_secs below idle_secs (a swept row could still have been read)");
+    int n_dev = 0;
+    if (device < 0 || hipGetDeviceCount(&n_dev) != hipSuccess || device >= n_dev) return fail(SRN_ENODEV, "srn_feedback_create: no such GPU");
+    HIP_TRY(hipSetDevice(device));
+    srn_feedback* f = new srn_feedback();
+    struct Guard { srn_feedback*& f; ~Guard() { if (f) fb_free(f); } } guard{f};
+    f->device = device; f->capacity = capacity; f->row_cap = row_cap; f->ttl = ttl; f->idle = idle;
+    f->n_slots = 2; while (f->n_slots < 2 * (uint64_t)capacity) f->n_slots <<= 1;
+    f->stride = (uint32_t)((kFbHead + 8 * row_cap + 127) / 128 * 128);
+    const size_t bytes = (size_t)f->n_slots * f->stride;
+    if (hipMalloc((void**)&f->table, bytes) != hipSuccess) { (void)hipGetLastError(); f->table = nullptr; return fail(SRN_ENOMEM, "srn_feedback_create: no device memory for the table"); }
+    HIP_TRY(hipMalloc((void**)&f->small, 128 + 8 * (3 + SRN_MAX_HOW_MANY)));
+    HIP_TRY(hipMalloc((void**)&f->ctr, 8 * (size_t)f->n_bins()));
+    HIP_TRY(hipStreamCreateWithFlags(&f->own, hipStreamNonBlocking));
+    HIP_TRY(hipEventCreateWithFlags(&f->last, hipEventDisableTiming));
+    HIP_TRY(hipMemsetAsync(f->table, 0, bytes, f->own));
+    HIP_TRY(hipMemsetAsync(f->small, 0, 128, f->own));
+    HIP_TRY(hipMemsetAsync(f->ctr, 0, 8 * (size_t)f->n_bins(), f->own));
+    HIP_TRY(hipStreamSynchronize(f->own));
+    *out = f; f = nullptr;
+    return SRN_OK;
+}
+
+int fb_observe_device(srn_feedback* f, const uint64_t* d_hi, const uint64_t* d_lo, const uint64_t* d_item, const uint8_t* d_consent, size_t n, uint64_t now_secs,
+                      const uint64_t* d_ids, const double* d_scores, const uint32_t* d_counts, size_t how_many, uint32_t* d_out_rank, void* stream) {
+    if (!f) return fail(SRN_EINVAL, "srn_feedback_observe: null log");
+    if (n == 0) return SRN_OK;
+    if (!d_hi || !d_lo || !d_item || !d_ids || !d_counts) return fail(SRN_EINVAL, "srn_feedback_observe: null buffer");
+    if (n > kMaxBatch) return fail(SRN_ERANGE, "srn_feedback_observe: more than 2^24 requests in one call");
+    if (how_many == 0) return fail(SRN_EINVAL, "srn_feedback_observe: how_many must be > 0");
+    if (how_many > f->row_cap) return fail(SRN_ERANGE, "srn_feedback_observe: how_many above the log's row_cap");
+    hipStream_t st = (hipStream_t)stream;
+    const uint64_t now = now_secs ? now_secs : wall_secs();
+    std::lock_guard<std::mutex> g(f->mu);
+    int rc = make_room(f, n, now); if (rc) return rc;
+    HIP_TRY(hipSetDevice(f->device));
+    // scratch: sort keys and indices (double-buffered), the per-position words, rocPRIM's temporary storage
+    size_t tmp = 0, t1 = 0;
+    HIP_TRY(rocprim::radix_sort_pairs(nullptr, t1, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, n, 0, 64, st)); tmp = std::max(tmp, t1);
+    HIP_TRY(rocprim::radix_sort_pairs(nullptr, t1, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, n, 0, 1, st)); tmp = std::max(tmp, t1);
+    HIP_TRY(rocprim::inclusive_scan(nullptr, t1, (uint32_t*)nullptr, (uint32_t*)nullptr, n, rocprim::maximum<uint32_t>(), st)); tmp = std::max(tmp, t1);
+    const size_t w = align256(n * 4);
+    const size_t o_keyA = 0, o_keyB = o_keyA + align256(n * 8), o_idxA = o_keyB + align256(n * 8), o_idxB = o_idxA + w, o_slot = o_idxB + w, o_stat = o_slot + w,
+                 o_head = o_stat + w, o_run = o_head + w, o_tmp = o_run + w, bytes = o_tmp + align256(tmp);
+    if (bytes > f->ws_bytes) {   // (the previous call may still read the scratch: wait for it before it is freed)
+        HIP_TRY(hipEventSynchronize(f->last));
+        if ((rc = ensure(&f->ws, &f->ws_bytes, bytes))) return rc;
+    }
+    HIP_TRY(hipStreamWaitEvent(st, f->last, 0));
+    char* b = f->ws;
+    uint64_t* keyA = (uint64_t*)(b + o_keyA); uint64_t* keyB = (uint64_t*)(b + o_keyB); uint32_t* idxA = (uint32_t*)(b + o_idxA); uint32_t* idxB = (uint32_t*)(b + o_idxB);
+    const dim3 gn = grid_for(n);
+    const uint32_t n32 = (uint32_t)n;
+    // stable LSD passes: key_lo, key_hi, then (where some request may not consent) the consent bit -- consenting requests first, each visitor's in request order
+    fb_keys_init<<<gn, kTPB, 0, st>>>(d_lo, n32, keyA, idxA);
+    t1 = tmp; HIP_TRY(rocprim::radix_sort_pairs(b + o_tmp, t1, keyA, keyB, idxA, idxB, n, 0, 64, st));
+    fb_keys_gather<<<gn, kTPB, 0, st>>>(d_hi, idxB, n32, keyA);
+    t1 = tmp; HIP_TRY(rocprim::radix_sort_pairs(b + o_tmp, t1, keyA, keyB, idxB, idxA, n, 0, 64, st));
+    const uint32_t* order = idxA;
+    if (d_consent) {
+        fb_keys_consent<<<gn, kTPB, 0, st>>>(d_consent, idxA, n32, keyA);
+        t1 = tmp; HIP_TRY(rocprim::radix_sort_pairs(b + o_tmp, t1, keyA, keyB, idxA, idxB, n, 0, 1, st));
+        order = idxB;
+    }
+    ObsArgs a{};
+    a.t = f->tab(); a.key_hi = d_hi; a.key_lo = d_lo; a.item = d_item; a.consent = d_consent;
+    a.ids = d_ids; a.scores = (const uint64_t*)d_scores; a.counts = d_counts; a.how_many = (uint32_t)how_many;
+    a.order = order; a.n = n32; a.row_cap = (uint32_t)f->row_cap;
+    a.lanes_shift = f->row_cap <= 8 ? 3 : 4;
+    a.rounds = (uint32_t)((f->row_cap + (1u << a.lanes_shift) - 1) >> a.lanes_shift);
+    a.now = now; a.idle = f->idle;
+    a.slot_of = (uint32_t*)(b + o_slot); a.status = (uint32_t*)(b + o_stat); a.headpos = (uint32_t*)(b + o_head); a.run_start = (uint32_t*)(b + o_run);
+    a.out_rank = d_out_rank; a.ctr = f->ctr; a.err = f->err();
+    const dim3 gg = grid_for(n << a.lanes_shift);   // (n <= 2^24: 2^28 lanes at the most)
+    fb_find<<<gn, kTPB, 0, st>>>(a);
+    t1 = tmp; HIP_TRY(rocprim::inclusive_scan(b + o_tmp, t1, a.headpos, a.run_start, n, rocprim::maximum<uint32_t>(), st));
+    fb_rank<<<dim3(std::min<unsigned>(gg.x, kRankBlocks)), kTPB, 4 * (size_t)f->n_bins(), st>>>(a);
+    fb_store<<<gg, kTPB, 0, st>>>(a);
+    HIP_TRY(hipGetLastError());
+    // from here on the log has changed: the next call is ordered behind this one
+    f->bound += n;
+    HIP_TRY(hipEventRecord(f->last, st));
+    return SRN_OK;
+}
+
+int fb_observe_host(srn_feedback* f, const uint64_t* hi, const uint64_t* lo, const uint64_t* item, const uint8_t* consent, size_t n, uint64_t now_secs,
+                    const uint64_t* ids, const double* scores, const uint32_t* counts, size_t how_many, uint32_t* out_rank) {
+    if (!f) return fail(SRN_EINVAL, "srn_feedback_observe: null log");
+    if (n == 0) return SRN_OK;
+    if (!hi || !lo || !item || !ids || !counts) return fail(SRN_EINVAL, "srn_feedback_observe: null buffer");
+    if (n > kMaxBatch) return fail(SRN_ERANGE, "srn_feedback_observe: more than 2^24 requests in one call");
+    if (how_many == 0) return fail(SRN_EINVAL, "srn_feedback_observe: how_many must be > 0");
+    if (how_many > f->row_cap) return fail(SRN_ERANGE, "srn_feedback_observe: how_many above the log's row_cap");
+    HIP_TRY(hipSetDevice(f->device));
+    const size_t rows = n * how_many * 8;
+    const size_t o_hi = 0, o_lo = o_hi + align256(n * 8), o_item = o_lo + align256(n * 8), o_con = o_item + align256(n * 8), o_ids = o_con + align256(n),
+                 o_sc = o_ids + align256(rows), o_cnt = o_sc + align256(rows), o_rank = o_cnt + align256(n * 4), bytes = o_rank + align256(n * 4);
+    DevBuf buf; int rc = buf.alloc(bytes, "srn_feedback_observe"); if (rc) return rc;
+    char* b = buf.p;
+    hipStream_t st = nullptr;   // a stream of this call's own: two host callers do not wait for each other's copies
+    HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    auto run = [&]() -> int {
+        HIP_TRY(hipMemcpyAsync(b + o_hi, hi, n * 8, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(b + o_lo, lo, n * 8, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(b + o_item, item, n * 8, hipMemcpyHostToDevice, st));
+        if (consent) HIP_TRY(hipMemcpyAsync(b + o_con, consent, n, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(b + o_ids, ids, rows, hipMemcpyHostToDevice, st));
+        if (scores) HIP_TRY(hipMemcpyAsync(b + o_sc, scores, rows, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(b + o_cnt, counts, n * 4, hipMemcpyHostToDevice, st));
+        int rc2 = fb_observe_device(f, (const uint64_t*)(b + o_hi), (const uint64_t*)(b + o_lo), (const uint64_t*)(b + o_item), consent ? (const uint8_t*)(b + o_con) : nullptr, n,
+                                    now_secs, (const uint64_t*)(b + o_ids), scores ? (const double*)(b + o_sc) : nullptr, (const uint32_t*)(b + o_cnt), how_many,
+                                    (uint32_t*)(b + o_rank), st);
+        if (rc2) { (void)hipStreamSynchronize(st); return rc2; }
+        if (out_rank) HIP_TRY(hipMemcpyAsync(out_rank, b + o_rank, n * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        return SRN_OK;
+    };
+    rc = run();
+    (void)hipStreamSynchronize(st);
+    (void)hipStreamDestroy(st);
+    return rc;
+}
+
+int fb_stats(srn_feedback* f, srn_feedback_stats_t* out) {
+    if (!f || !out) return fail(SRN_EINVAL, "srn_feedback_stats: null argument");
+    std::lock_guard<std::mutex> g(f->mu);
+    HIP_TRY(hipSetDevice(f->device));
+    HIP_TRY(hipEventSynchronize(f->last));
+    unsigned long long c[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    HIP_TRY(hipMemcpy(c, f->ctr, sizeof(c), hipMemcpyDeviceToHost));
+    *out = srn_feedback_stats_t{f->capacity, f->n_slots, f->row_cap, f->stride, f->bound, f->sweeps, f->refused, f->ttl, f->idle,
+                                c[kRequests], c[kNoConsent], c[kFirstSeen], c[kIdleExpired], c[kObserved], c[kHitsModel], c[kHitsFilled], c[kStored]};
+    uint32_t err = 0;
+    HIP_TRY(hipMemcpy(&err, f->err(), 4, hipMemcpyDeviceToHost));
+    if (err) return fail(SRN_ESTATE, "click feedback log: a batch found the table full (the capacity rule was violated)");
+    return SRN_OK;
+}
+
+int fb_histogram(srn_feedback* f, uint64_t* hits_model, uint64_t* hits_filled, size_t cap) {
+    if (!f) return fail(SRN_EINVAL, "srn_feedback_histogram: null log");
+    if (cap < f->row_cap + 1) return fail(SRN_ERANGE, "srn_feedback_histogram: fewer than row_cap + 1 entries per array");
+    std::lock_guard<std::mutex> g(f->mu);
+    HIP_TRY(hipSetDevice(f->device));
+    HIP_TRY(hipEventSynchronize(f->last));
+    const size_t bins = f->row_cap + 1;
+    std::vector<unsigned long long> h(2 * bins);
+    HIP_TRY(hipMemcpy(h.data(), f->ctr + kHist, h.size() * 8, hipMemcpyDeviceToHost));
+    for (size_t r = 0; r < cap; ++r) {
+        if (hits_model) hits_model[r] = r < bins ? h[r] : 0;
+        if (hits_filled) hits_filled[r] = r < bins ? h[bins + r] : 0;
+    }
+    return SRN_OK;
+}
+
+int fb_reset_counters(srn_feedback* f) {
+    if (!f) return fail(SRN_EINVAL, "srn_feedback_reset_counters: null log");
+    std::lock_guard<std::mutex> g(f->mu);
+    int rc = own_after_last(f); if (rc) return rc;
+    HIP_TRY(hipMemsetAsync(f->ctr, 0, 8 * (size_t)f->n_bins(), f->own));
+    HIP_TRY(hipStreamSynchronize(f->own));
+    return SRN_OK;
+}
+
+int fb_sweep(srn_feedback* f, uint64_t now_secs, uint64_t* n_live) {
+    if (!f) return fail(SRN_EINVAL, "srn_feedback_sweep: null log");
+    const uint64_t now = now_secs ? now_secs : wall_secs();
+    std::lock_guard<std::mutex> g(f->mu);
+    int rc = own_after_last(f); if (rc) return rc;
+    if ((rc = rebuild(f, now))) return rc;
+    uint64_t occupied = 0, live = 0;
+    if ((rc = count(f, now, &occupied, &live))) return rc;
+    f->bound = occupied;
+    if (n_live) *n_live = occupied;
+    uint32_t err = 0;
+    HIP_TRY(hipMemcpy(&err, f->err(), 4, hipMemcpyDeviceToHost));
+    if (err) return fail(SRN_ESTATE, "click feedback log: a batch found the table full (the capacity rule was violated)");
+    return SRN_OK;
+}
+
+int fb_get(srn_feedback* f, uint64_t hi, uint64_t lo, uint64_t now_secs, uint64_t* out_ids, size_t cap, uint32_t* out_count, uint32_t* out_n_model, uint64_t* out_epoch) {
+    if (!f || !out_count || (cap && !out_ids)) return fail(SRN_EINVAL, "srn_feedback_get: null argument");
+    const uint64_t now = now_secs ? now_secs : wall_secs();
+    std::lock_guard<std::mutex> g(f->mu);
+    int rc = own_after_last(f); if (rc) return rc;
+    *out_count = SRN_FEEDBACK_NONE;
+    if (out_n_model) *out_n_model = 0;
+    if (out_epoch) *out_epoch = 0;
+    fb_get_one<<<1, 1, 0, f->own>>>(f->tab(), hi, lo, (uint32_t)f->row_cap, f->one());
+    HIP_TRY(hipGetLastError());
+    std::vector<uint64_t> h(3 + f->row_cap);
+    HIP_TRY(hipMemcpyAsync(h.data(), f->one(), h.size() * 8, hipMemcpyDeviceToHost, f->own));
+    HIP_TRY(hipStreamSynchronize(f->own));
+    if (h[0] == ~0ull || idle_or_old(now, h[1], f->idle)) return SRN_OK;
+    if (h[0] > cap) return fail(SRN_ERANGE, "srn_feedback_get: output buffer too small");
+    if (h[0]) std::memcpy(out_ids, h.data() + 3, h[0] * 8);
+    *out_count = (uint32_t)h[0];
+    if (out_n_model) *out_n_model = (uint32_t)h[2];
+    if (out_epoch) *out_epoch = h[1];
+    return SRN_OK;
+}
+
+}  // namespace srn

@@ -312,4 +312,16 @@ int dsess_recommend_host(const srn_index* idx, srn_device_sessions* s, const uin
 // trending items (srn_trending.hip): the items the store's live sessions hold most often
 int dsess_top_items(srn_device_sessions* s, uint64_t now_secs, uint64_t since_secs, uint32_t min_count, size_t cap, uint64_t* out_ids, uint32_t* out_counts, size_t* out_n);
 int dsess_device_of(const srn_device_sessions* s);
+// click feedback log (srn_feedback.hip): every argument check is its own
+int fb_create(int device, size_t capacity, size_t row_cap, uint64_t ttl_secs, uint64_t idle_secs, srn_feedback** out);
+void fb_free(srn_feedback* f);
+int fb_observe_device(srn_feedback* f, const uint64_t* d_hi, const uint64_t* d_lo, const uint64_t* d_item, const uint8_t* d_consent, size_t n, uint64_t now_secs,
+                      const uint64_t* d_ids, const double* d_scores, const uint32_t* d_counts, size_t how_many, uint32_t* d_out_rank, void* stream);
+int fb_observe_host(srn_feedback* f, const uint64_t* hi, const uint64_t* lo, const uint64_t* item, const uint8_t* consent, size_t n, uint64_t now_secs,
+                    const uint64_t* ids, const double* scores, const uint32_t* counts, size_t how_many, uint32_t* out_rank);
+int fb_stats(srn_feedback* f, srn_feedback_stats_t* out);
+int fb_histogram(srn_feedback* f, uint64_t* hits_model, uint64_t* hits_filled, size_t cap);
+int fb_reset_counters(srn_feedback* f);
+int fb_sweep(srn_feedback* f, uint64_t now_secs, uint64_t* n_live);
+int fb_get(srn_feedback* f, uint64_t hi, uint64_t lo, uint64_t now_secs, uint64_t* out_ids, size_t cap, uint32_t* out_count, uint32_t* out_n_model, uint64_t* out_epoch);
 }  // namespace srn

@@ -7,6 +7,8 @@ import collections
 import ctypes as C
 import os
 import struct
+import time
+import warnings
 
 import numpy as np
 
@@ -440,16 +442,197 @@ class DeviceSessionStore:
     __del__ = close
 
 
+# ---- click feedback: served rows scored against the visitor's next click (srn_feedback_*) ----
+_FEEDBACK_COUNTERS = ("requests", "no_consent", "first_seen", "idle_expired", "observed", "hits_model", "hits_filled", "stored")
+
+
+def feedback_model(state, keys, items, consent, ids, counts, scores, now, idle_secs=20 * 60, row_cap=None):
+    """NumPy statement of ClickFeedback.observe (srn_feedback.hip): what the device computes, bit for bit.  It needs no GPU and no library.
+    state: dict, 128-bit key -> (ids uint64[c], n_model, epoch); updated in place.  keys = (hi, lo); consent / scores may be None (all consent / every entry a model
+    entry).  ids[n, how_many], counts[n]: the rows just served to the requests.  Requests j = 0..n-1 in order, with one `now`:
+      no consent                 rank NONE; nothing is read or stored
+      no entry for the key       rank NONE (first_seen);   an entry with now > epoch and now - epoch > idle_secs: rank NONE (idle_expired)
+      otherwise observed:        r = 1-based position of items[j] among the entry's ids (0: absent), FILLED or-ed in when r > n_model
+      then, with consent:        the entry becomes (ids[j, :c], finite scores among those c, now), c = counts[j] (0xFFFFFFFF -> 0; above how_many -> how_many)
+    -> (ranks uint32[n], counters): the words of ClickFeedback.stats() plus "hist_model" / "hist_filled", hits by rank ([0] unused): uint64[row_cap + 1], or with
+    row_cap = None as long as the widest row of the call and the state needs."""
+    hi, lo = (np.asarray(a, np.uint64) for a in keys)
+    items, counts = np.asarray(items, np.uint64), np.asarray(counts, np.uint32)
+    n = len(items)
+    ids = np.asarray(ids, np.uint64).reshape(n, -1) if n else np.zeros((0, 1), np.uint64)
+    how_many = ids.shape[1]
+    sc = None if scores is None else np.asarray(scores, np.float64).reshape(n, how_many)
+    if not (len(hi) == len(lo) == len(counts) == n) or (consent is not None and len(consent) != n):
+        raise ValueError("keys, items, consent, ids and counts differ in length")
+    ranks = np.full(n, capi.FEEDBACK_NONE, np.uint32)
+    ctr = {name: 0 for name in _FEEDBACK_COUNTERS}
+    widest = max([how_many] + [len(e[0]) for e in state.values()]) if row_cap is None else int(row_cap)   # (a stored row may be wider than this call's)
+    ctr["hist_model"], ctr["hist_filled"] = np.zeros(widest + 1, np.uint64), np.zeros(widest + 1, np.uint64)
+    now = int(now)
+    for j in range(n):
+        ctr["requests"] += 1
+        if consent is not None and not consent[j]:
+            ctr["no_consent"] += 1
+            continue
+        key = (int(hi[j]) << 64) | int(lo[j])
+        entry = state.get(key)
+        if entry is None:
+            ctr["first_seen"] += 1
+        elif now > entry[2] and now - entry[2] > idle_secs:
+            ctr["idle_expired"] += 1
+        else:
+            row, n_model, _ = entry
+            at = np.flatnonzero(row == items[j])
+            r = int(at[0]) + 1 if len(at) else 0
+            filled = r > n_model
+            ranks[j] = r | (capi.FEEDBACK_FILLED if filled else 0)
+            ctr["observed"] += 1
+            if r:
+                ctr["hits_filled" if filled else "hits_model"] += 1
+                ctr["hist_filled" if filled else "hist_model"][r] += 1
+        c = 0 if counts[j] == capi.FEEDBACK_NONE else min(int(counts[j]), how_many)
+        state[key] = (ids[j, :c].copy(), c if sc is None else int(np.isfinite(sc[j, :c]).sum()), now)
+        ctr["stored"] += 1
+    return ranks, ctr
+
+
+def feedback_metrics(hist_model, hist_filled, observed):
+    """hit_rate = hits / observed and mrr = sum over r of hist[r] / r / observed, added in ascending r -- each for all hits and split into model and filled entries
+    (0.0 where nothing was observed): the reference's HitRate and Mrr at the row's length (metrics/hitrate.rs, mrr.rs) over the observed requests."""
+    hm, hf = (np.asarray(h, np.uint64) for h in (hist_model, hist_filled))
+    out = {}
+    for name, h in (("", hm + hf), ("_model", hm), ("_filled", hf)):
+        hits, mrr = 0, 0.0
+        for r in range(1, len(h)):
+            hits += int(h[r])
+            mrr += int(h[r]) / r
+        out["hit_rate" + name] = hits / observed if observed else 0.0
+        out["mrr" + name] = mrr / observed if observed else 0.0
+    return out
+
+
+class ClickFeedback:
+    """A click feedback log in the GPU's memory (srn_feedback_*): the last row served to every visitor, scored against the visitor's next click.  An object of its own
+    beside the session store; recommend_batch(..., feedback=fb) feeds it."""
+
+    def __init__(self, index_or_device, capacity, row_cap=21, ttl_secs=30 * 60, idle_secs=20 * 60):
+        device = index_or_device if isinstance(index_or_device, int) else index_or_device.info["device"]
+        h = C.c_void_p()
+        capi.check(capi.lib().srn_feedback_create(int(device), int(capacity), int(row_cap), int(ttl_secs), int(idle_secs), C.byref(h)))
+        self._h, self.device, self.row_cap = h, int(device), int(row_cap)
+        self.last_ranks = None
+        self.last_error = None          # recommend_batch(..., feedback=self): the error of a call the log refused (its rows were served all the same)
+
+    def observe(self, keys, item_ids, consent, ids, counts, scores=None, now=0):
+        """Requests (keys[i], item_ids[i], consent[i]) and the rows just served to them (ids[n, how_many], counts[n], scores or None) -> ranks[n]: the 1-based rank of
+        the clicked item in the visitor's PREVIOUS row (0: a miss; capi.FEEDBACK_FILLED or-ed in for a filled entry) or capi.FEEDBACK_NONE where there is no previous
+        row to score; then the rows are remembered.  NumPy arrays in, a uint32 array out; tensors on the log's GPU are read in place on the current stream, without
+        synchronising, and the ranks are an int32 tensor there (the same bits).  The result is also left in self.last_ranks."""
+        hi, lo = keys
+        n = len(item_ids)
+        arrs = [hi, lo, item_ids, ids, counts] + ([consent] if consent is not None else []) + ([scores] if scores is not None else [])
+        if any(len(a) != n for a in arrs) or ids.ndim != 2 or (scores is not None and tuple(scores.shape) != tuple(ids.shape)):
+            raise ValueError("keys, item_ids, consent and counts must have one entry per row of ids[n, how_many] (and scores its shape)")
+        how_many = int(ids.shape[1])
+        on_gpu = [_is_torch(a) and a.device.type == "cuda" for a in arrs]
+        if any(on_gpu):
+            import torch
+            if not all(on_gpu) or any(a.device.index != self.device for a in arrs):
+                raise ValueError("keys, item_ids, consent, ids, counts and scores must all be tensors on the log's GPU (device %d), or none of them" % self.device)
+            if any(a.dtype not in (torch.int64, getattr(torch, "uint64", torch.int64)) for a in (hi, lo, item_ids, ids)) or \
+                    counts.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or (scores is not None and scores.dtype != torch.float64) or \
+                    (consent is not None and consent.dtype not in (torch.uint8, torch.bool)):
+                raise TypeError("keys, item_ids and ids must be 64-bit integer, counts 32-bit integer, scores float64 and consent uint8 or bool tensors")
+            t = [a.contiguous() for a in arrs]
+            con = t[5] if consent is not None else None
+            sc = t[-1] if scores is not None else None
+            ranks = torch.zeros(n, dtype=torch.int32, device=torch.device("cuda", self.device))
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            p = lambda a: None if a is None else C.c_void_p(a.data_ptr())
+            capi.check(capi.lib().srn_feedback_observe_device(self._h, p(t[0]), p(t[1]), p(t[2]), p(con), n, int(now), p(t[3]), p(sc), p(t[4]), how_many, p(ranks),
+                                                              C.c_void_p(stream)))
+            self.last_ranks = ranks
+            return ranks
+        as_np = lambda a: a.numpy() if _is_torch(a) else a
+        hi, lo, it, rows = (capi.as_u64(as_np(a)) for a in (hi, lo, item_ids, ids))
+        cnt = capi.as_u32(as_np(counts))
+        con = None if consent is None else np.ascontiguousarray(as_np(consent)).astype(np.uint8)
+        sc = None if scores is None else np.ascontiguousarray(as_np(scores), dtype=np.float64)
+        ranks = np.zeros(n, np.uint32)
+        capi.check(capi.lib().srn_feedback_observe(self._h, capi.ptr(hi), capi.ptr(lo), capi.ptr(it), capi.ptr(con), n, int(now), capi.ptr(rows), capi.ptr(sc),
+                                                   capi.ptr(cnt), how_many, capi.ptr(ranks)))
+        self.last_ranks = ranks
+        return ranks
+
+    def histogram(self):
+        """-> (hits_model, hits_filled): uint64[row_cap + 1], hits by rank ([0] unused).  Blocks."""
+        hm, hf = np.zeros(self.row_cap + 1, np.uint64), np.zeros(self.row_cap + 1, np.uint64)
+        capi.check(capi.lib().srn_feedback_histogram(self._h, capi.ptr(hm), capi.ptr(hf), self.row_cap + 1))
+        return hm, hf
+
+    def stats(self):
+        """srn_feedback_stats_t as a dict (waits for the log's kernels), with feedback_metrics of the histograms: hit_rate, mrr and their _model / _filled parts."""
+        st = capi.FeedbackStats()
+        capi.check(capi.lib().srn_feedback_stats(self._h, C.byref(st)))
+        out = {n: getattr(st, n) for n, _ in capi.FeedbackStats._fields_}
+        out.update(feedback_metrics(*self.histogram(), out["observed"]))
+        return out
+
+    def reset_counters(self):
+        capi.check(capi.lib().srn_feedback_reset_counters(self._h))
+
+    def sweep(self, now=0):
+        n = C.c_uint64()
+        capi.check(capi.lib().srn_feedback_sweep(self._h, int(now), C.byref(n)))
+        return n.value
+
+    def get(self, key, now=1):
+        """(test aid) -> (ids uint64[c], n_model, epoch) as a request at `now` would read the key's entry, or None (unknown, or idle at `now`); now = 1: whatever is stored."""
+        out, c, nm, ep = np.zeros(self.row_cap, np.uint64), C.c_uint32(), C.c_uint32(), C.c_uint64()
+        capi.check(capi.lib().srn_feedback_get(self._h, key >> 64, key & (2**64 - 1), int(now), capi.ptr(out), self.row_cap, C.byref(c), C.byref(nm), C.byref(ep)))
+        return None if c.value == capi.FEEDBACK_NONE else (out[:c.value].copy(), nm.value, ep.value)
+
+    def close(self):
+        if getattr(self, "_h", None) and capi is not None and getattr(capi, "lib", None) is not None:
+            capi.lib().srn_feedback_free(self._h)
+            self._h = None
+
+    __del__ = close
+
+
+def _observe_served(feedback, keys, item_ids, consent, ids, counts, scores, now):
+    """recommend_batch's call of feedback.observe.  The session store has advanced and the rows are written by now, so a log that refuses the call (SRN_ENOMEM under the
+    capacity rule, counted in stats()["refused"]) must not fail the serving call: the refusal becomes a warning, feedback.last_ranks None and feedback.last_error the
+    exception; the log is as it was."""
+    feedback.last_error = None
+    try:
+        feedback.observe(keys, item_ids, consent, ids, counts, scores, now=now)
+    except capi.SerenadeError as e:
+        if e.code != capi.SRN_ENOMEM:
+            raise
+        feedback.last_ranks, feedback.last_error = None, e
+        warnings.warn("recommend_batch: the click feedback log did not take this call's rows: %s" % e, RuntimeWarning, stacklevel=3)
+
+
 def recommend_batch(index, store, keys, item_ids, consent=None, *, k, m, how_many, max_items_in_session=2, enable_business_logic=False, now=0,
-                    scores=False, exclude_seen=False, fill=False):
+                    scores=False, exclude_seen=False, fill=False, feedback=None):
     """/v1/recommend for a batch: request i = (keys[i], item_ids[i], consent[i]); the result is what the requests served one after the other give.
     keys: (hi, lo) uint64 arrays / tensors, or a list of session-id strings.  -> (ids[n, how_many], counts[n]) and scores[n, how_many] with scores=True.
     NumPy arrays (or CPU tensors) in, NumPy arrays out; tensors on the index's GPU are read in place (on the current stream, without synchronising) and the
     outputs are tensors on it.  store may be None only if no request consents.
     exclude_seen (SRN_FLAG_EXCLUDE_SEEN): a request's rows leave out its visitor's window as the request sees it -- the store's history window, or the session window on a
     store without one; without consent nothing beyond the item itself.
-    fill (SRN_FLAG_FILL): rows of fewer than how_many entries are filled from the index's fallback ranking (score -inf), leaving out what the request excludes."""
+    fill (SRN_FLAG_FILL): rows of fewer than how_many entries are filled from the index's fallback ranking (score -inf), leaving out what the request excludes.
+    feedback (a ClickFeedback): the call's requests and rows also go through feedback.observe -- enqueued behind the recommend call on the same stream, with the same
+    `now` (the clock is read once here when now = 0); the requests' ranks are left in feedback.last_ranks.  The return value is the same with or without it, also when
+    the log refuses the call (its capacity is reached): that is a RuntimeWarning, feedback.last_ranks None and the error in feedback.last_error."""
     n = len(item_ids)
+    if feedback is not None:
+        if how_many > feedback.row_cap:
+            raise ValueError("how_many %d above the feedback log's row_cap %d" % (how_many, feedback.row_cap))
+        if feedback.device != index.info["device"]:
+            raise ValueError("the feedback log and the index are on different devices")
+        now = int(now) or int(time.time())
     if isinstance(keys, list) and (not keys or isinstance(keys[0], (str, bytes))):
         if len(keys) != n:
             raise ValueError("keys, item_ids and consent differ in length")
@@ -484,10 +667,14 @@ def recommend_batch(index, store, keys, item_ids, consent=None, *, k, m, how_man
             index._h, sh, C.c_void_p(hi.data_ptr()), C.c_void_p(lo.data_ptr()), C.c_void_p(it.data_ptr()), None if con is None else C.c_void_p(con.data_ptr()),
             n, int(now), int(max_items_in_session), int(k), int(m), int(how_many), flags,
             C.c_void_p(ids.data_ptr()), C.c_void_p(sc.data_ptr()), C.c_void_p(cnt.data_ptr()), C.c_void_p(stream)))
+        if feedback is not None and n:
+            _observe_served(feedback, (hi, lo), it, con, ids, cnt, sc, now)
         return (ids, cnt, sc) if scores else (ids, cnt)
     hi, lo, it = (capi.as_u64(a.numpy() if _is_torch(a) else a) for a in arrs[:3])
     con = None if consent is None else np.ascontiguousarray(consent.numpy() if _is_torch(consent) else consent).astype(np.uint8)
     ids, sc, cnt = np.zeros((n, how_many), np.uint64), np.zeros((n, how_many), np.float64), np.zeros(n, np.uint32)
     capi.check(capi.lib().srn_recommend_batch(index._h, sh, capi.ptr(hi), capi.ptr(lo), capi.ptr(it), capi.ptr(con), n, int(now), int(max_items_in_session),
                                               int(k), int(m), int(how_many), flags, capi.ptr(ids), capi.ptr(sc), capi.ptr(cnt)))
+    if feedback is not None and n:
+        _observe_served(feedback, (hi, lo), it, con, ids, cnt, sc, now)
     return (ids, cnt, sc) if scores else (ids, cnt)
