@@ -701,6 +701,61 @@ int srn_feedback_sweep(srn_feedback_t* f, uint64_t now_secs, uint64_t* n_live);
 int srn_feedback_get(srn_feedback_t* f, uint64_t key_hi, uint64_t key_lo, uint64_t now_secs, uint64_t* out_ids, size_t cap, uint32_t* out_count, uint32_t* out_n_model,
                      uint64_t* out_epoch);
 
+/* ---- session harvest: finished sessions logged on the device, and training events from them (srn_harvest.hip) ----
+ * A harvest is a device-resident log, attached to one device session store, that receives every session at the moment the store forgets it: each one exactly once,
+ * on the stream of the call that forgets it, with nothing read back.  An entry (key, epoch, len, items[0 .. len)) is harvested when, and only when, the store drops
+ * it by its own rules:
+ *   (R) return after idle   inside srn_recommend_batch*: the first consenting request of a key in the call finds the key stored with len > 0 and idle
+ *                           (now > epoch and now - epoch > idle_secs); the stored entry is copied before the call's result overwrites it
+ *   (S) a rebuild drops it  the entry is occupied and older than ttl_secs at the rebuild's now: srn_device_sessions_sweep, the capacity rule's automatic sweep,
+ *                           srn_device_sessions_resize, growth.  A resize or growth that is refused or fails harvests nothing: store and harvest are as they were
+ * NOT harvested: what srn_device_sessions_update replaces; an entry replaced or beaten in srn_device_sessions_import*; the entries of a store that is freed
+ * (srn_device_sessions_free); anything srn_device_sessions_load reads; requests without consent, which never touch the store.
+ * A harvested session carries the epoch as stored -- the time of its last click -- and exactly the items the slot held: with a history window H the last H clicks,
+ * otherwise the last max_items_in_session.  An entry of fewer than min_len items (0 is read as 1) is counted in skipped_short and not stored.  Sessions beyond
+ * `capacity` are not stored and counted exactly in `lost`; the serving call and the sweep never fail or wait because the log is full.  The log is appended in a fixed
+ * order -- (R): ascending (key_hi, key_lo) within a call; (S): ascending slot -- behind a device cursor, without atomics, so which sessions a full log loses does not
+ * depend on scheduling (for (S) it depends on where the keys lie in the table).
+ *   capacity   sessions the log holds (1..2^30); items_cap: items per session (1..SRN_MAX_SESSION_LEN).  All storage -- 28 + 8 * items_cap bytes per session -- is
+ *              allocated at creation.  capacity or items_cap 0: SRN_EINVAL; above their limits: SRN_ERANGE; no such GPU: SRN_ENODEV; no device memory: SRN_ENOMEM.
+ * srn_device_sessions_set_harvest(store, h) attaches, (store, NULL) detaches (SRN_OK also when nothing is attached; it waits for the store's last call).  One harvest
+ * is attached to at most one store and a store has at most one harvest: a second attach is SRN_ESTATE; a harvest on another device than the store SRN_EINVAL; a
+ * harvest whose items_cap is below the store's SRN_ERANGE, and so is a srn_device_sessions_resize to an items_cap above the attached harvest's (before anything
+ * changes).  Freeing the store detaches; srn_harvest_free of an attached harvest is SRN_ESTATE (NULL: SRN_OK).  With no harvest attached every store call does what it
+ * did before.  Every harvest call takes the store's mutex and is ordered behind the store's previous call, like the store's own calls; a detached harvest uses a
+ * stream and an event of its own. */
+typedef struct srn_harvest srn_harvest_t;
+typedef struct {
+    uint64_t capacity, items_cap, min_len;
+    uint64_t stored, stored_items;      /* the sessions the log holds now, and the sum of their lengths = the rows srn_harvest_events_device writes */
+    uint64_t lost, skipped_short;       /* offered when the log was full | offered with fewer than min_len items */
+    uint64_t from_return, from_rebuild; /* offered by (R) | by (S) */
+    uint64_t cleared;                   /* sessions srn_harvest_clear removed: from_return + from_rebuild = stored + cleared + lost + skipped_short */
+} srn_harvest_stats_t;
+int srn_harvest_create(int device, size_t capacity, size_t items_cap, uint32_t min_len, srn_harvest_t** out);
+int srn_harvest_free(srn_harvest_t* h);
+int srn_device_sessions_set_harvest(srn_device_sessions_t* s, srn_harvest_t* harvest_or_null);
+/* blocks and reads the device words back */
+int srn_harvest_stats(srn_harvest_t* h, srn_harvest_stats_t* out);
+/* The stored sessions in CANONICAL order -- (epoch, key_hi, key_lo) ascending, a triple that is unique because two sessions of one visitor end more than idle_secs
+ * apart -- sorted on the device by stable radix passes, in the arrays of srn_device_sessions_export: the same set of sessions gives the same bytes however the requests
+ * were cut into calls and wherever the sweeps fell; the log's internal order is not exposed.  Neither call consumes the log.  items_stride below the harvest's
+ * items_cap: SRN_ERANGE.
+ * _export_device: device buffers on the harvest's GPU, enqueued on `stream` with no host synchronisation; writes the first min(stored, cap) sessions and *d_n = stored
+ *                 -- the caller compares.  NULL harvest or d_n: SRN_EINVAL.
+ * _export:        host arrays; blocks.  stored > cap: SRN_ERANGE with *n = stored and the arrays untouched.  NULL harvest or n: SRN_EINVAL. */
+int srn_harvest_export(srn_harvest_t* h, size_t cap, uint64_t* key_hi, uint64_t* key_lo, uint64_t* epoch, uint32_t* len, uint64_t* items, size_t items_stride, size_t* n);
+int srn_harvest_export_device(srn_harvest_t* h, size_t cap, uint64_t* d_key_hi, uint64_t* d_key_lo, uint64_t* d_epoch, uint32_t* d_len, uint64_t* d_items,
+                              size_t items_stride, uint64_t* d_n, void* stream);
+/* The stored sessions as the rows srn_sessions_from_events reads with SRN_EVENTS_TIME_I64 | SRN_EVENTS_DEVICE: session i in canonical order gets
+ * session_id = id_base + i and one row per stored item, in session order, each with time = its epoch.  Device buffers, enqueued on `stream` with no host
+ * synchronisation; writes the first min(rows, cap_rows) rows and *d_rows = rows (= stored_items) -- the caller compares. */
+int srn_harvest_events_device(srn_harvest_t* h, uint64_t id_base, size_t cap_rows, uint64_t* d_session_ids, uint64_t* d_item_ids, int64_t* d_times, uint64_t* d_rows,
+                              void* stream);
+/* Empties the log -- stored and stored_items become 0, the sessions removed are added to `cleared` -- behind the previous call.  lost, skipped_short, from_return and
+ * from_rebuild keep running until the harvest is freed. */
+int srn_harvest_clear(srn_harvest_t* h);
+
 /* ---- offline evaluation: test sets and hyper-parameter trials ----------------------------------------------------------
  * The reference's evaluation loop (src/bin/evaluator.rs:46-76, src/objective.rs:8-52) on the GPU: every prefix of every test session is
  * predicted and scored against the rest of its session, and the eight metrics of src/metrics/evaluation_reporter.rs come back.  Prefixes,

@@ -93,6 +93,10 @@ class FeedbackStats(C.Structure):
                                           "requests", "no_consent", "first_seen", "idle_expired", "observed", "hits_model", "hits_filled", "stored")]
 
 
+class HarvestStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("capacity", "items_cap", "min_len", "stored", "stored_items", "lost", "skipped_short", "from_return", "from_rebuild", "cleared")]
+
+
 class ResultCacheStats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("rows", "ways", "bytes")] + [(n, C.c_uint32) for n in ("max_len", "k", "m", "how_many", "flags", "reserved")] + \
                [(n, C.c_uint64) for n in ("lookups", "hits", "inserts", "evictions", "bypassed_calls", "clears")]
@@ -231,6 +235,14 @@ SYMBOLS = {
     "srn_feedback_reset_counters": (_i, [_vp]),
     "srn_feedback_sweep": (_i, [_vp, _u64, C.POINTER(_u64)]),
     "srn_feedback_get": (_i, [_vp, _u64, _u64, _u64, _vp, _sz, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(_u64)]),
+    "srn_harvest_create": (_i, [_i, _sz, _sz, C.c_uint32, C.POINTER(_vp)]),
+    "srn_harvest_free": (_i, [_vp]),
+    "srn_device_sessions_set_harvest": (_i, [_vp, _vp]),
+    "srn_harvest_stats": (_i, [_vp, C.POINTER(HarvestStats)]),
+    "srn_harvest_export": (_i, [_vp, _sz, _vp, _vp, _vp, _vp, _vp, _sz, C.POINTER(_sz)]),
+    "srn_harvest_export_device": (_i, [_vp, _sz, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+    "srn_harvest_events_device": (_i, [_vp, _u64, _sz, _vp, _vp, _vp, _vp, _vp]),
+    "srn_harvest_clear": (_i, [_vp]),
     "srn_device_count": (_i, [C.POINTER(_i)]),
     "srn_limits": (None, [C.POINTER(Limits)]),
     "srn_last_error": (C.c_char_p, []),

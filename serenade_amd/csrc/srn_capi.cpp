@@ -900,6 +900,26 @@ int srn_recommend_batch(const srn_index_t* idx, srn_device_sessions_t* store, co
                                     out_ids, out_scores, out_counts); });
 }
 
+// ---- session harvest (srn_harvest.hip) ----
+int srn_harvest_create(int device, size_t capacity, size_t items_cap, uint32_t min_len, srn_harvest_t** out) {
+    return guarded([&]() -> int { return harvest_create(device, capacity, items_cap, min_len, out); });
+}
+int srn_harvest_free(srn_harvest_t* h) { return guarded([&]() -> int { return harvest_free(h); }); }
+int srn_device_sessions_set_harvest(srn_device_sessions_t* s, srn_harvest_t* h) { return guarded([&]() -> int { return dsess_set_harvest(s, h); }); }
+int srn_harvest_stats(srn_harvest_t* h, srn_harvest_stats_t* out) { return guarded([&]() -> int { return harvest_stats(h, out); }); }
+int srn_harvest_export(srn_harvest_t* h, size_t cap, uint64_t* key_hi, uint64_t* key_lo, uint64_t* epoch, uint32_t* len, uint64_t* items, size_t items_stride, size_t* n) {
+    return guarded([&]() -> int { return harvest_export_host(h, cap, key_hi, key_lo, epoch, len, items, items_stride, n); });
+}
+int srn_harvest_export_device(srn_harvest_t* h, size_t cap, uint64_t* d_key_hi, uint64_t* d_key_lo, uint64_t* d_epoch, uint32_t* d_len, uint64_t* d_items, size_t items_stride,
+                              uint64_t* d_n, void* stream) {
+    return guarded([&]() -> int { return harvest_export_device(h, cap, d_key_hi, d_key_lo, d_epoch, d_len, d_items, items_stride, d_n, stream); });
+}
+int srn_harvest_events_device(srn_harvest_t* h, uint64_t id_base, size_t cap_rows, uint64_t* d_session_ids, uint64_t* d_item_ids, int64_t* d_times, uint64_t* d_rows,
+                              void* stream) {
+    return guarded([&]() -> int { return harvest_events_device(h, id_base, cap_rows, d_session_ids, d_item_ids, d_times, d_rows, stream); });
+}
+int srn_harvest_clear(srn_harvest_t* h) { return guarded([&]() -> int { return harvest_clear(h); }); }
+
 // ---- click feedback log (srn_feedback.hip) ----
 int srn_feedback_create(int device, size_t capacity, size_t row_cap, uint64_t ttl_secs, uint64_t idle_secs, srn_feedback_t** out) {
     return guarded([&]() -> int { return fb_create(device, capacity, row_cap, ttl_secs, idle_secs, out); });

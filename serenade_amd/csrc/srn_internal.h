@@ -312,6 +312,16 @@ int dsess_recommend_host(const srn_index* idx, srn_device_sessions* s, const uin
 // trending items (srn_trending.hip): the items the store's live sessions hold most often
 int dsess_top_items(srn_device_sessions* s, uint64_t now_secs, uint64_t since_secs, uint32_t min_count, size_t cap, uint64_t* out_ids, uint32_t* out_counts, size_t* out_n);
 int dsess_device_of(const srn_device_sessions* s);
+// session harvest (srn_harvest.hip): every argument check is its own
+int harvest_create(int device, size_t capacity, size_t items_cap, uint32_t min_len, srn_harvest** out);
+int harvest_free(srn_harvest* h);
+int dsess_set_harvest(srn_device_sessions* s, srn_harvest* h);
+int harvest_stats(srn_harvest* h, srn_harvest_stats_t* out);
+int harvest_clear(srn_harvest* h);
+int harvest_export_device(srn_harvest* h, size_t cap, uint64_t* d_hi, uint64_t* d_lo, uint64_t* d_epoch, uint32_t* d_len, uint64_t* d_items, size_t items_stride,
+                          uint64_t* d_n, void* stream);
+int harvest_export_host(srn_harvest* h, size_t cap, uint64_t* hi, uint64_t* lo, uint64_t* epoch, uint32_t* len, uint64_t* items, size_t items_stride, size_t* n);
+int harvest_events_device(srn_harvest* h, uint64_t id_base, size_t cap_rows, uint64_t* d_session_ids, uint64_t* d_item_ids, int64_t* d_times, uint64_t* d_rows, void* stream);
 // click feedback log (srn_feedback.hip): every argument check is its own
 int fb_create(int device, size_t capacity, size_t row_cap, uint64_t ttl_secs, uint64_t idle_secs, srn_feedback** out);
 void fb_free(srn_feedback* f);

@@ -31,6 +31,9 @@
 //                   finds its slot; a second kernel writes the winners.  Checked before anything is changed
 //   resize / growth sess_rebuild into a freshly allocated pair of tables of another capacity or items_cap
 //   save / load     the export's arrays behind a 96-byte header with a checksum, written through a rename
+// The store forgets a session in two places -- sess_store overwrites the slot of a visitor who returns after idle, and sess_rebuild leaves out what is older than the
+// TTL (rebuild, resize_locked) -- and an attached session harvest (srn_harvest.hip) is handed the entry at both, before the old bytes go away:
+// sess_return_flag + harvest_append between sess_find and sess_store, harvest_dropped behind sess_rebuild over the old table.  Without one nothing here differs.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -181,6 +184,28 @@ __global__ void __launch_bounds__(kTPB) sess_store(BatchArgs a) {
     uint64_t* it = slot_items(s);
     for (uint32_t i = 0; i < len; ++i) it[i] = a.items_flat[off + i];
     s->len = len; s->epoch = a.now; s->state = kFull;
+}
+
+// Session harvest, return after idle (srn_harvest.hip): flag[p] for sorted position p, behind sess_find and before sess_store.  A run head whose key was found stored
+// with len > 0 and idle is about to have its slot overwritten: kHvStore (kHvSkip below min_len).  sess_find left such a head with slen 0 and the slot untouched (a slot
+// claimed in this call is in state kClaimed with len 0).  flag[n] = 0.
+__global__ void __launch_bounds__(kTPB) sess_return_flag(BatchArgs a, uint32_t min_len, uint64_t* __restrict__ flag) {
+    const uint32_t p = blockIdx.x * kTPB + threadIdx.x;
+    if (p > a.n) return;
+    uint64_t f = 0;
+    if (p < a.n) {
+        const uint32_t req = a.order[p];
+        if (consents(a, req)) {
+            bool head = p == 0;
+            if (!head) { const uint32_t pr = a.order[p - 1]; head = !consents(a, pr) || a.key_hi[pr] != a.key_hi[req] || a.key_lo[pr] != a.key_lo[req]; }
+            const uint32_t slot = head ? a.slot_of[p] : kNone;
+            if (slot != kNone && a.slen[p] == 0) {
+                const SlotHead* s = slot_at(a.t, slot);
+                if (s->state == kFull && s->len > 0 && idle_or_old(a.now, s->epoch, a.idle)) f = s->len >= min_len ? kHvStore : kHvSkip;
+            }
+        }
+    }
+    flag[p] = f;
 }
 
 // a NULL store: every request's session is its item
@@ -380,9 +405,10 @@ void dsess_free(srn_device_sessions* s) {
     if (!s) return;
     (void)hipSetDevice(s->device);
     if (s->last) { (void)hipEventSynchronize(s->last); (void)hipEventDestroy(s->last); }
+    if (s->harvest) { std::lock_guard<std::mutex> g(s->harvest->mu); s->harvest->store = nullptr; s->harvest = nullptr; }   // freeing the store detaches its harvest
     for (hipEvent_t e : s->tev) if (e) (void)hipEventDestroy(e);
     if (s->own) { (void)hipStreamSynchronize(s->own); (void)hipStreamDestroy(s->own); }
-    for (void* p : {(void*)s->table[0], (void*)s->table[1], (void*)s->ws, (void*)s->stage, (void*)s->small, (void*)s->xs}) if (p) (void)hipFree(p);
+    for (void* p : {(void*)s->table[0], (void*)s->table[1], (void*)s->ws, (void*)s->stage, (void*)s->small, (void*)s->xs, (void*)s->hs}) if (p) (void)hipFree(p);
     delete s;
 }
 
@@ -421,11 +447,23 @@ namespace {
 // behind everything enqueued on the store so far, on its own stream (mu held)
 int own_after_last(srn_device_sessions* s) { HIP_TRY(hipSetDevice(s->device)); HIP_TRY(hipStreamWaitEvent(s->own, s->last, 0)); return SRN_OK; }
 
+// room for an attached harvest's append over n table slots (own stream behind `last`, mu held).  A scratch of its own: a rebuild runs inside make_room, below an
+// import that already holds pointers into the export / import scratch, which must neither move nor be overwritten here
+int harvest_room(srn_device_sessions* s, size_t n) {
+    size_t bytes = 0;
+    int rc = harvest_scratch_bytes(n, &bytes); if (rc) return rc;
+    if (bytes <= s->hs_bytes) return SRN_OK;
+    HIP_TRY(hipStreamSynchronize(s->own));   // (only rebuilds use it, on the own stream: wait for the previous one before it is freed)
+    return ensure(&s->hs, &s->hs_bytes, bytes);
+}
+
 int rebuild(srn_device_sessions* s, uint64_t now) {   // (own stream, mu held)
     const Table from = s->tab(); Table to = from; to.base = s->table[s->cur ^ 1];
+    if (s->harvest) { const int rc = harvest_room(s, s->n_slots); if (rc) return rc; }
     HIP_TRY(hipMemsetAsync(to.base, 0, (size_t)s->n_slots * s->stride, s->own));
     sess_rebuild<<<grid_for(s->n_slots), kTPB, 0, s->own>>>(from, to, now, s->ttl);
     HIP_TRY(hipGetLastError());
+    if (s->harvest) { const int rc = harvest_dropped(s->harvest, from, now, s->ttl, s->hs, s->own); if (rc) return rc; }   // what the rebuild left out, from the old table (it stays until the next rebuild)
     s->cur ^= 1; ++s->sweeps;
     return SRN_OK;
 }
@@ -455,11 +493,13 @@ uint32_t stride_for(uint64_t items_cap) { return (uint32_t)((kSlotHead + 8 * ite
 // old ones are touched -- peak device memory is the old pair + the new pair -- and every failure leaves the store as it was.
 int resize_locked(srn_device_sessions* s, uint64_t capacity, uint64_t items_cap, uint64_t now, const char* who) {
     uint64_t occupied = 0, live = 0, longest = 0;
+    if (s->harvest && items_cap > s->harvest->items_cap) return fail(SRN_ERANGE, std::string(who) + ": the new items_cap is above the attached harvest's");
     int rc = count_max(s, now, &occupied, &live, &longest); if (rc) return rc;
     if (live > capacity) return fail(SRN_ENOMEM, std::string(who) + ": more live sessions than the new capacity");
     if (longest > items_cap) return fail(SRN_ERANGE, std::string(who) + ": a stored session is longer than the new items_cap");
     const uint64_t n_slots = slots_for(capacity); const uint32_t stride = stride_for(items_cap);
     const size_t bytes = (size_t)n_slots * stride;
+    if (s->harvest && (rc = harvest_room(s, s->n_slots))) return rc;   // (a refused or failed resize harvests nothing: the append is enqueued behind the rebuild below)
     char* nt[2] = {nullptr, nullptr};
     for (int i = 0; i < 2; ++i)
         if (hipMalloc((void**)&nt[i], bytes) != hipSuccess) {
@@ -470,6 +510,10 @@ int resize_locked(srn_device_sessions* s, uint64_t capacity, uint64_t items_cap,
     const Table from = s->tab(), to{nt[0], (uint32_t)(n_slots - 1), stride};
     hipError_t e = hipMemsetAsync(nt[0], 0, bytes, s->own);
     if (e == hipSuccess) { sess_rebuild<<<grid_for(s->n_slots), kTPB, 0, s->own>>>(from, to, now, s->ttl); e = hipGetLastError(); }
+    if (e == hipSuccess && s->harvest && (rc = harvest_dropped(s->harvest, from, now, s->ttl, s->hs, s->own))) {   // from the old table, before it is freed
+        (void)hipStreamSynchronize(s->own); (void)hipFree(nt[0]); (void)hipFree(nt[1]);
+        return rc;
+    }
     if (e == hipSuccess) e = hipStreamSynchronize(s->own);
     if (e != hipSuccess) { (void)hipFree(nt[0]); (void)hipFree(nt[1]); return fail(SRN_EHIP, std::string(who) + ": " + hipGetErrorString(e)); }
     (void)hipFree(s->table[0]); (void)hipFree(s->table[1]);
@@ -675,11 +719,14 @@ int dsess_recommend_device(const srn_index* idx, srn_device_sessions* s, const u
     HIP_TRY(rocprim::radix_sort_pairs(nullptr, t1, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, n, 0, 1, st)); tmp = std::max(tmp, t1);
     HIP_TRY(rocprim::exclusive_scan(nullptr, t1, (uint32_t*)nullptr, (uint32_t*)nullptr, 0u, n + 1, rocprim::plus<uint32_t>(), st)); tmp = std::max(tmp, t1);
     HIP_TRY(rocprim::inclusive_scan(nullptr, t1, (uint32_t*)nullptr, (uint32_t*)nullptr, n, rocprim::maximum<uint32_t>(), st)); tmp = std::max(tmp, t1);
+    srn_harvest* const hv = s->harvest;
+    size_t hv_bytes = 0;   // an attached harvest's flags, places and scan storage for the heads that return after idle
+    if (hv && (rc = harvest_scratch_bytes(n, &hv_bytes))) return rc;
     const size_t w = align256((n + 1) * 4);
     const size_t o_keyA = 0, o_keyB = o_keyA + align256(n * 8), o_idxA = o_keyB + align256(n * 8), o_idxB = o_idxA + w, o_slot = o_idxB + w, o_slen = o_slot + w,
                  o_kept = o_slen + w, o_head = o_kept + w, o_kex = o_head + w, o_run = o_kex + w, o_qlen = o_run + w, o_qoff = o_qlen + w, o_comp = o_qoff + w,
                  o_flat = o_comp + align256(n * 8), o_tmp = o_flat + align256(n * (size_t)hint * 8),
-                 o_plen = o_tmp + align256(tmp), o_poff = o_plen + (H ? w : 0), o_pflat = o_poff + (H ? w : 0), bytes = o_pflat + (H ? align256(n * (size_t)phint * 8) : 0);
+                 o_plen = o_tmp + align256(tmp), o_poff = o_plen + (H ? w : 0), o_pflat = o_poff + (H ? w : 0), o_hv = o_pflat + (H ? align256(n * (size_t)phint * 8) : 0), bytes = o_hv + hv_bytes;
     if (bytes > s->ws_bytes) {   // (the previous call may still read the scratch: wait for it before it is freed)
         HIP_TRY(hipEventSynchronize(s->last));
         if ((rc = ensure(&s->ws, &s->ws_bytes, bytes))) return rc;
@@ -710,6 +757,11 @@ int dsess_recommend_device(const srn_index* idx, srn_device_sessions* s, const u
     a.kex = (uint32_t*)(b + o_kex); a.run_start = (uint32_t*)(b + o_run); a.qlen = (uint32_t*)(b + o_qlen); a.q_off = (uint32_t*)(b + o_qoff);
     a.compact = (uint64_t*)(b + o_comp); a.items_flat = (uint64_t*)(b + o_flat); a.err = s->err();
     sess_find<<<gn1, kTPB, 0, st>>>(a);
+    if (hv) {   // the stored sessions the heads found idle, copied before sess_store overwrites their slots
+        sess_return_flag<<<gn1, kTPB, 0, st>>>(a, hv->min_len, (uint64_t*)(b + o_hv));
+        HIP_TRY(hipGetLastError());
+        if ((rc = harvest_append(hv, a.t, a.slot_of, n, b + o_hv, true, st))) return rc;
+    }
     t1 = tmp; HIP_TRY(rocprim::exclusive_scan(b + o_tmp, t1, a.kept, a.kex, 0u, n + 1, rocprim::plus<uint32_t>(), st));
     t1 = tmp; HIP_TRY(rocprim::inclusive_scan(b + o_tmp, t1, a.headpos, a.run_start, n, rocprim::maximum<uint32_t>(), st));
     sess_len<<<gn1, kTPB, 0, st>>>(a);

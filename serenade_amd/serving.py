@@ -407,6 +407,17 @@ class DeviceSessionStore:
         capi.check(capi.lib().srn_device_sessions_sweep(self._h, int(now), C.byref(n)))
         return n.value
 
+    def set_harvest(self, harvest):
+        """srn_device_sessions_set_harvest: from now on `harvest` (a SessionHarvest) receives every session the store forgets -- a visitor's return after idle inside
+        recommend_batch, and what a sweep, the capacity rule's automatic sweep, a resize or growth drops.  None detaches.  Nothing else about the store changes."""
+        capi.check(capi.lib().srn_device_sessions_set_harvest(self._h, None if harvest is None else harvest._h))
+        old = getattr(self, "_harvest", None)
+        if old is not None:
+            old._store = None
+        self._harvest = harvest
+        if harvest is not None:
+            harvest._store = self
+
     @property
     def stats(self):
         st = capi.DeviceSessionsStats()
@@ -436,10 +447,196 @@ class DeviceSessionStore:
 
     def close(self):
         if getattr(self, "_h", None) and capi is not None and getattr(capi, "lib", None) is not None:
-            capi.lib().srn_device_sessions_free(self._h)
+            capi.lib().srn_device_sessions_free(self._h)                # (detaches an attached harvest)
+            self._h = None
+            if getattr(self, "_harvest", None) is not None:
+                self._harvest._store, self._harvest = None, None
+
+    __del__ = close
+
+
+# ---- session harvest: finished sessions logged on the GPU, and an index rebuilt from them (srn_harvest_*) ----
+_HARVEST_COUNTERS = ("stored", "stored_items", "lost", "skipped_short", "from_return", "from_rebuild")
+
+
+def harvest_model(state, keys, items, consent, now, *, limit=2, idle_secs=20 * 60, ttl_secs=30 * 60, min_len=1, capacity=None, sweep=False):
+    """Pure-Python statement of the session harvest (srn_harvest.hip): a dictionary replay of the /v1/recommend handler's rule that keeps what the
+    store forgets.  It needs no GPU and no library.
+    state: dict, updated in place: 128-bit key -> (items list, epoch) for every stored session, and under the key "log" the harvest itself (created on first use).
+    One call is one recommend_batch call at `now` -- keys = (hi, lo), items, consent (None: all consent); keys = None: no requests -- followed, with sweep=True, by
+    store.sweep(now).  Requests j = 0..n-1 in order:
+      no consent                              nothing is read or stored
+      the key is stored with len > 0 and now > epoch and now - epoch > idle_secs (strict): the stored session is OFFERED (a return after idle) and the visitor
+                                              starts from an empty session
+      then the click is appended unless it repeats the session's last item; beyond `limit` items (max_items_in_session, or the store's history window H) the
+      oldest one is dropped; the session is stored with epoch = now
+    A sweep offers and removes every stored session with now > epoch and now - epoch > ttl_secs.  An offered session of fewer than min_len items is counted in
+    skipped_short; one offered when the log holds `capacity` sessions (None: unbounded) in lost; every other one is stored with its epoch and items as they were.
+    The log is appended in the device's order: the returns of one call in ascending key order (not request order), so the result does not depend on how the requests
+    of one time step are cut into calls.  A sweep's sessions are appended in ascending key order here and in slot order on the device: which of them a FULL log loses
+    is the one thing this model does not predict.
+    -> (sessions, counters): the stored sessions as (key, epoch, [items]) tuples in canonical order -- (epoch, key) ascending -- and the words of SessionHarvest.stats()
+    plus "append_order": the same tuples in the order they were stored."""
+    log = state.setdefault("log", {"sessions": [], "lost": 0, "skipped_short": 0, "from_return": 0, "from_rebuild": 0})
+    now, min_len = int(now), max(int(min_len), 1)
+
+    def offer(found, which):
+        for key, (its, epoch) in sorted(found, key=lambda e: e[0]):
+            log[which] += 1
+            if len(its) < min_len:
+                log["skipped_short"] += 1
+            elif capacity is not None and len(log["sessions"]) >= capacity:
+                log["lost"] += 1
+            else:
+                log["sessions"].append((key, int(epoch), [int(x) for x in its]))
+
+    if keys is not None:
+        hi, lo = (np.asarray(a, np.uint64) for a in keys)
+        items = np.asarray(items, np.uint64)
+        if not (len(hi) == len(lo) == len(items)) or (consent is not None and len(consent) != len(items)):
+            raise ValueError("keys, items and consent differ in length")
+        returned = []
+        for j in range(len(items)):
+            if consent is not None and not consent[j]:
+                continue
+            key = (int(hi[j]) << 64) | int(lo[j])
+            cur, epoch = state.get(key, ([], 0))
+            if cur and now > epoch and now - epoch > idle_secs:
+                returned.append((key, (cur, epoch)))
+                cur = []
+            item = int(items[j])
+            if not cur or cur[-1] != item:
+                cur = cur + [item]
+                if len(cur) > limit:
+                    cur = cur[1:]
+            state[key] = (cur, now)
+        offer(returned, "from_return")
+    if sweep:
+        old = [(k, v) for k, v in state.items() if k != "log" and now > v[1] and now - v[1] > ttl_secs]
+        for k, _ in old:
+            del state[k]
+        offer(old, "from_rebuild")
+    counters = {n: log[n] for n in ("lost", "skipped_short", "from_return", "from_rebuild")}
+    counters["stored"], counters["stored_items"] = len(log["sessions"]), sum(len(s[2]) for s in log["sessions"])
+    counters["append_order"] = list(log["sessions"])
+    return sorted(log["sessions"], key=lambda s: (s[1], s[0])), counters
+
+
+class SessionHarvest:
+    """A session harvest in the GPU's memory (srn_harvest_*): the log that receives every session a DeviceSessionStore forgets, once, on the serving call's stream.
+    store.set_harvest(hv) attaches it; export / events read it in canonical order -- (epoch, key) ascending -- without consuming it."""
+
+    def __init__(self, index_or_device, capacity, items_cap=16, min_len=1):
+        device = index_or_device if isinstance(index_or_device, int) else index_or_device.info["device"]
+        h = C.c_void_p()
+        capi.check(capi.lib().srn_harvest_create(int(device), int(capacity), int(items_cap), int(min_len), C.byref(h)))
+        self._h, self.device, self.capacity, self.items_cap = h, int(device), int(capacity), int(items_cap)
+        self._store = None
+
+    def stats(self):
+        """srn_harvest_stats_t as a dict (blocks): capacity, items_cap, min_len; stored, stored_items -- what the log holds now; lost, skipped_short, from_return,
+        from_rebuild, cleared.  from_return + from_rebuild = stored + cleared + lost + skipped_short."""
+        st = capi.HarvestStats()
+        capi.check(capi.lib().srn_harvest_stats(self._h, C.byref(st)))
+        return {n: getattr(st, n) for n, _ in capi.HarvestStats._fields_}
+
+    def export(self, device=False):
+        """The stored sessions in canonical order -> (hi, lo), epoch, len, items[n, items_cap] (zero beyond len), like DeviceSessionStore.export.  NumPy arrays, or with
+        device=True tensors on the harvest's GPU, written on the current stream."""
+        L, stride = capi.lib(), self.items_cap
+        cap = int(self.stats()["stored"])
+        while True:
+            if device:
+                import torch
+                dev = torch.device("cuda", self.device)
+                hi, lo, ep = (torch.zeros(cap, dtype=torch.int64, device=dev) for _ in range(3))
+                ln = torch.zeros(cap, dtype=torch.int32, device=dev)
+                it = torch.zeros((cap, stride), dtype=torch.int64, device=dev)
+                d_n = torch.zeros(1, dtype=torch.int64, device=dev)
+                stream = torch.cuda.current_stream(self.device).cuda_stream
+                capi.check(L.srn_harvest_export_device(self._h, cap, *(C.c_void_p(t.data_ptr()) for t in (hi, lo, ep, ln, it)), stride, C.c_void_p(d_n.data_ptr()),
+                                                       C.c_void_p(stream)))
+                n = int(d_n.item())
+            else:
+                hi, lo, ep = (np.zeros(cap, np.uint64) for _ in range(3))
+                ln, it, got = np.zeros(cap, np.uint32), np.zeros((cap, stride), np.uint64), C.c_size_t()
+                rc = L.srn_harvest_export(self._h, cap, capi.ptr(hi), capi.ptr(lo), capi.ptr(ep), capi.ptr(ln), capi.ptr(it), stride, C.byref(got))
+                n = got.value
+                if rc != 0 and not (rc == capi.SRN_ERANGE and n > cap):
+                    capi.check(rc)
+            if n <= cap:                                    # (more: sessions arrived between the count and the export)
+                return (hi[:n], lo[:n]), ep[:n], ln[:n], it[:n]
+            cap = n
+
+    def events(self, id_base=0):
+        """srn_harvest_events_device: the stored sessions as training rows -> (session_ids, item_ids, times), int64 tensors on the harvest's GPU, written on the current
+        stream: canonical session i has the id id_base + i and one row per item, in session order, each with time = the session's epoch.  What
+        VMISIndex.from_events / TrainingSessions.from_events read."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        cap = int(self.stats()["stored_items"])
+        while True:
+            sid, item, t = (torch.zeros(cap, dtype=torch.int64, device=dev) for _ in range(3))
+            d_rows = torch.zeros(1, dtype=torch.int64, device=dev)
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            capi.check(capi.lib().srn_harvest_events_device(self._h, int(id_base), cap, *(C.c_void_p(x.data_ptr()) for x in (sid, item, t, d_rows)), C.c_void_p(stream)))
+            n = int(d_rows.item())
+            if n <= cap:
+                return sid[:n], item[:n], t[:n]
+            cap = n
+
+    def clear(self):
+        """Empties the log (stored sessions move to stats()["cleared"]); lost, skipped_short, from_return and from_rebuild keep running."""
+        capi.check(capi.lib().srn_harvest_clear(self._h))
+
+    def close(self):
+        if getattr(self, "_h", None) and capi is not None and getattr(capi, "lib", None) is not None:
+            store = getattr(self, "_store", None)
+            if store is not None and getattr(store, "_h", None):
+                store.set_harvest(None)
+            capi.lib().srn_harvest_free(self._h)
             self._h = None
 
     __del__ = close
+
+
+def refreshed_index(base_session_ids, base_item_ids, base_times, harvest, m_most_recent_sessions, idf_weighting, max_session_len=0, device=0):
+    """The index of the base training events with the harvested sessions appended: exactly VMISIndex.from_events over the base arrays (NumPy, CPU tensors or tensors
+    on `device`, as from_events takes them) followed by harvest.events(id_base=max(base_session_ids) + 1), concatenated on the device.  That is what
+    VMISIndex.new_from_csv gives for the training file with those rows appended -- read_from_file's quirk included: the file's final row closes its session and the
+    last session is dropped, so the most recent harvested session does not enter the index.  The harvested times are epochs in seconds; base times above them are the
+    caller's business.  The harvest is not consumed."""
+    import torch
+    from .vmisknn import VMISIndex
+    if harvest.device != int(device):
+        raise ValueError("the harvest is on device %d, not %d" % (harvest.device, int(device)))
+    dev = torch.device("cuda", int(device))
+
+    def on_device(a, floating_ok=False):
+        if not _is_torch(a):
+            a = np.ascontiguousarray(a)
+            if np.issubdtype(a.dtype, np.floating):
+                a = a.astype(np.float64, copy=False)
+            else:
+                a = a.astype(np.uint64, copy=False).view(np.int64) if a.dtype == np.uint64 else a.astype(np.int64, copy=False)
+            a = torch.from_numpy(a)
+        if a.dtype == getattr(torch, "uint64", None):
+            a = a.view(torch.int64)
+        if a.is_floating_point():
+            if not floating_ok:
+                raise TypeError("session and item ids must be integers")
+            a = a.to(torch.float64)
+        elif a.dtype != torch.int64:
+            a = a.to(torch.int64)
+        return a.to(dev).contiguous()
+
+    sid, item, t = on_device(base_session_ids), on_device(base_item_ids), on_device(base_times, True)
+    if not (sid.numel() == item.numel() == t.numel()):
+        raise ValueError("the base arrays differ in length")
+    id_base = int(sid.max().item()) + 1 if sid.numel() else 0           # (session ids below 2^63, as everywhere a tensor carries them)
+    h_sid, h_item, h_t = harvest.events(id_base)
+    return VMISIndex.from_events(torch.cat([sid, h_sid]), torch.cat([item, h_item]), torch.cat([t, h_t.to(t.dtype)]), m_most_recent_sessions, idf_weighting,
+                                 max_session_len=max_session_len, device=int(device))
 
 
 # ---- click feedback: served rows scored against the visitor's next click (srn_feedback_*, DESIGN.md 11.4) ----

@@ -1,0 +1,372 @@
+"""Session harvest on the GPU (srn_harvest_*, serving.SessionHarvest): every session the device store forgets arrives in the log exactly once.
+Exports, counters and training events are compared exactly with serving.harvest_model; an index refreshed from the harvest equals new_from_csv on the training
+file with the harvested rows appended."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import serenade_amd as sa
+from serenade_amd import capi
+from serenade_amd.serving import DeviceSessionStore, SessionHarvest, harvest_model, recommend_batch, refreshed_index
+
+import harvest_cases as hc
+from helpers import small_dataset
+
+pytestmark = pytest.mark.gpu
+
+K, M, HOW_MANY = 50, 200, 21
+IDLE, TTL, T0, FAR = hc.IDLE, hc.TTL, hc.T0, hc.FAR
+COUNTERS = ("stored", "stored_items", "lost", "skipped_short", "from_return", "from_rebuild")
+
+
+@pytest.fixture(scope="module")
+def index():
+    off, items, ts, _ = small_dataset(33, n_sessions=1500, n_items=200)
+    gix = sa.VMISIndex.from_sessions(off, items, ts, 200, 12, 1.0)
+    yield gix
+    gix.close()
+
+
+def code_of(fn):
+    with pytest.raises(capi.SerenadeError) as e:
+        fn()
+    return e.value.code
+
+
+def same_export(a, b):
+    return all(np.array_equal(x, y) for x, y in zip((a[0][0], a[0][1]) + tuple(a[1:]), (b[0][0], b[0][1]) + tuple(b[1:])))
+
+
+def export_bytes(e):
+    return b"".join(np.ascontiguousarray(x).tobytes() for x in (e[0][0], e[0][1]) + tuple(e[1:]))
+
+
+def by_key(e):
+    """a store's export with its entries in ascending (key_hi, key_lo) order"""
+    order = np.lexsort((e[0][1], e[0][0]))
+    return (e[0][0][order], e[0][1][order]), e[1][order], e[2][order], e[3][order]
+
+
+def keys_of(e):
+    return [(int(h) << 64) | int(l) for h, l in zip(e[0][0], e[0][1])]
+
+
+_SERVED = {}
+
+
+def served(index, history, parts, with_harvest):
+    """the stream of harvest_cases served once per (history, parts, with_harvest) -> what the tests compare (computed once, never changed)"""
+    key = (history, parts, with_harvest)
+    if key in _SERVED:
+        return _SERVED[key]
+    steps = hc.make_stream()
+    store = DeviceSessionStore(index, capacity=512, items_cap=8, ttl_secs=TTL, idle_secs=IDLE, history=history)
+    hv = None
+    if with_harvest:
+        hv = SessionHarvest(index, capacity=256, items_cap=8, min_len=2)
+        store.set_harvest(hv)
+    rows = []
+    for st in steps:
+        for sl in hc.cut(st, parts):
+            if sl.stop > sl.start:
+                rows.append(recommend_batch(index, store, (st["hi"][sl], st["lo"][sl]), st["items"][sl], st["consent"][sl], k=K, m=M, how_many=HOW_MANY,
+                                            max_items_in_session=2, now=st["now"], scores=True))
+        if st["sweep"]:
+            store.sweep(st["now"])
+    before_last = store.export(now=1)
+    store.sweep(FAR)
+    out = dict(rows=[np.concatenate([r[i] for r in rows]) for i in range(3)], store=before_last, store_after=store.export(now=1), sweeps=store.stats["sweeps"])
+    if hv is not None:
+        out["export"], out["stats"] = hv.export(), hv.stats()
+        dev = hv.export(device=True)
+        out["export_device"] = ((dev[0][0].cpu().numpy().view(np.uint64), dev[0][1].cpu().numpy().view(np.uint64)), dev[1].cpu().numpy().view(np.uint64),
+                                dev[2].cpu().numpy().view(np.uint32), dev[3].cpu().numpy().view(np.uint64))
+        hv.close()
+    store.close()
+    _SERVED[key] = out
+    return out
+
+
+@pytest.mark.parametrize("history", [0, 6])
+def test_replay_equals_the_model(index, history):
+    """~2 000 requests over 40 time steps, one call per step and every step cut into three calls: the export, in canonical order, and the counters are the model's;
+    the two cuts give the same bytes."""
+    limit = history or 2
+    want, ctr, props = hc.replay(hc.make_stream(), 1, limit=limit, min_len=2)
+    assert props["return_at_run_head"] >= 1 and props["by_explicit_sweep"] >= 1 and ctr["skipped_short"] >= 1      # the stream produced every case (the model says so)
+    assert ctr["stored"] <= 256 and ctr["lost"] == 0
+    want = hc.as_arrays(want, 8)
+    got = {parts: served(index, history, parts, True) for parts in (1, 3)}
+    for parts, g in got.items():
+        e = g["export"]
+        assert len(e[1]) == ctr["stored"], (parts, len(e[1]), ctr["stored"])
+        for name, x, y in zip(("key_hi", "key_lo", "epoch", "len", "items"), (e[0][0], e[0][1]) + tuple(e[1:]), (want[0][0], want[0][1]) + tuple(want[1:])):
+            assert np.array_equal(x, y), (parts, name, np.flatnonzero((x != y).reshape(len(x), -1).any(axis=1))[:8])
+        for name in COUNTERS:
+            assert g["stats"][name] == ctr[name], (parts, name, g["stats"][name], ctr[name])
+        s = g["stats"]
+        assert s["from_return"] + s["from_rebuild"] == s["stored"] + s["lost"] + s["skipped_short"] and s["cleared"] == 0
+        assert (s["capacity"], s["items_cap"], s["min_len"]) == (256, 8, 2)
+        assert same_export(g["export_device"], e)
+        assert len(g["store_after"][1]) == 0
+    assert export_bytes(got[1]["export"]) == export_bytes(got[3]["export"])
+    if history:
+        assert int(got[1]["export"][2].max()) > 2                                                                     # the window the slot held, not what predict read
+
+
+@pytest.mark.parametrize("history", [0, 6])
+def test_an_attached_harvest_changes_nothing_served(index, history):
+    for parts in (1, 3):
+        a, b = served(index, history, parts, True), served(index, history, parts, False)
+        for x, y in zip(a["rows"], b["rows"]):
+            assert x.tobytes() == y.tobytes()
+        # the store's export is in slot order, and where two colliding keys land is decided by the claim races of sess_find and sess_rebuild: two stores
+        # driven alike hold the same entries, not always in the same slots.  The entries are therefore compared in key order, every array exactly
+        assert export_bytes(by_key(a["store"])) == export_bytes(by_key(b["store"])) and len(a["store"][1]) > 0
+        assert a["sweeps"] == b["sweeps"]
+
+
+def fill(index, store, lo_keys, now, clicks=(11, 12, 13), hi=5):
+    """every key clicks `clicks`, one call per click (the capacity rule counts a call's requests as new keys)"""
+    lo = np.asarray(lo_keys, np.uint64)
+    for c in clicks:
+        recommend_batch(index, store, (np.full(len(lo), hi, np.uint64), lo), np.full(len(lo), c, np.uint64), None, k=K, m=M, how_many=HOW_MANY,
+                        max_items_in_session=3, now=now)
+
+
+def test_the_other_rebuild_sites(index):
+    """growth, an explicit resize and the capacity rule's automatic sweep hand over what they drop, once; a refused resize hands over nothing"""
+    store = DeviceSessionStore(index, capacity=100, items_cap=4, ttl_secs=TTL, idle_secs=IDLE, max_capacity=400)
+    hv = SessionHarvest(index, capacity=256, items_cap=4, min_len=1)
+    store.set_harvest(hv)
+    fill(index, store, range(100, 130), T0)
+    fill(index, store, range(200, 230), T0 + 25)
+    assert hv.stats()["stored"] == 0
+    # growth: at T0 + 40 the first thirty are older than the TTL and 30 live + 75 new keys pass the capacity
+    fill(index, store, range(300, 375), T0 + 40)
+    assert store.growth()["grows"] == 1 and store.stats["capacity"] == 200 and store.stats["sweeps"] == 0
+    e = hv.export()
+    assert sorted(keys_of(e)) == [(5 << 64) | k for k in range(100, 130)] and set(e[1].tolist()) == {T0} and set(e[2].tolist()) == {3}
+    assert np.array_equal(e[3], np.tile(np.array([11, 12, 13, 0], np.uint64), (30, 1)))
+    s = hv.stats()
+    assert (s["stored"], s["from_rebuild"], s["from_return"], s["stored_items"]) == (30, 30, 0, 90)
+    # refused resizes: too many live sessions, a live session longer than the new items_cap, an items_cap above the harvest's -- nothing arrives
+    now = T0 + 60                                                                  # the second thirty are now older than the TTL, the 75 are live
+    assert code_of(lambda: store.resize(16, now=now)) == capi.SRN_ENOMEM
+    assert code_of(lambda: store.resize(200, items_cap=2, now=now)) == capi.SRN_ERANGE
+    assert code_of(lambda: store.resize(200, items_cap=5, now=now)) == capi.SRN_ERANGE
+    assert hv.stats() == s and store.count(1).occupied == 105
+    # an explicit resize drops the second thirty
+    store.resize(256, now=now)
+    e2 = hv.export()
+    new = sorted(set(keys_of(e2)) - set(keys_of(e)))
+    assert len(e2[1]) == 60 and new == [(5 << 64) | k for k in range(200, 230)] and len(set(zip(keys_of(e2), e2[1].tolist()))) == 60
+    assert store.count(1).occupied == 75 and hv.stats()["from_rebuild"] == 60
+    # the capacity rule's automatic sweep: a small store whose bound is reached while everything in it is old
+    small = DeviceSessionStore(index, capacity=48, items_cap=4, ttl_secs=TTL, idle_secs=IDLE)
+    hv2 = SessionHarvest(index, capacity=64, items_cap=8, min_len=1)               # (a harvest may be wider than its store)
+    small.set_harvest(hv2)
+    fill(index, small, range(400, 420), T0, clicks=(21, 22))
+    fill(index, small, range(500, 530), T0 + 100, clicks=(23,))
+    assert small.stats["sweeps"] == 1 and small.growth()["resizes"] == 0
+    e3 = hv2.export()
+    assert keys_of(e3) == [(5 << 64) | k for k in range(400, 420)] and set(e3[2].tolist()) == {2} and hv2.stats()["from_rebuild"] == 20
+    assert np.array_equal(e3[3][:, :3], np.tile(np.array([21, 22, 0], np.uint64), (20, 1)))
+    for o in (store, small, hv, hv2):
+        o.close()
+
+
+def test_an_import_that_grows_the_store_with_a_harvest_attached(index):
+    """growth below an import: the rebuild's append runs inside the import's capacity rule, while the import holds its sort scratch -- the table is large next to
+    the import, so the append's per-slot scratch is the larger one.  The imported entries arrive whole, the harvest is offered nothing (an import reclaims nothing),
+    and a later sweep hands over every entry once"""
+    store = DeviceSessionStore(index, capacity=1024, items_cap=4, ttl_secs=TTL, idle_secs=IDLE, max_capacity=4096)
+    hv = SessionHarvest(index, capacity=2048, items_cap=4, min_len=1)
+    store.set_harvest(hv)
+    rng = np.random.default_rng(23)
+    n = 512 + 513
+    hi, lo = rng.integers(0, 4, n).astype(np.uint64), rng.permutation(np.arange(1, n + 1, dtype=np.uint64))
+    ep = (T0 + rng.integers(0, 10, n)).astype(np.uint64)
+    ln = rng.integers(1, 5, n).astype(np.uint32)
+    it = rng.integers(1, 1000, (n, 4)).astype(np.uint64) * (np.arange(4)[None, :] < ln[:, None])
+    entries = lambda sl: ((hi[sl], lo[sl]), ep[sl], ln[sl], it[sl])   # noqa: E731
+    store.import_entries(*entries(slice(0, 512)))                               # half full
+    assert store.growth()["grows"] == 0 and hv.stats()["from_rebuild"] == 0
+    store.import_entries(*entries(slice(512, n)))                               # capacity / 2 + 1 more: growth
+    assert store.growth()["grows"] == 1 and store.stats["capacity"] == 2048
+    s = hv.stats()
+    assert (s["stored"], s["from_rebuild"], s["from_return"], s["skipped_short"], s["lost"]) == (0, 0, 0, 0, 0)
+    assert export_bytes(by_key(store.export(now=1))) == export_bytes(by_key(entries(slice(0, n))))
+    import torch
+    dev = torch.device("cuda", index.info["device"])
+    more = ((np.full(600, 9, np.uint64), np.arange(1, 601, dtype=np.uint64)), np.full(600, T0 + 5, np.uint64), np.full(600, 2, np.uint32),
+            np.tile(np.array([7, 8, 0, 0], np.uint64), (600, 1)))
+    t = [torch.from_numpy(a.view(np.int64 if a.dtype == np.uint64 else np.int32)).to(dev) for a in (more[0][0], more[0][1], more[1], more[2], more[3])]
+    store2 = DeviceSessionStore(index, capacity=1024, items_cap=4, ttl_secs=TTL, idle_secs=IDLE, max_capacity=4096)
+    hv2 = SessionHarvest(index, capacity=2048, items_cap=4, min_len=1)
+    store2.set_harvest(hv2)
+    store2.import_entries(*entries(slice(0, 512)))
+    store2.import_entries((t[0], t[1]), t[2], t[3], t[4])                       # the device-pointer form, on the current stream
+    torch.cuda.current_stream(index.info["device"]).synchronize()
+    assert store2.growth()["grows"] == 1 and hv2.stats()["from_rebuild"] == 0
+    both = ((np.concatenate([hi[:512], more[0][0]]), np.concatenate([lo[:512], more[0][1]])), np.concatenate([ep[:512], more[1]]), np.concatenate([ln[:512], more[2]]),
+            np.concatenate([it[:512], more[3]]))
+    assert export_bytes(by_key(store2.export(now=1))) == export_bytes(by_key(both))
+    store.sweep(FAR)
+    e = hv.export()
+    s = hv.stats()
+    assert (s["stored"], s["from_rebuild"], s["stored_items"]) == (n, n, int(ln.sum())) and store.count(1).occupied == 0
+    want = np.lexsort((lo, hi, ep))                                             # canonical: epoch, then key
+    assert export_bytes(e) == export_bytes(((hi[want], lo[want]), ep[want], ln[want], it[want]))
+    for o in (store, store2, hv, hv2):
+        o.close()
+
+
+def test_overflow_is_counted_and_the_call_is_served(index):
+    stores = [DeviceSessionStore(index, capacity=128, items_cap=4, ttl_secs=TTL, idle_secs=IDLE) for _ in range(2)]
+    hv = SessionHarvest(index, capacity=8, items_cap=4, min_len=1)
+    stores[0].set_harvest(hv)
+    rng = np.random.default_rng(5)
+    lo = rng.integers(1, 2 ** 63, 20, dtype=np.uint64)
+    hi = rng.integers(0, 3, 20).astype(np.uint64)
+    state, model = {}, None
+    calls = [(T0, (31, 32)), (T0 + IDLE + 5, (33,))]                               # every visitor returns after idle, in one call: 20 sessions offered by (R)
+    for now, clicks in calls:
+        khi, klo = np.repeat(hi, len(clicks)), np.repeat(lo, len(clicks))
+        its = np.tile(np.asarray(clicks, np.uint64), 20)
+        rows = [recommend_batch(index, s, (khi, klo), its, None, k=K, m=M, how_many=HOW_MANY, max_items_in_session=3, now=now, scores=True) for s in stores]
+        for x, y in zip(*rows):
+            assert x.tobytes() == y.tobytes()                                      # the call is served as without a harvest, full log or not
+        model = harvest_model(state, (khi, klo), its, None, now, limit=3, idle_secs=IDLE, ttl_secs=TTL, min_len=1, capacity=8)
+    s = hv.stats()
+    assert (s["stored"], s["lost"], s["from_return"], s["stored_items"]) == (8, 12, 20, 16)
+    assert model[1]["stored"] == 8 and model[1]["lost"] == 12
+    want = hc.as_arrays(model[1]["append_order"], 4)                               # the first 8 in append order; with one epoch that is also the canonical order
+    assert same_export(hv.export(), want) and model[1]["append_order"] == model[0]
+    hv.clear()
+    s = hv.stats()
+    assert (s["stored"], s["stored_items"], s["cleared"], s["lost"]) == (0, 0, 8, 12) and len(hv.export()[1]) == 0
+    stores[0].sweep(FAR)
+    s = hv.stats()
+    assert (s["stored"], s["cleared"], s["lost"], s["from_rebuild"]) == (8, 8, 24, 20)
+    e = hv.export()
+    assert set(e[1].tolist()) == {T0 + IDLE + 5} and np.array_equal(e[3], np.tile(np.array([33, 0, 0, 0], np.uint64), (8, 1)))
+    assert s["from_return"] + s["from_rebuild"] == s["stored"] + s["cleared"] + s["lost"] + s["skipped_short"]
+    for o in stores + [hv]:
+        o.close()
+
+
+def test_argument_and_state_errors(index):
+    L = capi.lib()
+    dev = index.info["device"]
+    assert code_of(lambda: SessionHarvest(dev, capacity=0)) == capi.SRN_EINVAL
+    assert code_of(lambda: SessionHarvest(dev, capacity=8, items_cap=0)) == capi.SRN_EINVAL
+    assert code_of(lambda: SessionHarvest(dev, capacity=8, items_cap=capi.MAX_SESSION_LEN + 1)) == capi.SRN_ERANGE
+    assert code_of(lambda: SessionHarvest(dev, capacity=2 ** 30 + 1)) == capi.SRN_ERANGE
+    assert code_of(lambda: SessionHarvest(capi.device_count() + 7, capacity=8)) == capi.SRN_ENODEV
+    assert L.srn_harvest_create(dev, 8, 4, 1, None) == capi.SRN_EINVAL and L.srn_harvest_free(None) == capi.SRN_OK
+    assert L.srn_device_sessions_set_harvest(None, None) == capi.SRN_EINVAL and L.srn_harvest_stats(None, None) == capi.SRN_EINVAL
+    assert L.srn_harvest_clear(None) == capi.SRN_EINVAL
+    a, b = (DeviceSessionStore(dev, capacity=32, items_cap=6, ttl_secs=TTL, idle_secs=IDLE) for _ in range(2))
+    hv, other, narrow = SessionHarvest(dev, 16, items_cap=8, min_len=0), SessionHarvest(dev, 16, items_cap=8), SessionHarvest(dev, 16, items_cap=5)
+    assert hv.stats()["min_len"] == 1                                              # 0 is read as 1
+    assert code_of(lambda: a.set_harvest(narrow)) == capi.SRN_ERANGE               # items_cap below the store's
+    a.set_harvest(None)                                                            # nothing attached: fine
+    a.set_harvest(hv)
+    assert code_of(lambda: b.set_harvest(hv)) == capi.SRN_ESTATE                   # one harvest, one store
+    assert code_of(lambda: a.set_harvest(hv)) == capi.SRN_ESTATE
+    assert code_of(lambda: a.set_harvest(other)) == capi.SRN_ESTATE                # one store, one harvest
+    assert L.srn_harvest_free(hv._h) == capi.SRN_ESTATE                            # attached
+    assert code_of(lambda: a.resize(32, items_cap=9)) == capi.SRN_ERANGE and a.stats["items_cap"] == 6
+    a.resize(32, items_cap=8)
+    if capi.device_count() > 1:
+        far = DeviceSessionStore(1 - dev if dev < 2 else 0, capacity=32, items_cap=6)
+        assert code_of(lambda: far.set_harvest(other)) == capi.SRN_EINVAL
+        far.close()
+    fill(index, a, range(4), T0)
+    a.sweep(FAR)
+    n = C.c_size_t()
+    buf = [np.zeros(4, np.uint64) for _ in range(3)] + [np.zeros(4, np.uint32), np.zeros((4, 8), np.uint64)]
+    p = [capi.ptr(x) for x in buf]
+    assert L.srn_harvest_export(hv._h, 3, *p, 8, C.byref(n)) == capi.SRN_ERANGE and n.value == 4 and not buf[0].any()
+    assert L.srn_harvest_export(hv._h, 4, *p, 7, C.byref(n)) == capi.SRN_ERANGE
+    assert L.srn_harvest_export(hv._h, 4, *p, 8, None) == capi.SRN_EINVAL and L.srn_harvest_export(hv._h, 4, None, *p[1:], 8, C.byref(n)) == capi.SRN_EINVAL
+    assert L.srn_harvest_export(hv._h, 4, *p, 8, C.byref(n)) == capi.SRN_OK and n.value == 4 and buf[3].tolist() == [3] * 4
+    assert L.srn_harvest_export_device(hv._h, 4, None, None, None, None, None, 8, None, None) == capi.SRN_EINVAL
+    assert L.srn_harvest_events_device(hv._h, 0, 4, None, None, None, None, None) == capi.SRN_EINVAL
+    a.set_harvest(None)                                                            # detached: it keeps what it holds, and goes to another store
+    assert hv.stats()["stored"] == 4 and len(hv.export()[1]) == 4
+    b.set_harvest(hv)
+    b.close()                                                                      # freeing the store detaches
+    assert hv._store is None and hv.stats()["stored"] == 4
+    a.set_harvest(hv)
+    for o in (hv, a, other, narrow):                                               # (closing an attached harvest detaches it first)
+        o.close()
+
+
+HEADER = "SessionId\tItemId\tTime\n"
+
+
+def test_events_and_refresh_end_to_end(index, tmp_path):
+    """today's sessions become training data: the refreshed index is new_from_csv on the training file with the harvested rows appended, and it knows item X"""
+    rng = np.random.default_rng(17)
+    pool = np.arange(1, 61, dtype=np.uint64) * np.uint64(101)
+    A, X = int(pool[3]), 999_001
+    n_base = 300
+    lens = rng.integers(2, 7, n_base)
+    b_sid = np.repeat(np.arange(1, n_base + 1, dtype=np.uint64), lens)
+    b_item = pool[rng.integers(0, len(pool), len(b_sid))]
+    b_time = (1_600_000_000 + np.repeat(np.arange(n_base) * 50, lens) + rng.integers(0, 40, len(b_sid))).astype(np.int64)
+    rows = lambda s, i, t: "".join("%d\t%d\t%d\n" % r for r in zip(s.tolist(), i.tolist(), t.tolist()))
+    base_path = tmp_path / "base.tsv"
+    base_path.write_text(HEADER + rows(b_sid, b_item, b_time))
+    m, idfw, k = 100, 1.0, 50
+    base = sa.VMISIndex.new_from_csv(str(base_path), m, idfw, device=0, loader="host")
+    ids, _, cnt = sa.predict_batch(base, [[X], [A]], k, m, HOW_MANY)
+    assert cnt[0] == 0 and cnt[1] > 0 and X not in ids[1, :cnt[1]].tolist() and base.postings(X)[0] is None
+    # today: 30 visitors, most of them click A and X together
+    store = DeviceSessionStore(base, capacity=256, items_cap=4, ttl_secs=TTL, idle_secs=IDLE)
+    hv = SessionHarvest(base, capacity=128, items_cap=4, min_len=2)
+    store.set_harvest(hv)
+    lo = rng.integers(1, 2 ** 63, 30, dtype=np.uint64)
+    hi = rng.integers(0, 2, 30).astype(np.uint64)
+    for step in range(6):
+        now = T0 + 7 * step
+        who = np.flatnonzero(rng.random(30) < 0.6)
+        clicks = np.where((who + step) % 3 == 0, np.uint64(X), np.where((who + step) % 3 == 1, np.uint64(A), pool[rng.integers(0, len(pool), len(who))]))
+        recommend_batch(base, store, (hi[who], lo[who]), clicks.astype(np.uint64), None, k=k, m=m, how_many=HOW_MANY, max_items_in_session=3, now=now)
+    store.sweep(FAR)
+    (ehi, elo), ep, ln, it = hv.export()
+    n = len(ep)
+    assert n >= 10 and hv.stats()["from_rebuild"] >= n
+    id_base = int(b_sid.max()) + 1
+    sid, item, t = (x.cpu().numpy() for x in hv.events(id_base))
+    assert np.array_equal(sid, np.repeat(np.arange(id_base, id_base + n), ln)) and np.array_equal(t, np.repeat(ep.astype(np.int64), ln))
+    assert np.array_equal(item.view(np.uint64), np.concatenate([it[i, :ln[i]] for i in range(n)])) and len(sid) == hv.stats()["stored_items"]
+    assert np.all(np.diff(ep.astype(np.int64)) >= 0) and keys_of(((ehi, elo),)) == [k_ for _, k_ in sorted(zip(ep.tolist(), keys_of(((ehi, elo),))))]
+    assert sum(1 for i in range(n - 1) if A in it[i, :ln[i]].tolist() and X in it[i, :ln[i]].tolist()) >= 3        # (the last session is dropped by the loader's quirk)
+    full_path = tmp_path / "full.tsv"
+    full_path.write_text(HEADER + rows(b_sid, b_item, b_time) + rows(sid, item, t))
+    want = sa.VMISIndex.new_from_csv(str(full_path), m, idfw, device=0, loader="host")
+    import torch
+    forms = {"numpy": (b_sid, b_item, b_time),
+             "torch_gpu": tuple(torch.from_numpy(a.view(np.int64)).to(torch.device("cuda", 0)) for a in (b_sid, b_item, b_time))}
+    queries = [[int(x) for x in pool[rng.integers(0, len(pool), int(rng.integers(1, 4)))]] + ([X] if q % 5 == 0 else []) for q in range(300)] + [[A], [X], [A, X]]
+    ref = sa.predict_batch(want, queries, k, m, HOW_MANY)
+    for name, (a, b, c) in forms.items():
+        got = refreshed_index(a, b, c, hv, m, idfw, device=0)
+        assert got.info == want.info, name
+        for x in [X] + pool.tolist():
+            pa, ia = got.postings(x)
+            pb, ib = want.postings(x)
+            assert (pa is None) == (pb is None) and (pb is None or (np.array_equal(pa, pb) and ia == ib)), (name, x)
+        res = sa.predict_batch(got, queries, k, m, HOW_MANY)
+        assert np.array_equal(res[0], ref[0]) and np.array_equal(res[2], ref[2]), name
+        np.testing.assert_allclose(res[1], ref[1], rtol=1e-12, atol=0)
+        row = res[0][300, :res[2][300]].tolist()
+        assert X in row, (name, row)                                                                                    # the new index returns X for [A]
+        got.close()
+    assert hv.stats()["stored"] == n                                                                                    # neither events nor the refresh consume the log
+    for o in (store, hv, want, base):
+        o.close()
