@@ -811,6 +811,26 @@ int srn_eval_set_from_tsv(const srn_index_t* idx, const char* test_path, const c
 int srn_evaluate(srn_eval_set_t* set, const srn_eval_trial_t* trials, size_t n_trials, srn_eval_result_t* out, void* stream);
 void srn_eval_set_free(srn_eval_set_t* set);
 
+/* ---- bootstrap confidence intervals for trials ------------------------------------------------------------
+ * srn_evaluate with a session-clustered Poisson bootstrap next to every trial: replicate b weighs all queries of test session s (its index in the set's order;
+ * sessions of one event give no query but keep their index) with
+ *   w(seed, b, s) = #{ i : T[i] <= u },  u = mix64( mix64(seed + (b + 1) * 0x9E3779B97F4A7C15) ^ (s * 0xD1B54A32D192ED03 + 1) ) >> 32     (mod 2^64)
+ *   T[i] = round(2^32 * P(Poisson(1) <= i)), i = 0..11 -- an integer in 0..12 that depends on (seed, b, s) alone: not on replicates, the trial, the index or the chunk.
+ * rep[t][b][0] = sum of the weights over the queries; rep[t][b][1..6] = the weighted sums of mrr, ndcg, hit_rate, popularity, precision, recall (the order of the
+ * sum_* fields).  The order of the additions is fixed: per group of 256 consecutive query indices from +0.0 in query order, acc = acc + (double)w * term (product
+ * rounded, then the sum), then the groups in order onto the total.  A replicate's seven doubles are the same bits from run to run, for any max_chunk_queries, alone or
+ * among other trials and for any replicates > b.  Coverage is not resampled.  Only the rep array comes back beside the results; device memory beyond srn_evaluate's:
+ * the totals (n_trials * replicates * 7 doubles) and (chunk / 256) * min(replicates, 1024) * 7 doubles of scratch.
+ * out[t] is srn_evaluate's result for the trial, bit for bit (the two ms_* fields aside; the bootstrap kernels are in neither).
+ * boot or rep NULL, replicates == 0, flags != 0: SRN_EINVAL; replicates > SRN_MAX_BOOTSTRAP: SRN_ERANGE; then srn_evaluate's own refusals, all before anything is launched. */
+#define SRN_MAX_BOOTSTRAP 4096
+#define SRN_BOOTSTRAP_SUMS 7
+typedef struct { uint64_t seed; uint32_t replicates; uint32_t flags; } srn_bootstrap_t;   /* flags: 0 */
+int srn_evaluate_bootstrap(srn_eval_set_t* set, const srn_eval_trial_t* trials, size_t n_trials, const srn_bootstrap_t* boot,
+                           srn_eval_result_t* out, double* rep /* [n_trials][replicates][7], host */, void* stream);
+/* host only: the rule -- out[i] = w(seed, replicate, first_session + i), i < n.  NULL out with n > 0: SRN_EINVAL */
+int srn_bootstrap_weights(uint64_t seed, uint32_t replicate, uint64_t first_session, size_t n, uint8_t* out);
+
 int srn_device_count(int* out);
 void srn_limits(srn_limits_t* out);
 const char* srn_last_error(void);

@@ -69,6 +69,13 @@ class EvalResult(C.Structure):
                [("covered_items", C.c_uint64), ("unique_training_items", C.c_uint64), ("ms_predict", C.c_double), ("ms_eval", C.c_double)]
 
 
+MAX_BOOTSTRAP, BOOTSTRAP_SUMS = 4096, 7
+
+
+class Bootstrap(C.Structure):   # srn_bootstrap_t
+    _fields_ = [("seed", C.c_uint64), ("replicates", C.c_uint32), ("flags", C.c_uint32)]
+
+
 class LoadInfo(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("lines", "rows", "skipped", "host_parsed")] + \
                [(n, C.c_double) for n in ("ms_read", "ms_upload", "ms_parse", "ms_group", "ms_download")]
@@ -198,6 +205,8 @@ SYMBOLS = {
     "srn_eval_set_from_tsv": (_i, [_vp, C.c_char_p, C.c_char_p, C.POINTER(_vp)]),
     "srn_evaluate": (_i, [_vp, C.POINTER(EvalTrial), _sz, C.POINTER(EvalResult), _vp]),
     "srn_eval_set_free": (None, [_vp]),
+    "srn_evaluate_bootstrap": (_i, [_vp, C.POINTER(EvalTrial), _sz, C.POINTER(Bootstrap), C.POINTER(EvalResult), _vp, _vp]),
+    "srn_bootstrap_weights": (_i, [_u64, C.c_uint32, _u64, _sz, _vp]),
     "srn_debug_eval_terms": (_i, [_vp, C.POINTER(EvalTrial), _vp, _sz, C.POINTER(_sz), C.POINTER(EvalResult)]),
     "srn_device_sessions_create": (_i, [_i, _sz, _sz, _u64, _u64, C.POINTER(_vp)]),
     "srn_device_sessions_free": (None, [_vp]),

@@ -761,6 +761,25 @@ int srn_evaluate(srn_eval_set_t* set, const srn_eval_trial_t* trials, size_t n_t
         return eval_run(set, trials, n_trials, out, stream, nullptr, 0); });
 }
 
+int srn_evaluate_bootstrap(srn_eval_set_t* set, const srn_eval_trial_t* trials, size_t n_trials, const srn_bootstrap_t* boot, srn_eval_result_t* out, double* rep,
+                           void* stream) {
+    return guarded([&]() -> int {
+        if (!boot || !rep) return fail(SRN_EINVAL, "null argument");
+        if (boot->replicates == 0) return fail(SRN_EINVAL, "replicates must be > 0");
+        if (boot->flags != 0) return fail(SRN_EINVAL, "srn_bootstrap_t.flags must be 0");
+        if (boot->replicates > SRN_MAX_BOOTSTRAP) return fail(SRN_ERANGE, "replicates above SRN_MAX_BOOTSTRAP");
+        int rc = check_trials(set, trials, n_trials, out); if (rc) return rc;
+        if (n_trials == 0) return SRN_OK;
+        return eval_run(set, trials, n_trials, out, stream, nullptr, 0, boot, rep); });
+}
+
+int srn_bootstrap_weights(uint64_t seed, uint32_t replicate, uint64_t first_session, size_t n, uint8_t* out) {
+    return guarded([&]() -> int {
+        if (n && !out) return fail(SRN_EINVAL, "null argument");
+        boot_weights_host(seed, replicate, first_session, n, out);
+        return SRN_OK; });
+}
+
 int srn_debug_eval_terms(srn_eval_set_t* set, const srn_eval_trial_t* trial, double* out_terms, size_t cap, size_t* out_n, srn_eval_result_t* out) {
     return guarded([&]() -> int {
         if (!trial || !out_n) return fail(SRN_EINVAL, "null argument");

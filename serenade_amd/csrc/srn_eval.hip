@@ -53,6 +53,7 @@ struct EvalDevice {
     char* chunk = nullptr; size_t chunk_bytes = 0;             // a chunk's prefixes, q_off, (session, state), rows, terms
     char* part = nullptr; size_t part_bytes = 0;               // per-group partial sums of every trial of a call
     char* cover = nullptr; size_t cover_bytes = 0;             // coverage bitmaps + popcounts + the error word
+    char* boot = nullptr; size_t boot_bytes = 0;               // srn_evaluate_bootstrap: every trial's replicate totals, then one replicate tile's group partials
     std::vector<hipEvent_t> ev;
 };
 
@@ -253,7 +254,7 @@ void eval_set_free(srn_eval_set* set) {
     if (!set) return;
     if (EvalDevice* e = set->dev) {
         (void)hipSetDevice(e->device);
-        for (void* p : {(void*)e->items, (void*)e->sess_off, (void*)e->freq, (void*)e->ndcg_w, (void*)e->scan, (void*)e->chunk, (void*)e->part, (void*)e->cover})
+        for (void* p : {(void*)e->items, (void*)e->sess_off, (void*)e->freq, (void*)e->ndcg_w, (void*)e->scan, (void*)e->chunk, (void*)e->part, (void*)e->cover, (void*)e->boot})
             if (p) (void)hipFree(p);
         for (hipEvent_t x : e->ev) (void)hipEventDestroy(x);
         delete e;
@@ -342,7 +343,8 @@ static uint32_t chunk_queries(const srn_eval_trial_t& t) {
     return std::max(c, kGroup);
 }
 
-int eval_run(srn_eval_set* set, const srn_eval_trial_t* trials, size_t n_trials, srn_eval_result_t* out, void* user_stream, double* terms_out, size_t cap) {
+int eval_run(srn_eval_set* set, const srn_eval_trial_t* trials, size_t n_trials, srn_eval_result_t* out, void* user_stream, double* terms_out, size_t cap,
+             const srn_bootstrap_t* boot, double* rep) {
     EvalDevice* e = set->dev; const srn_index* idx = set->idx; const FlatIndex& ix = idx->flat;
     HIP_TRY(hipSetDevice(e->device));
     hipStream_t st = (hipStream_t)user_stream;
@@ -363,6 +365,12 @@ int eval_run(srn_eval_set* set, const srn_eval_trial_t* trials, size_t n_trials,
     for (size_t t = 0; t < n_trials; ++t) { const uint64_t c = std::min<uint64_t>(chunk_queries(trials[t]), nq_all); max_chunk = std::max<size_t>(max_chunk, c);
                                             n_events += 4 * ((nq_all + chunk_queries(trials[t]) - 1) / chunk_queries(trials[t])); }
     while (e->ev.size() < n_events) { hipEvent_t x; HIP_TRY(hipEventCreate(&x)); e->ev.push_back(x); }
+    // the bootstrap's totals [trial][replicate][sum], zeroed here and copied back with the sums, and behind them the scratch of the largest chunk
+    const size_t boot_totals = boot ? align256(n_trials * (size_t)boot->replicates * SRN_BOOTSTRAP_SUMS * 8) : 0;
+    if (boot) {
+        if ((rc = ensure(&e->boot, &e->boot_bytes, boot_totals + boot_scratch_bytes(max_chunk, boot->replicates)))) return rc;
+        HIP_TRY(hipMemsetAsync(e->boot, 0, boot_totals, st));
+    }
     if ((rc = ensure(&e->scan, &e->scan_bytes, 2 * (n_s + 1) * 8))) return rc;
     std::vector<uint64_t> scan(2 * (n_s + 1));
     uint32_t scan_W = 0;
@@ -463,6 +471,8 @@ int eval_run(srn_eval_set* set, const srn_eval_trial_t* trials, size_t n_trials,
             eval_group_kernel<<<(nq + kGroup - 1) / kGroup, 64, 0, st>>>(d_terms, nq, part + (q0 / kGroup) * kSums);
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipEventRecord(ev[3], st));
+            if (boot && (rc = boot_chunk(d_terms, d_ss, nq, *boot, (double*)(e->boot + boot_totals),
+                                         (double*)e->boot + ti * (size_t)boot->replicates * SRN_BOOTSTRAP_SUMS, st))) return rc;
             if (terms_out) {   // (test aid) the chunk's terms, 7 per query
                 std::vector<double> h((size_t)nq * kTerms);
                 HIP_TRY(hipMemcpyAsync(h.data(), d_terms, h.size() * 8, hipMemcpyDeviceToHost, st));
@@ -480,6 +490,7 @@ int eval_run(srn_eval_set* set, const srn_eval_trial_t* trials, size_t n_trials,
     if (n_trials * n_groups) HIP_TRY(hipMemcpyAsync(part.data(), e->part, n_trials * n_groups * kSums * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(cov.data(), covered, n_trials * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(&h_err, err, 4, hipMemcpyDeviceToHost, st));
+    if (boot) HIP_TRY(hipMemcpyAsync(rep, e->boot, n_trials * (size_t)boot->replicates * SRN_BOOTSTRAP_SUMS * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     if (h_err) return fail(SRN_ERANGE, "a query exceeded the kernel's table limits");
     for (size_t ti = 0; ti < n_trials; ++ti) {

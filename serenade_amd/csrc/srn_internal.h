@@ -264,7 +264,14 @@ int eval_set_create(const srn_index* idx, const uint64_t* items_flat, const uint
                     const uint64_t* train_ids, const uint64_t* train_counts, size_t n_train, srn_eval_set** out);
 int eval_set_from_tsv(const srn_index* idx, const char* test_path, const char* train_path, srn_eval_set** out);
 // trials already checked (srn_capi.cpp).  terms != nullptr: one trial, its per-query terms [n * 7] (cap entries of room)
-int eval_run(srn_eval_set* set, const srn_eval_trial_t* trials, size_t n_trials, srn_eval_result_t* out, void* stream, double* terms, size_t cap);
+// boot != nullptr (already checked): every trial's replicate sums too, rep[n_trials][boot->replicates][SRN_BOOTSTRAP_SUMS] on the host
+int eval_run(srn_eval_set* set, const srn_eval_trial_t* trials, size_t n_trials, srn_eval_result_t* out, void* stream, double* terms, size_t cap,
+             const srn_bootstrap_t* boot = nullptr, double* rep = nullptr);
+// the bootstrap behind the metrics kernel (srn_bootstrap.hip): one chunk's terms [nq][8] and (session, state) pairs onto a trial's running totals
+// [replicates][SRN_BOOTSTRAP_SUMS], through scratch of boot_scratch_bytes(largest chunk, replicates); only enqueues
+size_t boot_scratch_bytes(uint64_t chunk_queries, uint32_t replicates);
+int boot_chunk(const double* terms, const void* session_state, uint32_t nq, const srn_bootstrap_t& boot, double* scratch, double* totals, void* stream);
+void boot_weights_host(uint64_t seed, uint32_t replicate, uint64_t first_session, size_t n, uint8_t* out);
 uint64_t eval_n_queries(const srn_eval_set* set);   // queries of any trial: sum over sessions of (len - 1)
 // a trial's exclusion lists hold at most this many ids (0: the trial excludes nothing): the history window -- the session window without one -- with
 // SRN_FLAG_EXCLUDE_SEEN, the session window with SRN_FLAG_EXCLUDE_SESSION alone.  The launch sequence runs at how_many + this

@@ -12,6 +12,10 @@ session window with history=0; history without exclude_seen changes no row).  ha
 serves; serving_queries() states the queries and lists of such a trial in Python.
 A report holds the evaluator's report line under its own names (qty_evaluations, Mrr@20, ..., F1score@20), the raw sums and the
 device milliseconds of predict and of the evaluation kernels.
+
+Confidence intervals: evaluate(es, trials, bootstrap=B, seed=S) resamples the test sessions B times on the GPU next to every trial
+(srn_evaluate_bootstrap) and adds percentile intervals and the replicate sums to each report; compare(report_a, report_b) is the paired comparison of two such
+reports.  bootstrap_weights / bootstrap_model state the rule in NumPy: the device's replicate sums are the model's, bit for bit.
 """
 import ctypes as C
 
@@ -117,10 +121,145 @@ class EvalSet:
         return out[:n.value], _report(r, t.length)
 
 
-def evaluate(eval_set, trials, stream=0):
-    """One srn_evaluate call over all trials -> list of reports (dicts), in trial order."""
+def evaluate(eval_set, trials, stream=0, bootstrap=0, seed=0, ci=0.95):
+    """One srn_evaluate call over all trials -> list of reports (dicts), in trial order.
+    bootstrap=B > 0: srn_evaluate_bootstrap with B replicates of the session-clustered Poisson bootstrap at `seed`.  Each report gains
+    "bootstrap": {"replicates", "seed", "ci", "weights": float64[B] (a replicate's sum of weights), "sums": {name: float64[B]} (its weighted sums, the names of
+    "sums"), "empty_replicates": replicates of weight 0} and, for every metric but Coverage, "<Name>@N_ci": (lo, hi) -- the percentile interval at level `ci` over
+    the replicates of non-zero weight ((0, 0) when there is none).  Reports of one seed and B on one test set are paired: compare()."""
     trials = list(trials)
+    B = int(bootstrap)
+    if B < 0 or not 0.0 < float(ci) < 1.0:
+        raise ValueError("bootstrap must be >= 0 and ci inside (0, 1)")
     arr = (capi.EvalTrial * max(len(trials), 1))(*[_trial(t) for t in trials])
     res = (capi.EvalResult * max(len(trials), 1))()
-    capi.check(capi.lib().srn_evaluate(eval_set._h if eval_set is not None else None, arr, len(trials), res, C.c_void_p(stream)))
-    return [_report(res[i], arr[i].length) for i in range(len(trials))]
+    h = eval_set._h if eval_set is not None else None
+    if B == 0:
+        capi.check(capi.lib().srn_evaluate(h, arr, len(trials), res, C.c_void_p(stream)))
+        return [_report(res[i], arr[i].length) for i in range(len(trials))]
+    boot = capi.Bootstrap(int(seed) & _M64, B, 0)
+    rep = np.zeros((max(len(trials), 1), B, capi.BOOTSTRAP_SUMS))
+    capi.check(capi.lib().srn_evaluate_bootstrap(h, arr, len(trials), C.byref(boot), res, capi.ptr(rep), C.c_void_p(stream)))
+    return [_with_bootstrap(_report(res[i], arr[i].length), rep[i], arr[i].length, int(boot.seed), float(ci)) for i in range(len(trials))]
+
+
+# ---- the bootstrap (DESIGN.md 10.2): the rule in NumPy, the reports' intervals, paired comparison ----
+_M64 = (1 << 64) - 1
+# round(2^32 * P(Poisson(1) <= i)), i = 0..11
+BOOTSTRAP_THRESHOLDS = (1580030169, 3160060337, 3950075422, 4213413783, 4279248374, 4292415292,
+                        4294609778, 4294923276, 4294962463, 4294966817, 4294967253, 4294967292)
+BOOTSTRAP_SUMS = ("mrr", "ndcg", "hit_rate", "popularity", "precision", "recall")   # rep[..][1..6]; rep[..][0] is the replicate's sum of weights
+_BOOT_TERM_COLUMNS = [TERMS.index(n) for n in ("mrr", "ndcg", "hit", "popularity", "precision", "recall")]
+_BOOT_METRICS = (("Mrr", "mrr"), ("Ndcg", "ndcg"), ("HitRate", "hit_rate"), ("Popularity", "popularity"), ("Precision", "precision"), ("Recall", "recall"))
+GROUP = 256   # queries per partial sum
+
+
+def _mix64(x):
+    """srn_internal.h mix64 on uint64 arrays (arithmetic mod 2^64)."""
+    x = x ^ (x >> np.uint64(33))
+    x = x * np.uint64(0xff51afd7ed558ccd)
+    x = x ^ (x >> np.uint64(33))
+    x = x * np.uint64(0xc4ceb9fe1a85ec53)
+    return x ^ (x >> np.uint64(33))
+
+
+def bootstrap_weights(seed, B, n_sessions, first_session=0):
+    """w(seed, b, s) for b < B and s = first_session .. first_session + n_sessions - 1 -> uint8[B, n_sessions]: the number of thresholds T[i] <= u,
+    u = mix64(mix64(seed + (b + 1) * 0x9E3779B97F4A7C15) ^ (s * 0xD1B54A32D192ED03 + 1)) >> 32.  Row b does not depend on B."""
+    with np.errstate(over="ignore"):
+        b = np.arange(int(B), dtype=np.uint64)
+        key = _mix64(np.uint64(int(seed) & _M64) + (b + np.uint64(1)) * np.uint64(0x9E3779B97F4A7C15))
+        s = np.uint64(int(first_session) & _M64) + np.arange(int(n_sessions), dtype=np.uint64)
+        u = _mix64(key[:, None] ^ (s * np.uint64(0xD1B54A32D192ED03) + np.uint64(1))[None, :]) >> np.uint64(32)
+    return np.searchsorted(np.array(BOOTSTRAP_THRESHOLDS, np.uint64), u, side="right").astype(np.uint8)
+
+
+def bootstrap_model(terms, session_of_query, B, seed):
+    """The replicate sums of srn_evaluate_bootstrap, bit for bit -> float64[B, 7].  terms: float64[n, 7] in TERMS order (EvalSet.terms), queries in set order;
+    session_of_query[q]: the index of q's test session in the set's order (sessions of one event count).  Per group of 256 consecutive queries, from +0.0 in query
+    order, acc = acc + w * term (the product rounded, then the sum); then the groups in order onto the total."""
+    terms = np.asarray(terms, np.float64).reshape(-1, len(TERMS))
+    sess = np.asarray(session_of_query, np.int64).reshape(-1)
+    if len(sess) != len(terms):
+        raise ValueError("one session index per query")
+    total = np.zeros((int(B), 1 + len(BOOTSTRAP_SUMS)))
+    if not len(terms):
+        return total
+    first = int(sess.min())
+    w_all = bootstrap_weights(seed, B, int(sess.max()) - first + 1, first).astype(np.float64)
+    cols = np.concatenate([np.ones((len(terms), 1)), terms[:, _BOOT_TERM_COLUMNS]], axis=1)
+    for g0 in range(0, len(terms), GROUP):
+        acc = np.zeros_like(total)
+        for q in range(g0, min(g0 + GROUP, len(terms))):
+            acc = acc + w_all[:, sess[q] - first, None] * cols[q][None, :]
+        total = total + acc
+    return total
+
+
+def session_of_query(test_sessions):
+    """For each query of a set in set order, the index of its test session (a session of n events gives n - 1 queries; one of a single event none, but it counts)."""
+    seqs = test_sessions.values() if isinstance(test_sessions, dict) else test_sessions
+    return np.array([s for s, ev in enumerate(seqs) for _ in range(1, len(ev))], np.int64)
+
+
+def _f1(p, r):
+    with np.errstate(invalid="ignore", divide="ignore"):
+        f = 2.0 * (p * r) / (p + r)
+    return np.where(np.isnan(f), 0.0, f)   # f1score.rs:27-36
+
+
+def replicate_values(report, metric="Mrr"):
+    """A bootstrapped report's metric per replicate -> (float64[B] -- weighted sum / weight, F1score from the replicate's Precision and Recall means; 0 where the
+    weight is 0 --, bool[B]: the replicate's weight is not 0)."""
+    boot = report["bootstrap"]
+    w = np.asarray(boot["weights"], np.float64)
+    ok = w > 0
+    mean = lambda name: np.divide(np.asarray(boot["sums"][name], np.float64), w, out=np.zeros_like(w), where=ok)
+    if metric == "F1score":
+        return np.where(ok, _f1(mean("precision"), mean("recall")), 0.0), ok
+    names = dict(_BOOT_METRICS)
+    if metric not in names:
+        raise ValueError("metric must be one of %s (Coverage is not resampled)" % ", ".join(list(names) + ["F1score"]))
+    return mean(names[metric]), ok
+
+
+def _interval(values, ci):
+    if not len(values):
+        return (0.0, 0.0)
+    lo, hi = np.quantile(values, [(1.0 - ci) / 2.0, 1.0 - (1.0 - ci) / 2.0])
+    return (float(lo), float(hi))
+
+
+def _with_bootstrap(rep, sums, length, seed, ci):
+    sums = np.asarray(sums, np.float64)
+    rep["bootstrap"] = {"replicates": int(sums.shape[0]), "seed": seed, "ci": ci, "weights": sums[:, 0].copy(),
+                        "sums": {n: sums[:, 1 + j].copy() for j, n in enumerate(BOOTSTRAP_SUMS)}, "empty_replicates": int(np.count_nonzero(sums[:, 0] == 0))}
+    for name in [m for m, _ in _BOOT_METRICS] + ["F1score"]:
+        v, ok = replicate_values(rep, name)
+        rep["%s@%d_ci" % (name, length)] = _interval(v[ok], ci)
+    return rep
+
+
+def _point(report, metric):
+    keys = [k for k in report if k.startswith(metric + "@") and not k.endswith("_ci")]
+    if len(keys) != 1:
+        raise ValueError("the report has no single %s@N" % metric)
+    return float(report[keys[0]])
+
+
+def compare(report_a, report_b, metric="Mrr"):
+    """Paired bootstrap comparison of two reports of evaluate(..., bootstrap=B) -> {"delta": a - b of the point estimates, "ci": the percentile interval of the
+    replicate-by-replicate differences (at report_a's level), "p_better": the share of replicates where a is above b, "replicates": how many entered}.
+    The weights depend on (seed, replicate, the session's place in the test set) alone, so reports pair across evaluate calls and across indices on one test set;
+    ValueError when seed, B or qty_evaluations differ."""
+    ba, bb = report_a.get("bootstrap"), report_b.get("bootstrap")
+    if ba is None or bb is None:
+        raise ValueError("compare needs reports of evaluate(..., bootstrap=B)")
+    if ba["seed"] != bb["seed"] or ba["replicates"] != bb["replicates"] or report_a["qty_evaluations"] != report_b["qty_evaluations"]:
+        raise ValueError("the reports are not paired: seed, replicates and qty_evaluations must be equal")
+    va, oka = replicate_values(report_a, metric)
+    vb, okb = replicate_values(report_b, metric)
+    ok = oka & okb
+    d = (va - vb)[ok]
+    return {"delta": _point(report_a, metric) - _point(report_b, metric), "ci": _interval(d, float(ba["ci"])),
+            "p_better": float(np.count_nonzero(d > 0)) / len(d) if len(d) else 0.0, "replicates": int(len(d))}

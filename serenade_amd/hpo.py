@@ -5,11 +5,15 @@ vmis_index.rs:325-390), and only idf_weighting is baked into an index (mod.rs:14
 idf weighting, at the largest m asked for with it, and evaluates all of that weighting's trials in one srn_evaluate call.
 
     python -m serenade_amd.hpo <config.toml> [--random N --seed S] [--exclude-seen] [--exclude-session] [--history H] [--handler-sessions] [--fill]
+                               [--bootstrap B [--seed S] [--ci C] [--ci-csv PATH]]
 
 reads the [hyperparam] keys of the reference's configuration (training_data_path, test_data_path, save_records, out_path,
 enable_business_logic), writes exhaustive_grid_search.rs's CSV and prints its "Best ..." lines.  TPE (tpe_hyperparameter_optm.rs) is
 not restated: evaluate() takes any list of trials, so an external optimiser can drive it.  The serving rules (evaluation.py: exclude_seen, exclude_session,
 history, handler_sessions, fill) are options of the whole search, not grid axes: every trial runs under them, and the CSV keeps the reference's columns.
+--bootstrap B runs every trial with B bootstrap replicates (--seed seeds them too): one more line after the "Best ..." lines gives the best trial's
+Mrr interval and how many other trials are within noise of it (the interval of their paired difference to the best contains 0); the intervals go to --ci-csv, never into
+the reference's CSV.
 """
 import argparse
 import ctypes as C
@@ -20,7 +24,7 @@ import sys
 import numpy as np
 
 from . import capi
-from .evaluation import EvalSet, evaluate
+from .evaluation import EvalSet, compare, evaluate
 from .vmisknn import VMISIndex
 
 # exhaustive_grid_search.rs:22-25, loop order m > k > window > idf (:48-51)
@@ -68,11 +72,12 @@ def _build_index(sessions, m_index, idf_weighting, device):
 
 
 def search(train_path, test_path, trials, business_logic=False, device=0, how_many=20, length=20, loader="host", exclude_seen=False, exclude_session=False, history=0,
-           handler_sessions=False, fill=False):
+           handler_sessions=False, fill=False, bootstrap=0, seed=0, ci=0.95):
     """objective() (src/objective.rs:8-52) for every trial: Mrr@length of predict(k, m, how_many) over every windowed prefix.
     loader="gpu" reads the training sessions with the GPU loader (srn_sessions_from_tsv_gpu: the same sessions).
     exclude_seen, exclude_session, history, handler_sessions, fill: the serving rules of evaluation.py, applied to every trial (fill: from the most popular
     training items, set on each index the search builds).
+    bootstrap, seed, ci: evaluate()'s -- every record's report then holds its replicate arrays and intervals, paired across the search's indices.
     -> {"records": [one per trial, in trial order], "best": the first record of the highest Mrr}."""
     trials = [dict(t) for t in trials]
     for i, t in enumerate(trials):   # what srn_evaluate refuses with SRN_ERANGE, said before any index is built: a store's history window is never below the session window
@@ -96,7 +101,7 @@ def search(train_path, test_path, trials, business_logic=False, device=0, how_ma
             mine = [i for i, t in enumerate(trials) if float(t["idf_weighting"]) == w]
             reps = evaluate(es, [dict(k=trials[i]["k"], m=trials[i]["m"], max_items_in_session=trials[i]["max_items_in_session"], how_many=how_many,
                                       length=length, business_logic=business_logic, exclude_seen=exclude_seen, exclude_session=exclude_session, history=history,
-                                      handler_sessions=handler_sessions, fill=fill) for i in mine])
+                                      handler_sessions=handler_sessions, fill=fill) for i in mine], bootstrap=bootstrap, seed=seed, ci=ci)
             for i, rep in zip(mine, reps):
                 t = trials[i]
                 records[i] = {"iteration": i, "n_most_recent_sessions": int(t["m"]), "neighborhood_size_k": int(t["k"]),
@@ -149,11 +154,17 @@ def hyperparam_config(path):
             "enable_business_logic": kv.get("hyperparam.enable_business_logic", "false") == "true"}
 
 
-def main(argv=None):
+def within_noise(records, best, metric="Mrr"):
+    """Bootstrapped records against the best one -> [(record, compare(best, record))] for every other record; a record is within noise of the best when the
+    interval of the paired difference contains 0."""
+    return [(r, compare(best["report"], r["report"], metric)) for r in records if r is not best]
+
+
+def parser():
     ap = argparse.ArgumentParser(prog="python -m serenade_amd.hpo", description="exhaustive (or random) hyper-parameter search on the GPU")
     ap.add_argument("config")
     ap.add_argument("--random", type=int, default=0, help="N random combinations of the exhaustive grid instead of all of it")
-    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--seed", type=int, default=0, help="of --random's draw and of --bootstrap's weights")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--gpu-loader", action="store_true", help="read the training file with the GPU loader (the same sessions)")
     ap.add_argument("--exclude-seen", action="store_true", help="every trial leaves out what the visitor has seen (the last --history items, or the session window)")
@@ -161,12 +172,19 @@ def main(argv=None):
     ap.add_argument("--history", type=int, default=0, metavar="H", help="the seen-items window of --exclude-seen (0: the session window); at least the largest last_items_in_session of the grid (10)")
     ap.add_argument("--handler-sessions", action="store_true", help="queries are the sessions /v1/recommend builds: repeated clicks dropped")
     ap.add_argument("--fill", action="store_true", help="short rows are filled from the most popular training items before they are scored")
-    a = ap.parse_args(argv)
+    ap.add_argument("--bootstrap", type=int, default=0, metavar="B", help="B bootstrap replicates per trial (0: none): confidence intervals next to the point estimates")
+    ap.add_argument("--ci", type=float, default=0.95, metavar="C", help="the intervals' level")
+    ap.add_argument("--ci-csv", default=None, metavar="PATH", help="with --bootstrap: every trial's Mrr interval and its paired difference to the best trial")
+    return ap
+
+
+def main(argv=None):
+    a = parser().parse_args(argv)
     cfg = hyperparam_config(a.config)
     trials = random(EXHAUSTIVE_GRID, a.random, a.seed) if a.random else exhaustive()
     rules = dict(exclude_seen=a.exclude_seen, exclude_session=a.exclude_session, history=a.history, handler_sessions=a.handler_sessions, fill=a.fill)
     res = search(cfg["training_data_path"], cfg["test_data_path"], trials, cfg["enable_business_logic"], a.device,
-                 loader="gpu" if a.gpu_loader else "host", **rules)
+                 loader="gpu" if a.gpu_loader else "host", bootstrap=a.bootstrap, seed=a.seed if a.bootstrap else 0, ci=a.ci, **rules)
     with open(cfg["out_path"], "w") as f:   # exhaustive_grid_search.rs:34-46 (the file is created either way)
         if cfg["save_records"]:
             f.write("iteration,n_most_recent_sessions,neighborhood_size_k,last_items_in_session,idf_weighting,%s\n" % GOAL)
@@ -183,6 +201,20 @@ def main(argv=None):
     print("Best idf_weighting: %d" % (-1 if none else int(b["idf_weighting"])))
     print("Business logic were %s." % ("enabled" if cfg["enable_business_logic"] else "disabled"))
     print("Best value for the goal metric: %s" % rust_f64(float("-inf") if none else b[GOAL]))
+    if a.bootstrap and not none:
+        key = [k for k in b["report"] if k.startswith("Mrr@") and k.endswith("_ci")][0]
+        lo, hi = b["report"][key]
+        others = within_noise(res["records"], b)
+        near = sum(1 for _, c in others if c["ci"][0] <= 0.0 <= c["ci"][1])
+        print("Bootstrap (%d replicates, seed %d): best %s %d%% interval [%s, %s]; %d of %d other trials within noise of the best" %
+              (a.bootstrap, a.seed, key[:-3], round(a.ci * 100), rust_f64(lo), rust_f64(hi), near, len(others)))
+        if a.ci_csv:
+            by_id = {id(r): c for r, c in others}
+            with open(a.ci_csv, "w") as f:
+                f.write("iteration,%s,ci_lo,ci_hi,best_minus_trial,diff_lo,diff_hi,p_best_better\n" % GOAL)
+                for r in res["records"]:
+                    c = by_id.get(id(r), {"delta": 0.0, "ci": (0.0, 0.0), "p_better": 0.0})
+                    f.write("%d,%s,%s\n" % (r["iteration"], rust_f64(r[GOAL]), ",".join(rust_f64(v) for v in (*r["report"][key], c["delta"], *c["ci"], c["p_better"]))))
     return 0
 
 

@@ -9,6 +9,13 @@ how_many 21 + H' (the launch sequence of an excluding trial without its filter a
 A library without the serving rules runs the two plain arms only, so the same file measures the commit before them.  Writes profiles/eval_serving_<config>.json.
 
     python tools/eval_bench.py --serving [--history 8] [--reps 5]
+
+--bootstrap [B ...]: what the bootstrap of DESIGN.md 10.2 costs.  The same trial alternates in one process, --reps rounds (default here 5), through srn_evaluate of the
+parent commit's library loaded beside this one (--parent-lib; its own index and set from the same data), srn_evaluate of this library, and srn_evaluate_bootstrap at each
+B (default 256 and 1024); medians of the wall times.  The yardstick of the cost is the plain arm of the same run; the plain arm against the parent's shows whether the
+call without bootstrap moved.  Writes profiles/eval_bootstrap_<config>.json.
+
+    python tools/eval_bench.py --bootstrap [256 1024] [--reps 5] [--parent-lib PATH | --skip-parent]
 """
 import argparse
 import ctypes as C
@@ -70,20 +77,105 @@ def serving_arms(a, es, trial, res):
     print(json.dumps(res))
 
 
+class ParentLibrary:
+    """srn_evaluate on another build of the library: an index and an evaluation set of its own from the same arrays."""
+    NAMES = ("srn_index_build_gpu", "srn_index_free", "srn_eval_set_create", "srn_eval_set_free", "srn_evaluate", "srn_last_error")
+
+    def __init__(self, path, capi):
+        self.L = C.CDLL(path)
+        for name in self.NAMES:
+            fn = getattr(self.L, name)
+            fn.restype, fn.argtypes = capi.SYMBOLS[name]
+        self.capi = capi
+
+    def check(self, rc):
+        if rc:
+            raise RuntimeError("parent library: %d %s" % (rc, self.L.srn_last_error().decode(errors="replace")))
+
+    def eval_set(self, off, items, ts, m, max_len, idfw, sessions):
+        capi = self.capi
+        off, items, ts = capi.as_u64(off), capi.as_u64(items), capi.as_u32(ts)
+        v = capi.SessionsView(off.ctypes.data, items.ctypes.data, ts.ctypes.data, len(ts))
+        self.index = C.c_void_p()
+        self.check(self.L.srn_index_build_gpu(C.byref(v), m, max_len, idfw, 0, C.byref(self.index)))
+        s_off = np.zeros(len(sessions) + 1, np.uint64)
+        s_off[1:] = np.cumsum([len(ev) for ev in sessions.values()])
+        s_items = np.fromiter((x for ev in sessions.values() for x in ev), dtype=np.uint64, count=int(s_off[-1]))
+        ids, counts = np.unique(items, return_counts=True)
+        ids, counts = capi.as_u64(ids), capi.as_u64(counts)
+        self.set = C.c_void_p()
+        self.check(self.L.srn_eval_set_create(self.index, capi.ptr(s_items), capi.ptr(s_off), len(sessions), capi.ptr(ids), capi.ptr(counts), len(ids), C.byref(self.set)))
+
+    def evaluate(self, trial):
+        res = self.capi.EvalResult()
+        self.check(self.L.srn_evaluate(self.set, C.byref(trial), 1, C.byref(res), None))
+        return res
+
+    def close(self):
+        self.L.srn_eval_set_free(self.set)
+        self.L.srn_index_free(self.index)
+
+
+def bootstrap_arms(a, es, trial, res, parent):
+    from serenade_amd import evaluation
+    reps = a.reps
+    Bs = a.bootstrap or [256, 1024]
+    arms = {}
+    if parent:
+        t_parent = evaluation._trial(trial)
+        arms["parent_plain"] = lambda: parent.evaluate(t_parent).sum_mrr
+    arms["plain"] = lambda: evaluation.evaluate(es, [trial])[0]["sums"]["mrr"]
+    for B in Bs:
+        arms["bootstrap_%d" % B] = lambda B=B: evaluation.evaluate(es, [trial], bootstrap=B, seed=1)[0]
+    out = {n: {"wall_ms": []} for n in arms}
+    for f in arms.values():   # first calls size the workspaces
+        f()
+    for _ in range(reps):
+        for n, f in arms.items():
+            t0 = time.perf_counter()
+            got = f()
+            out[n]["wall_ms"].append(round((time.perf_counter() - t0) * 1e3, 4))
+            if n.startswith("bootstrap_"):
+                out[n]["Mrr@20"], out[n]["Mrr@20_ci"], got = got["Mrr@20"], got["Mrr@20_ci"], got["sums"]["mrr"]
+            out[n]["sum_mrr"] = got
+    if len({o["sum_mrr"] for o in out.values()}) != 1:
+        raise SystemExit("the arms' Mrr sums differ: %s" % {n: o["sum_mrr"] for n, o in out.items()})
+    med = lambda v: float(np.median(v))   # noqa: E731
+    for o in out.values():
+        o["wall_ms_median"], o["wall_ms_spread"] = round(med(o["wall_ms"]), 4), round(max(o["wall_ms"]) - min(o["wall_ms"]), 4)
+    res.update({"reps": reps, "seed": 1, "parent_lib": bool(parent), "arms": out})
+    for B in Bs:
+        res["bootstrap_%d_minus_plain_ms" % B] = round(out["bootstrap_%d" % B]["wall_ms_median"] - out["plain"]["wall_ms_median"], 4)
+    if parent:
+        res["plain_minus_parent_ms"] = round(out["plain"]["wall_ms_median"] - out["parent_plain"]["wall_ms_median"], 4)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="cfg3")
     ap.add_argument("--queries", type=int, default=1 << 20)
     ap.add_argument("--window", type=int, default=4)
-    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--reps", type=int, default=None, help="default 3, with --bootstrap 5")
     ap.add_argument("--skip-host", action="store_true", help="leave out (c)")
     ap.add_argument("--grid", type=int, default=1, help="0: leave out the 24-trial call")
     ap.add_argument("--out", default=None, help="default: profiles/eval_bench_cfg3.json, with --serving profiles/eval_serving_<config>.json")
     ap.add_argument("--serving", action="store_true", help="the serving-rule arms instead of (a), (b), (c) and the grid")
     ap.add_argument("--history", type=int, default=8, help="--serving: H' (>= --window)")
+    ap.add_argument("--bootstrap", type=int, nargs="*", default=None, metavar="B", help="the bootstrap arms (default B: 256 1024) instead of (a), (b), (c) and the grid")
+    ap.add_argument("--parent-lib", default=os.path.join(ROOT, "serenade_amd", "variants", "libserenade_hip_parent.so"), help="--bootstrap: the parent commit's library")
+    ap.add_argument("--skip-parent", action="store_true", help="--bootstrap: no parent arm; the run then cannot tell whether the plain call moved")
     a = ap.parse_args()
+    if a.reps is None:
+        a.reps = 5 if a.bootstrap is not None else 3
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "eval_serving_%s.json" % a.config if a.serving else "eval_bench_cfg3.json")
+        a.out = os.path.join(ROOT, "profiles", "eval_bootstrap_%s.json" % a.config if a.bootstrap is not None else
+                             "eval_serving_%s.json" % a.config if a.serving else "eval_bench_cfg3.json")
+    if a.bootstrap is not None and not a.skip_parent and not os.path.exists(a.parent_lib):
+        raise SystemExit("the parent commit's library %s is missing: build it from the parent commit and pass --parent-lib, or pass --skip-parent" % a.parent_lib)
     import torch
     import serenade_amd as sa
     from serenade_amd import capi, evaluation, synth
@@ -112,6 +204,15 @@ def main():
 
     if a.serving:
         serving_arms(a, es, trial, res)
+        return
+    if a.bootstrap is not None:
+        parent = None
+        if not a.skip_parent:
+            parent = ParentLibrary(a.parent_lib, capi)
+            parent.eval_set(off, items, ts, m, 34, idfw, sessions)
+        bootstrap_arms(a, es, trial, res, parent)
+        if parent:
+            parent.close()
         return
 
     # (a) srn_evaluate, one trial per call
