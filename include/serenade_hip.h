@@ -636,6 +636,26 @@ int srn_recommend_batch_device(const srn_index_t* idx, srn_device_sessions_t* st
 int srn_recommend_batch(const srn_index_t* idx, srn_device_sessions_t* store, const uint64_t* key_hi, const uint64_t* key_lo, const uint64_t* item_ids,
                         const uint8_t* consent, size_t n, uint64_t now_secs, size_t max_items_in_session, size_t k, size_t m, size_t how_many,
                         unsigned flags, uint64_t* out_ids, double* out_scores, uint32_t* out_counts);
+/* ---- the timed batch: every request its own clock ----
+ * srn_recommend_batch_device / srn_recommend_batch with times[i], request i's clock in seconds, after the consent array.  A time is used as given: 0 is a time like any
+ * other.  The call leaves the rows, the store and an attached harvest exactly as n one-request untimed calls would, call i with now_secs = times[i], in request order
+ * i = 0 .. n-1 -- as long as the capacity rule's automatic sweep does not run.  Times need not be monotone: the rule is still "one after the other".  For a visitor's
+ * consenting requests r_0 .. r_m in request order: r_0 tests the stored session against times[r_0]; r_j (j >= 1) starts from an empty session iff
+ * times[r_j] > times[r_j-1] and times[r_j] - times[r_j-1] > idle_secs (the predecessor would have stored its own time, whether or not its click was appended) -- its click
+ * is then kept even where it repeats the previous one; the last request stores its window with epoch = times[r_m] (the last time, not the largest).  An attached harvest
+ * is offered the session every such break ends, once: the visitor's key, epoch = times[r_j-1], the items of r_j-1's window as the store would have held it (the history
+ * window H where one is set); min_len, capacity and lost apply as for (R) and the offer counts in from_return.  Append order within one call: the heads' stored sessions
+ * in ascending key order, as for the untimed call, then the sessions ended inside the call in ascending key order and, within a key, request order.
+ * now_secs is the SWEEP CLOCK: the capacity rule's automatic sweep alone reads it.  Pass a lower bound of times -- what the sweep drops is then older than ttl_secs for
+ * every request of the call, which would have found it idle anyway (ttl_secs >= idle_secs), and the sweep only moves a session from (R) to (S) in the harvest's counters.
+ * now_secs = 0 reads the system clock, as everywhere in this ABI: that is WRONG for a recorded log, whose sessions it would drop as long expired.
+ * NULL times: SRN_EINVAL.  Every check of the untimed call applies unchanged, before anything is launched.  A call without times enqueues exactly what it always has. */
+int srn_recommend_batch_device_at(const srn_index_t* idx, srn_device_sessions_t* store, const uint64_t* d_key_hi, const uint64_t* d_key_lo, const uint64_t* d_item_ids,
+                                  const uint8_t* d_consent, const uint64_t* d_times, size_t n, uint64_t now_secs, size_t max_items_in_session, size_t k, size_t m,
+                                  size_t how_many, unsigned flags, uint64_t* d_out_ids, double* d_out_scores, uint32_t* d_out_counts, void* stream);
+int srn_recommend_batch_at(const srn_index_t* idx, srn_device_sessions_t* store, const uint64_t* key_hi, const uint64_t* key_lo, const uint64_t* item_ids,
+                           const uint8_t* consent, const uint64_t* times, size_t n, uint64_t now_secs, size_t max_items_in_session, size_t k, size_t m, size_t how_many,
+                           unsigned flags, uint64_t* out_ids, double* out_scores, uint32_t* out_counts);
 
 /* ---- click feedback: served rows scored against the visitor's next click, on the device (srn_feedback.hip) ----
  * A click feedback log keeps, per visitor, the last row served to it: key (128 bit) -> (ids[0 .. c), n_model, epoch).  It is an object of its own, beside the session
@@ -685,6 +705,16 @@ int srn_feedback_observe_device(srn_feedback_t* f, const uint64_t* d_key_hi, con
 /* The same with host pointers (pageable allowed); blocks. */
 int srn_feedback_observe(srn_feedback_t* f, const uint64_t* key_hi, const uint64_t* key_lo, const uint64_t* item_ids, const uint8_t* consent, size_t n,
                          uint64_t now_secs, const uint64_t* ids, const double* scores, const uint32_t* counts, size_t how_many, uint32_t* out_rank);
+/* The timed batch: times[i] is request i's clock, and the call gives what n one-request calls give, call i with now_secs = times[i], in request order.
+ * The first consenting request of a visitor tests its entry's epoch against its own time; a later one is scored against the row served to its predecessor unless
+ * times[r_j] > times[r_j-1] and times[r_j] - times[r_j-1] > idle_secs -- then its rank is SRN_FEEDBACK_NONE and it counts in idle_expired; the entry is stored with the
+ * last request's time.  now_secs is the capacity rule's sweep clock alone (a lower bound of times; 0 = the system clock, wrong for a recorded log).  NULL times:
+ * SRN_EINVAL; every other check as for the untimed call. */
+int srn_feedback_observe_device_at(srn_feedback_t* f, const uint64_t* d_key_hi, const uint64_t* d_key_lo, const uint64_t* d_item_ids, const uint8_t* d_consent,
+                                   const uint64_t* d_times, size_t n, uint64_t now_secs, const uint64_t* d_ids, const double* d_scores, const uint32_t* d_counts,
+                                   size_t how_many, uint32_t* d_out_rank, void* stream);
+int srn_feedback_observe_at(srn_feedback_t* f, const uint64_t* key_hi, const uint64_t* key_lo, const uint64_t* item_ids, const uint8_t* consent, const uint64_t* times,
+                            size_t n, uint64_t now_secs, const uint64_t* ids, const double* scores, const uint32_t* counts, size_t how_many, uint32_t* out_rank);
 /* geometry and counters; waits for the log's kernels.  SRN_ESTATE, with *out filled in, if a batch ever found the table full -- rows were dropped; the capacity
  * rule excludes it (srn_feedback_sweep reports the same) */
 int srn_feedback_stats(srn_feedback_t* f, srn_feedback_stats_t* out);

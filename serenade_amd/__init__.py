@@ -7,7 +7,7 @@ used by bench.py (synth)."""
 from .vmisknn import CSR, ItemScore, VMISIndex, SerenadeError, predict, predict_batch, predict_batch_debug, predict_batch_device, predict_batch_device_excl, reserve  # noqa: F401
 from .evaluation import EvalSet, evaluate  # noqa: F401
 from .ingest import TrainingSessions  # noqa: F401
-from .serving import SessionHarvest, harvest_model, refreshed_index  # noqa: F401
+from .serving import SessionHarvest, harvest_model, refreshed_index, replay  # noqa: F401
 
 __all__ = ["CSR", "ItemScore", "VMISIndex", "SerenadeError", "predict", "predict_batch", "predict_batch_debug", "predict_batch_device", "predict_batch_device_excl", "reserve",
-           "EvalSet", "evaluate", "TrainingSessions", "SessionHarvest", "harvest_model", "refreshed_index"]
+           "EvalSet", "evaluate", "TrainingSessions", "SessionHarvest", "harvest_model", "refreshed_index", "replay"]

@@ -234,6 +234,10 @@ SYMBOLS = {
     "srn_device_sessions_history": (_i, [_vp, C.POINTER(_sz)]),
     "srn_recommend_batch_device": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _u64, _sz, _sz, _sz, _sz, C.c_uint, _vp, _vp, _vp, _vp]),
     "srn_recommend_batch": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _u64, _sz, _sz, _sz, _sz, C.c_uint, _vp, _vp, _vp]),
+    "srn_recommend_batch_device_at": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _u64, _sz, _sz, _sz, _sz, C.c_uint, _vp, _vp, _vp, _vp]),
+    "srn_recommend_batch_at": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _u64, _sz, _sz, _sz, _sz, C.c_uint, _vp, _vp, _vp]),
+    "srn_feedback_observe_device_at": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _u64, _vp, _vp, _vp, _sz, _vp, _vp]),
+    "srn_feedback_observe_at": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _u64, _vp, _vp, _vp, _sz, _vp]),
     "srn_debug_device_sessions_last_batch": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_sz), C.POINTER(_sz), _vp, _sz, _vp]),
     "srn_feedback_create": (_i, [_i, _sz, _sz, _u64, _u64, C.POINTER(_vp)]),
     "srn_feedback_free": (None, [_vp]),

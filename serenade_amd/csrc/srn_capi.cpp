@@ -918,6 +918,28 @@ int srn_recommend_batch(const srn_index_t* idx, srn_device_sessions_t* store, co
         return dsess_recommend_host(idx, store, key_hi, key_lo, item_ids, consent, n, now_secs, max_items_in_session, k, m, how_many, flags,
                                     out_ids, out_scores, out_counts); });
 }
+// the timed batch: the same checks, with `times` among the buffers; now_secs is the capacity rule's sweep clock alone
+int srn_recommend_batch_device_at(const srn_index_t* idx, srn_device_sessions_t* store, const uint64_t* d_key_hi, const uint64_t* d_key_lo, const uint64_t* d_item_ids,
+                                  const uint8_t* d_consent, const uint64_t* d_times, size_t n, uint64_t now_secs, size_t max_items_in_session, size_t k, size_t m,
+                                  size_t how_many, unsigned flags, uint64_t* d_out_ids, double* d_out_scores, uint32_t* d_out_counts, void* stream) {
+    return guarded([&]() -> int {
+        bool done;
+        int rc = check_recommend_args(idx, n, k, m, how_many, flags, d_key_hi && d_key_lo && d_item_ids && d_times && d_out_ids && d_out_scores && d_out_counts, &done);
+        if (rc || done) return rc;
+        return dsess_recommend_device(idx, store, d_key_hi, d_key_lo, d_item_ids, d_consent, n, now_secs, max_items_in_session, k, m, how_many, flags,
+                                      d_out_ids, d_out_scores, d_out_counts, stream, d_times); });
+}
+int srn_recommend_batch_at(const srn_index_t* idx, srn_device_sessions_t* store, const uint64_t* key_hi, const uint64_t* key_lo, const uint64_t* item_ids,
+                           const uint8_t* consent, const uint64_t* times, size_t n, uint64_t now_secs, size_t max_items_in_session, size_t k, size_t m, size_t how_many,
+                           unsigned flags, uint64_t* out_ids, double* out_scores, uint32_t* out_counts) {
+    return guarded([&]() -> int {
+        bool done;
+        int rc = check_recommend_args(idx, n, k, m, how_many, flags, key_hi && key_lo && item_ids && times && out_ids && out_scores && out_counts, &done);
+        if (rc || done) return rc;
+        if (max_items_in_session == 0) return fail(SRN_EINVAL, "srn_recommend_batch: max_items_in_session must be > 0");
+        return dsess_recommend_host(idx, store, key_hi, key_lo, item_ids, consent, n, now_secs, max_items_in_session, k, m, how_many, flags,
+                                    out_ids, out_scores, out_counts, times); });
+}
 
 // ---- session harvest (srn_harvest.hip) ----
 int srn_harvest_create(int device, size_t capacity, size_t items_cap, uint32_t min_len, srn_harvest_t** out) {
@@ -952,6 +974,19 @@ int srn_feedback_observe_device(srn_feedback_t* f, const uint64_t* d_key_hi, con
 int srn_feedback_observe(srn_feedback_t* f, const uint64_t* key_hi, const uint64_t* key_lo, const uint64_t* item_ids, const uint8_t* consent, size_t n,
                          uint64_t now_secs, const uint64_t* ids, const double* scores, const uint32_t* counts, size_t how_many, uint32_t* out_rank) {
     return guarded([&]() -> int { return fb_observe_host(f, key_hi, key_lo, item_ids, consent, n, now_secs, ids, scores, counts, how_many, out_rank); });
+}
+int srn_feedback_observe_device_at(srn_feedback_t* f, const uint64_t* d_key_hi, const uint64_t* d_key_lo, const uint64_t* d_item_ids, const uint8_t* d_consent,
+                                   const uint64_t* d_times, size_t n, uint64_t now_secs, const uint64_t* d_ids, const double* d_scores, const uint32_t* d_counts,
+                                   size_t how_many, uint32_t* d_out_rank, void* stream) {
+    return guarded([&]() -> int {
+        if (f && n && !d_times) return fail(SRN_EINVAL, "srn_feedback_observe: null buffer");
+        return fb_observe_device(f, d_key_hi, d_key_lo, d_item_ids, d_consent, n, now_secs, d_ids, d_scores, d_counts, how_many, d_out_rank, stream, d_times); });
+}
+int srn_feedback_observe_at(srn_feedback_t* f, const uint64_t* key_hi, const uint64_t* key_lo, const uint64_t* item_ids, const uint8_t* consent, const uint64_t* times,
+                            size_t n, uint64_t now_secs, const uint64_t* ids, const double* scores, const uint32_t* counts, size_t how_many, uint32_t* out_rank) {
+    return guarded([&]() -> int {
+        if (f && n && !times) return fail(SRN_EINVAL, "srn_feedback_observe: null buffer");
+        return fb_observe_host(f, key_hi, key_lo, item_ids, consent, n, now_secs, ids, scores, counts, how_many, out_rank, times); });
 }
 int srn_feedback_stats(srn_feedback_t* f, srn_feedback_stats_t* out) { return guarded([&]() -> int { return fb_stats(f, out); }); }
 int srn_feedback_histogram(srn_feedback_t* f, uint64_t* hits_model, uint64_t* hits_filled, size_t cap) {

@@ -20,6 +20,8 @@
 //              2048 workgroups, each taking every 2048th block of positions, so that a call of 2^20 requests ends in at most 2048 atomics per counter word, not 65536
 //   fb_store   behind fb_rank: the run's last request writes its row, count, n_model, epoch and state full, once (the same lane groups)
 // Integer work throughout: ranks, counters and the table's entries do not depend on the run or on how the requests are cut into calls.
+// A batch whose requests carry their own clocks (srn_feedback_observe*_at) runs fb_find_at, fb_rank_at and fb_store_at in their places, behind one
+// gather of the times into sorted order.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -240,6 +242,152 @@ __global__ void __launch_bounds__(kTPB) fb_store(ObsArgs a) {
     if (s && lane == 0) { s->count = c; s->n_model = sc ? fin : c; s->epoch = a.now; s->state = kFull; }
 }
 
+// ---- the timed batch: every request its own clock ----
+// t: the requests' times by SORTED position (one gather through `order`: a position reads t[p] and t[p - 1] as adjacent words).  A run head tests its slot's epoch against
+// its own time; any other request tests its predecessor's time -- the epoch the predecessor's row would have been stored with -- and a break is counted as idle_expired;
+// the run's last request stores its own time.  The runs are the untimed call's, so one max scan over the run heads still gives the slot.
+struct ObsTimedArgs { ObsArgs a; const uint64_t* t; };   // (a.now is not read)
+__global__ void __launch_bounds__(kTPB) fb_times_gather(const uint64_t* __restrict__ times, const uint32_t* __restrict__ order, uint32_t n, uint64_t* __restrict__ t) {
+    const uint32_t p = blockIdx.x * kTPB + threadIdx.x;
+    if (p < n) t[p] = times[order[p]];
+}
+__global__ void __launch_bounds__(kTPB) fb_find_at(ObsTimedArgs ta) {
+    const ObsArgs& a = ta.a;
+    const uint32_t p = blockIdx.x * kTPB + threadIdx.x;
+    if (p >= a.n) return;
+    const uint32_t req = a.order[p];
+    a.headpos[p] = 0;
+    if (!consents(a, req)) return;
+    const uint64_t hi = a.key_hi[req], lo = a.key_lo[req];
+    if (p) {
+        const uint32_t pr = a.order[p - 1];
+        if (consents(a, pr) && a.key_hi[pr] == hi && a.key_lo[pr] == lo) return;   // not a head
+    }
+    // find-or-insert: a slot claimed during this kernel belongs to another key
+    uint32_t h = key_hash(hi, lo) & a.t.mask, found = kNone, status = kNew;
+    for (uint32_t probes = 0; probes <= a.t.mask; ++probes, h = (h + 1) & a.t.mask) {
+        FbSlot* s = fb_slot(a.t, h);
+        uint32_t st = __hip_atomic_load(&s->state, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (st == kEmpty) {
+            st = atomicCAS(&s->state, kEmpty, kClaimed);
+            if (st == kEmpty) { s->key_hi = hi; s->key_lo = lo; s->epoch = 0; s->count = 0; s->n_model = 0; found = h; break; }
+        }
+        if (st == kFull && s->key_hi == hi && s->key_lo == lo) {
+            found = h;
+            status = idle_or_old(ta.t[p], s->epoch, a.idle) ? kIdle : kLive;
+            break;
+        }
+    }
+    if (found == kNone) atomicOr(a.err, 1u);
+    a.slot_of[p] = found; a.status[p] = status; a.headpos[p] = p;
+}
+
+// fb_rank with the break test inside a run.  No lane leaves early and the round count is the same across the wave: the ballots need all 64 lanes.  Dynamic LDS: one u32 per bin.
+__global__ void __launch_bounds__(kTPB) fb_rank_at(ObsTimedArgs ta) {
+    const ObsArgs& a = ta.a;
+    extern __shared__ uint32_t bins[];
+    const uint32_t n_bins = kHist + 2u * (a.row_cap + 1u);
+    for (uint32_t i = threadIdx.x; i < n_bins; i += kTPB) bins[i] = 0;
+    __syncthreads();
+    const uint32_t lanes = 1u << a.lanes_shift, lane = threadIdx.x & (lanes - 1);
+    const uint32_t gbase = (threadIdx.x & 63u) & ~(lanes - 1);   // the group's first lane in the wave
+    const uint32_t gmask = (1u << lanes) - 1u;                   // lanes <= 16
+    const uint64_t groups = (uint64_t)gridDim.x * (kTPB >> a.lanes_shift);
+    const uint32_t trips = (uint32_t)((a.n + groups - 1) / groups);
+    for (uint32_t trip = 0; trip < trips; ++trip) {
+        const uint64_t p = trip * groups + (uint64_t)blockIdx.x * (kTPB >> a.lanes_shift) + (threadIdx.x >> a.lanes_shift);
+        uint32_t kind = kRequests;                                   // (no request: nothing is counted)
+        uint32_t req = 0, c = 0, n_model = 0;                        // c = 0: no position is ever read
+        const uint64_t* row = nullptr; const uint64_t* sc = nullptr;
+        uint64_t item = 0;
+        if (p < a.n) {
+            req = a.order[p];
+            if (!consents(a, req)) kind = kNoConsent;
+            else {
+                const uint64_t hi = a.key_hi[req], lo = a.key_lo[req];
+                item = a.item[req];
+                bool head = p == 0;
+                uint32_t pr = 0;
+                if (!head) { pr = a.order[p - 1]; head = !consents(a, pr) || a.key_hi[pr] != hi || a.key_lo[pr] != lo; }
+                if (head) {
+                    const uint32_t st = a.status[p], slot = a.slot_of[p];
+                    kind = st == kLive ? kObserved : st == kIdle ? kIdleExpired : kFirstSeen;
+                    if (st == kLive && slot != kNone) { FbSlot* s = fb_slot(a.t, slot); c = min(s->count, a.row_cap); n_model = s->n_model; row = fb_ids(s); }
+                } else if (idle_or_old(ta.t[p], ta.t[p - 1], a.idle)) {
+                    kind = kIdleExpired;                             // a break: the predecessor's row is idle by the time of this click
+                } else {   // the row served to the previous request of the run
+                    kind = kObserved;
+                    c = served_count(a, pr); n_model = c;
+                    row = a.ids + (size_t)pr * a.how_many;
+                    if (a.scores) sc = a.scores + (size_t)pr * a.how_many;
+                }
+            }
+        }
+        uint32_t found = 0, fin = 0;                                 // the same in every lane of the group
+        for (uint32_t r = 0; r < a.rounds; ++r) {
+            const uint32_t i = (r << a.lanes_shift) + lane;
+            const bool in = i < c;
+            const bool match = in && row[i] == item;
+            const bool finite = in && sc && finite_bits(sc[i]);
+            const uint32_t mm = (uint32_t)(__ballot(match) >> gbase) & gmask, mf = (uint32_t)(__ballot(finite) >> gbase) & gmask;
+            if (!found && mm) found = (r << a.lanes_shift) + (uint32_t)__ffs((int)mm);
+            fin += __popc(mf);
+        }
+        if (sc) n_model = fin;
+        if (kind != kRequests && lane == 0) {
+            uint32_t rank = SRN_FEEDBACK_NONE;
+            atomicAdd(&bins[kRequests], 1u);
+            atomicAdd(&bins[kind], 1u);
+            if (kind != kNoConsent) atomicAdd(&bins[kStored], 1u);
+            if (kind == kObserved) {
+                const bool filled = found > n_model;
+                rank = found | (filled ? SRN_FEEDBACK_FILLED : 0u);
+                if (found) { atomicAdd(&bins[filled ? kHitsFilled : kHitsModel], 1u); atomicAdd(&bins[kHist + (filled ? a.row_cap + 1u : 0u) + found], 1u); }   // found <= c <= row_cap
+            }
+            if (a.out_rank) a.out_rank[req] = rank;
+        }
+    }
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < n_bins; i += kTPB) { const uint32_t v = bins[i]; if (v) atomicAdd(&a.ctr[i], (unsigned long long)v); }
+}
+
+// fb_store with the last request's own time
+__global__ void __launch_bounds__(kTPB) fb_store_at(ObsTimedArgs ta) {
+    const ObsArgs& a = ta.a;
+    const uint64_t tid = (uint64_t)blockIdx.x * kTPB + threadIdx.x;
+    const uint64_t p = tid >> a.lanes_shift;
+    const uint32_t lanes = 1u << a.lanes_shift, lane = (uint32_t)tid & (lanes - 1);
+    const uint32_t gbase = (threadIdx.x & 63u) & ~(lanes - 1), gmask = (1u << lanes) - 1u;
+    FbSlot* s = nullptr;
+    uint32_t c = 0;
+    const uint64_t* row = nullptr; const uint64_t* sc = nullptr;
+    if (p < a.n) {
+        const uint32_t req = a.order[p];
+        bool last = consents(a, req);
+        if (last && p + 1 < a.n) {
+            const uint32_t nx = a.order[p + 1];
+            last = !(consents(a, nx) && a.key_hi[nx] == a.key_hi[req] && a.key_lo[nx] == a.key_lo[req]);
+        }
+        const uint32_t slot = last ? a.slot_of[a.run_start[p]] : kNone;
+        if (slot != kNone) {
+            s = fb_slot(a.t, slot);
+            c = served_count(a, req);                            // <= how_many <= row_cap
+            row = a.ids + (size_t)req * a.how_many;
+            if (a.scores) sc = a.scores + (size_t)req * a.how_many;
+        }
+    }
+    uint64_t* dst = s ? fb_ids(s) : nullptr;
+    uint32_t fin = 0;
+    for (uint32_t r = 0; r < a.rounds; ++r) {
+        const uint32_t i = (r << a.lanes_shift) + lane;
+        const bool in = i < c;
+        if (in) dst[i] = row[i];
+        const bool finite = in && sc && finite_bits(sc[i]);
+        fin += __popc((uint32_t)(__ballot(finite) >> gbase) & gmask);
+    }
+    if (s && lane == 0) { s->count = c; s->n_model = sc ? fin : c; s->epoch = ta.t[p]; s->state = kFull; }
+}
+
 // ---- one key, from the host: out[0] = count (~0: unknown key), out[1] = epoch, out[2] = n_model, out[3..] = ids ----
 __global__ void fb_get_one(Table t, uint64_t hi, uint64_t lo, uint32_t row_cap, uint64_t* out) {
     out[0] = ~0ull;
@@ -378,7 +526,8 @@ int fb_create(int device, size_t capacity, size_t row_cap, uint64_t ttl_secs, ui
 }
 
 int fb_observe_device(srn_feedback* f, const uint64_t* d_hi, const uint64_t* d_lo, const uint64_t* d_item, const uint8_t* d_consent, size_t n, uint64_t now_secs,
-                      const uint64_t* d_ids, const double* d_scores, const uint32_t* d_counts, size_t how_many, uint32_t* d_out_rank, void* stream) {
+                      const uint64_t* d_ids, const double* d_scores, const uint32_t* d_counts, size_t how_many, uint32_t* d_out_rank, void* stream,
+                      const uint64_t* d_times) {
     if (!f) return fail(SRN_EINVAL, "srn_feedback_observe: null log");
     if (n == 0) return SRN_OK;
     if (!d_hi || !d_lo || !d_item || !d_ids || !d_counts) return fail(SRN_EINVAL, "srn_feedback_observe: null buffer");
@@ -397,7 +546,7 @@ int fb_observe_device(srn_feedback* f, const uint64_t* d_hi, const uint64_t* d_l
     HIP_TRY(rocprim::inclusive_scan(nullptr, t1, (uint32_t*)nullptr, (uint32_t*)nullptr, n, rocprim::maximum<uint32_t>(), st)); tmp = std::max(tmp, t1);
     const size_t w = align256(n * 4);
     const size_t o_keyA = 0, o_keyB = o_keyA + align256(n * 8), o_idxA = o_keyB + align256(n * 8), o_idxB = o_idxA + w, o_slot = o_idxB + w, o_stat = o_slot + w,
-                 o_head = o_stat + w, o_run = o_head + w, o_tmp = o_run + w, bytes = o_tmp + align256(tmp);
+                 o_head = o_stat + w, o_run = o_head + w, o_tmp = o_run + w, o_t = o_tmp + align256(tmp), bytes = o_t + (d_times ? align256(n * 8) : 0);   // (o_t: a timed batch only)
     if (bytes > f->ws_bytes) {   // (the previous call may still read the scratch: wait for it before it is freed)
         HIP_TRY(hipEventSynchronize(f->last));
         if ((rc = ensure(&f->ws, &f->ws_bytes, bytes))) return rc;
@@ -428,10 +577,19 @@ int fb_observe_device(srn_feedback* f, const uint64_t* d_hi, const uint64_t* d_l
     a.slot_of = (uint32_t*)(b + o_slot); a.status = (uint32_t*)(b + o_stat); a.headpos = (uint32_t*)(b + o_head); a.run_start = (uint32_t*)(b + o_run);
     a.out_rank = d_out_rank; a.ctr = f->ctr; a.err = f->err();
     const dim3 gg = grid_for(n << a.lanes_shift);   // (n <= 2^24: 2^28 lanes at the most)
-    fb_find<<<gn, kTPB, 0, st>>>(a);
-    t1 = tmp; HIP_TRY(rocprim::inclusive_scan(b + o_tmp, t1, a.headpos, a.run_start, n, rocprim::maximum<uint32_t>(), st));
-    fb_rank<<<dim3(std::min<unsigned>(gg.x, kRankBlocks)), kTPB, 4 * (size_t)f->n_bins(), st>>>(a);
-    fb_store<<<gg, kTPB, 0, st>>>(a);
+    if (d_times) {   // a timed batch: the same sequence behind one gather of the times into sorted order
+        const ObsTimedArgs ta{a, (const uint64_t*)(b + o_t)};
+        fb_times_gather<<<gn, kTPB, 0, st>>>(d_times, order, n32, (uint64_t*)(b + o_t));
+        fb_find_at<<<gn, kTPB, 0, st>>>(ta);
+        t1 = tmp; HIP_TRY(rocprim::inclusive_scan(b + o_tmp, t1, a.headpos, a.run_start, n, rocprim::maximum<uint32_t>(), st));
+        fb_rank_at<<<dim3(std::min<unsigned>(gg.x, kRankBlocks)), kTPB, 4 * (size_t)f->n_bins(), st>>>(ta);
+        fb_store_at<<<gg, kTPB, 0, st>>>(ta);
+    } else {
+        fb_find<<<gn, kTPB, 0, st>>>(a);
+        t1 = tmp; HIP_TRY(rocprim::inclusive_scan(b + o_tmp, t1, a.headpos, a.run_start, n, rocprim::maximum<uint32_t>(), st));
+        fb_rank<<<dim3(std::min<unsigned>(gg.x, kRankBlocks)), kTPB, 4 * (size_t)f->n_bins(), st>>>(a);
+        fb_store<<<gg, kTPB, 0, st>>>(a);
+    }
     HIP_TRY(hipGetLastError());
     // from here on the log has changed: the next call is ordered behind this one
     f->bound += n;
@@ -440,7 +598,7 @@ int fb_observe_device(srn_feedback* f, const uint64_t* d_hi, const uint64_t* d_l
 }
 
 int fb_observe_host(srn_feedback* f, const uint64_t* hi, const uint64_t* lo, const uint64_t* item, const uint8_t* consent, size_t n, uint64_t now_secs,
-                    const uint64_t* ids, const double* scores, const uint32_t* counts, size_t how_many, uint32_t* out_rank) {
+                    const uint64_t* ids, const double* scores, const uint32_t* counts, size_t how_many, uint32_t* out_rank, const uint64_t* times) {
     if (!f) return fail(SRN_EINVAL, "srn_feedback_observe: null log");
     if (n == 0) return SRN_OK;
     if (!hi || !lo || !item || !ids || !counts) return fail(SRN_EINVAL, "srn_feedback_observe: null buffer");
@@ -450,7 +608,7 @@ int fb_observe_host(srn_feedback* f, const uint64_t* hi, const uint64_t* lo, con
     HIP_TRY(hipSetDevice(f->device));
     const size_t rows = n * how_many * 8;
     const size_t o_hi = 0, o_lo = o_hi + align256(n * 8), o_item = o_lo + align256(n * 8), o_con = o_item + align256(n * 8), o_ids = o_con + align256(n),
-                 o_sc = o_ids + align256(rows), o_cnt = o_sc + align256(rows), o_rank = o_cnt + align256(n * 4), bytes = o_rank + align256(n * 4);
+                 o_sc = o_ids + align256(rows), o_cnt = o_sc + align256(rows), o_rank = o_cnt + align256(n * 4), o_times = o_rank + align256(n * 4), bytes = o_times + (times ? align256(n * 8) : 0);
     DevBuf buf; int rc = buf.alloc(bytes, "srn_feedback_observe"); if (rc) return rc;
     char* b = buf.p;
     hipStream_t st = nullptr;   // a stream of this call's own: two host callers do not wait for each other's copies
@@ -463,9 +621,10 @@ int fb_observe_host(srn_feedback* f, const uint64_t* hi, const uint64_t* lo, con
         HIP_TRY(hipMemcpyAsync(b + o_ids, ids, rows, hipMemcpyHostToDevice, st));
         if (scores) HIP_TRY(hipMemcpyAsync(b + o_sc, scores, rows, hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(b + o_cnt, counts, n * 4, hipMemcpyHostToDevice, st));
+        if (times) HIP_TRY(hipMemcpyAsync(b + o_times, times, n * 8, hipMemcpyHostToDevice, st));
         int rc2 = fb_observe_device(f, (const uint64_t*)(b + o_hi), (const uint64_t*)(b + o_lo), (const uint64_t*)(b + o_item), consent ? (const uint8_t*)(b + o_con) : nullptr, n,
                                     now_secs, (const uint64_t*)(b + o_ids), scores ? (const double*)(b + o_sc) : nullptr, (const uint32_t*)(b + o_cnt), how_many,
-                                    (uint32_t*)(b + o_rank), st);
+                                    (uint32_t*)(b + o_rank), st, times ? (const uint64_t*)(b + o_times) : nullptr);
         if (rc2) { (void)hipStreamSynchronize(st); return rc2; }
         if (out_rank) HIP_TRY(hipMemcpyAsync(out_rank, b + o_rank, n * 4, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));

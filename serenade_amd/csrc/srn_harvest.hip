@@ -12,6 +12,8 @@
 //                   beyond the capacity are not written
 //   hv_advance      one lane: cursor and counters, plain stores, ordered by the stream
 // No atomic cursor: the append order is the position order, so which sessions a full log loses does not depend on how the lanes were scheduled.
+// A timed batch appends a second time in the same shape, from the call's CSR instead of slots: the sessions that ended inside the call
+// (harvest_append_csr, hv_scatter_csr).
 //
 // Reading: the stored sessions are presented sorted by (epoch, key_hi, key_lo) -- stable LSD rocPRIM radix passes over key_lo, key_hi, epoch and a last one-bit pass
 // that puts the places beyond the cursor behind the stored ones (the sort's size is the host's upper bound of the cursor, exact after a read-back; the cursor itself
@@ -81,6 +83,29 @@ __global__ void __launch_bounds__(kTPB) hv_scatter(AppendArgs a) {
             dst[0] = v.x; if (j + 1 < a.items_cap) dst[1] = v.y;
         }
     }
+}
+// A timed batch ends sessions inside the call: flagged sorted position p ends the session of position p - 1, which no slot ever held.  Its source is
+// the call's CSR: the key of request order[p] (the run's), the predecessor's time t[p - 1] and the predecessor's window items_flat[q_off[pr] .. q_off[pr + 1]).
+struct CsrAppendArgs {
+    const uint32_t* order; const uint64_t* src_hi; const uint64_t* src_lo; const uint64_t* t; const uint64_t* items_flat; const uint32_t* q_off;
+    const uint64_t* flag; const uint64_t* pos; uint64_t n;
+    const uint64_t* words; uint64_t capacity, items_cap;
+    uint64_t* key_hi; uint64_t* key_lo; uint64_t* epoch; uint32_t* len; uint64_t* items;
+};
+// 8 adjacent lanes write one entry: lane l the items l, l + 8, ... (zero from `len` on), the first lane the head words
+__global__ void __launch_bounds__(kTPB) hv_scatter_csr(CsrAppendArgs a) {
+    const uint64_t tid = (uint64_t)blockIdx.x * kTPB + threadIdx.x;
+    const uint64_t p = tid >> 3;
+    const uint32_t lane = (uint32_t)tid & 7u;
+    if (p == 0 || p >= a.n || a.flag[p] != kHvStore) return;
+    const uint64_t d = a.words[kHvCursor] + (uint32_t)a.pos[p];
+    if (d >= a.capacity) return;   // the log is full: counted by hv_advance
+    const uint32_t req = a.order[p], pr = a.order[p - 1];
+    const uint32_t off = a.q_off[pr];
+    const uint32_t len = (uint32_t)min((uint64_t)(a.q_off[pr + 1] - off), a.items_cap);   // (a window is never longer than the store's items_cap <= the log's)
+    if (lane == 0) { a.key_hi[d] = a.src_hi[req]; a.key_lo[d] = a.src_lo[req]; a.epoch[d] = a.t[p - 1]; a.len[d] = len; }
+    uint64_t* dst = a.items + d * a.items_cap;
+    for (uint64_t j = lane; j < a.items_cap; j += 8) dst[j] = j < len ? a.items_flat[off + j] : 0;
 }
 // total = the scan's last word: stored candidates in the low half, short ones in the high half
 __global__ void hv_advance(uint64_t* words, const uint64_t* total, uint64_t capacity, uint32_t which) {
@@ -239,6 +264,23 @@ int harvest_append(srn_harvest* h, const Table& t, const uint32_t* slot_of, size
     a.lanes_shift = t.stride == 128 ? 3 : 4;
     hv_scatter<<<grid_for(n << a.lanes_shift), kTPB, 0, st>>>(a);
     hv_advance<<<1, 1, 0, st>>>(h->words, pos + n, h->capacity, from_return ? kHvReturn : kHvRebuild);
+    HIP_TRY(hipGetLastError());
+    h->bound = std::min<uint64_t>(h->capacity, h->bound + n);
+    return SRN_OK;
+}
+int harvest_append_csr(srn_harvest* h, const uint32_t* order, const uint64_t* src_hi, const uint64_t* src_lo, const uint64_t* t, const uint64_t* items_flat,
+                       const uint32_t* q_off, size_t n, char* scratch, hipStream_t st) {
+    const size_t w = align256((n + 1) * 8);
+    uint64_t* flag = (uint64_t*)scratch; uint64_t* pos = (uint64_t*)(scratch + w);
+    size_t tmp = 0;
+    HIP_TRY(rocprim::exclusive_scan(nullptr, tmp, flag, pos, 0ull, n + 1, rocprim::plus<uint64_t>(), st));
+    HIP_TRY(rocprim::exclusive_scan(scratch + 2 * w, tmp, flag, pos, 0ull, n + 1, rocprim::plus<uint64_t>(), st));
+    CsrAppendArgs a{};
+    a.order = order; a.src_hi = src_hi; a.src_lo = src_lo; a.t = t; a.items_flat = items_flat; a.q_off = q_off;
+    a.flag = flag; a.pos = pos; a.n = n; a.words = h->words; a.capacity = h->capacity; a.items_cap = h->items_cap;
+    a.key_hi = h->key_hi; a.key_lo = h->key_lo; a.epoch = h->epoch; a.len = h->len; a.items = h->items;
+    hv_scatter_csr<<<grid_for(n << 3), kTPB, 0, st>>>(a);
+    hv_advance<<<1, 1, 0, st>>>(h->words, pos + n, h->capacity, kHvReturn);
     HIP_TRY(hipGetLastError());
     h->bound = std::min<uint64_t>(h->capacity, h->bound + n);
     return SRN_OK;

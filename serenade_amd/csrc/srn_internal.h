@@ -312,10 +312,10 @@ int dsess_load(const char* path, int device, size_t capacity, size_t items_cap, 
 int dsess_file_info(const char* path, srn_device_sessions_file_info_t* out);
 int dsess_recommend_device(const srn_index* idx, srn_device_sessions* s, const uint64_t* d_hi, const uint64_t* d_lo, const uint64_t* d_item, const uint8_t* d_consent,
                            size_t n, uint64_t now_secs, size_t max_items, size_t k, size_t m, size_t how_many, unsigned flags,
-                           uint64_t* d_ids, double* d_scores, uint32_t* d_counts, void* stream);
+                           uint64_t* d_ids, double* d_scores, uint32_t* d_counts, void* stream, const uint64_t* d_times = nullptr);   // d_times: a timed batch
 int dsess_recommend_host(const srn_index* idx, srn_device_sessions* s, const uint64_t* hi, const uint64_t* lo, const uint64_t* item, const uint8_t* consent,
                          size_t n, uint64_t now_secs, size_t max_items, size_t k, size_t m, size_t how_many, unsigned flags,
-                         uint64_t* ids, double* scores, uint32_t* counts);
+                         uint64_t* ids, double* scores, uint32_t* counts, const uint64_t* times = nullptr);
 // trending items (srn_trending.hip): the items the store's live sessions hold most often
 int dsess_top_items(srn_device_sessions* s, uint64_t now_secs, uint64_t since_secs, uint32_t min_count, size_t cap, uint64_t* out_ids, uint32_t* out_counts, size_t* out_n);
 int dsess_device_of(const srn_device_sessions* s);
@@ -333,9 +333,10 @@ int harvest_events_device(srn_harvest* h, uint64_t id_base, size_t cap_rows, uin
 int fb_create(int device, size_t capacity, size_t row_cap, uint64_t ttl_secs, uint64_t idle_secs, srn_feedback** out);
 void fb_free(srn_feedback* f);
 int fb_observe_device(srn_feedback* f, const uint64_t* d_hi, const uint64_t* d_lo, const uint64_t* d_item, const uint8_t* d_consent, size_t n, uint64_t now_secs,
-                      const uint64_t* d_ids, const double* d_scores, const uint32_t* d_counts, size_t how_many, uint32_t* d_out_rank, void* stream);
+                      const uint64_t* d_ids, const double* d_scores, const uint32_t* d_counts, size_t how_many, uint32_t* d_out_rank, void* stream,
+                      const uint64_t* d_times = nullptr);
 int fb_observe_host(srn_feedback* f, const uint64_t* hi, const uint64_t* lo, const uint64_t* item, const uint8_t* consent, size_t n, uint64_t now_secs,
-                    const uint64_t* ids, const double* scores, const uint32_t* counts, size_t how_many, uint32_t* out_rank);
+                    const uint64_t* ids, const double* scores, const uint32_t* counts, size_t how_many, uint32_t* out_rank, const uint64_t* times = nullptr);
 int fb_stats(srn_feedback* f, srn_feedback_stats_t* out);
 int fb_histogram(srn_feedback* f, uint64_t* hits_model, uint64_t* hits_filled, size_t cap);
 int fb_reset_counters(srn_feedback* f);

@@ -47,6 +47,10 @@ namespace srn {
 // (n + 1) u64 words are the flags -- kHvStore / kHvSkip / 0 per position, the last one 0.  slot_of: position -> slot (null: the position is the slot)
 int harvest_scratch_bytes(size_t n, size_t* bytes);
 int harvest_append(srn_harvest* h, const Table& t, const uint32_t* slot_of, size_t n, char* scratch, bool from_return, hipStream_t st);
+// the sessions a timed batch ends inside the call, from the call's CSR: flagged sorted position p appends (key of request order[p], t[p - 1], the window of
+// request order[p - 1]); counted in from_return.  scratch as for harvest_append, the flags by sorted position
+int harvest_append_csr(srn_harvest* h, const uint32_t* order, const uint64_t* src_hi, const uint64_t* src_lo, const uint64_t* t, const uint64_t* items_flat,
+                       const uint32_t* q_off, size_t n, char* scratch, hipStream_t st);
 int harvest_dropped(srn_harvest* h, const Table& from, uint64_t now, uint64_t ttl, char* scratch, hipStream_t st);   // flags what a rebuild of `from` at `now` leaves out, then appends
 }  // namespace srn
 

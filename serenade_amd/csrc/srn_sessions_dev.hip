@@ -34,6 +34,11 @@
 // The store forgets a session in two places -- sess_store overwrites the slot of a visitor who returns after idle, and sess_rebuild leaves out what is older than the
 // TTL (rebuild, resize_locked) -- and an attached session harvest (srn_harvest.hip) is handed the entry at both, before the old bytes go away:
 // sess_return_flag + harvest_append between sess_find and sess_store, harvest_dropped behind sess_rebuild over the old table.  Without one nothing here differs.
+//
+// A batch whose requests carry their own clocks (srn_recommend_batch*_at) runs the same sequence with sess_find_at, sess_return_flag_at and
+// sess_store_at in the places of their namesakes: a run is cut into SEGMENTS where a request finds its predecessor's time idle, headpos marks segment heads, a second
+// max scan keeps the run's head for the slot, and the sessions that end inside the call go to the harvest from the call's CSR behind sess_emit.  Without times
+// nothing here differs either.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -204,6 +209,116 @@ __global__ void __launch_bounds__(kTPB) sess_return_flag(BatchArgs a, uint32_t m
                 if (s->state == kFull && s->len > 0 && idle_or_old(a.now, s->epoch, a.idle)) f = s->len >= min_len ? kHvStore : kHvSkip;
             }
         }
+    }
+    flag[p] = f;
+}
+
+// ---- the timed batch: every request its own clock ----
+// The untimed call's arrays, read by the same sess_len and sess_emit, plus: t the requests' times by SORTED position (one gather through `order`, so that a position
+// reads t[p] and t[p - 1] as adjacent words), and the RUN's head beside the SEGMENT's.  A run is cut into segments wherever a request finds its predecessor's time idle:
+// a.headpos marks segment heads, so that a.run_start becomes the segment start and a.slen is 0 at a break; runpos marks run heads only and its inclusive max scan,
+// run_head, is where sess_store_at and the harvest find the run's slot.
+struct TimedArgs {
+    BatchArgs a;             // (a.now is not read)
+    const uint64_t* t;       // [n] times[order[p]]
+    uint32_t* runpos;        // [n] p for a run head, 0 otherwise; inclusive max scan -> run_head
+    uint32_t* run_head;      // [n]
+};
+__global__ void __launch_bounds__(kTPB) sess_times_gather(const uint64_t* __restrict__ times, const uint32_t* __restrict__ order, uint32_t n, uint64_t* __restrict__ t) {
+    const uint32_t p = blockIdx.x * kTPB + threadIdx.x;
+    if (p < n) t[p] = times[order[p]];
+}
+__device__ __forceinline__ bool run_head_at(const BatchArgs& a, uint32_t p, uint32_t req) {
+    if (p == 0) return true;
+    const uint32_t pr = a.order[p - 1];
+    return !consents(a, pr) || a.key_hi[pr] != a.key_hi[req] || a.key_lo[pr] != a.key_lo[req];
+}
+
+// sess_find with the request's own time at a run head, and the break test against the predecessor's time everywhere else
+__global__ void __launch_bounds__(kTPB) sess_find_at(TimedArgs ta) {
+    const BatchArgs& a = ta.a;
+    const uint32_t p = blockIdx.x * kTPB + threadIdx.x;
+    if (p > a.n) return;
+    if (p == a.n) { a.kept[p] = 0; return; }
+    const uint32_t req = a.order[p];
+    if (!consents(a, req)) { a.kept[p] = 0; a.headpos[p] = 0; ta.runpos[p] = 0; return; }
+    const uint64_t hi = a.key_hi[req], lo = a.key_lo[req], item = a.item[req], now = ta.t[p];
+    if (!run_head_at(a, p, req)) {
+        ta.runpos[p] = 0;
+        if (idle_or_old(now, ta.t[p - 1], a.idle)) { a.slen[p] = 0; a.headpos[p] = p; a.kept[p] = 1; }   // a break: an empty session, whose first click is kept
+        else { a.headpos[p] = 0; a.kept[p] = item != a.item[a.order[p - 1]]; }
+        return;
+    }
+    // find-or-insert: a slot claimed during this kernel belongs to another key
+    uint32_t h = key_hash(hi, lo) & a.t.mask, found = kNone, stored = 0;
+    uint64_t last = 0;
+    for (uint32_t probes = 0; probes <= a.t.mask; ++probes, h = (h + 1) & a.t.mask) {
+        SlotHead* s = slot_at(a.t, h);
+        uint32_t st = __hip_atomic_load(&s->state, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (st == kEmpty) {
+            st = atomicCAS(&s->state, kEmpty, kClaimed);
+            if (st == kEmpty) { s->key_hi = hi; s->key_lo = lo; s->epoch = 0; s->len = 0; found = h; break; }
+        }
+        if (st == kFull && s->key_hi == hi && s->key_lo == lo) {
+            found = h;
+            const uint32_t len = s->len;
+            if (len && !idle_or_old(now, s->epoch, a.idle)) { stored = len; last = slot_items(s)[len - 1]; }
+            break;
+        }
+    }
+    if (found == kNone) atomicOr(a.err, 1u);
+    a.slot_of[p] = found; a.slen[p] = stored; a.headpos[p] = p; ta.runpos[p] = p;
+    a.kept[p] = stored == 0 || last != item;
+}
+
+// the run's last request writes its window and ITS time (not the largest one) into the run's slot
+__global__ void __launch_bounds__(kTPB) sess_store_at(TimedArgs ta) {
+    const BatchArgs& a = ta.a;
+    const uint32_t p = blockIdx.x * kTPB + threadIdx.x;
+    if (p >= a.n) return;
+    const uint32_t req = a.order[p];
+    if (!consents(a, req)) return;
+    if (p + 1 < a.n) {
+        const uint32_t nx = a.order[p + 1];
+        if (consents(a, nx) && a.key_hi[nx] == a.key_hi[req] && a.key_lo[nx] == a.key_lo[req]) return;   // not the run's last request
+    }
+    const uint32_t slot = a.slot_of[ta.run_head[p]];
+    if (slot == kNone) return;
+    SlotHead* s = slot_at(a.t, slot);
+    const uint32_t off = a.q_off[req], len = a.q_off[req + 1] - off;
+    uint64_t* it = slot_items(s);
+    for (uint32_t i = 0; i < len; ++i) it[i] = a.items_flat[off + i];
+    s->len = len; s->epoch = ta.t[p]; s->state = kFull;
+}
+
+// sess_return_flag with the head's own time
+__global__ void __launch_bounds__(kTPB) sess_return_flag_at(TimedArgs ta, uint32_t min_len, uint64_t* __restrict__ flag) {
+    const BatchArgs& a = ta.a;
+    const uint32_t p = blockIdx.x * kTPB + threadIdx.x;
+    if (p > a.n) return;
+    uint64_t f = 0;
+    if (p < a.n) {
+        const uint32_t req = a.order[p];
+        if (consents(a, req) && run_head_at(a, p, req)) {
+            const uint32_t slot = a.slot_of[p];
+            if (slot != kNone && a.slen[p] == 0) {
+                const SlotHead* s = slot_at(a.t, slot);
+                if (s->state == kFull && s->len > 0 && idle_or_old(ta.t[p], s->epoch, a.idle)) f = s->len >= min_len ? kHvStore : kHvSkip;
+            }
+        }
+    }
+    flag[p] = f;
+}
+// The sessions that end INSIDE the call, behind sess_emit: a break at sorted position p ends the session of position p - 1, whose window is in the call's CSR.
+// flag[p] = kHvStore / kHvSkip by that window's length; flag[n] = 0.  (A break is a segment head that is not a run head.)
+__global__ void __launch_bounds__(kTPB) sess_break_flag(TimedArgs ta, uint32_t min_len, uint64_t* __restrict__ flag) {
+    const BatchArgs& a = ta.a;
+    const uint32_t p = blockIdx.x * kTPB + threadIdx.x;
+    if (p > a.n) return;
+    uint64_t f = 0;
+    if (p > 0 && p < a.n && a.headpos[p] == p && ta.runpos[p] == 0) {
+        const uint32_t pr = a.order[p - 1];
+        f = a.q_off[pr + 1] - a.q_off[pr] >= min_len ? kHvStore : kHvSkip;
     }
     flag[p] = f;
 }
@@ -689,7 +804,7 @@ static int recommend_no_store(const srn_index* idx, const uint64_t* d_item, cons
 // arguments already checked by the C ABI glue (predict's own checks, null buffers, n > 0)
 int dsess_recommend_device(const srn_index* idx, srn_device_sessions* s, const uint64_t* d_hi, const uint64_t* d_lo, const uint64_t* d_item, const uint8_t* d_consent,
                            size_t n, uint64_t now_secs, size_t max_items, size_t k, size_t m, size_t how_many, unsigned flags,
-                           uint64_t* d_ids, double* d_scores, uint32_t* d_counts, void* stream) {
+                           uint64_t* d_ids, double* d_scores, uint32_t* d_counts, void* stream, const uint64_t* d_times) {
     if (max_items == 0) return fail(SRN_EINVAL, "srn_recommend_batch: max_items_in_session must be > 0");
     if (n > kMaxBatch) return fail(SRN_ERANGE, "srn_recommend_batch: more than 2^24 requests in one call");
     hipStream_t st = (hipStream_t)stream;
@@ -726,7 +841,8 @@ int dsess_recommend_device(const srn_index* idx, srn_device_sessions* s, const u
     const size_t o_keyA = 0, o_keyB = o_keyA + align256(n * 8), o_idxA = o_keyB + align256(n * 8), o_idxB = o_idxA + w, o_slot = o_idxB + w, o_slen = o_slot + w,
                  o_kept = o_slen + w, o_head = o_kept + w, o_kex = o_head + w, o_run = o_kex + w, o_qlen = o_run + w, o_qoff = o_qlen + w, o_comp = o_qoff + w,
                  o_flat = o_comp + align256(n * 8), o_tmp = o_flat + align256(n * (size_t)hint * 8),
-                 o_plen = o_tmp + align256(tmp), o_poff = o_plen + (H ? w : 0), o_pflat = o_poff + (H ? w : 0), o_hv = o_pflat + (H ? align256(n * (size_t)phint * 8) : 0), bytes = o_hv + hv_bytes;
+                 o_plen = o_tmp + align256(tmp), o_poff = o_plen + (H ? w : 0), o_pflat = o_poff + (H ? w : 0), o_hv = o_pflat + (H ? align256(n * (size_t)phint * 8) : 0),
+                 o_t = o_hv + hv_bytes, o_rpos = o_t + (d_times ? align256(n * 8) : 0), o_rhead = o_rpos + (d_times ? w : 0), bytes = o_rhead + (d_times ? w : 0);   // (a timed batch only)
     if (bytes > s->ws_bytes) {   // (the previous call may still read the scratch: wait for it before it is freed)
         HIP_TRY(hipEventSynchronize(s->last));
         if ((rc = ensure(&s->ws, &s->ws_bytes, bytes))) return rc;
@@ -756,19 +872,35 @@ int dsess_recommend_device(const srn_index* idx, srn_device_sessions* s, const u
     a.slot_of = (uint32_t*)(b + o_slot); a.slen = (uint32_t*)(b + o_slen); a.kept = (uint32_t*)(b + o_kept); a.headpos = (uint32_t*)(b + o_head);
     a.kex = (uint32_t*)(b + o_kex); a.run_start = (uint32_t*)(b + o_run); a.qlen = (uint32_t*)(b + o_qlen); a.q_off = (uint32_t*)(b + o_qoff);
     a.compact = (uint64_t*)(b + o_comp); a.items_flat = (uint64_t*)(b + o_flat); a.err = s->err();
-    sess_find<<<gn1, kTPB, 0, st>>>(a);
+    TimedArgs ta{};   // a timed batch: the same sequence over segments, with a second max scan for the run's slot and a second append behind sess_emit
+    if (d_times) {
+        ta.a = a; ta.t = (const uint64_t*)(b + o_t); ta.runpos = (uint32_t*)(b + o_rpos); ta.run_head = (uint32_t*)(b + o_rhead);
+        sess_times_gather<<<gn, kTPB, 0, st>>>(d_times, order, n32, (uint64_t*)(b + o_t));
+        sess_find_at<<<gn1, kTPB, 0, st>>>(ta);
+    } else
+        sess_find<<<gn1, kTPB, 0, st>>>(a);
     if (hv) {   // the stored sessions the heads found idle, copied before sess_store overwrites their slots
-        sess_return_flag<<<gn1, kTPB, 0, st>>>(a, hv->min_len, (uint64_t*)(b + o_hv));
+        if (d_times) sess_return_flag_at<<<gn1, kTPB, 0, st>>>(ta, hv->min_len, (uint64_t*)(b + o_hv));
+        else sess_return_flag<<<gn1, kTPB, 0, st>>>(a, hv->min_len, (uint64_t*)(b + o_hv));
         HIP_TRY(hipGetLastError());
         if ((rc = harvest_append(hv, a.t, a.slot_of, n, b + o_hv, true, st))) return rc;
     }
     t1 = tmp; HIP_TRY(rocprim::exclusive_scan(b + o_tmp, t1, a.kept, a.kex, 0u, n + 1, rocprim::plus<uint32_t>(), st));
     t1 = tmp; HIP_TRY(rocprim::inclusive_scan(b + o_tmp, t1, a.headpos, a.run_start, n, rocprim::maximum<uint32_t>(), st));
-    sess_len<<<gn1, kTPB, 0, st>>>(a);
+    if (d_times) { t1 = tmp; HIP_TRY(rocprim::inclusive_scan(b + o_tmp, t1, ta.runpos, ta.run_head, n, rocprim::maximum<uint32_t>(), st)); }
+    sess_len<<<gn1, kTPB, 0, st>>>(a);   // (run_start is the segment start and slen 0 at a break: sess_len and sess_emit read a timed batch as they read any other)
     t1 = tmp; HIP_TRY(rocprim::exclusive_scan(b + o_tmp, t1, a.qlen, a.q_off, 0u, n + 1, rocprim::plus<uint32_t>(), st));
     if (H) { t1 = tmp; HIP_TRY(rocprim::exclusive_scan(b + o_tmp, t1, a.plen, a.p_off, 0u, n + 1, rocprim::plus<uint32_t>(), st)); }
     sess_emit<<<gn, kTPB, 0, st>>>(a);
-    sess_store<<<gn, kTPB, 0, st>>>(a);
+    if (d_times) {
+        if (hv) {   // the sessions ended inside the call, from the windows just emitted
+            sess_break_flag<<<gn1, kTPB, 0, st>>>(ta, hv->min_len, (uint64_t*)(b + o_hv));
+            HIP_TRY(hipGetLastError());
+            if ((rc = harvest_append_csr(hv, order, d_hi, d_lo, ta.t, a.items_flat, a.q_off, n, b + o_hv, st))) return rc;
+        }
+        sess_store_at<<<gn, kTPB, 0, st>>>(ta);
+    } else
+        sess_store<<<gn, kTPB, 0, st>>>(a);
     HIP_TRY(hipGetLastError());
     // from here on the store has changed: whatever happens below, the next call is ordered behind this one
     s->bound += n;
@@ -791,14 +923,14 @@ int dsess_recommend_device(const srn_index* idx, srn_device_sessions* s, const u
 
 int dsess_recommend_host(const srn_index* idx, srn_device_sessions* s, const uint64_t* hi, const uint64_t* lo, const uint64_t* item, const uint8_t* consent,
                          size_t n, uint64_t now_secs, size_t max_items, size_t k, size_t m, size_t how_many, unsigned flags,
-                         uint64_t* ids, double* scores, uint32_t* counts) {
+                         uint64_t* ids, double* scores, uint32_t* counts, const uint64_t* times) {
     if (!s && (!consent || std::any_of(consent, consent + n, [](uint8_t x) { return x != 0; }))) return fail(SRN_EINVAL, "srn_recommend_batch: user consent needs a session store");
     if (n > kMaxBatch) return fail(SRN_ERANGE, "srn_recommend_batch: more than 2^24 requests in one call");
     HIP_TRY(hipSetDevice(idx->device));
     // device copies: the store's staging, or (no store) a buffer of this call's own
     const size_t rows = n * how_many * 8;
     const size_t o_hi = 0, o_lo = o_hi + align256(n * 8), o_item = o_lo + align256(n * 8), o_con = o_item + align256(n * 8), o_ids = o_con + align256(n),
-                 o_sc = o_ids + align256(rows), o_cnt = o_sc + align256(rows), bytes = o_cnt + align256(n * 4);
+                 o_sc = o_ids + align256(rows), o_cnt = o_sc + align256(rows), o_times = o_cnt + align256(n * 4), bytes = o_times + (times ? align256(n * 8) : 0);
     char* own_buf = nullptr; hipStream_t st = nullptr;
     std::unique_lock<std::mutex> sl;
     if (s) {
@@ -815,9 +947,11 @@ int dsess_recommend_host(const srn_index* idx, srn_device_sessions* s, const uin
         HIP_TRY(hipMemcpyAsync(b + o_lo, lo, n * 8, hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(b + o_item, item, n * 8, hipMemcpyHostToDevice, st));
         if (consent) HIP_TRY(hipMemcpyAsync(b + o_con, consent, n, hipMemcpyHostToDevice, st));
+        if (times) HIP_TRY(hipMemcpyAsync(b + o_times, times, n * 8, hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemsetAsync(b + o_ids, 0, o_cnt - o_ids, st));   // (entries beyond a row's count read as zero, as in buffers a caller cleared)
         int rc = dsess_recommend_device(idx, s, (const uint64_t*)(b + o_hi), (const uint64_t*)(b + o_lo), (const uint64_t*)(b + o_item), consent ? (const uint8_t*)(b + o_con) : nullptr,
-                                        n, now_secs, max_items, k, m, how_many, flags, (uint64_t*)(b + o_ids), (double*)(b + o_sc), (uint32_t*)(b + o_cnt), st);
+                                        n, now_secs, max_items, k, m, how_many, flags, (uint64_t*)(b + o_ids), (double*)(b + o_sc), (uint32_t*)(b + o_cnt), st,
+                                        times ? (const uint64_t*)(b + o_times) : nullptr);
         if (rc) { (void)hipStreamSynchronize(st); return rc; }
         HIP_TRY(hipSetDevice(idx->device));
         HIP_TRY(hipMemcpyAsync(ids, b + o_ids, rows, hipMemcpyDeviceToHost, st));

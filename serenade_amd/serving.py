@@ -459,7 +459,7 @@ class DeviceSessionStore:
 _HARVEST_COUNTERS = ("stored", "stored_items", "lost", "skipped_short", "from_return", "from_rebuild")
 
 
-def harvest_model(state, keys, items, consent, now, *, limit=2, idle_secs=20 * 60, ttl_secs=30 * 60, min_len=1, capacity=None, sweep=False):
+def harvest_model(state, keys, items, consent, now, *, limit=2, idle_secs=20 * 60, ttl_secs=30 * 60, min_len=1, capacity=None, sweep=False, times=None):
     """Pure-Python statement of the session harvest (srn_harvest.hip): a dictionary replay of the /v1/recommend handler's rule that keeps what the
     store forgets.  It needs no GPU and no library.
     state: dict, updated in place: 128-bit key -> (items list, epoch) for every stored session, and under the key "log" the harvest itself (created on first use).
@@ -475,13 +475,17 @@ def harvest_model(state, keys, items, consent, now, *, limit=2, idle_secs=20 * 6
     The log is appended in the device's order: the returns of one call in ascending key order (not request order), so the result does not depend on how the requests
     of one time step are cut into calls.  A sweep's sessions are appended in ascending key order here and in slot order on the device: which of them a FULL log loses
     is the one thing this model does not predict.
+    times (rule T): request j's own clock -- the call is len(times) one-request calls, call j at times[j], in request order; `now` is then read by the
+    sweep alone.  A visitor's stored session is tested against the time of the visitor's first consenting request; every later request of the visitor tests the time
+    its predecessor stored, so sessions also end INSIDE the call.  The call's appends: the stored sessions the visitors' first requests found idle, in ascending key
+    order as above, then the sessions ended inside the call in ascending key order and, within a key, request order.
     -> (sessions, counters): the stored sessions as (key, epoch, [items]) tuples in canonical order -- (epoch, key) ascending -- and the words of SessionHarvest.stats()
     plus "append_order": the same tuples in the order they were stored."""
     log = state.setdefault("log", {"sessions": [], "lost": 0, "skipped_short": 0, "from_return": 0, "from_rebuild": 0})
     now, min_len = int(now), max(int(min_len), 1)
 
-    def offer(found, which):
-        for key, (its, epoch) in sorted(found, key=lambda e: e[0]):
+    def offer(found, which, ordered=False):
+        for key, (its, epoch) in (found if ordered else sorted(found, key=lambda e: e[0])):
             log[which] += 1
             if len(its) < min_len:
                 log["skipped_short"] += 1
@@ -495,15 +499,20 @@ def harvest_model(state, keys, items, consent, now, *, limit=2, idle_secs=20 * 6
         items = np.asarray(items, np.uint64)
         if not (len(hi) == len(lo) == len(items)) or (consent is not None and len(consent) != len(items)):
             raise ValueError("keys, items and consent differ in length")
-        returned = []
+        if times is not None and len(times) != len(items):
+            raise ValueError("times must have one entry per request")
+        returned, inside, seen, sweep_now = [], [], set(), now
         for j in range(len(items)):
             if consent is not None and not consent[j]:
                 continue
             key = (int(hi[j]) << 64) | int(lo[j])
+            if times is not None:
+                now = int(times[j])
             cur, epoch = state.get(key, ([], 0))
             if cur and now > epoch and now - epoch > idle_secs:
-                returned.append((key, (cur, epoch)))
+                (inside if key in seen else returned).append((key, (cur, epoch)))
                 cur = []
+            seen.add(key)
             item = int(items[j])
             if not cur or cur[-1] != item:
                 cur = cur + [item]
@@ -511,6 +520,8 @@ def harvest_model(state, keys, items, consent, now, *, limit=2, idle_secs=20 * 6
                     cur = cur[1:]
             state[key] = (cur, now)
         offer(returned, "from_return")
+        offer(sorted(inside, key=lambda e: e[0]), "from_return", ordered=True)   # (a stable sort: request order within a key)
+        now = sweep_now
     if sweep:
         old = [(k, v) for k, v in state.items() if k != "log" and now > v[1] and now - v[1] > ttl_secs]
         for k, _ in old:
@@ -643,7 +654,7 @@ def refreshed_index(base_session_ids, base_item_ids, base_times, harvest, m_most
 _FEEDBACK_COUNTERS = ("requests", "no_consent", "first_seen", "idle_expired", "observed", "hits_model", "hits_filled", "stored")
 
 
-def feedback_model(state, keys, items, consent, ids, counts, scores, now, idle_secs=20 * 60, row_cap=None):
+def feedback_model(state, keys, items, consent, ids, counts, scores, now, idle_secs=20 * 60, row_cap=None, times=None):
     """NumPy statement of ClickFeedback.observe (srn_feedback.hip): what the device computes, bit for bit.  It needs no GPU and no library.
     state: dict, 128-bit key -> (ids uint64[c], n_model, epoch); updated in place.  keys = (hi, lo); consent / scores may be None (all consent / every entry a model
     entry).  ids[n, how_many], counts[n]: the rows just served to the requests.  Requests j = 0..n-1 in order, with one `now`:
@@ -651,6 +662,7 @@ def feedback_model(state, keys, items, consent, ids, counts, scores, now, idle_s
       no entry for the key       rank NONE (first_seen);   an entry with now > epoch and now - epoch > idle_secs: rank NONE (idle_expired)
       otherwise observed:        r = 1-based position of items[j] among the entry's ids (0: absent), FILLED or-ed in when r > n_model
       then, with consent:        the entry becomes (ids[j, :c], finite scores among those c, now), c = counts[j] (0xFFFFFFFF -> 0; above how_many -> how_many)
+    times (rule T): request j's own clock, read in `now`'s place -- the call is n one-request calls, call j at times[j], in request order.
     -> (ranks uint32[n], counters): the words of ClickFeedback.stats() plus "hist_model" / "hist_filled", hits by rank ([0] unused): uint64[row_cap + 1], or with
     row_cap = None as long as the widest row of the call and the state needs."""
     hi, lo = (np.asarray(a, np.uint64) for a in keys)
@@ -666,7 +678,11 @@ def feedback_model(state, keys, items, consent, ids, counts, scores, now, idle_s
     widest = max([how_many] + [len(e[0]) for e in state.values()]) if row_cap is None else int(row_cap)   # (a stored row may be wider than this call's)
     ctr["hist_model"], ctr["hist_filled"] = np.zeros(widest + 1, np.uint64), np.zeros(widest + 1, np.uint64)
     now = int(now)
+    if times is not None and len(times) != n:
+        raise ValueError("times must have one entry per request")
     for j in range(n):
+        if times is not None:
+            now = int(times[j])
         ctr["requests"] += 1
         if consent is not None and not consent[j]:
             ctr["no_consent"] += 1
@@ -720,14 +736,22 @@ class ClickFeedback:
         self.last_ranks = None
         self.last_error = None          # recommend_batch(..., feedback=self): the error of a call the log refused (its rows were served all the same)
 
-    def observe(self, keys, item_ids, consent, ids, counts, scores=None, now=0):
+    def observe(self, keys, item_ids, consent, ids, counts, scores=None, now=0, times=None):
         """Requests (keys[i], item_ids[i], consent[i]) and the rows just served to them (ids[n, how_many], counts[n], scores or None) -> ranks[n]: the 1-based rank of
         the clicked item in the visitor's PREVIOUS row (0: a miss; capi.FEEDBACK_FILLED or-ed in for a filled entry) or capi.FEEDBACK_NONE where there is no previous
         row to score; then the rows are remembered.  NumPy arrays in, a uint32 array out; tensors on the log's GPU are read in place on the current stream, without
-        synchronising, and the ranks are an int32 tensor there (the same bits).  The result is also left in self.last_ranks."""
+        synchronising, and the ranks are an int32 tensor there (the same bits).  The result is also left in self.last_ranks.
+        times (srn_feedback_observe*_at): request i's own clock in seconds, an array or tensor like the others -- the call gives what one call per
+        request at times[i] gives, in request order, and `now` is only the capacity rule's sweep clock: pass a lower bound of times (0 reads the wall clock, which is
+        wrong for a recorded log)."""
         hi, lo = keys
         n = len(item_ids)
         arrs = [hi, lo, item_ids, ids, counts] + ([consent] if consent is not None else []) + ([scores] if scores is not None else [])
+        if times is not None:
+            if len(times) != n:
+                raise ValueError("times must have one entry per request")
+            if (_is_torch(times) and times.device.type == "cuda") != (_is_torch(hi) and hi.device.type == "cuda") or (_is_torch(times) and times.device != hi.device):
+                raise ValueError("times must be where keys are: a tensor on the same GPU, or an array")
         if any(len(a) != n for a in arrs) or ids.ndim != 2 or (scores is not None and tuple(scores.shape) != tuple(ids.shape)):
             raise ValueError("keys, item_ids, consent and counts must have one entry per row of ids[n, how_many] (and scores its shape)")
         how_many = int(ids.shape[1])
@@ -746,6 +770,14 @@ class ClickFeedback:
             ranks = torch.zeros(n, dtype=torch.int32, device=torch.device("cuda", self.device))
             stream = torch.cuda.current_stream(self.device).cuda_stream
             p = lambda a: None if a is None else C.c_void_p(a.data_ptr())
+            if times is not None:
+                if times.dtype not in (torch.int64, getattr(torch, "uint64", torch.int64)):
+                    raise TypeError("times must be a 64-bit integer tensor")
+                tm = times.contiguous()
+                capi.check(capi.lib().srn_feedback_observe_device_at(self._h, p(t[0]), p(t[1]), p(t[2]), p(con), p(tm), n, int(now), p(t[3]), p(sc), p(t[4]), how_many,
+                                                                     p(ranks), C.c_void_p(stream)))
+                self.last_ranks = ranks
+                return ranks
             capi.check(capi.lib().srn_feedback_observe_device(self._h, p(t[0]), p(t[1]), p(t[2]), p(con), n, int(now), p(t[3]), p(sc), p(t[4]), how_many, p(ranks),
                                                               C.c_void_p(stream)))
             self.last_ranks = ranks
@@ -756,6 +788,12 @@ class ClickFeedback:
         con = None if consent is None else np.ascontiguousarray(as_np(consent)).astype(np.uint8)
         sc = None if scores is None else np.ascontiguousarray(as_np(scores), dtype=np.float64)
         ranks = np.zeros(n, np.uint32)
+        if times is not None:
+            tm = capi.as_u64(as_np(times))
+            capi.check(capi.lib().srn_feedback_observe_at(self._h, capi.ptr(hi), capi.ptr(lo), capi.ptr(it), capi.ptr(con), capi.ptr(tm), n, int(now), capi.ptr(rows),
+                                                          capi.ptr(sc), capi.ptr(cnt), how_many, capi.ptr(ranks)))
+            self.last_ranks = ranks
+            return ranks
         capi.check(capi.lib().srn_feedback_observe(self._h, capi.ptr(hi), capi.ptr(lo), capi.ptr(it), capi.ptr(con), n, int(now), capi.ptr(rows), capi.ptr(sc),
                                                    capi.ptr(cnt), how_many, capi.ptr(ranks)))
         self.last_ranks = ranks
@@ -797,13 +835,13 @@ class ClickFeedback:
     __del__ = close
 
 
-def _observe_served(feedback, keys, item_ids, consent, ids, counts, scores, now):
+def _observe_served(feedback, keys, item_ids, consent, ids, counts, scores, now, times=None):
     """recommend_batch's call of feedback.observe.  The session store has advanced and the rows are written by now, so a log that refuses the call (SRN_ENOMEM under the
     capacity rule, counted in stats()["refused"]) must not fail the serving call: the refusal becomes a warning, feedback.last_ranks None and feedback.last_error the
     exception; the log is as it was."""
     feedback.last_error = None
     try:
-        feedback.observe(keys, item_ids, consent, ids, counts, scores, now=now)
+        feedback.observe(keys, item_ids, consent, ids, counts, scores, now=now, times=times)
     except capi.SerenadeError as e:
         if e.code != capi.SRN_ENOMEM:
             raise
@@ -812,7 +850,7 @@ def _observe_served(feedback, keys, item_ids, consent, ids, counts, scores, now)
 
 
 def recommend_batch(index, store, keys, item_ids, consent=None, *, k, m, how_many, max_items_in_session=2, enable_business_logic=False, now=0,
-                    scores=False, exclude_seen=False, fill=False, feedback=None):
+                    scores=False, exclude_seen=False, fill=False, feedback=None, times=None):
     """/v1/recommend for a batch: request i = (keys[i], item_ids[i], consent[i]); the result is what the requests served one after the other give.
     keys: (hi, lo) uint64 arrays / tensors, or a list of session-id strings.  -> (ids[n, how_many], counts[n]) and scores[n, how_many] with scores=True.
     NumPy arrays (or CPU tensors) in, NumPy arrays out; tensors on the index's GPU are read in place (on the current stream, without synchronising) and the
@@ -822,14 +860,24 @@ def recommend_batch(index, store, keys, item_ids, consent=None, *, k, m, how_man
     fill (SRN_FLAG_FILL): rows of fewer than how_many entries are filled from the index's fallback ranking (score -inf), leaving out what the request excludes.
     feedback (a ClickFeedback): the call's requests and rows also go through feedback.observe -- enqueued behind the recommend call on the same stream, with the same
     `now` (the clock is read once here when now = 0); the requests' ranks are left in feedback.last_ranks.  The return value is the same with or without it, also when
-    the log refuses the call (its capacity is reached): that is a RuntimeWarning, feedback.last_ranks None and the error in feedback.last_error."""
+    the log refuses the call (its capacity is reached): that is a RuntimeWarning, feedback.last_ranks None and the error in feedback.last_error.
+    times (srn_recommend_batch*_at): request i's own clock in seconds (uint64 / int64; 0 is a time like any other), an array or tensor like keys -- the
+    call leaves rows, store, an attached harvest and the feedback log (which receives the same times) as one call per request at times[i] would, in request order;
+    sessions end by idle time inside the call.  `now` is then only the SWEEP CLOCK of the capacity rule's automatic sweep and must be a lower bound of times; left at 0
+    it is int(times.min()) -- for tensors that is ONE SYNCHRONISATION with the device, so a caller who knows a lower bound passes it.  (A log whose smallest time is
+    0 still reads the wall clock there, as everywhere in the ABI.)"""
     n = len(item_ids)
+    if times is not None:
+        if len(times) != n:
+            raise ValueError("times must have one entry per request")
+        if not int(now) and n:
+            now = int(times.min())
     if feedback is not None:
         if how_many > feedback.row_cap:
             raise ValueError("how_many %d above the feedback log's row_cap %d" % (how_many, feedback.row_cap))
         if feedback.device != index.info["device"]:
             raise ValueError("the feedback log and the index are on different devices")
-        now = int(now) or int(time.time())
+        now = int(now) or (int(time.time()) if times is None else 0)
     if isinstance(keys, list) and (not keys or isinstance(keys[0], (str, bytes))):
         if len(keys) != n:
             raise ValueError("keys, item_ids and consent differ in length")
@@ -860,6 +908,19 @@ def recommend_batch(index, store, keys, item_ids, consent=None, *, k, m, how_man
         sc = torch.zeros((n, how_many), dtype=torch.float64, device=dev)
         cnt = torch.zeros(n, dtype=torch.int32, device=dev)
         stream = torch.cuda.current_stream(device).cuda_stream
+        if times is not None:
+            if not (_is_torch(times) and times.device.type == "cuda" and times.device.index == device):
+                raise ValueError("times must be a tensor on the index's GPU (device %d), like keys" % device)
+            if times.dtype not in (torch.int64, getattr(torch, "uint64", torch.int64)):
+                raise TypeError("times must be a 64-bit integer tensor")
+            tm = times.contiguous()
+            capi.check(capi.lib().srn_recommend_batch_device_at(
+                index._h, sh, C.c_void_p(hi.data_ptr()), C.c_void_p(lo.data_ptr()), C.c_void_p(it.data_ptr()), None if con is None else C.c_void_p(con.data_ptr()),
+                C.c_void_p(tm.data_ptr()), n, int(now), int(max_items_in_session), int(k), int(m), int(how_many), flags,
+                C.c_void_p(ids.data_ptr()), C.c_void_p(sc.data_ptr()), C.c_void_p(cnt.data_ptr()), C.c_void_p(stream)))
+            if feedback is not None and n:
+                _observe_served(feedback, (hi, lo), it, con, ids, cnt, sc, now, tm)
+            return (ids, cnt, sc) if scores else (ids, cnt)
         capi.check(capi.lib().srn_recommend_batch_device(
             index._h, sh, C.c_void_p(hi.data_ptr()), C.c_void_p(lo.data_ptr()), C.c_void_p(it.data_ptr()), None if con is None else C.c_void_p(con.data_ptr()),
             n, int(now), int(max_items_in_session), int(k), int(m), int(how_many), flags,
@@ -870,8 +931,93 @@ def recommend_batch(index, store, keys, item_ids, consent=None, *, k, m, how_man
     hi, lo, it = (capi.as_u64(a.numpy() if _is_torch(a) else a) for a in arrs[:3])
     con = None if consent is None else np.ascontiguousarray(consent.numpy() if _is_torch(consent) else consent).astype(np.uint8)
     ids, sc, cnt = np.zeros((n, how_many), np.uint64), np.zeros((n, how_many), np.float64), np.zeros(n, np.uint32)
+    if times is not None:
+        if _is_torch(times) and times.device.type == "cuda":
+            raise ValueError("times must be where keys are: an array or CPU tensor here")
+        tm = capi.as_u64(times.numpy() if _is_torch(times) else times)
+        capi.check(capi.lib().srn_recommend_batch_at(index._h, sh, capi.ptr(hi), capi.ptr(lo), capi.ptr(it), capi.ptr(con), capi.ptr(tm), n, int(now),
+                                                     int(max_items_in_session), int(k), int(m), int(how_many), flags, capi.ptr(ids), capi.ptr(sc), capi.ptr(cnt)))
+        if feedback is not None and n:
+            _observe_served(feedback, (hi, lo), it, con, ids, cnt, sc, now, tm)
+        return (ids, cnt, sc) if scores else (ids, cnt)
     capi.check(capi.lib().srn_recommend_batch(index._h, sh, capi.ptr(hi), capi.ptr(lo), capi.ptr(it), capi.ptr(con), n, int(now), int(max_items_in_session),
                                               int(k), int(m), int(how_many), flags, capi.ptr(ids), capi.ptr(sc), capi.ptr(cnt)))
     if feedback is not None and n:
         _observe_served(feedback, (hi, lo), it, con, ids, cnt, sc, now)
     return (ids, cnt, sc) if scores else (ids, cnt)
+
+
+# ---- replay: a recorded click log through the timed batch ----
+def replay_plan(times, batch=1 << 20, every=None):
+    """How replay() cuts a time-sorted log -> [(start, stop, boundary)]: the calls in order, requests start..stop-1 each, and `boundary` the multiple t of `every`
+    that on_boundary is called with before the call (None: no boundary there).  With every=S there is a cut before every request i >= 1 whose time lies in another
+    S-second interval than its predecessor's (times[i] // S != times[i - 1] // S), at t = times[i] // S * S -- a gap that spans several multiples is one cut, at the
+    last of them; the stretches between those cuts are served in calls of at most `batch` requests.  ValueError if times decreases anywhere."""
+    t = np.asarray(times).astype(np.uint64)
+    n = len(t)
+    if batch < 1 or (every is not None and every < 1):
+        raise ValueError("batch and every must be positive")
+    if n > 1 and bool((t[1:] < t[:-1]).any()):
+        raise ValueError("replay: times must not decrease (sort the log by time first)")
+    edges = [(0, None)]
+    if every is not None and n > 1:
+        q = t // np.uint64(every)
+        edges += [(int(i), int(q[i]) * int(every)) for i in np.flatnonzero(q[1:] != q[:-1]) + 1]
+    plan = []
+    for (a, boundary), (b, _) in zip(edges, edges[1:] + [(n, None)]):
+        for s in range(a, b, int(batch)):
+            plan.append((s, min(s + int(batch), b), boundary if s == a else None))
+    return plan
+
+
+def replay(index, store, keys, item_ids, times, consent=None, *, k, m, how_many, max_items_in_session=2, batch=1 << 20, every=None, on_boundary=None, feedback=None,
+           exclude_seen=False, fill=False, enable_business_logic=False, collect=False):
+    """Serves a recorded click log (keys[i], item_ids[i], times[i], consent[i]), sorted by time, through recommend_batch(..., times=...): every request sees the store,
+    the harvest and the feedback log as it would have at its own second, at the speed of the batch path.  Arrays or tensors as recommend_batch takes them (times on the
+    GPU are copied to the host once, to plan the cuts and read the sweep clocks).  The log is cut into calls by replay_plan(times, batch, every): at most `batch` requests each and, with
+    every=S, a cut wherever the log crosses a multiple t of S seconds -- there on_boundary(t) is called before the requests at or after t are served: the place to
+    store.sweep(t), or to refresh the ranking with index.set_fallback_trending(store, n, now=t).  Each call's sweep clock is its first request's time.  ValueError
+    before anything is served if times decreases anywhere.  No device code of its own.
+    -> {"requests", "calls", "boundaries"}, plus feedback.stats() under "feedback" with a feedback log, plus with collect=True the calls' concatenated "ids",
+    "counts" and (with a feedback log) "ranks"."""
+    n = len(item_ids)
+    if len(times) != n:
+        raise ValueError("times must have one entry per request")
+    host_times = times.cpu().numpy() if _is_torch(times) else np.asarray(times)
+    plan = replay_plan(host_times, batch, every)
+    if isinstance(keys, list) and (not keys or isinstance(keys[0], (str, bytes))):
+        if len(keys) != n:
+            raise ValueError("keys, item_ids and consent differ in length")
+        keys = session_keys(keys)
+    hi, lo = keys
+    out = {"requests": n, "calls": 0, "boundaries": 0}
+    parts = {"ids": [], "counts": [], "ranks": []}
+    for start, stop, boundary in plan:
+        if boundary is not None:
+            out["boundaries"] += 1
+            if on_boundary is not None:
+                on_boundary(boundary)
+        if stop == start:
+            continue
+        sl = slice(start, stop)
+        ids, counts = recommend_batch(index, store, (hi[sl], lo[sl]), item_ids[sl], None if consent is None else consent[sl], k=k, m=m, how_many=how_many,
+                                      max_items_in_session=max_items_in_session, enable_business_logic=enable_business_logic, now=int(host_times[start]),
+                                      exclude_seen=exclude_seen, fill=fill, feedback=feedback, times=times[sl])
+        out["calls"] += 1
+        if collect:
+            parts["ids"].append(ids)
+            parts["counts"].append(counts)
+            if feedback is not None:
+                parts["ranks"].append(feedback.last_ranks)
+    if feedback is not None:
+        out["feedback"] = feedback.stats()
+    if collect:
+        for name, got in parts.items():
+            if name == "ranks" and feedback is None:
+                continue
+            if got and _is_torch(got[0]):
+                import torch
+                out[name] = torch.cat(got)
+            else:
+                out[name] = np.concatenate(got) if got else np.zeros((0, how_many) if name == "ids" else 0, np.uint64 if name == "ids" else np.uint32)
+    return out
