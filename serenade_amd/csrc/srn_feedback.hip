@@ -20,8 +20,11 @@
 //              2048 workgroups, each taking every 2048th block of positions, so that a call of 2^20 requests ends in at most 2048 atomics per counter word, not 65536
 //   fb_store   behind fb_rank: the run's last request writes its row, count, n_model, epoch and state full, once (the same lane groups)
 // Integer work throughout: ranks, counters and the table's entries do not depend on the run or on how the requests are cut into calls.
-// A batch whose requests carry their own clocks (srn_feedback_observe*_at) runs fb_find_at, fb_rank_at and fb_store_at in their places, behind one
-// gather of the times into sorted order.
+// A batch whose requests carry their own clocks (srn_feedback_observe*_at) runs the timed form of fb_find, fb_rank and fb_store -- one body each,
+// template <bool kTimed> -- behind one gather of the times into sorted order: a run head tests its slot's epoch against its own time; any other request tests its
+// predecessor's time -- the epoch the predecessor's row would have been stored with -- and a break is counted as idle_expired; the run's last request stores its own
+// time.  The runs are the untimed call's, so one max scan over the run heads still gives the slot.
+// The sort, the run predicates and the find-or-claim probe are srn_visitors.h's, shared with the session store.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -36,6 +39,7 @@
 #include "srn_runtime.h"
 #include "srn_device.h"
 #include "srn_sessions_dev.h"   // Table, the slot states, idle_or_old, wall_secs
+#include "srn_visitors.h"       // key_hash, the run predicates, find_or_claim, the key sort
 #include "srn_hipsync.h"
 
 struct srn_feedback {
@@ -66,13 +70,13 @@ constexpr uint32_t kRankBlocks = 2048;          // fb_rank's grid at the most (2
 constexpr uint32_t kFbHead = 40;                // bytes before the ids
 struct FbSlot { uint64_t key_hi, key_lo, epoch; uint32_t count, state, n_model, pad; };
 static_assert(sizeof(FbSlot) == kFbHead, "slot header");
+static_assert(offsetof(FbSlot, key_lo) == offsetof(SlotHead, key_lo) && offsetof(FbSlot, state) == offsetof(SlotHead, state), "find_or_claim probes a slot as SlotHead");
 // bins of the counters: the words of srn_feedback_stats_t in its order, then the two histograms
 enum : uint32_t { kRequests = 0, kNoConsent = 1, kFirstSeen = 2, kIdleExpired = 3, kObserved = 4, kHitsModel = 5, kHitsFilled = 6, kStored = 7, kHist = 8 };
 enum : uint32_t { kNew = 0, kIdle = 1, kLive = 2 };   // what fb_find saw in a head's slot
 
 __device__ __forceinline__ FbSlot* fb_slot(const Table& t, uint32_t s) { return (FbSlot*)(t.base + (size_t)s * t.stride); }
 __device__ __forceinline__ uint64_t* fb_ids(FbSlot* h) { return (uint64_t*)((char*)h + kFbHead); }
-__device__ __forceinline__ uint32_t key_hash(uint64_t hi, uint64_t lo) { return (uint32_t)dev_mix64(lo ^ dev_mix64(hi)); }
 __device__ __forceinline__ bool finite_bits(uint64_t b) { return ((b >> 52) & 0x7FFull) != 0x7FFull; }
 
 struct ObsArgs {
@@ -91,24 +95,14 @@ struct ObsArgs {
     uint32_t* out_rank;      // [n] by REQUEST index (may be null)
     unsigned long long* ctr;
     uint32_t* err;
+    const uint64_t* when;    // a timed batch: [n] times[order[p]], read in `now`'s place, so that a position reads when[p] and when[p - 1] as adjacent
+                             // words.  Null and never read in an untimed one
 };
-__device__ __forceinline__ bool consents(const ObsArgs& a, uint32_t req) { return a.consent == nullptr || a.consent[req] != 0; }
 // the row served to request req: its length as it is stored
 __device__ __forceinline__ uint32_t served_count(const ObsArgs& a, uint32_t req) { const uint32_t c = a.counts[req]; return c == SRN_FEEDBACK_NONE ? 0u : min(c, a.how_many); }
 
-__global__ void __launch_bounds__(kTPB) fb_keys_init(const uint64_t* __restrict__ lo, uint32_t n, uint64_t* __restrict__ key, uint32_t* __restrict__ idx) {
-    const uint32_t i = blockIdx.x * kTPB + threadIdx.x;
-    if (i < n) { key[i] = lo[i]; idx[i] = i; }
-}
-__global__ void __launch_bounds__(kTPB) fb_keys_gather(const uint64_t* __restrict__ src, const uint32_t* __restrict__ idx, uint32_t n, uint64_t* __restrict__ key) {
-    const uint32_t i = blockIdx.x * kTPB + threadIdx.x;
-    if (i < n) key[i] = src[idx[i]];
-}
-__global__ void __launch_bounds__(kTPB) fb_keys_consent(const uint8_t* __restrict__ consent, const uint32_t* __restrict__ idx, uint32_t n, uint64_t* __restrict__ key) {
-    const uint32_t i = blockIdx.x * kTPB + threadIdx.x;
-    if (i < n) key[i] = consent[idx[i]] ? 0ull : 1ull;
-}
-
+// one lane per run head: its slot, and whether the stored entry is new, idle -- at `now` or (timed) at the head's own time -- or live
+template <bool kTimed>
 __global__ void __launch_bounds__(kTPB) fb_find(ObsArgs a) {
     const uint32_t p = blockIdx.x * kTPB + threadIdx.x;
     if (p >= a.n) return;
@@ -116,30 +110,23 @@ __global__ void __launch_bounds__(kTPB) fb_find(ObsArgs a) {
     a.headpos[p] = 0;
     if (!consents(a, req)) return;
     const uint64_t hi = a.key_hi[req], lo = a.key_lo[req];
-    if (p) {
-        const uint32_t pr = a.order[p - 1];
-        if (consents(a, pr) && a.key_hi[pr] == hi && a.key_lo[pr] == lo) return;   // not a head
+    if (run_prev(a, p, hi, lo) != kNone) return;   // not a head
+    const Claim c = find_or_claim(a.t, hi, lo);
+    uint32_t status = kNew;
+    if (c.slot == kNone) atomicOr(a.err, 1u);
+    else {
+        FbSlot* s = fb_slot(a.t, c.slot);
+        uint64_t now = a.now;
+        if constexpr (kTimed) now = a.when[p];
+        if (c.fresh) { s->key_hi = hi; s->key_lo = lo; s->epoch = 0; s->count = 0; s->n_model = 0; }
+        else status = idle_or_old(now, s->epoch, a.idle) ? kIdle : kLive;
     }
-    // find-or-insert: a slot claimed during this kernel belongs to another key
-    uint32_t h = key_hash(hi, lo) & a.t.mask, found = kNone, status = kNew;
-    for (uint32_t probes = 0; probes <= a.t.mask; ++probes, h = (h + 1) & a.t.mask) {
-        FbSlot* s = fb_slot(a.t, h);
-        uint32_t st = __hip_atomic_load(&s->state, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (st == kEmpty) {
-            st = atomicCAS(&s->state, kEmpty, kClaimed);
-            if (st == kEmpty) { s->key_hi = hi; s->key_lo = lo; s->epoch = 0; s->count = 0; s->n_model = 0; found = h; break; }
-        }
-        if (st == kFull && s->key_hi == hi && s->key_lo == lo) {
-            found = h;
-            status = idle_or_old(a.now, s->epoch, a.idle) ? kIdle : kLive;
-            break;
-        }
-    }
-    if (found == kNone) atomicOr(a.err, 1u);
-    a.slot_of[p] = found; a.status[p] = status; a.headpos[p] = p;
+    a.slot_of[p] = c.slot; a.status[p] = status; a.headpos[p] = p;
 }
 
+// One lane group per request; timed, a request inside a run first tests its predecessor's time and counts a break as idle_expired.
 // No lane leaves early and the round count is the same across the wave: the ballots need all 64 lanes.  Dynamic LDS: one u32 per bin.
+template <bool kTimed>
 __global__ void __launch_bounds__(kTPB) fb_rank(ObsArgs a) {
     extern __shared__ uint32_t bins[];
     const uint32_t n_bins = kHist + 2u * (a.row_cap + 1u);
@@ -163,157 +150,12 @@ __global__ void __launch_bounds__(kTPB) fb_rank(ObsArgs a) {
             else {
                 const uint64_t hi = a.key_hi[req], lo = a.key_lo[req];
                 item = a.item[req];
-                bool head = p == 0;
-                uint32_t pr = 0;
-                if (!head) { pr = a.order[p - 1]; head = !consents(a, pr) || a.key_hi[pr] != hi || a.key_lo[pr] != lo; }
-                if (head) {
+                const uint32_t pr = run_prev(a, (uint32_t)p, hi, lo);
+                if (pr == kNone) {   // a run head
                     const uint32_t st = a.status[p], slot = a.slot_of[p];
                     kind = st == kLive ? kObserved : st == kIdle ? kIdleExpired : kFirstSeen;
                     if (st == kLive && slot != kNone) { FbSlot* s = fb_slot(a.t, slot); c = min(s->count, a.row_cap); n_model = s->n_model; row = fb_ids(s); }
-                } else {   // the row served to the previous request of the run
-                    kind = kObserved;
-                    c = served_count(a, pr); n_model = c;
-                    row = a.ids + (size_t)pr * a.how_many;
-                    if (a.scores) sc = a.scores + (size_t)pr * a.how_many;
-                }
-            }
-        }
-        uint32_t found = 0, fin = 0;                                 // the same in every lane of the group
-        for (uint32_t r = 0; r < a.rounds; ++r) {
-            const uint32_t i = (r << a.lanes_shift) + lane;
-            const bool in = i < c;
-            const bool match = in && row[i] == item;
-            const bool finite = in && sc && finite_bits(sc[i]);
-            const uint32_t mm = (uint32_t)(__ballot(match) >> gbase) & gmask, mf = (uint32_t)(__ballot(finite) >> gbase) & gmask;
-            if (!found && mm) found = (r << a.lanes_shift) + (uint32_t)__ffs((int)mm);
-            fin += __popc(mf);
-        }
-        if (sc) n_model = fin;
-        if (kind != kRequests && lane == 0) {
-            uint32_t rank = SRN_FEEDBACK_NONE;
-            atomicAdd(&bins[kRequests], 1u);
-            atomicAdd(&bins[kind], 1u);
-            if (kind != kNoConsent) atomicAdd(&bins[kStored], 1u);
-            if (kind == kObserved) {
-                const bool filled = found > n_model;
-                rank = found | (filled ? SRN_FEEDBACK_FILLED : 0u);
-                if (found) { atomicAdd(&bins[filled ? kHitsFilled : kHitsModel], 1u); atomicAdd(&bins[kHist + (filled ? a.row_cap + 1u : 0u) + found], 1u); }   // found <= c <= row_cap
-            }
-            if (a.out_rank) a.out_rank[req] = rank;
-        }
-    }
-    __syncthreads();
-    for (uint32_t i = threadIdx.x; i < n_bins; i += kTPB) { const uint32_t v = bins[i]; if (v) atomicAdd(&a.ctr[i], (unsigned long long)v); }
-}
-
-// the run's last request writes the row it was served: the same lane groups, lane l the positions l, l + lanes, ...
-__global__ void __launch_bounds__(kTPB) fb_store(ObsArgs a) {
-    const uint64_t tid = (uint64_t)blockIdx.x * kTPB + threadIdx.x;
-    const uint64_t p = tid >> a.lanes_shift;
-    const uint32_t lanes = 1u << a.lanes_shift, lane = (uint32_t)tid & (lanes - 1);
-    const uint32_t gbase = (threadIdx.x & 63u) & ~(lanes - 1), gmask = (1u << lanes) - 1u;
-    FbSlot* s = nullptr;
-    uint32_t c = 0;
-    const uint64_t* row = nullptr; const uint64_t* sc = nullptr;
-    if (p < a.n) {
-        const uint32_t req = a.order[p];
-        bool last = consents(a, req);
-        if (last && p + 1 < a.n) {
-            const uint32_t nx = a.order[p + 1];
-            last = !(consents(a, nx) && a.key_hi[nx] == a.key_hi[req] && a.key_lo[nx] == a.key_lo[req]);
-        }
-        const uint32_t slot = last ? a.slot_of[a.run_start[p]] : kNone;
-        if (slot != kNone) {
-            s = fb_slot(a.t, slot);
-            c = served_count(a, req);                            // <= how_many <= row_cap
-            row = a.ids + (size_t)req * a.how_many;
-            if (a.scores) sc = a.scores + (size_t)req * a.how_many;
-        }
-    }
-    uint64_t* dst = s ? fb_ids(s) : nullptr;
-    uint32_t fin = 0;
-    for (uint32_t r = 0; r < a.rounds; ++r) {
-        const uint32_t i = (r << a.lanes_shift) + lane;
-        const bool in = i < c;
-        if (in) dst[i] = row[i];
-        const bool finite = in && sc && finite_bits(sc[i]);
-        fin += __popc((uint32_t)(__ballot(finite) >> gbase) & gmask);
-    }
-    if (s && lane == 0) { s->count = c; s->n_model = sc ? fin : c; s->epoch = a.now; s->state = kFull; }
-}
-
-// ---- the timed batch: every request its own clock ----
-// t: the requests' times by SORTED position (one gather through `order`: a position reads t[p] and t[p - 1] as adjacent words).  A run head tests its slot's epoch against
-// its own time; any other request tests its predecessor's time -- the epoch the predecessor's row would have been stored with -- and a break is counted as idle_expired;
-// the run's last request stores its own time.  The runs are the untimed call's, so one max scan over the run heads still gives the slot.
-struct ObsTimedArgs { ObsArgs a; const uint64_t* t; };   // (a.now is not read)
-__global__ void __launch_bounds__(kTPB) fb_times_gather(const uint64_t* __restrict__ times, const uint32_t* __restrict__ order, uint32_t n, uint64_t* __restrict__ t) {
-    const uint32_t p = blockIdx.x * kTPB + threadIdx.x;
-    if (p < n) t[p] = times[order[p]];
-}
-__global__ void __launch_bounds__(kTPB) fb_find_at(ObsTimedArgs ta) {
-    const ObsArgs& a = ta.a;
-    const uint32_t p = blockIdx.x * kTPB + threadIdx.x;
-    if (p >= a.n) return;
-    const uint32_t req = a.order[p];
-    a.headpos[p] = 0;
-    if (!consents(a, req)) return;
-    const uint64_t hi = a.key_hi[req], lo = a.key_lo[req];
-    if (p) {
-        const uint32_t pr = a.order[p - 1];
-        if (consents(a, pr) && a.key_hi[pr] == hi && a.key_lo[pr] == lo) return;   // not a head
-    }
-    // find-or-insert: a slot claimed during this kernel belongs to another key
-    uint32_t h = key_hash(hi, lo) & a.t.mask, found = kNone, status = kNew;
-    for (uint32_t probes = 0; probes <= a.t.mask; ++probes, h = (h + 1) & a.t.mask) {
-        FbSlot* s = fb_slot(a.t, h);
-        uint32_t st = __hip_atomic_load(&s->state, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (st == kEmpty) {
-            st = atomicCAS(&s->state, kEmpty, kClaimed);
-            if (st == kEmpty) { s->key_hi = hi; s->key_lo = lo; s->epoch = 0; s->count = 0; s->n_model = 0; found = h; break; }
-        }
-        if (st == kFull && s->key_hi == hi && s->key_lo == lo) {
-            found = h;
-            status = idle_or_old(ta.t[p], s->epoch, a.idle) ? kIdle : kLive;
-            break;
-        }
-    }
-    if (found == kNone) atomicOr(a.err, 1u);
-    a.slot_of[p] = found; a.status[p] = status; a.headpos[p] = p;
-}
-
-// fb_rank with the break test inside a run.  No lane leaves early and the round count is the same across the wave: the ballots need all 64 lanes.  Dynamic LDS: one u32 per bin.
-__global__ void __launch_bounds__(kTPB) fb_rank_at(ObsTimedArgs ta) {
-    const ObsArgs& a = ta.a;
-    extern __shared__ uint32_t bins[];
-    const uint32_t n_bins = kHist + 2u * (a.row_cap + 1u);
-    for (uint32_t i = threadIdx.x; i < n_bins; i += kTPB) bins[i] = 0;
-    __syncthreads();
-    const uint32_t lanes = 1u << a.lanes_shift, lane = threadIdx.x & (lanes - 1);
-    const uint32_t gbase = (threadIdx.x & 63u) & ~(lanes - 1);   // the group's first lane in the wave
-    const uint32_t gmask = (1u << lanes) - 1u;                   // lanes <= 16
-    const uint64_t groups = (uint64_t)gridDim.x * (kTPB >> a.lanes_shift);
-    const uint32_t trips = (uint32_t)((a.n + groups - 1) / groups);
-    for (uint32_t trip = 0; trip < trips; ++trip) {
-        const uint64_t p = trip * groups + (uint64_t)blockIdx.x * (kTPB >> a.lanes_shift) + (threadIdx.x >> a.lanes_shift);
-        uint32_t kind = kRequests;                                   // (no request: nothing is counted)
-        uint32_t req = 0, c = 0, n_model = 0;                        // c = 0: no position is ever read
-        const uint64_t* row = nullptr; const uint64_t* sc = nullptr;
-        uint64_t item = 0;
-        if (p < a.n) {
-            req = a.order[p];
-            if (!consents(a, req)) kind = kNoConsent;
-            else {
-                const uint64_t hi = a.key_hi[req], lo = a.key_lo[req];
-                item = a.item[req];
-                bool head = p == 0;
-                uint32_t pr = 0;
-                if (!head) { pr = a.order[p - 1]; head = !consents(a, pr) || a.key_hi[pr] != hi || a.key_lo[pr] != lo; }
-                if (head) {
-                    const uint32_t st = a.status[p], slot = a.slot_of[p];
-                    kind = st == kLive ? kObserved : st == kIdle ? kIdleExpired : kFirstSeen;
-                    if (st == kLive && slot != kNone) { FbSlot* s = fb_slot(a.t, slot); c = min(s->count, a.row_cap); n_model = s->n_model; row = fb_ids(s); }
-                } else if (idle_or_old(ta.t[p], ta.t[p - 1], a.idle)) {
+                } else if (kTimed && idle_or_old(a.when[p], a.when[p - 1], a.idle)) {   // (kTimed is a constant: the untimed form holds no trace of this)
                     kind = kIdleExpired;                             // a break: the predecessor's row is idle by the time of this click
                 } else {   // the row served to the previous request of the run
                     kind = kObserved;
@@ -351,9 +193,9 @@ __global__ void __launch_bounds__(kTPB) fb_rank_at(ObsTimedArgs ta) {
     for (uint32_t i = threadIdx.x; i < n_bins; i += kTPB) { const uint32_t v = bins[i]; if (v) atomicAdd(&a.ctr[i], (unsigned long long)v); }
 }
 
-// fb_store with the last request's own time
-__global__ void __launch_bounds__(kTPB) fb_store_at(ObsTimedArgs ta) {
-    const ObsArgs& a = ta.a;
+// the run's last request writes the row it was served, with `now` or (timed) its own time: the same lane groups, lane l the positions l, l + lanes, ...
+template <bool kTimed>
+__global__ void __launch_bounds__(kTPB) fb_store(ObsArgs a) {
     const uint64_t tid = (uint64_t)blockIdx.x * kTPB + threadIdx.x;
     const uint64_t p = tid >> a.lanes_shift;
     const uint32_t lanes = 1u << a.lanes_shift, lane = (uint32_t)tid & (lanes - 1);
@@ -363,11 +205,7 @@ __global__ void __launch_bounds__(kTPB) fb_store_at(ObsTimedArgs ta) {
     const uint64_t* row = nullptr; const uint64_t* sc = nullptr;
     if (p < a.n) {
         const uint32_t req = a.order[p];
-        bool last = consents(a, req);
-        if (last && p + 1 < a.n) {
-            const uint32_t nx = a.order[p + 1];
-            last = !(consents(a, nx) && a.key_hi[nx] == a.key_hi[req] && a.key_lo[nx] == a.key_lo[req]);
-        }
+        const bool last = consents(a, req) && run_last(a, (uint32_t)p, req);
         const uint32_t slot = last ? a.slot_of[a.run_start[p]] : kNone;
         if (slot != kNone) {
             s = fb_slot(a.t, slot);
@@ -385,7 +223,11 @@ __global__ void __launch_bounds__(kTPB) fb_store_at(ObsTimedArgs ta) {
         const bool finite = in && sc && finite_bits(sc[i]);
         fin += __popc((uint32_t)(__ballot(finite) >> gbase) & gmask);
     }
-    if (s && lane == 0) { s->count = c; s->n_model = sc ? fin : c; s->epoch = ta.t[p]; s->state = kFull; }
+    if (s && lane == 0) {
+        uint64_t now = a.now;
+        if constexpr (kTimed) now = a.when[p];
+        s->count = c; s->n_model = sc ? fin : c; s->epoch = now; s->state = kFull;
+    }
 }
 
 // ---- one key, from the host: out[0] = count (~0: unknown key), out[1] = epoch, out[2] = n_model, out[3..] = ids ----
@@ -541,8 +383,7 @@ int fb_observe_device(srn_feedback* f, const uint64_t* d_hi, const uint64_t* d_l
     HIP_TRY(hipSetDevice(f->device));
     // scratch: sort keys and indices (double-buffered), the per-position words, rocPRIM's temporary storage
     size_t tmp = 0, t1 = 0;
-    HIP_TRY(rocprim::radix_sort_pairs(nullptr, t1, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, n, 0, 64, st)); tmp = std::max(tmp, t1);
-    HIP_TRY(rocprim::radix_sort_pairs(nullptr, t1, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, n, 0, 1, st)); tmp = std::max(tmp, t1);
+    if ((rc = key_sort_tmp_bytes(n, st, &tmp))) return rc;
     HIP_TRY(rocprim::inclusive_scan(nullptr, t1, (uint32_t*)nullptr, (uint32_t*)nullptr, n, rocprim::maximum<uint32_t>(), st)); tmp = std::max(tmp, t1);
     const size_t w = align256(n * 4);
     const size_t o_keyA = 0, o_keyB = o_keyA + align256(n * 8), o_idxA = o_keyB + align256(n * 8), o_idxB = o_idxA + w, o_slot = o_idxB + w, o_stat = o_slot + w,
@@ -553,20 +394,12 @@ int fb_observe_device(srn_feedback* f, const uint64_t* d_hi, const uint64_t* d_l
     }
     HIP_TRY(hipStreamWaitEvent(st, f->last, 0));
     char* b = f->ws;
-    uint64_t* keyA = (uint64_t*)(b + o_keyA); uint64_t* keyB = (uint64_t*)(b + o_keyB); uint32_t* idxA = (uint32_t*)(b + o_idxA); uint32_t* idxB = (uint32_t*)(b + o_idxB);
     const dim3 gn = grid_for(n);
     const uint32_t n32 = (uint32_t)n;
     // stable LSD passes: key_lo, key_hi, then (where some request may not consent) the consent bit -- consenting requests first, each visitor's in request order
-    fb_keys_init<<<gn, kTPB, 0, st>>>(d_lo, n32, keyA, idxA);
-    t1 = tmp; HIP_TRY(rocprim::radix_sort_pairs(b + o_tmp, t1, keyA, keyB, idxA, idxB, n, 0, 64, st));
-    fb_keys_gather<<<gn, kTPB, 0, st>>>(d_hi, idxB, n32, keyA);
-    t1 = tmp; HIP_TRY(rocprim::radix_sort_pairs(b + o_tmp, t1, keyA, keyB, idxB, idxA, n, 0, 64, st));
-    const uint32_t* order = idxA;
-    if (d_consent) {
-        fb_keys_consent<<<gn, kTPB, 0, st>>>(d_consent, idxA, n32, keyA);
-        t1 = tmp; HIP_TRY(rocprim::radix_sort_pairs(b + o_tmp, t1, keyA, keyB, idxA, idxB, n, 0, 1, st));
-        order = idxB;
-    }
+    KeySort ks{{(uint64_t*)(b + o_keyA), (uint64_t*)(b + o_keyB)}, {(uint32_t*)(b + o_idxA), (uint32_t*)(b + o_idxB)}, b + o_tmp, tmp, n, st};
+    if ((rc = ks.begin(d_lo)) || (rc = ks.pass(KeyWord{d_hi})) || (d_consent && (rc = ks.pass(KeyNoConsent{d_consent}, 0, 1)))) return rc;
+    const uint32_t* order = ks.order();
     ObsArgs a{};
     a.t = f->tab(); a.key_hi = d_hi; a.key_lo = d_lo; a.item = d_item; a.consent = d_consent;
     a.ids = d_ids; a.scores = (const uint64_t*)d_scores; a.counts = d_counts; a.how_many = (uint32_t)how_many;
@@ -578,17 +411,17 @@ int fb_observe_device(srn_feedback* f, const uint64_t* d_hi, const uint64_t* d_l
     a.out_rank = d_out_rank; a.ctr = f->ctr; a.err = f->err();
     const dim3 gg = grid_for(n << a.lanes_shift);   // (n <= 2^24: 2^28 lanes at the most)
     if (d_times) {   // a timed batch: the same sequence behind one gather of the times into sorted order
-        const ObsTimedArgs ta{a, (const uint64_t*)(b + o_t)};
-        fb_times_gather<<<gn, kTPB, 0, st>>>(d_times, order, n32, (uint64_t*)(b + o_t));
-        fb_find_at<<<gn, kTPB, 0, st>>>(ta);
+        a.when = (const uint64_t*)(b + o_t);
+        key_gather<<<gn, kTPB, 0, st>>>(KeyWord{d_times}, order, n32, (uint64_t*)(b + o_t));
+        fb_find<true><<<gn, kTPB, 0, st>>>(a);
         t1 = tmp; HIP_TRY(rocprim::inclusive_scan(b + o_tmp, t1, a.headpos, a.run_start, n, rocprim::maximum<uint32_t>(), st));
-        fb_rank_at<<<dim3(std::min<unsigned>(gg.x, kRankBlocks)), kTPB, 4 * (size_t)f->n_bins(), st>>>(ta);
-        fb_store_at<<<gg, kTPB, 0, st>>>(ta);
+        fb_rank<true><<<dim3(std::min<unsigned>(gg.x, kRankBlocks)), kTPB, 4 * (size_t)f->n_bins(), st>>>(a);
+        fb_store<true><<<gg, kTPB, 0, st>>>(a);
     } else {
-        fb_find<<<gn, kTPB, 0, st>>>(a);
+        fb_find<false><<<gn, kTPB, 0, st>>>(a);
         t1 = tmp; HIP_TRY(rocprim::inclusive_scan(b + o_tmp, t1, a.headpos, a.run_start, n, rocprim::maximum<uint32_t>(), st));
-        fb_rank<<<dim3(std::min<unsigned>(gg.x, kRankBlocks)), kTPB, 4 * (size_t)f->n_bins(), st>>>(a);
-        fb_store<<<gg, kTPB, 0, st>>>(a);
+        fb_rank<false><<<dim3(std::min<unsigned>(gg.x, kRankBlocks)), kTPB, 4 * (size_t)f->n_bins(), st>>>(a);
+        fb_store<false><<<gg, kTPB, 0, st>>>(a);
     }
     HIP_TRY(hipGetLastError());
     // from here on the log has changed: the next call is ordered behind this one

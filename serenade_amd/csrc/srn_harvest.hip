@@ -30,6 +30,7 @@
 #include "srn_internal.h"
 #include "srn_runtime.h"
 #include "srn_sessions_dev.h"
+#include "srn_visitors.h"       // the key sort
 #include "srn_hipsync.h"
 
 namespace srn {
@@ -125,18 +126,8 @@ __global__ void __launch_bounds__(kTPB) hv_sum_len(const uint32_t* __restrict__ 
 }
 
 // ---- the canonical order ----
-__global__ void __launch_bounds__(kTPB) hv_keys_init(const uint64_t* __restrict__ src, uint32_t n, uint64_t* __restrict__ key, uint32_t* __restrict__ idx) {
-    const uint32_t i = blockIdx.x * kTPB + threadIdx.x;
-    if (i < n) { key[i] = src[i]; idx[i] = i; }
-}
-__global__ void __launch_bounds__(kTPB) hv_keys_gather(const uint64_t* __restrict__ src, const uint32_t* __restrict__ idx, uint32_t n, uint64_t* __restrict__ key) {
-    const uint32_t i = blockIdx.x * kTPB + threadIdx.x;
-    if (i < n) key[i] = src[idx[i]];
-}
-__global__ void __launch_bounds__(kTPB) hv_keys_beyond(const uint64_t* __restrict__ words, const uint32_t* __restrict__ idx, uint32_t n, uint64_t* __restrict__ key) {
-    const uint32_t i = blockIdx.x * kTPB + threadIdx.x;
-    if (i < n) key[i] = idx[i] >= words[kHvCursor] ? 1ull : 0ull;
-}
+// the key sort's last, one-bit word: is place e at or beyond the cursor
+struct KeyBeyond { const uint64_t* words; __device__ __forceinline__ uint64_t operator()(uint32_t e) const { return e >= words[kHvCursor] ? 1ull : 0ull; } };
 
 struct ReadArgs {
     const uint64_t* key_hi; const uint64_t* key_lo; const uint64_t* epoch; const uint32_t* len; const uint64_t* items; const uint64_t* words;
@@ -188,31 +179,23 @@ struct Enter {
     }
 };
 
-struct SortScratch { uint64_t* keyA; uint64_t* keyB; uint32_t* idxA; uint32_t* idxB; uint64_t* lens; uint64_t* off; char* tmp; size_t tmp_bytes; };
-// the canonical order of the log's first n places on `st` (which already waits for `last`): sc->idxA
+struct SortScratch { const uint32_t* order; uint64_t* lens; uint64_t* off; char* tmp; size_t tmp_bytes; };
+// the canonical order of the log's first n places on `st` (which already waits for `last`): sc->order
 int canonical_order(srn_harvest* h, size_t n, hipEvent_t last, hipStream_t st, SortScratch* sc) {
     size_t tmp = 0, t1 = 0;
-    HIP_TRY(rocprim::radix_sort_pairs(nullptr, t1, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, n, 0, 64, st)); tmp = std::max(tmp, t1);
-    HIP_TRY(rocprim::radix_sort_pairs(nullptr, t1, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, n, 0, 1, st)); tmp = std::max(tmp, t1);
+    int rc = key_sort_tmp_bytes(n, st, &tmp); if (rc) return rc;
     HIP_TRY(rocprim::exclusive_scan(nullptr, t1, (uint64_t*)nullptr, (uint64_t*)nullptr, 0ull, n + 1, rocprim::plus<uint64_t>(), st)); tmp = std::max(tmp, t1);
     const size_t k8 = align256((n + 1) * 8), w = align256(n * 4), bytes = 4 * k8 + 2 * w + align256(tmp);
     if (bytes > h->xs_bytes) {   // (an earlier call may still use the scratch: wait for it before it is freed)
         HIP_TRY(hipEventSynchronize(last));
-        int rc = ensure(&h->xs, &h->xs_bytes, bytes); if (rc) return rc;
+        if ((rc = ensure(&h->xs, &h->xs_bytes, bytes))) return rc;
     }
     char* b = h->xs;
-    sc->keyA = (uint64_t*)b; sc->keyB = (uint64_t*)(b + k8); sc->lens = (uint64_t*)(b + 2 * k8); sc->off = (uint64_t*)(b + 3 * k8);
-    sc->idxA = (uint32_t*)(b + 4 * k8); sc->idxB = (uint32_t*)(b + 4 * k8 + w); sc->tmp = b + 4 * k8 + 2 * w; sc->tmp_bytes = tmp;
-    const uint32_t n32 = (uint32_t)n; const dim3 gn = grid_for(n);
-    hv_keys_init<<<gn, kTPB, 0, st>>>(h->key_lo, n32, sc->keyA, sc->idxA);
-    t1 = tmp; HIP_TRY(rocprim::radix_sort_pairs(sc->tmp, t1, sc->keyA, sc->keyB, sc->idxA, sc->idxB, n, 0, 64, st));
-    hv_keys_gather<<<gn, kTPB, 0, st>>>(h->key_hi, sc->idxB, n32, sc->keyA);
-    t1 = tmp; HIP_TRY(rocprim::radix_sort_pairs(sc->tmp, t1, sc->keyA, sc->keyB, sc->idxB, sc->idxA, n, 0, 64, st));
-    hv_keys_gather<<<gn, kTPB, 0, st>>>(h->epoch, sc->idxA, n32, sc->keyA);
-    t1 = tmp; HIP_TRY(rocprim::radix_sort_pairs(sc->tmp, t1, sc->keyA, sc->keyB, sc->idxA, sc->idxB, n, 0, 64, st));
-    hv_keys_beyond<<<gn, kTPB, 0, st>>>(h->words, sc->idxB, n32, sc->keyA);
-    t1 = tmp; HIP_TRY(rocprim::radix_sort_pairs(sc->tmp, t1, sc->keyA, sc->keyB, sc->idxB, sc->idxA, n, 0, 1, st));
+    sc->lens = (uint64_t*)(b + 2 * k8); sc->off = (uint64_t*)(b + 3 * k8); sc->tmp = b + 4 * k8 + 2 * w; sc->tmp_bytes = tmp;
+    KeySort ks{{(uint64_t*)b, (uint64_t*)(b + k8)}, {(uint32_t*)(b + 4 * k8), (uint32_t*)(b + 4 * k8 + w)}, sc->tmp, tmp, n, st};
+    if ((rc = ks.begin(h->key_lo)) || (rc = ks.pass(KeyWord{h->key_hi})) || (rc = ks.pass(KeyWord{h->epoch})) || (rc = ks.pass(KeyBeyond{h->words}, 0, 1))) return rc;
     HIP_TRY(hipGetLastError());
+    sc->order = ks.order();
     return SRN_OK;
 }
 ReadArgs read_args(const srn_harvest* h, const uint32_t* order, size_t n) {
@@ -223,7 +206,7 @@ int export_enqueue(srn_harvest* h, size_t n, size_t cap, uint64_t* d_hi, uint64_
                    uint64_t* d_n, hipEvent_t last, hipStream_t st) {
     SortScratch sc{};
     int rc = canonical_order(h, n, last, st, &sc); if (rc) return rc;
-    const ReadArgs a = read_args(h, sc.idxA, n);
+    const ReadArgs a = read_args(h, sc.order, n);
     hv_export_heads<<<grid_for(n), kTPB, 0, st>>>(a, cap, d_hi, d_lo, d_epoch, d_len, d_n);
     if (items_stride && cap) hv_export_items<<<grid_for(std::min(n, cap) * items_stride), kTPB, 0, st>>>(a, cap, d_items, items_stride);
     HIP_TRY(hipGetLastError());
@@ -440,7 +423,7 @@ int harvest_events_device(srn_harvest* h, uint64_t id_base, size_t cap_rows, uin
         const size_t n = sort_places(h);
         SortScratch sc{};
         int rc = canonical_order(h, n, e.last, st, &sc); if (rc) return rc;
-        const ReadArgs a = read_args(h, sc.idxA, n);
+        const ReadArgs a = read_args(h, sc.order, n);
         hv_event_lens<<<grid_for(n + 1), kTPB, 0, st>>>(a, sc.lens);
         size_t t1 = sc.tmp_bytes;
         HIP_TRY(rocprim::exclusive_scan(sc.tmp, t1, sc.lens, sc.off, 0ull, n + 1, rocprim::plus<uint64_t>(), st));

@@ -35,10 +35,11 @@
 // TTL (rebuild, resize_locked) -- and an attached session harvest (srn_harvest.hip) is handed the entry at both, before the old bytes go away:
 // sess_return_flag + harvest_append between sess_find and sess_store, harvest_dropped behind sess_rebuild over the old table.  Without one nothing here differs.
 //
-// A batch whose requests carry their own clocks (srn_recommend_batch*_at) runs the same sequence with sess_find_at, sess_return_flag_at and
-// sess_store_at in the places of their namesakes: a run is cut into SEGMENTS where a request finds its predecessor's time idle, headpos marks segment heads, a second
-// max scan keeps the run's head for the slot, and the sessions that end inside the call go to the harvest from the call's CSR behind sess_emit.  Without times
-// nothing here differs either.
+// A batch whose requests carry their own clocks (srn_recommend_batch*_at) runs the same sequence with the timed form of sess_find, sess_return_flag
+// and sess_store -- one body each, template <bool kTimed>, the untimed instantiation compiled without a trace of the other: a run is cut into SEGMENTS where a request
+// finds its predecessor's time idle, headpos marks segment heads, a second max scan keeps the run's head for the slot, and the sessions that end inside the call go to
+// the harvest from the call's CSR behind sess_emit.  Without times nothing here differs either.
+// The sort, the run predicates and the find-or-claim probe are srn_visitors.h's, shared with the feedback log and the harvest.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -57,6 +58,7 @@
 #include "srn_runtime.h"
 #include "srn_device.h"
 #include "srn_sessions_dev.h"   // the slot, the table and the handle (shared with srn_trending.hip)
+#include "srn_visitors.h"       // key_hash, the run predicates, find_or_claim, the key sort (shared with srn_feedback.hip, srn_harvest.hip)
 #include "srn_hipsync.h"
 
 namespace srn {
@@ -65,8 +67,9 @@ namespace {
 constexpr uint32_t kTPB = 256;
 constexpr uint32_t kMaxBatch = 1u << 24;       // q_off is 32-bit: n * SRN_MAX_SESSION_LEN < 2^32
 
-__device__ __forceinline__ uint32_t key_hash(uint64_t hi, uint64_t lo) { return (uint32_t)dev_mix64(lo ^ dev_mix64(hi)); }
-
+// One struct for the untimed and the timed batch.  Untimed, when, runpos and run_head are null and never read; timed, `now` is not read: a run is cut
+// into SEGMENTS wherever a request finds its predecessor's time idle, headpos marks segment heads -- so that run_start becomes the segment start and slen is 0 at a
+// break -- and runpos marks run heads only: its inclusive max scan, run_head, is where sess_store<true> and the harvest find the run's slot.
 struct BatchArgs {
     Table t;
     const uint64_t* key_hi; const uint64_t* key_lo; const uint64_t* item; const uint8_t* consent;   // the caller's arrays
@@ -88,56 +91,42 @@ struct BatchArgs {
     uint32_t* p_off;
     uint64_t* pflat;
     uint32_t* err;
+    const uint64_t* when;    // timed: [n] times[order[p]], so that a position reads when[p] and when[p - 1] as adjacent words
+    uint32_t* runpos;        // timed: [n] p for a run head, 0 otherwise; inclusive max scan -> run_head
+    uint32_t* run_head;      // timed: [n]
 };
-__device__ __forceinline__ bool consents(const BatchArgs& a, uint32_t req) { return a.consent == nullptr || a.consent[req] != 0; }
 
-__global__ void __launch_bounds__(kTPB) sess_keys_init(const uint64_t* __restrict__ lo, uint32_t n, uint64_t* __restrict__ key, uint32_t* __restrict__ idx) {
-    const uint32_t i = blockIdx.x * kTPB + threadIdx.x;
-    if (i < n) { key[i] = lo[i]; idx[i] = i; }
-}
-__global__ void __launch_bounds__(kTPB) sess_keys_gather(const uint64_t* __restrict__ src, const uint32_t* __restrict__ idx, uint32_t n, uint64_t* __restrict__ key) {
-    const uint32_t i = blockIdx.x * kTPB + threadIdx.x;
-    if (i < n) key[i] = src[idx[i]];
-}
-__global__ void __launch_bounds__(kTPB) sess_keys_consent(const uint8_t* __restrict__ consent, const uint32_t* __restrict__ idx, uint32_t n, uint64_t* __restrict__ key) {
-    const uint32_t i = blockIdx.x * kTPB + threadIdx.x;
-    if (i < n) key[i] = consent[idx[i]] ? 0ull : 1ull;
-}
-
+// One lane per sorted position.  A run head finds or claims its slot and reads the stored length under the idle rule, against `now` or (timed) its own time; any
+// other request keeps its click iff it differs from its predecessor's, and (timed) starts an empty session where it finds its predecessor's time idle
+template <bool kTimed>
 __global__ void __launch_bounds__(kTPB) sess_find(BatchArgs a) {
     const uint32_t p = blockIdx.x * kTPB + threadIdx.x;
     if (p > a.n) return;
     if (p == a.n) { a.kept[p] = 0; return; }
     const uint32_t req = a.order[p];
-    if (!consents(a, req)) { a.kept[p] = 0; a.headpos[p] = 0; return; }
+    if (!consents(a, req)) { a.kept[p] = 0; a.headpos[p] = 0; if constexpr (kTimed) a.runpos[p] = 0; return; }
     const uint64_t hi = a.key_hi[req], lo = a.key_lo[req], item = a.item[req];
-    bool head = p == 0;
-    uint64_t prev_item = 0;
-    if (!head) {
-        const uint32_t pr = a.order[p - 1];
-        head = !consents(a, pr) || a.key_hi[pr] != hi || a.key_lo[pr] != lo;
-        prev_item = a.item[pr];
+    uint64_t now = a.now;
+    if constexpr (kTimed) now = a.when[p];
+    if (const uint32_t pr = run_prev(a, p, hi, lo); pr != kNone) {
+        if constexpr (kTimed) {
+            a.runpos[p] = 0;
+            if (idle_or_old(now, a.when[p - 1], a.idle)) { a.slen[p] = 0; a.headpos[p] = p; a.kept[p] = 1; return; }   // a break: an empty session, whose first click is kept
+        }
+        a.headpos[p] = 0; a.kept[p] = item != a.item[pr];
+        return;
     }
-    if (!head) { a.kept[p] = item != prev_item; a.headpos[p] = 0; return; }
-    // find-or-insert: a slot claimed during this kernel belongs to another key
-    uint32_t h = key_hash(hi, lo) & a.t.mask, found = kNone, stored = 0;
+    const Claim c = find_or_claim(a.t, hi, lo);
+    uint32_t stored = 0;
     uint64_t last = 0;
-    for (uint32_t probes = 0; probes <= a.t.mask; ++probes, h = (h + 1) & a.t.mask) {
-        SlotHead* s = slot_at(a.t, h);
-        uint32_t st = __hip_atomic_load(&s->state, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (st == kEmpty) {
-            st = atomicCAS(&s->state, kEmpty, kClaimed);
-            if (st == kEmpty) { s->key_hi = hi; s->key_lo = lo; s->epoch = 0; s->len = 0; found = h; break; }
-        }
-        if (st == kFull && s->key_hi == hi && s->key_lo == lo) {
-            found = h;
-            const uint32_t len = s->len;
-            if (len && !idle_or_old(a.now, s->epoch, a.idle)) { stored = len; last = slot_items(s)[len - 1]; }
-            break;
-        }
+    if (c.slot == kNone) atomicOr(a.err, 1u);
+    else {
+        SlotHead* s = slot_at(a.t, c.slot);
+        if (c.fresh) { s->key_hi = hi; s->key_lo = lo; s->epoch = 0; s->len = 0; }
+        else if (const uint32_t len = s->len; len && !idle_or_old(now, s->epoch, a.idle)) { stored = len; last = slot_items(s)[len - 1]; }
     }
-    if (found == kNone) atomicOr(a.err, 1u);
-    a.slot_of[p] = found; a.slen[p] = stored; a.headpos[p] = p;
+    a.slot_of[p] = c.slot; a.slen[p] = stored; a.headpos[p] = p;
+    if constexpr (kTimed) a.runpos[p] = p;
     a.kept[p] = stored == 0 || last != item;
 }
 
@@ -173,150 +162,53 @@ __global__ void __launch_bounds__(kTPB) sess_emit(BatchArgs a) {
     }
 }
 
+// the run's last request writes its window -- the final session -- into the run's slot, with `now` or (timed) ITS time, not the largest one
+template <bool kTimed>
 __global__ void __launch_bounds__(kTPB) sess_store(BatchArgs a) {
     const uint32_t p = blockIdx.x * kTPB + threadIdx.x;
     if (p >= a.n) return;
     const uint32_t req = a.order[p];
-    if (!consents(a, req)) return;
-    if (p + 1 < a.n) {
-        const uint32_t nx = a.order[p + 1];
-        if (consents(a, nx) && a.key_hi[nx] == a.key_hi[req] && a.key_lo[nx] == a.key_lo[req]) return;   // not the run's last request
-    }
-    const uint32_t slot = a.slot_of[a.run_start[p]];
+    if (!consents(a, req) || !run_last(a, p, req)) return;
+    uint32_t head = 0; uint64_t now = a.now;
+    if constexpr (kTimed) { head = a.run_head[p]; now = a.when[p]; } else head = a.run_start[p];
+    const uint32_t slot = a.slot_of[head];
     if (slot == kNone) return;
     SlotHead* s = slot_at(a.t, slot);
     const uint32_t off = a.q_off[req], len = a.q_off[req + 1] - off;
     uint64_t* it = slot_items(s);
     for (uint32_t i = 0; i < len; ++i) it[i] = a.items_flat[off + i];
-    s->len = len; s->epoch = a.now; s->state = kFull;
+    s->len = len; s->epoch = now; s->state = kFull;
 }
 
 // Session harvest, return after idle (srn_harvest.hip): flag[p] for sorted position p, behind sess_find and before sess_store.  A run head whose key was found stored
-// with len > 0 and idle is about to have its slot overwritten: kHvStore (kHvSkip below min_len).  sess_find left such a head with slen 0 and the slot untouched (a slot
-// claimed in this call is in state kClaimed with len 0).  flag[n] = 0.
+// with len > 0 and idle -- at `now` or (timed) at its own time -- is about to have its slot overwritten: kHvStore (kHvSkip below min_len).  sess_find left such a head
+// with slen 0 and the slot untouched (a slot claimed in this call is in state kClaimed with len 0).  flag[n] = 0.
+template <bool kTimed>
 __global__ void __launch_bounds__(kTPB) sess_return_flag(BatchArgs a, uint32_t min_len, uint64_t* __restrict__ flag) {
     const uint32_t p = blockIdx.x * kTPB + threadIdx.x;
     if (p > a.n) return;
     uint64_t f = 0;
     if (p < a.n) {
         const uint32_t req = a.order[p];
-        if (consents(a, req)) {
-            bool head = p == 0;
-            if (!head) { const uint32_t pr = a.order[p - 1]; head = !consents(a, pr) || a.key_hi[pr] != a.key_hi[req] || a.key_lo[pr] != a.key_lo[req]; }
-            const uint32_t slot = head ? a.slot_of[p] : kNone;
-            if (slot != kNone && a.slen[p] == 0) {
-                const SlotHead* s = slot_at(a.t, slot);
-                if (s->state == kFull && s->len > 0 && idle_or_old(a.now, s->epoch, a.idle)) f = s->len >= min_len ? kHvStore : kHvSkip;
-            }
-        }
-    }
-    flag[p] = f;
-}
-
-// ---- the timed batch: every request its own clock ----
-// The untimed call's arrays, read by the same sess_len and sess_emit, plus: t the requests' times by SORTED position (one gather through `order`, so that a position
-// reads t[p] and t[p - 1] as adjacent words), and the RUN's head beside the SEGMENT's.  A run is cut into segments wherever a request finds its predecessor's time idle:
-// a.headpos marks segment heads, so that a.run_start becomes the segment start and a.slen is 0 at a break; runpos marks run heads only and its inclusive max scan,
-// run_head, is where sess_store_at and the harvest find the run's slot.
-struct TimedArgs {
-    BatchArgs a;             // (a.now is not read)
-    const uint64_t* t;       // [n] times[order[p]]
-    uint32_t* runpos;        // [n] p for a run head, 0 otherwise; inclusive max scan -> run_head
-    uint32_t* run_head;      // [n]
-};
-__global__ void __launch_bounds__(kTPB) sess_times_gather(const uint64_t* __restrict__ times, const uint32_t* __restrict__ order, uint32_t n, uint64_t* __restrict__ t) {
-    const uint32_t p = blockIdx.x * kTPB + threadIdx.x;
-    if (p < n) t[p] = times[order[p]];
-}
-__device__ __forceinline__ bool run_head_at(const BatchArgs& a, uint32_t p, uint32_t req) {
-    if (p == 0) return true;
-    const uint32_t pr = a.order[p - 1];
-    return !consents(a, pr) || a.key_hi[pr] != a.key_hi[req] || a.key_lo[pr] != a.key_lo[req];
-}
-
-// sess_find with the request's own time at a run head, and the break test against the predecessor's time everywhere else
-__global__ void __launch_bounds__(kTPB) sess_find_at(TimedArgs ta) {
-    const BatchArgs& a = ta.a;
-    const uint32_t p = blockIdx.x * kTPB + threadIdx.x;
-    if (p > a.n) return;
-    if (p == a.n) { a.kept[p] = 0; return; }
-    const uint32_t req = a.order[p];
-    if (!consents(a, req)) { a.kept[p] = 0; a.headpos[p] = 0; ta.runpos[p] = 0; return; }
-    const uint64_t hi = a.key_hi[req], lo = a.key_lo[req], item = a.item[req], now = ta.t[p];
-    if (!run_head_at(a, p, req)) {
-        ta.runpos[p] = 0;
-        if (idle_or_old(now, ta.t[p - 1], a.idle)) { a.slen[p] = 0; a.headpos[p] = p; a.kept[p] = 1; }   // a break: an empty session, whose first click is kept
-        else { a.headpos[p] = 0; a.kept[p] = item != a.item[a.order[p - 1]]; }
-        return;
-    }
-    // find-or-insert: a slot claimed during this kernel belongs to another key
-    uint32_t h = key_hash(hi, lo) & a.t.mask, found = kNone, stored = 0;
-    uint64_t last = 0;
-    for (uint32_t probes = 0; probes <= a.t.mask; ++probes, h = (h + 1) & a.t.mask) {
-        SlotHead* s = slot_at(a.t, h);
-        uint32_t st = __hip_atomic_load(&s->state, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (st == kEmpty) {
-            st = atomicCAS(&s->state, kEmpty, kClaimed);
-            if (st == kEmpty) { s->key_hi = hi; s->key_lo = lo; s->epoch = 0; s->len = 0; found = h; break; }
-        }
-        if (st == kFull && s->key_hi == hi && s->key_lo == lo) {
-            found = h;
-            const uint32_t len = s->len;
-            if (len && !idle_or_old(now, s->epoch, a.idle)) { stored = len; last = slot_items(s)[len - 1]; }
-            break;
-        }
-    }
-    if (found == kNone) atomicOr(a.err, 1u);
-    a.slot_of[p] = found; a.slen[p] = stored; a.headpos[p] = p; ta.runpos[p] = p;
-    a.kept[p] = stored == 0 || last != item;
-}
-
-// the run's last request writes its window and ITS time (not the largest one) into the run's slot
-__global__ void __launch_bounds__(kTPB) sess_store_at(TimedArgs ta) {
-    const BatchArgs& a = ta.a;
-    const uint32_t p = blockIdx.x * kTPB + threadIdx.x;
-    if (p >= a.n) return;
-    const uint32_t req = a.order[p];
-    if (!consents(a, req)) return;
-    if (p + 1 < a.n) {
-        const uint32_t nx = a.order[p + 1];
-        if (consents(a, nx) && a.key_hi[nx] == a.key_hi[req] && a.key_lo[nx] == a.key_lo[req]) return;   // not the run's last request
-    }
-    const uint32_t slot = a.slot_of[ta.run_head[p]];
-    if (slot == kNone) return;
-    SlotHead* s = slot_at(a.t, slot);
-    const uint32_t off = a.q_off[req], len = a.q_off[req + 1] - off;
-    uint64_t* it = slot_items(s);
-    for (uint32_t i = 0; i < len; ++i) it[i] = a.items_flat[off + i];
-    s->len = len; s->epoch = ta.t[p]; s->state = kFull;
-}
-
-// sess_return_flag with the head's own time
-__global__ void __launch_bounds__(kTPB) sess_return_flag_at(TimedArgs ta, uint32_t min_len, uint64_t* __restrict__ flag) {
-    const BatchArgs& a = ta.a;
-    const uint32_t p = blockIdx.x * kTPB + threadIdx.x;
-    if (p > a.n) return;
-    uint64_t f = 0;
-    if (p < a.n) {
-        const uint32_t req = a.order[p];
-        if (consents(a, req) && run_head_at(a, p, req)) {
+        if (consents(a, req) && run_head(a, p, req)) {
             const uint32_t slot = a.slot_of[p];
             if (slot != kNone && a.slen[p] == 0) {
                 const SlotHead* s = slot_at(a.t, slot);
-                if (s->state == kFull && s->len > 0 && idle_or_old(ta.t[p], s->epoch, a.idle)) f = s->len >= min_len ? kHvStore : kHvSkip;
+                uint64_t now = a.now;
+                if constexpr (kTimed) now = a.when[p];
+                if (s->state == kFull && s->len > 0 && idle_or_old(now, s->epoch, a.idle)) f = s->len >= min_len ? kHvStore : kHvSkip;
             }
         }
     }
     flag[p] = f;
 }
-// The sessions that end INSIDE the call, behind sess_emit: a break at sorted position p ends the session of position p - 1, whose window is in the call's CSR.
-// flag[p] = kHvStore / kHvSkip by that window's length; flag[n] = 0.  (A break is a segment head that is not a run head.)
-__global__ void __launch_bounds__(kTPB) sess_break_flag(TimedArgs ta, uint32_t min_len, uint64_t* __restrict__ flag) {
-    const BatchArgs& a = ta.a;
+// A timed batch only.  The sessions that end INSIDE the call, behind sess_emit: a break at sorted position p ends the session of position p - 1, whose window is in
+// the call's CSR.  flag[p] = kHvStore / kHvSkip by that window's length; flag[n] = 0.  (A break is a segment head that is not a run head.)
+__global__ void __launch_bounds__(kTPB) sess_break_flag(BatchArgs a, uint32_t min_len, uint64_t* __restrict__ flag) {
     const uint32_t p = blockIdx.x * kTPB + threadIdx.x;
     if (p > a.n) return;
     uint64_t f = 0;
-    if (p > 0 && p < a.n && a.headpos[p] == p && ta.runpos[p] == 0) {
+    if (p > 0 && p < a.n && a.headpos[p] == p && a.runpos[p] == 0) {
         const uint32_t pr = a.order[p - 1];
         f = a.q_off[pr + 1] - a.q_off[pr] >= min_len ? kHvStore : kHvSkip;
     }
@@ -449,6 +341,7 @@ struct ImportArgs {
     uint32_t* slot_of;       // [n] by sorted position of a run head: its slot
     uint32_t* win;           // [n] ... and the entry that is written there (kNone: the stored entry is newer, or not a head)
     uint32_t* err;
+    static constexpr const uint8_t* consent = nullptr;   // (run_head: every entry takes part)
 };
 __global__ void __launch_bounds__(kTPB) sess_import_maxlen(const uint32_t* __restrict__ len, uint32_t n, uint32_t* __restrict__ out) {
     const uint32_t i = blockIdx.x * kTPB + threadIdx.x;
@@ -463,7 +356,7 @@ __global__ void __launch_bounds__(kTPB) sess_import_find(ImportArgs a) {
     if (p >= a.n) return;
     const uint32_t e0 = a.order[p];
     const uint64_t hi = a.key_hi[e0], lo = a.key_lo[e0];
-    if (p) { const uint32_t pr = a.order[p - 1]; if (a.key_hi[pr] == hi && a.key_lo[pr] == lo) { a.slot_of[p] = kNone; a.win[p] = kNone; return; } }
+    if (run_prev(a, p, hi, lo) != kNone) { a.slot_of[p] = kNone; a.win[p] = kNone; return; }   // not a head
     uint32_t w = e0; uint64_t we = a.epoch[e0];
     for (uint32_t q = p + 1; q < a.n; ++q) {   // (the sort is stable: a later position of the run is a later entry)
         const uint32_t r = a.order[q];
@@ -471,22 +364,10 @@ __global__ void __launch_bounds__(kTPB) sess_import_find(ImportArgs a) {
         const uint64_t re = a.epoch[r];
         if (re >= we) { w = r; we = re; }
     }
-    uint32_t h = key_hash(hi, lo) & a.t.mask, found = kNone;
-    for (uint32_t probes = 0; probes <= a.t.mask; ++probes, h = (h + 1) & a.t.mask) {
-        SlotHead* s = slot_at(a.t, h);
-        uint32_t st = __hip_atomic_load(&s->state, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (st == kEmpty) {
-            st = atomicCAS(&s->state, kEmpty, kClaimed);
-            if (st == kEmpty) { found = h; break; }
-        }
-        if (st == kFull && s->key_hi == hi && s->key_lo == lo) {
-            found = h;
-            if (we < s->epoch) w = kNone;   // the stored entry is newer: it stays
-            break;
-        }
-    }
-    if (found == kNone) { atomicOr(a.err, 1u); w = kNone; }
-    a.slot_of[p] = found; a.win[p] = w;
+    const Claim c = find_or_claim(a.t, hi, lo);
+    if (c.slot == kNone) { atomicOr(a.err, 1u); w = kNone; }
+    else if (!c.fresh && we < slot_at(a.t, c.slot)->epoch) w = kNone;   // the stored entry is newer: it stays
+    a.slot_of[p] = c.slot; a.win[p] = w;
 }
 // 16 adjacent lanes write one winner into its slot, a 16-byte element each per round (the layout of sess_export_scatter)
 __global__ void __launch_bounds__(kTPB) sess_import_write(ImportArgs a) {
@@ -830,8 +711,7 @@ int dsess_recommend_device(const srn_index* idx, srn_device_sessions* s, const u
     HIP_TRY(hipSetDevice(s->device));
     // scratch: sort keys and indices (double-buffered), the per-position and per-request words, the kept clicks, the CSR batch, rocPRIM's temporary storage
     size_t tmp = 0, t1 = 0;
-    HIP_TRY(rocprim::radix_sort_pairs(nullptr, t1, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, n, 0, 64, st)); tmp = std::max(tmp, t1);
-    HIP_TRY(rocprim::radix_sort_pairs(nullptr, t1, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, n, 0, 1, st)); tmp = std::max(tmp, t1);
+    if ((rc = key_sort_tmp_bytes(n, st, &tmp))) return rc;
     HIP_TRY(rocprim::exclusive_scan(nullptr, t1, (uint32_t*)nullptr, (uint32_t*)nullptr, 0u, n + 1, rocprim::plus<uint32_t>(), st)); tmp = std::max(tmp, t1);
     HIP_TRY(rocprim::inclusive_scan(nullptr, t1, (uint32_t*)nullptr, (uint32_t*)nullptr, n, rocprim::maximum<uint32_t>(), st)); tmp = std::max(tmp, t1);
     srn_harvest* const hv = s->harvest;
@@ -851,20 +731,12 @@ int dsess_recommend_device(const srn_index* idx, srn_device_sessions* s, const u
     const bool timed = s->timing;
     if (timed) HIP_TRY(hipEventRecord(s->tev[0], st));
     char* b = s->ws;
-    uint64_t* keyA = (uint64_t*)(b + o_keyA); uint64_t* keyB = (uint64_t*)(b + o_keyB); uint32_t* idxA = (uint32_t*)(b + o_idxA); uint32_t* idxB = (uint32_t*)(b + o_idxB);
     const dim3 gn = grid_for(n), gn1 = grid_for(n + 1);
     const uint32_t n32 = (uint32_t)n;
     // stable LSD passes: key_lo, key_hi, then (where some request may not consent) the consent bit -- consenting requests first, each visitor's in request order
-    sess_keys_init<<<gn, kTPB, 0, st>>>(d_lo, n32, keyA, idxA);
-    t1 = tmp; HIP_TRY(rocprim::radix_sort_pairs(b + o_tmp, t1, keyA, keyB, idxA, idxB, n, 0, 64, st));
-    sess_keys_gather<<<gn, kTPB, 0, st>>>(d_hi, idxB, n32, keyA);
-    t1 = tmp; HIP_TRY(rocprim::radix_sort_pairs(b + o_tmp, t1, keyA, keyB, idxB, idxA, n, 0, 64, st));
-    const uint32_t* order = idxA;
-    if (d_consent) {
-        sess_keys_consent<<<gn, kTPB, 0, st>>>(d_consent, idxA, n32, keyA);
-        t1 = tmp; HIP_TRY(rocprim::radix_sort_pairs(b + o_tmp, t1, keyA, keyB, idxA, idxB, n, 0, 1, st));
-        order = idxB;
-    }
+    KeySort ks{{(uint64_t*)(b + o_keyA), (uint64_t*)(b + o_keyB)}, {(uint32_t*)(b + o_idxA), (uint32_t*)(b + o_idxB)}, b + o_tmp, tmp, n, st};
+    if ((rc = ks.begin(d_lo)) || (rc = ks.pass(KeyWord{d_hi})) || (d_consent && (rc = ks.pass(KeyNoConsent{d_consent}, 0, 1)))) return rc;
+    const uint32_t* order = ks.order();
     BatchArgs a{};
     a.t = s->tab(); a.key_hi = d_hi; a.key_lo = d_lo; a.item = d_item; a.consent = d_consent; a.order = order; a.n = n32; a.max_items = (uint32_t)max_items; a.limit = limit;
     if (H) { a.plen = (uint32_t*)(b + o_plen); a.p_off = (uint32_t*)(b + o_poff); a.pflat = (uint64_t*)(b + o_pflat); }
@@ -872,35 +744,34 @@ int dsess_recommend_device(const srn_index* idx, srn_device_sessions* s, const u
     a.slot_of = (uint32_t*)(b + o_slot); a.slen = (uint32_t*)(b + o_slen); a.kept = (uint32_t*)(b + o_kept); a.headpos = (uint32_t*)(b + o_head);
     a.kex = (uint32_t*)(b + o_kex); a.run_start = (uint32_t*)(b + o_run); a.qlen = (uint32_t*)(b + o_qlen); a.q_off = (uint32_t*)(b + o_qoff);
     a.compact = (uint64_t*)(b + o_comp); a.items_flat = (uint64_t*)(b + o_flat); a.err = s->err();
-    TimedArgs ta{};   // a timed batch: the same sequence over segments, with a second max scan for the run's slot and a second append behind sess_emit
-    if (d_times) {
-        ta.a = a; ta.t = (const uint64_t*)(b + o_t); ta.runpos = (uint32_t*)(b + o_rpos); ta.run_head = (uint32_t*)(b + o_rhead);
-        sess_times_gather<<<gn, kTPB, 0, st>>>(d_times, order, n32, (uint64_t*)(b + o_t));
-        sess_find_at<<<gn1, kTPB, 0, st>>>(ta);
+    if (d_times) {   // a timed batch: the same sequence over segments, with a second max scan for the run's slot and a second append behind sess_emit
+        a.when = (const uint64_t*)(b + o_t); a.runpos = (uint32_t*)(b + o_rpos); a.run_head = (uint32_t*)(b + o_rhead);
+        key_gather<<<gn, kTPB, 0, st>>>(KeyWord{d_times}, order, n32, (uint64_t*)(b + o_t));
+        sess_find<true><<<gn1, kTPB, 0, st>>>(a);
     } else
-        sess_find<<<gn1, kTPB, 0, st>>>(a);
+        sess_find<false><<<gn1, kTPB, 0, st>>>(a);
     if (hv) {   // the stored sessions the heads found idle, copied before sess_store overwrites their slots
-        if (d_times) sess_return_flag_at<<<gn1, kTPB, 0, st>>>(ta, hv->min_len, (uint64_t*)(b + o_hv));
-        else sess_return_flag<<<gn1, kTPB, 0, st>>>(a, hv->min_len, (uint64_t*)(b + o_hv));
+        if (d_times) sess_return_flag<true><<<gn1, kTPB, 0, st>>>(a, hv->min_len, (uint64_t*)(b + o_hv));
+        else sess_return_flag<false><<<gn1, kTPB, 0, st>>>(a, hv->min_len, (uint64_t*)(b + o_hv));
         HIP_TRY(hipGetLastError());
         if ((rc = harvest_append(hv, a.t, a.slot_of, n, b + o_hv, true, st))) return rc;
     }
     t1 = tmp; HIP_TRY(rocprim::exclusive_scan(b + o_tmp, t1, a.kept, a.kex, 0u, n + 1, rocprim::plus<uint32_t>(), st));
     t1 = tmp; HIP_TRY(rocprim::inclusive_scan(b + o_tmp, t1, a.headpos, a.run_start, n, rocprim::maximum<uint32_t>(), st));
-    if (d_times) { t1 = tmp; HIP_TRY(rocprim::inclusive_scan(b + o_tmp, t1, ta.runpos, ta.run_head, n, rocprim::maximum<uint32_t>(), st)); }
+    if (d_times) { t1 = tmp; HIP_TRY(rocprim::inclusive_scan(b + o_tmp, t1, a.runpos, a.run_head, n, rocprim::maximum<uint32_t>(), st)); }
     sess_len<<<gn1, kTPB, 0, st>>>(a);   // (run_start is the segment start and slen 0 at a break: sess_len and sess_emit read a timed batch as they read any other)
     t1 = tmp; HIP_TRY(rocprim::exclusive_scan(b + o_tmp, t1, a.qlen, a.q_off, 0u, n + 1, rocprim::plus<uint32_t>(), st));
     if (H) { t1 = tmp; HIP_TRY(rocprim::exclusive_scan(b + o_tmp, t1, a.plen, a.p_off, 0u, n + 1, rocprim::plus<uint32_t>(), st)); }
     sess_emit<<<gn, kTPB, 0, st>>>(a);
     if (d_times) {
         if (hv) {   // the sessions ended inside the call, from the windows just emitted
-            sess_break_flag<<<gn1, kTPB, 0, st>>>(ta, hv->min_len, (uint64_t*)(b + o_hv));
+            sess_break_flag<<<gn1, kTPB, 0, st>>>(a, hv->min_len, (uint64_t*)(b + o_hv));
             HIP_TRY(hipGetLastError());
-            if ((rc = harvest_append_csr(hv, order, d_hi, d_lo, ta.t, a.items_flat, a.q_off, n, b + o_hv, st))) return rc;
+            if ((rc = harvest_append_csr(hv, order, d_hi, d_lo, a.when, a.items_flat, a.q_off, n, b + o_hv, st))) return rc;
         }
-        sess_store_at<<<gn, kTPB, 0, st>>>(ta);
+        sess_store<true><<<gn, kTPB, 0, st>>>(a);
     } else
-        sess_store<<<gn, kTPB, 0, st>>>(a);
+        sess_store<false><<<gn, kTPB, 0, st>>>(a);
     HIP_TRY(hipGetLastError());
     // from here on the store has changed: whatever happens below, the next call is ordered behind this one
     s->bound += n;
@@ -1042,10 +913,10 @@ int import_locked(srn_device_sessions* s, const uint64_t* d_hi, const uint64_t* 
     if (n == 0) return SRN_OK;
     if (n > (1ull << 30)) return fail(SRN_ERANGE, std::string(who) + ": more than 2^30 entries in one call");
     size_t tmp = 0;
-    HIP_TRY(rocprim::radix_sort_pairs(nullptr, tmp, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, n, 0, 64, st));
+    int rc = key_sort_tmp_bytes(n, st, &tmp); if (rc) return rc;
     const size_t w = align256(n * 4), k8 = align256(n * 8);
     const size_t o_word = 0, o_keyA = 256, o_keyB = o_keyA + k8, o_idxA = o_keyB + k8, o_idxB = o_idxA + w, o_slot = o_idxB + w, o_win = o_slot + w, o_tmp = o_win + w;
-    int rc = xs_ensure(s, o_tmp + align256(tmp)); if (rc) return rc;
+    if ((rc = xs_ensure(s, o_tmp + align256(tmp)))) return rc;
     char* b = s->xs;
     const uint32_t n32 = (uint32_t)n; const dim3 gn = grid_for(n);
     HIP_TRY(hipStreamWaitEvent(st, s->last, 0));
@@ -1060,15 +931,11 @@ int import_locked(srn_device_sessions* s, const uint64_t* d_hi, const uint64_t* 
     // every entry counts as a new key; an import reclaims nothing (now = 1: no entry is older than the TTL), so a refused import leaves every slot where it was
     if ((rc = make_room(s, n, 1))) return rc;
     HIP_TRY(hipSetDevice(s->device));
-    uint64_t* keyA = (uint64_t*)(b + o_keyA); uint64_t* keyB = (uint64_t*)(b + o_keyB); uint32_t* idxA = (uint32_t*)(b + o_idxA); uint32_t* idxB = (uint32_t*)(b + o_idxB);
-    size_t t1 = tmp;
-    sess_keys_init<<<gn, kTPB, 0, st>>>(d_lo, n32, keyA, idxA);
-    HIP_TRY(rocprim::radix_sort_pairs(b + o_tmp, t1, keyA, keyB, idxA, idxB, n, 0, 64, st));
-    sess_keys_gather<<<gn, kTPB, 0, st>>>(d_hi, idxB, n32, keyA);
-    t1 = tmp; HIP_TRY(rocprim::radix_sort_pairs(b + o_tmp, t1, keyA, keyB, idxB, idxA, n, 0, 64, st));
+    KeySort ks{{(uint64_t*)(b + o_keyA), (uint64_t*)(b + o_keyB)}, {(uint32_t*)(b + o_idxA), (uint32_t*)(b + o_idxB)}, b + o_tmp, tmp, n, st};
+    if ((rc = ks.begin(d_lo)) || (rc = ks.pass(KeyWord{d_hi}))) return rc;
     ImportArgs a{};
     a.t = s->tab(); a.key_hi = d_hi; a.key_lo = d_lo; a.epoch = d_epoch; a.len = d_len; a.items = d_items; a.items_stride = items_stride;
-    a.order = idxA; a.n = n32; a.slot_of = (uint32_t*)(b + o_slot); a.win = (uint32_t*)(b + o_win); a.err = s->err();
+    a.order = ks.order(); a.n = n32; a.slot_of = (uint32_t*)(b + o_slot); a.win = (uint32_t*)(b + o_win); a.err = s->err();
     sess_import_find<<<gn, kTPB, 0, st>>>(a);
     sess_import_write<<<grid_for(n * 16), kTPB, 0, st>>>(a);
     HIP_TRY(hipGetLastError());

@@ -182,6 +182,40 @@ def _is_torch(x):
     return type(x).__module__.split(".")[0] == "torch"
 
 
+def _device_of(device_or_index):
+    """A GPU's number, or the one an index is on."""
+    return device_or_index if isinstance(device_or_index, int) else device_or_index.info["device"]
+
+
+def _export_entries(cap, stride_of, device, export_device, export_host):
+    """The grow-and-retry loop of DeviceSessionStore.export and SessionHarvest.export -> (hi, lo), epoch, len, items[n, stride].  cap: the caller's count of the
+    entries, which may have grown by the time of the export: the call then reports the number and is made again with that much room.  stride_of(): the width of items,
+    read before every try.  device: a GPU's number for tensors there, written on the current stream (export_device(cap, [hi, lo, ep, ln, it] as pointers, stride,
+    d_n, stream) -> rc), or None for NumPy arrays (export_host(cap, the five as pointers, stride, byref(n)) -> rc)."""
+    while True:
+        stride = stride_of()
+        if device is not None:
+            import torch
+            dev = torch.device("cuda", device)
+            hi, lo, ep = (torch.zeros(cap, dtype=torch.int64, device=dev) for _ in range(3))
+            ln = torch.zeros(cap, dtype=torch.int32, device=dev)
+            it = torch.zeros((cap, stride), dtype=torch.int64, device=dev)
+            d_n = torch.zeros(1, dtype=torch.int64, device=dev)
+            stream = torch.cuda.current_stream(device).cuda_stream
+            capi.check(export_device(cap, [C.c_void_p(t.data_ptr()) for t in (hi, lo, ep, ln, it)], stride, C.c_void_p(d_n.data_ptr()), C.c_void_p(stream)))
+            n = int(d_n.item())
+        else:
+            hi, lo, ep = (np.zeros(cap, np.uint64) for _ in range(3))
+            ln, it, got = np.zeros(cap, np.uint32), np.zeros((cap, stride), np.uint64), C.c_size_t()
+            rc = export_host(cap, [capi.ptr(a) for a in (hi, lo, ep, ln, it)], stride, C.byref(got))
+            n = got.value
+            if rc != 0 and not (rc == capi.SRN_ERANGE and n > cap):
+                capi.check(rc)
+        if n <= cap:                                    # (more: entries arrived between the count and the export)
+            return (hi[:n], lo[:n]), ep[:n], ln[:n], it[:n]
+        cap = n
+
+
 def session_keys(session_ids):
     """session_key for a list of strings in one call -> (hi, lo) as uint64 arrays."""
     raw = [s.encode() if isinstance(s, str) else bytes(s) for s in session_ids]
@@ -277,7 +311,7 @@ class DeviceSessionStore:
         """max_capacity: opt-in growth -- a batch the capacity rule would refuse doubles the capacity (up to max_capacity) instead; None = a fixed capacity.
         history: the store keeps a window of the last `history` clicks (<= items_cap) and recommend_batch predicts on its last max_items_in_session items; 0 = the
         store keeps max_items_in_session items, as the reference does."""
-        device = device_or_index if isinstance(device_or_index, int) else device_or_index.info["device"]
+        device = _device_of(device_or_index)
         h = C.c_void_p()
         capi.check(capi.lib().srn_device_sessions_create(int(device), int(capacity), int(items_cap), int(ttl_secs), int(idle_secs), C.byref(h)))
         self._h, self.device, self.items_cap = h, int(device), int(items_cap)
@@ -299,7 +333,7 @@ class DeviceSessionStore:
     @classmethod
     def load(cls, device_or_index, path, capacity=None, items_cap=None, ttl_secs=None, idle_secs=None):
         """A store on that GPU with the sessions of a snapshot file (save, write_session_snapshot); None = the value the file records."""
-        device = device_or_index if isinstance(device_or_index, int) else device_or_index.info["device"]
+        device = _device_of(device_or_index)
         h = C.c_void_p()
         capi.check(capi.lib().srn_device_sessions_load(os.fsencode(path), int(device), int(capacity or 0), int(items_cap or 0), int(ttl_secs or 0), int(idle_secs or 0),
                                                        C.byref(h)))
@@ -322,30 +356,9 @@ class DeviceSessionStore:
         """The live sessions at `now`, in slot order -> (hi, lo), epoch, len, items[n, items_cap] (zero beyond len).  NumPy arrays, or with device=True tensors
         on the store's GPU, written on the current stream."""
         L = capi.lib()
-        cap = self.count(now).live
-        while True:
-            stride = int(self.stats["items_cap"])
-            if device:
-                import torch
-                dev = torch.device("cuda", self.device)
-                hi, lo, ep = (torch.zeros(cap, dtype=torch.int64, device=dev) for _ in range(3))
-                ln = torch.zeros(cap, dtype=torch.int32, device=dev)
-                it = torch.zeros((cap, stride), dtype=torch.int64, device=dev)
-                d_n = torch.zeros(1, dtype=torch.int64, device=dev)
-                stream = torch.cuda.current_stream(self.device).cuda_stream
-                capi.check(L.srn_device_sessions_export_device(self._h, int(now), cap, *(C.c_void_p(t.data_ptr()) for t in (hi, lo, ep, ln, it)), stride,
-                                                               C.c_void_p(d_n.data_ptr()), C.c_void_p(stream)))
-                n = int(d_n.item())
-            else:
-                hi, lo, ep = (np.zeros(cap, np.uint64) for _ in range(3))
-                ln, it, got = np.zeros(cap, np.uint32), np.zeros((cap, stride), np.uint64), C.c_size_t()
-                rc = L.srn_device_sessions_export(self._h, int(now), cap, capi.ptr(hi), capi.ptr(lo), capi.ptr(ep), capi.ptr(ln), capi.ptr(it), stride, C.byref(got))
-                n = got.value
-                if rc != 0 and not (rc == capi.SRN_ERANGE and n > cap):
-                    capi.check(rc)
-            if n <= cap:                                    # (more: the store grew between the count and the export)
-                return (hi[:n], lo[:n]), ep[:n], ln[:n], it[:n]
-            cap = n
+        return _export_entries(self.count(now).live, lambda: int(self.stats["items_cap"]), self.device if device else None,
+                               lambda cap, arrays, *rest: L.srn_device_sessions_export_device(self._h, int(now), cap, *arrays, *rest),
+                               lambda cap, arrays, *rest: L.srn_device_sessions_export(self._h, int(now), cap, *arrays, *rest))
 
     def import_entries(self, keys, epoch, len, items):
         """Inserts the entries (keys[i], epoch[i], items[i, :len[i]]) under the merge rule: the larger epoch wins, a tie replaces.  NumPy arrays, or tensors on the
@@ -538,7 +551,7 @@ class SessionHarvest:
     store.set_harvest(hv) attaches it; export / events read it in canonical order -- (epoch, key) ascending -- without consuming it."""
 
     def __init__(self, index_or_device, capacity, items_cap=16, min_len=1):
-        device = index_or_device if isinstance(index_or_device, int) else index_or_device.info["device"]
+        device = _device_of(index_or_device)
         h = C.c_void_p()
         capi.check(capi.lib().srn_harvest_create(int(device), int(capacity), int(items_cap), int(min_len), C.byref(h)))
         self._h, self.device, self.capacity, self.items_cap = h, int(device), int(capacity), int(items_cap)
@@ -554,30 +567,10 @@ class SessionHarvest:
     def export(self, device=False):
         """The stored sessions in canonical order -> (hi, lo), epoch, len, items[n, items_cap] (zero beyond len), like DeviceSessionStore.export.  NumPy arrays, or with
         device=True tensors on the harvest's GPU, written on the current stream."""
-        L, stride = capi.lib(), self.items_cap
-        cap = int(self.stats()["stored"])
-        while True:
-            if device:
-                import torch
-                dev = torch.device("cuda", self.device)
-                hi, lo, ep = (torch.zeros(cap, dtype=torch.int64, device=dev) for _ in range(3))
-                ln = torch.zeros(cap, dtype=torch.int32, device=dev)
-                it = torch.zeros((cap, stride), dtype=torch.int64, device=dev)
-                d_n = torch.zeros(1, dtype=torch.int64, device=dev)
-                stream = torch.cuda.current_stream(self.device).cuda_stream
-                capi.check(L.srn_harvest_export_device(self._h, cap, *(C.c_void_p(t.data_ptr()) for t in (hi, lo, ep, ln, it)), stride, C.c_void_p(d_n.data_ptr()),
-                                                       C.c_void_p(stream)))
-                n = int(d_n.item())
-            else:
-                hi, lo, ep = (np.zeros(cap, np.uint64) for _ in range(3))
-                ln, it, got = np.zeros(cap, np.uint32), np.zeros((cap, stride), np.uint64), C.c_size_t()
-                rc = L.srn_harvest_export(self._h, cap, capi.ptr(hi), capi.ptr(lo), capi.ptr(ep), capi.ptr(ln), capi.ptr(it), stride, C.byref(got))
-                n = got.value
-                if rc != 0 and not (rc == capi.SRN_ERANGE and n > cap):
-                    capi.check(rc)
-            if n <= cap:                                    # (more: sessions arrived between the count and the export)
-                return (hi[:n], lo[:n]), ep[:n], ln[:n], it[:n]
-            cap = n
+        L = capi.lib()
+        return _export_entries(int(self.stats()["stored"]), lambda: self.items_cap, self.device if device else None,
+                               lambda cap, arrays, *rest: L.srn_harvest_export_device(self._h, cap, *arrays, *rest),
+                               lambda cap, arrays, *rest: L.srn_harvest_export(self._h, cap, *arrays, *rest))
 
     def events(self, id_base=0):
         """srn_harvest_events_device: the stored sessions as training rows -> (session_ids, item_ids, times), int64 tensors on the harvest's GPU, written on the current
@@ -729,7 +722,7 @@ class ClickFeedback:
     beside the session store; recommend_batch(..., feedback=fb) feeds it."""
 
     def __init__(self, index_or_device, capacity, row_cap=21, ttl_secs=30 * 60, idle_secs=20 * 60):
-        device = index_or_device if isinstance(index_or_device, int) else index_or_device.info["device"]
+        device = _device_of(index_or_device)
         h = C.c_void_p()
         capi.check(capi.lib().srn_feedback_create(int(device), int(capacity), int(row_cap), int(ttl_secs), int(idle_secs), C.byref(h)))
         self._h, self.device, self.row_cap = h, int(device), int(row_cap)
@@ -764,38 +757,29 @@ class ClickFeedback:
                     counts.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or (scores is not None and scores.dtype != torch.float64) or \
                     (consent is not None and consent.dtype not in (torch.uint8, torch.bool)):
                 raise TypeError("keys, item_ids and ids must be 64-bit integer, counts 32-bit integer, scores float64 and consent uint8 or bool tensors")
+            if times is not None and times.dtype not in (torch.int64, getattr(torch, "uint64", torch.int64)):
+                raise TypeError("times must be a 64-bit integer tensor")
             t = [a.contiguous() for a in arrs]
+            hi, lo, it, rows, cnt = t[:5]
             con = t[5] if consent is not None else None
             sc = t[-1] if scores is not None else None
+            tm = None if times is None else times.contiguous()
             ranks = torch.zeros(n, dtype=torch.int32, device=torch.device("cuda", self.device))
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-            p = lambda a: None if a is None else C.c_void_p(a.data_ptr())
-            if times is not None:
-                if times.dtype not in (torch.int64, getattr(torch, "uint64", torch.int64)):
-                    raise TypeError("times must be a 64-bit integer tensor")
-                tm = times.contiguous()
-                capi.check(capi.lib().srn_feedback_observe_device_at(self._h, p(t[0]), p(t[1]), p(t[2]), p(con), p(tm), n, int(now), p(t[3]), p(sc), p(t[4]), how_many,
-                                                                     p(ranks), C.c_void_p(stream)))
-                self.last_ranks = ranks
-                return ranks
-            capi.check(capi.lib().srn_feedback_observe_device(self._h, p(t[0]), p(t[1]), p(t[2]), p(con), n, int(now), p(t[3]), p(sc), p(t[4]), how_many, p(ranks),
-                                                              C.c_void_p(stream)))
-            self.last_ranks = ranks
-            return ranks
-        as_np = lambda a: a.numpy() if _is_torch(a) else a
-        hi, lo, it, rows = (capi.as_u64(as_np(a)) for a in (hi, lo, item_ids, ids))
-        cnt = capi.as_u32(as_np(counts))
-        con = None if consent is None else np.ascontiguousarray(as_np(consent)).astype(np.uint8)
-        sc = None if scores is None else np.ascontiguousarray(as_np(scores), dtype=np.float64)
-        ranks = np.zeros(n, np.uint32)
-        if times is not None:
-            tm = capi.as_u64(as_np(times))
-            capi.check(capi.lib().srn_feedback_observe_at(self._h, capi.ptr(hi), capi.ptr(lo), capi.ptr(it), capi.ptr(con), capi.ptr(tm), n, int(now), capi.ptr(rows),
-                                                          capi.ptr(sc), capi.ptr(cnt), how_many, capi.ptr(ranks)))
-            self.last_ranks = ranks
-            return ranks
-        capi.check(capi.lib().srn_feedback_observe(self._h, capi.ptr(hi), capi.ptr(lo), capi.ptr(it), capi.ptr(con), n, int(now), capi.ptr(rows), capi.ptr(sc),
-                                                   capi.ptr(cnt), how_many, capi.ptr(ranks)))
+            entry, p, tail = "srn_feedback_observe_device", lambda a: None if a is None else C.c_void_p(a.data_ptr()), [C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)]
+        else:
+            as_np = lambda a: a.numpy() if _is_torch(a) else a
+            hi, lo, it, rows = (capi.as_u64(as_np(a)) for a in (hi, lo, item_ids, ids))
+            cnt = capi.as_u32(as_np(counts))
+            con = None if consent is None else np.ascontiguousarray(as_np(consent)).astype(np.uint8)
+            sc = None if scores is None else np.ascontiguousarray(as_np(scores), dtype=np.float64)
+            tm = None if times is None else capi.as_u64(as_np(times))
+            ranks = np.zeros(n, np.uint32)
+            entry, p, tail = "srn_feedback_observe", capi.ptr, []
+        args = [self._h, p(hi), p(lo), p(it), p(con), n, int(now), p(rows), p(sc), p(cnt), how_many, p(ranks)] + tail
+        if times is not None:   # the _at form takes the times behind consent
+            entry += "_at"
+            args.insert(5, p(tm))
+        capi.check(getattr(capi.lib(), entry)(*args))
         self.last_ranks = ranks
         return ranks
 
@@ -907,43 +891,31 @@ def recommend_batch(index, store, keys, item_ids, consent=None, *, k, m, how_man
         ids = torch.zeros((n, how_many), dtype=torch.int64, device=dev)
         sc = torch.zeros((n, how_many), dtype=torch.float64, device=dev)
         cnt = torch.zeros(n, dtype=torch.int32, device=dev)
-        stream = torch.cuda.current_stream(device).cuda_stream
+        tm = None
         if times is not None:
             if not (_is_torch(times) and times.device.type == "cuda" and times.device.index == device):
                 raise ValueError("times must be a tensor on the index's GPU (device %d), like keys" % device)
             if times.dtype not in (torch.int64, getattr(torch, "uint64", torch.int64)):
                 raise TypeError("times must be a 64-bit integer tensor")
             tm = times.contiguous()
-            capi.check(capi.lib().srn_recommend_batch_device_at(
-                index._h, sh, C.c_void_p(hi.data_ptr()), C.c_void_p(lo.data_ptr()), C.c_void_p(it.data_ptr()), None if con is None else C.c_void_p(con.data_ptr()),
-                C.c_void_p(tm.data_ptr()), n, int(now), int(max_items_in_session), int(k), int(m), int(how_many), flags,
-                C.c_void_p(ids.data_ptr()), C.c_void_p(sc.data_ptr()), C.c_void_p(cnt.data_ptr()), C.c_void_p(stream)))
-            if feedback is not None and n:
-                _observe_served(feedback, (hi, lo), it, con, ids, cnt, sc, now, tm)
-            return (ids, cnt, sc) if scores else (ids, cnt)
-        capi.check(capi.lib().srn_recommend_batch_device(
-            index._h, sh, C.c_void_p(hi.data_ptr()), C.c_void_p(lo.data_ptr()), C.c_void_p(it.data_ptr()), None if con is None else C.c_void_p(con.data_ptr()),
-            n, int(now), int(max_items_in_session), int(k), int(m), int(how_many), flags,
-            C.c_void_p(ids.data_ptr()), C.c_void_p(sc.data_ptr()), C.c_void_p(cnt.data_ptr()), C.c_void_p(stream)))
-        if feedback is not None and n:
-            _observe_served(feedback, (hi, lo), it, con, ids, cnt, sc, now)
-        return (ids, cnt, sc) if scores else (ids, cnt)
-    hi, lo, it = (capi.as_u64(a.numpy() if _is_torch(a) else a) for a in arrs[:3])
-    con = None if consent is None else np.ascontiguousarray(consent.numpy() if _is_torch(consent) else consent).astype(np.uint8)
-    ids, sc, cnt = np.zeros((n, how_many), np.uint64), np.zeros((n, how_many), np.float64), np.zeros(n, np.uint32)
-    if times is not None:
-        if _is_torch(times) and times.device.type == "cuda":
-            raise ValueError("times must be where keys are: an array or CPU tensor here")
-        tm = capi.as_u64(times.numpy() if _is_torch(times) else times)
-        capi.check(capi.lib().srn_recommend_batch_at(index._h, sh, capi.ptr(hi), capi.ptr(lo), capi.ptr(it), capi.ptr(con), capi.ptr(tm), n, int(now),
-                                                     int(max_items_in_session), int(k), int(m), int(how_many), flags, capi.ptr(ids), capi.ptr(sc), capi.ptr(cnt)))
-        if feedback is not None and n:
-            _observe_served(feedback, (hi, lo), it, con, ids, cnt, sc, now, tm)
-        return (ids, cnt, sc) if scores else (ids, cnt)
-    capi.check(capi.lib().srn_recommend_batch(index._h, sh, capi.ptr(hi), capi.ptr(lo), capi.ptr(it), capi.ptr(con), n, int(now), int(max_items_in_session),
-                                              int(k), int(m), int(how_many), flags, capi.ptr(ids), capi.ptr(sc), capi.ptr(cnt)))
+        entry, p, tail = "srn_recommend_batch_device", lambda a: None if a is None else C.c_void_p(a.data_ptr()), [C.c_void_p(torch.cuda.current_stream(device).cuda_stream)]
+    else:
+        hi, lo, it = (capi.as_u64(a.numpy() if _is_torch(a) else a) for a in arrs[:3])
+        con = None if consent is None else np.ascontiguousarray(consent.numpy() if _is_torch(consent) else consent).astype(np.uint8)
+        ids, sc, cnt = np.zeros((n, how_many), np.uint64), np.zeros((n, how_many), np.float64), np.zeros(n, np.uint32)
+        tm = None
+        if times is not None:
+            if _is_torch(times) and times.device.type == "cuda":
+                raise ValueError("times must be where keys are: an array or CPU tensor here")
+            tm = capi.as_u64(times.numpy() if _is_torch(times) else times)
+        entry, p, tail = "srn_recommend_batch", capi.ptr, []
+    args = [index._h, sh, p(hi), p(lo), p(it), p(con), n, int(now), int(max_items_in_session), int(k), int(m), int(how_many), flags, p(ids), p(sc), p(cnt)] + tail
+    if times is not None:   # the _at form takes the times behind consent
+        entry += "_at"
+        args.insert(6, p(tm))
+    capi.check(getattr(capi.lib(), entry)(*args))
     if feedback is not None and n:
-        _observe_served(feedback, (hi, lo), it, con, ids, cnt, sc, now)
+        _observe_served(feedback, (hi, lo), it, con, ids, cnt, sc, now, tm)
     return (ids, cnt, sc) if scores else (ids, cnt)
 
 

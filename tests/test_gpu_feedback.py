@@ -173,6 +173,37 @@ def test_row_widths(how_many):
     fb.close()
 
 
+@pytest.mark.parametrize("device", [False, True])
+def test_timed_call_on_eight_lane_groups(device):
+    """observe(..., times=) at row_cap = how_many = 8, where a request is an 8-lane group (test_gpu_replay.py drives the timed kernels at row_cap = 21 only): one call of
+    257 requests from 3 visitors, every fifth without consent, with gaps above idle_secs before requests 255 and 256 -- both in the run of the visitor with the largest
+    key, the second one past the first 256 positions.  Ranks, counters, histograms and the three entries are the model's, exactly."""
+    n, how_many = 257, 8
+    vis = [(7 << 64) | 11, (7 << 64) | 12, (9 << 64) | 3]
+    keys = [vis[j % 3] for j in range(n)]
+    keys[255] = keys[256] = vis[2]
+    consent = (np.arange(n) % 5 != 0).astype(np.uint8)
+    consent[255:] = 1
+    s = make_stream(4108, keys, how_many, consent)
+    times = NOW + np.arange(n, dtype=np.uint64)
+    times[255:] += np.uint64(IDLE + 1)
+    times[256:] += np.uint64(IDLE + 1)
+    state = {}
+    want, total = feedback_model(state, (s["hi"], s["lo"]), s["items"], s["consent"], s["ids"], s["counts"], s["sc"], NOW, IDLE, row_cap=how_many, times=times)
+    assert total["idle_expired"] >= 2 and total["hits_model"] + total["hits_filled"] >= 1 and total["no_consent"] > 0   # no vacuous pass
+    fb = ClickFeedback(0, capacity=2 * n, row_cap=how_many, ttl_secs=TTL, idle_secs=IDLE)
+    args = [s["hi"], s["lo"], s["items"], s["consent"], s["ids"], s["counts"], s["sc"], times]
+    if device:
+        import torch
+        args = [torch.from_numpy(np.ascontiguousarray(x).view(np.int64 if x.dtype == np.uint64 else np.int32 if x.dtype == np.uint32 else x.dtype)).to(torch.device("cuda", fb.device))
+                for x in args]
+    got = fb.observe((args[0], args[1]), args[2], args[3], args[4], args[5], args[6], now=NOW, times=args[7])
+    got = got.cpu().numpy().view(np.uint32) if device else got
+    assert np.array_equal(got, want), (np.flatnonzero(got != want)[:8], got[got != want][:8], want[got != want][:8])
+    check_log(fb, state, total, vis)
+    fb.close()
+
+
 def test_rows_narrower_than_the_log():
     keys, _ = key_pattern("zipf", 600, 5)
     s = make_stream(5, keys, 5)

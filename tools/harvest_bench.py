@@ -26,10 +26,11 @@ sys.path.insert(0, ROOT)
 class ParentLibrary:
     """The few entry points the serving arm needs, bound on another build of the library: an index from the same sessions, a store, the batch call."""
     NAMES = ("srn_index_build_gpu", "srn_index_free", "srn_device_sessions_create", "srn_device_sessions_free", "srn_recommend_batch_device", "srn_last_error")
+    NEWER = ("srn_recommend_batch_device_at", "srn_feedback_create", "srn_feedback_free", "srn_feedback_observe_device", "srn_feedback_observe_device_at")   # bound where the build has them
 
     def __init__(self, path, capi):
         self.L = C.CDLL(path)
-        for name in self.NAMES:
+        for name in self.NAMES + tuple(x for x in self.NEWER if hasattr(self.L, x)):
             fn = getattr(self.L, name)
             fn.restype, fn.argtypes = capi.SYMBOLS[name]
         self.capi = capi
@@ -51,10 +52,25 @@ class ParentLibrary:
         self.check(self.L.srn_device_sessions_create(0, capacity, items_cap, ttl, idle, C.byref(h)))
         return h
 
-    def recommend(self, index, store, hi, lo, it, now, max_items, k, m, how_many, out, stream):
+    def recommend(self, index, store, hi, lo, it, now, max_items, k, m, how_many, out, stream, times=None):
         p = lambda t: C.c_void_p(t.data_ptr())   # noqa: E731
-        self.check(self.L.srn_recommend_batch_device(index, store, p(hi), p(lo), p(it), None, len(it), now, max_items, k, m, how_many, 0, p(out[0]), p(out[1]), p(out[2]),
-                                                     C.c_void_p(stream)))
+        args = [index, store, p(hi), p(lo), p(it), None, len(it), now, max_items, k, m, how_many, 0, p(out[0]), p(out[1]), p(out[2]), C.c_void_p(stream)]
+        if times is not None:
+            args.insert(6, p(times))
+        self.check((self.L.srn_recommend_batch_device if times is None else self.L.srn_recommend_batch_device_at)(*args))
+
+    def feedback(self, capacity, row_cap, ttl, idle):
+        h = C.c_void_p()
+        self.check(self.L.srn_feedback_create(0, capacity, row_cap, ttl, idle, C.byref(h)))
+        return h
+
+    def observe(self, fb, hi, lo, it, now, out, how_many, ranks, stream, times=None):
+        """the rows `out` = (ids, scores, counts) just served to the requests, as recommend_batch(..., feedback=) hands them on"""
+        p = lambda t: C.c_void_p(t.data_ptr())   # noqa: E731
+        args = [fb, p(hi), p(lo), p(it), None, len(it), now, p(out[0]), p(out[1]), p(out[2]), how_many, p(ranks), C.c_void_p(stream)]
+        if times is not None:
+            args.insert(5, p(times))
+        self.check((self.L.srn_feedback_observe_device if times is None else self.L.srn_feedback_observe_device_at)(*args))
 
 
 def main():

@@ -3,10 +3,13 @@ recommend_batch on device tensors, 2^20 requests per call, about four clicks per
   (a) the untimed call
   (b) the timed call with all times equal (the same result as (a): what the timed kernels and the gather cost where nothing breaks)
   (c) the timed call over `--spread` seconds, sorted by time as a recorded log is: a visitor's clicks lie further apart than idle_secs, so runs break inside the call
-  (d) (a) through the parent commit's library (--parent-lib, loaded beside this one through ctypes, with an index and a store of its own): (a) against (d) shows
-      whether the untimed path moved beyond the spread of the repeated runs -- the same kernels are enqueued
+  (d) (a) (b) (c) through the parent commit's library (--parent-lib, loaded beside this one through ctypes, with an index and stores of its own), each right before
+      its namesake: an arm against its parent arm shows whether that path moved beyond the spread of the repeated runs (`<arm>_within_spread`: the medians differ by
+      no more than the larger of the two arms' min-max spreads) -- the same kernels are enqueued.  A parent arm clears its output rows inside its timed region, as
+      recommend_batch hands out cleared ones inside its own
   (e) the log of (c) served as it had to be before: one untimed call per distinct second (`--stepped-reps` runs, not alternated: each takes seconds)
-and, with --feedback, (a) (b) (c) again with a click feedback log attached (feedback=).  There is no gate: the numbers are recorded.  Writes one JSON file.
+and, with --feedback, (a) (b) (c) and their parent arms again with a click feedback log attached (feedback=; the parent's through srn_feedback_observe_device*).
+There is no gate: the numbers are recorded.  Writes one JSON file.
 
     python tools/replay_bench.py [--config cfg3] [--requests 1048576] [--reps 5] [--spread 3600] [--parent-lib PATH | --skip-parent] [--out profiles/replay_cfg3.json]
 """
@@ -89,39 +92,53 @@ def main():
         arms = ["untimed", "timed_equal", "timed_spread"]
         stores = {x: DeviceSessionStore(index, capacity=12 * n, items_cap=8, ttl_secs=ttl, idle_secs=idle) for x in arms}
         fbs = {x: ClickFeedback(index, capacity=12 * n, row_cap=how_many, ttl_secs=ttl, idle_secs=idle) if with_fb else None for x in arms}
-        use_parent = parent is not None and not with_fb
-        p_store = parent.store(12 * n, 8, ttl, idle) if use_parent else None
+        p_stores = {x: parent.store(12 * n, 8, ttl, idle) for x in arms} if parent else {}
+        p_fbs = {x: parent.feedback(12 * n, how_many, ttl, idle) for x in arms} if parent and with_fb else {}
         p_out = (torch.zeros((n, how_many), dtype=torch.int64, device=dev), torch.zeros((n, how_many), dtype=torch.float64, device=dev),
                  torch.zeros(n, dtype=torch.int32, device=dev))
-        ms = {x: [] for x in arms + (["parent"] if use_parent else [])}
+        p_ranks = torch.zeros(n, dtype=torch.int32, device=dev)
+        ms = {x: [] for x in arms + (["parent_" + x for x in arms] if parent else [])}
         now, warm = 1_700_000_000, 3
+
+        def parent_call(x, it, now, times, stream):   # what recommend_batch(..., feedback=) enqueues, through the parent's library
+            for o in p_out + ((p_ranks,) if with_fb else ()):
+                o.zero_()                                                                # (recommend_batch and observe hand out cleared rows: the fills belong to both arms' time)
+            parent.recommend(p_index, p_stores[x], hi, lo, it, now, max_items, k, m, how_many, p_out, stream, times)
+            if with_fb:
+                parent.observe(p_fbs[x], hi, lo, it, now, p_out, how_many, p_ranks, stream, times)
+
         for rep in range(warm + a.reps):
             now += a.spread + step
             it = t_its[rep % len(t_its)]
             stream = torch.cuda.current_stream(0).cuda_stream
-            t_equal, t_spread = torch.full((n,), now, dtype=torch.int64, device=dev), t_off + now
-            for x in p_out:
-                x.zero_()                                                                # (recommend_batch hands out cleared rows: entries beyond a row's count are compared too)
-            tp = timed(lambda: parent.recommend(p_index, p_store, hi, lo, it, now, max_items, k, m, how_many, p_out, stream))[1] if use_parent else None
-            ra, ta = timed(lambda: recommend_batch(index, stores["untimed"], (hi, lo), it, now=now, feedback=fbs["untimed"], **kw))
-            rb, tb = timed(lambda: recommend_batch(index, stores["timed_equal"], (hi, lo), it, now=now, times=t_equal, feedback=fbs["timed_equal"], **kw))
-            rc, tc = timed(lambda: recommend_batch(index, stores["timed_spread"], (hi, lo), it, now=now, times=t_spread, feedback=fbs["timed_spread"], **kw))
-            if not all(torch.equal(x, y) for x, y in zip(ra, rb)):
-                raise SystemExit("the rows differ between the untimed call and the timed call with all times equal")
-            if use_parent and not (torch.equal(ra[0], p_out[0]) and torch.equal(ra[1], p_out[2])):
-                raise SystemExit("the rows differ between the parent library and this one")
-            if rep >= warm:
-                for x, t in (("untimed", ta), ("timed_equal", tb), ("timed_spread", tc)) + ((("parent", tp),) if use_parent else ()):
+            times = {"untimed": None, "timed_equal": torch.full((n,), now, dtype=torch.int64, device=dev), "timed_spread": t_off + now}
+            rows = {}
+            for x in arms:                                                               # parent, this library, arm by arm
+                if parent:
+                    tp = timed(lambda: parent_call(x, it, now, times[x], stream))[1]
+                rows[x], t = timed(lambda: recommend_batch(index, stores[x], (hi, lo), it, now=now, times=times[x], feedback=fbs[x], **kw))
+                if parent and not (torch.equal(rows[x][0], p_out[0]) and torch.equal(rows[x][1], p_out[2]) and (not with_fb or torch.equal(fbs[x].last_ranks, p_ranks))):
+                    raise SystemExit("%s: the rows%s differ between the parent library and this one" % (x, " or ranks" if with_fb else ""))
+                if rep >= warm:
                     ms[x].append(round(t, 4))
+                    if parent:
+                        ms["parent_" + x].append(round(tp, 4))
+            if not all(torch.equal(x, y) for x, y in zip(rows["untimed"], rows["timed_equal"])):
+                raise SystemExit("the rows differ between the untimed call and the timed call with all times equal")
         r = {"ms": ms}
         for x in ms:
             r[x + "_ms"] = round(med(ms[x]), 4)
             r[x + "_spread_ms"] = round(max(ms[x]) - min(ms[x]), 4)
         r["timed_equal_minus_untimed_ms"] = round(med(ms["timed_equal"]) - med(ms["untimed"]), 4)
         r["timed_spread_minus_untimed_ms"] = round(med(ms["timed_spread"]) - med(ms["untimed"]), 4)
-        if use_parent:
-            r["untimed_minus_parent_ms"] = round(med(ms["untimed"]) - med(ms["parent"]), 4)
-            parent.L.srn_device_sessions_free(p_store)
+        if parent:   # an arm has not moved when the medians differ by no more than the larger of the two arms' own min-max spreads
+            for x in arms:
+                r[x + "_minus_parent_ms"] = round(med(ms[x]) - med(ms["parent_" + x]), 4)
+                r[x + "_within_spread"] = bool(abs(r[x + "_minus_parent_ms"]) <= max(r[x + "_spread_ms"], r["parent_" + x + "_spread_ms"]))
+            for h in p_stores.values():
+                parent.L.srn_device_sessions_free(h)
+            for h in p_fbs.values():
+                parent.L.srn_feedback_free(h)
         if with_fb:
             r["feedback_idle_expired"] = {x: fbs[x].stats()["idle_expired"] for x in arms}
         res["with_feedback" if with_fb else "serving"] = r
