@@ -721,7 +721,7 @@ int srn_feedback_stats(srn_feedback_t* f, srn_feedback_stats_t* out);
 /* hits by rank: hits_model[r] / hits_filled[r] for r = 1 .. row_cap ([0] is unused and 0; either array may be NULL).  cap = entries per array, at least row_cap + 1
  * (below: SRN_ERANGE); entries beyond row_cap are written as 0.  Blocks. */
 int srn_feedback_histogram(srn_feedback_t* f, uint64_t* hits_model, uint64_t* hits_filled, size_t cap);
-/* every counter and both histograms back to 0, behind the log's previous call; the table is untouched */
+/* every counter, both histograms and (where enabled) the bootstrap's replicate words back to 0, behind the log's previous call; the table is untouched */
 int srn_feedback_reset_counters(srn_feedback_t* f);
 /* drops the entries older than ttl_secs at now_secs (a rebuild); *n_live (may be NULL) = entries kept.  No device memory for the second table: SRN_ENOMEM, the log as it
  * was.  Blocks. */
@@ -730,6 +730,28 @@ int srn_feedback_sweep(srn_feedback_t* f, uint64_t now_secs, uint64_t* n_live);
  * *out_count = SRN_FEEDBACK_NONE for a key the log does not hold or whose entry fails the idle rule at now_secs (now_secs = 1: whatever is stored; 0: the clock). */
 int srn_feedback_get(srn_feedback_t* f, uint64_t key_hi, uint64_t key_lo, uint64_t now_secs, uint64_t* out_ids, size_t cap, uint32_t* out_count, uint32_t* out_n_model,
                      uint64_t* out_epoch);
+/* Visitor-clustered bootstrap of the log's counters.  While it is enabled, replicate b = 0 .. replicates-1 weighs every OBSERVED request of
+ * visitor (key_hi, key_lo) with
+ *   w(seed, b, key) = boot_weight(boot_replicate_key(seed, b), fold(key)),   fold(key) = mix64(key_hi ^ 0x9E3779B97F4A7C15) ^ key_lo
+ * -- the Poisson(1)-cut-at-12 rule of srn_bootstrap_weights with the folded key in the session index's place, from nothing but (seed, b, key): not from `replicates`,
+ * the call, the cut of the requests into calls, the rows or the configuration -- and the log keeps, per replicate, 1 + 2 * row_cap exact unsigned 64-bit sums:
+ *   observed_w[b] = sum of w over the observed requests;  hits_model_w[b][r] / hits_filled_w[b][r] = sum of w over those whose rank is r on a model / a filled entry
+ * Requests that are not observed (rank SRN_FEEDBACK_NONE) add nothing.  Integer sums: the same for any order, run, entry point and cut into calls, and for a timed call
+ * what one call per request gives.  Every srn_feedback_observe* call on the log runs one more kernel behind its own on the same stream; with the bootstrap off nothing
+ * about a call changes.  srn_feedback_reset_counters zeroes the words, a sweep leaves them, a call refused with SRN_ENOMEM leaves them, srn_feedback_free releases them.
+ *   enable   allocates and zeroes the words behind the log's previous call.  replicates 0: SRN_EINVAL; above SRN_MAX_BOOTSTRAP: SRN_ERANGE; a log whose row_cap is above
+ *            SRN_FEEDBACK_BOOTSTRAP_MAX_ROW_CAP: SRN_ERANGE; already enabled: SRN_ESTATE
+ *   disable  frees them (waits for the log's kernels); SRN_OK when not enabled
+ *   info     *replicates / *seed (either may be NULL); 0 / 0 when off
+ *   read     blocks.  observed[replicates] and hits_*[replicates][rank_cap], rank_cap >= row_cap + 1, entry [b][0] unused and 0, entries beyond row_cap 0; any array may
+ *            be NULL.  replicates_cap below `replicates` or rank_cap below row_cap + 1: SRN_ERANGE; not enabled: SRN_ESTATE
+ *   weights  the rule on the host, no GPU needed: out[i] = w(seed, replicate, (key_hi[i], key_lo[i])).  n = 0: SRN_OK; a NULL array with n > 0: SRN_EINVAL */
+#define SRN_FEEDBACK_BOOTSTRAP_MAX_ROW_CAP 64
+int srn_feedback_bootstrap_enable(srn_feedback_t* f, uint32_t replicates, uint64_t seed);
+int srn_feedback_bootstrap_disable(srn_feedback_t* f);
+int srn_feedback_bootstrap_info(srn_feedback_t* f, uint32_t* replicates, uint64_t* seed);
+int srn_feedback_bootstrap_read(srn_feedback_t* f, uint64_t* observed, uint64_t* hits_model, uint64_t* hits_filled, size_t replicates_cap, size_t rank_cap);
+int srn_feedback_bootstrap_weights(uint64_t seed, uint32_t replicate, const uint64_t* key_hi, const uint64_t* key_lo, size_t n, uint8_t* out);
 
 /* ---- session harvest: finished sessions logged on the device, and training events from them (srn_harvest.hip) ----
  * A harvest is a device-resident log, attached to one device session store, that receives every session at the moment the store forgets it: each one exactly once,

@@ -93,6 +93,7 @@ class DeviceSessionsFileInfo(C.Structure):
 
 
 FEEDBACK_NONE, FEEDBACK_FILLED = 0xFFFFFFFF, 0x80000000
+FEEDBACK_BOOTSTRAP_MAX_ROW_CAP = 64
 
 
 class FeedbackStats(C.Structure):
@@ -248,6 +249,11 @@ SYMBOLS = {
     "srn_feedback_reset_counters": (_i, [_vp]),
     "srn_feedback_sweep": (_i, [_vp, _u64, C.POINTER(_u64)]),
     "srn_feedback_get": (_i, [_vp, _u64, _u64, _u64, _vp, _sz, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(_u64)]),
+    "srn_feedback_bootstrap_enable": (_i, [_vp, C.c_uint32, _u64]),
+    "srn_feedback_bootstrap_disable": (_i, [_vp]),
+    "srn_feedback_bootstrap_info": (_i, [_vp, C.POINTER(C.c_uint32), C.POINTER(_u64)]),
+    "srn_feedback_bootstrap_read": (_i, [_vp, _vp, _vp, _vp, _sz, _sz]),
+    "srn_feedback_bootstrap_weights": (_i, [_u64, C.c_uint32, _vp, _vp, _sz, _vp]),
     "srn_harvest_create": (_i, [_i, _sz, _sz, C.c_uint32, C.POINTER(_vp)]),
     "srn_harvest_free": (_i, [_vp]),
     "srn_device_sessions_set_harvest": (_i, [_vp, _vp]),

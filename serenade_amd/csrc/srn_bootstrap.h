@@ -1,6 +1,7 @@
 // The bootstrap's weight rule, one statement for the host (srn_bootstrap_weights) and the device (srn_bootstrap.hip):
 //   w(seed, b, s) = #{ i : T[i] <= u },  u = mix64( mix64(seed + (b + 1) * 0x9E3779B97F4A7C15) ^ (s * 0xD1B54A32D192ED03 + 1) ) >> 32
 // a Poisson(1) count cut at 12, from nothing but (seed, replicate, session index): not from B, the trial, the index or the chunk.
+// The click feedback log (srn_feedback.hip) resamples visitors by the same rule: s = fold(key_hi, key_lo).
 #pragma once
 #include <cstdint>
 
@@ -34,5 +35,9 @@ SRN_BOOT_HD uint32_t boot_weight(uint64_t replicate_key, uint64_t s) {
     for (uint32_t i = 0; i < kBootMaxWeight; ++i) w += T[i] <= u ? 1u : 0u;
     return w;
 }
+
+// the click feedback log's resampling unit: a visitor's 128-bit key folded to the word boot_weight takes.  boot_mix64 is a bijection, so keys that
+// differ in one half fold to different words
+SRN_BOOT_HD uint64_t boot_fold(uint64_t key_hi, uint64_t key_lo) { return boot_mix64(key_hi ^ 0x9E3779B97F4A7C15ull) ^ key_lo; }
 
 }  // namespace srn

@@ -998,5 +998,17 @@ int srn_feedback_get(srn_feedback_t* f, uint64_t key_hi, uint64_t key_lo, uint64
                      uint64_t* out_epoch) {
     return guarded([&]() -> int { return fb_get(f, key_hi, key_lo, now_secs, out_ids, cap, out_count, out_n_model, out_epoch); });
 }
+int srn_feedback_bootstrap_enable(srn_feedback_t* f, uint32_t replicates, uint64_t seed) { return guarded([&]() -> int { return fb_boot_enable(f, replicates, seed); }); }
+int srn_feedback_bootstrap_disable(srn_feedback_t* f) { return guarded([&]() -> int { return fb_boot_disable(f); }); }
+int srn_feedback_bootstrap_info(srn_feedback_t* f, uint32_t* replicates, uint64_t* seed) { return guarded([&]() -> int { return fb_boot_info(f, replicates, seed); }); }
+int srn_feedback_bootstrap_read(srn_feedback_t* f, uint64_t* observed, uint64_t* hits_model, uint64_t* hits_filled, size_t replicates_cap, size_t rank_cap) {
+    return guarded([&]() -> int { return fb_boot_read(f, observed, hits_model, hits_filled, replicates_cap, rank_cap); });
+}
+int srn_feedback_bootstrap_weights(uint64_t seed, uint32_t replicate, const uint64_t* key_hi, const uint64_t* key_lo, size_t n, uint8_t* out) {
+    return guarded([&]() -> int {
+        if (n && (!key_hi || !key_lo || !out)) return fail(SRN_EINVAL, "srn_feedback_bootstrap_weights: null argument");
+        fb_boot_weights_host(seed, replicate, key_hi, key_lo, n, out);
+        return SRN_OK; });
+}
 
 }  // extern "C"

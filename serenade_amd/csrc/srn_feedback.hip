@@ -19,6 +19,8 @@
 //              first lane writes out_rank and adds to a histogram in LDS; the workgroup then issues one 64-bit global atomic per non-zero bin.  The grid is capped at
 //              2048 workgroups, each taking every 2048th block of positions, so that a call of 2^20 requests ends in at most 2048 atomics per counter word, not 65536
 //   fb_store   behind fb_rank: the run's last request writes its row, count, n_model, epoch and state full, once (the same lane groups)
+//   fb_boot    only while the bootstrap is enabled (srn_feedback_bootstrap_enable), behind fb_rank and fb_store: one lane per replicate weighs every
+//              observed request with w(seed, replicate, visitor) and adds it to the replicate's own observed count and histograms (its comment below)
 // Integer work throughout: ranks, counters and the table's entries do not depend on the run or on how the requests are cut into calls.
 // A batch whose requests carry their own clocks (srn_feedback_observe*_at) runs the timed form of fb_find, fb_rank and fb_store -- one body each,
 // template <bool kTimed> -- behind one gather of the times into sorted order: a run head tests its slot's epoch against its own time; any other request tests its
@@ -40,6 +42,7 @@
 #include "srn_device.h"
 #include "srn_sessions_dev.h"   // Table, the slot states, idle_or_old, wall_secs
 #include "srn_visitors.h"       // key_hash, the run predicates, find_or_claim, the key sort
+#include "srn_bootstrap.h"      // the weight rule and the key's fold
 #include "srn_hipsync.h"
 
 struct srn_feedback {
@@ -54,6 +57,9 @@ struct srn_feedback {
     char* ws = nullptr; size_t ws_bytes = 0;                // per-batch scratch, grows with the largest n seen
     char* small = nullptr;                                  // err word | occupied, live | one entry out
     unsigned long long* ctr = nullptr;                      // the counters: 8 words, hits_model[row_cap + 1], hits_filled[row_cap + 1]
+    unsigned long long* boot = nullptr;                     // the bootstrap's replicate words (null: off), word-major [1 + 2 * row_cap][boot_b]: observed_w, then
+    uint32_t boot_b = 0; uint64_t boot_seed = 0;            // hits_model_w[1 .. row_cap], then hits_filled_w[1 .. row_cap] -- a flush's lanes add to adjacent words
+    size_t boot_words() const { return (size_t)(1 + 2 * row_cap) * boot_b; }
     srn::Table tab() const { return srn::Table{table, (uint32_t)(n_slots - 1), stride}; }
     uint32_t n_bins() const { return 8u + 2u * ((uint32_t)row_cap + 1u); }
     uint32_t* err() const { return (uint32_t*)small; }
@@ -230,6 +236,66 @@ __global__ void __launch_bounds__(kTPB) fb_store(ObsArgs a) {
     }
 }
 
+// ---- the visitor-clustered bootstrap of the counters, behind fb_rank: replicate b weighs every observed request of a visitor with
+// w(seed, b, key) = boot_weight(boot_replicate_key(seed, b), boot_fold(key)) and keeps the weighted observed count and both weighted histograms as exact integers ----
+constexpr uint32_t kBootBlocks = 512;           // fb_boot's grid.x at the most: a (word, replicate) takes at most 512 global atomics per call
+constexpr uint32_t kBootStage = 128;            // sorted positions staged in LDS at a time
+constexpr uint32_t kBootWide = 256, kBootNarrow = 64, kBootWideRows = 31;   // replicates per workgroup: 2 * row_cap columns of u32 per lane plus the stage stay within 64 KiB
+uint32_t boot_tile(uint64_t row_cap) { return row_cap <= kBootWideRows ? kBootWide : kBootNarrow; }
+size_t boot_lds_bytes(uint64_t row_cap) { return (size_t)2 * row_cap * boot_tile(row_cap) * 4 + (size_t)kBootStage * 12; }
+static_assert(2 * kBootWideRows * kBootWide * 4 + kBootStage * 12 <= 65536 && 2 * SRN_FEEDBACK_BOOTSTRAP_MAX_ROW_CAP * kBootNarrow * 4 + kBootStage * 12 <= 65536, "fb_boot's LDS");
+
+struct BootArgs {
+    const uint64_t* key_hi; const uint64_t* key_lo;
+    const uint32_t* order;   // [n] request index of each sorted position: the observed requests of one visitor are adjacent
+    const uint32_t* rank;    // [n] by request index, as fb_rank left it
+    uint32_t n, row_cap, replicates;
+    uint64_t seed;
+    unsigned long long* words;
+};
+// One lane per replicate, blockDim.x replicates per workgroup (blockIdx.y: the tile).  A workgroup takes every gridDim.x-th stage of kBootStage sorted positions: it
+// puts (fold(key), rank) of the stage into LDS, then every lane walks the stage -- all lanes at the same position, the staged words read through readfirstlane, so
+// every branch is wave-uniform.  The weight is computed where the folded key changes and never carried from one stage to the next.  A hit goes to the lane's own
+// column bins[bin][lane] (no two lanes share a word: plain adds), observed_w stays in a register; one 64-bit global atomic per non-zero (word, replicate) at the end.
+// A workgroup's sums stay below 12 * 2^24 (kMaxBatch): u32 is enough.
+__global__ void __launch_bounds__(kBootWide) fb_boot(BootArgs a) {
+    extern __shared__ __align__(16) uint32_t boot_lds[];
+    const uint32_t tile = blockDim.x, lane = threadIdx.x, n_bins = 2u * a.row_cap;
+    uint32_t* bins = boot_lds;                                        // [n_bins][tile]
+    uint64_t* s_fold = (uint64_t*)(boot_lds + (size_t)n_bins * tile);  // [kBootStage]   (n_bins * tile * 4 is a multiple of 8)
+    uint32_t* s_rank = (uint32_t*)(s_fold + kBootStage);              // [kBootStage]
+    for (uint32_t i = 0; i < n_bins; ++i) bins[i * tile + lane] = 0;
+    const uint32_t b = blockIdx.y * tile + lane;                      // (b >= replicates: the lane walks along and adds nothing to memory)
+    const uint64_t key = boot_replicate_key(a.seed, b);
+    uint32_t obs = 0;
+    const uint32_t n_stages = (a.n + kBootStage - 1) / kBootStage;
+    for (uint32_t stage = blockIdx.x; stage < n_stages; stage += gridDim.x) {
+        const uint32_t p0 = stage * kBootStage, cnt = min(kBootStage, a.n - p0);
+        __syncthreads();                                              // the previous stage has been walked by every wave
+        for (uint32_t i = lane; i < cnt; i += tile) {
+            const uint32_t req = a.order[p0 + i], r = a.rank[req];
+            s_rank[i] = r;
+            if (r != SRN_FEEDBACK_NONE) s_fold[i] = boot_fold(a.key_hi[req], a.key_lo[req]);
+        }
+        __syncthreads();
+        uint64_t prev = 0; bool have = false; uint32_t w = 0;         // (have: no folded key is reserved as "none")
+        for (uint32_t q = 0; q < cnt; ++q) {
+            const uint32_t rk = __builtin_amdgcn_readfirstlane(s_rank[q]);
+            if (rk == SRN_FEEDBACK_NONE) continue;                    // not observed: adds nothing
+            const uint32_t* fw = (const uint32_t*)(s_fold + q);
+            const uint32_t f_lo = __builtin_amdgcn_readfirstlane(fw[0]), f_hi = __builtin_amdgcn_readfirstlane(fw[1]);   // (the builtin gives an int: no sign extension)
+            const uint64_t fold = (uint64_t)f_lo | ((uint64_t)f_hi << 32);
+            if (!have || fold != prev) { w = boot_weight(key, fold); prev = fold; have = true; }
+            obs += w;
+            const uint32_t r = rk & ~SRN_FEEDBACK_FILLED;
+            if (r != 0 && r <= a.row_cap) bins[(((rk & SRN_FEEDBACK_FILLED) ? a.row_cap : 0u) + r - 1u) * tile + lane] += w;
+        }
+    }
+    if (b >= a.replicates) return;                                    // (behind the last barrier)
+    if (obs) atomicAdd(&a.words[b], (unsigned long long)obs);
+    for (uint32_t i = 0; i < n_bins; ++i) { const uint32_t v = bins[i * tile + lane]; if (v) atomicAdd(&a.words[(size_t)(1 + i) * a.replicates + b], (unsigned long long)v); }
+}
+
 // ---- one key, from the host: out[0] = count (~0: unknown key), out[1] = epoch, out[2] = n_model, out[3..] = ids ----
 __global__ void fb_get_one(Table t, uint64_t hi, uint64_t lo, uint32_t row_cap, uint64_t* out) {
     out[0] = ~0ull;
@@ -332,7 +398,7 @@ void fb_free(srn_feedback* f) {
     (void)hipSetDevice(f->device);
     if (f->last) { (void)hipEventSynchronize(f->last); (void)hipEventDestroy(f->last); }
     if (f->own) { (void)hipStreamSynchronize(f->own); (void)hipStreamDestroy(f->own); }
-    for (void* p : {(void*)f->table, (void*)f->ws, (void*)f->small, (void*)f->ctr}) if (p) (void)hipFree(p);
+    for (void* p : {(void*)f->table, (void*)f->ws, (void*)f->small, (void*)f->ctr, (void*)f->boot}) if (p) (void)hipFree(p);
     delete f;
 }
 
@@ -387,7 +453,8 @@ int fb_observe_device(srn_feedback* f, const uint64_t* d_hi, const uint64_t* d_l
     HIP_TRY(rocprim::inclusive_scan(nullptr, t1, (uint32_t*)nullptr, (uint32_t*)nullptr, n, rocprim::maximum<uint32_t>(), st)); tmp = std::max(tmp, t1);
     const size_t w = align256(n * 4);
     const size_t o_keyA = 0, o_keyB = o_keyA + align256(n * 8), o_idxA = o_keyB + align256(n * 8), o_idxB = o_idxA + w, o_slot = o_idxB + w, o_stat = o_slot + w,
-                 o_head = o_stat + w, o_run = o_head + w, o_tmp = o_run + w, o_t = o_tmp + align256(tmp), bytes = o_t + (d_times ? align256(n * 8) : 0);   // (o_t: a timed batch only)
+                 o_head = o_stat + w, o_run = o_head + w, o_tmp = o_run + w, o_t = o_tmp + align256(tmp), o_rank = o_t + (d_times ? align256(n * 8) : 0),     // (o_t: a timed batch only)
+                 bytes = o_rank + (f->boot && !d_out_rank ? w : 0);   // (o_rank: the bootstrap reads the ranks; the caller gave no buffer for them)
     if (bytes > f->ws_bytes) {   // (the previous call may still read the scratch: wait for it before it is freed)
         HIP_TRY(hipEventSynchronize(f->last));
         if ((rc = ensure(&f->ws, &f->ws_bytes, bytes))) return rc;
@@ -408,7 +475,7 @@ int fb_observe_device(srn_feedback* f, const uint64_t* d_hi, const uint64_t* d_l
     a.rounds = (uint32_t)((f->row_cap + (1u << a.lanes_shift) - 1) >> a.lanes_shift);
     a.now = now; a.idle = f->idle;
     a.slot_of = (uint32_t*)(b + o_slot); a.status = (uint32_t*)(b + o_stat); a.headpos = (uint32_t*)(b + o_head); a.run_start = (uint32_t*)(b + o_run);
-    a.out_rank = d_out_rank; a.ctr = f->ctr; a.err = f->err();
+    a.out_rank = d_out_rank ? d_out_rank : f->boot ? (uint32_t*)(b + o_rank) : nullptr; a.ctr = f->ctr; a.err = f->err();
     const dim3 gg = grid_for(n << a.lanes_shift);   // (n <= 2^24: 2^28 lanes at the most)
     if (d_times) {   // a timed batch: the same sequence behind one gather of the times into sorted order
         a.when = (const uint64_t*)(b + o_t);
@@ -422,6 +489,11 @@ int fb_observe_device(srn_feedback* f, const uint64_t* d_hi, const uint64_t* d_l
         t1 = tmp; HIP_TRY(rocprim::inclusive_scan(b + o_tmp, t1, a.headpos, a.run_start, n, rocprim::maximum<uint32_t>(), st));
         fb_rank<false><<<dim3(std::min<unsigned>(gg.x, kRankBlocks)), kTPB, 4 * (size_t)f->n_bins(), st>>>(a);
         fb_store<false><<<gg, kTPB, 0, st>>>(a);
+    }
+    if (f->boot) {   // the replicate words, from the ranks fb_rank wrote
+        const BootArgs ba{d_hi, d_lo, order, a.out_rank, n32, (uint32_t)f->row_cap, f->boot_b, f->boot_seed, f->boot};
+        const uint32_t tile = boot_tile(f->row_cap);
+        fb_boot<<<dim3(std::min<unsigned>((n32 + kBootStage - 1) / kBootStage, kBootBlocks), (f->boot_b + tile - 1) / tile), tile, boot_lds_bytes(f->row_cap), st>>>(ba);
     }
     HIP_TRY(hipGetLastError());
     // from here on the log has changed: the next call is ordered behind this one
@@ -505,8 +577,73 @@ int fb_reset_counters(srn_feedback* f) {
     std::lock_guard<std::mutex> g(f->mu);
     int rc = own_after_last(f); if (rc) return rc;
     HIP_TRY(hipMemsetAsync(f->ctr, 0, 8 * (size_t)f->n_bins(), f->own));
+    if (f->boot) HIP_TRY(hipMemsetAsync(f->boot, 0, 8 * f->boot_words(), f->own));
     HIP_TRY(hipStreamSynchronize(f->own));
     return SRN_OK;
+}
+
+int fb_boot_enable(srn_feedback* f, uint32_t replicates, uint64_t seed) {
+    if (!f) return fail(SRN_EINVAL, "srn_feedback_bootstrap_enable: null log");
+    if (replicates == 0) return fail(SRN_EINVAL, "srn_feedback_bootstrap_enable: replicates must be > 0");
+    if (replicates > SRN_MAX_BOOTSTRAP) return fail(SRN_ERANGE, "srn_feedback_bootstrap_enable: replicates above SRN_MAX_BOOTSTRAP");
+    if (f->row_cap > SRN_FEEDBACK_BOOTSTRAP_MAX_ROW_CAP) return fail(SRN_ERANGE, "srn_feedback_bootstrap_enable: the log's row_cap is above 64");
+    std::lock_guard<std::mutex> g(f->mu);
+    if (f->boot) return fail(SRN_ESTATE, "srn_feedback_bootstrap_enable: the bootstrap is already enabled (disable it first)");
+    int rc = own_after_last(f); if (rc) return rc;
+    const size_t bytes = 8 * (size_t)(1 + 2 * f->row_cap) * replicates;
+    unsigned long long* words = nullptr;
+    if (hipMalloc((void**)&words, bytes) != hipSuccess) { (void)hipGetLastError(); return fail(SRN_ENOMEM, "srn_feedback_bootstrap_enable: no device memory for the replicate words"); }
+    hipError_t e = hipMemsetAsync(words, 0, bytes, f->own);
+    if (e == hipSuccess) e = hipStreamSynchronize(f->own);
+    if (e != hipSuccess) { (void)hipFree(words); return fail(SRN_EHIP, std::string("srn_feedback_bootstrap_enable: ") + hipGetErrorString(e)); }
+    f->boot = words; f->boot_b = replicates; f->boot_seed = seed;
+    return SRN_OK;
+}
+
+int fb_boot_disable(srn_feedback* f) {
+    if (!f) return fail(SRN_EINVAL, "srn_feedback_bootstrap_disable: null log");
+    std::lock_guard<std::mutex> g(f->mu);
+    if (!f->boot) return SRN_OK;
+    HIP_TRY(hipSetDevice(f->device));
+    HIP_TRY(hipEventSynchronize(f->last));   // (the previous call may still add to the words)
+    (void)hipFree(f->boot);
+    f->boot = nullptr; f->boot_b = 0; f->boot_seed = 0;
+    return SRN_OK;
+}
+
+int fb_boot_info(srn_feedback* f, uint32_t* replicates, uint64_t* seed) {
+    if (!f) return fail(SRN_EINVAL, "srn_feedback_bootstrap_info: null log");
+    std::lock_guard<std::mutex> g(f->mu);
+    if (replicates) *replicates = f->boot_b;
+    if (seed) *seed = f->boot_seed;
+    return SRN_OK;
+}
+
+int fb_boot_read(srn_feedback* f, uint64_t* observed, uint64_t* hits_model, uint64_t* hits_filled, size_t replicates_cap, size_t rank_cap) {
+    if (!f) return fail(SRN_EINVAL, "srn_feedback_bootstrap_read: null log");
+    std::lock_guard<std::mutex> g(f->mu);
+    if (!f->boot) return fail(SRN_ESTATE, "srn_feedback_bootstrap_read: the bootstrap is not enabled");
+    if (replicates_cap < f->boot_b) return fail(SRN_ERANGE, "srn_feedback_bootstrap_read: fewer than `replicates` entries per array");
+    if (rank_cap < f->row_cap + 1) return fail(SRN_ERANGE, "srn_feedback_bootstrap_read: fewer than row_cap + 1 entries per replicate");
+    HIP_TRY(hipSetDevice(f->device));
+    HIP_TRY(hipEventSynchronize(f->last));
+    std::vector<unsigned long long> h(f->boot_words());
+    HIP_TRY(hipMemcpy(h.data(), f->boot, h.size() * 8, hipMemcpyDeviceToHost));
+    const size_t B = f->boot_b, R = f->row_cap;
+    for (size_t b = 0; b < B; ++b) {
+        if (observed) observed[b] = h[b];
+        for (size_t r = 0; r < rank_cap; ++r) {   // [0] is unused; entries beyond row_cap are written as 0
+            const bool in = r >= 1 && r <= R;
+            if (hits_model) hits_model[b * rank_cap + r] = in ? h[r * B + b] : 0;
+            if (hits_filled) hits_filled[b * rank_cap + r] = in ? h[(R + r) * B + b] : 0;
+        }
+    }
+    return SRN_OK;
+}
+
+void fb_boot_weights_host(uint64_t seed, uint32_t replicate, const uint64_t* key_hi, const uint64_t* key_lo, size_t n, uint8_t* out) {
+    const uint64_t key = boot_replicate_key(seed, replicate);
+    for (size_t i = 0; i < n; ++i) out[i] = (uint8_t)boot_weight(key, boot_fold(key_hi[i], key_lo[i]));
 }
 
 int fb_sweep(srn_feedback* f, uint64_t now_secs, uint64_t* n_live) {

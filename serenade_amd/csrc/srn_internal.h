@@ -342,4 +342,10 @@ int fb_histogram(srn_feedback* f, uint64_t* hits_model, uint64_t* hits_filled, s
 int fb_reset_counters(srn_feedback* f);
 int fb_sweep(srn_feedback* f, uint64_t now_secs, uint64_t* n_live);
 int fb_get(srn_feedback* f, uint64_t hi, uint64_t lo, uint64_t now_secs, uint64_t* out_ids, size_t cap, uint32_t* out_count, uint32_t* out_n_model, uint64_t* out_epoch);
+// ... and its visitor-clustered bootstrap
+int fb_boot_enable(srn_feedback* f, uint32_t replicates, uint64_t seed);
+int fb_boot_disable(srn_feedback* f);
+int fb_boot_info(srn_feedback* f, uint32_t* replicates, uint64_t* seed);
+int fb_boot_read(srn_feedback* f, uint64_t* observed, uint64_t* hits_model, uint64_t* hits_filled, size_t replicates_cap, size_t rank_cap);
+void fb_boot_weights_host(uint64_t seed, uint32_t replicate, const uint64_t* key_hi, const uint64_t* key_lo, size_t n, uint8_t* out);
 }  // namespace srn

@@ -13,6 +13,7 @@ import warnings
 import numpy as np
 
 from . import capi
+from .evaluation import BOOTSTRAP_THRESHOLDS, _M64, _interval, _mix64
 from .vmisknn import ItemScore
 
 
@@ -717,17 +718,157 @@ def feedback_metrics(hist_model, hist_filled, observed):
     return out
 
 
+# ---- the visitor-clustered bootstrap of the log's counters (srn_feedback_bootstrap_*) ----
+_FEEDBACK_METRICS = tuple(m + part for part in ("", "_model", "_filled") for m in ("hit_rate", "mrr"))
+_FOLD = 0x9E3779B97F4A7C15
+
+
+def feedback_fold(keys):
+    """fold(key) = mix64(key_hi ^ 0x9E3779B97F4A7C15) ^ key_lo on uint64 arrays: the word the weight rule takes in the session index's place."""
+    hi, lo = (np.asarray(a, np.uint64) for a in keys)
+    return _mix64(hi ^ np.uint64(_FOLD)) ^ lo
+
+
+def feedback_bootstrap_weights(seed, B, keys, first_replicate=0):
+    """w(seed, b, key) for b = first_replicate .. first_replicate + B - 1 and keys = (hi, lo) -> uint8[B, n]: evaluation.bootstrap_weights' rule -- a Poisson(1)
+    count cut at 12 -- at fold(key).  Row b depends on (seed, b, key) alone."""
+    with np.errstate(over="ignore"):
+        b = np.uint64(int(first_replicate)) + np.arange(int(B), dtype=np.uint64)
+        rkey = _mix64(np.uint64(int(seed) & _M64) + (b + np.uint64(1)) * np.uint64(_FOLD))
+        s = feedback_fold(keys).reshape(-1)
+        u = _mix64(rkey[:, None] ^ (s * np.uint64(0xD1B54A32D192ED03) + np.uint64(1))[None, :]) >> np.uint64(32)
+    return np.searchsorted(np.array(BOOTSTRAP_THRESHOLDS, np.uint64), u, side="right").astype(np.uint8)
+
+
+def feedback_bootstrap_model(ranks, keys, B, seed, row_cap):
+    """NumPy statement of the log's replicate words (srn_feedback.hip fb_boot), exactly: ranks uint32[n] as feedback_model (or ClickFeedback.observe) gives them for the
+    requests of keys = (hi, lo), of any number of calls, concatenated.  Replicate b adds w(seed, b, key) per observed request -- rank not FEEDBACK_NONE -- to
+    observed[b], and for a rank r > 0 to hist_model[b, r], or hist_filled[b, r] where the rank carries FEEDBACK_FILLED.
+    -> {"observed": uint64[B], "hist_model": uint64[B, row_cap + 1], "hist_filled": the same}; integer sums, so the order of the requests does not matter."""
+    ranks = np.asarray(ranks, np.uint32).reshape(-1)
+    hi, lo = (np.asarray(a, np.uint64).reshape(-1) for a in keys)
+    if not (len(hi) == len(lo) == len(ranks)):
+        raise ValueError("one key per rank")
+    B, R = int(B), int(row_cap) + 1
+    out = {"observed": np.zeros(B, np.uint64), "hist_model": np.zeros((B, R), np.uint64), "hist_filled": np.zeros((B, R), np.uint64)}
+    obs = np.flatnonzero(ranks != capi.FEEDBACK_NONE)
+    if not len(obs):
+        return out
+    r = (ranks[obs] & np.uint32(0x7FFFFFFF)).astype(np.int64)
+    if r.max() >= R:
+        raise ValueError("a rank above row_cap")
+    column = np.where((ranks[obs] & np.uint32(capi.FEEDBACK_FILLED)) != 0, R, 0) + r      # the request's column in [hist_model | hist_filled]; r = 0: a miss
+    order = np.argsort(column, kind="stable")
+    cols, starts = np.unique(column[order], return_index=True)
+    visitors, of = np.unique(np.stack([hi[obs], lo[obs]], axis=1), axis=0, return_inverse=True)   # (a visitor's weight once)
+    of = of.reshape(-1)[order]
+    hist = np.zeros((B, 2 * R), np.uint64)
+    step = max(1, (1 << 22) // len(visitors))
+    for b0 in range(0, B, step):
+        w = feedback_bootstrap_weights(seed, min(step, B - b0), (visitors[:, 0], visitors[:, 1]), first_replicate=b0)[:, of]
+        sums = np.add.reduceat(w, starts, axis=1, dtype=np.uint64)
+        out["observed"][b0:b0 + len(w)] = sums.sum(axis=1, dtype=np.uint64)
+        hist[b0:b0 + len(w), cols] = sums
+    hist[:, 0] = hist[:, R] = 0                                                          # (the misses count in observed alone)
+    out["hist_model"], out["hist_filled"] = hist[:, :R].copy(), hist[:, R:].copy()
+    return out
+
+
+def _feedback_replicate_metrics(hist_model, hist_filled, observed):
+    """feedback_metrics of every replicate's weighted histograms over its observed_w, replicate by replicate the same bits -> ({metric: float64[B]}, bool[B]: the
+    replicate's observed_w is not 0; its values are 0 where it is)."""
+    hm, hf = (np.asarray(h, np.uint64) for h in (hist_model, hist_filled))
+    w = np.asarray(observed, np.uint64).astype(np.float64)
+    ok = w > 0
+    out = {}
+    for name, h in (("", hm + hf), ("_model", hm), ("_filled", hf)):
+        hits, mrr = np.zeros(len(w)), np.zeros(len(w))
+        for r in range(1, h.shape[1]):   # ascending r, as feedback_metrics adds
+            hits = hits + h[:, r].astype(np.float64)
+            mrr = mrr + h[:, r].astype(np.float64) / r
+        out["hit_rate" + name] = np.divide(hits, w, out=np.zeros_like(w), where=ok)
+        out["mrr" + name] = np.divide(mrr, w, out=np.zeros_like(w), where=ok)
+    return out, ok
+
+
+def feedback_replicate_values(stats, metric="mrr"):
+    """A bootstrapped ClickFeedback.stats()'s metric per replicate -> (float64[B], bool[B]: the replicate observed something)."""
+    boot = stats.get("bootstrap")
+    if boot is None:
+        raise ValueError("the stats carry no bootstrap: enable it on the log (ClickFeedback(..., bootstrap=B))")
+    if metric not in _FEEDBACK_METRICS:
+        raise ValueError("metric must be one of %s" % ", ".join(_FEEDBACK_METRICS))
+    values, ok = _feedback_replicate_metrics(boot["hist_model"], boot["hist_filled"], boot["observed"])
+    return values[metric], ok
+
+
+def feedback_compare(stats_a, stats_b, metric="mrr"):
+    """Bootstrap comparison of two logs' stats() -- evaluation.compare's counterpart for the online numbers -> {"delta": a - b of the point estimates, "ci": the
+    percentile interval of the replicate-by-replicate differences (at stats_a's level), "p_better": the share of replicates where a is above b, "replicates": how
+    many entered (those with something observed on both sides), "paired"}.  ValueError when seed or B differ.
+    A visitor's weight depends on (seed, replicate, key) alone.  The same log replayed under two configurations therefore resamples the same visitors on both sides
+    -- whether a request is observed does not depend on the rows served, so the two `observed` arrays are equal, and exactly then "paired" is true: the interval is
+    the paired one, the visitors' noise cancels in every difference.  Two logs with disjoint visitors (live traffic split over two logs) have independent
+    replicates: the same differences then form an ordinary unpaired two-sample interval, "paired" is false, and nothing cancels."""
+    ba, bb = stats_a.get("bootstrap"), stats_b.get("bootstrap")
+    if ba is None or bb is None:
+        raise ValueError("feedback_compare needs the stats of logs with the bootstrap enabled")
+    if ba["seed"] != bb["seed"] or ba["replicates"] != bb["replicates"]:
+        raise ValueError("the stats do not share their replicates: seed and replicates must be equal")
+    va, oka = feedback_replicate_values(stats_a, metric)
+    vb, okb = feedback_replicate_values(stats_b, metric)
+    d = (va - vb)[oka & okb]
+    return {"delta": float(stats_a[metric]) - float(stats_b[metric]), "ci": _interval(d, float(ba["ci"])),
+            "p_better": float(np.count_nonzero(d > 0)) / len(d) if len(d) else 0.0, "replicates": int(len(d)),
+            "paired": bool(np.array_equal(ba["observed"], bb["observed"]))}
+
+
+def _with_feedback_bootstrap(out, boot, ci):
+    """stats() of a log with the bootstrap enabled: the arrays under "bootstrap" and a percentile interval per metric over the replicates that observed something."""
+    values, ok = _feedback_replicate_metrics(boot["hist_model"], boot["hist_filled"], boot["observed"])
+    out["bootstrap"] = dict(boot, ci=ci, empty_replicates=int(np.count_nonzero(~ok)))
+    for name in _FEEDBACK_METRICS:
+        out[name + "_ci"] = _interval(values[name][ok], ci)
+    return out
+
+
 class ClickFeedback:
     """A click feedback log in the GPU's memory (srn_feedback_*): the last row served to every visitor, scored against the visitor's next click.  An object of its own
-    beside the session store; recommend_batch(..., feedback=fb) feeds it."""
+    beside the session store; recommend_batch(..., feedback=fb) feeds it.  bootstrap=B (and seed): enable_bootstrap(B, seed) at creation."""
 
-    def __init__(self, index_or_device, capacity, row_cap=21, ttl_secs=30 * 60, idle_secs=20 * 60):
+    def __init__(self, index_or_device, capacity, row_cap=21, ttl_secs=30 * 60, idle_secs=20 * 60, bootstrap=0, seed=0):
         device = _device_of(index_or_device)
         h = C.c_void_p()
         capi.check(capi.lib().srn_feedback_create(int(device), int(capacity), int(row_cap), int(ttl_secs), int(idle_secs), C.byref(h)))
         self._h, self.device, self.row_cap = h, int(device), int(row_cap)
         self.last_ranks = None
         self.last_error = None          # recommend_batch(..., feedback=self): the error of a call the log refused (its rows were served all the same)
+        if bootstrap:
+            try:
+                self.enable_bootstrap(bootstrap, seed)
+            except Exception:
+                self.close()
+                raise
+
+    def enable_bootstrap(self, replicates, seed=0):
+        """From the next call on the log keeps, per replicate b < replicates, the observed count and both histograms with every request weighted by
+        w(seed, b, visitor) (srn_feedback_bootstrap_enable): one more kernel per observe call; stats() then carries intervals.  The words start at 0."""
+        capi.check(capi.lib().srn_feedback_bootstrap_enable(self._h, int(replicates), int(seed) & _M64))
+
+    def disable_bootstrap(self):
+        capi.check(capi.lib().srn_feedback_bootstrap_disable(self._h))
+
+    def bootstrap(self):
+        """-> {"replicates", "seed", "observed": uint64[B], "hist_model": uint64[B, row_cap + 1], "hist_filled": the same} (column 0 unused), or None when the
+        bootstrap is off.  Blocks."""
+        B, seed = C.c_uint32(), C.c_uint64()
+        capi.check(capi.lib().srn_feedback_bootstrap_info(self._h, C.byref(B), C.byref(seed)))
+        if not B.value:
+            return None
+        obs = np.zeros(B.value, np.uint64)
+        hm, hf = np.zeros((B.value, self.row_cap + 1), np.uint64), np.zeros((B.value, self.row_cap + 1), np.uint64)
+        capi.check(capi.lib().srn_feedback_bootstrap_read(self._h, capi.ptr(obs), capi.ptr(hm), capi.ptr(hf), B.value, self.row_cap + 1))
+        return {"replicates": B.value, "seed": seed.value, "observed": obs, "hist_model": hm, "hist_filled": hf}
 
     def observe(self, keys, item_ids, consent, ids, counts, scores=None, now=0, times=None):
         """Requests (keys[i], item_ids[i], consent[i]) and the rows just served to them (ids[n, how_many], counts[n], scores or None) -> ranks[n]: the 1-based rank of
@@ -789,13 +930,17 @@ class ClickFeedback:
         capi.check(capi.lib().srn_feedback_histogram(self._h, capi.ptr(hm), capi.ptr(hf), self.row_cap + 1))
         return hm, hf
 
-    def stats(self):
-        """srn_feedback_stats_t as a dict (waits for the log's kernels), with feedback_metrics of the histograms: hit_rate, mrr and their _model / _filled parts."""
+    def stats(self, ci=0.95):
+        """srn_feedback_stats_t as a dict (waits for the log's kernels), with feedback_metrics of the histograms: hit_rate, mrr and their _model / _filled parts.
+        With the bootstrap enabled also "bootstrap" -- bootstrap()'s arrays, `ci` and "empty_replicates" -- and "<metric>_ci" for each of the six: the percentile
+        interval at level `ci` of the replicates' values, feedback_metrics of a replicate's weighted histograms over its observed_w; replicates that observed
+        nothing are left out and counted.  feedback_compare takes two such dicts."""
         st = capi.FeedbackStats()
         capi.check(capi.lib().srn_feedback_stats(self._h, C.byref(st)))
         out = {n: getattr(st, n) for n, _ in capi.FeedbackStats._fields_}
         out.update(feedback_metrics(*self.histogram(), out["observed"]))
-        return out
+        boot = self.bootstrap()
+        return out if boot is None else _with_feedback_bootstrap(out, boot, float(ci))
 
     def reset_counters(self):
         capi.check(capi.lib().srn_feedback_reset_counters(self._h))
