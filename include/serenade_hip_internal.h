@@ -69,6 +69,14 @@ int srn_debug_fill(const srn_index_t* idx, size_t nq, uint64_t* d_ids, double* d
  * HOST pointers; blocks until the result is back. */
 int srn_debug_class_counts(const uint64_t* acc, size_t n_waves, uint32_t* out16, int device);
 
+/* Test aid (tests/test_gpu_merge_pair.py): the fast kernel's merge_pair alone.  One 512-thread workgroup copies room [SRN_DEBUG_MERGE_ROOM words: the lean form's merge
+ * room] into LDS, merges n_pairs (1 or 2) pairs of adjacent descending runs from the room's lower half into its upper half -- the second pair behind the first with no
+ * barrier in between, as level 0 of a four-list query does -- and copies the whole room back.  pairs [n_pairs * 5] = (sa, la, lb, lg, reversed) per pair: the runs
+ * in[sa, sa + la) and in[sa + la, sa + la + lb) -> out[sa, sa + la + lb), sa + la + lb < SRN_DEBUG_MERGE_ROOM / 2, by a team of 2^lg threads (6 <= lg <= 9) counted
+ * from thread 0 up, or from thread 511 down where reversed != 0.  HOST pointers; blocks until the result is back. */
+#define SRN_DEBUG_MERGE_ROOM 12032
+int srn_debug_merge_pair(uint32_t* room, const uint32_t* pairs, size_t n_pairs, int device);
+
 /* Test / experiment knobs (environment variables SRN_NO_FAST, SRN_NO_MID, SRN_NO_MASKS, SRN_NO_MERGE, SRN_HOT_SLOTS,
  * SRN_SKETCH_SLOTS, SRN_LDS_BUDGET_KB, SRN_GRID_MULT, SRN_DEBUG) force individual kernel code paths.  They are read ONCE,
  * when the library is first used -- never on the launch path; this call re-reads them (the parity tests switch paths

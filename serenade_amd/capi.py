@@ -171,6 +171,7 @@ SYMBOLS = {
     "srn_debug_exclude_filter": (_i, [_vp, _sz, _vp, _vp, _vp, _sz, _vp, _vp, _sz, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
     "srn_debug_fill": (_i, [_vp, _sz, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, C.c_uint, _vp]),
     "srn_debug_class_counts": (_i, [_vp, _sz, _vp, _i]),
+    "srn_debug_merge_pair": (_i, [_vp, _vp, _sz, _i]),
     "srn_predict_batch_debug": (_i, [_vp, _vp, _vp, _sz, _sz, _sz, _sz, C.c_uint, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "srn_index_reserve": (_i, [_vp, _sz, _sz, _sz, _sz, _sz, C.c_uint, _vp]),
     "srn_last_kernel_ms": (_i, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint32)]),

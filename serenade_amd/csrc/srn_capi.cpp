@@ -559,6 +559,10 @@ int srn_debug_class_counts(const uint64_t* acc, size_t n_waves, uint32_t* out16,
     return guarded([&]() -> int { return device_debug_class_counts(acc, n_waves, out16, device); });
 }
 
+int srn_debug_merge_pair(uint32_t* room, const uint32_t* pairs, size_t n_pairs, int device) {
+    return guarded([&]() -> int { return device_debug_merge_pair(room, pairs, n_pairs, device); });
+}
+
 int srn_index_reserve(const srn_index_t* idx, size_t nq, size_t max_len_hint, size_t k, size_t m, size_t how_many, unsigned flags, void* stream) {
     return guarded([&]() -> int {
         int rc = check_predict_args(idx, k, m, how_many); if (rc) return rc;

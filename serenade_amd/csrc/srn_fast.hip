@@ -219,6 +219,11 @@ __device__ __forceinline__ uint32_t merge_team(uint32_t total) {   // log2 of th
     const uint32_t want = (total + (uint32_t)SRN_MERGE_G - 1u) / (uint32_t)SRN_MERGE_G;
     return want <= 64u ? 6u : want <= 128u ? 7u : want <= 256u ? 8u : 9u;
 }
+// (an LDS word by its 32-bit byte address: what a DS instruction takes, so address arithmetic written on it is the arithmetic the ISA does)
+typedef __attribute__((address_space(3))) uint32_t lds_u32;
+__device__ __forceinline__ uint32_t lds_addr(const uint32_t* p) { return (uint32_t)(uintptr_t)(const lds_u32*)p; }
+__device__ __forceinline__ uint32_t lds_ld(uint32_t a) { return *(const lds_u32*)(uintptr_t)a; }
+__device__ __forceinline__ void lds_st(uint32_t a, uint32_t v) { *(lds_u32*)(uintptr_t)a = v; }
 __device__ __forceinline__ void merge_pair(const uint32_t* in, uint32_t* out, uint32_t sa, uint32_t la, uint32_t lb, uint32_t ttid, uint32_t lg_nthr) {
     if ((ttid >> lg_nthr) != 0u) return;   // (whole waves)
 #ifndef SRN_MERGE_ODD
@@ -226,29 +231,51 @@ __device__ __forceinline__ void merge_pair(const uint32_t* in, uint32_t* out, ui
 #endif
     // (round 6) a thread's share is made ODD: lane l writes out[d0 + i] with d0 = l g -- an even g puts the 64 lanes of a store on 32 / 16 / 8 of the 64 banks
     // (g = 8, a quarter of the merges: an 8-way conflict on every step); an odd stride touches all banks.  The last threads of the team get nothing: they leave at once
-    const uint32_t sb = sa + la, total = la + lb, g = ((total + (1u << lg_nthr) - 1u) >> lg_nthr) | (SRN_MERGE_ODD ? 1u : 0u);
+    const uint32_t total = la + lb, g = ((total + (1u << lg_nthr) - 1u) >> lg_nthr) | (SRN_MERGE_ODD ? 1u : 0u);
     const uint32_t d0 = min(ttid * g, total), d1 = min(d0 + g, total);
     if (d0 >= d1) return;
-    uint32_t lo = d0 > lb ? d0 - lb : 0u, hi = min(d0, la);
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (in[sa + mid] > in[sb + d0 - 1 - mid]) lo = mid + 1; else hi = mid;
+    // Everything below works on LDS BYTE addresses held in VGPRs: with indices the compiler rebuilt both probe addresses in every search step, and without machine LICM (this file's
+    // build flag, kept for the per-query loop) it re-derived the loop invariants of the merge loop from their SGPRs in every iteration -- 10 VALU per search step and 16 per output.
+    const uint32_t a0 = lds_addr(in) + sa * 4u;   // A[0]
+    // The partition: pos = lo + the number of mid in [lo, hi) with A[mid] > B[d0 - 1 - mid] (true up to the partition, false behind it), hi - lo = min(d0, la, lb, total - d0).
+    // A descent in fixed steps P2 .. 1, P2 the largest power of two <= span, a wave-uniform bound on hi - lo (the loop counter is scalar and no lane leaves on its own): c = min(pos + step, hi),
+    // pos = c where A[c - 1] > B[d0 - c].  A clamped probe that holds means pos = hi, which later steps leave alone.  p = the address of A[pos - 1], x that of A[c - 1], kb - x that
+    // of B[d0 - c]; every probe lies in in[sa, sa + total).  The thread with d0 = 0 has no mid to look at: both its probes read A[0], which is not above itself.
+    const uint32_t lo = d0 > lb ? d0 - lb : 0u, hi = min(d0, la);
+    uint32_t p = a0 + lo * 4u - 4u;
+    // (measured, NOT kept: the bound tightened per wave to min(span, the wave's largest d0, total - its smallest d0) -- one or two steps fewer in a team's outer waves, which wait
+    //  for the middle ones at the barrier anyway: 18.97 against 18.85 ms, profiles/merge_loops_ab.txt)
+    const uint32_t span = min(la, lb);
+    if (span != 0u) {
+        uint32_t xh = a0 + max(hi, 1u) * 4u - 4u, kb = d0 != 0u ? 2u * a0 + (la + d0) * 4u - 4u : 2u * a0;
+        asm volatile("" : "+v"(xh), "+v"(kb));
+        for (uint32_t st = 4u << (31u - (uint32_t)__clz((int)span)); st >= 4u; st >>= 1) {
+            const uint32_t x = min(p + st, xh);
+            p = lds_ld(x) > lds_ld(kb - x) ? x : p;
+        }
     }
-    // sequential steps on two read pointers: one compare, one max, one dependent LDS read per output (12 VALU instructions; the index
-    // form with its per-step bound checks on both runs compiled to ~20)
-    const uint32_t* pa = in + sa + lo; const uint32_t* pb = in + sb + (d0 - lo);
-    const uint32_t* const ea = in + sb; const uint32_t* const eb = in + sb + lb;
-    uint32_t va = pa < ea ? *pa : 0u, vb = pb < eb ? *pb : 0u;   // (a staged slot is never 0)
-    uint32_t* c = out + sa + d0; uint32_t* const ce = out + sa + d1;
-    for (; c < ce; ++c) {
+    // sequential steps on two read pointers: one compare, one max, one dependent LDS read per output (in the ISA 24 VALU instructions per trip of two outputs, the loop's own
+    // compare and increment included, and 5 per search step above: profiles/merge_loops_ab.txt; the index form with its per-step bound checks on both runs compiled to ~20)
+    uint32_t pa = p + 4u, pb = 2u * a0 + (la + d0) * 4u - 4u - p;   // A[pos], B[d0 - pos]
+    uint32_t ea = a0 + la * 4u, eb = ea + lb * 4u;
+    asm volatile("" : "+v"(ea), "+v"(eb));
+    uint32_t va = 0u, vb = 0u;   // (a staged slot is never 0)
+    if (pa < ea) va = lds_ld(pa);
+    if (pb < eb) vb = lds_ld(pb);
+    // (two outputs per trip -- one increment and one exit compare for both -- and the share's last output, which is odd for every thread but the team's last, behind the loop:
+    //  it has no successor to fetch)
+    uint32_t c = lds_addr(out) + (sa + d0) * 4u; const uint32_t ce = c + (d1 - d0) * 4u, ce1 = ce - 4u;
+    auto put = [&](uint32_t off) {
         const bool ta = va > vb;
-        *c = max(va, vb);
-        const uint32_t* q = (ta ? pa : pb) + 1;
+        lds_st(c + off, max(va, vb));
+        const uint32_t q = (ta ? pa : pb) + 4u;
         pa = ta ? q : pa; pb = ta ? pb : q;
-        const uint32_t nxt = *q;   // (past a run's end: a neighbour's entry or scratch, discarded)
+        const uint32_t nxt = lds_ld(q);   // (past a run's end: a neighbour's entry or scratch, discarded)
         const uint32_t nv = q < (ta ? ea : eb) ? nxt : 0u;
         va = ta ? nv : va; vb = ta ? vb : nv;
-    }
+    };
+    for (; c < ce1; c += 8u) { put(0u); put(4u); }
+    if (c < ce) lds_st(c, max(va, vb));
 }
 
 // -------------------------------------------------------------------------------------
@@ -1677,6 +1704,48 @@ hipError_t launch_rows_to_packed(hipStream_t st, const uint64_t* row_off, const 
     else
     hipLaunchKernelGGL(rows_to_packed_kernel, dim3((unsigned)((n_rows + 1 + 1023) / 1024)), dim3(1024), 0, st, row_off, row_items, n_rows, block_base, packed, ext16);
     return hipGetLastError();
+}
+
+// test aid (srn_debug_merge_pair): merge_pair alone -- the inline function the kernel above calls, in a 512-thread workgroup over the lean form's merge room.  The pairs ride
+// in the kernel arguments (SGPRs, as the run tables of the kernel do); the second pair follows the first with no barrier in between, as at level 0 of a four-list query
+struct MergePairDebug { uint32_t sa, la, lb, lg, rev; };
+__global__ __launch_bounds__(512) void merge_pair_debug_kernel(uint32_t* __restrict__ room_g, MergePairDebug a, MergePairDebug b, uint32_t n_pairs) {
+    __shared__ uint32_t room[F_WORK_WORDS];
+    const uint32_t tid = threadIdx.x;
+    for (uint32_t i = tid; i < F_WORK_WORDS; i += 512u) room[i] = room_g[i];
+    __syncthreads();
+    const uint32_t* const in = room; uint32_t* const out = room + F_WORK_WORDS / 2u;
+    merge_pair(in, out, a.sa, a.la, a.lb, a.rev ? 511u - tid : tid, a.lg);
+    if (n_pairs > 1u) merge_pair(in, out, b.sa, b.la, b.lb, b.rev ? 511u - tid : tid, b.lg);
+    __syncthreads();
+    for (uint32_t i = tid; i < F_WORK_WORDS; i += 512u) room_g[i] = room[i];
+}
+
+int device_debug_merge_pair(uint32_t* room, const uint32_t* pairs, size_t n_pairs, int device) {
+    static_assert(F_WORK_WORDS == 12032u, "srn_debug_merge_pair documents the lean form's merge room");
+    if (!room || !pairs) return fail(SRN_EINVAL, "null buffer");
+    if (n_pairs < 1 || n_pairs > 2) return fail(SRN_ERANGE, "srn_debug_merge_pair: one or two pairs");
+    MergePairDebug pr[2] = {};
+    for (size_t i = 0; i < n_pairs; ++i) {
+        pr[i] = MergePairDebug{pairs[5 * i], pairs[5 * i + 1], pairs[5 * i + 2], pairs[5 * i + 3], pairs[5 * i + 4]};
+        // (the merge loop looks one word past the pair, as in the kernel: that word lies in the lower half too)
+        if (pr[i].lg < 6u || pr[i].lg > 9u || (uint64_t)pr[i].sa + pr[i].la + pr[i].lb >= F_WORK_WORDS / 2u) return fail(SRN_ERANGE, "srn_debug_merge_pair: a pair leaves the room's half, or lg is not 6 .. 9");
+    }
+    int prev_device = 0;
+    if (hipGetDevice(&prev_device) != hipSuccess || hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); return fail(SRN_EHIP, "srn_debug_merge_pair: no such device"); }
+    struct Restore { int d; ~Restore() { (void)hipSetDevice(d); } } restore{prev_device};   // (the caller's current device is left as it was, on every return below)
+    uint32_t* d_room = nullptr;
+    const size_t bytes = (size_t)F_WORK_WORDS * 4;
+    if (hipMalloc((void**)&d_room, bytes) != hipSuccess) { (void)hipGetLastError(); return fail(SRN_ENOMEM, "srn_debug_merge_pair: hipMalloc failed"); }
+    hipError_t e = hipMemcpy(d_room, room, bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(merge_pair_debug_kernel, dim3(1), dim3(512), 0, 0, d_room, pr[0], pr[1], (uint32_t)n_pairs);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpy(room, d_room, bytes, hipMemcpyDeviceToHost);   // (the null stream: the copy waits for the kernel)
+    (void)hipFree(d_room);
+    if (e != hipSuccess) return fail(SRN_EHIP, std::string("srn_debug_merge_pair: ") + hipGetErrorString(e));
+    return SRN_OK;
 }
 
 }  // namespace srn

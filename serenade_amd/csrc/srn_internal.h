@@ -160,6 +160,8 @@ int device_fill(DeviceState* d, uint32_t nq, uint64_t* ids, double* scores, uint
                 const uint64_t* items_flat, const uint32_t* q_off, bool whole_session, bool business, void* stream);
 // test aid (srn_debug_class_counts): the k-cut's wave-wide class counts (wave_class_counts, srn_device.h) alone; host pointers, acc [n_waves * 64], out16 [n_waves * 16]
 int device_debug_class_counts(const uint64_t* acc, size_t n_waves, uint32_t* out16, int device);
+// test aid (srn_debug_merge_pair): the fast kernel's merge_pair (srn_fast.hip) alone in one workgroup; host pointers, room [12 032 words], pairs [n_pairs * 5]
+int device_debug_merge_pair(uint32_t* room, const uint32_t* pairs, size_t n_pairs, int device);
 struct ShardIO {
     void* cand; uint32_t* cand_cnt;                                       // A out: [nq * m] packed slots, [nq]
     const void* gathered; const uint32_t* gathered_cnt; uint32_t n_shards;   // B in: [G][nq * gathered_stride], [G][nq]
