@@ -119,6 +119,67 @@ typedef struct {
 } srn_load_info_t;
 int srn_sessions_load_info(const srn_sessions_t* s, srn_load_info_t* out); /* zeros for a host-loaded handle */
 
+/* ---- preparing a click log: its rows on the device, and a split by time (srn_split.hip) ----
+ * srn_events_from_tsv_gpu holds what srn_sessions_from_tsv_gpu holds just before it groups: the file's rows in file order as three device arrays, the times as
+ * rounded seconds (u64), lines the host re-read patched in, skipped lines gone.  The view's pointers are device memory on `device`, valid until srn_events_free,
+ * and are passed on with SRN_EVENTS_DEVICE | SRN_EVENTS_TIME_I64.  A file without a row gives n = 0. */
+typedef struct srn_events srn_events_t;
+typedef struct {
+    const uint64_t* session_ids; const uint64_t* item_ids; const uint64_t* times; /* device memory */
+    size_t n;
+    int32_t device, reserved;
+} srn_events_view_t;
+int srn_events_from_tsv_gpu(const char* path, int device, srn_events_t** out);
+int srn_events_view(const srn_events_t* e, srn_events_view_t* out);
+void srn_events_free(srn_events_t* e);
+
+/* srn_events_split: n rows (session, item, time) in file order, passed exactly as to srn_sessions_from_events (host arrays, or device arrays with SRN_EVENTS_DEVICE;
+ * f64 times are rounded like the file's, int64 seconds with SRN_EVENTS_TIME_I64 have negative -> 0; every comparison is on these rounded seconds), get one code each.
+ * The rule, in this order -- a later step sees only rows no earlier step dropped:
+ *   1. last(s) = the largest time of any row of session s.  Sessions are never cut: the evaluator scores a session's later items against its earlier ones.
+ *   2. OUT: every row of a session with last(s) < start, or with end > 0 and last(s) >= end.
+ *   3. the other sessions are on the test side if last(s) >= cutoff, else on the train side (a test session's early rows may lie before the cutoff).
+ *   4. RARE: a train-side row whose item occurs in fewer than min_item_support train-side ROWS (rows, not distinct sessions).
+ *   5. SHORT_TRAIN: the remaining rows of a train session with fewer than min_session_len rows left.  One pass, no fixed point: dropping a short session may leave
+ *      an item with fewer than min_item_support rows, and it stays.
+ *   6. TRAIN: what is left on the train side.
+ *   7. UNKNOWN (with SRN_SPLIT_TEST_KNOWN_ITEMS): a test-side row whose item has no TRAIN row.
+ *   8. SHORT_TEST: the remaining rows of a test session with fewer than min_session_len rows left.
+ *   9. TEST: the rest.
+ * code[n] gets the codes; pos[n] for a TRAIN or TEST row the number of earlier rows with the same code, 0xFFFFFFFF otherwise -- both in memory of the inputs' kind.
+ * Exact integer work: the outputs are the same bytes from run to run.  The call waits for `stream` (it returns counts).
+ * srn_events_take is the stable compaction of one side: row j with code[j] == which goes to out_*[pos[j]]; times are copied as the 8 bytes given.  Device arrays:
+ * only enqueued on `stream`; host arrays: done on return.
+ * n = 0, a null buffer, cutoff = 0, start >= cutoff or end <= cutoff (when not 0), unknown flags, which not 1 or 2: SRN_EINVAL; n >= 2^32 - 1: SRN_ERANGE;
+ * device < 0: SRN_ENODEV. */
+#define SRN_SPLIT_TRAIN 1
+#define SRN_SPLIT_TEST 2
+#define SRN_SPLIT_OUT 16
+#define SRN_SPLIT_RARE 17
+#define SRN_SPLIT_SHORT_TRAIN 18
+#define SRN_SPLIT_UNKNOWN 19
+#define SRN_SPLIT_SHORT_TEST 20
+#define SRN_SPLIT_TEST_KNOWN_ITEMS 1u
+typedef struct {
+    uint64_t cutoff;           /* > 0 */
+    uint64_t start, end;       /* 0 = none; else start < cutoff < end */
+    uint32_t min_item_support; /* 0 reads as 1 */
+    uint32_t min_session_len;  /* 0 reads as 1 */
+    uint32_t flags;            /* SRN_SPLIT_TEST_KNOWN_ITEMS */
+    uint32_t reserved;         /* 0 */
+} srn_split_t;
+typedef struct {
+    uint64_t train_rows, train_sessions, train_items; /* TRAIN rows, the sessions and the distinct items that have one */
+    uint64_t test_rows, test_sessions, test_items;    /* the same for TEST */
+    uint64_t dropped_out, dropped_rare, dropped_short_train, dropped_unknown, dropped_short_test; /* rows per drop code */
+    uint64_t sessions, items;                         /* distinct in the input */
+    uint64_t t_min, t_max;                            /* over all rows, rounded seconds */
+} srn_split_info_t;
+int srn_events_split(const uint64_t* session_ids, const uint64_t* item_ids, const void* times, size_t n, unsigned flags, const srn_split_t* split, int device,
+                     void* stream, uint8_t* code, uint32_t* pos, srn_split_info_t* info);
+int srn_events_take(const uint8_t* code, const uint32_t* pos, size_t n, uint8_t which, const uint64_t* session_ids, const uint64_t* item_ids, const void* times,
+                    unsigned flags, uint64_t* out_sessions, uint64_t* out_items, void* out_times, int device, void* stream);
+
 /* ---- index ------------------------------------------------------------------------------ */
 
 /* prepare_hashmap() (src/vmisknn/vmis_index.rs:422-528) into the flat HBM layout:
@@ -854,6 +915,14 @@ int srn_eval_set_create(const srn_index_t* idx, const uint64_t* items_flat, cons
                         const uint64_t* train_item_ids, const uint64_t* train_item_counts, size_t n_train_items, srn_eval_set_t** out);
 /* the same from the reference's TSV files "SessionId ItemId Time" (src/io.rs:13-59): sessions in ascending SessionId, events by rounded time */
 int srn_eval_set_from_tsv(const srn_index_t* idx, const char* test_path, const char* train_path, srn_eval_set_t** out);
+/* the same from rows in memory, grouped and counted on the index's GPU: n_test test rows passed as to srn_sessions_from_events (the same flags; device arrays must
+ * be on the index's GPU and are read on `stream`) and the item column of the n_train training rows.  Test sessions in ascending session id, each one's rows by
+ * rounded time, equal times in input order; training counts are occurrences per id.  The set is the one srn_eval_set_from_tsv builds from files holding those rows
+ * (session ids below 2^32 and times that are not negative: the file reader keeps 32 bits of a session id and orders negative times, this call keeps 64 and reads
+ * them as 0): every report and every bootstrap replicate is the same bits.  Only the session offsets come to the host.  n_test >= 2^32 - 1 or n_train >= 2^32 - 1:
+ * SRN_ERANGE; a null buffer with rows, unknown flags: SRN_EINVAL.  n_test = 0 gives a set without queries.  The call waits for `stream`. */
+int srn_eval_set_from_events(const srn_index_t* idx, const uint64_t* test_session_ids, const uint64_t* test_item_ids, const void* test_times, size_t n_test,
+                             const uint64_t* train_item_ids, size_t n_train, unsigned flags, void* stream, srn_eval_set_t** out);
 /* Runs n_trials trials and blocks until they are done; out[t] is trial t's result.  Sums are added in a fixed order (partial sums per
  * group of 256 queries): the same trial gives the same bits from call to call, alone or among others, for any max_chunk_queries.
  * Every trial is checked before anything is launched: predict's argument checks, length 0 (SRN_EINVAL) or above SRN_MAX_HOW_MANY, and a

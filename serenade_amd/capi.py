@@ -82,6 +82,23 @@ class LoadInfo(C.Structure):
 
 
 EVENTS_TIME_I64, EVENTS_DEVICE = 1, 2
+SPLIT_TRAIN, SPLIT_TEST, SPLIT_OUT, SPLIT_RARE, SPLIT_SHORT_TRAIN, SPLIT_UNKNOWN, SPLIT_SHORT_TEST = 1, 2, 16, 17, 18, 19, 20
+SPLIT_TEST_KNOWN_ITEMS = 1
+SPLIT_NO_POS = 0xFFFFFFFF
+
+
+class EventsView(C.Structure):   # srn_events_view_t
+    _fields_ = [("session_ids", C.c_void_p), ("item_ids", C.c_void_p), ("times", C.c_void_p), ("n", C.c_size_t), ("device", C.c_int32), ("reserved", C.c_int32)]
+
+
+class Split(C.Structure):   # srn_split_t
+    _fields_ = [("cutoff", C.c_uint64), ("start", C.c_uint64), ("end", C.c_uint64)] + \
+               [(n, C.c_uint32) for n in ("min_item_support", "min_session_len", "flags", "reserved")]
+
+
+class SplitInfo(C.Structure):   # srn_split_info_t
+    _fields_ = [(n, C.c_uint64) for n in ("train_rows", "train_sessions", "train_items", "test_rows", "test_sessions", "test_items", "dropped_out", "dropped_rare",
+                                          "dropped_short_train", "dropped_unknown", "dropped_short_test", "sessions", "items", "t_min", "t_max")]
 
 
 class DeviceSessionsStats(C.Structure):
@@ -124,6 +141,11 @@ SYMBOLS = {
     "srn_sessions_from_tsv_gpu": (_i, [C.c_char_p, _i, C.POINTER(_vp)]),
     "srn_sessions_from_events": (_i, [_vp, _vp, _vp, _sz, C.c_uint, _i, _vp, C.POINTER(_vp)]),
     "srn_sessions_load_info": (_i, [_vp, C.POINTER(LoadInfo)]),
+    "srn_events_from_tsv_gpu": (_i, [C.c_char_p, _i, C.POINTER(_vp)]),
+    "srn_events_view": (_i, [_vp, C.POINTER(EventsView)]),
+    "srn_events_free": (None, [_vp]),
+    "srn_events_split": (_i, [_vp, _vp, _vp, _sz, C.c_uint, C.POINTER(Split), _i, _vp, _vp, _vp, C.POINTER(SplitInfo)]),
+    "srn_events_take": (_i, [_vp, _vp, _sz, C.c_uint8, _vp, _vp, _vp, C.c_uint, _vp, _vp, _vp, _i, _vp]),
     "srn_index_new_from_csv_gpu": (_i, [C.c_char_p, _sz, C.c_double, _sz, _i, C.POINTER(_vp)]),
     "srn_index_build": (_i, [C.POINTER(SessionsView), _sz, _sz, C.c_double, _i, C.POINTER(_vp)]),
     "srn_index_new_from_avro": (_i, [C.c_char_p, _i, C.POINTER(_vp)]),
@@ -205,6 +227,7 @@ SYMBOLS = {
     "srn_last_path_counts": (_i, [_vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "srn_eval_set_create": (_i, [_vp, _vp, _vp, _sz, _vp, _vp, _sz, C.POINTER(_vp)]),
     "srn_eval_set_from_tsv": (_i, [_vp, C.c_char_p, C.c_char_p, C.POINTER(_vp)]),
+    "srn_eval_set_from_events": (_i, [_vp, _vp, _vp, _vp, _sz, _vp, _sz, C.c_uint, _vp, C.POINTER(_vp)]),
     "srn_evaluate": (_i, [_vp, C.POINTER(EvalTrial), _sz, C.POINTER(EvalResult), _vp]),
     "srn_eval_set_free": (None, [_vp]),
     "srn_evaluate_bootstrap": (_i, [_vp, C.POINTER(EvalTrial), _sz, C.POINTER(Bootstrap), C.POINTER(EvalResult), _vp, _vp]),

@@ -118,6 +118,45 @@ int srn_sessions_from_events(const uint64_t* session_ids, const uint64_t* item_i
         if (rc) { delete s; return rc; }
         *out = s; return SRN_OK; });
 }
+// ---- a click log's rows on the device and their split by time (srn_ingest.hip, srn_split.hip) ----
+int srn_events_from_tsv_gpu(const char* path, int device, srn_events_t** out) {
+    return guarded([&]() -> int {
+        if (!path || !out) return fail(SRN_EINVAL, "null argument");
+        *out = nullptr;
+        if (device < 0) return fail(SRN_ENODEV, "the GPU loader needs a device");
+        return events_from_tsv_gpu(path, device, out); });
+}
+int srn_events_view(const srn_events_t* e, srn_events_view_t* out) {
+    if (!e || !out) return fail(SRN_EINVAL, "null argument");
+    *out = srn_events_view_t{e->s, e->i, e->t, e->n, e->device, 0};
+    return SRN_OK;
+}
+void srn_events_free(srn_events_t* e) { events_free(e); }
+int srn_events_split(const uint64_t* session_ids, const uint64_t* item_ids, const void* times, size_t n, unsigned flags, const srn_split_t* split, int device,
+                     void* stream, uint8_t* code, uint32_t* pos, srn_split_info_t* info) {
+    return guarded([&]() -> int {
+        if (!session_ids || !item_ids || !times || !split || !code || !pos || !info) return fail(SRN_EINVAL, "null argument");
+        if (n == 0) return fail(SRN_EINVAL, "no rows to split");
+        if (flags & ~(SRN_EVENTS_TIME_I64 | SRN_EVENTS_DEVICE)) return fail(SRN_EINVAL, "unknown flags");
+        if (split->cutoff == 0) return fail(SRN_EINVAL, "cutoff must be > 0");
+        if (split->start && split->start >= split->cutoff) return fail(SRN_EINVAL, "start must be below cutoff");
+        if (split->end && split->end <= split->cutoff) return fail(SRN_EINVAL, "end must be above cutoff");
+        if ((split->flags & ~SRN_SPLIT_TEST_KNOWN_ITEMS) || split->reserved) return fail(SRN_EINVAL, "unknown split flags");
+        if (n >= 0xFFFFFFFFull) return fail(SRN_ERANGE, "a split takes < 2^32 - 1 rows per call");
+        if (device < 0) return fail(SRN_ENODEV, "the split runs on a GPU");
+        return events_split(session_ids, item_ids, times, n, flags, *split, device, stream, code, pos, info); });
+}
+int srn_events_take(const uint8_t* code, const uint32_t* pos, size_t n, uint8_t which, const uint64_t* session_ids, const uint64_t* item_ids, const void* times,
+                    unsigned flags, uint64_t* out_sessions, uint64_t* out_items, void* out_times, int device, void* stream) {
+    return guarded([&]() -> int {
+        if (!code || !pos || !session_ids || !item_ids || !times || !out_sessions || !out_items || !out_times) return fail(SRN_EINVAL, "null argument");
+        if (n == 0) return fail(SRN_EINVAL, "no rows to take from");
+        if (flags & ~(SRN_EVENTS_TIME_I64 | SRN_EVENTS_DEVICE)) return fail(SRN_EINVAL, "unknown flags");
+        if (which != SRN_SPLIT_TRAIN && which != SRN_SPLIT_TEST) return fail(SRN_EINVAL, "which must be SRN_SPLIT_TRAIN or SRN_SPLIT_TEST");
+        if (n >= 0xFFFFFFFFull) return fail(SRN_ERANGE, "a split takes < 2^32 - 1 rows per call");
+        if (device < 0) return fail(SRN_ENODEV, "the split runs on a GPU");
+        return events_take(code, pos, n, which, session_ids, item_ids, times, flags, out_sessions, out_items, out_times, device, stream); });
+}
 int srn_sessions_load_info(const srn_sessions_t* s, srn_load_info_t* out) {
     if (!s || !out) return fail(SRN_EINVAL, "null argument");
     *out = s->info;
@@ -756,6 +795,18 @@ int srn_eval_set_from_tsv(const srn_index_t* idx, const char* test_path, const c
         *out = nullptr;
         int rc = check_eval_index(idx); if (rc) return rc;
         return eval_set_from_tsv(idx, test_path, train_path, out); });
+}
+
+int srn_eval_set_from_events(const srn_index_t* idx, const uint64_t* test_session_ids, const uint64_t* test_item_ids, const void* test_times, size_t n_test,
+                             const uint64_t* train_item_ids, size_t n_train, unsigned flags, void* stream, srn_eval_set_t** out) {
+    return guarded([&]() -> int {
+        if (!out) return fail(SRN_EINVAL, "null argument");
+        *out = nullptr;
+        int rc = check_eval_index(idx); if (rc) return rc;
+        if ((n_test && (!test_session_ids || !test_item_ids || !test_times)) || (n_train && !train_item_ids)) return fail(SRN_EINVAL, "null buffer");
+        if (flags & ~(SRN_EVENTS_TIME_I64 | SRN_EVENTS_DEVICE)) return fail(SRN_EINVAL, "unknown flags");
+        if (n_test >= 0xFFFFFFFFull || n_train >= 0xFFFFFFFFull) return fail(SRN_ERANGE, "an evaluation set takes < 2^32 - 1 test rows and training rows");
+        return eval_set_from_events(idx, test_session_ids, test_item_ids, test_times, n_test, train_item_ids, n_train, flags, stream, out); });
 }
 
 int srn_evaluate(srn_eval_set_t* set, const srn_eval_trial_t* trials, size_t n_trials, srn_eval_result_t* out, void* stream) {

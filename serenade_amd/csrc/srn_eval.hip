@@ -30,6 +30,7 @@
 #include "srn_runtime.h"
 #include "srn_device.h"
 #include "srn_hipsync.h"
+#include "srn_events.h"
 
 // the terms must be the bits the host formulas give: no fused multiply-adds
 #pragma clang fp contract(off)
@@ -248,6 +249,13 @@ template <typename T> int upload_new(T** p, const T* src, size_t n) {
     return SRN_OK;
 }
 size_t align256(size_t b) { return (b + 255) / 256 * 256; }
+// ndcg.rs:13-27 on the host (std::log2), so that the device terms are the host formulas' bits
+std::vector<double> ndcg_weights() {
+    std::vector<double> w(2 * SRN_MAX_HOW_MANY + 1, 0.0);
+    for (uint32_t i = 0; i < SRN_MAX_HOW_MANY; ++i) w[i] = i == 0 ? 1.0 : 1.0 / std::log2((double)i + 1.0);
+    for (uint32_t n = 1; n <= SRN_MAX_HOW_MANY; ++n) w[SRN_MAX_HOW_MANY + n] = w[SRN_MAX_HOW_MANY + n - 1] + w[n - 1];
+    return w;
+}
 }  // namespace
 
 void eval_set_free(srn_eval_set* set) {
@@ -281,10 +289,7 @@ int eval_set_create(const srn_index* idx, const uint64_t* items_flat, const uint
     }
     set->max_freq = max_freq ? (double)max_freq : 1.0;
     set->unique_training_items = merged.size();
-    // ndcg.rs:13-27 on the host (std::log2), so that the device terms are the host formulas' bits
-    std::vector<double> w(2 * SRN_MAX_HOW_MANY + 1, 0.0);
-    for (uint32_t i = 0; i < SRN_MAX_HOW_MANY; ++i) w[i] = i == 0 ? 1.0 : 1.0 / std::log2((double)i + 1.0);
-    for (uint32_t n = 1; n <= SRN_MAX_HOW_MANY; ++n) w[SRN_MAX_HOW_MANY + n] = w[SRN_MAX_HOW_MANY + n - 1] + w[n - 1];
+    const std::vector<double> w = ndcg_weights();
     EvalDevice* e = new EvalDevice(); set->dev = e; e->device = idx->device;
     HIP_TRY(hipSetDevice(e->device));
     int rc;
@@ -332,6 +337,173 @@ int eval_set_from_tsv(const srn_index* idx, const char* test_path, const char* t
     std::vector<uint64_t> ids, cnt;
     for (const auto& kv : counts) { ids.push_back(kv.first); cnt.push_back(kv.second); }
     return eval_set_create(idx, items.data(), off.data(), off.size() - 1, ids.data(), cnt.data(), ids.size(), out);
+}
+
+// ---- the same set from rows in memory, grouped and counted on the device (srn_eval_set_from_events) ----
+// Test rows: two stable LSD radix sorts that carry the row index, by rounded time and then by session id, leave the rows in (session, time, input order); the items
+// gathered in that order are the set's items, and a scan of the session heads gives the offsets.  Training items: one open-addressing table on the full ids
+// (srn_events.h) counts the occurrences; a pass over its slots takes the distinct count and the largest count over ALL ids, as eval_set_create does, and writes the
+// count of every id the index knows to its dense item.  The counts are integers below 2^32: the doubles are exact whatever order the atomics arrived in.
+namespace {
+constexpr int kEvTPB = 256;
+constexpr unsigned kEvReduceBlocks = 1024;
+inline dim3 ev_grid(uint64_t n, unsigned cap = 1u << 16) { return dim3((unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + kEvTPB - 1) / kEvTPB, cap))); }
+inline int ev_bits(uint64_t v) { int b = 0; while (v) { ++b; v >>= 1; } return std::max(b, 1); }
+
+__global__ void ev_time_keys(const void* times, bool i64, uint64_t n, uint64_t* key, uint32_t* idx) {
+    for (uint64_t j = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; j < n; j += (uint64_t)gridDim.x * blockDim.x) { key[j] = event_time(times, i64, j); idx[j] = (uint32_t)j; }
+}
+__global__ void ev_gather(const uint64_t* src, const uint32_t* idx, uint64_t n, uint64_t* out) {
+    for (uint64_t j = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; j < n; j += (uint64_t)gridDim.x * blockDim.x) out[j] = src[idx[j]];
+}
+__global__ void ev_max(const uint64_t* a, uint64_t n, unsigned long long* out) {   // one atomic per wave of a small grid
+    unsigned long long m = 0;
+    for (uint64_t j = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; j < n; j += (uint64_t)gridDim.x * blockDim.x) m = max(m, (unsigned long long)a[j]);
+    for (int o = 32; o > 0; o >>= 1) m = max(m, __shfl_xor(m, o));
+    if ((threadIdx.x & 63) == 0 && m) atomicMax(out, m);
+}
+__global__ void ev_heads(const uint64_t* sess_sorted, uint64_t n, uint32_t* head) {   // head[n] = 0 (the scan's total)
+    for (uint64_t j = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; j <= n; j += (uint64_t)gridDim.x * blockDim.x)
+        head[j] = j < n && (j == 0 || sess_sorted[j] != sess_sorted[j - 1]) ? 1u : 0u;
+}
+__global__ void ev_offsets(const uint32_t* head, const uint32_t* sid, uint64_t n, uint64_t* off) {   // sid = exclusive scan of head; sid[n] = number of sessions
+    for (uint64_t j = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; j <= n; j += (uint64_t)gridDim.x * blockDim.x)
+        if (j == n || head[j]) off[sid[j]] = j;
+}
+__global__ void __launch_bounds__(kEvTPB) ev_count(const uint64_t* ids, uint64_t n, KeyTable T, uint32_t* cnt, unsigned long long* full) {
+    __shared__ CombTable comb;   // the item column is Zipf: equal ids of a block are combined before they reach global memory
+    comb_init(comb);
+    for (uint64_t base = blockIdx.x * (uint64_t)kCombTile; base < n; base += (uint64_t)gridDim.x * kCombTile) {   // whole blocks stay in the loop together
+        for (uint32_t q = 0; q < kCombTile / kEvTPB; ++q) {
+            const uint64_t j = base + q * kEvTPB + threadIdx.x;
+            if (j >= n) break;
+            bool fresh;
+            const uint32_t s = key_table_insert(T, ids[j], &fresh);
+            if (s == kNone) { atomicAdd(full, 1ull); continue; }
+            comb_add(comb, cnt, s);
+        }
+        comb_flush(comb, cnt);
+    }
+}
+// out2: distinct ids, largest count
+__global__ void ev_freq(KeyTable T, const uint32_t* cnt, const IdSlot* id_table, uint32_t id_mask, double* freq, unsigned long long* out2) {
+    unsigned long long distinct = 0, mx = 0;
+    for (uint64_t e = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; e <= (uint64_t)T.mask + 1; e += (uint64_t)gridDim.x * blockDim.x) {
+        const bool own = e == (uint64_t)T.mask + 1;   // the slot of the id ~0
+        const unsigned long long key = own ? kEmptyKey : T.keys[e];
+        if (own ? T.keys[e] != 0 : key == kEmptyKey) continue;
+        const uint32_t c = cnt[e];
+        ++distinct; mx = max(mx, (unsigned long long)c);
+        if (!id_table) continue;
+        for (uint32_t h = (uint32_t)dev_mix64(key) & id_mask;; h = (h + 1) & id_mask) {   // FlatIndex::lookup
+            const IdSlot s = id_table[h];
+            if (s.idx == kNone) break;
+            if (s.key == key) { freq[s.idx] = (double)c; break; }
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) { distinct += __shfl_xor(distinct, o); mx = max(mx, __shfl_xor(mx, o)); }
+    if ((threadIdx.x & 63) == 0 && distinct) { atomicAdd(&out2[0], distinct); atomicMax(&out2[1], mx); }
+}
+}  // namespace
+
+int eval_set_from_events(const srn_index* idx, const uint64_t* test_sess, const uint64_t* test_item, const void* test_times, size_t n_test,
+                         const uint64_t* train_item, size_t n_train, unsigned flags, void* stream, srn_eval_set** out) {
+    const FlatIndex& ix = idx->flat;
+    const bool on_device = flags & SRN_EVENTS_DEVICE, i64 = flags & SRN_EVENTS_TIME_I64;
+    if (on_device) {
+        int rc = SRN_OK;
+        if (n_test && ((rc = check_device_rows(test_sess, idx->device, "test_session_ids")) || (rc = check_device_rows(test_item, idx->device, "test_item_ids")) ||
+                       (rc = check_device_rows(test_times, idx->device, "test_times")))) return rc;
+        if (n_train && (rc = check_device_rows(train_item, idx->device, "train_item_ids"))) return rc;
+    }
+    HIP_TRY(hipSetDevice(idx->device));
+    hipStream_t st = (hipStream_t)stream;
+    srn_eval_set* set = new srn_eval_set();
+    struct Guard { srn_eval_set*& s; ~Guard() { if (s) eval_set_free(s); } } guard{set};
+    set->idx = idx;
+    EvalDevice* e = new EvalDevice(); set->dev = e; e->device = idx->device;
+    DevBuf u_s, u_i, u_t, u_tr;
+    if (!on_device) {
+        if (n_test) {
+            HIP_TRY(u_s.alloc(n_test * 8)); HIP_TRY(u_i.alloc(n_test * 8)); HIP_TRY(u_t.alloc(n_test * 8));
+            HIP_TRY(hipMemcpyAsync(u_s.p, test_sess, n_test * 8, hipMemcpyHostToDevice, st)); HIP_TRY(hipMemcpyAsync(u_i.p, test_item, n_test * 8, hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(u_t.p, test_times, n_test * 8, hipMemcpyHostToDevice, st));
+            test_sess = u_s.as<uint64_t>(); test_item = u_i.as<uint64_t>(); test_times = u_t.p;
+        }
+        if (n_train) {
+            HIP_TRY(u_tr.alloc(n_train * 8));
+            HIP_TRY(hipMemcpyAsync(u_tr.p, train_item, n_train * 8, hipMemcpyHostToDevice, st));
+            train_item = u_tr.as<uint64_t>();
+        }
+    }
+    // the test sessions
+    const uint64_t n = n_test;
+    HIP_TRY(hipMalloc((void**)&e->items, std::max<size_t>(n * 8, 16)));
+    uint64_t n_sessions = 0;
+    if (n) {
+        DevBuf keyA, keyB, idxA, idxB, mx, head, sid, tmp;
+        HIP_TRY(keyA.alloc(n * 8)); HIP_TRY(keyB.alloc(n * 8)); HIP_TRY(idxA.alloc(n * 4)); HIP_TRY(idxB.alloc(n * 4)); HIP_TRY(mx.alloc(16));
+        HIP_TRY(head.alloc((n + 1) * 4)); HIP_TRY(sid.alloc((n + 1) * 4));
+        HIP_TRY(hipMemsetAsync(mx.p, 0, 16, st));
+        hipLaunchKernelGGL(ev_time_keys, ev_grid(n), dim3(kEvTPB), 0, st, test_times, i64, n, keyA.as<uint64_t>(), idxA.as<uint32_t>());
+        hipLaunchKernelGGL(ev_max, ev_grid(n, kEvReduceBlocks), dim3(kEvTPB), 0, st, keyA.as<uint64_t>(), n, mx.as<unsigned long long>());
+        hipLaunchKernelGGL(ev_max, ev_grid(n, kEvReduceBlocks), dim3(kEvTPB), 0, st, test_sess, n, mx.as<unsigned long long>() + 1);
+        unsigned long long maxes[2];
+        HIP_TRY(hipMemcpyAsync(maxes, mx.p, 16, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        size_t tb = 0, t1 = 0;
+        HIP_TRY(rocprim::radix_sort_pairs(nullptr, t1, keyA.as<uint64_t>(), keyB.as<uint64_t>(), idxA.as<uint32_t>(), idxB.as<uint32_t>(), n, 0, 64, st)); tb = t1;
+        HIP_TRY(rocprim::exclusive_scan(nullptr, t1, head.as<uint32_t>(), sid.as<uint32_t>(), 0u, n + 1, rocprim::plus<uint32_t>(), st)); tb = std::max(tb, t1);
+        HIP_TRY(tmp.alloc(tb));
+        t1 = tb; HIP_TRY(rocprim::radix_sort_pairs(tmp.p, t1, keyA.as<uint64_t>(), keyB.as<uint64_t>(), idxA.as<uint32_t>(), idxB.as<uint32_t>(), n, 0, ev_bits(maxes[0]), st));
+        hipLaunchKernelGGL(ev_gather, ev_grid(n), dim3(kEvTPB), 0, st, test_sess, idxB.as<uint32_t>(), n, keyA.as<uint64_t>());
+        t1 = tb; HIP_TRY(rocprim::radix_sort_pairs(tmp.p, t1, keyA.as<uint64_t>(), keyB.as<uint64_t>(), idxB.as<uint32_t>(), idxA.as<uint32_t>(), n, 0, ev_bits(maxes[1]), st));
+        // keyB = the session ids in set order, idxA = the rows' input indices
+        hipLaunchKernelGGL(ev_gather, ev_grid(n), dim3(kEvTPB), 0, st, test_item, idxA.as<uint32_t>(), n, e->items);
+        hipLaunchKernelGGL(ev_heads, ev_grid(n + 1), dim3(kEvTPB), 0, st, keyB.as<uint64_t>(), n, head.as<uint32_t>());
+        t1 = tb; HIP_TRY(rocprim::exclusive_scan(tmp.p, t1, head.as<uint32_t>(), sid.as<uint32_t>(), 0u, n + 1, rocprim::plus<uint32_t>(), st));
+        uint32_t ns32 = 0;
+        HIP_TRY(hipMemcpyAsync(&ns32, sid.as<uint32_t>() + n, 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        n_sessions = ns32;
+        HIP_TRY(hipMalloc((void**)&e->sess_off, (n_sessions + 1) * 8));
+        hipLaunchKernelGGL(ev_offsets, ev_grid(n + 1), dim3(kEvTPB), 0, st, head.as<uint32_t>(), sid.as<uint32_t>(), n, e->sess_off);
+        HIP_TRY(hipGetLastError());
+        set->sess_off.resize(n_sessions + 1);
+        HIP_TRY(hipMemcpyAsync(set->sess_off.data(), e->sess_off, (n_sessions + 1) * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    } else {
+        set->sess_off.assign(1, 0);
+        HIP_TRY(hipMalloc((void**)&e->sess_off, 16));
+        HIP_TRY(hipMemsetAsync(e->sess_off, 0, 16, st));
+    }
+    for (uint64_t s = 0; s < n_sessions; ++s) set->max_session_len = std::max<uint64_t>(set->max_session_len, set->sess_off[s + 1] - set->sess_off[s]);
+    // the training counts
+    HIP_TRY(hipMalloc((void**)&e->freq, std::max<size_t>(ix.n_items * 8, 16)));
+    HIP_TRY(hipMemsetAsync(e->freq, 0, std::max<size_t>(ix.n_items * 8, 16), st));
+    unsigned long long h3[3] = {0, 0, 0};   // distinct ids, largest count, inserts the table refused
+    if (n_train) {
+        const uint32_t slots = key_table_slots(n_train);
+        DevBuf keys, cnt, out3;
+        HIP_TRY(keys.alloc(((uint64_t)slots + 1) * 8)); HIP_TRY(cnt.alloc(((uint64_t)slots + 1) * 4)); HIP_TRY(out3.alloc(24));
+        HIP_TRY(hipMemsetAsync(keys.p, 0xFF, ((uint64_t)slots + 1) * 8, st)); HIP_TRY(hipMemsetAsync(cnt.p, 0, ((uint64_t)slots + 1) * 4, st)); HIP_TRY(hipMemsetAsync(out3.p, 0, 24, st));
+        const KeyTable T{keys.as<unsigned long long>(), slots - 1, split_hash_bits()};
+        hipLaunchKernelGGL(ev_count, dim3((unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n_train + kCombTile - 1) / kCombTile, 2048))), dim3(kEvTPB), 0, st, train_item, (uint64_t)n_train, T, cnt.as<uint32_t>(), out3.as<unsigned long long>() + 2);
+        hipLaunchKernelGGL(ev_freq, ev_grid((uint64_t)slots + 1, kEvReduceBlocks), dim3(kEvTPB), 0, st, T, cnt.as<uint32_t>(), ix.id_table.empty() ? nullptr : idx->dev->di.id_table,
+                           idx->dev->di.id_mask, e->freq, out3.as<unsigned long long>());
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(h3, out3.p, 24, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (h3[2]) return fail(SRN_ERANGE, "more distinct training items than the counting table's 2^31 slots");
+    }
+    set->max_freq = h3[1] ? (double)h3[1] : 1.0;
+    set->unique_training_items = h3[0];
+    const std::vector<double> w = ndcg_weights();
+    int rc;
+    if ((rc = upload_new(&e->ndcg_w, w.data(), w.size()))) return rc;
+    HIP_TRY(hipStreamSynchronize(st));
+    *out = set; set = nullptr;
+    return SRN_OK;
 }
 
 static uint32_t chunk_queries(const srn_eval_trial_t& t) {

@@ -12,7 +12,7 @@
 // order); k_mark keeps the heads of the (session, item) runs except the dropped row; a scan compacts them; a scan of the session heads
 // gives the offsets; k_session_max takes the max time per session (a wave-segmented max, then one atomic per session and wave).
 //
-// Parsing (sessions_from_tsv_gpu).  The host reads the file in chunks into two pinned staging buffers and uploads one while it reads the
+// Parsing (tsv_rows_device: shared by sessions_from_tsv_gpu, which groups the rows, and events_from_tsv_gpu, which hands them out).  The host reads the file in chunks into two pinned staging buffers and uploads one while it reads the
 // next; a chunk ends at its last '\n' and the tail is carried into the next.  Per chunk: k_nl_count / k_nl_ends find the line ends with a
 // wave64 ballot per 64 bytes plus a scan over 4 KiB tiles; k_row_count / k_row_scatter parse one line per thread, mirroring parse_line
 // (srn_index.cpp) exactly for the ids and the field structure, and compact the kept lines into the row arrays in file order.  The time
@@ -38,6 +38,7 @@
 
 #include "srn_internal.h"
 #include "srn_hipsync.h"
+#include "srn_events.h"
 
 namespace srn {
 
@@ -55,12 +56,6 @@ constexpr uint32_t kByteTile = 4096;           // bytes per block of the line-en
 constexpr uint32_t kLineTile = 1024;           // lines per block of the parse kernels: 4 rounds of 256
 constexpr size_t kDefaultChunk = 32u << 20;
 
-struct DevBuf {   // RAII device allocation
-    void* p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t bytes) { if (p) { (void)hipFree(p); p = nullptr; } return hipMalloc(&p, std::max<size_t>(bytes, 16)); }
-    template <typename T> T* as() const { return (T*)p; }
-};
 struct PinnedBuf {
     void* p = nullptr;
     ~PinnedBuf() { if (p) (void)hipHostFree(p); }
@@ -164,15 +159,6 @@ __global__ void k_low32(const unsigned long long* in, uint64_t n, uint32_t* out)
 __device__ const double kPow10[23] = {1e0, 1e1, 1e2, 1e3, 1e4, 1e5, 1e6, 1e7, 1e8, 1e9, 1e10, 1e11, 1e12, 1e13, 1e14, 1e15, 1e16,
                                       1e17, 1e18, 1e19, 1e20, 1e21, 1e22};
 __device__ inline bool is_digit(unsigned char c) { return c >= '0' && c <= '9'; }
-
-// `!(t >= 0)` -> 0, then llround (half away from zero) as u64.  t - trunc(t) is exact for t >= 0.
-__device__ inline uint64_t round_time(double t) {
-    if (!(t >= 0)) t = 0;
-    if (t >= 9223372036854775808.0) return 0x8000000000000000ull;   // llround's out-of-range value (inputs out of scope: the TSV path hands these to the host)
-    double r = trunc(t);
-    if (t - r >= 0.5) r += 1.0;
-    return (uint64_t)r;
-}
 
 // One line [p, end) without its '\n'.  0: skipped (the host's parse_line returns false), 1: a row, 2: the host parses the time field.
 __device__ int parse_line_dev(const unsigned char* p, const unsigned char* end, uint64_t& s, uint64_t& it, uint64_t& t) {
@@ -469,7 +455,8 @@ int sessions_from_events(const uint64_t* sess, const uint64_t* item, const void*
     return group_rows_device(ps, pi, d_t.as<uint64_t>(), n, st, out, info);
 }
 
-int sessions_from_tsv_gpu(const char* path, int device, Sessions& out, srn_load_info_t* info) {
+// the file's rows on the device, in file order (what group_rows_device takes); li: lines, rows, skipped, host_parsed and the read / upload / parse times
+int tsv_rows_device(const char* path, int device, hipStream_t st, TsvRows& out, srn_load_info_t& li) {
     const int fd = open(path, O_RDONLY);
     if (fd < 0) return fail(SRN_EIO, std::string("cannot open ") + path);
     struct FdGuard { int fd; ~FdGuard() { close(fd); } } guard{fd};
@@ -477,10 +464,6 @@ int sessions_from_tsv_gpu(const char* path, int device, Sessions& out, srn_load_
     if (fstat(fd, &sb) != 0) return fail(SRN_EIO, std::string("cannot stat ") + path);
     const uint64_t file_size = (uint64_t)sb.st_size;
     ING_TRY(hipSetDevice(device));
-    hipStream_t st = nullptr;
-    ING_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    struct StreamGuard { hipStream_t s; ~StreamGuard() { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } } sguard{st};
-    srn_load_info_t li{};
 
     // chunk buffers (grown when a line is longer than a chunk)
     size_t cap = std::max<size_t>(64, std::min<size_t>(chunk_bytes(), std::max<uint64_t>(file_size, 64)));
@@ -496,7 +479,8 @@ int sessions_from_tsv_gpu(const char* path, int device, Sessions& out, srn_load_
     };
     int rc = alloc_chunk(cap); if (rc) return rc;
     // rows: grown on demand; a kept line holds at least "d\td\tX" and its '\n', so a chunk of `len` bytes adds at most len / 6 + 1 rows
-    DevBuf rs, ri, rt, counters;   // counters: n_rows, n_lines, n_fallback
+    DevBuf& rs = out.s; DevBuf& ri = out.i; DevBuf& rt = out.t;
+    DevBuf counters;   // n_rows, n_lines, n_fallback
     uint64_t rcap = file_size / 24 + 2 * (cap / 6 + 1) + 16;
     ING_TRY(rs.alloc(rcap * 8)); ING_TRY(ri.alloc(rcap * 8)); ING_TRY(rt.alloc(rcap * 8)); ING_TRY(counters.alloc(24));
     ING_TRY(hipMemsetAsync(counters.p, 0, 24, st));
@@ -633,11 +617,60 @@ int sessions_from_tsv_gpu(const char* path, int device, Sessions& out, srn_load_
         li.ms_parse += ms_since(tf);
     }
     li.rows = n; li.skipped = li.lines - n;
-    if (n >= 0xFFFFFFFFull) return fail(SRN_ERANGE, "the GPU loader groups < 2^32 rows per call; use the host loader");
-    rc = group_rows_device(rs.as<uint64_t>(), ri.as<uint64_t>(), rt.as<uint64_t>(), n, st, out, &li);
+    out.n = n;
+    return SRN_OK;
+}
+
+namespace {
+struct OwnStream {   // a stream of the call's own, drained and destroyed when the call leaves
+    hipStream_t s = nullptr;
+    ~OwnStream() { if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } }
+};
+
+// a missing file is SRN_EIO before the device is touched
+int check_readable(const char* path) {
+    const int fd = open(path, O_RDONLY);
+    if (fd < 0) return fail(SRN_EIO, std::string("cannot open ") + path);
+    close(fd);
+    return SRN_OK;
+}
+}  // namespace
+
+int sessions_from_tsv_gpu(const char* path, int device, Sessions& out, srn_load_info_t* info) {
+    if (int rc0 = check_readable(path)) return rc0;
+    ING_TRY(hipSetDevice(device));
+    OwnStream own;
+    ING_TRY(hipStreamCreateWithFlags(&own.s, hipStreamNonBlocking));
+    TsvRows rows; srn_load_info_t li{};
+    int rc = tsv_rows_device(path, device, own.s, rows, li);
+    if (rc) return rc;
+    if (rows.n >= 0xFFFFFFFFull) return fail(SRN_ERANGE, "the GPU loader groups < 2^32 rows per call; use the host loader");
+    rc = group_rows_device(rows.s.as<uint64_t>(), rows.i.as<uint64_t>(), rows.t.as<uint64_t>(), rows.n, own.s, out, &li);
     if (rc) return rc;
     if (info) *info = li;
     return SRN_OK;
+}
+
+int events_from_tsv_gpu(const char* path, int device, srn_events** out) {
+    if (int rc0 = check_readable(path)) return rc0;
+    ING_TRY(hipSetDevice(device));
+    OwnStream own;
+    ING_TRY(hipStreamCreateWithFlags(&own.s, hipStreamNonBlocking));
+    TsvRows rows; srn_load_info_t li{};
+    int rc = tsv_rows_device(path, device, own.s, rows, li);
+    if (rc) return rc;
+    ING_TRY(hipStreamSynchronize(own.s));
+    srn_events* e = new srn_events();
+    e->n = rows.n; e->device = device;
+    e->s = (uint64_t*)rows.s.release(); e->i = (uint64_t*)rows.i.release(); e->t = (uint64_t*)rows.t.release();
+    *out = e;
+    return SRN_OK;
+}
+void events_free(srn_events* e) {
+    if (!e) return;
+    (void)hipSetDevice(e->device);
+    for (void* p : {(void*)e->s, (void*)e->i, (void*)e->t}) if (p) (void)hipFree(p);
+    delete e;
 }
 
 // exact q-quantile of the session lengths, as sessions_length_quantile computes it, by counting instead of sorting

@@ -44,6 +44,15 @@ int sessions_from_events(const uint64_t* session_ids, const uint64_t* item_ids, 
                          Sessions& out, srn_load_info_t* info);
 uint64_t sessions_length_quantile_counting(const uint64_t* off, size_t n, double q);   // = sessions_length_quantile, by counting the lengths
 void ingest_reload_knobs();                                                              // SRN_INGEST_CHUNK_BYTES
+// a click log's rows on the device and their split by time (srn_ingest.hip, srn_split.hip); arguments already checked by the C ABI glue
+int events_from_tsv_gpu(const char* path, int device, srn_events** out);
+void events_free(srn_events* e);
+int events_split(const uint64_t* session_ids, const uint64_t* item_ids, const void* times, size_t n, unsigned flags, const srn_split_t& split, int device, void* stream,
+                 uint8_t* code, uint32_t* pos, srn_split_info_t* info);
+int events_take(const uint8_t* code, const uint32_t* pos, size_t n, uint8_t which, const uint64_t* session_ids, const uint64_t* item_ids, const void* times, unsigned flags,
+                uint64_t* out_sessions, uint64_t* out_items, void* out_times, int device, void* stream);
+void split_reload_knobs();                                                               // SRN_SPLIT_HASH_BITS, SRN_SPLIT_NO_COMBINE
+uint32_t split_hash_bits();
 
 // ---- the flat index (host copy).  Layout and invariants: DESIGN.md "Data layout in HBM" ----
 struct FlatIndex {
@@ -250,6 +259,11 @@ struct srn_sessions {
     srn::Sessions s;
     srn_load_info_t info{};   // the GPU loader's counts and stage times (zeros for the host loader)
 };
+struct srn_events {   // a file's rows on the device (srn_events_from_tsv_gpu): three hipMalloc'ed arrays, released by events_free
+    uint64_t* s = nullptr; uint64_t* i = nullptr; uint64_t* t = nullptr;
+    size_t n = 0;
+    int device = -1;
+};
 
 // ---- offline evaluation (srn_eval.hip): test sessions + training-item frequencies bound to one index ----
 namespace srn { struct EvalDevice; }
@@ -265,6 +279,8 @@ namespace srn {
 int eval_set_create(const srn_index* idx, const uint64_t* items_flat, const uint64_t* sess_off, size_t n_sessions,
                     const uint64_t* train_ids, const uint64_t* train_counts, size_t n_train, srn_eval_set** out);
 int eval_set_from_tsv(const srn_index* idx, const char* test_path, const char* train_path, srn_eval_set** out);
+int eval_set_from_events(const srn_index* idx, const uint64_t* test_session_ids, const uint64_t* test_item_ids, const void* test_times, size_t n_test,
+                         const uint64_t* train_item_ids, size_t n_train, unsigned flags, void* stream, srn_eval_set** out);
 // trials already checked (srn_capi.cpp).  terms != nullptr: one trial, its per-query terms [n * 7] (cap entries of room)
 // boot != nullptr (already checked): every trial's replicate sums too, rep[n_trials][boot->replicates][SRN_BOOTSTRAP_SUMS] on the host
 int eval_run(srn_eval_set* set, const srn_eval_trial_t* trials, size_t n_trials, srn_eval_result_t* out, void* stream, double* terms, size_t cap,

@@ -60,7 +60,7 @@ static void knobs_read() {
 Knobs knobs() { std::call_once(g_knobs_once, knobs_read); std::lock_guard<std::mutex> lk(g_knobs_mu); return g_knobs; }
 int knob_predict_lanes() { return knobs().lanes; }
 size_t knob_tiny_max() { return (size_t)std::max(1, knobs().tiny_max); }
-void reload_knobs() { std::call_once(g_knobs_once, knobs_read); knobs_read(); ingest_reload_knobs(); }
+void reload_knobs() { std::call_once(g_knobs_once, knobs_read); knobs_read(); ingest_reload_knobs(); split_reload_knobs(); }
 
 namespace {
 template <typename T> const T* upload(DeviceState* d, const std::vector<T>& v, bool& ok, size_t pad = 0, size_t = 0) {   // (hipMalloc is 256-byte aligned)

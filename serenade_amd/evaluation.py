@@ -105,6 +105,34 @@ class EvalSet:
         capi.check(capi.lib().srn_eval_set_from_tsv(index._h, str(test_path).encode(), str(train_path).encode(), C.byref(h)))
         return cls(index, None, None, _handle=h)
 
+    @classmethod
+    def from_events(cls, index, test_events, train_item_ids):
+        """The set from_tsv builds from files holding these rows, grouped and counted on the index's GPU (srn_eval_set_from_events): test_events =
+        (session_ids, item_ids, times) of the test rows in file order, train_item_ids = the item column of the training rows.  NumPy arrays, or torch tensors on
+        the index's GPU (read in place on the current stream); times float (rounded like the file's) or integer seconds."""
+        from .ingest import _event_args, _is_torch
+        device = int(index.info["device"])
+        sess, items, times = test_events
+        keep, (ps, pi, pt), n, flags, stream = _event_args(sess, items, times, device)
+        train_on_gpu = _is_torch(train_item_ids) and train_item_ids.device.type == "cuda"
+        if train_on_gpu != bool(flags & capi.EVENTS_DEVICE):
+            raise ValueError("test_events and train_item_ids must all be GPU tensors or none of them")
+        if train_on_gpu:
+            if train_item_ids.device.index != device:
+                raise ValueError("train_item_ids is not on device %d" % device)
+            train = train_item_ids.contiguous()
+            if train.element_size() != 8 or train.dtype.is_floating_point:
+                raise TypeError("train_item_ids must be a 64-bit integer tensor")
+            ptrain, n_train = train.data_ptr(), train.numel()
+        else:
+            train = capi.as_u64(train_item_ids.numpy() if _is_torch(train_item_ids) else train_item_ids)
+            ptrain, n_train = train.ctypes.data, len(train)
+        h = C.c_void_p()
+        capi.check(capi.lib().srn_eval_set_from_events(index._h, C.c_void_p(ps), C.c_void_p(pi), C.c_void_p(pt), n, C.c_void_p(ptrain), n_train, flags,
+                                                       None if stream is None else C.c_void_p(stream), C.byref(h)))
+        del keep, train
+        return cls(index, None, None, _handle=h)
+
     def close(self):
         if getattr(self, "_h", None) and capi is not None and getattr(capi, "lib", None) is not None:   # (None at interpreter shutdown)
             capi.lib().srn_eval_set_free(self._h)
