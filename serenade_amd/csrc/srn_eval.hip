@@ -31,6 +31,7 @@
 #include "srn_device.h"
 #include "srn_hipsync.h"
 #include "srn_events.h"
+#include "srn_visitor_table.h"  // align256
 
 // the terms must be the bits the host formulas give: no fused multiply-adds
 #pragma clang fp contract(off)
@@ -248,7 +249,6 @@ template <typename T> int upload_new(T** p, const T* src, size_t n) {
     if (n) HIP_TRY(hipMemcpy(*p, src, n * sizeof(T), hipMemcpyHostToDevice));
     return SRN_OK;
 }
-size_t align256(size_t b) { return (b + 255) / 256 * 256; }
 // ndcg.rs:13-27 on the host (std::log2), so that the device terms are the host formulas' bits
 std::vector<double> ndcg_weights() {
     std::vector<double> w(2 * SRN_MAX_HOW_MANY + 1, 0.0);

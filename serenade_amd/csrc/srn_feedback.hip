@@ -26,6 +26,9 @@
 // template <bool kTimed> -- behind one gather of the times into sorted order: a run head tests its slot's epoch against its own time; any other request tests its
 // predecessor's time -- the epoch the predecessor's row would have been stored with -- and a break is counted as idle_expired; the run's last request stores its own
 // time.  The runs are the untimed call's, so one max scan over the run heads still gives the slot.
+// The table underneath -- the slot's head, the count and rebuild kernels over a payload functor, the capacity rule (make_room), the sweep's tail, the one-key read-back
+// and create's and free's shared halves -- is srn_visitor_table.h's, shared with the session store.  Here: the payload (count, n_model, ids), the batch
+// kernels, the single table and the sweep that allocates its successor, the counters, the histograms and the bootstrap's words.
 // The sort, the run predicates and the find-or-claim probe are srn_visitors.h's, shared with the session store.
 #include <hip/hip_runtime.h>
 
@@ -40,43 +43,30 @@
 #include "srn_internal.h"
 #include "srn_runtime.h"
 #include "srn_device.h"
-#include "srn_sessions_dev.h"   // Table, the slot states, idle_or_old, wall_secs
-#include "srn_visitors.h"       // key_hash, the run predicates, find_or_claim, the key sort
+#include "srn_visitor_table.h"  // the table, its kernels and the capacity rule (shared with srn_sessions_dev.hip)
+#include "srn_visitors.h"       // the run predicates, find_or_claim, the key sort
 #include "srn_bootstrap.h"      // the weight rule and the key's fold
 #include "srn_hipsync.h"
 
-struct srn_feedback {
-    int device = 0;
-    uint64_t capacity = 0, n_slots = 0, row_cap = 0, ttl = 0, idle = 0;
-    uint32_t stride = 0;
-    char* table = nullptr;                                  // a sweep rebuilds into a second one, allocated for it
-    std::mutex mu;                                          // covers the enqueue of a call and everything below
-    hipEvent_t last = nullptr;                              // end of the most recent call, whatever stream it ran on
-    hipStream_t own = nullptr;                              // stats / get / sweep / reset and the host-pointer entry point
-    uint64_t bound = 0, sweeps = 0, refused = 0;            // bound: upper bound of the occupied slots
+struct srn_feedback : srn::VisitorTable {                   // one table stands: a sweep rebuilds into a second one, allocated for it; stats / get / sweep / reset run on `own`
+    uint64_t row_cap = 0;
     char* ws = nullptr; size_t ws_bytes = 0;                // per-batch scratch, grows with the largest n seen
-    char* small = nullptr;                                  // err word | occupied, live | one entry out
     unsigned long long* ctr = nullptr;                      // the counters: 8 words, hits_model[row_cap + 1], hits_filled[row_cap + 1]
     unsigned long long* boot = nullptr;                     // the bootstrap's replicate words (null: off), word-major [1 + 2 * row_cap][boot_b]: observed_w, then
     uint32_t boot_b = 0; uint64_t boot_seed = 0;            // hits_model_w[1 .. row_cap], then hits_filled_w[1 .. row_cap] -- a flush's lanes add to adjacent words
     size_t boot_words() const { return (size_t)(1 + 2 * row_cap) * boot_b; }
-    srn::Table tab() const { return srn::Table{table, (uint32_t)(n_slots - 1), stride}; }
     uint32_t n_bins() const { return 8u + 2u * ((uint32_t)row_cap + 1u); }
-    uint32_t* err() const { return (uint32_t*)small; }
-    unsigned long long* counts() const { return (unsigned long long*)(small + 64); }
-    uint64_t* one() const { return (uint64_t*)(small + 128); }
 };
 
 namespace srn {
 
 namespace {
-constexpr uint32_t kTPB = 256;
+constexpr uint32_t kTPB = kTableTPB;            // (grid_for)
 constexpr uint32_t kMaxBatch = 1u << 24;
 constexpr uint32_t kRankBlocks = 2048;          // fb_rank's grid at the most (256 CUs x 8 workgroups): each workgroup pays one global atomic per non-zero bin
 constexpr uint32_t kFbHead = 40;                // bytes before the ids
 struct FbSlot { uint64_t key_hi, key_lo, epoch; uint32_t count, state, n_model, pad; };
 static_assert(sizeof(FbSlot) == kFbHead, "slot header");
-static_assert(offsetof(FbSlot, key_lo) == offsetof(SlotHead, key_lo) && offsetof(FbSlot, state) == offsetof(SlotHead, state), "find_or_claim probes a slot as SlotHead");
 // bins of the counters: the words of srn_feedback_stats_t in its order, then the two histograms
 enum : uint32_t { kRequests = 0, kNoConsent = 1, kFirstSeen = 2, kIdleExpired = 3, kObserved = 4, kHitsModel = 5, kHitsFilled = 6, kStored = 7, kHist = 8 };
 enum : uint32_t { kNew = 0, kIdle = 1, kLive = 2 };   // what fb_find saw in a head's slot
@@ -296,137 +286,60 @@ __global__ void __launch_bounds__(kBootWide) fb_boot(BootArgs a) {
     for (uint32_t i = 0; i < n_bins; ++i) { const uint32_t v = bins[i * tile + lane]; if (v) atomicAdd(&a.words[(size_t)(1 + i) * a.replicates + b], (unsigned long long)v); }
 }
 
-// ---- one key, from the host: out[0] = count (~0: unknown key), out[1] = epoch, out[2] = n_model, out[3..] = ids ----
-__global__ void fb_get_one(Table t, uint64_t hi, uint64_t lo, uint32_t row_cap, uint64_t* out) {
-    out[0] = ~0ull;
-    uint32_t h = key_hash(hi, lo) & t.mask;
-    for (uint32_t probes = 0; probes <= t.mask; ++probes, h = (h + 1) & t.mask) {
-        FbSlot* s = fb_slot(t, h);
-        if (s->state == kEmpty) return;
-        if (s->key_hi == hi && s->key_lo == lo) {
-            const uint32_t c = min(s->count, row_cap);
-            out[0] = c; out[1] = s->epoch; out[2] = s->n_model;
-            for (uint32_t i = 0; i < c; ++i) out[3 + i] = fb_ids(s)[i];
-            return;
-        }
-    }
-}
-// counters[0] = occupied slots, [1] = entries a sweep at `now` keeps
-__global__ void __launch_bounds__(kTPB) fb_count(Table t, uint64_t now, uint64_t ttl, unsigned long long* counters) {
-    const uint32_t i = blockIdx.x * kTPB + threadIdx.x;
-    bool occ = false, live = false;
-    if (i <= t.mask) { const FbSlot* s = fb_slot(t, i); occ = s->state != kEmpty; live = occ && !idle_or_old(now, s->epoch, ttl); }
-    const unsigned long long mo = __ballot(occ), ml = __ballot(live);
-    if ((threadIdx.x & 63) == 0) { if (mo) atomicAdd(&counters[0], (unsigned long long)__popcll(mo)); if (ml) atomicAdd(&counters[1], (unsigned long long)__popcll(ml)); }
-}
-// the entries a sweep keeps, into the cleared table `to` (every key once: a taken slot is another key's)
-__global__ void __launch_bounds__(kTPB) fb_rebuild(Table from, Table to, uint64_t now, uint64_t ttl, uint32_t row_cap) {
-    const uint32_t i = blockIdx.x * kTPB + threadIdx.x;
-    if (i > from.mask) return;
-    FbSlot* s = fb_slot(from, i);
-    if (s->state == kEmpty || idle_or_old(now, s->epoch, ttl)) return;
-    uint32_t h = key_hash(s->key_hi, s->key_lo) & to.mask;
-    for (uint32_t probes = 0; probes <= to.mask; ++probes, h = (h + 1) & to.mask) {
-        FbSlot* d = fb_slot(to, h);
-        if (atomicCAS(&d->state, kEmpty, kFull) != kEmpty) continue;
+// the log's payload for the table's rebuild and one-key read-back: out[0] = count, out[2] = n_model, out[3..] = ids
+struct FbPayload {
+    using Head = FbSlot;
+    uint32_t row_cap;
+    __device__ void copy(const FbSlot* s, FbSlot* d) const {
         const uint32_t c = min(s->count, row_cap);
-        d->key_hi = s->key_hi; d->key_lo = s->key_lo; d->epoch = s->epoch; d->count = c; d->n_model = s->n_model;
-        for (uint32_t j = 0; j < c; ++j) fb_ids(d)[j] = fb_ids(s)[j];
-        return;
+        d->count = c; d->n_model = s->n_model;
+        for (uint32_t j = 0; j < c; ++j) fb_ids(d)[j] = fb_ids(const_cast<FbSlot*>(s))[j];
     }
-}
+    __device__ void read(const FbSlot* s, uint64_t* out) const {
+        const uint32_t c = min(s->count, row_cap);
+        out[0] = c; out[2] = s->n_model;
+        for (uint32_t i = 0; i < c; ++i) out[3 + i] = fb_ids(const_cast<FbSlot*>(s))[i];
+    }
+};
 
-size_t align256(size_t b) { return (b + 255) / 256 * 256; }
-dim3 grid_for(size_t n) { return dim3((unsigned)((n + kTPB - 1) / kTPB)); }
-
-// behind everything enqueued on the log so far, on its own stream (mu held)
-int own_after_last(srn_feedback* f) { HIP_TRY(hipSetDevice(f->device)); HIP_TRY(hipStreamWaitEvent(f->own, f->last, 0)); return SRN_OK; }
-
-int count(srn_feedback* f, uint64_t now, uint64_t* occupied, uint64_t* live) {   // blocks (own stream, mu held)
-    HIP_TRY(hipMemsetAsync(f->counts(), 0, 16, f->own));
-    fb_count<<<grid_for(f->n_slots), kTPB, 0, f->own>>>(f->tab(), now, f->ttl, f->counts());
-    HIP_TRY(hipGetLastError());
-    unsigned long long c[2] = {0, 0};
-    HIP_TRY(hipMemcpyAsync(c, f->counts(), 16, hipMemcpyDeviceToHost, f->own));
-    HIP_TRY(hipStreamSynchronize(f->own));
-    *occupied = c[0]; *live = c[1];
-    return SRN_OK;
-}
 // The entries not older than the TTL into a second table, allocated here; the first one is freed (own stream, mu held, behind `last`; blocks).  A failure leaves the log as it was.
 int rebuild(srn_feedback* f, uint64_t now) {
     const size_t bytes = (size_t)f->n_slots * f->stride;
     char* nt = nullptr;
     if (hipMalloc((void**)&nt, bytes) != hipSuccess) { (void)hipGetLastError(); return fail(SRN_ENOMEM, "click feedback log: no device memory for the sweep's second table"); }
-    const Table from = f->tab(); Table to = from; to.base = nt;
-    hipError_t e = hipMemsetAsync(nt, 0, bytes, f->own);
-    if (e == hipSuccess) { fb_rebuild<<<grid_for(f->n_slots), kTPB, 0, f->own>>>(from, to, now, f->ttl, (uint32_t)f->row_cap); e = hipGetLastError(); }
+    Table to = f->tab(); to.base = nt;
+    hipError_t e = rebuild_into(f, to, now, FbPayload{(uint32_t)f->row_cap});
     if (e == hipSuccess) e = hipStreamSynchronize(f->own);
     if (e != hipSuccess) { (void)hipFree(nt); return fail(SRN_EHIP, std::string("click feedback log (sweep): ") + hipGetErrorString(e)); }
     (void)hipFree(f->table);
     f->table = nt; ++f->sweeps;
     return SRN_OK;
 }
-// The capacity rule (mu held): room for n more keys, or SRN_ENOMEM with the table as it was.  Only when the host's bound does not fit does anything wait for the device:
-// the exact counts replace the bound, and entries older than the TTL are dropped (a rebuild) if that makes the room.
-int make_room(srn_feedback* f, uint64_t n, uint64_t now) {
-    if (f->bound + n <= f->capacity) return SRN_OK;
-    int rc = own_after_last(f); if (rc) return rc;
-    uint64_t occupied = 0, live = 0;
-    if ((rc = count(f, now, &occupied, &live))) return rc;
-    f->bound = occupied;
-    if (occupied + n <= f->capacity) return SRN_OK;
-    if (live + n > f->capacity) {
-        ++f->refused;
-        return fail(SRN_ENOMEM, "click feedback log: the batch does not fit the log's capacity (live entries + batch > capacity)");
-    }
-    if ((rc = rebuild(f, now))) return rc;
-    f->bound = live;
-    return SRN_OK;
-}
-struct DevBuf {   // a blocking call's own device copies
-    char* p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    int alloc(size_t bytes, const char* who) {
-        if (hipMalloc((void**)&p, bytes ? bytes : 256) != hipSuccess) { (void)hipGetLastError(); p = nullptr; return fail(SRN_ENOMEM, std::string(who) + ": no device memory for the staging copies"); }
-        return SRN_OK;
-    }
-};
+// the capacity rule (srn_visitor_table.h) with the log's rebuild; the log never grows (mu held)
+int room_for(srn_feedback* f, uint64_t n, uint64_t now) { return make_room(f, n, now, [f](uint64_t at) { return rebuild(f, at); }, never_grows); }
 }  // namespace
 
 void fb_free(srn_feedback* f) {
     if (!f) return;
-    (void)hipSetDevice(f->device);
-    if (f->last) { (void)hipEventSynchronize(f->last); (void)hipEventDestroy(f->last); }
-    if (f->own) { (void)hipStreamSynchronize(f->own); (void)hipStreamDestroy(f->own); }
-    for (void* p : {(void*)f->table, (void*)f->ws, (void*)f->small, (void*)f->ctr, (void*)f->boot}) if (p) (void)hipFree(p);
+    table_release(f);
+    for (void* p : {(void*)f->ws, (void*)f->ctr, (void*)f->boot}) if (p) (void)hipFree(p);
     delete f;
 }
 
 int fb_create(int device, size_t capacity, size_t row_cap, uint64_t ttl_secs, uint64_t idle_secs, srn_feedback** out) {
     if (!out) return fail(SRN_EINVAL, "srn_feedback_create: null output");
     *out = nullptr;
-    if (capacity == 0) return fail(SRN_EINVAL, "srn_feedback_create: capacity must be > 0");
-    if (capacity > (1ull << 30)) return fail(SRN_ERANGE, "srn_feedback_create: capacity above 2^30 visitors");
     if (row_cap == 0) return fail(SRN_EINVAL, "srn_feedback_create: row_cap must be > 0");
     if (row_cap > SRN_MAX_HOW_MANY) return fail(SRN_ERANGE, "srn_feedback_create: row_cap above SRN_MAX_HOW_MANY");
-    const uint64_t ttl = ttl_secs ? ttl_secs : 30 * 60, idle = idle_secs ? idle_secs : 20 * 60;   // srn_device_sessions_create's defaults
-    if (ttl < idle) return fail(SRN_EINVAL, "srn_feedback_create: ttl_secs below idle_secs (a swept row could still have been read)");
-    int n_dev = 0;
-    if (device < 0 || hipGetDeviceCount(&n_dev) != hipSuccess || device >= n_dev) return fail(SRN_ENODEV, "srn_feedback_create: no such GPU");
-    HIP_TRY(hipSetDevice(device));
     srn_feedback* f = new srn_feedback();
     struct Guard { srn_feedback*& f; ~Guard() { if (f) fb_free(f); } } guard{f};
-    f->device = device; f->capacity = capacity; f->row_cap = row_cap; f->ttl = ttl; f->idle = idle;
-    f->n_slots = 2; while (f->n_slots < 2 * (uint64_t)capacity) f->n_slots <<= 1;
-    f->stride = (uint32_t)((kFbHead + 8 * row_cap + 127) / 128 * 128);
+    f->row_cap = row_cap;
+    const int rc = table_create(f, "srn_feedback_create", "click feedback log", device, capacity, ttl_secs, idle_secs, kFbHead, row_cap, 3 + SRN_MAX_HOW_MANY);
+    if (rc) return rc;
     const size_t bytes = (size_t)f->n_slots * f->stride;
     if (hipMalloc((void**)&f->table, bytes) != hipSuccess) { (void)hipGetLastError(); f->table = nullptr; return fail(SRN_ENOMEM, "srn_feedback_create: no device memory for the table"); }
-    HIP_TRY(hipMalloc((void**)&f->small, 128 + 8 * (3 + SRN_MAX_HOW_MANY)));
     HIP_TRY(hipMalloc((void**)&f->ctr, 8 * (size_t)f->n_bins()));
-    HIP_TRY(hipStreamCreateWithFlags(&f->own, hipStreamNonBlocking));
-    HIP_TRY(hipEventCreateWithFlags(&f->last, hipEventDisableTiming));
     HIP_TRY(hipMemsetAsync(f->table, 0, bytes, f->own));
-    HIP_TRY(hipMemsetAsync(f->small, 0, 128, f->own));
     HIP_TRY(hipMemsetAsync(f->ctr, 0, 8 * (size_t)f->n_bins(), f->own));
     HIP_TRY(hipStreamSynchronize(f->own));
     *out = f; f = nullptr;
@@ -445,7 +358,7 @@ int fb_observe_device(srn_feedback* f, const uint64_t* d_hi, const uint64_t* d_l
     hipStream_t st = (hipStream_t)stream;
     const uint64_t now = now_secs ? now_secs : wall_secs();
     std::lock_guard<std::mutex> g(f->mu);
-    int rc = make_room(f, n, now); if (rc) return rc;
+    int rc = room_for(f, n, now); if (rc) return rc;
     HIP_TRY(hipSetDevice(f->device));
     // scratch: sort keys and indices (double-buffered), the per-position words, rocPRIM's temporary storage
     size_t tmp = 0, t1 = 0;
@@ -514,7 +427,7 @@ int fb_observe_host(srn_feedback* f, const uint64_t* hi, const uint64_t* lo, con
     const size_t rows = n * how_many * 8;
     const size_t o_hi = 0, o_lo = o_hi + align256(n * 8), o_item = o_lo + align256(n * 8), o_con = o_item + align256(n * 8), o_ids = o_con + align256(n),
                  o_sc = o_ids + align256(rows), o_cnt = o_sc + align256(rows), o_rank = o_cnt + align256(n * 4), o_times = o_rank + align256(n * 4), bytes = o_times + (times ? align256(n * 8) : 0);
-    DevBuf buf; int rc = buf.alloc(bytes, "srn_feedback_observe"); if (rc) return rc;
+    StageBuf buf; int rc = buf.alloc(bytes, "srn_feedback_observe"); if (rc) return rc;
     char* b = buf.p;
     hipStream_t st = nullptr;   // a stream of this call's own: two host callers do not wait for each other's copies
     HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
@@ -550,10 +463,7 @@ int fb_stats(srn_feedback* f, srn_feedback_stats_t* out) {
     HIP_TRY(hipMemcpy(c, f->ctr, sizeof(c), hipMemcpyDeviceToHost));
     *out = srn_feedback_stats_t{f->capacity, f->n_slots, f->row_cap, f->stride, f->bound, f->sweeps, f->refused, f->ttl, f->idle,
                                 c[kRequests], c[kNoConsent], c[kFirstSeen], c[kIdleExpired], c[kObserved], c[kHitsModel], c[kHitsFilled], c[kStored]};
-    uint32_t err = 0;
-    HIP_TRY(hipMemcpy(&err, f->err(), 4, hipMemcpyDeviceToHost));
-    if (err) return fail(SRN_ESTATE, "click feedback log: a batch found the table full (the capacity rule was violated)");
-    return SRN_OK;
+    return check_err(f);
 }
 
 int fb_histogram(srn_feedback* f, uint64_t* hits_model, uint64_t* hits_filled, size_t cap) {
@@ -650,32 +560,19 @@ int fb_sweep(srn_feedback* f, uint64_t now_secs, uint64_t* n_live) {
     if (!f) return fail(SRN_EINVAL, "srn_feedback_sweep: null log");
     const uint64_t now = now_secs ? now_secs : wall_secs();
     std::lock_guard<std::mutex> g(f->mu);
-    int rc = own_after_last(f); if (rc) return rc;
-    if ((rc = rebuild(f, now))) return rc;
-    uint64_t occupied = 0, live = 0;
-    if ((rc = count(f, now, &occupied, &live))) return rc;
-    f->bound = occupied;
-    if (n_live) *n_live = occupied;
-    uint32_t err = 0;
-    HIP_TRY(hipMemcpy(&err, f->err(), 4, hipMemcpyDeviceToHost));
-    if (err) return fail(SRN_ESTATE, "click feedback log: a batch found the table full (the capacity rule was violated)");
-    return SRN_OK;
+    return sweep(f, now, [f](uint64_t at) { return rebuild(f, at); }, n_live);
 }
 
 int fb_get(srn_feedback* f, uint64_t hi, uint64_t lo, uint64_t now_secs, uint64_t* out_ids, size_t cap, uint32_t* out_count, uint32_t* out_n_model, uint64_t* out_epoch) {
     if (!f || !out_count || (cap && !out_ids)) return fail(SRN_EINVAL, "srn_feedback_get: null argument");
     const uint64_t now = now_secs ? now_secs : wall_secs();
     std::lock_guard<std::mutex> g(f->mu);
-    int rc = own_after_last(f); if (rc) return rc;
     *out_count = SRN_FEEDBACK_NONE;
     if (out_n_model) *out_n_model = 0;
     if (out_epoch) *out_epoch = 0;
-    fb_get_one<<<1, 1, 0, f->own>>>(f->tab(), hi, lo, (uint32_t)f->row_cap, f->one());
-    HIP_TRY(hipGetLastError());
-    std::vector<uint64_t> h(3 + f->row_cap);
-    HIP_TRY(hipMemcpyAsync(h.data(), f->one(), h.size() * 8, hipMemcpyDeviceToHost, f->own));
-    HIP_TRY(hipStreamSynchronize(f->own));
-    if (h[0] == ~0ull || idle_or_old(now, h[1], f->idle)) return SRN_OK;
+    std::vector<uint64_t> h; bool found = false;
+    const int rc = read_one(f, hi, lo, now, FbPayload{(uint32_t)f->row_cap}, 3 + f->row_cap, &h, &found);
+    if (rc || !found) return rc;
     if (h[0] > cap) return fail(SRN_ERANGE, "srn_feedback_get: output buffer too small");
     if (h[0]) std::memcpy(out_ids, h.data() + 3, h[0] * 8);
     *out_count = (uint32_t)h[0];

@@ -29,16 +29,14 @@
 
 #include "srn_internal.h"
 #include "srn_runtime.h"
-#include "srn_sessions_dev.h"
+#include "srn_sessions_dev.h"   // the store's and the harvest's handles over srn_visitor_table.h: Table, SlotHead, align256, grid_for
 #include "srn_visitors.h"       // the key sort
 #include "srn_hipsync.h"
 
 namespace srn {
 
 namespace {
-constexpr uint32_t kTPB = 256;
-size_t align256(size_t b) { return (b + 255) / 256 * 256; }
-dim3 grid_for(size_t n) { return dim3((unsigned)((std::max<size_t>(n, 1) + kTPB - 1) / kTPB)); }
+constexpr uint32_t kTPB = kTableTPB;   // (grid_for)
 
 // flag[i] for slot i of a table a rebuild at `now` reads: what the rebuild leaves out (occupied and older than the TTL); flag[n_slots] = 0
 __global__ void __launch_bounds__(kTPB) hv_dropped_flag(Table t, uint64_t now, uint64_t ttl, uint32_t min_len, uint64_t* __restrict__ flag) {

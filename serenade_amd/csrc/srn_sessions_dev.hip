@@ -29,16 +29,19 @@
 //   export          live flag per slot, exclusive scan, scatter in slot order into dense arrays (no atomic cursor: an unchanged store exports the same bytes)
 //   import          the batch's sort over the entries' keys; one lane per distinct key picks the run's winner (largest epoch, later index on a tie) and claims or
 //                   finds its slot; a second kernel writes the winners.  Checked before anything is changed
-//   resize / growth sess_rebuild into a freshly allocated pair of tables of another capacity or items_cap
+//   resize / growth table_rebuild into a freshly allocated pair of tables of another capacity or items_cap
 //   save / load     the export's arrays behind a 96-byte header with a checksum, written through a rename
-// The store forgets a session in two places -- sess_store overwrites the slot of a visitor who returns after idle, and sess_rebuild leaves out what is older than the
+// The store forgets a session in two places -- sess_store overwrites the slot of a visitor who returns after idle, and table_rebuild leaves out what is older than the
 // TTL (rebuild, resize_locked) -- and an attached session harvest (srn_harvest.hip) is handed the entry at both, before the old bytes go away:
-// sess_return_flag + harvest_append between sess_find and sess_store, harvest_dropped behind sess_rebuild over the old table.  Without one nothing here differs.
+// sess_return_flag + harvest_append between sess_find and sess_store, harvest_dropped behind table_rebuild over the old table.  Without one nothing here differs.
 //
 // A batch whose requests carry their own clocks (srn_recommend_batch*_at) runs the same sequence with the timed form of sess_find, sess_return_flag
 // and sess_store -- one body each, template <bool kTimed>, the untimed instantiation compiled without a trace of the other: a run is cut into SEGMENTS where a request
 // finds its predecessor's time idle, headpos marks segment heads, a second max scan keeps the run's head for the slot, and the sessions that end inside the call go to
 // the harvest from the call's CSR behind sess_emit.  Without times nothing here differs either.
+// The table underneath -- the slot's head, the count and rebuild kernels over a payload functor, the capacity rule (make_room), the sweep's tail, the one-key read-back
+// and create's and free's shared halves -- is srn_visitor_table.h's, shared with the click feedback log.  Here: the payload (len, items), the batch kernels, the
+// pair of tables and its flip, the harvest hooks, resize and growth, export / import and the file form.
 // The sort, the run predicates and the find-or-claim probe are srn_visitors.h's, shared with the feedback log and the harvest.
 #include <hip/hip_runtime.h>
 
@@ -57,14 +60,14 @@
 #include "srn_internal.h"
 #include "srn_runtime.h"
 #include "srn_device.h"
-#include "srn_sessions_dev.h"   // the slot, the table and the handle (shared with srn_trending.hip)
-#include "srn_visitors.h"       // key_hash, the run predicates, find_or_claim, the key sort (shared with srn_feedback.hip, srn_harvest.hip)
+#include "srn_sessions_dev.h"   // the store's handle (shared with srn_trending.hip, srn_harvest.hip) over srn_visitor_table.h: the table, its kernels and the capacity rule
+#include "srn_visitors.h"       // the run predicates, find_or_claim, the key sort (shared with srn_feedback.hip, srn_harvest.hip)
 #include "srn_hipsync.h"
 
 namespace srn {
 
 namespace {
-constexpr uint32_t kTPB = 256;
+constexpr uint32_t kTPB = kTableTPB;          // (grid_for)
 constexpr uint32_t kMaxBatch = 1u << 24;       // q_off is 32-bit: n * SRN_MAX_SESSION_LEN < 2^32
 
 // One struct for the untimed and the timed batch.  Untimed, when, runpos and run_head are null and never read; timed, `now` is not read: a run is cut
@@ -222,20 +225,18 @@ __global__ void __launch_bounds__(kTPB) sess_iota(uint32_t n, uint32_t* q_off) {
 }
 
 // ---- one key, from the host ----
-// out[0] = stored length (~0: unknown key), out[1] = epoch, out[2..] = items
-__global__ void sess_get_one(Table t, uint64_t hi, uint64_t lo, uint64_t* out) {
-    out[0] = ~0ull;
-    uint32_t h = key_hash(hi, lo) & t.mask;
-    for (uint32_t probes = 0; probes <= t.mask; ++probes, h = (h + 1) & t.mask) {
-        SlotHead* s = slot_at(t, h);
-        if (s->state == kEmpty) return;
-        if (s->key_hi == hi && s->key_lo == lo) {
-            out[0] = s->len; out[1] = s->epoch;
-            for (uint32_t i = 0; i < s->len; ++i) out[2 + i] = slot_items(s)[i];
-            return;
-        }
+// the store's payload for the table's rebuild and one-key read-back: out[0] = stored length, out[2..] = items
+struct SessSlot {
+    using Head = SlotHead;
+    __device__ void copy(const SlotHead* s, SlotHead* d) const {
+        d->len = s->len;
+        for (uint32_t j = 0; j < s->len; ++j) slot_items(d)[j] = slot_items(const_cast<SlotHead*>(s))[j];
     }
-}
+    __device__ void read(const SlotHead* s, uint64_t* out) const {
+        out[0] = s->len;
+        for (uint32_t i = 0; i < s->len; ++i) out[2 + i] = slot_items(const_cast<SlotHead*>(s))[i];
+    }
+};
 // io[0] = n, io[1..] = items in; io[0] <- 1 if the key is new, 0 if it was there, 2 if the table is full
 __global__ void sess_put_one(Table t, uint64_t hi, uint64_t lo, uint64_t now, uint64_t* io) {
     const uint32_t n = (uint32_t)io[0];
@@ -251,30 +252,6 @@ __global__ void sess_put_one(Table t, uint64_t hi, uint64_t lo, uint64_t now, ui
         }
     }
     io[0] = 2;
-}
-
-// counters[0] = occupied slots, [1] = entries a sweep at `now` keeps
-__global__ void __launch_bounds__(kTPB) sess_count(Table t, uint64_t now, uint64_t ttl, unsigned long long* counters) {
-    const uint32_t i = blockIdx.x * kTPB + threadIdx.x;
-    bool occ = false, live = false;
-    if (i <= t.mask) { const SlotHead* s = slot_at(t, i); occ = s->state != kEmpty; live = occ && !idle_or_old(now, s->epoch, ttl); }
-    const unsigned long long mo = __ballot(occ), ml = __ballot(live);
-    if ((threadIdx.x & 63) == 0) { if (mo) atomicAdd(&counters[0], (unsigned long long)__popcll(mo)); if (ml) atomicAdd(&counters[1], (unsigned long long)__popcll(ml)); }
-}
-// the entries a sweep keeps, into the cleared table `to` (every key once: a claimed slot is another key's)
-__global__ void __launch_bounds__(kTPB) sess_rebuild(Table from, Table to, uint64_t now, uint64_t ttl) {
-    const uint32_t i = blockIdx.x * kTPB + threadIdx.x;
-    if (i > from.mask) return;
-    const SlotHead* s = slot_at(from, i);
-    if (s->state == kEmpty || idle_or_old(now, s->epoch, ttl)) return;
-    uint32_t h = key_hash(s->key_hi, s->key_lo) & to.mask;
-    for (uint32_t probes = 0; probes <= to.mask; ++probes, h = (h + 1) & to.mask) {
-        SlotHead* d = slot_at(to, h);
-        if (atomicCAS(&d->state, kEmpty, kFull) != kEmpty) continue;
-        d->key_hi = s->key_hi; d->key_lo = s->key_lo; d->epoch = s->epoch; d->len = s->len;
-        for (uint32_t j = 0; j < s->len; ++j) slot_items(d)[j] = slot_items(const_cast<SlotHead*>(s))[j];
-        return;
-    }
 }
 
 // ---- bulk export / import / resize ----
@@ -387,8 +364,6 @@ __global__ void __launch_bounds__(kTPB) sess_import_write(ImportArgs a) {
     }
 }
 
-size_t align256(size_t b) { return (b + 255) / 256 * 256; }
-dim3 grid_for(size_t n) { return dim3((unsigned)((n + kTPB - 1) / kTPB)); }
 }  // namespace
 
 }  // namespace srn
@@ -399,50 +374,34 @@ namespace srn {
 
 void dsess_free(srn_device_sessions* s) {
     if (!s) return;
-    (void)hipSetDevice(s->device);
-    if (s->last) { (void)hipEventSynchronize(s->last); (void)hipEventDestroy(s->last); }
-    if (s->harvest) { std::lock_guard<std::mutex> g(s->harvest->mu); s->harvest->store = nullptr; s->harvest = nullptr; }   // freeing the store detaches its harvest
+    if (s->harvest) { std::lock_guard<std::mutex> g(s->harvest->mu); s->harvest->store = nullptr; s->harvest = nullptr; }   // freeing the store detaches its harvest, before its stream goes
+    table_release(s);
     for (hipEvent_t e : s->tev) if (e) (void)hipEventDestroy(e);
-    if (s->own) { (void)hipStreamSynchronize(s->own); (void)hipStreamDestroy(s->own); }
-    for (void* p : {(void*)s->table[0], (void*)s->table[1], (void*)s->ws, (void*)s->stage, (void*)s->small, (void*)s->xs, (void*)s->hs}) if (p) (void)hipFree(p);
+    for (void* p : {(void*)s->old, (void*)s->ws, (void*)s->stage, (void*)s->xs, (void*)s->hs}) if (p) (void)hipFree(p);
     delete s;
 }
 
 int dsess_create(int device, size_t capacity, size_t items_cap, uint64_t ttl_secs, uint64_t idle_secs, srn_device_sessions** out) {
     if (!out) return fail(SRN_EINVAL, "srn_device_sessions_create: null output");
     *out = nullptr;
-    if (capacity == 0) return fail(SRN_EINVAL, "srn_device_sessions_create: capacity must be > 0");
-    if (capacity > (1ull << 30)) return fail(SRN_ERANGE, "srn_device_sessions_create: capacity above 2^30 sessions");
     if (items_cap == 0) return fail(SRN_EINVAL, "srn_device_sessions_create: items_cap must be > 0");
     if (items_cap > SRN_MAX_SESSION_LEN) return fail(SRN_ERANGE, "srn_device_sessions_create: items_cap above SRN_MAX_SESSION_LEN");
-    const uint64_t ttl = ttl_secs ? ttl_secs : 30 * 60, idle = idle_secs ? idle_secs : 20 * 60;   // srn_session_store_create's defaults
-    if (ttl < idle) return fail(SRN_EINVAL, "srn_device_sessions_create: ttl_secs below idle_secs (a swept session could still have been read)");
-    int n_dev = 0;
-    if (device < 0 || hipGetDeviceCount(&n_dev) != hipSuccess || device >= n_dev) return fail(SRN_ENODEV, "srn_device_sessions_create: no such GPU");
-    HIP_TRY(hipSetDevice(device));
     srn_device_sessions* s = new srn_device_sessions();
     struct Guard { srn_device_sessions*& s; ~Guard() { if (s) dsess_free(s); } } guard{s};
-    s->device = device; s->capacity = capacity; s->items_cap = items_cap; s->ttl = ttl; s->idle = idle;
-    s->n_slots = 2; while (s->n_slots < 2 * (uint64_t)capacity) s->n_slots <<= 1;
-    s->stride = (uint32_t)((kSlotHead + 8 * items_cap + 127) / 128 * 128);
+    s->items_cap = items_cap;
+    const int rc = table_create(s, "srn_device_sessions_create", "device session store", device, capacity, ttl_secs, idle_secs, kSlotHead, items_cap, 2 + SRN_MAX_SESSION_LEN + 1);
+    if (rc) return rc;
     const size_t bytes = (size_t)s->n_slots * s->stride;
-    for (int i = 0; i < 2; ++i)
-        if (hipMalloc((void**)&s->table[i], bytes) != hipSuccess) { (void)hipGetLastError(); return fail(SRN_ENOMEM, "srn_device_sessions_create: no device memory for the table"); }
-    HIP_TRY(hipMalloc((void**)&s->small, 128 + 8 * (2 + SRN_MAX_SESSION_LEN + 1)));
-    HIP_TRY(hipStreamCreateWithFlags(&s->own, hipStreamNonBlocking));
-    HIP_TRY(hipEventCreateWithFlags(&s->last, hipEventDisableTiming));
+    for (char** t : {&s->table, &s->old})
+        if (hipMalloc((void**)t, bytes) != hipSuccess) { (void)hipGetLastError(); *t = nullptr; return fail(SRN_ENOMEM, "srn_device_sessions_create: no device memory for the table"); }
     for (hipEvent_t& e : s->tev) HIP_TRY(hipEventCreate(&e));
-    HIP_TRY(hipMemsetAsync(s->table[0], 0, bytes, s->own));
-    HIP_TRY(hipMemsetAsync(s->small, 0, 128, s->own));
+    HIP_TRY(hipMemsetAsync(s->table, 0, bytes, s->own));
     HIP_TRY(hipStreamSynchronize(s->own));
     *out = s; s = nullptr;
     return SRN_OK;
 }
 
 namespace {
-// behind everything enqueued on the store so far, on its own stream (mu held)
-int own_after_last(srn_device_sessions* s) { HIP_TRY(hipSetDevice(s->device)); HIP_TRY(hipStreamWaitEvent(s->own, s->last, 0)); return SRN_OK; }
-
 // room for an attached harvest's append over n table slots (own stream behind `last`, mu held).  A scratch of its own: a rebuild runs inside make_room, below an
 // import that already holds pointers into the export / import scratch, which must neither move nor be overwritten here
 int harvest_room(srn_device_sessions* s, size_t n) {
@@ -454,23 +413,11 @@ int harvest_room(srn_device_sessions* s, size_t n) {
 }
 
 int rebuild(srn_device_sessions* s, uint64_t now) {   // (own stream, mu held)
-    const Table from = s->tab(); Table to = from; to.base = s->table[s->cur ^ 1];
+    const Table from = s->tab(); Table to = from; to.base = s->old;
     if (s->harvest) { const int rc = harvest_room(s, s->n_slots); if (rc) return rc; }
-    HIP_TRY(hipMemsetAsync(to.base, 0, (size_t)s->n_slots * s->stride, s->own));
-    sess_rebuild<<<grid_for(s->n_slots), kTPB, 0, s->own>>>(from, to, now, s->ttl);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(rebuild_into(s, to, now, SessSlot{}));
     if (s->harvest) { const int rc = harvest_dropped(s->harvest, from, now, s->ttl, s->hs, s->own); if (rc) return rc; }   // what the rebuild left out, from the old table (it stays until the next rebuild)
-    s->cur ^= 1; ++s->sweeps;
-    return SRN_OK;
-}
-int count(srn_device_sessions* s, uint64_t now, uint64_t* occupied, uint64_t* live) {   // blocks (own stream, mu held)
-    HIP_TRY(hipMemsetAsync(s->counters(), 0, 16, s->own));
-    sess_count<<<grid_for(s->n_slots), kTPB, 0, s->own>>>(s->tab(), now, s->ttl, s->counters());
-    HIP_TRY(hipGetLastError());
-    unsigned long long c[2] = {0, 0};
-    HIP_TRY(hipMemcpyAsync(c, s->counters(), 16, hipMemcpyDeviceToHost, s->own));
-    HIP_TRY(hipStreamSynchronize(s->own));
-    *occupied = c[0]; *live = c[1];
+    std::swap(s->table, s->old); ++s->sweeps;
     return SRN_OK;
 }
 int count_max(srn_device_sessions* s, uint64_t now, uint64_t* occupied, uint64_t* live, uint64_t* longest) {   // blocks (own stream, mu held)
@@ -483,8 +430,6 @@ int count_max(srn_device_sessions* s, uint64_t now, uint64_t* occupied, uint64_t
     *occupied = c[0]; *live = c[1]; *longest = c[2];
     return SRN_OK;
 }
-uint64_t slots_for(uint64_t capacity) { uint64_t n = 2; while (n < 2 * capacity) n <<= 1; return n; }
-uint32_t stride_for(uint64_t items_cap) { return (uint32_t)((kSlotHead + 8 * items_cap + 127) / 128 * 128); }
 // Rebuilds the entries a sweep at `now` keeps into tables of another shape (own stream, mu held, behind `last`; blocks).  Both new tables are allocated before the
 // old ones are touched -- peak device memory is the old pair + the new pair -- and every failure leaves the store as it was.
 int resize_locked(srn_device_sessions* s, uint64_t capacity, uint64_t items_cap, uint64_t now, const char* who) {
@@ -493,7 +438,7 @@ int resize_locked(srn_device_sessions* s, uint64_t capacity, uint64_t items_cap,
     int rc = count_max(s, now, &occupied, &live, &longest); if (rc) return rc;
     if (live > capacity) return fail(SRN_ENOMEM, std::string(who) + ": more live sessions than the new capacity");
     if (longest > items_cap) return fail(SRN_ERANGE, std::string(who) + ": a stored session is longer than the new items_cap");
-    const uint64_t n_slots = slots_for(capacity); const uint32_t stride = stride_for(items_cap);
+    const uint64_t n_slots = slots_for(capacity); const uint32_t stride = stride_for(kSlotHead, items_cap);
     const size_t bytes = (size_t)n_slots * stride;
     if (s->harvest && (rc = harvest_room(s, s->n_slots))) return rc;   // (a refused or failed resize harvests nothing: the append is enqueued behind the rebuild below)
     char* nt[2] = {nullptr, nullptr};
@@ -504,46 +449,32 @@ int resize_locked(srn_device_sessions* s, uint64_t capacity, uint64_t items_cap,
             return fail(SRN_ENOMEM, std::string(who) + ": no device memory for the new tables");
         }
     const Table from = s->tab(), to{nt[0], (uint32_t)(n_slots - 1), stride};
-    hipError_t e = hipMemsetAsync(nt[0], 0, bytes, s->own);
-    if (e == hipSuccess) { sess_rebuild<<<grid_for(s->n_slots), kTPB, 0, s->own>>>(from, to, now, s->ttl); e = hipGetLastError(); }
+    hipError_t e = rebuild_into(s, to, now, SessSlot{});
     if (e == hipSuccess && s->harvest && (rc = harvest_dropped(s->harvest, from, now, s->ttl, s->hs, s->own))) {   // from the old table, before it is freed
         (void)hipStreamSynchronize(s->own); (void)hipFree(nt[0]); (void)hipFree(nt[1]);
         return rc;
     }
     if (e == hipSuccess) e = hipStreamSynchronize(s->own);
     if (e != hipSuccess) { (void)hipFree(nt[0]); (void)hipFree(nt[1]); return fail(SRN_EHIP, std::string(who) + ": " + hipGetErrorString(e)); }
-    (void)hipFree(s->table[0]); (void)hipFree(s->table[1]);
-    s->table[0] = nt[0]; s->table[1] = nt[1]; s->cur = 0;
+    (void)hipFree(s->table); (void)hipFree(s->old);
+    s->table = nt[0]; s->old = nt[1];
     s->capacity = capacity; s->items_cap = items_cap; s->n_slots = n_slots; s->stride = stride;
     s->bound = live; s->len_bound = std::max<uint32_t>(1u, std::min<uint32_t>(s->len_bound, (uint32_t)items_cap));
     ++s->resizes;
     return SRN_OK;
 }
-// The capacity rule (mu held): room for n more keys, or SRN_ENOMEM with the table as it was.  Only when the host's bound does not fit does anything wait for the device:
-// the exact counts replace the bound, and entries older than the TTL are dropped (a rebuild) if that makes the room.
-int make_room(srn_device_sessions* s, uint64_t n, uint64_t now) {
-    if (s->bound + n <= s->capacity) return SRN_OK;
-    int rc = own_after_last(s); if (rc) return rc;
-    uint64_t occupied = 0, live = 0;
-    if ((rc = count(s, now, &occupied, &live))) return rc;
-    s->bound = occupied;
-    if (occupied + n <= s->capacity) return SRN_OK;
-    if (live + n > s->capacity) {
-        // opt-in growth: the smallest power-of-two multiple of the capacity that holds live + n, if max_capacity allows it (this path already waits for the device)
-        uint64_t grown = s->capacity;
-        while (grown < live + n && grown < s->max_capacity) grown *= 2;
-        if (grown >= live + n && grown <= s->max_capacity) {
-            rc = resize_locked(s, grown, s->items_cap, now, "device session store (growth)");
-            if (rc == SRN_OK) { ++s->grows; return SRN_OK; }
-            if (rc != SRN_ENOMEM) return rc;
-        }
-        ++s->refused;
-        return fail(SRN_ENOMEM, "device session store: the batch does not fit the store's capacity (live sessions + batch > capacity)");
-    }
-    if ((rc = rebuild(s, now))) return rc;
-    HIP_TRY(hipStreamSynchronize(s->own));
-    s->bound = live;
-    return SRN_OK;
+// opt-in growth: the smallest power-of-two multiple of the capacity that holds `need`, if max_capacity allows it (the capacity rule already waits for the device here)
+int grow(srn_device_sessions* s, uint64_t need, uint64_t now) {
+    uint64_t grown = s->capacity;
+    while (grown < need && grown < s->max_capacity) grown *= 2;
+    if (grown < need || grown > s->max_capacity) return SRN_ENOMEM;
+    const int rc = resize_locked(s, grown, s->items_cap, now, "device session store (growth)");
+    if (rc == SRN_OK) ++s->grows;
+    return rc;
+}
+// the capacity rule (srn_visitor_table.h) with the store's rebuild and growth (mu held)
+int room_for(srn_device_sessions* s, uint64_t n, uint64_t now) {
+    return make_room(s, n, now, [s](uint64_t at) { return rebuild(s, at); }, [s](uint64_t need, uint64_t at) { return grow(s, need, at); });
 }
 }  // namespace
 
@@ -551,14 +482,10 @@ int dsess_get(srn_device_sessions* s, uint64_t hi, uint64_t lo, uint64_t now_sec
     if (!s || !out_n || (cap && !out_items)) return fail(SRN_EINVAL, "srn_device_sessions_get: null argument");
     const uint64_t now = now_secs ? now_secs : wall_secs();
     std::lock_guard<std::mutex> g(s->mu);
-    int rc = own_after_last(s); if (rc) return rc;
     *out_n = 0;
-    sess_get_one<<<1, 1, 0, s->own>>>(s->tab(), hi, lo, s->one());
-    HIP_TRY(hipGetLastError());
-    std::vector<uint64_t> h(2 + s->items_cap);
-    HIP_TRY(hipMemcpyAsync(h.data(), s->one(), h.size() * 8, hipMemcpyDeviceToHost, s->own));
-    HIP_TRY(hipStreamSynchronize(s->own));
-    if (h[0] == ~0ull || idle_or_old(now, h[1], s->idle)) return SRN_OK;
+    std::vector<uint64_t> h; bool found = false;
+    const int rc = read_one(s, hi, lo, now, SessSlot{}, 2 + s->items_cap, &h, &found);
+    if (rc || !found) return rc;
     if (h[0] > cap) return fail(SRN_ERANGE, "srn_device_sessions_get: output buffer too small");
     std::memcpy(out_items, h.data() + 2, h[0] * 8);
     *out_n = (size_t)h[0];
@@ -570,7 +497,7 @@ int dsess_update(srn_device_sessions* s, uint64_t hi, uint64_t lo, uint64_t now_
     if (n > s->items_cap) return fail(SRN_ERANGE, "srn_device_sessions_update: session longer than the store's items_cap");
     const uint64_t now = now_secs ? now_secs : wall_secs();
     std::lock_guard<std::mutex> g(s->mu);
-    int rc = make_room(s, 1, now); if (rc) return rc;
+    int rc = room_for(s, 1, now); if (rc) return rc;
     if ((rc = own_after_last(s))) return rc;
     std::vector<uint64_t> h(1 + n); h[0] = n;
     if (n) std::memcpy(h.data() + 1, items, n * 8);
@@ -590,16 +517,7 @@ int dsess_sweep(srn_device_sessions* s, uint64_t now_secs, uint64_t* n_live) {
     if (!s) return fail(SRN_EINVAL, "srn_device_sessions_sweep: null store");
     const uint64_t now = now_secs ? now_secs : wall_secs();
     std::lock_guard<std::mutex> g(s->mu);
-    int rc = own_after_last(s); if (rc) return rc;
-    if ((rc = rebuild(s, now))) return rc;
-    uint64_t occupied = 0, live = 0;
-    if ((rc = count(s, now, &occupied, &live))) return rc;
-    s->bound = occupied;
-    if (n_live) *n_live = occupied;
-    uint32_t err = 0;
-    HIP_TRY(hipMemcpy(&err, s->err(), 4, hipMemcpyDeviceToHost));
-    if (err) return fail(SRN_ESTATE, "device session store: a batch found the table full (the capacity rule was violated)");
-    return SRN_OK;
+    return sweep(s, now, [s](uint64_t at) { return rebuild(s, at); }, n_live);
 }
 
 int dsess_stats(srn_device_sessions* s, srn_device_sessions_stats_t* out) {
@@ -707,7 +625,7 @@ int dsess_recommend_device(const srn_index* idx, srn_device_sessions* s, const u
     const uint32_t hint = std::max<uint32_t>(s->len_bound, limit);          // the longest window the store may hold behind this call
     const uint32_t phint = H ? (uint32_t)max_items : hint;                  // ... and the longest session predict reads
     if (excl_seen && how_many + hint > SRN_MAX_HOW_MANY) return fail(SRN_ERANGE, "srn_recommend_batch: how_many + the store's longest window above SRN_MAX_HOW_MANY (SRN_FLAG_EXCLUDE_SEEN)");
-    int rc = make_room(s, n, now); if (rc) return rc;
+    int rc = room_for(s, n, now); if (rc) return rc;
     HIP_TRY(hipSetDevice(s->device));
     // scratch: sort keys and indices (double-buffered), the per-position and per-request words, the kept clicks, the CSR batch, rocPRIM's temporary storage
     size_t tmp = 0, t1 = 0;
@@ -846,14 +764,6 @@ int xs_ensure(srn_device_sessions* s, size_t bytes) {   // (the previous call ma
     HIP_TRY(hipEventSynchronize(s->last));
     return ensure(&s->xs, &s->xs_bytes, bytes);
 }
-struct DevBuf {   // a blocking call's own device copies
-    char* p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    int alloc(size_t bytes, const char* who) {
-        if (hipMalloc((void**)&p, bytes ? bytes : 256) != hipSuccess) { (void)hipGetLastError(); p = nullptr; return fail(SRN_ENOMEM, std::string(who) + ": no device memory for the staging copies"); }
-        return SRN_OK;
-    }
-};
 // offsets of the dense arrays of n entries in one buffer: key_hi | key_lo | epoch | len | items | (a u64 word)
 struct Dense { size_t hi, lo, ep, len, items, word, bytes; };
 Dense dense_layout(size_t n, size_t items_stride) {
@@ -893,7 +803,7 @@ int export_host_locked(srn_device_sessions* s, uint64_t now, size_t cap, uint64_
     if (live > cap) return fail(SRN_ERANGE, std::string(who) + ": more live sessions than the arrays hold (*n is their number)");
     if (live == 0) return SRN_OK;
     const Dense d = dense_layout(live, items_stride);
-    DevBuf b; if ((rc = b.alloc(d.bytes, who))) return rc;
+    StageBuf b; if ((rc = b.alloc(d.bytes, who))) return rc;
     rc = export_enqueue(s, now, live, (uint64_t*)(b.p + d.hi), (uint64_t*)(b.p + d.lo), (uint64_t*)(b.p + d.ep), (uint32_t*)(b.p + d.len), (uint64_t*)(b.p + d.items),
                         items_stride, (uint64_t*)(b.p + d.word), s->own);
     if (rc) { (void)hipStreamSynchronize(s->own); return rc; }
@@ -929,7 +839,7 @@ int import_locked(srn_device_sessions* s, const uint64_t* d_hi, const uint64_t* 
     if (longest > s->items_cap) return fail(SRN_ERANGE, std::string(who) + ": a session is longer than the store's items_cap");
     if (longest > items_stride) return fail(SRN_ERANGE, std::string(who) + ": a session is longer than items_stride");
     // every entry counts as a new key; an import reclaims nothing (now = 1: no entry is older than the TTL), so a refused import leaves every slot where it was
-    if ((rc = make_room(s, n, 1))) return rc;
+    if ((rc = room_for(s, n, 1))) return rc;
     HIP_TRY(hipSetDevice(s->device));
     KeySort ks{{(uint64_t*)(b + o_keyA), (uint64_t*)(b + o_keyB)}, {(uint32_t*)(b + o_idxA), (uint32_t*)(b + o_idxB)}, b + o_tmp, tmp, n, st};
     if ((rc = ks.begin(d_lo)) || (rc = ks.pass(KeyWord{d_hi}))) return rc;
@@ -1044,7 +954,7 @@ int dsess_import_host(srn_device_sessions* s, const uint64_t* hi, const uint64_t
     std::lock_guard<std::mutex> g(s->mu);
     int rc = own_after_last(s); if (rc) return rc;
     const Dense d = dense_layout(n, items_stride);
-    DevBuf b; if ((rc = b.alloc(d.bytes, who))) return rc;
+    StageBuf b; if ((rc = b.alloc(d.bytes, who))) return rc;
     hipError_t e = hipMemcpyAsync(b.p + d.hi, hi, n * 8, hipMemcpyHostToDevice, s->own);
     if (e == hipSuccess) e = hipMemcpyAsync(b.p + d.lo, lo, n * 8, hipMemcpyHostToDevice, s->own);
     if (e == hipSuccess) e = hipMemcpyAsync(b.p + d.ep, epoch, n * 8, hipMemcpyHostToDevice, s->own);

@@ -26,13 +26,13 @@
 
 #include "srn_internal.h"
 #include "srn_runtime.h"
-#include "srn_sessions_dev.h"
+#include "srn_sessions_dev.h"   // the store's handle over srn_visitor_table.h: Table, SlotHead, align256, grid_for
 #include "srn_hipsync.h"
 
 namespace srn {
 
 namespace {
-constexpr uint32_t kTPB = 256;
+constexpr uint32_t kTPB = kTableTPB;   // (grid_for)
 constexpr const char* kWho = "srn_device_sessions_top_items";
 
 struct TrendArgs {
@@ -113,16 +113,6 @@ __global__ void __launch_bounds__(kTPB) trend_cut(const uint32_t* __restrict__ c
     if (in && i < take) { out_ids[i] = ids[i]; out_cnt[i] = c; }
 }
 
-struct Scratch {   // the call's own device memory
-    char* p = nullptr;
-    ~Scratch() { if (p) (void)hipFree(p); }
-    int alloc(size_t bytes) {
-        if (hipMalloc((void**)&p, bytes ? bytes : 256) != hipSuccess) { (void)hipGetLastError(); p = nullptr; return fail(SRN_ENOMEM, std::string(kWho) + ": no device memory for the scratch"); }
-        return SRN_OK;
-    }
-};
-size_t align256(size_t b) { return (b + 255) / 256 * 256; }
-dim3 grid_for(size_t n) { return dim3((unsigned)((n + kTPB - 1) / kTPB)); }
 }  // namespace
 
 int dsess_device_of(const srn_device_sessions* s) { return s->device; }
@@ -144,7 +134,7 @@ int dsess_top_items(srn_device_sessions* s, uint64_t now_secs, uint64_t since_se
     size_t tmp_scan = 0;
     HIP_TRY(rocprim::exclusive_scan(nullptr, tmp_scan, (uint32_t*)nullptr, (uint64_t*)nullptr, (uint64_t)0, n1, rocprim::plus<uint64_t>(), st));
     const size_t o_pos = align256(n1 * 4), o_tmp = o_pos + align256(n1 * 8);
-    Scratch per_slot; if ((rc = per_slot.alloc(o_tmp + align256(tmp_scan)))) return rc;
+    StageBuf per_slot; if ((rc = per_slot.alloc(o_tmp + align256(tmp_scan), kWho, "the scratch"))) return rc;
     TrendArgs a{};
     a.t = s->tab(); a.now = now; a.ttl = s->ttl; a.since = since_secs;
     a.lanes_shift = s->stride == 128 ? 3 : 4;
@@ -167,7 +157,7 @@ int dsess_top_items(srn_device_sessions* s, uint64_t now_secs, uint64_t since_se
     HIP_TRY(rocprim::run_length_encode(nullptr, tmp_rle, (const uint64_t*)nullptr, T, (uint64_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, st));
     const size_t tmp1 = std::max(tmp_sort, tmp_rle);
     const size_t o_b = align256((size_t)T * 8), o_c = 2 * o_b, o_word = o_c + align256((size_t)T * 4), o_tmp1 = o_word + 256;
-    Scratch per_id; if ((rc = per_id.alloc(o_tmp1 + align256(tmp1)))) return rc;
+    StageBuf per_id; if ((rc = per_id.alloc(o_tmp1 + align256(tmp1), kWho, "the scratch"))) return rc;
     ids = rocprim::double_buffer<uint64_t>((uint64_t*)per_id.p, (uint64_t*)(per_id.p + o_b));
     uint32_t* run_cnt = (uint32_t*)(per_id.p + o_c);
     uint32_t* d_runs = (uint32_t*)(per_id.p + o_word);
@@ -190,7 +180,7 @@ int dsess_top_items(srn_device_sessions* s, uint64_t now_secs, uint64_t since_se
     size_t tmp2 = 0;
     HIP_TRY(rocprim::radix_sort_pairs_desc(nullptr, tmp2, keys, vals, R, 0, 32, st));
     const size_t o_oid = align256((size_t)R * 4), o_ocnt = o_oid + align256(take * 8), o_tmp2 = o_ocnt + align256(take * 4);
-    Scratch per_run; if ((rc = per_run.alloc(o_tmp2 + align256(tmp2)))) return rc;
+    StageBuf per_run; if ((rc = per_run.alloc(o_tmp2 + align256(tmp2), kWho, "the scratch"))) return rc;
     keys = rocprim::double_buffer<uint32_t>(run_cnt, (uint32_t*)per_run.p);
     HIP_TRY(rocprim::radix_sort_pairs_desc(per_run.p + o_tmp2, tmp2, keys, vals, R, 0, 32, st));
     uint64_t* d_oid = (uint64_t*)(per_run.p + o_oid); uint32_t* d_ocnt = (uint32_t*)(per_run.p + o_ocnt);

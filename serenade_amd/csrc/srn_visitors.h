@@ -1,6 +1,6 @@
-// What the tables keyed by visitor share (srn_sessions_dev.hip, srn_feedback.hip, srn_harvest.hip): the key's hash, the run predicates over a batch sorted by visitor,
-// the find-or-claim probe of a batch's run heads, and the stable sort of 128-bit keys that makes the runs.  No relocatable device code: every kernel here is a
-// template, every function inline.
+// What a batch against a table keyed by visitor needs (srn_sessions_dev.hip, srn_feedback.hip, srn_harvest.hip): the run predicates over a batch sorted by visitor,
+// the find-or-claim probe of a batch's run heads, and the stable sort of 128-bit keys that makes the runs.  The table and its capacity rule are
+// srn_visitor_table.h's.  No relocatable device code: every kernel here is a template, every function inline.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -11,11 +11,9 @@
 #include "srn_internal.h"
 #include "srn_runtime.h"
 #include "srn_device.h"
-#include "srn_sessions_dev.h"
+#include "srn_visitor_table.h"   // the table itself: SlotHead, Table, the slot states, key_hash
 
 namespace srn {
-
-__device__ __forceinline__ uint32_t key_hash(uint64_t hi, uint64_t lo) { return (uint32_t)dev_mix64(lo ^ dev_mix64(hi)); }
 
 // ---- runs: a batch sorted by (no consent, key_hi, key_lo) holds the consenting requests of one visitor as one contiguous run, in request order ----
 // A: a kernel's arguments with order[n] (request index of each sorted position), consent (null: every request consents), key_hi, key_lo and n
@@ -40,8 +38,8 @@ template <class A> __device__ __forceinline__ bool run_head(const A& a, uint32_t
 template <class A> __device__ __forceinline__ bool run_last(const A& a, uint32_t p, uint32_t req) { return p + 1 >= a.n || !same_visitor(a, a.order[p + 1], req); }
 
 // ---- find-or-claim: one lane per run head of a batch ----
-// Both tables' slots begin { key_hi u64 | key_lo u64 | epoch u64 | u32 | state u32 } (SlotHead; srn_feedback.hip asserts it of its own), so the probe reads them as
-// SlotHead.  The claim protocol: CAS empty -> claimed.  Two heads never hold the same key, so a slot claimed during the kernel belongs to another key and the loser
+// Both tables' slots begin { key_hi u64 | key_lo u64 | epoch u64 | u32 | state u32 } (SlotHead; table_rebuild asserts it of every owner's slot), so the probe reads
+// them as SlotHead.  The claim protocol: CAS empty -> claimed.  Two heads never hold the same key, so a slot claimed during the kernel belongs to another key and the loser
 // of a claim probes on: nobody waits for anybody.  A slot in state kFull was complete before the kernel began and its key can be compared.
 // -> the slot, and whether it was claimed here (the caller writes the key and its own fields; state stays kClaimed until the call's store kernel) or found kFull (the
 // caller reads it); slot kNone: the table is full -- cannot happen under the capacity rule.

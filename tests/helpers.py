@@ -113,6 +113,47 @@ def random_queries(seed, ids, n, max_len=6, unknown_rate=0.05, dup_rate=0.2):
     return qs
 
 
+def capacity_rule_sequence(table, capacity, t, ttl):
+    """The capacity rule on a device table keyed by visitor -- the session store or the click feedback log -- at a capacity small enough that probes
+    wrap the table's end and the automatic sweep rebuilds a table at load 0.5.  `table` adapts the object and its dictionary model:
+      call(keys, now)   one batch, a request per key, on the object and -- unless the object refuses it, which raises -- on the model
+      stats()           the object's stats dict ("live_bound", "sweeps", "refused" among its words)
+      sweep(now)        the object's explicit sweep -> what it returns
+      expire(now)       the model forgets what a sweep at `now` drops
+      check(keys)       every key's stored entry, read back, equals the model's (no entry where the model has none)"""
+    from serenade_amd import capi
+    keys = [((7 + j) << 64) | (1000003 * j + 1) for j in range(capacity)]
+    extra = (5 << 64) | 99
+    # 1. as many distinct visitors as the capacity
+    table.call(keys, t)
+    before = table.stats()
+    assert (before["live_bound"], before["sweeps"], before["refused"]) == (capacity, 0, 0), before
+    table.check(keys + [extra])
+    # 2. one more, while every entry is younger than the TTL: refused, and nothing but `refused` has changed
+    try:
+        table.call([extra], t)
+        raise AssertionError("a visitor beyond the capacity was accepted")
+    except capi.SerenadeError as e:
+        assert e.code == capi.SRN_ENOMEM, e
+    after = table.stats()
+    assert after["refused"] == 1 and {k: v for k, v in after.items() if k != "refused"} == {k: v for k, v in before.items() if k != "refused"}, (before, after)
+    table.check(keys + [extra])
+    # 3. the same call once the entries are older than the TTL: one automatic sweep drops them all and the bound is the batch
+    later = t + ttl + 1
+    table.expire(later)
+    table.call([extra], later)
+    st = table.stats()
+    assert (st["live_bound"], st["sweeps"], st["refused"]) == (1, 1, 1), st
+    table.check(keys + [extra])
+    # 4. an explicit sweep returns the occupied count
+    assert table.sweep(later) == 1
+    st = table.stats()
+    assert (st["live_bound"], st["sweeps"], st["refused"]) == (1, 2, 1), st
+    # 5. every key against the model
+    table.check(keys + [extra])
+    return keys, extra
+
+
 def big_config_unavailable(config, why):
     """A BASELINE config that cannot run at full size on this box must not vanish quietly: the test FAILS (the driver then reports the config as
     untested) unless SRN_ALLOW_SKIP_BIG=1 says the smaller box is intended."""

@@ -270,10 +270,53 @@ def test_idle_and_ttl_clocks_of_the_device_store(small):
     d.close()
 
 
-def test_capacity_rule(small):
+class StoreTable:
+    """helpers.capacity_rule_sequence's view of a DeviceSessionStore and the handler's Model: a request per key through recommend_batch, the rows not looked at"""
+
+    def __init__(self, gix, ids, store):
+        self.gix, self.ids, self.store, self.model = gix, ids, store, Model()
+
+    def call(self, keys, now):
+        items = [int(self.ids[j % 90]) for j in range(len(keys))]
+        run(self.gix, self.store, keys, items, None, now, 2, "device")   # (a refusal raises here: the model stays as it was)
+        for k_, i in zip(keys, items):
+            self.model.serve(k_, i, True, now, 2)
+
+    def stats(self):
+        return self.store.stats
+
+    def sweep(self, now):
+        return self.store.sweep(now=now)
+
+    def expire(self, now):
+        self.model.s = {k_: (sess, t) for k_, (sess, t) in self.model.s.items() if not (now > t and now - t > 1800)}
+
+    def check(self, keys):
+        for k_ in keys:   # now = 1: whatever is stored, idle or not
+            assert self.store.get_session_items(k_, now=1) == self.model.s.get(k_, ([], 0))[0], k_
+
+
+@pytest.mark.parametrize("capacity", [1, 2, 3, 33, 1000])
+def test_capacity_rule(small, capacity):
+    from helpers import capacity_rule_sequence
     from serenade_amd import SerenadeError
     from serenade_amd.serving import DeviceSessionStore
     gix, oix, ids = small
+    if capacity != 1000:   # the rule at its smallest tables: 2, 4, 8 and 128 slots
+        store = DeviceSessionStore(gix, capacity=capacity, items_cap=4, ttl_secs=1800, idle_secs=1200)
+        assert store.stats["slots"] == {1: 2, 2: 4, 3: 8, 33: 128}[capacity]
+        keys, extra = capacity_rule_sequence(StoreTable(gix, ids, store), capacity, 100_000, 1800)
+        store.close()
+        # with growth allowed, the visitor beyond the capacity makes the store grow instead: nothing is refused and nothing is lost
+        store = DeviceSessionStore(gix, capacity=capacity, items_cap=4, ttl_secs=1800, idle_secs=1200, max_capacity=4 * capacity)
+        table = StoreTable(gix, ids, store)
+        table.call(keys, 100_000)
+        table.call([extra], 100_000)
+        st = store.stats
+        assert store.growth()["grows"] == 1 and (st["refused"], st["sweeps"], st["live_bound"]) == (0, 0, capacity + 1), (st, store.growth())
+        table.check(keys + [extra])
+        store.close()
+        return
     store = DeviceSessionStore(gix, capacity=1000, items_cap=4, ttl_secs=1800, idle_secs=1200)
     model, now = Model(), 100_000
     first = [(1 << 64) | i for i in range(600)]

@@ -215,7 +215,41 @@ def test_rows_narrower_than_the_log():
     fb.close()
 
 
-def test_capacity_rule_refusal_and_sweeps():
+class LogTable:
+    """helpers.capacity_rule_sequence's view of a ClickFeedback and feedback_model's state: a request per key, rows of 4"""
+
+    def __init__(self, fb):
+        self.fb, self.state, self.total = fb, {}, {}
+
+    def call(self, keys, now):
+        s = make_stream(len(keys), keys, 4)
+        got = observe(self.fb, s, 0, len(keys), now)          # (a refusal raises here: the model stays as it was)
+        want, ctr = model(self.state, s, 0, len(keys), now, 4)
+        assert np.array_equal(got, want)
+        add(self.total, ctr)
+
+    def stats(self):
+        return check_log(self.fb, self.state, self.total)
+
+    def sweep(self, now):
+        return self.fb.sweep(now)
+
+    def expire(self, now):
+        self.state = {k: e for k, e in self.state.items() if not (now > e[2] and now - e[2] > TTL)}
+
+    def check(self, keys):
+        check_log(self.fb, self.state, self.total, keys)
+
+
+@pytest.mark.parametrize("capacity", [1, 2, 3, 33, 64])
+def test_capacity_rule_refusal_and_sweeps(capacity):
+    if capacity != 64:   # the rule at its smallest tables: 2, 4, 8 and 128 slots
+        from helpers import capacity_rule_sequence
+        fb = ClickFeedback(0, capacity=capacity, row_cap=4, ttl_secs=TTL, idle_secs=IDLE)
+        assert fb.stats()["slots"] == {1: 2, 2: 4, 3: 8, 33: 128}[capacity]
+        capacity_rule_sequence(LogTable(fb), capacity, NOW, TTL)
+        fb.close()
+        return
     T0 = NOW
     ks = [(int(h) << 64) | 5 for h in range(1, 66)]
     s = make_stream(11, ks, 4)

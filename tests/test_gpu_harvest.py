@@ -121,7 +121,7 @@ def test_an_attached_harvest_changes_nothing_served(index, history):
         a, b = served(index, history, parts, True), served(index, history, parts, False)
         for x, y in zip(a["rows"], b["rows"]):
             assert x.tobytes() == y.tobytes()
-        # the store's export is in slot order, and where two colliding keys land is decided by the claim races of sess_find and sess_rebuild: two stores
+        # the store's export is in slot order, and where two colliding keys land is decided by the claim races of sess_find and table_rebuild: two stores
         # driven alike hold the same entries, not always in the same slots.  The entries are therefore compared in key order, every array exactly
         assert export_bytes(by_key(a["store"])) == export_bytes(by_key(b["store"])) and len(a["store"][1]) > 0
         assert a["sweeps"] == b["sweeps"]

@@ -146,7 +146,11 @@ def main():
                 hi, lo = keysets[rep % 2 if mode == "tenth_returns" else 0]
                 it = t_its[rep % len(t_its)]
                 stream = torch.cuda.current_stream(0).cuda_stream
-                tp = timed(lambda: parent.recommend(p_index, p_store, hi, lo, it, now, max_items, k, m, how_many, p_out, stream))[1] if parent else None
+                def parent_call():   # (recommend_batch hands out cleared rows: the fills belong to both arms' time, and a row's tail beyond its count must not be the previous call's)
+                    for o in p_out:
+                        o.zero_()
+                    parent.recommend(p_index, p_store, hi, lo, it, now, max_items, k, m, how_many, p_out, stream)
+                tp = timed(parent_call)[1] if parent else None
                 (ids, cnt, sc), td = timed(lambda: recommend_batch(index, stores[0], (hi, lo), it, now=now, **kw))
                 (ids2, cnt2, sc2), ta = timed(lambda: recommend_batch(index, stores[1], (hi, lo), it, now=now, **kw))
                 if not (torch.equal(ids, ids2) and torch.equal(cnt, cnt2) and torch.equal(sc, sc2)):
