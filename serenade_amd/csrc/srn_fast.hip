@@ -95,8 +95,12 @@ enum { FP_REC = 10000000, FP_FRONT = 1000000, FP_CUT = 100000, FP_REQ = 10000, F
 #ifndef SRN_FAST_STOP
 #define SRN_FAST_STOP (-1)   // experiments only (tools/fast_phase_insts.sh): every query leaves after phase tick N, to count instructions per phase
 #endif
+// (SRN_FAST_TICK_TID: the thread that keeps the phase clock -- 0, or 64 in a variant build to see the phases as wave 1 does, the wave that fetches the next record)
+#ifndef SRN_FAST_TICK_TID
+#define SRN_FAST_TICK_TID 0
+#endif
 #define FAST_TICK(ph) \
-    do { if (ticking && tid == 0) { const long long t_ = clock64(); tacc[ph] += (unsigned long long)(t_ - t_prev); t_prev = t_; } } while (0); \
+    do { if (ticking && tid == (SRN_FAST_TICK_TID)) { const long long t_ = clock64(); tacc[ph] += (unsigned long long)(t_ - t_prev); t_prev = t_; } } while (0); \
     if (SRN_FAST_STOP == (ph)) continue
 
 // -------------------------------------------------------------------------------------
@@ -224,6 +228,17 @@ typedef __attribute__((address_space(3))) uint32_t lds_u32;
 __device__ __forceinline__ uint32_t lds_addr(const uint32_t* p) { return (uint32_t)(uintptr_t)(const lds_u32*)p; }
 __device__ __forceinline__ uint32_t lds_ld(uint32_t a) { return *(const lds_u32*)(uintptr_t)a; }
 __device__ __forceinline__ void lds_st(uint32_t a, uint32_t v) { *(lds_u32*)(uintptr_t)a = v; }
+// One dword per lane from global memory straight into LDS at dst + 4 lane (dst: a wave-uniform LDS byte address, handed over in M0), written as assembly so that the
+// compiler does NOT count it.  The builtin (__builtin_amdgcn_global_load_lds) is a pending LDS write on the VM counter to the compiler: until it has waited for it, every
+// DS instruction that may alias it, every use of an ordinary load's result and every __syncthreads() gets s_waitcnt vmcnt(0) -- a wave that parks the next query's record
+// with the builtin sits out the record's HBM round trip at its next ds_add (profiles/record_prefetch_ab.txt).  Whoever issues this waits for it with an explicit
+// s_waitcnt vmcnt(0), and a barrier stands between that wait and the first read.  The hardware's counter does hold it: a compiler-made vmcnt(N) of the same wave is
+// stricter by the dwords in flight, never laxer -- so it is issued BEHIND the wave's own loads (loads return in order), where it delays only the last of their waits.
+// (The builtin moved to a span without loads -- behind the stage -- still drained at the span's first __syncthreads(): its use would need a raw s_barrier at ~15 sites.)
+__device__ __forceinline__ void glds_dword_uncounted(const void* g, uint32_t dst) {
+    uint32_t keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0" : "=&s"(keep) : "v"(g), "s"(dst) : "memory");
+}
 __device__ __forceinline__ void merge_pair(const uint32_t* in, uint32_t* out, uint32_t sa, uint32_t la, uint32_t lb, uint32_t ttid, uint32_t lg_nthr) {
     if ((ttid >> lg_nthr) != 0u) return;   // (whole waves)
 #ifndef SRN_MERGE_ODD
@@ -477,10 +492,17 @@ __global__ __launch_bounds__(512, TINY ? SRN_TINY_WAVES : BIG ? 4 : SRN_FAST_WAV
     const uint32_t n_kept = ix.n_kept;
     auto qpos = [&](uint32_t pq) -> uint32_t { return ((wave + NW * (pq >> 6)) << 6) + (pq & 63u); };   // the wave's own neighbour-list slots
 
-    // The NEXT query's record is fetched during this one (wave 1, between walk A and the end of phase 4a) and parked in LDS: a query's critical path then starts
-    // with the list loads, not with the record's HBM round trip followed by theirs.  The record's first 256 bytes go from global memory STRAIGHT into LDS
-    // (global_load_lds: one dword per lane, no registers held): words 0..17 = PrepHead, words 18 + 6 l .. = item l.  (The 448 bytes behind the 16 entries
-    // the weight table uses are free.)
+    // The NEXT query's record is fetched during this one by wave 1 and parked in LDS: a query's critical path then starts with the list loads, not with the record's
+    // HBM round trip followed by theirs.  The record goes from global memory STRAIGHT into LDS (global_load_lds, one dword per lane, no registers held; uncounted by
+    // the compiler: glds_dword_uncounted above): words 0..17 = PrepHead, words 18 + 6 l .. = item l.  (The 448 bytes behind the 16 entries the weight table uses are free.)
+    // WHEN: in walk A, behind wave 1's own row requests; the wave waits for it (an explicit s_waitcnt vmcnt(0): the compiler knows of no load) at the end of phase 4a,
+    // and the barrier behind that wait publishes it.  A query that leaves before walk A (no known item, not admitted, handed on) parks nothing: its successor reads its
+    // record from global memory.
+    // (measured, NOT kept: a lean query of >= 2 lists requesting it behind its FIRST barrier instead, once its posting lists are in -- the stage, the merge tree and the
+    //  cuts touch LDS only, ~8.5 K cycles without a vector-memory instruction -- and waiting in front of the row requests, so that walk A has no record in it at all:
+    //  18.844 ms against this placement's 18.686, parent 18.917; built from one source, 18.843 early against 18.820 in walk A, parent 18.890 (medians of three,
+    //  profiles/record_prefetch_ab.txt).  With the phase clock on wave 1 the record costs that wave ~680 cycles of walk A, and the wave still stands 690 cycles at
+    //  walk A's closing barrier: it is not the wave the others wait for.)
     uint32_t* const pre = (uint32_t*)(smem + F_W10 + 64);
     bool have_pre = false;   // block-uniform
     { const ItemMeta m0 = f.meta_sample[tid];
@@ -990,6 +1012,9 @@ __global__ __launch_bounds__(512, TINY ? SRN_TINY_WAVES : BIG ? 4 : SRN_FAST_WAV
 #ifdef SRN_FAST_SUBTICKS
         FAST_TICK(5);   // (wave 0 has its rows' first 16 bytes)
 #endif
+        uint32_t wr[3];   // the rows' weights, looked up ahead of the requests below
+#pragma unroll
+        for (int t = 0; t < 3; ++t) wr[t] = LONG ? wvr[t] : w10_of(svr[t] & NBM);
         // The second 16 bytes (items 6..13) are asked for only now, and only by the rows that have them (1 in 4): the other lanes all read the empty
         // slot's -- one line for the lot -- so the address unit sees a quarter of the requests; the lines themselves came with the first 16 bytes.
         if constexpr (!FRAG) {
@@ -1016,35 +1041,49 @@ __global__ __launch_bounds__(512, TINY ? SRN_TINY_WAVES : BIG ? 4 : SRN_FAST_WAV
                 c4 = eb[0]; d4 = eb[1]; blk = s4.w + 2u;
             } else {
                 const RowQuad* rowp = f.row_packed + (size_t)(base + (sv >> NB)) * 4;
-                hdr = *reinterpret_cast<const uint32_t*>(rowp); c4 = *reinterpret_cast<const uint4*>(rowp + 2); d4 = *reinterpret_cast<const uint4*>(rowp + 3); blk = d4.w;
+                hdr = *reinterpret_cast<const uint32_t*>(rowp); c4 = *reinterpret_cast<const uint4*>(rowp + 2); d4 = *reinterpret_cast<const uint4*>(rowp + 3); blk = 0u;   // (the caller takes d4.w when it gets to the overflow blocks: a copy here is a wait for the load here)
             } };
         uint32_t tk3 = 0, sv3 = 0, hdr3 = 0, blk3 = 0; uint4 c43 = make_uint4(0u, 0u, 0u, 0u), d43 = c43;
         if (cnt3) q3_load(0u, tk3, sv3, hdr3, c43, d43, blk3);   // (wave-uniform)
-        // the next query's record: requested by wave 1 HERE -- behind its own row requests, with no other load of the wave due for thousands of cycles (loads return
-        // in order: anywhere else the record's HBM round trip would sit in front of data the wave needs at once); it lands in LDS by itself, the wave
-        // waits for it at the end of phase 4a, before the barrier that everybody passes on the way to the next query
+        const uint32_t w3 = cnt3 ? tok_w(tk3, sv3) : 0u;   // (its weight now, with the queue's read: looked up in front of its adds the read came back behind the 42 adds of round (i))
+        // the next query's record: requested by wave 1 HERE -- behind its own row requests (loads return in order: in front of them the record's HBM round trip would sit
+        // before data the wave needs at once).  The hardware counts it and the compiler does not (glds_dword_uncounted): the waits below stay counted for every wave, wave
+        // 1's are stricter by two, and only the wait for its LAST tail load sits the record out -- which that wave can afford (see `pre`).  It lands in LDS by itself; the
+        // wave waits for it at the end of phase 4a, before the barrier that everybody passes on the way to the next query
         const uint32_t qn = MID ? q_after : ordered || listed ? q_ord_next : q + gridDim.x;
         const bool park = MID ? q_after != 0xFFFFFFFFu : ordered || listed ? q_ord_next != 0xFFFFFFFFu : qn < p.nq;   // (block-uniform)
         if (wave == 1u && park) {   // (a record is at most 72 + 8 * 24 = 264 bytes -- MID: 72 + 10 * 24 = 312 --: two rounds of a dword per lane)
             const char* const rn = p.prep + (size_t)qn * p.prep_stride + lane * 4u;
-            if (lane * 4u < p.prep_stride) __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)rn, (__attribute__((address_space(3))) void*)pre, 4, 0, 0);
-            if (256u + lane * 4u < min(p.prep_stride, 320u)) __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(rn + 256), (__attribute__((address_space(3))) void*)(pre + 64), 4, 0, 0);
+            const uint32_t dst = (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_addr(pre));
+            if (lane * 4u < p.prep_stride) glds_dword_uncounted(rn, dst);
+            if (256u + lane * 4u < min(p.prep_stride, 320u)) glds_dword_uncounted(rn + 256, dst + 256u);
         }
+        // Round (i) in two passes, so that it runs under the loads it was written to hide: first the 18 adds of items 0..5 of the wave's three rows -- their quads are in
+        // registers since the queue was built --, then items 6..13, each row behind a COUNTED wait for its own second 16 bytes.  (One pass, row by row, put the wait for
+        // row 0's second 16 bytes in front of rows 1 and 2's first adds.)  The three weights were looked up ahead of the requests: a look-up inside a row's branch made the
+        // branch end in s_waitcnt lgkmcnt(0) -- the wave drained its own adds before it started the next row.  (Integer adds into LDS words: the order changes no sum.)
 #pragma unroll
-        for (int t = 0; t < 3; ++t) {   // (i) items 0..13
+        for (int t = 0; t < 3; ++t) {   // (i) items 0..5
             if (wave * 64u + (uint32_t)t * BLOCK < K) {
                 const bool act = wave * 64u + lane + (uint32_t)t * BLOCK < K;
-                const uint32_t w = LONG ? wvr[t] : w10_of(svr[t] & NBM), len = rq[t].x & 0xFFFFu;
+                const uint32_t w = wr[t], len = rq[t].x & 0xFFFFu;
                 if constexpr (FRAG) { if (act) { add2(rq[t].y, w); add2(rq[t].z, w); if (len <= 6u) add2(rq[t].w, w); } }
-                else {
-                if (act) { add2(rq[t].y, w); add2(rq[t].z, w); add2(rq[t].w, w); }
-                if (act && len > 6u) { add2(rq1[t].x, w); add2(rq1[t].y, w); add2(rq1[t].z, w); add2(rq1[t].w, w); }
-                }
+                else if (act) { add2(rq[t].y, w); add2(rq[t].z, w); add2(rq[t].w, w); }
             }
         }
-        auto add_tail = [&](uint32_t p0, uint32_t tok, uint32_t sv, uint32_t hdr, const uint4& c4, const uint4& d4, uint32_t blk) {   // items 14..29 (FRAG: 4..19), then the overflow blocks
+        if constexpr (!FRAG) {
+#pragma unroll
+        for (int t = 0; t < 3; ++t) {   // (i) items 6..13
+            if (wave * 64u + (uint32_t)t * BLOCK < K) {
+                const bool act = wave * 64u + lane + (uint32_t)t * BLOCK < K;
+                const uint32_t w = wr[t], len = rq[t].x & 0xFFFFu;
+                if (act && len > 6u) { add2(rq1[t].x, w); add2(rq1[t].y, w); add2(rq1[t].z, w); add2(rq1[t].w, w); }
+            }
+        }
+        }
+        auto add_tail = [&](uint32_t p0, uint32_t w, uint32_t hdr, const uint4& c4, const uint4& d4, uint32_t blk) {   // items 14..29 (FRAG: 4..19), then the overflow blocks
             const bool act = p0 + lane < cnt3;
-            const uint32_t len = hdr & 0xFFFFu, w = tok_w(tok, sv);
+            const uint32_t len = hdr & 0xFFFFu;
             const bool more = FRAG ? true : len > 30u;   // (a slot without overflow blocks keeps items in the words the others use for the block index)
             if constexpr (FRAG) {
                 if (act) { add2(c4.x, w); add2(c4.y, w); add2(c4.z, w); add2(c4.w, w); }
@@ -1064,8 +1103,14 @@ __global__ __launch_bounds__(512, TINY ? SRN_TINY_WAVES : BIG ? 4 : SRN_FAST_WAV
         FAST_TICK(6);   // (round (i): second 16 bytes + adds issued)
 #endif
         FAST_PRIO_X(1);
-        if (cnt3) add_tail(0u, tk3, sv3, hdr3, c43, d43, blk3);
-        for (uint32_t p0 = 64u; p0 < cnt3; p0 += 64u) { uint32_t tk, sv, hdr, blk; uint4 c4, d4; q3_load(p0, tk, sv, hdr, c4, d4, blk); add_tail(p0, tk, sv, hdr, c4, d4, blk); }
+        // (the tail's header and the word that is item 28-29 or the block index stay as they were loaded until HERE: consumed at the request -- their registers were
+        //  wanted -- they put the waits for the tail's loads in front of round (i))
+        { fin_v4u dv = {d43.x, d43.y, d43.z, d43.w};   // (the whole quad as ONE operand: named alone, its last word was still copied out of the tuple at the request)
+          asm volatile("" : "+v"(hdr3), "+v"(dv));
+          d43 = make_uint4(dv.x, dv.y, dv.z, dv.w); }
+        if constexpr (!FRAG) blk3 = d43.w;
+        if (cnt3) add_tail(0u, w3, hdr3, c43, d43, blk3);
+        for (uint32_t p0 = 64u; p0 < cnt3; p0 += 64u) { uint32_t tk, sv, hdr, blk; uint4 c4, d4; q3_load(p0, tk, sv, hdr, c4, d4, blk); if constexpr (!FRAG) blk = d4.w; add_tail(p0, tok_w(tk, sv), hdr, c4, d4, blk); }
 #ifdef SRN_FAST_SUBTICKS
         FAST_TICK(7);   // (wave 0's tail rounds done; what follows is the wait for the other waves)
 #endif
@@ -1182,7 +1227,7 @@ __global__ __launch_bounds__(512, TINY ? SRN_TINY_WAVES : BIG ? 4 : SRN_FAST_WAV
                 floor_b = (uint32_t)fmin(4.0e9, fmax(1.0, floor(x_lo * ((const double*)(smem + SINV))[8] * (1.0 - 1e-9)) - 1.0));
             }
         }
-        if (wave == 1u) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the record has landed
+        if (wave == 1u) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the record has landed (the compiler knows of no load to wait for here: this IS the wait)
         FAST_TICK(10);
         FAST_PRIO(FP_WB);
         {
@@ -1250,6 +1295,7 @@ __global__ __launch_bounds__(512, TINY ? SRN_TINY_WAVES : BIG ? 4 : SRN_FAST_WAV
             }
 #endif
             if (cnt3) q3_load(0u, tk3b, sv3b, hdr3b, c43b, d43b, blk3b);   // requested before round (i)
+            if constexpr (!FRAG) blk3b = d43b.w;
 #pragma unroll
             for (int t = 0; t < 3; ++t) {   // (i) from the registers
                 if (wave * 64u + (uint32_t)t * BLOCK < K) {
@@ -1306,7 +1352,7 @@ __global__ __launch_bounds__(512, TINY ? SRN_TINY_WAVES : BIG ? 4 : SRN_FAST_WAV
                     list_hits(hm2, 8u, sv, t8);   // (rows of > 30 items are few: no fast path)
                 } };
             if (cnt3) chk_tail(0u, tk3b, hdr3b, c43b, d43b, blk3b);
-            for (uint32_t p0 = 64u; p0 < cnt3; p0 += 64u) { uint32_t tk, sv, hdr, blk; uint4 c4, d4; q3_load(p0, tk, sv, hdr, c4, d4, blk); chk_tail(p0, tk, hdr, c4, d4, blk); }
+            for (uint32_t p0 = 64u; p0 < cnt3; p0 += 64u) { uint32_t tk, sv, hdr, blk; uint4 c4, d4; q3_load(p0, tk, sv, hdr, c4, d4, blk); if constexpr (!FRAG) blk = d4.w; chk_tail(p0, tk, hdr, c4, d4, blk); }
             if (ticking) { const uint32_t hs = wave_sum(dbg_hits); if (lane == 0u && hs) atomicAdd(&tacc[5], (unsigned long long)hs); }
         }
         __syncthreads();
