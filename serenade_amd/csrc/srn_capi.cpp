@@ -34,6 +34,25 @@ static int check_not_a_shard(const srn_index_t* idx) {
     return idx && idx->flat.n_shards > 1 ? fail(SRN_EINVAL, "this index is one item shard of several: predictions go through its shard group (srn_shard_group_predict_batch)") : SRN_OK;
 }
 
+// a host batch's sessions: *max_len = the longest, or the first offence
+int scan_q_off(const uint32_t* q_off, size_t nq, uint32_t* max_len) {
+    uint32_t longest = 0;
+    for (size_t q = 0; q < nq; ++q) {
+        if (q_off[q + 1] < q_off[q]) return fail(SRN_EINVAL, "q_off not monotone");
+        if (q_off[q + 1] == q_off[q]) return fail(SRN_EINVAL, "empty evolving session (the reference panics: src/vmisknn/mod.rs:157)");
+        longest = std::max(longest, q_off[q + 1] - q_off[q]);
+    }
+    if (longest > SRN_MAX_SESSION_LEN) return fail(SRN_ERANGE, "evolving session longer than SRN_MAX_SESSION_LEN");
+    *max_len = longest;
+    return SRN_OK;
+}
+// the tail every index constructor shares: attach to the device (device < 0: a host-only index), hand the handle out or drop it
+int finish_index(srn_index* ix, int rc, int device, srn_index_t** out) {
+    if (rc == SRN_OK && device >= 0) { ix->dev = device_attach(ix->flat, device); ix->device = device; if (!ix->dev) rc = SRN_EHIP; else ix->comb = combiner_create(); }
+    if (rc) { delete ix; return rc; }
+    *out = ix; return SRN_OK;
+}
+
 int predict_host(const srn_index_t* idx, const uint64_t* items_flat, const uint32_t* q_off, size_t nq, size_t k, size_t m,
                  size_t how_many, unsigned flags, uint64_t* out_ids, double* out_scores, uint32_t* out_counts,
                  uint32_t* out_stats, uint32_t* out_nb_sessions, uint32_t* out_nb_num, uint32_t* out_nb_counts) {
@@ -45,20 +64,11 @@ int predict_host(const srn_index_t* idx, const uint64_t* items_flat, const uint3
     if ((out_nb_sessions != nullptr) != (out_nb_num != nullptr) || (out_nb_sessions != nullptr) != (out_nb_counts != nullptr))
         return fail(SRN_EINVAL, "neighbour debug outputs must be given together");
     uint32_t max_len = 0;
-    for (size_t q = 0; q < nq; ++q) {
-        if (q_off[q + 1] < q_off[q]) return fail(SRN_EINVAL, "q_off not monotone");
-        const uint32_t len = q_off[q + 1] - q_off[q];
-        if (len == 0) return fail(SRN_EINVAL, "empty evolving session (the reference panics: src/vmisknn/mod.rs:157)");
-        max_len = std::max(max_len, len);
-    }
-    if (max_len > SRN_MAX_SESSION_LEN) return fail(SRN_ERANGE, "evolving session longer than SRN_MAX_SESSION_LEN");
-    LaunchParams p{};
-    p.nq = (uint32_t)nq; p.k = (uint32_t)k; p.m = (uint32_t)m; p.how_many = (uint32_t)how_many; p.flags = flags; p.max_len = max_len;
-    rc = device_predict(idx->dev, idx->flat, p, false, nullptr, items_flat, q_off, out_ids, out_scores, out_counts, out_stats,
-                        out_nb_sessions, out_nb_num, out_nb_counts);
+    rc = scan_q_off(q_off, nq, &max_len); if (rc) return rc;
+    rc = device_predict_host(idx->dev, idx->flat, launch_params(nq, k, m, how_many, flags, max_len),
+                             HostRows{items_flat, q_off, out_ids, out_scores, out_counts, out_stats, out_nb_sessions, out_nb_num, out_nb_counts});
     if (rc) return rc;
-    for (size_t q = 0; q < nq; ++q)
-        if (out_counts[q] == 0xFFFFFFFFu) return fail(SRN_ERANGE, "a query exceeded the kernel's table limits");
+    rc = check_all_served(out_counts, nq); if (rc) return rc;
     if (out_nb_sessions)   // recency rank -> reference session index
         for (size_t q = 0; q < nq; ++q)
             for (uint32_t j = 0; j < out_nb_counts[q]; ++j) {
@@ -169,10 +179,7 @@ int srn_index_build(const srn_sessions_view_t* sessions, size_t m_index, size_t 
         if (!sessions || !out) return fail(SRN_EINVAL, "null argument");
         *out = nullptr;
         srn_index* ix = new srn_index();
-        int rc = build_flat_index(*sessions, m_index, max_session_len, idf_weighting, 0, 1, ix->flat);
-        if (rc == SRN_OK && device >= 0) { ix->dev = device_attach(ix->flat, device); ix->device = device; if (!ix->dev) rc = SRN_EHIP; else ix->comb = combiner_create(); }
-        if (rc) { delete ix; return rc; }
-        *out = ix; return SRN_OK; });
+        return finish_index(ix, build_flat_index(*sessions, m_index, max_session_len, idf_weighting, 0, 1, ix->flat), device, out); });
 }
 
 int srn_index_build_gpu(const srn_sessions_view_t* sessions, size_t m_index, size_t max_session_len, double idf_weighting,
@@ -182,10 +189,7 @@ int srn_index_build_gpu(const srn_sessions_view_t* sessions, size_t m_index, siz
         if (device < 0) return fail(SRN_ENODEV, "the GPU index builder needs a device");
         *out = nullptr;
         srn_index* ix = new srn_index();
-        int rc = build_flat_index_gpu(*sessions, m_index, max_session_len, idf_weighting, device, ix->flat);
-        if (rc == SRN_OK) { ix->dev = device_attach(ix->flat, device); ix->device = device; if (!ix->dev) rc = SRN_EHIP; else ix->comb = combiner_create(); }
-        if (rc) { delete ix; return rc; }
-        *out = ix; return SRN_OK; });
+        return finish_index(ix, build_flat_index_gpu(*sessions, m_index, max_session_len, idf_weighting, device, ix->flat), device, out); });   // (device >= 0: checked above)
 }
 
 int srn_index_new_from_csv(const char* path, size_t m_most_recent_sessions, double idf_weighting, size_t max_session_len,
@@ -221,10 +225,7 @@ int srn_index_new_from_avro(const char* base_path, int device, srn_index_t** out
         if (!base_path || !out) return fail(SRN_EINVAL, "null argument");
         *out = nullptr;
         srn_index* ix = new srn_index();
-        int rc = build_flat_index_from_avro(base_path, ix->flat);
-        if (rc == SRN_OK && device >= 0) { ix->dev = device_attach(ix->flat, device); ix->device = device; if (!ix->dev) rc = SRN_EHIP; else ix->comb = combiner_create(); }
-        if (rc) { delete ix; return rc; }
-        *out = ix; return SRN_OK; });
+        return finish_index(ix, build_flat_index_from_avro(base_path, ix->flat), device, out); });
 }
 
 int srn_index_save(const srn_index_t* idx, const char* path) {
@@ -236,10 +237,7 @@ int srn_index_load(const char* path, int device, srn_index_t** out) {
         if (!path || !out) return fail(SRN_EINVAL, "null argument");
         *out = nullptr;
         srn_index* ix = new srn_index();
-        int rc = load_flat_index(path, ix->flat);
-        if (rc == SRN_OK && device >= 0) { ix->dev = device_attach(ix->flat, device); ix->device = device; if (!ix->dev) rc = SRN_EHIP; else ix->comb = combiner_create(); }
-        if (rc) { delete ix; return rc; }
-        *out = ix; return SRN_OK; });
+        return finish_index(ix, load_flat_index(path, ix->flat), device, out); });
 }
 int srn_index_set_attributes(srn_index_t* idx, const uint64_t* item_ids, const uint8_t* flags, size_t n) {
     if (!idx || (n && (!item_ids || !flags))) return fail(SRN_EINVAL, "null argument");
@@ -368,9 +366,7 @@ int srn_find_neighbors(const srn_index_t* idx, const uint64_t* evolving, size_t 
         std::vector<uint32_t> nb_rank(k), nb_num(k); uint32_t nb_cnt = 0, cnt = 0, stats[8] = {0};
         uint64_t id1 = 0; double sc1 = 0.0;
         const uint32_t q_off[2] = {0u, (uint32_t)len};
-        LaunchParams p{};
-        p.nq = 1; p.k = (uint32_t)k; p.m = (uint32_t)m; p.how_many = 1; p.flags = 0; p.max_len = (uint32_t)len;
-        rc = device_predict(idx->dev, idx->flat, p, false, nullptr, evolving, q_off, &id1, &sc1, &cnt, stats, nb_rank.data(), nb_num.data(), &nb_cnt);
+        rc = device_predict_host(idx->dev, idx->flat, launch_params(1, k, m, 1, 0, len), HostRows{evolving, q_off, &id1, &sc1, &cnt, stats, nb_rank.data(), nb_num.data(), &nb_cnt});
         if (rc) return rc;
         if (cnt == 0xFFFFFFFFu) return fail(SRN_ERANGE, "the query exceeded the kernel's table limits");
         size_t U = 0;   // distinct raw ids, known or not (vmis_index.rs:334-352: the decay's denominator)
@@ -497,12 +493,7 @@ int srn_predict_batch_device(const srn_index_t* idx, const uint64_t* d_items_fla
         if (!d_items_flat || !d_q_off || !d_out_ids || !d_out_scores || !d_out_counts) return fail(SRN_EINVAL, "null buffer");
         if (nq > 0x7FFFFFFFull) return fail(SRN_ERANGE, "too many queries in one batch");
         if (max_len_hint == 0 || max_len_hint > SRN_MAX_SESSION_LEN) return fail(SRN_ERANGE, "max_len_hint out of range");
-        LaunchParams p{};
-        p.nq = (uint32_t)nq; p.k = (uint32_t)k; p.m = (uint32_t)m; p.how_many = (uint32_t)how_many; p.flags = flags;
-        p.max_len = (uint32_t)max_len_hint;
-        p.items_flat = d_items_flat; p.q_off = d_q_off; p.out_ids = d_out_ids; p.out_scores = d_out_scores; p.out_counts = d_out_counts;
-        return device_predict(idx->dev, idx->flat, p, true, stream, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                              nullptr, nullptr); });
+        return device_predict_device(idx->dev, idx->flat, launch_params(nq, k, m, how_many, flags, max_len_hint, d_items_flat, d_q_off, d_out_ids, d_out_scores, d_out_counts), stream); });
 }
 
 // SRN_FLAG_FILL without a ranking: refused before anything is enqueued
@@ -519,11 +510,14 @@ static int check_excl_args(const srn_index_t* idx, size_t nq, size_t max_len_hin
     if (nq > 0x7FFFFFFFull) return fail(SRN_ERANGE, "too many queries in one batch");
     if (max_len_hint == 0 || max_len_hint > SRN_MAX_SESSION_LEN) return fail(SRN_ERANGE, "max_len_hint out of range");
     if (max_excl > SRN_MAX_HOW_MANY) return fail(SRN_ERANGE, "how_many + max_excl above SRN_MAX_HOW_MANY");
-    *wide = how_many + max_excl + ((flags & SRN_FLAG_EXCLUDE_SESSION) ? max_len_hint - 1 : 0);
+    *wide = wide_how_many(how_many, max_excl, (flags & SRN_FLAG_EXCLUDE_SESSION) != 0u, max_len_hint);
     if (*wide > SRN_MAX_HOW_MANY) return fail(SRN_ERANGE, "how_many + max_excl (+ max_len_hint - 1 with SRN_FLAG_EXCLUDE_SESSION) above SRN_MAX_HOW_MANY");
     if (max_excl > 0 && (!excl_flat || !excl_off)) return fail(SRN_EINVAL, "null exclusion list with max_excl > 0");
     if (flags & SRN_FLAG_FILL) return check_has_fallback(idx);
     return SRN_OK;
+}
+static RowRule excl_rule(const uint64_t* excl_flat, const uint32_t* excl_off, size_t max_excl, unsigned flags) {
+    return RowRule{excl_flat, excl_off, (uint32_t)max_excl, (flags & SRN_FLAG_EXCLUDE_SESSION) != 0u, (flags & SRN_FLAG_FILL) != 0u};
 }
 int srn_predict_batch_device_excl(const srn_index_t* idx, const uint64_t* d_items_flat, const uint32_t* d_q_off, size_t nq, size_t max_len_hint,
                                   const uint64_t* d_excl_flat, const uint32_t* d_excl_off, size_t max_excl, size_t k, size_t m, size_t how_many, unsigned flags,
@@ -533,15 +527,9 @@ int srn_predict_batch_device_excl(const srn_index_t* idx, const uint64_t* d_item
         int rc = check_excl_args(idx, nq, max_len_hint, d_excl_flat, d_excl_off, max_excl, k, m, how_many, flags, &wide); if (rc) return rc;
         if (nq == 0) return SRN_OK;
         if (!d_items_flat || !d_q_off || !d_out_ids || !d_out_scores || !d_out_counts) return fail(SRN_EINVAL, "null buffer");
-        LaunchParams p{};
-        const bool fill = (flags & SRN_FLAG_FILL) != 0u;   // (the launch sequence never sees the flag: device_fast_eligible sends any flag but the business rules to the general kernel)
-        p.nq = (uint32_t)nq; p.k = (uint32_t)k; p.m = (uint32_t)m; p.how_many = (uint32_t)wide; p.flags = flags & ~(unsigned)(SRN_FLAG_EXCLUDE_SESSION | SRN_FLAG_FILL); p.max_len = (uint32_t)max_len_hint;
-        p.items_flat = d_items_flat; p.q_off = d_q_off; p.out_ids = d_out_ids; p.out_scores = d_out_scores; p.out_counts = d_out_counts;
-        if (wide == how_many)   // nothing can be excluded (one-item sessions at most, whose item is never in its row): the plain call -- no scratch, no extra kernel (SRN_FLAG_FILL: the fill kernel, in place on the caller's rows)
-            return device_predict(idx->dev, idx->flat, p, true, stream, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, false, false, nullptr, fill);
-        const ExclSpec x{max_excl ? d_excl_flat : nullptr, max_excl ? d_excl_off : nullptr, (uint32_t)max_excl, (flags & SRN_FLAG_EXCLUDE_SESSION) != 0u, (uint32_t)how_many, d_out_ids, d_out_scores, d_out_counts};
-        p.out_ids = nullptr; p.out_scores = nullptr; p.out_counts = nullptr;
-        return device_predict(idx->dev, idx->flat, p, true, stream, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, false, false, &x, fill); });
+        // (the launch sequence never sees the rule's flags: device_fast_eligible sends any flag but the business rules to the general kernel)
+        const LaunchParams p = launch_params(nq, k, m, how_many, flags & ~(unsigned)(SRN_FLAG_EXCLUDE_SESSION | SRN_FLAG_FILL), max_len_hint, d_items_flat, d_q_off, d_out_ids, d_out_scores, d_out_counts);
+        return device_predict_device(idx->dev, idx->flat, p, stream, excl_rule(d_excl_flat, d_excl_off, max_excl, flags)); });
 }
 int srn_predict_batch_excl(const srn_index_t* idx, const uint64_t* items_flat, const uint32_t* q_off, size_t nq, const uint64_t* excl_flat, const uint32_t* excl_off, size_t max_excl,
                            size_t k, size_t m, size_t how_many, unsigned flags, uint64_t* out_ids, double* out_scores, uint32_t* out_counts) {
@@ -550,25 +538,14 @@ int srn_predict_batch_excl(const srn_index_t* idx, const uint64_t* items_flat, c
         if (!items_flat || !q_off || !out_ids || !out_scores || !out_counts) return fail(SRN_EINVAL, "null buffer");
         if (nq > 0x7FFFFFFFull) return fail(SRN_ERANGE, "too many queries in one batch");
         uint32_t max_len = 0;
-        for (size_t q = 0; q < nq; ++q) {
-            if (q_off[q + 1] < q_off[q]) return fail(SRN_EINVAL, "q_off not monotone");
-            if (q_off[q + 1] == q_off[q]) return fail(SRN_EINVAL, "empty evolving session (the reference panics: src/vmisknn/mod.rs:157)");
-            max_len = std::max(max_len, q_off[q + 1] - q_off[q]);
-        }
-        if (max_len > SRN_MAX_SESSION_LEN) return fail(SRN_ERANGE, "evolving session longer than SRN_MAX_SESSION_LEN");
+        int rc = scan_q_off(q_off, nq, &max_len); if (rc) return rc;
         size_t wide = 0;
-        int rc = check_excl_args(idx, nq, max_len, excl_flat, excl_off, max_excl, k, m, how_many, flags & ~(unsigned)SRN_FLAG_INPUTS_RESIDENT, &wide); if (rc) return rc;
+        rc = check_excl_args(idx, nq, max_len, excl_flat, excl_off, max_excl, k, m, how_many, flags & ~(unsigned)SRN_FLAG_INPUTS_RESIDENT, &wide); if (rc) return rc;
         if (max_excl) for (size_t q = 0; q < nq; ++q) if (excl_off[q + 1] < excl_off[q]) return fail(SRN_EINVAL, "excl_off not monotone");
-        const bool fill = (flags & SRN_FLAG_FILL) != 0u;   // (with the flag the rows always pass through the filter's buffers: the fill kernel works on device rows)
-        if (wide == how_many && !fill) return predict_host(idx, items_flat, q_off, nq, k, m, how_many, flags & (unsigned)SRN_FLAG_BUSINESS_LOGIC, out_ids, out_scores, out_counts, nullptr, nullptr, nullptr, nullptr);   // nothing can be excluded: the plain call
-        LaunchParams p{};
-        p.nq = (uint32_t)nq; p.k = (uint32_t)k; p.m = (uint32_t)m; p.how_many = (uint32_t)wide; p.flags = flags & (unsigned)SRN_FLAG_BUSINESS_LOGIC; p.max_len = max_len;
-        const ExclSpec x{max_excl ? excl_flat : nullptr, max_excl ? excl_off : nullptr, (uint32_t)max_excl, (flags & SRN_FLAG_EXCLUDE_SESSION) != 0u, (uint32_t)how_many, nullptr, nullptr, nullptr};
-        rc = device_predict(idx->dev, idx->flat, p, false, nullptr, items_flat, q_off, out_ids, out_scores, out_counts, nullptr, nullptr, nullptr, nullptr, nullptr, false, false, &x, fill);
+        rc = device_predict_host(idx->dev, idx->flat, launch_params(nq, k, m, how_many, flags & (unsigned)SRN_FLAG_BUSINESS_LOGIC, max_len),
+                                 HostRows{items_flat, q_off, out_ids, out_scores, out_counts}, excl_rule(excl_flat, excl_off, max_excl, flags));
         if (rc) return rc;
-        if (wide == how_many)   // (the plain call's contract, which this one replaces under SRN_FLAG_FILL)
-            for (size_t q = 0; q < nq; ++q) if (out_counts[q] == 0xFFFFFFFFu) return fail(SRN_ERANGE, "a query exceeded the kernel's table limits");
-        return SRN_OK; });
+        return wide == how_many ? check_all_served(out_counts, nq) : SRN_OK; });   // (nothing could be excluded: the plain call's contract)
 }
 
 int srn_debug_exclude_filter(const srn_index_t* idx, size_t nq, const uint64_t* d_wide_ids, const double* d_wide_scores, const uint32_t* d_wide_counts, size_t wide, const uint64_t* d_excl_flat,
@@ -607,9 +584,7 @@ int srn_index_reserve(const srn_index_t* idx, size_t nq, size_t max_len_hint, si
         int rc = check_predict_args(idx, k, m, how_many); if (rc) return rc;
         if (nq == 0 || nq > 0x7FFFFFFFull) return fail(SRN_ERANGE, "nq out of range");
         if (max_len_hint == 0 || max_len_hint > SRN_MAX_SESSION_LEN) return fail(SRN_ERANGE, "max_len_hint out of range");
-        LaunchParams p{};
-        p.nq = (uint32_t)nq; p.k = (uint32_t)k; p.m = (uint32_t)m; p.how_many = (uint32_t)how_many; p.flags = flags; p.max_len = (uint32_t)max_len_hint;
-        return device_reserve(idx->dev, idx->flat, p, stream); });
+        return device_reserve(idx->dev, idx->flat, launch_params(nq, k, m, how_many, flags, max_len_hint), stream); });
 }
 
 int srn_last_kernel_ms(const srn_index_t* idx, double* out_ms_main, double* out_ms_retry, uint32_t* out_retried) {
@@ -624,10 +599,7 @@ int srn_index_build_shard(const srn_sessions_view_t* sessions, size_t m_index, s
         if (!sessions || !out) return fail(SRN_EINVAL, "null argument");
         *out = nullptr;
         srn_index* ix = new srn_index();
-        int rc = build_flat_index(*sessions, m_index, max_session_len, idf_weighting, shard, n_shards, ix->flat);
-        if (rc == SRN_OK && device >= 0) { ix->dev = device_attach(ix->flat, device); ix->device = device; if (!ix->dev) rc = SRN_EHIP; else ix->comb = combiner_create(); }
-        if (rc) { delete ix; return rc; }
-        *out = ix; return SRN_OK; });
+        return finish_index(ix, build_flat_index(*sessions, m_index, max_session_len, idf_weighting, shard, n_shards, ix->flat), device, out); });
 }
 int srn_index_shard(const srn_index_t* full, uint32_t shard, uint32_t n_shards, int device, srn_index_t** out) {
     return guarded([&]() -> int {
@@ -635,10 +607,7 @@ int srn_index_shard(const srn_index_t* full, uint32_t shard, uint32_t n_shards, 
         *out = nullptr;
         { int rc0 = check_has_rows(full->flat, "srn_index_shard"); if (rc0) return rc0; }
         srn_index* ix = new srn_index();
-        int rc = shard_flat_index(full->flat, shard, n_shards, ix->flat);
-        if (rc == SRN_OK && device >= 0) { ix->dev = device_attach(ix->flat, device); ix->device = device; if (!ix->dev) rc = SRN_EHIP; else ix->comb = combiner_create(); }
-        if (rc) { delete ix; return rc; }
-        *out = ix; return SRN_OK; });
+        return finish_index(ix, shard_flat_index(full->flat, shard, n_shards, ix->flat), device, out); });
 }
 // The replicated part of an item-sharded index: the whole index's dictionary, idf / attributes and posting lists WITHOUT its rows (config 5: ~10 GB of the 66.6 GB)
 int srn_index_postings_view(const srn_index_t* full, int device, srn_index_t** out) {
@@ -668,10 +637,7 @@ int srn_index_build_shard_gpu(const srn_sessions_view_t* sessions, size_t m_inde
         int rc = build_flat_index_gpu(*sessions, m_index, max_session_len, idf_weighting, device, full);
         if (rc) return rc;
         srn_index* ix = new srn_index();
-        rc = shard_flat_index(full, shard, n_shards, ix->flat);
-        if (rc == SRN_OK) { ix->dev = device_attach(ix->flat, device); ix->device = device; if (!ix->dev) rc = SRN_EHIP; else ix->comb = combiner_create(); }
-        if (rc) { delete ix; return rc; }
-        *out = ix; return SRN_OK; });
+        return finish_index(ix, shard_flat_index(full, shard, n_shards, ix->flat), device, out); });   // (device >= 0: checked above)
 }
 int srn_index_load_shard(const char* path, uint32_t shard, uint32_t n_shards, int device, srn_index_t** out) {
     return guarded([&]() -> int {
@@ -683,9 +649,7 @@ int srn_index_load_shard(const char* path, uint32_t shard, uint32_t n_shards, in
         srn_index* ix = new srn_index();
         rc = full.n_shards == 1 ? shard_flat_index(full, shard, n_shards, ix->flat)
                                 : (full.shard == shard && full.n_shards == n_shards ? (ix->flat = std::move(full), SRN_OK) : fail(SRN_EINVAL, "the file holds another shard"));
-        if (rc == SRN_OK && device >= 0) { ix->dev = device_attach(ix->flat, device); ix->device = device; if (!ix->dev) rc = SRN_EHIP; else ix->comb = combiner_create(); }
-        if (rc) { delete ix; return rc; }
-        *out = ix; return SRN_OK; });
+        return finish_index(ix, rc, device, out); });
 }
 int srn_kernel_times(const srn_index_t* idx, uint32_t max_n, double* out_ms_main, double* out_ms_retry, uint32_t* out_n) {
     if (!idx || !idx->dev) return fail(SRN_ENODEV, "index has no device attached");
@@ -715,8 +679,7 @@ int srn_last_path_counts(const srn_index_t* idx, uint32_t* out_nq, uint32_t* out
     return guarded([&]() -> int { return device_last_path_counts(idx->dev, out_nq, out_general, out_global_pass); });
 }
 uint32_t srn_debug_shard_nb_positions_stride(size_t k, size_t m) {
-    LaunchParams p{}; p.k = (uint32_t)k; p.m = (uint32_t)m; p.max_len = 4; p.nq = 1; p.how_many = 21;
-    return device_shard_nb_positions_stride(p);
+    return device_shard_nb_positions_stride(launch_params(1, k, m, 21, 0, 4));
 }
 int srn_debug_serve_stamps(const srn_index_t* idx, uint32_t* out4) {
     if (!idx || !idx->dev || !out4) return fail(SRN_EINVAL, "null argument");

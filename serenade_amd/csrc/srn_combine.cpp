@@ -120,11 +120,9 @@ int combiner_predict(Combiner* c, const srn_index* idx, const uint64_t* evolving
             std::vector<uint64_t> flat; std::vector<uint32_t> off(nq + 1, 0); uint32_t max_len = 0;
             for (size_t i = 0; i < nq; ++i) { flat.insert(flat.end(), r->ev[i], r->ev[i] + r->len[i]); off[i + 1] = (uint32_t)flat.size(); max_len = std::max(max_len, r->len[i]); }
             r->ids.assign(nq * how_many, 0); r->scores.assign(nq * how_many, 0.0); r->counts.assign(nq, 0);
-            LaunchParams p{};
-            p.nq = (uint32_t)nq; p.k = (uint32_t)k; p.m = (uint32_t)m; p.how_many = (uint32_t)how_many; p.flags = flags; p.max_len = max_len;
+            const LaunchParams p = launch_params(nq, k, m, how_many, flags, max_len);
             // a lone caller spins on its result (lowest latency); a shared round sleeps on an interrupt: its members' cores are better spent on their next requests
-            r->rc = device_predict(idx->dev, idx->flat, p, false, nullptr, flat.data(), off.data(), r->ids.data(), r->scores.data(), r->counts.data(), nullptr, nullptr, nullptr, nullptr,
-                                   nullptr, false, /*blocking_wait=*/nq > 1);
+            r->rc = device_predict_host(idx->dev, idx->flat, p, HostRows{flat.data(), off.data(), r->ids.data(), r->scores.data(), r->counts.data()}, {}, /*blocking_wait=*/nq > 1);
             if (r->rc) r->err = last_error_string();
             // The reference's predict() calls are independent (src/endpoints/recommend_resource.rs:56): one member's session must not fail the others'.  A round
             // refused for its shape (a long session pushing the batch geometry over a limit) is re-run member by member, each with its own verdict.
@@ -133,8 +131,7 @@ int combiner_predict(Combiner* c, const srn_index* idx, const uint64_t* evolving
                 for (size_t i = 0; i < nq; ++i) {
                     const uint32_t off1[2] = {0u, r->len[i]};
                     LaunchParams p1 = p; p1.nq = 1; p1.max_len = r->len[i];
-                    r->member_rc[i] = device_predict(idx->dev, idx->flat, p1, false, nullptr, r->ev[i], off1, &r->ids[i * how_many], &r->scores[i * how_many], &r->counts[i], nullptr, nullptr,
-                                                     nullptr, nullptr, nullptr, false, /*blocking_wait=*/true);
+                    r->member_rc[i] = device_predict_host(idx->dev, idx->flat, p1, HostRows{r->ev[i], off1, &r->ids[i * how_many], &r->scores[i * how_many], &r->counts[i]}, {}, /*blocking_wait=*/true);
                     if (r->member_rc[i]) r->member_err[i] = last_error_string();
                 }
                 r->rc = SRN_OK; r->err.clear();

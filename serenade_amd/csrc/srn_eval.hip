@@ -1,7 +1,7 @@
 // Offline evaluation on the GPU (include/serenade_hip.h, "offline evaluation"): the reference's evaluation loop (src/bin/evaluator.rs:46-76,
 // src/objective.rs:8-52) over a test set resident in HBM.  A trial runs in chunks of queries; per chunk
 //   eval_expand_kernel   the chunk's prefixes (CSR) straight from the resident test sessions, windowed to the trial's max_items_in_session
-//   device_predict       the same launch sequence srn_predict_batch_device takes (the rows are the same bytes)
+//   device_predict_device  the same launch sequence srn_predict_batch_device takes (the rows are the same bytes)
 //   eval_metrics_kernel  one wave per query: the per-query terms of src/metrics/*.rs, and the recommended items' coverage bits
 //   eval_group_kernel    partial sums per group of 256 GLOBAL query indices (chunks are multiples of 256, so a group never straddles two)
 // The host adds the groups' partial sums in group order: a trial's sums do not depend on the chunk size or on the other trials of the call.
@@ -11,7 +11,7 @@
 //   eval_serve_count_kernel   per query: |query(t)| and |list| packed into one 64-bit word, from a walk back from e_t under the handler's rule
 //   rocprim::exclusive_scan   both offsets in one scan (the halves cannot carry into each other: a chunk's items and list ids are both below 2^32)
 //   eval_serve_write_kernel   the same walk: items_flat / q_off, the exclusion CSR x_flat / x_off, (session, state)
-// and predict with an ExclSpec over the lists, as srn_predict_batch_device_excl does: wide rows in the workspace's scratch, the filter and the fill kernel behind the
+// and predict with a RowRule over the lists, as srn_predict_batch_device_excl does: wide rows in the workspace's scratch, the filter and the fill kernel behind the
 // launch sequence.  Nothing waits on the host between chunks: the buffers are sized from the capacities.  The metric, group and popcount kernels are the same.
 #include <hip/hip_runtime.h>
 
@@ -619,18 +619,12 @@ int eval_run(srn_eval_set* set, const srn_eval_trial_t* trials, size_t n_trials,
                 HIP_TRY(hipGetLastError());
             }
             HIP_TRY(hipEventRecord(ev[1], st));
-            LaunchParams p{};
-            p.nq = nq; p.k = tr.k; p.m = tr.m; p.how_many = tr.how_many; p.flags = (tr.flags & SRN_FLAG_BUSINESS_LOGIC) | kFlagNoResultCache; p.max_len = max_len;   // (a grid of trials is no serving traffic: the index's result cache is bypassed)
-            p.items_flat = d_items; p.q_off = d_qoff; p.out_ids = d_ids; p.out_scores = d_sc; p.out_counts = d_cnt;
-            // (SRN_FLAG_FILL: the metric kernel scores the filled rows -- the fill kernel runs behind the launch sequence, inside the call)
-            const bool fill = (tr.flags & SRN_FLAG_FILL) != 0u;
-            if (cap) {   // the lists are the exclusion CSR of srn_predict_batch_device_excl: the launch sequence writes rows of how_many + cap into the workspace's scratch, the filter the chunk's
-                const ExclSpec x{d_x, d_xoff, cap, false, tr.how_many, d_ids, d_sc, d_cnt};
-                p.how_many = tr.how_many + cap; p.out_ids = nullptr; p.out_scores = nullptr; p.out_counts = nullptr;
-                rc = device_predict(idx->dev, ix, p, true, st, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, false, false, &x, fill);
-            } else
-                rc = device_predict(idx->dev, ix, p, true, st, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, false, false, nullptr, fill);
-            if (rc) return rc;
+            // (a grid of trials is no serving traffic: the index's result cache is bypassed)
+            const LaunchParams p = launch_params(nq, tr.k, tr.m, tr.how_many, (tr.flags & SRN_FLAG_BUSINESS_LOGIC) | kFlagNoResultCache, max_len, d_items, d_qoff, d_ids, d_sc, d_cnt);
+            // the lists are the exclusion CSR of srn_predict_batch_device_excl, their capacity `cap` (0: the trial excludes nothing, the plain call); SRN_FLAG_FILL: the metric
+            // kernel scores the filled rows -- the fill kernel runs behind the launch sequence, inside the call
+            RowRule rule; rule.x_flat = d_x; rule.x_off = d_xoff; rule.max_excl = cap; rule.fill = (tr.flags & SRN_FLAG_FILL) != 0u;
+            if ((rc = device_predict_device(idx->dev, ix, p, st, rule))) return rc;
             HIP_TRY(hipSetDevice(e->device));
             HIP_TRY(hipEventRecord(ev[2], st));
             MetricArgs a{};

@@ -99,12 +99,13 @@ int exclude_wide_room(Workspace* w, uint32_t nq, uint32_t W, uint64_t** ids, dou
 int exclude_host_room(Workspace* w, hipStream_t st, uint32_t nq, ExclSpec& x) {
     const uint64_t* h_xflat = x.x_flat; const uint32_t* h_xoff = x.x_off;
     const size_t nx = h_xoff ? h_xoff[nq] : 0, n_out = (size_t)nq * x.how_many;
-    size_t off = 0; auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
-    const size_t o_x = take(nx * 8), o_xoff = take(h_xoff ? ((size_t)nq + 1) * 4 : 0), o_ids = take(n_out * 8), o_sc = take(n_out * 8), o_cnt = take((size_t)nq * 4);
-    { const int rc = ensure(&w->wide, &w->wide_bytes, off); if (rc) return rc; }
+    Bump b;
+    const auto r_x = b.take<const uint64_t>(nx * 8); const auto r_xoff = b.take<const uint32_t>(h_xoff ? ((size_t)nq + 1) * 4 : 0);
+    const auto r_ids = b.take<uint64_t>(n_out * 8); const auto r_sc = b.take<double>(n_out * 8); const auto r_cnt = b.take<uint32_t>((size_t)nq * 4);
+    { const int rc = ensure(&w->wide, &w->wide_bytes, b.bytes); if (rc) return rc; }
     char* s = w->wide;
-    x.x_flat = h_xoff ? (const uint64_t*)(s + o_x) : nullptr; x.x_off = h_xoff ? (const uint32_t*)(s + o_xoff) : nullptr;
-    x.out_ids = (uint64_t*)(s + o_ids); x.out_scores = (double*)(s + o_sc); x.out_counts = (uint32_t*)(s + o_cnt);
+    x.x_flat = h_xoff ? r_x.at(s) : nullptr; x.x_off = h_xoff ? r_xoff.at(s) : nullptr;
+    x.out_ids = r_ids.at(s); x.out_scores = r_sc.at(s); x.out_counts = r_cnt.at(s);
     HIP_TRY(hipMemsetAsync(x.out_ids, 0, n_out * 8, st));
     HIP_TRY(hipMemsetAsync(x.out_scores, 0, n_out * 8, st));
     if (h_xoff) {

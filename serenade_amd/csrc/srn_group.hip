@@ -406,11 +406,9 @@ int group_predict_locked(srn_shard_group* g, const uint64_t* d_items_flat, const
     HIP_TRY(hipSetDevice(g->device));
     const uint32_t G = G_of(g), nq = (uint32_t)nq_, ML = (uint32_t)max_len_hint, n = (uint32_t)how_many;
     const bool local = g->kind == srn_shard_group::LOCAL;
-    LaunchParams p{};
     const bool resident = (flags & SRN_FLAG_INPUTS_RESIDENT) != 0u;   // the inputs do not hang on the caller's stream: this batch's exchange may start while the previous batch still runs there
     flags &= ~(unsigned)SRN_FLAG_INPUTS_RESIDENT;
-    p.nq = nq; p.k = (uint32_t)k; p.m = (uint32_t)m; p.how_many = n; p.flags = flags; p.max_len = ML; p.items_flat = d_items_flat; p.q_off = d_q_off;
-    p.out_ids = d_out_ids; p.out_scores = d_out_scores; p.out_counts = d_out_counts;
+    LaunchParams p = launch_params(nq, k, m, n, flags, ML, d_items_flat, d_q_off, d_out_ids, d_out_scores, d_out_counts);
     for (const srn_index* ix : g->shards)
         if (!device_shard_lists_supported(ix->dev, ix->flat, p)) return group_predict_stages(g, p, d_out_ids, d_out_scores, d_out_counts, user);   // (every rank holds the same index parameters: the same choice everywhere)
     if (g->postings && G > 1) {   // (the same index parameters and the same batch shape on every rank: the same choice everywhere.  A group of ONE shard gains nothing from

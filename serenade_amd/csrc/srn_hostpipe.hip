@@ -238,7 +238,7 @@ int device_predict_host_pipelined(DeviceState* d, const FlatIndex& ix, const Lau
         p.q_off = (const uint32_t*)(hp->dev_in[i] + (in_items + 255) / 256 * 256);
         p.out_ids = (uint64_t*)hp->dev_out[i]; p.out_scores = (double*)(hp->dev_out[i] + (size_t)cq * n * 8); p.out_counts = (uint32_t*)(hp->dev_out[i] + (size_t)cq * n * 16);
         HIP_TRY(hipMemsetAsync(hp->dev_out[i], 0, (size_t)cq * n * 16, sk));   // the unused tail of each row reads as 0
-        { int rc = device_predict(d, ix, p, true, sk, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr); if (rc) return rc; }
+        { int rc = device_predict_device(d, ix, p, sk); if (rc) return rc; }
         if (!one) HIP_TRY(hipEventRecord(hp->e_k[i], sk));
         // download: the pinned slot's previous contents (chunk c - NOUT) must have reached the caller's buffers
         tr_enq += now_us() - t0; t0 = now_us();

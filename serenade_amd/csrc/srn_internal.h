@@ -146,21 +146,39 @@ struct ExtLists { const char* prep; uint32_t prep_stride; const uint32_t* post_r
                   int mode = 0; uint32_t* xchg = nullptr; uint32_t xchg_stride = 0; uint32_t q_lo = 0;
                   const unsigned long long* order = nullptr;     // mode 2: the batch's serving order (device_shard_nb_prep sorted it), or null
                   bool positions = false; };                     // mode 2: xchg holds position records (device_shard_nb_positions), not neighbour slots: the streaming back end
-// Exclusion lists (srn_exclude.hip).  The call's LaunchParams carry the INTERNAL how_many W = how_many + the lists' capacity and no output buffers: the
-// launch sequence writes wide rows into the workspace's scratch, and the filter kernel behind it writes the caller's rows.  Device pointers; x_flat / x_off may be null
-// (max_excl 0); session: the items of the query's own session are excluded too (SRN_FLAG_EXCLUDE_SESSION).  A host-pointer call (srn_predict_batch_excl) hands x_flat / x_off
-// as host pointers and leaves out_* null: the rows come back through device_predict's h_ids / h_scores / h_counts
-struct ExclSpec { const uint64_t* x_flat; const uint32_t* x_off; uint32_t max_excl; bool session; uint32_t how_many; uint64_t* out_ids; double* out_scores; uint32_t* out_counts; };
-int device_predict(DeviceState* d, const FlatIndex& ix, const LaunchParams& p, bool buffers_on_device, void* stream,
-                   // host-pointer mode: these are host buffers copied in/out by the call
-                   const uint64_t* h_items, const uint32_t* h_qoff, uint64_t* h_ids, double* h_scores,
-                   uint32_t* h_counts, uint32_t* h_stats, uint32_t* h_nb_rank, uint32_t* h_nb_num, uint32_t* h_nb_cnt, const ExtLists* ext = nullptr,
-                   bool reserve_only = false, bool blocking_wait = false, const ExclSpec* excl = nullptr, bool fill = false);   // reserve_only (srn_index_reserve): size the call's workspace, enqueue nothing; blocking_wait: the latency path sleeps on an interrupt instead of spinning
+// ---- the predict call.  Every entry takes the caller's OWN how_many (and, on device buffers, the caller's own rows) in LaunchParams ----
+inline LaunchParams launch_params(size_t nq, size_t k, size_t m, size_t how_many, unsigned flags, size_t max_len, const uint64_t* items_flat = nullptr, const uint32_t* q_off = nullptr,
+                                  uint64_t* out_ids = nullptr, double* out_scores = nullptr, uint32_t* out_counts = nullptr) {
+    LaunchParams p{};
+    p.nq = (uint32_t)nq; p.k = (uint32_t)k; p.m = (uint32_t)m; p.how_many = (uint32_t)how_many; p.flags = flags; p.max_len = (uint32_t)max_len;
+    p.items_flat = items_flat; p.q_off = q_off; p.out_ids = out_ids; p.out_scores = out_scores; p.out_counts = out_counts;
+    return p;
+}
+// a host-pointer call's buffers, copied in and out by the call; stats [nq * 8] and the neighbour dump (all three or none) may be null
+struct HostRows { const uint64_t* items; const uint32_t* q_off; uint64_t* ids; double* scores; uint32_t* counts;
+                  uint32_t* stats = nullptr; uint32_t* nb_rank = nullptr; uint32_t* nb_num = nullptr; uint32_t* nb_cnt = nullptr; };
+// What happens to a call's rows behind the launch sequence (srn_exclude.hip, srn_fill.hip).  x_flat / x_off: the exclusion CSR, at most max_excl ids per
+// query (null with max_excl 0; device pointers for device_predict_device, host pointers for device_predict_host); session: the items of the query's own session are excluded
+// too (SRN_FLAG_EXCLUDE_SESSION); fill (SRN_FLAG_FILL): short rows are then filled in place from the index's fallback ranking (SRN_ESTATE without one).  The callers strip
+// these flags from LaunchParams::flags: the kernels never see them.  With something to exclude the launch sequence runs at the internal how_many wide_how_many() into wide
+// rows of the call's workspace and the filter kernel behind it writes the caller's; where that width is the caller's how_many nothing can be excluded and the call is the plain one
+struct RowRule { const uint64_t* x_flat = nullptr; const uint32_t* x_off = nullptr; uint32_t max_excl = 0; bool session = false; bool fill = false; };
+inline size_t wide_how_many(size_t how_many, size_t max_excl, bool session, size_t max_len) { return how_many + max_excl + (session ? max_len - 1 : 0); }
+// device buffers, asynchronous on `stream` (SRN_FLAG_INPUTS_RESIDENT and kFlagNoResultCache in p.flags are consumed here)
+int device_predict_device(DeviceState* d, const FlatIndex& ix, const LaunchParams& p, void* stream, const RowRule& rule = {});
+// host buffers; returns with the rows in place.  Small batches take the latency path (blocking_wait: it sleeps on an interrupt instead of spinning), larger ones the chunked
+// pipeline; stats, the neighbour dump and a rule that filters go through one staged workspace (a rule together with stats or the dump: SRN_EINVAL)
+int device_predict_host(DeviceState* d, const FlatIndex& ix, const LaunchParams& p, const HostRows& rows, const RowRule& rule = {}, bool blocking_wait = false);
+// the unserved-query mark of a call's count words
+inline int check_all_served(const uint32_t* counts, size_t nq) {
+    for (size_t q = 0; q < nq; ++q) if (counts[q] == 0xFFFFFFFFu) return fail(SRN_ERANGE, "a query exceeded the kernel's table limits");
+    return SRN_OK;
+}
 // measurement aid (srn_debug_exclude_filter): the filter kernel alone over the caller's wide rows, enqueued on `stream`
 int device_exclude_filter(DeviceState* d, uint32_t nq, const uint64_t* w_ids, const double* w_scores, const uint32_t* w_counts, uint32_t wide, const uint64_t* x_flat, const uint32_t* x_off,
                           uint32_t max_excl, const uint64_t* items_flat, const uint32_t* q_off, uint64_t* out_ids, double* out_scores, uint32_t* out_counts, uint32_t how_many, void* stream);
-// The fallback ranking (srn_fill.hip).  device_predict's `fill` (SRN_FLAG_FILL, stripped from LaunchParams::flags by the caller): behind the launch sequence
-// and the exclusion filter, short rows of the call's final rows are filled in place from the ranking; buffers_on_device calls and host-pointer calls with an ExclSpec only
+// The fallback ranking (srn_fill.hip).  RowRule::fill: behind the launch sequence and the exclusion filter, short rows of the call's final rows are filled in
+// place from the ranking (a host-pointer call's rows then always pass through the filter's device buffers)
 bool device_has_fallback(const DeviceState* d);
 int device_set_fallback(DeviceState* d, const FlatIndex& ix, const uint64_t* item_ids, uint32_t n);   // replaces an earlier ranking; synchronises the device
 void device_clear_fallback(DeviceState* d);
@@ -223,7 +241,7 @@ int device_last_path_counts(DeviceState* d, uint32_t* nq, uint32_t* general, uin
 int device_last_mid_count(DeviceState* d, uint32_t* listed, uint32_t* big_listed = nullptr);   // queries the last call's lean fast kernel listed for its MID instantiation
 int device_last_dedup_count(DeviceState* d, uint32_t* merged);   // queries of the last call merged into an equal, earlier query of the same call (srn_dedup.hip)
 // ---- the device result cache (srn_result_cache.hip): served rows kept across calls, used by the batch launch sequence where its fast path is ----
-static constexpr unsigned kFlagNoResultCache = 0x80000000u;   // LaunchParams::flags, internal (device_predict strips it): this call bypasses an enabled cache (srn_evaluate)
+static constexpr unsigned kFlagNoResultCache = 0x80000000u;   // LaunchParams::flags, internal (the predict entries strip it): this call bypasses an enabled cache (srn_evaluate)
 int device_result_cache_enable(DeviceState* d, uint64_t rows, uint32_t max_len, uint32_t k, uint32_t m, uint32_t how_many, uint32_t flags);
 int device_result_cache_disable(DeviceState* d);
 int device_result_cache_clear(DeviceState* d);            // SRN_ESTATE: none enabled

@@ -22,14 +22,16 @@ namespace srn {
 // results come back the same way; two launches (prep kernel + general kernel, one workgroup per query) and one stream synchronise.
 // Returns 1 if a query needs the global-table pass (the caller then takes the normal path).
 
-// the call's pinned buffer: where its inputs, rows and the general kernel's retry list / count stand (byte offsets), and the buffer as the device sees it
-struct TinyPin { size_t o_items = 0, o_qoff = 0, o_ids = 0, o_sc = 0, o_cnt = 0, o_rc = 0, o_rl = 0; char* dp = nullptr; };
+// the call's pinned buffer: where its inputs, rows and the general kernel's retry list / count stand (regions of 64 bytes' alignment: at(w->pin) for the host, at(dp) for
+// the device), and the buffer as the device sees it
+struct TinyPin { Bump::Region<uint64_t> items{}, ids{}; Bump::Region<double> sc{}; Bump::Region<uint32_t> qoff{}, cnt{}, rc{}, rl{}; char* dp = nullptr; };
 // grows the pinned buffer, copies the sessions in and points p's inputs and outputs at it
 static int tiny_stage(Workspace* w, LaunchParams& p, const uint64_t* h_items, const uint32_t* h_qoff, TinyPin& t) {
     const size_t nitems = h_qoff[p.nq], n_out = (size_t)p.nq * p.how_many;
-    size_t off = 0; auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 63) / 64 * 64; return o; };
-    t.o_items = take(nitems * 8); t.o_qoff = take(((size_t)p.nq + 1) * 4); t.o_ids = take(n_out * 8); t.o_sc = take(n_out * 8); t.o_cnt = take((size_t)p.nq * 4);
-    t.o_rc = take(4); t.o_rl = take((size_t)p.nq * 4 + 4);
+    Bump b(64);
+    t.items = b.take<uint64_t>(nitems * 8); t.qoff = b.take<uint32_t>(((size_t)p.nq + 1) * 4); t.ids = b.take<uint64_t>(n_out * 8); t.sc = b.take<double>(n_out * 8); t.cnt = b.take<uint32_t>((size_t)p.nq * 4);
+    t.rc = b.take<uint32_t>(4); t.rl = b.take<uint32_t>((size_t)p.nq * 4 + 4);
+    const size_t off = b.bytes;
     if (w->pin_bytes < off) {
         if (w->pin) HIP_TRY(hipHostFree(w->pin));
         w->pin = nullptr; w->pin_bytes = 0;
@@ -39,16 +41,16 @@ static int tiny_stage(Workspace* w, LaunchParams& p, const uint64_t* h_items, co
     }
     char* dp = nullptr; HIP_TRY(hipHostGetDevicePointer((void**)&dp, w->pin, 0));
     t.dp = dp;
-    memcpy(w->pin + t.o_items, h_items, nitems * 8); memcpy(w->pin + t.o_qoff, h_qoff, ((size_t)p.nq + 1) * 4);
-    *(volatile uint32_t*)(w->pin + t.o_rc) = 0;
-    p.items_flat = (const uint64_t*)(dp + t.o_items); p.q_off = (const uint32_t*)(dp + t.o_qoff);
-    p.out_ids = (uint64_t*)(dp + t.o_ids); p.out_scores = (double*)(dp + t.o_sc); p.out_counts = (uint32_t*)(dp + t.o_cnt);
+    memcpy(t.items.at(w->pin), h_items, nitems * 8); memcpy(t.qoff.at(w->pin), h_qoff, ((size_t)p.nq + 1) * 4);
+    *(volatile uint32_t*)t.rc.at(w->pin) = 0;
+    p.items_flat = t.items.at(dp); p.q_off = t.qoff.at(dp);
+    p.out_ids = t.ids.at(dp); p.out_scores = t.sc.at(dp); p.out_counts = t.cnt.at(dp);
     p.stats = nullptr; p.nb_rank = p.nb_num = p.nb_cnt = nullptr; p.phase_cycles = nullptr;
     return SRN_OK;
 }
 // the rows, from the pinned buffer to the caller's arrays
 static void tiny_unstage(const Workspace* w, const LaunchParams& p, const TinyPin& t, uint64_t* h_ids, double* h_scores, uint32_t* h_counts) {
-    const uint64_t* r_ids = (const uint64_t*)(w->pin + t.o_ids); const double* r_sc = (const double*)(w->pin + t.o_sc); const uint32_t* r_cnt = (const uint32_t*)(w->pin + t.o_cnt);
+    const uint64_t* r_ids = t.ids.at(w->pin); const double* r_sc = t.sc.at(w->pin); const uint32_t* r_cnt = t.cnt.at(w->pin);
     for (uint32_t q = 0; q < p.nq; ++q) {
         const uint32_t n = r_cnt[q] == 0xFFFFFFFFu ? 0u : std::min<uint32_t>(r_cnt[q], p.how_many);
         h_counts[q] = r_cnt[q];
@@ -76,7 +78,7 @@ struct TinyCall {
 static int tiny_general(const TinyCall& c, bool fast_list, uint32_t grid) {
     PredictLaunch a; a.masks = c.geo.masks; a.slot64 = c.geo.slot64; a.spill = c.w->spill;
     if (fast_list) { a.qlist = c.w->slow_list; a.qn = c.w->slow_cnt; }
-    a.retry_list = (uint32_t*)(c.pin.dp + c.pin.o_rl); a.retry_cnt = (uint32_t*)(c.pin.dp + c.pin.o_rc);
+    a.retry_list = c.pin.rl.at(c.pin.dp); a.retry_cnt = c.pin.rc.at(c.pin.dp);
     HIP_TRY(launch_predict(a, dim3(grid), c.geo.lds, c.st, c.d->di, c.p, c.geo.c));
     return SRN_OK;
 }
@@ -182,7 +184,7 @@ int device_predict_tiny(DeviceState* d, const FlatIndex& ix, Workspace* w, const
         if (!rc) rc = latency_wait(w, st, blocking_wait);
     }
     if (rc) return rc;
-    if (*(volatile uint32_t*)(w->pin + pin.o_rc) != 0) return 1;   // (rare: tables too small for some query)
+    if (*(volatile uint32_t*)pin.rc.at(w->pin) != 0) return 1;   // (rare: tables too small for some query)
     // what the timing / path-count APIs report after this call: its query count, how many of them the fast sequence handed to the general kernel (all of them where the
     // two-launch form ran), not timed (the stream is idle here: nothing of an earlier call is still writing the pinned words)
     ++w->untimed_calls; w->last_nq = p.nq; w->last_retry = 0; w->last_fast = tiny_fast; w->last_mid = tiny_fast && plan.mid_tier; w->last_dedup = false; w->last_untimed = true;   // (`calls` indexes the event ring: timed calls only)

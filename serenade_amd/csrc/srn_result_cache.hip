@@ -157,13 +157,15 @@ int device_result_cache_enable(DeviceState* d, uint64_t rows, uint32_t max_len, 
     v.n_buckets = (uint32_t)((rows + RC_WAYS - 1) / RC_WAYS); v.max_len = max_len; v.how_many = how_many;
     v.hash_mask = 0xFFFFFFFFu;
     const size_t R = (size_t)v.n_buckets * RC_WAYS;
-    size_t off = 0; auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
-    const size_t o_cnt = take(RC_COUNTERS * 8), o_stamp = take(R * 4), o_len = take(R * 4), o_count = take(R * 4), o_keys = take(R * max_len * 8), o_ids = take(R * how_many * 8), o_sc = take(R * how_many * 8);
+    Bump b;
+    const auto r_cnt = b.take<unsigned long long>(RC_COUNTERS * 8); const auto r_stamp = b.take<uint32_t>(R * 4), r_len = b.take<uint32_t>(R * 4), r_count = b.take<uint32_t>(R * 4);
+    const auto r_keys = b.take<uint64_t>(R * max_len * 8), r_ids = b.take<uint64_t>(R * how_many * 8); const auto r_sc = b.take<double>(R * how_many * 8);
+    const size_t off = b.bytes;
     // (everything the cache will ever need is allocated HERE: hipMalloc synchronises the device, the calls allocate nothing for it)
     if (hipMalloc((void**)&rc->mem, off) != hipSuccess) { (void)hipGetLastError(); rc->mem = nullptr; return fail(SRN_ENOMEM, "result cache: hipMalloc failed"); }
-    rc->bytes = off; rc->stamp_bytes = o_count - o_stamp;   // (stamps and lengths are adjacent: one memset empties the table)
-    v.counters = (unsigned long long*)(rc->mem + o_cnt); v.stamp = (uint32_t*)(rc->mem + o_stamp); v.len = (uint32_t*)(rc->mem + o_len); v.count = (uint32_t*)(rc->mem + o_count);
-    v.keys = (uint64_t*)(rc->mem + o_keys); v.ids = (uint64_t*)(rc->mem + o_ids); v.scores = (double*)(rc->mem + o_sc);
+    rc->bytes = off; rc->stamp_bytes = r_count.off - r_stamp.off;   // (stamps and lengths are adjacent: one memset empties the table)
+    v.counters = r_cnt.at(rc->mem); v.stamp = r_stamp.at(rc->mem); v.len = r_len.at(rc->mem); v.count = r_count.at(rc->mem);
+    v.keys = r_keys.at(rc->mem); v.ids = r_ids.at(rc->mem); v.scores = r_sc.at(rc->mem);
     HIP_TRY(hipEventCreateWithFlags(&rc->ev, hipEventDisableTiming));
     HIP_TRY(hipStreamCreateWithFlags(&rc->own, hipStreamNonBlocking));
     HIP_TRY(hipMemsetAsync(rc->mem, 0, off, rc->own));

@@ -141,6 +141,14 @@ struct DeviceState {
 };
 
 // ---- shared helpers (srn_runtime.hip) ----
+// Regions of one buffer, carved before the buffer exists: take() reserves `bytes` at the cursor and moves it to the next multiple of `align`; the region is typed once the
+// base is known, region.at(base).  `bytes` is then the size to allocate
+struct Bump {
+    template <typename T> struct Region { size_t off; T* at(char* base) const { return (T*)(base + off); } };
+    size_t align, bytes = 0;
+    explicit Bump(size_t align_ = 256) : align(align_) {}
+    template <typename T> Region<T> take(size_t n_bytes) { const size_t o = bytes; bytes += (n_bytes + align - 1) / align * align; return Region<T>{o}; }
+};
 int ensure(char** p, size_t* have, size_t need, bool exact = false);   // grow-only device scratch (exact: no room to spare)
 int ensure_list(uint32_t** p, size_t* cap, size_t nq, size_t bytes);   // ... a list sized for `nq` queries: exactly `bytes`, *cap = nq
 
@@ -173,6 +181,9 @@ int device_predict_host_pipelined(DeviceState* d, const FlatIndex& ix, const Lau
                                   uint64_t* h_ids, double* h_scores, uint32_t* h_counts);
 uint32_t hostpipe_chunks(uint32_t nq, uint32_t how_many);
 std::shared_ptr<ResultCache> device_result_cache(DeviceState* d);   // the enabled cache, or null
+// a RowRule that filters, as one call carries it (predict_core): the lists (device pointers; a host-pointer call's are host pointers until exclude_host_room has copied
+// them), the caller's how_many and the caller-sized rows the filter writes behind the wide ones
+struct ExclSpec { const uint64_t* x_flat; const uint32_t* x_off; uint32_t max_excl; bool session; uint32_t how_many; uint64_t* out_ids; double* out_scores; uint32_t* out_counts; };
 // srn_exclude.hip: the wide rows' room in the workspace, and the filter kernel over them (x_flat / items_flat may be null)
 int exclude_wide_room(Workspace* w, uint32_t nq, uint32_t W, uint64_t** ids, double** scores, uint32_t** counts);
 int exclude_host_room(Workspace* w, hipStream_t st, uint32_t nq, ExclSpec& x);   // host-pointer calls: the lists' device copies and the caller-sized rows (the staged output rows are the wide ones)

@@ -1,6 +1,6 @@
 // =====================================================================================
 // Device runtime of libserenade_hip.so: index upload (row slots laid out on the device), per-call workspaces (own stream,
-// staging buffers, event ring), LDS geometry of a launch, the batch launch sequence (device_predict: plan, reserve, enqueue), the item-sharded pipeline's stages,
+// staging buffers, event ring), LDS geometry of a launch, the batch launch sequence (predict_core behind the device_predict_* entries: plan, reserve, enqueue), the item-sharded pipeline's stages,
 // timing and debug counters.  The latency paths live in srn_latency.hip, the kernels in srn_kernels.hip and srn_fast.hip.
 // =====================================================================================
 #include <hip/hip_runtime.h>
@@ -487,7 +487,7 @@ FastParams fast_params(const DeviceState* d, const FastBuffers& b, const FastPla
 }
 
 // ---- the batch launch sequence: plan -> reserve -> enqueue ----
-// What a call of device_predict will do, computed once from the index, the parameters, the knobs and the call's kind; nothing in it touches the device.
+// What a predict call (predict_core) will do, computed once from the index, the parameters, the knobs and the call's kind; nothing in it touches the device.
 struct LaunchPlan {
     Knobs kn; Geometry geo;
     bool retry = false;                                             // some query's session or item table may not fit LDS: the global-table pass stands behind the launch
@@ -565,41 +565,42 @@ struct BatchCall {
     hipEvent_t* ev = nullptr; bool timed = false, fork_retry = false;
     bool sback_second = false;   // the item shard's wave-per-query back end ran with the fast kernel's back-end form behind it (its list is the MID tier's: srn_debug_last_mid_count reports it)
     FastParams fp{};
-    ResultCache* rcache = nullptr; uint32_t cache_now = 0;   // (pl.cache) the index's result cache, held by device_predict for the length of the call; the call's number in it
+    ResultCache* rcache = nullptr; uint32_t cache_now = 0;   // (pl.cache) the index's result cache, held by predict_core for the length of the call; the call's number in it
 };
 
 // host-pointer calls: the staging buffer, p pointed at it, the inputs on their way
-static int stage_host_inputs(Workspace* w, hipStream_t st, LaunchParams& p, const uint64_t* h_items, const uint32_t* h_qoff, bool stats, bool nb) {
-    const size_t n_out = (size_t)p.nq * p.how_many, nitems = h_qoff[p.nq];
-    size_t off = 0; auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
-    const size_t o_items = take(nitems * 8), o_qoff = take(((size_t)p.nq + 1) * 4), o_ids = take(n_out * 8), o_sc = take(n_out * 8),
-                 o_cnt = take((size_t)p.nq * 4), o_st = take(stats ? (size_t)p.nq * 32 : 0),
-                 o_nr = take(nb ? (size_t)p.nq * p.k * 4 : 0), o_nn = take(nb ? (size_t)p.nq * p.k * 4 : 0),
-                 o_nc = take(nb ? (size_t)p.nq * 4 : 0);
-    int rc = ensure(&w->stage, &w->stage_bytes, off); if (rc) return rc;
+static int stage_host_inputs(Workspace* w, hipStream_t st, LaunchParams& p, const HostRows& h) {
+    const bool stats = h.stats != nullptr, nb = h.nb_rank != nullptr;
+    const size_t n_out = (size_t)p.nq * p.how_many, nitems = h.q_off[p.nq];
+    Bump b;
+    const auto r_items = b.take<const uint64_t>(nitems * 8); const auto r_qoff = b.take<const uint32_t>(((size_t)p.nq + 1) * 4);
+    const auto r_ids = b.take<uint64_t>(n_out * 8); const auto r_sc = b.take<double>(n_out * 8); const auto r_cnt = b.take<uint32_t>((size_t)p.nq * 4);
+    const auto r_st = b.take<uint32_t>(stats ? (size_t)p.nq * 32 : 0);
+    const auto r_nr = b.take<uint32_t>(nb ? (size_t)p.nq * p.k * 4 : 0), r_nn = b.take<uint32_t>(nb ? (size_t)p.nq * p.k * 4 : 0), r_nc = b.take<uint32_t>(nb ? (size_t)p.nq * 4 : 0);
+    int rc = ensure(&w->stage, &w->stage_bytes, b.bytes); if (rc) return rc;
     char* s = w->stage;
-    p.items_flat = (const uint64_t*)(s + o_items); p.q_off = (const uint32_t*)(s + o_qoff);
-    p.out_ids = (uint64_t*)(s + o_ids); p.out_scores = (double*)(s + o_sc); p.out_counts = (uint32_t*)(s + o_cnt);
-    p.stats = stats ? (uint32_t*)(s + o_st) : nullptr;
-    p.nb_rank = nb ? (uint32_t*)(s + o_nr) : nullptr; p.nb_num = nb ? (uint32_t*)(s + o_nn) : nullptr;
-    p.nb_cnt = nb ? (uint32_t*)(s + o_nc) : nullptr;
+    p.items_flat = r_items.at(s); p.q_off = r_qoff.at(s);
+    p.out_ids = r_ids.at(s); p.out_scores = r_sc.at(s); p.out_counts = r_cnt.at(s);
+    p.stats = stats ? r_st.at(s) : nullptr;
+    p.nb_rank = nb ? r_nr.at(s) : nullptr; p.nb_num = nb ? r_nn.at(s) : nullptr;
+    p.nb_cnt = nb ? r_nc.at(s) : nullptr;
     HIP_TRY(hipMemsetAsync(p.out_ids, 0, n_out * 8, st));      // unused tail of each row reads as 0
     HIP_TRY(hipMemsetAsync(p.out_scores, 0, n_out * 8, st));
-    HIP_TRY(hipMemcpyAsync((void*)p.items_flat, h_items, nitems * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync((void*)p.q_off, h_qoff, ((size_t)p.nq + 1) * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync((void*)p.items_flat, h.items, nitems * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync((void*)p.q_off, h.q_off, ((size_t)p.nq + 1) * 4, hipMemcpyHostToDevice, st));
     return SRN_OK;
 }
 // ... and the results back, then the wait for them
-static int fetch_host_outputs(const BatchCall& c, uint64_t* h_ids, double* h_scores, uint32_t* h_counts, uint32_t* h_stats, uint32_t* h_nb_rank, uint32_t* h_nb_num, uint32_t* h_nb_cnt) {
+static int fetch_host_outputs(const BatchCall& c, const HostRows& h) {
     const LaunchParams& p = c.p; hipStream_t st = c.st; const size_t n_out = (size_t)p.nq * p.how_many;
-    HIP_TRY(hipMemcpyAsync(h_ids, p.out_ids, n_out * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(h_scores, p.out_scores, n_out * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(h_counts, p.out_counts, (size_t)p.nq * 4, hipMemcpyDeviceToHost, st));
-    if (h_stats) HIP_TRY(hipMemcpyAsync(h_stats, p.stats, (size_t)p.nq * 32, hipMemcpyDeviceToHost, st));
-    if (h_nb_rank) {
-        HIP_TRY(hipMemcpyAsync(h_nb_rank, p.nb_rank, (size_t)p.nq * p.k * 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(h_nb_num, p.nb_num, (size_t)p.nq * p.k * 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(h_nb_cnt, p.nb_cnt, (size_t)p.nq * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(h.ids, p.out_ids, n_out * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(h.scores, p.out_scores, n_out * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(h.counts, p.out_counts, (size_t)p.nq * 4, hipMemcpyDeviceToHost, st));
+    if (h.stats) HIP_TRY(hipMemcpyAsync(h.stats, p.stats, (size_t)p.nq * 32, hipMemcpyDeviceToHost, st));
+    if (h.nb_rank) {
+        HIP_TRY(hipMemcpyAsync(h.nb_rank, p.nb_rank, (size_t)p.nq * p.k * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(h.nb_num, p.nb_num, (size_t)p.nq * p.k * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(h.nb_cnt, p.nb_cnt, (size_t)p.nq * 4, hipMemcpyDeviceToHost, st));
     }
     HIP_TRY(hipStreamSynchronize(st));
     return SRN_OK;
@@ -785,16 +786,30 @@ static int enqueue_batch(BatchCall& c, bool on_device) {
     return enqueue_tail(c);
 }
 
-int device_predict(DeviceState* d, const FlatIndex& ix, const LaunchParams& p_in, bool on_device, void* user_stream,
-                   const uint64_t* h_items, const uint32_t* h_qoff, uint64_t* h_ids, double* h_scores, uint32_t* h_counts,
-                   uint32_t* h_stats, uint32_t* h_nb_rank, uint32_t* h_nb_num, uint32_t* h_nb_cnt, const ExtLists* ext, bool reserve_only, bool blocking_wait, const ExclSpec* excl, bool fill) {
+// What one call is, beyond its LaunchParams: each entry below fills in its own kind and nothing else.  host: a host-pointer call (null: device buffers on `stream`);
+// ext: the shard group's pipelines; reserve_only (srn_index_reserve): size the call's workspace, enqueue nothing
+struct CallKind { void* stream = nullptr; const HostRows* host = nullptr; const ExtLists* ext = nullptr; const RowRule* rule = nullptr; bool reserve_only = false, blocking_wait = false; };
+
+// every predict call: plan -> reserve -> enqueue, with the row rule's filter and fill kernels behind the launch sequence
+static int predict_core(DeviceState* d, const FlatIndex& ix, const LaunchParams& p_in, const CallKind& kind) {
+    const HostRows* const host = kind.host; const ExtLists* const ext = kind.ext; const bool on_device = !host, reserve_only = kind.reserve_only;
+    void* const user_stream = kind.stream;
     HIP_TRY(hipSetDevice(d->device));
     LaunchParams p = p_in;
     if (p.nq == 0) return SRN_OK;
-    if (excl && (ext || h_stats || h_nb_rank)) return fail(SRN_EINVAL, "exclusion lists: batch calls on an unsharded index only");
-    if (fill && (ext || h_stats || h_nb_rank || reserve_only || (!on_device && !excl))) return fail(SRN_EINVAL, "SRN_FLAG_FILL: batch calls on an unsharded index only");
+    const bool fill = kind.rule && kind.rule->fill;
     if (fill && !device_has_fallback(d)) return fail(SRN_ESTATE, "SRN_FLAG_FILL: the index has no fallback ranking (srn_index_set_fallback)");
-    ExclSpec xs{}; if (excl) xs = *excl;
+    // The row rule (srn_exclude.hip): with something to exclude the launch sequence runs at the internal, wide how_many and writes wide rows -- the workspace's scratch; a
+    // host-pointer call's staged rows -- and the filter behind it the caller's.  Where the width is the caller's own, nothing can be excluded: the plain call, no scratch,
+    // no filter kernel (fill: in place on the rows) -- but a host-pointer call's rows pass through the filter's buffers all the same: the fill kernel works on device rows
+    const uint32_t wide = kind.rule ? (uint32_t)wide_how_many(p.how_many, kind.rule->max_excl, kind.rule->session, p.max_len) : p.how_many;
+    const bool excl = wide != p.how_many || (host && fill);
+    ExclSpec xs{};
+    if (excl) {
+        const RowRule& r = *kind.rule;
+        xs = ExclSpec{r.max_excl ? r.x_flat : nullptr, r.max_excl ? r.x_off : nullptr, r.max_excl, r.session, p.how_many, p.out_ids, p.out_scores, p.out_counts};
+        p.how_many = wide; p.out_ids = nullptr; p.out_scores = nullptr; p.out_counts = nullptr;
+    }
     // SRN_FLAG_INPUTS_RESIDENT (device-pointer calls): the query buffers are complete in device memory at call time, so the prep kernel of THIS call may run on a side
     // stream while the previous call's kernels still occupy the caller's stream (enqueue_front_resident); the kernels never see the flag
     const bool resident = on_device && !ext && (p.flags & SRN_FLAG_INPUTS_RESIDENT) != 0u;
@@ -813,20 +828,18 @@ int device_predict(DeviceState* d, const FlatIndex& ix, const LaunchParams& p_in
     hipStream_t st = on_device ? (hipStream_t)user_stream : w->stream;
     Geometry geo; { int rc = make_geometry(d, ix, p, 0, geo); if (rc) return rc; }
 
-    if (!on_device && !reserve_only && !h_stats && !h_nb_rank && !excl) {
+    if (host && !host->stats && !host->nb_rank && !excl) {
         if (p.nq <= (uint32_t)knobs().tiny_max && !d->phase_on) {
-            const int rc = device_predict_tiny(d, ix, w, geo, p, h_items, h_qoff, h_ids, h_scores, h_counts, blocking_wait);
+            const int rc = device_predict_tiny(d, ix, w, geo, p, host->items, host->q_off, host->ids, host->scores, host->counts, kind.blocking_wait);
             if (rc != 1) { if (rcache) rcache->bypassed.fetch_add(1, std::memory_order_relaxed); return rc; }   // (1: some query needs the global-table pass -- the paths below have it)
         }
         // everything larger: chunks through pinned staging, uploads / kernels / downloads overlapped (srn_hostpipe.hip); each chunk comes back here as a
         // device-pointer call on one of the pipeline's kernel streams.  (This call's own workspace goes back to the pool first.)
         ws_release(d, w, false); rel.w = nullptr;
-        return device_predict_host_pipelined(d, ix, p, h_items, h_qoff, h_ids, h_scores, h_counts);
+        return device_predict_host_pipelined(d, ix, p, host->items, host->q_off, host->ids, host->scores, host->counts);
     }
     // ---- plan -> reserve -> enqueue ----
-    if (!on_device) { int rc = stage_host_inputs(w, st, p, h_items, h_qoff, h_stats != nullptr, h_nb_rank != nullptr); if (rc) return rc; }   // (p.stats / p.nb_rank decide the plan)
-    // exclusion lists (srn_exclude.hip): p.how_many is the internal, wide one -- the launch sequence writes wide rows (the workspace's scratch; a host-pointer call's staged
-    // rows), the filter behind it the caller's
+    if (host) { int rc = stage_host_inputs(w, st, p, *host); if (rc) return rc; }   // (p.stats / p.nb_rank decide the plan)
     if (excl) { int rc = on_device ? exclude_wide_room(w, p.nq, p.how_many, &p.out_ids, &p.out_scores, &p.out_counts) : exclude_host_room(w, st, p.nq, xs); if (rc) return rc; }
     const LaunchPlan pl = make_plan(d, ix, p, geo, ext, resident, w, no_cache ? nullptr : rcache.get());
     BatchCall c{d, w, pl, ext, st, di, p}; c.rcache = rcache.get();
@@ -843,8 +856,23 @@ int device_predict(DeviceState* d, const FlatIndex& ix, const LaunchParams& p_in
     // merged or cached above are the unfilled rows
     if (fill) HIP_TRY(excl ? launch_fill(st, d, p.nq, xs.out_ids, xs.out_scores, xs.out_counts, xs.how_many, xs.x_flat, xs.x_off, p.items_flat, p.q_off, xs.session, (p.flags & SRN_FLAG_BUSINESS_LOGIC) != 0u)
                            : launch_fill(st, d, p.nq, p.out_ids, p.out_scores, p.out_counts, p.how_many, nullptr, nullptr, p.items_flat, p.q_off, false, (p.flags & SRN_FLAG_BUSINESS_LOGIC) != 0u));
-    if (excl && !on_device) return exclude_fetch_host(st, p.nq, xs, h_ids, h_scores, h_counts);
-    return on_device ? SRN_OK : fetch_host_outputs(c, h_ids, h_scores, h_counts, h_stats, h_nb_rank, h_nb_num, h_nb_cnt);
+    if (excl && host) return exclude_fetch_host(st, p.nq, xs, host->ids, host->scores, host->counts);
+    return host ? fetch_host_outputs(c, *host) : SRN_OK;
+}
+
+int device_predict_device(DeviceState* d, const FlatIndex& ix, const LaunchParams& p, void* stream, const RowRule& rule) {
+    CallKind kind; kind.stream = stream; kind.rule = &rule;
+    return predict_core(d, ix, p, kind);
+}
+int device_predict_host(DeviceState* d, const FlatIndex& ix, const LaunchParams& p, const HostRows& rows, const RowRule& rule, bool blocking_wait) {
+    if ((rows.stats || rows.nb_rank) && (rule.max_excl || rule.session || rule.fill)) return fail(SRN_EINVAL, "exclusion lists, SRN_FLAG_FILL: batch calls without statistics or the neighbour dump only");
+    CallKind kind; kind.host = &rows; kind.rule = &rule; kind.blocking_wait = blocking_wait;
+    return predict_core(d, ix, p, kind);
+}
+// the shard group's three pipelines: device buffers, prep records and posting lists from the exchange (ExtLists)
+static int predict_ext(DeviceState* d, const FlatIndex& ix, const LaunchParams& p, void* stream, const ExtLists& ext) {
+    CallKind kind; kind.stream = stream; kind.ext = &ext;
+    return predict_core(d, ix, p, kind);
 }
 
 // One stage of the item-sharded pipeline (device buffers, asynchronous on `stream`); see ShardIO.  Like the unsharded launch sequence, a stage has a second pass
@@ -891,7 +919,7 @@ bool device_shard_lists_supported(DeviceState* d, const FlatIndex& ix, const Lau
     Geometry g;
     return make_geometry(d, ix, p, 0, g) == SRN_OK && g.masks && (p.flags & ~(unsigned)SRN_FLAG_BUSINESS_LOGIC) == 0 && p.stats == nullptr && p.nb_rank == nullptr;
 }
-// the batch shape the fast kernel takes (the same test device_predict makes): what the shard group's neighbours pipeline needs on top of lists mode
+// the batch shape the fast kernel takes (the same test a predict call makes): what the shard group's neighbours pipeline needs on top of lists mode
 // (the shard group's choice of pipeline must be the SAME on every rank: `max_row_len_all` = the longest row of the whole index -- a shard's own longest fragment differs from
 //  rank to rank and is never longer -- and the packed rows, which device_attach may fail to allocate on ONE rank, are checked where the postings are set, not here)
 bool device_fast_eligible(DeviceState* d, const FlatIndex& ix, const LaunchParams& p, uint64_t max_row_len_all) {
@@ -932,7 +960,7 @@ int device_shard_lists_predict(DeviceState* d, const FlatIndex& ix, const Launch
     const uint32_t stride = device_prep_stride(p.max_len);
     HIP_TRY(launch_shard_prep((hipStream_t)stream, p.items_flat, p.q_off, p.nq, p.max_len, n_shards, kept_g, off_g, shard_stride, head, (const ShardPos*)pos_local, records, stride, shard_base, direct));
     ExtLists ext{records, stride, direct ? d->di.post_rank : lists_g};
-    return device_predict(d, ix, p, true, stream, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &ext);
+    return predict_ext(d, ix, p, stream, ext);
 }
 
 // ---- item-sharded index, neighbours pipeline (round 4): the posting lists are replicated (`post` = the device state of the whole index or of its postings-only view),
@@ -953,7 +981,7 @@ int device_shard_nb_front(DeviceState* d, const FlatIndex& ix, DeviceState* post
     if (q_lo >= q_hi) return SRN_OK;
     LaunchParams p = p_in; p.nq = q_hi;
     ExtLists ext{records, device_prep_stride(p.max_len), post->di.post_rank, 1, xchg, xchg_stride, q_lo};
-    return device_predict(d, ix, p, true, stream, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &ext);
+    return predict_ext(d, ix, p, stream, ext);
 }
 // the fronting rank's neighbour lists [q_lo, q_hi) of `xin` -> position records in `xout` (the streaming form's exchange format, srn_sback.hip)
 int device_shard_nb_positions(DeviceState* d, const FlatIndex& ix, DeviceState* post, const LaunchParams& p, const char* records, const uint32_t* xin, uint32_t in_stride, uint32_t* xout, uint32_t out_stride,
@@ -974,11 +1002,11 @@ uint32_t device_shard_nb_positions_stride(const LaunchParams& p) {
 int device_shard_nb_back(DeviceState* d, const FlatIndex& ix, DeviceState* post, const LaunchParams& p, const char* records, uint32_t* xchg, uint32_t xchg_stride, void* stream, const unsigned long long* order, bool positions) {
     if (p.nq == 0) return SRN_OK;
     ExtLists ext{records, device_prep_stride(p.max_len), post->di.post_rank, 2, xchg, xchg_stride, 0u, order, positions};
-    return device_predict(d, ix, p, true, stream, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &ext);
+    return predict_ext(d, ix, p, stream, ext);
 }
 
 int device_slot_bytes(DeviceState* d, const FlatIndex& ix, uint32_t max_len, uint32_t* num_bits) {   // element size of the packed candidate / neighbour buffers
-    LaunchParams p{}; p.max_len = max_len; p.k = 1; p.m = 1; Geometry g;
+    const LaunchParams p = launch_params(0, 1, 1, 0, 0, max_len); Geometry g;
     if (make_geometry(d, ix, p, 0, g) != SRN_OK) return -1;
     if (num_bits) *num_bits = g.c.num_bits;
     return (int)g.slot_bytes;
@@ -1006,7 +1034,8 @@ int device_last_kernel_ms(DeviceState* d, double* ms_main, double* ms_retry, uin
 // Sizes the workspace bound to `stream` for device-pointer calls of up to nq queries with these parameters, so that
 // srn_predict_batch_device allocates nothing (hipMalloc / hipFree synchronise the device) once traffic starts.
 int device_reserve(DeviceState* d, const FlatIndex& ix, const LaunchParams& p, void* stream) {
-    return device_predict(d, ix, p, true, stream, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, /*reserve_only=*/true);
+    CallKind kind; kind.stream = stream; kind.reserve_only = true;
+    return predict_core(d, ix, p, kind);
 }
 
 int device_last_path_counts(DeviceState* d, uint32_t* nq, uint32_t* general, uint32_t* global_pass) {

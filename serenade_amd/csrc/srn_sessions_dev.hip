@@ -2,7 +2,7 @@
 //
 // srn_recommend (srn_session_store.cpp) is the handler body for ONE request against a host table.  Here the table lives in HBM and one call applies the
 // handler's update rule (recommend_resource.rs:39-56, sessions/mod.rs:37-72) to a whole batch of (key, clicked item, consent) triples, exactly as if the
-// requests had been served one after the other, and predicts every request's session through device_predict -- the launch sequence of srn_predict_batch_device.
+// requests had been served one after the other, and predicts every request's session through device_predict_device -- the launch sequence of srn_predict_batch_device.
 //
 // The table: power-of-two open addressing, linear probing, load <= 0.5, no tombstones (a sweep rebuilds into the second table).  One slot per visitor:
 //   { key_hi u64 | key_lo u64 | epoch u64 | len u32 | state u32 | items u64[items_cap] }   rounded up to a multiple of 128 bytes, 128-byte aligned
@@ -19,7 +19,7 @@
 //   sess_len        window lengths in ORIGINAL request order + the kept clicks compacted; exclusive scan -> q_off
 //   sess_emit       every request copies its window into items_flat: O(window) per request, whatever the run's length
 //   sess_store      the last request of a run writes its window -- the final session -- and the epoch back, once
-//   device_predict  on (items_flat, q_off)
+//   device_predict_device  on (items_flat, q_off)
 // With a history window (srn_device_sessions_set_history) the store keeps the last H clicks under the same rules -- H takes the limit's place in sess_len and
 // sess_store -- and predict reads the last min(window, max_items_in_session) items of each window: sess_len writes that length too, a second scan gives p_off, and
 // sess_emit copies the window's suffix into a second buffer.  SRN_FLAG_EXCLUDE_SEEN hands the windows (items_flat, q_off) to the exclusion filter (srn_exclude.hip) as the
@@ -593,8 +593,8 @@ static int recommend_no_store(const srn_index* idx, const uint64_t* d_item, cons
     HIP_TRY(hipMalloc((void**)&q_off, (n + 1) * 4));
     sess_iota<<<grid_for(n + 1), kTPB, 0, st>>>((uint32_t)n, q_off);
     p.max_len = 1; p.items_flat = d_item; p.q_off = q_off;
-    int rc = hipGetLastError() == hipSuccess ? device_predict(idx->dev, idx->flat, p, true, st, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, false, false, nullptr, fill)
-                                             : fail(SRN_EHIP, "sess_iota launch failed");
+    RowRule rule; rule.fill = fill;
+    int rc = hipGetLastError() == hipSuccess ? device_predict_device(idx->dev, idx->flat, p, st, rule) : fail(SRN_EHIP, "sess_iota launch failed");
     (void)hipStreamSynchronize(st);
     (void)hipFree(q_off);
     return rc;
@@ -607,10 +607,8 @@ int dsess_recommend_device(const srn_index* idx, srn_device_sessions* s, const u
     if (max_items == 0) return fail(SRN_EINVAL, "srn_recommend_batch: max_items_in_session must be > 0");
     if (n > kMaxBatch) return fail(SRN_ERANGE, "srn_recommend_batch: more than 2^24 requests in one call");
     hipStream_t st = (hipStream_t)stream;
-    LaunchParams p{};
     const bool excl_seen = (flags & SRN_FLAG_EXCLUDE_SEEN) != 0u, fill = (flags & SRN_FLAG_FILL) != 0u;   // (SRN_FLAG_FILL: srn_fill.hip, behind the call's launch sequence and filter)
-    p.nq = (uint32_t)n; p.k = (uint32_t)k; p.m = (uint32_t)m; p.how_many = (uint32_t)how_many; p.flags = flags & ~(unsigned)(SRN_FLAG_EXCLUDE_SEEN | SRN_FLAG_FILL);
-    p.out_ids = d_ids; p.out_scores = d_scores; p.out_counts = d_counts;
+    LaunchParams p = launch_params(n, k, m, how_many, flags & ~(unsigned)(SRN_FLAG_EXCLUDE_SEEN | SRN_FLAG_FILL), 0, nullptr, nullptr, d_ids, d_scores, d_counts);   // (the sessions: below)
     if (!s) {   // (every session is its item, which is never in its own row: SRN_FLAG_EXCLUDE_SEEN has nothing to exclude)
         if (max_items > SRN_MAX_SESSION_LEN) return fail(SRN_ERANGE, "srn_recommend_batch: max_items_in_session above SRN_MAX_SESSION_LEN");
         return recommend_no_store(idx, d_item, d_consent, n, p, st, fill);
@@ -697,12 +695,9 @@ int dsess_recommend_device(const srn_index* idx, srn_device_sessions* s, const u
     p.max_len = phint; p.items_flat = H ? a.pflat : a.items_flat; p.q_off = H ? a.p_off : a.q_off;
     s->last_items = p.items_flat; s->last_qoff = p.q_off; s->last_n = n; s->last_hint = phint;
     if (timed) (void)hipEventRecord(s->tev[1], st);
-    if (excl_seen) {   // the windows are the exclusion CSR, the bound of their lengths its capacity: the launch sequence runs at how_many + hint (srn_exclude.hip)
-        const ExclSpec x{a.items_flat, a.q_off, hint, false, (uint32_t)how_many, d_ids, d_scores, d_counts};
-        p.how_many = (uint32_t)how_many + hint; p.out_ids = nullptr; p.out_scores = nullptr; p.out_counts = nullptr;
-        rc = device_predict(idx->dev, idx->flat, p, true, st, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, false, false, &x, fill);
-    } else
-        rc = device_predict(idx->dev, idx->flat, p, true, st, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, false, false, nullptr, fill);
+    RowRule rule; rule.fill = fill;
+    if (excl_seen) { rule.x_flat = a.items_flat; rule.x_off = a.q_off; rule.max_excl = hint; }   // the windows are the exclusion CSR, the bound of their lengths its capacity: the launch sequence runs at how_many + hint (srn_exclude.hip)
+    rc = device_predict_device(idx->dev, idx->flat, p, st, rule);
     (void)hipSetDevice(s->device);
     if (timed) (void)hipEventRecord(s->tev[2], st);
     s->last_timed = timed;
@@ -751,10 +746,7 @@ int dsess_recommend_host(const srn_index* idx, srn_device_sessions* s, const uin
     };
     const int rc = run();
     if (own_buf) (void)hipFree(own_buf);
-    if (rc) return rc;
-    for (size_t q = 0; q < n; ++q)
-        if (counts[q] == 0xFFFFFFFFu) return fail(SRN_ERANGE, "a query exceeded the kernel's table limits");
-    return SRN_OK;
+    return rc ? rc : check_all_served(counts, n);
 }
 
 // ---- snapshot: count, bulk export / import, resize, growth, the file form ----
