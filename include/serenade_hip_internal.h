@@ -77,6 +77,14 @@ int srn_debug_class_counts(const uint64_t* acc, size_t n_waves, uint32_t* out16,
 #define SRN_DEBUG_MERGE_ROOM 12032
 int srn_debug_merge_pair(uint32_t* room, const uint32_t* pairs, size_t n_pairs, int device);
 
+/* Test aid (tests/test_gpu_ready_record.py): the prep kernel alone.  Writes the prep records of the batch (request q = items_flat[q_off[q] .. q_off[q + 1]), oldest item
+ * first) for neighbourhood cut m and sessions of up to max_len items, as a predict call on this index would, and copies them to out_records: *out_stride bytes per record
+ * = an 18-word head, the 16-word launch-ready block the lean fast kernel starts from, then max_len entries of 6 words {idx, len, pre, kept, base (64-bit)}, position 0 =
+ * the most recent item.  A session of 0 or of more than max_len items has no item entries (zeros).  cap_bytes < nq * stride: SRN_ERANGE, with
+ * *out_stride set.  HOST pointers; blocks until the records are back. */
+int srn_debug_prep_records(const srn_index_t* idx, const uint64_t* items_flat, const uint32_t* q_off, size_t nq, size_t m, size_t max_len, void* out_records, size_t cap_bytes,
+                           size_t* out_stride);
+
 /* Test / experiment knobs (environment variables SRN_NO_FAST, SRN_NO_MID, SRN_NO_MASKS, SRN_NO_MERGE, SRN_HOT_SLOTS,
  * SRN_SKETCH_SLOTS, SRN_LDS_BUDGET_KB, SRN_GRID_MULT, SRN_DEBUG) force individual kernel code paths.  They are read ONCE,
  * when the library is first used -- never on the launch path; this call re-reads them (the parity tests switch paths

@@ -689,6 +689,10 @@ int srn_debug_last_mid_count(const srn_index_t* idx, uint32_t* out_listed) {
     if (!idx || !idx->dev) return fail(SRN_ENODEV, "index has no device attached");
     return guarded([&]() -> int { return device_last_mid_count(idx->dev, out_listed); });
 }
+int srn_debug_prep_records(const srn_index_t* idx, const uint64_t* items_flat, const uint32_t* q_off, size_t nq, size_t m, size_t max_len, void* out_records, size_t cap_bytes, size_t* out_stride) {
+    if (!idx || !idx->dev) return fail(SRN_ENODEV, "index has no device attached");
+    return guarded([&]() -> int { return device_debug_prep_records(idx->dev, idx->flat, items_flat, q_off, nq, m, max_len, out_records, cap_bytes, out_stride); });
+}
 int srn_debug_last_dedup_count(const srn_index_t* idx, uint32_t* out_merged) {
     if (!idx || !idx->dev || !out_merged) return fail(SRN_EINVAL, "null argument");
     return guarded([&]() -> int { return device_last_dedup_count(idx->dev, out_merged); });

@@ -423,7 +423,8 @@ __global__ __launch_bounds__(512, TINY ? SRN_TINY_WAVES : BIG ? 4 : SRN_FAST_WAV
     // (with a dynamic allocation each computed address pays a v_add of the -- zero -- base: two per row item in the walks)
     static_assert(!BIG || MID, "BIG is a form of MID"); static_assert(!LONG || BIG, "LONG is a form of BIG");
     constexpr uint32_t SIDF = BIG ? F_BIG_TOTAL - (F_TOTAL - F_SIDF) : F_SIDF, SATTR = SIDF + 512 * 8;   // per-thread sample constants: behind the merge buffers' room
-    constexpr uint32_t MW = (SIDF - F_WORK) / 4;   // words the merge buffers may use (= F_MERGE_WORDS in the 53 KB layout)
+    constexpr uint32_t MW = (SIDF - F_WORK) / 4;   // words the merge buffers may use
+    static_assert(BIG || MW == F_LEAN_MW, "the prep record's lean_ok (ready_words, srn_prep.h) is evaluated for the 53 KB layout's merge room");
     __shared__ __attribute__((aligned(16))) char smem[BIG ? F_BIG_TOTAL : F_TOTAL];
 #else
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -452,8 +453,8 @@ __global__ __launch_bounds__(512, TINY ? SRN_TINY_WAVES : BIG ? 4 : SRN_FAST_WAV
         const uint32_t alen = f.tiny_len;
         if (f.serve == nullptr) {   // (the persistent form writes the record per request, at the top of the loop below)
         if (alen) { if (tid < 8u) a_items[tid] = f.tiny_items[tid]; if (tid == 0u) { a_off[0] = 0u; a_off[1] = alen; } __syncthreads(); }
-        if (tid < PREP_LANES) prep_group(ix_arg, alen ? (const uint64_t*)a_items : p.items_flat, alen ? (const uint32_t*)a_off : p.q_off, alen ? 0u : blockIdx.x, tid, p.m, p.max_len,
-                                         const_cast<char*>(p.prep) + (size_t)blockIdx.x * p.prep_stride, nullptr, 0u, nullptr);
+        if (tid < PREP_LANES) prep_group<false>(ix_arg, alen ? (const uint64_t*)a_items : p.items_flat, alen ? (const uint32_t*)a_off : p.q_off, alen ? 0u : blockIdx.x, tid, p.m, p.max_len,
+                                         const_cast<char*>(p.prep) + (size_t)blockIdx.x * p.prep_stride, nullptr, 0u, nullptr, WIDE);   // (no launch-ready block: READY below)
         __syncthreads();   // (workgroup-scope release / acquire: the record's words for every wave)
         }
     }
@@ -494,7 +495,7 @@ __global__ __launch_bounds__(512, TINY ? SRN_TINY_WAVES : BIG ? 4 : SRN_FAST_WAV
 
     // The NEXT query's record is fetched during this one by wave 1 and parked in LDS: a query's critical path then starts with the list loads, not with the record's
     // HBM round trip followed by theirs.  The record goes from global memory STRAIGHT into LDS (global_load_lds, one dword per lane, no registers held; uncounted by
-    // the compiler: glds_dword_uncounted above): words 0..17 = PrepHead, words 18 + 6 l .. = item l.  (The 448 bytes behind the 16 entries the weight table uses are free.)
+    // the compiler: glds_dword_uncounted above): words 0..33 = PrepHead (18..33: the launch-ready block), words 34 + 6 l .. = item l.  (Behind the 16 entries the weight table uses: 352 bytes up to F_SINV.)
     // WHEN: in walk A, behind wave 1's own row requests; the wave waits for it (an explicit s_waitcnt vmcnt(0): the compiler knows of no load) at the end of phase 4a,
     // and the barrier behind that wait publishes it.  A query that leaves before walk A (no known item, not admitted, handed on) parks nothing: its successor reads its
     // record from global memory.
@@ -503,7 +504,8 @@ __global__ __launch_bounds__(512, TINY ? SRN_TINY_WAVES : BIG ? 4 : SRN_FAST_WAV
     //  18.844 ms against this placement's 18.686, parent 18.917; built from one source, 18.843 early against 18.820 in walk A, parent 18.890 (medians of three,
     //  profiles/record_prefetch_ab.txt).  With the phase clock on wave 1 the record costs that wave ~680 cycles of walk A, and the wave still stands 690 cycles at
     //  walk A's closing barrier: it is not the wave the others wait for.)
-    uint32_t* const pre = (uint32_t*)(smem + F_W10 + 64);
+    constexpr uint32_t F_PRE = F_W10 + 32u;   // (right behind the weight table's 16 entries: a lean record of 328 bytes ends in front of F_SINV)
+    uint32_t* const pre = (uint32_t*)(smem + F_PRE);
     bool have_pre = false;   // block-uniform
     { const ItemMeta m0 = f.meta_sample[tid];
       ((double*)(smem + SIDF))[tid] = m0.idf > 0.0 ? m0.idf : 1.0; ((uint8_t*)(smem + SATTR))[tid] = (uint8_t)m0.attr;   // (own slot only: no barrier)
@@ -572,7 +574,7 @@ __global__ __launch_bounds__(512, TINY ? SRN_TINY_WAVES : BIG ? 4 : SRN_FAST_WAV
                 }
                 __syncthreads();
                 if (sv_flag[0] != 0u) break;   // (block-uniform)
-                if (tid < PREP_LANES) prep_group(ix_arg, (const uint64_t*)sv_items, (const uint32_t*)sv_off, 0u, tid, p.m, p.max_len, const_cast<char*>(p.prep) + (size_t)blockIdx.x * p.prep_stride, nullptr, 0u, nullptr);
+                if (tid < PREP_LANES) prep_group<false>(ix_arg, (const uint64_t*)sv_items, (const uint32_t*)sv_off, 0u, tid, p.m, p.max_len, const_cast<char*>(p.prep) + (size_t)blockIdx.x * p.prep_stride, nullptr, 0u, nullptr, WIDE);   // (no launch-ready block: READY below)
                 __syncthreads();
                 if (tid == 0u) c->stamp[1] = (uint32_t)(wall_clock64() - serve_t0);
             }
@@ -590,30 +592,61 @@ __global__ __launch_bounds__(512, TINY ? SRN_TINY_WAVES : BIG ? 4 : SRN_FAST_WAV
         const char* const rec = p.prep + (size_t)q * p.prep_stride;
         struct { uint32_t U, rmax, xlo, sumw, L, n_staged, cur_attr, unsafe; } hd;
         constexpr uint32_t HW = (uint32_t)sizeof(PrepHead) / 4u;   // record words before the items
+        constexpr uint32_t RW0 = (uint32_t)offsetof(PrepHead, ready) / 4u;   // ... and before the launch-ready block
+        // READY (the lean forms with a front end): the routing predicate and the run descriptors come ready-made in the record's launch-ready block (ReadyWord,
+        // srn_kernels.h: written once per query by the prep kernel), lanes 0..15 hold its 16 words and readlanes with constant lane numbers hand them out -- no ballot, no
+        // ffs loop over the items, no `fits` ladder in front of the list loads.  A query whose lean_ok is clear takes the decode of the other forms, for the routing alone.
+        // TINY (one workgroup = one query, the record written by its own first eight lanes just before): the block's work would stand serially IN FRONT of the query instead of
+        // in a kernel of its own -- measured, one query per call 36.5 us against 35.9 (profiles/ready_record_ab.txt); it writes a zero block and decodes the items as before.
+        constexpr bool READY = !MID && MODE != FM_BACK && !TINY;
+        static_assert(!READY || sizeof(PrepHead) + 8u * sizeof(PrepItem) <= 128u * 4u, "a lean record lies inside the 128 words wave 1 parks");
         struct { uint32_t idx, kept; unsigned long long base; } x0{kNone, 0u, 0ull};
-        if (have_pre) {
-            auto uni = [&](uint32_t w) -> uint32_t { return (uint32_t)__builtin_amdgcn_readfirstlane((int)pre[w]); };   // (SGPRs: the branches on these stay scalar)
-            hd.U = uni(0); hd.rmax = uni(1); hd.xlo = uni(2); hd.sumw = uni(3); hd.L = uni(6); hd.n_staged = uni(7); hd.cur_attr = uni(16); hd.unsafe = uni(17);
-            if (lane < (LONG ? 32u : MID ? 16u : 8u) && lane < hd.L) { const uint32_t* it = pre + HW + 6u * lane; x0.idx = it[0]; x0.kept = it[3]; x0.base = ((unsigned long long)it[5] << 32) | it[4]; }
-        } else {
-            const PrepHead h0 = *(const PrepHead*)rec;   // (uniform address)
-            hd.U = h0.U; hd.rmax = h0.rmax; hd.xlo = h0.xlo; hd.sumw = h0.sumw; hd.L = h0.L; hd.n_staged = h0.n_staged; hd.cur_attr = h0.cur_attr; hd.unsafe = h0.unsafe;
-            if ((MID ? lane < (LONG ? 32u : 16u) && lane < p.max_len : lane < 8u) && lane < hd.L) { const PrepItem pi = ((const PrepItem*)(rec + sizeof(PrepHead)))[lane]; x0.idx = pi.idx; x0.kept = pi.kept; x0.base = pi.base; }
-        }
+        const bool from_pre = have_pre;   // block-uniform
         have_pre = false;
+        auto uni = [&](uint32_t w) -> uint32_t { return (uint32_t)__builtin_amdgcn_readfirstlane((int)pre[w]); };   // (SGPRs: the branches on these stay scalar)
+        auto load_x0 = [&]() {   // lane l: the item at position l
+            if (from_pre) { if (lane < (LONG ? 32u : MID ? 16u : 8u) && lane < hd.L) { const uint32_t* it = pre + HW + 6u * lane; x0.idx = it[0]; x0.kept = it[3]; x0.base = ((unsigned long long)it[5] << 32) | it[4]; } }
+            else if ((MID ? lane < (LONG ? 32u : 16u) && lane < p.max_len : lane < 8u) && lane < hd.L) { const PrepItem pi = ((const PrepItem*)(rec + sizeof(PrepHead)))[lane]; x0.idx = pi.idx; x0.kept = pi.kept; x0.base = pi.base; } };
+        uint32_t rw = 0u;   // (READY) lane l: word l & 15 of the launch-ready block
+        uint32_t l15 = lane; asm volatile("" : "+v"(l15)); l15 &= 15u;   // (opaque: as a loop invariant the block's lane offset takes a register the query loop does not have -- 3 VGPRs spilled)
+        if (from_pre) {
+            hd.U = uni(0); hd.xlo = uni(2); hd.L = uni(6); hd.n_staged = uni(7); hd.cur_attr = uni(16);
+            if constexpr (READY) { rw = pre[RW0 + l15]; asm volatile("" : "+v"(rw)); }   // (opaque: merged with the other branch's load the two became ONE flat load behind the branches -- vmcnt and lgkmcnt both)
+            else { hd.rmax = uni(1); hd.sumw = uni(3); hd.unsafe = uni(17); }
+        } else {
+            const PrepHead& h0 = *(const PrepHead*)rec;   // (uniform address)
+            hd.U = h0.U; hd.xlo = h0.xlo; hd.L = h0.L; hd.n_staged = h0.n_staged; hd.cur_attr = h0.cur_attr;
+            if constexpr (READY) rw = ((const uint32_t*)rec)[RW0 + l15];
+            else { hd.rmax = h0.rmax; hd.sumw = h0.sumw; hd.unsafe = h0.unsafe; }
+        }
+        auto rdy = [&](uint32_t w) -> uint32_t { return (uint32_t)__builtin_amdgcn_readlane((int)rw, (int)w); };
         const uint32_t L = hd.L, n = hd.n_staged, U = hd.U;
-        unsigned long long rm = __ballot(x0.kept > 0u);
+        const uint32_t rflags = READY ? rdy(RW_FLAGS) : 0u;
+        const bool ready_ok = READY && (rflags & 1u) != 0u;   // (block-uniform)
+        unsigned long long rm = 0ull;
+        uint32_t nr = (rflags >> 8) & 7u;
+        if (!ready_ok) {   // (READY: the rare path -- 0.3 % of the headline's queries -- ends in the routing below)
+            if constexpr (READY) {
+                if (from_pre) { hd.rmax = uni(1); hd.sumw = uni(3); hd.unsafe = uni(17); }
+                else { const PrepHead& h0 = *(const PrepHead*)rec; hd.rmax = h0.rmax; hd.sumw = h0.sumw; hd.unsafe = h0.unsafe; }
+            }
+            load_x0();
+            rm = __ballot(x0.kept > 0u);
 #ifdef SRN_FAST_EXP_ONELIST   // experiment (timing only, wrong results): every query as if it had its first list alone -- no merge, no cuts: what the walks + harvest cost by themselves
-        rm &= 0ull - rm;
+            rm &= 0ull - rm;
 #endif
-        const uint32_t nr = (uint32_t)__popcll(rm);
+            nr = (uint32_t)__popcll(rm);
+        }
+#ifdef SRN_FAST_EXP_ONELIST
+        else nr = min(nr, 1u);
+#endif
         // Slot = (rank - base) << NB | set of lists.  Normally NB = 4 (WIDE, above 2^28 sessions: 3) and base = 0.  A query with MORE lists than bits
         // (4 lists on an index of > 2^28 sessions) takes NB = 4 with the ranks counted from the cut x_lo -- every staged entry is >= x_lo -- if that fits 28 bits.
-        const bool rel = MID || (WIDE && nr > 3u);   // (block-uniform)
+        const bool rel = MID || (WIDE && (ready_ok ? (rflags >> 16) & 1u : nr > 3u));   // (block-uniform)
         const uint32_t NB = LONG ? F_LONG_NB : MID ? max(nr, 4u) : WIDE && !rel ? 3u : 4u, NBM = (1u << NB) - 1u, base = rel ? hd.xlo : 0u;
         // (MID: the last 256 words of the merge buffers' room hold the class histogram of the k-cut)
         // (round 6: hd.unsafe -- an incomplete posting list of a pre-built index can reach this query's neighbours: the general kernel's row pass serves it, srn_prep.h)
-        const bool fits = hd.unsafe != 0u ? false : LONG ? L >= 1u && L <= F_LONG_LMAX && L <= p.max_len && hd.sumw <= F_LONG_CLASSES && nr <= F_LONG_LISTS && 2u * n + 8u + F_LONG_RES_WORDS <= MW && hd.rmax - hd.xlo < (1u << (32u - F_LONG_NB))
+        const bool fits = READY ? ready_ok : hd.unsafe != 0u ? false : LONG ? L >= 1u && L <= F_LONG_LMAX && L <= p.max_len && hd.sumw <= F_LONG_CLASSES && nr <= F_LONG_LISTS && 2u * n + 8u + F_LONG_RES_WORDS <= MW && hd.rmax - hd.xlo < (1u << (32u - F_LONG_NB))
                         : MID ? L >= 1u && L <= F_MID_LMAX && L <= p.max_len && hd.sumw <= F_MID_CLASSES && nr <= F_MID_LISTS && 2u * n + 8u + 256u <= MW && hd.rmax - hd.xlo < (1u << (32u - NB))
                               : L >= 1u && L <= 8u && L <= p.max_len && hd.sumw <= 15u && nr <= 4u && 2u * n + 8u <= MW && (!rel || hd.rmax - hd.xlo < (1u << 28));
         uint32_t* const xq = MODE == FM_FUSED ? nullptr : f.xchg + (size_t)q * f.xchg_stride;   // this query's place in the exchange buffer: K | K slots
@@ -637,6 +670,23 @@ __global__ __launch_bounds__(512, TINY ? SRN_TINY_WAVES : BIG ? 4 : SRN_FAST_WAV
         }
         if (n == 0u) { if (tid == 0) { if constexpr (MODE == FM_FRONT) xq[0] = 0u; else p.out_counts[q] = 0u; } continue; }   // no known item (vmis_index.rs:350): empty result
         uint32_t kp[NL], ps[NL]; const uint32_t* src[NL];
+        uint32_t lmask = 0u, cur_idx;
+        if constexpr (READY) {   // (fits: the block is meaningful; runs the query does not have are all zero)
+            lmask = rdy(RW_LMASK);
+#ifdef SRN_FAST_EXP_ONELIST
+            lmask &= 31u;
+#endif
+            const uint32_t psw = rdy(RW_PS);
+#pragma unroll
+            for (int r = 0; r < NL; ++r) {
+                kp[r] = rdy(RW_KEPT + r); ps[r] = (psw >> (8 * r)) & 0xFFu;
+#ifdef SRN_FAST_EXP_ONELIST
+                if (r) kp[r] = 0u;
+#endif
+                src[r] = ix.post_rank + (((unsigned long long)rdy(RW_BASE + 2 * r + 1) << 32) | rdy(RW_BASE + 2 * r));
+            }
+            cur_idx = rdy(RW_CUR);
+        } else {
 #pragma unroll
         for (int r = 0; r < NL; ++r) {
             const int l = rm ? __ffsll((long long)rm) - 1 : 0;
@@ -646,7 +696,8 @@ __global__ __launch_bounds__(512, TINY ? SRN_TINY_WAVES : BIG ? 4 : SRN_FAST_WAV
             ps[r] = (uint32_t)l;
             rm &= rm - 1ull;
         }
-        const uint32_t cur_idx = (uint32_t)__builtin_amdgcn_readlane((int)x0.idx, 0);
+        cur_idx = (uint32_t)__builtin_amdgcn_readlane((int)x0.idx, 0);
+        }
         const uint32_t cur_attr = hd.cur_attr;   // business rules (mod.rs:162-182): the current item's attribute byte, looked up by the prep kernel
         const uint32_t s1 = kp[0], s2 = s1 + kp[1], s3 = s2 + kp[2];
 
@@ -666,8 +717,11 @@ __global__ __launch_bounds__(512, TINY ? SRN_TINY_WAVES : BIG ? 4 : SRN_FAST_WAV
 #pragma unroll
         for (int r = 0; r < 4; ++r)
 #pragma unroll
-            for (int j = 0; j < 5; ++j) { v[r][j] = 0u; if ((uint32_t)j * BLOCK < kp[r]) v[r][j] = src[r][min(tid + j * BLOCK, kp[r] - 1u)]; }
+            for (int j = 0; j < 5; ++j) { v[r][j] = 0u; if (READY ? (lmask >> (5 * r + j)) & 1u : (uint32_t)j * BLOCK < kp[r]) v[r][j] = src[r][min(tid + j * BLOCK, kp[r] - 1u)]; }   // (READY: the skip is one bit test of the record's lmask)
         }
+#ifdef SRN_FAST_SUBTICKS
+        FAST_TICK(15);   // (the record is decoded and the last list load issued; 15 -> 0: the wait at the barrier + the loads' round trip.  Slot 15 otherwise holds the overflow counts)
+#endif
         __syncthreads();   // previous query's LDS reads are done
         FAST_PRIO(FP_FRONT);
         // (opaque copies: with a compile-time shift the packing of a staged entry is otherwise hoisted into the conditional block of its load, which then
@@ -1052,11 +1106,14 @@ __global__ __launch_bounds__(512, TINY ? SRN_TINY_WAVES : BIG ? 4 : SRN_FAST_WAV
         // wave waits for it at the end of phase 4a, before the barrier that everybody passes on the way to the next query
         const uint32_t qn = MID ? q_after : ordered || listed ? q_ord_next : q + gridDim.x;
         const bool park = MID ? q_after != 0xFFFFFFFFu : ordered || listed ? q_ord_next != 0xFFFFFFFFu : qn < p.nq;   // (block-uniform)
-        if (wave == 1u && park) {   // (a record is at most 72 + 8 * 24 = 264 bytes -- MID: 72 + 10 * 24 = 312 --: two rounds of a dword per lane)
-            const char* const rn = p.prep + (size_t)qn * p.prep_stride + lane * 4u;
+        if (wave == 1u && park) {   // (what the next query reads of its record is at most 136 + 8 * 24 = 328 bytes -- MID: 136 + 10 * 24 = 376 --: two rounds of a dword per lane)
+            uint32_t lo4 = lane * 4u; asm volatile("" : "+v"(lo4));   // (opaque: p.prep + lane * 4 as a loop invariant is a register pair held through the whole query -- the pair that spilled when the launch-ready block took a register)
+            const char* const rn = p.prep + (size_t)qn * p.prep_stride + lo4;
             const uint32_t dst = (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_addr(pre));
             if (lane * 4u < p.prep_stride) glds_dword_uncounted(rn, dst);
-            if (256u + lane * 4u < min(p.prep_stride, 320u)) glds_dword_uncounted(rn + 256, dst + 256u);
+            constexpr uint32_t PARK = (uint32_t)(sizeof(PrepHead) + (MID ? 10u : 8u) * sizeof(PrepItem));
+            static_assert((MID && !SRN_MID_PREFETCH) || F_PRE + PARK <= F_SINV, "the parked record ends in front of F_SINV");
+            if (256u + lane * 4u < min(p.prep_stride, PARK)) glds_dword_uncounted(rn + 256, dst + 256u);
         }
         // Round (i) in two passes, so that it runs under the loads it was written to hide: first the 18 adds of items 0..5 of the wave's three rows -- their quads are in
         // registers since the queue was built --, then items 6..13, each row behind a COUNTED wait for its own second 16 bytes.  (One pass, row by row, put the wait for

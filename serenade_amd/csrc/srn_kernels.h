@@ -32,7 +32,17 @@ struct KernelCfg {
 struct LaunchAux { const uint32_t* qlist; const uint32_t* qlist_n; uint32_t* retry_list; uint32_t* retry_cnt; char* gscratch; unsigned long long gscratch_stride; char* nb_spill; };
 
 // record written by the prep kernel for every query: PrepHead + max_len * PrepItem, positions counted from the most recent item
-struct PrepHead { uint32_t U, rmax, xlo, sumw, P, nruns, L, n_staged, run_start[8], cur_attr, unsafe; };   // S_U, S_RMAX, S_XLO, S_SUMW, S_P of the query; number of non-empty lists, session length as given, sum of the lists' kept counts, where the first 8 lists start; cur_attr = the attribute byte of the current (most recent) item, SRN_ATTR_NONE if unknown
+// The launch-ready block (PrepHead::ready, 16 words): what the lean forms of vmis_fast_kernel used to work out of the fields above, in every wave of every query, before
+// their first posting-list load could leave -- the routing predicate and the run descriptors -- worked out ONCE by whoever writes the record (ready_add / ready_words,
+// srn_prep.h).  Runs: run r = the r-th item, in position order, with kept > 0.  The block is meaningful when 1 <= L <= min(8, max_len) and the query has <= 4 runs;
+// otherwise all 16 words are 0.
+//   RW_FLAGS   bit 0 lean_ok: the lean form's `fits` (srn_fast.hip) for the 53 KB layout; bits 8..10 nr: the runs, capped at 7; bit 16 rel: ranks counted from x_lo
+//   RW_LMASK   bit 5 r + j: j * 512 < kept of run r -- which of the 20 stage loads exist
+//   RW_CUR     the dense idx of the most recent item (kNone: unknown)
+//   RW_PS      byte r: the session position of run r's item
+//   RW_KEPT+r  kept of run r;   RW_BASE+2r, +2r+1: its list's start in post_rank (64-bit element offset, low word first)
+enum ReadyWord : uint32_t { RW_FLAGS = 0, RW_LMASK = 1, RW_CUR = 2, RW_PS = 3, RW_KEPT = 4, RW_BASE = 8, RW_WORDS = 16 };
+struct PrepHead { uint32_t U, rmax, xlo, sumw, P, nruns, L, n_staged, run_start[8], cur_attr, unsafe, ready[RW_WORDS]; };   // S_U, S_RMAX, S_XLO, S_SUMW, S_P of the query; number of non-empty lists, session length as given, sum of the lists' kept counts, where the first 8 lists start; cur_attr = the attribute byte of the current (most recent) item, SRN_ATTR_NONE if unknown; ready: above
 struct PrepItem { uint32_t idx, len, pre, kept; unsigned long long base; };   // dense idx | kNone, truncated list length, prefix of len, entries >= x_lo (a prefix of the list), list start
 
 // item-sharded index, lists mode (srn_shard.hip): what a shard knows about one evolving position of a query
@@ -70,7 +80,9 @@ static constexpr uint32_t F_REP_ITEMS = SRN_FAST_REPLICAS ? SRN_FAST_REP_ITEMS :
 static constexpr uint32_t F_SURV = F_TABLE + F_TABLE_WORDS * 8;          // survivors of the integer floors, packed (idx << 20 | acc), then the threshold histogram
 static constexpr uint32_t F_LDS_BYTES = F_SURV + F_SURV_WORDS * 4;
 static constexpr uint32_t F_WORK = F_NBL, F_WORK_WORDS = (F_LDS_BYTES - F_WORK) / 4;   // merge buffers: 2 * n_staged words
+static constexpr uint32_t F_LEAN_MW = F_WORK_WORDS;   // words the lean form's merge buffers may use (2 * n_staged + 8 of them): the prep record's lean_ok and vmis_fast_kernel's MW
 static constexpr uint32_t F_M_MAX = 2560;
+static_assert(F_M_MAX <= 5 * 512, "a list is staged in <= 5 loads of 512 entries: ReadyWord RW_LMASK has 5 bits per run");
 static constexpr uint32_t F_FIN_BYTES = 1024, F_FIN_ENTRIES = F_FIN_BYTES / 16 - 1;   // a query's record: header + 63 entries
 static_assert(F_CAND + F_CAND_CAP * 12 <= F_HOT, "candidate buffer overlaps the accumulators");
 static constexpr uint32_t F_BIG_TOTAL = 80 * 1024;   // LDS of the MID instantiation's BIG form (two workgroups per CU): the same map with the merge buffers' room grown to 19 072 words (n <= 9 404 staged entries)
@@ -189,8 +201,8 @@ struct PredictLaunch {
 };
 hipError_t launch_predict(const PredictLaunch& a, dim3 grid, size_t lds, hipStream_t st, const DeviceIndex& di, const LaunchParams& p, const KernelCfg& c);
 hipError_t launch_prep(hipStream_t st, const DeviceIndex& di, const uint64_t* items_flat, const uint32_t* q_off, uint32_t nq, uint32_t m,
-                       uint32_t max_len, char* out, uint32_t stride, uint32_t* zero_a = nullptr, uint32_t* zero_b = nullptr,
-                       const IdSlot* loc_table = nullptr, uint32_t loc_mask = 0, unsigned long long* okeys = nullptr);   // zero_a[0..7], zero_b[0]: counters cleared by the prep kernel; loc_table: the item shard's id table (the record's idx), di = the whole index's dictionary and lists
+                       uint32_t max_len, char* out, uint32_t stride, bool wide, uint32_t* zero_a = nullptr, uint32_t* zero_b = nullptr,
+                       const IdSlot* loc_table = nullptr, uint32_t loc_mask = 0, unsigned long long* okeys = nullptr);   // wide: the records' consumer is the WIDE lean form (FastParams::nb == 3: the launch-ready block's `rel`); zero_a[0..7], zero_b[0]: counters cleared by the prep kernel; loc_table: the item shard's id table (the record's idx), di = the whole index's dictionary and lists
 hipError_t launch_finish_big(hipStream_t st, const DeviceIndex& di, const FastParams& f, uint64_t* out_ids, double* out_scores, uint32_t* out_counts, uint32_t how_many, uint32_t grid, const uint32_t* cnt_retry = nullptr, const uint32_t* cnt_slow = nullptr, uint32_t* host_words = nullptr);
 hipError_t launch_finish(hipStream_t st, const DeviceIndex& di, const FastParams& f, uint64_t* out_ids, double* out_scores, uint32_t* out_counts, uint32_t nq, uint32_t how_many);   // scores, ranking, public ids of the rows the fast kernel served
 hipError_t launch_shard_lists_head(hipStream_t st, const DeviceIndex& di, const uint64_t* items_flat, const uint32_t* q_off, uint32_t nq, uint32_t m, uint32_t max_len,
@@ -200,7 +212,7 @@ hipError_t launch_shard_lists_count(hipStream_t st, const DeviceIndex& di, const
 hipError_t launch_shard_lists_copy(hipStream_t st, const DeviceIndex& di, uint32_t nq, uint32_t max_len, const ShardPos* pos_in, const uint32_t* kept, const long long* off,
                                    uint32_t* out);
 hipError_t launch_shard_prep(hipStream_t st, const uint64_t* items_flat, const uint32_t* q_off, uint32_t nq, uint32_t max_len, uint32_t n_shards, const uint32_t* kept_g,
-                             const long long* off_g, unsigned long long shard_stride, const int* head, const ShardPos* pos_local, char* out, uint32_t stride,
+                             const long long* off_g, unsigned long long shard_stride, const int* head, const ShardPos* pos_local, char* out, uint32_t stride, bool wide,
                              const unsigned long long* shard_base = nullptr, bool direct = false);   // shard_base [n_shards] (device): where each shard's segment starts in the gathered buffer (null: g * shard_stride); direct: one shard, lists read in place
 hipError_t launch_shard_max(hipStream_t st, int* dst, const int* src, size_t n);
 hipError_t launch_shard_offsets(hipStream_t st, const uint32_t* kept_g, uint32_t nq, uint32_t max_len, uint32_t n_shards, long long* off_g, unsigned long long* tot_dev,

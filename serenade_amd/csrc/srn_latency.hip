@@ -169,7 +169,7 @@ int device_predict_tiny(DeviceState* d, const FlatIndex& ix, Workspace* w, const
     const bool tiny_fast = plan.fast && (kn.tiny_fast == 3 || (kn.tiny_fast >= 1 && p.max_len > 8) || (kn.tiny_fast == 2 && p.nq <= (kn.no_tiny_fused ? 32u : (uint32_t)kn.tiny_fused_max)));   // (the crossover measured with tools/tiny_crossover.py: profiles/r04_serving_tiny_fast.txt)
     if (tiny_fast) { int rc = reserve_fast(w, cap_q); if (rc) return rc; }   // (sized once, for the largest round)
     const bool fused = tiny_fast && p.nq <= (uint32_t)kn.tiny_fused_max && !kn.no_tiny_fused;
-    if (!fused) { w->cnt_dirty = true; HIP_TRY(launch_prep(st, d->di, p.items_flat, p.q_off, p.nq, p.m, p.max_len, w->prep, prep_stride, tiny_fast ? w->slow_cnt : nullptr)); }
+    if (!fused) { w->cnt_dirty = true; HIP_TRY(launch_prep(st, d->di, p.items_flat, p.q_off, p.nq, p.m, p.max_len, w->prep, prep_stride, plan.nb_fast == 3u, tiny_fast ? w->slow_cnt : nullptr)); }
     p.prep = w->prep; p.prep_stride = prep_stride;
     TinyCall c{d, w, geo, p, plan, kn, pin, st, blocking_wait};
     int rc = SRN_OK;

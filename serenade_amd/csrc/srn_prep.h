@@ -8,9 +8,35 @@
 
 namespace srn {
 
+// The launch-ready block of a record (ReadyWord, srn_kernels.h), shared by the two record writers (prep_group below, shard_prep_kernel in srn_shard.hip): the items are
+// added in position order, most recent first, then the 16 words are made from the runs and the head's fields.
+struct ReadyRuns { uint32_t nr = 0, lmask = 0, ps = 0, kept[4] = {0u, 0u, 0u, 0u}; unsigned long long base[4] = {0ull, 0ull, 0ull, 0ull}; };
+__device__ __forceinline__ void ready_add(ReadyRuns& rr, uint32_t pos, uint32_t kept, unsigned long long base) {
+    if (kept == 0u) return;   // (an unknown item, an older duplicate, a list that ends above the cut: no run)
+#pragma unroll
+    for (uint32_t r = 0; r < 4u; ++r) if (rr.nr == r) { rr.kept[r] = kept; rr.base[r] = base; }
+    if (rr.nr < 4u) { rr.lmask |= ((1u << min((kept + 511u) >> 9, 5u)) - 1u) << (5u * rr.nr); rr.ps |= (pos & 0xFFu) << (8u * rr.nr); }
+    rr.nr = min(rr.nr + 1u, 7u);
+}
+// wide: the launch sequence's lean form is the WIDE one (29 rank bits + 3 list bits per slot: FastParams::nb == 3); a query of 4 runs then counts its ranks from x_lo
+__device__ __forceinline__ void ready_words(const ReadyRuns& rr, uint32_t (&w)[RW_WORDS], uint32_t L, uint32_t max_len, uint32_t sumw, uint32_t n_staged, uint32_t rmax, uint32_t xlo,
+                                            uint32_t unsafe, bool wide, uint32_t cur_idx) {
+#pragma unroll
+    for (uint32_t i = 0; i < RW_WORDS; ++i) w[i] = 0u;
+    if (!(L >= 1u && L <= 8u && L <= max_len && rr.nr <= 4u)) return;
+    const bool rel = wide && rr.nr > 3u;
+    const bool lean_ok = unsafe == 0u && sumw <= 15u && 2u * n_staged + 8u <= F_LEAN_MW && (!rel || rmax - xlo < (1u << 28));
+    w[RW_FLAGS] = (lean_ok ? 1u : 0u) | (rr.nr << 8) | (rel ? 1u << 16 : 0u);
+    w[RW_LMASK] = rr.lmask; w[RW_CUR] = cur_idx; w[RW_PS] = rr.ps;
+#pragma unroll
+    for (uint32_t r = 0; r < 4u; ++r) { w[RW_KEPT + r] = rr.kept[r]; w[RW_BASE + 2u * r] = (uint32_t)rr.base[r]; w[RW_BASE + 2u * r + 1u] = (uint32_t)(rr.base[r] >> 32); }
+}
+
 static constexpr uint32_t PREP_LANES = 8;
+// BLOCK = false (the latency path's inline call, vmis_fast_kernel<TINY>): the launch-ready block is written as zeros -- lean_ok clear: "decode the items" -- see there
+template <bool BLOCK = true>
 __device__ __forceinline__ void prep_group(const DeviceIndex& ix, const uint64_t* __restrict__ items_flat, const uint32_t* __restrict__ q_off, uint32_t q, uint32_t sub, uint32_t m, uint32_t max_len,
-                                           char* rec, const IdSlot* __restrict__ loc_table, uint32_t loc_mask, unsigned long long* __restrict__ okeys) {
+                                           char* rec, const IdSlot* __restrict__ loc_table, uint32_t loc_mask, unsigned long long* __restrict__ okeys, bool wide) {
     const uint32_t qb = q_off[q], L = q_off[q + 1] - qb;
     PrepItem* items = (PrepItem*)(rec + sizeof(PrepHead));
     uint32_t U = 0, rmax = 0, xlo = 0, sumw = 0, P = 0, nruns = 0, n_staged = 0, cur_attr = SRN_ATTR_NONE, my_run_start = 0;
@@ -71,6 +97,7 @@ __device__ __forceinline__ void prep_group(const DeviceIndex& ix, const uint64_t
         if (have && rounds > 1) items[pos] = PrepItem{idx, len, pre, 0u, base};
     }
     // entries >= x_lo of every list (a prefix: the lists are sorted by rank, descending): what the merge-mode kernels stage
+    uint32_t kept_last = 0;   // this lane's `kept` of the last round
     for (uint32_t r = 0; r < rounds; ++r) {
         const uint32_t pos = r * PREP_LANES + sub;
         const bool have = pos < L;
@@ -108,6 +135,7 @@ __device__ __forceinline__ void prep_group(const DeviceIndex& ix, const uint64_t
             }
             if (rounds > 1) items[pos].kept = kept; else items[pos] = PrepItem{idx, len, pre, kept, base};
         }
+        kept_last = kept;
         uint32_t ks = kept;
         #pragma unroll
         for (uint32_t d = 1; d < PREP_LANES; d <<= 1) ks += __shfl_xor(ks, d, PREP_LANES);
@@ -129,12 +157,30 @@ __device__ __forceinline__ void prep_group(const DeviceIndex& ix, const uint64_t
 #endif
     if (okeys && sub == 0) okeys[q] = SRN_ORDER_KEY2 ? ((unsigned long long)min(hot_key, 0xFFFFu) << 40) | ((unsigned long long)min(hot_key2 >> 4, 0xFFu) << 32) | q :
                                       ((unsigned long long)min(hot_key, 0xFFFFu) << 32) | q;   // (16 key bits: beyond the 65 535 most popular items there is nothing to group -- two radix passes instead of three)
-    uint32_t* hw = (uint32_t*)rec;   // PrepHead, word by word: U rmax xlo sumw | P nruns L n_staged | run_start[8] | cur_attr unsafe
-    if (sub == 0) {   // (records are 8-byte aligned: 72 + 24 * max_len)
+    uint32_t* hw = (uint32_t*)rec;   // PrepHead, word by word: U rmax xlo sumw | P nruns L n_staged | run_start[8] | cur_attr unsafe | ready[16]
+    if (sub == 0) {   // (records are 8-byte aligned: 136 + 24 * max_len)
         *(uint2*)hw = make_uint2(U, rmax); *(uint2*)(hw + 2) = make_uint2(xlo, sumw); *(uint2*)(hw + 4) = make_uint2(P, nruns); *(uint2*)(hw + 6) = make_uint2(L, n_staged);
         *(uint2*)(hw + 16) = make_uint2(cur_attr, unsafe);
     }
     hw[8 + sub] = sub < nruns ? my_run_start : 0u;
+    // the launch-ready block: a session of <= 8 items has one round, lane s holds the item at position s (every lane of the group works out all 16 words, lane s stores two)
+    static_assert(offsetof(PrepHead, ready) == 72 && RW_WORDS == 2 * PREP_LANES, "lane s writes words 2 s, 2 s + 1 of the block");
+    if constexpr (!BLOCK) *(uint2*)(hw + 18 + 2u * sub) = make_uint2(0u, 0u);
+    else {
+        ReadyRuns rr;
+        const uint32_t k1 = rounds == 1u ? kept_last : 0u;
+#pragma unroll
+        for (uint32_t s = 0; s < PREP_LANES; ++s) {
+            const uint32_t ks = __shfl(k1, s, PREP_LANES), blo = __shfl((uint32_t)base, s, PREP_LANES), bhi = __shfl((uint32_t)(base >> 32), s, PREP_LANES);
+            ready_add(rr, s, ks, ((unsigned long long)bhi << 32) | blo);
+        }
+        uint32_t w[RW_WORDS];
+        ready_words(rr, w, L, max_len, sumw, n_staged, rmax, xlo, unsafe, wide, __shfl(idx, 0, PREP_LANES));
+        uint2 o = make_uint2(0u, 0u);
+#pragma unroll
+        for (uint32_t s = 0; s < PREP_LANES; ++s) if (sub == s) o = make_uint2(w[2u * s], w[2u * s + 1u]);
+        *(uint2*)(hw + 18 + 2u * sub) = o;
+    }
 }
 
 }  // namespace srn

@@ -415,10 +415,11 @@ int make_geometry(const DeviceState* d, const FlatIndex& ix, const LaunchParams&
 // What the fast kernel needs of the LAUNCH is the position-set condition (DESIGN.md "Why MASKS is exact": m <= m_index, lists complete) and sketch words that cannot wrap
 // at ITS session lengths (<= 10 items: the admission is per query, on the device); the batch's longest session only decides which kernels serve the hand-overs -- up to
 // round 3 one session of nine items sent the whole batch to the general kernel.
-static uint32_t fast_nb(const FlatIndex& ix, const Knobs& kn) {   // bits of a fast-kernel slot's list set (0: the index has too many sessions for any)
-    const int rank_bits_f = std::max(1, bits_host(ix.n_kept ? ix.n_kept - 1 : 0));
+static uint32_t fast_nb_of(uint64_t n_kept, const Knobs& kn) {   // bits of a fast-kernel slot's list set (0: the index has too many sessions for any)
+    const int rank_bits_f = std::max(1, bits_host(n_kept ? n_kept - 1 : 0));
     return kn.fast_runs == 3 && rank_bits_f <= 29 ? 3u : rank_bits_f <= 28 ? 4u : rank_bits_f <= 29 ? 3u : 0u;
 }
+static uint32_t fast_nb(const FlatIndex& ix, const Knobs& kn) { return fast_nb_of(ix.n_kept, kn); }
 FastPlan fast_plan(const DeviceState* d, const FlatIndex& ix, const LaunchParams& p, const Geometry& geo, const Knobs& kn, bool has_ext) {
     FastPlan f;
     // the fast kernel packs (rank, set of <= 4 lists) into 32 bits whatever the general kernel's slots look like: up to 2^28 sessions with 4 lists per query,
@@ -610,7 +611,7 @@ static int fetch_host_outputs(const BatchCall& c, const HostRows& h) {
 // stream (prep_clears) the prep kernel also clears the sequence's counters and the grouping pass writes the merged rows' count words; a resident call runs it on the side stream.
 static int enqueue_front(BatchCall& c, hipStream_t s, char* rec) {
     const LaunchParams& p = c.p; const LaunchPlan& pl = c.pl; OrderBufs& ob = c.ob; Workspace* w = c.w;
-    HIP_TRY(launch_prep(s, c.di, p.items_flat, p.q_off, p.nq, p.m, p.max_len, rec, pl.prep_stride, pl.prep_clears && pl.fast.fast ? w->slow_cnt : nullptr,
+    HIP_TRY(launch_prep(s, c.di, p.items_flat, p.q_off, p.nq, p.m, p.max_len, rec, pl.prep_stride, pl.fast.nb_fast == 3u, pl.prep_clears && pl.fast.fast ? w->slow_cnt : nullptr,
                         pl.prep_clears && pl.retry ? w->retry_cnt : nullptr, nullptr, 0, ob.keys_in));
     if (pl.dedup) {   // (a resident call: the count word of a merged row is written on the caller's stream -- the previous call's kernels may still be writing these very buffers)
         HIP_TRY(hipMemsetAsync(ob.dd.slots, 0xFF, (size_t)ob.dd.n_slots * 8, s));
@@ -958,7 +959,7 @@ int device_shard_lists_predict(DeviceState* d, const FlatIndex& ix, const Launch
     if (n_shards != ix.n_shards) return fail(SRN_EINVAL, "n_shards differs from the number of shards this index was cut into");
     if (!device_shard_lists_supported(d, ix, p)) return fail(SRN_EINVAL, "lists mode needs position-set slots (sessions of <= 8 items, m <= m_index, complete lists): use the three-stage pipeline");
     const uint32_t stride = device_prep_stride(p.max_len);
-    HIP_TRY(launch_shard_prep((hipStream_t)stream, p.items_flat, p.q_off, p.nq, p.max_len, n_shards, kept_g, off_g, shard_stride, head, (const ShardPos*)pos_local, records, stride, shard_base, direct));
+    HIP_TRY(launch_shard_prep((hipStream_t)stream, p.items_flat, p.q_off, p.nq, p.max_len, n_shards, kept_g, off_g, shard_stride, head, (const ShardPos*)pos_local, records, stride, fast_nb(ix, knobs()) == 3u, shard_base, direct));
     ExtLists ext{records, stride, direct ? d->di.post_rank : lists_g};
     return predict_ext(d, ix, p, stream, ext);
 }
@@ -973,7 +974,7 @@ int device_shard_nb_prep(DeviceState* d, DeviceState* post, const LaunchParams& 
     const bool ordered = order_buf && kn.order_min > 0 && p.nq >= (uint32_t)kn.order_min;
     OrderBufs ob;
     if (ordered) { int rc = order_room(order_buf, order_bytes, p.nq, &ob); if (rc) return rc; }
-    HIP_TRY(launch_prep((hipStream_t)stream, post->di, p.items_flat, p.q_off, p.nq, p.m, p.max_len, records, device_prep_stride(p.max_len), nullptr, nullptr, d->di.id_table, d->di.id_mask, ob.keys_in));
+    HIP_TRY(launch_prep((hipStream_t)stream, post->di, p.items_flat, p.q_off, p.nq, p.m, p.max_len, records, device_prep_stride(p.max_len), fast_nb_of(d->di.n_kept, kn) == 3u /* (the fronting kernel runs on d's index) */, nullptr, nullptr, d->di.id_table, d->di.id_mask, ob.keys_in));
     if (ordered) { HIP_TRY(sort_order_keys((hipStream_t)stream, ob.keys_in, ob.keys_out, p.nq, ob.temp, &ob.temp_bytes)); *order_out = ob.keys_out; }
     return SRN_OK;
 }
@@ -1047,6 +1048,30 @@ int device_last_path_counts(DeviceState* d, uint32_t* nq, uint32_t* general, uin
     if (nq) *nq = w->last_nq;
     if (general) *general = w->last_fast ? w->h_retry[HW_GENERAL] : w->last_nq;
     if (global_pass) *global_pass = w->last_retry ? w->h_retry[HW_GLOBAL] : 0;
+    return SRN_OK;
+}
+int device_debug_prep_records(DeviceState* d, const FlatIndex& ix, const uint64_t* items_flat, const uint32_t* q_off, size_t nq, size_t m, size_t max_len, void* out, size_t cap_bytes, size_t* out_stride) {
+    if (!q_off || !out_stride || (nq && !out)) return fail(SRN_EINVAL, "null buffer");
+    if (nq > (1u << 24) || m == 0 || m > 0xFFFFFFFFull || max_len == 0 || max_len > SRN_MAX_SESSION_LEN) return fail(SRN_ERANGE, "srn_debug_prep_records: sizes out of range");
+    for (size_t q = 0; q < nq; ++q) if (q_off[q + 1] < q_off[q]) return fail(SRN_EINVAL, "srn_debug_prep_records: q_off must not decrease");
+    const uint32_t stride = prep_stride_of((uint32_t)max_len);
+    *out_stride = stride;
+    if (nq == 0) return SRN_OK;
+    const size_t n_items = q_off[nq], rec_bytes = nq * (size_t)stride;
+    if (n_items && !items_flat) return fail(SRN_EINVAL, "null buffer");
+    if (cap_bytes < rec_bytes) return fail(SRN_ERANGE, "srn_debug_prep_records: the output buffer is too small");
+    HIP_TRY(hipSetDevice(d->device));
+    const size_t items_bytes = (n_items + 1) * 8, off_bytes = ((nq + 1) * 4 + 7) & ~(size_t)7;
+    void* mem = nullptr;
+    if (hipMalloc(&mem, items_bytes + off_bytes + rec_bytes) != hipSuccess) { (void)hipGetLastError(); return fail(SRN_ENOMEM, "srn_debug_prep_records: hipMalloc failed"); }
+    uint64_t* d_items = (uint64_t*)mem; uint32_t* d_off = (uint32_t*)((char*)mem + items_bytes); char* d_rec = (char*)mem + items_bytes + off_bytes;
+    hipError_t e = hipMemset(d_rec, 0, rec_bytes);   // (a session of 0 or of > max_len items has no item entries: they read as zeros)
+    if (e == hipSuccess && n_items) e = hipMemcpy(d_items, items_flat, n_items * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_off, q_off, (nq + 1) * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = launch_prep(0, d->di, d_items, d_off, (uint32_t)nq, (uint32_t)m, (uint32_t)max_len, d_rec, stride, fast_nb(ix, knobs()) == 3u);
+    if (e == hipSuccess) e = hipMemcpy(out, d_rec, rec_bytes, hipMemcpyDeviceToHost);   // (the null stream: the copy waits for the kernel)
+    (void)hipFree(mem);
+    if (e != hipSuccess) return fail(SRN_EHIP, std::string("srn_debug_prep_records: ") + hipGetErrorString(e));
     return SRN_OK;
 }
 int device_last_mid_count(DeviceState* d, uint32_t* listed, uint32_t* big_listed) {   // queries the last call's lean fast kernel listed for the MID instantiation (0: no such tier in that call)

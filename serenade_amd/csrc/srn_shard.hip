@@ -25,6 +25,7 @@
 
 #include "srn_device.h"
 #include "srn_kernels.h"
+#include "srn_prep.h"
 
 namespace srn {
 
@@ -95,11 +96,12 @@ __global__ __launch_bounds__(256) void shard_lists_copy_kernel(DeviceIndex ix, u
 __global__ __launch_bounds__(256) void shard_prep_kernel(const uint64_t* __restrict__ items_flat, const uint32_t* __restrict__ q_off, uint32_t nq, uint32_t max_len,
                                                          uint32_t n_shards, const uint32_t* __restrict__ kept_g, const long long* __restrict__ off_g,
                                                          unsigned long long shard_stride, const unsigned long long* __restrict__ shard_base, const int* __restrict__ head,
-                                                         const ShardPos* __restrict__ pos_local, char* __restrict__ out, uint32_t stride, bool direct) {
+                                                         const ShardPos* __restrict__ pos_local, char* __restrict__ out, uint32_t stride, bool direct, bool wide) {
     const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= nq) return;
     const uint32_t qb = q_off[q], L = q_off[q + 1] - qb;
-    PrepHead h{0u, 0u, 0u, 0u, 0u, 0u, L, 0u, {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u}, SRN_ATTR_NONE, 0u};
+    PrepHead h{0u, 0u, 0u, 0u, 0u, 0u, L, 0u, {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u}, SRN_ATTR_NONE, 0u, {}};
+    ReadyRuns rr; uint32_t cur_idx = kNone;
     PrepItem* items = (PrepItem*)(out + (size_t)q * stride + sizeof(PrepHead));
     if (L != 0 && L <= max_len) {
         h.xlo = (uint32_t)head[3 * (size_t)q]; h.rmax = (uint32_t)head[3 * (size_t)q + 1];
@@ -122,10 +124,12 @@ __global__ __launch_bounds__(256) void shard_prep_kernel(const uint64_t* __restr
             }
             if (kp) { h.sumw += L - pos; if (h.nruns < 8) h.run_start[h.nruns] = h.P; ++h.nruns; }
             items[pos] = PrepItem{pos_local[(size_t)q * max_len + pos].idx, kp, h.P, kp, base};
+            ready_add(rr, pos, kp, base); if (pos == 0) cur_idx = items[0].idx;
             h.P += kp;
         }
         h.n_staged = h.P;
     }
+    ready_words(rr, h.ready, L, max_len, h.sumw, h.n_staged, h.rmax, h.xlo, h.unsafe, wide, cur_idx);   // (the launch-ready block: srn_prep.h)
     *(PrepHead*)(out + (size_t)q * stride) = h;
 }
 
@@ -145,10 +149,10 @@ hipError_t launch_shard_lists_copy(hipStream_t st, const DeviceIndex& di, uint32
     return hipGetLastError();
 }
 hipError_t launch_shard_prep(hipStream_t st, const uint64_t* items_flat, const uint32_t* q_off, uint32_t nq, uint32_t max_len, uint32_t n_shards, const uint32_t* kept_g,
-                             const long long* off_g, unsigned long long shard_stride, const int* head, const ShardPos* pos_local, char* out, uint32_t stride,
+                             const long long* off_g, unsigned long long shard_stride, const int* head, const ShardPos* pos_local, char* out, uint32_t stride, bool wide,
                              const unsigned long long* shard_base, bool direct) {
     hipLaunchKernelGGL(shard_prep_kernel, dim3((nq + 255) / 256), dim3(256), 0, st, items_flat, q_off, nq, max_len, n_shards, kept_g, off_g, shard_stride, shard_base, head, pos_local,
-                       out, stride, direct);
+                       out, stride, direct, wide);
     return hipGetLastError();
 }
 
