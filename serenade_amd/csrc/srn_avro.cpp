@@ -32,6 +32,9 @@ namespace {
 struct Err { std::string msg; };
 [[noreturn]] void bad(const std::string& m) { throw Err{m}; }
 
+// the positive idf values the index serves (the loader's check below says why): 2^-900 .. 2^900
+const double kIdfMax = std::ldexp(1.0, 900), kIdfMin = std::ldexp(1.0, -900);
+
 // ---- byte cursor with Avro's primitive encodings ---------------------------------------------
 struct Cur {
     const uint8_t* p; const uint8_t* end;
@@ -250,6 +253,11 @@ int build_flat_index_from_avro(const char* base_path, FlatIndex& ix) {
         for (const std::string& f : avro_files(base + "/itemindex"))
             read_container(f, {"ItemId", "session_indices_time_ordered", "idf", "ForSale", "IsAdult"}, [&](const std::vector<Value>& v) {
                 Item it; it.id = (uint64_t)v[0].i; it.idf = v[2].d; it.attr = (uint8_t)((v[4].i ? SRN_ATTR_ADULT : 0) | (v[3].i ? SRN_ATTR_FOR_SALE : 0));
+                // idf is served AS GIVEN where the kernels' arithmetic carries it: any finite value <= 0 (the un-weighted branch) and any positive value in [2^-900, 2^900].
+                // Inside that range x = idf * acc (acc < 2^31), x * (10 U) and x / (10 U) are all finite normal doubles, so the scores, the thresholds in the top 32 bits of x
+                // and the integer floors thr * denom / idf_hi neither overflow nor lose bits.  NaN, +-inf and positive values outside the range are refused.
+                if (!std::isfinite(it.idf) || (it.idf > 0.0 && (it.idf < kIdfMin || it.idf > kIdfMax)))
+                    bad("item " + std::to_string(it.id) + " has an idf this library does not serve (NaN, infinite, or positive and outside 2^-900 .. 2^900): idf must be finite, and <= 0 or within that range");
                 for (int64_t s : v[1].arr) { if (s < 0 || (size_t)s >= rows.size()) bad("item " + std::to_string(it.id) + " lists a session the session index does not hold"); it.sessions.push_back((uint32_t)s); }
                 items.push_back(std::move(it)); });
         const size_t ns = rows.size();

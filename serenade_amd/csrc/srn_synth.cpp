@@ -232,6 +232,8 @@ void srn_synth_producer_copy(void* h, uint64_t* item_ids, uint64_t* list_off, ui
     memcpy(item_ids, P->item_ids.data(), P->item_ids.size() * 8); memcpy(list_off, P->list_off.data(), P->list_off.size() * 8);
     memcpy(list_sessions, P->list_sessions.data(), P->list_sessions.size() * 4); memcpy(idf, P->idf.data(), P->idf.size() * 8);
 }
+// idf AS GIVEN (one double per item, aligned with the ascending item_ids) in place of the computed values: what srn_synth_write_avro then writes
+void srn_synth_producer_set_idf(void* h, const double* idf) { Producer* P = (Producer*)h; memcpy(P->idf.data(), idf, P->idf.size() * 8); }
 void srn_synth_producer_free(void* h) { delete (Producer*)h; }
 
 }  // extern "C"

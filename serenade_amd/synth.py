@@ -53,6 +53,7 @@ def lib():
         L.srn_synth_producer_nnz.restype = u64
         L.srn_synth_producer_nnz.argtypes = [vp]
         L.srn_synth_producer_copy.argtypes = [vp, vp, vp, vp, vp]
+        L.srn_synth_producer_set_idf.argtypes = [vp, vp]
         L.srn_synth_producer_free.argtypes = [vp]
         L.srn_synth_write_avro.restype = C.c_int
         L.srn_synth_write_avro.argtypes = [C.c_char_p, vp, vp, vp, vp, u64, C.c_int]
@@ -110,23 +111,89 @@ def tie_timestamps(ts, per_second, t0=T0):
     return (t0 + (ts.astype(np.int64) - t0) // int(per_second)).astype(np.uint32)
 
 
-def avro_index(base, off, items, ts, m_index, max_len, idf_weighting, tie_mode="reverse", files=4):
+def avro_index(base, off, items, ts, m_index, max_len, idf_weighting, tie_mode="reverse", files=4, idf=None):
     """A stand-in for the reference's offline index producer (srn_synth.cpp): writes <base>/itemindex/*.avro + <base>/sessionindex/*.avro and returns what it
-    wrote as arrays (item_ids ascending, list_off, list_sessions, idf) -- the lists AS GIVEN, for a checker."""
+    wrote as arrays (item_ids ascending, list_off, list_sessions, idf) -- the lists AS GIVEN, for a checker.
+    idf: the items' idf AS GIVEN in place of the builder's ln(total / count) * weighting -- a float64 array aligned with the returned ascending item_ids, or a callable
+    item_ids -> such an array; the files and the returned idf carry it (lists, rows and tie modes are untouched).  None: the computed values."""
     L = lib()
     off, items, ts = np.ascontiguousarray(off, np.uint64), np.ascontiguousarray(items, np.uint64), np.ascontiguousarray(ts, np.uint32)
     n = len(ts)
     h = L.srn_synth_producer(off.ctypes.data, items.ctypes.data, ts.ctypes.data, n, int(m_index), int(max_len), float(idf_weighting), TIE_MODES[tie_mode])
     ni, nnz = L.srn_synth_producer_n_items(h), L.srn_synth_producer_nnz(h)
-    ids, loff, lsess, idf = np.empty(ni, np.uint64), np.empty(ni + 1, np.uint64), np.empty(max(nnz, 1), np.uint32), np.empty(ni, np.float64)
-    L.srn_synth_producer_copy(h, ids.ctypes.data, loff.ctypes.data, lsess.ctypes.data, idf.ctypes.data)
-    os.makedirs(os.path.join(base, "itemindex"), exist_ok=True)
-    os.makedirs(os.path.join(base, "sessionindex"), exist_ok=True)
-    rc = L.srn_synth_write_avro(str(base).encode(), h, off.ctypes.data, items.ctypes.data, ts.ctypes.data, n, int(files))
-    L.srn_synth_producer_free(h)
+    ids, loff, lsess, idf_out = np.empty(ni, np.uint64), np.empty(ni + 1, np.uint64), np.empty(max(nnz, 1), np.uint32), np.empty(ni, np.float64)
+    L.srn_synth_producer_copy(h, ids.ctypes.data, loff.ctypes.data, lsess.ctypes.data, idf_out.ctypes.data)
+    try:
+        if idf is not None:
+            given = np.ascontiguousarray(idf(ids) if callable(idf) else idf, np.float64)
+            if given.shape != (ni,):
+                raise ValueError("idf must hold one value per item of the index (%d), aligned with the ascending item ids" % ni)
+            L.srn_synth_producer_set_idf(h, given.ctypes.data)
+            idf_out = given.copy()
+        os.makedirs(os.path.join(base, "itemindex"), exist_ok=True)
+        os.makedirs(os.path.join(base, "sessionindex"), exist_ok=True)
+        rc = L.srn_synth_write_avro(str(base).encode(), h, off.ctypes.data, items.ctypes.data, ts.ctypes.data, n, int(files))
+    finally:
+        L.srn_synth_producer_free(h)
     if rc:
         raise IOError("could not write the Avro index under %s" % base)
-    return ids, loff, lsess[:nnz], idf
+    return ids, loff, lsess[:nnz], idf_out
+
+
+def id_hash(ids, salt):
+    """A fixed integer hash of item ids (splitmix64's finaliser over id + salt * golden ratio) -> u64 array."""
+    x = np.asarray(ids).astype(np.uint64) + np.uint64(salt * 0x9E3779B97F4A7C15 & 0xFFFFFFFFFFFFFFFF)
+    x = (x ^ (x >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+    x = (x ^ (x >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    return x ^ (x >> np.uint64(31))
+
+
+def dense_rank(item_ids, list_sessions, off, items):
+    """The dense index the Avro loader gives the items of avro_index()'s files (srn_avro.cpp): popularity over the rows of the sessions some list names, count
+    descending, id ascending -> i64[n_items] aligned with the ascending item_ids."""
+    listed = np.zeros(len(off) - 1, bool)
+    listed[np.asarray(list_sessions, np.int64)] = True
+    u, c = np.unique(np.asarray(items)[np.repeat(listed, np.diff(np.asarray(off).astype(np.int64)))], return_counts=True)
+    if not np.array_equal(u, item_ids):
+        raise ValueError("the listed sessions' rows do not hold exactly the index's items")
+    r = np.empty(len(u), np.int64)
+    r[np.lexsort((u, -c))] = np.arange(len(u))
+    return r
+
+
+IDF_PROFILES = ("near", "rising", "falling", "spike", "signs", "limits")
+IDF_SERVED_MIN, IDF_SERVED_MAX = 2.0 ** -900, 2.0 ** 900           # the positive idf values the Avro loader serves (srn_avro.cpp)
+IDF_SPIKES = {3: 60, 5: -60, 1030: 60, 1040: -60, 3970: 60, 3980: -60}   # dense rank -> exponent: the fast kernel's sample, its direct-mapped chunk 2, its sketch region
+
+
+def idf_profile(name, item_ids, r, base):
+    """idf AS GIVEN by a producer that does not follow the builder's rule, for avro_index(..., idf=): a pure function of (item id, dense rank r); base = the computed idf.
+      near     B[h % 6] * (1 + s * 2^-44), B = {1, 1.5, 2, 3, 4, 6}, s hashed in +-1024: scores that share their top 32 bits and differ below
+      rising   (1 + (r % 16) / 16) * 2^(-100 + 200 r / n); falling: the mirror image
+      spike    1 everywhere but 2^60 / 2^-60 on the items of IDF_SPIKES
+      signs    a hashed third of the items in {-3.5, -0.0, 0.0} (the un-weighted branch), the rest `base`
+      limits   both ends of the range the loader serves, hashed: {2^900, 1.5 * 2^899, 2^-900, 1.5 * 2^-900, 1, base}[h % 6]"""
+    item_ids, r = np.asarray(item_ids, np.uint64), np.asarray(r, np.int64)
+    n = len(item_ids)
+    h = id_hash(item_ids, 1)
+    if name == "near":
+        s = ((h >> np.uint64(8)) % np.uint64(2049)).astype(np.int64) - 1024
+        return np.array([1.0, 1.5, 2.0, 3.0, 4.0, 6.0])[(h % np.uint64(6)).astype(np.int64)] * (1.0 + s * 2.0 ** -44)       # (exact: < 50 significant bits)
+    if name in ("rising", "falling"):
+        e = -100 + (200 * r) // n
+        return np.ldexp(1.0 + (r % 16) / 16.0, (e if name == "rising" else -e).astype(np.int32))
+    if name == "spike":
+        out = np.ones(n)
+        for rr, e in IDF_SPIKES.items():
+            out[r == rr] = 2.0 ** e
+        return out
+    if name == "signs":
+        h2 = id_hash(item_ids, 2)
+        return np.where(h2 % np.uint64(3) == 0, np.array([-3.5, -0.0, 0.0])[((h2 >> np.uint64(4)) % np.uint64(3)).astype(np.int64)], np.asarray(base, np.float64))
+    if name == "limits":
+        vals = np.array([IDF_SERVED_MAX, 1.5 * 2.0 ** 899, IDF_SERVED_MIN, 1.5 * IDF_SERVED_MIN, 1.0, 0.0])
+        return np.where(h % np.uint64(6) == 5, np.asarray(base, np.float64), vals[(h % np.uint64(6)).astype(np.int64)])
+    raise KeyError(name)
 
 
 def training_events(off, items, ts, seed=SEED, duplicates=0.01):

@@ -113,6 +113,42 @@ def random_queries(seed, ids, n, max_len=6, unknown_rate=0.05, dup_rate=0.2):
     return qs
 
 
+def canonical_acc_over_given_lists(lists, rows, ts, session, k, m, rank=None):
+    """DESIGN.md section 1 with the posting lists AS GIVEN (not rebuilt from the rows), up to the integers: what a pre-built index whose lists are not
+    most-recent prefixes must still produce -- the reference uses the lists as they are (vmis_index.rs:201-228, 332-391) and tests the first match against
+    the full row (mod.rs:133-138).  -> ({item: acc = sum over the k neighbours of w10 * numerator}, U = distinct items of the session); the session's
+    last item is not scored.  score = idf_eff * acc / (10 U)."""
+    L = len(session)
+    recency = (lambda s: (int(ts[s]), s)) if rank is None else (lambda s: int(rank[s]))   # rank: the index's own order among equal timestamps (srn_index_session_recency)
+    seen, num = set(), {}
+    for pos in range(L):
+        it = session[L - 1 - pos]
+        if it in seen:
+            continue
+        seen.add(it)
+        for s in sorted(lists.get(it, []), key=recency, reverse=True)[:m]:
+            num[s] = num.get(s, 0) + (L - pos)
+    U = len(seen)
+    cand = sorted(num, key=recency, reverse=True)[:m]
+    nb = sorted(cand, key=lambda s: (num[s], recency(s)), reverse=True)[:k]
+    acc = {}
+    rev = session[::-1]
+    for s in nb:
+        p = next(i + 1 for i, it in enumerate(rev) if it in rows[s])
+        w10 = 10 - p if p < 100 else 0
+        for it in rows[s]:
+            acc[it] = acc.get(it, 0) + w10 * num[s]
+    acc.pop(session[-1], None)
+    return acc, U
+
+
+def canonical_over_given_lists(lists, rows, ts, idf, session, k, m, n, rank=None):
+    """... and the top n of it: (ids, scores) by (score descending, id ascending); idf = {item: idf as given}."""
+    acc, U = canonical_acc_over_given_lists(lists, rows, ts, session, k, m, rank=rank)
+    scored = sorted(((-(idf[it] if idf[it] > 0 else 1.0) * a / (10.0 * U), it) for it, a in acc.items()))[:n]
+    return [it for _, it in scored], [-x for x, _ in scored]
+
+
 def capacity_rule_sequence(table, capacity, t, ttl):
     """The capacity rule on a device table keyed by visitor -- the session store or the click feedback log -- at a capacity small enough that probes
     wrap the table's end and the automatic sweep rebuilds a table at load 0.5.  `table` adapts the object and its dictionary model:

@@ -8,7 +8,7 @@ import pytest
 
 import avro_spec_reader as ASR
 import avro_write as AW
-from helpers import flatten, random_queries, small_dataset
+from helpers import canonical_over_given_lists as _canonical_over_given_lists, flatten, random_queries, small_dataset
 
 
 def pyarrow_snappy(data):
@@ -224,35 +224,6 @@ def test_avro_schema_with_reordered_and_extra_fields(tmp_path):
     for it in list(per_item)[:30]:
         a, b = ix.postings(it), ref.postings(it)
         assert np.array_equal(a[0], b[0]) and a[1] == b[1]
-
-
-def _canonical_over_given_lists(lists, rows, ts, idf, session, k, m, n, rank=None):
-    """DESIGN.md section 1 with the posting lists AS GIVEN (not rebuilt from the rows): what a pre-built index whose lists are not
-    most-recent prefixes must still produce -- the reference uses the lists as they are (vmis_index.rs:201-228, 332-391) and tests
-    the first match against the full row (mod.rs:133-138)."""
-    L = len(session)
-    recency = (lambda s: (int(ts[s]), s)) if rank is None else (lambda s: int(rank[s]))   # rank: the index's own order among equal timestamps (srn_index_session_recency)
-    seen, num = set(), {}
-    for pos in range(L):
-        it = session[L - 1 - pos]
-        if it in seen:
-            continue
-        seen.add(it)
-        for s in sorted(lists.get(it, []), key=recency, reverse=True)[:m]:
-            num[s] = num.get(s, 0) + (L - pos)
-    U = len(seen)
-    cand = sorted(num, key=recency, reverse=True)[:m]
-    nb = sorted(cand, key=lambda s: (num[s], recency(s)), reverse=True)[:k]
-    acc = {}
-    rev = session[::-1]
-    for s in nb:
-        p = next(i + 1 for i, it in enumerate(rev) if it in rows[s])
-        w10 = 10 - p if p < 100 else 0
-        for it in rows[s]:
-            acc[it] = acc.get(it, 0) + w10 * num[s]
-    acc.pop(session[-1], None)
-    scored = sorted(((-(idf[it] if idf[it] > 0 else 1.0) * a / (10.0 * U), it) for it, a in acc.items()))[:n]
-    return [it for _, it in scored], [-x for x, _ in scored]
 
 
 def _write(tmp_path, item_recs, sess_recs):

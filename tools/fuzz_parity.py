@@ -68,7 +68,15 @@ while time.time() < t_end and rounds < max_rounds:
         avro_mode = str(rng.choice(["ours", "reverse", "mixed", "per-item"])); cut = max(1, row_max - int(rng.integers(0, 3)))
         tmpd = tempfile.mkdtemp(prefix="srn_fuzz_avro_")
         try:
-            p_ids, p_off, p_sess, p_idf = _synth.avro_index(tmpd, off, items, ts, m_index, cut, idfw, avro_mode, files=int(rng.integers(1, 4)))
+            n_files = int(rng.integers(1, 4))
+            p_ids, p_off, p_sess, p_idf = _synth.avro_index(tmpd, off, items, ts, m_index, cut, idfw, avro_mode, files=n_files)
+            # idf AS GIVEN: half of the pre-built indices carry one of synth.idf_profile's profiles, the ones tests/test_gpu_given_idf.py runs (near-ties, 2^-100 .. 2^100 rising / falling, spikes, mixed
+            # signs) in place of the builder's rule -- the same lists, written again with idf=
+            given_idf = str(rng.choice(["builder", "near", "rising", "falling", "spike", "signs"], p=[0.5, 0.1, 0.1, 0.1, 0.1, 0.1]))
+            if given_idf != "builder":
+                p_idf = _synth.idf_profile(given_idf, p_ids, _synth.dense_rank(p_ids, p_sess, off, items), p_idf)
+                p_idf = _synth.avro_index(tmpd, off, items, ts, m_index, cut, idfw, avro_mode, files=n_files, idf=p_idf)[3]
+            avro_mode += "/idf:" + given_idf
             gix = sa.VMISIndex.new_from_avro(tmpd)
         finally:
             shutil.rmtree(tmpd, ignore_errors=True)
