@@ -908,59 +908,41 @@ int srn_index_set_fallback_trending(srn_index_t* idx, srn_device_sessions_t* sto
         return SRN_OK; });
 }
 
-// the checks both entry points share, in srn_predict_batch_device's order; *done: nothing to do (n == 0)
-static int check_recommend_args(const srn_index_t* idx, size_t n, size_t k, size_t m, size_t how_many, unsigned flags, bool buffers, bool* done) {
-    *done = false;
-    int rc = check_predict_args(idx, k, m, how_many); if (rc) return rc;
-    rc = check_not_a_shard(idx); if (rc) return rc;
-    if (n == 0) { *done = true; return SRN_OK; }
-    if (!buffers) return fail(SRN_EINVAL, "null buffer");
-    if (flags & ~(unsigned)(SRN_FLAG_BUSINESS_LOGIC | SRN_FLAG_EXCLUDE_SEEN | SRN_FLAG_FILL)) return fail(SRN_EINVAL, "srn_recommend_batch: unknown flags");
-    if (flags & SRN_FLAG_FILL) return check_has_fallback(idx);   // (before the store changes)
-    return SRN_OK;
+// Every form of the batch call: the checks in srn_predict_batch_device's order, then the store's entry for device or host pointers.  timed (the _at forms, DESIGN.md
+// 11.6): `times` is among the buffers; now_secs is then the capacity rule's sweep clock alone
+static int recommend_batch(const srn_index_t* idx, srn_device_sessions_t* store, const VisitorBatch& r, const RecommendCall& c, bool timed, bool host) {
+    return guarded([&]() -> int {
+        int rc = check_predict_args(idx, c.k, c.m, c.how_many); if (rc) return rc;
+        rc = check_not_a_shard(idx); if (rc) return rc;
+        if (r.n == 0) return SRN_OK;
+        if (!has_request_arrays(r, timed) || !c.ids || !c.scores || !c.counts) return fail(SRN_EINVAL, "null buffer");
+        if (c.flags & ~(unsigned)(SRN_FLAG_BUSINESS_LOGIC | SRN_FLAG_EXCLUDE_SEEN | SRN_FLAG_FILL)) return fail(SRN_EINVAL, "srn_recommend_batch: unknown flags");
+        if ((c.flags & SRN_FLAG_FILL) && (rc = check_has_fallback(idx))) return rc;   // (before the store changes)
+        return host ? dsess_recommend_host(idx, store, r, c) : dsess_recommend_device(idx, store, r, c); });
 }
 int srn_recommend_batch_device(const srn_index_t* idx, srn_device_sessions_t* store, const uint64_t* d_key_hi, const uint64_t* d_key_lo, const uint64_t* d_item_ids,
                                const uint8_t* d_consent, size_t n, uint64_t now_secs, size_t max_items_in_session, size_t k, size_t m, size_t how_many,
                                unsigned flags, uint64_t* d_out_ids, double* d_out_scores, uint32_t* d_out_counts, void* stream) {
-    return guarded([&]() -> int {
-        bool done;
-        int rc = check_recommend_args(idx, n, k, m, how_many, flags, d_key_hi && d_key_lo && d_item_ids && d_out_ids && d_out_scores && d_out_counts, &done);
-        if (rc || done) return rc;
-        return dsess_recommend_device(idx, store, d_key_hi, d_key_lo, d_item_ids, d_consent, n, now_secs, max_items_in_session, k, m, how_many, flags,
-                                      d_out_ids, d_out_scores, d_out_counts, stream); });
+    return recommend_batch(idx, store, {d_key_hi, d_key_lo, d_item_ids, d_consent, nullptr, n, now_secs},
+                           {max_items_in_session, k, m, how_many, flags, d_out_ids, d_out_scores, d_out_counts, stream}, false, false);
 }
 int srn_recommend_batch(const srn_index_t* idx, srn_device_sessions_t* store, const uint64_t* key_hi, const uint64_t* key_lo, const uint64_t* item_ids,
                         const uint8_t* consent, size_t n, uint64_t now_secs, size_t max_items_in_session, size_t k, size_t m, size_t how_many,
                         unsigned flags, uint64_t* out_ids, double* out_scores, uint32_t* out_counts) {
-    return guarded([&]() -> int {
-        bool done;
-        int rc = check_recommend_args(idx, n, k, m, how_many, flags, key_hi && key_lo && item_ids && out_ids && out_scores && out_counts, &done);
-        if (rc || done) return rc;
-        if (max_items_in_session == 0) return fail(SRN_EINVAL, "srn_recommend_batch: max_items_in_session must be > 0");
-        return dsess_recommend_host(idx, store, key_hi, key_lo, item_ids, consent, n, now_secs, max_items_in_session, k, m, how_many, flags,
-                                    out_ids, out_scores, out_counts); });
+    return recommend_batch(idx, store, {key_hi, key_lo, item_ids, consent, nullptr, n, now_secs},
+                           {max_items_in_session, k, m, how_many, flags, out_ids, out_scores, out_counts, nullptr}, false, true);
 }
-// the timed batch: the same checks, with `times` among the buffers; now_secs is the capacity rule's sweep clock alone
 int srn_recommend_batch_device_at(const srn_index_t* idx, srn_device_sessions_t* store, const uint64_t* d_key_hi, const uint64_t* d_key_lo, const uint64_t* d_item_ids,
                                   const uint8_t* d_consent, const uint64_t* d_times, size_t n, uint64_t now_secs, size_t max_items_in_session, size_t k, size_t m,
                                   size_t how_many, unsigned flags, uint64_t* d_out_ids, double* d_out_scores, uint32_t* d_out_counts, void* stream) {
-    return guarded([&]() -> int {
-        bool done;
-        int rc = check_recommend_args(idx, n, k, m, how_many, flags, d_key_hi && d_key_lo && d_item_ids && d_times && d_out_ids && d_out_scores && d_out_counts, &done);
-        if (rc || done) return rc;
-        return dsess_recommend_device(idx, store, d_key_hi, d_key_lo, d_item_ids, d_consent, n, now_secs, max_items_in_session, k, m, how_many, flags,
-                                      d_out_ids, d_out_scores, d_out_counts, stream, d_times); });
+    return recommend_batch(idx, store, {d_key_hi, d_key_lo, d_item_ids, d_consent, d_times, n, now_secs},
+                           {max_items_in_session, k, m, how_many, flags, d_out_ids, d_out_scores, d_out_counts, stream}, true, false);
 }
 int srn_recommend_batch_at(const srn_index_t* idx, srn_device_sessions_t* store, const uint64_t* key_hi, const uint64_t* key_lo, const uint64_t* item_ids,
                            const uint8_t* consent, const uint64_t* times, size_t n, uint64_t now_secs, size_t max_items_in_session, size_t k, size_t m, size_t how_many,
                            unsigned flags, uint64_t* out_ids, double* out_scores, uint32_t* out_counts) {
-    return guarded([&]() -> int {
-        bool done;
-        int rc = check_recommend_args(idx, n, k, m, how_many, flags, key_hi && key_lo && item_ids && times && out_ids && out_scores && out_counts, &done);
-        if (rc || done) return rc;
-        if (max_items_in_session == 0) return fail(SRN_EINVAL, "srn_recommend_batch: max_items_in_session must be > 0");
-        return dsess_recommend_host(idx, store, key_hi, key_lo, item_ids, consent, n, now_secs, max_items_in_session, k, m, how_many, flags,
-                                    out_ids, out_scores, out_counts, times); });
+    return recommend_batch(idx, store, {key_hi, key_lo, item_ids, consent, times, n, now_secs},
+                           {max_items_in_session, k, m, how_many, flags, out_ids, out_scores, out_counts, nullptr}, true, true);
 }
 
 // ---- session harvest (srn_harvest.hip) ----
@@ -988,27 +970,29 @@ int srn_feedback_create(int device, size_t capacity, size_t row_cap, uint64_t tt
     return guarded([&]() -> int { return fb_create(device, capacity, row_cap, ttl_secs, idle_secs, out); });
 }
 void srn_feedback_free(srn_feedback_t* f) { fb_free(f); }
+// every form of the observe call; timed (the _at forms): `times` is among the buffers.  Every other check is the log's own
+static int feedback_observe(srn_feedback_t* f, const VisitorBatch& r, const ObserveCall& c, bool timed, bool host) {
+    return guarded([&]() -> int {
+        if (f && r.n && timed && !r.times) return fail(SRN_EINVAL, "srn_feedback_observe: null buffer");
+        return host ? fb_observe_host(f, r, c) : fb_observe_device(f, r, c); });
+}
 int srn_feedback_observe_device(srn_feedback_t* f, const uint64_t* d_key_hi, const uint64_t* d_key_lo, const uint64_t* d_item_ids, const uint8_t* d_consent, size_t n,
                                 uint64_t now_secs, const uint64_t* d_ids, const double* d_scores, const uint32_t* d_counts, size_t how_many, uint32_t* d_out_rank,
                                 void* stream) {
-    return guarded([&]() -> int { return fb_observe_device(f, d_key_hi, d_key_lo, d_item_ids, d_consent, n, now_secs, d_ids, d_scores, d_counts, how_many, d_out_rank, stream); });
+    return feedback_observe(f, {d_key_hi, d_key_lo, d_item_ids, d_consent, nullptr, n, now_secs}, {d_ids, d_scores, d_counts, how_many, d_out_rank, stream}, false, false);
 }
 int srn_feedback_observe(srn_feedback_t* f, const uint64_t* key_hi, const uint64_t* key_lo, const uint64_t* item_ids, const uint8_t* consent, size_t n,
                          uint64_t now_secs, const uint64_t* ids, const double* scores, const uint32_t* counts, size_t how_many, uint32_t* out_rank) {
-    return guarded([&]() -> int { return fb_observe_host(f, key_hi, key_lo, item_ids, consent, n, now_secs, ids, scores, counts, how_many, out_rank); });
+    return feedback_observe(f, {key_hi, key_lo, item_ids, consent, nullptr, n, now_secs}, {ids, scores, counts, how_many, out_rank, nullptr}, false, true);
 }
 int srn_feedback_observe_device_at(srn_feedback_t* f, const uint64_t* d_key_hi, const uint64_t* d_key_lo, const uint64_t* d_item_ids, const uint8_t* d_consent,
                                    const uint64_t* d_times, size_t n, uint64_t now_secs, const uint64_t* d_ids, const double* d_scores, const uint32_t* d_counts,
                                    size_t how_many, uint32_t* d_out_rank, void* stream) {
-    return guarded([&]() -> int {
-        if (f && n && !d_times) return fail(SRN_EINVAL, "srn_feedback_observe: null buffer");
-        return fb_observe_device(f, d_key_hi, d_key_lo, d_item_ids, d_consent, n, now_secs, d_ids, d_scores, d_counts, how_many, d_out_rank, stream, d_times); });
+    return feedback_observe(f, {d_key_hi, d_key_lo, d_item_ids, d_consent, d_times, n, now_secs}, {d_ids, d_scores, d_counts, how_many, d_out_rank, stream}, true, false);
 }
 int srn_feedback_observe_at(srn_feedback_t* f, const uint64_t* key_hi, const uint64_t* key_lo, const uint64_t* item_ids, const uint8_t* consent, const uint64_t* times,
                             size_t n, uint64_t now_secs, const uint64_t* ids, const double* scores, const uint32_t* counts, size_t how_many, uint32_t* out_rank) {
-    return guarded([&]() -> int {
-        if (f && n && !times) return fail(SRN_EINVAL, "srn_feedback_observe: null buffer");
-        return fb_observe_host(f, key_hi, key_lo, item_ids, consent, n, now_secs, ids, scores, counts, how_many, out_rank, times); });
+    return feedback_observe(f, {key_hi, key_lo, item_ids, consent, times, n, now_secs}, {ids, scores, counts, how_many, out_rank, nullptr}, true, true);
 }
 int srn_feedback_stats(srn_feedback_t* f, srn_feedback_stats_t* out) { return guarded([&]() -> int { return fb_stats(f, out); }); }
 int srn_feedback_histogram(srn_feedback_t* f, uint64_t* hits_model, uint64_t* hits_filled, size_t cap) {

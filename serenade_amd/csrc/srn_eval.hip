@@ -581,17 +581,19 @@ int eval_run(srn_eval_set* set, const srn_eval_trial_t* trials, size_t n_trials,
                 scan_tmp = std::max(scan_tmp, t1);
             }
         // chunk buffers: items | q_off | (session, state) | ids | scores | counts | terms, and under the serving rules | list ids | x_off | packed lengths | packed offsets | scan storage
-        const size_t o_items = 0, o_qoff = align256((size_t)cq * max_len * 8), o_ss = o_qoff + align256(((size_t)cq + 1) * 4),
-                     o_ids = o_ss + align256((size_t)cq * 8), o_sc = o_ids + align256((size_t)cq * tr.how_many * 8),
-                     o_cnt = o_sc + align256((size_t)cq * tr.how_many * 8), o_terms = o_cnt + align256((size_t)cq * 4),
-                     o_x = o_terms + align256((size_t)cq * kTerms * 8), o_xoff = o_x + (serving ? align256((size_t)cq * max_x * 8) : 0),
-                     o_pk = o_xoff + (serving ? align256(((size_t)cq + 1) * 4) : 0), o_po = o_pk + (serving ? align256(((size_t)cq + 1) * 8) : 0),
-                     o_tmp = o_po + (serving ? align256(((size_t)cq + 1) * 8) : 0), bytes = o_tmp + align256(scan_tmp);
-        if (bytes > e->chunk_bytes) { HIP_TRY(hipStreamSynchronize(st)); if ((rc = ensure(&e->chunk, &e->chunk_bytes, bytes))) return rc; }
+        // (the serving rules' regions are empty, not absent, without them: the plain call is handed the same pointers as ever)
+        const size_t q1 = (size_t)cq + 1, sv = serving ? 1 : 0;
+        Bump cbump;
+        const auto r_items = cbump.of<uint64_t>((size_t)cq * max_len); const auto r_qoff = cbump.of<uint32_t>(q1); const auto r_ss = cbump.of<uint2>(cq);
+        const auto r_ids = cbump.of<uint64_t>((size_t)cq * tr.how_many); const auto r_sc = cbump.of<double>((size_t)cq * tr.how_many); const auto r_cnt = cbump.of<uint32_t>(cq);
+        const auto r_terms = cbump.of<double>((size_t)cq * kTerms);
+        const auto r_x = cbump.of<uint64_t>(sv * cq * max_x); const auto r_xoff = cbump.of<uint32_t>(sv * q1); const auto r_pk = cbump.of<uint64_t>(sv * q1), r_po = cbump.of<uint64_t>(sv * q1);
+        const auto r_tmp = cbump.of<char>(scan_tmp);
+        if (cbump.bytes > e->chunk_bytes) { HIP_TRY(hipStreamSynchronize(st)); if ((rc = ensure(&e->chunk, &e->chunk_bytes, cbump.bytes))) return rc; }
         char* cb = e->chunk;
-        uint64_t* d_items = (uint64_t*)(cb + o_items); uint32_t* d_qoff = (uint32_t*)(cb + o_qoff); uint2* d_ss = (uint2*)(cb + o_ss);
-        uint64_t* d_ids = (uint64_t*)(cb + o_ids); double* d_sc = (double*)(cb + o_sc); uint32_t* d_cnt = (uint32_t*)(cb + o_cnt); double* d_terms = (double*)(cb + o_terms);
-        uint64_t* d_x = (uint64_t*)(cb + o_x); uint32_t* d_xoff = (uint32_t*)(cb + o_xoff);
+        uint64_t* d_items = r_items.at(cb); uint32_t* d_qoff = r_qoff.at(cb); uint2* d_ss = r_ss.at(cb);
+        uint64_t* d_ids = r_ids.at(cb); double* d_sc = r_sc.at(cb); uint32_t* d_cnt = r_cnt.at(cb); double* d_terms = r_terms.at(cb);
+        uint64_t* d_x = r_x.at(cb); uint32_t* d_xoff = r_xoff.at(cb);
         double* part = (double*)e->part + ti * n_groups * kSums;
         uint32_t* bitmap = (uint32_t*)(e->cover + ti * cover_stride);
         for (uint64_t q0 = 0; q0 < nq_all; q0 += chunk) {
@@ -603,12 +605,12 @@ int eval_run(srn_eval_set* set, const srn_eval_trial_t* trials, size_t n_trials,
                 ServeArgs sa{};
                 sa.items = e->items; sa.sess_off = e->sess_off; sa.sess_q = sess_q; sa.n_sessions = (uint32_t)n_s; sa.q0 = q0; sa.nq = nq;
                 sa.W = W; sa.cap = cap; sa.handler = (tr.flags & SRN_FLAG_EVAL_HANDLER) ? 1u : 0u;
-                sa.packed = (uint64_t*)(cb + o_pk); sa.offs = (const uint64_t*)(cb + o_po);
+                sa.packed = r_pk.at(cb); sa.offs = r_po.at(cb);
                 sa.out_items = d_items; sa.out_qoff = d_qoff; sa.x_flat = d_x; sa.x_off = d_xoff; sa.out_ss = d_ss;
                 eval_serve_count_kernel<<<(nq + 1 + 255) / 256, 256, 0, st>>>(sa);
                 HIP_TRY(hipGetLastError());
                 size_t t1 = scan_tmp;
-                HIP_TRY(rocprim::exclusive_scan(cb + o_tmp, t1, sa.packed, (uint64_t*)(cb + o_po), 0ull, (size_t)nq + 1, rocprim::plus<uint64_t>(), st));
+                HIP_TRY(rocprim::exclusive_scan(r_tmp.at(cb), t1, sa.packed, r_po.at(cb), 0ull, (size_t)nq + 1, rocprim::plus<uint64_t>(), st));
                 eval_serve_write_kernel<<<(nq + 1 + 255) / 256, 256, 0, st>>>(sa);
                 HIP_TRY(hipGetLastError());
             } else {

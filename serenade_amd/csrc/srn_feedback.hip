@@ -29,7 +29,8 @@
 // The table underneath -- the slot's head, the count and rebuild kernels over a payload functor, the capacity rule (make_room), the sweep's tail, the one-key read-back
 // and create's and free's shared halves -- is srn_visitor_table.h's, shared with the session store.  Here: the payload (count, n_model, ids), the batch
 // kernels, the single table and the sweep that allocates its successor, the counters, the histograms and the bootstrap's words.
-// The sort, the run predicates and the find-or-claim probe are srn_visitors.h's, shared with the session store.
+// The sort, the run predicates, the find-or-claim probe and what a batch call opens with (the sorted front of the call's VisitorBatch, the timed / untimed dispatch,
+// the host stage) are srn_visitors.h's, shared with the session store.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -44,13 +45,12 @@
 #include "srn_runtime.h"
 #include "srn_device.h"
 #include "srn_visitor_table.h"  // the table, its kernels and the capacity rule (shared with srn_sessions_dev.hip)
-#include "srn_visitors.h"       // the run predicates, find_or_claim, the key sort
+#include "srn_visitors.h"       // the run predicates, find_or_claim, the key sort, the sorted front and the host stage
 #include "srn_bootstrap.h"      // the weight rule and the key's fold
 #include "srn_hipsync.h"
 
 struct srn_feedback : srn::VisitorTable {                   // one table stands: a sweep rebuilds into a second one, allocated for it; stats / get / sweep / reset run on `own`
     uint64_t row_cap = 0;
-    char* ws = nullptr; size_t ws_bytes = 0;                // per-batch scratch, grows with the largest n seen
     unsigned long long* ctr = nullptr;                      // the counters: 8 words, hits_model[row_cap + 1], hits_filled[row_cap + 1]
     unsigned long long* boot = nullptr;                     // the bootstrap's replicate words (null: off), word-major [1 + 2 * row_cap][boot_b]: observed_w, then
     uint32_t boot_b = 0; uint64_t boot_seed = 0;            // hits_model_w[1 .. row_cap], then hits_filled_w[1 .. row_cap] -- a flush's lanes add to adjacent words
@@ -62,7 +62,6 @@ namespace srn {
 
 namespace {
 constexpr uint32_t kTPB = kTableTPB;            // (grid_for)
-constexpr uint32_t kMaxBatch = 1u << 24;
 constexpr uint32_t kRankBlocks = 2048;          // fb_rank's grid at the most (256 CUs x 8 workgroups): each workgroup pays one global atomic per non-zero bin
 constexpr uint32_t kFbHead = 40;                // bytes before the ids
 struct FbSlot { uint64_t key_hi, key_lo, epoch; uint32_t count, state, n_model, pad; };
@@ -322,7 +321,7 @@ int room_for(srn_feedback* f, uint64_t n, uint64_t now) { return make_room(f, n,
 void fb_free(srn_feedback* f) {
     if (!f) return;
     table_release(f);
-    for (void* p : {(void*)f->ws, (void*)f->ctr, (void*)f->boot}) if (p) (void)hipFree(p);
+    for (void* p : {(void*)f->ctr, (void*)f->boot}) if (p) (void)hipFree(p);
     delete f;
 }
 
@@ -346,67 +345,65 @@ int fb_create(int device, size_t capacity, size_t row_cap, uint64_t ttl_secs, ui
     return SRN_OK;
 }
 
-int fb_observe_device(srn_feedback* f, const uint64_t* d_hi, const uint64_t* d_lo, const uint64_t* d_item, const uint8_t* d_consent, size_t n, uint64_t now_secs,
-                      const uint64_t* d_ids, const double* d_scores, const uint32_t* d_counts, size_t how_many, uint32_t* d_out_rank, void* stream,
-                      const uint64_t* d_times) {
+// the checks both entry points make, in their order; *done: nothing to do (n == 0)
+static int check_observe(const srn_feedback* f, const VisitorBatch& r, const ObserveCall& c, bool* done) {
+    *done = false;
     if (!f) return fail(SRN_EINVAL, "srn_feedback_observe: null log");
-    if (n == 0) return SRN_OK;
-    if (!d_hi || !d_lo || !d_item || !d_ids || !d_counts) return fail(SRN_EINVAL, "srn_feedback_observe: null buffer");
-    if (n > kMaxBatch) return fail(SRN_ERANGE, "srn_feedback_observe: more than 2^24 requests in one call");
-    if (how_many == 0) return fail(SRN_EINVAL, "srn_feedback_observe: how_many must be > 0");
-    if (how_many > f->row_cap) return fail(SRN_ERANGE, "srn_feedback_observe: how_many above the log's row_cap");
-    hipStream_t st = (hipStream_t)stream;
-    const uint64_t now = now_secs ? now_secs : wall_secs();
+    if (r.n == 0) { *done = true; return SRN_OK; }
+    if (!has_request_arrays(r, false) || !c.ids || !c.counts) return fail(SRN_EINVAL, "srn_feedback_observe: null buffer");
+    if (r.n > kMaxBatch) return fail(SRN_ERANGE, "srn_feedback_observe: more than 2^24 requests in one call");
+    if (c.how_many == 0) return fail(SRN_EINVAL, "srn_feedback_observe: how_many must be > 0");
+    if (c.how_many > f->row_cap) return fail(SRN_ERANGE, "srn_feedback_observe: how_many above the log's row_cap");
+    return SRN_OK;
+}
+
+int fb_observe_device(srn_feedback* f, const VisitorBatch& r, const ObserveCall& c) {
+    bool done;
+    int rc = check_observe(f, r, c, &done); if (rc || done) return rc;
+    const size_t n = r.n;
+    hipStream_t st = (hipStream_t)c.stream;
+    const uint64_t now = r.now_secs ? r.now_secs : wall_secs();
     std::lock_guard<std::mutex> g(f->mu);
-    int rc = room_for(f, n, now); if (rc) return rc;
+    if ((rc = room_for(f, n, now))) return rc;
     HIP_TRY(hipSetDevice(f->device));
-    // scratch: sort keys and indices (double-buffered), the per-position words, rocPRIM's temporary storage
-    size_t tmp = 0, t1 = 0;
-    if ((rc = key_sort_tmp_bytes(n, st, &tmp))) return rc;
-    HIP_TRY(rocprim::inclusive_scan(nullptr, t1, (uint32_t*)nullptr, (uint32_t*)nullptr, n, rocprim::maximum<uint32_t>(), st)); tmp = std::max(tmp, t1);
-    const size_t w = align256(n * 4);
-    const size_t o_keyA = 0, o_keyB = o_keyA + align256(n * 8), o_idxA = o_keyB + align256(n * 8), o_idxB = o_idxA + w, o_slot = o_idxB + w, o_stat = o_slot + w,
-                 o_head = o_stat + w, o_run = o_head + w, o_tmp = o_run + w, o_t = o_tmp + align256(tmp), o_rank = o_t + (d_times ? align256(n * 8) : 0),     // (o_t: a timed batch only)
-                 bytes = o_rank + (f->boot && !d_out_rank ? w : 0);   // (o_rank: the bootstrap reads the ranks; the caller gave no buffer for them)
-    if (bytes > f->ws_bytes) {   // (the previous call may still read the scratch: wait for it before it is freed)
-        HIP_TRY(hipEventSynchronize(f->last));
-        if ((rc = ensure(&f->ws, &f->ws_bytes, bytes))) return rc;
-    }
+    // scratch: the sorted front's (sort keys and indices, rocPRIM's temporary storage -- also the scan's -- and a timed batch's times), then the per-position words
+    size_t scan = 0;
+    HIP_TRY(rocprim::inclusive_scan(nullptr, scan, (uint32_t*)nullptr, (uint32_t*)nullptr, n, rocprim::maximum<uint32_t>(), st));
+    Bump b; SortedFront front;
+    if ((rc = front.plan(b, r, st, scan))) return rc;
+    const auto slot_of = b.of<uint32_t>(n), status = b.of<uint32_t>(n), headpos = b.of<uint32_t>(n), run_start = b.of<uint32_t>(n);
+    Bump::Region<uint32_t> rank;
+    if (f->boot && !c.out_rank) rank = b.of<uint32_t>(n);   // (the bootstrap reads the ranks; the caller gave no buffer for them)
+    if ((rc = grow_behind(f->last, &f->ws, &f->ws_bytes, b.bytes))) return rc;
     HIP_TRY(hipStreamWaitEvent(st, f->last, 0));
-    char* b = f->ws;
-    const dim3 gn = grid_for(n);
-    const uint32_t n32 = (uint32_t)n;
-    // stable LSD passes: key_lo, key_hi, then (where some request may not consent) the consent bit -- consenting requests first, each visitor's in request order
-    KeySort ks{{(uint64_t*)(b + o_keyA), (uint64_t*)(b + o_keyB)}, {(uint32_t*)(b + o_idxA), (uint32_t*)(b + o_idxB)}, b + o_tmp, tmp, n, st};
-    if ((rc = ks.begin(d_lo)) || (rc = ks.pass(KeyWord{d_hi})) || (d_consent && (rc = ks.pass(KeyNoConsent{d_consent}, 0, 1)))) return rc;
-    const uint32_t* order = ks.order();
+    char* const ws = f->ws;
+    if ((rc = front.run(ws, r, st))) return rc;
     ObsArgs a{};
-    a.t = f->tab(); a.key_hi = d_hi; a.key_lo = d_lo; a.item = d_item; a.consent = d_consent;
-    a.ids = d_ids; a.scores = (const uint64_t*)d_scores; a.counts = d_counts; a.how_many = (uint32_t)how_many;
-    a.order = order; a.n = n32; a.row_cap = (uint32_t)f->row_cap;
+    a.t = f->tab(); a.key_hi = r.key_hi; a.key_lo = r.key_lo; a.item = r.item; a.consent = r.consent;
+    a.ids = c.ids; a.scores = (const uint64_t*)c.scores; a.counts = c.counts; a.how_many = (uint32_t)c.how_many;
+    a.order = front.order; a.n = (uint32_t)n; a.row_cap = (uint32_t)f->row_cap;
     a.lanes_shift = f->row_cap <= 8 ? 3 : 4;
     a.rounds = (uint32_t)((f->row_cap + (1u << a.lanes_shift) - 1) >> a.lanes_shift);
     a.now = now; a.idle = f->idle;
-    a.slot_of = (uint32_t*)(b + o_slot); a.status = (uint32_t*)(b + o_stat); a.headpos = (uint32_t*)(b + o_head); a.run_start = (uint32_t*)(b + o_run);
-    a.out_rank = d_out_rank ? d_out_rank : f->boot ? (uint32_t*)(b + o_rank) : nullptr; a.ctr = f->ctr; a.err = f->err();
-    const dim3 gg = grid_for(n << a.lanes_shift);   // (n <= 2^24: 2^28 lanes at the most)
-    if (d_times) {   // a timed batch: the same sequence behind one gather of the times into sorted order
-        a.when = (const uint64_t*)(b + o_t);
-        key_gather<<<gn, kTPB, 0, st>>>(KeyWord{d_times}, order, n32, (uint64_t*)(b + o_t));
-        fb_find<true><<<gn, kTPB, 0, st>>>(a);
-        t1 = tmp; HIP_TRY(rocprim::inclusive_scan(b + o_tmp, t1, a.headpos, a.run_start, n, rocprim::maximum<uint32_t>(), st));
-        fb_rank<true><<<dim3(std::min<unsigned>(gg.x, kRankBlocks)), kTPB, 4 * (size_t)f->n_bins(), st>>>(a);
-        fb_store<true><<<gg, kTPB, 0, st>>>(a);
-    } else {
-        fb_find<false><<<gn, kTPB, 0, st>>>(a);
-        t1 = tmp; HIP_TRY(rocprim::inclusive_scan(b + o_tmp, t1, a.headpos, a.run_start, n, rocprim::maximum<uint32_t>(), st));
-        fb_rank<false><<<dim3(std::min<unsigned>(gg.x, kRankBlocks)), kTPB, 4 * (size_t)f->n_bins(), st>>>(a);
-        fb_store<false><<<gg, kTPB, 0, st>>>(a);
-    }
+    a.slot_of = slot_of.at(ws); a.status = status.at(ws); a.headpos = headpos.at(ws); a.run_start = run_start.at(ws);
+    a.out_rank = c.out_rank ? c.out_rank : rank.at(ws); a.ctr = f->ctr; a.err = f->err();
+    a.when = front.when;   // a timed batch: the same sequence behind the front's gather of the times into sorted order
+    const dim3 gn = grid_for(n), gg = grid_for(n << a.lanes_shift);   // (n <= 2^24: 2^28 lanes at the most)
+    hipError_t scanned = hipSuccess;
+    by_timed(r, [&](auto t) {
+        constexpr bool kTimed = decltype(t)::value;
+        fb_find<kTimed><<<gn, kTPB, 0, st>>>(a);
+        size_t t1 = front.tmp_bytes;
+        scanned = rocprim::inclusive_scan(front.tmp, t1, a.headpos, a.run_start, n, rocprim::maximum<uint32_t>(), st);
+        if (scanned != hipSuccess) return;
+        fb_rank<kTimed><<<dim3(std::min<unsigned>(gg.x, kRankBlocks)), kTPB, 4 * (size_t)f->n_bins(), st>>>(a);
+        fb_store<kTimed><<<gg, kTPB, 0, st>>>(a);
+    });
+    HIP_TRY(scanned);
     if (f->boot) {   // the replicate words, from the ranks fb_rank wrote
-        const BootArgs ba{d_hi, d_lo, order, a.out_rank, n32, (uint32_t)f->row_cap, f->boot_b, f->boot_seed, f->boot};
+        const BootArgs ba{r.key_hi, r.key_lo, a.order, a.out_rank, a.n, (uint32_t)f->row_cap, f->boot_b, f->boot_seed, f->boot};
         const uint32_t tile = boot_tile(f->row_cap);
-        fb_boot<<<dim3(std::min<unsigned>((n32 + kBootStage - 1) / kBootStage, kBootBlocks), (f->boot_b + tile - 1) / tile), tile, boot_lds_bytes(f->row_cap), st>>>(ba);
+        fb_boot<<<dim3(std::min<unsigned>((a.n + kBootStage - 1) / kBootStage, kBootBlocks), (f->boot_b + tile - 1) / tile), tile, boot_lds_bytes(f->row_cap), st>>>(ba);
     }
     HIP_TRY(hipGetLastError());
     // from here on the log has changed: the next call is ordered behind this one
@@ -415,42 +412,32 @@ int fb_observe_device(srn_feedback* f, const uint64_t* d_hi, const uint64_t* d_l
     return SRN_OK;
 }
 
-int fb_observe_host(srn_feedback* f, const uint64_t* hi, const uint64_t* lo, const uint64_t* item, const uint8_t* consent, size_t n, uint64_t now_secs,
-                    const uint64_t* ids, const double* scores, const uint32_t* counts, size_t how_many, uint32_t* out_rank, const uint64_t* times) {
-    if (!f) return fail(SRN_EINVAL, "srn_feedback_observe: null log");
-    if (n == 0) return SRN_OK;
-    if (!hi || !lo || !item || !ids || !counts) return fail(SRN_EINVAL, "srn_feedback_observe: null buffer");
-    if (n > kMaxBatch) return fail(SRN_ERANGE, "srn_feedback_observe: more than 2^24 requests in one call");
-    if (how_many == 0) return fail(SRN_EINVAL, "srn_feedback_observe: how_many must be > 0");
-    if (how_many > f->row_cap) return fail(SRN_ERANGE, "srn_feedback_observe: how_many above the log's row_cap");
+int fb_observe_host(srn_feedback* f, const VisitorBatch& r, const ObserveCall& c) {
+    bool done;
+    int rc = check_observe(f, r, c, &done); if (rc || done) return rc;
     HIP_TRY(hipSetDevice(f->device));
-    const size_t rows = n * how_many * 8;
-    const size_t o_hi = 0, o_lo = o_hi + align256(n * 8), o_item = o_lo + align256(n * 8), o_con = o_item + align256(n * 8), o_ids = o_con + align256(n),
-                 o_sc = o_ids + align256(rows), o_cnt = o_sc + align256(rows), o_rank = o_cnt + align256(n * 4), o_times = o_rank + align256(n * 4), bytes = o_times + (times ? align256(n * 8) : 0);
-    StageBuf buf; int rc = buf.alloc(bytes, "srn_feedback_observe"); if (rc) return rc;
-    char* b = buf.p;
+    const size_t n = r.n, rows = n * c.how_many;
+    Bump b; StagedBatch in;
+    in.plan(b, r);
+    const auto ids = b.of<uint64_t>(rows); const auto scores = b.of<double>(rows); const auto counts = b.of<uint32_t>(n), rank = b.of<uint32_t>(n);
+    StageBuf buf; if ((rc = buf.alloc(b.bytes, "srn_feedback_observe"))) return rc;
+    char* const base = buf.p;
     hipStream_t st = nullptr;   // a stream of this call's own: two host callers do not wait for each other's copies
     HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
     auto run = [&]() -> int {
-        HIP_TRY(hipMemcpyAsync(b + o_hi, hi, n * 8, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(b + o_lo, lo, n * 8, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(b + o_item, item, n * 8, hipMemcpyHostToDevice, st));
-        if (consent) HIP_TRY(hipMemcpyAsync(b + o_con, consent, n, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(b + o_ids, ids, rows, hipMemcpyHostToDevice, st));
-        if (scores) HIP_TRY(hipMemcpyAsync(b + o_sc, scores, rows, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(b + o_cnt, counts, n * 4, hipMemcpyHostToDevice, st));
-        if (times) HIP_TRY(hipMemcpyAsync(b + o_times, times, n * 8, hipMemcpyHostToDevice, st));
-        int rc2 = fb_observe_device(f, (const uint64_t*)(b + o_hi), (const uint64_t*)(b + o_lo), (const uint64_t*)(b + o_item), consent ? (const uint8_t*)(b + o_con) : nullptr, n,
-                                    now_secs, (const uint64_t*)(b + o_ids), scores ? (const double*)(b + o_sc) : nullptr, (const uint32_t*)(b + o_cnt), how_many,
-                                    (uint32_t*)(b + o_rank), st, times ? (const uint64_t*)(b + o_times) : nullptr);
-        if (rc2) { (void)hipStreamSynchronize(st); return rc2; }
-        if (out_rank) HIP_TRY(hipMemcpyAsync(out_rank, b + o_rank, n * 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
+        VisitorBatch dr;
+        int rc2 = in.upload(base, r, st, &dr); if (rc2) return rc2;
+        HIP_TRY(hipMemcpyAsync(ids.at(base), c.ids, rows * 8, hipMemcpyHostToDevice, st));
+        if (c.scores) HIP_TRY(hipMemcpyAsync(scores.at(base), c.scores, rows * 8, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(counts.at(base), c.counts, n * 4, hipMemcpyHostToDevice, st));
+        if ((rc2 = fb_observe_device(f, dr, ObserveCall{ids.at(base), c.scores ? scores.at(base) : nullptr, counts.at(base), c.how_many, rank.at(base), st}))) return rc2;
+        if (c.out_rank) HIP_TRY(hipMemcpyAsync(c.out_rank, rank.at(base), n * 4, hipMemcpyDeviceToHost, st));
         return SRN_OK;
     };
     rc = run();
-    (void)hipStreamSynchronize(st);
+    const hipError_t e = hipStreamSynchronize(st);
     (void)hipStreamDestroy(st);
+    if (rc == SRN_OK && e != hipSuccess) return fail(SRN_EHIP, std::string("hipStreamSynchronize(st): ") + hipGetErrorString(e));
     return rc;
 }
 

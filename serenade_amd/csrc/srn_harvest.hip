@@ -183,14 +183,13 @@ int canonical_order(srn_harvest* h, size_t n, hipEvent_t last, hipStream_t st, S
     size_t tmp = 0, t1 = 0;
     int rc = key_sort_tmp_bytes(n, st, &tmp); if (rc) return rc;
     HIP_TRY(rocprim::exclusive_scan(nullptr, t1, (uint64_t*)nullptr, (uint64_t*)nullptr, 0ull, n + 1, rocprim::plus<uint64_t>(), st)); tmp = std::max(tmp, t1);
-    const size_t k8 = align256((n + 1) * 8), w = align256(n * 4), bytes = 4 * k8 + 2 * w + align256(tmp);
-    if (bytes > h->xs_bytes) {   // (an earlier call may still use the scratch: wait for it before it is freed)
-        HIP_TRY(hipEventSynchronize(last));
-        if ((rc = ensure(&h->xs, &h->xs_bytes, bytes))) return rc;
-    }
-    char* b = h->xs;
-    sc->lens = (uint64_t*)(b + 2 * k8); sc->off = (uint64_t*)(b + 3 * k8); sc->tmp = b + 4 * k8 + 2 * w; sc->tmp_bytes = tmp;
-    KeySort ks{{(uint64_t*)b, (uint64_t*)(b + k8)}, {(uint32_t*)(b + 4 * k8), (uint32_t*)(b + 4 * k8 + w)}, sc->tmp, tmp, n, st};
+    Bump b;   // (the key buffers n + 1 wide, as the events' lengths and offsets: a sort by four words over the log's own arrays, so KeySort directly, not the batch's front)
+    const auto keyA = b.of<uint64_t>(n + 1), keyB = b.of<uint64_t>(n + 1), lens = b.of<uint64_t>(n + 1), off = b.of<uint64_t>(n + 1);
+    const auto idxA = b.of<uint32_t>(n), idxB = b.of<uint32_t>(n); const auto tmp_at = b.of<char>(tmp);
+    if ((rc = grow_behind(last, &h->xs, &h->xs_bytes, b.bytes))) return rc;
+    char* const xs = h->xs;
+    sc->lens = lens.at(xs); sc->off = off.at(xs); sc->tmp = tmp_at.at(xs); sc->tmp_bytes = tmp;
+    KeySort ks{{keyA.at(xs), keyB.at(xs)}, {idxA.at(xs), idxB.at(xs)}, sc->tmp, tmp, n, st};
     if ((rc = ks.begin(h->key_lo)) || (rc = ks.pass(KeyWord{h->key_hi})) || (rc = ks.pass(KeyWord{h->epoch})) || (rc = ks.pass(KeyBeyond{h->words}, 0, 1))) return rc;
     HIP_TRY(hipGetLastError());
     sc->order = ks.order();
@@ -390,22 +389,19 @@ int harvest_export_host(srn_harvest* h, size_t cap, uint64_t* hi, uint64_t* lo, 
     if (items_stride < h->items_cap) return fail(SRN_ERANGE, std::string(who) + ": items_stride below the longest session the harvest may hold (its items_cap)");
     if (held > cap) return fail(SRN_ERANGE, std::string(who) + ": more stored sessions than the arrays hold (*n is their number)");
     if (held == 0) return SRN_OK;
-    const size_t o_hi = 0, o_lo = o_hi + align256(held * 8), o_ep = o_lo + align256(held * 8), o_len = o_ep + align256(held * 8), o_items = o_len + align256(held * 4),
-                 o_word = o_items + align256(held * items_stride * 8), bytes = o_word + 256;
-    char* b = nullptr;
-    if (hipMalloc((void**)&b, bytes) != hipSuccess) { (void)hipGetLastError(); return fail(SRN_ENOMEM, std::string(who) + ": no device memory for the staging copies"); }
-    rc = export_enqueue(h, held, held, (uint64_t*)(b + o_hi), (uint64_t*)(b + o_lo), (uint64_t*)(b + o_ep), (uint32_t*)(b + o_len), (uint64_t*)(b + o_items), items_stride,
-                        (uint64_t*)(b + o_word), e.last, e.own);
+    const Dense d(held, items_stride);
+    StageBuf buf; if ((rc = buf.alloc(d.bytes, who))) return rc;
+    char* const p = buf.p;
+    rc = export_enqueue(h, held, held, d.hi.at(p), d.lo.at(p), d.ep.at(p), d.len.at(p), d.items.at(p), items_stride, d.word.at(p), e.last, e.own);
     hipError_t err = hipSuccess;
     if (rc == SRN_OK) {
-        err = hipMemcpyAsync(hi, b + o_hi, held * 8, hipMemcpyDeviceToHost, e.own);
-        if (err == hipSuccess) err = hipMemcpyAsync(lo, b + o_lo, held * 8, hipMemcpyDeviceToHost, e.own);
-        if (err == hipSuccess) err = hipMemcpyAsync(epoch, b + o_ep, held * 8, hipMemcpyDeviceToHost, e.own);
-        if (err == hipSuccess) err = hipMemcpyAsync(len, b + o_len, held * 4, hipMemcpyDeviceToHost, e.own);
-        if (err == hipSuccess && items_stride) err = hipMemcpyAsync(items, b + o_items, held * items_stride * 8, hipMemcpyDeviceToHost, e.own);
+        err = hipMemcpyAsync(hi, d.hi.at(p), held * 8, hipMemcpyDeviceToHost, e.own);
+        if (err == hipSuccess) err = hipMemcpyAsync(lo, d.lo.at(p), held * 8, hipMemcpyDeviceToHost, e.own);
+        if (err == hipSuccess) err = hipMemcpyAsync(epoch, d.ep.at(p), held * 8, hipMemcpyDeviceToHost, e.own);
+        if (err == hipSuccess) err = hipMemcpyAsync(len, d.len.at(p), held * 4, hipMemcpyDeviceToHost, e.own);
+        if (err == hipSuccess && items_stride) err = hipMemcpyAsync(items, d.items.at(p), held * items_stride * 8, hipMemcpyDeviceToHost, e.own);
     }
     const hipError_t err2 = hipStreamSynchronize(e.own);
-    (void)hipFree(b);
     if (rc) return rc;
     if (err != hipSuccess || err2 != hipSuccess) return fail(SRN_EHIP, std::string(who) + ": " + hipGetErrorString(err != hipSuccess ? err : err2));
     return SRN_OK;

@@ -320,6 +320,18 @@ inline uint32_t eval_excl_capacity(const srn_eval_trial_t& t) {
 void eval_set_free(srn_eval_set* set);
 }  // namespace srn
 
+// ---- a visitor batch: what the batch calls of the session store and the click feedback log take (srn_visitors.h sorts and stages it) ----
+namespace srn {
+// the request side, host or device pointers alike: request i = (key_hi[i], key_lo[i], item[i], consent[i]) at times[i].  consent null: every request consents;
+// times null: an untimed batch, every request at now_secs (timed, now_secs is the capacity rule's sweep clock alone: DESIGN.md 11.6)
+struct VisitorBatch { const uint64_t* key_hi; const uint64_t* key_lo; const uint64_t* item; const uint8_t* consent; const uint64_t* times; size_t n; uint64_t now_secs; };
+inline bool has_request_arrays(const VisitorBatch& r, bool timed) { return r.key_hi && r.key_lo && r.item && (!timed || r.times); }
+constexpr uint32_t kMaxBatch = 1u << 24;   // requests in one call (the store's q_off is 32-bit: n * SRN_MAX_SESSION_LEN < 2^32)
+// ... and each owner's side: the predict parameters and the rows out; the served rows in and the ranks out (scores and out_rank may be null).  stream: the device entries'
+struct RecommendCall { size_t max_items, k, m, how_many; unsigned flags; uint64_t* ids; double* scores; uint32_t* counts; void* stream; };
+struct ObserveCall { const uint64_t* ids; const double* scores; const uint32_t* counts; size_t how_many; uint32_t* out_rank; void* stream; };
+}  // namespace srn
+
 // ---- device-resident session store (srn_sessions_dev.hip); arguments of the batch calls already checked by the C ABI glue ----
 namespace srn {
 int dsess_create(int device, size_t capacity, size_t items_cap, uint64_t ttl_secs, uint64_t idle_secs, srn_device_sessions** out);
@@ -348,12 +360,8 @@ int dsess_growth(srn_device_sessions* s, uint64_t* max_capacity, uint64_t* grows
 int dsess_save(srn_device_sessions* s, const char* path, uint64_t now_secs);
 int dsess_load(const char* path, int device, size_t capacity, size_t items_cap, uint64_t ttl_secs, uint64_t idle_secs, srn_device_sessions** out);
 int dsess_file_info(const char* path, srn_device_sessions_file_info_t* out);
-int dsess_recommend_device(const srn_index* idx, srn_device_sessions* s, const uint64_t* d_hi, const uint64_t* d_lo, const uint64_t* d_item, const uint8_t* d_consent,
-                           size_t n, uint64_t now_secs, size_t max_items, size_t k, size_t m, size_t how_many, unsigned flags,
-                           uint64_t* d_ids, double* d_scores, uint32_t* d_counts, void* stream, const uint64_t* d_times = nullptr);   // d_times: a timed batch
-int dsess_recommend_host(const srn_index* idx, srn_device_sessions* s, const uint64_t* hi, const uint64_t* lo, const uint64_t* item, const uint8_t* consent,
-                         size_t n, uint64_t now_secs, size_t max_items, size_t k, size_t m, size_t how_many, unsigned flags,
-                         uint64_t* ids, double* scores, uint32_t* counts, const uint64_t* times = nullptr);
+int dsess_recommend_device(const srn_index* idx, srn_device_sessions* s, const VisitorBatch& r, const RecommendCall& c);
+int dsess_recommend_host(const srn_index* idx, srn_device_sessions* s, const VisitorBatch& r, const RecommendCall& c);
 // trending items (srn_trending.hip): the items the store's live sessions hold most often
 int dsess_top_items(srn_device_sessions* s, uint64_t now_secs, uint64_t since_secs, uint32_t min_count, size_t cap, uint64_t* out_ids, uint32_t* out_counts, size_t* out_n);
 int dsess_device_of(const srn_device_sessions* s);
@@ -370,11 +378,8 @@ int harvest_events_device(srn_harvest* h, uint64_t id_base, size_t cap_rows, uin
 // click feedback log (srn_feedback.hip): every argument check is its own
 int fb_create(int device, size_t capacity, size_t row_cap, uint64_t ttl_secs, uint64_t idle_secs, srn_feedback** out);
 void fb_free(srn_feedback* f);
-int fb_observe_device(srn_feedback* f, const uint64_t* d_hi, const uint64_t* d_lo, const uint64_t* d_item, const uint8_t* d_consent, size_t n, uint64_t now_secs,
-                      const uint64_t* d_ids, const double* d_scores, const uint32_t* d_counts, size_t how_many, uint32_t* d_out_rank, void* stream,
-                      const uint64_t* d_times = nullptr);
-int fb_observe_host(srn_feedback* f, const uint64_t* hi, const uint64_t* lo, const uint64_t* item, const uint8_t* consent, size_t n, uint64_t now_secs,
-                    const uint64_t* ids, const double* scores, const uint32_t* counts, size_t how_many, uint32_t* out_rank, const uint64_t* times = nullptr);
+int fb_observe_device(srn_feedback* f, const VisitorBatch& r, const ObserveCall& c);
+int fb_observe_host(srn_feedback* f, const VisitorBatch& r, const ObserveCall& c);
 int fb_stats(srn_feedback* f, srn_feedback_stats_t* out);
 int fb_histogram(srn_feedback* f, uint64_t* hits_model, uint64_t* hits_filled, size_t cap);
 int fb_reset_counters(srn_feedback* f);

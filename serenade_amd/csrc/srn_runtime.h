@@ -142,12 +142,15 @@ struct DeviceState {
 
 // ---- shared helpers (srn_runtime.hip) ----
 // Regions of one buffer, carved before the buffer exists: take() reserves `bytes` at the cursor and moves it to the next multiple of `align`; the region is typed once the
-// base is known, region.at(base).  `bytes` is then the size to allocate
+// base is known, region.at(base).  `bytes` is then the size to allocate.  of<T>(count) takes count elements of T.  A region that was never taken -- one declared under a
+// condition that did not hold -- is null at every base
 struct Bump {
-    template <typename T> struct Region { size_t off; T* at(char* base) const { return (T*)(base + off); } };
+    static constexpr size_t kNowhere = ~(size_t)0;
+    template <typename T> struct Region { size_t off = kNowhere; T* at(char* base) const { return off == kNowhere ? nullptr : (T*)(base + off); } };
     size_t align, bytes = 0;
     explicit Bump(size_t align_ = 256) : align(align_) {}
     template <typename T> Region<T> take(size_t n_bytes) { const size_t o = bytes; bytes += (n_bytes + align - 1) / align * align; return Region<T>{o}; }
+    template <typename T> Region<T> of(size_t count) { return take<T>(count * sizeof(T)); }
 };
 int ensure(char** p, size_t* have, size_t need, bool exact = false);   // grow-only device scratch (exact: no room to spare)
 int ensure_list(uint32_t** p, size_t* cap, size_t nq, size_t bytes);   // ... a list sized for `nq` queries: exactly `bytes`, *cap = nq

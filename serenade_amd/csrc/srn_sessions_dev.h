@@ -1,5 +1,5 @@
 // The device session store's slot and handle (srn_sessions_dev.hip), shared with the code that reads the table beside it (srn_trending.hip, srn_harvest.hip).
-// The table underneath is srn_visitor_table.h's; the store's layout and rules: the head comment of srn_sessions_dev.hip.
+// The table underneath is srn_visitor_table.h's; the store's layout and rules: the head comment of srn_sessions_dev.hip.  Also the staging layout of an export's dense arrays.
 #pragma once
 #include "srn_visitor_table.h"   // SlotHead, Table, the slot states, VisitorTable
 
@@ -10,6 +10,16 @@ __device__ __forceinline__ uint64_t* slot_items(SlotHead* h) { return (uint64_t*
 // the session harvest's device words (srn_harvest.hip) and the two halves of an append flag
 enum : uint32_t { kHvCursor = 0, kHvLost, kHvShort, kHvReturn, kHvRebuild, kHvCleared, kHvItems, kHvWords = 8 };
 constexpr uint64_t kHvStore = 1, kHvSkip = 1ull << 32;
+
+// the dense arrays of n entries in one staging buffer -- the export form of the store and of the harvest: key_hi | key_lo | epoch | len | items | a u64 word
+struct Dense {
+    Bump::Region<uint64_t> hi, lo, ep, items, word; Bump::Region<uint32_t> len; size_t bytes;
+    Dense(size_t n, size_t items_stride) {
+        Bump b;
+        hi = b.of<uint64_t>(n); lo = b.of<uint64_t>(n); ep = b.of<uint64_t>(n); len = b.of<uint32_t>(n); items = b.of<uint64_t>(n * items_stride); word = b.of<uint64_t>(1);
+        bytes = b.bytes;
+    }
+};
 
 }  // namespace srn
 
@@ -44,7 +54,6 @@ struct srn_device_sessions : srn::VisitorTable {            // get / update / sw
     char* old = nullptr;                                    // the pair's other table: a sweep rebuilds into it and flips, so it holds the previous contents until the next one
     uint32_t len_bound = 1;                                 // upper bound of the stored session lengths (predict's max_len_hint)
     uint32_t history = 0;                                   // srn_device_sessions_set_history: the window the store keeps (0: max_items_in_session, as the reference)
-    char* ws = nullptr; size_t ws_bytes = 0;                // per-batch scratch, grows with the largest n seen
     char* stage = nullptr; size_t stage_bytes = 0;          // the host-pointer entry point's device copies
     std::mutex stage_mu;
     char* xs = nullptr; size_t xs_bytes = 0;                // export / import scratch (flags and places per slot; sort buffers per entry)

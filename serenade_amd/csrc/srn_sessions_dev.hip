@@ -42,7 +42,8 @@
 // The table underneath -- the slot's head, the count and rebuild kernels over a payload functor, the capacity rule (make_room), the sweep's tail, the one-key read-back
 // and create's and free's shared halves -- is srn_visitor_table.h's, shared with the click feedback log.  Here: the payload (len, items), the batch kernels, the
 // pair of tables and its flip, the harvest hooks, resize and growth, export / import and the file form.
-// The sort, the run predicates and the find-or-claim probe are srn_visitors.h's, shared with the feedback log and the harvest.
+// The sort, the run predicates and the find-or-claim probe are srn_visitors.h's, shared with the feedback log and the harvest; so is what a batch call opens with --
+// the sorted front of the call's VisitorBatch (srn_internal.h), the timed / untimed dispatch, the host stage -- over a scratch plan (Bump) and grow_behind.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -61,14 +62,13 @@
 #include "srn_runtime.h"
 #include "srn_device.h"
 #include "srn_sessions_dev.h"   // the store's handle (shared with srn_trending.hip, srn_harvest.hip) over srn_visitor_table.h: the table, its kernels and the capacity rule
-#include "srn_visitors.h"       // the run predicates, find_or_claim, the key sort (shared with srn_feedback.hip, srn_harvest.hip)
+#include "srn_visitors.h"       // the run predicates, find_or_claim, the key sort, the sorted front and the host stage (shared with srn_feedback.hip, srn_harvest.hip)
 #include "srn_hipsync.h"
 
 namespace srn {
 
 namespace {
 constexpr uint32_t kTPB = kTableTPB;          // (grid_for)
-constexpr uint32_t kMaxBatch = 1u << 24;       // q_off is 32-bit: n * SRN_MAX_SESSION_LEN < 2^32
 
 // One struct for the untimed and the timed batch.  Untimed, when, runpos and run_head are null and never read; timed, `now` is not read: a run is cut
 // into SEGMENTS wherever a request finds its predecessor's time idle, headpos marks segment heads -- so that run_start becomes the segment start and slen is 0 at a
@@ -377,7 +377,7 @@ void dsess_free(srn_device_sessions* s) {
     if (s->harvest) { std::lock_guard<std::mutex> g(s->harvest->mu); s->harvest->store = nullptr; s->harvest = nullptr; }   // freeing the store detaches its harvest, before its stream goes
     table_release(s);
     for (hipEvent_t e : s->tev) if (e) (void)hipEventDestroy(e);
-    for (void* p : {(void*)s->old, (void*)s->ws, (void*)s->stage, (void*)s->xs, (void*)s->hs}) if (p) (void)hipFree(p);
+    for (void* p : {(void*)s->old, (void*)s->stage, (void*)s->xs, (void*)s->hs}) if (p) (void)hipFree(p);
     delete s;
 }
 
@@ -600,22 +600,28 @@ static int recommend_no_store(const srn_index* idx, const uint64_t* d_item, cons
     return rc;
 }
 
-// arguments already checked by the C ABI glue (predict's own checks, null buffers, n > 0)
-int dsess_recommend_device(const srn_index* idx, srn_device_sessions* s, const uint64_t* d_hi, const uint64_t* d_lo, const uint64_t* d_item, const uint8_t* d_consent,
-                           size_t n, uint64_t now_secs, size_t max_items, size_t k, size_t m, size_t how_many, unsigned flags,
-                           uint64_t* d_ids, double* d_scores, uint32_t* d_counts, void* stream, const uint64_t* d_times) {
-    if (max_items == 0) return fail(SRN_EINVAL, "srn_recommend_batch: max_items_in_session must be > 0");
-    if (n > kMaxBatch) return fail(SRN_ERANGE, "srn_recommend_batch: more than 2^24 requests in one call");
-    hipStream_t st = (hipStream_t)stream;
-    const bool excl_seen = (flags & SRN_FLAG_EXCLUDE_SEEN) != 0u, fill = (flags & SRN_FLAG_FILL) != 0u;   // (SRN_FLAG_FILL: srn_fill.hip, behind the call's launch sequence and filter)
-    LaunchParams p = launch_params(n, k, m, how_many, flags & ~(unsigned)(SRN_FLAG_EXCLUDE_SEEN | SRN_FLAG_FILL), 0, nullptr, nullptr, d_ids, d_scores, d_counts);   // (the sessions: below)
+// The checks every form of the call shares, in the order the entry points have always made them; the C ABI glue has checked predict's own arguments, the buffers
+// and n > 0.  host: the host-pointer form can read the consent array, so a call without a store that needs one is refused before anything is staged
+static int check_recommend(const srn_device_sessions* s, const VisitorBatch& r, const RecommendCall& c, bool host) {
+    if (c.max_items == 0) return fail(SRN_EINVAL, "srn_recommend_batch: max_items_in_session must be > 0");
+    if (host && !s && (!r.consent || std::any_of(r.consent, r.consent + r.n, [](uint8_t x) { return x != 0; }))) return fail(SRN_EINVAL, "srn_recommend_batch: user consent needs a session store");
+    if (r.n > kMaxBatch) return fail(SRN_ERANGE, "srn_recommend_batch: more than 2^24 requests in one call");
+    return SRN_OK;
+}
+
+int dsess_recommend_device(const srn_index* idx, srn_device_sessions* s, const VisitorBatch& r, const RecommendCall& c) {
+    int rc = check_recommend(s, r, c, false); if (rc) return rc;
+    const size_t n = r.n, max_items = c.max_items, how_many = c.how_many;
+    hipStream_t st = (hipStream_t)c.stream;
+    const bool excl_seen = (c.flags & SRN_FLAG_EXCLUDE_SEEN) != 0u, fill = (c.flags & SRN_FLAG_FILL) != 0u;   // (SRN_FLAG_FILL: srn_fill.hip, behind the call's launch sequence and filter)
+    LaunchParams p = launch_params(n, c.k, c.m, how_many, c.flags & ~(unsigned)(SRN_FLAG_EXCLUDE_SEEN | SRN_FLAG_FILL), 0, nullptr, nullptr, c.ids, c.scores, c.counts);   // (the sessions: below)
     if (!s) {   // (every session is its item, which is never in its own row: SRN_FLAG_EXCLUDE_SEEN has nothing to exclude)
         if (max_items > SRN_MAX_SESSION_LEN) return fail(SRN_ERANGE, "srn_recommend_batch: max_items_in_session above SRN_MAX_SESSION_LEN");
-        return recommend_no_store(idx, d_item, d_consent, n, p, st, fill);
+        return recommend_no_store(idx, r.item, r.consent, n, p, st, fill);
     }
     if (max_items > s->items_cap) return fail(SRN_ERANGE, "srn_recommend_batch: max_items_in_session above the store's items_cap");
     if (s->device != idx->device) return fail(SRN_EINVAL, "srn_recommend_batch: the store and the index are on different devices");
-    const uint64_t now = now_secs ? now_secs : wall_secs();
+    const uint64_t now = r.now_secs ? r.now_secs : wall_secs();
     std::lock_guard<std::mutex> g(s->mu);
     const uint32_t H = s->history, limit = H ? H : (uint32_t)max_items;
     if (H > s->items_cap) return fail(SRN_ERANGE, "srn_recommend_batch: the store's history window is above its items_cap (lowered by a resize): set a smaller history or resize again");
@@ -623,71 +629,61 @@ int dsess_recommend_device(const srn_index* idx, srn_device_sessions* s, const u
     const uint32_t hint = std::max<uint32_t>(s->len_bound, limit);          // the longest window the store may hold behind this call
     const uint32_t phint = H ? (uint32_t)max_items : hint;                  // ... and the longest session predict reads
     if (excl_seen && how_many + hint > SRN_MAX_HOW_MANY) return fail(SRN_ERANGE, "srn_recommend_batch: how_many + the store's longest window above SRN_MAX_HOW_MANY (SRN_FLAG_EXCLUDE_SEEN)");
-    int rc = room_for(s, n, now); if (rc) return rc;
+    if ((rc = room_for(s, n, now))) return rc;
     HIP_TRY(hipSetDevice(s->device));
-    // scratch: sort keys and indices (double-buffered), the per-position and per-request words, the kept clicks, the CSR batch, rocPRIM's temporary storage
-    size_t tmp = 0, t1 = 0;
-    if ((rc = key_sort_tmp_bytes(n, st, &tmp))) return rc;
-    HIP_TRY(rocprim::exclusive_scan(nullptr, t1, (uint32_t*)nullptr, (uint32_t*)nullptr, 0u, n + 1, rocprim::plus<uint32_t>(), st)); tmp = std::max(tmp, t1);
-    HIP_TRY(rocprim::inclusive_scan(nullptr, t1, (uint32_t*)nullptr, (uint32_t*)nullptr, n, rocprim::maximum<uint32_t>(), st)); tmp = std::max(tmp, t1);
+    // scratch: the sorted front's (sort keys and indices, rocPRIM's temporary storage -- also the scans' -- and a timed batch's times), then the per-position and
+    // per-request words, the kept clicks and the CSR batch; a region under a condition is null where the condition does not hold
+    size_t scan = 0, t1 = 0;
+    HIP_TRY(rocprim::exclusive_scan(nullptr, scan, (uint32_t*)nullptr, (uint32_t*)nullptr, 0u, n + 1, rocprim::plus<uint32_t>(), st));
+    HIP_TRY(rocprim::inclusive_scan(nullptr, t1, (uint32_t*)nullptr, (uint32_t*)nullptr, n, rocprim::maximum<uint32_t>(), st)); scan = std::max(scan, t1);
     srn_harvest* const hv = s->harvest;
     size_t hv_bytes = 0;   // an attached harvest's flags, places and scan storage for the heads that return after idle
     if (hv && (rc = harvest_scratch_bytes(n, &hv_bytes))) return rc;
-    const size_t w = align256((n + 1) * 4);
-    const size_t o_keyA = 0, o_keyB = o_keyA + align256(n * 8), o_idxA = o_keyB + align256(n * 8), o_idxB = o_idxA + w, o_slot = o_idxB + w, o_slen = o_slot + w,
-                 o_kept = o_slen + w, o_head = o_kept + w, o_kex = o_head + w, o_run = o_kex + w, o_qlen = o_run + w, o_qoff = o_qlen + w, o_comp = o_qoff + w,
-                 o_flat = o_comp + align256(n * 8), o_tmp = o_flat + align256(n * (size_t)hint * 8),
-                 o_plen = o_tmp + align256(tmp), o_poff = o_plen + (H ? w : 0), o_pflat = o_poff + (H ? w : 0), o_hv = o_pflat + (H ? align256(n * (size_t)phint * 8) : 0),
-                 o_t = o_hv + hv_bytes, o_rpos = o_t + (d_times ? align256(n * 8) : 0), o_rhead = o_rpos + (d_times ? w : 0), bytes = o_rhead + (d_times ? w : 0);   // (a timed batch only)
-    if (bytes > s->ws_bytes) {   // (the previous call may still read the scratch: wait for it before it is freed)
-        HIP_TRY(hipEventSynchronize(s->last));
-        if ((rc = ensure(&s->ws, &s->ws_bytes, bytes))) return rc;
-    }
+    Bump b; SortedFront front;
+    if ((rc = front.plan(b, r, st, scan))) return rc;
+    const auto slot_of = b.of<uint32_t>(n + 1), slen = b.of<uint32_t>(n + 1), kept = b.of<uint32_t>(n + 1), headpos = b.of<uint32_t>(n + 1), kex = b.of<uint32_t>(n + 1),
+               run_start = b.of<uint32_t>(n + 1), qlen = b.of<uint32_t>(n + 1), q_off = b.of<uint32_t>(n + 1);
+    const auto compact = b.of<uint64_t>(n), items_flat = b.of<uint64_t>(n * (size_t)hint);
+    Bump::Region<uint32_t> plen, p_off, runpos, run_head; Bump::Region<uint64_t> pflat, hv_words;
+    if (H) { plen = b.of<uint32_t>(n + 1); p_off = b.of<uint32_t>(n + 1); pflat = b.of<uint64_t>(n * (size_t)phint); }
+    if (hv) hv_words = b.take<uint64_t>(hv_bytes);
+    if (r.times) { runpos = b.of<uint32_t>(n + 1); run_head = b.of<uint32_t>(n + 1); }   // a timed batch: a second max scan for the run's slot
+    if ((rc = grow_behind(s->last, &s->ws, &s->ws_bytes, b.bytes))) return rc;
     HIP_TRY(hipStreamWaitEvent(st, s->last, 0));
     const bool timed = s->timing;
     if (timed) HIP_TRY(hipEventRecord(s->tev[0], st));
-    char* b = s->ws;
+    char* const ws = s->ws;
+    if ((rc = front.run(ws, r, st))) return rc;
     const dim3 gn = grid_for(n), gn1 = grid_for(n + 1);
-    const uint32_t n32 = (uint32_t)n;
-    // stable LSD passes: key_lo, key_hi, then (where some request may not consent) the consent bit -- consenting requests first, each visitor's in request order
-    KeySort ks{{(uint64_t*)(b + o_keyA), (uint64_t*)(b + o_keyB)}, {(uint32_t*)(b + o_idxA), (uint32_t*)(b + o_idxB)}, b + o_tmp, tmp, n, st};
-    if ((rc = ks.begin(d_lo)) || (rc = ks.pass(KeyWord{d_hi})) || (d_consent && (rc = ks.pass(KeyNoConsent{d_consent}, 0, 1)))) return rc;
-    const uint32_t* order = ks.order();
     BatchArgs a{};
-    a.t = s->tab(); a.key_hi = d_hi; a.key_lo = d_lo; a.item = d_item; a.consent = d_consent; a.order = order; a.n = n32; a.max_items = (uint32_t)max_items; a.limit = limit;
-    if (H) { a.plen = (uint32_t*)(b + o_plen); a.p_off = (uint32_t*)(b + o_poff); a.pflat = (uint64_t*)(b + o_pflat); }
+    a.t = s->tab(); a.key_hi = r.key_hi; a.key_lo = r.key_lo; a.item = r.item; a.consent = r.consent; a.order = front.order; a.n = (uint32_t)n; a.max_items = (uint32_t)max_items; a.limit = limit;
+    a.plen = plen.at(ws); a.p_off = p_off.at(ws); a.pflat = pflat.at(ws);
     a.now = now; a.idle = s->idle;
-    a.slot_of = (uint32_t*)(b + o_slot); a.slen = (uint32_t*)(b + o_slen); a.kept = (uint32_t*)(b + o_kept); a.headpos = (uint32_t*)(b + o_head);
-    a.kex = (uint32_t*)(b + o_kex); a.run_start = (uint32_t*)(b + o_run); a.qlen = (uint32_t*)(b + o_qlen); a.q_off = (uint32_t*)(b + o_qoff);
-    a.compact = (uint64_t*)(b + o_comp); a.items_flat = (uint64_t*)(b + o_flat); a.err = s->err();
-    if (d_times) {   // a timed batch: the same sequence over segments, with a second max scan for the run's slot and a second append behind sess_emit
-        a.when = (const uint64_t*)(b + o_t); a.runpos = (uint32_t*)(b + o_rpos); a.run_head = (uint32_t*)(b + o_rhead);
-        key_gather<<<gn, kTPB, 0, st>>>(KeyWord{d_times}, order, n32, (uint64_t*)(b + o_t));
-        sess_find<true><<<gn1, kTPB, 0, st>>>(a);
-    } else
-        sess_find<false><<<gn1, kTPB, 0, st>>>(a);
+    a.slot_of = slot_of.at(ws); a.slen = slen.at(ws); a.kept = kept.at(ws); a.headpos = headpos.at(ws);
+    a.kex = kex.at(ws); a.run_start = run_start.at(ws); a.qlen = qlen.at(ws); a.q_off = q_off.at(ws);
+    a.compact = compact.at(ws); a.items_flat = items_flat.at(ws); a.err = s->err();
+    a.when = front.when; a.runpos = runpos.at(ws); a.run_head = run_head.at(ws);
+    uint64_t* const hv_flags = hv_words.at(ws);
+    char* const tmp = front.tmp; const size_t tmp_bytes = front.tmp_bytes;
+    by_timed(r, [&](auto t) { sess_find<decltype(t)::value><<<gn1, kTPB, 0, st>>>(a); });
     if (hv) {   // the stored sessions the heads found idle, copied before sess_store overwrites their slots
-        if (d_times) sess_return_flag<true><<<gn1, kTPB, 0, st>>>(a, hv->min_len, (uint64_t*)(b + o_hv));
-        else sess_return_flag<false><<<gn1, kTPB, 0, st>>>(a, hv->min_len, (uint64_t*)(b + o_hv));
+        by_timed(r, [&](auto t) { sess_return_flag<decltype(t)::value><<<gn1, kTPB, 0, st>>>(a, hv->min_len, hv_flags); });
         HIP_TRY(hipGetLastError());
-        if ((rc = harvest_append(hv, a.t, a.slot_of, n, b + o_hv, true, st))) return rc;
+        if ((rc = harvest_append(hv, a.t, a.slot_of, n, (char*)hv_flags, true, st))) return rc;
     }
-    t1 = tmp; HIP_TRY(rocprim::exclusive_scan(b + o_tmp, t1, a.kept, a.kex, 0u, n + 1, rocprim::plus<uint32_t>(), st));
-    t1 = tmp; HIP_TRY(rocprim::inclusive_scan(b + o_tmp, t1, a.headpos, a.run_start, n, rocprim::maximum<uint32_t>(), st));
-    if (d_times) { t1 = tmp; HIP_TRY(rocprim::inclusive_scan(b + o_tmp, t1, a.runpos, a.run_head, n, rocprim::maximum<uint32_t>(), st)); }
+    t1 = tmp_bytes; HIP_TRY(rocprim::exclusive_scan(tmp, t1, a.kept, a.kex, 0u, n + 1, rocprim::plus<uint32_t>(), st));
+    t1 = tmp_bytes; HIP_TRY(rocprim::inclusive_scan(tmp, t1, a.headpos, a.run_start, n, rocprim::maximum<uint32_t>(), st));
+    if (r.times) { t1 = tmp_bytes; HIP_TRY(rocprim::inclusive_scan(tmp, t1, a.runpos, a.run_head, n, rocprim::maximum<uint32_t>(), st)); }
     sess_len<<<gn1, kTPB, 0, st>>>(a);   // (run_start is the segment start and slen 0 at a break: sess_len and sess_emit read a timed batch as they read any other)
-    t1 = tmp; HIP_TRY(rocprim::exclusive_scan(b + o_tmp, t1, a.qlen, a.q_off, 0u, n + 1, rocprim::plus<uint32_t>(), st));
-    if (H) { t1 = tmp; HIP_TRY(rocprim::exclusive_scan(b + o_tmp, t1, a.plen, a.p_off, 0u, n + 1, rocprim::plus<uint32_t>(), st)); }
+    t1 = tmp_bytes; HIP_TRY(rocprim::exclusive_scan(tmp, t1, a.qlen, a.q_off, 0u, n + 1, rocprim::plus<uint32_t>(), st));
+    if (H) { t1 = tmp_bytes; HIP_TRY(rocprim::exclusive_scan(tmp, t1, a.plen, a.p_off, 0u, n + 1, rocprim::plus<uint32_t>(), st)); }
     sess_emit<<<gn, kTPB, 0, st>>>(a);
-    if (d_times) {
-        if (hv) {   // the sessions ended inside the call, from the windows just emitted
-            sess_break_flag<<<gn1, kTPB, 0, st>>>(a, hv->min_len, (uint64_t*)(b + o_hv));
-            HIP_TRY(hipGetLastError());
-            if ((rc = harvest_append_csr(hv, order, d_hi, d_lo, a.when, a.items_flat, a.q_off, n, b + o_hv, st))) return rc;
-        }
-        sess_store<true><<<gn, kTPB, 0, st>>>(a);
-    } else
-        sess_store<false><<<gn, kTPB, 0, st>>>(a);
+    if (r.times && hv) {   // the sessions ended inside the call, from the windows just emitted
+        sess_break_flag<<<gn1, kTPB, 0, st>>>(a, hv->min_len, hv_flags);
+        HIP_TRY(hipGetLastError());
+        if ((rc = harvest_append_csr(hv, a.order, r.key_hi, r.key_lo, a.when, a.items_flat, a.q_off, n, (char*)hv_flags, st))) return rc;
+    }
+    by_timed(r, [&](auto t) { sess_store<decltype(t)::value><<<gn, kTPB, 0, st>>>(a); });
     HIP_TRY(hipGetLastError());
     // from here on the store has changed: whatever happens below, the next call is ordered behind this one
     s->bound += n;
@@ -705,65 +701,40 @@ int dsess_recommend_device(const srn_index* idx, srn_device_sessions* s, const u
     return rc;
 }
 
-int dsess_recommend_host(const srn_index* idx, srn_device_sessions* s, const uint64_t* hi, const uint64_t* lo, const uint64_t* item, const uint8_t* consent,
-                         size_t n, uint64_t now_secs, size_t max_items, size_t k, size_t m, size_t how_many, unsigned flags,
-                         uint64_t* ids, double* scores, uint32_t* counts, const uint64_t* times) {
-    if (!s && (!consent || std::any_of(consent, consent + n, [](uint8_t x) { return x != 0; }))) return fail(SRN_EINVAL, "srn_recommend_batch: user consent needs a session store");
-    if (n > kMaxBatch) return fail(SRN_ERANGE, "srn_recommend_batch: more than 2^24 requests in one call");
+int dsess_recommend_host(const srn_index* idx, srn_device_sessions* s, const VisitorBatch& r, const RecommendCall& c) {
+    int rc = check_recommend(s, r, c, true); if (rc) return rc;
     HIP_TRY(hipSetDevice(idx->device));
     // device copies: the store's staging, or (no store) a buffer of this call's own
-    const size_t rows = n * how_many * 8;
-    const size_t o_hi = 0, o_lo = o_hi + align256(n * 8), o_item = o_lo + align256(n * 8), o_con = o_item + align256(n * 8), o_ids = o_con + align256(n),
-                 o_sc = o_ids + align256(rows), o_cnt = o_sc + align256(rows), o_times = o_cnt + align256(n * 4), bytes = o_times + (times ? align256(n * 8) : 0);
-    char* own_buf = nullptr; hipStream_t st = nullptr;
+    const size_t n = r.n, rows = n * c.how_many;
+    Bump b; StagedBatch in;
+    in.plan(b, r);
+    const auto ids = b.of<uint64_t>(rows); const auto scores = b.of<double>(rows); const auto counts = b.of<uint32_t>(n);
+    StageBuf own_buf; hipStream_t st = nullptr;
     std::unique_lock<std::mutex> sl;
     if (s) {
         sl = std::unique_lock<std::mutex>(s->stage_mu);
         if (s->device != idx->device) return fail(SRN_EINVAL, "srn_recommend_batch: the store and the index are on different devices");
-        int rc = ensure(&s->stage, &s->stage_bytes, bytes); if (rc) return rc;
+        if ((rc = ensure(&s->stage, &s->stage_bytes, b.bytes))) return rc;
         st = s->own;
     } else {
-        HIP_TRY(hipMalloc((void**)&own_buf, bytes));
+        HIP_TRY(hipMalloc((void**)&own_buf.p, b.bytes));
     }
-    char* b = s ? s->stage : own_buf;
-    auto run = [&]() -> int {
-        HIP_TRY(hipMemcpyAsync(b + o_hi, hi, n * 8, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(b + o_lo, lo, n * 8, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(b + o_item, item, n * 8, hipMemcpyHostToDevice, st));
-        if (consent) HIP_TRY(hipMemcpyAsync(b + o_con, consent, n, hipMemcpyHostToDevice, st));
-        if (times) HIP_TRY(hipMemcpyAsync(b + o_times, times, n * 8, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemsetAsync(b + o_ids, 0, o_cnt - o_ids, st));   // (entries beyond a row's count read as zero, as in buffers a caller cleared)
-        int rc = dsess_recommend_device(idx, s, (const uint64_t*)(b + o_hi), (const uint64_t*)(b + o_lo), (const uint64_t*)(b + o_item), consent ? (const uint8_t*)(b + o_con) : nullptr,
-                                        n, now_secs, max_items, k, m, how_many, flags, (uint64_t*)(b + o_ids), (double*)(b + o_sc), (uint32_t*)(b + o_cnt), st,
-                                        times ? (const uint64_t*)(b + o_times) : nullptr);
-        if (rc) { (void)hipStreamSynchronize(st); return rc; }
-        HIP_TRY(hipSetDevice(idx->device));
-        HIP_TRY(hipMemcpyAsync(ids, b + o_ids, rows, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(scores, b + o_sc, rows, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(counts, b + o_cnt, n * 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        return SRN_OK;
-    };
-    const int rc = run();
-    if (own_buf) (void)hipFree(own_buf);
-    return rc ? rc : check_all_served(counts, n);
+    char* const base = s ? s->stage : own_buf.p;
+    VisitorBatch dr; RecommendCall dc = c;
+    dc.ids = ids.at(base); dc.scores = scores.at(base); dc.counts = counts.at(base); dc.stream = st;
+    if ((rc = in.upload(base, r, st, &dr))) return rc;
+    HIP_TRY(hipMemsetAsync(dc.ids, 0, counts.off - ids.off, st));   // (entries beyond a row's count read as zero, as in buffers a caller cleared)
+    if ((rc = dsess_recommend_device(idx, s, dr, dc))) { (void)hipStreamSynchronize(st); return rc; }
+    HIP_TRY(hipSetDevice(idx->device));
+    HIP_TRY(hipMemcpyAsync(c.ids, dc.ids, rows * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(c.scores, dc.scores, rows * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(c.counts, dc.counts, n * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return check_all_served(c.counts, n);
 }
 
 // ---- snapshot: count, bulk export / import, resize, growth, the file form ----
 namespace {
-int xs_ensure(srn_device_sessions* s, size_t bytes) {   // (the previous call may still use the scratch: wait for it before it is freed)
-    if (bytes <= s->xs_bytes) return SRN_OK;
-    HIP_TRY(hipEventSynchronize(s->last));
-    return ensure(&s->xs, &s->xs_bytes, bytes);
-}
-// offsets of the dense arrays of n entries in one buffer: key_hi | key_lo | epoch | len | items | (a u64 word)
-struct Dense { size_t hi, lo, ep, len, items, word, bytes; };
-Dense dense_layout(size_t n, size_t items_stride) {
-    Dense d{};
-    d.hi = 0; d.lo = d.hi + align256(n * 8); d.ep = d.lo + align256(n * 8); d.len = d.ep + align256(n * 8); d.items = d.len + align256(n * 4);
-    d.word = d.items + align256(n * items_stride * 8); d.bytes = d.word + 256;
-    return d;
-}
 
 // flags, scan, scatter on `st`, which already waits for `last` (mu held)
 int export_enqueue(srn_device_sessions* s, uint64_t now, size_t cap, uint64_t* d_hi, uint64_t* d_lo, uint64_t* d_epoch, uint32_t* d_len, uint64_t* d_items,
@@ -771,11 +742,12 @@ int export_enqueue(srn_device_sessions* s, uint64_t now, size_t cap, uint64_t* d
     const size_t n1 = (size_t)s->n_slots + 1;
     size_t tmp = 0;
     HIP_TRY(rocprim::exclusive_scan(nullptr, tmp, (uint32_t*)nullptr, (uint32_t*)nullptr, 0u, n1, rocprim::plus<uint32_t>(), st));
-    const size_t w = align256(n1 * 4);
-    int rc = xs_ensure(s, 2 * w + align256(tmp)); if (rc) return rc;
-    uint32_t* flag = (uint32_t*)s->xs; uint32_t* pos = (uint32_t*)(s->xs + w);
+    Bump b;
+    const auto flag_at = b.of<uint32_t>(n1), pos_at = b.of<uint32_t>(n1); const auto tmp_at = b.of<char>(tmp);
+    const int rc = grow_behind(s->last, &s->xs, &s->xs_bytes, b.bytes); if (rc) return rc;
+    uint32_t* flag = flag_at.at(s->xs); uint32_t* pos = pos_at.at(s->xs);
     sess_live_flag<<<grid_for(n1), kTPB, 0, st>>>(s->tab(), now, s->ttl, flag);
-    HIP_TRY(rocprim::exclusive_scan(s->xs + 2 * w, tmp, flag, pos, 0u, n1, rocprim::plus<uint32_t>(), st));
+    HIP_TRY(rocprim::exclusive_scan(tmp_at.at(s->xs), tmp, flag, pos, 0u, n1, rocprim::plus<uint32_t>(), st));
     ExportArgs a{};
     a.t = s->tab(); a.pos = pos; a.now = now; a.ttl = s->ttl; a.cap = cap; a.items_stride = items_stride;
     a.key_hi = d_hi; a.key_lo = d_lo; a.epoch = d_epoch; a.len = d_len; a.items = d_items; a.d_n = d_n;
@@ -794,16 +766,15 @@ int export_host_locked(srn_device_sessions* s, uint64_t now, size_t cap, uint64_
     if (items_stride < (exact_stride ? longest : (uint64_t)s->len_bound)) return fail(SRN_ERANGE, std::string(who) + ": items_stride below the longest session the store may hold");
     if (live > cap) return fail(SRN_ERANGE, std::string(who) + ": more live sessions than the arrays hold (*n is their number)");
     if (live == 0) return SRN_OK;
-    const Dense d = dense_layout(live, items_stride);
+    const Dense d(live, items_stride);
     StageBuf b; if ((rc = b.alloc(d.bytes, who))) return rc;
-    rc = export_enqueue(s, now, live, (uint64_t*)(b.p + d.hi), (uint64_t*)(b.p + d.lo), (uint64_t*)(b.p + d.ep), (uint32_t*)(b.p + d.len), (uint64_t*)(b.p + d.items),
-                        items_stride, (uint64_t*)(b.p + d.word), s->own);
+    rc = export_enqueue(s, now, live, d.hi.at(b.p), d.lo.at(b.p), d.ep.at(b.p), d.len.at(b.p), d.items.at(b.p), items_stride, d.word.at(b.p), s->own);
     if (rc) { (void)hipStreamSynchronize(s->own); return rc; }
-    hipError_t e = hipMemcpyAsync(hi, b.p + d.hi, live * 8, hipMemcpyDeviceToHost, s->own);
-    if (e == hipSuccess) e = hipMemcpyAsync(lo, b.p + d.lo, live * 8, hipMemcpyDeviceToHost, s->own);
-    if (e == hipSuccess) e = hipMemcpyAsync(epoch, b.p + d.ep, live * 8, hipMemcpyDeviceToHost, s->own);
-    if (e == hipSuccess) e = hipMemcpyAsync(len, b.p + d.len, live * 4, hipMemcpyDeviceToHost, s->own);
-    if (e == hipSuccess && items_stride) e = hipMemcpyAsync(items, b.p + d.items, live * items_stride * 8, hipMemcpyDeviceToHost, s->own);
+    hipError_t e = hipMemcpyAsync(hi, d.hi.at(b.p), live * 8, hipMemcpyDeviceToHost, s->own);
+    if (e == hipSuccess) e = hipMemcpyAsync(lo, d.lo.at(b.p), live * 8, hipMemcpyDeviceToHost, s->own);
+    if (e == hipSuccess) e = hipMemcpyAsync(epoch, d.ep.at(b.p), live * 8, hipMemcpyDeviceToHost, s->own);
+    if (e == hipSuccess) e = hipMemcpyAsync(len, d.len.at(b.p), live * 4, hipMemcpyDeviceToHost, s->own);
+    if (e == hipSuccess && items_stride) e = hipMemcpyAsync(items, d.items.at(b.p), live * items_stride * 8, hipMemcpyDeviceToHost, s->own);
     const hipError_t e2 = hipStreamSynchronize(s->own);
     if (e != hipSuccess || e2 != hipSuccess) return fail(SRN_EHIP, std::string(who) + ": " + hipGetErrorString(e != hipSuccess ? e : e2));
     return SRN_OK;
@@ -814,30 +785,32 @@ int import_locked(srn_device_sessions* s, const uint64_t* d_hi, const uint64_t* 
                   size_t items_stride, size_t n, hipStream_t st, const char* who) {
     if (n == 0) return SRN_OK;
     if (n > (1ull << 30)) return fail(SRN_ERANGE, std::string(who) + ": more than 2^30 entries in one call");
-    size_t tmp = 0;
-    int rc = key_sort_tmp_bytes(n, st, &tmp); if (rc) return rc;
-    const size_t w = align256(n * 4), k8 = align256(n * 8);
-    const size_t o_word = 0, o_keyA = 256, o_keyB = o_keyA + k8, o_idxA = o_keyB + k8, o_idxB = o_idxA + w, o_slot = o_idxB + w, o_win = o_slot + w, o_tmp = o_win + w;
-    if ((rc = xs_ensure(s, o_tmp + align256(tmp)))) return rc;
-    char* b = s->xs;
+    // scratch: the longest length's word, the sorted front of the entries' keys (no consent, no times), the heads' slots and the runs' winners
+    const VisitorBatch keys{d_hi, d_lo, nullptr, nullptr, nullptr, n, 0};
+    Bump b; SortedFront front;
+    const auto word_at = b.of<uint32_t>(1);
+    int rc = front.plan(b, keys, st); if (rc) return rc;
+    const auto slot_of = b.of<uint32_t>(n), win = b.of<uint32_t>(n);
+    if ((rc = grow_behind(s->last, &s->xs, &s->xs_bytes, b.bytes))) return rc;
+    char* const xs = s->xs;
+    uint32_t* const word = word_at.at(xs);
     const uint32_t n32 = (uint32_t)n; const dim3 gn = grid_for(n);
     HIP_TRY(hipStreamWaitEvent(st, s->last, 0));
-    HIP_TRY(hipMemsetAsync(b + o_word, 0, 4, st));
-    sess_import_maxlen<<<gn, kTPB, 0, st>>>(d_len, n32, (uint32_t*)(b + o_word));
+    HIP_TRY(hipMemsetAsync(word, 0, 4, st));
+    sess_import_maxlen<<<gn, kTPB, 0, st>>>(d_len, n32, word);
     HIP_TRY(hipGetLastError());
     uint32_t longest = 0;
-    HIP_TRY(hipMemcpyAsync(&longest, b + o_word, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&longest, word, 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     if (longest > s->items_cap) return fail(SRN_ERANGE, std::string(who) + ": a session is longer than the store's items_cap");
     if (longest > items_stride) return fail(SRN_ERANGE, std::string(who) + ": a session is longer than items_stride");
     // every entry counts as a new key; an import reclaims nothing (now = 1: no entry is older than the TTL), so a refused import leaves every slot where it was
     if ((rc = room_for(s, n, 1))) return rc;
     HIP_TRY(hipSetDevice(s->device));
-    KeySort ks{{(uint64_t*)(b + o_keyA), (uint64_t*)(b + o_keyB)}, {(uint32_t*)(b + o_idxA), (uint32_t*)(b + o_idxB)}, b + o_tmp, tmp, n, st};
-    if ((rc = ks.begin(d_lo)) || (rc = ks.pass(KeyWord{d_hi}))) return rc;
+    if ((rc = front.run(xs, keys, st))) return rc;
     ImportArgs a{};
     a.t = s->tab(); a.key_hi = d_hi; a.key_lo = d_lo; a.epoch = d_epoch; a.len = d_len; a.items = d_items; a.items_stride = items_stride;
-    a.order = ks.order(); a.n = n32; a.slot_of = (uint32_t*)(b + o_slot); a.win = (uint32_t*)(b + o_win); a.err = s->err();
+    a.order = front.order; a.n = n32; a.slot_of = slot_of.at(xs); a.win = win.at(xs); a.err = s->err();
     sess_import_find<<<gn, kTPB, 0, st>>>(a);
     sess_import_write<<<grid_for(n * 16), kTPB, 0, st>>>(a);
     HIP_TRY(hipGetLastError());
@@ -945,16 +918,15 @@ int dsess_import_host(srn_device_sessions* s, const uint64_t* hi, const uint64_t
     if (items_stride > SRN_MAX_SESSION_LEN) return fail(SRN_ERANGE, std::string(who) + ": items_stride above SRN_MAX_SESSION_LEN");
     std::lock_guard<std::mutex> g(s->mu);
     int rc = own_after_last(s); if (rc) return rc;
-    const Dense d = dense_layout(n, items_stride);
+    const Dense d(n, items_stride);
     StageBuf b; if ((rc = b.alloc(d.bytes, who))) return rc;
-    hipError_t e = hipMemcpyAsync(b.p + d.hi, hi, n * 8, hipMemcpyHostToDevice, s->own);
-    if (e == hipSuccess) e = hipMemcpyAsync(b.p + d.lo, lo, n * 8, hipMemcpyHostToDevice, s->own);
-    if (e == hipSuccess) e = hipMemcpyAsync(b.p + d.ep, epoch, n * 8, hipMemcpyHostToDevice, s->own);
-    if (e == hipSuccess) e = hipMemcpyAsync(b.p + d.len, len, n * 4, hipMemcpyHostToDevice, s->own);
-    if (e == hipSuccess && items_stride) e = hipMemcpyAsync(b.p + d.items, items, n * items_stride * 8, hipMemcpyHostToDevice, s->own);
+    hipError_t e = hipMemcpyAsync(d.hi.at(b.p), hi, n * 8, hipMemcpyHostToDevice, s->own);
+    if (e == hipSuccess) e = hipMemcpyAsync(d.lo.at(b.p), lo, n * 8, hipMemcpyHostToDevice, s->own);
+    if (e == hipSuccess) e = hipMemcpyAsync(d.ep.at(b.p), epoch, n * 8, hipMemcpyHostToDevice, s->own);
+    if (e == hipSuccess) e = hipMemcpyAsync(d.len.at(b.p), len, n * 4, hipMemcpyHostToDevice, s->own);
+    if (e == hipSuccess && items_stride) e = hipMemcpyAsync(d.items.at(b.p), items, n * items_stride * 8, hipMemcpyHostToDevice, s->own);
     if (e != hipSuccess) { (void)hipStreamSynchronize(s->own); return fail(SRN_EHIP, std::string(who) + ": " + hipGetErrorString(e)); }
-    rc = import_locked(s, (const uint64_t*)(b.p + d.hi), (const uint64_t*)(b.p + d.lo), (const uint64_t*)(b.p + d.ep), (const uint32_t*)(b.p + d.len),
-                       (const uint64_t*)(b.p + d.items), items_stride, n, s->own, who);
+    rc = import_locked(s, d.hi.at(b.p), d.lo.at(b.p), d.ep.at(b.p), d.len.at(b.p), d.items.at(b.p), items_stride, n, s->own, who);
     (void)hipStreamSynchronize(s->own);
     return rc;
 }

@@ -133,17 +133,18 @@ int dsess_top_items(srn_device_sessions* s, uint64_t now_secs, uint64_t since_se
     const size_t n1 = (size_t)s->n_slots + 1;
     size_t tmp_scan = 0;
     HIP_TRY(rocprim::exclusive_scan(nullptr, tmp_scan, (uint32_t*)nullptr, (uint64_t*)nullptr, (uint64_t)0, n1, rocprim::plus<uint64_t>(), st));
-    const size_t o_pos = align256(n1 * 4), o_tmp = o_pos + align256(n1 * 8);
-    StageBuf per_slot; if ((rc = per_slot.alloc(o_tmp + align256(tmp_scan), kWho, "the scratch"))) return rc;
+    Bump b1;
+    const auto cnt_at = b1.of<uint32_t>(n1); const auto pos_at = b1.of<uint64_t>(n1); const auto scan_at = b1.of<char>(tmp_scan);
+    StageBuf per_slot; if ((rc = per_slot.alloc(b1.bytes, kWho, "the scratch"))) return rc;
     TrendArgs a{};
     a.t = s->tab(); a.now = now; a.ttl = s->ttl; a.since = since_secs;
     a.lanes_shift = s->stride == 128 ? 3 : 4;
     a.n_el = 2 + (uint32_t)((s->items_cap + 1) / 2);
-    a.cnt = (uint32_t*)per_slot.p; a.pos = (const uint64_t*)(per_slot.p + o_pos);
+    a.cnt = cnt_at.at(per_slot.p); a.pos = pos_at.at(per_slot.p);
     const dim3 gw = grid_for(n1 << a.lanes_shift);
     trend_windows<false><<<gw, kTPB, 0, st>>>(a);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(rocprim::exclusive_scan(per_slot.p + o_tmp, tmp_scan, a.cnt, (uint64_t*)(per_slot.p + o_pos), (uint64_t)0, n1, rocprim::plus<uint64_t>(), st));
+    HIP_TRY(rocprim::exclusive_scan(scan_at.at(per_slot.p), tmp_scan, a.cnt, pos_at.at(per_slot.p), (uint64_t)0, n1, rocprim::plus<uint64_t>(), st));
     uint64_t total = 0;
     HIP_TRY(hipMemcpyAsync(&total, a.pos + s->n_slots, 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -156,19 +157,20 @@ int dsess_top_items(srn_device_sessions* s, uint64_t now_secs, uint64_t since_se
     HIP_TRY(rocprim::radix_sort_keys(nullptr, tmp_sort, ids, T, 0, 64, st));
     HIP_TRY(rocprim::run_length_encode(nullptr, tmp_rle, (const uint64_t*)nullptr, T, (uint64_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, st));
     const size_t tmp1 = std::max(tmp_sort, tmp_rle);
-    const size_t o_b = align256((size_t)T * 8), o_c = 2 * o_b, o_word = o_c + align256((size_t)T * 4), o_tmp1 = o_word + 256;
-    StageBuf per_id; if ((rc = per_id.alloc(o_tmp1 + align256(tmp1), kWho, "the scratch"))) return rc;
-    ids = rocprim::double_buffer<uint64_t>((uint64_t*)per_id.p, (uint64_t*)(per_id.p + o_b));
-    uint32_t* run_cnt = (uint32_t*)(per_id.p + o_c);
-    uint32_t* d_runs = (uint32_t*)(per_id.p + o_word);
-    uint64_t* d_ranked = (uint64_t*)(per_id.p + o_word + 8);
+    Bump b2;   // (words: the number of runs, then the number of ranked ids)
+    const auto idA = b2.of<uint64_t>(T), idB = b2.of<uint64_t>(T); const auto run_cnt_at = b2.of<uint32_t>(T); const auto words_at = b2.of<uint64_t>(2); const auto tmp1_at = b2.of<char>(tmp1);
+    StageBuf per_id; if ((rc = per_id.alloc(b2.bytes, kWho, "the scratch"))) return rc;
+    ids = rocprim::double_buffer<uint64_t>(idA.at(per_id.p), idB.at(per_id.p));
+    uint32_t* run_cnt = run_cnt_at.at(per_id.p);
+    uint64_t* d_ranked = words_at.at(per_id.p) + 1;
+    uint32_t* d_runs = (uint32_t*)(d_ranked - 1);
     a.ids = ids.current();
     trend_windows<true><<<grid_for((size_t)s->n_slots << a.lanes_shift), kTPB, 0, st>>>(a);
     HIP_TRY(hipGetLastError());
     size_t t1 = tmp1;
-    HIP_TRY(rocprim::radix_sort_keys(per_id.p + o_tmp1, t1, ids, T, 0, 64, st));
+    HIP_TRY(rocprim::radix_sort_keys(tmp1_at.at(per_id.p), t1, ids, T, 0, 64, st));
     t1 = tmp1;
-    HIP_TRY(rocprim::run_length_encode(per_id.p + o_tmp1, t1, (const uint64_t*)ids.current(), T, ids.alternate(), run_cnt, d_runs, st));
+    HIP_TRY(rocprim::run_length_encode(tmp1_at.at(per_id.p), t1, (const uint64_t*)ids.current(), T, ids.alternate(), run_cnt, d_runs, st));
     uint32_t R = 0;
     HIP_TRY(hipMemcpyAsync(&R, d_runs, 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -179,11 +181,12 @@ int dsess_top_items(srn_device_sessions* s, uint64_t now_secs, uint64_t since_se
     rocprim::double_buffer<uint64_t> vals(ids.alternate(), ids.current());
     size_t tmp2 = 0;
     HIP_TRY(rocprim::radix_sort_pairs_desc(nullptr, tmp2, keys, vals, R, 0, 32, st));
-    const size_t o_oid = align256((size_t)R * 4), o_ocnt = o_oid + align256(take * 8), o_tmp2 = o_ocnt + align256(take * 4);
-    StageBuf per_run; if ((rc = per_run.alloc(o_tmp2 + align256(tmp2), kWho, "the scratch"))) return rc;
-    keys = rocprim::double_buffer<uint32_t>(run_cnt, (uint32_t*)per_run.p);
-    HIP_TRY(rocprim::radix_sort_pairs_desc(per_run.p + o_tmp2, tmp2, keys, vals, R, 0, 32, st));
-    uint64_t* d_oid = (uint64_t*)(per_run.p + o_oid); uint32_t* d_ocnt = (uint32_t*)(per_run.p + o_ocnt);
+    Bump b3;
+    const auto keyB_at = b3.of<uint32_t>(R); const auto oid_at = b3.of<uint64_t>(take); const auto ocnt_at = b3.of<uint32_t>(take); const auto tmp2_at = b3.of<char>(tmp2);
+    StageBuf per_run; if ((rc = per_run.alloc(b3.bytes, kWho, "the scratch"))) return rc;
+    keys = rocprim::double_buffer<uint32_t>(run_cnt, keyB_at.at(per_run.p));
+    HIP_TRY(rocprim::radix_sort_pairs_desc(tmp2_at.at(per_run.p), tmp2, keys, vals, R, 0, 32, st));
+    uint64_t* d_oid = oid_at.at(per_run.p); uint32_t* d_ocnt = ocnt_at.at(per_run.p);
     trend_cut<<<grid_for(R), kTPB, 0, st>>>(keys.current(), vals.current(), R, min_count, (uint32_t)take, d_oid, d_ocnt, d_ranked);
     HIP_TRY(hipGetLastError());
     uint64_t ranked = 0;

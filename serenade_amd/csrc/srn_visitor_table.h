@@ -1,7 +1,9 @@
 // The table keyed by visitor underneath the device session store (srn_sessions_dev.hip) and the click feedback log (srn_feedback.hip), read beside them by
 // srn_trending.hip and srn_harvest.hip: the slot's head, the probe, count and rebuild kernels, the host-side core of an owner's handle and the capacity rule, once
 // (DESIGN.md 11).  An owner brings its slot, a payload functor, its batch kernels and where its second table comes from: the store keeps a pair and flips, the log
-// allocates one inside a sweep.  The batch-side pieces (run predicates, find_or_claim, the key sort) are srn_visitors.h's.
+// allocates one inside a sweep.  Also the host code's scratch idiom: regions of one buffer are declared on a Bump (srn_runtime.h) -- element type and count, once,
+// where they are named; the total falls out -- and grow_behind is the one rule by which such a buffer grows while the owner's last call may still read it.
+// The batch-side pieces (run predicates, find_or_claim, the key sort, the sorted front and the host stage of a visitor batch) are srn_visitors.h's.
 // No relocatable device code: every kernel here is a template or static, every function inline.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -49,6 +51,12 @@ struct StageBuf {   // a blocking call's own device memory (not DevBuf: that is 
         return SRN_OK;
     }
 };
+// The grow rule of a scratch buffer that the owner's calls share: the call recorded in `last` may still read it, so wait for that call before the buffer is freed and
+// reallocated.  A buffer that is large enough costs nothing
+inline int grow_behind(hipEvent_t last, char** buf, size_t* bytes, size_t need) {
+    if (need > *bytes) HIP_TRY(hipEventSynchronize(last));
+    return ensure(buf, bytes, need);
+}
 
 // ---- kernels ----
 // the slot that holds the key, or kNone (one lane, from the host: no claim is running)
@@ -112,6 +120,7 @@ struct VisitorTable {
     hipStream_t own = nullptr;                              // get / sweep / count and the host-pointer entry points
     uint64_t bound = 0, sweeps = 0, refused = 0;            // bound: upper bound of the occupied slots
     char* small = nullptr;                                  // err word | counters | one entry in / out
+    char* ws = nullptr; size_t ws_bytes = 0;                // per-batch scratch, grows with the largest n seen (grow_behind)
     Table tab() const { return Table{table, (uint32_t)(n_slots - 1), stride}; }
     uint32_t* err() const { return (uint32_t*)small; }
     unsigned long long* counters() const { return (unsigned long long*)(small + 64); }
@@ -147,6 +156,7 @@ inline void table_release(VisitorTable* c) {
     if (c->own) { (void)hipStreamSynchronize(c->own); (void)hipStreamDestroy(c->own); }
     if (c->table) (void)hipFree(c->table);
     if (c->small) (void)hipFree(c->small);
+    if (c->ws) (void)hipFree(c->ws);
 }
 
 // behind everything enqueued on the owner so far, on its own stream (mu held)

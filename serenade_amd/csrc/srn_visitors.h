@@ -1,10 +1,12 @@
 // What a batch against a table keyed by visitor needs (srn_sessions_dev.hip, srn_feedback.hip, srn_harvest.hip): the run predicates over a batch sorted by visitor,
-// the find-or-claim probe of a batch's run heads, and the stable sort of 128-bit keys that makes the runs.  The table and its capacity rule are
-// srn_visitor_table.h's.  No relocatable device code: every kernel here is a template, every function inline.
+// the find-or-claim probe of a batch's run heads, the stable sort of 128-bit keys that makes the runs, and what the batch calls of the store and the log open with:
+// the sorted front of a request descriptor (VisitorBatch, srn_internal.h), the timed / untimed dispatch and the host stage of the descriptor's arrays.  The table, its
+// capacity rule and the scratch's grow rule are srn_visitor_table.h's.  No relocatable device code: every kernel here is a template, every function inline.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #include <rocprim/rocprim.hpp>
 
@@ -105,6 +107,58 @@ struct KeySort {
     template <class W> int pass(W word, unsigned begin_bit = 0, unsigned end_bit = 64) {
         key_gather<<<grid(), kKeyTPB, 0, st>>>(word, idx[cur], (uint32_t)n, key[0]);
         return sort(begin_bit, end_bit);
+    }
+};
+
+// ---- the sorted front: a request descriptor -> the batch sorted by (no consent, key_hi, key_lo) ----
+// Two phases, around the owner's scratch growing.  plan() declares the front's regions on the owner's Bump: two key and two index buffers, rocPRIM's temporary storage
+// -- the sort's, or scan_bytes for the owner's scans where those need more -- and, for a timed batch, the times in sorted order.  run(base), once the buffer stands,
+// enqueues the stable LSD passes: key_lo, key_hi, then (where some request may not consent) the consent bit -- consenting requests first, each visitor's in request
+// order -- and the gather of the times through that order.  Then: order, when (null untimed) and tmp / tmp_bytes for the owner's scans.
+// (Templates only so that a file which sorts by KeySort alone instantiates none of the front's kernels.)
+struct SortedFront {
+    Bump::Region<uint64_t> key[2], when_at; Bump::Region<uint32_t> idx[2]; Bump::Region<char> tmp_at;
+    const uint32_t* order = nullptr; const uint64_t* when = nullptr; char* tmp = nullptr; size_t tmp_bytes = 0;
+    template <class Req> int plan(Bump& b, const Req& r, hipStream_t st, size_t scan_bytes = 0) {
+        const int rc = key_sort_tmp_bytes(r.n, st, &tmp_bytes); if (rc) return rc;
+        tmp_bytes = std::max(tmp_bytes, scan_bytes);
+        for (auto& k : key) k = b.of<uint64_t>(r.n);
+        for (auto& i : idx) i = b.of<uint32_t>(r.n);
+        tmp_at = b.of<char>(tmp_bytes);
+        if (r.times) when_at = b.of<uint64_t>(r.n);
+        return SRN_OK;
+    }
+    template <class Req> int run(char* base, const Req& r, hipStream_t st) {
+        tmp = tmp_at.at(base);
+        KeySort ks{{key[0].at(base), key[1].at(base)}, {idx[0].at(base), idx[1].at(base)}, tmp, tmp_bytes, r.n, st};
+        int rc;
+        if ((rc = ks.begin(r.key_lo)) || (rc = ks.pass(KeyWord{r.key_hi})) || (r.consent && (rc = ks.pass(KeyNoConsent{r.consent}, 0, 1)))) return rc;
+        order = ks.order();
+        if (r.times) {
+            key_gather<<<ks.grid(), kKeyTPB, 0, st>>>(KeyWord{r.times}, order, (uint32_t)r.n, when_at.at(base));
+            when = when_at.at(base);
+        }
+        return SRN_OK;
+    }
+};
+// f(std::true_type) for a timed batch, f(std::false_type) for an untimed one: a launch that differs in <kTimed> alone is written once, `decltype(timed)::value` its argument
+template <class F> inline auto by_timed(const VisitorBatch& r, F&& f) { if (r.times) return f(std::true_type{}); return f(std::false_type{}); }
+
+// ---- the host stage: a host-pointer call's request arrays on the device ----
+// plan() declares the five arrays' copies on the caller's Bump (consent always, times for a timed batch); upload(base, r, st) enqueues the copies of those that are
+// given and returns the descriptor of the device side.  The owner stages its own arrays beside them
+struct StagedBatch {
+    Bump::Region<uint64_t> hi, lo, item, times; Bump::Region<uint8_t> consent;
+    void plan(Bump& b, const VisitorBatch& r) {
+        hi = b.of<uint64_t>(r.n); lo = b.of<uint64_t>(r.n); item = b.of<uint64_t>(r.n); consent = b.of<uint8_t>(r.n);
+        if (r.times) times = b.of<uint64_t>(r.n);
+    }
+    int upload(char* base, const VisitorBatch& r, hipStream_t st, VisitorBatch* dev) const {
+        *dev = VisitorBatch{hi.at(base), lo.at(base), item.at(base), r.consent ? consent.at(base) : nullptr, times.at(base), r.n, r.now_secs};
+        const struct { void* to; const void* from; size_t bytes; } copies[] = {
+            {hi.at(base), r.key_hi, r.n * 8}, {lo.at(base), r.key_lo, r.n * 8}, {item.at(base), r.item, r.n * 8}, {consent.at(base), r.consent, r.n}, {times.at(base), r.times, r.n * 8}};
+        for (const auto& c : copies) if (c.from) HIP_TRY(hipMemcpyAsync(c.to, c.from, c.bytes, hipMemcpyHostToDevice, st));
+        return SRN_OK;
     }
 };
 

@@ -832,6 +832,58 @@ def _with_feedback_bootstrap(out, boot, ci):
     return out
 
 
+def _on_gpu(a):
+    return _is_torch(a) and a.device.type == "cuda"
+
+
+def _as_numpy(a):
+    return a.numpy() if _is_torch(a) else a
+
+
+def _visitor_batch(keys, item_ids, consent, times, device, who):
+    """The request side of a visitor batch, marshalled for the C ABI -> (hi, lo, items, consent, times, on_gpu, p, tail): uint64 / uint8 NumPy arrays (CPU tensors
+    count as arrays) or the contiguous tensors, consent and times None where not given; whether they are on the GPU; the function that makes a pointer argument of
+    an array (None stays None); and what follows a call's last argument: the current stream for tensors, nothing for arrays.
+    device(): the GPU the tensors must be on, asked only when there are tensors; who: that GPU's owner in a message."""
+    hi, lo = keys
+    n = len(item_ids)
+    given = [a for a in (hi, lo, item_ids, consent) if a is not None]
+    if any(len(a) != n for a in given):
+        raise ValueError("keys, item_ids and consent differ in length")
+    if times is not None and len(times) != n:
+        raise ValueError("times must have one entry per request")
+    if any(_on_gpu(a) for a in given):
+        import torch
+        dev = device()
+        if not all(_on_gpu(a) and a.device.index == dev for a in given):
+            raise ValueError("keys, item_ids and consent must all be tensors on %s's GPU (device %d), or none of them" % (who, dev))
+        if times is not None and not (_on_gpu(times) and times.device.index == dev):
+            raise ValueError("times must be a tensor on %s's GPU (device %d), like keys" % (who, dev))
+        i64 = (torch.int64, getattr(torch, "uint64", torch.int64))
+        if any(a.dtype not in i64 for a in (hi, lo, item_ids)):
+            raise TypeError("keys and item_ids must be 64-bit integer tensors")
+        if consent is not None and consent.dtype not in (torch.uint8, torch.bool):
+            raise TypeError("consent must be a uint8 or bool tensor")
+        if times is not None and times.dtype not in i64:
+            raise TypeError("times must be a 64-bit integer tensor")
+        arrs = [None if a is None else a.contiguous() for a in (hi, lo, item_ids, consent, times)]
+        return (*arrs, True, lambda a: None if a is None else C.c_void_p(a.data_ptr()), [C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)])
+    if times is not None and _on_gpu(times):
+        raise ValueError("times must be where keys are: an array or CPU tensor here")
+    hi, lo, it, tm = (None if a is None else capi.as_u64(_as_numpy(a)) for a in (hi, lo, item_ids, times))
+    con = None if consent is None else np.ascontiguousarray(_as_numpy(consent)).astype(np.uint8)
+    return hi, lo, it, con, tm, False, capi.ptr, []
+
+
+def _call_visitor_batch(entry, handles, batch, now, rest):
+    """The C ABI's form of `entry` for this batch: <entry>[_device][_at](*handles, key_hi, key_lo, item_ids, consent[, times], n, now, *rest[, stream]) -- _device for
+    tensors, _at and the times behind consent for a timed batch."""
+    hi, lo, it, con, tm, on_gpu, p, tail = batch
+    name = entry + ("_device" if on_gpu else "") + ("_at" if tm is not None else "")
+    args = list(handles) + [p(hi), p(lo), p(it), p(con)] + ([p(tm)] if tm is not None else []) + [len(it), int(now)] + list(rest) + tail
+    capi.check(getattr(capi.lib(), name)(*args))
+
+
 class ClickFeedback:
     """A click feedback log in the GPU's memory (srn_feedback_*): the last row served to every visitor, scored against the visitor's next click.  An object of its own
     beside the session store; recommend_batch(..., feedback=fb) feeds it.  bootstrap=B (and seed): enable_bootstrap(B, seed) at creation."""
@@ -878,49 +930,26 @@ class ClickFeedback:
         times (srn_feedback_observe*_at): request i's own clock in seconds, an array or tensor like the others -- the call gives what one call per
         request at times[i] gives, in request order, and `now` is only the capacity rule's sweep clock: pass a lower bound of times (0 reads the wall clock, which is
         wrong for a recorded log)."""
-        hi, lo = keys
         n = len(item_ids)
-        arrs = [hi, lo, item_ids, ids, counts] + ([consent] if consent is not None else []) + ([scores] if scores is not None else [])
-        if times is not None:
-            if len(times) != n:
-                raise ValueError("times must have one entry per request")
-            if (_is_torch(times) and times.device.type == "cuda") != (_is_torch(hi) and hi.device.type == "cuda") or (_is_torch(times) and times.device != hi.device):
-                raise ValueError("times must be where keys are: a tensor on the same GPU, or an array")
-        if any(len(a) != n for a in arrs) or ids.ndim != 2 or (scores is not None and tuple(scores.shape) != tuple(ids.shape)):
+        rows_in = [a for a in (ids, counts, scores) if a is not None]
+        if ids.ndim != 2 or len(ids) != n or len(counts) != n or (scores is not None and tuple(scores.shape) != tuple(ids.shape)):
             raise ValueError("keys, item_ids, consent and counts must have one entry per row of ids[n, how_many] (and scores its shape)")
-        how_many = int(ids.shape[1])
-        on_gpu = [_is_torch(a) and a.device.type == "cuda" for a in arrs]
-        if any(on_gpu):
+        batch = _visitor_batch(keys, item_ids, consent, times, lambda: self.device, "the log")
+        on_gpu, p = batch[5], batch[6]
+        if on_gpu != all(_on_gpu(a) and a.device.index == self.device for a in rows_in) or on_gpu != any(_on_gpu(a) for a in rows_in):
+            raise ValueError("keys, item_ids, consent, ids, counts and scores must all be tensors on the log's GPU (device %d), or none of them" % self.device)
+        if on_gpu:
             import torch
-            if not all(on_gpu) or any(a.device.index != self.device for a in arrs):
-                raise ValueError("keys, item_ids, consent, ids, counts and scores must all be tensors on the log's GPU (device %d), or none of them" % self.device)
-            if any(a.dtype not in (torch.int64, getattr(torch, "uint64", torch.int64)) for a in (hi, lo, item_ids, ids)) or \
-                    counts.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or (scores is not None and scores.dtype != torch.float64) or \
-                    (consent is not None and consent.dtype not in (torch.uint8, torch.bool)):
-                raise TypeError("keys, item_ids and ids must be 64-bit integer, counts 32-bit integer, scores float64 and consent uint8 or bool tensors")
-            if times is not None and times.dtype not in (torch.int64, getattr(torch, "uint64", torch.int64)):
-                raise TypeError("times must be a 64-bit integer tensor")
-            t = [a.contiguous() for a in arrs]
-            hi, lo, it, rows, cnt = t[:5]
-            con = t[5] if consent is not None else None
-            sc = t[-1] if scores is not None else None
-            tm = None if times is None else times.contiguous()
+            if ids.dtype not in (torch.int64, getattr(torch, "uint64", torch.int64)) or counts.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or \
+                    (scores is not None and scores.dtype != torch.float64):
+                raise TypeError("ids must be a 64-bit integer, counts a 32-bit integer and scores a float64 tensor")
+            rows, cnt, sc = (None if a is None else a.contiguous() for a in (ids, counts, scores))
             ranks = torch.zeros(n, dtype=torch.int32, device=torch.device("cuda", self.device))
-            entry, p, tail = "srn_feedback_observe_device", lambda a: None if a is None else C.c_void_p(a.data_ptr()), [C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)]
         else:
-            as_np = lambda a: a.numpy() if _is_torch(a) else a
-            hi, lo, it, rows = (capi.as_u64(as_np(a)) for a in (hi, lo, item_ids, ids))
-            cnt = capi.as_u32(as_np(counts))
-            con = None if consent is None else np.ascontiguousarray(as_np(consent)).astype(np.uint8)
-            sc = None if scores is None else np.ascontiguousarray(as_np(scores), dtype=np.float64)
-            tm = None if times is None else capi.as_u64(as_np(times))
+            rows, cnt = capi.as_u64(_as_numpy(ids)), capi.as_u32(_as_numpy(counts))
+            sc = None if scores is None else np.ascontiguousarray(_as_numpy(scores), dtype=np.float64)
             ranks = np.zeros(n, np.uint32)
-            entry, p, tail = "srn_feedback_observe", capi.ptr, []
-        args = [self._h, p(hi), p(lo), p(it), p(con), n, int(now), p(rows), p(sc), p(cnt), how_many, p(ranks)] + tail
-        if times is not None:   # the _at form takes the times behind consent
-            entry += "_at"
-            args.insert(5, p(tm))
-        capi.check(getattr(capi.lib(), entry)(*args))
+        _call_visitor_batch("srn_feedback_observe", [self._h], batch, now, [p(rows), p(sc), p(cnt), int(ids.shape[1]), p(ranks)])
         self.last_ranks = ranks
         return ranks
 
@@ -996,11 +1025,8 @@ def recommend_batch(index, store, keys, item_ids, consent=None, *, k, m, how_man
     it is int(times.min()) -- for tensors that is ONE SYNCHRONISATION with the device, so a caller who knows a lower bound passes it.  (A log whose smallest time is
     0 still reads the wall clock there, as everywhere in the ABI.)"""
     n = len(item_ids)
-    if times is not None:
-        if len(times) != n:
-            raise ValueError("times must have one entry per request")
-        if not int(now) and n:
-            now = int(times.min())
+    if times is not None and not int(now) and n:
+        now = int(times.min())
     if feedback is not None:
         if how_many > feedback.row_cap:
             raise ValueError("how_many %d above the feedback log's row_cap %d" % (how_many, feedback.row_cap))
@@ -1011,54 +1037,19 @@ def recommend_batch(index, store, keys, item_ids, consent=None, *, k, m, how_man
         if len(keys) != n:
             raise ValueError("keys, item_ids and consent differ in length")
         keys = session_keys(keys)
-    hi, lo = keys
-    arrs = [hi, lo, item_ids] + ([consent] if consent is not None else [])
-    if any(len(a) != n for a in arrs):
-        raise ValueError("keys, item_ids and consent differ in length")
     flags = (capi.FLAG_BUSINESS_LOGIC if enable_business_logic else 0) | (capi.FLAG_EXCLUDE_SEEN if exclude_seen else 0) | (capi.FLAG_FILL if fill else 0)
-    sh = store._h if store is not None else None
-    on_gpu = [_is_torch(a) and a.device.type == "cuda" for a in arrs]
-    if any(on_gpu):
+    batch = _visitor_batch(keys, item_ids, consent, times, lambda: index.info["device"], "the index")
+    hi, lo, it, con, tm, on_gpu, p, _ = batch
+    if on_gpu:
         import torch
-        device = index.info["device"]
-        if not all(on_gpu) or any(a.device.index != device for a in arrs):
-            raise ValueError("keys, item_ids and consent must all be tensors on the index's GPU (device %d), or none of them" % device)
-        hi, lo, it = (a.contiguous() for a in arrs[:3])
-        for a in (hi, lo, it):
-            if a.dtype not in (torch.int64, getattr(torch, "uint64", torch.int64)):
-                raise TypeError("keys and item_ids must be 64-bit integer tensors")
-        con = None
-        if consent is not None:
-            con = consent.contiguous()
-            if con.dtype not in (torch.uint8, torch.bool):
-                raise TypeError("consent must be a uint8 or bool tensor")
-        dev = torch.device("cuda", device)
+        dev = torch.device("cuda", index.info["device"])
         ids = torch.zeros((n, how_many), dtype=torch.int64, device=dev)
         sc = torch.zeros((n, how_many), dtype=torch.float64, device=dev)
         cnt = torch.zeros(n, dtype=torch.int32, device=dev)
-        tm = None
-        if times is not None:
-            if not (_is_torch(times) and times.device.type == "cuda" and times.device.index == device):
-                raise ValueError("times must be a tensor on the index's GPU (device %d), like keys" % device)
-            if times.dtype not in (torch.int64, getattr(torch, "uint64", torch.int64)):
-                raise TypeError("times must be a 64-bit integer tensor")
-            tm = times.contiguous()
-        entry, p, tail = "srn_recommend_batch_device", lambda a: None if a is None else C.c_void_p(a.data_ptr()), [C.c_void_p(torch.cuda.current_stream(device).cuda_stream)]
     else:
-        hi, lo, it = (capi.as_u64(a.numpy() if _is_torch(a) else a) for a in arrs[:3])
-        con = None if consent is None else np.ascontiguousarray(consent.numpy() if _is_torch(consent) else consent).astype(np.uint8)
         ids, sc, cnt = np.zeros((n, how_many), np.uint64), np.zeros((n, how_many), np.float64), np.zeros(n, np.uint32)
-        tm = None
-        if times is not None:
-            if _is_torch(times) and times.device.type == "cuda":
-                raise ValueError("times must be where keys are: an array or CPU tensor here")
-            tm = capi.as_u64(times.numpy() if _is_torch(times) else times)
-        entry, p, tail = "srn_recommend_batch", capi.ptr, []
-    args = [index._h, sh, p(hi), p(lo), p(it), p(con), n, int(now), int(max_items_in_session), int(k), int(m), int(how_many), flags, p(ids), p(sc), p(cnt)] + tail
-    if times is not None:   # the _at form takes the times behind consent
-        entry += "_at"
-        args.insert(6, p(tm))
-    capi.check(getattr(capi.lib(), entry)(*args))
+    _call_visitor_batch("srn_recommend_batch", [index._h, store._h if store is not None else None], batch, now,
+                        [int(max_items_in_session), int(k), int(m), int(how_many), flags, p(ids), p(sc), p(cnt)])
     if feedback is not None and n:
         _observe_served(feedback, (hi, lo), it, con, ids, cnt, sc, now, tm)
     return (ids, cnt, sc) if scores else (ids, cnt)

@@ -174,6 +174,49 @@ def test_cut_invariance_and_entry_points(small):
         store.close()
 
 
+@pytest.mark.parametrize("timed", [False, True])
+def test_the_scratch_grows_behind_a_call_that_may_still_run(small, timed):
+    """Two device-pointer calls on one stream with nothing between them: one request, then 257 -- two blocks of 256 lanes and the n + 1 lane -- so the store's scratch is
+    freed and reallocated while the first call may still read it: the grow rule waits for that call.  The second call repeats visitors, every seventh request does
+    not consent and, timed, one gap lies above the idle limit.  Rows, counts and the store's export are the bytes of the same two calls on a fresh store with a
+    synchronisation in between."""
+    import torch
+    from serenade_amd.serving import DeviceSessionStore, recommend_batch
+    gix, oix, ids = small
+    dev = torch.device("cuda", gix.info["device"])
+    n, now, max_items, idle = 258, 90_000, 3, 1200
+    vis = [((7 + v) << 64) | (11 * v + 1) for v in range(5)]
+    hi, lo = split_keys([vis[j % 5] for j in range(n)])
+    items = np.array([int(ids[(3 * j) % 17]) for j in range(n)], np.uint64)
+    consent = (np.arange(n) % 7 != 3).astype(np.uint8)
+    times = now + np.arange(n, dtype=np.uint64)
+    times[200:] += np.uint64(idle + 1)
+    assert consent[0] and consent[200] and not consent.all()
+    hi, lo, items, times = (torch.from_numpy(a.view(np.int64)).to(dev) for a in (hi, lo, items, times))   # every copy before the first call: none between the two
+    consent = torch.from_numpy(consent).to(dev)
+    stream = torch.cuda.current_stream(dev)
+    results = []
+    for synchronise in (False, True):
+        store = DeviceSessionStore(gix, capacity=1024, items_cap=4, idle_secs=idle)   # (room for both calls by the host's bound: the capacity rule waits for nothing)
+        stream.synchronize()
+        rows = []
+        for sl in (slice(0, 1), slice(1, n)):
+            rows += recommend_batch(gix, store, (hi[sl], lo[sl]), items[sl], consent[sl], k=K, m=M, how_many=HOW_MANY, max_items_in_session=max_items, now=now,
+                                    scores=True, times=times[sl] if timed else None)
+            if synchronise:
+                stream.synchronize()
+        stream.synchronize()
+        at = int(times[-1]) if timed else now
+        (xhi, xlo), epoch, length, xitems = store.export(now=at)
+        results.append([to_numpy(r) for r in rows] + [xhi, xlo, epoch, length, xitems])
+        store.close()
+    assert results[0][4].shape == (n - 1,) and len(results[0][-2]) == len(vis)       # counts of the second call; one stored session per visitor
+    if timed:
+        assert (results[0][-3] >= int(times[200])).all()                              # ... each of them stored behind the gap
+    for a, b in zip(*results):
+        assert a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
+
+
 @pytest.mark.timeout(300)
 def test_hot_key(small):
     """65 536 requests on ONE key in one call (items from 5 ids: repeats and appends both occur), interleaved with 1 000 other keys: every row against the model."""

@@ -204,6 +204,45 @@ def test_timed_call_on_eight_lane_groups(device):
     fb.close()
 
 
+@pytest.mark.parametrize("timed", [False, True])
+def test_the_scratch_grows_behind_a_call_that_may_still_run(timed):
+    """Two device-pointer calls on one stream with nothing between them: one request, then 257 -- two blocks of 256 lanes and one more -- so the log's scratch is freed
+    and reallocated while the first call may still read it: the grow rule waits for that call.  The second call repeats visitors, every seventh request does not
+    consent and, timed, one gap lies above idle_secs.  Ranks, counters, histograms and entries are those of the same two calls on a fresh log with a synchronisation
+    in between."""
+    import torch
+    n, how_many = 258, 8
+    vis = [((7 + v) << 64) | (11 * v + 1) for v in range(5)]
+    consent = (np.arange(n) % 7 != 3).astype(np.uint8)
+    s = make_stream(4109, [vis[j % 5] for j in range(n)], how_many, consent)
+    times = NOW + np.arange(n, dtype=np.uint64)
+    times[200:] += np.uint64(IDLE + 1)
+    assert consent[195] and consent[200] and consent[0]
+    dev = torch.device("cuda", 0)
+    t = {name: torch.from_numpy(np.ascontiguousarray(x).view(np.int64 if x.dtype == np.uint64 else np.int32 if x.dtype == np.uint32 else x.dtype)).to(dev)
+         for name, x in dict(s, times=times).items() if isinstance(x, np.ndarray)}           # every copy before the first call: none between the two
+    stream = torch.cuda.current_stream(dev)
+    results = []
+    for synchronise in (False, True):
+        fb = ClickFeedback(0, capacity=1024, row_cap=how_many, ttl_secs=TTL, idle_secs=IDLE)   # (room for both calls by the host's bound: the capacity rule waits for nothing)
+        stream.synchronize()
+        ranks = []
+        for sl in (slice(0, 1), slice(1, n)):
+            ranks.append(fb.observe((t["hi"][sl], t["lo"][sl]), t["items"][sl], t["consent"][sl], t["ids"][sl], t["counts"][sl], t["sc"][sl], now=NOW,
+                                    times=t["times"][sl] if timed else None))
+            if synchronise:
+                stream.synchronize()
+        stream.synchronize()
+        st = fb.stats()
+        results.append(([r.cpu().numpy() for r in ranks], [st[c] for c in COUNTERS], fb.histogram(), [fb.get(k) for k in vis]))
+        fb.close()
+    (ranks, counters, hist, entries), (ranks_s, counters_s, hist_s, entries_s) = results
+    assert counters[COUNTERS.index("observed")] > 100 and counters[COUNTERS.index("no_consent")] > 0 and (counters[COUNTERS.index("idle_expired")] > 0) == timed
+    assert all(a.tobytes() == b.tobytes() for a, b in zip(ranks, ranks_s)) and counters == counters_s
+    assert all(np.array_equal(a, b) for a, b in zip(hist, hist_s))
+    assert all(a is not None and np.array_equal(a[0], b[0]) and a[1:] == b[1:] for a, b in zip(entries, entries_s))
+
+
 def test_rows_narrower_than_the_log():
     keys, _ = key_pattern("zipf", 600, 5)
     s = make_stream(5, keys, 5)
