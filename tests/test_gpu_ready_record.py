@@ -12,28 +12,25 @@ The batch: 4 096 sessions of the `tiny` data set over an index built with m = 2 
 Sessions of 1..8 items; an item repeated (the older occurrence owns no run); unknown ids at every position, the most recent included; only unknown ids (n = 0); 5+ distinct
 known items (nr > 4); 8 items with numerators summing above 15; 9 and 12 items (L > 8: the block is zero); lists cut by x_lo to kept = 1 and to the nearest the index
 has to 512 / 513 / 1 024 / 1 025 (found by a first pass over pairs of popular items: the test prints what it reached and requires a kept count on either side of 512
-and of 1 024 -- this index reaches 1, 510, 514, 1 021 and 1 029; the exact edges 512 / 513 / 1 024 no pair of its items has); the hottest items four at a time, and four at a time the most popular items with FEWER than m sessions (they set no cut: the largest n).
+and of 1 024 -- this index reaches 1, 510, 514, 1 021 and 1 029; the exact edges 512 / 513 / 1 024 no pair of its items has: tests/test_gpu_edge_cases.py places every
+multiple of 512 up to 2 560, one below and one above, on a designed index, tests/edge_cases.py); the hottest items four at a time, and four at a time the most popular items with FEWER than m sessions (they set no cut: the largest n).
 Which side of 2 n + 8 <= MW (12 032 words) the index reaches: both -- the second kind of four-item sessions stages up to 7 014 entries and goes to the BIG form; the
 test requires both sides among the queries that pass every other term.  (The latency path's one-workgroup launches write a zero block and decode the items themselves,
 srn_fast.hip: a zero block is always valid -- lean_ok clear -- and the existing latency tests cover that form.)
 """
-import ctypes as C
 import os
 
 import numpy as np
 import pytest
 
 from helpers import flatten
+from record_cases import K_NONE, MW_LEAN, READY0, READY_WORDS, legacy, prep_records, ready_from_legacy, routing   # (the record's layout and the ONE statement of the routing: shared with tests/test_gpu_edge_cases.py)
 
 pytestmark = pytest.mark.gpu
 
 SCORE_RTOL = 1e-12
 KNOBS = ("SRN_GRID_MULT", "SRN_ORDER_MIN", "SRN_NO_FAST", "SRN_FAST_RUNS")
 NQ, MAX_LEN, N, M = 4096, 12, 21, 2048
-HEAD_WORDS, READY0, READY_WORDS, ITEM_WORDS = 34, 18, 16, 6
-MW_LEAN = 12032                  # F_LEAN_MW: words of the 53 KB layout's merge room
-MW_BIG = 19072                   # ... and of the BIG form's 80 KB layout
-K_NONE = 0xFFFFFFFF
 
 
 @pytest.fixture
@@ -51,77 +48,6 @@ def knobs():
     for name in KNOBS:
         os.environ.pop(name, None)
     capi.reload_knobs()
-
-
-def prep_records(gix, qs, m=M, max_len=MAX_LEN):
-    """The prep kernel's records of a batch as u32 [nq, stride / 4]."""
-    from serenade_amd import capi
-    flat, off = flatten(qs)
-    flat = np.concatenate([flat, np.zeros(1, np.uint64)])
-    stride = C.c_size_t(0)
-    out = np.zeros(len(qs) * (HEAD_WORDS + ITEM_WORDS * max_len), np.uint32)
-    capi.check(capi.lib().srn_debug_prep_records(gix._h, C.c_void_p(flat.ctypes.data), C.c_void_p(off.ctypes.data), len(qs), m, max_len, C.c_void_p(out.ctypes.data), out.nbytes, C.byref(stride)))
-    assert stride.value == 4 * (HEAD_WORDS + ITEM_WORDS * max_len) == 136 + 24 * max_len
-    return out.reshape(len(qs), -1)
-
-
-def legacy(rec, max_len=MAX_LEN):
-    """The record's fields from before the block: head words and the items' (idx, kept, base)."""
-    h = rec[:, :READY0].astype(np.int64)
-    it = rec[:, HEAD_WORDS:].reshape(len(rec), max_len, ITEM_WORDS)
-    return dict(rmax=h[:, 1], xlo=h[:, 2], sumw=h[:, 3], L=h[:, 6], n=h[:, 7], unsafe=h[:, 17], idx=it[:, :, 0], kept=it[:, :, 3].astype(np.int64), blo=it[:, :, 4], bhi=it[:, :, 5])
-
-
-def ready_from_legacy(rec, wide, max_len=MAX_LEN):
-    """The 16 words as srn_kernels.h defines them, from the legacy fields alone."""
-    f = legacy(rec, max_len)
-    out = np.zeros((len(rec), READY_WORDS), np.uint32)
-    for q in range(len(rec)):
-        L = int(f["L"][q])
-        if not (1 <= L <= 8 and L <= max_len):
-            continue
-        runs = [p for p in range(L) if f["kept"][q, p] > 0]
-        nr = len(runs)
-        if nr > 4:
-            continue
-        rel = wide and nr > 3
-        lean_ok = (f["unsafe"][q] == 0 and f["sumw"][q] <= 15 and 2 * f["n"][q] + 8 <= MW_LEAN and (not rel or f["rmax"][q] - f["xlo"][q] < (1 << 28)))
-        out[q, 0] = int(lean_ok) | (nr << 8) | (int(rel) << 16)
-        out[q, 2] = f["idx"][q, 0]
-        for r, p in enumerate(runs):
-            kept = int(f["kept"][q, p])
-            out[q, 1] |= sum(1 << (5 * r + j) for j in range(5) if j * 512 < kept)
-            out[q, 3] |= p << (8 * r)
-            out[q, 4 + r] = kept
-            out[q, 8 + 2 * r], out[q, 9 + 2 * r] = f["blo"][q, p], f["bhi"][q, p]
-    return out
-
-
-def routing(rec, max_len=MAX_LEN, wide=False):
-    """Where the launch sequence sends each query, from the legacy fields and the kernels' predicates (srn_fast.hip): 'lean', 'big', 'mid', 'long', 'general'; the MID
-    form's own hand-overs ('mid>big', 'mid>general') included."""
-    f = legacy(rec, max_len)
-    out = []
-    for q in range(len(rec)):
-        L, n, sumw, span = int(f["L"][q]), int(f["n"][q]), int(f["sumw"][q]), int(f["rmax"][q] - f["xlo"][q])
-        ok_len = 1 <= L <= max_len
-        nr = int((f["kept"][q, :L] > 0).sum()) if ok_len else 0
-        rel = wide and nr > 3
-        if f["unsafe"][q]:
-            out.append("general")
-        elif ok_len and L <= 8 and sumw <= 15 and nr <= 4 and 2 * n + 8 <= MW_LEAN and (not rel or span < (1 << 28)):
-            out.append("lean")
-        elif ok_len and L <= 8 and sumw <= 15 and nr <= 4 and span < (1 << 28) and 2 * n + 8 + 256 <= MW_BIG:
-            out.append("big")
-        elif ok_len and L <= 10:
-            nb = max(nr, 4)
-            shape = sumw <= 63 and nr <= 10 and span < (1 << (32 - nb))
-            out.append("mid" if shape and 2 * n + 8 + 256 <= MW_LEAN else "mid>big" if shape and 2 * n + 8 + 256 <= MW_BIG else "mid>general")
-        elif ok_len and 10 < L <= 20:
-            out.append("long")
-        else:
-            out.append("general")
-    return out
 
 
 def _batch(pop, counts, edges, rng, nq=NQ):
@@ -174,7 +100,7 @@ def _batch(pop, counts, edges, rng, nq=NQ):
 def _edge_sessions(gix, pop):
     """First pass: sessions [b, a] of a popular item b under the cut of a hotter item a (the most recent), and what the prep kernel keeps of b's list."""
     cand = [[int(pop[b]), int(pop[a])] for a in range(12) for b in range(64) if a != b] + [[int(pop[b]), int(pop[a])] for a in range(3) for b in range(64, 1024)]
-    f = legacy(prep_records(gix, cand))
+    f = legacy(prep_records(gix, cand, M, MAX_LEN), MAX_LEN)
     kept_b = f["kept"][:, 1]
     found = {}
     for name, target, below in (("1", 1, True), ("<=512", 512, True), (">=513", 513, False), ("<=1024", 1024, True), (">=1025", 1025, False)):
@@ -255,12 +181,12 @@ def world():
 @pytest.mark.parametrize("wide", [False, True])
 def test_every_word_of_every_query(world, knobs, wide):
     knobs(SRN_FAST_RUNS=3 if wide else None)
-    rec = prep_records(world["gix"], world["qs"])
-    got, want = rec[:, READY0:READY0 + READY_WORDS], ready_from_legacy(rec, wide)
+    rec = prep_records(world["gix"], world["qs"], M, MAX_LEN)
+    got, want = rec[:, READY0:READY0 + READY_WORDS], ready_from_legacy(rec, wide, MAX_LEN)
     bad = np.flatnonzero((got != want).any(axis=1))
     assert len(bad) == 0, "%d records differ, the first: query %d %s\n got  %s\n want %s" % (len(bad), bad[0], world["qs"][bad[0]], got[bad[0]], want[bad[0]])
     # what the batch holds (conditions, so that the comparison above is about something)
-    f = legacy(rec)
+    f = legacy(rec, MAX_LEN)
     L, nr = f["L"], (f["kept"][:, :8] > 0).sum(axis=1)
     ok = got[:, 0] & 1
     assert set(range(1, 9)) <= set(L[ok == 1].tolist()) and {9, 12} <= set(L.tolist())
@@ -283,14 +209,14 @@ def test_rows_and_routing(world, knobs, how):
     gix, dv, qs = world["gix"], world["dv"], world["qs"]
     wide = how == "wide"
     knobs(SRN_GRID_MULT=64 if how == "single" else 1, SRN_ORDER_MIN=1 if how == "ordered" else None, SRN_FAST_RUNS=3 if wide else None)
-    rec = prep_records(gix, qs)
+    rec = prep_records(gix, qs, M, MAX_LEN)
     got = dv.call(world["k"], M)
     nq, general, _glob = gix.last_path_counts()
     mid, big, merged = gix.last_mid_count(), gix.last_big_count(), gix.last_dedup_count()
     _vs_oracle(got, world["ref"], how)
     _same_bytes(got, world["slow"], "%s against SRN_NO_FAST=1" % how)
     # the routing is the predicate's: over the queries that were served themselves (a copy of an earlier query of the call is not, where the call merges them)
-    route = routing(rec, wide=wide)
+    route = routing(rec, MAX_LEN, wide)
     seen, served = set(), []
     for q, s in enumerate(qs):
         if merged and tuple(s) in seen:
