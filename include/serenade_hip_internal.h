@@ -32,6 +32,10 @@ int srn_debug_last_dedup_count(const srn_index_t* idx, uint32_t* out_merged);
 /* the persistent latency path: 100 MHz ticks of the last session the lean form's first resident workgroup served -- [0] waited for the doorbell, [1] doorbell -> prep record
  * written, [2] doorbell -> answer posted */
 int srn_debug_serve_stamps(const srn_index_t* idx, uint32_t* out4);
+/* Test aid (tests/test_gpu_persistent_edges.py): per resident workgroup of one form of the persistent latency path (form 0: sessions of <= 4 items, form 1: of 5..10), how
+ * many sessions it has answered itself (status 0) since srn_index_serve_start -- counted on the host, where srn_index_serve_stats' `served` is.  *out_n = the form's
+ * workgroups (out_n may be NULL); cap < that: SRN_ERANGE, with *out_n set.  SRN_ESTATE: nothing resident, or no such form. */
+int srn_debug_serve_lane_counts(const srn_index_t* idx, unsigned form, uint64_t* out_served, size_t cap, size_t* out_n);
 /* 32-bit words per query of the streaming back end's exchange record at this (k, m) -- 0: none (knobs, shape); the gather form ships k + 1 words */
 uint32_t srn_debug_shard_nb_positions_stride(size_t k, size_t m);
 /* ... and how many of those MID listed for its BIG form (80 KB of LDS: merged lists beyond the 53 KB layout's buffers). */

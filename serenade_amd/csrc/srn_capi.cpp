@@ -685,6 +685,10 @@ int srn_debug_serve_stamps(const srn_index_t* idx, uint32_t* out4) {
     if (!idx || !idx->dev || !out4) return fail(SRN_EINVAL, "null argument");
     return device_serve_last_stamps(idx->dev, out4);
 }
+int srn_debug_serve_lane_counts(const srn_index_t* idx, unsigned form, uint64_t* out_served, size_t cap, size_t* out_n) {
+    if (!idx || !idx->dev || (!out_served && cap)) return fail(SRN_EINVAL, "null argument");
+    return device_serve_lane_counts(idx->dev, form, out_served, cap, out_n);
+}
 int srn_debug_last_mid_count(const srn_index_t* idx, uint32_t* out_listed) {
     if (!idx || !idx->dev) return fail(SRN_ENODEV, "index has no device attached");
     return guarded([&]() -> int { return device_last_mid_count(idx->dev, out_listed); });

@@ -209,6 +209,7 @@ struct ServeForm {   // one resident launch: N workgroups of the lean form (sess
     char *prep = nullptr, *fin = nullptr, *big = nullptr; uint32_t *slow_list = nullptr, *slow_cnt = nullptr, *counts = nullptr;
     LaunchParams p{}; FastParams fp{};
     std::unique_ptr<std::atomic<int>[]> busy; std::vector<uint32_t> seq;   // per workgroup: taken by a caller; the last number posted
+    std::unique_ptr<std::atomic<uint64_t>[]> lane_served;   // per workgroup: sessions it answered itself (test aid: srn_debug_serve_lane_counts)
     std::mutex mu; bool running = false;   // (mu: starting / parking the launch)
 };
 struct ServeState {
@@ -298,6 +299,7 @@ int device_serve_start(DeviceState* d, const FlatIndex& ix, uint32_t k, uint32_t
     for (int form = 0; form < (s->max_items > 4 ? 2 : 1); ++form) {
         ServeForm* f = new ServeForm(); f->d = d; f->mid = form == 1; f->n = lanes; s->forms.push_back(f);
         f->busy.reset(new std::atomic<int>[lanes]); for (uint32_t i = 0; i < lanes; ++i) f->busy[i].store(0); f->seq.assign(lanes, 0u);
+        f->lane_served.reset(new std::atomic<uint64_t>[lanes]); for (uint32_t i = 0; i < lanes; ++i) f->lane_served[i].store(0);
         { std::lock_guard<std::mutex> lk(g_serve_mu); g_serve_forms.push_back(f); }
         LaunchParams& p = f->p;
         p.nq = lanes; p.k = k; p.m = m; p.how_many = how_many; p.flags = flags; p.max_len = f->mid ? F_MID_LMAX : 8u;
@@ -334,6 +336,15 @@ int device_serve_stats(DeviceState* d, uint64_t* served, uint64_t* not_served, u
     if (served) *served = s ? s->served.load() : 0; if (not_served) *not_served = s ? s->not_served.load() : 0; if (launches) *launches = s ? s->launches.load() : 0;
     uint32_t n = 0; if (s) for (ServeForm* f : s->forms) n += f->n;
     if (lanes) *lanes = n;
+    return SRN_OK;
+}
+int device_serve_lane_counts(DeviceState* d, uint32_t form, uint64_t* out_served, size_t cap, size_t* out_n) {   // (test aid) per resident workgroup of one form: sessions it answered itself
+    ServeState* s = d->serve.load();
+    if (!s || form >= s->forms.size()) return fail(SRN_ESTATE, "no such resident form");
+    ServeForm* f = s->forms[form];
+    if (out_n) *out_n = f->n;
+    if (cap < f->n) return fail(SRN_ERANGE, "one counter per resident workgroup of the form");
+    for (uint32_t i = 0; i < f->n; ++i) out_served[i] = f->lane_served[i].load(std::memory_order_relaxed);
     return SRN_OK;
 }
 int device_serve_last_stamps(DeviceState* d, uint32_t* out4) {   // (measurement aid) 100 MHz ticks of the lean form's first workgroup's last session: waited | record written | answered
@@ -385,6 +396,7 @@ int device_serve_predict(DeviceState* d, const uint64_t* items, uint32_t len, ui
         }
         lane_unlock(f, li);
         (ret == 0 ? s->served : s->not_served).fetch_add(1);
+        if (ret == 0) f->lane_served[li].fetch_add(1, std::memory_order_relaxed);
         return ret;
     }
     s->not_served.fetch_add(1);

@@ -177,6 +177,13 @@ class VMISIndex:
         capi.check(capi.lib().srn_index_serve_stats(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(n)))
         return a.value, b.value, c.value, n.value
 
+    def serve_lane_counts(self, form):
+        """srn_debug_serve_lane_counts: sessions each resident workgroup of `form` (0: <= 4 items, 1: 5..10) has answered itself; test aid."""
+        n = C.c_size_t()
+        out = np.zeros(256, np.uint64)
+        capi.check(capi.lib().srn_debug_serve_lane_counts(self._h, int(form), capi.ptr(out), len(out), C.byref(n)))
+        return [int(x) for x in out[:n.value]]
+
     def enable_result_cache(self, rows, max_len, k, m, how_many, business_logic=False):
         """srn_index_result_cache_enable: keep served rows of sequences of 1..max_len (<= 8) items in a device table of `rows` entries; batch calls with exactly these
         parameters on the fast path then answer repeated sequences from it (the same bytes), every other call bypasses it."""

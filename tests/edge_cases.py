@@ -501,3 +501,145 @@ def route_counts(tied, shape):
     for r in restate(tied, shape):
         out[r["route"]] = out.get(r["route"], 0) + 1
     return out
+
+
+# ---- full-width ids (test_gpu_persistent_edges.py, test_edge_cases_host.py) -------------------------------------------------------------------------------------------
+# The designed ids stay below 2^43 (ID0 + ID_STEP * number, UNKNOWN0 + j).  wide_ids is a strictly increasing injection into 64 bits: the id itself in bits 20..62 and 20
+# mixed bits below it, so that both 32-bit halves are non-zero, the halves differ, and hi ^ lo differs between neighbours (ids 7 apart share their high half: the low half
+# alone tells them apart, and a lost or swapped half names another item or none).  Strictly increasing, so the canonical order (score descending, id ascending) of the
+# mapped index is the map of the narrow index's: the expected rows are the oracle's with the map applied to the ids, the scores the same bits (asserted on the CPU).
+WIDE_SHIFT = 20
+
+
+def _mix64(x):
+    """The splitmix64 finaliser on a uint64 array."""
+    x = x.astype(np.uint64).copy()
+    with np.errstate(over="ignore"):
+        x ^= x >> np.uint64(30)
+        x *= np.uint64(0xBF58476D1CE4E5B9)
+        x ^= x >> np.uint64(27)
+        x *= np.uint64(0x94D049BB133111EB)
+        x ^= x >> np.uint64(31)
+    return x
+
+
+def wide_ids(ids):
+    """u64 array of the mapped ids (0 stays 0: the unused tail of a row)."""
+    a = np.asarray(ids, dtype=np.uint64)
+    assert a.size == 0 or int(a.max()) < (1 << (63 - WIDE_SHIFT))
+    out = (a << np.uint64(WIDE_SHIFT)) | (_mix64(a) & np.uint64((1 << WIDE_SHIFT) - 1))
+    return np.where(a == 0, np.uint64(0), out)
+
+
+def designed_ids(ix):
+    """Every id the index or a query of the batch holds, ascending."""
+    return np.unique(np.concatenate([ix.items, np.array([x for q in ix.queries for x in q], np.uint64), serve_extra_ids()]))
+
+
+# ---- the persistent latency path in the restatement's terms (srn_latency.hip: device_serve_predict; srn_fast.hip: the serving loop of vmis_fast_kernel<TINY>) ----------
+# A session of 1..4 items goes to the resident lean form, one of 5..max_items (<= 10) to the resident form for 5..10 items; neither has a tier behind it.  The workgroup
+# answers status 0 iff a finishing path wrote the row's count over its sentinel:
+#   (1) the form's own `fits`: lean   L <= 4, sumw <= 15, nr <= 4, 2 n + 8 <= 12 032
+#                              5..10  sumw <= 63, nr <= 10, 2 n + 8 + 256 <= 12 032        (what the launch sequence would list for BIG or hand over is NOT served),
+#   (2) no known item (n = 0): the count 0 is written at once -- served;
+#   (3) the back end keeps the query (backend_fits: asserted by the census for every fast route), and wave 0 finishes the row from its registers: M <= 63 entries, or
+#       M > 63 and, of the M keys' top 32 bits, at most 64 lie at or above ONE STEP BELOW the how_many-th largest (srn_fast.hip: `if (S <= 64u && S >= p.how_many)`).
+# M itself depends on the sample's thresholds, but every entry set the back end can arrive at holds ALL valid items down to one step below the how_many-th best (that is
+# what its thresholds guarantee), so with  T = |{valid items: hi32(idf_eff * acc) >= (how_many-th largest hi32) - 1}|  (all valid items where there are fewer than
+# how_many): M <= 63 implies T <= 63, and M > 63 gives S = T.  Served iff T <= 64.  Valid: acc > 0, not the current item, and under the business rules what they let
+# through.  A row of E <= 63 scored items has T <= 63 whatever the scores are; rows of 64 and of 65 items are served or not by their ties at the cut (tight_set).
+SERVE_MAX_ENTRIES = 64
+
+
+def tight_set(ix, r, how_many, attrs=None):
+    """T of the comment above, from the restatement's accumulators and idf = ln(interactions / sessions that hold the item), the index's own formula in the same libm."""
+    import math
+    acc, scored = r["acc"], r["scored"]
+    cnt = np.diff(ix.l_off)[np.searchsorted(ix.l_items, scored)]
+    total = float(len(ix.row_num))
+    idf = np.array([math.log(total / float(c)) for c in cnt], np.float64)
+    idf = np.where(idf > 0.0, idf, 1.0)
+    valid = (acc > 0) & (scored != r["cur"])
+    if attrs is not None:
+        fl = np.array([attrs.get(int(x), 0xFF) for x in scored], np.int64)
+        cur_fl = attrs.get(r["cur"], 0xFF)
+        cur_adult = cur_fl != 0xFF and bool(cur_fl & 1)
+        valid &= (fl != 0xFF) & ((fl & 2) != 0) & (((fl & 1) == 0) | cur_adult)
+    hi = ((idf * acc.astype(np.float64)).view(np.uint64) >> np.uint64(32)).astype(np.int64)[valid]
+    if len(hi) < how_many:
+        return len(hi)
+    cut = int(np.sort(hi)[::-1][how_many - 1]) - 1
+    return int((hi >= cut).sum())
+
+
+def resident_route(r, max_items=10):
+    """What the resident form that gets the session does with it at the front end: 'none' (not posted: length outside 1..max_items), 'lean' / 'mid' (its own), 'big' (the
+    lean form's oversized query: the launch sequence's BIG list, nobody's here), 'general' (every other hand-over)."""
+    L = r["L"]
+    if not 1 <= L <= max_items:
+        return "none"
+    span = r["rmax"] - r["xlo"]
+    if L <= 4:
+        route = route_of(L, r["n"], r["sumw"], span, r["nr"], 0, 8)
+        return route if route in ("lean", "big") else "general"
+    nb = max(r["nr"], 4)
+    return "mid" if r["sumw"] <= 63 and r["nr"] <= 10 and span < (1 << (32 - nb)) and 2 * r["n"] + 8 + 256 <= MW_LEAN else "general"
+
+
+def resident_kind(ix, r, how_many=21, attrs=None, max_items=10):
+    """'served' or why not: 'none', 'big', 'general', 'over64' (T > 64: the row is left to a finish kernel nobody launches)."""
+    route = resident_route(r, max_items)
+    if route not in ("lean", "mid"):
+        return route
+    return "served" if r["n"] == 0 or tight_set(ix, r, how_many, attrs) <= SERVE_MAX_ENTRIES else "over64"
+
+
+def serve_extra_ids():
+    return np.array([UNKNOWN0 + 2 * 10**6 + j for j in range(3)], np.uint64)
+
+
+def serve_extras():
+    """Sessions outside the batch that the persistent tests post as well: no known item at all -- the row of count 0, which the workgroup writes at once (both forms)."""
+    u = [int(x) for x in serve_extra_ids()]
+    return [("no known item, L=1", [u[0]]), ("no known item, L=2", [u[1], u[0]]), ("no known item, L=6", [u[0], u[1], u[2], u[0], u[1], u[2]])]
+
+
+@functools.lru_cache(maxsize=None)
+def serve_calls(tied, shape, max_items=10):
+    """The single calls of the persistent tests at one shape, in cell order: every query of the batch of at most max_items items and no q_shift (the selection of
+    test_gpu_edge_cases.py (d)), then serve_extras.  -> [dict(name, q, qi (None for an extra), r = the restatement)]."""
+    ix = build(tied)
+    k, m = SHAPES[shape]
+    R = restate(tied, shape)
+    out = [dict(name=ix.cells[ix.q_cell[qi]]["name"], q=list(q), qi=qi, r=R[qi]) for qi, q in enumerate(ix.queries) if not ix.q_shift[qi] and len(q) <= max_items]
+    return out + [dict(name=name, q=q, qi=None, r=restate_one(ix, q, k, m)) for name, q in serve_extras()]
+
+
+def serve_weight(c):
+    """How much a call leaves behind in a workgroup: (staged entries, scored items, hot-head accumulators in use)."""
+    r = c["r"]
+    return (r["n"], r["E"], int((r["dense"] < N_HOT).sum()) if len(r["dense"]) else 0)
+
+
+def serve_orders(tied, shape, how_many=21, attrs=None):
+    """-> {'cells': ..., 'reversed': ..., 'interleave': ...}: index lists into serve_calls.  The interleave, per resident form (a workgroup keeps only ITS form's state):
+    the served calls sorted by weight, dealt heaviest, lightest, second heaviest, second lightest, ...; then every call the form does not finish itself, each with a served
+    call directly behind it (the light half first: a light row behind a handed-over heavy one is where left-over state would show)."""
+    ix = build(tied)
+    calls = serve_calls(tied, shape)
+    kinds = [resident_kind(ix, c["r"], how_many, attrs) for c in calls]
+    inter = []
+    for form in (0, 1):
+        mine = [i for i, c in enumerate(calls) if (c["r"]["L"] > 4) == bool(form)]
+        served = sorted((i for i in mine if kinds[i] == "served"), key=lambda i: (serve_weight(calls[i]), i))
+        rest = [i for i in mine if kinds[i] != "served"]
+        a, b = 0, len(served) - 1
+        while a <= b:
+            inter.append(served[b])
+            if a < b:
+                inter.append(served[a])
+            a, b = a + 1, b - 1
+        for j, i in enumerate(rest):
+            inter += [i, served[j % len(served)]]
+    n = len(calls)
+    return dict(cells=list(range(n)), reversed=list(range(n - 1, -1, -1)), interleave=inter), kinds

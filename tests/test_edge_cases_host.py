@@ -5,7 +5,10 @@
 (b) The restatement against the oracle: posting-list lengths, neighbors_canonical's K and (session, numerator) sets, and the counters P, C, K, I, D, H, L of
     predict_batch(..., want_stats=True), for every query at both call shapes.
 (c) The oracle's rows for every 8th query against helpers.canonical_acc_over_given_lists with exact Fraction scores (as tests/test_gpu_given_idf.py does for its index).
-(d) The tied variant: the designed counts are those of the distinct variant, and tie groups straddle x_lo and the k-cut's boundary (part of its census)."""
+(d) The tied variant: the designed counts are those of the distinct variant, and tie groups straddle x_lo and the k-cut's boundary (part of its census).
+(e) edge_cases.wide_ids: a strictly increasing injection with two non-zero, different halves, under which the oracle's rows map id for id with the same score bits.
+(f) The census of the persistent latency path: the single calls of tests/test_gpu_persistent_edges.py hold every kind of answer a resident form gives, on both sides of
+    every edge (lengths 1..4 / 5, 6, 10; hand-overs; the row of 64 against 65 entries at the cut), and the designed interleave has the adjacencies it promises."""
 from fractions import Fraction
 
 import numpy as np
@@ -123,3 +126,87 @@ def test_tied_variant_has_the_designed_counts():
         for ra, rb in zip(E.restate(False, sh), E.restate(True, sh)):
             for key in ("len", "kept", "xlo", "n", "nr", "sumw", "C", "K", "nb", "E", "route", "P", "I", "D"):
                 assert ra[key] == rb[key], key
+
+
+def test_wide_ids_are_an_increasing_injection_and_the_oracle_commutes_with_them(oracles):
+    """edge_cases.wide_ids over every id of the designed index and its batch: strictly increasing, both 32-bit halves non-zero and different, hi ^ lo different between
+    neighbours (the persistent path's check word xors the halves: equal halves would cancel).  And what the GPU tests rely on instead of a second oracle run per world:
+    the oracle on the MAPPED index answers the mapped batch with the narrow index's rows, ids mapped, counts equal, scores the same bits -- one variant, one shape."""
+    from oracle import oracle as O
+    ix, _oix, rows = oracles[True]
+    ids = E.designed_ids(ix)
+    wide = E.wide_ids(ids)
+    hi, lo = (wide >> np.uint64(32)).astype(np.int64), (wide & np.uint64(0xFFFFFFFF)).astype(np.int64)
+    assert (np.diff(ids.astype(np.int64)) > 0).all() and (wide[1:] > wide[:-1]).all(), "strictly increasing"
+    assert (hi != 0).all() and (lo != 0).all() and (hi != lo).all() and int(wide.max()) < 2**63
+    assert (np.diff(hi ^ lo) != 0).all(), "hi ^ lo repeats between neighbours"
+    assert len(np.unique(hi)) < len(hi) // 4 and len(np.unique(lo)) == len(lo), "ids 7 apart share a high half: the low half alone tells them apart"
+    assert E.wide_ids([0])[0] == 0
+    sh = 1
+    k, m = E.SHAPES[sh]
+    wix = O.OracleIndex(ix.off, E.wide_ids(ix.items), ix.ts, E.M_INDEX, E.ROW_MAX, 1.0, fast=True)
+    flat, off = flatten(ix.queries)
+    got = wix.predict_batch("canonical", E.wide_ids(flat), off, k, m, HOW_MANY, False, threads=4)
+    ref = rows[sh]
+    inside = np.arange(HOW_MANY)[None, :] < ref["counts"][:, None].astype(np.int64)
+    assert np.array_equal(got["counts"], ref["counts"]) and inside.sum() > 5000
+    assert np.array_equal(got["ids"][inside], E.wide_ids(ref["ids"])[inside])
+    assert np.array_equal(got["scores"][inside].view(np.uint64), ref["scores"][inside].view(np.uint64))
+
+
+@pytest.mark.parametrize("tied", VARIANTS, ids=IDS)
+def test_census_of_the_persistent_path(tied):
+    """What keeps tests/test_gpu_persistent_edges.py from passing vacuously: the single calls it posts (edge_cases.serve_calls) hold, at BOTH shapes, every kind of answer the
+    resident forms can give, on both sides of every edge, and the designed interleave has the adjacencies its docstring promises."""
+    ix = E.build(tied)
+    attrs = E.business_attrs(ix)
+    for sh, (k, m) in enumerate(E.SHAPES):
+        calls = E.serve_calls(tied, sh)
+        assert len(calls) >= 120 and all(1 <= c["r"]["L"] <= 10 for c in calls)
+        # the routing half of the predicate: with L <= 4 on the lean form and 5..10 on the other one, a resident form keeps exactly what the launch sequence routes lean / mid
+        for c in calls:
+            assert (E.resident_route(c["r"]) in ("lean", "mid")) == (c["r"]["route"] in ("lean", "mid")), c["name"]
+        for how_many, at, what in ((21, None, "default"), (64, None, "how_many 64"), (21, attrs, "business rules")):
+            kinds = [E.resident_kind(ix, c["r"], how_many, at) for c in calls]
+            count = {kd: kinds.count(kd) for kd in set(kinds)}
+            print("%s, (k, m) = (%d, %d), %s: %d calls, %s" % ("tied" if tied else "distinct", k, m, what, len(calls), count))
+            served = [c for c, kd in zip(calls, kinds) if kd == "served"]
+            for L in (1, 2, 3, 4):
+                assert any(c["r"]["L"] == L and c["r"]["route"] == "lean" and c["r"]["n"] > 0 for c in served), "no served lean query of %d items" % L
+            for L in (5, 6, 10):   # (5: one control line, five items; 6: the second line's first item; 10: max_items)
+                assert any(c["r"]["L"] == L and c["r"]["n"] > 0 for c in served), "no served query of %d items on the form for 5..10" % L
+            assert count.get("general", 0) >= 1, "no query that a resident form hands to the general kernel"
+            # the lean form's oversized route needs n > 6 012 from at most four lists of at most m entries: out of reach at m = 1 100, placed at m = 2 560
+            assert (count.get("big", 0) >= 1) == (sh == 1) and (sh == 1 or 4 * m < E.N_LEAN)
+            assert any(c["r"]["L"] > 4 for c, kd in zip(calls, kinds) if kd == "general"), "nothing that the form for 5..10 items hands over"
+            assert sh == 0 or any(c["r"]["L"] <= 4 for c, kd in zip(calls, kinds) if kd == "general"), "nothing that the lean form hands to the general kernel"
+            # a row of count 0 (no known item: the count is written at once, status 0), on both forms
+            assert any(c["r"]["n"] == 0 and c["r"]["E"] == 0 and c["r"]["L"] == 1 for c in served) and any(c["r"]["n"] == 0 and c["r"]["L"] > 5 for c in served)
+            # the row edge: T = tight_set, served iff T <= 64.  E <= 63 bounds T whatever the scores are
+            by_E = {c["r"]["E"]: (c, kd) for c, kd in zip(calls, kinds) if c["name"].startswith("rows E=")}
+            T = {e: E.tight_set(ix, by_E[e][0]["r"], how_many, at) for e in (63, 64, 65)}
+            for c, kd in zip(calls, kinds):
+                if kd in ("served", "over64") and c["r"]["E"] <= 63:
+                    assert kd == "served" and E.tight_set(ix, c["r"], how_many, at) <= c["r"]["E"]
+            if how_many == 64:      # the edge is live: 63 and 64 entries at the cut are finished in place, 65 are not
+                assert (T[63], T[64], T[65]) == (63, 64, 65) and [by_E[e][1] for e in (63, 64, 65)] == ["served", "served", "over64"]
+            else:                   # how_many-th best + ties: far fewer than the rows' scored items -- rows of 64 and 65 items ARE served (not `E <= 63`)
+                assert all(how_many <= T[e] <= E.SERVE_MAX_ENTRIES and by_E[e][1] == "served" for e in (63, 64, 65)), T
+                assert sum(1 for c in served if c["r"]["E"] > 63) >= 60, "large queries whose thresholds leave a short entry list"
+            # the interleave
+            orders, kinds2 = E.serve_orders(tied, sh, how_many, at)
+            assert kinds2 == kinds and orders["cells"] == list(range(len(calls))) and orders["reversed"] == orders["cells"][::-1]
+            order = orders["interleave"]
+            assert set(order) == set(range(len(calls))), "the interleave leaves a call out"
+            form = lambda i: calls[i]["r"]["L"] > 4   # noqa: E731
+            for p, i in enumerate(order):
+                if kinds[i] != "served":   # every call the form does not finish: a served one of the SAME form (the same workgroup, with one caller) directly behind it
+                    assert p + 1 < len(order) and kinds[order[p + 1]] == "served" and form(order[p + 1]) == form(i), (calls[i]["name"], p)
+            for f in (False, True):
+                mine = [i for i in range(len(calls)) if form(i) == f and kinds[i] == "served"]
+                heavy, light = max(mine, key=lambda i: (E.serve_weight(calls[i]), i)), min(mine, key=lambda i: (E.serve_weight(calls[i]), i))
+                p = order.index(heavy)
+                assert order[p + 1] == light and calls[light]["r"]["n"] == 0 and calls[heavy]["r"]["n"] == (E.N_MID if f else min(E.N_LEAN, 4 * m - 3)), (calls[heavy]["name"], calls[light]["name"])   # (the largest n the form takes; at m = 1 100 four lists under a cut)
+                head = order[p:p + len(mine)]
+                assert sorted(head) == sorted(mine) and all(E.serve_weight(calls[a]) >= E.serve_weight(calls[b]) for a, b in zip(head[0::2], head[1::2]))
+                assert any(int((calls[i]["r"]["dense"] < E.N_HOT).sum()) >= 150 for i in head[0:8:2]), "the heaviest carry a hot-head payload"

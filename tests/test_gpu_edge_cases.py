@@ -15,93 +15,21 @@ every test one batch of all queries, at the call shapes (k, m) = (500, 1 100) an
     table; edge_cases.backend_fits states that on the CPU and the census asserts it.)  The ABI has no count for the LONG form's list or for rows of more than 63 entries.
 (c) Outside the fast limits, (k, m) = (1 537, 2 560) and (1 536, 2 561): the whole batch goes to the general kernel and stays oracle-exact.
 (d) The latency path: every cell of <= 10 items as a single srn_predict call (the TINY form, which decodes the items itself), fused and with SRN_TINY_FUSED=0; after
-    each call last_path_counts says whether the TINY form served it (lean and MID routes) or the general kernel behind it (everything else).  The persistent form is not
-    covered here."""
-import os
-import time
-
+    each call last_path_counts says whether the TINY form served it (lean and MID routes) or the general kernel behind it (everything else).  The persistent form of
+    that path -- resident workgroups, the same sessions posted one by one -- is tests/test_gpu_persistent_edges.py.
+World, the row comparisons and the knobs fixture are tests/edge_world.py's, shared with that file."""
 import numpy as np
 import pytest
 
 import edge_cases as E
 import record_cases as RC
-from fill_cases import draw_attrs
-from helpers import flatten
+from edge_world import SCORE_RTOL, World, _same_bytes, _vs_oracle, knobs  # noqa: F401  (knobs: the fixture)
 
 pytestmark = pytest.mark.gpu
 
-SCORE_RTOL = 1e-12   # (as tests/test_gpu_parity.py: one f64 multiply + divide of an exact integer accumulator on both sides)
-KNOBS = ("SRN_GRID_MULT", "SRN_ORDER_MIN", "SRN_NO_FAST", "SRN_FAST_RUNS", "SRN_NO_MID", "SRN_NO_BIG", "SRN_NO_LONG", "SRN_TINY_FUSED")
 VARIANTS = ["distinct", "tied"]
 PATHS = {"default": {}, "grid1": dict(SRN_GRID_MULT=1), "ordered": dict(SRN_ORDER_MIN=1), "wide": dict(SRN_FAST_RUNS=3), "no_mid": dict(SRN_NO_MID=1), "no_big": dict(SRN_NO_BIG=1),
          "no_long": dict(SRN_NO_LONG=1), "how_many64": {}, "business": {}}
-
-
-@pytest.fixture
-def knobs():
-    from serenade_amd import capi
-
-    def set_(**kv):
-        for name in KNOBS:
-            os.environ.pop(name, None)
-        for name, v in kv.items():
-            os.environ[name] = str(v)
-        capi.reload_knobs()
-    yield set_
-    for name in KNOBS:
-        os.environ.pop(name, None)
-    capi.reload_knobs()
-
-
-class World:
-    """One timestamp variant: the index on the GPU and in the oracle, the batch on the device, and the reference rows, each computed once and never changed."""
-
-    def __init__(self, tied):
-        import serenade_amd as sa
-        import torch
-        from oracle import oracle as O
-        t0 = time.time()
-        self.torch, self.tied = torch, tied
-        self.ix = ix = E.build(tied)
-        self.gix = sa.VMISIndex.from_sessions(ix.off, ix.items, ix.ts, E.M_INDEX, E.ROW_MAX, 1.0, device=0)
-        self.oix = O.OracleIndex(ix.off, ix.items, ix.ts, E.M_INDEX, E.ROW_MAX, 1.0, fast=True)
-        known, flags = draw_attrs(ix.items)
-        self.gix.set_attributes(known, flags)
-        self.oix.set_attributes(known, flags)
-        self.qs, self.nq = ix.queries, len(ix.queries)
-        self.flat, self.off = flatten(self.qs)
-        self.d_flat = torch.from_numpy(np.concatenate([self.flat, np.zeros(1, np.uint64)]).view(np.int64).copy()).to("cuda:0")
-        self.d_off = torch.from_numpy(self.off.view(np.int32).copy()).to("cuda:0")
-        self._ref, self._slow = {}, {}
-        self.seconds = time.time() - t0
-
-    def ref(self, k, m, how_many=21, business=False):
-        key = (k, m, how_many, business)
-        if key not in self._ref:
-            r = self.oix.predict_batch("canonical", self.flat, self.off, k, m, how_many, business, threads=8, want_stats=True)
-            for a in (r["ids"], r["scores"], r["counts"], r["stats"]):
-                a.setflags(write=False)
-            self._ref[key] = r
-        return self._ref[key]
-
-    def call(self, k, m, how_many=21, business=False):
-        """srn_predict_batch_device over the resident batch -> (ids u64[nq, n], scores f64[nq, n], counts u32[nq])."""
-        import serenade_amd as sa
-        t = self.torch
-        o = (t.zeros(self.nq * how_many, dtype=t.int64, device="cuda:0"), t.zeros(self.nq * how_many, dtype=t.float64, device="cuda:0"), t.zeros(self.nq, dtype=t.int32, device="cuda:0"))
-        sa.predict_batch_device(self.gix, self.d_flat.data_ptr(), self.d_off.data_ptr(), self.nq, E.MAX_LEN, k, m, how_many, business,
-                                o[0].data_ptr(), o[1].data_ptr(), o[2].data_ptr(), t.cuda.current_stream().cuda_stream, resident=True)
-        t.cuda.synchronize()
-        return (o[0].cpu().numpy().view(np.uint64).reshape(-1, how_many).copy(), o[1].cpu().numpy().reshape(-1, how_many).copy(), o[2].cpu().numpy().view(np.uint32).copy())
-
-    def slow(self, knobs, k, m, how_many=21, business=False):
-        """The rows without the fast kernels (SRN_NO_FAST=1)."""
-        key = (k, m, how_many, business)
-        if key not in self._slow:
-            knobs(SRN_NO_FAST=1)
-            self._slow[key] = self.call(k, m, how_many, business)
-            knobs()
-        return self._slow[key]
 
 
 @pytest.fixture(scope="module", params=VARIANTS)
@@ -109,24 +37,6 @@ def world(request):
     w = World(request.param == "tied")
     print("%s: %d cells, %d sessions, %d queries, fixture built in %.1f s" % (request.param, len(w.ix.cells), len(w.ix.ts), w.nq, w.seconds))
     return w
-
-
-def _vs_oracle(got, ref, what):
-    ids, sc, cnt = got
-    assert np.array_equal(cnt, ref["counts"]), "%s: counts differ from the oracle at queries %s" % (what, np.flatnonzero(cnt != ref["counts"])[:8])
-    inside = np.arange(ids.shape[1])[None, :] < ref["counts"][:, None].astype(np.int64)
-    bad = np.flatnonzero(((ids != ref["ids"]) & inside).any(axis=1))
-    assert len(bad) == 0, "%s: ranked ids differ from the oracle at queries %s" % (what, bad[:8])
-    np.testing.assert_allclose(sc[inside], ref["scores"][inside], rtol=SCORE_RTOL, atol=0)
-
-
-def _same_bytes(got, ref, what):
-    ids, sc, cnt = got
-    rids, rsc, rcnt = ref
-    assert np.array_equal(cnt, rcnt), "%s: counts differ at %s" % (what, np.flatnonzero(cnt != rcnt)[:8])
-    inside = np.arange(ids.shape[1])[None, :] < np.minimum(cnt, ids.shape[1]).astype(np.int64)[:, None]
-    assert np.array_equal(ids[inside], rids[inside]), "%s: ids differ" % what
-    assert np.array_equal(sc[inside].view(np.uint64), rsc[inside].view(np.uint64)), "%s: scores differ in their bits" % what
 
 
 @pytest.mark.parametrize("wide", [False, True], ids=["narrow", "wide"])
