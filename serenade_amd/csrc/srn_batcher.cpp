@@ -23,12 +23,6 @@
 using namespace srn;
 
 namespace {
-template <typename F> int guarded(F f) {   // never let an exception cross the C boundary
-    try { return f(); }
-    catch (const std::bad_alloc&) { return fail(SRN_ENOMEM, "out of host memory"); }
-    catch (const std::exception& e) { return fail(SRN_EINVAL, std::string("internal error: ") + e.what()); }
-    catch (...) { return fail(SRN_EINVAL, "internal error"); }
-}
 struct Request {
     const uint64_t* evolving; size_t len;
     uint64_t* out_ids; double* out_scores; size_t* out_n;

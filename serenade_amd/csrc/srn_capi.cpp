@@ -11,12 +11,6 @@ namespace srn { const char* last_error_cstr(); int device_count(); }
 using namespace srn;
 
 namespace {
-template <typename F> int guarded(F f) {   // never let an exception cross the C boundary
-    try { return f(); }
-    catch (const std::bad_alloc&) { return fail(SRN_ENOMEM, "out of host memory"); }
-    catch (const std::exception& e) { return fail(SRN_EINVAL, std::string("internal error: ") + e.what()); }
-    catch (...) { return fail(SRN_EINVAL, "internal error"); }
-}
 
 int check_predict_args(const srn_index_t* idx, size_t k, size_t m, size_t how_many) {
     if (!idx) return fail(SRN_EINVAL, "null index");

@@ -19,6 +19,10 @@
 // Three transports behind one interface: RCCL (one process per GPU), host callbacks (an application's own transport; the tests drive two
 // processes over gloo with it), and an in-process group (all shards of the group on this process's device: collectives degenerate to kernels --
 // tests, and capacity experiments on one GPU).  Same kernels, same bytes in all three.
+//
+// In this file: srn_shard_group_predict_batch validates and makes a GroupBatch; group_predict (lock, broken-group rule) -> group_predict_locked (the rank-invariant choice)
+// -> one function per pipeline: group_predict_lists (the sketch above), group_predict_neighbours, group_predict_stages.  What a batch needs whatever its pipeline -- the
+// slot, the stream ordering, each local shard's result block, the result all-gather + merge, the counters -- is written once, in Frame.
 // =====================================================================================
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
@@ -40,13 +44,6 @@
 namespace srn {
 
 namespace {
-template <typename F> int guarded(F f) {   // never let an exception cross the C boundary
-    try { return f(); }
-    catch (const std::bad_alloc&) { return fail(SRN_ENOMEM, "out of host memory"); }
-    catch (const std::exception& e) { return fail(SRN_EINVAL, std::string("internal error: ") + e.what()); }
-    catch (...) { return fail(SRN_EINVAL, "internal error"); }
-}
-
 // ---- RCCL through dlopen: no link-time dependency, and ONE RCCL per process (a host that already loaded librccl -- torch does -- shares it) ----
 struct RcclApi {
     void* h = nullptr;
@@ -90,25 +87,37 @@ RcclApi* rccl() {
         if (r_ != ncclSuccess) return fail(SRN_EHIP, std::string(#expr) + ": " + (rccl()->GetErrorString ? rccl()->GetErrorString(r_) : "rccl error")); \
     } while (0)
 
-struct Slot {   // everything one batch in flight needs (grow-only); two slots: batch i + 1's exchange overlaps batch i's kernels
-    std::vector<char*> pos; std::vector<size_t> pos_bytes;   // per local shard
-    char* head = nullptr; size_t head_bytes = 0;             // [nq][3] int32 (in-process group: + one scratch copy behind it)
-    char* kept = nullptr; size_t kept_bytes = 0;             // [G][nq * max_len] u32
-    char* tot = nullptr; size_t tot_bytes = 0;               // [nq] int32 (the count kernel's per-query totals; unused here)
-    char* off = nullptr; size_t off_bytes = 0;               // [G][nq] int64
-    char* small = nullptr; size_t small_bytes = 0;           // tot_dev [G] u64 | base_dev [G] u64
-    unsigned long long* tot_host = nullptr;                  // pinned, device-mapped: [G] totals | [G] bases
-    char* lists = nullptr; size_t lists_bytes = 0;           // the gathered list prefixes, segment g at base[g]
-    char* records = nullptr; size_t records_bytes = 0;
-    char* part = nullptr; size_t part_bytes = 0;             // [G] blocks: ids | scores | counts
+struct Buf {   // one grow-only device buffer
+    char* p = nullptr; size_t bytes = 0;
+    int ensure(size_t need) { return srn::ensure(&p, &bytes, need); }
+};
+enum SlotBuf {
+    HEAD,      // [nq][3] int32 (in-process group: + one scratch copy behind it)
+    KEPT,      // [G][nq * max_len] u32
+    TOT,       // [nq] int32 (the count kernel's per-query totals; unused here)
+    OFF,       // [G][nq] int64
+    SMALL,     // tot_dev [G] u64 | base_dev [G] u64
+    LISTS,     // the gathered list prefixes, segment g at base[g]
+    RECORDS,
+    PART,      // [G] blocks: ids | scores | counts
     // three-stage pipeline: [G] candidate blocks + [G][nq] counts, the neighbour list, first-match positions (+ one scratch copy for an in-process group), overflow flags
-    char* cand = nullptr; size_t cand_bytes = 0; char* cand_cnt = nullptr; size_t cand_cnt_bytes = 0;
-    char* nb = nullptr; size_t nb_bytes = 0; char* nb_cnt = nullptr; size_t nb_cnt_bytes = 0; char* minpos = nullptr; size_t minpos_bytes = 0; char* flagq = nullptr; size_t flagq_bytes = 0;
-    // neighbours pipeline: [G * per][k + 1] words (a query's row: K | K packed slots), and every local shard's prep records of the whole batch
-    char* xpos = nullptr; size_t xpos_bytes = 0;   // the neighbours as posting positions (the streaming back end's exchange format)
-    char* xchg = nullptr; size_t xchg_bytes = 0; std::vector<char*> nrec; std::vector<size_t> nrec_bytes;
-    std::vector<char*> nord; std::vector<size_t> nord_bytes; std::vector<const unsigned long long*> nord_ptr;   // ... and the batch's serving order (keys, sorted keys, scratch)
+    CAND, CAND_CNT, NB, NB_CNT, MINPOS, FLAGQ,
+    // neighbours pipeline: [G * per][k + 1] words (a query's row: K | K packed slots); the neighbours as posting positions (the streaming back end's exchange format)
+    XCHG, XPOS,
+    N_SLOT_BUF
+};
+struct Slot {   // everything one batch in flight needs (grow-only); two slots: batch i + 1's exchange overlaps batch i's kernels
+    Buf buf[N_SLOT_BUF];
+    // per local shard: the lists pipeline's positions; the neighbours pipeline's prep records of the whole batch and its serving order (keys, sorted keys, scratch)
+    std::vector<Buf> pos, nrec, nord; std::vector<const unsigned long long*> nord_ptr;
+    unsigned long long* tot_host = nullptr;                  // pinned, device-mapped: [G] totals | [G] bases
     hipEvent_t e_done = nullptr;
+    int ensure(std::initializer_list<std::pair<SlotBuf, size_t>> needs) { for (const auto& n : needs) { const int rc = buf[n.first].ensure(n.second); if (rc) return rc; } return SRN_OK; }
+};
+struct GroupBatch {   // one srn_shard_group_predict_batch call, validated
+    LaunchParams p;       // with the caller's three output pointers
+    bool resident;        // SRN_FLAG_INPUTS_RESIDENT (group_predict_locked takes it out of p.flags)
+    hipStream_t stream;   // the caller's
 };
 }  // namespace
 
@@ -183,12 +192,8 @@ int all_gather_v(srn_shard_group* g, int channel, char* buf, const unsigned long
 }
 
 void slot_free(Slot& s) {
-    for (char* p : s.pos) if (p) hipFree(p);
-    for (char* p : s.nrec) if (p) hipFree(p);
-    for (char* p : s.nord) if (p) hipFree(p);
-    if (s.xchg) hipFree(s.xchg);
-    if (s.xpos) hipFree(s.xpos);
-    for (char* p : {s.head, s.kept, s.tot, s.off, s.small, s.lists, s.records, s.part, s.cand, s.cand_cnt, s.nb, s.nb_cnt, s.minpos, s.flagq}) if (p) hipFree(p);
+    for (Buf& b : s.buf) if (b.p) hipFree(b.p);
+    for (auto* v : {&s.pos, &s.nrec, &s.nord}) for (Buf& b : *v) if (b.p) hipFree(b.p);
     if (s.tot_host) hipHostFree(s.tot_host);
     if (s.e_done) hipEventDestroy(s.e_done);
     s = Slot();
@@ -204,9 +209,7 @@ int group_init_common(srn_shard_group* g) {
     for (Slot& s : g->slot) {
         HIP_TRY(hipEventCreateWithFlags(&s.e_done, hipEventDisableTiming));
         HIP_TRY(hipHostMalloc((void**)&s.tot_host, (size_t)G * 16, hipHostMallocMapped));
-        s.pos.assign(g->shards.size(), nullptr); s.pos_bytes.assign(g->shards.size(), 0);
-        s.nrec.assign(g->shards.size(), nullptr); s.nrec_bytes.assign(g->shards.size(), 0);
-        s.nord.assign(g->shards.size(), nullptr); s.nord_bytes.assign(g->shards.size(), 0); s.nord_ptr.assign(g->shards.size(), nullptr);
+        s.pos.assign(g->shards.size(), Buf()); s.nrec.assign(g->shards.size(), Buf()); s.nord.assign(g->shards.size(), Buf()); s.nord_ptr.assign(g->shards.size(), nullptr);
     }
     if (const char* e = getenv("SRN_GROUP_OVERLAP")) g->overlap = atoi(e) != 0;
     g->no_direct = getenv("SRN_GROUP_NO_DIRECT") != nullptr;
@@ -222,74 +225,115 @@ int check_shard(const srn_index* ix, uint32_t want_shard, uint32_t n_shards) {
     return SRN_OK;
 }
 
+// ---- the frame of a batch, the same for the three pipelines: its slot and streams, the ordering behind the slot's previous batch, each local shard's result block, and
+// the tail (result all-gather + merge, the slot's event, the group's counters).  exchange: the pipeline has an exchange part that may run on the group's second stream
+// (lists, neighbours) and is timed under SRN_GROUP_TIMING; the three-stage pipeline keeps everything on the caller's stream ----
+struct Frame {
+    srn_shard_group* g; const GroupBatch& b; Slot& s; uint32_t G, nq, n; bool local, exchange, overlap, timed; hipStream_t user, sx;
+    size_t block_bytes;   // one shard's block of s.buf[PART]
+    LaunchParams p;       // the batch for every step but the last: an exchange pipeline's without the output pointers (the stages mark an unservable query in the caller's counts at once)
+    Frame(srn_shard_group* g_, const GroupBatch& b_, bool exchange_)
+        : g(g_), b(b_), s(g_->slot[g_->calls & 1u]), G(G_of(g_)), nq(b_.p.nq), n(b_.p.how_many), local(g_->kind == srn_shard_group::LOCAL), exchange(exchange_),
+          overlap(exchange_ && g_->overlap && !local), timed(exchange_ && g_->timing), user(b_.stream), sx(overlap ? g_->s_x : b_.stream),
+          block_bytes(((size_t)nq * n * 16 + (size_t)nq * 4 + 255) / 256 * 256), p(b_.p) {
+        if (exchange) { p.out_ids = nullptr; p.out_scores = nullptr; p.out_counts = nullptr; }
+    }
+    uint32_t gi(size_t i) const { return local ? (uint32_t)i : (uint32_t)g->rank; }   // local shard i's index in the group
+    ShardCall shard(size_t i, hipStream_t st) const { return ShardCall{g->shards[i]->dev, &g->shards[i]->flat, g->postings ? g->postings->dev : nullptr, st}; }
+    // behind the pipeline's own buffers (grow-only; growing synchronises the device, like every hipFree): the result blocks, then the exchange stream ordered behind the
+    // caller's inputs, and both streams behind the batch that used this slot two calls ago
+    int begin() {
+        { int rc = s.buf[PART].ensure((size_t)G * block_bytes); if (rc) return rc; }
+        if (overlap) {
+            if (!b.resident) { HIP_TRY(hipEventRecord(g->e_in, user)); HIP_TRY(hipStreamWaitEvent(sx, g->e_in, 0)); }   // (behind everything on the caller's stream: correct, but no overlap)
+            if (g->calls >= 2) HIP_TRY(hipStreamWaitEvent(sx, s.e_done, 0));
+        }
+        if (g->calls >= 2) HIP_TRY(hipStreamWaitEvent(user, s.e_done, 0));   // (callers may alternate between streams: the slot's previous user may have run on another one, or on the exchange stream)
+        return SRN_OK;
+    }
+    int exchanged() {   // the caller's stream goes on behind the exchange
+        if (overlap) { HIP_TRY(hipEventRecord(g->e_x, sx)); HIP_TRY(hipStreamWaitEvent(user, g->e_x, 0)); }
+        return SRN_OK;
+    }
+    // local shard i's parameters with its result rows, zeroed: its block of s.buf[PART], or the caller's buffers when it is the only shard (its top-n IS the result)
+    int rows(size_t i, LaunchParams* pi) {
+        char* blk = s.buf[PART].p + (size_t)gi(i) * block_bytes;
+        *pi = b.p;
+        if (G > 1) { pi->out_ids = (uint64_t*)blk; pi->out_scores = (double*)(blk + (size_t)nq * n * 8); pi->out_counts = (uint32_t*)(blk + (size_t)nq * n * 16); }
+        if (timed && i == 0) HIP_TRY(hipEventRecord(g->e_t[2], user));
+        HIP_TRY(hipMemsetAsync(pi->out_ids, 0, (size_t)nq * n * 8, user)); HIP_TRY(hipMemsetAsync(pi->out_scores, 0, (size_t)nq * n * 8, user));
+        return SRN_OK;
+    }
+    int finish() {
+        if (G > 1) {
+            int rc = all_gather_blocks(g, 1, s.buf[PART].p, block_bytes, user); if (rc) return rc;
+            if (timed) HIP_TRY(hipEventRecord(g->e_t[4], user));
+            HIP_TRY(launch_shard_merge_topn(user, s.buf[PART].p, block_bytes, G, nq, n, b.p.out_ids, b.p.out_scores, b.p.out_counts));
+            if (timed) HIP_TRY(hipEventRecord(g->e_t[5], user));
+        }
+        if (!exchange) HIP_TRY(launch_shard_mark(user, (const uint32_t*)s.buf[FLAGQ].p, nq, b.p.out_counts));   // (the stages' overflow flags)
+        HIP_TRY(hipEventRecord(s.e_done, user));
+        if (timed) {   // (measurement runs only: synchronises.  [0] = everything between the pipeline's events 0 and 1 on the exchange stream)
+            HIP_TRY(hipEventSynchronize(s.e_done));
+            HIP_TRY(hipEventElapsedTime(&g->last_ms[0], g->e_t[0], g->e_t[1])); HIP_TRY(hipEventElapsedTime(&g->last_ms[1], g->e_t[2], g->e_t[3]));
+            g->last_ms[2] = 0.f; if (G > 1) HIP_TRY(hipEventElapsedTime(&g->last_ms[2], g->e_t[4], g->e_t[5]));
+        }
+        ++g->calls;
+        g->st_queries += nq; g->st_bytes_results += G > 1 ? (uint64_t)block_bytes * (local ? G : 1) : 0;
+        return SRN_OK;   // (the batch is issued: the pipeline's own counters follow)
+    }
+};
+
 // The three-stage pipeline (round 1's kernels, `STAGE` instantiations of vmis_predict_kernel) for what the lists pipeline does not serve -- sessions of > 8 items,
 // m > m_index, incomplete posting lists: stage A (this shard's candidates, locally cut to m) -> all-gather -> stage B (global cuts: the neighbour list, identical on every
 // rank; partial first-match positions over the evolving items this shard owns) -> all-reduce(min) -> stage C (accumulate over the shard's row fragments, exact top-n among
 // the items it owns) -> all-gather -> merge.  Everything on the caller's stream, no host synchronisation; a query whose session table overflowed on some shard comes back
 // with out_counts = 0xFFFFFFFF like on the unsharded path.  (serenade_amd/sharded.py drove these stages from Python until round 3, with a compaction of the candidate slabs
 // that is not repeated here: the lists pipeline is the fast path, this is the complete one.)
-int group_predict_stages(srn_shard_group* g, const LaunchParams& p, uint64_t* d_out_ids, double* d_out_scores, uint32_t* d_out_counts, hipStream_t user) {
-    const uint32_t G = G_of(g), nq = p.nq, n = p.how_many;
-    const bool local = g->kind == srn_shard_group::LOCAL;
+int group_predict_stages(srn_shard_group* g, const GroupBatch& b) {
     if (g->kind == srn_shard_group::CALLBACKS && !g->cb.all_reduce_min_i32) return fail(SRN_EINVAL, "this batch needs the three-stage pipeline, and the group's transport has no all_reduce_min_i32");
-    Slot& s = g->slot[g->calls & 1u];
+    Frame f(g, b, false);
+    Slot& s = f.s; const LaunchParams& p = f.p; const uint32_t G = f.G, nq = f.nq; const hipStream_t user = f.user;
     uint32_t num_bits = 0;
     const int sb = device_slot_bytes(g->shards[0]->dev, g->shards[0]->flat, p.max_len, &num_bits);
     if (sb < 0) return SRN_ERANGE;
-    const size_t cand_block = (size_t)nq * p.m * (size_t)sb /* exactly [nq][m] slots: stage B indexes the gathered buffer as [G][nq][m] */, block_bytes = ((size_t)nq * n * 16 + (size_t)nq * 4 + 255) / 256 * 256;
+    const size_t cand_block = (size_t)nq * p.m * (size_t)sb;   // exactly [nq][m] slots: stage B indexes the gathered buffer as [G][nq][m]
     const size_t mp_count = (size_t)nq * ((size_t)p.k + 1);
     {
-        int rc = ensure(&s.cand, &s.cand_bytes, (size_t)G * cand_block);
-        if (!rc) rc = ensure(&s.cand_cnt, &s.cand_cnt_bytes, (size_t)G * nq * 4);
-        if (!rc) rc = ensure(&s.nb, &s.nb_bytes, (size_t)nq * p.k * (size_t)sb);
-        if (!rc) rc = ensure(&s.nb_cnt, &s.nb_cnt_bytes, (size_t)nq * 4);
-        if (!rc) rc = ensure(&s.minpos, &s.minpos_bytes, mp_count * 4 * 2);
-        if (!rc) rc = ensure(&s.flagq, &s.flagq_bytes, (size_t)nq * 4);
-        if (!rc) rc = ensure(&s.part, &s.part_bytes, (size_t)G * block_bytes);
+        int rc = s.ensure({{CAND, (size_t)G * cand_block}, {CAND_CNT, (size_t)G * nq * 4}, {NB, (size_t)nq * p.k * (size_t)sb}, {NB_CNT, (size_t)nq * 4}, {MINPOS, mp_count * 4 * 2}, {FLAGQ, (size_t)nq * 4}});
+        if (!rc) rc = f.begin();
         if (rc) return rc;
     }
-    uint32_t* cnt_g = (uint32_t*)s.cand_cnt; int* minpos = (int*)s.minpos;
-    if (g->calls >= 2) HIP_TRY(hipStreamWaitEvent(user, s.e_done, 0));   // (the batch that used this slot two calls ago -- on the exchange stream, or on ANOTHER caller's stream -- is done with its buffers)
+    char* cand = s.buf[CAND].p; char* nb = s.buf[NB].p; uint32_t* cnt_g = (uint32_t*)s.buf[CAND_CNT].p; uint32_t* nb_cnt = (uint32_t*)s.buf[NB_CNT].p; int* minpos = (int*)s.buf[MINPOS].p;
     // stage A
     for (size_t i = 0; i < g->shards.size(); ++i) {
-        const uint32_t gi = local ? (uint32_t)i : (uint32_t)g->rank;
-        ShardIO sh{}; sh.cand = s.cand + (size_t)gi * cand_block; sh.cand_cnt = cnt_g + (size_t)gi * nq;
-        int rc = device_shard_stage(g->shards[i]->dev, g->shards[i]->flat, 1, p, sh, user); if (rc) return rc;
+        ShardIO sh{}; sh.cand = cand + (size_t)f.gi(i) * cand_block; sh.cand_cnt = cnt_g + (size_t)f.gi(i) * nq;
+        int rc = device_shard_stage(f.shard(i, user), 1, p, sh); if (rc) return rc;
     }
-    { int rc = all_gather_blocks(g, 1, s.cand, cand_block, user); if (rc) return rc; }
-    { int rc = all_gather_blocks(g, 1, s.cand_cnt, (size_t)nq * 4, user); if (rc) return rc; }
-    HIP_TRY(launch_shard_scrub_counts(user, cnt_g, G, nq, (uint32_t*)s.flagq));
+    { int rc = all_gather_blocks(g, 1, cand, cand_block, user); if (rc) return rc; }
+    { int rc = all_gather_blocks(g, 1, (char*)cnt_g, (size_t)nq * 4, user); if (rc) return rc; }
+    HIP_TRY(launch_shard_scrub_counts(user, cnt_g, G, nq, (uint32_t*)s.buf[FLAGQ].p));
     // stage B (every rank computes the same neighbour list; its own partial first-match positions)
     for (size_t i = 0; i < g->shards.size(); ++i) {
         int* mp_i = i == 0 ? minpos : minpos + mp_count;
-        HIP_TRY(hipMemsetAsync(s.nb, 0, (size_t)nq * p.k * (size_t)sb, user));
+        HIP_TRY(hipMemsetAsync(nb, 0, (size_t)nq * p.k * (size_t)sb, user));
         HIP_TRY(launch_shard_fill_i32(user, mp_i, 0x7FFFFFFF, mp_count));
-        ShardIO sh{}; sh.gathered = s.cand; sh.gathered_cnt = cnt_g; sh.n_shards = G; sh.gathered_stride = 0;
-        sh.nb = s.nb; sh.nb_cnt = (uint32_t*)s.nb_cnt; sh.minpos = mp_i;
-        int rc = device_shard_stage(g->shards[i]->dev, g->shards[i]->flat, 2, p, sh, user); if (rc) return rc;
+        ShardIO sh{}; sh.gathered = cand; sh.gathered_cnt = cnt_g; sh.n_shards = G; sh.gathered_stride = 0;
+        sh.nb = nb; sh.nb_cnt = nb_cnt; sh.minpos = mp_i;
+        int rc = device_shard_stage(f.shard(i, user), 2, p, sh); if (rc) return rc;
         if (i > 0) HIP_TRY(launch_shard_min(user, minpos, mp_i, mp_count));
     }
     { int rc = all_reduce_min_i32(g, 1, minpos, mp_count, user); if (rc) return rc; }
     // stage C
     for (size_t i = 0; i < g->shards.size(); ++i) {
-        const uint32_t gi = local ? (uint32_t)i : (uint32_t)g->rank;
-        char* blk = s.part + (size_t)gi * block_bytes;
-        LaunchParams pi = p;
-        const bool direct = G == 1;
-        pi.out_ids = direct ? d_out_ids : (uint64_t*)blk; pi.out_scores = direct ? d_out_scores : (double*)(blk + (size_t)nq * n * 8); pi.out_counts = direct ? d_out_counts : (uint32_t*)(blk + (size_t)nq * n * 16);
-        HIP_TRY(hipMemsetAsync(pi.out_ids, 0, (size_t)nq * n * 8, user)); HIP_TRY(hipMemsetAsync(pi.out_scores, 0, (size_t)nq * n * 8, user)); HIP_TRY(hipMemsetAsync(pi.out_counts, 0, (size_t)nq * 4, user));
-        ShardIO sh{}; sh.nb = s.nb; sh.nb_cnt = (uint32_t*)s.nb_cnt; sh.minpos = minpos;
-        int rc = device_shard_stage(g->shards[i]->dev, g->shards[i]->flat, 3, pi, sh, user); if (rc) return rc;
+        LaunchParams pi;
+        { int rc = f.rows(i, &pi); if (rc) return rc; }
+        HIP_TRY(hipMemsetAsync(pi.out_counts, 0, (size_t)nq * 4, user));
+        ShardIO sh{}; sh.nb = nb; sh.nb_cnt = nb_cnt; sh.minpos = minpos;
+        int rc = device_shard_stage(f.shard(i, user), 3, pi, sh); if (rc) return rc;
     }
-    if (G > 1) {
-        int rc = all_gather_blocks(g, 1, s.part, block_bytes, user); if (rc) return rc;
-        HIP_TRY(launch_shard_merge_topn(user, s.part, block_bytes, G, nq, n, d_out_ids, d_out_scores, d_out_counts));
-    }
-    HIP_TRY(launch_shard_mark(user, (const uint32_t*)s.flagq, nq, d_out_counts));
-    HIP_TRY(hipEventRecord(s.e_done, user));
-    ++g->calls;
-    g->st_queries += nq; g->st_bytes_stage_cand += (uint64_t)(cand_block + (size_t)nq * 4) * (local ? G : 1); g->st_bytes_stage_minpos += (uint64_t)mp_count * 4;
-    g->st_bytes_results += G > 1 ? (uint64_t)block_bytes * (local ? G : 1) : 0; ++g->st_stage_batches;
+    { int rc = f.finish(); if (rc) return rc; }
+    g->st_bytes_stage_cand += (uint64_t)(cand_block + (size_t)nq * 4) * (f.local ? G : 1); g->st_bytes_stage_minpos += (uint64_t)mp_count * 4; ++g->st_stage_batches;
     return SRN_OK;
 }
 
@@ -298,15 +342,10 @@ int group_predict_stages(srn_shard_group* g, const LaunchParams& p, uint64_t* d_
 // (no host synchronisation anywhere in the batch); then every rank runs the fast kernel's back end (walks, thresholds) over ALL queries on its own row fragments, the
 // general kernel behind it for the few queries no front end could take (marker in the exchange row: every rank then does that query's candidate work itself, against the
 // replicated lists), the finish kernels, and the usual all-gather + merge of the per-shard top-n.  The candidate work of a batch is done ONCE per group, not once per rank.
-int group_predict_neighbours(srn_shard_group* g, const LaunchParams& p_in, bool resident, uint64_t* d_out_ids, double* d_out_scores, uint32_t* d_out_counts, hipStream_t user) {
-    const uint32_t G = G_of(g), nq = p_in.nq, n = p_in.how_many;
-    const bool local = g->kind == srn_shard_group::LOCAL;
-    LaunchParams p = p_in; p.out_ids = nullptr; p.out_scores = nullptr; p.out_counts = nullptr;
-    Slot& s = g->slot[g->calls & 1u];
-    const bool overlap = g->overlap && !local;
-    hipStream_t sx = overlap ? g->s_x : user;
-    const uint32_t rec_stride = device_prep_stride(p.max_len), xstride = p.k + 1u, per = (nq + G - 1) / G;
-    const size_t block_bytes = ((size_t)nq * n * 16 + (size_t)nq * 4 + 255) / 256 * 256, xblock = (size_t)per * xstride * 4;
+int group_predict_neighbours(srn_shard_group* g, const GroupBatch& b) {
+    Frame f(g, b, true);
+    Slot& s = f.s; const LaunchParams& p = f.p; const uint32_t G = f.G, nq = f.nq; const hipStream_t user = f.user, sx = f.sx;
+    const uint32_t rec_stride = device_prep_stride(p.max_len), per = (nq + G - 1) / G;
     // Streaming form (round 5): the exchange carries, instead of the neighbour slots, WHERE the neighbours sit in the query's posting lists -- a third of the bytes --, and
     // every rank's back end streams its fragments in posting order.  Chosen from rank-invariant inputs (batch shape, knobs) + what set_postings settled for this rank.
     // streaming or gather form (rank-invariant inputs only: the knob, the group's kind, the overlap switch, what set_postings agreed on): see Knobs::sback_stream_mode
@@ -322,145 +361,68 @@ int group_predict_neighbours(srn_shard_group* g, const LaunchParams& p_in, bool 
         want_stream = saved_ns > 8.5;
     }
     const uint32_t pstride = want_stream ? pstride_all : 0u;
-    const bool positions = pstride != 0u;
-    const size_t pblock = (size_t)per * pstride * 4;
     {
-        int rc = ensure(&s.xchg, &s.xchg_bytes, (size_t)G * xblock);
-        if (!rc && positions) rc = ensure(&s.xpos, &s.xpos_bytes, (size_t)G * pblock);
-        for (size_t i = 0; i < g->shards.size() && !rc; ++i) rc = ensure(&s.nrec[i], &s.nrec_bytes[i], (size_t)nq * rec_stride);
-        if (!rc) rc = ensure(&s.part, &s.part_bytes, (size_t)G * block_bytes);
+        int rc = s.buf[XCHG].ensure((size_t)G * per * (p.k + 1u) * 4);
+        if (!rc && pstride) rc = s.buf[XPOS].ensure((size_t)G * per * pstride * 4);
+        for (size_t i = 0; i < g->shards.size() && !rc; ++i) rc = s.nrec[i].ensure((size_t)nq * rec_stride);
+        if (!rc) rc = f.begin();
         if (rc) return rc;
     }
-    if (overlap) {
-        if (!resident) { HIP_TRY(hipEventRecord(g->e_in, user)); HIP_TRY(hipStreamWaitEvent(sx, g->e_in, 0)); }
-        if (g->calls >= 2) HIP_TRY(hipStreamWaitEvent(sx, s.e_done, 0));
-    }
-    if (g->calls >= 2) HIP_TRY(hipStreamWaitEvent(user, s.e_done, 0));
-    DeviceState* post = g->postings->dev;
+    // the front ends' neighbour slots, and what the ranks exchange: those, or the position records made from them
+    const ShardXchg slots{(uint32_t*)s.buf[XCHG].p, p.k + 1u, false}, sent = pstride ? ShardXchg{(uint32_t*)s.buf[XPOS].p, pstride, true} : slots;
+    const size_t sent_block = (size_t)per * sent.stride * 4;
     for (size_t i = 0; i < g->shards.size(); ++i) {
-        const uint32_t gi = local ? (uint32_t)i : (uint32_t)g->rank;
-        if (g->timing && i == 0) HIP_TRY(hipEventRecord(g->e_t[0], sx));
-        int rc = device_shard_nb_prep(g->shards[i]->dev, post, p, s.nrec[i], sx, &s.nord[i], &s.nord_bytes[i], &s.nord_ptr[i]); if (rc) return rc;
-        const uint32_t q_lo = std::min<uint64_t>(nq, (uint64_t)gi * per), q_hi = std::min<uint64_t>(nq, (uint64_t)q_lo + per);
-        rc = device_shard_nb_front(g->shards[i]->dev, g->shards[i]->flat, post, p, s.nrec[i], (uint32_t*)s.xchg, xstride, q_lo, q_hi, sx); if (rc) return rc;
-        if (positions) { rc = device_shard_nb_positions(g->shards[i]->dev, g->shards[i]->flat, post, p, s.nrec[i], (const uint32_t*)s.xchg, xstride, (uint32_t*)s.xpos, pstride, q_lo, q_hi, sx); if (rc) return rc; }
-        if (g->timing && i == 0) HIP_TRY(hipEventRecord(g->e_t[1], sx));
+        const ShardCall c = f.shard(i, sx);
+        if (f.timed && i == 0) HIP_TRY(hipEventRecord(g->e_t[0], sx));
+        int rc = device_shard_nb_prep(c, p, s.nrec[i].p, &s.nord[i].p, &s.nord[i].bytes, &s.nord_ptr[i]); if (rc) return rc;
+        ExtLists front{}; front.mode = 1; front.x = slots; front.q_lo = (uint32_t)std::min<uint64_t>(nq, (uint64_t)f.gi(i) * per);
+        LaunchParams pf = p; pf.nq = (uint32_t)std::min<uint64_t>(nq, (uint64_t)front.q_lo + per);   // this rank fronts the queries [q_lo, pf.nq)
+        rc = device_shard_nb_run(c, pf, s.nrec[i].p, front); if (rc) return rc;
+        if (sent.positions) { rc = device_shard_nb_positions(c, pf, s.nrec[i].p, slots, sent, front.q_lo); if (rc) return rc; }
+        if (f.timed && i == 0) HIP_TRY(hipEventRecord(g->e_t[1], sx));
     }
-    { int rc = all_gather_blocks(g, 0, positions ? s.xpos : s.xchg, positions ? pblock : xblock, sx); if (rc) return rc; }
-    if (overlap) { HIP_TRY(hipEventRecord(g->e_x, sx)); HIP_TRY(hipStreamWaitEvent(user, g->e_x, 0)); }
+    { int rc = all_gather_blocks(g, 0, (char*)sent.words, sent_block, sx); if (rc) return rc; }
+    { int rc = f.exchanged(); if (rc) return rc; }
     for (size_t i = 0; i < g->shards.size(); ++i) {
-        const uint32_t gi = local ? (uint32_t)i : (uint32_t)g->rank;
-        char* blk = s.part + (size_t)gi * block_bytes;
-        LaunchParams pi = p;
-        const bool direct = G == 1;   // one shard: its top-n IS the result
-        pi.out_ids = direct ? d_out_ids : (uint64_t*)blk; pi.out_scores = direct ? d_out_scores : (double*)(blk + (size_t)nq * n * 8); pi.out_counts = direct ? d_out_counts : (uint32_t*)(blk + (size_t)nq * n * 16);
-        if (g->timing && i == 0) HIP_TRY(hipEventRecord(g->e_t[2], user));
-        HIP_TRY(hipMemsetAsync(pi.out_ids, 0, (size_t)nq * n * 8, user)); HIP_TRY(hipMemsetAsync(pi.out_scores, 0, (size_t)nq * n * 8, user));
-        int rc = device_shard_nb_back(g->shards[i]->dev, g->shards[i]->flat, post, pi, s.nrec[i], (uint32_t*)(positions ? s.xpos : s.xchg), positions ? pstride : xstride, user, s.nord_ptr[i], positions); if (rc) return rc;
-        if (g->timing && i == 0) HIP_TRY(hipEventRecord(g->e_t[3], user));
+        LaunchParams pi;
+        { int rc = f.rows(i, &pi); if (rc) return rc; }
+        ExtLists back{}; back.mode = 2; back.x = sent; back.order = s.nord_ptr[i];
+        int rc = device_shard_nb_run(f.shard(i, user), pi, s.nrec[i].p, back); if (rc) return rc;
+        if (f.timed && i == 0) HIP_TRY(hipEventRecord(g->e_t[3], user));
     }
-    if (G > 1) {
-        int rc = all_gather_blocks(g, 1, s.part, block_bytes, user); if (rc) return rc;
-        if (g->timing) HIP_TRY(hipEventRecord(g->e_t[4], user));
-        HIP_TRY(launch_shard_merge_topn(user, s.part, block_bytes, G, nq, n, d_out_ids, d_out_scores, d_out_counts));
-        if (g->timing) HIP_TRY(hipEventRecord(g->e_t[5], user));
-    }
-    HIP_TRY(hipEventRecord(s.e_done, user));
-    if (g->timing) {   // (measurement runs only: synchronises)
-        HIP_TRY(hipEventSynchronize(s.e_done));
-        HIP_TRY(hipEventElapsedTime(&g->last_ms[0], g->e_t[0], g->e_t[1])); HIP_TRY(hipEventElapsedTime(&g->last_ms[1], g->e_t[2], g->e_t[3]));
-        g->last_ms[2] = 0.f; if (G > 1) HIP_TRY(hipEventElapsedTime(&g->last_ms[2], g->e_t[4], g->e_t[5]));
-    }
-    ++g->calls;
-    g->st_queries += nq; ++g->st_nb_batches; g->st_bytes_nb += G > 1 ? (uint64_t)(positions ? pblock : xblock) * (local ? G : 1) : 0;
-    g->st_bytes_results += G > 1 ? (uint64_t)block_bytes * (local ? G : 1) : 0;
+    { int rc = f.finish(); if (rc) return rc; }
+    ++g->st_nb_batches; g->st_bytes_nb += G > 1 ? (uint64_t)sent_block * (f.local ? G : 1) : 0;
     return SRN_OK;
 }
 
-int group_predict_locked(srn_shard_group* g, const uint64_t* d_items_flat, const uint32_t* d_q_off, size_t nq_, size_t max_len_hint, size_t k, size_t m, size_t how_many,
-                         unsigned flags, uint64_t* d_out_ids, double* d_out_scores, uint32_t* d_out_counts, hipStream_t user);
-// The group gives up: nothing of this rank may keep a peer waiting, and nothing further is issued.  RCCL: both communicators are aborted (ncclCommAbort ends their kernels
-// on this GPU; a peer blocked in the matching collective sees the connection go and fails, or runs into its own srn_shard_group_wait timeout); callbacks: the
-// application's transport is the application's to tear down -- it learns of the failure from the return code.
-void group_break(srn_shard_group* g, const std::string& why) {
-    if (g->broken) return;
-    g->broken = true; g->broken_why = why;
-    if (g->kind == srn_shard_group::RCCL)
-        for (auto& c : g->comm) if (c) { if (rccl()->CommAbort) rccl()->CommAbort(c); else if (rccl()->CommDestroy) rccl()->CommDestroy(c); c = nullptr; }
-}
-int group_predict(srn_shard_group* g, const uint64_t* d_items_flat, const uint32_t* d_q_off, size_t nq_, size_t max_len_hint, size_t k, size_t m, size_t how_many,
-                  unsigned flags, uint64_t* d_out_ids, double* d_out_scores, uint32_t* d_out_counts, hipStream_t user) {
-    std::lock_guard<std::mutex> lk(g->mu);
-    if (g->broken) return fail(SRN_ESTATE, "the shard group is unusable since an earlier batch failed (" + g->broken_why + "): free it and create a new one on every rank");
-    g->issued = false;
-    const int rc = group_predict_locked(g, d_items_flat, d_q_off, nq_, max_len_hint, k, m, how_many, flags, d_out_ids, d_out_scores, d_out_counts, user);
-    if (rc == SRN_OK) { if (g->e_last) (void)hipEventRecord(g->e_last, user); return rc; }
-    // A refusal that every rank makes alike before anything was issued (a parameter beyond a limit) leaves the group as it was; anything else -- a collective that failed,
-    // a HIP error, an allocation that failed on THIS rank -- may have left the peers in a collective of this batch, or be about to.
-    const bool peers = g->kind != srn_shard_group::LOCAL && g->world > 1;
-    if (g->issued || (peers && rc != SRN_EINVAL && rc != SRN_ERANGE)) { const std::string why = last_error_string(); group_break(g, why); set_error(why); }
-    return rc;
-}
-int group_predict_locked(srn_shard_group* g, const uint64_t* d_items_flat, const uint32_t* d_q_off, size_t nq_, size_t max_len_hint, size_t k, size_t m, size_t how_many,
-                         unsigned flags, uint64_t* d_out_ids, double* d_out_scores, uint32_t* d_out_counts, hipStream_t user) {
-    HIP_TRY(hipSetDevice(g->device));
-    const uint32_t G = G_of(g), nq = (uint32_t)nq_, ML = (uint32_t)max_len_hint, n = (uint32_t)how_many;
-    const bool local = g->kind == srn_shard_group::LOCAL;
-    const bool resident = (flags & SRN_FLAG_INPUTS_RESIDENT) != 0u;   // the inputs do not hang on the caller's stream: this batch's exchange may start while the previous batch still runs there
-    flags &= ~(unsigned)SRN_FLAG_INPUTS_RESIDENT;
-    LaunchParams p = launch_params(nq, k, m, n, flags, ML, d_items_flat, d_q_off, d_out_ids, d_out_scores, d_out_counts);
-    for (const srn_index* ix : g->shards)
-        if (!device_shard_lists_supported(ix->dev, ix->flat, p)) return group_predict_stages(g, p, d_out_ids, d_out_scores, d_out_counts, user);   // (every rank holds the same index parameters: the same choice everywhere)
-    if (g->postings && G > 1) {   // (the same index parameters and the same batch shape on every rank: the same choice everywhere.  A group of ONE shard gains nothing from
-                                 //  dividing the candidate work: its lists pipeline reads the lists in place and runs the fused kernel -- 23.4 against 10 + 16.7 ms per 2^20 queries)
-        // (rank-invariant inputs only: the batch shape, the index parameters, the whole index's longest row; that every shard has its packed rows was checked by set_postings.
-        //  ADVICE r4: a choice made from rank-local state would pair one rank's all-reduce with its peers' all-gather on the same communicator)
-        bool all = true;
-        for (const srn_index* ix : g->shards) all = all && device_fast_eligible(ix->dev, ix->flat, p, std::max<uint64_t>(1, g->postings_max_row_len));
-        if (all) return group_predict_neighbours(g, p, resident, d_out_ids, d_out_scores, d_out_counts, user);
-    }
-    p.out_ids = nullptr; p.out_scores = nullptr; p.out_counts = nullptr;
-    Slot& s = g->slot[g->calls & 1u];
-    const bool overlap = g->overlap && !local;
-    hipStream_t sx = overlap ? g->s_x : user;
-    // ---- buffers (grow-only; growing synchronises the device, like every hipFree) ----
-    const uint32_t rec_stride = device_prep_stride(ML);
-    const size_t block_bytes = ((size_t)nq * n * 16 + (size_t)nq * 4 + 255) / 256 * 256;
+// The LISTS pipeline (the head comment of this file): posting lists and rows both sharded; the kept list prefixes are exchanged, every rank serves every query over them.
+int group_predict_lists(srn_shard_group* g, const GroupBatch& b) {
+    Frame f(g, b, true);
+    Slot& s = f.s; const LaunchParams& p = f.p; const uint32_t G = f.G, nq = f.nq, ML = p.max_len; const hipStream_t user = f.user, sx = f.sx;
+    unsigned long long* tot_host_dev = nullptr; HIP_TRY(hipHostGetDevicePointer((void**)&tot_host_dev, s.tot_host, 0));
     {
         int rc = SRN_OK;
-        for (size_t i = 0; i < g->shards.size() && !rc; ++i) rc = ensure(&s.pos[i], &s.pos_bytes[i], (size_t)nq * ML * 16);
-        if (!rc) rc = ensure(&s.head, &s.head_bytes, (size_t)nq * 12 * 2);
-        if (!rc) rc = ensure(&s.kept, &s.kept_bytes, (size_t)G * nq * ML * 4);
-        if (!rc) rc = ensure(&s.tot, &s.tot_bytes, (size_t)nq * 4);
-        if (!rc) rc = ensure(&s.off, &s.off_bytes, (size_t)G * nq * 8);
-        if (!rc) rc = ensure(&s.small, &s.small_bytes, (size_t)G * 16 + (size_t)G * ((nq + 1023) / 1024) * 8);
-        if (!rc) rc = ensure(&s.records, &s.records_bytes, (size_t)nq * rec_stride);
-        if (!rc) rc = ensure(&s.part, &s.part_bytes, (size_t)G * block_bytes);
+        for (size_t i = 0; i < g->shards.size() && !rc; ++i) rc = s.pos[i].ensure((size_t)nq * ML * 16);
+        if (!rc) rc = s.ensure({{HEAD, (size_t)nq * 12 * 2}, {KEPT, (size_t)G * nq * ML * 4}, {TOT, (size_t)nq * 4}, {OFF, (size_t)G * nq * 8}, {SMALL, (size_t)G * 16 + (size_t)G * ((nq + 1023) / 1024) * 8},
+                                {RECORDS, (size_t)nq * device_prep_stride(ML)}});
+        if (!rc) rc = f.begin();
         if (rc) return rc;
     }
-    int* head = (int*)s.head; uint32_t* kept_g = (uint32_t*)s.kept; long long* off_g = (long long*)s.off;
-    unsigned long long* tot_dev = (unsigned long long*)s.small; unsigned long long* base_dev = tot_dev + G;
-    unsigned long long* tot_host_dev = nullptr; HIP_TRY(hipHostGetDevicePointer((void**)&tot_host_dev, s.tot_host, 0));
-    // ---- exchange stream: ordered behind the caller's inputs and behind the batch that used this slot two calls ago ----
-    if (overlap) {
-        if (!resident) { HIP_TRY(hipEventRecord(g->e_in, user)); HIP_TRY(hipStreamWaitEvent(sx, g->e_in, 0)); }   // (behind everything on the caller's stream: correct, but no overlap)
-        if (g->calls >= 2) HIP_TRY(hipStreamWaitEvent(sx, s.e_done, 0));
-    }
-    if (g->calls >= 2) HIP_TRY(hipStreamWaitEvent(user, s.e_done, 0));   // (callers may alternate between streams: the slot's previous user may have run on another one)
-    if (g->timing) HIP_TRY(hipEventRecord(g->e_t[0], sx));
+    int* head = (int*)s.buf[HEAD].p; uint32_t* kept_g = (uint32_t*)s.buf[KEPT].p; long long* off_g = (long long*)s.buf[OFF].p;
+    unsigned long long* tot_dev = (unsigned long long*)s.buf[SMALL].p; unsigned long long* base_dev = tot_dev + G;
+    if (f.timed) HIP_TRY(hipEventRecord(g->e_t[0], sx));
     // head: every shard's view of the evolving positions, the local cuts -> global cuts
     for (size_t i = 0; i < g->shards.size(); ++i) {
         int* h_i = i == 0 ? head : head + (size_t)nq * 3;
-        int rc = device_shard_lists_head(g->shards[i]->dev, p, s.pos[i], h_i, sx); if (rc) return rc;
+        int rc = device_shard_lists_head(f.shard(i, sx), p, s.pos[i].p, h_i); if (rc) return rc;
         if (i > 0) HIP_TRY(launch_shard_max(sx, head, h_i, (size_t)nq * 3));
     }
     { int rc = all_reduce_max_i32(g, 0, head, (size_t)nq * 3, sx); if (rc) return rc; }
     // count: the entries at or above the cut, per owned list -> every rank knows every shard's counts
     for (size_t i = 0; i < g->shards.size(); ++i) {
-        const uint32_t gi = local ? (uint32_t)i : (uint32_t)g->rank;
-        int rc = device_shard_lists_count(g->shards[i]->dev, p, s.pos[i], head, kept_g + (size_t)gi * nq * ML, (int*)s.tot, sx); if (rc) return rc;
+        int rc = device_shard_lists_count(f.shard(i, sx), p, s.pos[i].p, head, kept_g + (size_t)f.gi(i) * nq * ML, (int*)s.buf[TOT].p); if (rc) return rc;
     }
-    { int rc = all_gather_blocks(g, 0, s.kept, (size_t)nq * ML * 4, sx); if (rc) return rc; }
+    { int rc = all_gather_blocks(g, 0, (char*)kept_g, (size_t)nq * ML * 4, sx); if (rc) return rc; }
     HIP_TRY(launch_shard_offsets(sx, kept_g, nq, ML, G, off_g, tot_dev, tot_host_dev, base_dev + G));
     HIP_TRY(hipStreamSynchronize(sx));   // the batch's one host synchronisation (with the exchange stream: only this batch's small kernels are waited for)
     unsigned long long base[64], cnt_b[64], off_b[64], total = 0;
@@ -472,48 +434,71 @@ int group_predict_locked(srn_shard_group* g, const uint64_t* d_items_flat, const
     const bool direct = G == 1 && !g->no_direct;
     uint32_t* lists_g = nullptr;
     if (!direct) {
-        if (s.lists_bytes < total * 4 + 256) { int rc = ensure(&s.lists, &s.lists_bytes, (size_t)(total * 4 + total / 2 + 4096)); if (rc) return rc; }   // (head room: the totals of like batches differ by a per cent or two)
+        Buf& lists = s.buf[LISTS];
+        if (lists.bytes < total * 4 + 256) { int rc = lists.ensure((size_t)(total * 4 + total / 2 + 4096)); if (rc) return rc; }   // (head room: the totals of like batches differ by a per cent or two)
         HIP_TRY(hipMemcpyAsync(base_dev, s.tot_host + G, (size_t)G * 8, hipMemcpyHostToDevice, sx));
-        lists_g = (uint32_t*)s.lists;
+        lists_g = (uint32_t*)lists.p;
         for (size_t i = 0; i < g->shards.size(); ++i) {
-            const uint32_t gi = local ? (uint32_t)i : (uint32_t)g->rank;
-            int rc = device_shard_lists_copy(g->shards[i]->dev, p, s.pos[i], kept_g + (size_t)gi * nq * ML, off_g + (size_t)gi * nq, lists_g + base[gi], sx); if (rc) return rc;
+            const uint32_t gi = f.gi(i);
+            int rc = device_shard_lists_copy(f.shard(i, sx), p, s.pos[i].p, kept_g + (size_t)gi * nq * ML, off_g + (size_t)gi * nq, lists_g + base[gi]); if (rc) return rc;
         }
-        { int rc = all_gather_v(g, 0, s.lists, off_b, cnt_b, sx); if (rc) return rc; }
+        { int rc = all_gather_v(g, 0, lists.p, off_b, cnt_b, sx); if (rc) return rc; }
     }
-    if (g->timing) HIP_TRY(hipEventRecord(g->e_t[1], sx));
-    if (overlap) { HIP_TRY(hipEventRecord(g->e_x, sx)); HIP_TRY(hipStreamWaitEvent(user, g->e_x, 0)); }
+    if (f.timed) HIP_TRY(hipEventRecord(g->e_t[1], sx));   // ([0]..[1] = head + count + copy of ALL local shards incl. the offsets kernels and the one host synchronisation)
+    { int rc = f.exchanged(); if (rc) return rc; }
     // ---- caller's stream: the unsharded launch sequence over every local shard's row fragments ----
     for (size_t i = 0; i < g->shards.size(); ++i) {
-        const uint32_t gi = local ? (uint32_t)i : (uint32_t)g->rank;
-        char* blk = s.part + (size_t)gi * block_bytes;
-        LaunchParams pi = p;
-        const bool direct = G == 1;   // one shard: its top-n IS the result
-        pi.out_ids = direct ? d_out_ids : (uint64_t*)blk; pi.out_scores = direct ? d_out_scores : (double*)(blk + (size_t)nq * n * 8); pi.out_counts = direct ? d_out_counts : (uint32_t*)(blk + (size_t)nq * n * 16);
-        if (g->timing && i == 0) HIP_TRY(hipEventRecord(g->e_t[2], user));
-        HIP_TRY(hipMemsetAsync(pi.out_ids, 0, (size_t)nq * n * 8, user)); HIP_TRY(hipMemsetAsync(pi.out_scores, 0, (size_t)nq * n * 8, user));
-        int rc = device_shard_lists_predict(g->shards[i]->dev, g->shards[i]->flat, pi, G, kept_g, off_g, 0ull, lists_g, head, s.pos[i], s.records, user, base_dev, direct); if (rc) return rc;
-        if (g->timing && i == 0) HIP_TRY(hipEventRecord(g->e_t[3], user));
+        LaunchParams pi;
+        { int rc = f.rows(i, &pi); if (rc) return rc; }
+        const ShardLists l{G, kept_g, off_g, lists_g, base_dev, head, s.pos[i].p, G == 1};   // (G == 1, not `direct`: under SRN_GROUP_NO_DIRECT the copy + exchange run, the launch sequence still reads the one shard's lists in place)
+        int rc = device_shard_lists_predict(f.shard(i, user), pi, l, s.buf[RECORDS].p); if (rc) return rc;
+        if (f.timed && i == 0) HIP_TRY(hipEventRecord(g->e_t[3], user));
     }
-    if (G > 1) {
-        int rc = all_gather_blocks(g, 1, s.part, block_bytes, user); if (rc) return rc;
-        if (g->timing) HIP_TRY(hipEventRecord(g->e_t[4], user));
-        HIP_TRY(launch_shard_merge_topn(user, s.part, block_bytes, G, nq, n, d_out_ids, d_out_scores, d_out_counts));
-        if (g->timing) HIP_TRY(hipEventRecord(g->e_t[5], user));
-    }
-    HIP_TRY(hipEventRecord(s.e_done, user));
-    if (g->timing) {   // (measurement runs only: synchronises.  [0] = head + count + copy of ALL local shards incl. the offsets kernels and the one host synchronisation)
-        HIP_TRY(hipEventSynchronize(s.e_done));
-        HIP_TRY(hipEventElapsedTime(&g->last_ms[0], g->e_t[0], g->e_t[1])); HIP_TRY(hipEventElapsedTime(&g->last_ms[1], g->e_t[2], g->e_t[3]));
-        g->last_ms[2] = 0.f; if (G > 1) HIP_TRY(hipEventElapsedTime(&g->last_ms[2], g->e_t[4], g->e_t[5]));
-    }
-    ++g->calls;
-    const uint32_t me = local ? 0u : (uint32_t)g->rank;
-    g->st_queries += nq; g->st_bytes_head += (uint64_t)nq * 12; g->st_bytes_kept += (uint64_t)nq * ML * 4 * (local ? G : 1);
-    { uint64_t mine = 0, mx = 0; for (uint32_t i = 0; i < G; ++i) { mx = std::max<uint64_t>(mx, s.tot_host[i]); if (local || i == me) mine += s.tot_host[i]; }
+    { int rc = f.finish(); if (rc) return rc; }
+    const uint32_t me = f.local ? 0u : (uint32_t)g->rank;
+    g->st_bytes_head += (uint64_t)nq * 12; g->st_bytes_kept += (uint64_t)nq * ML * 4 * (f.local ? G : 1);
+    { uint64_t mine = 0, mx = 0; for (uint32_t i = 0; i < G; ++i) { mx = std::max<uint64_t>(mx, s.tot_host[i]); if (f.local || i == me) mine += s.tot_host[i]; }
       if (!direct) { g->st_bytes_lists += mine * 4; g->st_lists_max += mx * 4; } }
-    g->st_bytes_results += G > 1 ? (uint64_t)block_bytes * (local ? G : 1) : 0;
     return SRN_OK;
+}
+
+int group_predict_locked(srn_shard_group* g, const GroupBatch& in) {
+    GroupBatch b = in;
+    HIP_TRY(hipSetDevice(g->device));
+    b.resident = (b.p.flags & SRN_FLAG_INPUTS_RESIDENT) != 0u;   // the inputs do not hang on the caller's stream: this batch's exchange may start while the previous batch still runs there
+    b.p.flags &= ~(unsigned)SRN_FLAG_INPUTS_RESIDENT;
+    for (const srn_index* ix : g->shards)
+        if (!device_shard_lists_supported(ix->dev, ix->flat, b.p)) return group_predict_stages(g, b);   // (every rank holds the same index parameters: the same choice everywhere)
+    if (g->postings && G_of(g) > 1) {   // (the same index parameters and the same batch shape on every rank: the same choice everywhere.  A group of ONE shard gains nothing from
+                                        //  dividing the candidate work: its lists pipeline reads the lists in place and runs the fused kernel -- 23.4 against 10 + 16.7 ms per 2^20 queries)
+        // (rank-invariant inputs only: the batch shape, the index parameters, the whole index's longest row; that every shard has its packed rows was checked by set_postings.
+        //  ADVICE r4: a choice made from rank-local state would pair one rank's all-reduce with its peers' all-gather on the same communicator)
+        bool all = true;
+        for (const srn_index* ix : g->shards) all = all && device_fast_eligible(ix->dev, ix->flat, b.p, std::max<uint64_t>(1, g->postings_max_row_len));
+        if (all) return group_predict_neighbours(g, b);
+    }
+    return group_predict_lists(g, b);
+}
+// The group gives up: nothing of this rank may keep a peer waiting, and nothing further is issued.  RCCL: both communicators are aborted (ncclCommAbort ends their kernels
+// on this GPU; a peer blocked in the matching collective sees the connection go and fails, or runs into its own srn_shard_group_wait timeout); callbacks: the
+// application's transport is the application's to tear down -- it learns of the failure from the return code.
+void group_break(srn_shard_group* g, const std::string& why) {
+    if (g->broken) return;
+    g->broken = true; g->broken_why = why;
+    if (g->kind == srn_shard_group::RCCL)
+        for (auto& c : g->comm) if (c) { if (rccl()->CommAbort) rccl()->CommAbort(c); else if (rccl()->CommDestroy) rccl()->CommDestroy(c); c = nullptr; }
+}
+int group_predict(srn_shard_group* g, const GroupBatch& b) {
+    std::lock_guard<std::mutex> lk(g->mu);
+    if (g->broken) return fail(SRN_ESTATE, "the shard group is unusable since an earlier batch failed (" + g->broken_why + "): free it and create a new one on every rank");
+    g->issued = false;
+    const int rc = group_predict_locked(g, b);
+    if (rc == SRN_OK) { if (g->e_last) (void)hipEventRecord(g->e_last, b.stream); return rc; }
+    // A refusal that every rank makes alike before anything was issued (a parameter beyond a limit) leaves the group as it was; anything else -- a collective that failed,
+    // a HIP error, an allocation that failed on THIS rank -- may have left the peers in a collective of this batch, or be about to.
+    const bool peers = g->kind != srn_shard_group::LOCAL && g->world > 1;
+    if (g->issued || (peers && rc != SRN_EINVAL && rc != SRN_ERANGE)) { const std::string why = last_error_string(); group_break(g, why); set_error(why); }
+    return rc;
 }
 }  // namespace
 
@@ -603,7 +588,7 @@ int srn_shard_group_predict_batch(srn_shard_group_t* g, const uint64_t* d_items_
         if (!d_items_flat || !d_q_off || !d_out_ids || !d_out_scores || !d_out_counts) return fail(SRN_EINVAL, "null buffer");
         if (nq > 0x7FFFFFFFull) return fail(SRN_ERANGE, "too many queries in one batch");
         if (max_len_hint == 0 || max_len_hint > SRN_MAX_SESSION_LEN) return fail(SRN_ERANGE, "max_len_hint out of range");
-        return group_predict(g, d_items_flat, d_q_off, nq, max_len_hint, k, m, how_many, flags, d_out_ids, d_out_scores, d_out_counts, (hipStream_t)stream); });
+        return group_predict(g, GroupBatch{launch_params(nq, k, m, how_many, flags, max_len_hint, d_items_flat, d_q_off, d_out_ids, d_out_scores, d_out_counts), false, (hipStream_t)stream}); });
 }
 
 int srn_debug_shard_group_times(const srn_shard_group_t* g, double* out3) {   // SRN_GROUP_TIMING=1: ms of local shard 0's prep + front end, back end (incl. general + finish kernels), merge

@@ -3,6 +3,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <mutex>
+#include <new>
 #include <string>
 #include <vector>
 
@@ -141,11 +142,13 @@ void device_refresh_fast_bounds(DeviceState* d, const FlatIndex& ix);   // idf b
 void reload_knobs();                                                     // re-read the SRN_* test / experiment knobs from the environment
 uint64_t device_bytes(const DeviceState* d);
 // item-sharded index, lists mode: prep records (PrepHead + max_len * PrepItem per query) written against a gathered posting buffer
+// the neighbours pipeline's exchange buffer as one rank's kernels see it: `stride` words per query; positions: position records (device_shard_nb_positions: the
+// streaming back end's format), not neighbour slots
+struct ShardXchg { uint32_t* words = nullptr; uint32_t stride = 0; bool positions = false; };
 struct ExtLists { const char* prep; uint32_t prep_stride; const uint32_t* post_rank;
-                  // the shard group's neighbours pipeline: mode 1 = front end only (neighbour lists of the queries [q_lo, nq) -> xchg), 2 = back end (neighbour lists <- xchg)
-                  int mode = 0; uint32_t* xchg = nullptr; uint32_t xchg_stride = 0; uint32_t q_lo = 0;
-                  const unsigned long long* order = nullptr;     // mode 2: the batch's serving order (device_shard_nb_prep sorted it), or null
-                  bool positions = false; };                     // mode 2: xchg holds position records (device_shard_nb_positions), not neighbour slots: the streaming back end
+                  // the shard group's neighbours pipeline: mode 1 = front end only (neighbour lists of the queries [q_lo, nq) -> x), 2 = back end (neighbour lists <- x)
+                  int mode = 0; ShardXchg x; uint32_t q_lo = 0;
+                  const unsigned long long* order = nullptr; };   // mode 2: the batch's serving order (device_shard_nb_prep sorted it), or null
 // ---- the predict call.  Every entry takes the caller's OWN how_many (and, on device buffers, the caller's own rows) in LaunchParams ----
 inline LaunchParams launch_params(size_t nq, size_t k, size_t m, size_t how_many, unsigned flags, size_t max_len, const uint64_t* items_flat = nullptr, const uint32_t* q_off = nullptr,
                                   uint64_t* out_ids = nullptr, double* out_scores = nullptr, uint32_t* out_counts = nullptr) {
@@ -169,6 +172,12 @@ int device_predict_device(DeviceState* d, const FlatIndex& ix, const LaunchParam
 // host buffers; returns with the rows in place.  Small batches take the latency path (blocking_wait: it sleeps on an interrupt instead of spinning), larger ones the chunked
 // pipeline; stats, the neighbour dump and a rule that filters go through one staged workspace (a rule together with stats or the dump: SRN_EINVAL)
 int device_predict_host(DeviceState* d, const FlatIndex& ix, const LaunchParams& p, const HostRows& rows, const RowRule& rule = {}, bool blocking_wait = false);
+template <typename F> inline int guarded(F f) {   // every extern "C" entry that can throw: never let an exception cross the C boundary
+    try { return f(); }
+    catch (const std::bad_alloc&) { return fail(SRN_ENOMEM, "out of host memory"); }
+    catch (const std::exception& e) { return fail(SRN_EINVAL, std::string("internal error: ") + e.what()); }
+    catch (...) { return fail(SRN_EINVAL, "internal error"); }
+}
 // the unserved-query mark of a call's count words
 inline int check_all_served(const uint32_t* counts, size_t nq) {
     for (size_t q = 0; q < nq; ++q) if (counts[q] == 0xFFFFFFFFu) return fail(SRN_ERANGE, "a query exceeded the kernel's table limits");
@@ -205,24 +214,27 @@ int device_sback_attach_postings(DeviceState* d, DeviceState* post, uint64_t n_p
 bool device_sback_streams(const DeviceState* d);
 bool device_sback_wanted(const DeviceState* d);   // this shard has the wave-per-query back end's rows and the streaming form is not switched off: set_postings expects the copy
 uint64_t device_sback_launches(const DeviceState* d);
-// neighbours pipeline (replicated postings `post`: the whole index's dictionary + lists): prep records of ALL queries (lists looked up in `post`, dense idx in this shard's
-// table), then the front end over the queries [q_lo, q_hi) -> xchg, or the back end over all of them <- xchg
-int device_shard_nb_prep(DeviceState* d, DeviceState* post, const LaunchParams& p, char* records, void* stream, char** order_buf = nullptr, size_t* order_bytes = nullptr,
-                         const unsigned long long** order_out = nullptr);   // order_buf (grow-only, the caller's): the batch's serving order is sorted into it, *order_out = where (null: batch too small)
-int device_shard_nb_front(DeviceState* d, const FlatIndex& ix, DeviceState* post, const LaunchParams& p, const char* records, uint32_t* xchg, uint32_t xchg_stride, uint32_t q_lo, uint32_t q_hi, void* stream);
-int device_shard_nb_back(DeviceState* d, const FlatIndex& ix, DeviceState* post, const LaunchParams& p, const char* records, uint32_t* xchg, uint32_t xchg_stride, void* stream,
-                         const unsigned long long* order = nullptr, bool positions = false);
-int device_shard_nb_positions(DeviceState* d, const FlatIndex& ix, DeviceState* post, const LaunchParams& p, const char* records, const uint32_t* xin, uint32_t in_stride, uint32_t* xout, uint32_t out_stride,
-                              uint32_t q_lo, uint32_t q_hi, void* stream);
+// One local shard of a shard group, as every device_shard_* step below takes it (device buffers, asynchronous on `stream`).  post: the replicated postings of the
+// neighbours pipeline (the whole index's dictionary + lists), null otherwise
+struct ShardCall { DeviceState* d; const FlatIndex* ix; DeviceState* post; void* stream; };
+// neighbours pipeline: prep records of ALL queries (lists looked up in `post`, dense idx in this shard's table); order_buf (grow-only, the caller's): the batch's serving
+// order is sorted into it, *order_out = where (null: batch too small)
+int device_shard_nb_prep(const ShardCall& c, const LaunchParams& p, char* records, char** order_buf, size_t* order_bytes, const unsigned long long** order_out);
+// ... then the fast kernel over them: ext.mode 1 = the front end over the queries [ext.q_lo, p.nq) -> ext.x, 2 = the back end over all of them <- ext.x (prep, prep_stride
+// and post_rank are filled in here)
+int device_shard_nb_run(const ShardCall& c, const LaunchParams& p, const char* records, ExtLists ext);
+// the fronting rank's neighbour lists [q_lo, p.nq) of `in` -> position records in `out`
+int device_shard_nb_positions(const ShardCall& c, const LaunchParams& p, const char* records, const ShardXchg& in, const ShardXchg& out, uint32_t q_lo);
 uint32_t device_shard_nb_positions_stride(const LaunchParams& p);   // 0: no streaming form for this batch shape / these knobs (rank-invariant)
 uint32_t device_prep_stride(uint32_t max_len);
-int device_shard_lists_head(DeviceState* d, const LaunchParams& p, void* pos, int* head, void* stream);
-int device_shard_lists_count(DeviceState* d, const LaunchParams& p, const void* pos, const int* head, uint32_t* kept, int* tot, void* stream);
-int device_shard_lists_copy(DeviceState* d, const LaunchParams& p, const void* pos, const uint32_t* kept, const long long* off, uint32_t* out, void* stream);
-int device_shard_lists_predict(DeviceState* d, const FlatIndex& ix, const LaunchParams& p, uint32_t n_shards, const uint32_t* kept_g, const long long* off_g,
-                               unsigned long long shard_stride, const uint32_t* lists_g, const int* head, const void* pos_local, char* records, void* stream,
-                               const unsigned long long* shard_base = nullptr, bool direct = false);   // shard_base [n_shards] (device): the shards' segment starts (null: g * shard_stride); direct: a group of one shard reads its lists in place (lists_g = null)
-int device_shard_stage(DeviceState* d, const FlatIndex& ix, int stage, const LaunchParams& p, const ShardIO& sh, void* stream);
+int device_shard_lists_head(const ShardCall& c, const LaunchParams& p, void* pos, int* head);
+int device_shard_lists_count(const ShardCall& c, const LaunchParams& p, const void* pos, const int* head, uint32_t* kept, int* tot);
+int device_shard_lists_copy(const ShardCall& c, const LaunchParams& p, const void* pos, const uint32_t* kept, const long long* off, uint32_t* out);
+// what the exchanges of the lists pipeline left for the prep records: [n_shards][nq * max_len] kept counts, [n_shards][nq] offsets, the gathered prefixes with shard g's
+// segment at shard_base[g] (device), the global cuts, this shard's positions.  direct: a group of one shard reads its lists in place (lists_g = null)
+struct ShardLists { uint32_t n_shards; const uint32_t* kept_g; const long long* off_g; const uint32_t* lists_g; const unsigned long long* shard_base; const int* head; const void* pos_local; bool direct; };
+int device_shard_lists_predict(const ShardCall& c, const LaunchParams& p, const ShardLists& l, char* records);
+int device_shard_stage(const ShardCall& c, int stage, const LaunchParams& p, const ShardIO& sh);
 int device_slot_bytes(DeviceState* d, const FlatIndex& ix, uint32_t max_len, uint32_t* num_bits = nullptr);
 // ---- the persistent latency path (round 6): resident workgroups that serve srn_predict's call shape without a launch ----
 // lanes: resident workgroups of the lean form (sessions of <= 4 items); max_items >= 5: as many of the MID form (5..10 items) beside them; idle_ms: a resident workgroup

@@ -643,7 +643,7 @@ static int enqueue_shard_front(BatchCall& c) {
     if (ext->q_lo >= p.nq) return SRN_OK;
     p.prep = ext->prep; p.prep_stride = c.pl.prep_stride;
     FastParams fp = fast_params(c.d, FastBuffers{}, c.pl.fast);
-    fp.xchg = ext->xchg; fp.xchg_stride = ext->xchg_stride; fp.q_base = ext->q_lo;
+    fp.xchg = ext->x.words; fp.xchg_stride = ext->x.stride; fp.q_base = ext->q_lo;
     const uint64_t cnt = p.nq - ext->q_lo, res_wg = (uint64_t)c.d->n_cu * F_WG_PER_CU;
     const uint32_t grid_front = (uint32_t)std::min<uint64_t>(cnt, std::min<uint64_t>(res_wg * 64, std::max<uint64_t>(res_wg * 16, cnt / 12)));
     HIP_TRY(launch_fast(FastForm::Front, dim3(grid_front), c.st, c.di, p, fp, c.pl.kn.debug));
@@ -654,7 +654,7 @@ static int enqueue_shard_back(BatchCall& c) {
     DeviceState* d = c.d; Workspace* w = c.w; const ExtLists* ext = c.ext; const LaunchParams& p = c.p; const Knobs& kn = c.pl.kn; FastParams& fp = c.fp;
     SBackParams sbp = d->sback;
     // the streaming form where the shard holds its fragments in the posting order of the very lists the records were written against (9 waves per CU: 16.8 KB each)
-    const bool stream = ext->positions;
+    const bool stream = ext->x.positions;
     if (stream && !(d->sb_frag_post && d->sb_post_for == ext->post_rank)) return fail(SRN_ESTATE, "the batch's neighbours came as posting positions, but this shard does not hold its fragments in posting order");
     const uint64_t slots = (uint64_t)d->n_cu * (stream ? 9 : 12);
     uint32_t grid_b = (uint32_t)std::min<uint64_t>(p.nq, slots * (kn.grid_mult_set ? (uint32_t)kn.grid_mult : stream ? 4 : 16));   // (gather form, round 6: 1 / 2 / 4 / 8 / 16 / 32 waves per slot = 1.295 / 1.247 / 1.191 / 1.148 / 1.115 / 1.114 ms -- the tail of a persistent grid costs more than the first query of a wave, which has no prefetched record)
@@ -685,7 +685,7 @@ static int enqueue_fast_tiers(BatchCall& c) {
     FastParams& fp = c.fp;
     fp = fast_params(d, w, pl.fast, p.nq, (pl.fast.mid_tier ? TIER_MID : 0u) | (big_tier ? TIER_BIGQ : 0u) | (pl.fast.long_tier ? TIER_LONG : 0u));
     const bool back = ext && ext->mode == 2;   // neighbour lists from the exchange buffer (any rank's front end), this shard's rows
-    if (back) { fp.xchg = ext->xchg; fp.xchg_stride = ext->xchg_stride; }
+    if (back) { fp.xchg = ext->x.words; fp.xchg_stride = ext->x.stride; }
     fp.order = pl.ordered ? c.ob.keys_out : back ? ext->order : nullptr;
     fp.order_dups = pl.cache ? c.ob.n_skip : pl.dedup ? c.ob.dd.n_dup : nullptr;   // (the cache's count: its hits + the merged queries)
     const uint32_t grid_fo = fp.order ? std::max<uint32_t>(8u, pl.grid_fast / 8u * 8u) : pl.grid_fast;   // (an ordered launch walks an eighth of the order per XCD: the grid is a multiple of 8)
@@ -876,10 +876,11 @@ static int predict_ext(DeviceState* d, const FlatIndex& ix, const LaunchParams& 
     return predict_core(d, ix, p, kind);
 }
 
-// One stage of the item-sharded pipeline (device buffers, asynchronous on `stream`); see ShardIO.  Like the unsharded launch sequence, a stage has a second pass
-// with its tables in global memory for the queries whose session or item table does not fit LDS (numerator slots only: with position sets the shard group runs the
-// lists pipeline, and the stand-alone srn_shard_stage_* calls mark such a query 0xFFFFFFFF as before).
-int device_shard_stage(DeviceState* d, const FlatIndex& ix, int stage, const LaunchParams& p_in, const ShardIO& sh, void* stream) {
+// One stage of the item-sharded pipeline (see ShardIO, ShardCall).  Like the unsharded launch sequence, a stage has a second pass with its tables in global memory for
+// the queries whose session or item table does not fit LDS (numerator slots only: with position sets the shard group runs the lists pipeline); a query that fits
+// neither pass comes back marked 0xFFFFFFFF.
+int device_shard_stage(const ShardCall& c, int stage, const LaunchParams& p_in, const ShardIO& sh) {
+    DeviceState* d = c.d; const FlatIndex& ix = *c.ix; void* stream = c.stream;
     HIP_TRY(hipSetDevice(d->device));
     LaunchParams p = p_in;
     if (p.nq == 0) return SRN_OK;
@@ -933,65 +934,63 @@ bool device_fast_eligible(DeviceState* d, const FlatIndex& ix, const LaunchParam
            p.how_many <= 24 && (p.flags & ~(unsigned)SRN_FLAG_BUSINESS_LOGIC) == 0 && p.stats == nullptr && p.nb_rank == nullptr && p.max_len <= 8;
 }
 uint32_t device_prep_stride(uint32_t max_len) { return prep_stride_of(max_len); }
-int device_shard_lists_head(DeviceState* d, const LaunchParams& p, void* pos, int* head, void* stream) {
-    HIP_TRY(hipSetDevice(d->device));
+int device_shard_lists_head(const ShardCall& c, const LaunchParams& p, void* pos, int* head) {
+    HIP_TRY(hipSetDevice(c.d->device));
     if (p.nq == 0) return SRN_OK;
-    HIP_TRY(launch_shard_lists_head((hipStream_t)stream, d->di, p.items_flat, p.q_off, p.nq, p.m, p.max_len, (ShardPos*)pos, head));
+    HIP_TRY(launch_shard_lists_head((hipStream_t)c.stream, c.d->di, p.items_flat, p.q_off, p.nq, p.m, p.max_len, (ShardPos*)pos, head));
     return SRN_OK;
 }
-int device_shard_lists_count(DeviceState* d, const LaunchParams& p, const void* pos, const int* head, uint32_t* kept, int* tot, void* stream) {
-    HIP_TRY(hipSetDevice(d->device));
+int device_shard_lists_count(const ShardCall& c, const LaunchParams& p, const void* pos, const int* head, uint32_t* kept, int* tot) {
+    HIP_TRY(hipSetDevice(c.d->device));
     if (p.nq == 0) return SRN_OK;
-    HIP_TRY(launch_shard_lists_count((hipStream_t)stream, d->di, p.q_off, p.nq, p.max_len, (const ShardPos*)pos, head, kept, tot));
+    HIP_TRY(launch_shard_lists_count((hipStream_t)c.stream, c.d->di, p.q_off, p.nq, p.max_len, (const ShardPos*)pos, head, kept, tot));
     return SRN_OK;
 }
-int device_shard_lists_copy(DeviceState* d, const LaunchParams& p, const void* pos, const uint32_t* kept, const long long* off, uint32_t* out, void* stream) {
-    HIP_TRY(hipSetDevice(d->device));
+int device_shard_lists_copy(const ShardCall& c, const LaunchParams& p, const void* pos, const uint32_t* kept, const long long* off, uint32_t* out) {
+    HIP_TRY(hipSetDevice(c.d->device));
     if (p.nq == 0) return SRN_OK;
-    HIP_TRY(launch_shard_lists_copy((hipStream_t)stream, d->di, p.nq, p.max_len, (const ShardPos*)pos, kept, off, out));
+    HIP_TRY(launch_shard_lists_copy((hipStream_t)c.stream, c.d->di, p.nq, p.max_len, (const ShardPos*)pos, kept, off, out));
     return SRN_OK;
 }
-int device_shard_lists_predict(DeviceState* d, const FlatIndex& ix, const LaunchParams& p, uint32_t n_shards, const uint32_t* kept_g, const long long* off_g,
-                               unsigned long long shard_stride, const uint32_t* lists_g, const int* head, const void* pos_local, char* records, void* stream,
-                               const unsigned long long* shard_base, bool direct) {
+int device_shard_lists_predict(const ShardCall& c, const LaunchParams& p, const ShardLists& l, char* records) {
+    DeviceState* d = c.d; const FlatIndex& ix = *c.ix;
     HIP_TRY(hipSetDevice(d->device));
     if (p.nq == 0) return SRN_OK;
-    if (n_shards != ix.n_shards) return fail(SRN_EINVAL, "n_shards differs from the number of shards this index was cut into");
+    if (l.n_shards != ix.n_shards) return fail(SRN_EINVAL, "n_shards differs from the number of shards this index was cut into");
     if (!device_shard_lists_supported(d, ix, p)) return fail(SRN_EINVAL, "lists mode needs position-set slots (sessions of <= 8 items, m <= m_index, complete lists): use the three-stage pipeline");
     const uint32_t stride = device_prep_stride(p.max_len);
-    HIP_TRY(launch_shard_prep((hipStream_t)stream, p.items_flat, p.q_off, p.nq, p.max_len, n_shards, kept_g, off_g, shard_stride, head, (const ShardPos*)pos_local, records, stride, fast_nb(ix, knobs()) == 3u, shard_base, direct));
-    ExtLists ext{records, stride, direct ? d->di.post_rank : lists_g};
-    return predict_ext(d, ix, p, stream, ext);
+    HIP_TRY(launch_shard_prep((hipStream_t)c.stream, p.items_flat, p.q_off, p.nq, p.max_len, l.n_shards, l.kept_g, l.off_g, 0ull, l.head, (const ShardPos*)l.pos_local, records, stride, fast_nb(ix, knobs()) == 3u, l.shard_base, l.direct));
+    ExtLists ext{records, stride, l.direct ? d->di.post_rank : l.lists_g};
+    return predict_ext(d, ix, p, c.stream, ext);
 }
 
-// ---- item-sharded index, neighbours pipeline (round 4): the posting lists are replicated (`post` = the device state of the whole index or of its postings-only view),
+// ---- item-sharded index, neighbours pipeline (round 4): the posting lists are replicated (c.post = the device state of the whole index or of its postings-only view),
 // the rows stay sharded.  The record of a query is the same on every rank except for the dense idx of its items (this shard's numbering).
-int device_shard_nb_prep(DeviceState* d, DeviceState* post, const LaunchParams& p, char* records, void* stream, char** order_buf, size_t* order_bytes, const unsigned long long** order_out) {
+int device_shard_nb_prep(const ShardCall& c, const LaunchParams& p, char* records, char** order_buf, size_t* order_bytes, const unsigned long long** order_out) {
+    DeviceState* d = c.d;
     HIP_TRY(hipSetDevice(d->device));
-    if (order_out) *order_out = nullptr;
+    *order_out = nullptr;
     if (p.nq == 0) return SRN_OK;
     const Knobs kn = knobs();
-    const bool ordered = order_buf && kn.order_min > 0 && p.nq >= (uint32_t)kn.order_min;
+    const bool ordered = kn.order_min > 0 && p.nq >= (uint32_t)kn.order_min;
     OrderBufs ob;
     if (ordered) { int rc = order_room(order_buf, order_bytes, p.nq, &ob); if (rc) return rc; }
-    HIP_TRY(launch_prep((hipStream_t)stream, post->di, p.items_flat, p.q_off, p.nq, p.m, p.max_len, records, device_prep_stride(p.max_len), fast_nb_of(d->di.n_kept, kn) == 3u /* (the fronting kernel runs on d's index) */, nullptr, nullptr, d->di.id_table, d->di.id_mask, ob.keys_in));
-    if (ordered) { HIP_TRY(sort_order_keys((hipStream_t)stream, ob.keys_in, ob.keys_out, p.nq, ob.temp, &ob.temp_bytes)); *order_out = ob.keys_out; }
+    HIP_TRY(launch_prep((hipStream_t)c.stream, c.post->di, p.items_flat, p.q_off, p.nq, p.m, p.max_len, records, device_prep_stride(p.max_len), fast_nb_of(d->di.n_kept, kn) == 3u /* (the fronting kernel runs on d's index) */, nullptr, nullptr, d->di.id_table, d->di.id_mask, ob.keys_in));
+    if (ordered) { HIP_TRY(sort_order_keys((hipStream_t)c.stream, ob.keys_in, ob.keys_out, p.nq, ob.temp, &ob.temp_bytes)); *order_out = ob.keys_out; }
     return SRN_OK;
 }
-int device_shard_nb_front(DeviceState* d, const FlatIndex& ix, DeviceState* post, const LaunchParams& p_in, const char* records, uint32_t* xchg, uint32_t xchg_stride, uint32_t q_lo, uint32_t q_hi, void* stream) {
-    if (q_lo >= q_hi) return SRN_OK;
-    LaunchParams p = p_in; p.nq = q_hi;
-    ExtLists ext{records, device_prep_stride(p.max_len), post->di.post_rank, 1, xchg, xchg_stride, q_lo};
-    return predict_ext(d, ix, p, stream, ext);
+int device_shard_nb_run(const ShardCall& c, const LaunchParams& p, const char* records, ExtLists ext) {
+    if (ext.q_lo >= p.nq) return SRN_OK;   // (a front end with no query of its own; an empty batch)
+    ext.prep = records; ext.prep_stride = device_prep_stride(p.max_len); ext.post_rank = c.post->di.post_rank;
+    return predict_ext(c.d, *c.ix, p, c.stream, ext);
 }
-// the fronting rank's neighbour lists [q_lo, q_hi) of `xin` -> position records in `xout` (the streaming form's exchange format, srn_sback.hip)
-int device_shard_nb_positions(DeviceState* d, const FlatIndex& ix, DeviceState* post, const LaunchParams& p, const char* records, const uint32_t* xin, uint32_t in_stride, uint32_t* xout, uint32_t out_stride,
-                              uint32_t q_lo, uint32_t q_hi, void* stream) {
-    if (q_lo >= q_hi) return SRN_OK;
-    HIP_TRY(hipSetDevice(d->device));
-    const uint32_t grid = (uint32_t)std::min<uint64_t>(q_hi - q_lo, (uint64_t)d->n_cu * 16 * 4);
-    HIP_TRY(launch_shard_nb_positions(dim3(grid), (hipStream_t)stream, records, device_prep_stride(p.max_len), p.max_len, xin, in_stride, xout, out_stride, post->di.post_rank, q_lo, q_hi, p.m,
-                                      fast_nb(ix, knobs()) == 3u));
+// (the streaming form's exchange format, srn_sback.hip)
+int device_shard_nb_positions(const ShardCall& c, const LaunchParams& p, const char* records, const ShardXchg& in, const ShardXchg& out, uint32_t q_lo) {
+    if (q_lo >= p.nq) return SRN_OK;
+    HIP_TRY(hipSetDevice(c.d->device));
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(p.nq - q_lo, (uint64_t)c.d->n_cu * 16 * 4);
+    HIP_TRY(launch_shard_nb_positions(dim3(grid), (hipStream_t)c.stream, records, device_prep_stride(p.max_len), p.max_len, in.words, in.stride, out.words, out.stride, c.post->di.post_rank, q_lo, p.nq, p.m,
+                                      fast_nb(*c.ix, knobs()) == 3u));
     return SRN_OK;
 }
 // words per query of that format for this batch shape, 0 if the batch (or this build's knobs) has no streaming form: RANK-INVARIANT inputs only
@@ -999,11 +998,6 @@ uint32_t device_shard_nb_positions_stride(const LaunchParams& p) {
     const Knobs kn = knobs();
     if (kn.no_sback_stream || kn.no_sback || p.max_len > 8) return 0u;
     return shard_nb_positions_stride(p.k, p.m);
-}
-int device_shard_nb_back(DeviceState* d, const FlatIndex& ix, DeviceState* post, const LaunchParams& p, const char* records, uint32_t* xchg, uint32_t xchg_stride, void* stream, const unsigned long long* order, bool positions) {
-    if (p.nq == 0) return SRN_OK;
-    ExtLists ext{records, device_prep_stride(p.max_len), post->di.post_rank, 2, xchg, xchg_stride, 0u, order, positions};
-    return predict_ext(d, ix, p, stream, ext);
 }
 
 int device_slot_bytes(DeviceState* d, const FlatIndex& ix, uint32_t max_len, uint32_t* num_bits) {   // element size of the packed candidate / neighbour buffers

@@ -24,12 +24,6 @@
 using namespace srn;
 
 namespace {
-template <typename F> int guarded(F f) {
-    try { return f(); }
-    catch (const std::bad_alloc&) { return fail(SRN_ENOMEM, "out of host memory"); }
-    catch (const std::exception& e) { return fail(SRN_EINVAL, std::string("internal error: ") + e.what()); }
-    catch (...) { return fail(SRN_EINVAL, "internal error"); }
-}
 
 // ---- MD5 (RFC 1321), for the session key only: same digest, same u128, as md5::compute + uuid::Builder::from_bytes ----
 struct Md5 {

@@ -394,6 +394,59 @@ def test_neighbours_pipeline_synthetic_shape_and_misuse():
         grp.set_postings(shards[0])                                             # a shard is not the whole index's postings
 
 
+def test_the_three_pipelines_interleaved_share_the_slots_the_streams_and_the_counters():
+    """What the pipelines share of a batch -- the two buffer slots with their events, the call count, the group's counters -- under an interleaving no other case has:
+    neighbours, lists and three-stage batches in turn on one group of 3, so that each slot's next user is another pipeline, on two caller streams.  The streams change at
+    every second step (A B B A A B ...): with two slots, a strict A B A B would pin each slot to one stream, and the slot's event would never have to order anything
+    across streams; this way EVERY reuse of a slot happens on the other stream.  Batch sizes 203 (not divisible by 3), 2 (the third shard fronts no query) and 64."""
+    import torch
+    import serenade_amd as sa
+    from serenade_amd import sharded, capi
+    from oracle import oracle as O
+    G, k, m = 3, 100, 400
+    off, items, ts, ids = small_dataset(181, n_sessions=9000, n_items=600, max_len=80)
+    full = sa.VMISIndex.from_sessions(off, items, ts, 400, 80, 1.0)
+    oix = O.OracleIndex(off, items, ts, 400, 80, 1.0)
+    grp = sharded.ShardGroup.local([sharded.ShardedVMISIndex.from_full(full, g, G) for g in range(G)])
+    grp.set_postings(full)
+    short = random_queries(124, ids, 203, max_len=8, unknown_rate=0.03, dup_rate=0.1)
+    longer = random_queries(125, ids, 203, max_len=12, unknown_rate=0.03, dup_rate=0.1)
+    # shape -> (sessions, max_len hint, how_many); the pipeline each one routes to is confirmed from the counters below
+    shapes = {"neighbours": (short, 8, 21), "lists": (short, 8, 32), "stages": (longer, 12, 21)}
+    refs = {}
+    for name, (qs, ml, n) in shapes.items():   # one reference per shape, over all 203 queries: a batch of nq queries is the first nq of them
+        flat, qoff = flatten(qs)
+        refs[name] = (oix.predict_batch("canonical", flat, qoff, k, m, n, False, threads=4), sa.predict_batch(full, (flat, qoff), k, m, n, False))
+    plan = [(name, nq) for nq in (203, 2, 64) for name in shapes]   # sizes descending: the slots' buffers grow (and the device synchronises) in the first round only
+    inputs = {(name, nq): _to_dev(*flatten(shapes[name][0][:nq])) for name, nq in plan}
+    torch.cuda.synchronize()
+    streams = [torch.cuda.Stream(), torch.cuda.Stream()]
+    roundup256 = lambda b: (b + 255) // 256 * 256
+    moved = ("batches", "queries", "neighbour_batches", "stage_batches", "bytes_results", "bytes_neighbours")
+    results = []
+    for j, (name, nq) in enumerate(plan):   # issued back to back, nothing waited for in between: only the group's own events order a slot's users
+        _, ml, n = shapes[name]
+        d_flat, d_off = inputs[(name, nq)]
+        before = grp.stats
+        if j in (4, 8):   # a refused call between two batches: nothing counted, no slot taken, and the next batch is served
+            with pytest.raises(capi.SerenadeError) as e:
+                grp.predict_batch(d_flat, d_off, nq, ml, capi.MAX_K + 1, m, n, stream=streams[j & 1].cuda_stream)
+            assert e.value.code == capi.SRN_ERANGE and grp.stats == before
+        results.append(grp.predict_batch(d_flat, d_off, nq, ml, k, m, n, stream=streams[((j + 1) >> 1) & 1].cuda_stream))
+        after = grp.stats
+        d = {key: after[key] - before[key] for key in moved}
+        assert d["batches"] == 1 and d["queries"] == nq, (name, nq, d)
+        assert (d["neighbour_batches"], d["stage_batches"]) == {"neighbours": (1, 0), "lists": (0, 0), "stages": (0, 1)}[name], (name, nq, d)
+        assert d["bytes_results"] == G * roundup256(nq * n * 16 + nq * 4), (name, nq, d)
+        assert d["bytes_neighbours"] == (G * ((nq + G - 1) // G) * (k + 1) * 4 if name == "neighbours" else 0), (name, nq, d)   # (an in-process group: the gather form)
+    for (name, nq), res in zip(plan, results):
+        got = _np(res)
+        ref, u = refs[name]
+        _check_oracle(got, {key: ref[key][:nq] for key in ("ids", "scores", "counts")}, shapes[name][2])
+        assert np.array_equal(got[0], u[0][:nq]) and np.array_equal(got[1], u[1][:nq]) and np.array_equal(got[2], u[2][:nq]), (name, nq)
+    assert grp.stats["batches"] == 9
+
+
 def _cb_nb_worker(rank, world, port, q):
     os.environ.update(RANK=str(rank), LOCAL_RANK="0", WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     try:
