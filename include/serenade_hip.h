@@ -952,6 +952,38 @@ int srn_evaluate_bootstrap(srn_eval_set_t* set, const srn_eval_trial_t* trials, 
 /* host only: the rule -- out[i] = w(seed, replicate, first_session + i), i < n.  NULL out with n > 0: SRN_EINVAL */
 int srn_bootstrap_weights(uint64_t seed, uint32_t replicate, uint64_t first_session, size_t n, uint8_t* out);
 
+/* ---- trials by segment ------------------------------------------------------------------------------------
+ * srn_evaluate (with boot: srn_evaluate_bootstrap) that also says which queries a figure comes from.  A segmentation maps every query (s, t) of the set -- s the
+ * test session's index in the set's order, t = 1..n-1 its state, scored against the raw e_{t+1}..e_n -- to a segment id in 0..segments-1.  The id depends on the set
+ * and the segmentation alone, never on the trial: under SRN_FLAG_EVAL_HANDLER it is still the raw t, e_t and e_{t+1}.
+ *   SRN_SEG_STATE          min(t, segments) - 1: states 1..segments-1 each their own segment, the last one holds t >= segments
+ *   SRN_SEG_LABEL          labels[s]: one uint16 per test session in the set's order, sessions of one event included (n_labels = the set's sessions, else SRN_EINVAL;
+ *                          a label >= segments: SRN_EINVAL)
+ *   SRN_SEG_TARGET_COUNT   #{ j : bounds[j] <= c(e_{t+1}) } over segments-1 strictly ascending bounds; c(x) is the training count the set holds for x, 0 for an item the
+ *                          index's dictionary does not know.  With bounds[0] = 1 segment 0 is "the next item was never trained on"
+ *   SRN_SEG_CURRENT_COUNT  the same over c(e_t), the clicked item
+ * labels and bounds are host pointers, read during the call.  seg_out[t][g] holds the segment's queries and the six sums of srn_eval_result_t; Coverage is a property
+ * of the whole row set and is not segmented.  The order of the additions is 10.2's: per group of 256 consecutive global query indices from +0.0 in query order over the
+ * group's queries of the segment, acc = acc + term, then the groups in order onto the segment's total -- a segment's sums do not depend on max_chunk_queries, on the
+ * other trials, or on `segments` where its queries do not change.  With boot, seg_rep[t][g][b][0..6] are the seven sums of srn_evaluate_bootstrap over the segment's
+ * queries: the same weights w(seed, b, s), so a segment is paired with the total, with every other segment and across trials, calls and indices; the same order rule,
+ * acc = acc + (double)w * term.  out[t] and rep are srn_evaluate's and srn_evaluate_bootstrap's, bit for bit (the two ms_* fields aside).
+ * Refusals, all before anything is launched: seg NULL, seg_out NULL, an unknown mode, segments == 0, reserved != 0, labels NULL or a label >= segments (SRN_SEG_LABEL),
+ * bounds NULL with segments > 1 or not strictly ascending (the count modes), with boot a NULL rep or seg_rep: SRN_EINVAL; segments > SRN_MAX_SEGMENTS, with boot
+ * segments * replicates > 16 * SRN_MAX_BOOTSTRAP: SRN_ERANGE; then srn_evaluate_bootstrap's and srn_evaluate's own; then n_labels. */
+#define SRN_MAX_SEGMENTS 64
+#define SRN_SEG_STATE 1u
+#define SRN_SEG_LABEL 2u
+#define SRN_SEG_TARGET_COUNT 3u
+#define SRN_SEG_CURRENT_COUNT 4u
+typedef struct { uint32_t mode, segments; const uint16_t* labels; size_t n_labels; const uint64_t* bounds; uint64_t reserved; } srn_segments_t;   /* reserved: 0 */
+typedef struct { uint64_t n_evaluations; double sum_mrr, sum_ndcg, sum_hit_rate, sum_popularity, sum_precision, sum_recall; } srn_eval_segment_t;
+int srn_evaluate_segments(srn_eval_set_t* set, const srn_eval_trial_t* trials, size_t n_trials, const srn_segments_t* seg, const srn_bootstrap_t* boot /* or NULL */,
+                          srn_eval_result_t* out, srn_eval_segment_t* seg_out /* [n_trials][segments] */,
+                          double* rep /* [n_trials][replicates][7], or NULL without boot */, double* seg_rep /* [n_trials][segments][replicates][7] */, void* stream);
+/* the ids alone, in query order, to the host: *n_queries = the set's queries; out may be NULL (the count alone), else cap < *n_queries: SRN_ERANGE */
+int srn_eval_segment_ids(srn_eval_set_t* set, const srn_segments_t* seg, uint16_t* out, size_t cap, size_t* n_queries);
+
 int srn_device_count(int* out);
 void srn_limits(srn_limits_t* out);
 const char* srn_last_error(void);

@@ -49,6 +49,11 @@ int srn_debug_sback_launches(const srn_index_t* idx, uint64_t* out_launches);
  * cap < n: SRN_ERANGE).  *out (may be NULL) = what srn_evaluate returns for the trial. */
 int srn_debug_eval_terms(srn_eval_set_t* set, const srn_eval_trial_t* trial, double* out_terms, size_t cap, size_t* out_n, srn_eval_result_t* out);
 
+/* Measurement aid (tools/eval_bench.py --segments): device time (HIP events, summed over chunks and trials) of the set's most recent srn_evaluate_segments call's
+ * segment kernels -- *ms_segments: the id, group and accumulate kernels; *ms_segment_bootstrap: the segmented bootstrap's (0 without boot).  Neither is in ms_eval.
+ * Either output may be NULL. */
+int srn_debug_eval_segment_ms(srn_eval_set_t* set, double* ms_segments, double* ms_segment_bootstrap);
+
 /* Test / measurement aid: the sessions the store's most recent srn_recommend_batch* call emitted (request q = items[q_off[q] .. q_off[q + 1])), where predict read them:
  * the device pointers (valid until the next call on the store), the request count and the max_len_hint; with h_q_off ([n + 1]) / h_items (cap entries) also copied to
  * the host.  Any output may be NULL.  Blocks until that call is done. */

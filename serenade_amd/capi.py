@@ -76,6 +76,18 @@ class Bootstrap(C.Structure):   # srn_bootstrap_t
     _fields_ = [("seed", C.c_uint64), ("replicates", C.c_uint32), ("flags", C.c_uint32)]
 
 
+MAX_SEGMENTS = 64
+SEG_STATE, SEG_LABEL, SEG_TARGET_COUNT, SEG_CURRENT_COUNT = 1, 2, 3, 4
+
+
+class Segments(C.Structure):   # srn_segments_t
+    _fields_ = [("mode", C.c_uint32), ("segments", C.c_uint32), ("labels", C.c_void_p), ("n_labels", C.c_size_t), ("bounds", C.c_void_p), ("reserved", C.c_uint64)]
+
+
+class EvalSegment(C.Structure):   # srn_eval_segment_t
+    _fields_ = [("n_evaluations", C.c_uint64)] + [(n, C.c_double) for n in ("sum_mrr", "sum_ndcg", "sum_hit_rate", "sum_popularity", "sum_precision", "sum_recall")]
+
+
 class LoadInfo(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("lines", "rows", "skipped", "host_parsed")] + \
                [(n, C.c_double) for n in ("ms_read", "ms_upload", "ms_parse", "ms_group", "ms_download")]
@@ -235,6 +247,9 @@ SYMBOLS = {
     "srn_evaluate_bootstrap": (_i, [_vp, C.POINTER(EvalTrial), _sz, C.POINTER(Bootstrap), C.POINTER(EvalResult), _vp, _vp]),
     "srn_bootstrap_weights": (_i, [_u64, C.c_uint32, _u64, _sz, _vp]),
     "srn_debug_eval_terms": (_i, [_vp, C.POINTER(EvalTrial), _vp, _sz, C.POINTER(_sz), C.POINTER(EvalResult)]),
+    "srn_evaluate_segments": (_i, [_vp, C.POINTER(EvalTrial), _sz, C.POINTER(Segments), C.POINTER(Bootstrap), C.POINTER(EvalResult), C.POINTER(EvalSegment), _vp, _vp, _vp]),
+    "srn_eval_segment_ids": (_i, [_vp, C.POINTER(Segments), _vp, _sz, C.POINTER(_sz)]),
+    "srn_debug_eval_segment_ms": (_i, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "srn_device_sessions_create": (_i, [_i, _sz, _sz, _u64, _u64, C.POINTER(_vp)]),
     "srn_device_sessions_free": (None, [_vp]),
     "srn_device_sessions_get": (_i, [_vp, _u64, _u64, _u64, _vp, _sz, C.POINTER(_sz)]),

@@ -800,6 +800,66 @@ int srn_bootstrap_weights(uint64_t seed, uint32_t replicate, uint64_t first_sess
         return SRN_OK; });
 }
 
+// a segmentation on its own: everything but n_labels, which needs the set
+static int check_segments(const srn_segments_t* seg) {
+    if (!seg) return fail(SRN_EINVAL, "null segmentation");
+    if (seg->mode < SRN_SEG_STATE || seg->mode > SRN_SEG_CURRENT_COUNT) return fail(SRN_EINVAL, "unknown segmentation mode");
+    if (seg->segments == 0) return fail(SRN_EINVAL, "segments must be > 0");
+    if (seg->segments > SRN_MAX_SEGMENTS) return fail(SRN_ERANGE, "segments above SRN_MAX_SEGMENTS");
+    if (seg->reserved != 0) return fail(SRN_EINVAL, "srn_segments_t.reserved must be 0");
+    if (seg->mode == SRN_SEG_LABEL) {
+        if (seg->n_labels && !seg->labels) return fail(SRN_EINVAL, "null labels");
+        for (size_t s = 0; s < seg->n_labels; ++s)
+            if (seg->labels[s] >= seg->segments) return fail(SRN_EINVAL, "a label is not below segments");
+    } else if (seg->mode != SRN_SEG_STATE) {
+        if (seg->segments > 1 && !seg->bounds) return fail(SRN_EINVAL, "null bounds");
+        for (uint32_t j = 0; j + 2 < seg->segments; ++j)
+            if (seg->bounds[j] >= seg->bounds[j + 1]) return fail(SRN_EINVAL, "bounds must be strictly ascending");
+    }
+    return SRN_OK;
+}
+static int check_labels_fit(const srn_eval_set_t* set, const srn_segments_t* seg) {
+    if (seg->mode == SRN_SEG_LABEL && seg->n_labels != set->sess_off.size() - 1) return fail(SRN_EINVAL, "n_labels must be the set's number of test sessions");
+    return SRN_OK;
+}
+
+int srn_evaluate_segments(srn_eval_set_t* set, const srn_eval_trial_t* trials, size_t n_trials, const srn_segments_t* seg, const srn_bootstrap_t* boot,
+                          srn_eval_result_t* out, srn_eval_segment_t* seg_out, double* rep, double* seg_rep, void* stream) {
+    return guarded([&]() -> int {
+        int rc = check_segments(seg); if (rc) return rc;
+        if (n_trials && !seg_out) return fail(SRN_EINVAL, "null argument");
+        if (boot) {
+            if (!rep || !seg_rep) return fail(SRN_EINVAL, "null argument");
+            if (boot->replicates == 0) return fail(SRN_EINVAL, "replicates must be > 0");
+            if (boot->flags != 0) return fail(SRN_EINVAL, "srn_bootstrap_t.flags must be 0");
+            if (boot->replicates > SRN_MAX_BOOTSTRAP) return fail(SRN_ERANGE, "replicates above SRN_MAX_BOOTSTRAP");
+            if ((uint64_t)seg->segments * boot->replicates > 16ull * SRN_MAX_BOOTSTRAP) return fail(SRN_ERANGE, "segments * replicates above 16 * SRN_MAX_BOOTSTRAP");
+        }
+        rc = check_trials(set, trials, n_trials, out); if (rc) return rc;
+        rc = check_labels_fit(set, seg); if (rc) return rc;
+        if (n_trials == 0) return SRN_OK;
+        return eval_run(set, trials, n_trials, out, stream, nullptr, 0, boot, rep, seg, seg_out, seg_rep); });
+}
+
+int srn_eval_segment_ids(srn_eval_set_t* set, const srn_segments_t* seg, uint16_t* out, size_t cap, size_t* n_queries) {
+    return guarded([&]() -> int {
+        int rc = check_segments(seg); if (rc) return rc;
+        if (!n_queries) return fail(SRN_EINVAL, "null argument");
+        if (!set) return fail(SRN_EINVAL, "null evaluation set");
+        rc = check_labels_fit(set, seg); if (rc) return rc;
+        *n_queries = (size_t)eval_n_queries(set);
+        if (!out) return SRN_OK;
+        if (cap < *n_queries) return fail(SRN_ERANGE, "segment ids: no room for every query of the set");
+        return eval_segment_ids(set, seg, out); });
+}
+
+int srn_debug_eval_segment_ms(srn_eval_set_t* set, double* ms_segments, double* ms_segment_bootstrap) {
+    return guarded([&]() -> int {
+        if (!set) return fail(SRN_EINVAL, "null evaluation set");
+        eval_segment_ms(set, ms_segments, ms_segment_bootstrap);
+        return SRN_OK; });
+}
+
 int srn_debug_eval_terms(srn_eval_set_t* set, const srn_eval_trial_t* trial, double* out_terms, size_t cap, size_t* out_n, srn_eval_result_t* out) {
     return guarded([&]() -> int {
         if (!trial || !out_n) return fail(SRN_EINVAL, "null argument");

@@ -32,6 +32,7 @@
 #include "srn_hipsync.h"
 #include "srn_events.h"
 #include "srn_visitor_table.h"  // align256
+#include "srn_segments.h"
 
 // the terms must be the bits the host formulas give: no fused multiply-adds
 #pragma clang fp contract(off)
@@ -56,7 +57,10 @@ struct EvalDevice {
     char* part = nullptr; size_t part_bytes = 0;               // per-group partial sums of every trial of a call
     char* cover = nullptr; size_t cover_bytes = 0;             // coverage bitmaps + popcounts + the error word
     char* boot = nullptr; size_t boot_bytes = 0;               // srn_evaluate_bootstrap: every trial's replicate totals, then one replicate tile's group partials
+    char* seg = nullptr; size_t seg_bytes = 0;                 // srn_evaluate_segments: the regions of seg_buffers (srn_segments.h)
     std::vector<hipEvent_t> ev;
+    std::vector<hipEvent_t> seg_ev;                             // three per chunk around the segment kernels
+    double ms_seg = 0.0, ms_seg_boot = 0.0;                     // ... and what they measured in the last srn_evaluate_segments call (srn_debug_eval_segment_ms)
 };
 
 uint64_t eval_n_queries(const srn_eval_set* set) {
@@ -262,9 +266,10 @@ void eval_set_free(srn_eval_set* set) {
     if (!set) return;
     if (EvalDevice* e = set->dev) {
         (void)hipSetDevice(e->device);
-        for (void* p : {(void*)e->items, (void*)e->sess_off, (void*)e->freq, (void*)e->ndcg_w, (void*)e->scan, (void*)e->chunk, (void*)e->part, (void*)e->cover, (void*)e->boot})
+        for (void* p : {(void*)e->items, (void*)e->sess_off, (void*)e->freq, (void*)e->ndcg_w, (void*)e->scan, (void*)e->chunk, (void*)e->part, (void*)e->cover, (void*)e->boot, (void*)e->seg})
             if (p) (void)hipFree(p);
         for (hipEvent_t x : e->ev) (void)hipEventDestroy(x);
+        for (hipEvent_t x : e->seg_ev) (void)hipEventDestroy(x);
         delete e;
     }
     delete set;
@@ -516,7 +521,7 @@ static uint32_t chunk_queries(const srn_eval_trial_t& t) {
 }
 
 int eval_run(srn_eval_set* set, const srn_eval_trial_t* trials, size_t n_trials, srn_eval_result_t* out, void* user_stream, double* terms_out, size_t cap,
-             const srn_bootstrap_t* boot, double* rep) {
+             const srn_bootstrap_t* boot, double* rep, const srn_segments_t* seg, srn_eval_segment_t* seg_out, double* seg_rep) {
     EvalDevice* e = set->dev; const srn_index* idx = set->idx; const FlatIndex& ix = idx->flat;
     HIP_TRY(hipSetDevice(e->device));
     hipStream_t st = (hipStream_t)user_stream;
@@ -542,6 +547,23 @@ int eval_run(srn_eval_set* set, const srn_eval_trial_t* trials, size_t n_trials,
     if (boot) {
         if ((rc = ensure(&e->boot, &e->boot_bytes, boot_totals + boot_scratch_bytes(max_chunk, boot->replicates)))) return rc;
         HIP_TRY(hipMemsetAsync(e->boot, 0, boot_totals, st));
+    }
+    // the segmentation: labels up, totals zeroed; the ids of a chunk and the partials of its groups are rewritten chunk by chunk
+    const uint32_t S = seg ? seg->segments : 0, seg_B = seg && boot ? boot->replicates : 0;
+    SegBuffers sb; SegSet seg_set{}; SegRule seg_rule{};
+    size_t seg_ev_at = 0;
+    if (seg) {
+        sb = seg_buffers(n_s, max_chunk, n_trials, S, seg_B);
+        if ((rc = ensure(&e->seg, &e->seg_bytes, sb.bytes))) return rc;
+        size_t n_seg_events = 0;
+        for (size_t t = 0; t < n_trials; ++t) n_seg_events += 3 * ((nq_all + chunk_queries(trials[t]) - 1) / chunk_queries(trials[t]));
+        while (e->seg_ev.size() < n_seg_events) { hipEvent_t x; HIP_TRY(hipEventCreate(&x)); e->seg_ev.push_back(x); }
+        seg_set = SegSet{e->items, e->sess_off, e->freq, idx->dev->di.id_table, idx->dev->di.id_mask};
+        seg_rule.mode = seg->mode; seg_rule.S = S; seg_rule.labels = (const uint16_t*)(e->seg + sb.labels);
+        for (uint32_t j = 0; j + 1 < S && seg->bounds && seg->mode != SRN_SEG_STATE && seg->mode != SRN_SEG_LABEL; ++j) seg_rule.bounds[j] = seg->bounds[j];
+        if (seg->mode == SRN_SEG_LABEL && n_s) HIP_TRY(hipMemcpyAsync(e->seg + sb.labels, seg->labels, n_s * sizeof(uint16_t), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemsetAsync(e->seg + sb.totals, 0, n_trials * S * kSegSums * 8, st));
+        if (seg_B) HIP_TRY(hipMemsetAsync(e->seg + sb.boot_totals, 0, n_trials * S * (size_t)seg_B * kSegSums * 8, st));
     }
     if ((rc = ensure(&e->scan, &e->scan_bytes, 2 * (n_s + 1) * 8))) return rc;
     std::vector<uint64_t> scan(2 * (n_s + 1));
@@ -641,6 +663,17 @@ int eval_run(srn_eval_set* set, const srn_eval_trial_t* trials, size_t n_trials,
             HIP_TRY(hipEventRecord(ev[3], st));
             if (boot && (rc = boot_chunk(d_terms, d_ss, nq, *boot, (double*)(e->boot + boot_totals),
                                          (double*)e->boot + ti * (size_t)boot->replicates * SRN_BOOTSTRAP_SUMS, st))) return rc;
+            if (seg) {
+                hipEvent_t* sev = &e->seg_ev[seg_ev_at]; seg_ev_at += 3;
+                uint16_t* d_seg_ids = (uint16_t*)(e->seg + sb.ids);
+                HIP_TRY(hipEventRecord(sev[0], st));
+                if ((rc = seg_ids(seg_set, seg_rule, d_ss, nq, d_seg_ids, st))) return rc;
+                if ((rc = seg_chunk(d_terms, d_seg_ids, nq, S, (double*)(e->seg + sb.part), (double*)(e->seg + sb.totals) + ti * S * kSegSums, st))) return rc;
+                HIP_TRY(hipEventRecord(sev[1], st));
+                if (seg_B && (rc = seg_boot_chunk(d_terms, d_ss, d_seg_ids, nq, S, *boot, (double*)(e->seg + sb.boot_part),
+                                                  (double*)(e->seg + sb.boot_totals) + ti * S * (size_t)seg_B * kSegSums, st))) return rc;
+                HIP_TRY(hipEventRecord(sev[2], st));
+            }
             if (terms_out) {   // (test aid) the chunk's terms, 7 per query
                 std::vector<double> h((size_t)nq * kTerms);
                 HIP_TRY(hipMemcpyAsync(h.data(), d_terms, h.size() * 8, hipMemcpyDeviceToHost, st));
@@ -659,8 +692,26 @@ int eval_run(srn_eval_set* set, const srn_eval_trial_t* trials, size_t n_trials,
     HIP_TRY(hipMemcpyAsync(cov.data(), covered, n_trials * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(&h_err, err, 4, hipMemcpyDeviceToHost, st));
     if (boot) HIP_TRY(hipMemcpyAsync(rep, e->boot, n_trials * (size_t)boot->replicates * SRN_BOOTSTRAP_SUMS * 8, hipMemcpyDeviceToHost, st));
+    std::vector<double> seg_tot(seg ? n_trials * S * kSegSums : 0);
+    if (seg) {
+        HIP_TRY(hipMemcpyAsync(seg_tot.data(), e->seg + sb.totals, seg_tot.size() * 8, hipMemcpyDeviceToHost, st));
+        if (seg_B) HIP_TRY(hipMemcpyAsync(seg_rep, e->seg + sb.boot_totals, n_trials * S * (size_t)seg_B * kSegSums * 8, hipMemcpyDeviceToHost, st));
+    }
     HIP_TRY(hipStreamSynchronize(st));
     if (h_err) return fail(SRN_ERANGE, "a query exceeded the kernel's table limits");
+    if (seg) {
+        for (size_t i = 0; i < n_trials * S; ++i) {   // (the counts are integers far below 2^53: exact as doubles)
+            const double* v = &seg_tot[i * kSegSums];
+            seg_out[i] = srn_eval_segment_t{(uint64_t)v[0], v[1], v[2], v[3], v[4], v[5], v[6]};
+        }
+        e->ms_seg = e->ms_seg_boot = 0.0;
+        for (size_t k = 0; k < seg_ev_at; k += 3) {
+            float a = 0, b = 0;
+            HIP_TRY(hipEventElapsedTime(&a, e->seg_ev[k], e->seg_ev[k + 1]));
+            HIP_TRY(hipEventElapsedTime(&b, e->seg_ev[k + 1], e->seg_ev[k + 2]));
+            e->ms_seg += (double)a; e->ms_seg_boot += (double)b;
+        }
+    }
     for (size_t ti = 0; ti < n_trials; ++ti) {
         srn_eval_result_t& r = out[ti];
         r = srn_eval_result_t{};
@@ -685,6 +736,39 @@ int eval_run(srn_eval_set* set, const srn_eval_trial_t* trials, size_t n_trials,
         }
     }
     return SRN_OK;
+}
+
+// srn_eval_segment_ids: the (session, state) pairs of every query from the host's offsets, the id kernel over them, the ids back
+int eval_segment_ids(srn_eval_set* set, const srn_segments_t* seg, uint16_t* out) {
+    EvalDevice* e = set->dev; const srn_index* idx = set->idx;
+    HIP_TRY(hipSetDevice(e->device));
+    const size_t n_s = set->sess_off.size() - 1;
+    const uint64_t nq = eval_n_queries(set);
+    if (nq == 0) return SRN_OK;
+    if (nq > 0xFFFFFFFFull) return fail(SRN_ERANGE, "more than 2^32 - 1 queries");
+    std::vector<uint2> ss; ss.reserve(nq);
+    for (size_t s = 0; s < n_s; ++s)
+        for (uint64_t t = 1; t + set->sess_off[s] < set->sess_off[s + 1]; ++t) ss.push_back(make_uint2((uint32_t)s, (uint32_t)t));
+    DevBuf d_ss, d_ids, d_labels;
+    HIP_TRY(d_ss.alloc(nq * sizeof(uint2))); HIP_TRY(d_ids.alloc(nq * sizeof(uint16_t)));
+    HIP_TRY(hipMemcpy(d_ss.p, ss.data(), nq * sizeof(uint2), hipMemcpyHostToDevice));
+    SegRule rule{}; rule.mode = seg->mode; rule.S = seg->segments;
+    if (seg->mode == SRN_SEG_LABEL) {
+        HIP_TRY(d_labels.alloc(n_s * sizeof(uint16_t)));
+        if (n_s) HIP_TRY(hipMemcpy(d_labels.p, seg->labels, n_s * sizeof(uint16_t), hipMemcpyHostToDevice));
+        rule.labels = d_labels.as<uint16_t>();
+    } else if (seg->mode != SRN_SEG_STATE) {
+        for (uint32_t j = 0; j + 1 < seg->segments; ++j) rule.bounds[j] = seg->bounds[j];
+    }
+    const SegSet ss_set{e->items, e->sess_off, e->freq, idx->dev->di.id_table, idx->dev->di.id_mask};
+    int rc = seg_ids(ss_set, rule, d_ss.p, (uint32_t)nq, d_ids.as<uint16_t>(), nullptr); if (rc) return rc;
+    HIP_TRY(hipMemcpy(out, d_ids.p, nq * sizeof(uint16_t), hipMemcpyDeviceToHost));
+    return SRN_OK;
+}
+
+void eval_segment_ms(const srn_eval_set* set, double* ms_segments, double* ms_segment_bootstrap) {
+    if (ms_segments) *ms_segments = set->dev->ms_seg;
+    if (ms_segment_bootstrap) *ms_segment_bootstrap = set->dev->ms_seg_boot;
 }
 
 }  // namespace srn

@@ -317,7 +317,12 @@ int eval_set_from_events(const srn_index* idx, const uint64_t* test_session_ids,
 // trials already checked (srn_capi.cpp).  terms != nullptr: one trial, its per-query terms [n * 7] (cap entries of room)
 // boot != nullptr (already checked): every trial's replicate sums too, rep[n_trials][boot->replicates][SRN_BOOTSTRAP_SUMS] on the host
 int eval_run(srn_eval_set* set, const srn_eval_trial_t* trials, size_t n_trials, srn_eval_result_t* out, void* stream, double* terms, size_t cap,
-             const srn_bootstrap_t* boot = nullptr, double* rep = nullptr);
+             const srn_bootstrap_t* boot = nullptr, double* rep = nullptr,
+             const srn_segments_t* seg = nullptr, srn_eval_segment_t* seg_out = nullptr, double* seg_rep = nullptr);
+// seg != nullptr (already checked, its n_labels included): every trial's sums by segment too (srn_segments.hip), seg_out[n_trials][segments] and, with boot,
+// seg_rep[n_trials][segments][replicates][SRN_BOOTSTRAP_SUMS] on the host
+int eval_segment_ids(srn_eval_set* set, const srn_segments_t* seg, uint16_t* out);   // out: room for eval_n_queries(set) ids
+void eval_segment_ms(const srn_eval_set* set, double* ms_segments, double* ms_segment_bootstrap);   // device time of the last call's segment kernels
 // the bootstrap behind the metrics kernel (srn_bootstrap.hip): one chunk's terms [nq][8] and (session, state) pairs onto a trial's running totals
 // [replicates][SRN_BOOTSTRAP_SUMS], through scratch of boot_scratch_bytes(largest chunk, replicates); only enqueues
 size_t boot_scratch_bytes(uint64_t chunk_queries, uint32_t replicates);

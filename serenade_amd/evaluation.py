@@ -16,6 +16,14 @@ device milliseconds of predict and of the evaluation kernels.
 Confidence intervals: evaluate(es, trials, bootstrap=B, seed=S) resamples the test sessions B times on the GPU next to every trial
 (srn_evaluate_bootstrap) and adds percentile intervals and the replicate sums to each report; compare(report_a, report_b) is the paired comparison of two such
 reports.  bootstrap_weights / bootstrap_model state the rule in NumPy: the device's replicate sums are the model's, bit for bit.
+
+Segments: evaluate(es, trials, segments=spec) also says which queries a figure comes from (srn_evaluate_segments).  spec is one of
+    dict(by="position", n=8)                              the state t of the query: t = 1 .. n-1 each their own segment, the last one t >= n
+    dict(by="labels", labels=array, n=S, names=None)      the caller's label (0 .. S-1) per test session, in the set's order, sessions of one event included
+    dict(by="target_count", bounds=[1, 10, 100])          how often the next item e_{t+1} occurs in the training data the set holds (0: the index does not know it)
+    dict(by="current_count", bounds=[...])                the same for the clicked item e_t
+Each report gains "segments": one dict per segment with "name", "qty_evaluations", the seven metrics @N (no Coverage) and "sums"; with bootstrap= also the
+intervals and replicate arrays, paired with the totals: compare(a, b, metric, segment=i).  segment_ids_model / segment_model state the rule in NumPy.
 """
 import ctypes as C
 
@@ -148,13 +156,25 @@ class EvalSet:
         capi.check(capi.lib().srn_debug_eval_terms(self._h, C.byref(t), capi.ptr(out), out.shape[0], C.byref(n), C.byref(r)))
         return out[:n.value], _report(r, t.length)
 
+    def segment_ids(self, spec):
+        """The segment id of every query under a segments spec (srn_eval_segment_ids) -> uint16[n], queries in set order, states ascending."""
+        seg, _, keep = _segments(spec)
+        n = C.c_size_t()
+        capi.check(capi.lib().srn_eval_segment_ids(self._h, C.byref(seg), None, 0, C.byref(n)))
+        out = np.zeros(max(n.value, 1), np.uint16)
+        capi.check(capi.lib().srn_eval_segment_ids(self._h, C.byref(seg), capi.ptr(out), out.shape[0], C.byref(n)))
+        del keep
+        return out[:n.value]
 
-def evaluate(eval_set, trials, stream=0, bootstrap=0, seed=0, ci=0.95):
+
+def evaluate(eval_set, trials, stream=0, bootstrap=0, seed=0, ci=0.95, segments=None):
     """One srn_evaluate call over all trials -> list of reports (dicts), in trial order.
     bootstrap=B > 0: srn_evaluate_bootstrap with B replicates of the session-clustered Poisson bootstrap at `seed`.  Each report gains
     "bootstrap": {"replicates", "seed", "ci", "weights": float64[B] (a replicate's sum of weights), "sums": {name: float64[B]} (its weighted sums, the names of
     "sums"), "empty_replicates": replicates of weight 0} and, for every metric but Coverage, "<Name>@N_ci": (lo, hi) -- the percentile interval at level `ci` over
-    the replicates of non-zero weight ((0, 0) when there is none).  Reports of one seed and B on one test set are paired: compare()."""
+    the replicates of non-zero weight ((0, 0) when there is none).  Reports of one seed and B on one test set are paired: compare().
+    segments=spec (the module's docstring): srn_evaluate_segments -- the same reports, each with "segments": [{"name", "qty_evaluations", "<Name>@N" for the seven
+    metrics but Coverage (F1score from the segment's own Precision and Recall), "sums"}], and with bootstrap= each segment's "<Name>@N_ci" and "bootstrap" too."""
     trials = list(trials)
     B = int(bootstrap)
     if B < 0 or not 0.0 < float(ci) < 1.0:
@@ -162,6 +182,27 @@ def evaluate(eval_set, trials, stream=0, bootstrap=0, seed=0, ci=0.95):
     arr = (capi.EvalTrial * max(len(trials), 1))(*[_trial(t) for t in trials])
     res = (capi.EvalResult * max(len(trials), 1))()
     h = eval_set._h if eval_set is not None else None
+    if segments is not None:
+        seg, names, keep = _segments(segments)
+        S, n = int(seg.segments), max(len(trials), 1)
+        seg_out = (capi.EvalSegment * (n * max(S, 1)))()
+        boot = capi.Bootstrap(int(seed) & _M64, B, 0) if B else None
+        rep = np.zeros((n, B, capi.BOOTSTRAP_SUMS)) if B else None
+        seg_rep = np.zeros((n, max(S, 1), B, capi.BOOTSTRAP_SUMS)) if B else None
+        capi.check(capi.lib().srn_evaluate_segments(h, arr, len(trials), C.byref(seg), C.byref(boot) if B else None, res, seg_out, capi.ptr(rep), capi.ptr(seg_rep),
+                                                    C.c_void_p(stream)))
+        del keep
+        out = []
+        for i in range(len(trials)):
+            length = arr[i].length
+            r = _report(res[i], length)
+            if B:
+                r = _with_bootstrap(r, rep[i], length, int(boot.seed), float(ci))
+            r["segments"] = [_segment_report(names[g], seg_out[i * S + g], length) for g in range(S)]
+            if B:
+                r["segments"] = [_with_bootstrap(sr, seg_rep[i, g], length, int(boot.seed), float(ci)) for g, sr in enumerate(r["segments"])]
+            out.append(r)
+        return out
     if B == 0:
         capi.check(capi.lib().srn_evaluate(h, arr, len(trials), res, C.c_void_p(stream)))
         return [_report(res[i], arr[i].length) for i in range(len(trials))]
@@ -275,11 +316,28 @@ def _point(report, metric):
     return float(report[keys[0]])
 
 
-def compare(report_a, report_b, metric="Mrr"):
+def compare(report_a, report_b, metric="Mrr", segment=None):
     """Paired bootstrap comparison of two reports of evaluate(..., bootstrap=B) -> {"delta": a - b of the point estimates, "ci": the percentile interval of the
     replicate-by-replicate differences (at report_a's level), "p_better": the share of replicates where a is above b, "replicates": how many entered}.
     The weights depend on (seed, replicate, the session's place in the test set) alone, so reports pair across evaluate calls and across indices on one test set;
-    ValueError when seed, B or qty_evaluations differ."""
+    ValueError when seed, B or qty_evaluations differ.
+    segment=i pairs segment i of both reports (evaluate(..., segments=spec, bootstrap=B)); segment=(i, j) pairs a's segment i with b's segment j, None standing for
+    the whole report -- (i, None) is a segment against the total.  The weights are the same, so the replicates pair; qty_evaluations must agree only where both
+    sides are the same part."""
+    if segment is not None:
+        sa, sb = segment if isinstance(segment, tuple) else (segment, segment)
+        def pick(r, i):
+            if i is None:
+                return r
+            if "segments" not in r:
+                raise ValueError("compare(segment=) needs reports of evaluate(..., segments=spec)")
+            return r["segments"][int(i)]
+        ra, rb = pick(report_a, sa), pick(report_b, sb)
+        if sa != sb:   # different parts of the test set: only the resampling has to be the same
+            if ra.get("bootstrap") is None or rb.get("bootstrap") is None:
+                raise ValueError("compare needs reports of evaluate(..., bootstrap=B)")
+            rb = dict(rb, qty_evaluations=ra["qty_evaluations"])
+        return compare(ra, rb, metric)
     ba, bb = report_a.get("bootstrap"), report_b.get("bootstrap")
     if ba is None or bb is None:
         raise ValueError("compare needs reports of evaluate(..., bootstrap=B)")
@@ -291,3 +349,113 @@ def compare(report_a, report_b, metric="Mrr"):
     d = (va - vb)[ok]
     return {"delta": _point(report_a, metric) - _point(report_b, metric), "ci": _interval(d, float(ba["ci"])),
             "p_better": float(np.count_nonzero(d > 0)) / len(d) if len(d) else 0.0, "replicates": int(len(d))}
+
+
+# ---- segments: the spec, the reports, the rule in NumPy ----
+_SEG_METRICS = (("Mrr", "sum_mrr"), ("Ndcg", "sum_ndcg"), ("HitRate", "sum_hit_rate"), ("Popularity", "sum_popularity"), ("Precision", "sum_precision"), ("Recall", "sum_recall"))
+SEGMENT_MODES = {"position": capi.SEG_STATE, "labels": capi.SEG_LABEL, "target_count": capi.SEG_TARGET_COUNT, "current_count": capi.SEG_CURRENT_COUNT}
+
+
+def _spec(spec):
+    """A segments spec checked and normalised -> (by, S, labels uint16[] or None, bounds uint64[] or None, names)."""
+    if not isinstance(spec, dict) or spec.get("by") not in SEGMENT_MODES:
+        raise ValueError("segments: a dict with by= one of %s" % ", ".join(SEGMENT_MODES))
+    by = spec["by"]
+    if by == "position":
+        S = int(spec["n"])
+        return by, S, None, None, ["t=%d" % t for t in range(1, S)] + ["t>=%d" % S]
+    if by == "labels":
+        raw = np.asarray(spec["labels"])
+        if raw.size and (raw.min() < 0 or raw.max() > 0xFFFF):
+            raise ValueError("segments: labels must be in 0..65535")
+        labels = np.ascontiguousarray(raw, dtype=np.uint16).reshape(-1)
+        S = int(spec["n"])
+        names = spec.get("names")
+        names = ["label=%d" % g for g in range(S)] if names is None else [str(x) for x in names]
+        if len(names) != S:
+            raise ValueError("segments: one name per label")
+        return by, S, labels, None, names
+    raw = [int(b) for b in spec["bounds"]]
+    if any(b < 0 or b > _M64 for b in raw):
+        raise ValueError("segments: bounds must be unsigned 64-bit counts")
+    bounds = np.array(raw, dtype=np.uint64).reshape(-1)
+    names = ["count>=0"] if not raw else ["count<%d" % raw[0]] + ["%d<=count<%d" % (a, b) for a, b in zip(raw, raw[1:])] + ["count>=%d" % raw[-1]]
+    return by, len(raw) + 1, None, bounds, names
+
+
+def _segments(spec):
+    """-> (capi.Segments, the segments' names, what the struct points into: keep it alive across the call)."""
+    by, S, labels, bounds, names = _spec(spec)
+    if not 0 <= S <= 0xFFFFFFFF:
+        raise ValueError("segments: n out of range")
+    seg = capi.Segments(SEGMENT_MODES[by], S, None if labels is None else labels.ctypes.data, 0 if labels is None else len(labels),
+                        None if bounds is None or not len(bounds) else bounds.ctypes.data, 0)
+    return seg, names, (labels, bounds)
+
+
+def _segment_report(name, r, length):
+    n = int(r.n_evaluations)
+    rep = {"name": name, "qty_evaluations": n}
+    for metric, field in _SEG_METRICS:
+        rep["%s@%d" % (metric, length)] = float(getattr(r, field)) / n if n else 0.0
+    rep["F1score@%d" % length] = float(_f1(np.float64(rep["Precision@%d" % length]), np.float64(rep["Recall@%d" % length])))
+    rep["sums"] = {field[4:]: float(getattr(r, field)) for _, field in _SEG_METRICS}
+    return rep
+
+
+def segment_ids_model(test_sessions, spec, counts=None):
+    """The segment id of every query, in set order (sessions in order, states ascending) -> uint16[n]; the rule of srn_evaluate_segments in Python, without a GPU.
+    counts: {item id: training count} of what the set holds -- the count modes read it, an id it does not hold counts 0."""
+    by, S, labels, bounds, _ = _spec(spec)
+    if S < 1:
+        raise ValueError("segments: at least one segment")
+    seqs = list(test_sessions.values() if isinstance(test_sessions, dict) else test_sessions)
+    if by == "labels" and len(labels) != len(seqs):
+        raise ValueError("segments: one label per test session")
+    if by == "labels" and len(labels) and int(labels.max()) >= S:
+        raise ValueError("segments: a label is not below n")
+    if bounds is not None and any(int(a) >= int(b) for a, b in zip(bounds, bounds[1:])):
+        raise ValueError("segments: bounds must be strictly ascending")
+    counts = {} if counts is None else counts
+    out = []
+    for s, ev in enumerate(seqs):
+        ev = list(ev)
+        for t in range(1, len(ev)):
+            if by == "position":
+                out.append(min(t, S) - 1)
+            elif by == "labels":
+                out.append(int(labels[s]))
+            else:
+                c = int(counts.get(int(ev[t] if by == "target_count" else ev[t - 1]), 0))
+                out.append(sum(1 for b in bounds if int(b) <= c))
+    return np.array(out, np.uint16)
+
+
+def segment_model(terms, ids, S, session_of_query=None, B=0, seed=0):
+    """The sums of srn_evaluate_segments, bit for bit.  terms: float64[n, 7] in TERMS order (EvalSet.terms); ids[q]: the query's segment, below S.
+    -> float64[S, 7]: per segment the number of queries, then the sums of mrr, ndcg, hit_rate, popularity, precision, recall -- per group of 256 consecutive queries
+    from +0.0 in query order over the group's queries of the segment, acc = acc + term, then the groups in order onto the total.
+    B > 0 (with session_of_query, as bootstrap_model takes it): -> (that, float64[S, B, 7]): bootstrap_model's seven sums restricted to each segment's queries, the
+    same weights and the same order rule."""
+    terms = np.asarray(terms, np.float64).reshape(-1, len(TERMS))
+    ids = np.asarray(ids, np.int64).reshape(-1)
+    S, B = int(S), int(B)
+    if len(ids) != len(terms) or (len(ids) and (ids.min() < 0 or ids.max() >= S)):
+        raise ValueError("one segment id below S per query")
+    cols = np.concatenate([np.ones((len(terms), 1)), terms[:, _BOOT_TERM_COLUMNS]], axis=1)
+    total = np.zeros((S, 1 + len(BOOTSTRAP_SUMS)))
+    rep = np.zeros((S, B, 1 + len(BOOTSTRAP_SUMS)))
+    if B:
+        sess = np.asarray(session_of_query, np.int64).reshape(-1)
+        if len(sess) != len(terms):
+            raise ValueError("one session index per query")
+        first = int(sess.min()) if len(sess) else 0
+        w_all = bootstrap_weights(seed, B, int(sess.max()) - first + 1, first).astype(np.float64) if len(sess) else np.zeros((B, 0))
+    for g0 in range(0, len(terms), GROUP):
+        acc, racc = np.zeros_like(total), np.zeros_like(rep)
+        for q in range(g0, min(g0 + GROUP, len(terms))):
+            acc[ids[q]] = acc[ids[q]] + cols[q]
+            if B:
+                racc[ids[q]] = racc[ids[q]] + w_all[:, sess[q] - first, None] * cols[q][None, :]
+        total, rep = total + acc, rep + racc
+    return (total, rep) if B else total

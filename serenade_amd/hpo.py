@@ -5,7 +5,7 @@ vmis_index.rs:325-390), and only idf_weighting is baked into an index (mod.rs:14
 idf weighting, at the largest m asked for with it, and evaluates all of that weighting's trials in one srn_evaluate call.
 
     python -m serenade_amd.hpo <config.toml> [--random N --seed S] [--exclude-seen] [--exclude-session] [--history H] [--handler-sessions] [--fill]
-                               [--bootstrap B [--seed S] [--ci C] [--ci-csv PATH]]
+                               [--bootstrap B [--seed S] [--ci C] [--ci-csv PATH]] [--segments SPEC]
 
 reads the [hyperparam] keys of the reference's configuration (training_data_path, test_data_path, save_records, out_path,
 enable_business_logic), writes exhaustive_grid_search.rs's CSV and prints its "Best ..." lines.  TPE (tpe_hyperparameter_optm.rs) is
@@ -14,6 +14,8 @@ history, handler_sessions, fill) are options of the whole search, not grid axes:
 --bootstrap B runs every trial with B bootstrap replicates (--seed seeds them too): one more line after the "Best ..." lines gives the best trial's
 Mrr interval and how many other trials are within noise of it (the interval of their paired difference to the best contains 0); the intervals go to --ci-csv, never into
 the reference's CSV.
+--segments SPEC (position:N, target_count:B1,B2,... or current_count:B1,B2,...) evaluates every trial by segment too and prints the best trial's
+metrics per segment after the "Best ..." lines; the CSV keeps the reference's columns.
 """
 import argparse
 import ctypes as C
@@ -72,12 +74,14 @@ def _build_index(sessions, m_index, idf_weighting, device):
 
 
 def search(train_path, test_path, trials, business_logic=False, device=0, how_many=20, length=20, loader="host", exclude_seen=False, exclude_session=False, history=0,
-           handler_sessions=False, fill=False, bootstrap=0, seed=0, ci=0.95):
+           handler_sessions=False, fill=False, bootstrap=0, seed=0, ci=0.95, segments=None):
     """objective() (src/objective.rs:8-52) for every trial: Mrr@length of predict(k, m, how_many) over every windowed prefix.
     loader="gpu" reads the training sessions with the GPU loader (srn_sessions_from_tsv_gpu: the same sessions).
     exclude_seen, exclude_session, history, handler_sessions, fill: the serving rules of evaluation.py, applied to every trial (fill: from the most popular
     training items, set on each index the search builds).
     bootstrap, seed, ci: evaluate()'s -- every record's report then holds its replicate arrays and intervals, paired across the search's indices.
+    segments: evaluate()'s spec -- every record's report then holds its "segments"; a by="labels" spec labels the test file's sessions in
+    ascending SessionId.
     -> {"records": [one per trial, in trial order], "best": the first record of the highest Mrr}."""
     trials = [dict(t) for t in trials]
     for i, t in enumerate(trials):   # what srn_evaluate refuses with SRN_ERANGE, said before any index is built: a store's history window is never below the session window
@@ -101,7 +105,7 @@ def search(train_path, test_path, trials, business_logic=False, device=0, how_ma
             mine = [i for i, t in enumerate(trials) if float(t["idf_weighting"]) == w]
             reps = evaluate(es, [dict(k=trials[i]["k"], m=trials[i]["m"], max_items_in_session=trials[i]["max_items_in_session"], how_many=how_many,
                                       length=length, business_logic=business_logic, exclude_seen=exclude_seen, exclude_session=exclude_session, history=history,
-                                      handler_sessions=handler_sessions, fill=fill) for i in mine], bootstrap=bootstrap, seed=seed, ci=ci)
+                                      handler_sessions=handler_sessions, fill=fill) for i in mine], bootstrap=bootstrap, seed=seed, ci=ci, segments=segments)
             for i, rep in zip(mine, reps):
                 t = trials[i]
                 records[i] = {"iteration": i, "n_most_recent_sessions": int(t["m"]), "neighborhood_size_k": int(t["k"]),
@@ -160,6 +164,29 @@ def within_noise(records, best, metric="Mrr"):
     return [(r, compare(best["report"], r["report"], metric)) for r in records if r is not best]
 
 
+def parse_segments(text):
+    """--segments: "position:8", "target_count:1,10,100" or "current_count:1,10,100" -> evaluate()'s spec (labels come from a caller, not from a command line)."""
+    by, _, arg = str(text).partition(":")
+    try:
+        if by == "position":
+            return dict(by=by, n=int(arg))
+        if by in ("target_count", "current_count"):
+            return dict(by=by, bounds=[int(x) for x in arg.split(",") if x.strip()])
+    except ValueError:
+        pass
+    raise argparse.ArgumentTypeError("--segments takes position:N, target_count:B1,B2,... or current_count:B1,B2,...")
+
+
+def segment_table(report):
+    """A report's segments as lines of text: one row per segment, the seven metrics in the report's order."""
+    keys = [k for k in report["segments"][0] if "@" in k and not k.endswith("_ci")] if report["segments"] else []
+    width = max([len(s["name"]) for s in report["segments"]] + [7])
+    lines = ["%-*s %12s %s" % (width, "segment", "evaluations", " ".join("%13s" % k for k in keys))]
+    for s in report["segments"]:
+        lines.append("%-*s %12d %s" % (width, s["name"], s["qty_evaluations"], " ".join("%13.6f" % s[k] for k in keys)))
+    return lines
+
+
 def parser():
     ap = argparse.ArgumentParser(prog="python -m serenade_amd.hpo", description="exhaustive (or random) hyper-parameter search on the GPU")
     ap.add_argument("config")
@@ -175,6 +202,8 @@ def parser():
     ap.add_argument("--bootstrap", type=int, default=0, metavar="B", help="B bootstrap replicates per trial (0: none): confidence intervals next to the point estimates")
     ap.add_argument("--ci", type=float, default=0.95, metavar="C", help="the intervals' level")
     ap.add_argument("--ci-csv", default=None, metavar="PATH", help="with --bootstrap: every trial's Mrr interval and its paired difference to the best trial")
+    ap.add_argument("--segments", type=parse_segments, default=None, metavar="SPEC", help="position:N, target_count:B1,B2,... or current_count:B1,B2,...: the best trial's "
+                    "metrics by segment, printed after the Best ... lines (the CSV keeps its columns)")
     return ap
 
 
@@ -184,7 +213,7 @@ def main(argv=None):
     trials = random(EXHAUSTIVE_GRID, a.random, a.seed) if a.random else exhaustive()
     rules = dict(exclude_seen=a.exclude_seen, exclude_session=a.exclude_session, history=a.history, handler_sessions=a.handler_sessions, fill=a.fill)
     res = search(cfg["training_data_path"], cfg["test_data_path"], trials, cfg["enable_business_logic"], a.device,
-                 loader="gpu" if a.gpu_loader else "host", bootstrap=a.bootstrap, seed=a.seed if a.bootstrap else 0, ci=a.ci, **rules)
+                 loader="gpu" if a.gpu_loader else "host", bootstrap=a.bootstrap, seed=a.seed if a.bootstrap else 0, ci=a.ci, segments=a.segments, **rules)
     with open(cfg["out_path"], "w") as f:   # exhaustive_grid_search.rs:34-46 (the file is created either way)
         if cfg["save_records"]:
             f.write("iteration,n_most_recent_sessions,neighborhood_size_k,last_items_in_session,idf_weighting,%s\n" % GOAL)
@@ -201,6 +230,10 @@ def main(argv=None):
     print("Best idf_weighting: %d" % (-1 if none else int(b["idf_weighting"])))
     print("Business logic were %s." % ("enabled" if cfg["enable_business_logic"] else "disabled"))
     print("Best value for the goal metric: %s" % rust_f64(float("-inf") if none else b[GOAL]))
+    if a.segments is not None and not none:
+        print("Best trial by segment (%s):" % a.segments["by"])
+        for line in segment_table(b["report"]):
+            print(line)
     if a.bootstrap and not none:
         key = [k for k in b["report"] if k.startswith("Mrr@") and k.endswith("_ci")][0]
         lo, hi = b["report"][key]

@@ -16,6 +16,13 @@ B (default 256 and 1024); medians of the wall times.  The yardstick of the cost 
 call without bootstrap moved.  Writes profiles/eval_bootstrap_<config>.json.
 
     python tools/eval_bench.py --bootstrap [256 1024] [--reps 5] [--parent-lib PATH | --skip-parent]
+
+--segments: what the segments of DESIGN.md 10.4 cost.  The same trial alternates in one process, --reps rounds (default 5), medians of the wall times: without a
+bootstrap through the parent commit's library (as above), srn_evaluate of this library, srn_evaluate_segments with position:8 and with 64 label segments; with one,
+srn_evaluate_bootstrap at B = 256 and srn_evaluate_segments at B = 256 with position:8.  The segment kernels alone come from HIP events (srn_debug_eval_segment_ms),
+next to ms_eval of the same call.  Writes profiles/eval_segments_<config>.json.
+
+    python tools/eval_bench.py --segments [--reps 5] [--parent-lib PATH | --skip-parent]
 """
 import argparse
 import ctypes as C
@@ -154,6 +161,63 @@ def bootstrap_arms(a, es, trial, res, parent):
     print(json.dumps(res))
 
 
+def segment_arms(a, es, trial, res, parent):
+    from serenade_amd import capi, evaluation
+    B = 256
+    n_sessions = res["test_sessions"]
+    position, labels = dict(by="position", n=8), dict(by="labels", labels=np.arange(n_sessions) % 64, n=64)
+    arms = {}
+    if parent:
+        t_parent = evaluation._trial(trial)
+        arms["parent_plain"] = lambda: parent.evaluate(t_parent).sum_mrr
+    arms["plain"] = lambda: evaluation.evaluate(es, [trial])[0]
+    arms["position_8"] = lambda: evaluation.evaluate(es, [trial], segments=position)[0]
+    arms["labels_64"] = lambda: evaluation.evaluate(es, [trial], segments=labels)[0]
+    arms["bootstrap_%d" % B] = lambda: evaluation.evaluate(es, [trial], bootstrap=B, seed=1)[0]
+    arms["bootstrap_%d_position_8" % B] = lambda: evaluation.evaluate(es, [trial], bootstrap=B, seed=1, segments=position)[0]
+    out = {n: {"wall_ms": [], "ms_eval": [], "ms_segments": [], "ms_segment_bootstrap": []} for n in arms}
+    for f in arms.values():   # first calls size the workspaces
+        f()
+    ms = (C.c_double(), C.c_double())
+    for _ in range(a.reps):
+        for n, f in arms.items():
+            t0 = time.perf_counter()
+            got = f()
+            out[n]["wall_ms"].append(round((time.perf_counter() - t0) * 1e3, 4))
+            if n == "parent_plain":
+                out[n]["sum_mrr"] = got
+                continue
+            out[n]["sum_mrr"] = got["sums"]["mrr"]
+            out[n]["ms_eval"].append(round(got["ms_eval"], 4))
+            if "segments" in got:
+                capi.check(capi.lib().srn_debug_eval_segment_ms(es._h, C.byref(ms[0]), C.byref(ms[1])))
+                out[n]["ms_segments"].append(round(ms[0].value, 4))
+                out[n]["ms_segment_bootstrap"].append(round(ms[1].value, 4))
+                out[n]["segment_evaluations"] = [x["qty_evaluations"] for x in got["segments"]]
+                if sum(out[n]["segment_evaluations"]) != got["qty_evaluations"]:
+                    raise SystemExit("%s: the segments' queries do not add up" % n)
+    if len({o["sum_mrr"] for o in out.values()}) != 1:
+        raise SystemExit("the arms' Mrr sums differ: %s" % {n: o["sum_mrr"] for n, o in out.items()})
+    med = lambda v: round(float(np.median(v)), 4) if len(v) else None   # noqa: E731
+    for o in out.values():
+        o["wall_ms_median"], o["wall_ms_spread"] = med(o["wall_ms"]), round(max(o["wall_ms"]) - min(o["wall_ms"]), 4)
+        for key in ("ms_eval", "ms_segments", "ms_segment_bootstrap"):
+            o[key + "_median"] = med(o[key])
+    res.update({"reps": a.reps, "seed": 1, "replicates": B, "parent_lib": bool(parent), "arms": out})
+    plain, boot = out["plain"]["wall_ms_median"], out["bootstrap_%d" % B]["wall_ms_median"]
+    res["position_8_minus_plain_ms"] = round(out["position_8"]["wall_ms_median"] - plain, 4)
+    res["labels_64_minus_plain_ms"] = round(out["labels_64"]["wall_ms_median"] - plain, 4)
+    res["bootstrap_minus_plain_ms"] = round(boot - plain, 4)
+    res["segmented_bootstrap_minus_bootstrap_ms"] = round(out["bootstrap_%d_position_8" % B]["wall_ms_median"] - boot, 4)
+    res["naive_segmented_bootstrap_ms"] = round(8 * (boot - plain), 4)   # boot_group_kernel once per segment: S times the bootstrap's added cost
+    if parent:
+        res["plain_minus_parent_ms"] = round(plain - out["parent_plain"]["wall_ms_median"], 4)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="cfg3")
@@ -166,15 +230,16 @@ def main():
     ap.add_argument("--serving", action="store_true", help="the serving-rule arms instead of (a), (b), (c) and the grid")
     ap.add_argument("--history", type=int, default=8, help="--serving: H' (>= --window)")
     ap.add_argument("--bootstrap", type=int, nargs="*", default=None, metavar="B", help="the bootstrap arms (default B: 256 1024) instead of (a), (b), (c) and the grid")
-    ap.add_argument("--parent-lib", default=os.path.join(ROOT, "serenade_amd", "variants", "libserenade_hip_parent.so"), help="--bootstrap: the parent commit's library")
+    ap.add_argument("--segments", action="store_true", help="the segment arms (DESIGN.md 10.4) instead of (a), (b), (c) and the grid")
+    ap.add_argument("--parent-lib", default=os.path.join(ROOT, "serenade_amd", "variants", "libserenade_hip_parent.so"), help="--bootstrap, --segments: the parent commit's library")
     ap.add_argument("--skip-parent", action="store_true", help="--bootstrap: no parent arm; the run then cannot tell whether the plain call moved")
     a = ap.parse_args()
     if a.reps is None:
-        a.reps = 5 if a.bootstrap is not None else 3
+        a.reps = 5 if a.bootstrap is not None or a.segments else 3
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "eval_bootstrap_%s.json" % a.config if a.bootstrap is not None else
+        a.out = os.path.join(ROOT, "profiles", "eval_segments_%s.json" % a.config if a.segments else "eval_bootstrap_%s.json" % a.config if a.bootstrap is not None else
                              "eval_serving_%s.json" % a.config if a.serving else "eval_bench_cfg3.json")
-    if a.bootstrap is not None and not a.skip_parent and not os.path.exists(a.parent_lib):
+    if (a.bootstrap is not None or a.segments) and not a.skip_parent and not os.path.exists(a.parent_lib):
         raise SystemExit("the parent commit's library %s is missing: build it from the parent commit and pass --parent-lib, or pass --skip-parent" % a.parent_lib)
     import torch
     import serenade_amd as sa
@@ -204,6 +269,15 @@ def main():
 
     if a.serving:
         serving_arms(a, es, trial, res)
+        return
+    if a.segments:
+        parent = None
+        if not a.skip_parent:
+            parent = ParentLibrary(a.parent_lib, capi)
+            parent.eval_set(off, items, ts, m, 34, idfw, sessions)
+        segment_arms(a, es, trial, res, parent)
+        if parent:
+            parent.close()
         return
     if a.bootstrap is not None:
         parent = None
