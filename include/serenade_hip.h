@@ -193,6 +193,29 @@ int srn_index_build(const srn_sessions_view_t* sessions, size_t m_index, size_t 
  * Bit-identical to srn_index_build(); 582 M interactions take seconds instead of ~45 s on one host core. */
 int srn_index_build_gpu(const srn_sessions_view_t* sessions, size_t m_index, size_t max_session_len,
                         double idf_weighting, int device, srn_index_t** out);
+/* srn_sessions_from_events + srn_index_build_gpu in one call, with nothing large on the host in between: n event rows passed exactly as to srn_sessions_from_events
+ * (host arrays are uploaded once; SRN_EVENTS_DEVICE arrays are read in place on `stream`) are grouped, built and attached on `device`.  max_session_len = 0: the exact
+ * p99.5 of the session lengths, from a histogram kernel.  The index is the one srn_index_build_gpu gives for those sessions, bit for bit -- every predict call, every
+ * accessor and srn_index_save see the same bytes -- but its host copy is LAZY: the scalars and the per-item arrays (ids, idf, attributes, posting offsets, the id table)
+ * are on the host from the start, while the posting lists, the rows and the rank -> session map stay on the device until a call that reads them on the host asks:
+ * srn_index_save, srn_index_postings, srn_index_items_for_session, srn_index_session_recency, srn_find_neighbors and the neighbour dump of srn_predict_batch_debug,
+ * srn_index_shard, srn_index_postings_view.  That first call downloads them once (under a mutex; concurrent callers wait) and frees the device copies serving does not
+ * read.  Predict, evaluate, recommend, the result cache, the fallback rankings, srn_index_set_attributes, srn_index_info and the evaluation sets never trigger it.
+ * Unsharded only.  Errors as the two calls it replaces: a NULL array or out, unknown flags, n = 0, m_most_recent_sessions = 0: SRN_EINVAL; device < 0: SRN_ENODEV;
+ * n >= 2^32 - 1: SRN_ERANGE. */
+int srn_index_from_events_device(const uint64_t* session_ids, const uint64_t* item_ids, const void* times, size_t n, unsigned flags, size_t m_most_recent_sessions,
+                                 double idf_weighting, size_t max_session_len, int device, void* stream, srn_index_t** out);
+typedef struct {
+    int32_t host_complete;          /* 1: every array of the index is on the host (always, unless srn_index_from_events_device built it and no host reader has asked yet) */
+    int32_t reserved;
+    uint64_t build_bytes_on_device; /* device bytes held only for the deferred download (part of srn_index_info's device_bytes); 0 once host_complete */
+    uint64_t materialisations;      /* downloads of the large arrays so far: 0 or 1 */
+    double ms_upload, ms_group, ms_quantile, ms_build, ms_items, ms_attach; /* srn_index_from_events_device's stages: host rows up | times + grouping | the length
+                                     * quantile | the builder's sorts and scans | per-item arrays down + idf + id table | row slots and the rest of the attach; else 0 */
+    double ms_materialize;          /* the deferred download, once it has happened */
+} srn_index_host_state_t;
+int srn_index_host_state(const srn_index_t* idx, srn_index_host_state_t* out);
+int srn_index_materialize(srn_index_t* idx); /* bring the host copy up to date now; idempotent, SRN_OK on any index */
 /* VMISIndex::new_from_csv(path, m_most_recent_sessions, idf_weighting) (vmis_index.rs:38-83);
  * max_session_len = 0 selects the exact p99.5 of the session lengths. */
 int srn_index_new_from_csv(const char* path, size_t m_most_recent_sessions, double idf_weighting,

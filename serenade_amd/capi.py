@@ -32,6 +32,11 @@ class IndexInfo(C.Structure):
                [("device", C.c_int32), ("offsets_64bit", C.c_int32), ("idf_weighting", C.c_double), ("incomplete_items", C.c_uint64)]
 
 
+class IndexHostState(C.Structure):   # srn_index_host_state_t
+    _fields_ = [("host_complete", C.c_int32), ("reserved", C.c_int32), ("build_bytes_on_device", C.c_uint64), ("materialisations", C.c_uint64)] + \
+               [(n, C.c_double) for n in ("ms_upload", "ms_group", "ms_quantile", "ms_build", "ms_items", "ms_attach", "ms_materialize")]
+
+
 class ShardGroupStats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("n_shards", "batches", "queries", "bytes_head", "bytes_counts", "bytes_lists", "bytes_results", "bytes_lists_max_rank")] + \
                [("transport", C.c_uint32), ("overlapped", C.c_uint32)] + [(n, C.c_uint64) for n in ("stage_batches", "bytes_stage_candidates", "bytes_stage_minpos", "neighbour_batches", "bytes_neighbours")]
@@ -162,6 +167,9 @@ SYMBOLS = {
     "srn_index_build": (_i, [C.POINTER(SessionsView), _sz, _sz, C.c_double, _i, C.POINTER(_vp)]),
     "srn_index_new_from_avro": (_i, [C.c_char_p, _i, C.POINTER(_vp)]),
     "srn_index_build_gpu": (_i, [C.POINTER(SessionsView), _sz, _sz, C.c_double, _i, C.POINTER(_vp)]),
+    "srn_index_from_events_device": (_i, [_vp, _vp, _vp, _sz, C.c_uint, _sz, C.c_double, _sz, _i, _vp, C.POINTER(_vp)]),
+    "srn_index_host_state": (_i, [_vp, C.POINTER(IndexHostState)]),
+    "srn_index_materialize": (_i, [_vp]),
     "srn_index_new_from_csv": (_i, [C.c_char_p, _sz, C.c_double, _sz, _i, C.POINTER(_vp)]),
     "srn_index_save": (_i, [_vp, C.c_char_p]),
     "srn_index_load": (_i, [C.c_char_p, _i, C.POINTER(_vp)]),

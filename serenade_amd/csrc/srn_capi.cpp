@@ -1,6 +1,7 @@
 // C ABI of libserenade_hip.so (include/serenade_hip.h): argument validation, error codes, handle
 // ownership.  No compute happens here -- predict calls go to the HIP kernels or fail.
 #include <algorithm>
+#include <chrono>
 #include <cstring>
 #include <new>
 #include <vector>
@@ -9,6 +10,21 @@
 
 namespace srn { const char* last_error_cstr(); int device_count(); }
 using namespace srn;
+
+// The one door to post_rank, row_off, row_items and rank_to_session on the host.  An index from srn_index_from_events_device keeps them on the device until the first
+// caller comes through here; every other index passes straight through
+const FlatIndex* srn::host_flat(const srn_index* idx) {
+    if (idx->host_complete.load(std::memory_order_acquire)) return &idx->flat;
+    std::lock_guard<std::mutex> lk(idx->host_mu);
+    if (!idx->host_complete.load(std::memory_order_relaxed)) {
+        const auto t0 = std::chrono::steady_clock::now();
+        if (device_materialize(idx->dev, const_cast<FlatIndex&>(idx->flat)) != SRN_OK) return nullptr;
+        idx->ms_materialize = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        ++idx->materialisations;
+        idx->host_complete.store(true, std::memory_order_release);
+    }
+    return &idx->flat;
+}
 
 namespace {
 
@@ -63,12 +79,14 @@ int predict_host(const srn_index_t* idx, const uint64_t* items_flat, const uint3
                              HostRows{items_flat, q_off, out_ids, out_scores, out_counts, out_stats, out_nb_sessions, out_nb_num, out_nb_counts});
     if (rc) return rc;
     rc = check_all_served(out_counts, nq); if (rc) return rc;
-    if (out_nb_sessions)   // recency rank -> reference session index
+    if (out_nb_sessions) {   // recency rank -> reference session index
+        const FlatIndex* hf = host_flat(idx); if (!hf) return SRN_EHIP;
         for (size_t q = 0; q < nq; ++q)
             for (uint32_t j = 0; j < out_nb_counts[q]; ++j) {
                 uint32_t& r = out_nb_sessions[q * k + j];
-                r = idx->flat.rank_to_session[r];
+                r = hf->rank_to_session[r];
             }
+    }
     return SRN_OK;
 }
 }  // namespace
@@ -186,6 +204,35 @@ int srn_index_build_gpu(const srn_sessions_view_t* sessions, size_t m_index, siz
         return finish_index(ix, build_flat_index_gpu(*sessions, m_index, max_session_len, idf_weighting, device, ix->flat), device, out); });   // (device >= 0: checked above)
 }
 
+int srn_index_from_events_device(const uint64_t* session_ids, const uint64_t* item_ids, const void* times, size_t n, unsigned flags, size_t m_most_recent_sessions,
+                                 double idf_weighting, size_t max_session_len, int device, void* stream, srn_index_t** out) {
+    return guarded([&]() -> int {
+        if (!out || (n && (!session_ids || !item_ids || !times))) return fail(SRN_EINVAL, "null argument");
+        *out = nullptr;
+        if (flags & ~(SRN_EVENTS_TIME_I64 | SRN_EVENTS_DEVICE)) return fail(SRN_EINVAL, "unknown flags");
+        if (device < 0) return fail(SRN_ENODEV, "the GPU loader and the GPU index builder need a device");
+        if (n == 0) return fail(SRN_EINVAL, "no training rows");
+        if (n >= 0xFFFFFFFFull) return fail(SRN_ERANGE, "the GPU loader groups < 2^32 rows per call; use the host loader");
+        if (m_most_recent_sessions == 0) return fail(SRN_EINVAL, "m_index must be > 0");
+        srn_index* ix = new srn_index();
+        int rc = index_from_events_device(session_ids, item_ids, times, n, flags, m_most_recent_sessions, idf_weighting, max_session_len, device, stream, ix);
+        if (rc) { if (ix->dev) device_release(ix->dev); delete ix; return rc; }
+        ix->comb = combiner_create();
+        *out = ix; return SRN_OK; });
+}
+int srn_index_host_state(const srn_index_t* idx, srn_index_host_state_t* out) {
+    if (!idx || !out) return fail(SRN_EINVAL, "null argument");
+    std::lock_guard<std::mutex> lk(idx->host_mu);
+    *out = idx->build_state;
+    out->host_complete = idx->host_complete.load() ? 1 : 0; out->reserved = 0;
+    out->build_bytes_on_device = device_residue_bytes(idx->dev); out->materialisations = idx->materialisations; out->ms_materialize = idx->ms_materialize;
+    return SRN_OK;
+}
+int srn_index_materialize(srn_index_t* idx) {
+    if (!idx) return fail(SRN_EINVAL, "null index");
+    return guarded([&]() -> int { return host_flat(idx) ? SRN_OK : SRN_EHIP; });
+}
+
 int srn_index_new_from_csv(const char* path, size_t m_most_recent_sessions, double idf_weighting, size_t max_session_len,
                            int device, srn_index_t** out) {
     return guarded([&]() -> int {
@@ -224,7 +271,10 @@ int srn_index_new_from_avro(const char* base_path, int device, srn_index_t** out
 
 int srn_index_save(const srn_index_t* idx, const char* path) {
     if (!idx || !path) return fail(SRN_EINVAL, "null argument");
-    return guarded([&]() -> int { int rc = check_has_rows(idx->flat, "srn_index_save"); if (rc) return rc; return save_flat_index(idx->flat, path); });
+    return guarded([&]() -> int {
+        int rc = check_has_rows(idx->flat, "srn_index_save"); if (rc) return rc;
+        const FlatIndex* hf = host_flat(idx); if (!hf) return SRN_EHIP;
+        return save_flat_index(*hf, path); });
 }
 int srn_index_load(const char* path, int device, srn_index_t** out) {
     return guarded([&]() -> int {
@@ -287,7 +337,7 @@ int srn_index_clear_fallback(srn_index_t* idx) {
 }
 int srn_index_info(const srn_index_t* idx, srn_index_info_t* out) {
     if (!idx || !out) return fail(SRN_EINVAL, "null argument");
-    const FlatIndex& f = idx->flat;
+    const FlatIndex& f = idx->flat;   // (post_rank is read for a pre-built index alone: never one with a lazy host copy)
     uint64_t incomplete = 0;
     if (!f.lists_complete && f.viol.size() == f.n_items)
         for (uint64_t i = 0; i < f.n_items; ++i) { const uint64_t len = f.post_off[i + 1] - f.post_off[i];
@@ -305,9 +355,12 @@ int srn_index_postings(const srn_index_t* idx, uint64_t item_id, uint32_t* out_s
     if (j == kNone) { *out_len = -1; return SRN_OK; }
     const uint64_t o0 = f.post_off[j], o1 = f.post_off[j + 1];
     *out_len = (int64_t)(o1 - o0);
-    if (out_sessions) for (uint64_t t = o0; t < o1 && t - o0 < cap; ++t) out_sessions[t - o0] = f.rank_to_session[f.post_rank[t]];
     if (out_idf) *out_idf = f.idf[j];
-    return SRN_OK;
+    if (!out_sessions) return SRN_OK;   // (length and idf are per-item: no host copy of the lists needed)
+    return guarded([&]() -> int {
+        const FlatIndex* hf = host_flat(idx); if (!hf) return SRN_EHIP;
+        for (uint64_t t = o0; t < o1 && t - o0 < cap; ++t) out_sessions[t - o0] = hf->rank_to_session[hf->post_rank[t]];
+        return SRN_OK; });
 }
 // ---- the rest of SimilarityComputationNew (src/vmisknn/similarity_indexed.rs:9-23) at the ABI: with srn_index_postings (+ idf) above, a maintainer can write
 // `impl SimilarityComputationNew for HipVMISIndex`, not only swap the free function predict ----
@@ -315,10 +368,11 @@ int srn_index_items_for_session(const srn_index_t* idx, uint32_t session, uint64
     return guarded([&]() -> int {
         if (!idx || !out_len) return fail(SRN_EINVAL, "null argument");
         *out_len = 0;
-        const FlatIndex& f = idx->flat;
-        int rc = check_has_rows(f, "srn_index_items_for_session"); if (rc) return rc;
-        if (f.n_shards > 1) return fail(SRN_EINVAL, "an item shard holds row FRAGMENTS (the items it owns): ask the unsharded index");
-        if (session >= f.n_sessions_total) return fail(SRN_EINVAL, "no such session (the reference indexes out of bounds: vmis_index.rs:317-319)");
+        int rc = check_has_rows(idx->flat, "srn_index_items_for_session"); if (rc) return rc;
+        if (idx->flat.n_shards > 1) return fail(SRN_EINVAL, "an item shard holds row FRAGMENTS (the items it owns): ask the unsharded index");
+        if (session >= idx->flat.n_sessions_total) return fail(SRN_EINVAL, "no such session (the reference indexes out of bounds: vmis_index.rs:317-319)");
+        const FlatIndex* hf = host_flat(idx); if (!hf) return SRN_EHIP;
+        const FlatIndex& f = *hf;
         std::call_once(idx->s2r_once, [&] { idx->session_to_rank.assign(f.n_sessions_total, kNone); for (uint64_t r = 0; r < f.n_kept; ++r) idx->session_to_rank[f.rank_to_session[r]] = (uint32_t)r; });
         const uint32_t r = idx->session_to_rank[session];
         // (the reference keeps the rows of ALL sessions, vmis_index.rs:79, but only sessions of <= max_session_len items enter the posting lists, :452 -- and only those can
@@ -332,9 +386,10 @@ int srn_index_items_for_session(const srn_index_t* idx, uint32_t session, uint64
 int srn_index_session_recency(const srn_index_t* idx, uint32_t* out_rank, size_t cap) {
     return guarded([&]() -> int {
         if (!idx || !out_rank) return fail(SRN_EINVAL, "null argument");
-        const FlatIndex& f = idx->flat;
-        int rc = check_has_rows(f, "srn_index_session_recency"); if (rc) return rc;
-        if (cap < f.n_sessions_total) return fail(SRN_EINVAL, "room for n_sessions entries needed");
+        int rc = check_has_rows(idx->flat, "srn_index_session_recency"); if (rc) return rc;
+        if (cap < idx->flat.n_sessions_total) return fail(SRN_EINVAL, "room for n_sessions entries needed");
+        const FlatIndex* hf = host_flat(idx); if (!hf) return SRN_EHIP;
+        const FlatIndex& f = *hf;
         std::fill(out_rank, out_rank + f.n_sessions_total, kNone);
         for (uint64_t r = 0; r < f.n_kept; ++r) out_rank[f.rank_to_session[r]] = (uint32_t)r;
         return SRN_OK; });
@@ -365,10 +420,11 @@ int srn_find_neighbors(const srn_index_t* idx, const uint64_t* evolving, size_t 
         if (cnt == 0xFFFFFFFFu) return fail(SRN_ERANGE, "the query exceeded the kernel's table limits");
         size_t U = 0;   // distinct raw ids, known or not (vmis_index.rs:334-352: the decay's denominator)
         for (size_t i = 0; i < len; ++i) { bool first = true; for (size_t j = 0; j < i; ++j) first = first && evolving[j] != evolving[i]; U += first; }
+        const FlatIndex* hf = host_flat(idx); if (!hf) return SRN_EHIP;
         std::vector<uint32_t> ord(nb_cnt);
         for (uint32_t i = 0; i < nb_cnt; ++i) ord[i] = i;
         std::sort(ord.begin(), ord.end(), [&](uint32_t a, uint32_t b) { return nb_num[a] != nb_num[b] ? nb_num[a] > nb_num[b] : nb_rank[a] > nb_rank[b]; });
-        for (uint32_t i = 0; i < nb_cnt; ++i) { out_sessions[i] = idx->flat.rank_to_session[nb_rank[ord[i]]]; out_scores[i] = (double)nb_num[ord[i]] / (double)U; }
+        for (uint32_t i = 0; i < nb_cnt; ++i) { out_sessions[i] = hf->rank_to_session[nb_rank[ord[i]]]; out_scores[i] = (double)nb_num[ord[i]] / (double)U; }
         *out_n = nb_cnt;
         return SRN_OK; });
 }
@@ -600,8 +656,9 @@ int srn_index_shard(const srn_index_t* full, uint32_t shard, uint32_t n_shards, 
         if (!full || !out) return fail(SRN_EINVAL, "null argument");
         *out = nullptr;
         { int rc0 = check_has_rows(full->flat, "srn_index_shard"); if (rc0) return rc0; }
+        const FlatIndex* hf = host_flat(full); if (!hf) return SRN_EHIP;
         srn_index* ix = new srn_index();
-        return finish_index(ix, shard_flat_index(full->flat, shard, n_shards, ix->flat), device, out); });
+        return finish_index(ix, shard_flat_index(*hf, shard, n_shards, ix->flat), device, out); });
 }
 // The replicated part of an item-sharded index: the whole index's dictionary, idf / attributes and posting lists WITHOUT its rows (config 5: ~10 GB of the 66.6 GB)
 int srn_index_postings_view(const srn_index_t* full, int device, srn_index_t** out) {
@@ -611,8 +668,9 @@ int srn_index_postings_view(const srn_index_t* full, int device, srn_index_t** o
         if (full->flat.n_shards != 1) return fail(SRN_EINVAL, "the postings view is cut from an UNSHARDED index");
         { int rc0 = check_has_rows(full->flat, "srn_index_postings_view"); if (rc0) return rc0; }
         if (device < 0) return fail(SRN_ENODEV, "a postings view lives on a device");
+        const FlatIndex* hf = host_flat(full); if (!hf) return SRN_EHIP;
         srn_index* ix = new srn_index();
-        const FlatIndex& f = full->flat; FlatIndex& g = ix->flat;
+        const FlatIndex& f = *hf; FlatIndex& g = ix->flat;
         g.n_items = f.n_items; g.n_sessions_total = f.n_sessions_total; g.n_kept = f.n_kept; g.nnz_rows = 0; g.nnz_post = f.nnz_post; g.m_index = f.m_index;
         g.max_session_len = f.max_session_len; g.max_row_len = f.max_row_len /* (of the index the lists belong to: the shard group derives its choice of pipeline from it, the same on every rank) */; g.idf_weighting = f.idf_weighting; g.lists_complete = f.lists_complete; g.postings_only = true;
         g.total_pairs = f.total_pairs; g.item_id = f.item_id; g.id_rank = f.id_rank; g.idf = f.idf; g.attr = f.attr; g.post_off = f.post_off; g.post_rank = f.post_rank;

@@ -1,6 +1,7 @@
 // Click-log rows on the device: what the loader (srn_ingest.hip), the splitter (srn_split.hip) and the evaluation set built from events (srn_eval.hip) share.
 //   round_time / event_time   the loader's rounding of a time field, and a row's rounded seconds straight from the caller's f64 or i64 column
 //   DevBuf                    a device allocation that frees itself
+//   DevSessions / DevFlat     grouped sessions and a built index's arrays while they are still on the device: the seams of srn_index_from_events_device
 //   KeyTable                  open addressing on full 64-bit keys: a key's slot index is its dense handle for the rest of a call
 //   CombTable                 a block's LDS table that combines equal slots before a count reaches global memory
 // Include after srn_hipsync.h (DevBuf frees).
@@ -52,6 +53,25 @@ inline int check_device_rows(const void* p, int device, const char* what) {
 // rows of a TSV file, parsed on the device (srn_ingest.hip): three device arrays in file order, times rounded; host-parsed lines patched in, skipped lines compacted away
 struct TsvRows { DevBuf s, i, t; uint64_t n = 0; };
 int tsv_rows_device(const char* path, int device, hipStream_t st, TsvRows& out, srn_load_info_t& li);
+
+// grouped training sessions on the device (group_rows_device_core, srn_ingest.hip): what Sessions holds on the host, before any download
+struct DevSessions { DevBuf off, items, ts, session_ids; uint64_t n_sessions = 0, nnz = 0; };
+int group_rows_device_core(const uint64_t* sess, const uint64_t* item, const uint64_t* time, size_t n, hipStream_t st, DevSessions& out, srn_load_info_t* info);
+// srn_sessions_from_events up to the grouping, nothing downloaded (arguments already checked by the C ABI glue)
+int device_sessions_from_events(const uint64_t* session_ids, const uint64_t* item_ids, const void* times, size_t n, unsigned flags, int device, void* stream,
+                                DevSessions& out, srn_load_info_t* info);
+// sessions_length_quantile_counting on device offsets: a histogram kernel over the lengths 0..4095 (+ a count and a maximum of the longer ones), finished on the host;
+// an order statistic in the overflow bin downloads the offsets and counts there
+int device_length_quantile(const uint64_t* d_off, uint64_t n_sessions, double q, hipStream_t st, uint64_t* out);
+
+// ---- the index builder's device side (srn_build_gpu.hip) ------------------------------------------
+// what build_flat_index_core leaves on the device: the four large arrays of a FlatIndex and its per-item arrays (counts by dense idx feed the idf)
+struct DevFlat { DevBuf post_rank, row_off, row_items, rank_to_session, item_id, id_rank, count, post_off; };
+// device session arrays -> DevFlat + the scalars of ix (n_kept, nnz_*, n_items, max_row_len ...); nothing but scalars comes back
+int build_flat_index_core(const uint64_t* d_off, const uint64_t* d_items, const uint32_t* d_ts, uint64_t n_sessions, uint64_t nnz_in, size_t m_index, size_t max_session_len,
+                          double idf_weighting, FlatIndex& ix, DevFlat& out);
+// the per-item arrays to the host, then idf (the host's std::log), default attributes and the id table
+int build_flat_index_items(const DevFlat& dev, FlatIndex& ix);
 
 // ---- open addressing on the full key -----------------------------------------------------------
 // keys[0 .. mask] start as kEmptyKey (memset 0xFF); slot mask + 1 belongs to the key that IS kEmptyKey.  A slot goes from empty to its key once and never changes, so a

@@ -354,8 +354,8 @@ size_t chunk_bytes() { std::call_once(g_chunk_once, read_chunk_knob); return g_c
 
 void ingest_reload_knobs() { std::call_once(g_chunk_once, read_chunk_knob); read_chunk_knob(); }
 
-// rows (device, file order, times rounded) -> sessions on the host
-int group_rows_device(const uint64_t* sess, const uint64_t* item, const uint64_t* time, size_t n, hipStream_t st, Sessions& out, srn_load_info_t* info) {
+// rows (device, file order, times rounded) -> sessions on the device
+int group_rows_device_core(const uint64_t* sess, const uint64_t* item, const uint64_t* time, size_t n, hipStream_t st, DevSessions& out, srn_load_info_t* info) {
     if (n == 0) return fail(SRN_EINVAL, "no training rows");
     if (n >= 0xFFFFFFFFull) return fail(SRN_ERANGE, "the GPU loader groups < 2^32 rows per call; use the host loader");
     auto t0 = std::chrono::steady_clock::now();
@@ -411,30 +411,40 @@ int group_rows_device(const uint64_t* sess, const uint64_t* item, const uint64_t
     ING_TRY(hipGetLastError());
     ING_TRY(hipStreamSynchronize(st));
     if (info) info->ms_group = ms_since(t0);
-    // 4. download
-    t0 = std::chrono::steady_clock::now();
+    std::swap(out.off.p, d_off.p); std::swap(out.items.p, c_item.p); std::swap(out.ts.p, d_ts.p); std::swap(out.session_ids.p, d_sid.p);   // (what `out` held before goes with the locals)
+    out.n_sessions = ns; out.nnz = m;
+    return SRN_OK;
+}
+
+// ... -> sessions on the host: the core, then the download
+int group_rows_device(const uint64_t* sess, const uint64_t* item, const uint64_t* time, size_t n, hipStream_t st, Sessions& out, srn_load_info_t* info) {
+    DevSessions d;
+    int rc = group_rows_device_core(sess, item, time, n, st, d, info); if (rc) return rc;
+    const uint64_t ns = d.n_sessions, m = d.nnz;
+    auto t0 = std::chrono::steady_clock::now();
     out = Sessions();
     out.off.resize(ns + 1); out.items.resize(m); out.ts.resize(ns); out.session_ids.resize(ns);
-    ING_TRY(hipMemcpyAsync(out.off.data(), d_off.p, (ns + 1) * 8, hipMemcpyDeviceToHost, st));
-    if (m) ING_TRY(hipMemcpyAsync(out.items.data(), c_item.p, m * 8, hipMemcpyDeviceToHost, st));
+    ING_TRY(hipMemcpyAsync(out.off.data(), d.off.p, (ns + 1) * 8, hipMemcpyDeviceToHost, st));
+    if (m) ING_TRY(hipMemcpyAsync(out.items.data(), d.items.p, m * 8, hipMemcpyDeviceToHost, st));
     if (ns) {
-        ING_TRY(hipMemcpyAsync(out.ts.data(), d_ts.p, ns * 4, hipMemcpyDeviceToHost, st));
-        ING_TRY(hipMemcpyAsync(out.session_ids.data(), d_sid.p, ns * 8, hipMemcpyDeviceToHost, st));
+        ING_TRY(hipMemcpyAsync(out.ts.data(), d.ts.p, ns * 4, hipMemcpyDeviceToHost, st));
+        ING_TRY(hipMemcpyAsync(out.session_ids.data(), d.session_ids.p, ns * 8, hipMemcpyDeviceToHost, st));
     }
     ING_TRY(hipStreamSynchronize(st));
     if (info) info->ms_download = ms_since(t0);
     return SRN_OK;
 }
 
-int sessions_from_events(const uint64_t* sess, const uint64_t* item, const void* times, size_t n, unsigned flags, int device, void* stream, Sessions& out,
-                         srn_load_info_t* info) {
+namespace {
+// the rows of an in-memory call on the device, times rounded: host arrays are uploaded once, device arrays read in place
+struct EventRows { DevBuf d_s, d_i, d_tin, d_t; const uint64_t* s = nullptr; const uint64_t* i = nullptr; };
+int event_rows_device(const uint64_t* sess, const uint64_t* item, const void* times, size_t n, unsigned flags, int device, hipStream_t st, EventRows& r, srn_load_info_t* info) {
     if (n == 0) return fail(SRN_EINVAL, "no training rows");
     if (n >= 0xFFFFFFFFull) return fail(SRN_ERANGE, "the GPU loader groups < 2^32 rows per call; use the host loader");
     ING_TRY(hipSetDevice(device));
-    hipStream_t st = (hipStream_t)stream;
     const bool on_device = flags & SRN_EVENTS_DEVICE;
     auto t0 = std::chrono::steady_clock::now();
-    DevBuf d_s, d_i, d_tin, d_t;
+    DevBuf& d_s = r.d_s; DevBuf& d_i = r.d_i; DevBuf& d_tin = r.d_tin; DevBuf& d_t = r.d_t;
     const uint64_t* ps = sess; const uint64_t* pi = item; const void* pt = times;
     if (!on_device) {
         ING_TRY(d_s.alloc(n * 8)); ING_TRY(d_i.alloc(n * 8)); ING_TRY(d_tin.alloc(n * 8));
@@ -452,7 +462,22 @@ int sessions_from_events(const uint64_t* sess, const uint64_t* item, const void*
     ING_TRY(hipGetLastError());
     ING_TRY(hipStreamSynchronize(st));
     if (info) { info->ms_parse = ms_since(t0); info->lines = n; info->rows = n; }
-    return group_rows_device(ps, pi, d_t.as<uint64_t>(), n, st, out, info);
+    r.s = ps; r.i = pi;
+    return SRN_OK;
+}
+}  // namespace
+
+int sessions_from_events(const uint64_t* sess, const uint64_t* item, const void* times, size_t n, unsigned flags, int device, void* stream, Sessions& out,
+                         srn_load_info_t* info) {
+    EventRows r;
+    int rc = event_rows_device(sess, item, times, n, flags, device, (hipStream_t)stream, r, info); if (rc) return rc;
+    return group_rows_device(r.s, r.i, r.d_t.as<uint64_t>(), n, (hipStream_t)stream, out, info);
+}
+int device_sessions_from_events(const uint64_t* sess, const uint64_t* item, const void* times, size_t n, unsigned flags, int device, void* stream, DevSessions& out,
+                                srn_load_info_t* info) {
+    EventRows r;
+    int rc = event_rows_device(sess, item, times, n, flags, device, (hipStream_t)stream, r, info); if (rc) return rc;
+    return group_rows_device_core(r.s, r.i, r.d_t.as<uint64_t>(), n, (hipStream_t)stream, out, info);
 }
 
 // the file's rows on the device, in file order (what group_rows_device takes); li: lines, rows, skipped, host_parsed and the read / upload / parse times
@@ -688,6 +713,63 @@ uint64_t sessions_length_quantile_counting(const uint64_t* off, size_t n, double
     const size_t hi = std::min(n - 1, lo + 1); const double frac = pos - (double)lo;
     const double a = (double)kth(lo), b = (double)kth(hi);
     return (uint64_t)std::llround(a + frac * (b - a));
+}
+
+// ... and on offsets that are still on the device
+namespace {
+constexpr uint32_t kLenBins = 4096;       // lengths 0..4095: 16 KiB of LDS per block
+constexpr unsigned kHistBlocks = 256;     // one block per CU: a block adds each bin it touched once, so fewer blocks mean fewer global atomics
+// hist[L] = sessions of length L < kLenBins (dropped ones included); over[0] = the sessions longer than that, over[1] = the longest of them.  Counted in LDS first
+// (the lengths 1..3 draw most of the adds), then one atomic per touched bin and block
+__global__ void k_len_hist(const uint64_t* off, uint64_t n, unsigned long long* hist, unsigned long long* over) {
+    __shared__ uint32_t bins[kLenBins];
+    __shared__ unsigned long long lds[2][TPB / 64];
+    for (uint32_t e = threadIdx.x; e < kLenBins; e += blockDim.x) bins[e] = 0;
+    __syncthreads();
+    unsigned long long n_over = 0, longest = 0;
+    for (uint64_t s = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; s < n; s += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t len = off[s + 1] - off[s];
+        if (len < kLenBins) atomicAdd(&bins[len], 1u);
+        else { ++n_over; longest = max(longest, (unsigned long long)len); }
+    }
+    __syncthreads();
+    for (uint32_t e = threadIdx.x; e < kLenBins; e += blockDim.x) if (bins[e]) atomicAdd(&hist[e], (unsigned long long)bins[e]);
+    for (int o = 32; o > 0; o >>= 1) n_over += __shfl_xor(n_over, o);
+    if (lane_id() == 0) lds[0][threadIdx.x / 64] = n_over;
+    longest = block_max(longest, lds[1]);   // (synchronises)
+    if (threadIdx.x == 0) {
+        unsigned long long t = 0; for (int i = 0; i < TPB / 64; ++i) t += lds[0][i];
+        if (t) { atomicAdd(&over[0], t); atomicMax(&over[1], longest); }
+    }
+}
+}  // namespace
+
+int device_length_quantile(const uint64_t* d_off, uint64_t n, double q, hipStream_t st, uint64_t* out) {
+    *out = 0;
+    if (n == 0) return SRN_OK;
+    DevBuf d_hist;
+    ING_TRY(d_hist.alloc((kLenBins + 2) * 8));
+    ING_TRY(hipMemsetAsync(d_hist.p, 0, (kLenBins + 2) * 8, st));
+    hipLaunchKernelGGL(k_len_hist, dim3(std::min(grid_for(n).x, kHistBlocks)), dim3(TPB), 0, st, d_off, n, d_hist.as<unsigned long long>(), d_hist.as<unsigned long long>() + kLenBins);
+    ING_TRY(hipGetLastError());
+    std::vector<unsigned long long> hist(kLenBins + 2);
+    ING_TRY(hipMemcpyAsync(hist.data(), d_hist.p, (kLenBins + 2) * 8, hipMemcpyDeviceToHost, st));
+    ING_TRY(hipStreamSynchronize(st));
+    bool overflow = false;
+    auto kth = [&](size_t k) -> uint64_t {   // k-th smallest length (0-based), as in sessions_length_quantile_counting
+        uint64_t acc = 0;
+        for (uint64_t L = 0; L < kLenBins; ++L) { acc += hist[L]; if (acc > k) return L; }
+        overflow = true; return 0; };
+    const double pos = q * (double)(n - 1); const size_t lo = (size_t)std::floor(pos);
+    const size_t hi = std::min<size_t>(n - 1, lo + 1); const double frac = pos - (double)lo;
+    const double a = (double)kth(lo), b = (double)kth(hi);
+    if (!overflow) { *out = (uint64_t)std::llround(a + frac * (b - a)); return SRN_OK; }
+    // an order statistic lies among the hist[kLenBins] sessions of 4096 items or more (the longest has hist[kLenBins + 1]): their lengths are not binned
+    std::vector<uint64_t> off(n + 1);
+    ING_TRY(hipMemcpyAsync(off.data(), d_off, (n + 1) * 8, hipMemcpyDeviceToHost, st));
+    ING_TRY(hipStreamSynchronize(st));
+    *out = sessions_length_quantile_counting(off.data(), n, q);
+    return SRN_OK;
 }
 
 }  // namespace srn

@@ -1,5 +1,6 @@
 // Internal declarations shared by the host index builder, the C ABI glue and the HIP kernels.
 #pragma once
+#include <atomic>
 #include <cstddef>
 #include <cstdint>
 #include <mutex>
@@ -136,6 +137,15 @@ struct Workspace;   // per-call device scratch + events, owned by the index hand
 struct DeviceState;  // uploaded arrays + workspace pool
 
 DeviceState* device_attach(const FlatIndex& ix, int device);   // nullptr on failure (error set)
+// ... of an index whose builder left its four large arrays on the device (srn_index_from_events_device): post_rank becomes the served array, the rows are laid out from
+// row_off / row_items in place, and those two and rank_to_session stay as residue until device_materialize copies all four into ix and frees what serving does not read.
+// ix: the scalars and the per-item arrays.  The allocations belong to the attach from the call on, also when it fails
+struct ResidentArrays { void* post_rank; void* row_off; void* row_items; void* rank_to_session; };
+DeviceState* device_attach_resident(const FlatIndex& ix, int device, const ResidentArrays& a);
+int device_materialize(DeviceState* d, FlatIndex& ix);
+uint64_t device_residue_bytes(const DeviceState* d);   // bytes of the residue still on the device (part of device_bytes)
+// the block_base arrays of launch_rows_to_slots / launch_rows_to_packed from row offsets on the device (srn_build_gpu.hip): totals = {overflow items + 16, overflow blocks + 1, longest row}
+int row_block_bases(const uint64_t* d_row_off, uint64_t n_rows, bool frag, uint32_t* d_base_ext, uint32_t* d_base_packed, uint64_t totals[3]);
 void device_release(DeviceState* d);
 int device_update_attr(DeviceState* d, const FlatIndex& ix);
 void device_refresh_fast_bounds(DeviceState* d, const FlatIndex& ix);   // idf bounds of the fast kernel's integer floors (srn_runtime.hip)
@@ -280,14 +290,24 @@ size_t knob_tiny_max();     // SRN_TINY_MAX: largest host batch on the zero-copy
 }  // namespace srn
 
 struct srn_index {
-    srn::FlatIndex flat;
+    srn::FlatIndex flat;             // host readers of post_rank, row_off, row_items and rank_to_session go through srn::host_flat(): a resident index fetches them lazily
     srn::DeviceState* dev = nullptr;
     int device = -1;
     srn::Combiner* comb = nullptr;   // created with the device state
     std::vector<uint64_t> fallback;  // the fallback ranking as set (srn_index_set_fallback*; empty: none)
     // reference session index -> recency rank (kNone: not a kept session), built at the first srn_index_items_for_session call (the index is immutable: call_once)
     mutable std::vector<uint32_t> session_to_rank; mutable std::once_flag s2r_once;
+    // srn_index_from_events_device: flat holds every scalar and per-item array, the four large arrays are on the device until the first host reader (host_complete = false)
+    mutable std::atomic<bool> host_complete{true}; mutable std::mutex host_mu; mutable uint64_t materialisations = 0; mutable double ms_materialize = 0.0;
+    srn_index_host_state_t build_state{};   // the build's stage times (the other fields are filled in by srn_index_host_state)
 };
+namespace srn {
+// the index's FlatIndex with all of its arrays on the host: downloads the four large arrays of a resident index once (under host_mu), frees the build residue serving does
+// not read.  nullptr: the download failed (error set, SRN_EHIP)
+const FlatIndex* host_flat(const srn_index* idx);
+int index_from_events_device(const uint64_t* session_ids, const uint64_t* item_ids, const void* times, size_t n, unsigned flags, size_t m_index, double idf_weighting,
+                             size_t max_session_len, int device, void* stream, srn_index* idx);   // srn_build_gpu.hip; fills idx->flat, idx->dev, idx->device
+}  // namespace srn
 struct srn_sessions {
     srn::Sessions s;
     srn_load_info_t info{};   // the GPU loader's counts and stage times (zeros for the host loader)

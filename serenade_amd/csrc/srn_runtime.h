@@ -121,6 +121,8 @@ struct DeviceState {
     int device = 0;
     std::atomic<ServeState*> serve{nullptr}; std::vector<ServeState*> serve_retired;   // (retired: stopped, kept until device_release -- a concurrent srn_predict may still hold the pointer)
     std::vector<void*> allocs; uint64_t bytes = 0;
+    // an index attached by device_attach_resident: the builder's arrays that only the host copy needs, here (res_bytes of `bytes`) until device_materialize takes them down
+    void* res_row_off = nullptr; void* res_row_items = nullptr; void* res_rank_to_session = nullptr; uint64_t res_bytes = 0;
     DeviceIndex di{};
     ItemMeta* d_meta = nullptr;
     FastParams fast{};            // packed row slots + idf bounds of the fast kernel (row_packed == nullptr: no fast path for this index)

@@ -178,6 +178,98 @@ DeviceState* device_attach(const FlatIndex& ix, int device) {
     return d;
 }
 
+// device_attach for an index whose builder (build_flat_index_core) left post_rank, row_off, row_items and rank_to_session on this device: the same DeviceState, with
+// post_rank adopted as the served array, the rows laid out from the device arrays, and row_off / row_items / rank_to_session kept as residue until device_materialize
+// brings the host copy up to date.  ix holds the scalars and the per-item arrays.  The four allocations are the attach's from here on, whatever it returns
+DeviceState* device_attach_resident(const FlatIndex& ix, int device, const ResidentArrays& a) {
+    auto drop = [&] { for (void* p : {a.post_rank, a.row_off, a.row_items, a.rank_to_session}) if (p) hipFree(p); };
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device >= ndev) { set_error("no such HIP device"); drop(); return nullptr; }
+    if (hipSetDevice(device) != hipSuccess) { set_error("hipSetDevice failed"); drop(); return nullptr; }
+    DeviceState* d = new DeviceState(); d->device = device; d->timing.store(knobs().timing);
+    const size_t n = ix.n_kept;
+    d->allocs.push_back(a.post_rank); d->bytes += std::max<size_t>(ix.nnz_post * 4, 16);
+    d->res_row_off = a.row_off; d->res_row_items = a.row_items; d->res_rank_to_session = a.rank_to_session;
+    d->res_bytes = std::max<size_t>((n + 1) * 8, 16) + std::max<size_t>(ix.nnz_rows * 4, 16) + std::max<size_t>(n * 4, 16); d->bytes += d->res_bytes;
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, device) == hipSuccess) { d->n_cu = prop.multiProcessorCount; d->lds_per_block_max = (int)prop.sharedMemPerBlock; }
+    bool ok = true;
+    d->di.id_table = upload(d, ix.id_table, ok); d->di.id_mask = ix.id_mask;
+    { std::vector<ItemMeta> meta(ix.n_items); std::vector<uint64_t> id_sorted(ix.n_items);
+      for (size_t i = 0; i < ix.n_items; ++i) { meta[i] = ItemMeta{ix.idf[i], ix.id_rank[i], ix.attr[i]}; id_sorted[ix.id_rank[i]] = ix.item_id[i]; }
+      d->d_meta = (ItemMeta*)upload(d, meta, ok); d->di.meta = d->d_meta; d->di.id_sorted = upload(d, id_sorted, ok);
+      std::vector<ItemMeta> ms(512, ItemMeta{0.0, 0u, 0u});   // the fast kernel's threshold sample, as device_attach lays it out
+      for (uint32_t w8 = 0; w8 < 8; ++w8) for (uint32_t l = 0; l < 64; ++l) if (8 * l + w8 < ix.n_items) ms[64 * w8 + l] = meta[8 * l + w8];
+      d->fast.meta_sample = upload(d, ms, ok); }
+    d->di.post_off = upload(d, ix.post_off, ok); d->di.post_rank = (const uint32_t*)a.post_rank;
+    d->di.viol = nullptr;   // (a built index: every list complete)
+    if (ok) {   // rows -> slots: device_attach's layout, its three host walks over the rows replaced by row_block_bases
+        const int rs16 = knobs().row_slots16;
+        const bool frag = rs16 == 1;   // (unsharded: fragments only when SRN_ROW_SLOTS=16 forces them)
+        const size_t slot_bytes = frag ? 16 : 64;
+        const size_t nblocks = (n + 1 + 1023) / 1024;
+        const uint64_t* d_off = (const uint64_t*)a.row_off; const uint32_t* d_items = (const uint32_t*)a.row_items;
+        void *d_base = nullptr, *d_base_pk = nullptr, *d_slots = nullptr, *d_ext = nullptr;
+        uint64_t totals[3] = {0, 0, 0};
+        bool good = hipMalloc(&d_base, nblocks * 4) == hipSuccess && hipMalloc(&d_base_pk, nblocks * 4) == hipSuccess &&
+                    row_block_bases(d_off, n, frag, (uint32_t*)d_base, (uint32_t*)d_base_pk, totals) == SRN_OK;
+        if (good && totals[0] >= 0xFFFFFFF0ull) {
+            set_error("row overflow area exceeds 2^32 items"); hipFree(d_base); hipFree(d_base_pk); device_release(d); return nullptr; }
+        const size_t ext_words = totals[0] + 16;   // (4-item loads may run past the last row)
+        good = good && hipMalloc(&d_slots, (n + 1) * slot_bytes) == hipSuccess && hipMalloc(&d_ext, ext_words * 4) == hipSuccess &&
+               hipMemset(d_ext, 0xFF, ext_words * 4) == hipSuccess;
+        good = good && (frag ? launch_rows_to_frags : launch_rows_to_slots)(nullptr, d_off, d_items, (uint64_t)n, (const uint32_t*)d_base, (uint32_t*)d_slots, (uint32_t*)d_ext) == hipSuccess &&
+               hipDeviceSynchronize() == hipSuccess;
+        if (good) {   // the fast kernel's packed rows: optional, as in device_attach
+            const uint64_t blocks = totals[1];
+            void *d_pk = nullptr, *d_e16 = nullptr;
+            bool g2 = blocks < 0xFFFFFFF0ull && hipMalloc(&d_pk, (n + 1) * slot_bytes) == hipSuccess && hipMalloc(&d_e16, (blocks + 2) * 16) == hipSuccess &&
+                      hipMemset(d_e16, 0, (blocks + 2) * 16) == hipSuccess &&
+                      launch_rows_to_packed(nullptr, d_off, d_items, (uint64_t)n, (const uint32_t*)d_base_pk, (uint32_t*)d_pk, (uint32_t*)d_e16, frag) == hipSuccess &&
+                      hipDeviceSynchronize() == hipSuccess;
+            if (g2) { d->allocs.push_back(d_pk); d->bytes += (n + 1) * slot_bytes; d->allocs.push_back(d_e16); d->bytes += (blocks + 2) * 16;
+                      d->fast.row_packed = (const RowQuad*)d_pk; d->fast.row_ext16 = (const uint32_t*)d_e16; }
+            else {
+                (void)hipGetLastError();   // (clear the sticky allocation error)
+                if (d_pk) hipFree(d_pk); if (d_e16) hipFree(d_e16);
+                d->fast.row_packed = nullptr; d->fast.row_ext16 = nullptr;
+                if (knobs().debug) fprintf(stderr, "[srn] no room for the fast kernel's packed rows (%zu bytes): general kernel only\n", (size_t)((n + 1) * slot_bytes + (blocks + 2) * 16));
+            }
+        }
+        if (d_base) hipFree(d_base); if (d_base_pk) hipFree(d_base_pk);
+        if (d_slots) { d->allocs.push_back(d_slots); d->bytes += (n + 1) * slot_bytes; }
+        d->di.row_frag = frag ? 1u : 0u;
+        if (d_ext) { d->allocs.push_back(d_ext); d->bytes += ext_words * 4; }
+        if (!good) { ok = false; set_error("row slot layout on the device failed"); }
+        if (good && totals[2] != ix.max_row_len) { ok = false; set_error("the rows on the device disagree with the index's max_row_len"); }
+        d->di.row_slots = (const RowQuad*)d_slots; d->di.row_ext = (const uint32_t*)d_ext;
+    }
+    d->di.n_items = (uint32_t)ix.n_items; d->di.n_kept = (uint32_t)ix.n_kept;
+    double hi = 1.0, lo = 1.0; bool any = false;   // bounds of idf_eff = (idf > 0 ? idf : 1) for the top-n pre-filter
+    for (double v : ix.idf) { const double e = v > 0.0 ? v : 1.0; if (!any) { hi = lo = e; any = true; } else { hi = std::max(hi, e); lo = std::min(lo, e); } }
+    d->di.idf_hi = hi; d->di.idf_lo = lo;
+    device_refresh_fast_bounds(d, ix);
+    if (!ok) { device_release(d); return nullptr; }
+    return d;
+}
+
+// The host copy of a resident index, now: post_rank, row_off, row_items and rank_to_session into ix, then the residue serving does not read is freed (post_rank stays:
+// it is the served array).  The caller holds the index's host mutex
+int device_materialize(DeviceState* d, FlatIndex& ix) {
+    if (!d->res_row_off) return SRN_OK;
+    HIP_TRY(hipSetDevice(d->device));
+    ix.post_rank.resize(ix.nnz_post); ix.row_off.resize(ix.n_kept + 1); ix.row_items.resize(ix.nnz_rows); ix.rank_to_session.resize(ix.n_kept);
+    if (ix.nnz_post) HIP_TRY(hipMemcpy(ix.post_rank.data(), d->di.post_rank, ix.nnz_post * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(ix.row_off.data(), d->res_row_off, (ix.n_kept + 1) * 8, hipMemcpyDeviceToHost));
+    if (ix.nnz_rows) HIP_TRY(hipMemcpy(ix.row_items.data(), d->res_row_items, ix.nnz_rows * 4, hipMemcpyDeviceToHost));
+    if (ix.n_kept) HIP_TRY(hipMemcpy(ix.rank_to_session.data(), d->res_rank_to_session, ix.n_kept * 4, hipMemcpyDeviceToHost));
+    for (void* p : {d->res_row_off, d->res_row_items, d->res_rank_to_session}) if (p) hipFree(p);
+    d->res_row_off = d->res_row_items = d->res_rank_to_session = nullptr;
+    d->bytes -= d->res_bytes; d->res_bytes = 0;
+    return SRN_OK;
+}
+uint64_t device_residue_bytes(const DeviceState* d) { return d ? d->res_bytes : 0; }
+
 // idf bounds of the fast kernel's integer floors: the largest idf_eff of each chunk of 512 direct-mapped items, and of all items
 void device_refresh_fast_bounds(DeviceState* d, const FlatIndex& ix) {
     double hi_all = 1.0; bool any = false;
@@ -232,6 +324,7 @@ void device_release(DeviceState* d) {
     hostpipes_free(d);
     for (Workspace* w : d->all_ws) ws_free(w);
     for (void* p : d->allocs) hipFree(p);
+    for (void* p : {d->res_row_off, d->res_row_items, d->res_rank_to_session}) if (p) hipFree(p);
     if (d->sb_frag_post) hipFree(d->sb_frag_post);
     delete d;
 }

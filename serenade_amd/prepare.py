@@ -203,13 +203,14 @@ def _t_max(times):
     return int(round_times(times).max())
 
 
-def backtest(events, trials, m, idf_weighting, cutoffs=None, folds=None, test_span=86400, train_span=None, bootstrap=0, seed=0, ci=0.95, segments=None, **split_kwargs):
+def backtest(events, trials, m, idf_weighting, cutoffs=None, folds=None, test_span=86400, train_span=None, bootstrap=0, seed=0, ci=0.95, segments=None, builder="gpu", **split_kwargs):
     """Walk-forward evaluation of a click log.  events: (session_ids, item_ids, times), NumPy or device tensors; trials as evaluate() takes them; m and
     idf_weighting as VMISIndex.from_events takes them.  cutoffs: the folds' cutoffs; or folds=K: cutoff j = t_max + 1 - (K - j) * test_span, j = 0 .. K - 1.
     Per cutoff c: start = c - train_span (0 = all the past without train_span), end = c + test_span; split_events(..., **split_kwargs), VMISIndex.from_events
     on the training side, EvalSet.from_events on the test side and the training side's item column, evaluate(trials, bootstrap, seed, ci); the index and the set
     are closed again.  -> [{"cutoff", "start", "end", "info", "reports"}] in cutoff order.  With device tensors nothing but counts and reports leaves the GPU,
-    except inside from_events, which hands the grouped sessions to the index builder through the host as it always did.
+    except inside from_events with builder="gpu" (the default), which hands the grouped sessions to the index builder through the host and brings the built index
+    down before attaching it; builder="resident" (VMISIndex.from_events) keeps all of that on the device -- same index, same reports.
     split_kwargs may also hold max_session_len (VMISIndex.from_events) and device.
     segments: evaluate()'s spec by position or by an item count -- every fold's reports then hold their "segments".  by="labels" is refused:
     a fold's session order is its own, so one label array cannot fit the folds."""
@@ -236,7 +237,7 @@ def backtest(events, trials, m, idf_weighting, cutoffs=None, folds=None, test_sp
         c = int(c)
         start = max(c - int(train_span), 0) if train_span else 0
         sp = split_events(sess, items, times, c, start=start, end=c + test_span, device=device, **split_kwargs)
-        index = VMISIndex.from_events(*sp.train, m, idf_weighting, max_session_len=max_session_len, device=device)
+        index = VMISIndex.from_events(*sp.train, m, idf_weighting, max_session_len=max_session_len, device=device, builder=builder)
         try:
             es = EvalSet.from_events(index, sp.test, sp.train[1])
             try:

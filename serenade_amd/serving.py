@@ -605,14 +605,16 @@ class SessionHarvest:
     __del__ = close
 
 
-def refreshed_index(base_session_ids, base_item_ids, base_times, harvest, m_most_recent_sessions, idf_weighting, max_session_len=0, device=0):
+def refreshed_index(base_session_ids, base_item_ids, base_times, harvest, m_most_recent_sessions, idf_weighting, max_session_len=0, device=0, builder="gpu"):
     """The index of the base training events with the harvested sessions appended: exactly VMISIndex.from_events over the base arrays (NumPy, CPU tensors or tensors
     on `device`, as from_events takes them) followed by harvest.events(id_base=max(base_session_ids) + 1), concatenated on the device.  That is what
     VMISIndex.new_from_csv gives for the training file with those rows appended -- read_from_file's quirk included: the file's final row closes its session and the
     last session is dropped, so the most recent harvested session does not enter the index.  The harvested times are epochs in seconds; base times above them are the
-    caller's business.  The harvest is not consumed."""
+    caller's business.  The harvest is not consumed.  builder: as VMISIndex.from_events takes it ("resident": the build never leaves the device)."""
     import torch
     from .vmisknn import VMISIndex
+    if builder not in ("gpu", "resident"):
+        raise ValueError("builder must be 'gpu' or 'resident'")
     if harvest.device != int(device):
         raise ValueError("the harvest is on device %d, not %d" % (harvest.device, int(device)))
     dev = torch.device("cuda", int(device))
@@ -641,7 +643,7 @@ def refreshed_index(base_session_ids, base_item_ids, base_times, harvest, m_most
     id_base = int(sid.max().item()) + 1 if sid.numel() else 0           # (session ids below 2^63, as everywhere a tensor carries them)
     h_sid, h_item, h_t = harvest.events(id_base)
     return VMISIndex.from_events(torch.cat([sid, h_sid]), torch.cat([item, h_item]), torch.cat([t, h_t.to(t.dtype)]), m_most_recent_sessions, idf_weighting,
-                                 max_session_len=max_session_len, device=int(device))
+                                 max_session_len=max_session_len, device=int(device), builder=builder)
 
 
 # ---- click feedback: served rows scored against the visitor's next click (srn_feedback_*) ----

@@ -44,9 +44,22 @@ class VMISIndex:
         return cls(h)
 
     @classmethod
-    def from_events(cls, session_ids, item_ids, times, m_most_recent_sessions, idf_weighting, max_session_len=0, device=0):
+    def from_events(cls, session_ids, item_ids, times, m_most_recent_sessions, idf_weighting, max_session_len=0, device=0, builder="gpu"):
         """new_from_csv on rows already in memory, in file order: NumPy arrays, torch tensors on the CPU, or torch tensors on this
-        device (read in place).  times: float (rounded like the file's) or integer seconds.  Grouped and built on the GPU."""
+        device (read in place).  times: float (rounded like the file's) or integer seconds.  Grouped and built on the GPU.
+        builder="gpu": the grouped sessions come to the host, go back up for the builder, and the built index comes down before it is attached
+        (srn_sessions_from_events + srn_index_build_gpu).  builder="resident" (srn_index_from_events_device): the same index, bit for bit, with the large arrays never
+        leaving the device; its host copy is fetched once, by the first call that reads it there (save, postings, items_for_session ...: host_state(), materialize())."""
+        if builder not in ("gpu", "resident"):
+            raise ValueError("builder must be 'gpu' or 'resident'")
+        if builder == "resident":
+            from .ingest import _event_args
+            keep, (ps, pi, pt), n, flags, stream = _event_args(session_ids, item_ids, times, int(device))
+            h = C.c_void_p()
+            capi.check(capi.lib().srn_index_from_events_device(C.c_void_p(ps), C.c_void_p(pi), C.c_void_p(pt), n, flags, int(m_most_recent_sessions), float(idf_weighting),
+                                                               int(max_session_len), int(device), None if stream is None else C.c_void_p(stream), C.byref(h)))
+            del keep
+            return cls(h)
         from .ingest import TrainingSessions
         ts = TrainingSessions.from_events(session_ids, item_ids, times, device=device)
         try:
@@ -100,6 +113,19 @@ class VMISIndex:
         out = capi.IndexInfo()
         capi.check(capi.lib().srn_index_info(self._h, C.byref(out)))
         return {n: getattr(out, n) for n, _ in capi.IndexInfo._fields_}
+
+    def host_state(self):
+        """srn_index_host_state as a dict: host_complete (False only for a builder="resident" index no host reader has asked yet), build_bytes_on_device (device bytes
+        held for that deferred download alone; part of info["device_bytes"]), materialisations (0 or 1), and the resident build's stage times in ms."""
+        st = capi.IndexHostState()
+        capi.check(capi.lib().srn_index_host_state(self._h, C.byref(st)))
+        out = {n: getattr(st, n) for n, _ in capi.IndexHostState._fields_ if n != "reserved"}
+        out["host_complete"] = bool(out["host_complete"])
+        return out
+
+    def materialize(self):
+        """Bring the host copy up to date now (what the first save / postings / items_for_session call would do); idempotent."""
+        capi.check(capi.lib().srn_index_materialize(self._h))
 
     def set_attributes(self, item_ids, flags):
         ids, fl = capi.as_u64(item_ids), np.ascontiguousarray(flags, np.uint8)
