@@ -29,6 +29,9 @@ int srn_debug_last_mid_count(const srn_index_t* idx, uint32_t* out_listed);
 /* Measurement aid: how many queries of the last predict call were not served themselves but received the row of an earlier query of the SAME call with the same item
  * sequence (batches of at least SRN_ORDER_MIN queries on the fast path).  0 when the call did not merge (small batch, SRN_NO_DEDUP, other paths). */
 int srn_debug_last_dedup_count(const srn_index_t* idx, uint32_t* out_merged);
+/* light representatives of the last call -- distinct queries with one posting run of <= 64 kept entries, served one wave each (or handed to the general kernel) by
+ * vmis_light_kernel; 0 where the form was off: a batch below SRN_LIGHT_MIN, a call that uses the result cache, a shard group's call */
+int srn_debug_last_light_count(const srn_index_t* idx, uint32_t* out_light);
 /* the persistent latency path: 100 MHz ticks of the last session the lean form's first resident workgroup served -- [0] waited for the doorbell, [1] doorbell -> prep record
  * written, [2] doorbell -> answer posted */
 int srn_debug_serve_stamps(const srn_index_t* idx, uint32_t* out4);

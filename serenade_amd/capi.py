@@ -240,6 +240,7 @@ SYMBOLS = {
     "srn_debug_reload_knobs": (None, []),
     "srn_debug_last_mid_count": (_i, [_vp, C.POINTER(C.c_uint32)]),
     "srn_debug_last_dedup_count": (_i, [_vp, C.POINTER(C.c_uint32)]),
+    "srn_debug_last_light_count": (_i, [_vp, C.POINTER(C.c_uint32)]),
     "srn_debug_serve_stamps": (_i, [_vp, _vp]),
     "srn_debug_serve_lane_counts": (_i, [_vp, C.c_uint, _vp, _sz, C.POINTER(_sz)]),
     "srn_debug_shard_nb_positions_stride": (C.c_uint32, [_sz, _sz]),

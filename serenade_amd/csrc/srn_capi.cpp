@@ -753,6 +753,10 @@ int srn_debug_last_dedup_count(const srn_index_t* idx, uint32_t* out_merged) {
     if (!idx || !idx->dev || !out_merged) return fail(SRN_EINVAL, "null argument");
     return guarded([&]() -> int { return device_last_dedup_count(idx->dev, out_merged); });
 }
+int srn_debug_last_light_count(const srn_index_t* idx, uint32_t* out_light) {
+    if (!idx || !idx->dev || !out_light) return fail(SRN_EINVAL, "null argument");
+    return guarded([&]() -> int { return device_last_light_count(idx->dev, out_light); });
+}
 int srn_debug_last_big_count(const srn_index_t* idx, uint32_t* out_listed) {
     if (!idx || !idx->dev) return fail(SRN_ENODEV, "index has no device attached");
     return guarded([&]() -> int { return device_last_mid_count(idx->dev, nullptr, out_listed); });

@@ -7,7 +7,9 @@
 //                              full sequences, read from the call's read-only input -- and only an equal one ends the probe: a group is the queries that ended on one slot.
 //                              The slot's second word takes the atomicMin of their indices.
 //   vmis_dedup_resolve_kernel  rep[q] = that minimum (rep[q] == q: a representative).  A merged query's order key becomes 0xFFFF << 32 | q -- the radix sort behind this
-//                              kernel puts it behind every representative, whose keys are clamped to 0xFFFE -- and the merged queries are counted.
+//                              kernel puts it behind every representative, whose keys are clamped to 0xFFFE -- and the merged queries are counted.  Where the launch
+//                              sequence has the light form on (srn_light.hip) the prep kernel has clamped the keys to 0xFFFD and given 0xFFFE to the light queries:
+//                              the kernel also counts the light REPRESENTATIVES and merged + light, the end of the lean kernel's loop.
 //   vmis_dedup_mark_kernel     out_counts[q] = 0 for the merged queries, on the stream the serving kernels run on: the finish kernels act on every row of [0, nq) whose
 //                              count word is 0x80000000 / 0x80000001, and a merged row's word is whatever the caller's buffer held.  (Where grouping runs on that stream
 //                              itself the resolve kernel writes the word.)
@@ -30,9 +32,9 @@ __device__ __forceinline__ bool same_sequence(const uint64_t* __restrict__ items
 }  // namespace
 
 __global__ __launch_bounds__(256) void vmis_dedup_group_kernel(const uint64_t* __restrict__ items_flat, const uint32_t* __restrict__ q_off, uint32_t nq, uint32_t* slots, uint32_t* slot_min,
-                                                               uint32_t slot_mask, uint32_t hash_mask, uint32_t* slot_of, uint32_t* n_dup) {
+                                                               uint32_t slot_mask, uint32_t hash_mask, uint32_t* slot_of, uint32_t* n_dup, uint32_t* light_cnt) {
     const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
-    if (q == 0u) *n_dup = 0u;   // (counted by the resolve kernel, behind this one on the stream)
+    if (q == 0u) { *n_dup = 0u; if (light_cnt) { light_cnt[0] = 0u; light_cnt[1] = 0u; } }   // (counted by the resolve kernel, behind this one on the stream)
     if (q >= nq) return;
     const uint32_t qb = q_off[q], L = q_off[q + 1] - qb;
     uint64_t h = dev_mix64(0x9E3779B97F4A7C15ull + L);
@@ -51,17 +53,34 @@ __global__ __launch_bounds__(256) void vmis_dedup_group_kernel(const uint64_t* _
 }
 
 __global__ __launch_bounds__(256) void vmis_dedup_resolve_kernel(uint32_t nq, const uint32_t* __restrict__ slot_min, uint32_t* rep, unsigned long long* __restrict__ okeys,
-                                                                 uint32_t* __restrict__ out_counts, uint32_t* n_dup) {
+                                                                 uint32_t* __restrict__ out_counts, uint32_t* n_dup, uint32_t* light_cnt) {
     const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
-    bool dup = false;
+    bool dup = false, light = false;
     if (q < nq) {
         const uint32_t r = slot_min[rep[q]];   // (rep[q] holds the query's slot until here)
         rep[q] = r; dup = r != q;
         if (dup) { okeys[q] = (0xFFFFull << 32) | q; if (out_counts) out_counts[q] = 0u; }
-        else if ((okeys[q] >> 32) >= 0xFFFFull) okeys[q] = (0xFFFEull << 32) | q;
+        else {
+            const uint32_t key = (uint32_t)(okeys[q] >> 32);
+            if (key >= 0xFFFFu) okeys[q] = (0xFFFEull << 32) | q;
+            else light = light_cnt != nullptr && key == 0xFFFEu;   // (the light form is on: the prep kernel gave 0xFFFE to the light queries alone; a merged one is not served)
+        }
     }
     const unsigned long long b = __ballot(dup);
-    if (b != 0ull && (threadIdx.x & 63u) == 0u) atomicAdd(n_dup, (uint32_t)__popcll(b));
+    if (!light_cnt) { if (b != 0ull && (threadIdx.x & 63u) == 0u) atomicAdd(n_dup, (uint32_t)__popcll(b)); return; }
+    // the light form is on: three counts -- merged | light representatives | merged + light, where the lean kernel's loop ends -- summed over the workgroup first (every
+    // wave adding to three words of one line took the kernel from 0.19 to 0.37 ms per 2^20 queries); [0] and [1] are one 64-bit word
+    __shared__ uint32_t part[2];
+    if (threadIdx.x < 2u) part[threadIdx.x] = 0u;
+    __syncthreads();
+    const unsigned long long bl = __ballot(light);
+    if ((threadIdx.x & 63u) == 0u) { if (b) atomicAdd(&part[0], (uint32_t)__popcll(b)); if (bl) atomicAdd(&part[1], (uint32_t)__popcll(bl)); }
+    __syncthreads();
+    if (threadIdx.x == 0u) {
+        const uint32_t nd = part[0], nl = part[1];
+        if (nd) atomicAdd(n_dup, nd);
+        if (nd | nl) atomicAdd(reinterpret_cast<unsigned long long*>(light_cnt), ((unsigned long long)(nd + nl) << 32) | nl);
+    }
 }
 
 __global__ __launch_bounds__(256) void vmis_dedup_mark_kernel(uint32_t nq, const uint32_t* __restrict__ rep, uint32_t* __restrict__ out_counts) {
@@ -90,10 +109,10 @@ __global__ __launch_bounds__(256) void vmis_dedup_fill_kernel(uint32_t nq, const
 // out_counts: null where the serving kernels run on another stream (launch_dedup_mark there).  hash_bits: SRN_DEDUP_HASH_BITS (tests; 0 = all of them)
 uint32_t dedup_slots(uint32_t nq) { uint32_t s = 1024u; while (s < 0x80000000u && (uint64_t)s < 2ull * nq) s <<= 1; return s; }
 hipError_t launch_dedup_group(hipStream_t st, const uint64_t* items_flat, const uint32_t* q_off, uint32_t nq, uint32_t* slots, uint32_t* slot_min, uint32_t n_slots, uint32_t hash_bits,
-                              uint32_t* rep, unsigned long long* okeys, uint32_t* out_counts, uint32_t* n_dup) {
+                              uint32_t* rep, unsigned long long* okeys, uint32_t* out_counts, uint32_t* n_dup, uint32_t* light_cnt) {
     const uint32_t hash_mask = hash_bits >= 1u && hash_bits < 32u ? (1u << hash_bits) - 1u : 0xFFFFFFFFu;
-    hipLaunchKernelGGL(vmis_dedup_group_kernel, dim3((nq + 255u) / 256u), dim3(256), 0, st, items_flat, q_off, nq, slots, slot_min, n_slots - 1u, hash_mask, rep, n_dup);
-    hipLaunchKernelGGL(vmis_dedup_resolve_kernel, dim3((nq + 255u) / 256u), dim3(256), 0, st, nq, (const uint32_t*)slot_min, rep, okeys, out_counts, n_dup);
+    hipLaunchKernelGGL(vmis_dedup_group_kernel, dim3((nq + 255u) / 256u), dim3(256), 0, st, items_flat, q_off, nq, slots, slot_min, n_slots - 1u, hash_mask, rep, n_dup, light_cnt);
+    hipLaunchKernelGGL(vmis_dedup_resolve_kernel, dim3((nq + 255u) / 256u), dim3(256), 0, st, nq, (const uint32_t*)slot_min, rep, okeys, out_counts, n_dup, light_cnt);
     return hipGetLastError();
 }
 hipError_t launch_dedup_mark(hipStream_t st, uint32_t nq, const uint32_t* rep, uint32_t* out_counts) {

@@ -164,5 +164,38 @@ __device__ __forceinline__ void finish_inline(const DeviceIndex& ix, uint32_t M,
     if (ln == 0u) out_counts[q] = min(M, how_many);
 }
 
+// A row of MORE entries than finish_inline takes, cut down to it by one wave (the latency path's fused launch, the light form): hk[t] of lane ln = the top 32 bits of the key
+// x = idf_eff * acc (f64 bits) of entry 64 t + ln, 0 beyond the row.  wave_nth_top32: the n-th largest of them, by a bitwise search over ballots (0: fewer than n are non-zero).
+template <uint32_t SLOTS>
+__device__ __forceinline__ uint32_t wave_nth_top32(const uint32_t (&hk)[SLOTS], uint32_t n) {
+    uint32_t t32 = 0u;
+    for (int b = 31; b >= 0; --b) {
+        const uint32_t c = t32 | (1u << b);
+        uint32_t n_ge = 0;
+#pragma unroll
+        for (uint32_t t = 0; t < SLOTS; ++t) n_ge += (uint32_t)__popcll(__ballot(hk[t] >= c));
+        t32 = n_ge >= n ? c : t32;
+    }
+    return t32;
+}
+// ... and what is at or above ONE STEP BELOW it (so that what is dropped stays strictly smaller after the division by 10 U, as everywhere) -- n entries and the ties at the
+// cut -- compacted in entry order: put(at, i) places entry i at `at` < 64.  Returns the number of entries at or above the cut (wave-uniform); more than 64 of them: the
+// caller hands the query on.
+template <uint32_t SLOTS, class Put>
+__device__ __forceinline__ uint32_t wave_keep_top(const uint32_t (&hk)[SLOTS], uint32_t M, uint32_t t32, uint32_t ln, unsigned long long ltl, Put&& put) {
+    const uint32_t cut = t32 ? t32 - 1u : 0u;
+    uint32_t S = 0;
+#pragma unroll
+    for (uint32_t t = 0; t < SLOTS; ++t) {
+        const uint32_t i = t * 64u + ln;
+        const bool keep = i < M && hk[t] >= cut && hk[t] != 0u;
+        const unsigned long long bm = __ballot(keep);
+        const uint32_t at = S + (uint32_t)__popcll(bm & ltl);
+        if (keep && at < 64u) put(at, i);
+        S += (uint32_t)__popcll(bm);
+    }
+    return S;
+}
+
 
 }  // namespace srn

@@ -1524,25 +1524,8 @@ __global__ __launch_bounds__(512, TINY ? SRN_TINY_WAVES : BIG ? 4 : SRN_FAST_WAV
                         if (i < M) { kx[i] = x; kt[i] = tie; }
                     }
                 }
-                uint32_t t32 = 0u;
-                for (int b = 31; b >= 0; --b) {
-                    const uint32_t c = t32 | (1u << b);
-                    uint32_t n_ge = 0;
-#pragma unroll
-                    for (uint32_t t = 0; t < TB_SLOTS; ++t) n_ge += (uint32_t)__popcll(__ballot(hk[t] >= c));
-                    t32 = n_ge >= p.how_many ? c : t32;
-                }
-                const uint32_t cut = t32 ? t32 - 1u : 0u;
-                uint32_t S = 0;   // (wave-uniform) entries at or above the cut
-#pragma unroll
-                for (uint32_t t = 0; t < TB_SLOTS; ++t) {
-                    const uint32_t i = t * 64u + ln;
-                    const bool keep = i < M && hk[t] >= cut && hk[t] != 0u;
-                    const unsigned long long bm = __ballot(keep);
-                    const uint32_t at = S + (uint32_t)__popcll(bm & ltl);
-                    if (keep && at < 64u) { cx[at] = kx[i]; ct[at] = kt[i]; }
-                    S += (uint32_t)__popcll(bm);
-                }
+                // (the search and the compaction: wave_nth_top32 / wave_keep_top, srn_device.h -- shared with the light form)
+                const uint32_t S = wave_keep_top(hk, M, wave_nth_top32(hk, p.how_many), ln, ltl, [&](uint32_t at, uint32_t i) { cx[at] = kx[i]; ct[at] = kt[i]; });   // (wave-uniform) entries at or above the cut
                 if (S <= 64u && S >= p.how_many) {
                     __builtin_amdgcn_wave_barrier();   // (one wave, LDS in order: the compacted entries are there)
                     uint4 e = make_uint4(0u, 0u, 0u, 0u);

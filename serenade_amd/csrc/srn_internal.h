@@ -264,6 +264,7 @@ int device_last_path_counts(DeviceState* d, uint32_t* nq, uint32_t* general, uin
 // test aid (srn_debug_prep_records): the prep kernel alone over a host batch, its records copied to out [nq * stride]; *out_stride = bytes per record
 int device_debug_prep_records(DeviceState* d, const FlatIndex& ix, const uint64_t* items_flat, const uint32_t* q_off, size_t nq, size_t m, size_t max_len, void* out, size_t cap_bytes, size_t* out_stride);
 int device_last_mid_count(DeviceState* d, uint32_t* listed, uint32_t* big_listed = nullptr);   // queries the last call's lean fast kernel listed for its MID instantiation
+int device_last_light_count(DeviceState* d, uint32_t* light);     // light representatives of the last call (srn_light.hip); 0 where the form was off
 int device_last_dedup_count(DeviceState* d, uint32_t* merged);   // queries of the last call merged into an equal, earlier query of the same call (srn_dedup.hip)
 // ---- the device result cache (srn_result_cache.hip): served rows kept across calls, used by the batch launch sequence where its fast path is ----
 static constexpr unsigned kFlagNoResultCache = 0x80000000u;   // LaunchParams::flags, internal (the predict entries strip it): this call bypasses an enabled cache (srn_evaluate)

@@ -37,11 +37,13 @@ struct LaunchAux { const uint32_t* qlist; const uint32_t* qlist_n; uint32_t* ret
 // srn_prep.h).  Runs: run r = the r-th item, in position order, with kept > 0.  The block is meaningful when 1 <= L <= min(8, max_len) and the query has <= 4 runs;
 // otherwise all 16 words are 0.
 //   RW_FLAGS   bit 0 lean_ok: the lean form's `fits` (srn_fast.hip) for the 53 KB layout; bits 8..10 nr: the runs, capped at 7; bit 16 rel: ranks counted from x_lo
+//              bit 1 RW_LIGHT (only where the launch sequence has the light form on): lean_ok, one run, kept <= RW_LIGHT_KEPT -- vmis_light_kernel serves the query (srn_light.hip)
 //   RW_LMASK   bit 5 r + j: j * 512 < kept of run r -- which of the 20 stage loads exist
 //   RW_CUR     the dense idx of the most recent item (kNone: unknown)
 //   RW_PS      byte r: the session position of run r's item
 //   RW_KEPT+r  kept of run r;   RW_BASE+2r, +2r+1: its list's start in post_rank (64-bit element offset, low word first)
 enum ReadyWord : uint32_t { RW_FLAGS = 0, RW_LMASK = 1, RW_CUR = 2, RW_PS = 3, RW_KEPT = 4, RW_BASE = 8, RW_WORDS = 16 };
+static constexpr uint32_t RW_LIGHT = 2u, RW_LIGHT_KEPT = 64u;
 struct PrepHead { uint32_t U, rmax, xlo, sumw, P, nruns, L, n_staged, run_start[8], cur_attr, unsafe, ready[RW_WORDS]; };   // S_U, S_RMAX, S_XLO, S_SUMW, S_P of the query; number of non-empty lists, session length as given, sum of the lists' kept counts, where the first 8 lists start; cur_attr = the attribute byte of the current (most recent) item, SRN_ATTR_NONE if unknown; ready: above
 struct PrepItem { uint32_t idx, len, pre, kept; unsigned long long base; };   // dense idx | kNone, truncated list length, prefix of len, entries >= x_lo (a prefix of the list), list start
 
@@ -117,7 +119,7 @@ enum SlowCnt : uint32_t { SC_GENERAL = 0, SC_MID = 1, SC_BIG_TICKET_LO = 2, SC_B
 using SlowCntBlock = uint32_t[SC_WORDS];
 // ... and the pinned words the kernels publish a call's counters in (Workspace::h_retry, FastParams::host_words): queries of the global-table pass | handed to the general kernel |
 // listed for MID | for MID's BIG form | with more than 63 entries | the fused call's number, written last of all | queries that got the row of an equal, earlier query (srn_dedup.hip)
-enum HostWord : uint32_t { HW_GLOBAL = 0, HW_GENERAL = 1, HW_MID = 2, HW_BIGQ = 3, HW_OVER63 = 4, HW_SEQ = 5, HW_MERGED = 6, HW_WORDS = 8 };
+enum HostWord : uint32_t { HW_GLOBAL = 0, HW_GENERAL = 1, HW_MID = 2, HW_BIGQ = 3, HW_OVER63 = 4, HW_SEQ = 5, HW_MERGED = 6, HW_LIGHT = 7, HW_WORDS = 8 };   // (HW_LIGHT: the light representatives vmis_light_kernel served or handed on, srn_light.hip)
 using HostWordBlock = uint32_t[HW_WORDS];
 // the four lists inside slow_list, each slow_cap + 16 words
 enum SlowPart : uint32_t { SL_GENERAL = 0, SL_MID = 1, SL_BIGQ = 2, SL_LONG = 3 };
@@ -152,7 +154,7 @@ hipError_t sort_order_keys(hipStream_t st, const unsigned long long* in, unsigne
 // queries of one call with the same item sequence (srn_dedup.hip): groups on the device, the smallest query index of each serves, the others get its row at the end
 uint32_t dedup_slots(uint32_t nq);   // words of the hash table (and of its second array) for a batch of nq queries
 hipError_t launch_dedup_group(hipStream_t st, const uint64_t* items_flat, const uint32_t* q_off, uint32_t nq, uint32_t* slots, uint32_t* slot_min, uint32_t n_slots, uint32_t hash_bits,
-                              uint32_t* rep, unsigned long long* okeys, uint32_t* out_counts, uint32_t* n_dup);
+                              uint32_t* rep, unsigned long long* okeys, uint32_t* out_counts, uint32_t* n_dup, uint32_t* light_cnt = nullptr);   // light_cnt (the light form is on): [0] the light representatives (key 0xFFFE), [1] merged + light -- both counted by the resolve kernel
 hipError_t launch_dedup_mark(hipStream_t st, uint32_t nq, const uint32_t* rep, uint32_t* out_counts);
 hipError_t launch_dedup_fill(hipStream_t st, uint32_t nq, const uint32_t* rep, uint64_t* out_ids, double* out_scores, uint32_t* out_counts, uint32_t how_many, const uint32_t* n_dup, uint32_t* host_word);
 
@@ -202,7 +204,11 @@ struct PredictLaunch {
 hipError_t launch_predict(const PredictLaunch& a, dim3 grid, size_t lds, hipStream_t st, const DeviceIndex& di, const LaunchParams& p, const KernelCfg& c);
 hipError_t launch_prep(hipStream_t st, const DeviceIndex& di, const uint64_t* items_flat, const uint32_t* q_off, uint32_t nq, uint32_t m,
                        uint32_t max_len, char* out, uint32_t stride, bool wide, uint32_t* zero_a = nullptr, uint32_t* zero_b = nullptr,
-                       const IdSlot* loc_table = nullptr, uint32_t loc_mask = 0, unsigned long long* okeys = nullptr);   // wide: the records' consumer is the WIDE lean form (FastParams::nb == 3: the launch-ready block's `rel`); zero_a[0..7], zero_b[0]: counters cleared by the prep kernel; loc_table: the item shard's id table (the record's idx), di = the whole index's dictionary and lists
+                       const IdSlot* loc_table = nullptr, uint32_t loc_mask = 0, unsigned long long* okeys = nullptr, bool light = false, uint32_t* light_cnt = nullptr);   // wide: the records' consumer is the WIDE lean form (FastParams::nb == 3: the launch-ready block's `rel`); zero_a[0..7], zero_b[0]: counters cleared by the prep kernel; loc_table: the item shard's id table (the record's idx), di = the whole index's dictionary and lists
+// light: the records' launch sequence has the light form on (RW_LIGHT, the order keys 0xFFFE / <= 0xFFFD: srn_prep.h); light_cnt: a call that does not merge -- the prep kernel counts the light queries itself ([0] and [1], cleared by the caller)
+// the light form (srn_light.hip): one wave per light representative of the order's segment [nq - *cnt_end, nq - *cnt_end + *cnt_light)
+hipError_t launch_light(hipStream_t st, uint32_t grid, const DeviceIndex& di, const LaunchParams& p, const unsigned long long* order, const uint32_t* cnt_light, const uint32_t* cnt_end,
+                        uint32_t* slow_list, uint32_t* slow_cnt, uint32_t* host_word);
 hipError_t launch_finish_big(hipStream_t st, const DeviceIndex& di, const FastParams& f, uint64_t* out_ids, double* out_scores, uint32_t* out_counts, uint32_t how_many, uint32_t grid, const uint32_t* cnt_retry = nullptr, const uint32_t* cnt_slow = nullptr, uint32_t* host_words = nullptr);
 hipError_t launch_finish(hipStream_t st, const DeviceIndex& di, const FastParams& f, uint64_t* out_ids, double* out_scores, uint32_t* out_counts, uint32_t nq, uint32_t how_many);   // scores, ranking, public ids of the rows the fast kernel served
 hipError_t launch_shard_lists_head(hipStream_t st, const DeviceIndex& di, const uint64_t* items_flat, const uint32_t* q_off, uint32_t nq, uint32_t m, uint32_t max_len,

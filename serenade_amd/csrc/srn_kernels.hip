@@ -363,7 +363,7 @@ __global__ __launch_bounds__(1024) void rows_to_frags_kernel(const uint64_t* __r
 // -------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void vmis_prep_kernel(DeviceIndex ix, const uint64_t* __restrict__ items_flat, const uint32_t* __restrict__ q_off,
                                                         uint32_t nq, uint32_t m, uint32_t max_len, char* out, uint32_t stride, bool wide, uint32_t* zero_a, uint32_t* zero_b,
-                                                        const IdSlot* __restrict__ loc_table, uint32_t loc_mask, unsigned long long* __restrict__ okeys) {
+                                                        const IdSlot* __restrict__ loc_table, uint32_t loc_mask, unsigned long long* __restrict__ okeys, bool light, uint32_t* light_cnt) {
     // okeys (round 5, or null): one 64-bit sort key per query -- (dense idx of its MOST POPULAR known item, clamped to 16 bits) << 32 | q.  Queries that share their most
     // popular item share most of their posting-list entries and neighbour rows; the launch sequence sorts the batch by this key and serves it in that order, an eighth of
     // the order per XCD, so that the second of two such queries finds the first one's lines in its XCD's L2 (the dense idx is the popularity rank).
@@ -375,7 +375,11 @@ __global__ __launch_bounds__(256) void vmis_prep_kernel(DeviceIndex ix, const ui
     if (t == 8 && zero_b) *zero_b = 0u;
     const uint32_t q = t / PREP_LANES, sub = t % PREP_LANES;
     if (q >= nq) return;   // (nq is a multiple of nothing in particular: whole 8-lane groups leave together, the shuffles below stay within a group)
-    prep_group(ix, items_flat, q_off, q, sub, m, max_len, out + (size_t)q * stride, loc_table, loc_mask, okeys, wide);
+    const bool is_light = prep_group(ix, items_flat, q_off, q, sub, m, max_len, out + (size_t)q * stride, loc_table, loc_mask, okeys, wide, light);
+    if (light_cnt) {   // (a call that does not merge: the key is final here -- one atomic per wave and word, as n_dup is counted)
+        const unsigned long long b = __ballot(is_light && sub == 0u);
+        if (b != 0ull && (threadIdx.x & 63u) == (uint32_t)(__ffsll((long long)b) - 1)) { atomicAdd(&light_cnt[0], (uint32_t)__popcll(b)); atomicAdd(&light_cnt[1], (uint32_t)__popcll(b)); }
+    }
 }
 
 // Wave priorities by phase (s_setprio), as in vmis_fast_kernel (srn_fast.hip, where the measurements are): four decimal digits = front end (record .. cuts) | clears |
@@ -1525,10 +1529,10 @@ hipError_t launch_predict(const PredictLaunch& a, dim3 grid, size_t lds, hipStre
 }
 
 hipError_t launch_prep(hipStream_t st, const DeviceIndex& di, const uint64_t* items_flat, const uint32_t* q_off, uint32_t nq, uint32_t m,
-                       uint32_t max_len, char* out, uint32_t stride, bool wide, uint32_t* zero_a, uint32_t* zero_b, const IdSlot* loc_table, uint32_t loc_mask, unsigned long long* okeys) {
+                       uint32_t max_len, char* out, uint32_t stride, bool wide, uint32_t* zero_a, uint32_t* zero_b, const IdSlot* loc_table, uint32_t loc_mask, unsigned long long* okeys, bool light, uint32_t* light_cnt) {
     static_assert(sizeof(PrepHead) == 136 && offsetof(PrepHead, ready) == 72 && sizeof(PrepItem) == 24, "vmis_prep_kernel writes the record word by word");
     const uint32_t per_block = 256 / PREP_LANES;
-    hipLaunchKernelGGL(vmis_prep_kernel, dim3((nq + per_block - 1) / per_block), dim3(256), 0, st, di, items_flat, q_off, nq, m, max_len, out, stride, wide, zero_a, zero_b, loc_table, loc_mask, okeys);
+    hipLaunchKernelGGL(vmis_prep_kernel, dim3((nq + per_block - 1) / per_block), dim3(256), 0, st, di, items_flat, q_off, nq, m, max_len, out, stride, wide, zero_a, zero_b, loc_table, loc_mask, okeys, light, light_cnt);
     return hipGetLastError();
 }
 

@@ -187,7 +187,7 @@ int device_predict_tiny(DeviceState* d, const FlatIndex& ix, Workspace* w, const
     if (*(volatile uint32_t*)pin.rc.at(w->pin) != 0) return 1;   // (rare: tables too small for some query)
     // what the timing / path-count APIs report after this call: its query count, how many of them the fast sequence handed to the general kernel (all of them where the
     // two-launch form ran), not timed (the stream is idle here: nothing of an earlier call is still writing the pinned words)
-    ++w->untimed_calls; w->last_nq = p.nq; w->last_retry = 0; w->last_fast = tiny_fast; w->last_mid = tiny_fast && plan.mid_tier; w->last_dedup = false; w->last_untimed = true;   // (`calls` indexes the event ring: timed calls only)
+    ++w->untimed_calls; w->last_nq = p.nq; w->last_retry = 0; w->last_fast = tiny_fast; w->last_mid = tiny_fast && plan.mid_tier; w->last_dedup = false; w->last_light = false; w->last_untimed = true;   // (`calls` indexes the event ring: timed calls only)
     tiny_unstage(w, p, pin, h_ids, h_scores, h_counts);
     return SRN_OK;
 }

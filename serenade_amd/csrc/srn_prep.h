@@ -34,9 +34,12 @@ __device__ __forceinline__ void ready_words(const ReadyRuns& rr, uint32_t (&w)[R
 
 static constexpr uint32_t PREP_LANES = 8;
 // BLOCK = false (the latency path's inline call, vmis_fast_kernel<TINY>): the launch-ready block is written as zeros -- lean_ok clear: "decode the items" -- see there
+// light (the launch sequence serves its light queries with vmis_light_kernel, srn_light.hip): a query whose block says lean_ok, one run, kept <= RW_LIGHT_KEPT gets
+// RW_LIGHT and the order key 0xFFFE, every other query's key is clamped to 0xFFFD -- the light queries are one segment of the sorted order.  Returns RW_LIGHT's value
+// (every lane of the group).  A zero block (BLOCK = false) is never light.
 template <bool BLOCK = true>
-__device__ __forceinline__ void prep_group(const DeviceIndex& ix, const uint64_t* __restrict__ items_flat, const uint32_t* __restrict__ q_off, uint32_t q, uint32_t sub, uint32_t m, uint32_t max_len,
-                                           char* rec, const IdSlot* __restrict__ loc_table, uint32_t loc_mask, unsigned long long* __restrict__ okeys, bool wide) {
+__device__ __forceinline__ bool prep_group(const DeviceIndex& ix, const uint64_t* __restrict__ items_flat, const uint32_t* __restrict__ q_off, uint32_t q, uint32_t sub, uint32_t m, uint32_t max_len,
+                                           char* rec, const IdSlot* __restrict__ loc_table, uint32_t loc_mask, unsigned long long* __restrict__ okeys, bool wide, bool light = false) {
     const uint32_t qb = q_off[q], L = q_off[q + 1] - qb;
     PrepItem* items = (PrepItem*)(rec + sizeof(PrepHead));
     uint32_t U = 0, rmax = 0, xlo = 0, sumw = 0, P = 0, nruns = 0, n_staged = 0, cur_attr = SRN_ATTR_NONE, my_run_start = 0;
@@ -165,7 +168,7 @@ __device__ __forceinline__ void prep_group(const DeviceIndex& ix, const uint64_t
     hw[8 + sub] = sub < nruns ? my_run_start : 0u;
     // the launch-ready block: a session of <= 8 items has one round, lane s holds the item at position s (every lane of the group works out all 16 words, lane s stores two)
     static_assert(offsetof(PrepHead, ready) == 72 && RW_WORDS == 2 * PREP_LANES, "lane s writes words 2 s, 2 s + 1 of the block");
-    if constexpr (!BLOCK) *(uint2*)(hw + 18 + 2u * sub) = make_uint2(0u, 0u);
+    if constexpr (!BLOCK) { *(uint2*)(hw + 18 + 2u * sub) = make_uint2(0u, 0u); return false; }
     else {
         ReadyRuns rr;
         const uint32_t k1 = rounds == 1u ? kept_last : 0u;
@@ -176,10 +179,14 @@ __device__ __forceinline__ void prep_group(const DeviceIndex& ix, const uint64_t
         }
         uint32_t w[RW_WORDS];
         ready_words(rr, w, L, max_len, sumw, n_staged, rmax, xlo, unsafe, wide, __shfl(idx, 0, PREP_LANES));
+        const bool is_light = light && (w[RW_FLAGS] & 1u) != 0u && rr.nr == 1u && rr.kept[0] <= RW_LIGHT_KEPT;
+        if (is_light) w[RW_FLAGS] |= RW_LIGHT;
+        if (light && okeys && sub == 0) okeys[q] = ((unsigned long long)(is_light ? 0xFFFEu : min(hot_key, 0xFFFDu)) << 32) | q;   // (over the key written above)
         uint2 o = make_uint2(0u, 0u);
 #pragma unroll
         for (uint32_t s = 0; s < PREP_LANES; ++s) if (sub == s) o = make_uint2(w[2u * s], w[2u * s + 1u]);
         *(uint2*)(hw + 18 + 2u * sub) = o;
+        return is_light;
     }
 }
 

@@ -43,6 +43,8 @@ struct Knobs {
     int row_slots16 = -1;     // SRN_ROW_SLOTS = 16 | 64: the device row layout (-1 = by index kind: 64-byte slots unsharded, 16-byte fragment slots for item shards)
     int order_min = 131072;    // SRN_ORDER_MIN: batches of at least this many queries are served in the order of their most popular item, an eighth of the order per XCD (0 = never); the ordering
                               // pass is one radix sort of the batch's keys behind the prep kernel
+    int light_min = 131072;    // SRN_LIGHT_MIN: ordered batches of at least this many queries serve their light queries (one posting run of <= 64 kept entries) one wave each, with
+                              // vmis_light_kernel in front of the lean launch (srn_light.hip); 0 = never.  The A/B switch of the form
     bool no_dedup = false;     // SRN_NO_DEDUP: every query of an ordered batch is served, also the copies of an earlier query of the same call (srn_dedup.hip; A/B and the tests' reference)
     int dedup_hash_bits = 0;   // SRN_DEDUP_HASH_BITS (tests only): the grouping pass's hash cut to this many bits -- unequal queries share hashes and the probe chains get long; 0 = all 32
     int cache_hash_bits = 0;   // SRN_CACHE_HASH_BITS (tests only): the result cache's hash cut to this many bits -- unequal sequences share buckets, and only the comparison of the keys keeps them apart; 0 = all 32
@@ -75,6 +77,7 @@ struct Workspace {
     bool last_fast = false;      // the last call went through the fast kernel: h_retry[HW_GENERAL] = what it handed to the general kernel (otherwise: all of last_nq)
     bool last_mid = false;       // ... and through its MID instantiation: h_retry[HW_MID] = the queries the lean instantiation listed for it
     bool last_dedup = false;     // ... and merged the queries with equal sequences: h_retry[HW_MERGED] = how many were merged
+    bool last_light = false;     // ... and served its light queries with vmis_light_kernel: h_retry[HW_LIGHT] = the light representatives
     bool last_untimed = false;   // the last call took the latency path: no events were recorded for it
     // device scratch
     uint32_t* retry_list = nullptr; size_t retry_cap = 0; uint32_t* retry_cnt = nullptr;

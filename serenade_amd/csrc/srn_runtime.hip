@@ -46,6 +46,7 @@ static void knobs_read() {
     k.tiny_fast = env_int("SRN_TINY_FAST", k.tiny_fast, 0, 3);
     k.lanes = env_int("SRN_PREDICT_LANES", k.lanes, 0);
     k.order_min = env_int("SRN_ORDER_MIN", k.order_min, 0);
+    k.light_min = env_int("SRN_LIGHT_MIN", k.light_min, 0);
     k.no_dedup = env_flag("SRN_NO_DEDUP"); k.dedup_hash_bits = env_int("SRN_DEDUP_HASH_BITS", 0, 0, 32);
     k.cache_hash_bits = env_int("SRN_CACHE_HASH_BITS", 0, 0, 32);
     k.no_sback_second = env_flag("SRN_NO_SBACK_SECOND");
@@ -534,8 +535,9 @@ FastPlan fast_plan(const DeviceState* d, const FlatIndex& ix, const LaunchParams
 // itself, enqueued on the stream the prep kernel ran on.
 struct DedupRoom { uint32_t* n_dup = nullptr; uint32_t* rep = nullptr; uint32_t* slots = nullptr; uint32_t* slot_min = nullptr; uint32_t n_slots = 0; };
 struct OrderBufs { unsigned long long* keys_in = nullptr; unsigned long long* keys_out = nullptr; void* temp = nullptr; size_t temp_bytes = 0; DedupRoom dd;
-                   uint32_t* n_skip = nullptr; };   // (a call that uses the result cache) queries at the end of the order that nobody serves: the merged ones + the cache's hits
-static int order_room(char** buf, size_t* have, uint32_t nq, OrderBufs* o, bool dedup = false, bool cache = false) {
+                   uint32_t* n_skip = nullptr;   // (a call that uses the result cache) queries at the end of the order that nobody serves: the merged ones + the cache's hits
+                   uint32_t* light_cnt = nullptr; };   // (the light form is on) [0] the light representatives of the call, [1] merged + light: where the lean kernel's loop ends (FastParams::order_dups)
+static int order_room(char** buf, size_t* have, uint32_t nq, OrderBufs* o, bool dedup = false, bool cache = false, bool light = false) {
     DedupRoom* dd = dedup ? &o->dd : nullptr;
     size_t tb = 0;
     if (sort_order_keys(nullptr, nullptr, nullptr, nq, nullptr, &tb) != hipSuccess) return fail(SRN_EHIP, "rocprim::radix_sort_keys (size query) failed");
@@ -544,10 +546,11 @@ static int order_room(char** buf, size_t* have, uint32_t nq, OrderBufs* o, bool 
     //  the side stream while the previous call's kernels still read THEIR count and representatives)
     const size_t rb = ((size_t)nq * 4 + 255) / 256 * 256, n_slots = dd ? dedup_slots(nq) : 0;
     const size_t dd_bytes = dd ? 256 + rb + 2 * n_slots * 4 : 0;
-    int rc = ensure(buf, have, 2 * kb + tbr + 256 + dd_bytes + (cache ? 256 + 256 : 0)); if (rc) return rc;
+    int rc = ensure(buf, have, 2 * kb + tbr + 256 + dd_bytes + (cache || light ? 256 + 256 : 0)); if (rc) return rc;
     o->keys_in = (unsigned long long*)*buf; o->keys_out = (unsigned long long*)(*buf + kb); o->temp = *buf + 2 * kb; o->temp_bytes = tb;
     if (dd) { char* b = *buf + 2 * kb + tbr + 256; dd->n_dup = (uint32_t*)b; dd->rep = (uint32_t*)(b + 256); dd->slots = (uint32_t*)(b + 256 + rb); dd->slot_min = dd->slots + n_slots; dd->n_slots = (uint32_t)n_slots; }
     if (cache) o->n_skip = (uint32_t*)(*buf + (2 * kb + tbr + 256 + dd_bytes + 255) / 256 * 256);
+    if (light) o->light_cnt = (uint32_t*)(*buf + (2 * kb + tbr + 256 + dd_bytes + 255) / 256 * 256);   // (never both: a call that uses the result cache has no light form)
     return SRN_OK;
 }
 
@@ -590,6 +593,7 @@ struct LaunchPlan {
     FastPlan fast;
     bool resident = false, order_set2 = false;                      // SRN_FLAG_INPUTS_RESIDENT: the front on the side stream; on the second set of order buffers
     bool ordered = false, dedup = false, prep_clears = false;
+    bool light = false;                                             // the call's light queries -- one posting run of <= 64 kept entries -- are served by vmis_light_kernel (srn_light.hip), a wave each
     bool cache = false;                                             // the call looks its queries up in the index's result cache and stores what it served (srn_result_cache.hip)
 };
 // the global-table pass: tables at twice the worst case in a global-memory arena per workgroup (cg: geo.c on entry), as many workgroups as 2 GB hold, at most one per CU
@@ -628,6 +632,9 @@ static LaunchPlan make_plan(const DeviceState* d, const FlatIndex& ix, const Lau
     // the hits' rows are written into the caller's buffers at the front of the call, which on the side stream could overtake a previous call that still owns them.
     pl.cache = rcache != nullptr && pl.fast.fast && !ext && p.k == rcache->k && p.m == rcache->m && p.how_many == rcache->how_many && (p.flags & SRN_FLAG_BUSINESS_LOGIC) == rcache->flags;
     if (pl.cache) { pl.ordered = true; pl.resident = false; resident = false; }
+    // The light form: K = kept needs k >= 64, finish_inline ranks <= 64 entries; its segment of the order exists in an ordered call only.  SRN_LIGHT_MIN is
+    // the A/B switch, and keeps small ordered batches (SRN_ORDER_MIN=1 in the tests) on the lean chain
+    pl.light = pl.ordered && pl.fast.fast && !ext && !pl.cache && p.k >= RW_LIGHT_KEPT && p.how_many <= 64u && kn.light_min > 0 && p.nq >= (uint32_t)kn.light_min && d->di.row_frag == 0u;
     // (one order per set of prep records: a resident call's prep kernel and sort run on the side stream while the previous call's kernels still read THEIR order)
     pl.order_set2 = resident && (w->resident_calls & 1u) != 0u;
     // The prep kernel clears the launch sequence's counters where it runs on this stream ahead of everything that uses them (two fill kernels otherwise: 6 us each)
@@ -649,7 +656,7 @@ static int reserve_batch(Workspace* w, const LaunchPlan& pl, const LaunchParams&
         rc = ensure_side(w); if (rc) return rc;
     }
     if (pl.fast.fast) { int rc = reserve_fast(w, p.nq); if (rc) return rc; }
-    if (pl.ordered) return order_room(pl.order_set2 ? &w->order2 : &w->order, pl.order_set2 ? &w->order2_bytes : &w->order_bytes, p.nq, &ob, pl.dedup, pl.cache);
+    if (pl.ordered) return order_room(pl.order_set2 ? &w->order2 : &w->order, pl.order_set2 ? &w->order2_bytes : &w->order_bytes, p.nq, &ob, pl.dedup, pl.cache, pl.light);
     return SRN_OK;
 }
 
@@ -704,11 +711,13 @@ static int fetch_host_outputs(const BatchCall& c, const HostRows& h) {
 // stream (prep_clears) the prep kernel also clears the sequence's counters and the grouping pass writes the merged rows' count words; a resident call runs it on the side stream.
 static int enqueue_front(BatchCall& c, hipStream_t s, char* rec) {
     const LaunchParams& p = c.p; const LaunchPlan& pl = c.pl; OrderBufs& ob = c.ob; Workspace* w = c.w;
+    // (the light form: the light representatives are counted where their key becomes final -- by the grouping pass's resolve kernel, or, in a call that does not merge, by the prep kernel)
+    if (pl.light && !pl.dedup) HIP_TRY(hipMemsetAsync(ob.light_cnt, 0, 8, s));
     HIP_TRY(launch_prep(s, c.di, p.items_flat, p.q_off, p.nq, p.m, p.max_len, rec, pl.prep_stride, pl.fast.nb_fast == 3u, pl.prep_clears && pl.fast.fast ? w->slow_cnt : nullptr,
-                        pl.prep_clears && pl.retry ? w->retry_cnt : nullptr, nullptr, 0, ob.keys_in));
+                        pl.prep_clears && pl.retry ? w->retry_cnt : nullptr, nullptr, 0, ob.keys_in, pl.light, pl.light && !pl.dedup ? ob.light_cnt : nullptr));
     if (pl.dedup) {   // (a resident call: the count word of a merged row is written on the caller's stream -- the previous call's kernels may still be writing these very buffers)
         HIP_TRY(hipMemsetAsync(ob.dd.slots, 0xFF, (size_t)ob.dd.n_slots * 8, s));
-        HIP_TRY(launch_dedup_group(s, p.items_flat, p.q_off, p.nq, ob.dd.slots, ob.dd.slot_min, ob.dd.n_slots, (uint32_t)pl.kn.dedup_hash_bits, ob.dd.rep, ob.keys_in, pl.prep_clears ? p.out_counts : nullptr, ob.dd.n_dup));
+        HIP_TRY(launch_dedup_group(s, p.items_flat, p.q_off, p.nq, ob.dd.slots, ob.dd.slot_min, ob.dd.n_slots, (uint32_t)pl.kn.dedup_hash_bits, ob.dd.rep, ob.keys_in, pl.prep_clears ? p.out_counts : nullptr, ob.dd.n_dup, pl.light ? ob.light_cnt : nullptr));
     }
     // the result cache's lookup: over the representatives, behind their grouping and ahead of the sort -- a hit's row is written here, its key moves behind the served queries
     if (pl.cache) { int rc = rcache_enqueue_lookup(c.rcache, s, p, pl.dedup ? ob.dd.rep : nullptr, ob.keys_in, pl.dedup ? ob.dd.n_dup : nullptr, ob.n_skip, pl.kn.cache_hash_bits, &c.cache_now); if (rc) return rc; }
@@ -780,7 +789,9 @@ static int enqueue_fast_tiers(BatchCall& c) {
     const bool back = ext && ext->mode == 2;   // neighbour lists from the exchange buffer (any rank's front end), this shard's rows
     if (back) { fp.xchg = ext->x.words; fp.xchg_stride = ext->x.stride; }
     fp.order = pl.ordered ? c.ob.keys_out : back ? ext->order : nullptr;
-    fp.order_dups = pl.cache ? c.ob.n_skip : pl.dedup ? c.ob.dd.n_dup : nullptr;   // (the cache's count: its hits + the merged queries)
+    fp.order_dups = pl.cache ? c.ob.n_skip : pl.light ? c.ob.light_cnt + 1 : pl.dedup ? c.ob.dd.n_dup : nullptr;   // (the cache's count: its hits + the merged queries; the light form's: the merged queries + the light ones)
+    // the light form, right behind the front and ahead of the lean launch: a fixed grid of waves that stride over the light segment of the order and leave at once when it is empty
+    if (pl.light) HIP_TRY(launch_light(st, (uint32_t)std::min<uint64_t>((p.nq + 3u) / 4u, (uint64_t)d->n_cu * 4u), c.di, p, c.ob.keys_out, c.ob.light_cnt, c.ob.light_cnt + 1, fp.slow_list, fp.slow_cnt, w->h_retry_dev + HW_LIGHT));
     const uint32_t grid_fo = fp.order ? std::max<uint32_t>(8u, pl.grid_fast / 8u * 8u) : pl.grid_fast;   // (an ordered launch walks an eighth of the order per XCD: the grid is a multiple of 8)
     if (back && d->sback.frag8 && !kn.no_sback && p.max_len <= 8) { int rc = enqueue_shard_back(c); if (rc) return rc; }
     else HIP_TRY(launch_fast(back ? FastForm::Back : FastForm::Lean, dim3(grid_fo), st, c.di, p, fp, kn.debug));
@@ -846,7 +857,7 @@ static int enqueue_tail(BatchCall& c) {
     HIP_TRY(hipEventRecord(c.ev[2], st));
     if (pl.resident) { const int par = (int)(w->resident_calls & 1u); HIP_TRY(hipEventRecord(w->ev_done[par], st)); w->rec_used[par] = true; ++w->resident_calls; }
     else if (!c.ext && w->side) { HIP_TRY(hipEventRecord(w->ev_done[0], st)); w->rec_used[0] = true; }   // (a workspace that has served resident calls: the next one's side-stream prep must not overwrite w->prep under this call's kernels)
-    ++w->calls; w->last_retry = pl.retry ? 1 : 0; w->last_nq = p.nq; w->last_fast = fast; w->last_mid = fast && (pl.fast.mid_tier || c.sback_second); w->last_dedup = pl.dedup; w->last_untimed = false;
+    ++w->calls; w->last_retry = pl.retry ? 1 : 0; w->last_nq = p.nq; w->last_fast = fast; w->last_mid = fast && (pl.fast.mid_tier || c.sback_second); w->last_dedup = pl.dedup; w->last_light = pl.light; w->last_untimed = false;
     if (pl.retry) w->h_retry_valid = true;   // (from now on the pinned counter holds a finished call's count -- or is being overwritten by a newer one)
     return SRN_OK;
 }
@@ -1178,6 +1189,15 @@ int device_last_dedup_count(DeviceState* d, uint32_t* merged) {   // queries of 
     Workspace* w;
     { std::lock_guard<std::mutex> lk(d->mu); w = d->last_ws; }
     if (merged) *merged = w->last_dedup ? w->h_retry[HW_MERGED] : 0u;
+    return SRN_OK;
+}
+
+int device_last_light_count(DeviceState* d, uint32_t* light) {   // light representatives of the last call: served by vmis_light_kernel or handed on by it (0: the form was off in that call)
+    const int rc = device_last_path_counts(d, nullptr, nullptr, nullptr);   // (waits for the call's end)
+    if (rc != SRN_OK) return rc;
+    Workspace* w;
+    { std::lock_guard<std::mutex> lk(d->mu); w = d->last_ws; }
+    if (light) *light = w->last_light ? w->h_retry[HW_LIGHT] : 0u;
     return SRN_OK;
 }
 

@@ -284,6 +284,13 @@ class VMISIndex:
         capi.check(capi.lib().srn_debug_last_dedup_count(self._h, C.byref(a)))
         return a.value
 
+    def last_light_count(self):
+        """Light representatives of the last call: distinct queries with one posting run of <= 64 kept entries, which the light form served one wave each (0: the form was
+        off in that call -- SRN_LIGHT_MIN, a result-cache call); measurement aid."""
+        a = C.c_uint32()
+        capi.check(capi.lib().srn_debug_last_light_count(self._h, C.byref(a)))
+        return a.value
+
     def last_big_count(self):
         """... and how many of those the MID instantiation listed for its BIG form (merged lists beyond the 53 KB layout's buffers); measurement aid."""
         a = C.c_uint32()
