@@ -97,6 +97,18 @@ int srn_debug_merge_pair(uint32_t* room, const uint32_t* pairs, size_t n_pairs, 
 int srn_debug_prep_records(const srn_index_t* idx, const uint64_t* items_flat, const uint32_t* q_off, size_t nq, size_t m, size_t max_len, void* out_records, size_t cap_bytes,
                            size_t* out_stride);
 
+/* Test aid (tests/test_gpu_general_edges.py): what the runtime decides for ONE launch of the general kernel (vmis_predict_kernel) with these parameters on this index
+ * under the current SRN_* knobs -- the LDS layout and table sizes every workgroup of a plain predict call gets (no extra room in region B).  Host code only: nothing is
+ * launched.  out_words [SRN_DEBUG_GEOMETRY_WORDS]:
+ *   [0] masks (position-set slots)  [1] slot64  [2] bytes per session slot  [3] LDS bytes per workgroup  [4] sess_may_overflow  [5] item_may_overflow  [6] sketch_may_wrap
+ *   [7] the device's LDS bytes per workgroup as the layout uses it (an input of the decision, reported so that a restatement can take it)
+ *   [8..23] the kernel's configuration words in declaration order: sess_slots, item_slots, item_buckets, hot_slots, sketch_slots, sketch_shift, sum_bits, num_bits, q_cap,
+ *           off_q, off_wave, off_b, off_a, region_a_bytes, no_merge, 0
+ * The geometry depends on neither the batch size nor how_many, so the call takes neither.  SRN_ENODEV: the index has no device attached; SRN_ERANGE where the
+ * runtime refuses the launch (k / session length too large for the layout or the accumulators). */
+#define SRN_DEBUG_GEOMETRY_WORDS 24
+int srn_debug_geometry(const srn_index_t* idx, size_t k, size_t m, size_t max_len, unsigned flags, uint32_t* out_words);
+
 /* Test / experiment knobs (environment variables SRN_NO_FAST, SRN_NO_MID, SRN_NO_MASKS, SRN_NO_MERGE, SRN_HOT_SLOTS,
  * SRN_SKETCH_SLOTS, SRN_LDS_BUDGET_KB, SRN_GRID_MULT, SRN_DEBUG) force individual kernel code paths.  They are read ONCE,
  * when the library is first used -- never on the launch path; this call re-reads them (the parity tests switch paths

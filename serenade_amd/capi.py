@@ -245,6 +245,7 @@ SYMBOLS = {
     "srn_debug_serve_lane_counts": (_i, [_vp, C.c_uint, _vp, _sz, C.POINTER(_sz)]),
     "srn_debug_shard_nb_positions_stride": (C.c_uint32, [_sz, _sz]),
     "srn_debug_last_big_count": (_i, [_vp, C.POINTER(C.c_uint32)]),
+    "srn_debug_geometry": (_i, [_vp, _sz, _sz, _sz, C.c_uint, _vp]),
     "srn_debug_prep_records": (_i, [_vp, _vp, _vp, _sz, _sz, _sz, _vp, _sz, C.POINTER(_sz)]),
     "srn_debug_sback_launches": (_i, [_vp, C.POINTER(_u64)]),
     "srn_last_path_counts": (_i, [_vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),

@@ -749,6 +749,12 @@ int srn_debug_prep_records(const srn_index_t* idx, const uint64_t* items_flat, c
     if (!idx || !idx->dev) return fail(SRN_ENODEV, "index has no device attached");
     return guarded([&]() -> int { return device_debug_prep_records(idx->dev, idx->flat, items_flat, q_off, nq, m, max_len, out_records, cap_bytes, out_stride); });
 }
+int srn_debug_geometry(const srn_index_t* idx, size_t k, size_t m, size_t max_len, unsigned flags, uint32_t* out_words) {
+    if (!idx || !idx->dev) return fail(SRN_ENODEV, "index has no device attached");
+    if (!out_words) return fail(SRN_EINVAL, "null argument");
+    if (k == 0 || k > 0xFFFFFFFFull || m == 0 || m > 0xFFFFFFFFull || max_len == 0 || max_len > SRN_MAX_SESSION_LEN) return fail(SRN_ERANGE, "srn_debug_geometry: sizes out of range");
+    return guarded([&]() -> int { return device_debug_geometry(idx->dev, idx->flat, launch_params(1, k, m, 21, flags, max_len), out_words); });   // (the geometry reads neither the batch size nor how_many)
+}
 int srn_debug_last_dedup_count(const srn_index_t* idx, uint32_t* out_merged) {
     if (!idx || !idx->dev || !out_merged) return fail(SRN_EINVAL, "null argument");
     return guarded([&]() -> int { return device_last_dedup_count(idx->dev, out_merged); });

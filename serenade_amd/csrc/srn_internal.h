@@ -246,6 +246,7 @@ struct ShardLists { uint32_t n_shards; const uint32_t* kept_g; const long long* 
 int device_shard_lists_predict(const ShardCall& c, const LaunchParams& p, const ShardLists& l, char* records);
 int device_shard_stage(const ShardCall& c, int stage, const LaunchParams& p, const ShardIO& sh);
 int device_slot_bytes(DeviceState* d, const FlatIndex& ix, uint32_t max_len, uint32_t* num_bits = nullptr);
+int device_debug_geometry(DeviceState* d, const FlatIndex& ix, const LaunchParams& p, uint32_t* out24);   // test aid (srn_debug_geometry): make_geometry's decision for a plain predict launch, as words
 // ---- the persistent latency path (round 6): resident workgroups that serve srn_predict's call shape without a launch ----
 // lanes: resident workgroups of the lean form (sessions of <= 4 items); max_items >= 5: as many of the MID form (5..10 items) beside them; idle_ms: a resident workgroup
 // leaves by itself after that long without a request (it is started again by the next call that wants it)

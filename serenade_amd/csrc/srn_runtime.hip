@@ -1111,6 +1111,19 @@ int device_slot_bytes(DeviceState* d, const FlatIndex& ix, uint32_t max_len, uin
     return (int)g.slot_bytes;
 }
 
+int device_debug_geometry(DeviceState* d, const FlatIndex& ix, const LaunchParams& p, uint32_t* out24) {   // (host code only: no launch, no hipSetDevice)
+    Geometry g;
+    const int rc = make_geometry(d, ix, p, 0, g); if (rc) return rc;   // (min_region_b = 0: what predict_core passes)
+    const KernelCfg& c = g.c;
+    const uint32_t w[24] = {g.masks ? 1u : 0u, g.slot64 ? 1u : 0u, g.slot_bytes, (uint32_t)g.lds, g.sess_may_overflow ? 1u : 0u, g.item_may_overflow ? 1u : 0u, g.sketch_may_wrap ? 1u : 0u,
+                            (uint32_t)std::min(d->lds_per_block_max, 160 * 1024),
+                            c.sess_slots, c.item_slots, c.item_buckets, c.hot_slots, c.sketch_slots, c.sketch_shift, c.sum_bits, c.num_bits, c.q_cap,
+                            c.off_q, c.off_wave, c.off_b, c.off_a, c.region_a_bytes, c.no_merge, 0u};
+    static_assert(sizeof(KernelCfg) == 15 * 4, "srn_debug_geometry reports every word of KernelCfg: a new word belongs in the list above");
+    for (int i = 0; i < 24; ++i) out24[i] = w[i];
+    return SRN_OK;
+}
+
 int device_last_kernel_ms(DeviceState* d, double* ms_main, double* ms_retry, uint32_t* retried) {
     HIP_TRY(hipSetDevice(d->device));
     Workspace* w;

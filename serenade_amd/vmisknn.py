@@ -297,6 +297,17 @@ class VMISIndex:
         capi.check(capi.lib().srn_debug_last_big_count(self._h, C.byref(a)))
         return a.value
 
+    GEOMETRY_WORDS = ("masks", "slot64", "slot_bytes", "lds", "sess_may_overflow", "item_may_overflow", "sketch_may_wrap", "lds_max",
+                      "sess_slots", "item_slots", "item_buckets", "hot_slots", "sketch_slots", "sketch_shift", "sum_bits", "num_bits", "q_cap",
+                      "off_q", "off_wave", "off_b", "off_a", "region_a_bytes", "no_merge")
+
+    def debug_geometry(self, k, m, max_len, flags=0):
+        """srn_debug_geometry: what the runtime decides for one launch of the general kernel at (k, m, max_len, flags) under the current knobs -> {name: word}
+        (GEOMETRY_WORDS).  Host code only, nothing is launched; test aid."""
+        out = np.zeros(24, np.uint32)
+        capi.check(capi.lib().srn_debug_geometry(self._h, int(k), int(m), int(max_len), int(flags), capi.ptr(out)))
+        return dict(zip(self.GEOMETRY_WORDS, (int(x) for x in out)))
+
     def kernel_times(self, max_n=64):
         """Per-call (main kernel ms, retry pass ms) of the most recent predict calls, oldest first (HIP events
         recorded on the launch stream around each launch)."""
