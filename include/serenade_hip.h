@@ -837,6 +837,67 @@ int srn_feedback_bootstrap_info(srn_feedback_t* f, uint32_t* replicates, uint64_
 int srn_feedback_bootstrap_read(srn_feedback_t* f, uint64_t* observed, uint64_t* hits_model, uint64_t* hits_filled, size_t replicates_cap, size_t rank_cap);
 int srn_feedback_bootstrap_weights(uint64_t seed, uint32_t replicate, const uint64_t* key_hi, const uint64_t* key_lo, size_t n, uint8_t* out);
 
+/* ---- traffic split: one batch served under several arms, sticky per visitor (srn_arms.hip) ----
+ * A split is (seed, weights[0 .. A)), A = 1 .. SRN_MAX_ARMS, weights uint32 (zeros allowed), W = their sum in 1 .. 2^32 - 1.  A visitor's arm is
+ *   fold(key)  = mix64(key_hi ^ 0x9E3779B97F4A7C15) ^ key_lo                      (the feedback bootstrap's fold)
+ *   u          = mix64( mix64(seed ^ 0x53524E5F41524D53) ^ (fold * 0xD1B54A32D192ED03 + 1) ) >> 32
+ *   T_a        = floor(2^32 * (w_0 + .. + w_a) / W),  a = 0 .. A-2            (64-bit: T_a may be 2^32)
+ *   arm(key)   = #{ a : T_a <= u }
+ * so arm a holds the u in [T_(a-1), T_a), an arm of weight 0 holds nothing, and the arm depends on (seed, weights, key) alone: not on consent, the item, the time,
+ * the batch, the cut of the requests into calls or the run.  A request without consent is assigned by its key like any other and served with its arm's parameters.
+ * srn_recommend_batch_split_device serves request i with arms[arm(key_i)]: its index, window, k, m and flags (those of srn_recommend_batch*), all arms against the one
+ * store, and feeds arm a's requests and rows to arms[a].feedback where that is not NULL.  Rows, store, an attached harvest and every log are left as by one
+ * srn_recommend_batch_device[_at] call (and one srn_feedback_observe_device[_at] call) per non-empty arm, arm 0 first, each over its arm's requests in request order
+ * with the call's one `now` (now_secs = 0: the system clock, read once for all of them).  A visitor is in one arm, so the visitor's clicks stay in order.
+ * The call assigns, counts and gathers the requests by arm on `stream`, then WAITS FOR THE STREAM ONCE (hipStreamSynchronize: the arms' calls need their sizes on
+ * the host), then enqueues the arms' calls into arm-ordered row buffers and one kernel that puts the rows back in request order; it returns without waiting again.
+ * As in the plain call, entries of a row beyond its count are not written.  d_out_arm[n] (may be NULL) receives the arms, d_out_rank[n] (may be NULL) the logs'
+ * ranks -- SRN_FEEDBACK_NONE for the requests of an arm without a log.  A log that refuses its arm's call under its capacity rule does not fail the call: the rows
+ * are served, the arm's ranks are SRN_FEEDBACK_NONE and feedback_rc[a] (may be NULL; SRN_OK otherwise) is SRN_ENOMEM.
+ * The store's capacity rule is asked once for all n requests before the first arm is served, so SRN_ENOMEM leaves the store as it was.  With A = 1 the call is the
+ * plain call on the caller's buffers: no scratch, no kernel of its own, no synchronisation (counted in shortcut_calls, not in calls).
+ * create allocates every buffer of the device form -- about max_batch * (46 + 16 * max_how_many) bytes, none for A = 1 -- so calls allocate nothing; the host form
+ * stages through a buffer that grows with the largest call, as srn_recommend_batch does.  Calls on one handle take turns (a mutex, and an event between
+ * consecutive calls).  The arms' indices may differ but must be on the split's device, as the store and the logs.  The result cache behaves as for any call.
+ * Errors, all before anything is enqueued or changed: NULL handle, arms, store, request array or output (ids, scores, counts) SRN_EINVAL; n_arms outside
+ * 1 .. SRN_MAX_ARMS SRN_ERANGE, not the handle's SRN_EINVAL; W = 0 SRN_EINVAL, W >= 2^32 SRN_ERANGE; n > max_batch, how_many > max_how_many or above a log's row_cap
+ * SRN_ERANGE; one log in two arms, an index or a log on another device SRN_EINVAL; and for every arm the error srn_recommend_batch_device gives for its parameters.
+ * n = 0: SRN_OK.  create: max_batch or max_how_many 0 SRN_EINVAL, max_batch above 2^24 or max_how_many above SRN_MAX_HOW_MANY SRN_ERANGE, no such GPU SRN_ENODEV.
+ *   set_weights  the ramp: other weights for the same number of arms, from the next call on.  Only the keys whose u lies between an old and a new threshold move.
+ *   arms         the rule on the host, no GPU needed: out[i] = arm(key_hi[i], key_lo[i]).  n = 0: SRN_OK; a NULL array with n > 0: SRN_EINVAL.
+ *   info         thresholds[a] = T_a for a < n_arms (thresholds[n_arms - 1] = 2^32), 0 behind; served[a] = requests arm a has served; device_bytes: what the
+ *                handle holds on the device now. */
+#define SRN_MAX_ARMS 16
+typedef struct srn_traffic_split srn_traffic_split_t;
+typedef struct {
+    const srn_index_t* idx;
+    srn_feedback_t* feedback;   /* or NULL */
+    uint32_t max_items_in_session, k, m, flags;
+} srn_arm_t;
+typedef struct {
+    uint32_t n_arms, max_how_many;
+    uint64_t seed, max_batch, device_bytes, thresholds[SRN_MAX_ARMS], served[SRN_MAX_ARMS], calls, shortcut_calls;
+} srn_traffic_split_info_t;
+int srn_traffic_split_create(int device, const uint32_t* weights, size_t n_arms, uint64_t seed, size_t max_batch, size_t max_how_many, srn_traffic_split_t** out);
+int srn_traffic_split_free(srn_traffic_split_t* split);
+int srn_traffic_split_info(const srn_traffic_split_t* split, srn_traffic_split_info_t* out);
+int srn_traffic_split_set_weights(srn_traffic_split_t* split, const uint32_t* weights, size_t n_arms);
+int srn_traffic_split_arms(uint64_t seed, const uint32_t* weights, size_t n_arms, const uint64_t* key_hi, const uint64_t* key_lo, size_t n, uint8_t* out);
+/* d_times NULL: an untimed batch; otherwise the timed one (srn_recommend_batch_device_at), now_secs its sweep clock */
+int srn_recommend_batch_split_device(srn_traffic_split_t* split, const srn_arm_t* arms, size_t n_arms, srn_device_sessions_t* store,
+                                     const uint64_t* d_key_hi, const uint64_t* d_key_lo, const uint64_t* d_item_ids, const uint8_t* d_consent, const uint64_t* d_times,
+                                     size_t n, uint64_t now_secs, size_t how_many, uint64_t* d_out_ids, double* d_out_scores, uint32_t* d_out_counts,
+                                     uint8_t* d_out_arm, uint32_t* d_out_rank, int* feedback_rc, void* stream);
+/* The same with host pointers (pageable allowed): staged, served through the device form on a stream of the handle's, copied back; blocks. */
+int srn_recommend_batch_split(srn_traffic_split_t* split, const srn_arm_t* arms, size_t n_arms, srn_device_sessions_t* store,
+                              const uint64_t* key_hi, const uint64_t* key_lo, const uint64_t* item_ids, const uint8_t* consent, const uint64_t* times,
+                              size_t n, uint64_t now_secs, size_t how_many, uint64_t* out_ids, double* out_scores, uint32_t* out_counts,
+                              uint8_t* out_arm, uint32_t* out_rank, int* feedback_rc);
+/* (measurement aid) with timing enabled the device form records HIP events around its own kernels; last_ms waits for them: *ms_front = assign + offsets + gather,
+ * *ms_scatter = the scatter (either may be NULL).  SRN_EINVAL when the last call was not timed or took the shortcut. */
+int srn_traffic_split_timing(srn_traffic_split_t* split, int enable);
+int srn_traffic_split_last_ms(srn_traffic_split_t* split, double* ms_front, double* ms_scatter);
+
 /* ---- session harvest: finished sessions logged on the device, and training events from them (srn_harvest.hip) ----
  * A harvest is a device-resident log, attached to one device session store, that receives every session at the moment the store forgets it: each one exactly once,
  * on the stream of the call that forgets it, with nothing read back.  An entry (key, epoch, len, items[0 .. len)) is harvested when, and only when, the store drops

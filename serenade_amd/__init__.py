@@ -7,7 +7,7 @@ used by bench.py (synth)."""
 from .vmisknn import CSR, ItemScore, VMISIndex, SerenadeError, predict, predict_batch, predict_batch_debug, predict_batch_device, predict_batch_device_excl, reserve  # noqa: F401
 from .evaluation import EvalSet, evaluate  # noqa: F401
 from .ingest import TrainingSessions  # noqa: F401
-from .serving import SessionHarvest, harvest_model, refreshed_index, replay  # noqa: F401
+from .serving import SessionHarvest, TrafficSplit, arms_model, harvest_model, recommend_batch_split, refreshed_index, replay, split_compare  # noqa: F401
 
 _PREPARE = ("Split", "backtest", "read_events", "split_events", "split_model")
 
@@ -21,4 +21,5 @@ def __getattr__(name):   # prepare is also a command (python -m serenade_amd.pre
 
 
 __all__ = ["CSR", "ItemScore", "VMISIndex", "SerenadeError", "predict", "predict_batch", "predict_batch_debug", "predict_batch_device", "predict_batch_device_excl", "reserve",
-           "EvalSet", "evaluate", "TrainingSessions", "SessionHarvest", "harvest_model", "refreshed_index", "replay", *_PREPARE]
+           "EvalSet", "evaluate", "TrainingSessions", "SessionHarvest", "harvest_model", "refreshed_index", "replay",
+           "TrafficSplit", "recommend_batch_split", "arms_model", "split_compare", *_PREPARE]

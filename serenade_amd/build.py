@@ -10,8 +10,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libserenade_hip.so")
 SYNTH_LIB = os.path.join(HERE, "libsrn_synth.so")
-SOURCES = ["srn_index.cpp", "srn_capi.cpp", "srn_batcher.cpp", "srn_combine.cpp", "srn_session_store.cpp", "srn_avro.cpp", "srn_kernels.hip", "srn_fast.hip", "srn_light.hip", "srn_dedup.hip", "srn_result_cache.hip", "srn_exclude.hip", "srn_fill.hip", "srn_shard.hip", "srn_sback.hip", "srn_runtime.hip", "srn_latency.hip", "srn_hostpipe.hip", "srn_group.hip", "srn_build_gpu.hip", "srn_eval.hip", "srn_bootstrap.hip", "srn_segments.hip", "srn_ingest.hip", "srn_sessions_dev.hip", "srn_trending.hip", "srn_feedback.hip", "srn_harvest.hip", "srn_split.hip"]
-HEADERS = ["srn_internal.h", "srn_kernels.h", "srn_device.h", "srn_prep.h", "srn_runtime.h", "srn_visitor_table.h", "srn_sessions_dev.h", "srn_visitors.h", "srn_bootstrap.h", "srn_segments.h", "srn_hipsync.h", "srn_events.h", os.path.join("..", "..", "include", "serenade_hip.h")]
+SOURCES = ["srn_index.cpp", "srn_capi.cpp", "srn_batcher.cpp", "srn_combine.cpp", "srn_session_store.cpp", "srn_avro.cpp", "srn_kernels.hip", "srn_fast.hip", "srn_light.hip", "srn_dedup.hip", "srn_result_cache.hip", "srn_exclude.hip", "srn_fill.hip", "srn_shard.hip", "srn_sback.hip", "srn_runtime.hip", "srn_latency.hip", "srn_hostpipe.hip", "srn_group.hip", "srn_build_gpu.hip", "srn_eval.hip", "srn_bootstrap.hip", "srn_segments.hip", "srn_ingest.hip", "srn_sessions_dev.hip", "srn_trending.hip", "srn_feedback.hip", "srn_harvest.hip", "srn_split.hip", "srn_arms.hip"]
+HEADERS = ["srn_internal.h", "srn_kernels.h", "srn_device.h", "srn_prep.h", "srn_runtime.h", "srn_visitor_table.h", "srn_sessions_dev.h", "srn_visitors.h", "srn_bootstrap.h", "srn_segments.h", "srn_hipsync.h", "srn_events.h", "srn_arms.h", os.path.join("..", "..", "include", "serenade_hip.h")]
 
 
 EXPERIMENT_ONLY_FLAGS = ("SRN_FAST_EXP_", "SRN_FAST_STOP", "SRN_FAST_EARLY_CLEAR", "SRN_ABLATE")   # "timing only, wrong results" macros of the kernels

@@ -135,6 +135,19 @@ class FeedbackStats(C.Structure):
                                           "requests", "no_consent", "first_seen", "idle_expired", "observed", "hits_model", "hits_filled", "stored")]
 
 
+MAX_ARMS = 16
+
+
+class Arm(C.Structure):
+    """srn_arm_t: one arm of a traffic split"""
+    _fields_ = [("idx", C.c_void_p), ("feedback", C.c_void_p)] + [(n, C.c_uint32) for n in ("max_items_in_session", "k", "m", "flags")]
+
+
+class TrafficSplitInfo(C.Structure):
+    _fields_ = [("n_arms", C.c_uint32), ("max_how_many", C.c_uint32), ("seed", C.c_uint64), ("max_batch", C.c_uint64), ("device_bytes", C.c_uint64),
+                ("thresholds", C.c_uint64 * MAX_ARMS), ("served", C.c_uint64 * MAX_ARMS), ("calls", C.c_uint64), ("shortcut_calls", C.c_uint64)]
+
+
 class HarvestStats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("capacity", "items_cap", "min_len", "stored", "stored_items", "lost", "skipped_short", "from_return", "from_rebuild", "cleared")]
 
@@ -305,6 +318,15 @@ SYMBOLS = {
     "srn_feedback_bootstrap_info": (_i, [_vp, C.POINTER(C.c_uint32), C.POINTER(_u64)]),
     "srn_feedback_bootstrap_read": (_i, [_vp, _vp, _vp, _vp, _sz, _sz]),
     "srn_feedback_bootstrap_weights": (_i, [_u64, C.c_uint32, _vp, _vp, _sz, _vp]),
+    "srn_traffic_split_create": (_i, [_i, _vp, _sz, _u64, _sz, _sz, C.POINTER(_vp)]),
+    "srn_traffic_split_free": (_i, [_vp]),
+    "srn_traffic_split_info": (_i, [_vp, C.POINTER(TrafficSplitInfo)]),
+    "srn_traffic_split_set_weights": (_i, [_vp, _vp, _sz]),
+    "srn_traffic_split_arms": (_i, [_u64, _vp, _sz, _vp, _vp, _sz, _vp]),
+    "srn_traffic_split_timing": (_i, [_vp, _i]),
+    "srn_traffic_split_last_ms": (_i, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "srn_recommend_batch_split_device": (_i, [_vp, C.POINTER(Arm), _sz, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _u64, _sz, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i), _vp]),
+    "srn_recommend_batch_split": (_i, [_vp, C.POINTER(Arm), _sz, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _u64, _sz, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i)]),
     "srn_harvest_create": (_i, [_i, _sz, _sz, C.c_uint32, C.POINTER(_vp)]),
     "srn_harvest_free": (_i, [_vp]),
     "srn_device_sessions_set_harvest": (_i, [_vp, _vp]),

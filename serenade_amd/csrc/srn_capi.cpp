@@ -1143,4 +1143,45 @@ int srn_feedback_bootstrap_weights(uint64_t seed, uint32_t replicate, const uint
         return SRN_OK; });
 }
 
+// ---- traffic split (srn_arms.hip) ----
+// an arm's predict parameters, as recommend_batch checks a call's
+static int check_arm(const srn_arm_t& arm, size_t how_many) {
+    int rc = check_predict_args(arm.idx, arm.k, arm.m, how_many); if (rc) return rc;
+    if ((rc = check_not_a_shard(arm.idx))) return rc;
+    if (arm.flags & ~(unsigned)(SRN_FLAG_BUSINESS_LOGIC | SRN_FLAG_EXCLUDE_SEEN | SRN_FLAG_FILL)) return fail(SRN_EINVAL, "srn_recommend_batch: unknown flags");
+    if ((arm.flags & SRN_FLAG_FILL) && (rc = check_has_fallback(arm.idx))) return rc;
+    return SRN_OK;
+}
+int srn_traffic_split_create(int device, const uint32_t* weights, size_t n_arms, uint64_t seed, size_t max_batch, size_t max_how_many, srn_traffic_split_t** out) {
+    return guarded([&]() -> int { return split_create(device, weights, n_arms, seed, max_batch, max_how_many, out); });
+}
+int srn_traffic_split_free(srn_traffic_split_t* split) { return guarded([&]() -> int { return split_free(split); }); }
+int srn_traffic_split_info(const srn_traffic_split_t* split, srn_traffic_split_info_t* out) { return guarded([&]() -> int { return split_info(split, out); }); }
+int srn_traffic_split_set_weights(srn_traffic_split_t* split, const uint32_t* weights, size_t n_arms) {
+    return guarded([&]() -> int { return split_set_weights(split, weights, n_arms); });
+}
+int srn_traffic_split_arms(uint64_t seed, const uint32_t* weights, size_t n_arms, const uint64_t* key_hi, const uint64_t* key_lo, size_t n, uint8_t* out) {
+    return guarded([&]() -> int { return split_arms_host(seed, weights, n_arms, key_hi, key_lo, n, out); });
+}
+int srn_traffic_split_timing(srn_traffic_split_t* split, int enable) { return guarded([&]() -> int { return split_timing(split, enable); }); }
+int srn_traffic_split_last_ms(srn_traffic_split_t* split, double* ms_front, double* ms_scatter) {
+    return guarded([&]() -> int { return split_last_ms(split, ms_front, ms_scatter); });
+}
+int srn_recommend_batch_split_device(srn_traffic_split_t* split, const srn_arm_t* arms, size_t n_arms, srn_device_sessions_t* store,
+                                     const uint64_t* d_key_hi, const uint64_t* d_key_lo, const uint64_t* d_item_ids, const uint8_t* d_consent, const uint64_t* d_times,
+                                     size_t n, uint64_t now_secs, size_t how_many, uint64_t* d_out_ids, double* d_out_scores, uint32_t* d_out_counts,
+                                     uint8_t* d_out_arm, uint32_t* d_out_rank, int* feedback_rc, void* stream) {
+    return guarded([&]() -> int {
+        return split_recommend_device(split, arms, n_arms, store, {d_key_hi, d_key_lo, d_item_ids, d_consent, d_times, n, now_secs}, how_many,
+                                      {d_out_ids, d_out_scores, d_out_counts, d_out_arm, d_out_rank, feedback_rc}, stream, check_arm); });
+}
+int srn_recommend_batch_split(srn_traffic_split_t* split, const srn_arm_t* arms, size_t n_arms, srn_device_sessions_t* store,
+                              const uint64_t* key_hi, const uint64_t* key_lo, const uint64_t* item_ids, const uint8_t* consent, const uint64_t* times,
+                              size_t n, uint64_t now_secs, size_t how_many, uint64_t* out_ids, double* out_scores, uint32_t* out_counts,
+                              uint8_t* out_arm, uint32_t* out_rank, int* feedback_rc) {
+    return guarded([&]() -> int {
+        return split_recommend_host(split, arms, n_arms, store, {key_hi, key_lo, item_ids, consent, times, n, now_secs}, how_many,
+                                    {out_ids, out_scores, out_counts, out_arm, out_rank, feedback_rc}, check_arm); });
+}
+
 }  // extern "C"

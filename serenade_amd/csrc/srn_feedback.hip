@@ -345,6 +345,8 @@ int fb_create(int device, size_t capacity, size_t row_cap, uint64_t ttl_secs, ui
     return SRN_OK;
 }
 
+void fb_shape(const srn_feedback* f, int* device, uint64_t* row_cap) { *device = f->device; *row_cap = f->row_cap; }
+
 // the checks both entry points make, in their order; *done: nothing to do (n == 0)
 static int check_observe(const srn_feedback* f, const VisitorBatch& r, const ObserveCall& c, bool* done) {
     *done = false;

@@ -402,6 +402,8 @@ int dsess_load(const char* path, int device, size_t capacity, size_t items_cap, 
 int dsess_file_info(const char* path, srn_device_sessions_file_info_t* out);
 int dsess_recommend_device(const srn_index* idx, srn_device_sessions* s, const VisitorBatch& r, const RecommendCall& c);
 int dsess_recommend_host(const srn_index* idx, srn_device_sessions* s, const VisitorBatch& r, const RecommendCall& c);
+// the traffic split's front (srn_arms.hip): the arms' checks against the store, then the capacity rule once for all n requests (now: already read from the clock)
+int dsess_admit(srn_device_sessions* s, const srn_index* const* idx, const RecommendCall* c, size_t n_arms, uint64_t n, uint64_t now);
 // trending items (srn_trending.hip): the items the store's live sessions hold most often
 int dsess_top_items(srn_device_sessions* s, uint64_t now_secs, uint64_t since_secs, uint32_t min_count, size_t cap, uint64_t* out_ids, uint32_t* out_counts, size_t* out_n);
 int dsess_device_of(const srn_device_sessions* s);
@@ -420,6 +422,7 @@ int fb_create(int device, size_t capacity, size_t row_cap, uint64_t ttl_secs, ui
 void fb_free(srn_feedback* f);
 int fb_observe_device(srn_feedback* f, const VisitorBatch& r, const ObserveCall& c);
 int fb_observe_host(srn_feedback* f, const VisitorBatch& r, const ObserveCall& c);
+void fb_shape(const srn_feedback* f, int* device, uint64_t* row_cap);   // what a caller that feeds several logs checks before it feeds any
 int fb_stats(srn_feedback* f, srn_feedback_stats_t* out);
 int fb_histogram(srn_feedback* f, uint64_t* hits_model, uint64_t* hits_filled, size_t cap);
 int fb_reset_counters(srn_feedback* f);
@@ -431,4 +434,17 @@ int fb_boot_disable(srn_feedback* f);
 int fb_boot_info(srn_feedback* f, uint32_t* replicates, uint64_t* seed);
 int fb_boot_read(srn_feedback* f, uint64_t* observed, uint64_t* hits_model, uint64_t* hits_filled, size_t replicates_cap, size_t rank_cap);
 void fb_boot_weights_host(uint64_t seed, uint32_t replicate, const uint64_t* key_hi, const uint64_t* key_lo, size_t n, uint8_t* out);
+// traffic split (srn_arms.hip): every argument check is its own, but an arm's predict parameters -- check_arm(arm, how_many) is the C ABI glue's
+struct SplitOut { uint64_t* ids; double* scores; uint32_t* counts; uint8_t* arm; uint32_t* rank; int* feedback_rc; };   // arm, rank and feedback_rc may be null
+int split_create(int device, const uint32_t* weights, size_t n_arms, uint64_t seed, size_t max_batch, size_t max_how_many, srn_traffic_split** out);
+int split_free(srn_traffic_split* sp);
+int split_info(const srn_traffic_split* sp, srn_traffic_split_info_t* out);
+int split_set_weights(srn_traffic_split* sp, const uint32_t* weights, size_t n_arms);
+int split_arms_host(uint64_t seed, const uint32_t* weights, size_t n_arms, const uint64_t* key_hi, const uint64_t* key_lo, size_t n, uint8_t* out);
+int split_timing(srn_traffic_split* sp, int enable);
+int split_last_ms(srn_traffic_split* sp, double* ms_front, double* ms_scatter);
+int split_recommend_device(srn_traffic_split* sp, const srn_arm_t* arms, size_t n_arms, srn_device_sessions* store, const VisitorBatch& r, size_t how_many,
+                           const SplitOut& o, void* stream, int (*check_arm)(const srn_arm_t&, size_t));
+int split_recommend_host(srn_traffic_split* sp, const srn_arm_t* arms, size_t n_arms, srn_device_sessions* store, const VisitorBatch& r, size_t how_many,
+                         const SplitOut& o, int (*check_arm)(const srn_arm_t&, size_t));
 }  // namespace srn

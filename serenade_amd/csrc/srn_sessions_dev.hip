@@ -609,6 +609,33 @@ static int check_recommend(const srn_device_sessions* s, const VisitorBatch& r, 
     return SRN_OK;
 }
 
+// a call's windows against the store (mu held), and SRN_FLAG_EXCLUDE_SEEN's room behind the longest window the store may hold
+static int check_windows(const srn_device_sessions* s, const srn_index* idx, size_t max_items) {
+    if (max_items > s->items_cap) return fail(SRN_ERANGE, "srn_recommend_batch: max_items_in_session above the store's items_cap");
+    if (s->device != idx->device) return fail(SRN_EINVAL, "srn_recommend_batch: the store and the index are on different devices");
+    const uint32_t H = s->history;
+    if (H > s->items_cap) return fail(SRN_ERANGE, "srn_recommend_batch: the store's history window is above its items_cap (lowered by a resize): set a smaller history or resize again");
+    if (H && max_items > H) return fail(SRN_ERANGE, "srn_recommend_batch: max_items_in_session above the store's history window");
+    return SRN_OK;
+}
+static int check_exclude_seen(size_t how_many, uint32_t hint) {
+    return how_many + hint > SRN_MAX_HOW_MANY ? fail(SRN_ERANGE, "srn_recommend_batch: how_many + the store's longest window above SRN_MAX_HOW_MANY (SRN_FLAG_EXCLUDE_SEEN)") : SRN_OK;
+}
+
+// The traffic split's front (srn_arms.hip): every arm's checks against the store as its own call would make them, then the capacity rule for all n requests at once --
+// the arms' calls, whose sizes sum to n, then pass theirs.  hint grows from arm to arm as the calls will leave it
+int dsess_admit(srn_device_sessions* s, const srn_index* const* idx, const RecommendCall* c, size_t n_arms, uint64_t n, uint64_t now) {
+    std::lock_guard<std::mutex> g(s->mu);
+    uint32_t hint = s->len_bound;
+    for (size_t a = 0; a < n_arms; ++a) {
+        if (c[a].max_items == 0) return fail(SRN_EINVAL, "srn_recommend_batch: max_items_in_session must be > 0");
+        int rc = check_windows(s, idx[a], c[a].max_items); if (rc) return rc;
+        hint = std::max<uint32_t>(hint, s->history ? s->history : (uint32_t)c[a].max_items);
+        if ((c[a].flags & SRN_FLAG_EXCLUDE_SEEN) && (rc = check_exclude_seen(c[a].how_many, hint))) return rc;
+    }
+    return room_for(s, n, now);
+}
+
 int dsess_recommend_device(const srn_index* idx, srn_device_sessions* s, const VisitorBatch& r, const RecommendCall& c) {
     int rc = check_recommend(s, r, c, false); if (rc) return rc;
     const size_t n = r.n, max_items = c.max_items, how_many = c.how_many;
@@ -619,16 +646,13 @@ int dsess_recommend_device(const srn_index* idx, srn_device_sessions* s, const V
         if (max_items > SRN_MAX_SESSION_LEN) return fail(SRN_ERANGE, "srn_recommend_batch: max_items_in_session above SRN_MAX_SESSION_LEN");
         return recommend_no_store(idx, r.item, r.consent, n, p, st, fill);
     }
-    if (max_items > s->items_cap) return fail(SRN_ERANGE, "srn_recommend_batch: max_items_in_session above the store's items_cap");
-    if (s->device != idx->device) return fail(SRN_EINVAL, "srn_recommend_batch: the store and the index are on different devices");
     const uint64_t now = r.now_secs ? r.now_secs : wall_secs();
     std::lock_guard<std::mutex> g(s->mu);
+    if ((rc = check_windows(s, idx, max_items))) return rc;
     const uint32_t H = s->history, limit = H ? H : (uint32_t)max_items;
-    if (H > s->items_cap) return fail(SRN_ERANGE, "srn_recommend_batch: the store's history window is above its items_cap (lowered by a resize): set a smaller history or resize again");
-    if (H && max_items > H) return fail(SRN_ERANGE, "srn_recommend_batch: max_items_in_session above the store's history window");
     const uint32_t hint = std::max<uint32_t>(s->len_bound, limit);          // the longest window the store may hold behind this call
     const uint32_t phint = H ? (uint32_t)max_items : hint;                  // ... and the longest session predict reads
-    if (excl_seen && how_many + hint > SRN_MAX_HOW_MANY) return fail(SRN_ERANGE, "srn_recommend_batch: how_many + the store's longest window above SRN_MAX_HOW_MANY (SRN_FLAG_EXCLUDE_SEEN)");
+    if (excl_seen && (rc = check_exclude_seen(how_many, hint))) return rc;
     if ((rc = room_for(s, n, now))) return rc;
     HIP_TRY(hipSetDevice(s->device));
     // scratch: the sorted front's (sort keys and indices, rocPRIM's temporary storage -- also the scans' -- and a timed batch's times), then the per-position and

@@ -1057,6 +1057,164 @@ def recommend_batch(index, store, keys, item_ids, consent=None, *, k, m, how_man
     return (ids, cnt, sc) if scores else (ids, cnt)
 
 
+# ---- traffic split: one batch under several arms, sticky per visitor (srn_traffic_split_*) ----
+_ARM_DOMAIN = 0x53524E5F41524D53
+
+
+def _arm_weights(weights):
+    """-> the weights as Python ints, checked as far as a uint32 array can hold them (the sums are the C ABI's to refuse)."""
+    w = [int(x) for x in weights]
+    if any(x < 0 or x >= 1 << 32 for x in w):
+        raise ValueError("an arm's weight must be in 0 .. 2^32 - 1")
+    return w
+
+
+def arm_thresholds(weights):
+    """T_a = floor(2^32 * (w_0 + .. + w_a) / W) for a = 0 .. A-1 as Python ints (the last one is 2^32).  ValueError for A outside 1 .. 16 or W outside 1 .. 2^32 - 1."""
+    w = _arm_weights(weights)
+    W = sum(w)
+    if not 1 <= len(w) <= capi.MAX_ARMS or not 0 < W < 1 << 32:
+        raise ValueError("a split has 1 .. %d arms whose weights sum to 1 .. 2^32 - 1" % capi.MAX_ARMS)
+    out, cum = [], 0
+    for x in w:
+        cum += x
+        out.append((cum << 32) // W)
+    return out
+
+
+def arm_draws(seed, keys):
+    """u(seed, key) = mix64(mix64(seed ^ 0x53524E5F41524D53) ^ (fold(key) * 0xD1B54A32D192ED03 + 1)) >> 32 for keys = (hi, lo) -> uint64[n], each below 2^32."""
+    with np.errstate(over="ignore"):
+        rkey = _mix64(np.array([(int(seed) ^ _ARM_DOMAIN) & _M64], np.uint64))
+        s = feedback_fold(keys).reshape(-1)
+        return _mix64(rkey ^ (s * np.uint64(0xD1B54A32D192ED03) + np.uint64(1))) >> np.uint64(32)
+
+
+def arms_model(seed, weights, keys):
+    """The split's rule in NumPy, exactly (srn_arms.h): arm(key) = #{a < A - 1 : T_a <= u(seed, key)} -> uint8[n].  From (seed, weights, key) alone."""
+    T = np.array(arm_thresholds(weights)[:-1], np.uint64)
+    return np.searchsorted(T, arm_draws(seed, keys), side="right").astype(np.uint8)
+
+
+class TrafficSplit:
+    """A traffic split on one GPU (srn_traffic_split_*): (seed, weights) assign every visitor key to one of len(weights) arms, and recommend_batch_split serves a batch
+    under the arms' parameters in one call.  Create it before serving: it allocates every buffer its calls use, about max_batch * (46 + 16 * max_how_many) bytes.
+    After a call: last_arms (the requests' arms), last_ranks (their feedback ranks; capi.FEEDBACK_NONE where the arm has no log) and last_errors (per arm None, or
+    the SerenadeError of a log that refused the arm's rows)."""
+
+    def __init__(self, index_or_device, weights, seed=0, max_batch=1 << 20, max_how_many=21):
+        device = _device_of(index_or_device)
+        self.weights = _arm_weights(weights)
+        h = C.c_void_p()
+        capi.check(capi.lib().srn_traffic_split_create(int(device), capi.ptr(np.array(self.weights, np.uint32)), len(self.weights), int(seed) & _M64, int(max_batch),
+                                                       int(max_how_many), C.byref(h)))
+        self._h, self.device, self.seed, self.n_arms = h, int(device), int(seed) & _M64, len(self.weights)
+        self.last_arms = self.last_ranks = None
+        self.last_errors = [None] * self.n_arms
+
+    def info(self):
+        """srn_traffic_split_info_t as a dict; thresholds and served hold one entry per arm."""
+        st = capi.TrafficSplitInfo()
+        capi.check(capi.lib().srn_traffic_split_info(self._h, C.byref(st)))
+        out = {n: getattr(st, n) for n, _ in capi.TrafficSplitInfo._fields_ if n not in ("thresholds", "served")}
+        out["thresholds"], out["served"] = list(st.thresholds)[:st.n_arms], list(st.served)[:st.n_arms]
+        return out
+
+    def set_weights(self, weights):
+        """The ramp: other weights for the same arms from the next call on.  Only the keys whose u lies between an old and a new threshold change their arm."""
+        w = _arm_weights(weights)
+        capi.check(capi.lib().srn_traffic_split_set_weights(self._h, capi.ptr(np.array(w, np.uint32)), len(w)))
+        self.weights = w
+
+    def arm_of(self, keys):
+        """The rule on the host (srn_traffic_split_arms): the arms of keys = (hi, lo) under the split's seed and current weights -> uint8[n]."""
+        hi, lo = (capi.as_u64(_as_numpy(a.cpu() if _on_gpu(a) else a)) for a in keys)
+        if len(hi) != len(lo):
+            raise ValueError("keys differ in length")
+        out = np.zeros(len(hi), np.uint8)
+        capi.check(capi.lib().srn_traffic_split_arms(self.seed, capi.ptr(np.array(self.weights, np.uint32)), self.n_arms, capi.ptr(hi), capi.ptr(lo), len(hi), capi.ptr(out)))
+        return out
+
+    def timing(self, enable=True):
+        capi.check(capi.lib().srn_traffic_split_timing(self._h, 1 if enable else 0))
+
+    def last_ms(self):
+        """(assign + offsets + gather, scatter) of the last call in milliseconds, from HIP events (timing(True) first).  Blocks."""
+        a, b = C.c_double(), C.c_double()
+        capi.check(capi.lib().srn_traffic_split_last_ms(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def close(self):
+        if getattr(self, "_h", None) and capi is not None and getattr(capi, "lib", None) is not None:
+            capi.lib().srn_traffic_split_free(self._h)
+            self._h = None
+
+    __del__ = close
+
+
+def _arm_array(arms):
+    """The arms' dicts -- index, k, m, max_items_in_session (2), enable_business_logic, exclude_seen, fill, feedback -- as srn_arm_t[A]."""
+    known = {"index", "k", "m", "max_items_in_session", "enable_business_logic", "exclude_seen", "fill", "feedback"}
+    out = (capi.Arm * max(len(arms), 1))()
+    for a, arm in enumerate(arms):
+        if set(arm) - known:
+            raise TypeError("an arm has no parameter %s" % ", ".join(sorted(set(arm) - known)))
+        fb = arm.get("feedback")
+        flags = (capi.FLAG_BUSINESS_LOGIC if arm.get("enable_business_logic") else 0) | (capi.FLAG_EXCLUDE_SEEN if arm.get("exclude_seen") else 0) | \
+                (capi.FLAG_FILL if arm.get("fill") else 0)
+        out[a] = capi.Arm(arm["index"]._h, None if fb is None else fb._h, int(arm.get("max_items_in_session", 2)), int(arm["k"]), int(arm["m"]), flags)
+    return out
+
+
+def recommend_batch_split(split, arms, store, keys, item_ids, consent=None, *, how_many, now=0, times=None, scores=False):
+    """recommend_batch under a traffic split: request i is served with arms[arm(keys[i])] -- a dict of index, k, m and optionally max_items_in_session (2),
+    enable_business_logic, exclude_seen, fill and feedback (a ClickFeedback of the arm's own) -- all arms against the one store.  The result is what one
+    recommend_batch call per non-empty arm gives, arm 0 first, each over its arm's requests in request order with the call's one `now`: a visitor is in one arm, so
+    the visitor's clicks stay in order.  -> (ids[n, how_many], counts[n]) and scores with scores=True, in request order; arrays and tensors as recommend_batch
+    takes and gives them (tensors on the split's GPU are read in place on the current stream; the call waits for that stream once, to learn the arms' sizes).
+    Left in the split: last_arms, last_ranks (the logs' ranks, capi.FEEDBACK_NONE for an arm without a log) and last_errors -- per arm None, or the SerenadeError
+    of a log that refused its arm's rows under its capacity rule, which is a RuntimeWarning and does not fail the call.  The logs' own last_ranks are not touched.
+    now / times: as recommend_batch (times given and now 0: int(times.min()), one synchronisation for tensors)."""
+    n = len(item_ids)
+    if times is not None and not int(now) and n:
+        now = int(times.min())
+    if isinstance(keys, list) and (not keys or isinstance(keys[0], (str, bytes))):
+        if len(keys) != n:
+            raise ValueError("keys, item_ids and consent differ in length")
+        keys = session_keys(keys)
+    batch = _visitor_batch(keys, item_ids, consent, times, lambda: split.device, "the split")
+    hi, lo, it, con, tm, on_gpu, p, tail = batch
+    if on_gpu:
+        import torch
+        dev = torch.device("cuda", split.device)
+        ids = torch.zeros((n, how_many), dtype=torch.int64, device=dev)
+        sc = torch.zeros((n, how_many), dtype=torch.float64, device=dev)
+        cnt = torch.zeros(n, dtype=torch.int32, device=dev)
+        arm, rank = torch.zeros(n, dtype=torch.uint8, device=dev), torch.zeros(n, dtype=torch.int32, device=dev)
+    else:
+        ids, sc, cnt = np.zeros((n, how_many), np.uint64), np.zeros((n, how_many), np.float64), np.zeros(n, np.uint32)
+        arm, rank = np.zeros(n, np.uint8), np.zeros(n, np.uint32)
+    arm_array, log_rc = _arm_array(arms), (C.c_int * max(len(arms), 1))()
+    entry = getattr(capi.lib(), "srn_recommend_batch_split" + ("_device" if on_gpu else ""))
+    capi.check(entry(split._h, arm_array, len(arms), store._h if store is not None else None, p(hi), p(lo), p(it), p(con), p(tm), n, int(now), int(how_many),
+                     p(ids), p(sc), p(cnt), p(arm), p(rank), log_rc, *tail))
+    split.last_arms, split.last_ranks = arm, rank
+    split.last_errors = [None] * len(arms)
+    for a in range(len(arms)):
+        if log_rc[a]:
+            split.last_errors[a] = capi.SerenadeError(log_rc[a], "arm %d's click feedback log did not take the call's rows (its capacity is reached)" % a)
+            warnings.warn("recommend_batch_split: %s" % split.last_errors[a], RuntimeWarning, stacklevel=2)
+    return (ids, cnt, sc) if scores else (ids, cnt)
+
+
+def split_compare(stats, metric="mrr", baseline=0):
+    """feedback_compare of every arm's log against the baseline arm's: stats = [fb.stats() per arm] -> a list with feedback_compare(stats[a], stats[baseline], metric)
+    at a and None at the baseline.  The arms' visitors are disjoint, so the intervals are the unpaired ones."""
+    if not 0 <= baseline < len(stats):
+        raise ValueError("baseline must name one of the arms")
+    return [None if a == baseline else feedback_compare(s, stats[baseline], metric) for a, s in enumerate(stats)]
+
+
 # ---- replay: a recorded click log through the timed batch ----
 def replay_plan(times, batch=1 << 20, every=None):
     """How replay() cuts a time-sorted log -> [(start, stop, boundary)]: the calls in order, requests start..stop-1 each, and `boundary` the multiple t of `every`
@@ -1081,7 +1239,7 @@ def replay_plan(times, batch=1 << 20, every=None):
 
 
 def replay(index, store, keys, item_ids, times, consent=None, *, k, m, how_many, max_items_in_session=2, batch=1 << 20, every=None, on_boundary=None, feedback=None,
-           exclude_seen=False, fill=False, enable_business_logic=False, collect=False):
+           exclude_seen=False, fill=False, enable_business_logic=False, collect=False, split=None, arms=None):
     """Serves a recorded click log (keys[i], item_ids[i], times[i], consent[i]), sorted by time, through recommend_batch(..., times=...): every request sees the store,
     the harvest and the feedback log as it would have at its own second, at the speed of the batch path.  Arrays or tensors as recommend_batch takes them (times on the
     GPU are copied to the host once, to plan the cuts and read the sweep clocks).  The log is cut into calls by replay_plan(times, batch, every): at most `batch` requests each and, with
@@ -1089,7 +1247,12 @@ def replay(index, store, keys, item_ids, times, consent=None, *, k, m, how_many,
     store.sweep(t), or to refresh the ranking with index.set_fallback_trending(store, n, now=t).  Each call's sweep clock is its first request's time.  ValueError
     before anything is served if times decreases anywhere.  No device code of its own.
     -> {"requests", "calls", "boundaries"}, plus feedback.stats() under "feedback" with a feedback log, plus with collect=True the calls' concatenated "ids",
-    "counts" and (with a feedback log) "ranks"."""
+    "counts" and (with a feedback log) "ranks".
+    split and arms (a TrafficSplit and its arms' dicts, both or neither): the calls go through recommend_batch_split(split, arms, store, ...) instead -- index, k, m,
+    max_items_in_session, the flags and feedback are then the arms' and this call's are not read.  "feedback" is then a list per arm (the log's stats(), None for an
+    arm without one), "arms" the requests served per arm, and collect=True adds "arm" and always "ranks" (split.last_arms / last_ranks)."""
+    if (split is None) != (arms is None):
+        raise ValueError("replay: split and arms go together")
     n = len(item_ids)
     if len(times) != n:
         raise ValueError("times must have one entry per request")
@@ -1102,6 +1265,9 @@ def replay(index, store, keys, item_ids, times, consent=None, *, k, m, how_many,
     hi, lo = keys
     out = {"requests": n, "calls": 0, "boundaries": 0}
     parts = {"ids": [], "counts": [], "ranks": []}
+    if split is not None:
+        parts["arm"] = []
+        out["arms"] = [0] * len(arms)
     for start, stop, boundary in plan:
         if boundary is not None:
             out["boundaries"] += 1
@@ -1110,6 +1276,16 @@ def replay(index, store, keys, item_ids, times, consent=None, *, k, m, how_many,
         if stop == start:
             continue
         sl = slice(start, stop)
+        if split is not None:
+            ids, counts = recommend_batch_split(split, arms, store, (hi[sl], lo[sl]), item_ids[sl], None if consent is None else consent[sl], how_many=how_many,
+                                                now=int(host_times[start]), times=times[sl])
+            out["calls"] += 1
+            served = np.bincount(_as_numpy(split.last_arms.cpu() if _on_gpu(split.last_arms) else split.last_arms), minlength=len(arms))
+            out["arms"] = [int(x + y) for x, y in zip(out["arms"], served)]
+            if collect:
+                for name, got in (("ids", ids), ("counts", counts), ("ranks", split.last_ranks), ("arm", split.last_arms)):
+                    parts[name].append(got)
+            continue
         ids, counts = recommend_batch(index, store, (hi[sl], lo[sl]), item_ids[sl], None if consent is None else consent[sl], k=k, m=m, how_many=how_many,
                                       max_items_in_session=max_items_in_session, enable_business_logic=enable_business_logic, now=int(host_times[start]),
                                       exclude_seen=exclude_seen, fill=fill, feedback=feedback, times=times[sl])
@@ -1119,15 +1295,17 @@ def replay(index, store, keys, item_ids, times, consent=None, *, k, m, how_many,
             parts["counts"].append(counts)
             if feedback is not None:
                 parts["ranks"].append(feedback.last_ranks)
-    if feedback is not None:
+    if split is not None:
+        out["feedback"] = [None if arm.get("feedback") is None else arm["feedback"].stats() for arm in arms]
+    elif feedback is not None:
         out["feedback"] = feedback.stats()
     if collect:
         for name, got in parts.items():
-            if name == "ranks" and feedback is None:
+            if name == "ranks" and feedback is None and split is None:
                 continue
             if got and _is_torch(got[0]):
                 import torch
                 out[name] = torch.cat(got)
             else:
-                out[name] = np.concatenate(got) if got else np.zeros((0, how_many) if name == "ids" else 0, np.uint64 if name == "ids" else np.uint32)
+                out[name] = np.concatenate(got) if got else np.zeros((0, how_many) if name == "ids" else 0, {"ids": np.uint64, "arm": np.uint8}.get(name, np.uint32))
     return out
